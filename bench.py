@@ -7,12 +7,18 @@ voxel grid), appended in frame order -> [N>1: index-slice partition + one RCCL a
 per-frame voxel clouds] -> combined 2.5-D merge (pose.cpp:530) [N>1: all-gather of the merged slices].  Workload = BASELINE.json configs[1]: synthetic 1280x720 dense
 (jump_pixels 1), 200 frames per GPU, voxel_size 0.05.
 
-After the timed region the default run also reports, outside `value`: the PCIe-inclusive rate (host inputs), the rate
-with the reference's statistical outlier removal on (`sor_on_frames_per_sec`, checked against the oracle), the bit-for-bit
-verification of the whole step against the oracle, the distance of the merged cloud to the reference's own std::sort
-summation order (`verification.vs_reference_sort_order*`), and the oracle timed as `cpu_baseline`.
+A plain run sets up, warms up, times exactly --steps steps and prints one JSON line (`value` in frames/s, `ms_per_step`);
+--dump-outputs DIR also writes the merged cloud of the last timed step as .npy files (inputs are a pure function of
+the arguments, so two builds can be compared output for output).
 
-    python bench.py                       # N=1, defaults finish in a few minutes
+With --full, after the timed region the run also reports, outside `value`: the dominant kernel's roofline and the
+per-kernel times of one profiled step, the PCIe-inclusive rate (host inputs), the rate with the reference's statistical
+outlier removal on (`sor_on_frames_per_sec`, checked against the oracle), the bit-for-bit verification of the whole step
+against the oracle, the distance of the merged cloud to the reference's own std::sort summation order
+(`verification.vs_reference_sort_order*`), and the oracle timed as `cpu_baseline`.
+
+    python bench.py --gpus 1 --steps K --warmup W    # headline only
+    python bench.py --full                           # N=1, everything; defaults finish in a few minutes
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -32,6 +38,30 @@ if ROOT not in sys.path:
 PMC_TRAFFIC_FILE = "r04_pmc_traffic.json"
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec; what a plain device copy reaches on the box is measured below
                        # (roofline.measured_copy_GBps: 4.7-5.6 TB/s read+write over the boxes seen so far)
+DUMP_MAX_POINTS = 2_000_000  # --dump-outputs: 28 B per point at most (xyz, rgba, index) -> 56 MB
+
+
+def dump_outputs(out_dir, merged):
+    """The merged cloud a caller of the timed path receives ([M,4] int32 tensor = POINT records) -> out_dir/*.npy in
+    float32 / float64, exact: xyz as stored, the packed colour word as a float64.  Above DUMP_MAX_POINTS a fixed, seeded
+    sample of the points (ascending, their indices in merged_index.npy)."""
+    from online_3d_reconstruction_amd.api import points_from_torch
+    pts = points_from_torch(merged)
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    m = len(pts)
+    if m > DUMP_MAX_POINTS:
+        idx = np.sort(np.random.default_rng(20240601).choice(m, DUMP_MAX_POINTS, replace=False))
+        pts = pts[idx]
+        arrays["merged_index"] = idx.astype(np.float64)
+    elif os.path.exists(os.path.join(out_dir, "merged_index.npy")):
+        os.remove(os.path.join(out_dir, "merged_index.npy"))  # left by an earlier, sampled dump into the same folder
+    arrays["merged_xyz"] = np.stack([pts["x"], pts["y"], pts["z"]], axis=1).astype(np.float32)
+    arrays["merged_rgba"] = pts["rgba"].astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(n + ".npy" for n in arrays), "merged_points": m,
+            "sampled_points": int(len(pts)) if "merged_index" in arrays else None}
 
 
 def _gen(args):
@@ -165,7 +195,15 @@ def main():
     ap.add_argument("--cpu-frames", type=int, default=200)
     ap.add_argument("--cpu-threads", type=int, default=7)
     ap.add_argument("--gen-workers", type=int, default=min(16, os.cpu_count() or 1))
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: the per-kernel profiled "
+                    "step and roofline, the PCIe-inclusive and outlier-removal legs, the verification against the oracle, "
+                    "the reference-order comparison and the CPU baseline (the --no-* options above trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the merged cloud of the last timed step as DIR/<name>.npy "
+                    "(merged_xyz float32 [M,3], merged_rgba float64 [M]; a fixed, seeded sample of at most "
+                    f"{DUMP_MAX_POINTS} points, with merged_index, when the cloud is larger)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -211,7 +249,7 @@ def main():
     # N > 1: rank 0 checks the merged cloud against the oracle's run over the frames of ALL ranks; they are generated
     # here, before anything touches the GPU (the generator forks a process pool)
     all_disp = all_bgr = None
-    verify_all = (rank == 0 and world > 1 and not args.no_cpu_baseline and args.blur_kernel <= 1 and
+    verify_all = (args.full and rank == 0 and world > 1 and not args.no_cpu_baseline and args.blur_kernel <= 1 and
                   F * world <= args.verify_max_frames and host_can_verify(F * world))
     if verify_all:
         all_disp, all_bgr = generate_frames(0, F * world, args.rows, args.cols, args.invalid_frac, args.gen_workers)
@@ -294,27 +332,29 @@ def main():
     for _ in range(args.warmup):
         step()
 
-    # one untimed, fully bracketed step: which kernel dominates?
-    barrier()
-    ctx.profileReset()
-    ctx.profileEnable(-1, True)
-    step()
-    per_kernel = {L.KERNEL_NAMES[k]: ctx.profileRead(k) for k in range(len(L.KERNEL_NAMES))}
-    ctx.profileEnable(-1, False)
-    dom = max((k for k in range(len(L.KERNEL_NAMES)) if k != L.K_OTHER), key=lambda k: per_kernel[L.KERNEL_NAMES[k]][0])
+    if args.full:
+        # one untimed, fully bracketed step: which kernel dominates?
+        barrier()
+        ctx.profileReset()
+        ctx.profileEnable(-1, True)
+        step()
+        per_kernel = {L.KERNEL_NAMES[k]: ctx.profileRead(k) for k in range(len(L.KERNEL_NAMES))}
+        ctx.profileEnable(-1, False)
+        dom = max((k for k in range(len(L.KERNEL_NAMES)) if k != L.K_OTHER), key=lambda k: per_kernel[L.KERNEL_NAMES[k]][0])
+        ctx.profileReset()
+        ctx.profileEnable(dom, True)
 
-    # ---- timed region: exactly K steps, only the dominant kernel bracketed by HIP events -----------
-    ctx.profileReset()
-    ctx.profileEnable(dom, True)
+    # ---- timed region: exactly K steps; with --full, only the dominant kernel bracketed by HIP events ----------
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     barrier()
     dt = time.perf_counter() - t0
-    dom_ms, dom_launches = ctx.profileRead(dom)
-    stats = ctx.profileStatsAll()
-    ctx.profileEnable(dom, False)
+    if args.full:
+        dom_ms, dom_launches = ctx.profileRead(dom)
+        stats = ctx.profileStatsAll()
+        ctx.profileEnable(dom, False)
 
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=comm_dev or dev)
@@ -324,65 +364,7 @@ def main():
     frames_total = F * world * args.steps
     fps = frames_total / dt
     m1_total, m2 = state["m1_total"], state["m2"]
-
-    # ---- algorithmic bytes per step (DESIGN.md "Kernels and rooflines") --------------------------------
-    rec_passes, vox_in, vox_out, _unused, sort_recs = (v / args.steps for v in stats[:5])  # device counters, per step
     nv = n_valid_total  # valid points of this rank's frames (per step)
-    merge_n = m1_total // world  # points entering the combined merge on this rank (its index slice)
-    m1 = m1_total // world       # per-frame voxels of this rank's frames
-    merge_in = vox_in - nv       # points that entered whole-cloud grids (the merge), not per-frame ones
-    bytes_per_step = {
-        "reproject_count": 1 * n_cand * F,                     # 1 B disparity per candidate
-        "reproject_emit": 4 * n_cand * F + 16 * nv,            # 1 B disparity + 3 B colour in, 16 B point out
-        "voxel_keys": 0.25 * merge_in,                         # batch path: indices come from the emit pass; the merge reads its run-head flags
-        "radix_hist": 4 * rec_passes,                          # 4 B index per record per pass
-        "radix_scatter": 16 * rec_passes - 4 * sort_recs,      # (index,id) in and out; pass 0 has no id to read
-        "run_segments": 4.5 * sort_recs + 4 * vox_out,         # index read once, head flags out and in, run starts written
-        "centroid": 20 * nv + 16 * m1,                         # id + gathered point in, centroid out
-        "centroid_runs": 16 * merge_n + 16 * m2,               # merge: points in (group runs are contiguous), cells out
-    }
-    dom_name = L.KERNEL_NAMES[dom]
-    achieved = bytes_per_step[dom_name] * args.steps / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-    roofline = {"bound": "hbm", "kernel": dom_name, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
-                "traffic": None, "traffic_from_profile": None, "traffic_measured_in_this_run": False,
-                "avg_launch_us": round(dom_ms * 1e3 / max(dom_launches, 1), 2), "launches": int(dom_launches),
-                "algorithmic_bytes_per_launch": int(bytes_per_step[dom_name] * args.steps / max(dom_launches, 1))}
-    # what a plain device-to-device copy reaches on this box (read + write bytes): context for `peak`
-    try:
-        src_t = torch.empty(1 << 28, dtype=torch.int32, device=dev)  # 1 GiB
-        dst_t = torch.empty_like(src_t)
-        for _ in range(2):
-            dst_t.copy_(src_t)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(5):
-            dst_t.copy_(src_t)
-        e1.record()
-        torch.cuda.synchronize()
-        roofline["measured_copy_GBps"] = round(5 * 2 * src_t.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9, 1)
-        del src_t, dst_t
-    except Exception:
-        roofline["measured_copy_GBps"] = None
-    # HBM bytes per launch of the dominant kernel from the PMC passes kept under profiles/ (FETCH_SIZE x2 + WRITE_SIZE,
-    # MI355X_MICROARCH.md "HBM"); only reported when that file was measured on the same kernel sources as this run
-    # (a stored, builder-side measurement: `traffic_from_profile` says so; this run itself collects no PMC counters)
-    traffic_file = os.path.join(ROOT, "profiles", PMC_TRAFFIC_FILE)
-    roofline["traffic_source"] = None
-    if os.path.exists(traffic_file):
-        try:
-            tj = json.load(open(traffic_file))
-            if tj.get("kernel") == dom_name and tj.get("kernel_sources_sha1") == kernel_sources_sha1():
-                roofline["traffic"] = roofline["traffic_from_profile"] = tj.get("hbm_bytes_per_launch")
-                roofline["traffic_source"] = ("profiles/" + PMC_TRAFFIC_FILE + " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
-                                              "bench command on the same device sources, collected by the builder: not measured in this run)")
-        except Exception:
-            pass
-    # SURVEY 8d end-to-end figure: B_frame = 4N + 16Nv + 16Nv + 16M1 per frame, B_final = 16 SUM(M1) + 16 M2
-    b_frame = (4 * n_cand * F + 32 * nv + 16 * (m1_total // world)) / F
-    b_final = 16 * merge_n + 16 * m2
-    e2e_gbs = (b_frame * F + b_final) * args.steps * world / dt / 1e9
 
     result = {
         "metric": "frames_per_sec_pcie_inclusive" if args.host_inputs else "frames_per_sec", "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
@@ -396,14 +378,79 @@ def main():
         "mpoints_per_sec_into_global_cloud": round(m1_total * args.steps / dt / 1e6, 2),
         "points": {"candidates_per_frame": n_cand, "valid_per_step_per_gpu": nv, "per_frame_voxels_total": m1_total,
                    "merged_cells": m2},
-        "roofline": roofline,
-        "end_to_end": {"algorithmic_GBps": round(e2e_gbs, 2), "frac_of_hbm_peak": round(e2e_gbs / HBM_PEAK_GBS / world, 5),
-                       "bytes_per_frame": int(b_frame), "bytes_final_merge": int(b_final)},
-        "kernel_ms_per_step": {k: round(v[0], 3) for k, v in per_kernel.items()},
-        "sort": {"records_per_step": int(sort_recs), "record_passes_per_step": int(rec_passes)},
     }
+    # the merged cloud of the last timed step, before anything below runs the pipeline again
+    if args.dump_outputs and rank == 0:
+        result["outputs"] = dump_outputs(args.dump_outputs, state["out"])
+
+    if args.full:
+        # ---- algorithmic bytes per step (DESIGN.md "Kernels and rooflines") --------------------------------
+        rec_passes, vox_in, vox_out, _unused, sort_recs = (v / args.steps for v in stats[:5])  # device counters, per step
+        merge_n = m1_total // world  # points entering the combined merge on this rank (its index slice)
+        m1 = m1_total // world       # per-frame voxels of this rank's frames
+        merge_in = vox_in - nv       # points that entered whole-cloud grids (the merge), not per-frame ones
+        bytes_per_step = {
+            "reproject_count": 1 * n_cand * F,                     # 1 B disparity per candidate
+            "reproject_emit": 4 * n_cand * F + 16 * nv,            # 1 B disparity + 3 B colour in, 16 B point out
+            "voxel_keys": 0.25 * merge_in,                         # batch path: indices come from the emit pass; the merge reads its run-head flags
+            "radix_hist": 4 * rec_passes,                          # 4 B index per record per pass
+            "radix_scatter": 16 * rec_passes - 4 * sort_recs,      # (index,id) in and out; pass 0 has no id to read
+            "run_segments": 4.5 * sort_recs + 4 * vox_out,         # index read once, head flags out and in, run starts written
+            "centroid": 20 * nv + 16 * m1,                         # id + gathered point in, centroid out
+            "centroid_runs": 16 * merge_n + 16 * m2,               # merge: points in (group runs are contiguous), cells out
+        }
+        dom_name = L.KERNEL_NAMES[dom]
+        achieved = bytes_per_step[dom_name] * args.steps / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+        roofline = {"bound": "hbm", "kernel": dom_name, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
+                    "traffic": None, "traffic_from_profile": None, "traffic_measured_in_this_run": False,
+                    "avg_launch_us": round(dom_ms * 1e3 / max(dom_launches, 1), 2), "launches": int(dom_launches),
+                    "algorithmic_bytes_per_launch": int(bytes_per_step[dom_name] * args.steps / max(dom_launches, 1))}
+        # what a plain device-to-device copy reaches on this box (read + write bytes): context for `peak`
+        try:
+            src_t = torch.empty(1 << 28, dtype=torch.int32, device=dev)  # 1 GiB
+            dst_t = torch.empty_like(src_t)
+            for _ in range(2):
+                dst_t.copy_(src_t)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(5):
+                dst_t.copy_(src_t)
+            e1.record()
+            torch.cuda.synchronize()
+            roofline["measured_copy_GBps"] = round(5 * 2 * src_t.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9, 1)
+            del src_t, dst_t
+        except Exception:
+            roofline["measured_copy_GBps"] = None
+        # HBM bytes per launch of the dominant kernel from the PMC passes kept under profiles/ (FETCH_SIZE x2 + WRITE_SIZE,
+        # MI355X_MICROARCH.md "HBM"); only reported when that file was measured on the same kernel sources as this run
+        # (a stored, builder-side measurement: `traffic_from_profile` says so; this run itself collects no PMC counters)
+        traffic_file = os.path.join(ROOT, "profiles", PMC_TRAFFIC_FILE)
+        roofline["traffic_source"] = None
+        if os.path.exists(traffic_file):
+            try:
+                tj = json.load(open(traffic_file))
+                if tj.get("kernel") == dom_name and tj.get("kernel_sources_sha1") == kernel_sources_sha1():
+                    roofline["traffic"] = roofline["traffic_from_profile"] = tj.get("hbm_bytes_per_launch")
+                    roofline["traffic_source"] = ("profiles/" + PMC_TRAFFIC_FILE + " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
+                                                  "bench command on the same device sources, collected by the builder: not measured in this run)")
+            except Exception:
+                pass
+        # SURVEY 8d end-to-end figure: B_frame = 4N + 16Nv + 16Nv + 16M1 per frame, B_final = 16 SUM(M1) + 16 M2
+        b_frame = (4 * n_cand * F + 32 * nv + 16 * (m1_total // world)) / F
+        b_final = 16 * merge_n + 16 * m2
+        e2e_gbs = (b_frame * F + b_final) * args.steps * world / dt / 1e9
+        result.update({
+            "roofline": roofline,
+            "end_to_end": {"algorithmic_GBps": round(e2e_gbs, 2), "frac_of_hbm_peak": round(e2e_gbs / HBM_PEAK_GBS / world, 5),
+                           "bytes_per_frame": int(b_frame), "bytes_final_merge": int(b_final)},
+            "kernel_ms_per_step": {k: round(v[0], 3) for k, v in per_kernel.items()},
+            "sort": {"records_per_step": int(sort_recs), "record_passes_per_step": int(rec_passes)},
+        })
     if world > 1:  # collectives per step, host waits before the final gather, and what the exchange moved (dist.merge_partitioned)
         result["exchange"] = state.get("exchange")
+    if world > 1 and args.full:
         ex = state.get("exchange") or {}
         mine3 = torch.tensor([ex.get("points_local", 0), ex.get("points_sent_off_rank", 0), ex.get("points_received_off_rank", 0)],
                              dtype=torch.int64, device=comm_dev or dev)
@@ -423,7 +470,7 @@ def main():
             "modelled_xgmi_ms_links_to_all_peers": round(busiest / (153e9 * max(min(world - 1, 7), 1)) * 1e3, 3)}
 
     # ---- PCIe-inclusive rate: one extra, untimed-in-`value` step with HOST (pageable numpy) inputs -----------------
-    if world == 1 and not args.host_inputs and not args.no_pcie_step:
+    if args.full and world == 1 and not args.host_inputs and not args.no_pcie_step:
         for k in range(2):  # (the first call allocates the context's staging buffers; the second one is timed)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -435,7 +482,7 @@ def main():
 
     # ---- the reference's literal per-frame path: statistical outlier removal ON (pose_functions.cpp:1673-1686 runs it in
     # every per-frame call when jump_pixels > 0).  Reported next to the headline, which is measured with it off.
-    sor_leg = (world == 1 and not args.sor and not args.no_sor_leg and not args.host_inputs and args.jump_pixels > 0 and
+    sor_leg = (args.full and world == 1 and not args.sor and not args.no_sor_leg and not args.host_inputs and args.jump_pixels > 0 and
                args.blur_kernel <= 1)
     if sor_leg:
         prm_on = o3dr.Params(jump_pixels=args.jump_pixels, voxel_size=args.voxel_size, min_points_per_voxel=args.min_points,
@@ -483,7 +530,7 @@ def main():
 
     # ---- verification: the whole step of the headline config against the oracle, bit for bit -----------------------
     result["verified"] = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.blur_kernel <= 1:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.blur_kernel <= 1:
         from oracle import orc
         ctx.cloudBigReset()
         ctx.accumulateFrames(disp, bgr, poses)
@@ -527,7 +574,7 @@ def main():
 
     # ---- N > 1: every rank's shard of cloud_big (hashed) and the merged cloud every rank holds after the exchange against
     # the oracle's run over the frames of ALL ranks
-    if world > 1 and not args.no_cpu_baseline and args.blur_kernel <= 1:
+    if args.full and world > 1 and not args.no_cpu_baseline and args.blur_kernel <= 1:
         import hashlib
         ctx.cloudBigReset()
         ctx.accumulateFrames(disp, bgr, poses)
@@ -540,9 +587,9 @@ def main():
         dist.all_gather_into_tensor(allh, torch.from_numpy(mine).to(cd))
         allh = allh.cpu().numpy().reshape(world, 28)
         del shard
-    if rank == 0 and world > 1 and not args.no_cpu_baseline and args.blur_kernel <= 1 and not verify_all:
+    if args.full and rank == 0 and world > 1 and not args.no_cpu_baseline and args.blur_kernel <= 1 and not verify_all:
         result["verification"] = {"skipped": f"{F * world} frames in all: above --verify-max-frames or the host's free memory"}
-    elif rank == 0 and world > 1 and not args.no_cpu_baseline and args.blur_kernel <= 1:
+    elif args.full and rank == 0 and world > 1 and not args.no_cpu_baseline and args.blur_kernel <= 1:
         from oracle import orc
         all_poses = synth.make_poses(0, F * world)
         t0 = time.perf_counter()
@@ -568,7 +615,7 @@ def main():
                                   "oracle_seconds": round(t_or, 2)}
         del rbig, all_disp, all_bgr
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.blur_kernel <= 1:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.blur_kernel <= 1:
         nf = min(args.cpu_frames, F)
         v7, t7 = cpu_baseline(disp_h, bgr_h, poses_h, Q, args.voxel_size, args.jump_pixels, args.cpu_threads, nf, args.sor)
         n1 = min(100, F)

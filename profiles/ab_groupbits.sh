@@ -3,7 +3,7 @@
 # overridable (`#ifndef O3DR_GROUP_BITS ...`), compile with -DO3DR_GROUP_BITS=4 / 6 into lib/libo3dr_g4.so / _g6.so, copy the
 # default build to _g5.so.  Round 4: all three within 1 % on all three shapes; the header was left as it is.
 lib=online_3d_reconstruction_amd/lib
-F="--steps 4 --warmup 1 --no-cpu-baseline --no-pcie-step --no-sor-leg"
+F="--full --steps 4 --warmup 1 --no-cpu-baseline --no-pcie-step --no-sor-leg"
 for round in 1 2; do
  for v in g5 g4 g6; do
   cp $lib/libo3dr_$v.so $lib/libo3dr.so

@@ -8,7 +8,7 @@ mkdir -p $out
 ( while sleep 45; do echo "[heartbeat] $(date +%T) $(free -g | awk '/Mem/{print "host used " $3 " GiB"}')"; done ) &
 hb=$!
 trap 'kill $hb 2>/dev/null' EXIT
-B="python3 bench.py --gpus 1 --steps 3 --warmup 1 --no-pcie-step --no-sor-leg --no-reference-order --cpu-frames 100"
+B="python3 bench.py --full --gpus 1 --steps 3 --warmup 1 --no-pcie-step --no-sor-leg --no-reference-order --cpu-frames 100"
 run() {
   name=$1; limit=$2; shift 2
   echo "== $name: $*"
