@@ -235,6 +235,27 @@ int o3dr_cloud_big_transform(o3dr_ctx* ctx, const float T[16]);
 /* cloud_small = downsamplePtCloud(cloud_big, true) (pose.cpp:530); cloud_big is left intact */
 int o3dr_finalize(o3dr_ctx* ctx, o3dr_point* out, int64_t out_capacity, int64_t* n_out,
                   uint32_t* status, int32_t mem);
+/* cloud_small = downsamplePtCloud(cloud_big, true), like o3dr_finalize and bit-identical to it, but the context keeps
+ * every merged cell's running sums: a call folds only the points appended since the previous call and then writes the
+ * cells (the reference's per-cycle preview, pose.cpp:437-448, 638-674).  out == NULL with out_capacity == 0: fold and
+ * report the result's size in *n_out without writing it.  Output and *status are o3dr_finalize's at that moment
+ * (*status includes the per-frame bits OR-ed since the last reset); O3DR_ERR_CAPACITY when out_capacity is below the
+ * result's size (not cloud_big's).  A failed call leaves the state empty: the next call folds from the first point.
+ * Nothing is allocated or launched before the first call.
+ * The state is dropped (the next call refolds cloud_big from its first point) by o3dr_cloud_big_reset, _transform,
+ * _partition, _partition_dev, _place_slices, _adopt, _set_size, o3dr_merge_partitioned, an o3dr_set_params that changes
+ * voxel_size, and an o3dr_cloud_big_assume_size below the points folded.  Appends (frame calls, o3dr_cloud_big_append)
+ * are ordinary tails.  min_points_per_voxel is applied when the cells are written.  Writes into cloud_big through the
+ * pointers of o3dr_cloud_big_view / o3dr_cloud_big_raw_view are NOT tracked: after such a write outside the calls above,
+ * the state describes points that are no longer there.
+ * dont_downsample, PCL's overflow guard for the cloud's box, a cell coordinate of magnitude >= 2^24, or a grid of 2^32
+ * cells or more: the call runs o3dr_finalize's own code (and drops the state). */
+int o3dr_finalize_incremental(o3dr_ctx* ctx, o3dr_point* out, int64_t out_capacity, int64_t* n_out,
+                              uint32_t* status, int32_t mem);
+/* what the last o3dr_finalize_incremental did: [0] points folded, [1] 1 = started from an empty state,
+ * [2] 1 = answered by o3dr_finalize's own code (see above), [3] cells held, [4] groups held,
+ * [5] device bytes held by the state, [6..7] 0 */
+int o3dr_finalize_incremental_stats(o3dr_ctx* ctx, int64_t out[8]);
 
 /* ---- multi-GPU merge (frames sharded over ranks) ------------------------------
  * The reference's final merge (pose.cpp:530) runs one voxel grid over ALL frames' per-frame voxels.

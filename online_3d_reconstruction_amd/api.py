@@ -476,6 +476,41 @@ class Context:
                                                   C.byref(st), mem))
         return (out[: m.value], st.value) if return_status else out[: m.value]
 
+    def finalizeIncremental(self, device=None, return_status=False):
+        """finalize()'s result, bit for bit, folding only the points appended to cloud_big since the previous call
+        (the reference's per-cycle preview, pose.cpp:437-448, 638-674); sized exactly by a size query first"""
+        m = C.c_int64(0)
+        st = C.c_uint32(0)
+        L.check(self._lib.o3dr_finalize_incremental(self._h, None, 0, C.byref(m), C.byref(st), 0))
+        q = self._inc_stats_raw()
+        n = m.value
+        if device is not None:
+            import torch
+            out = torch.empty((max(n, 1), 4), dtype=torch.int32, device=device)
+        else:
+            out = np.empty(max(n, 1), POINT)
+        po, mem, _k = _ptr(out)
+        L.check(self._lib.o3dr_finalize_incremental(self._h, po, max(n, 1), C.byref(m), C.byref(st), mem))
+        w = self._inc_stats_raw()
+        # the size query folded, the second call only wrote: the statistics of the pair
+        both = dict(w, points_folded=q["points_folded"] + w["points_folded"], from_empty=q["from_empty"] | w["from_empty"],
+                    fallback=q["fallback"] | w["fallback"])
+        self._inc_last = (w, both)
+        return (out[: m.value], st.value) if return_status else out[: m.value]
+
+    def _inc_stats_raw(self):
+        out = (C.c_int64 * 8)()
+        L.check(self._lib.o3dr_finalize_incremental_stats(self._h, out))
+        keys = ("points_folded", "from_empty", "fallback", "cells", "groups", "state_bytes")
+        return dict(zip(keys, (int(v) for v in out)))
+
+    def finalizeIncrementalStats(self):
+        """what the last finalizeIncremental did (include/o3dr.h; both of its calls), or the last o3dr_finalize_incremental
+        made through the C ABI directly"""
+        raw = self._inc_stats_raw()
+        last = getattr(self, "_inc_last", None)
+        return dict(last[1]) if last is not None and last[0] == raw else raw
+
     # -- measurement hooks --------------------------------------------------------------------------
     def profileEnable(self, kernel_id=-1, enable=True):
         L.check(self._lib.o3dr_profile_enable(self._h, int(kernel_id), int(bool(enable))))

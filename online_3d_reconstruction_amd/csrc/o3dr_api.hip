@@ -133,6 +133,25 @@ struct o3dr_ctx {
     int place_parts = 0;     // the (slice, tile) table in the workspace is what o3dr_cloud_big_place_slices moves by
     int test_hooks = 0;    // O3DR_TEST_HOOKS=1 at o3dr_ctx_create: the entry points of include/o3dr_testing.h act
     int host_batch = 32;  // frames per upload while the previous batch computes (O3DR_HOST_BATCH_FRAMES)
+    // bumped by every call that rewrites points of cloud_big already in place (or shrinks it) and by a change of the merge's
+    // leaf: the incremental merge's state then describes points that are gone
+    uint64_t cloud_gen = 0;
+    // o3dr_finalize_incremental: the occupied cells of the combined grid over cloud_big's first inc_folded points, with
+    // their running sums (kernels/incremental.inc).  Two sets of (groups, cell offsets, cells) that swap; nothing exists
+    // before the first call.
+    struct {
+        bool valid = false;
+        int64_t folded = 0;
+        uint64_t gen = 0;
+        float leaf[3] = {0.f, 0.f, 0.f};
+        float zo = 0.f;
+        uint32_t n_groups = 0, n_cells = 0;
+        int cur = 0;
+        DevBuf grp[2], off[2], cells[2], box;                         // state
+        DevBuf scratch, tg, tmatch, flag, src, keep, partial, words;  // per-call workspace
+        DevBuf fb;                                                    // fallback: o3dr_finalize's result
+        int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    } inc;
     Profiler prof;
 };
 
@@ -444,6 +463,14 @@ extern "C" int o3dr_ctx_destroy(o3dr_ctx* c)
     }
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
+    for (int i = 0; i < 2; ++i) {
+        dev_release(c->inc.grp[i]);
+        dev_release(c->inc.off[i]);
+        dev_release(c->inc.cells[i]);
+    }
+    for (DevBuf* b : {&c->inc.box, &c->inc.scratch, &c->inc.tg, &c->inc.tmatch, &c->inc.flag, &c->inc.src, &c->inc.keep,
+                      &c->inc.partial, &c->inc.words, &c->inc.fb})
+        dev_release(*b);
     delete c;
     return O3DR_OK;
 }
@@ -503,6 +530,7 @@ extern "C" int o3dr_set_params(o3dr_ctx* c, const o3dr_params* p)
     if (!p) return fail(O3DR_ERR_INVALID_ARG, "params is NULL");
     if (p->bounding_box < 0 || p->cutout_ratio <= 0 || p->jump_pixels < 0 || !(p->voxel_size > 0))
         return fail(O3DR_ERR_INVALID_ARG, "params out of range");
+    if (p->voxel_size != c->params.voxel_size) ++c->cloud_gen;  // the merge's leaf (an incremental merge refolds)
     c->params = *p;
     return O3DR_OK;
 }
@@ -1292,6 +1320,7 @@ static const uint8_t* heads_for_merge(o3dr_ctx* c, const float leaf[3], float zo
 extern "C" int o3dr_cloud_big_reset(o3dr_ctx* c)
 {
     CTX_ENTER(c);
+    ++c->cloud_gen;
     CHK(zero_counters(c, c->cc_big));
     CHK(cloud_box_clear(c));
     c->cloud_ub = 0;
@@ -1369,6 +1398,7 @@ extern "C" int o3dr_cloud_big_transform(o3dr_ctx* c, const float T[16])
     if (!T) return fail(O3DR_ERR_INVALID_ARG, "T is NULL");
     CloudCounters cc;
     CHK(read_counters(c, c->cc_big, &cc));
+    ++c->cloud_gen;
     launch_transform(&c->prof, c->stream, c->cloud_big, (int64_t)cc.count, T, c->cloud_big);
     HIPCHK(hipGetLastError());
     c->cloud_box_valid = false;
@@ -1602,6 +1632,266 @@ extern "C" int o3dr_finalize(o3dr_ctx* c, o3dr_point* out, int64_t out_capacity,
     return finalize_impl(c, nullptr, nullptr, out, out_capacity, n_out, status, mem);
 }
 
+// ---- incremental merge (kernels/incremental.inc): the combined merge of cloud_big kept as running per-cell sums ----------
+static void inc_drop(o3dr_ctx* c)
+{
+    c->inc.valid = false;
+    c->inc.folded = 0;
+    c->inc.n_groups = c->inc.n_cells = 0;
+}
+static int64_t inc_state_bytes(const o3dr_ctx* c)
+{
+    size_t b = c->inc.box.cap;
+    for (int i = 0; i < 2; ++i) b += c->inc.grp[i].cap + c->inc.off[i].cap + c->inc.cells[i].cap;
+    return (int64_t)b;
+}
+// PCL's geometry of the combined grid over the box [mn, mx] (voxel_geom_of, in the same fp32 steps): 0 = the running sums
+// give the merge's result; 1 = PCL's overflow guard fires; 2 = a cell coordinate reaches 2^24 in magnitude (floor(x * inv)
+// and its difference to min_b are no longer exact); 3 = the uint32 linear index can wrap (distinct cells could merge)
+static int inc_geometry_check(const float mn_in[3], const float mx_in[3], const float leaf[3], float zo)
+{
+    float inv[3], mn[3], mx[3];
+    for (int a = 0; a < 3; ++a) {
+        inv[a] = 1.0f / leaf[a];
+        mn[a] = mn_in[a];
+        mx[a] = mx_in[a];
+    }
+    mn[2] = mn[2] + zo;
+    mx[2] = mx[2] + zo;
+    double prod = 1.0;  // dx * dy * dz > INT32_MAX, d = int64((max - min) * inv) + 1
+    for (int a = 0; a < 3; ++a) {
+        const float e = (mx[a] - mn[a]) * inv[a];
+        if (!(e < 2147483648.f)) return 1;
+        prod *= (double)((int64_t)e + 1);
+    }
+    if (prod > (double)INT32_MAX) return 1;
+    double cells = 1.0;
+    for (int a = 0; a < 3; ++a) {
+        const float lo = floorf(mn[a] * inv[a]), hi = floorf(mx[a] * inv[a]);
+        if (!(lo > -16777216.f && hi < 16777216.f)) return 2;
+        cells *= (double)(hi - lo) + 1.0;
+    }
+    return cells >= 4294967296.0 ? 3 : 0;
+}
+// o3dr_finalize's own code into a buffer of the state, then to the caller
+static int inc_fallback(o3dr_ctx* c, int64_t n, o3dr_point* out, int64_t out_capacity, int64_t* n_out, uint32_t* status,
+                        int32_t mem, int64_t* st)
+{
+    inc_drop(c);
+    st[2] = 1;
+    CHK(dev_ensure(c, c->inc.fb, (size_t)n * sizeof(o3dr_point)));
+    int64_t m = 0;
+    uint32_t s = 0;
+    const int r = finalize_impl(c, nullptr, nullptr, (o3dr_point*)c->inc.fb.p, n, &m, &s, O3DR_MEM_DEVICE);
+    if (r == O3DR_OK && !(out == nullptr && out_capacity == 0)) {
+        if (m > out_capacity) {
+            dev_release(c->inc.fb);
+            return fail(O3DR_ERR_CAPACITY, "output buffer too small");
+        }
+        if (m > 0) {
+            HIPCHK(hipMemcpyAsync(out, c->inc.fb.p, (size_t)m * sizeof(o3dr_point),
+                                  mem == O3DR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+        }
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    dev_release(c->inc.fb);  // (a fallback result is as large as the cloud: not kept)
+    if (r != O3DR_OK) return r;
+    *n_out = m;
+    if (status) *status = s;
+    return O3DR_OK;
+}
+// device words of the state's per-call workspace: [0] new groups, [1] cells, [2] kept cells
+static int inc_read_word(o3dr_ctx* c, int w, uint32_t* v)
+{
+    HIPCHK(hipMemcpyAsync(c->n_host, (uint32_t*)c->inc.words.p + w, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->cc_host, c->cc_tmp, sizeof(CloudCounters), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->cc_host->status & O3DR_STATUS_INTERNAL)
+        return fail(O3DR_ERR_INTERNAL, "a device-side guard of the incremental merge tripped (record or point id outside its range)");
+    *v = c->n_host[0];
+    return O3DR_OK;
+}
+
+static int inc_run(o3dr_ctx* c, o3dr_point* out, int64_t out_capacity, int64_t* n_out, uint32_t* status, int32_t mem, int64_t* st)
+{
+    auto& S = c->inc;
+    float leaf[3], zo;
+    uint32_t mp;
+    downsample_leaf(c->params, 1, leaf, &mp, &zo);
+    const uint32_t need = mp > 1u ? mp : 1u;
+    const bool query = out == nullptr && out_capacity == 0;
+    // 1. the cloud's size and status bits (and its running box, when the frame calls keep it) in one round trip
+    const bool box_kept = c->cloud_box_valid;
+    if (box_kept) HIPCHK(hipMemcpyAsync(c->misc_host, c->cloud_box, 6 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    CloudCounters cc;
+    CHK(read_counters(c, c->cc_big, &cc));
+    const int64_t n = (int64_t)cc.count;
+    if (n >= (int64_t)0xffffffffLL) return fail(O3DR_ERR_INVALID_ARG, "cloud_big exceeds 2^32-1 points");
+    if (S.valid && (S.gen != c->cloud_gen || n < S.folded || leaf[0] != S.leaf[0] || leaf[1] != S.leaf[1] || leaf[2] != S.leaf[2] ||
+                    zo != S.zo))
+        inc_drop(c);
+    if (c->params.dont_downsample) return inc_fallback(c, n, out, out_capacity, n_out, status, mem, st);
+    st[1] = S.valid ? 0 : 1;
+    if (!S.valid) {  // start from an empty state
+        static const float empty[6] = {__builtin_inff(), __builtin_inff(), __builtin_inff(),
+                                       -__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+        CHK(dev_ensure(c, S.box, 6 * sizeof(float)));
+        HIPCHK(hipMemcpyAsync(S.box.p, empty, sizeof empty, hipMemcpyHostToDevice, c->stream));
+        inc_drop(c);
+        S.gen = c->cloud_gen;
+        for (int a = 0; a < 3; ++a) S.leaf[a] = leaf[a];
+        S.zo = zo;
+        S.valid = true;
+    }
+    if (n == 0) return O3DR_OK;  // (like o3dr_finalize: no points, no status)
+    CHK(zero_counters(c, c->cc_tmp));
+    CHK(dev_ensure(c, S.words, 64));
+    const int64_t tail = n - S.folded;
+    if (tail > 0) {
+        // 2. the combined box: the cloud's running box, or the state's extended by one pass over the tail
+        CHK(ws_ensure(c, 1, tail, false));
+        launch_set_counts(&c->prof, c->stream, c->ws.n_valid, (uint32_t)tail, 1);
+        const o3dr_point* tp = c->cloud_big + S.folded;
+        float hb[6];
+        if (box_kept) {
+            memcpy(hb, c->misc_host, sizeof hb);
+            HIPCHK(hipMemcpyAsync(S.box.p, c->cloud_box, 6 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(c->ws.mm, c->cloud_box, 6 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        } else {
+            const int used = launch_points_minmax(&c->prof, c->stream, tp, 0, c->ws.n_valid, 1, tail, c->ws.mm_stride, c->ws.mm);
+            launch_bbox(&c->prof, c->stream, c->ws.mm, used, (float*)c->misc_dev);
+            launch_inc_box_fold(c->stream, (float*)S.box.p, (const float*)c->misc_dev, c->ws.mm);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(c->misc_host, S.box.p, 6 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            memcpy(hb, c->misc_host, sizeof hb);
+        }
+        if (inc_geometry_check(hb, hb + 3, leaf, zo) != 0) return inc_fallback(c, n, out, out_capacity, n_out, status, mem, st);
+        // 3. the tail's group runs sorted by group (heads as recorded while cloud_big grew, else from its points)
+        launch_inc_runs(&c->prof, c->stream, c->ws, tp, tail, leaf, zo, heads_for_merge(c, leaf, zo), S.folded, c->test_corrupt);
+        c->test_corrupt = 0;
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(S.words.p, c->ws.n_vox, sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+        uint32_t nt = 0;
+        CHK(inc_read_word(c, 0, &nt));
+        if ((int64_t)nt > tail) return fail(O3DR_ERR_INTERNAL, "more groups than points in the tail");
+        // 4. fold the tail's groups into the state's sums, merge the group lists, move the cells
+        const int o = S.cur, q = 1 - o;
+        const size_t nt1 = (size_t)nt + 1, np = ((size_t)S.n_groups + nt1) / 4096 + 64;
+        CHK(dev_ensure(c, S.scratch, nt1 * kGroupCells * sizeof(IncCell)));
+        CHK(dev_ensure(c, S.tg, nt1 * sizeof(IncGroup)));
+        CHK(dev_ensure(c, S.tmatch, nt1 * sizeof(uint32_t)));
+        CHK(dev_ensure(c, S.flag, nt1 * sizeof(uint32_t)));
+        CHK(dev_ensure(c, S.partial, np * sizeof(uint32_t)));
+        IncFoldArgs a;
+        a.old_g = (const IncGroup*)S.grp[o].p;
+        a.old_off = (const uint32_t*)S.off[o].p;
+        a.old_cells = (const IncCell*)S.cells[o].p;
+        a.n_old = S.n_groups;
+        a.n_old_cells = S.n_cells;
+        a.scratch = (IncCell*)S.scratch.p;
+        a.tg = (IncGroup*)S.tg.p;
+        a.tmatch = (uint32_t*)S.tmatch.p;
+        a.nt = nt;
+        a.flag = (uint32_t*)S.flag.p;
+        a.n_new_only = (uint32_t*)S.words.p;
+        a.cc = c->cc_tmp;
+        launch_inc_fold(&c->prof, c->stream, c->ws, tp, zo, a, (uint32_t*)S.partial.p);
+        HIPCHK(hipGetLastError());
+        uint32_t new_only = 0;
+        CHK(inc_read_word(c, 0, &new_only));
+        if (new_only > nt) return fail(O3DR_ERR_INTERNAL, "more new groups than tail groups");
+        const uint64_t n_new = (uint64_t)S.n_groups + new_only;
+        if (n_new >= (1ull << 31)) return fail(O3DR_ERR_INTERNAL, "more than 2^31 groups");
+        CHK(dev_ensure(c, S.grp[q], (size_t)(n_new + 1) * sizeof(IncGroup)));
+        CHK(dev_ensure(c, S.off[q], (size_t)(n_new + 1) * sizeof(uint32_t)));
+        CHK(dev_ensure(c, S.src, (size_t)(n_new + 1) * sizeof(uint32_t)));
+        launch_inc_place(&c->prof, c->stream, a, (uint32_t)n_new, (IncGroup*)S.grp[q].p, (uint32_t*)S.src.p, (uint32_t*)S.off[q].p,
+                         (uint32_t*)S.words.p + 1, (uint32_t*)S.partial.p);
+        HIPCHK(hipGetLastError());
+        uint32_t n_cells = 0;
+        CHK(inc_read_word(c, 1, &n_cells));
+        if ((uint64_t)n_cells > (uint64_t)S.n_cells + (uint64_t)tail || (uint64_t)n_cells > n_new * kGroupCells)
+            return fail(O3DR_ERR_INTERNAL, "cell count of the merged state out of range");
+        CHK(dev_ensure(c, S.cells[q], ((size_t)n_cells + 1) * sizeof(IncCell)));
+        launch_inc_copy(&c->prof, c->stream, a, (const IncGroup*)S.grp[q].p, (const uint32_t*)S.off[q].p, (const uint32_t*)S.src.p,
+                        (uint32_t)n_new, (IncCell*)S.cells[q].p, n_cells);
+        HIPCHK(hipGetLastError());
+        S.cur = q;
+        S.n_groups = (uint32_t)n_new;
+        S.n_cells = n_cells;
+        S.folded = n;
+        st[0] = tail;
+    }
+    // 5. the snapshot: cells with at least max(min_points_per_voxel, 1) points, in cell order
+    const IncGroup* grp = (const IncGroup*)S.grp[S.cur].p;
+    const uint32_t* off = (const uint32_t*)S.off[S.cur].p;
+    const IncCell* cells = (const IncCell*)S.cells[S.cur].p;
+    uint32_t m = S.n_cells;
+    const uint32_t* out_off = off;
+    if (need > 1u) {
+        CHK(dev_ensure(c, S.keep, ((size_t)S.n_groups + 1) * sizeof(uint32_t)));
+        CHK(dev_ensure(c, S.partial, (((size_t)S.n_groups + 1) / 4096 + 64) * sizeof(uint32_t)));
+        launch_inc_keep(&c->prof, c->stream, grp, off, cells, S.n_groups, S.n_cells, need, (uint32_t*)S.keep.p, (uint32_t*)S.words.p + 2,
+                        (uint32_t*)S.partial.p);
+        HIPCHK(hipGetLastError());
+        CHK(inc_read_word(c, 2, &m));
+        if (m > S.n_cells) return fail(O3DR_ERR_INTERNAL, "more kept cells than cells");
+        out_off = (const uint32_t*)S.keep.p;
+    }
+    if (!query && (int64_t)m > out_capacity) return fail(O3DR_ERR_CAPACITY, "output buffer too small");
+    o3dr_point* dst = out;
+    if (!query && mem == O3DR_MEM_HOST && m > 0) {
+        CHK(dev_ensure(c, c->st_out, (size_t)m * sizeof(o3dr_point)));
+        dst = (o3dr_point*)c->st_out.p;
+    }
+    if (!query && m > 0) {
+        launch_inc_snapshot(&c->prof, c->stream, grp, off, cells, S.n_groups, S.n_cells, need, out_off, zo, dst, m, c->cc_tmp);
+        HIPCHK(hipGetLastError());
+        if (mem == O3DR_MEM_HOST)
+            HIPCHK(hipMemcpyAsync(out, dst, (size_t)m * sizeof(o3dr_point), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipMemcpyAsync(c->cc_host, c->cc_tmp, sizeof(CloudCounters), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->cc_host->status & O3DR_STATUS_INTERNAL)
+        return fail(O3DR_ERR_INTERNAL, "a device-side guard of the incremental merge tripped (record or point id outside its range)");
+    *n_out = (int64_t)m;
+    if (status) *status = cc.status;
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_finalize_incremental(o3dr_ctx* c, o3dr_point* out, int64_t out_capacity, int64_t* n_out, uint32_t* status,
+                                         int32_t mem)
+{
+    if (n_out) *n_out = 0;
+    if (status) *status = 0;
+    CTX_ENTER(c);
+    if (!n_out) return fail(O3DR_ERR_INVALID_ARG, "n_out is NULL");
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    if (out_capacity < 0 || (out_capacity > 0 && !out)) return fail(O3DR_ERR_INVALID_ARG, "out is NULL with a capacity, or a negative capacity");
+    int64_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const int r = inc_run(c, out, out_capacity, n_out, status, mem, st);
+    if (r != O3DR_OK) {  // never half-folded: the next call rebuilds
+        inc_drop(c);
+        *n_out = 0;
+        if (status) *status = 0;
+    }
+    st[3] = c->inc.n_cells;
+    st[4] = c->inc.n_groups;
+    st[5] = inc_state_bytes(c);
+    memcpy(c->inc.stats, st, sizeof st);
+    return r;
+}
+
+extern "C" int o3dr_finalize_incremental_stats(o3dr_ctx* c, int64_t out[8])
+{
+    CTX_ENTER(c);
+    if (!out) return fail(O3DR_ERR_INVALID_ARG, "out is NULL");
+    memcpy(out, c->inc.stats, sizeof c->inc.stats);
+    return O3DR_OK;
+}
+
 // ---- multi-GPU merge: global box -> index-slice partition -> exchange -> local merge ----
 extern "C" int o3dr_finalize_global(o3dr_ctx* c, const float gmin[3], const float gmax[3], o3dr_point* out,
                                     int64_t out_capacity, int64_t* n_out, uint32_t* status, int32_t mem)
@@ -1635,6 +1925,7 @@ extern "C" int o3dr_cloud_big_assume_size(o3dr_ctx* c, int64_t n_points)
 {
     CTX_ENTER(c);
     if (n_points < 0 || n_points > c->cloud_ub) return fail(O3DR_ERR_INVALID_ARG, "size above what the calls so far can have produced");
+    if (n_points < c->inc.folded) ++c->cloud_gen;
     c->cloud_ub = n_points;
     c->cloud_n_exact = true;
     return O3DR_OK;
@@ -1654,6 +1945,7 @@ extern "C" int o3dr_cloud_big_adopt(o3dr_ctx* c, int64_t n_points)
     if (n_points >= (int64_t)0xffffffffLL) return fail(O3DR_ERR_INVALID_ARG, "cloud_big exceeds 2^32-1 points");
     // stream-ordered, no host round trip: the count is set by a one-thread kernel (the status bits accumulated so far
     // are kept); what filled the receive buffer must be ordered before this stream's next work by the caller
+    ++c->cloud_gen;
     launch_set_cloud_count(c->stream, c->cc_big, (uint64_t)n_points);
     HIPCHK(hipGetLastError());
     swap_clouds(c);
@@ -1716,6 +2008,7 @@ extern "C" int o3dr_cloud_big_partition_dev(o3dr_ctx* c, const void* hdrs_dev, i
     v.leaf[1] = leaf[1];
     v.leaf[2] = leaf[2];
     v.z_offset = zo;
+    ++c->cloud_gen;
     launch_partition(&c->prof, c->stream, c->ws, v, n_parts, nb, (uint64_t*)counts_dev, (uint32_t*)(counts_dev + n_parts), hdrs_dev, n_hdrs);
     if (hipGetLastError() != hipSuccess) return fail(O3DR_ERR_HIP, "partition launch failed");
     swap_clouds(c);  // the partitioned copy becomes cloud_big; the old buffer is kept as the alternate
@@ -1787,6 +2080,7 @@ extern "C" int o3dr_cloud_big_place_slices(o3dr_ctx* c, int32_t n_parts, int32_t
     c->place_ub = -1;                         // (the table is consumed)
     if (n_before == 0 && n_after == 0 && own == n_local) return O3DR_OK;  // nothing leaves, nothing arrives: the cloud stays as it is
     if (total >= (int64_t)0xffffffffLL) return fail(O3DR_ERR_INVALID_ARG, "the exchange buffer exceeds 2^32-1 points");
+    ++c->cloud_gen;
     CHK(alt_reserve(c, total > 0 ? total : 1));
     // part p's records start at sum(counts[0..p)) in the plain layout; where they go instead
     int64_t* sh = (int64_t*)(c->misc_host + 2560);
@@ -1822,6 +2116,7 @@ extern "C" int o3dr_cloud_big_set_size(o3dr_ctx* c, int64_t n_points)
     CTX_ENTER(c);
     if (n_points < 0 || n_points > c->cloud_cap) return fail(O3DR_ERR_INVALID_ARG, "more points than the cloud buffer holds");
     if (n_points >= (int64_t)0xffffffffLL) return fail(O3DR_ERR_INVALID_ARG, "cloud_big exceeds 2^32-1 points");
+    ++c->cloud_gen;
     launch_set_cloud_count(c->stream, c->cc_big, (uint64_t)n_points);  // stream-ordered, like o3dr_cloud_big_adopt
     HIPCHK(hipGetLastError());
     c->cloud_box_valid = false;
@@ -1902,6 +2197,7 @@ extern "C" int o3dr_cloud_big_partition(o3dr_ctx* c, const float gmin[3], const 
     v.z_offset = zo;
     uint32_t* ovf_dev = (uint32_t*)(c->misc_dev + 32);
     uint64_t* cnt_dev = (uint64_t*)(c->misc_dev + 64);
+    ++c->cloud_gen;
     launch_partition(&c->prof, c->stream, c->ws, v, n_parts, nb, cnt_dev, ovf_dev);
     if (hipGetLastError() != hipSuccess) return fail(O3DR_ERR_HIP, "partition launch failed");
     HIPCHK(hipMemcpyAsync(c->misc_host, c->misc_dev, 64 + 8 * (size_t)n_parts, hipMemcpyDeviceToHost, c->stream));
@@ -2135,6 +2431,7 @@ static int merge_partitioned_impl(o3dr_ctx* c, Transport& T, int32_t gather_resu
 {
     const int W = T.W, rank = T.rank;
     if (W < 1 || W > kMaxRadix || rank < 0 || rank >= W) return fail(O3DR_ERR_INVALID_ARG, "communicators of 1..128 ranks are supported");
+    ++c->cloud_gen;  // (the exchange reorders and replaces cloud_big)
     const size_t RW = (size_t)W + kRowExtra;
     // device scratch: own header | all headers | own row | row matrix (read back in one copy from o_hdrs on).  The one
     // allocation in front of the first collective (a few KiB); everything after it is decided by all ranks together.

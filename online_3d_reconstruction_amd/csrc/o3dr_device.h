@@ -186,6 +186,20 @@ struct CloudCounters {
     uint32_t pad;
 };
 
+// ---- incremental merge state (o3dr_finalize_incremental, kernels/incremental.inc) --------------------------------------
+// an occupied voxel group of the combined grid: ABSOLUTE coordinates (block of kGroupCells cells along x, row, layer) and
+// which of its cells are occupied; the state keeps them sorted by (iz, iy, bx) = ascending linear voxel index
+struct IncGroup {
+    int32_t bx, iy, iz;
+    uint32_t mask;
+};
+// an occupied cell: CentroidPoint's seven running fp32 sums (x, y, z + z_offset, r, g, b, a) and its point count
+struct IncCell {
+    float s[7];
+    uint32_t n;
+};
+static_assert(sizeof(IncCell) == 32, "32-byte cell records");
+
 // ---- launchers (o3dr_kernels.hip).  All are asynchronous on `s`. -------------------------------
 struct Profiler;  // o3dr_api.hip
 
@@ -277,5 +291,38 @@ void launch_partition_move(Profiler* pf, hipStream_t s, Workspace& ws, const Vox
 void launch_pack_header(hipStream_t s, const float* box6_dev, const CloudCounters* cc, void* hdr32_dev);
 void launch_count_from_cc(hipStream_t s, const CloudCounters* cc, uint32_t* n_dev);
 void launch_set_cloud_count(hipStream_t s, CloudCounters* cc, uint64_t n);
+// incremental merge (kernels/incremental.inc).  launch_inc_runs: the n points at `in` (the tail) as group runs sorted by
+// group, over the grid of the box in ws.mm slot 0 (ws.n_valid[0] = n); heads from rec_heads (cloud_big's recorded flags,
+// the tail starting at point `first`) or, rec_heads == nullptr, from the points.  Leaves ws.n_vox[0] groups.
+void launch_inc_runs(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_point* in, int64_t n, const float leaf[3], float z_offset,
+                     const uint8_t* rec_heads, int64_t first, int test_corrupt);
+struct IncFoldArgs {
+    const IncGroup* old_g;
+    const uint32_t* old_off;
+    const IncCell* old_cells;
+    uint32_t n_old, n_old_cells;
+    IncCell* scratch;  // 32 cells per tail group
+    IncGroup* tg;      // per tail group: coordinates + new mask
+    uint32_t* tmatch;  // per tail group: the state group it extends, or none
+    uint32_t nt;       // tail groups (ws.n_vox[0], read back)
+    uint32_t* flag;    // nt + 1 words: exclusive scan of "new group"
+    uint32_t* n_new_only;  // device word: new groups
+    CloudCounters* cc;
+};
+void launch_inc_fold(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_point* in, float z_offset, const IncFoldArgs& a,
+                     uint32_t* partial);
+// the merged group list (n_new groups) and its cell offsets: new_off (n_new + 1 words) ends in the cell count, also in *n_cells_dev
+void launch_inc_place(Profiler* pf, hipStream_t s, const IncFoldArgs& a, uint32_t n_new, IncGroup* new_g, uint32_t* src,
+                      uint32_t* new_off, uint32_t* n_cells_dev, uint32_t* partial);
+void launch_inc_copy(Profiler* pf, hipStream_t s, const IncFoldArgs& a, const IncGroup* new_g, const uint32_t* new_off,
+                     const uint32_t* src, uint32_t n_new, IncCell* cells, uint32_t cells_cap);
+// snapshot: keep_cnt == nullptr: every cell is kept (out_off = off); else kept cells per group -> their exclusive scan in
+// keep_cnt, the total in *n_keep_dev (launch_inc_keep), then the centroids (launch_inc_snapshot)
+void launch_inc_keep(Profiler* pf, hipStream_t s, const IncGroup* grp, const uint32_t* off, const IncCell* cells, uint32_t n_groups,
+                     uint32_t n_cells, uint32_t need, uint32_t* keep_cnt, uint32_t* n_keep_dev, uint32_t* partial);
+void launch_inc_snapshot(Profiler* pf, hipStream_t s, const IncGroup* grp, const uint32_t* off, const IncCell* cells, uint32_t n_groups,
+                         uint32_t n_cells, uint32_t need, const uint32_t* out_off, float z_offset, o3dr_point* out, uint32_t out_cap,
+                         CloudCounters* cc);
+void launch_inc_box_fold(hipStream_t s, float* box6, const float* tail6, float* mm6);
 
 }  // namespace o3dr

@@ -25,6 +25,7 @@
 //   multigpu     bounding-box fold, index-slice partition
 //   sor          statistical outlier removal
 //   small        clouds of at most kSmallMax points: the whole path in one launch of one workgroup
+//   incremental  the combined merge kept as running per-cell sums (o3dr_finalize_incremental)
 // The launchers follow in this file.
 #include <string.h>
 
@@ -40,6 +41,7 @@ namespace o3dr {
 #include "kernels/voxel_index.inc"
 #include "kernels/radix_sort.inc"
 #include "kernels/voxel_runs.inc"
+#include "kernels/incremental.inc"
 #include "kernels/multigpu.inc"
 #include "kernels/sor.inc"
 #include "kernels/small.inc"
@@ -411,6 +413,139 @@ void launch_voxel_grid(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelAr
         k_cloud_bbox_merge<<<1, 384, 0, s>>>(ws.out_mm_partial, kBoxFoldBlocks, v.cloud_box);
     }
 }
+
+// The grouped steps of launch_voxel_grid up to the group list (heads, run starts, run sort, group starts), on the tail of
+// an incremental merge; the cloud always takes group runs (its groups are folded by k_inc_fold, which has no point path)
+void launch_inc_runs(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_point* in, int64_t n, const float leaf[3], float z_offset,
+                     const uint8_t* rec_heads, int64_t first, int test_corrupt)
+{
+    const int64_t cap = n;
+    const int n_sort_tiles = cdiv64(cap, kSortTile);
+    const int n_seg_tiles = cdiv64(cap, kSegTile);
+    const size_t tm_lds = (size_t)n_sort_tiles * (kMaxRadix + 1) * sizeof(uint32_t);
+    const int tm = tm_lds <= 48 * 1024 ? 1 : 0;
+    const VoxelGeom* sort_geom = ws.geom_runs;
+    {
+        ProfScope ps(pf, O3DR_K_OTHER, s);
+        k_voxel_geom<<<1, 256, 0, s>>>(ws.mm, ws.mm_stride, 1, ws.n_valid, leaf[0], leaf[1], leaf[2], z_offset, ws.geom);
+    }
+    {
+        ProfScope ps(pf, O3DR_K_KEYGEN, s);
+        if (rec_heads) {
+            const int64_t bytes = (int64_t)n_seg_tiles * 256;
+            k_inc_heads_shift<<<cdiv64(bytes, 256), 256, 0, s>>>(rec_heads, (uint64_t)first, (uint64_t)n, ws.head_bits, (uint64_t)bytes);
+            k_head_counts<<<cdiv64(n_seg_tiles, 4), 256, 0, s>>>(ws.head_bits, ws.geom, n_seg_tiles, ws.seg_cnt);
+        } else {
+            k_group_heads<<<n_seg_tiles, 256, 0, s>>>(in, ws.geom, z_offset, n_seg_tiles, ws.seg_cnt, ws.head_bits);
+        }
+    }
+    {
+        ProfScope ps(pf, O3DR_K_OTHER, s);
+        launch_scan(s, ws.seg_cnt, n_seg_tiles, n_seg_tiles, 1, ws.n_runs, nullptr, ws.scan_partial);
+    }
+    {
+        ProfScope ps(pf, O3DR_K_SEGMENT, s);
+        k_run_geom<<<1, 64, 0, s>>>(ws.geom, ws.n_runs, 1, ws.geom_runs, 1, INT64_MAX);
+        k_run_starts<<<dim3(cdiv64(n_seg_tiles, kStartWaves), 1), kStartWaves * kWave, 0, s>>>(
+            ws.keys[0], ws.keys[1], cap, ws.geom, n_seg_tiles, ws.seg_cnt, ws.n_runs, ws.run_start, 0, ws.keys[1], ws.geom_runs, in,
+            z_offset, ws.head_bits);
+    }
+    const dim3 grid(n_sort_tiles, 1);
+    const int64_t hist_row = (int64_t)kMaxRadix * n_sort_tiles;
+    for (int pass = 0; pass < kMaxPasses; ++pass) {
+        {
+            ProfScope ps(pf, O3DR_K_SORT_HIST, s);
+            k_radix_hist<<<grid, kSortThreads, 0, s>>>(ws.keys[0], ws.keys[1], cap, sort_geom, pass, n_sort_tiles, ws.hist, ws.hist_part, tm);
+        }
+        {
+            ProfScope ps(pf, O3DR_K_OTHER, s);
+            if (tm)
+                k_scan_hist_tm<<<1, 1024, tm_lds, s>>>(ws.hist, sort_geom, pass, n_sort_tiles);
+            else
+                launch_scan(s, ws.hist, hist_row, hist_row, 1, nullptr, nullptr, ws.scan_partial, sort_geom, pass, n_sort_tiles);
+        }
+        {
+            ProfScope ps(pf, O3DR_K_SORT_SCATTER, s);
+            k_radix_scatter_lane<<<dim3(xcd_grid((int64_t)n_sort_tiles * kScatParts), 1), kScatThreads, 0, s>>>(
+                ws.keys[0], ws.vals[0], ws.keys[1], ws.vals[1], cap, sort_geom, pass, n_sort_tiles, ws.hist, ws.hist_part, tm);
+        }
+    }
+    {
+        ProfScope ps(pf, O3DR_K_SEGMENT, s);
+        k_run_heads<<<dim3(cdiv64(n_seg_tiles, kHeadWaves), 1), kHeadWaves * kWave, 0, s>>>(ws.keys[0], ws.keys[1], cap, sort_geom,
+                                                                                             n_seg_tiles, ws.seg_cnt, -1, ws.head_bits);
+    }
+    {
+        ProfScope ps(pf, O3DR_K_OTHER, s);
+        launch_scan(s, ws.seg_cnt, n_seg_tiles, n_seg_tiles, 1, ws.n_vox, nullptr, ws.scan_partial);
+    }
+    {
+        ProfScope ps(pf, O3DR_K_SEGMENT, s);
+        k_run_starts<<<dim3(cdiv64(n_seg_tiles, kStartWaves), 1), kStartWaves * kWave, 0, s>>>(
+            ws.keys[0], ws.keys[1], cap, sort_geom, n_seg_tiles, ws.seg_cnt, ws.n_vox, ws.seg_start, -1, nullptr, nullptr, nullptr, 0.f,
+            ws.head_bits);
+    }
+    if (test_corrupt) k_test_corrupt_payload<<<1, 1, 0, s>>>(ws.vals[0], ws.vals[1], sort_geom);
+}
+
+void launch_inc_fold(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_point* in, float z_offset, const IncFoldArgs& a,
+                     uint32_t* partial)
+{
+    {
+        ProfScope ps(pf, O3DR_K_CENTROID_RUNS, s);
+        int64_t nwg = cdiv64(a.nt, kGroupWaves);
+        if (nwg > 16384) nwg = 16384;
+        if (nwg < 1) nwg = 1;
+        k_inc_fold<<<(int)nwg, kGroupWaves * kWave, 0, s>>>(in, ws.keys[0], ws.keys[1], ws.vals[0], ws.vals[1], ws.seg_start, ws.run_start,
+                                                            ws.geom_runs, ws.geom, ws.n_vox, z_offset, a.old_g, a.old_off, a.old_cells,
+                                                            a.n_old, a.n_old_cells, a.scratch, a.nt, a.tg, a.tmatch, a.cc);
+    }
+    ProfScope ps(pf, O3DR_K_OTHER, s);
+    k_inc_new_flags<<<cdiv64((int64_t)a.nt + 1, 256), 256, 0, s>>>(a.tmatch, a.nt, a.flag);
+    launch_scan(s, a.flag, (int64_t)a.nt + 1, (int64_t)a.nt + 1, 1, a.n_new_only, nullptr, partial);
+}
+
+void launch_inc_place(Profiler* pf, hipStream_t s, const IncFoldArgs& a, uint32_t n_new, IncGroup* new_g, uint32_t* src,
+                      uint32_t* new_off, uint32_t* n_cells_dev, uint32_t* partial)
+{
+    ProfScope ps(pf, O3DR_K_OTHER, s);
+    (void)hipMemsetAsync(new_off, 0, sizeof(uint32_t) * ((size_t)n_new + 1), s);
+    if (a.n_old > 0)
+        k_inc_place_old<<<cdiv64(a.n_old, 256), 256, 0, s>>>(a.old_g, a.n_old, a.tg, a.tmatch, a.nt, a.flag, new_g, src, new_off, n_new, a.cc);
+    if (a.nt > 0)
+        k_inc_place_new<<<cdiv64(a.nt, 256), 256, 0, s>>>(a.old_g, a.n_old, a.tg, a.tmatch, a.nt, a.flag, new_g, src, new_off, n_new, a.cc);
+    launch_scan(s, new_off, (int64_t)n_new + 1, (int64_t)n_new + 1, 1, n_cells_dev, nullptr, partial);
+}
+
+void launch_inc_copy(Profiler* pf, hipStream_t s, const IncFoldArgs& a, const IncGroup* new_g, const uint32_t* new_off,
+                     const uint32_t* src, uint32_t n_new, IncCell* cells, uint32_t cells_cap)
+{
+    if (n_new == 0) return;
+    ProfScope ps(pf, O3DR_K_OTHER, s);
+    k_inc_copy<<<cdiv64((int64_t)n_new * kGroupCells, 256), 256, 0, s>>>(new_g, new_off, src, n_new, a.old_off, a.old_cells, a.n_old,
+                                                                         a.n_old_cells, a.scratch, a.nt, cells, cells_cap, a.cc);
+}
+
+void launch_inc_keep(Profiler* pf, hipStream_t s, const IncGroup* grp, const uint32_t* off, const IncCell* cells, uint32_t n_groups,
+                     uint32_t n_cells, uint32_t need, uint32_t* keep_cnt, uint32_t* n_keep_dev, uint32_t* partial)
+{
+    ProfScope ps(pf, O3DR_K_OTHER, s);
+    (void)hipMemsetAsync(keep_cnt + n_groups, 0, sizeof(uint32_t), s);
+    if (n_groups > 0) k_inc_keep_count<<<cdiv64(n_groups, 4), 256, 0, s>>>(grp, off, cells, n_groups, n_cells, need, keep_cnt);
+    launch_scan(s, keep_cnt, (int64_t)n_groups + 1, (int64_t)n_groups + 1, 1, n_keep_dev, nullptr, partial);
+}
+
+void launch_inc_snapshot(Profiler* pf, hipStream_t s, const IncGroup* grp, const uint32_t* off, const IncCell* cells, uint32_t n_groups,
+                         uint32_t n_cells, uint32_t need, const uint32_t* out_off, float z_offset, o3dr_point* out, uint32_t out_cap,
+                         CloudCounters* cc)
+{
+    if (n_groups == 0) return;
+    ProfScope ps(pf, O3DR_K_CENTROID, s);
+    k_inc_snapshot<<<cdiv64(n_groups, 4), 256, 0, s>>>(grp, off, cells, n_groups, n_cells, need, out_off, z_offset,
+                                                       reinterpret_cast<uint4*>(out), out_cap, cc);
+}
+
+void launch_inc_box_fold(hipStream_t s, float* box6, const float* tail6, float* mm6) { k_inc_box_fold<<<1, 64, 0, s>>>(box6, tail6, mm6); }
 
 void launch_bilateral(Profiler* pf, hipStream_t s, const uint8_t* src, int64_t src_pitch, int64_t src_fstride, int rows,
                       int cols, int frames, int radius, int maxk, const float* tab, uint8_t* dst, int64_t dst_pitch,

@@ -88,6 +88,8 @@ public:
     int n_gpus = 1;                 // --gpus N: frames sharded over devices device_id .. device_id+N-1, one host thread and
                                     // one context each, merged through o3dr_merge_partitioned (RCCL)
     bool partitioned_merge = false; // --partitioned_merge: take that path with one GPU as well
+    bool preview = false;           // --preview: after every cycle, the merged map so far -> <output_dir>/preview.ply
+                                    // (pose.cpp:437-448, 638-674), folded incrementally (o3dr_finalize_incremental)
 
     std::vector<RawImageData> rawImageDataVec;
     std::vector<ImageData> acceptedImageDataVec;

@@ -390,6 +390,8 @@ void Pose::printUsage()
             "       [--keypoints_dir d/]   (d/<img_num>.txt: one \"x y\" keypoint per line; used iff jump_pixels != 1)\n"
             "       [--gpus N]   (frames sharded over N GPUs from --device on, one host thread each; the final merge is exchanged\n"
             "                     over RCCL and equals the one-GPU result bit for bit)  [--partitioned_merge]  (same path, N = 1)\n"
+            "       [--preview]  (after every cycle of --seq_len frames: the merged cloud so far -> output_dir/preview.ply,\n"
+            "                     folding only the new points; single-GPU batched path only)\n"
             "--sor defaults to 1: like the reference, every per-frame cloud goes through StatisticalOutlierRemoval(50, 1.0)\n"
             "before its voxel grid when jump_pixels > 0.\n"
             "./pose --downsample file.ply [--voxel_size m] [--min_points_per_voxel n]\n"
@@ -432,7 +434,8 @@ int Pose::parseCmdArgs(int argc, char** argv)
         else if (a == "--gpus") n_gpus = atoi(need(i));
         else if (a == "--partitioned_merge") partitioned_merge = true;
         else if (a == "--dist_nearby" || a == "--search_radius" || a == "--range_width") { need(i); }
-        else if (a == "--preview" || a == "--use_segment_labels" || a == "--segment_cloud" || a == "--displayUAVPositions" ||
+        else if (a == "--preview") preview = true;
+        else if (a == "--use_segment_labels" || a == "--segment_cloud" || a == "--displayUAVPositions" ||
                  a == "--test_bad_data_rejection")
             cout << a << ": outside the hot path, ignored in this build" << endl;
         else if (a.rfind("--", 0) == 0) throw runtime_error("unknown flag " + a);
@@ -489,6 +492,10 @@ void Pose::run_reconstruction()
     if (!sor && jump_pixels > 0)
         cout << "NOTE: --sor 0: the per-frame StatisticalOutlierRemoval of the reference (pose_functions.cpp:1673-1686) is OFF;\n"
                 "      the clouds differ from the reference's for the same command line." << endl;
+    const bool sharded_path = n_gpus > 1 || partitioned_merge;
+    if (preview && (sharded_path || reference_fanout))
+        cout << "--preview: not available on the " << (sharded_path ? "--gpus / --partitioned_merge" : "--reference_fanout")
+             << " path" << endl;
     cout << "\n\nProgram Start!" << endl;
     while (current_idx <= last_idx) {
         cout << "\nCycle " << cycle << endl;
@@ -573,6 +580,21 @@ void Pose::run_reconstruction()
         const double dt = chrono::duration<double>(clk::now() - t3).count();
         cout << "\n\nPoint Cloud Creation time: " << dt << " sec" << endl;  // pose.cpp:429-431
         if (log_file.is_open()) log_file << "Point Cloud Creation time:\t\t\t" << dt << " sec" << endl;
+        if (preview && !sharded_path && !reference_fanout) {
+            // the reference's preview thread merges a copy of cloud_big after every cycle (pose.cpp:437-448, 638-674); here
+            // only the points this cycle appended are folded into the merge kept on the device
+            int64_t n_prev = 0;
+            uint32_t st = 0;
+            chk(o3dr_finalize_incremental(c, nullptr, 0, &n_prev, &st, O3DR_MEM_HOST), "finalize_incremental");
+            PointCloud::Ptr prev(new PointCloud());
+            prev->points.resize((size_t)(n_prev > 0 ? n_prev : 1));
+            chk(o3dr_finalize_incremental(c, prev->points.data(), n_prev > 0 ? n_prev : 1, &n_prev, &st, O3DR_MEM_HOST),
+                "finalize_incremental");
+            prev->points.resize((size_t)n_prev);
+            string ppath = outputPrefix + "preview.ply";
+            save_pt_cloud_to_PLY_File(prev, ppath);
+            cout << "preview: " << n_prev << " points" << endl;
+        }
         cycle++;
     }
     const double total = chrono::duration<double>(clk::now() - app_start).count();

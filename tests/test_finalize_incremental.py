@@ -1,0 +1,391 @@
+"""o3dr_finalize_incremental: the combined merge of cloud_big kept as running per-cell sums, folding only the points
+appended since the previous call (the reference's per-cycle preview, pose.cpp:437-448, 638-674).  Its result must be
+o3dr_finalize's at every call, bit for bit; these tests check that after every call, on every path that keeps or drops
+the state, and on the fallbacks."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import assert_points_equal, random_cloud
+
+NEW_SYMBOLS = ("o3dr_finalize_incremental", "o3dr_finalize_incremental_stats")
+
+
+def _params(**kw):
+    import online_3d_reconstruction_amd as o3dr
+    kw.setdefault("sor_enable", False)
+    return o3dr.Params(**kw)
+
+
+def _inc(ctx, **kw):
+    out, st = ctx.finalizeIncremental(return_status=True, **kw)
+    return out, st, ctx.finalizeIncrementalStats()
+
+
+def _points(t):
+    from online_3d_reconstruction_amd.api import points_from_torch
+    return t if isinstance(t, np.ndarray) else points_from_torch(t)
+
+
+# ---- without a GPU -------------------------------------------------------------------------------------------------------
+def test_new_symbols_are_declared_exported_and_bound():
+    from online_3d_reconstruction_amd import _lib as L
+    names = {n for n, _, _ in L.SYMBOLS}
+    for s in NEW_SYMBOLS:
+        assert s in names
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "o3dr.h")).read()
+    for s in NEW_SYMBOLS:
+        assert re.search(r"\bint\s+" + s + r"\(", header), s
+    lib = L.load_library()
+    for s in NEW_SYMBOLS:
+        assert getattr(lib, s).restype is C.c_int
+
+
+def test_null_context_is_rejected_and_n_out_zeroed():
+    from online_3d_reconstruction_amd import _lib as L
+    lib = L.load_library()
+    n = C.c_int64(1234)
+    st = C.c_uint32(77)
+    out = np.empty(4, np.uint32)
+    for mem in (L.MEM_HOST, L.MEM_DEVICE, 7):
+        n.value, st.value = 1234, 77
+        assert lib.o3dr_finalize_incremental(None, out.ctypes.data, 1, C.byref(n), C.byref(st), mem) == L.ERR_INVALID_ARG
+        assert n.value == 0 and st.value == 0
+    n.value = 1234
+    assert lib.o3dr_finalize_incremental(None, None, 0, C.byref(n), None, L.MEM_HOST) == L.ERR_INVALID_ARG
+    assert n.value == 0
+    stats = (C.c_int64 * 8)()
+    assert lib.o3dr_finalize_incremental_stats(None, stats) == L.ERR_INVALID_ARG
+
+
+def test_without_a_gpu_the_call_fails_loudly():
+    """no context without a device (no CPU fall-back), so nothing reaches a merge"""
+    import online_3d_reconstruction_amd as o3dr
+    from online_3d_reconstruction_amd import _lib as L
+    try:
+        ctx = o3dr.Context(0)
+    except L.O3drError as e:
+        assert e.code in (L.ERR_NO_DEVICE, L.ERR_INVALID_ARG)
+        return
+    with ctx:  # a GPU is present: the call itself works on an empty cloud
+        out, st, s = _inc(ctx)
+        assert len(out) == 0 and st == 0 and s["from_empty"] == 1
+
+
+# ---- on the GPU ----------------------------------------------------------------------------------------------------------
+def _frames(start, F, rows, cols, kp):
+    from online_3d_reconstruction_amd import synth
+    disp, bgr = synth.make_frames(start, F, rows, cols, invalid_frac=0.02)
+    poses = synth.make_poses(start, F)
+    kps = None
+    if kp:
+        rng = np.random.default_rng(start)
+        kps = [np.stack([rng.uniform(0, cols - 1, 40), rng.uniform(0, rows - 1, 40)], 1).astype(np.float32) for _ in range(F)]
+    return disp, bgr, poses, kps
+
+
+CASES = [  # jump, min_points, sor, keypoints, device memory, frames per call, calls, rows, cols
+    (1, 1, False, False, False, 1, 5, 120, 160),
+    (15, 3, True, True, True, 1, 4, 240, 320),
+    (1, 3, False, False, True, 64, 3, 120, 160),
+    (15, 1, False, True, False, 64, 2, 720, 1280),
+    (1, 1, True, False, False, 64, 2, 96, 128),
+    (15, 3, False, False, False, 64, 2, 240, 320),
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("jump,minpts,sor,kp,dev,per_call,calls,rows,cols", CASES)
+def test_equal_to_finalize_and_oracle_after_every_call(orc, jump, minpts, sor, kp, dev, per_call, calls, rows, cols):
+    import torch
+
+    import online_3d_reconstruction_amd as o3dr
+    from online_3d_reconstruction_amd import synth
+    with o3dr.Context(0, Q=synth.camera_Q(rows, cols),
+                      params=_params(jump_pixels=jump, voxel_size=0.05, min_points_per_voxel=minpts, sor_enable=sor)) as ctx:
+        n_prev = 0
+        for k in range(calls):
+            disp, bgr, poses, kps = _frames(1000 + k * per_call, per_call, rows, cols, kp)
+            if dev:
+                ctx.accumulateFrames(torch.from_numpy(disp).cuda(), torch.from_numpy(bgr).cuda(), torch.from_numpy(poses).cuda(),
+                                     keypoints=kps)
+            else:
+                ctx.accumulateFrames(disp, bgr, poses, keypoints=kps)
+            got, st, s = _inc(ctx, device="cuda" if dev else None)
+            got = _points(got)
+            big = ctx.cloudBigRead()
+            want, wst = ctx.finalize(return_status=True)
+            assert st == wst
+            assert_points_equal(got, want, f"call {k}: incremental vs finalize")
+            ref, _ = orc.downsample_pt_cloud(big, 0.05, True, minpts)
+            assert_points_equal(got, ref, f"call {k}: incremental vs oracle")
+            assert s["fallback"] == 0
+            assert s["points_folded"] == len(big) - n_prev
+            assert s["from_empty"] == (1 if k == 0 else 0)
+            n_prev = len(big)
+        # nothing appended: nothing folded, the same cloud
+        again, st2, s = _inc(ctx)
+        assert s["points_folded"] == 0 and s["from_empty"] == 0 and st2 == st
+        assert_points_equal(again, want, "repeat call")
+
+
+@pytest.mark.gpu
+def test_state_drops_exactly_where_cloud_big_is_rewritten(monkeypatch):
+    import online_3d_reconstruction_amd as o3dr
+    from online_3d_reconstruction_amd import _lib as L
+    from online_3d_reconstruction_amd import synth
+    monkeypatch.setenv("O3DR_TEST_HOOKS", "1")
+    rows, cols = 120, 160
+    prm = _params(jump_pixels=2, voxel_size=0.05)
+    with o3dr.Context(0, Q=synth.camera_Q(rows, cols), params=prm) as ctx:
+        step = [0]
+
+        def add(F=3):
+            disp, bgr, poses, _ = _frames(2000 + 10 * step[0], F, rows, cols, False)
+            step[0] += 1
+            ctx.accumulateFrames(disp, bgr, poses)
+
+        def check(from_empty, what, fallback=0):
+            got, st, s = _inc(ctx)
+            want, wst = ctx.finalize(return_status=True)
+            assert_points_equal(got, want, what)
+            assert st == wst, what
+            assert (s["from_empty"], s["fallback"]) == (from_empty, fallback), (what, s)
+            return s
+
+        add()
+        check(1, "first call")
+        add()
+        check(0, "appended frames")
+        T = np.eye(4, dtype=np.float32)
+        T[:3, 3] = (0.37, -0.21, 0.05)
+        ctx.cloudBigTransform(T)
+        check(1, "after cloudBigTransform")
+        add()
+        check(0, "appended after the refold")
+        foreign = random_cloud(5000, 7)
+        ctx.cloudBigAppend(foreign)
+        s = check(0, "foreign append (no recorded heads)")
+        assert s["points_folded"] == 5000
+        add()
+        check(0, "frames after a foreign append")
+        ctx.set_params(_params(jump_pixels=2, voxel_size=0.07))
+        check(1, "voxel_size changed")
+        ctx.set_params(_params(jump_pixels=2, voxel_size=0.07, min_points_per_voxel=3))
+        s = check(0, "min_points_per_voxel changed (no refold)")
+        assert s["points_folded"] == 0
+        ctx.set_params(_params(jump_pixels=2, voxel_size=0.07, min_points_per_voxel=3, dont_downsample=True))
+        check(0, "dont_downsample", fallback=1)
+        ctx.set_params(_params(jump_pixels=2, voxel_size=0.07, min_points_per_voxel=3))
+        check(1, "dont_downsample off again")
+        # the local-transport exchange (one rank) reorders cloud_big
+        comm = C.c_void_p()
+        L.check(ctx._lib.o3dr_test_local_comm_create(1, C.byref(comm)))
+        try:
+            n = ctx.cloudBigSize()[0]
+            out = np.empty(max(n, 1), L.POINT)
+            m, tot, st = C.c_int64(0), C.c_int64(0), C.c_uint32(0)
+            L.check(ctx._lib.o3dr_test_merge_partitioned_local(ctx._h, comm, 0, 1, out.ctypes.data, n, C.byref(m), C.byref(tot),
+                                                               C.byref(st), L.MEM_HOST))
+        finally:
+            L.check(ctx._lib.o3dr_test_local_comm_destroy(comm))
+        check(1, "after merge_partitioned (local transport)")
+        add()
+        check(0, "appended after the exchange")
+        ctx.cloudBigReset()
+        got, st, s = _inc(ctx)
+        assert len(got) == 0 and st == 0 and s["from_empty"] == 1
+        add()
+        check(0, "after cloudBigReset")
+
+
+@pytest.mark.gpu
+def test_geometry_edges(orc):
+    """negative coordinates, cells on both sides of 32-cell group boundaries, several z layers (below -500, above +500),
+    and tails that start in the middle of a group run"""
+    import online_3d_reconstruction_amd as o3dr
+    from oracle.orc import POINT
+    vs = 0.05
+    rng = np.random.default_rng(3)
+
+    def cloud(n, x0, x1, y0, y1, z):
+        p = np.empty(n, POINT)
+        p["x"] = rng.uniform(x0, x1, n).astype(np.float32)
+        p["y"] = rng.uniform(y0, y1, n).astype(np.float32)
+        p["z"] = np.asarray(z, np.float32) if np.ndim(z) else np.float32(z)
+        p["rgba"] = rng.integers(0, 1 << 24, n, dtype=np.uint32)
+        return p
+
+    g = 32 * vs  # one group along x
+    parts = [
+        cloud(3000, -3.2, -0.1, -2.0, -0.5, -1.0),                        # negative x and y
+        cloud(3000, g - 0.2, g + 0.2, 0.0, 0.3, 2.0),                     # both sides of a group boundary
+        cloud(2000, -g - 0.1, -g + 0.1, -0.3, 0.3, 0.5),                  # ... a negative one
+        cloud(2000, 0.0, 1.0, 0.0, 1.0, rng.uniform(-1700, 1700, 2000)),  # z layers below -500 and above +500
+    ]
+    # a tail that continues the last group run of the previous call: sorted along x, split in the middle of a run
+    row = cloud(4000, 5.0, 5.0 + 3 * g, 1.0, 1.02, 0.0)
+    row = row[np.argsort(row["x"], kind="stable")]
+    with o3dr.Context(0, params=_params(voxel_size=vs)) as ctx:
+        for p in parts + [row[:1234], row[1234:2001], row[2001:]]:
+            ctx.cloudBigAppend(p)
+            got, st, s = _inc(ctx)
+            assert s["fallback"] == 0
+            want = ctx.finalize()
+            assert_points_equal(got, want, "incremental vs finalize")
+        ref, _ = orc.downsample_pt_cloud(ctx.cloudBigRead(), vs, True, 1)
+        assert_points_equal(got, ref, "incremental vs oracle")
+
+
+@pytest.mark.gpu
+def test_fallbacks_run_finalize():
+    import online_3d_reconstruction_amd as o3dr
+    from online_3d_reconstruction_amd import _lib as L
+    from oracle.orc import POINT
+
+    def pts(xs, ys, zs):
+        p = np.zeros(len(xs), POINT)
+        p["x"], p["y"], p["z"] = np.float32(xs), np.float32(ys), np.float32(zs)
+        p["rgba"] = np.arange(len(xs), dtype=np.uint32) * 12345
+        return p
+
+    # PCL's overflow guard: a 1 mm grid over 200 m x 200 m
+    with o3dr.Context(0, params=_params(voxel_size=0.001)) as ctx:
+        a = pts([0.0, 200.0, 3.0], [0.0, 200.0, 1.0], [0.0, 0.0, 0.0])
+        ctx.cloudBigAppend(a)
+        got, st, s = _inc(ctx)
+        want, wst = ctx.finalize(return_status=True)
+        assert st == wst and st & L.STATUS_VOXEL_OVERFLOW and s["fallback"] == 1
+        assert_points_equal(got, want, "overflow guard")
+        assert_points_equal(got, a, "overflow guard returns cloud_big")
+    # a cell coordinate of 2^24 or more
+    with o3dr.Context(0, params=_params(voxel_size=0.05)) as ctx:
+        ctx.cloudBigAppend(pts([1.0e6, 1.0e6 + 0.3, 1.0e6 + 0.31], [2.0, 2.0, 2.01], [0.0, 0.1, 0.2]))
+        got, st, s = _inc(ctx)
+        assert s["fallback"] == 1
+        assert_points_equal(got, ctx.finalize(), "|cell| >= 2^24")
+    # a grid of 2^32 cells or more without PCL's guard firing (46341 x 46341 x 2 cells, dx*dy*dz = 46340^2)
+    with o3dr.Context(0, params=_params(voxel_size=0.05)) as ctx:
+        lo, hi = 0.025, 0.025 + 2316.99
+        ctx.cloudBigAppend(pts([lo, hi, lo, hi, 100.0], [lo, hi, hi, lo, 100.0], [499.95, 500.05, 499.95, 500.05, 500.0]))
+        got, st, s = _inc(ctx)
+        want, wst = ctx.finalize(return_status=True)
+        assert s["fallback"] == 1 and st == wst and not (st & L.STATUS_VOXEL_OVERFLOW)
+        assert_points_equal(got, want, "index that could wrap")
+
+
+@pytest.mark.gpu
+def test_growth_to_millions_of_cells(orc):
+    import online_3d_reconstruction_amd as o3dr
+    with o3dr.Context(0, params=_params(voxel_size=0.05)) as ctx:
+        for k, n in enumerate((2000, 50_000, 400_000, 1_500_000, 3_000_000)):
+            ctx.cloudBigAppend(random_cloud(n, 100 + k, extent=(120.0, 100.0, 5.0), origin=(-60.0, -40.0, -2.0)))
+            got, st, s = _inc(ctx)
+            assert s["fallback"] == 0 and s["points_folded"] == n
+            assert_points_equal(got, ctx.finalize(), f"step {k}")
+            assert s["cells"] == len(got)
+        assert s["cells"] > 3_000_000
+        ref, _ = orc.downsample_pt_cloud(ctx.cloudBigRead(), 0.05, True, 1)
+        assert_points_equal(got, ref, "oracle")
+
+
+@pytest.mark.gpu
+def test_errors_leave_an_empty_state_and_the_next_call_rebuilds(monkeypatch):
+    import online_3d_reconstruction_amd as o3dr
+    from online_3d_reconstruction_amd import _lib as L
+    monkeypatch.setenv("O3DR_TEST_HOOKS", "1")
+    with o3dr.Context(0, params=_params(voxel_size=0.05)) as ctx:
+        ctx.cloudBigAppend(random_cloud(200_000, 5))
+        want = ctx.finalize()
+        lib, h = ctx._lib, ctx._h
+        n, st = C.c_int64(0), C.c_uint32(0)
+        L.check(lib.o3dr_finalize_incremental(h, None, 0, C.byref(n), C.byref(st), L.MEM_HOST))
+        assert n.value == len(want)
+        small = np.empty(len(want) - 1, L.POINT)
+        n.value = 99
+        assert lib.o3dr_finalize_incremental(h, small.ctypes.data, len(small), C.byref(n), C.byref(st), L.MEM_HOST) == L.ERR_CAPACITY
+        assert n.value == 0
+        assert lib.o3dr_finalize_incremental(h, small.ctypes.data, len(small), C.byref(n), C.byref(st), 5) == L.ERR_INVALID_ARG
+        assert n.value == 0
+        got, _, s = _inc(ctx)
+        assert_points_equal(got, want, "after a capacity error")
+        # a corrupted run id reaching the fold: O3DR_ERR_INTERNAL, never a fault; the next call rebuilds
+        ctx.cloudBigAppend(random_cloud(300_000, 6))
+        want = ctx.finalize()
+        L.check(lib.o3dr_test_corrupt_next_gather(h))
+        n.value = 99
+        assert lib.o3dr_finalize_incremental(h, None, 0, C.byref(n), C.byref(st), L.MEM_HOST) == L.ERR_INTERNAL
+        assert n.value == 0
+        got, _, s = _inc(ctx)
+        assert s["from_empty"] == 1
+        assert_points_equal(got, want, "after O3DR_ERR_INTERNAL")
+
+
+@pytest.mark.gpu
+def test_full_size_two_steps_of_200_dense_720p_frames():
+    import torch
+
+    import online_3d_reconstruction_amd as o3dr
+    from online_3d_reconstruction_amd import synth
+    disp, bgr = synth.make_frames(0, 200)
+    d, c = torch.from_numpy(disp).cuda(), torch.from_numpy(bgr).cuda()
+    with o3dr.Context(0, Q=synth.camera_Q(), params=_params(jump_pixels=1, voxel_size=0.05)) as ctx:
+        ctx.accumulateFrames(d, c, torch.from_numpy(synth.make_poses(0, 200)).cuda())
+        first = _points(ctx.finalizeIncremental(device="cuda"))
+        assert_points_equal(first, _points(ctx.finalize(device="cuda")), "first 200 frames")
+        ctx.accumulateFrames(d, c, torch.from_numpy(synth.make_poses(200, 200)).cuda())
+        got = _points(ctx.finalizeIncremental(device="cuda"))
+        s = ctx.finalizeIncrementalStats()
+        assert s["from_empty"] == 0 and s["fallback"] == 0
+        assert_points_equal(got, _points(ctx.finalize(device="cuda")), "400 frames")
+        assert s["state_bytes"] <= 80 * s["cells"], s
+
+
+@pytest.mark.gpu
+def test_cli_preview_after_every_cycle(tmp_path, orc, Q):
+    from test_cli_pose import POSE_BIN, _oracle_frame, _read_ply, _write_dataset
+    tmp = str(tmp_path)
+    names = ("1239", "1240", "1246", "1248", "1249", "1251", "1255")
+    _write_dataset(tmp, names)
+    cmd = [POSE_BIN, "1230", "1280", "--jump_pixels", "15", "--voxel_size", "0.05", "--only_MAVLink", "--preview", "--seq_len", "2",
+           "--data_dir", tmp + "/data_files/", "--image_dir", tmp + "/images/", "--disparity_dir", tmp + "/disparities/",
+           "--output_dir", tmp + "/output/"]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stdout + res.stderr
+    out = res.stdout
+    assert "ignored in this build" not in out
+    accepted, counts = [], []
+    for line in out.splitlines():
+        m = re.match(r"(\d+) .*Accepted!", line)
+        if m:
+            accepted.append(len(counts))
+        m = re.match(r"preview: (\d+) points", line)
+        if m:
+            counts.append(int(m.group(1)))
+    clouds = [_oracle_frame(orc, Q, name, 15, True) for name in names[2:]]
+    assert len(clouds) == 5 and len(counts) == 3  # cycles of 2 accepted frames: 2, 2, 1
+    for k, n in enumerate(counts):
+        ref, _ = orc.downsample_pt_cloud(np.concatenate(clouds[: min(2 * (k + 1), 5)]), 0.05, True, 1)
+        assert n == len(ref), (k, n, len(ref))
+    prev = open(tmp + "/output/preview.ply", "rb").read()
+    assert prev == open(tmp + "/output/cloud.ply", "rb").read()
+    assert len(_read_ply(tmp + "/output/preview.ply")) == counts[-1]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("extra", [["--reference_fanout"], ["--partitioned_merge"]])
+def test_cli_preview_not_available_on_other_paths(tmp_path, extra):
+    from test_cli_pose import POSE_BIN, _write_dataset
+    tmp = str(tmp_path)
+    _write_dataset(tmp, ("1248", "1249"))
+    cmd = [POSE_BIN, "1248", "1249", "--jump_pixels", "15", "--voxel_size", "0.05", "--only_MAVLink", "--preview", "--sor", "0",
+           "--data_dir", tmp + "/data_files/", "--image_dir", tmp + "/images/", "--disparity_dir", tmp + "/disparities/",
+           "--output_dir", tmp + "/output/"] + extra
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stdout + res.stderr
+    assert "--preview: not available on the" in res.stdout
+    assert not os.path.exists(tmp + "/output/preview.ply")
