@@ -341,6 +341,61 @@ int o3dr_comm_destroy(void* comm);
 int o3dr_host_register(void* ptr, int64_t bytes);
 int o3dr_host_unregister(void* ptr);
 
+/* ---- point-cloud alignment: pcl::IterativeClosestPoint as the reference runs it (pose.cpp:46-112 --align_point_cloud,
+ * runICPalignment pose_functions.cpp:1634-1652): point-to-point ICP with the SVD estimate.  The contract below is this
+ * library's own (PCL's results are not bit-pinned); where PCL leaves something open it is made exact and deterministic.
+ *
+ * Nearest neighbour: for each query q the target point t minimising the key (d2, original target index) in lexicographic
+ * order, d2 = ((0 + dx*dx) + dy*dy) + dz*dz in fp32 without FMA (the d2 of A3b); ties go to the lowest index (duplicate
+ * target points are well defined).  A candidate counts only if d2 <= r2, r2 = (float)(max_distance * max_distance) (the
+ * product in fp64, then rounded; max_distance = +inf: no limit).  No qualifying point (or a query with a non-finite
+ * coordinate): idx = 0xFFFFFFFF, d2 = +inf.  Indices refer to the caller's target array.  Target points must be finite.
+ *
+ * ICP: the cumulative transform T is kept in fp64, starting from T_init (float[16] row-major like o3dr_transform_pt_cloud's
+ * T; NULL = identity).  Pass k:
+ *   1. P = A2(fp32(T), source): the ORIGINAL source through the fp32-rounded T, bit-identical to o3dr_transform_pt_cloud;
+ *   2. every P_i's nearest neighbour within max_correspondence_distance; the correspondences are the points that have one;
+ *   3. k > 0 and every source point has the neighbour index it had in pass k-1: stop, O3DR_ICP_UNCHANGED (T is the fixed point);
+ *   4. fewer than 3 correspondences: stop, O3DR_ICP_TOO_FEW (T as it is);
+ *   5. fp64 moments about c0 = the target's bounding-box centre (count, sum a, sum b, sum a b^T, sum d2 with a = P_i - c0,
+ *      b = t_idx(i) - c0) in a fixed order: per-workgroup partials over a fixed partition of the source, folded in a fixed
+ *      order - no float atomics, bit-reproducible;
+ *   6. dT by Kabsch / Umeyama without scale (fp64, host; proper rotation, reflections corrected); a cross-covariance of rank
+ *      < 2 (s2 <= 1e-12 s1): stop, O3DR_ICP_DEGENERATE;
+ *   7. T <- dT * T; max |dT - I| over the top three rows <= transformation_epsilon: stop, O3DR_ICP_SMALL_STEP;
+ *   8. max_iterations solves applied: stop, O3DR_ICP_MAX_ITERATIONS (max_iterations = 0: T_init with this reason).
+ * Then fitness = mean d2 over the correspondences at fp32(T_out) (pcl::Registration::getFitnessScore; DBL_MAX without
+ * correspondences) and n_correspondences = their count; UNCHANGED, TOO_FEW and DEGENERATE end on a pass at T_out already,
+ * the other reasons take one more pass.  iterations = solves applied.  An empty source or target: O3DR_OK, T = T_init,
+ * O3DR_ICP_TOO_FEW, no correspondence.
+ * Clouds of at most 2^32-1 points in `mem` (a device pointer such as o3dr_cloud_big_view's works as either).  Both calls
+ * synchronise.  They reuse the sort workspace: a pending o3dr_cloud_big_slice_counts_dev table is dropped (a following
+ * o3dr_cloud_big_place_slices fails with O3DR_ERR_INVALID_ARG).  On error *res / host outputs are zeroed. */
+typedef struct o3dr_icp_params {
+    int32_t max_iterations;              /* default 10 (PCL Registration) */
+    double  max_correspondence_distance; /* default +inf (no limit) */
+    double  transformation_epsilon;      /* default 0 */
+} o3dr_icp_params;
+typedef struct o3dr_icp_result {
+    double  T[16];                       /* row-major 4x4, fp64 */
+    double  fitness;
+    int64_t n_correspondences;
+    int32_t iterations;
+    int32_t reason;                      /* O3DR_ICP_* */
+} o3dr_icp_result;
+#define O3DR_ICP_MAX_ITERATIONS 0
+#define O3DR_ICP_UNCHANGED      1
+#define O3DR_ICP_SMALL_STEP     2
+#define O3DR_ICP_TOO_FEW        3
+#define O3DR_ICP_DEGENERATE     4
+void o3dr_icp_default_params(o3dr_icp_params* p);
+/* idx_out / d2_out: n_query entries each, in `mem` */
+int  o3dr_nearest_neighbors(o3dr_ctx* ctx, const o3dr_point* query, int64_t n_query, const o3dr_point* target, int64_t n_target,
+                            double max_distance, uint32_t* idx_out, float* d2_out, int32_t mem);
+/* the target's search grid is built once per call; only the queries move between passes */
+int  o3dr_icp_align(o3dr_ctx* ctx, const o3dr_point* source, int64_t n_source, const o3dr_point* target, int64_t n_target,
+                    const float T_init[16], const o3dr_icp_params* p, o3dr_icp_result* res, int32_t mem);
+
 /* ---- measurement hooks (bench.py; not part of the reference surface) ------------------------ */
 /* kernel ids for o3dr_profile_* */
 #define O3DR_K_COUNT        0  /* grid-pass valid count per tile */

@@ -31,6 +31,19 @@ class ParamsStruct(C.Structure):
                 ("dont_downsample", C.c_int32), ("sor_enable", C.c_int32), ("blur_kernel", C.c_int32), ("disparity_f64", C.c_int32)]
 
 
+class IcpParamsStruct(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("max_correspondence_distance", C.c_double), ("transformation_epsilon", C.c_double)]
+
+
+class IcpResultStruct(C.Structure):
+    _fields_ = [("T", C.c_double * 16), ("fitness", C.c_double), ("n_correspondences", C.c_int64), ("iterations", C.c_int32),
+                ("reason", C.c_int32)]
+
+
+ICP_MAX_ITERATIONS, ICP_UNCHANGED, ICP_SMALL_STEP, ICP_TOO_FEW, ICP_DEGENERATE = range(5)
+ICP_REASONS = ["MAX_ITERATIONS", "UNCHANGED", "SMALL_STEP", "TOO_FEW", "DEGENERATE"]
+
+
 def lib_path():
     return _LIB
 
@@ -90,6 +103,9 @@ SYMBOLS = [
     ("o3dr_comm_destroy", C.c_int, [_vp]),
     ("o3dr_host_register", C.c_int, [_vp, _i64]),
     ("o3dr_host_unregister", C.c_int, [_vp]),
+    ("o3dr_icp_default_params", None, [C.POINTER(IcpParamsStruct)]),
+    ("o3dr_nearest_neighbors", C.c_int, [_vp, _vp, _i64, _vp, _i64, C.c_double, _vp, _vp, _i32]),
+    ("o3dr_icp_align", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, C.POINTER(IcpParamsStruct), C.POINTER(IcpResultStruct), _i32]),
     ("o3dr_profile_enable", C.c_int, [_vp, _i32, _i32]),
     ("o3dr_profile_read", C.c_int, [_vp, _i32, C.POINTER(C.c_double), _pi64]),
     ("o3dr_profile_reset", C.c_int, [_vp]),

@@ -36,6 +36,21 @@ class Params:
                               int(bool(self.disparity_f64)))
 
 
+@dataclass
+class IcpResult:
+    """o3dr_icp_align's result: T (float64 4x4, source -> target), the mean squared distance of the correspondences at
+    fp32(T) (pcl::Registration::getFitnessScore), their number, the solves applied and why the loop stopped (ICP_REASONS)."""
+    T: np.ndarray
+    fitness: float
+    n_correspondences: int
+    iterations: int
+    reason: int
+
+    @property
+    def reason_name(self):
+        return L.ICP_REASONS[self.reason]
+
+
 def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
@@ -251,6 +266,59 @@ class Context:
         n = C.c_int64(0)
         L.check(self._lib.o3dr_statistical_outlier_removal(self._h, pi, n_in, po, max(n_in, 1), C.byref(n), mem))
         return out[: n.value]
+
+    # -- alignment (pcl::IterativeClosestPoint, pose.cpp:46-112 / pose_functions.cpp:1634-1652) -----------------------
+    @staticmethod
+    def _cloud(pts):
+        if _is_torch(pts):
+            assert pts.is_contiguous() and tuple(pts.shape[1:]) == (4,) and pts.element_size() == 4
+            return pts, int(pts.shape[0])
+        pts = np.ascontiguousarray(pts, POINT)
+        return pts, int(pts.shape[0])
+
+    def nearestNeighbors(self, query, target, max_distance=float("inf")):
+        """Exact nearest neighbour of every query point in `target`: -> (idx uint32, d2 float32), the point minimising
+        (fp32 d2, original index); idx 0xFFFFFFFF / d2 inf where no target point lies within max_distance.  numpy POINT
+        arrays, or torch [N,4] 4-byte CUDA tensors (results are then CUDA tensors too)."""
+        query, nq = self._cloud(query)
+        target, nt = self._cloud(target)
+        pq, mem, _k = _ptr(query)
+        pt, mem2, _k2 = _ptr(target)
+        if nq and nt:
+            assert mem == mem2, "query and target must live in the same memory"
+        if _is_torch(query) and query.is_cuda:
+            import torch
+            idx = torch.empty(max(nq, 1), dtype=torch.int32, device=query.device)
+            d2 = torch.empty(max(nq, 1), dtype=torch.float32, device=query.device)
+            self._order_after_torch()
+            L.check(self._lib.o3dr_nearest_neighbors(self._h, pq, nq, pt, nt, float(max_distance), idx.data_ptr(), d2.data_ptr(),
+                                                     L.MEM_DEVICE))
+            return idx[:nq].view(torch.uint32) if hasattr(torch, "uint32") else idx[:nq], d2[:nq]
+        idx = np.empty(max(nq, 1), np.uint32)
+        d2 = np.empty(max(nq, 1), np.float32)
+        L.check(self._lib.o3dr_nearest_neighbors(self._h, pq, nq, pt, nt, float(max_distance), idx.ctypes.data, d2.ctypes.data, mem))
+        return idx[:nq], d2[:nq]
+
+    def icpAlign(self, source, target, T_init=None, max_iterations=10, max_correspondence_distance=float("inf"),
+                 transformation_epsilon=0.0):
+        """Point-to-point ICP of `source` onto `target` (contract: include/o3dr.h, DESIGN.md "ICP") -> IcpResult."""
+        source, ns = self._cloud(source)
+        target, nt = self._cloud(target)
+        ps_, mem, _k = _ptr(source)
+        pt, mem2, _k2 = _ptr(target)
+        if ns and nt:
+            assert mem == mem2, "source and target must live in the same memory"
+        elif ns == 0:
+            mem = mem2
+        Tn = None if T_init is None else self._T(T_init)
+        prm = L.IcpParamsStruct(int(max_iterations), float(max_correspondence_distance), float(transformation_epsilon))
+        res = L.IcpResultStruct()
+        if mem == L.MEM_DEVICE:
+            self._order_after_torch()
+        L.check(self._lib.o3dr_icp_align(self._h, ps_, ns, pt, nt, None if Tn is None else Tn.ctypes.data, C.byref(prm), C.byref(res),
+                                         mem))
+        return IcpResult(np.array(res.T[:], np.float64).reshape(4, 4), float(res.fitness), int(res.n_correspondences),
+                         int(res.iterations), int(res.reason))
 
     def voxelGrid(self, pts, leaf, min_points=0, z_offset=0.0, return_status=False):
         """pcl::VoxelGrid<PointXYZRGB> as the reference configures it (pose_functions.cpp:1689-1700)."""

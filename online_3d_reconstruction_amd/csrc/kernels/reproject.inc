@@ -581,6 +581,13 @@ __global__ __launch_bounds__(256) void k_keypoint_pass(ReprojectArgs a, const fl
 struct Mat34 {
     float m[12];
 };
+// the A2 arithmetic of one point; also the transform of the ICP queries (kernels/nn.inc), which must match it bit for bit
+__device__ __forceinline__ void a2_apply(const float* __restrict__ m, float x, float y, float z, float& X, float& Y, float& Z)
+{
+    X = ((m[0] * x + m[1] * y) + m[2] * z) + m[3];
+    Y = ((m[4] * x + m[5] * y) + m[6] * z) + m[7];
+    Z = ((m[8] * x + m[9] * y) + m[10] * z) + m[11];
+}
 __global__ __launch_bounds__(kPtThreads) void k_transform(const o3dr_point* __restrict__ in, int64_t n, Mat34 T,
                                                           o3dr_point* __restrict__ out)
 {
@@ -588,9 +595,7 @@ __global__ __launch_bounds__(kPtThreads) void k_transform(const o3dr_point* __re
     if (i >= n) return;
     const uint4 v = reinterpret_cast<const uint4*>(in)[i];
     const float x = __uint_as_float(v.x), y = __uint_as_float(v.y), z = __uint_as_float(v.z);
-    const float* m = T.m;
-    const float X = ((m[0] * x + m[1] * y) + m[2] * z) + m[3];
-    const float Y = ((m[4] * x + m[5] * y) + m[6] * z) + m[7];
-    const float Z = ((m[8] * x + m[9] * y) + m[10] * z) + m[11];
+    float X, Y, Z;
+    a2_apply(T.m, x, y, z, X, Y, Z);
     reinterpret_cast<uint4*>(out)[i] = make_uint4(__float_as_uint(X), __float_as_uint(Y), __float_as_uint(Z), v.w);
 }

@@ -10,14 +10,16 @@
 //   expansion, conservative stop (no unvisited column can hold a point closer than 0.999*r*h).
 //   Every kernel takes grid y = frame: a batch of clouds goes through one set of launches.
 // =================================================================================================
-// the search grid of one cloud (~kSorCellPoints points per column of cells, at most max_cells cells) and the sort plan of its
-// cell ids; one statement of it for k_sor_plan and for the one-workgroup path of small clouds (kernels/small.inc)
+// the search grid of one cloud (~cell_points points per column of cells, at most max_cells cells) and the sort plan of its
+// cell ids; one statement of it for k_sor_plan and for the one-workgroup path of small clouds (kernels/small.inc).
+// The grid is active for clouds of more than active_above points (SOR: kSorMeanK; the nearest-neighbour search: 0).
 __device__ __forceinline__ void sor_plan_of(const float mn[2], const float mx[2], uint32_t n, uint32_t max_cells, SorGeom& g_out,
-                                            VoxelGeom& v_out)
+                                            VoxelGeom& v_out, double cell_points = kSorCellPoints,
+                                            uint32_t active_above = (uint32_t)kSorMeanK)
 {
     SorGeom g;
     g.n = n;
-    g.active = g.n > (uint32_t)kSorMeanK ? 1u : 0u;  // fewer points: the reference reads past its list; pass through
+    g.active = g.n > active_above ? 1u : 0u;  // SOR: fewer points - the reference reads past its list; pass through
     g.mnx = mn[0];
     g.mny = mn[1];
     const float mxx = mx[0];
@@ -25,7 +27,7 @@ __device__ __forceinline__ void sor_plan_of(const float mn[2], const float mx[2]
     double ex = (double)mxx - (double)g.mnx, ey = (double)mxy - (double)g.mny;
     if (!(ex > 1e-9)) ex = 1e-9;
     if (!(ey > 1e-9)) ey = 1e-9;
-    double h = sqrt(kSorCellPoints * ex * ey / (double)(g.n ? g.n : 1u));  // ~kSorCellPoints points per column
+    double h = sqrt(cell_points * ex * ey / (double)(g.n ? g.n : 1u));  // ~cell_points points per column
     if (h < 1e-6) h = 1e-6;
     int64_t gx = (int64_t)(ex / h) + 1, gy = (int64_t)(ey / h) + 1;
     while (gx * gy > (int64_t)max_cells) {
@@ -56,7 +58,8 @@ __device__ __forceinline__ void sor_plan_of(const float mn[2], const float mx[2]
 
 __global__ __launch_bounds__(256) void k_sor_plan(const float* __restrict__ mm_all, int64_t mm_stride, int mm_used,
                                                   const uint32_t* __restrict__ n_dev, uint32_t max_cells,
-                                                  SorGeom* __restrict__ sg, VoxelGeom* __restrict__ geom)
+                                                  SorGeom* __restrict__ sg, VoxelGeom* __restrict__ geom, double cell_points,
+                                                  uint32_t active_above)
 {
     __shared__ float red[6 * 4];
     const int f = blockIdx.x;
@@ -82,7 +85,7 @@ __global__ __launch_bounds__(256) void k_sor_plan(const float* __restrict__ mm_a
     if (threadIdx.x != 0) return;
     const float mn2[2] = {fminf(fminf(red[0], red[6]), fminf(red[12], red[18])), fminf(fminf(red[1], red[7]), fminf(red[13], red[19]))};
     const float mx2[2] = {fmaxf(fmaxf(red[3], red[9]), fmaxf(red[15], red[21])), fmaxf(fmaxf(red[4], red[10]), fmaxf(red[16], red[22]))};
-    sor_plan_of(mn2, mx2, n_dev[f], max_cells, sg[f], geom[f]);
+    sor_plan_of(mn2, mx2, n_dev[f], max_cells, sg[f], geom[f], cell_points, active_above);
 }
 
 __device__ __forceinline__ int sor_cell(const SorGeom& g, float x, float y, int& cx, int& cy)
@@ -129,7 +132,8 @@ __global__ __launch_bounds__(256) void k_sor_cell_counts(const uint32_t* __restr
     if (i + 1 == (int64_t)g.n || k[i + 1] != key) atomicAdd(&cnt[key], (uint32_t)i + 1u);
 }
 
-// after the sort: coordinates in cell order (coalesced candidate reads)
+// after the sort: coordinates in cell order (coalesced candidate reads); w = the point's original index (its bit pattern:
+// the nearest-neighbour search reports it, SOR does not read it)
 __global__ __launch_bounds__(256) void k_sor_gather(const o3dr_point* __restrict__ in, int64_t in_fstride, const uint32_t* __restrict__ ids0,
                                                     const uint32_t* __restrict__ ids1, const SorGeom* __restrict__ sg,
                                                     const VoxelGeom* __restrict__ geom, int64_t cap, float4* __restrict__ sxyz)
@@ -142,7 +146,7 @@ __global__ __launch_bounds__(256) void k_sor_gather(const o3dr_point* __restrict
     const uint32_t* id = sorted_buf(geom[f], ids0, ids1) + (int64_t)f * cap;
     const uint32_t src = id[j];
     const uint4 v = reinterpret_cast<const uint4*>(in + (int64_t)f * in_fstride)[src < g.n ? src : 0u];
-    sxyz[(int64_t)f * cap + j] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), 0.f);
+    sxyz[(int64_t)f * cap + j] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(src));
 }
 
 // ---- exact 51-NN, one query per lane, ONE candidate stream per wave -------------------------------------------------

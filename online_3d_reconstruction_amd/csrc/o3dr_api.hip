@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -129,6 +130,9 @@ struct o3dr_ctx {
     int test_corrupt = 0;  // o3dr_test_corrupt_next_gather: consumed by the next voxel grid
     int test_fail_at = 0;  // o3dr_test_fail_at: the numbered step of the next o3dr_merge_partitioned fails on this rank
     int64_t xchg_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // o3dr_merge_partitioned_stats
+    // o3dr_nearest_neighbors / o3dr_icp_align: staged host clouds, the target grid's cell boxes + box, the per-call source
+    // arrays (indices of this and the previous pass, d2, the moment partials and their folded record)
+    DevBuf nn_q, nn_t, nn_cells, nn_src;
     int64_t place_ub = -1;   // o3dr_cloud_big_slice_counts_dev ran for a cloud of at most this many points and place_parts slices:
     int place_parts = 0;     // the (slice, tile) table in the workspace is what o3dr_cloud_big_place_slices moves by
     int test_hooks = 0;    // O3DR_TEST_HOOKS=1 at o3dr_ctx_create: the entry points of include/o3dr_testing.h act
@@ -469,7 +473,7 @@ extern "C" int o3dr_ctx_destroy(o3dr_ctx* c)
         dev_release(c->inc.cells[i]);
     }
     for (DevBuf* b : {&c->inc.box, &c->inc.scratch, &c->inc.tg, &c->inc.tmatch, &c->inc.flag, &c->inc.src, &c->inc.keep,
-                      &c->inc.partial, &c->inc.words, &c->inc.fb})
+                      &c->inc.partial, &c->inc.words, &c->inc.fb, &c->nn_q, &c->nn_t, &c->nn_cells, &c->nn_src})
         dev_release(*b);
     delete c;
     return O3DR_OK;
@@ -2835,6 +2839,285 @@ extern "C" int o3dr_test_sor_distances(o3dr_ctx* c, float* out, int64_t n)
     if (n == 0) return O3DR_OK;
     HIPCHK(hipMemcpyAsync(out, c->ws.sor_dist, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    return O3DR_OK;
+}
+
+// -------------------------------------------------------------------------------------------------
+// exact nearest neighbour and point-to-point ICP (kernels/nn.inc; DESIGN.md "ICP")
+// -------------------------------------------------------------------------------------------------
+extern "C" void o3dr_icp_default_params(o3dr_icp_params* p)
+{
+    if (!p) return;
+    p->max_iterations = 10;                     // pcl::Registration max_iterations_
+    p->max_correspondence_distance = HUGE_VAL;  // pcl::Registration corr_dist_threshold_: no limit
+    p->transformation_epsilon = 0.0;
+}
+
+// the target's search grid, built once per call: grid in ws.sor_* (which the SOR path rebuilds whenever it runs), the
+// cells' boxes and the target's box in c->nn_cells.  The sort workspace is reused: the exchange's pending slice table is gone.
+static int nn_target(o3dr_ctx* c, const o3dr_point* target, int64_t n, int mem, float** box6, float4** cell_lo, float4** cell_hi)
+{
+    c->place_ub = -1;
+    const void* t_d;
+    CHK(stage_in(c, c->nn_t, target, (size_t)n * sizeof(o3dr_point), mem, &t_d));
+    CHK(ws_ensure(c, 1, n, false));
+    CHK(sor_ensure(c, 1, n));
+    const size_t cell_bytes = align256(((size_t)c->ws.sor_max_cells + 1) * sizeof(float4));
+    CHK(dev_ensure(c, c->nn_cells, 2 * cell_bytes + 256));
+    char* base = (char*)c->nn_cells.p;
+    *cell_lo = (float4*)base;
+    *cell_hi = (float4*)(base + cell_bytes);
+    *box6 = (float*)(base + 2 * cell_bytes);
+    launch_set_counts(&c->prof, c->stream, c->ws.n_valid, (uint32_t)n, 1);
+    const int used = launch_points_minmax(&c->prof, c->stream, (const o3dr_point*)t_d, 0, c->ws.n_valid, 1, n, c->ws.mm_stride, c->ws.mm);
+    launch_nn_grid(&c->prof, c->stream, c->ws, (const o3dr_point*)t_d, n, used, *box6, *cell_lo, *cell_hi);
+    HIPCHK(hipGetLastError());
+    return O3DR_OK;
+}
+
+// per-call source arrays: idx of two passes, d2, kIcpRecord partials per workgroup, the folded record
+struct NnSrc {
+    uint32_t* idx[2];
+    float* d2;
+    double* partial;
+    double* rec;
+};
+static int nn_source(o3dr_ctx* c, int64_t n, NnSrc* o)
+{
+    const size_t b_idx = align256((size_t)n * 4), b_part = align256((size_t)kIcpRecord * (size_t)nn_partial_blocks(n) * 8);
+    CHK(dev_ensure(c, c->nn_src, 3 * b_idx + b_part + align256(kIcpRecord * 8)));
+    char* base = (char*)c->nn_src.p;
+    o->idx[0] = (uint32_t*)base;
+    o->idx[1] = (uint32_t*)(base + b_idx);
+    o->d2 = (float*)(base + 2 * b_idx);
+    o->partial = (double*)(base + 3 * b_idx);
+    o->rec = (double*)(base + 3 * b_idx + b_part);
+    return O3DR_OK;
+}
+
+static int nn_check_cloud(int64_t n, const void* p)
+{
+    if (n < 0 || (n > 0 && !p)) return fail(O3DR_ERR_INVALID_ARG, "bad arguments (cloud pointer / size)");
+    if (n > (int64_t)0xffffffffLL) return fail(O3DR_ERR_INVALID_ARG, "more than 2^32-1 points in one cloud");
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_nearest_neighbors(o3dr_ctx* c, const o3dr_point* query, int64_t n_query, const o3dr_point* target,
+                                      int64_t n_target, double max_distance, uint32_t* idx_out, float* d2_out, int32_t mem)
+{
+    if (mem == O3DR_MEM_HOST && n_query > 0 && n_query <= (int64_t)0xffffffffLL) {  // outputs zeroed first
+        if (idx_out) memset(idx_out, 0, (size_t)n_query * sizeof(uint32_t));
+        if (d2_out) memset(d2_out, 0, (size_t)n_query * sizeof(float));
+    }
+    CTX_ENTER(c);
+    CHK(nn_check_cloud(n_query, query));
+    CHK(nn_check_cloud(n_target, target));
+    if (n_query > 0 && (!idx_out || !d2_out)) return fail(O3DR_ERR_INVALID_ARG, "idx_out / d2_out is NULL");
+    if (!(max_distance >= 0.0)) return fail(O3DR_ERR_INVALID_ARG, "max_distance must be >= 0 (+inf: no limit)");
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    c->place_ub = -1;
+    if (n_query == 0) return O3DR_OK;
+    const float r2 = (float)(max_distance * max_distance);
+    NnSrc o;
+    CHK(nn_source(c, n_query, &o));
+    uint32_t* idx_d = mem == O3DR_MEM_DEVICE ? idx_out : o.idx[0];
+    float* d2_d = mem == O3DR_MEM_DEVICE ? d2_out : o.d2;
+    if (n_target == 0) {  // no target point: none found
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)idx_d, (int)0xFFFFFFFFu, (size_t)n_query, c->stream));
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)d2_d, (int)0x7f800000u, (size_t)n_query, c->stream));
+    } else {
+        float *box6;
+        float4 *lo, *hi;
+        CHK(nn_target(c, target, n_target, mem, &box6, &lo, &hi));
+        const void* q_d;
+        CHK(stage_in(c, c->nn_q, query, (size_t)n_query * sizeof(o3dr_point), mem, &q_d));
+        launch_nn_query(&c->prof, c->stream, c->ws, (const o3dr_point*)q_d, n_query, nullptr, box6, lo, hi, r2, idx_d, d2_d, nullptr,
+                        nullptr, nullptr, nullptr);
+        HIPCHK(hipGetLastError());
+    }
+    if (mem == O3DR_MEM_HOST) {
+        HIPCHK(hipMemcpyAsync(idx_out, idx_d, (size_t)n_query * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(d2_out, d2_d, (size_t)n_query * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return O3DR_OK;
+}
+
+// ---- the rigid solve (fp64, host): Kabsch / Umeyama without scale ----------------------------------
+// one-sided Jacobi SVD of a 3x3 matrix: A = U diag(S) V^T, S descending; U's first two columns (the third is not needed)
+static void svd3(const double A_in[3][3], double U[3][3], double S[3], double V[3][3])
+{
+    double A[3][3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) A[i][j] = A_in[i][j], V[i][j] = i == j ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < 64; ++sweep) {
+        bool rotated = false;
+        for (int p = 0; p < 2; ++p)
+            for (int q = p + 1; q < 3; ++q) {
+                double alpha = 0.0, beta = 0.0, gamma = 0.0;
+                for (int i = 0; i < 3; ++i) {
+                    alpha += A[i][p] * A[i][p];
+                    beta += A[i][q] * A[i][q];
+                    gamma += A[i][p] * A[i][q];
+                }
+                if (!(std::fabs(gamma) > 1e-15 * std::sqrt(alpha * beta))) continue;
+                rotated = true;
+                const double zeta = (beta - alpha) / (2.0 * gamma);
+                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (std::fabs(zeta) + std::sqrt(1.0 + zeta * zeta));
+                const double cs = 1.0 / std::sqrt(1.0 + t * t), sn = cs * t;
+                for (int i = 0; i < 3; ++i) {
+                    const double ap = A[i][p], aq = A[i][q];
+                    A[i][p] = cs * ap - sn * aq;
+                    A[i][q] = sn * ap + cs * aq;
+                    const double vp = V[i][p], vq = V[i][q];
+                    V[i][p] = cs * vp - sn * vq;
+                    V[i][q] = sn * vp + cs * vq;
+                }
+            }
+        if (!rotated) break;
+    }
+    int order[3] = {0, 1, 2};
+    double nrm[3];
+    for (int j = 0; j < 3; ++j) nrm[j] = std::sqrt(A[0][j] * A[0][j] + A[1][j] * A[1][j] + A[2][j] * A[2][j]);
+    std::sort(order, order + 3, [&](int a, int b) { return nrm[a] > nrm[b]; });
+    double Vs[3][3];
+    for (int k = 0; k < 3; ++k) {
+        const int j = order[k];
+        S[k] = nrm[j];
+        for (int i = 0; i < 3; ++i) {
+            Vs[i][k] = V[i][j];
+            U[i][k] = nrm[j] > 0.0 ? A[i][j] / nrm[j] : 0.0;
+        }
+    }
+    for (int i = 0; i < 3; ++i)
+        for (int k = 0; k < 3; ++k) V[i][k] = Vs[i][k];
+}
+
+// dT (row-major 4x4) from the folded record of one pass (moments about c0): R = V diag(1, 1, d) U^T, t = mu_b - R mu_a
+// (pcl::registration::TransformationEstimationSVD with the reflection corrected); false: cross-covariance of rank < 2
+static bool icp_solve(const double* rec, const double c0[3], double dT[16])
+{
+    const double n = rec[0];
+    double ma[3], mb[3], H[3][3];
+    for (int k = 0; k < 3; ++k) ma[k] = rec[1 + k] / n, mb[k] = rec[4 + k] / n;
+    for (int j = 0; j < 3; ++j)
+        for (int k = 0; k < 3; ++k) H[j][k] = rec[7 + 3 * j + k] - n * ma[j] * mb[k];
+    double U[3][3], S[3], V[3][3];
+    svd3(H, U, S, V);
+    if (!(S[0] > 0.0) || !std::isfinite(S[0]) || !(S[1] > 1e-12 * S[0])) return false;
+    // U's third column as u1 x u2 (det U = +1): then d = det(V) gives the proper rotation
+    U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1];
+    U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];
+    U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
+    const double detV = V[0][0] * (V[1][1] * V[2][2] - V[1][2] * V[2][1]) - V[0][1] * (V[1][0] * V[2][2] - V[1][2] * V[2][0]) +
+                        V[0][2] * (V[1][0] * V[2][1] - V[1][1] * V[2][0]);
+    const double d[3] = {1.0, 1.0, detV < 0.0 ? -1.0 : 1.0};
+    double R[3][3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) R[i][j] = V[i][0] * d[0] * U[j][0] + V[i][1] * d[1] * U[j][1] + V[i][2] * d[2] * U[j][2];
+    for (int i = 0; i < 3; ++i) {
+        double t = c0[i] + mb[i];
+        for (int j = 0; j < 3; ++j) t -= R[i][j] * (c0[j] + ma[j]);
+        for (int j = 0; j < 3; ++j) dT[4 * i + j] = R[i][j];
+        dT[4 * i + 3] = t;
+    }
+    dT[12] = dT[13] = dT[14] = 0.0;
+    dT[15] = 1.0;
+    return std::isfinite(dT[3]) && std::isfinite(dT[7]) && std::isfinite(dT[11]);
+}
+
+extern "C" int o3dr_icp_align(o3dr_ctx* c, const o3dr_point* source, int64_t n_source, const o3dr_point* target, int64_t n_target,
+                              const float T_init[16], const o3dr_icp_params* p, o3dr_icp_result* res, int32_t mem)
+{
+    if (res) memset(res, 0, sizeof *res);
+    CTX_ENTER(c);
+    if (!res) return fail(O3DR_ERR_INVALID_ARG, "res is NULL");
+    CHK(nn_check_cloud(n_source, source));
+    CHK(nn_check_cloud(n_target, target));
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    o3dr_icp_params prm;
+    o3dr_icp_default_params(&prm);
+    if (p) prm = *p;
+    if (prm.max_iterations < 0 || !(prm.max_correspondence_distance >= 0.0) || !(prm.transformation_epsilon >= 0.0))
+        return fail(O3DR_ERR_INVALID_ARG, "bad parameters (max_iterations >= 0, max_correspondence_distance >= 0, transformation_epsilon >= 0)");
+    c->place_ub = -1;
+    double T[16];
+    for (int k = 0; k < 16; ++k) T[k] = T_init ? (double)T_init[k] : (k % 5 == 0 ? 1.0 : 0.0);
+    for (int k = 0; k < 16; ++k) res->T[k] = T[k];
+    res->fitness = DBL_MAX;  // pcl::Registration::getFitnessScore without correspondences
+    res->reason = O3DR_ICP_TOO_FEW;
+    if (n_source == 0 || n_target == 0) return O3DR_OK;
+
+    float *box6;
+    float4 *lo, *hi;
+    CHK(nn_target(c, target, n_target, mem, &box6, &lo, &hi));
+    const void* s_d;
+    CHK(stage_in(c, c->nn_q, source, (size_t)n_source * sizeof(o3dr_point), mem, &s_d));
+    NnSrc o;
+    CHK(nn_source(c, n_source, &o));
+    float box_h[6];
+    HIPCHK(hipMemcpyAsync(box_h, box6, sizeof box_h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const double c0[3] = {((double)box_h[0] + (double)box_h[3]) * 0.5, ((double)box_h[1] + (double)box_h[4]) * 0.5,
+                          ((double)box_h[2] + (double)box_h[5]) * 0.5};
+    const float r2 = (float)(prm.max_correspondence_distance * prm.max_correspondence_distance);
+    double rec[kIcpRecord];
+    int cur = 0, passes = 0;
+    // one pass at fp32(T): A2 of the original source, nearest neighbours, the record of the moments
+    auto pass = [&](bool compare) -> int {
+        float Tf[12];
+        for (int k = 0; k < 12; ++k) Tf[k] = (float)T[k];
+        launch_nn_query(&c->prof, c->stream, c->ws, (const o3dr_point*)s_d, n_source, Tf, box6, lo, hi, r2, o.idx[cur], nullptr,
+                        compare ? o.idx[cur ^ 1] : nullptr, c0, o.partial, o.rec);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(rec, o.rec, sizeof rec, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        cur ^= 1;
+        ++passes;
+        return O3DR_OK;
+    };
+    int iterations = 0, reason = O3DR_ICP_MAX_ITERATIONS;
+    bool rec_at_T = false;  // rec describes a pass at fp32 of the current T
+    for (;;) {
+        if (iterations >= prm.max_iterations) {
+            reason = O3DR_ICP_MAX_ITERATIONS;
+            break;
+        }
+        CHK(pass(passes > 0));
+        rec_at_T = true;
+        if (passes > 1 && rec[17] == 0.0) {
+            reason = O3DR_ICP_UNCHANGED;
+            break;
+        }
+        if (rec[0] < 3.0) {
+            reason = O3DR_ICP_TOO_FEW;
+            break;
+        }
+        double dT[16];
+        if (!icp_solve(rec, c0, dT)) {
+            reason = O3DR_ICP_DEGENERATE;
+            break;
+        }
+        double Tn[16];
+        for (int i = 0; i < 4; ++i)
+            for (int j = 0; j < 4; ++j)
+                Tn[4 * i + j] = dT[4 * i] * T[j] + dT[4 * i + 1] * T[4 + j] + dT[4 * i + 2] * T[8 + j] + dT[4 * i + 3] * T[12 + j];
+        for (int k = 0; k < 16; ++k) T[k] = Tn[k];
+        rec_at_T = false;
+        ++iterations;
+        double step = 0.0;
+        for (int k = 0; k < 12; ++k) step = std::max(step, std::fabs(dT[k] - (k % 5 == 0 ? 1.0 : 0.0)));
+        if (step <= prm.transformation_epsilon) {
+            reason = O3DR_ICP_SMALL_STEP;
+            break;
+        }
+    }
+    if (!rec_at_T) CHK(pass(false));  // fitness at T_out
+    for (int k = 0; k < 16; ++k) res->T[k] = T[k];
+    res->n_correspondences = (int64_t)rec[0];
+    res->fitness = rec[0] > 0.0 ? rec[16] / rec[0] : DBL_MAX;
+    res->iterations = iterations;
+    res->reason = reason;
     return O3DR_OK;
 }
 

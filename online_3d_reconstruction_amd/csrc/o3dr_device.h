@@ -279,6 +279,22 @@ void launch_bbox(Profiler* pf, hipStream_t s, const float* mm, int used, float* 
 int launch_sor(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_point* in, int64_t in_fstride, const uint32_t* n_dev,
                int frames, int64_t cap, int mm_used, double stddev_mul, o3dr_point* out, int64_t out_fstride,
                uint32_t* n_out_dev);
+// the search grid of `frames` clouds (plan with ~cell_points points per column, active above active_above points, cell ids,
+// radix sort, populations -> ws.sor_cell_first, points in cell order with their original index in .w -> ws.sor_xyz);
+// bounding boxes in ws.mm slots [0, mm_used) of every frame.  Part of launch_sor; the nearest-neighbour target grid too.
+void launch_search_grid(Workspace& ws, hipStream_t s, const o3dr_point* in, int64_t in_fstride, const uint32_t* n_dev, int frames,
+                        int64_t cap, int mm_used, double cell_points, uint32_t active_above);
+// exact nearest neighbour (kernels/nn.inc).  launch_nn_grid: the target's grid (n points, also in ws.n_valid[0]; bounding-box
+// slots ws.mm [0, mm_used)) in ws.sor_*, its box -> box6 (device, 6 floats), the cells' boxes -> cell_lo / cell_hi
+// (ws.sor_max_cells + 1 each).  launch_nn_query: idx (+ d2) of n queries (T12 != nullptr: each query is A2(T12, point) first);
+// partial != nullptr: the ICP epilogue (changed against idx_prev, moments about c0) and its fold into rec[kIcpRecord]
+constexpr int kIcpRecord = 18;  // count, sum a (3), sum b (3), sum a b^T (9, row-major), sum d2, changed queries
+void launch_nn_grid(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_point* target, int64_t n, int mm_used, float* box6,
+                    float4* cell_lo, float4* cell_hi);
+void launch_nn_query(Profiler* pf, hipStream_t s, const Workspace& ws, const o3dr_point* query, int64_t n, const float* T12,
+                     const float* box6, const float4* cell_lo, const float4* cell_hi, float r2, uint32_t* idx_out, float* d2_out,
+                     const uint32_t* idx_prev, const double c0[3], double* partial, double* rec);
+inline int64_t nn_partial_blocks(int64_t n) { return (n + 255) / 256; }  // workgroups of launch_nn_query (kNnThreads queries each)
 void launch_partition(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelArgs& v, int n_parts, o3dr_point* out,
                       uint64_t* counts_dev, uint32_t* overflow_dev, const void* hdrs_dev = nullptr, int n_hdrs = 0);
 // its two halves: slice sizes without moving anything (the (part, tile) table stays in ws for the second half), then the move

@@ -26,6 +26,7 @@
 //   sor          statistical outlier removal
 //   small        clouds of at most kSmallMax points: the whole path in one launch of one workgroup
 //   incremental  the combined merge kept as running per-cell sums (o3dr_finalize_incremental)
+//   nn           exact nearest neighbour into a target's search grid, the fused ICP pass and its fold
 // The launchers follow in this file.
 #include <string.h>
 
@@ -45,6 +46,7 @@ namespace o3dr {
 #include "kernels/multigpu.inc"
 #include "kernels/sor.inc"
 #include "kernels/small.inc"
+#include "kernels/nn.inc"
 
 // =================================================================================================
 // launchers
@@ -619,19 +621,16 @@ void launch_partition(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelArg
     launch_partition_move(pf, s, ws, v, n_parts, out, nullptr);
 }
 
-// Statistical outlier removal of a batch of clouds (see o3dr_device.h).  ws.sor_* are laid out for ws.sor_cap points
-// per frame; cap (<= ws.sor_cap) sizes the grids.
-int launch_sor(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_point* in, int64_t in_fstride, const uint32_t* n_dev,
-               int frames, int64_t cap, int mm_used, double stddev_mul, o3dr_point* out, int64_t out_fstride,
-               uint32_t* n_out_dev)
+// The search grid of a batch of clouds (see o3dr_device.h): plan, cell ids, radix sort of the cell ids, cell populations,
+// points gathered into cell order.  SOR and the nearest-neighbour search (kernels/nn.inc) both build theirs here.
+void launch_search_grid(Workspace& ws, hipStream_t s, const o3dr_point* in, int64_t in_fstride, const uint32_t* n_dev, int frames,
+                        int64_t cap, int mm_used, double cell_points, uint32_t active_above)
 {
-    ProfScope ps(pf, O3DR_K_OTHER, s);
     const int F = frames;
     const int n_sort_tiles = cdiv64(cap, kSortTile);
     const int64_t hist_row = (int64_t)kMaxRadix * n_sort_tiles;
     const size_t tm_lds = (size_t)n_sort_tiles * (kMaxRadix + 1) * sizeof(uint32_t);
     const int tm = tm_lds <= 48 * 1024 ? 1 : 0;
-    const int n_tiles = cdiv64(cap, 1024);
     const int64_t cell_stride = (int64_t)ws.sor_max_cells + 1;
     // The search grid never has more cells than points / 2 (and at least 1024): the cell ids of clouds of at most `cap`
     // points need ceil(log2(max_cells) / 7) sort passes, and only those are launched (a --jump_pixels 15 frame: 2 instead of
@@ -641,7 +640,7 @@ int launch_sor(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_point* in,
     int cell_bits = 1;
     while ((1u << cell_bits) < max_cells) ++cell_bits;
     const int sort_passes = (cell_bits + kMaxRadixBits - 1) / kMaxRadixBits;
-    k_sor_plan<<<F, 256, 0, s>>>(ws.mm, ws.mm_stride, mm_used, n_dev, max_cells, ws.sor_geom, ws.geom);
+    k_sor_plan<<<F, 256, 0, s>>>(ws.mm, ws.mm_stride, mm_used, n_dev, max_cells, ws.sor_geom, ws.geom, cell_points, active_above);
     (void)hipMemsetAsync(ws.sor_cell_first, 0, (size_t)F * (size_t)cell_stride * 4, s);
     k_sor_cells<<<dim3(cdiv64(cap, 256), F), 256, 0, s>>>(in, in_fstride, ws.sor_geom, cap, ws.keys[0]);
     for (int pass = 0; pass < sort_passes && pass < kMaxPasses; ++pass) {
@@ -657,6 +656,19 @@ int launch_sor(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_point* in,
     k_sor_cell_counts<<<dim3(cdiv64(cap, 256), F), 256, 0, s>>>(ws.keys[0], ws.keys[1], ws.geom, ws.sor_geom, cap, cell_stride, ws.sor_cell_first);
     launch_scan(s, ws.sor_cell_first, cell_stride, cell_stride, F, nullptr, nullptr, ws.scan_partial);
     k_sor_gather<<<dim3(cdiv64(cap, 256), F), 256, 0, s>>>(in, in_fstride, ws.vals[0], ws.vals[1], ws.sor_geom, ws.geom, cap, ws.sor_xyz);
+}
+
+// Statistical outlier removal of a batch of clouds (see o3dr_device.h).  ws.sor_* are laid out for ws.sor_cap points
+// per frame; cap (<= ws.sor_cap) sizes the grids.
+int launch_sor(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_point* in, int64_t in_fstride, const uint32_t* n_dev,
+               int frames, int64_t cap, int mm_used, double stddev_mul, o3dr_point* out, int64_t out_fstride,
+               uint32_t* n_out_dev)
+{
+    ProfScope ps(pf, O3DR_K_OTHER, s);
+    const int F = frames;
+    const int n_tiles = cdiv64(cap, 1024);
+    const int64_t cell_stride = (int64_t)ws.sor_max_cells + 1;
+    launch_search_grid(ws, s, in, in_fstride, n_dev, F, cap, mm_used, kSorCellPoints, (uint32_t)kSorMeanK);
     (void)hipMemsetAsync(ws.sor_left_cnt, 0, (size_t)F * 4, s);
     k_sor_knn<<<dim3(cdiv64(cap, kWave), F), kWave, 0, s>>>(ws.sor_xyz, ws.vals[0], ws.vals[1], ws.geom, ws.sor_cell_first, cell_stride,
                                                            ws.sor_geom, cap, ws.sor_dist, ws.sor_left, ws.sor_left_cnt);
@@ -676,6 +688,48 @@ int launch_sor(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_point* in,
     k_sor_emit<<<dim3(n_tiles, F), 256, 0, s>>>(in, in_fstride, ws.sor_dist, cap, ws.sor_geom, n_tiles, ws.tile_cnt, out, out_fstride,
                                                 ws.mm_stride, ws.mm);
     return n_tiles;
+}
+
+// Nearest neighbour (kernels/nn.inc).  launch_nn_grid: the target's search grid in ws.sor_* (its n points counted in
+// ws.n_valid[0], its bounding-box slots in ws.mm [0, mm_used)), the folded box -> box6 and the cells' exact boxes.
+void launch_nn_grid(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_point* target, int64_t n, int mm_used, float* box6,
+                    float4* cell_lo, float4* cell_hi)
+{
+    ProfScope ps(pf, O3DR_K_OTHER, s);
+    k_bbox_fold<<<1, 256, 0, s>>>(ws.mm, mm_used, box6);
+    launch_search_grid(ws, s, target, 0, ws.n_valid, 1, n, mm_used, kNnCellPoints, 0u);
+    int cg = cdiv64((int64_t)ws.sor_max_cells, 256);
+    if (cg > 4096) cg = 4096;
+    k_nn_cell_box<<<cg, 256, 0, s>>>(ws.sor_xyz, ws.sor_cell_first, ws.sor_geom, cell_lo, cell_hi);
+}
+
+void launch_nn_query(Profiler* pf, hipStream_t s, const Workspace& ws, const o3dr_point* query, int64_t n, const float* T12,
+                     const float* box6, const float4* cell_lo, const float4* cell_hi, float r2, uint32_t* idx_out, float* d2_out,
+                     const uint32_t* idx_prev, const double c0[3], double* partial, double* rec)
+{
+    if (n <= 0) return;
+    ProfScope ps(pf, O3DR_K_OTHER, s);
+    NnArgs a;
+    memset(&a, 0, sizeof a);
+    a.query = query;
+    a.n = (uint32_t)n;
+    a.xf = T12 ? 1 : 0;
+    for (int k = 0; k < 12; ++k) a.T.m[k] = T12 ? T12[k] : 0.f;
+    a.txyz = ws.sor_xyz;
+    a.cell_first = ws.sor_cell_first;
+    a.cell_lo = cell_lo;
+    a.cell_hi = cell_hi;
+    a.sg = ws.sor_geom;
+    a.box6 = box6;
+    a.r2 = r2;
+    a.idx_out = idx_out;
+    a.d2_out = d2_out;
+    a.idx_prev = idx_prev;
+    for (int k = 0; k < 3; ++k) a.c0[k] = c0 ? c0[k] : 0.0;
+    a.partial = partial;
+    a.n_blocks = (uint32_t)cdiv64(n, kNnThreads);
+    k_nn_query<<<a.n_blocks, kNnThreads, 0, s>>>(a);
+    if (partial) k_icp_fold<<<kIcpFields, kIcpFoldThreads, 0, s>>>(partial, a.n_blocks, rec);
 }
 
 }  // namespace o3dr

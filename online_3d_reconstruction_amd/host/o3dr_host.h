@@ -5,10 +5,12 @@
 // hot path that the CLI needs to run end to end (flag parsing, calibration/pose/time CSV readers,
 // timestamp binding, generateTmat, the variance gate, PNG/PLY I/O) is restated here in plain C++:
 // it is control plane, one call per frame or per run, and stays on the host.  Pose estimation (ORB,
-// matching, ICP), visualisation and the mesh/segment tools are not part of this build; the CLI runs
-// with the recorded MAVLink poses (the reference's --only_MAVLink mode, pose_functions.cpp:232-236).
+// matching, the ICP trajectory correction), visualisation and the mesh/segment tools are not part of
+// this build; the CLI runs with the recorded MAVLink poses (the reference's --only_MAVLink mode,
+// pose_functions.cpp:232-236).  The --align_point_cloud tool (ICP on two PLYs) runs on o3dr_icp_align.
 #pragma once
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <fstream>
 #include <memory>
@@ -83,7 +85,10 @@ public:
     std::string calib_file = "cam13calib.yml";
     std::string dataFilesPrefix = "data_files/", imagePrefix = "images/", disparityPrefix = "disparities/";
     std::string outputPrefix = "output/";
-    std::string read_PLY_filename0;
+    std::string read_PLY_filename0, read_PLY_filename1;
+    bool align_point_cloud = false;  // --align_point_cloud source.ply target.ply (pose.cpp:46-112): ICP through o3dr_icp_align
+    int icp_max_iterations = 10;     // --icp_max_iterations (pcl::Registration defaults)
+    double icp_max_corr_dist = HUGE_VAL, icp_transformation_epsilon = 0.0;  // --icp_max_corr_dist, --icp_transformation_epsilon
     int device_id = 0;
     int n_gpus = 1;                 // --gpus N: frames sharded over devices device_id .. device_id+N-1, one host thread and
                                     // one context each, merged through o3dr_merge_partitioned (RCCL)
@@ -119,6 +124,7 @@ private:
     void push_params(o3dr_ctx* c);
     void run_reconstruction();
     void run_sharded(PointCloud::Ptr cloud_small);  // --gpus N
+    void run_align_point_cloud();                   // --align_point_cloud
     int first_img_num = -1, last_img_num = -1;
     bool run3d_reconstruction = true;
     std::vector<std::vector<double>> pose_data, images_times_data;

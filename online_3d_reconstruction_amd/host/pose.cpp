@@ -395,7 +395,12 @@ void Pose::printUsage()
             "--sor defaults to 1: like the reference, every per-frame cloud goes through StatisticalOutlierRemoval(50, 1.0)\n"
             "before its voxel grid when jump_pixels > 0.\n"
             "./pose --downsample file.ply [--voxel_size m] [--min_points_per_voxel n]\n"
-            "Pose estimation (ORB matching, ICP), visualisation and the mesh/segment tools are not part of this build.\n";
+            "./pose --align_point_cloud source.ply target.ply [--icp_max_iterations n] [--icp_max_corr_dist m]\n"
+            "       [--icp_transformation_epsilon e]   (point-to-point ICP of source onto target: prints T, fitness, correspondences,\n"
+            "                     iterations and the reason it stopped; writes the source moved by T as aligned_<source> next to\n"
+            "                     it - that file name is this build's own)\n"
+            "Pose estimation (ORB matching, the ICP trajectory correction), visualisation and the mesh/segment tools are not\n"
+            "part of this build.\n";
 }
 
 int Pose::parseCmdArgs(int argc, char** argv)
@@ -413,6 +418,17 @@ int Pose::parseCmdArgs(int argc, char** argv)
         const string a = argv[i];
         if (a == "--help" || a == "/?") { printUsage(); return -1; }
         else if (a == "--downsample") { downsample = true; run3d_reconstruction = false; read_PLY_filename0 = need(i); }
+        else if (a == "--align_point_cloud") {
+            if (i + 2 >= argc || string(argv[i + 1]).rfind("--", 0) == 0 || string(argv[i + 2]).rfind("--", 0) == 0)
+                throw runtime_error("missing argument: --align_point_cloud needs source.ply and target.ply");
+            align_point_cloud = true;
+            run3d_reconstruction = false;
+            read_PLY_filename0 = argv[++i];
+            read_PLY_filename1 = argv[++i];
+        }
+        else if (a == "--icp_max_iterations") icp_max_iterations = atoi(need(i));
+        else if (a == "--icp_max_corr_dist") icp_max_corr_dist = atof(need(i));
+        else if (a == "--icp_transformation_epsilon") icp_transformation_epsilon = atof(need(i));
         else if (a == "--voxel_size") voxel_size = atof(need(i));
         else if (a == "--min_points_per_voxel") min_points_per_voxel = (unsigned)atoi(need(i));
         else if (a == "--jump_pixels") jump_pixels = atoi(need(i));
@@ -455,6 +471,45 @@ int Pose::parseCmdArgs(int argc, char** argv)
     return 0;
 }
 
+// pose.cpp:46-112: pcl::IterativeClosestPoint of source onto target, here o3dr_icp_align (contract: include/o3dr.h).  The
+// result is printed and the source, moved by fp32(T) through transformPtCloud, is written as aligned_<source> next to it.
+void Pose::run_align_point_cloud()
+{
+    Q = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // the tool needs no camera
+    PointCloud::Ptr src = read_PLY_File(read_PLY_filename0);
+    PointCloud::Ptr tgt = read_PLY_File(read_PLY_filename1);
+    o3dr_icp_params prm;
+    o3dr_icp_default_params(&prm);
+    prm.max_iterations = icp_max_iterations;
+    prm.max_correspondence_distance = icp_max_corr_dist;
+    prm.transformation_epsilon = icp_transformation_epsilon;
+    o3dr_icp_result res;
+    chk(o3dr_icp_align(ctx_for_this_thread(), src->points.data(), (int64_t)src->points.size(), tgt->points.data(),
+                       (int64_t)tgt->points.size(), nullptr, &prm, &res, O3DR_MEM_HOST),
+        "o3dr_icp_align");
+    static const char* kReason[] = {"MAX_ITERATIONS", "UNCHANGED", "SMALL_STEP", "TOO_FEW", "DEGENERATE"};
+    char line[256];
+    cout << "ICP transformation (source -> target):" << endl;
+    for (int r = 0; r < 4; ++r) {
+        snprintf(line, sizeof line, "%.17g %.17g %.17g %.17g", res.T[4 * r], res.T[4 * r + 1], res.T[4 * r + 2], res.T[4 * r + 3]);
+        cout << line << endl;
+    }
+    snprintf(line, sizeof line, "fitness %.17g", res.fitness);
+    cout << line << endl;
+    cout << "correspondences " << res.n_correspondences << endl;
+    cout << "iterations " << res.iterations << endl;
+    cout << "reason " << (res.reason >= 0 && res.reason < 5 ? kReason[res.reason] : "?") << endl;
+    Matrix4 Tf;
+    for (int k = 0; k < 16; ++k) Tf[k] = (float)res.T[k];
+    PointCloud::Ptr aligned(new PointCloud());
+    if (!src->points.empty()) transformPtCloud(src, aligned, Tf);
+    string out = read_PLY_filename0;
+    const size_t slash = out.find_last_of('/');
+    out = (slash == string::npos ? string() : out.substr(0, slash + 1)) + "aligned_" +
+          (slash == string::npos ? out : out.substr(slash + 1));
+    save_pt_cloud_to_PLY_File(aligned, out);
+}
+
 // pose.cpp:23-565 restricted to the hot path
 Pose::Pose(int argc, char* argv[])
 {
@@ -469,6 +524,10 @@ Pose::Pose(int argc, char* argv[])
         out = (slash == string::npos ? string() : out.substr(0, slash + 1)) + "downsampled_" +
               (slash == string::npos ? out : out.substr(slash + 1));
         save_pt_cloud_to_PLY_File(small, out);
+        return;
+    }
+    if (align_point_cloud) {
+        run_align_point_cloud();
         return;
     }
     if (!run3d_reconstruction) return;
