@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import assert_points_equal, random_cloud
+from merge_reference import downsample_pt_cloud
 
 NEW_SYMBOLS = ("o3dr_finalize_incremental", "o3dr_finalize_incremental_stats")
 
@@ -343,6 +344,10 @@ def test_full_size_two_steps_of_200_dense_720p_frames():
         assert s["from_empty"] == 0 and s["fallback"] == 0
         assert_points_equal(got, _points(ctx.finalize(device="cuda")), "400 frames")
         assert s["state_bytes"] <= 80 * s["cells"], s
+        ctx.synchronize()
+        ref = downsample_pt_cloud(ctx.cloudBigView(), 0.05, True, 1)  # torch restatement, none of libo3dr's kernels
+        assert ref.status == 0
+        assert_points_equal(got, ref.points, "400 frames against the torch reference")
 
 
 @pytest.mark.gpu

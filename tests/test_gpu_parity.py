@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import merge_reference as mr
 from conftest import GOLDEN, assert_points_equal, random_cloud
 
 pytestmark = pytest.mark.gpu
@@ -194,6 +195,9 @@ def test_A3a_within_tolerance_of_reference_sort_order(ctx, orc):
 # 2^-7 m, and ANY two summation orders differ by a random walk of such roundings.  Measured here (stable vs std::sort,
 # 229 points per cell, 9600 cells): max |dz| 4.9e-4 m, mean 1.0e-4 m; x / y (sums of ~1e3) below 1e-5 m.
 A5_Z_BOUND_M = 1e-3
+# the same statement at the headline's density against the exactly rounded mean: measured max |z - z_exact|
+# 2.3e-3 m in the canonical order and 1.9e-3 m in std::sort's, above A5_Z_BOUND_M for BOTH orders
+FULL_SIZE_Z_BOUND_M = 3e-3
 
 
 def test_A5_combined_mode_against_reference_sort_order(ctx, orc):
@@ -215,6 +219,20 @@ def test_A5_combined_mode_against_reference_sort_order(ctx, orc):
     dz = np.abs(got["z"].astype(np.float64) - ref["z"])
     assert dz.max() <= A5_Z_BOUND_M, dz.max()
     assert dz.max() > TOL_M  # (the point of the test: the reference's own result is not defined to 1e-4 m here)
+    # both summation orders against the exactly rounded mean (tests/merge_reference.py, on the GPU): each inside the
+    # order-independent bound in every cell, and the same error distribution - the canonical order is no worse than PCL's
+    exact = mr.downsample_pt_cloud(pts, 0.05, True, 1, device="cuda")
+    assert_points_equal(got, exact.points, "combined merge, torch reference")
+    bound = mr.error_bound(exact)
+    for k, ax in enumerate("xyz"):
+        e_gpu = np.abs(got[ax].astype(np.float64) - exact.exact[:, k])
+        e_std = np.abs(ref[ax].astype(np.float64) - exact.exact[:, k])
+        assert np.all(e_gpu <= bound[:, k]) and np.all(e_std <= bound[:, k]), ax
+        print(f"A5 |{ax} - exact|: GPU max {e_gpu.max():.3g} mean {e_gpu.mean():.3g} p99 {np.percentile(e_gpu, 99):.3g}; "
+              f"std::sort max {e_std.max():.3g} mean {e_std.mean():.3g} p99 {np.percentile(e_std, 99):.3g} m")
+        assert 0.8 <= e_gpu.mean() / e_std.mean() <= 1.25, ax
+        for a, b in ((np.percentile(e_gpu, 99), np.percentile(e_std, 99)), (e_gpu.max(), e_std.max())):
+            assert max(a / b, b / a) <= 1.5, (ax, a, b)
 
 
 # ---- A6 ------------------------------------------------------------------------------------------
@@ -509,6 +527,17 @@ def test_full_size_configs1_200_dense_frames_against_the_oracle(ctx, orc):
     assert len(again) == len(small) and np.array_equal(again["rgba"], small["rgba"])
     assert small["x"].min() >= big["x"].min() and small["x"].max() <= big["x"].max()
     assert np.abs(small["z"]).max() < 30
+    # against the exactly rounded mean: every cell inside the order-independent bound; z within what fp32 sums at +500 m
+    # allow at this density (~217 points per cell, up to a few thousand; the oracle's std::sort order measures 1.9e-3 m)
+    ctx.synchronize()
+    exact = mr.downsample_pt_cloud(ctx.cloudBigView(), 0.05, True, 1)
+    assert_points_equal(small, exact.points, "merged cloud of 200 dense frames, torch reference")
+    bound = mr.error_bound(exact)
+    for k, ax in enumerate("xyz"):
+        e = np.abs(small[ax].astype(np.float64) - exact.exact[:, k])
+        assert np.all(e <= bound[:, k]), ax
+        print(f"configs[1] |{ax} - exact|: max {e.max():.3g} mean {e.mean():.3g} p99 {np.percentile(e, 99):.3g} m")
+    assert e.max() <= FULL_SIZE_Z_BOUND_M, e.max()
     ctx.cloudBigReset()
 
 
@@ -556,8 +585,12 @@ def test_full_size_configs2_2000_dense_frames_through_size_independent_propertie
         view = full.cloudBigView()  # [n, 4] int32 in HBM
         assert view.shape[0] == n_all
         assert_points_equal(points_from_torch(view[: sizes[0]]), first_big, "first 200 frames' part of the 2000-frame cloud_big")
+        ref = _torch_merge_reference(full, view, 0.05, 1, "configs[2] 2000 frames")
         del view, first_big
         small = full.finalize()
+        assert ref.status == 0
+        assert_points_equal(small, ref.points, "2000-frame merge against the torch reference")
+        del ref
         lin = cells(small)
         assert np.all(np.diff(lin) > 0)
         assert np.array_equal(lin, np.unique(np.concatenate(union)))
@@ -568,6 +601,88 @@ def test_full_size_configs2_2000_dense_frames_through_size_independent_propertie
     finally:
         full.close()
         part.close()
+
+
+def _torch_merge_reference(ctx, view, vs, minpts, what):
+    """tests/merge_reference.py on cloud_big in HBM (the combined merge, torch ops only); prints wall time and peak extra HBM"""
+    import time
+
+    import torch
+    ctx.synchronize()
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    t0 = time.perf_counter()
+    ref = mr.downsample_pt_cloud(view, vs, True, minpts)
+    torch.cuda.synchronize()
+    print(f"{what}: torch reference of {view.shape[0]} points -> {len(ref.points)} cells in {time.perf_counter() - t0:.1f} s, "
+          f"peak extra HBM {(torch.cuda.max_memory_allocated() - base) / 2**30:.1f} GiB")
+    return ref
+
+
+def _frames_threaded(start, count, rows, cols, workers=16):
+    """synth frames made by a pool of at most 16 threads (numpy releases the GIL in the heavy parts)"""
+    from concurrent.futures import ThreadPoolExecutor
+
+    from online_3d_reconstruction_amd import synth
+    disp = np.empty((count, rows, cols), np.uint8)
+    bgr = np.empty((count, rows, cols, 3), np.uint8)
+
+    def one(i):
+        disp[i], bgr[i] = synth.make_frame(start + i, rows, cols)
+    with ThreadPoolExecutor(max_workers=min(workers, 16)) as pool:
+        list(pool.map(one, range(count)))
+    return disp, bgr
+
+
+@pytest.mark.parametrize("shape", ["configs3", "configs4"])
+def test_full_size_merge_bit_equal_to_the_torch_reference(orc, shape):
+    """BASELINE.json configs[3] (1920x1080, jump 1, voxel 0.02, min_points_per_voxel 3: every frame trips PCL's per-frame
+    overflow guard, so 345 M raw points reach the merge in 1.6-point group runs) and configs[4]'s shape (4096x2160, jump 4,
+    voxel 0.05) at 200 frames, in a context of their own: the first 4 frames' part of cloud_big bit for bit against
+    orc.run_frames, the last 4 frames' part against a second context's run of only those frames (frames are independent),
+    and the merged cloud bit for bit against tests/merge_reference.py run on cloud_big in HBM."""
+    import torch
+
+    import online_3d_reconstruction_amd as o3dr
+    from online_3d_reconstruction_amd import synth
+    from online_3d_reconstruction_amd.api import points_from_torch
+    rows, cols, jump, vs, minpts = (1080, 1920, 1, 0.02, 3) if shape == "configs3" else (2160, 4096, 4, 0.05, 1)
+    F, CHUNK = 200, 50
+    Qs = synth.camera_Q(rows, cols)
+    prm = _params(jump_pixels=jump, voxel_size=vs, min_points_per_voxel=minpts)
+    ny, nx, cs = orc.grid_shape(rows, cols, jump_pixels=jump)
+    with o3dr.Context(0, Q=Qs, params=prm) as full, o3dr.Context(0, Q=Qs, params=prm) as part:
+        valid = 0
+        for a in range(0, F, CHUNK):
+            disp, bgr = _frames_threaded(a, CHUNK, rows, cols)
+            full.accumulateFrames(disp, bgr, synth.make_poses(a, CHUNK))
+            valid += int((disp[:, 20:rows - 20:jump, cs:cols - 20:jump] > 64).sum())
+            if a == 0:
+                rbig, _ = orc.run_frames(disp[:4], bgr[:4], Qs, synth.make_poses(0, 4), vs, jump_pixels=jump,
+                                         min_points_per_voxel=minpts, threads=4)
+            if a + CHUNK == F:
+                part.accumulateFrames(disp[-4:], bgr[-4:], synth.make_poses(F - 4, 4))
+            del disp, bgr
+        n, st = full.cloudBigSize()
+        assert 0 < n <= F * ny * nx
+        if shape == "configs3":
+            assert st == orc.STATUS_VOXEL_OVERFLOW and n == valid == F * 1040 * 1660
+        full.synchronize()
+        view = full.cloudBigView()
+        assert view.shape[0] == n
+        assert_points_equal(points_from_torch(view[: len(rbig)]), rbig, f"{shape}: first 4 frames' part of cloud_big")
+        last = part.cloudBigRead()
+        assert_points_equal(points_from_torch(view[n - len(last):]), last, f"{shape}: last 4 frames' part of cloud_big")
+        del rbig, last
+        ref = _torch_merge_reference(full, view, vs, minpts, f"{shape} 200 frames")
+        del view
+        small, fst = full.finalize(return_status=True)
+        assert ref.status == 0 and fst == st  # the merge itself is below the guard; finalize reports cloud_big's status
+        assert_points_equal(small, ref.points, f"{shape}: 200-frame merge against the torch reference")
+        assert ref.counts.min() >= max(minpts, 1)
+        assert np.all(np.diff(ref.idx) > 0)
+        torch.cuda.empty_cache()
 
 
 # ---- multi-GPU merge pieces on one GPU: virtual ranks, exchange done by hand ---------------------------
