@@ -396,6 +396,55 @@ int  o3dr_nearest_neighbors(o3dr_ctx* ctx, const o3dr_point* query, int64_t n_qu
 int  o3dr_icp_align(o3dr_ctx* ctx, const o3dr_point* source, int64_t n_source, const o3dr_point* target, int64_t n_target,
                     const float T_init[16], const o3dr_icp_params* p, o3dr_icp_result* res, int32_t mem);
 
+/* ---- moving-least-squares smoothing and normals: pcl::MovingLeastSquares as the reference's --smooth_surface tool uses it
+ * (pose.cpp:27-112, pose_functions.cpp:1711-1813), upsampling NONE, polynomial fit on.  The reference's exact call
+ * parameters and PCL's rounding cannot be pinned here, so the contract below is this library's own; where PCL leaves
+ * something open it is made exact.
+ *
+ * Input: n points, every coordinate finite.  r = search_radius (finite, > 0), order = polynomial_order (0, 1 or 2; 0: no
+ * polynomial), h = sqr_gauss_param (finite, >= 0; 0 means r*r).  For every point i, p = P_i:
+ *   1. Neighbours N(i) = { j : d2(p, P_j) <= r2 }, d2 = ((0 + dx*dx) + dy*dy) + dz*dz in fp32 without FMA (the d2 of
+ *      o3dr_nearest_neighbors), r2 = (float)(r*r) with the product in fp64.  p is in N(i); k = |N(i)|.  The set is exact.
+ *   2. Plane: the unweighted centroid c and covariance C of N(i) in fp64 (accumulated about p, then shifted; divided by k).
+ *      Eigenvalues l0 <= l1 <= l2, the normal n = the unit eigenvector of l0, curvature = l0 / (l0 + l1 + l2) (0 when the
+ *      trace is 0).  Orientation: n_z > 0; if n_z == 0 then n_y > 0, then n_x > 0.  k < 3 or l1 <= 1e-12 l2: no fit
+ *      (O3DR_MLS_NONE): the point passes through unchanged, normal and curvature are NaN, k is still reported.
+ *   3. m = p - (n . (p - c)) n.
+ *   4. Polynomial (order >= 1 and k >= nc monomials: 3 for order 1, 6 for order 2): v = normalize(-n_y, n_x, 0) if
+ *      |n_z| <= 0.9, else normalize(0, -n_z, n_y); u = n x v.  For j in N(i), e = P_j - m: (u_j, v_j) = (e.u, e.v) / r,
+ *      f_j = e.n, w_j = exp(-d2_j / h) with d2_j the fp32 distance of step 1.  Monomials u^a v^b, a + b <= order, a outer
+ *      and b inner (1, v, v^2, u, uv, u^2).  (sum w phi phi^T) a = sum w f phi in fp64 by Cholesky without pivoting; a pivot
+ *      <= 1e-12 x the largest diagonal entry, k < nc or a non-finite solution: plane (O3DR_MLS_PLANE).  Output point
+ *      (float)(m + a_0 n), normal normalize(n - (a_u / r) u - (a_v / r) v), a_v = coefficient 1, a_u = coefficient
+ *      order + 1 (PCL 1.8 projectPointToMLSSurface at u = v = 0); curvature stays the plane's.
+ *      Order 0 or the plane fallback: the point (float)m, the normal n.
+ *   5. The output copies the input point's rgba bits.
+ * Each point's sums run in a fixed order (the cells of its search window row by row, points in cell order - by original
+ * index inside a cell), with no atomics: results are bit-identical across calls, host and device memory, and in-place
+ * (out == cloud) and out-of-place calls.  The cost grows with the sum of k over the cloud.
+ * Outputs are index-aligned with the input: out (n points, may equal cloud), normals (4 n floats: nx ny nz curvature, or
+ * NULL), nn_count (n, or NULL), fit (n O3DR_MLS_* bytes, or NULL), all in `mem`; *res the counts per fit kind and the
+ * largest k.  Clouds of at most 2^32-1 points; n == 0 is OK (zero counts).  A non-finite coordinate anywhere, a bad radius,
+ * order or h: O3DR_ERR_INVALID_ARG (host outputs and *res zeroed).  The call synchronises.  It reuses the sort workspace
+ * (the search grid of o3dr_nearest_neighbors): a pending o3dr_cloud_big_slice_counts_dev table is dropped; cloud_big is
+ * left alone. */
+typedef struct o3dr_mls_params {
+    double  search_radius;     /* > 0, finite; no usable default (0 is rejected) */
+    int32_t polynomial_order;  /* 0, 1, 2; default 2 */
+    double  sqr_gauss_param;   /* 0 = search_radius^2 (default) */
+} o3dr_mls_params;
+typedef struct o3dr_mls_result {
+    int64_t n_poly, n_plane, n_none;  /* points per fit kind */
+    int32_t max_neighbors;
+} o3dr_mls_result;
+#define O3DR_MLS_NONE  0
+#define O3DR_MLS_PLANE 1
+#define O3DR_MLS_POLY  2
+void o3dr_mls_default_params(o3dr_mls_params* p);
+/* out: n points (may equal cloud); normals: 4n floats nx ny nz curvature, or NULL; nn_count: n or NULL; fit: n or NULL */
+int  o3dr_mls_smooth(o3dr_ctx* ctx, const o3dr_point* cloud, int64_t n, const o3dr_mls_params* p, o3dr_point* out,
+                     float* normals, uint32_t* nn_count, uint8_t* fit, o3dr_mls_result* res, int32_t mem);
+
 /* ---- measurement hooks (bench.py; not part of the reference surface) ------------------------ */
 /* kernel ids for o3dr_profile_* */
 #define O3DR_K_COUNT        0  /* grid-pass valid count per tile */

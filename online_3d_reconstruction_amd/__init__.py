@@ -9,6 +9,6 @@ There is no CPU fallback: importing works anywhere, but creating a `Context` wit
 library or without a GPU raises.
 """
 from ._lib import POINT, O3drError, lib_path, load_library  # noqa: F401
-from .api import Context, IcpResult, Params  # noqa: F401
+from .api import Context, IcpResult, MlsResult, Params  # noqa: F401
 
-__all__ = ["Context", "IcpResult", "Params", "POINT", "O3drError", "lib_path", "load_library"]
+__all__ = ["Context", "IcpResult", "MlsResult", "Params", "POINT", "O3drError", "lib_path", "load_library"]

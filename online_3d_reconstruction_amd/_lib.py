@@ -44,6 +44,17 @@ ICP_MAX_ITERATIONS, ICP_UNCHANGED, ICP_SMALL_STEP, ICP_TOO_FEW, ICP_DEGENERATE =
 ICP_REASONS = ["MAX_ITERATIONS", "UNCHANGED", "SMALL_STEP", "TOO_FEW", "DEGENERATE"]
 
 
+class MlsParamsStruct(C.Structure):
+    _fields_ = [("search_radius", C.c_double), ("polynomial_order", C.c_int32), ("sqr_gauss_param", C.c_double)]
+
+
+class MlsResultStruct(C.Structure):
+    _fields_ = [("n_poly", C.c_int64), ("n_plane", C.c_int64), ("n_none", C.c_int64), ("max_neighbors", C.c_int32)]
+
+
+MLS_NONE, MLS_PLANE, MLS_POLY = range(3)
+
+
 def lib_path():
     return _LIB
 
@@ -106,6 +117,8 @@ SYMBOLS = [
     ("o3dr_icp_default_params", None, [C.POINTER(IcpParamsStruct)]),
     ("o3dr_nearest_neighbors", C.c_int, [_vp, _vp, _i64, _vp, _i64, C.c_double, _vp, _vp, _i32]),
     ("o3dr_icp_align", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, C.POINTER(IcpParamsStruct), C.POINTER(IcpResultStruct), _i32]),
+    ("o3dr_mls_default_params", None, [C.POINTER(MlsParamsStruct)]),
+    ("o3dr_mls_smooth", C.c_int, [_vp, _vp, _i64, C.POINTER(MlsParamsStruct), _vp, _vp, _vp, _vp, C.POINTER(MlsResultStruct), _i32]),
     ("o3dr_profile_enable", C.c_int, [_vp, _i32, _i32]),
     ("o3dr_profile_read", C.c_int, [_vp, _i32, C.POINTER(C.c_double), _pi64]),
     ("o3dr_profile_reset", C.c_int, [_vp]),

@@ -51,6 +51,15 @@ class IcpResult:
         return L.ICP_REASONS[self.reason]
 
 
+@dataclass
+class MlsResult:
+    """o3dr_mls_smooth's counts: points per fit kind (MLS_POLY, MLS_PLANE, MLS_NONE) and the largest neighbour count."""
+    n_poly: int
+    n_plane: int
+    n_none: int
+    max_neighbors: int
+
+
 def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
@@ -319,6 +328,55 @@ class Context:
                                          mem))
         return IcpResult(np.array(res.T[:], np.float64).reshape(4, 4), float(res.fitness), int(res.n_correspondences),
                          int(res.iterations), int(res.reason))
+
+    # -- surface smoothing (pcl::MovingLeastSquares, pose.cpp:27-112 / pose_functions.cpp:1711-1813) ---------------------
+    def mlsSmooth(self, pts, search_radius, polynomial_order=2, sqr_gauss_param=0.0, return_normals=False, return_info=False,
+                  fitted_only=False, out=None):
+        """Moving-least-squares smoothing of every point (contract: include/o3dr.h, DESIGN.md "MLS").  numpy POINT arrays,
+        or torch [N,4] 4-byte CUDA tensors such as cloudBigView() or finalize(device=...) (results are then CUDA tensors).
+        -> the smoothed points, index-aligned with `pts`; with return_normals also [N,4] float32 (nx, ny, nz, curvature;
+        NaN where no fit); with return_info also nn_count (uint32 / int32), fit (uint8, MLS_*) and an MlsResult.
+        fitted_only: keep only the fitted points (fit != MLS_NONE), in input order.  out: where the points go (may be
+        `pts` itself: in place)."""
+        pts, n = self._cloud(pts)
+        p_in, mem, _k = _ptr(pts)
+        prm = L.MlsParamsStruct(float(search_radius), int(polynomial_order), float(sqr_gauss_param))
+        res = L.MlsResultStruct()
+        if mem == L.MEM_DEVICE:
+            import torch
+            dev = pts.device
+            o = torch.empty_like(pts) if out is None else out
+            assert o.is_cuda and o.is_contiguous() and o.shape == pts.shape and o.element_size() == 4
+            nrm = torch.empty((max(n, 1), 4), dtype=torch.float32, device=dev) if return_normals else None
+            cnt = torch.empty(max(n, 1), dtype=torch.int32, device=dev) if return_info or fitted_only else None
+            fit = torch.empty(max(n, 1), dtype=torch.uint8, device=dev) if return_info or fitted_only else None
+            self._order_after_torch()
+            L.check(self._lib.o3dr_mls_smooth(self._h, p_in, n, C.byref(prm), o.data_ptr() if n else None,
+                                              None if nrm is None else nrm.data_ptr(), None if cnt is None else cnt.data_ptr(),
+                                              None if fit is None else fit.data_ptr(), C.byref(res), L.MEM_DEVICE))
+        else:
+            o = np.empty(n, POINT) if out is None else out
+            assert isinstance(o, np.ndarray) and o.dtype == POINT and o.shape == (n,) and o.flags.c_contiguous
+            nrm = np.empty((n, 4), np.float32) if return_normals else None
+            cnt = np.empty(n, np.uint32) if return_info or fitted_only else None
+            fit = np.empty(n, np.uint8) if return_info or fitted_only else None
+            L.check(self._lib.o3dr_mls_smooth(self._h, p_in, n, C.byref(prm), o.ctypes.data if n else None,
+                                              None if nrm is None else nrm.ctypes.data, None if cnt is None else cnt.ctypes.data,
+                                              None if fit is None else fit.ctypes.data, C.byref(res), mem))
+        o, nrm, cnt, fit = o[:n], (None if nrm is None else nrm[:n]), (None if cnt is None else cnt[:n]), (None if fit is None else fit[:n])
+        if fitted_only:
+            keep = fit != L.MLS_NONE
+            o, nrm, cnt, fit = o[keep], (None if nrm is None else nrm[keep]), cnt[keep], fit[keep]
+        if mem == L.MEM_DEVICE and cnt is not None:
+            import torch
+            if hasattr(torch, "uint32"):
+                cnt = cnt.view(torch.uint32)
+        ret = (o,)
+        if return_normals:
+            ret += (nrm,)
+        if return_info:
+            ret += (cnt, fit, MlsResult(int(res.n_poly), int(res.n_plane), int(res.n_none), int(res.max_neighbors)))
+        return ret[0] if len(ret) == 1 else ret
 
     def voxelGrid(self, pts, leaf, min_points=0, z_offset=0.0, return_status=False):
         """pcl::VoxelGrid<PointXYZRGB> as the reference configures it (pose_functions.cpp:1689-1700)."""

@@ -1,0 +1,295 @@
+// Part of libo3dr's single device translation unit: included by o3dr_kernels.hip inside namespace o3dr
+// (kernels and their launchers must share a translation unit without relocatable device code).
+
+// =================================================================================================
+// Moving-least-squares smoothing and normals (o3dr_mls_smooth; DESIGN.md "MLS")
+//   The cloud's search grid is the nearest-neighbour grid (launch_nn_grid: points in cell order with their original index
+//   in .w, exact per-cell boxes, the cloud's box).  ONE LANE PER QUERY, queries taken in the grid's cell order (lane t:
+//   sor_xyz[t], results to index .w), so the lanes of a wave share cells.  The window is every cell between the cells of
+//   the query's box (q -/+ r(1 + 1e-5), clamped to the cloud's box) in x and y: the cell assignment (sor_cell) is monotone
+//   in the coordinate, so no neighbour lies outside it.  A cell whose exact box is farther than r2 is skipped (the lower
+//   bound of nn_visit, never above a computed distance).  Pass 1: k and the fp64 moments about the query; a fixed-sweep
+//   3x3 Jacobi; pass 2 (polynomial fit): the weighted moments sum w u^a v^b (a + b <= 2 order) and sum w f u^a v^b; a
+//   Cholesky solve and the epilogue.  Sums run over the window's cells row by row, points in cell order: no atomics
+//   but the integer counters of the result.
+// =================================================================================================
+constexpr int kMlsThreads = 256;
+constexpr int kMlsJacobiSweeps = 8;  // cyclic (0,1) (0,2) (1,2): converged to fp64 rounding well before
+
+struct MlsArgs {
+    const o3dr_point* cloud;  // n points in the caller's order (colours are read here)
+    uint32_t n;
+    const float4* sxyz;       // the cloud in cell order, .w = original index bits
+    const uint32_t* cell_first;
+    const float4* cell_lo;
+    const float4* cell_hi;
+    const SorGeom* sg;
+    const float* box6;        // the cloud's bounding box (min xyz, max xyz)
+    float r2;                 // (float)(r * r)
+    double r, inv_h;          // search radius; 1 / sqr_gauss_param
+    float pad_r;              // max(r (1 + 1e-5), 1e-18): half the side of the query's box
+    o3dr_point* out;          // n (may be cloud)
+    float* normals;           // 4 n (nx ny nz curvature) or nullptr
+    uint32_t* nn_count;       // n or nullptr
+    uint8_t* fit;             // n or nullptr
+    unsigned long long* counters;  // n_none, n_plane, n_poly, max k
+};
+
+__device__ __forceinline__ int mls_col(const SorGeom& g, float x)
+{
+    int cx = (int)((x - g.mnx) * g.inv_h);
+    return cx < 0 ? 0 : (cx >= g.gx ? g.gx - 1 : cx);
+}
+__device__ __forceinline__ int mls_row(const SorGeom& g, float y)
+{
+    int cy = (int)((y - g.mny) * g.inv_h);
+    return cy < 0 ? 0 : (cy >= g.gy ? g.gy - 1 : cy);
+}
+
+// f(p, d2) for every point p of the cloud with the fp32 d2 <= r2, in the fixed order of the contract
+template <class F>
+__device__ __forceinline__ void mls_walk(const MlsArgs& a, const SorGeom& g, int x0, int x1, int y0, int y1, float qx, float qy,
+                                         float qz, F&& f)
+{
+    for (int yy = y0; yy <= y1; ++yy) {
+        const int64_t row = (int64_t)yy * g.gx;
+        for (int xx = x0; xx <= x1; ++xx) {
+            const int64_t c = row + xx;
+            const float4 lo = a.cell_lo[c], hi = a.cell_hi[c];
+            const float gx = fmaxf(fmaxf(lo.x - qx, qx - hi.x), 0.f);
+            const float gy = fmaxf(fmaxf(lo.y - qy, qy - hi.y), 0.f);
+            const float gz = fmaxf(fmaxf(lo.z - qz, qz - hi.z), 0.f);
+            const float lb = (gx * gx + gy * gy) + gz * gz;  // <= the computed d2 of every point of the cell
+            if (!(lb <= a.r2)) continue;
+            const uint32_t s = a.cell_first[c], e = a.cell_first[c + 1];
+            for (uint32_t j = s; j < e; ++j) {
+                const float4 p = a.sxyz[j];
+                const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
+                const float d = (dx * dx + dy * dy) + dz * dz;
+                if (d <= a.r2) f(p, d);
+            }
+        }
+    }
+}
+
+// symmetric 3x3 eigen-decomposition by cyclic Jacobi: A (upper triangle used) -> eigenvalues on the diagonal, V's columns
+__device__ __forceinline__ void mls_jacobi3(double A[3][3], double V[3][3])
+{
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+    A[1][0] = A[0][1], A[2][0] = A[0][2], A[2][1] = A[1][2];
+#pragma unroll
+    for (int sweep = 0; sweep < kMlsJacobiSweeps; ++sweep) {
+#pragma unroll
+        for (int pq = 0; pq < 3; ++pq) {
+            const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2, r = 3 - p - q;
+            const double apq = A[p][q];
+            if (apq == 0.0) continue;
+            const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+            const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+            const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
+            A[p][p] -= t * apq;
+            A[q][q] += t * apq;
+            A[p][q] = A[q][p] = 0.0;
+            const double arp = A[r][p], arq = A[r][q];
+            A[r][p] = A[p][r] = cs * arp - sn * arq;
+            A[r][q] = A[q][r] = sn * arp + cs * arq;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const double vp = V[i][p], vq = V[i][q];
+                V[i][p] = cs * vp - sn * vq;
+                V[i][q] = sn * vp + cs * vq;
+            }
+        }
+    }
+}
+
+template <int O>
+__global__ __launch_bounds__(kMlsThreads) void k_mls(MlsArgs a)
+{
+    const int64_t t = (int64_t)blockIdx.x * kMlsThreads + threadIdx.x;
+    const bool valid = t < (int64_t)a.n;
+    int kind = -1;
+    uint32_t k = 0;
+    if (valid) {
+        const SorGeom g = *a.sg;
+        const float4 q = a.sxyz[t];
+        const uint32_t idx = __float_as_uint(q.w);
+        // the window: the cells of the query's box, through the monotone cell assignment of the points
+        const float x0f = fmaxf(q.x - a.pad_r, a.box6[0]), x1f = fminf(q.x + a.pad_r, a.box6[3]);
+        const float y0f = fmaxf(q.y - a.pad_r, a.box6[1]), y1f = fminf(q.y + a.pad_r, a.box6[4]);
+        const int x0 = mls_col(g, x0f), x1 = mls_col(g, x1f), y0 = mls_row(g, y0f), y1 = mls_row(g, y1f);
+        // pass 1: k and the moments about the query
+        double s1[3] = {0.0, 0.0, 0.0}, s2[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        mls_walk(a, g, x0, x1, y0, y1, q.x, q.y, q.z, [&](const float4& p, float) {
+            const double ex = (double)p.x - (double)q.x, ey = (double)p.y - (double)q.y, ez = (double)p.z - (double)q.z;
+            ++k;
+            s1[0] += ex, s1[1] += ey, s1[2] += ez;
+            s2[0] += ex * ex, s2[1] += ex * ey, s2[2] += ex * ez;
+            s2[3] += ey * ey, s2[4] += ey * ez, s2[5] += ez * ez;
+        });
+        const double inv_k = k ? 1.0 / (double)k : 0.0;
+        const double mx = s1[0] * inv_k, my = s1[1] * inv_k, mz = s1[2] * inv_k;  // centroid - query
+        double A[3][3], V[3][3];
+        A[0][0] = s2[0] * inv_k - mx * mx, A[0][1] = s2[1] * inv_k - mx * my, A[0][2] = s2[2] * inv_k - mx * mz;
+        A[1][1] = s2[3] * inv_k - my * my, A[1][2] = s2[4] * inv_k - my * mz, A[2][2] = s2[5] * inv_k - mz * mz;
+        mls_jacobi3(A, V);
+        // ascending eigenvalues (ties keep the lower column); selects, not indexing: V stays in registers
+        const double d0 = A[0][0], d1 = A[1][1], d2 = A[2][2];
+        int i0 = 0, i1 = 1, i2 = 2;
+        auto ev = [&](int i) { return i == 0 ? d0 : (i == 1 ? d1 : d2); };
+        if (ev(i1) < ev(i0)) { const int s = i0; i0 = i1; i1 = s; }
+        if (ev(i2) < ev(i1)) { const int s = i1; i1 = i2; i2 = s; }
+        if (ev(i1) < ev(i0)) { const int s = i0; i0 = i1; i1 = s; }
+        const double l0 = ev(i0), l1 = ev(i1), l2 = ev(i2);
+        const o3dr_point src = a.cloud[idx];  // read before the write below: in-place calls are safe
+        o3dr_point o = src;
+        float nrm[4] = {__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""), __builtin_nanf("")};
+        if (k < 3 || !(l1 > 1e-12 * l2)) {
+            kind = O3DR_MLS_NONE;
+        } else {
+            double nx = i0 == 0 ? V[0][0] : (i0 == 1 ? V[0][1] : V[0][2]);
+            double ny = i0 == 0 ? V[1][0] : (i0 == 1 ? V[1][1] : V[1][2]);
+            double nz = i0 == 0 ? V[2][0] : (i0 == 1 ? V[2][1] : V[2][2]);
+            const double nl = 1.0 / sqrt(nx * nx + ny * ny + nz * nz);
+            nx *= nl, ny *= nl, nz *= nl;
+            if (nz < 0.0 || (nz == 0.0 && (ny < 0.0 || (ny == 0.0 && nx < 0.0)))) nx = -nx, ny = -ny, nz = -nz;
+            const double tr = l0 + l1 + l2;
+            const double curv = tr != 0.0 ? l0 / tr : 0.0;
+            // projection of the query onto the plane: m = p - (n . (p - c)) n, with p - c = -(mx, my, mz)
+            const double dn = -(nx * mx + ny * my + nz * mz);
+            const double px = (double)q.x - dn * nx, py = (double)q.y - dn * ny, pz = (double)q.z - dn * nz;
+            double a0 = 0.0, au = 0.0, av = 0.0;
+            kind = O3DR_MLS_PLANE;
+            double ux = 0.0, uy = 0.0, uz = 0.0, vx = 0.0, vy = 0.0, vz = 0.0;
+            if constexpr (O >= 1) {
+                constexpr int nc = (O + 1) * (O + 2) / 2;
+                constexpr int D = 2 * O, ns = (D + 1) * (D + 2) / 2;
+                if (k >= (uint32_t)nc) {
+                    // local frame
+                    if (fabs(nz) <= 0.9) vx = -ny, vy = nx, vz = 0.0;
+                    else vx = 0.0, vy = -nz, vz = ny;
+                    const double vl = 1.0 / sqrt(vx * vx + vy * vy + vz * vz);
+                    vx *= vl, vy *= vl, vz *= vl;
+                    ux = ny * vz - nz * vy, uy = nz * vx - nx * vz, uz = nx * vy - ny * vx;
+                    // pass 2: S[(a, b)] = sum w u^a v^b (a + b <= D), F[(a, b)] = sum w f u^a v^b (a + b <= O)
+                    double S[ns], Fv[nc];
+#pragma unroll
+                    for (int m = 0; m < ns; ++m) S[m] = 0.0;
+#pragma unroll
+                    for (int m = 0; m < nc; ++m) Fv[m] = 0.0;
+                    const double inv_r = 1.0 / a.r, inv_h = a.inv_h;
+                    mls_walk(a, g, x0, x1, y0, y1, q.x, q.y, q.z, [&](const float4& p, float d) {
+                        const double ex = (double)p.x - px, ey = (double)p.y - py, ez = (double)p.z - pz;
+                        const double u = (ex * ux + ey * uy + ez * uz) * inv_r, v = (ex * vx + ey * vy + ez * vz) * inv_r;
+                        const double f = ex * nx + ey * ny + ez * nz;
+                        const double w = exp(-(double)d * inv_h);
+                        double upow = w;
+                        int m = 0, mf = 0;
+#pragma unroll
+                        for (int ea = 0; ea <= D; ++ea) {
+                            double term = upow;
+#pragma unroll
+                            for (int eb = 0; eb <= D - ea; ++eb) {
+                                S[m++] += term;
+                                if (ea + eb <= O) Fv[mf++] += term * f;
+                                term *= v;
+                            }
+                            upow *= u;
+                        }
+                    });
+                    // the normal matrix M[i][j] = S[a_i + a_j, b_i + b_j] over the monomials u^a v^b (a outer, b inner)
+                    int ma[nc], mb[nc];
+                    {
+                        int m = 0;
+#pragma unroll
+                        for (int ea = 0; ea <= O; ++ea)
+#pragma unroll
+                            for (int eb = 0; eb <= O - ea; ++eb) ma[m] = ea, mb[m] = eb, ++m;
+                    }
+                    auto sidx = [](int ea, int eb) { return ea * (D + 1) - ea * (ea - 1) / 2 + eb; };
+                    double L[nc][nc], c[nc];
+                    double dmax = 0.0;
+#pragma unroll
+                    for (int i = 0; i < nc; ++i) dmax = fmax(dmax, S[sidx(2 * ma[i], 2 * mb[i])]);
+                    bool ok = true;
+#pragma unroll
+                    for (int i = 0; i < nc; ++i) {
+#pragma unroll
+                        for (int j = 0; j <= i; ++j) {
+                            double s = S[sidx(ma[i] + ma[j], mb[i] + mb[j])];
+#pragma unroll
+                            for (int l = 0; l < j; ++l) s -= L[i][l] * L[j][l];
+                            if (i == j) {
+                                ok = ok && s > 1e-12 * dmax;
+                                L[i][i] = sqrt(fmax(s, 0.0));
+                            } else {
+                                L[i][j] = L[j][j] > 0.0 ? s / L[j][j] : 0.0;
+                            }
+                        }
+                    }
+#pragma unroll
+                    for (int i = 0; i < nc; ++i) {  // L y = F
+                        double s = Fv[i];
+#pragma unroll
+                        for (int l = 0; l < i; ++l) s -= L[i][l] * c[l];
+                        c[i] = s / L[i][i];
+                    }
+#pragma unroll
+                    for (int i = nc - 1; i >= 0; --i) {  // L^T c = y
+                        double s = c[i];
+#pragma unroll
+                        for (int l = i + 1; l < nc; ++l) s -= L[l][i] * c[l];
+                        c[i] = s / L[i][i];
+                    }
+#pragma unroll
+                    for (int i = 0; i < nc; ++i) ok = ok && isfinite(c[i]);
+                    if (ok) {
+                        kind = O3DR_MLS_POLY;
+                        a0 = c[0], av = c[1] * inv_r, au = c[O + 1] * inv_r;
+                    }
+                }
+            }
+            double ox = px, oy = py, oz = pz, qnx = nx, qny = ny, qnz = nz;
+            if (kind == O3DR_MLS_POLY) {
+                ox += a0 * nx, oy += a0 * ny, oz += a0 * nz;
+                qnx = nx - au * ux - av * vx, qny = ny - au * uy - av * vy, qnz = nz - au * uz - av * vz;
+                const double ql = 1.0 / sqrt(qnx * qnx + qny * qny + qnz * qnz);
+                qnx *= ql, qny *= ql, qnz *= ql;
+            }
+            o.x = (float)ox, o.y = (float)oy, o.z = (float)oz;
+            nrm[0] = (float)qnx, nrm[1] = (float)qny, nrm[2] = (float)qnz, nrm[3] = (float)curv;
+        }
+        a.out[idx] = o;
+        if (a.normals) reinterpret_cast<float4*>(a.normals)[idx] = make_float4(nrm[0], nrm[1], nrm[2], nrm[3]);
+        if (a.nn_count) a.nn_count[idx] = k;
+        if (a.fit) a.fit[idx] = (uint8_t)kind;
+    }
+    // the result's counters: per wave, then one integer atomic per wave and counter (order-independent)
+    const unsigned long long none = __ballot(kind == O3DR_MLS_NONE), plane = __ballot(kind == O3DR_MLS_PLANE),
+                             poly = __ballot(kind == O3DR_MLS_POLY);
+    uint32_t km = k;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const uint32_t x = __shfl_xor(km, o, 64);
+        km = x > km ? x : km;
+    }
+    if ((threadIdx.x & 63) == 0 && (none | plane | poly)) {
+        if (none) atomicAdd(&a.counters[0], (unsigned long long)__popcll(none));
+        if (plane) atomicAdd(&a.counters[1], (unsigned long long)__popcll(plane));
+        if (poly) atomicAdd(&a.counters[2], (unsigned long long)__popcll(poly));
+        atomicMax(&a.counters[3], (unsigned long long)km);
+    }
+}
+static_assert(kMlsThreads % kWave == 0, "the counters are folded per wave");
+
+// 1 in flag[0] if any coordinate of the n points is not finite (every writer stores the same value)
+__global__ __launch_bounds__(256) void k_mls_finite(const o3dr_point* __restrict__ in, int64_t n, uint32_t* __restrict__ flag)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const float4 p = reinterpret_cast<const float4*>(in)[i];
+        if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) flag[0] = 1u;
+    }
+}

@@ -133,6 +133,8 @@ struct o3dr_ctx {
     // o3dr_nearest_neighbors / o3dr_icp_align: staged host clouds, the target grid's cell boxes + box, the per-call source
     // arrays (indices of this and the previous pass, d2, the moment partials and their folded record)
     DevBuf nn_q, nn_t, nn_cells, nn_src;
+    // o3dr_mls_smooth: the staged outputs of a host call and the device counters / non-finite flag
+    DevBuf mls_out, mls_misc;
     int64_t place_ub = -1;   // o3dr_cloud_big_slice_counts_dev ran for a cloud of at most this many points and place_parts slices:
     int place_parts = 0;     // the (slice, tile) table in the workspace is what o3dr_cloud_big_place_slices moves by
     int test_hooks = 0;    // O3DR_TEST_HOOKS=1 at o3dr_ctx_create: the entry points of include/o3dr_testing.h act
@@ -473,7 +475,7 @@ extern "C" int o3dr_ctx_destroy(o3dr_ctx* c)
         dev_release(c->inc.cells[i]);
     }
     for (DevBuf* b : {&c->inc.box, &c->inc.scratch, &c->inc.tg, &c->inc.tmatch, &c->inc.flag, &c->inc.src, &c->inc.keep,
-                      &c->inc.partial, &c->inc.words, &c->inc.fb, &c->nn_q, &c->nn_t, &c->nn_cells, &c->nn_src})
+                      &c->inc.partial, &c->inc.words, &c->inc.fb, &c->nn_q, &c->nn_t, &c->nn_cells, &c->nn_src, &c->mls_out, &c->mls_misc})
         dev_release(*b);
     delete c;
     return O3DR_OK;
@@ -3118,6 +3120,93 @@ extern "C" int o3dr_icp_align(o3dr_ctx* c, const o3dr_point* source, int64_t n_s
     res->fitness = rec[0] > 0.0 ? rec[16] / rec[0] : DBL_MAX;
     res->iterations = iterations;
     res->reason = reason;
+    return O3DR_OK;
+}
+
+// -------------------------------------------------------------------------------------------------
+// moving-least-squares smoothing and normals (kernels/mls.inc; DESIGN.md "MLS")
+// -------------------------------------------------------------------------------------------------
+extern "C" void o3dr_mls_default_params(o3dr_mls_params* p)
+{
+    if (!p) return;
+    p->search_radius = 0.0;    // no usable default: the caller sets it
+    p->polynomial_order = 2;   // pcl::MovingLeastSquares order_
+    p->sqr_gauss_param = 0.0;  // search_radius^2, as PCL's setSearchRadius sets it
+}
+
+extern "C" int o3dr_mls_smooth(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const o3dr_mls_params* p, o3dr_point* out,
+                               float* normals, uint32_t* nn_count, uint8_t* fit, o3dr_mls_result* res, int32_t mem)
+{
+    if (res) memset(res, 0, sizeof *res);
+    if (mem == O3DR_MEM_HOST && n > 0 && n <= (int64_t)0xffffffffLL) {  // outputs zeroed first (out may be the input)
+        if (out && out != cloud) memset(out, 0, (size_t)n * sizeof(o3dr_point));
+        if (normals) memset(normals, 0, (size_t)n * 4 * sizeof(float));
+        if (nn_count) memset(nn_count, 0, (size_t)n * sizeof(uint32_t));
+        if (fit) memset(fit, 0, (size_t)n);
+    }
+    CTX_ENTER(c);
+    CHK(nn_check_cloud(n, cloud));
+    if (!p) return fail(O3DR_ERR_INVALID_ARG, "params is NULL");
+    if (n > 0 && !out) return fail(O3DR_ERR_INVALID_ARG, "out is NULL");
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    const double r = p->search_radius;
+    if (!(std::isfinite(r) && r > 0.0)) return fail(O3DR_ERR_INVALID_ARG, "search_radius must be finite and > 0");
+    if (p->polynomial_order < 0 || p->polynomial_order > 2) return fail(O3DR_ERR_INVALID_ARG, "polynomial_order must be 0, 1 or 2");
+    if (!(std::isfinite(p->sqr_gauss_param) && p->sqr_gauss_param >= 0.0))
+        return fail(O3DR_ERR_INVALID_ARG, "sqr_gauss_param must be finite and >= 0 (0: search_radius^2)");
+    const double h = p->sqr_gauss_param > 0.0 ? p->sqr_gauss_param : r * r;
+    if (!(h > 0.0 && std::isfinite(h))) return fail(O3DR_ERR_INVALID_ARG, "search_radius^2 is not a usable sqr_gauss_param");
+    c->place_ub = -1;
+    if (n == 0) return O3DR_OK;
+    CHK(dev_ensure(c, c->mls_misc, 256));
+    unsigned long long* counters = (unsigned long long*)c->mls_misc.p;
+    uint32_t* flag = (uint32_t*)((char*)c->mls_misc.p + 64);
+    // every coordinate finite, checked before the grid sees the cloud
+    const void* cloud_d;
+    CHK(stage_in(c, c->nn_t, cloud, (size_t)n * sizeof(o3dr_point), mem, &cloud_d));
+    launch_mls_finite(&c->prof, c->stream, (const o3dr_point*)cloud_d, n, flag);
+    HIPCHK(hipGetLastError());
+    uint32_t bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (bad) {
+        if (mem == O3DR_MEM_HOST && out == cloud) memset(out, 0, (size_t)n * sizeof(o3dr_point));
+        return fail(O3DR_ERR_INVALID_ARG, "the cloud has a non-finite coordinate");
+    }
+    float* box6;
+    float4 *lo, *hi;
+    CHK(nn_target(c, (const o3dr_point*)cloud_d, n, O3DR_MEM_DEVICE, &box6, &lo, &hi));
+    o3dr_point* out_d = out;
+    float* nrm_d = normals;
+    uint32_t* cnt_d = nn_count;
+    uint8_t* fit_d = fit;
+    if (mem == O3DR_MEM_HOST) {  // staged: points, normals, counts, fit kinds
+        const size_t b_pts = align256((size_t)n * sizeof(o3dr_point)), b_nrm = align256((size_t)n * 16), b_cnt = align256((size_t)n * 4);
+        CHK(dev_ensure(c, c->mls_out, b_pts + b_nrm + b_cnt + align256((size_t)n)));
+        char* base = (char*)c->mls_out.p;
+        out_d = (o3dr_point*)base;
+        nrm_d = normals ? (float*)(base + b_pts) : nullptr;
+        cnt_d = nn_count ? (uint32_t*)(base + b_pts + b_nrm) : nullptr;
+        fit_d = fit ? (uint8_t*)(base + b_pts + b_nrm + b_cnt) : nullptr;
+    }
+    launch_mls(&c->prof, c->stream, c->ws, (const o3dr_point*)cloud_d, n, box6, lo, hi, r, p->polynomial_order, h, out_d, nrm_d, cnt_d,
+               fit_d, counters);
+    HIPCHK(hipGetLastError());
+    unsigned long long cnt_h[4];
+    HIPCHK(hipMemcpyAsync(cnt_h, counters, sizeof cnt_h, hipMemcpyDeviceToHost, c->stream));
+    if (mem == O3DR_MEM_HOST) {
+        HIPCHK(hipMemcpyAsync(out, out_d, (size_t)n * sizeof(o3dr_point), hipMemcpyDeviceToHost, c->stream));
+        if (normals) HIPCHK(hipMemcpyAsync(normals, nrm_d, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
+        if (nn_count) HIPCHK(hipMemcpyAsync(nn_count, cnt_d, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        if (fit) HIPCHK(hipMemcpyAsync(fit, fit_d, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (res) {
+        res->n_none = (int64_t)cnt_h[0];
+        res->n_plane = (int64_t)cnt_h[1];
+        res->n_poly = (int64_t)cnt_h[2];
+        res->max_neighbors = (int32_t)std::min<unsigned long long>(cnt_h[3], 0x7fffffffull);
+    }
     return O3DR_OK;
 }
 

@@ -295,6 +295,13 @@ void launch_nn_query(Profiler* pf, hipStream_t s, const Workspace& ws, const o3d
                      const float* box6, const float4* cell_lo, const float4* cell_hi, float r2, uint32_t* idx_out, float* d2_out,
                      const uint32_t* idx_prev, const double c0[3], double* partial, double* rec);
 inline int64_t nn_partial_blocks(int64_t n) { return (n + 255) / 256; }  // workgroups of launch_nn_query (kNnThreads queries each)
+// moving least squares (kernels/mls.inc).  launch_mls_finite: flag[0] = 1 if a coordinate of the n points is not finite.
+// launch_mls: o3dr_mls_smooth over the grid launch_nn_grid built for `cloud` (box6, cell_lo / cell_hi its outputs);
+// counters (device, 4 x u64): n_none, n_plane, n_poly, max neighbours
+void launch_mls_finite(Profiler* pf, hipStream_t s, const o3dr_point* in, int64_t n, uint32_t* flag);
+void launch_mls(Profiler* pf, hipStream_t s, const Workspace& ws, const o3dr_point* cloud, int64_t n, const float* box6,
+                const float4* cell_lo, const float4* cell_hi, double r, int order, double h, o3dr_point* out, float* normals,
+                uint32_t* nn_count, uint8_t* fit, unsigned long long* counters);
 void launch_partition(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelArgs& v, int n_parts, o3dr_point* out,
                       uint64_t* counts_dev, uint32_t* overflow_dev, const void* hdrs_dev = nullptr, int n_hdrs = 0);
 // its two halves: slice sizes without moving anything (the (part, tile) table stays in ws for the second half), then the move

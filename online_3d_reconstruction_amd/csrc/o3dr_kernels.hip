@@ -27,6 +27,7 @@
 //   small        clouds of at most kSmallMax points: the whole path in one launch of one workgroup
 //   incremental  the combined merge kept as running per-cell sums (o3dr_finalize_incremental)
 //   nn           exact nearest neighbour into a target's search grid, the fused ICP pass and its fold
+//   mls          moving-least-squares smoothing and normals over the same grid
 // The launchers follow in this file.
 #include <string.h>
 
@@ -47,6 +48,7 @@ namespace o3dr {
 #include "kernels/sor.inc"
 #include "kernels/small.inc"
 #include "kernels/nn.inc"
+#include "kernels/mls.inc"
 
 // =================================================================================================
 // launchers
@@ -730,6 +732,53 @@ void launch_nn_query(Profiler* pf, hipStream_t s, const Workspace& ws, const o3d
     a.n_blocks = (uint32_t)cdiv64(n, kNnThreads);
     k_nn_query<<<a.n_blocks, kNnThreads, 0, s>>>(a);
     if (partial) k_icp_fold<<<kIcpFields, kIcpFoldThreads, 0, s>>>(partial, a.n_blocks, rec);
+}
+
+// Moving least squares (kernels/mls.inc) over the grid launch_nn_grid left in ws.sor_*
+void launch_mls_finite(Profiler* pf, hipStream_t s, const o3dr_point* in, int64_t n, uint32_t* flag)
+{
+    ProfScope ps(pf, O3DR_K_OTHER, s);
+    (void)hipMemsetAsync(flag, 0, 4, s);
+    if (n <= 0) return;
+    int g = cdiv64(n, 256);
+    if (g > 4096) g = 4096;
+    k_mls_finite<<<g, 256, 0, s>>>(in, n, flag);
+}
+
+void launch_mls(Profiler* pf, hipStream_t s, const Workspace& ws, const o3dr_point* cloud, int64_t n, const float* box6,
+                const float4* cell_lo, const float4* cell_hi, double r, int order, double h, o3dr_point* out, float* normals,
+                uint32_t* nn_count, uint8_t* fit, unsigned long long* counters)
+{
+    ProfScope ps(pf, O3DR_K_OTHER, s);
+    (void)hipMemsetAsync(counters, 0, 4 * sizeof(unsigned long long), s);
+    if (n <= 0) return;
+    MlsArgs a;
+    memset(&a, 0, sizeof a);
+    a.cloud = cloud;
+    a.n = (uint32_t)n;
+    a.sxyz = ws.sor_xyz;
+    a.cell_first = ws.sor_cell_first;
+    a.cell_lo = cell_lo;
+    a.cell_hi = cell_hi;
+    a.sg = ws.sor_geom;
+    a.box6 = box6;
+    a.r2 = (float)(r * r);
+    a.r = r;
+    a.inv_h = 1.0 / h;
+    const double pad = r * (1.0 + 1e-5);
+    a.pad_r = (float)(pad > 1e-18 ? pad : 1e-18);
+    a.out = out;
+    a.normals = normals;
+    a.nn_count = nn_count;
+    a.fit = fit;
+    a.counters = counters;
+    const int blocks = cdiv64(n, kMlsThreads);
+    if (order == 0)
+        k_mls<0><<<blocks, kMlsThreads, 0, s>>>(a);
+    else if (order == 1)
+        k_mls<1><<<blocks, kMlsThreads, 0, s>>>(a);
+    else
+        k_mls<2><<<blocks, kMlsThreads, 0, s>>>(a);
 }
 
 }  // namespace o3dr

@@ -7,7 +7,8 @@
 // it is control plane, one call per frame or per run, and stays on the host.  Pose estimation (ORB,
 // matching, the ICP trajectory correction), visualisation and the mesh/segment tools are not part of
 // this build; the CLI runs with the recorded MAVLink poses (the reference's --only_MAVLink mode,
-// pose_functions.cpp:232-236).  The --align_point_cloud tool (ICP on two PLYs) runs on o3dr_icp_align.
+// pose_functions.cpp:232-236).  The --align_point_cloud tool (ICP on two PLYs) runs on o3dr_icp_align, the
+// --smooth_surface tool (MLS on one PLY) on o3dr_mls_smooth.
 #pragma once
 #include <array>
 #include <cmath>
@@ -41,9 +42,11 @@ struct Image8 {                                 // cv::Mat stand-in: 8-bit, 1 or
 // ---- I/O helpers (png_io.cpp, ply_io.cpp) ------------------------------------------------------------
 // cv::imread(path) / cv::imread(path, IMREAD_GRAYSCALE) for 8-bit non-interlaced PNGs; empty on failure
 Image8 read_png(const std::string& path, bool grayscale);
-// pcl::io::savePLYFileBinary layout (x,y,z float + r,g,b uchar, then one `camera` element)
-bool save_ply_binary(const std::string& path, const PointCloud& cloud);
-// pcl::PLYReader for the files save_ply_binary writes (and build/cloud.ply)
+// pcl::io::savePLYFileBinary layout (x,y,z float + r,g,b uchar, then one `camera` element); with normals (4 floats per
+// point: nx ny nz curvature) PointXYZRGBNormal's (the same, then normal_x normal_y normal_z curvature float)
+bool save_ply_binary(const std::string& path, const PointCloud& cloud, const std::vector<float>* normals = nullptr);
+// pcl::PLYReader for binary little-endian files: x y z red green blue by name out of the vertex element (the files
+// save_ply_binary writes, build/cloud.ply); false if one is missing or the vertex layout is not fixed-size
 bool read_ply(const std::string& path, PointCloud& cloud);
 
 class RawImageData {  // pose.h:54-70
@@ -89,6 +92,12 @@ public:
     bool align_point_cloud = false;  // --align_point_cloud source.ply target.ply (pose.cpp:46-112): ICP through o3dr_icp_align
     int icp_max_iterations = 10;     // --icp_max_iterations (pcl::Registration defaults)
     double icp_max_corr_dist = HUGE_VAL, icp_transformation_epsilon = 0.0;  // --icp_max_corr_dist, --icp_transformation_epsilon
+    bool smooth_surface = false;     // --smooth_surface file.ply (pose.cpp:27-112): MLS through o3dr_mls_smooth
+    double search_radius = 0.0;      // --search_radius: required by --smooth_surface, ignored elsewhere
+    bool search_radius_set = false;
+    int mls_polynomial_order = 2;    // --mls_polynomial_order (PCL's default)
+    double mls_sqr_gauss_param = 0.0;  // --mls_sqr_gauss_param (0: search_radius^2)
+    bool mls_normals = false;        // --mls_normals: PointXYZRGBNormal output
     int device_id = 0;
     int n_gpus = 1;                 // --gpus N: frames sharded over devices device_id .. device_id+N-1, one host thread and
                                     // one context each, merged through o3dr_merge_partitioned (RCCL)
@@ -125,6 +134,7 @@ private:
     void run_reconstruction();
     void run_sharded(PointCloud::Ptr cloud_small);  // --gpus N
     void run_align_point_cloud();                   // --align_point_cloud
+    void run_smooth_surface();                      // --smooth_surface
     int first_img_num = -1, last_img_num = -1;
     bool run3d_reconstruction = true;
     std::vector<std::vector<double>> pose_data, images_times_data;

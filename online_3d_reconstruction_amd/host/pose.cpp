@@ -399,6 +399,11 @@ void Pose::printUsage()
             "       [--icp_transformation_epsilon e]   (point-to-point ICP of source onto target: prints T, fitness, correspondences,\n"
             "                     iterations and the reason it stopped; writes the source moved by T as aligned_<source> next to\n"
             "                     it - that file name is this build's own)\n"
+            "./pose --smooth_surface file.ply --search_radius r [--mls_polynomial_order 0|1|2] [--mls_sqr_gauss_param h]\n"
+            "       [--mls_normals]   (moving-least-squares smoothing: writes the fitted points, in input order, as\n"
+            "                     smoothed_<file> next to it - that file name is this build's own; --search_radius is required\n"
+            "                     here; --mls_normals adds normal_x normal_y normal_z curvature per point)\n"
+            "--search_radius is ignored in every other mode.\n"
             "Pose estimation (ORB matching, the ICP trajectory correction), visualisation and the mesh/segment tools are not\n"
             "part of this build.\n";
 }
@@ -426,6 +431,16 @@ int Pose::parseCmdArgs(int argc, char** argv)
             read_PLY_filename0 = argv[++i];
             read_PLY_filename1 = argv[++i];
         }
+        else if (a == "--smooth_surface") {
+            if (i + 1 >= argc || string(argv[i + 1]).rfind("--", 0) == 0)
+                throw runtime_error("missing argument: --smooth_surface needs file.ply");
+            smooth_surface = true;
+            run3d_reconstruction = false;
+            read_PLY_filename0 = argv[++i];
+        }
+        else if (a == "--mls_polynomial_order") mls_polynomial_order = atoi(need(i));
+        else if (a == "--mls_sqr_gauss_param") mls_sqr_gauss_param = atof(need(i));
+        else if (a == "--mls_normals") mls_normals = true;
         else if (a == "--icp_max_iterations") icp_max_iterations = atoi(need(i));
         else if (a == "--icp_max_corr_dist") icp_max_corr_dist = atof(need(i));
         else if (a == "--icp_transformation_epsilon") icp_transformation_epsilon = atof(need(i));
@@ -449,7 +464,8 @@ int Pose::parseCmdArgs(int argc, char** argv)
         else if (a == "--device") device_id = atoi(need(i));
         else if (a == "--gpus") n_gpus = atoi(need(i));
         else if (a == "--partitioned_merge") partitioned_merge = true;
-        else if (a == "--dist_nearby" || a == "--search_radius" || a == "--range_width") { need(i); }
+        else if (a == "--search_radius") { search_radius = atof(need(i)); search_radius_set = true; }  // --smooth_surface only
+        else if (a == "--dist_nearby" || a == "--range_width") { need(i); }
         else if (a == "--preview") preview = true;
         else if (a == "--use_segment_labels" || a == "--segment_cloud" || a == "--displayUAVPositions" ||
                  a == "--test_bad_data_rejection")
@@ -510,6 +526,52 @@ void Pose::run_align_point_cloud()
     save_pt_cloud_to_PLY_File(aligned, out);
 }
 
+// pose.cpp:27-112 --smooth_surface: pcl::MovingLeastSquares over one PLY, here o3dr_mls_smooth (contract: include/o3dr.h).
+// The points with a fit (MLS_POLY or MLS_PLANE) are written in input order as smoothed_<file> next to it, with
+// --mls_normals in PointXYZRGBNormal's layout.
+void Pose::run_smooth_surface()
+{
+    if (!search_radius_set) throw runtime_error("missing argument: --smooth_surface needs --search_radius r");
+    Q = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // the tool needs no camera
+    PointCloud::Ptr cloud = read_PLY_File(read_PLY_filename0);
+    const int64_t n = (int64_t)cloud->points.size();
+    o3dr_mls_params prm;
+    o3dr_mls_default_params(&prm);
+    prm.search_radius = search_radius;
+    prm.polynomial_order = mls_polynomial_order;
+    prm.sqr_gauss_param = mls_sqr_gauss_param;
+    vector<PointXYZRGB> out((size_t)n);
+    vector<float> nrm(mls_normals ? (size_t)n * 4 : 0);
+    vector<uint8_t> fit((size_t)n);
+    o3dr_mls_result res;
+    o3dr_ctx* c = ctx_for_this_thread();
+    const auto t0 = chrono::steady_clock::now();
+    chk(o3dr_mls_smooth(c, cloud->points.data(), n, &prm, out.data(), mls_normals ? nrm.data() : nullptr, nullptr, fit.data(), &res,
+                        O3DR_MEM_HOST),
+        "o3dr_mls_smooth");
+    const double ms = chrono::duration<double, milli>(chrono::steady_clock::now() - t0).count();
+    PointCloud::Ptr kept(new PointCloud());
+    vector<float> kept_nrm;
+    for (int64_t i = 0; i < n; ++i) {
+        if (fit[(size_t)i] == O3DR_MLS_NONE) continue;
+        kept->points.push_back(out[(size_t)i]);
+        if (mls_normals) kept_nrm.insert(kept_nrm.end(), nrm.begin() + 4 * i, nrm.begin() + 4 * i + 4);
+    }
+    cout << "points in " << n << endl;
+    cout << "fitted " << res.n_poly + res.n_plane << " (poly " << res.n_poly << ", plane " << res.n_plane << ")" << endl;
+    cout << "dropped " << res.n_none << endl;
+    cout << "max neighbors " << res.max_neighbors << endl;
+    char line[64];
+    snprintf(line, sizeof line, "mls time %.3f ms", ms);
+    cout << line << endl;
+    string outp = read_PLY_filename0;
+    const size_t slash = outp.find_last_of('/');
+    outp = (slash == string::npos ? string() : outp.substr(0, slash + 1)) + "smoothed_" +
+           (slash == string::npos ? outp : outp.substr(slash + 1));
+    if (!save_ply_binary(outp, *kept, mls_normals ? &kept_nrm : nullptr)) throw runtime_error("could not write " + outp);
+    cerr << "Saved Point Cloud with " << kept->points.size() << " data points to " << outp << endl;
+}
+
 // pose.cpp:23-565 restricted to the hot path
 Pose::Pose(int argc, char* argv[])
 {
@@ -528,6 +590,10 @@ Pose::Pose(int argc, char* argv[])
     }
     if (align_point_cloud) {
         run_align_point_cloud();
+        return;
+    }
+    if (smooth_surface) {
+        run_smooth_surface();
         return;
     }
     if (!run3d_reconstruction) return;
