@@ -445,6 +445,77 @@ void o3dr_mls_default_params(o3dr_mls_params* p);
 int  o3dr_mls_smooth(o3dr_ctx* ctx, const o3dr_point* cloud, int64_t n, const o3dr_mls_params* p, o3dr_point* out,
                      float* normals, uint32_t* nn_count, uint8_t* fit, o3dr_mls_result* res, int32_t mem);
 
+/* ---- RANSAC plane segmentation, whole cloud or per XY tile: pcl::SACSegmentation (SACMODEL_PLANE, SAC_RANSAC,
+ * optimizeCoefficients) and pcl::ProjectInliers as the reference's segmentCloud uses them (pose_functions.cpp:2094-2249).
+ * The reference's call parameters and PCL's host random sampler cannot be pinned here, so the contract below is this
+ * library's own; where PCL leaves something open it is made exact.
+ *
+ * Input: n points, every coordinate finite.  t = distance_threshold (finite, > 0), H = max_iterations (1 <= H <= 2^20),
+ * s = tile_size (0: the whole cloud is one tile, else finite and > 0), seed, optimize (0 or 1).
+ *   1. Tiles: ix = floor((double)x / s), iy = floor((double)y / s), both within int32.  Only non-empty tiles exist, ordered
+ *      by (iy, ix) ascending; a tile's points are listed in input order.  key = ((uint64)(uint32)iy << 32) | (uint32)ix;
+ *      s = 0: one tile, ix = iy = 0, key 0.  m = the tile's point count.
+ *   2. Sampling: splitmix64(x) = mix(x + 0x9E3779B97F4A7C15) with mix(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9,
+ *      z = (z ^ (z >> 27)) * 0x94D049BB133111EB, z ^ (z >> 31) (all mod 2^64).  A tile's stream S = splitmix64(seed ^ key);
+ *      draw k (0, 1, 2) of hypothesis h (0 <= h < H) is r = splitmix64(S + 3h + k), local index ((r >> 32) * m) >> 32.
+ *      A tile's result therefore equals a call with s = 0 on that tile's points (input order) and seed ^ key.
+ *   3. Hypothesis plane in fp64 without FMA from the fp32 points p0 p1 p2: e1 = p1 - p0, e2 = p2 - p0, (a, b, c) = e1 x e2
+ *      (a = e1y e2z - e1z e2y, b = e1z e2x - e1x e2z, c = e1x e2y - e1y e2x), L2 = (a a + b b) + c c.  Degenerate if two
+ *      indices are equal or L2 <= 1e-12 (e1.e1)(e2.e2) (dots as (x x + y y) + z z).  n = (a, b, c) / sqrt(L2),
+ *      d = -((nx x0 + ny y0) + nz z0); oriented so that nz > 0 (nz == 0: ny > 0; both 0: nx > 0) by flipping all four; the
+ *      scored plane (A, B, C, D) is the four rounded to fp32.
+ *   4. Score: the points of the tile with |((A x + B y) + C z) + D| < (float)t in fp32 without FMA (PCL's strict test).
+ *      Every hypothesis is scored (no adaptive stop).  The chosen one has the largest count, the smallest h on a tie;
+ *      degenerate hypotheses never win.  Status O3DR_PLANE_TOO_FEW (m < 3: nothing drawn) or O3DR_PLANE_DEGENERATE (every
+ *      hypothesis degenerate): coefficients NaN, hypothesis -1, sample 0xffffffff, every point of the tile an outlier.
+ *   5. Refinement (optimize = 1, the chosen plane has >= 3 inliers): centroid c and covariance (divided by k) of those
+ *      inliers in fp64, accumulated about the chosen sample's p0 and then shifted.  Order: every run of 128 consecutive
+ *      points of the tile (listing order) is summed by 64 lanes (lane j: points j and 64 + j, in that order), then by an
+ *      xor butterfly over the lanes (distance 32, 16, .., 1); lane j of one wave sums the runs j, j + 64, .. in ascending
+ *      order, then the same butterfly.  The unit eigenvector of the smallest eigenvalue l0 <= l1 <= l2 by the cyclic Jacobi
+ *      of o3dr_mls_smooth.  l1 <= 1e-12 l2: the hypothesis plane stays (refined 0).  Else n is oriented as in 3,
+ *      d = -((nx cx + ny cy) + nz cz) in fp64, both rounded to fp32 (refined 1).
+ *   6. Labels: the score test of 4 with the final fp32 plane.  Projection: an inlier becomes q = p - dist (A, B, C) in fp32
+ *      (dist the test's signed value, the product then the difference); outliers are copied; rgba is always copied.
+ * Every count is an integer sum and every fp64 sum runs in the fixed order above: results are bit-identical across calls
+ * and across host and device memory.
+ * Outputs, all in `mem`, each optional (NULL: skipped), per point index-aligned with the input: inlier (n bytes, 1/0),
+ * tile (n int32: the point's tile ordinal), projected (n points), tiles (up to tiles_capacity records in tile order);
+ * *n_tiles (host) = the tile count.  tiles_capacity < that count: O3DR_ERR_CAPACITY with *n_tiles set and nothing else
+ * written.  Limits, else O3DR_ERR_INVALID_ARG: n <= 2^32-1; tile indices within int32;
+ * (ix_max - ix_min + 1)(iy_max - iy_min + 1) <= 2^32-1 (the dense tile id is a 32-bit sort key); n_tiles H <= 2^31.
+ * n == 0 is OK (no tiles).  A non-finite
+ * coordinate anywhere or a bad parameter: O3DR_ERR_INVALID_ARG.  On an error other than CAPACITY the host outputs are
+ * zeroed and *n_tiles is 0.  The call synchronises.  It reuses the sort workspace: a pending
+ * o3dr_cloud_big_slice_counts_dev table is dropped; cloud_big is left alone. */
+typedef struct o3dr_plane_params {
+    double   distance_threshold;  /* > 0, finite; no usable default (0 is rejected) */
+    int32_t  max_iterations;      /* hypotheses per tile, 1 .. 2^20; default 1000 */
+    double   tile_size;           /* 0 (default): one tile; else > 0, finite */
+    uint64_t seed;                /* default 0 */
+    int32_t  optimize;            /* 1 (default): least-squares refinement; 0: the RANSAC plane */
+} o3dr_plane_params;
+typedef struct o3dr_plane_tile {  /* 64 bytes */
+    float    coeff[4];            /* A B C D (fp32), NaN unless status OK */
+    int32_t  ix, iy;              /* tile indices (0, 0 when tile_size is 0) */
+    uint32_t n_points;            /* m */
+    uint32_t n_inliers;           /* final inliers (step 6) */
+    uint32_t ransac_inliers;      /* the chosen hypothesis's count (step 4) */
+    int32_t  hypothesis;          /* the chosen h, -1 if none */
+    uint32_t sample[3];           /* its three input indices, 0xffffffff if none */
+    int32_t  refined;             /* 1: the plane of step 5 */
+    int32_t  status;              /* O3DR_PLANE_* */
+    uint32_t reserved;            /* 0 */
+} o3dr_plane_tile;
+#define O3DR_PLANE_OK         0
+#define O3DR_PLANE_TOO_FEW    1
+#define O3DR_PLANE_DEGENERATE 2
+#define O3DR_PLANE_MAX_ITERATIONS (1 << 20)
+void o3dr_plane_default_params(o3dr_plane_params* p);
+int  o3dr_segment_plane(o3dr_ctx* ctx, const o3dr_point* cloud, int64_t n, const o3dr_plane_params* p, uint8_t* inlier,
+                        int32_t* tile, o3dr_point* projected, o3dr_plane_tile* tiles, int64_t tiles_capacity, int64_t* n_tiles,
+                        int32_t mem);
+
 /* ---- measurement hooks (bench.py; not part of the reference surface) ------------------------ */
 /* kernel ids for o3dr_profile_* */
 #define O3DR_K_COUNT        0  /* grid-pass valid count per tile */

@@ -33,6 +33,11 @@ int o3dr_test_local_comm_destroy(void* comm);
 int o3dr_test_merge_partitioned_local(o3dr_ctx* ctx, void* local_comm, int32_t rank, int32_t gather_result, o3dr_point* out,
                                       int64_t out_capacity, int64_t* n_out, int64_t* n_total, uint32_t* status, int32_t mem);
 int o3dr_test_fail_at(o3dr_ctx* ctx, int32_t point);
+/* The hypotheses of the last successful o3dr_segment_plane of this context with at least one tile: n_tiles * H planes
+ * (4 floats each, NaN for a degenerate hypothesis) and their scores, tile-major, into host memory.  *n_out = n_tiles * H;
+ * capacity (in hypotheses) below it: O3DR_ERR_CAPACITY with *n_out set.  The scores are what the choice of step 4 of the
+ * contract reads, so the tests compare every one of them with a restatement. */
+int o3dr_test_plane_hypotheses(o3dr_ctx* ctx, float* planes, uint32_t* counts, int64_t capacity, int64_t* n_out);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,7 @@ generates the benchmark inputs of SURVEY.md section 8d, `dist` shards frames ove
 There is no CPU fallback: importing works anywhere, but creating a `Context` without the built
 library or without a GPU raises.
 """
-from ._lib import POINT, O3drError, lib_path, load_library  # noqa: F401
+from ._lib import PLANE_TILE, POINT, O3drError, lib_path, load_library  # noqa: F401
 from .api import Context, IcpResult, MlsResult, Params  # noqa: F401
 
-__all__ = ["Context", "IcpResult", "MlsResult", "Params", "POINT", "O3drError", "lib_path", "load_library"]
+__all__ = ["Context", "IcpResult", "MlsResult", "Params", "PLANE_TILE", "POINT", "O3drError", "lib_path", "load_library"]

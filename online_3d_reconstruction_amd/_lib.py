@@ -55,6 +55,20 @@ class MlsResultStruct(C.Structure):
 MLS_NONE, MLS_PLANE, MLS_POLY = range(3)
 
 
+class PlaneParamsStruct(C.Structure):
+    _fields_ = [("distance_threshold", C.c_double), ("max_iterations", C.c_int32), ("tile_size", C.c_double),
+                ("seed", C.c_uint64), ("optimize", C.c_int32)]
+
+
+# o3dr_plane_tile (64 bytes), as a numpy record: Context.segmentPlane returns the tile records in this layout
+PLANE_TILE = np.dtype([("coeff", "<f4", (4,)), ("ix", "<i4"), ("iy", "<i4"), ("n_points", "<u4"), ("n_inliers", "<u4"),
+                       ("ransac_inliers", "<u4"), ("hypothesis", "<i4"), ("sample", "<u4", (3,)), ("refined", "<i4"),
+                       ("status", "<i4"), ("reserved", "<u4")])
+assert PLANE_TILE.itemsize == 64
+PLANE_OK, PLANE_TOO_FEW, PLANE_DEGENERATE = range(3)
+PLANE_MAX_ITERATIONS = 1 << 20
+
+
 def lib_path():
     return _LIB
 
@@ -119,6 +133,8 @@ SYMBOLS = [
     ("o3dr_icp_align", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, C.POINTER(IcpParamsStruct), C.POINTER(IcpResultStruct), _i32]),
     ("o3dr_mls_default_params", None, [C.POINTER(MlsParamsStruct)]),
     ("o3dr_mls_smooth", C.c_int, [_vp, _vp, _i64, C.POINTER(MlsParamsStruct), _vp, _vp, _vp, _vp, C.POINTER(MlsResultStruct), _i32]),
+    ("o3dr_plane_default_params", None, [C.POINTER(PlaneParamsStruct)]),
+    ("o3dr_segment_plane", C.c_int, [_vp, _vp, _i64, C.POINTER(PlaneParamsStruct), _vp, _vp, _vp, _vp, _i64, _pi64, _i32]),
     ("o3dr_profile_enable", C.c_int, [_vp, _i32, _i32]),
     ("o3dr_profile_read", C.c_int, [_vp, _i32, C.POINTER(C.c_double), _pi64]),
     ("o3dr_profile_reset", C.c_int, [_vp]),
@@ -129,6 +145,7 @@ SYMBOLS = [
     ("o3dr_test_local_comm_destroy", C.c_int, [_vp]),
     ("o3dr_test_merge_partitioned_local", C.c_int, [_vp, _vp, _i32, _i32, _vp, _i64, _pi64, _pi64, C.POINTER(C.c_uint32), _i32]),
     ("o3dr_test_fail_at", C.c_int, [_vp, _i32]),
+    ("o3dr_test_plane_hypotheses", C.c_int, [_vp, _vp, _vp, _i64, _pi64]),
     ("o3dr_device_info", C.c_int, [_vp, C.c_char_p, _i32, C.POINTER(_i32), _pi64]),
 ]
 

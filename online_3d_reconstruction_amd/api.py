@@ -378,6 +378,57 @@ class Context:
             ret += (cnt, fit, MlsResult(int(res.n_poly), int(res.n_plane), int(res.n_none), int(res.max_neighbors)))
         return ret[0] if len(ret) == 1 else ret
 
+    # -- plane segmentation (pcl::SACSegmentation + ProjectInliers, segmentCloud: pose_functions.cpp:2094-2249) -----------
+    def segmentPlane(self, pts, distance_threshold, max_iterations=1000, tile_size=0.0, seed=0, optimize=True, project=False,
+                     return_tile_index=False):
+        """RANSAC plane segmentation of the whole cloud (tile_size 0) or of every XY tile (contract: include/o3dr.h,
+        DESIGN.md "Plane segmentation").  numpy POINT arrays, or torch [N,4] 4-byte CUDA tensors such as cloudBigView() or
+        finalize(device=...) (per-point results are then CUDA tensors).  -> (inlier mask (bool, index-aligned with `pts`),
+        tile records (numpy PLANE_TILE array, tile order)); with project also the points with the inliers projected onto
+        their tile's plane; with return_tile_index also every point's tile ordinal (int32)."""
+        pts, n = self._cloud(pts)
+        p_in, mem, _k = _ptr(pts)
+        prm = L.PlaneParamsStruct(float(distance_threshold), int(max_iterations), float(tile_size), int(seed) & (2**64 - 1),
+                                  1 if optimize else 0)
+        n_tiles = C.c_int64(0)
+        cap = 1 if tile_size == 0 else 64
+        for attempt in range(2):  # one retry with the tile count the first call reported
+            if mem == L.MEM_DEVICE:
+                import torch
+                dev = pts.device
+                inl = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+                til = torch.empty(max(n, 1), dtype=torch.int32, device=dev) if return_tile_index else None
+                prj = torch.empty_like(pts) if project else None
+                rec = torch.empty((cap, 64), dtype=torch.uint8, device=dev)
+                self._order_after_torch()
+                ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+                rc = self._lib.o3dr_segment_plane(self._h, p_in, n, C.byref(prm), ptr(inl) if n else None, ptr(til) if n else None,
+                                                  ptr(prj) if n else None, rec.data_ptr(), cap, C.byref(n_tiles), L.MEM_DEVICE)
+            else:
+                inl = np.empty(n, np.uint8)
+                til = np.empty(n, np.int32) if return_tile_index else None
+                prj = np.empty(n, POINT) if project else None
+                rec = np.empty(cap, L.PLANE_TILE)
+                ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+                rc = self._lib.o3dr_segment_plane(self._h, p_in, n, C.byref(prm), ptr(inl) if n else None, ptr(til) if n else None,
+                                                  ptr(prj) if n else None, rec.ctypes.data, cap, C.byref(n_tiles), mem)
+            if rc == L.ERR_CAPACITY and attempt == 0:
+                cap = int(n_tiles.value)
+                continue
+            L.check(rc)
+            break
+        nt = int(n_tiles.value)
+        if mem == L.MEM_DEVICE:
+            tiles = rec[:nt].cpu().numpy().view(L.PLANE_TILE).reshape(nt)
+        else:
+            tiles = rec[:nt].copy()
+        ret = (inl[:n] != 0, tiles)
+        if project:
+            ret += (prj[:n],)
+        if return_tile_index:
+            ret += (til[:n],)
+        return ret
+
     def voxelGrid(self, pts, leaf, min_points=0, z_offset=0.0, return_status=False):
         """pcl::VoxelGrid<PointXYZRGB> as the reference configures it (pose_functions.cpp:1689-1700)."""
         if not _is_torch(pts):

@@ -235,3 +235,39 @@ __device__ __forceinline__ void block_minmax_store(const float lo[3], const floa
     }
     __syncthreads();
 }
+
+// shared by MLS (kernels/mls.inc) and the plane refinement (kernels/plane.inc)
+constexpr int kMlsJacobiSweeps = 8;  // cyclic (0,1) (0,2) (1,2): converged to fp64 rounding well before
+// symmetric 3x3 eigen-decomposition by cyclic Jacobi: A (upper triangle used) -> eigenvalues on the diagonal, V's columns
+__device__ __forceinline__ void mls_jacobi3(double A[3][3], double V[3][3])
+{
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+    A[1][0] = A[0][1], A[2][0] = A[0][2], A[2][1] = A[1][2];
+#pragma unroll
+    for (int sweep = 0; sweep < kMlsJacobiSweeps; ++sweep) {
+#pragma unroll
+        for (int pq = 0; pq < 3; ++pq) {
+            const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2, r = 3 - p - q;
+            const double apq = A[p][q];
+            if (apq == 0.0) continue;
+            const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+            const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+            const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
+            A[p][p] -= t * apq;
+            A[q][q] += t * apq;
+            A[p][q] = A[q][p] = 0.0;
+            const double arp = A[r][p], arq = A[r][q];
+            A[r][p] = A[p][r] = cs * arp - sn * arq;
+            A[r][q] = A[q][r] = sn * arp + cs * arq;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const double vp = V[i][p], vq = V[i][q];
+                V[i][p] = cs * vp - sn * vq;
+                V[i][q] = sn * vp + cs * vq;
+            }
+        }
+    }
+}

@@ -135,6 +135,9 @@ struct o3dr_ctx {
     DevBuf nn_q, nn_t, nn_cells, nn_src;
     // o3dr_mls_smooth: the staged outputs of a host call and the device counters / non-finite flag
     DevBuf mls_out, mls_misc;
+    // o3dr_segment_plane: points in tile order + run heads, tile tables, hypotheses + scores, flags, staged host outputs
+    DevBuf pl_pts, pl_tiles, pl_hyp, pl_misc, pl_out;
+    uint64_t pl_last_hyp = 0;  // hypotheses of the last call in pl_hyp (o3dr_test_plane_hypotheses)
     int64_t place_ub = -1;   // o3dr_cloud_big_slice_counts_dev ran for a cloud of at most this many points and place_parts slices:
     int place_parts = 0;     // the (slice, tile) table in the workspace is what o3dr_cloud_big_place_slices moves by
     int test_hooks = 0;    // O3DR_TEST_HOOKS=1 at o3dr_ctx_create: the entry points of include/o3dr_testing.h act
@@ -475,7 +478,8 @@ extern "C" int o3dr_ctx_destroy(o3dr_ctx* c)
         dev_release(c->inc.cells[i]);
     }
     for (DevBuf* b : {&c->inc.box, &c->inc.scratch, &c->inc.tg, &c->inc.tmatch, &c->inc.flag, &c->inc.src, &c->inc.keep,
-                      &c->inc.partial, &c->inc.words, &c->inc.fb, &c->nn_q, &c->nn_t, &c->nn_cells, &c->nn_src, &c->mls_out, &c->mls_misc})
+                      &c->inc.partial, &c->inc.words, &c->inc.fb, &c->nn_q, &c->nn_t, &c->nn_cells, &c->nn_src, &c->mls_out, &c->mls_misc,
+                      &c->pl_pts, &c->pl_tiles, &c->pl_hyp, &c->pl_misc, &c->pl_out})
         dev_release(*b);
     delete c;
     return O3DR_OK;
@@ -3208,6 +3212,166 @@ extern "C" int o3dr_mls_smooth(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, 
         res->max_neighbors = (int32_t)std::min<unsigned long long>(cnt_h[3], 0x7fffffffull);
     }
     return O3DR_OK;
+}
+
+// -------------------------------------------------------------------------------------------------
+// RANSAC plane segmentation per XY tile (kernels/plane.inc; DESIGN.md "Plane segmentation")
+// -------------------------------------------------------------------------------------------------
+extern "C" void o3dr_plane_default_params(o3dr_plane_params* p)
+{
+    if (!p) return;
+    p->distance_threshold = 0.0;  // no usable default: the caller sets it
+    p->max_iterations = 1000;     // pcl::SACSegmentation max_iterations_ (50 in PCL 1.8 is for the adaptive loop)
+    p->tile_size = 0.0;           // the whole cloud
+    p->seed = 0;
+    p->optimize = 1;              // setOptimizeCoefficients(true)
+}
+
+static int segment_plane(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const o3dr_plane_params* p, uint8_t* inlier,
+                         int32_t* tile, o3dr_point* projected, o3dr_plane_tile* tiles, int64_t tiles_capacity, int64_t* n_tiles,
+                         int32_t mem)
+{
+    CHK(nn_check_cloud(n, cloud));
+    if (!p) return fail(O3DR_ERR_INVALID_ARG, "params is NULL");
+    if (!n_tiles) return fail(O3DR_ERR_INVALID_ARG, "n_tiles is NULL");
+    if (tiles_capacity < 0 || (tiles_capacity > 0 && !tiles)) return fail(O3DR_ERR_INVALID_ARG, "bad tiles / tiles_capacity");
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    const double t = p->distance_threshold, ts = p->tile_size;
+    if (!(std::isfinite(t) && t > 0.0)) return fail(O3DR_ERR_INVALID_ARG, "distance_threshold must be finite and > 0");
+    if (p->max_iterations < 1 || p->max_iterations > O3DR_PLANE_MAX_ITERATIONS)
+        return fail(O3DR_ERR_INVALID_ARG, "max_iterations must be in [1, 2^20]");
+    if (!(std::isfinite(ts) && ts >= 0.0)) return fail(O3DR_ERR_INVALID_ARG, "tile_size must be 0 or finite and > 0");
+    if (p->optimize != 0 && p->optimize != 1) return fail(O3DR_ERR_INVALID_ARG, "optimize must be 0 or 1");
+    c->place_ub = -1;
+    if (n == 0) return O3DR_OK;
+    const bool tiled = ts > 0.0;
+    CHK(dev_ensure(c, c->pl_misc, 256));
+    uint32_t* flag = (uint32_t*)c->pl_misc.p;                     // [0] non-finite, [1] tile index out of int32
+    int32_t* range = (int32_t*)((char*)c->pl_misc.p + 64);        // ix_min ix_max iy_min iy_max (order-preserving)
+    uint32_t* n_tiles_dev = (uint32_t*)((char*)c->pl_misc.p + 128);
+    const void* cloud_d;
+    CHK(stage_in(c, c->nn_t, cloud, (size_t)n * sizeof(o3dr_point), mem, &cloud_d));
+    launch_mls_finite(&c->prof, c->stream, (const o3dr_point*)cloud_d, n, flag);
+    if (tiled) launch_plane_range(&c->prof, c->stream, (const o3dr_point*)cloud_d, n, ts, range, flag);
+    HIPCHK(hipGetLastError());
+    uint32_t hbuf[6];
+    HIPCHK(hipMemcpyAsync(hbuf, flag, 8, hipMemcpyDeviceToHost, c->stream));
+    if (tiled) HIPCHK(hipMemcpyAsync(hbuf + 2, range, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (hbuf[0]) return fail(O3DR_ERR_INVALID_ARG, "the cloud has a non-finite coordinate");
+    if (tiled && hbuf[1]) return fail(O3DR_ERR_INVALID_ARG, "a tile index does not fit in int32 (tile_size too small)");
+
+    PlaneArgs a;
+    memset(&a, 0, sizeof a);
+    a.cloud = (const o3dr_point*)cloud_d;
+    a.pts = (const float4*)cloud_d;
+    a.tiled = tiled ? 1 : 0;
+    a.n = (uint32_t)n;
+    a.H = (uint32_t)p->max_iterations;
+    a.s = ts;
+    a.tf = (float)t;
+    a.seed = p->seed;
+    a.range = range;
+    uint64_t T = 1;
+    if (tiled) {
+        const uint64_t wx = (uint64_t)(hbuf[3] - hbuf[2]) + 1, wy = (uint64_t)(hbuf[5] - hbuf[4]) + 1;
+        if (wx * wy > 0xffffffffull) return fail(O3DR_ERR_INVALID_ARG, "the tiles' index box holds more than 2^32-1 tiles");
+        a.wx = (uint32_t)wx;
+        const uint64_t max_key = wx * wy - 1;
+        int nbits = 0;
+        while (nbits < 32 && (max_key >> nbits) != 0) ++nbits;
+        CHK(ws_ensure(c, 1, n, false));
+        const size_t b_pts = align256((size_t)n * sizeof(float4));
+        CHK(dev_ensure(c, c->pl_pts, b_pts + align256((size_t)n * 4)));
+        float4* pts = (float4*)c->pl_pts.p;
+        uint32_t* head = (uint32_t*)((char*)c->pl_pts.p + b_pts);
+        launch_plane_order(&c->prof, c->stream, c->ws, a, nbits, head, pts, n_tiles_dev);
+        HIPCHK(hipGetLastError());
+        uint32_t th = 0;
+        HIPCHK(hipMemcpyAsync(&th, n_tiles_dev, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        T = th;
+    }
+    *n_tiles = (int64_t)T;
+    if ((int64_t)T > tiles_capacity && tiles) return fail(O3DR_ERR_CAPACITY, "tiles_capacity is below the tile count");
+    if (T * (uint64_t)a.H > (1ull << 31)) return fail(O3DR_ERR_INVALID_ARG, "n_tiles * max_iterations exceeds 2^31");
+    a.n_tiles = (uint32_t)T;
+    const int64_t max_chunks = n / kPlaneChunkPoints + (int64_t)T;
+    if (!tiled) CHK(ws_ensure(c, 1, 1, false));  // (the scan's chunk partials)
+    const size_t b_ts = align256((T + 1) * 4), b_rec = align256(T * sizeof(o3dr_plane_tile));
+    CHK(dev_ensure(c, c->pl_tiles, 2 * b_ts + b_rec + align256((size_t)max_chunks * kPlaneMomentsHost * 8)));
+    char* tb = (char*)c->pl_tiles.p;
+    a.tstart = (uint32_t*)tb;
+    a.cfirst = (uint32_t*)(tb + b_ts);
+    a.rec = (o3dr_plane_tile*)(tb + 2 * b_ts);
+    a.partial = (double*)(tb + 2 * b_ts + b_rec);
+    const size_t b_hyp = align256(T * a.H * sizeof(float4));
+    CHK(dev_ensure(c, c->pl_hyp, b_hyp + align256(T * a.H * 4)));
+    a.hyp = (float4*)c->pl_hyp.p;
+    a.counts = (uint32_t*)((char*)c->pl_hyp.p + b_hyp);
+    a.inlier = inlier;
+    a.tile = tile;
+    a.projected = projected;
+    if (mem == O3DR_MEM_HOST) {  // staged: labels, tile ordinals, projected points
+        const size_t b_in = align256((size_t)n), b_tl = align256((size_t)n * 4);
+        CHK(dev_ensure(c, c->pl_out, b_in + b_tl + (size_t)n * sizeof(o3dr_point)));
+        char* base = (char*)c->pl_out.p;
+        a.inlier = inlier ? (uint8_t*)base : nullptr;
+        a.tile = tile ? (int32_t*)(base + b_in) : nullptr;
+        a.projected = projected ? (o3dr_point*)(base + b_in + b_tl) : nullptr;
+    }
+    c->pl_last_hyp = 0;
+    launch_plane_tiles(&c->prof, c->stream, c->ws, a);
+    launch_plane_fit(&c->prof, c->stream, a, max_chunks, p->optimize);
+    HIPCHK(hipGetLastError());
+    const hipMemcpyKind back = mem == O3DR_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (tiles) HIPCHK(hipMemcpyAsync(tiles, a.rec, T * sizeof(o3dr_plane_tile), back, c->stream));
+    if (mem == O3DR_MEM_HOST) {
+        if (inlier) HIPCHK(hipMemcpyAsync(inlier, a.inlier, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        if (tile) HIPCHK(hipMemcpyAsync(tile, a.tile, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        if (projected) HIPCHK(hipMemcpyAsync(projected, a.projected, (size_t)n * sizeof(o3dr_point), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->pl_last_hyp = T * a.H;
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_test_plane_hypotheses(o3dr_ctx* c, float* planes, uint32_t* counts, int64_t capacity, int64_t* n_out)
+{
+    CTX_ENTER(c);
+    if (!c->test_hooks) return fail(O3DR_ERR_INVALID_ARG, "test hooks are off (create the context with O3DR_TEST_HOOKS=1)");
+    if (!n_out || capacity < 0 || (capacity > 0 && (!planes || !counts))) return fail(O3DR_ERR_INVALID_ARG, "bad arguments");
+    const uint64_t nh = c->pl_last_hyp;
+    *n_out = (int64_t)nh;
+    if ((uint64_t)capacity < nh) return fail(O3DR_ERR_CAPACITY, "capacity is below the hypothesis count");
+    if (nh == 0) return O3DR_OK;
+    const size_t b_hyp = align256(nh * sizeof(float4));
+    HIPCHK(hipMemcpyAsync(planes, c->pl_hyp.p, nh * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(counts, (char*)c->pl_hyp.p + b_hyp, nh * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_segment_plane(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const o3dr_plane_params* p, uint8_t* inlier,
+                                  int32_t* tile, o3dr_point* projected, o3dr_plane_tile* tiles, int64_t tiles_capacity,
+                                  int64_t* n_tiles, int32_t mem)
+{
+    if (n_tiles) *n_tiles = 0;
+    auto entered = [&]() -> int {
+        CTX_ENTER(c);
+        return segment_plane(c, cloud, n, p, inlier, tile, projected, tiles, tiles_capacity, n_tiles, mem);
+    };
+    const int rc = entered();
+    if (rc != O3DR_OK && rc != O3DR_ERR_CAPACITY) {  // host outputs zeroed on error
+        if (n_tiles) *n_tiles = 0;
+        if (mem == O3DR_MEM_HOST && n > 0 && n <= (int64_t)0xffffffffLL) {
+            if (inlier) memset(inlier, 0, (size_t)n);
+            if (tile) memset(tile, 0, (size_t)n * sizeof(int32_t));
+            if (projected && (const void*)projected != (const void*)cloud) memset(projected, 0, (size_t)n * sizeof(o3dr_point));
+        }
+        if (mem == O3DR_MEM_HOST && tiles && tiles_capacity > 0) memset(tiles, 0, (size_t)tiles_capacity * sizeof(o3dr_plane_tile));
+    }
+    return rc;
 }
 
 extern "C" int o3dr_profile_enable(o3dr_ctx* c, int32_t kernel_id, int32_t enable)

@@ -302,6 +302,41 @@ void launch_mls_finite(Profiler* pf, hipStream_t s, const o3dr_point* in, int64_
 void launch_mls(Profiler* pf, hipStream_t s, const Workspace& ws, const o3dr_point* cloud, int64_t n, const float* box6,
                 const float4* cell_lo, const float4* cell_hi, double r, int order, double h, o3dr_point* out, float* normals,
                 uint32_t* nn_count, uint8_t* fit, unsigned long long* counters);
+// RANSAC plane segmentation (kernels/plane.inc; the fields are filled by o3dr_segment_plane step by step)
+struct PlaneArgs {
+    const float4* pts;            // points in tile order: (x, y, z, original index bits) when tiled, else the cloud itself
+    const o3dr_point* cloud;      // the cloud in input order
+    int tiled;                    // 1: pts is the gathered tile order
+    uint32_t n, n_tiles, H;
+    const uint32_t* keys;         // tiled: the sorted dense tile ids
+    const uint32_t* tile_excl;    // tiled: exclusive scan of the run heads (tile ordinal of every run head)
+    const int32_t* range;         // tiled: ix_min, ix_max, iy_min, iy_max
+    uint32_t wx;                  // tiled: ix_max - ix_min + 1
+    double s;                     // tile size
+    float tf;                     // (float)distance_threshold
+    uint64_t seed;
+    uint32_t* tstart;             // n_tiles + 1: first point of every tile in tile order
+    uint32_t* cfirst;             // n_tiles + 1: first chunk of every tile; cfirst[n_tiles] = the chunk count
+    o3dr_plane_tile* rec;         // n_tiles records
+    float4* hyp;                  // n_tiles * H hypothesis planes (NaN: degenerate)
+    uint32_t* counts;             // n_tiles * H scores
+    double* partial;              // kPlaneMoments per chunk
+    uint8_t* inlier;              // n or nullptr
+    int32_t* tile;                // n or nullptr
+    o3dr_point* projected;        // n or nullptr
+};
+constexpr int kPlaneChunkPoints = 128;  // points per wave chunk (kPlaneChunk)
+constexpr int kPlaneMomentsHost = 10;   // fp64 moments per chunk (kPlaneMoments)
+// launch_plane_range: the order-preserving tile index range of the n points (range[4]: ix_min ix_max iy_min iy_max, each
+// as int32 ^ 0x80000000) and flag[1] = 1 if an index leaves int32.  launch_plane_order: the sort of the dense tile ids
+// (nbits wide) in ws, the run heads scanned into tile ordinals (head, n words; the tile count -> *n_tiles_dev), the points
+// gathered into tile order (pts).  launch_plane_tiles: tile starts, records and chunks (a.n_tiles set).
+// launch_plane_fit: hypotheses, scores, the choice, refinement (optimize) and labels.
+void launch_plane_range(Profiler* pf, hipStream_t s, const o3dr_point* in, int64_t n, double tile_size, int32_t* range, uint32_t* flag);
+void launch_plane_order(Profiler* pf, hipStream_t s, Workspace& ws, PlaneArgs& a, int nbits, uint32_t* head, float4* pts,
+                        uint32_t* n_tiles_dev);
+void launch_plane_tiles(Profiler* pf, hipStream_t s, Workspace& ws, const PlaneArgs& a);
+void launch_plane_fit(Profiler* pf, hipStream_t s, const PlaneArgs& a, int64_t max_chunks, int optimize);
 void launch_partition(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelArgs& v, int n_parts, o3dr_point* out,
                       uint64_t* counts_dev, uint32_t* overflow_dev, const void* hdrs_dev = nullptr, int n_hdrs = 0);
 // its two halves: slice sizes without moving anything (the (part, tile) table stays in ws for the second half), then the move

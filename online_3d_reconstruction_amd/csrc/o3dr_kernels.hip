@@ -28,6 +28,7 @@
 //   incremental  the combined merge kept as running per-cell sums (o3dr_finalize_incremental)
 //   nn           exact nearest neighbour into a target's search grid, the fused ICP pass and its fold
 //   mls          moving-least-squares smoothing and normals over the same grid
+//   plane        RANSAC plane segmentation per XY tile
 // The launchers follow in this file.
 #include <string.h>
 
@@ -49,6 +50,7 @@ namespace o3dr {
 #include "kernels/small.inc"
 #include "kernels/nn.inc"
 #include "kernels/mls.inc"
+#include "kernels/plane.inc"
 
 // =================================================================================================
 // launchers
@@ -623,16 +625,33 @@ void launch_partition(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelArg
     launch_partition_move(pf, s, ws, v, n_parts, out, nullptr);
 }
 
-// The search grid of a batch of clouds (see o3dr_device.h): plan, cell ids, radix sort of the cell ids, cell populations,
-// points gathered into cell order.  SOR and the nearest-neighbour search (kernels/nn.inc) both build theirs here.
-void launch_search_grid(Workspace& ws, hipStream_t s, const o3dr_point* in, int64_t in_fstride, const uint32_t* n_dev, int frames,
-                        int64_t cap, int mm_used, double cell_points, uint32_t active_above)
+// `passes` stable radix passes over ws.keys[0] / ws.vals (the plan in ws.geom, frames of at most cap records); the records
+// end in buffer passes & 1
+static void launch_radix_passes(Workspace& ws, hipStream_t s, int64_t cap, int passes, int frames = 1)
 {
     const int F = frames;
     const int n_sort_tiles = cdiv64(cap, kSortTile);
     const int64_t hist_row = (int64_t)kMaxRadix * n_sort_tiles;
     const size_t tm_lds = (size_t)n_sort_tiles * (kMaxRadix + 1) * sizeof(uint32_t);
     const int tm = tm_lds <= 48 * 1024 ? 1 : 0;
+    for (int pass = 0; pass < passes && pass < kMaxPasses; ++pass) {
+        k_radix_hist<<<dim3(n_sort_tiles, F), kSortThreads, 0, s>>>(ws.keys[0], ws.keys[1], cap, ws.geom, pass, n_sort_tiles, ws.hist,
+                                                                    ws.hist_part, tm);
+        if (tm)
+            k_scan_hist_tm<<<F, 1024, tm_lds, s>>>(ws.hist, ws.geom, pass, n_sort_tiles);
+        else
+            launch_scan(s, ws.hist, hist_row, hist_row, F, nullptr, nullptr, ws.scan_partial, ws.geom, pass, n_sort_tiles);
+        k_radix_scatter_lane<<<dim3(xcd_grid((int64_t)n_sort_tiles * kScatParts), F), kScatThreads, 0, s>>>(
+            ws.keys[0], ws.vals[0], ws.keys[1], ws.vals[1], cap, ws.geom, pass, n_sort_tiles, ws.hist, ws.hist_part, tm);
+    }
+}
+
+// The search grid of a batch of clouds (see o3dr_device.h): plan, cell ids, radix sort of the cell ids, cell populations,
+// points gathered into cell order.  SOR and the nearest-neighbour search (kernels/nn.inc) both build theirs here.
+void launch_search_grid(Workspace& ws, hipStream_t s, const o3dr_point* in, int64_t in_fstride, const uint32_t* n_dev, int frames,
+                        int64_t cap, int mm_used, double cell_points, uint32_t active_above)
+{
+    const int F = frames;
     const int64_t cell_stride = (int64_t)ws.sor_max_cells + 1;
     // The search grid never has more cells than points / 2 (and at least 1024): the cell ids of clouds of at most `cap`
     // points need ceil(log2(max_cells) / 7) sort passes, and only those are launched (a --jump_pixels 15 frame: 2 instead of
@@ -645,16 +664,7 @@ void launch_search_grid(Workspace& ws, hipStream_t s, const o3dr_point* in, int6
     k_sor_plan<<<F, 256, 0, s>>>(ws.mm, ws.mm_stride, mm_used, n_dev, max_cells, ws.sor_geom, ws.geom, cell_points, active_above);
     (void)hipMemsetAsync(ws.sor_cell_first, 0, (size_t)F * (size_t)cell_stride * 4, s);
     k_sor_cells<<<dim3(cdiv64(cap, 256), F), 256, 0, s>>>(in, in_fstride, ws.sor_geom, cap, ws.keys[0]);
-    for (int pass = 0; pass < sort_passes && pass < kMaxPasses; ++pass) {
-        k_radix_hist<<<dim3(n_sort_tiles, F), kSortThreads, 0, s>>>(ws.keys[0], ws.keys[1], cap, ws.geom, pass, n_sort_tiles, ws.hist,
-                                                                    ws.hist_part, tm);
-        if (tm)
-            k_scan_hist_tm<<<F, 1024, tm_lds, s>>>(ws.hist, ws.geom, pass, n_sort_tiles);
-        else
-            launch_scan(s, ws.hist, hist_row, hist_row, F, nullptr, nullptr, ws.scan_partial, ws.geom, pass, n_sort_tiles);
-        k_radix_scatter_lane<<<dim3(xcd_grid((int64_t)n_sort_tiles * kScatParts), F), kScatThreads, 0, s>>>(
-            ws.keys[0], ws.vals[0], ws.keys[1], ws.vals[1], cap, ws.geom, pass, n_sort_tiles, ws.hist, ws.hist_part, tm);
-    }
+    launch_radix_passes(ws, s, cap, sort_passes, F);
     k_sor_cell_counts<<<dim3(cdiv64(cap, 256), F), 256, 0, s>>>(ws.keys[0], ws.keys[1], ws.geom, ws.sor_geom, cap, cell_stride, ws.sor_cell_first);
     launch_scan(s, ws.sor_cell_first, cell_stride, cell_stride, F, nullptr, nullptr, ws.scan_partial);
     k_sor_gather<<<dim3(cdiv64(cap, 256), F), 256, 0, s>>>(in, in_fstride, ws.vals[0], ws.vals[1], ws.sor_geom, ws.geom, cap, ws.sor_xyz);
@@ -779,6 +789,71 @@ void launch_mls(Profiler* pf, hipStream_t s, const Workspace& ws, const o3dr_poi
         k_mls<1><<<blocks, kMlsThreads, 0, s>>>(a);
     else
         k_mls<2><<<blocks, kMlsThreads, 0, s>>>(a);
+}
+
+// RANSAC plane segmentation (kernels/plane.inc)
+void launch_plane_range(Profiler* pf, hipStream_t s, const o3dr_point* in, int64_t n, double tile_size, int32_t* range, uint32_t* flag)
+{
+    ProfScope ps(pf, O3DR_K_OTHER, s);
+    (void)hipMemsetAsync(flag + 1, 0, 4, s);
+    (void)hipMemsetAsync(range, 0xff, 4, s);
+    (void)hipMemsetAsync(range + 1, 0, 4, s);
+    (void)hipMemsetAsync(range + 2, 0xff, 4, s);
+    (void)hipMemsetAsync(range + 3, 0, 4, s);
+    if (n <= 0) return;
+    int g = cdiv64(n, 256);
+    if (g > 4096) g = 4096;
+    k_plane_range<<<g, 256, 0, s>>>(in, n, tile_size, range, flag);
+}
+
+void launch_plane_order(Profiler* pf, hipStream_t s, Workspace& ws, PlaneArgs& a, int nbits, uint32_t* head, float4* pts,
+                        uint32_t* n_tiles_dev)
+{
+    ProfScope ps(pf, O3DR_K_OTHER, s);
+    const int64_t n = a.n;
+    k_plane_keys<<<cdiv64(n, 256), 256, 0, s>>>(a, ws.keys[0]);
+    // the sort plan: at least one pass (it also writes the payload, the input index)
+    VoxelGeom g;
+    memset(&g, 0, sizeof g);
+    for (int k = 0; k < 3; ++k) g.inv[k] = 1.f, g.div_b[k] = 1;
+    g.mul1 = g.mul2 = 1;
+    g.n = a.n;
+    if (nbits < 1) nbits = 1;
+    g.passes = (uint32_t)((nbits + kMaxRadixBits - 1) / kMaxRadixBits);
+    g.bpp = (uint32_t)((nbits + (int)g.passes - 1) / (int)g.passes);
+    k_plane_sort_geom<<<1, 1, 0, s>>>(ws.geom, g);
+    launch_radix_passes(ws, s, n, (int)g.passes);
+    const int sorted = (int)(g.passes & 1u);
+    a.keys = ws.keys[sorted];
+    a.tile_excl = head;
+    a.pts = pts;
+    k_plane_heads<<<cdiv64(n, 256), 256, 0, s>>>(a, ws.vals[sorted], head, pts);
+    launch_scan(s, head, n, n, 1, n_tiles_dev, nullptr, ws.scan_partial);
+}
+
+void launch_plane_tiles(Profiler* pf, hipStream_t s, Workspace& ws, const PlaneArgs& a)
+{
+    ProfScope ps(pf, O3DR_K_OTHER, s);
+    k_plane_tiles<<<a.tiled ? cdiv64(a.n, 256) : 1, 256, 0, s>>>(a);
+    k_plane_chunks<<<cdiv64(a.n_tiles, 256), 256, 0, s>>>(a);
+    launch_scan(s, a.cfirst, a.n_tiles, a.n_tiles, 1, a.cfirst + a.n_tiles, nullptr, ws.scan_partial);
+}
+
+void launch_plane_fit(Profiler* pf, hipStream_t s, const PlaneArgs& a, int64_t max_chunks, int optimize)
+{
+    ProfScope ps(pf, O3DR_K_OTHER, s);
+    const uint64_t nh = (uint64_t)a.n_tiles * a.H;
+    (void)hipMemsetAsync(a.counts, 0, nh * sizeof(uint32_t), s);
+    k_plane_sample<<<(unsigned)((nh + 255) / 256), 256, 0, s>>>(a);
+    constexpr int wpb = kPlaneThreads / kWave;
+    const int chunk_blocks = cdiv64(max_chunks, wpb);  // waves past the chunk count return at once
+    k_plane_score<<<chunk_blocks, kPlaneThreads, 0, s>>>(a, a.hyp, a.counts);
+    k_plane_best<<<a.n_tiles, kWave, 0, s>>>(a);
+    if (optimize) {
+        k_plane_moments<<<chunk_blocks, kPlaneThreads, 0, s>>>(a);
+        k_plane_refine<<<a.n_tiles, kWave, 0, s>>>(a);
+    }
+    k_plane_label<<<chunk_blocks, kPlaneThreads, 0, s>>>(a);
 }
 
 }  // namespace o3dr

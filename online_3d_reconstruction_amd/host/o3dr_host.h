@@ -5,10 +5,11 @@
 // hot path that the CLI needs to run end to end (flag parsing, calibration/pose/time CSV readers,
 // timestamp binding, generateTmat, the variance gate, PNG/PLY I/O) is restated here in plain C++:
 // it is control plane, one call per frame or per run, and stays on the host.  Pose estimation (ORB,
-// matching, the ICP trajectory correction), visualisation and the mesh/segment tools are not part of
+// matching, the ICP trajectory correction), visualisation, the mesh tool and --segment_cloud in a reconstruction run are not part of
 // this build; the CLI runs with the recorded MAVLink poses (the reference's --only_MAVLink mode,
 // pose_functions.cpp:232-236).  The --align_point_cloud tool (ICP on two PLYs) runs on o3dr_icp_align, the
-// --smooth_surface tool (MLS on one PLY) on o3dr_mls_smooth.
+// --smooth_surface tool (MLS on one PLY) on o3dr_mls_smooth, the --segment_cloud_only tool (RANSAC planes per XY tile on
+// one PLY) on o3dr_segment_plane.
 #pragma once
 #include <array>
 #include <cmath>
@@ -98,6 +99,13 @@ public:
     int mls_polynomial_order = 2;    // --mls_polynomial_order (PCL's default)
     double mls_sqr_gauss_param = 0.0;  // --mls_sqr_gauss_param (0: search_radius^2)
     bool mls_normals = false;        // --mls_normals: PointXYZRGBNormal output
+    bool segment_cloud_only = false; // --segment_cloud_only file.ply (segmentCloud, pose_functions.cpp:2094-2249)
+    double sac_distance_threshold = 0.0;  // --sac_distance_threshold: required by --segment_cloud_only
+    bool sac_distance_threshold_set = false;
+    int sac_max_iterations = 1000;   // --sac_max_iterations
+    double segment_tile_size = 0.0;  // --segment_tile_size (0: one plane for the cloud)
+    unsigned long long sac_seed = 0; // --sac_seed
+    int sac_optimize = 1;            // --sac_optimize
     int device_id = 0;
     int n_gpus = 1;                 // --gpus N: frames sharded over devices device_id .. device_id+N-1, one host thread and
                                     // one context each, merged through o3dr_merge_partitioned (RCCL)
@@ -135,6 +143,7 @@ private:
     void run_sharded(PointCloud::Ptr cloud_small);  // --gpus N
     void run_align_point_cloud();                   // --align_point_cloud
     void run_smooth_surface();                      // --smooth_surface
+    void run_segment_cloud();                       // --segment_cloud_only
     int first_img_num = -1, last_img_num = -1;
     bool run3d_reconstruction = true;
     std::vector<std::vector<double>> pose_data, images_times_data;

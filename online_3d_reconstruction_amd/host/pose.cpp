@@ -404,8 +404,13 @@ void Pose::printUsage()
             "                     smoothed_<file> next to it - that file name is this build's own; --search_radius is required\n"
             "                     here; --mls_normals adds normal_x normal_y normal_z curvature per point)\n"
             "--search_radius is ignored in every other mode.\n"
-            "Pose estimation (ORB matching, the ICP trajectory correction), visualisation and the mesh/segment tools are not\n"
-            "part of this build.\n";
+            "./pose --segment_cloud_only file.ply --sac_distance_threshold t [--sac_max_iterations n] [--segment_tile_size m]\n"
+            "       [--sac_seed s] [--sac_optimize 0|1]   (RANSAC plane per XY tile of m metres, 0 = one plane for the cloud:\n"
+            "                     writes the inliers projected onto their tile's plane as ground_<file> and the rest as\n"
+            "                     nonground_<file>, both in input order, next to it - those file names are this build's own;\n"
+            "                     --sac_distance_threshold is required)\n"
+            "Pose estimation (ORB matching, the ICP trajectory correction), visualisation, the mesh tool and --segment_cloud in a\n"
+            "reconstruction run are not part of this build.\n";
 }
 
 int Pose::parseCmdArgs(int argc, char** argv)
@@ -438,6 +443,18 @@ int Pose::parseCmdArgs(int argc, char** argv)
             run3d_reconstruction = false;
             read_PLY_filename0 = argv[++i];
         }
+        else if (a == "--segment_cloud_only") {
+            if (i + 1 >= argc || string(argv[i + 1]).rfind("--", 0) == 0)
+                throw runtime_error("missing argument: --segment_cloud_only needs file.ply");
+            segment_cloud_only = true;
+            run3d_reconstruction = false;
+            read_PLY_filename0 = argv[++i];
+        }
+        else if (a == "--sac_distance_threshold") { sac_distance_threshold = atof(need(i)); sac_distance_threshold_set = true; }
+        else if (a == "--sac_max_iterations") sac_max_iterations = atoi(need(i));
+        else if (a == "--segment_tile_size") segment_tile_size = atof(need(i));
+        else if (a == "--sac_seed") sac_seed = strtoull(need(i), nullptr, 0);
+        else if (a == "--sac_optimize") sac_optimize = atoi(need(i));
         else if (a == "--mls_polynomial_order") mls_polynomial_order = atoi(need(i));
         else if (a == "--mls_sqr_gauss_param") mls_sqr_gauss_param = atof(need(i));
         else if (a == "--mls_normals") mls_normals = true;
@@ -572,6 +589,66 @@ void Pose::run_smooth_surface()
     cerr << "Saved Point Cloud with " << kept->points.size() << " data points to " << outp << endl;
 }
 
+// pose_functions.cpp:2094-2249 segmentCloud, its SACSegmentation (plane, RANSAC, optimizeCoefficients) and ProjectInliers
+// here o3dr_segment_plane over one PLY (contract: include/o3dr.h).  The inliers, projected onto their tile's plane, go to
+// ground_<file> and the other points to nonground_<file>, both in input order, next to the source.
+void Pose::run_segment_cloud()
+{
+    if (!sac_distance_threshold_set) throw runtime_error("missing argument: --segment_cloud_only needs --sac_distance_threshold t");
+    Q = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // the tool needs no camera
+    PointCloud::Ptr cloud = read_PLY_File(read_PLY_filename0);
+    const int64_t n = (int64_t)cloud->points.size();
+    o3dr_plane_params prm;
+    o3dr_plane_default_params(&prm);
+    prm.distance_threshold = sac_distance_threshold;
+    prm.max_iterations = sac_max_iterations;
+    prm.tile_size = segment_tile_size;
+    prm.seed = sac_seed;
+    prm.optimize = sac_optimize;
+    vector<uint8_t> inl((size_t)n);
+    vector<PointXYZRGB> proj((size_t)n);
+    vector<o3dr_plane_tile> tiles(segment_tile_size > 0.0 ? 256 : 1);
+    int64_t n_tiles = 0;
+    o3dr_ctx* c = ctx_for_this_thread();
+    const auto t0 = chrono::steady_clock::now();
+    int rc = o3dr_segment_plane(c, cloud->points.data(), n, &prm, inl.data(), nullptr, proj.data(), tiles.data(),
+                                (int64_t)tiles.size(), &n_tiles, O3DR_MEM_HOST);
+    if (rc == O3DR_ERR_CAPACITY) {
+        tiles.resize((size_t)n_tiles);
+        rc = o3dr_segment_plane(c, cloud->points.data(), n, &prm, inl.data(), nullptr, proj.data(), tiles.data(),
+                                (int64_t)tiles.size(), &n_tiles, O3DR_MEM_HOST);
+    }
+    chk(rc, "o3dr_segment_plane");
+    const double ms = chrono::duration<double, milli>(chrono::steady_clock::now() - t0).count();
+    PointCloud::Ptr ground(new PointCloud()), rest(new PointCloud());
+    for (int64_t i = 0; i < n; ++i) {
+        if (inl[(size_t)i]) ground->points.push_back(proj[(size_t)i]);
+        else rest->points.push_back(cloud->points[(size_t)i]);
+    }
+    cout << "points in " << n << endl;
+    cout << "tiles " << n_tiles << endl;
+    cout << "inliers " << ground->points.size() << endl;
+    char line[256];
+    for (int64_t k = 0; k < n_tiles && k < 10; ++k) {
+        const o3dr_plane_tile& r = tiles[(size_t)k];
+        snprintf(line, sizeof line, "tile %lld (%d, %d): points %u inliers %u status %d refined %d coeff %.9g %.9g %.9g %.9g", (long long)k,
+                 r.ix, r.iy, r.n_points, r.n_inliers, r.status, r.refined, r.coeff[0], r.coeff[1], r.coeff[2], r.coeff[3]);
+        cout << line << endl;
+    }
+    if (n_tiles > 10) cout << "... and " << n_tiles - 10 << " more tiles" << endl;
+    snprintf(line, sizeof line, "segment time %.3f ms", ms);
+    cout << line << endl;
+    string dir = read_PLY_filename0, base = read_PLY_filename0;
+    const size_t slash = base.find_last_of('/');
+    dir = slash == string::npos ? string() : base.substr(0, slash + 1);
+    if (slash != string::npos) base = base.substr(slash + 1);
+    for (const auto& out : {make_pair(string("ground_"), ground), make_pair(string("nonground_"), rest)}) {
+        const string path = dir + out.first + base;
+        if (!save_ply_binary(path, *out.second)) throw runtime_error("could not write " + path);
+        cerr << "Saved Point Cloud with " << out.second->points.size() << " data points to " << path << endl;
+    }
+}
+
 // pose.cpp:23-565 restricted to the hot path
 Pose::Pose(int argc, char* argv[])
 {
@@ -594,6 +671,10 @@ Pose::Pose(int argc, char* argv[])
     }
     if (smooth_surface) {
         run_smooth_surface();
+        return;
+    }
+    if (segment_cloud_only) {
+        run_segment_cloud();
         return;
     }
     if (!run3d_reconstruction) return;
