@@ -396,6 +396,76 @@ int  o3dr_nearest_neighbors(o3dr_ctx* ctx, const o3dr_point* query, int64_t n_qu
 int  o3dr_icp_align(o3dr_ctx* ctx, const o3dr_point* source, int64_t n_source, const o3dr_point* target, int64_t n_target,
                     const float T_init[16], const o3dr_icp_params* p, o3dr_icp_result* res, int32_t mem);
 
+/* ---- feature matching: cv::cuda::DescriptorMatcher::createBFMatcher(NORM_HAMMING)->knnMatch(query, train, k = 2) on
+ * 32-byte ORB descriptors, the ratio test and the distance gate (pose.h:180, pose_functions.cpp:2017), and
+ * pcl::registration::TransformationEstimationSVD on the matched 3-D keypoints (pose.cpp:213-235).  OpenCV's tie order and
+ * PCL's rounding cannot be pinned here, so the contract below is this library's own; where they leave something open it is
+ * made exact.
+ *
+ * o3dr_match_knn2_hamming - batched brute-force 2-NN.  `desc` holds rows of 32 bytes (memory kind `mem`); set s is rows
+ * [desc_offsets[s], desc_offsets[s+1]) (HOST array of n_sets + 1 non-decreasing entries, desc_offsets[0] >= 0: the layout of
+ * o3dr_accumulate_frames_kp's kp_offsets).  `pairs` (HOST) holds n_pairs (query_set, train_set) int32 pairs; query_set ==
+ * train_set is allowed.  For query row i of pair p: d(i, j) = popcount(q_i XOR t_j) over the 256 bits for every row j of the
+ * train set, j local to the train set (OpenCV's trainIdx).  The best and second-best rows are the two smallest keys (d, j) in
+ * lexicographic order: equal distances go to the lower index.  A missing neighbour (train set of 0 or 1 rows): index and
+ * distance 0xFFFFFFFF.  good (n bytes, or NULL: not written) is 1 iff the second neighbour exists, d1 < max_distance and
+ * (float)d1 < ratio * (float)d2 in fp32 (all comparisons strict).  Pair p's records start at the exclusive prefix sum of
+ * its query-set sizes, in pair order; *n_out = their total, out_capacity below it: O3DR_ERR_CAPACITY with *n_out set and
+ * nothing written.  Limits, else O3DR_ERR_INVALID_ARG (host outputs zeroed): the pool desc_offsets[n_sets] -
+ * desc_offsets[0] at most 2^32-1 rows, set indices in [0, n_sets), ratio finite and > 0, 0 <= max_distance <= 257.  The
+ * call synchronises once at the end; it does not use the sort workspace and leaves cloud_big alone.  Records are integers:
+ * results are identical across calls, batchings and memory kinds.
+ *
+ * o3dr_keypoints_3d - what findFeatures does with Q: one point per keypoint, index-aligned with the keypoints.  Frames in
+ * o3dr_accumulate_frames_kp's layout (kp_xy in `mem`, kp_offsets a HOST array of n_frames + 1 non-decreasing entries; bgr
+ * may be NULL; poses may be NULL for the camera frame, else 16 floats per frame in `mem`).  Keypoint i of frame f is
+ * accepted iff A1's keypoint pass accepts it with the context's params (truncation to int, the ROI, d > min_disparity,
+ * disparity_f64, the blur of blur_kernel > 1); it then gets exactly the point that pass emits (posed by poses[f] like
+ * o3dr_accumulate_frames_kp; rgba 0 when bgr is NULL).  A rejected keypoint gets NaN x y z and rgba 0.  out_capacity >= the
+ * keypoint count; *n_out = that count.  Fewer than 2^31 keypoints.  The call synchronises.
+ *
+ * o3dr_estimate_rigid_transform - batched TransformationEstimationSVD.  src and tgt: n index-aligned points each (`mem`);
+ * segments [seg_offsets[s], seg_offsets[s+1]) (HOST, n_segs + 1 non-decreasing entries within [0, n], each segment at most
+ * 2^32-1 points; seg_offsets NULL: one segment [0, n) and n_segs must be 1); mask: n bytes in `mem` or NULL.  Per segment:
+ *   1. the used pairs are those with mask != 0 (or no mask) whose six coordinates are all finite;
+ *   2. c0 = the segment's first used target point; fp64 moments about c0 (count, sum a, sum b, sum a b^T with a = src - c0,
+ *      b = tgt - c0) over the partition and fold of ICP step 5: per-workgroup partials over runs of 256 consecutive points
+ *      from the segment's first point, folded per segment in workgroup order - no float atomics;
+ *   3. the ICP's host Kabsch (proper rotation, reflection corrected); fewer than 3 used pairs: O3DR_RIGID_TOO_FEW; a
+ *      cross-covariance of rank < 2 (s2 <= 1e-12 s1): O3DR_RIGID_DEGENERATE; T is the identity in both cases;
+ *   4. rms = sqrt(mean |T src - tgt|^2) over the used pairs in fp64 (same partition and fold; 0 without used pairs).
+ * T maps src -> tgt (PCL's convention), row-major fp64.  Results are bit-identical across calls, host and device memory and
+ * segment batchings: a segment equals a call on that segment alone.  The call synchronises; it does not use the sort
+ * workspace.  On error the host results are zeroed. */
+typedef struct o3dr_match_params {
+    float   ratio;          /* default 0.5 (the reference's ratio test) */
+    int32_t max_distance;   /* default 40 (d1 < 40) */
+} o3dr_match_params;
+typedef struct o3dr_knn2 {  /* 16 bytes */
+    uint32_t train_idx[2];  /* best, second best; 0xFFFFFFFF if missing */
+    uint32_t distance[2];   /* Hamming distances; 0xFFFFFFFF if missing */
+} o3dr_knn2;
+typedef struct o3dr_rigid_result {
+    double  T[16];          /* row-major 4x4, src -> tgt */
+    double  rms;
+    int64_t n_used;
+    int32_t status;         /* O3DR_RIGID_* */
+    int32_t reserved;       /* 0 */
+} o3dr_rigid_result;
+#define O3DR_RIGID_OK         0
+#define O3DR_RIGID_TOO_FEW    1
+#define O3DR_RIGID_DEGENERATE 2
+void o3dr_match_default_params(o3dr_match_params* p);
+int  o3dr_match_knn2_hamming(o3dr_ctx* ctx, const uint8_t* desc, const int64_t* desc_offsets, int32_t n_sets, const int32_t* pairs,
+                             int64_t n_pairs, const o3dr_match_params* p, o3dr_knn2* out, uint8_t* good, int64_t out_capacity,
+                             int64_t* n_out, int32_t mem);
+int  o3dr_keypoints_3d(o3dr_ctx* ctx, const uint8_t* disp, int64_t disp_frame_stride, int64_t disp_pitch, const uint8_t* bgr,
+                       int64_t bgr_frame_stride, int64_t bgr_pitch, int32_t rows, int32_t cols, const float* poses, int32_t n_frames,
+                       const float* kp_xy, const int64_t* kp_offsets, o3dr_point* out, int64_t out_capacity, int64_t* n_out,
+                       int32_t mem);
+int  o3dr_estimate_rigid_transform(o3dr_ctx* ctx, const o3dr_point* src, const o3dr_point* tgt, int64_t n, const int64_t* seg_offsets,
+                                   int32_t n_segs, const uint8_t* mask, o3dr_rigid_result* res, int32_t mem);
+
 /* ---- moving-least-squares smoothing and normals: pcl::MovingLeastSquares as the reference's --smooth_surface tool uses it
  * (pose.cpp:27-112, pose_functions.cpp:1711-1813), upsampling NONE, polynomial fit on.  The reference's exact call
  * parameters and PCL's rounding cannot be pinned here, so the contract below is this library's own; where PCL leaves

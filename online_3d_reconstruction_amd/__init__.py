@@ -8,7 +8,8 @@ generates the benchmark inputs of SURVEY.md section 8d, `dist` shards frames ove
 There is no CPU fallback: importing works anywhere, but creating a `Context` without the built
 library or without a GPU raises.
 """
-from ._lib import PLANE_TILE, POINT, O3drError, lib_path, load_library  # noqa: F401
-from .api import Context, IcpResult, MlsResult, Params  # noqa: F401
+from ._lib import KNN2, PLANE_TILE, POINT, RIGID_RESULT, O3drError, lib_path, load_library  # noqa: F401
+from .api import Context, IcpResult, MlsResult, Params, RigidResult  # noqa: F401
 
-__all__ = ["Context", "IcpResult", "MlsResult", "Params", "PLANE_TILE", "POINT", "O3drError", "lib_path", "load_library"]
+__all__ = ["Context", "IcpResult", "KNN2", "MlsResult", "Params", "PLANE_TILE", "POINT", "RIGID_RESULT", "RigidResult", "O3drError",
+           "lib_path", "load_library"]

@@ -69,6 +69,23 @@ PLANE_OK, PLANE_TOO_FEW, PLANE_DEGENERATE = range(3)
 PLANE_MAX_ITERATIONS = 1 << 20
 
 
+class MatchParamsStruct(C.Structure):
+    _fields_ = [("ratio", C.c_float), ("max_distance", C.c_int32)]
+
+
+class RigidResultStruct(C.Structure):
+    _fields_ = [("T", C.c_double * 16), ("rms", C.c_double), ("n_used", C.c_int64), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+# o3dr_knn2 (16 bytes) and o3dr_rigid_result (152 bytes), as numpy records
+KNN2 = np.dtype([("train_idx", "<u4", (2,)), ("distance", "<u4", (2,))])
+assert KNN2.itemsize == 16
+RIGID_RESULT = np.dtype([("T", "<f8", (16,)), ("rms", "<f8"), ("n_used", "<i8"), ("status", "<i4"), ("reserved", "<i4")])
+assert RIGID_RESULT.itemsize == C.sizeof(RigidResultStruct) == 152
+MATCH_NONE = 0xFFFFFFFF
+RIGID_OK, RIGID_TOO_FEW, RIGID_DEGENERATE = range(3)
+
+
 def lib_path():
     return _LIB
 
@@ -131,6 +148,10 @@ SYMBOLS = [
     ("o3dr_icp_default_params", None, [C.POINTER(IcpParamsStruct)]),
     ("o3dr_nearest_neighbors", C.c_int, [_vp, _vp, _i64, _vp, _i64, C.c_double, _vp, _vp, _i32]),
     ("o3dr_icp_align", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, C.POINTER(IcpParamsStruct), C.POINTER(IcpResultStruct), _i32]),
+    ("o3dr_match_default_params", None, [C.POINTER(MatchParamsStruct)]),
+    ("o3dr_match_knn2_hamming", C.c_int, [_vp, _vp, _vp, _i32, _vp, _i64, C.POINTER(MatchParamsStruct), _vp, _vp, _i64, _pi64, _i32]),
+    ("o3dr_keypoints_3d", C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _pi64, _i32]),
+    ("o3dr_estimate_rigid_transform", C.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _i32]),
     ("o3dr_mls_default_params", None, [C.POINTER(MlsParamsStruct)]),
     ("o3dr_mls_smooth", C.c_int, [_vp, _vp, _i64, C.POINTER(MlsParamsStruct), _vp, _vp, _vp, _vp, C.POINTER(MlsResultStruct), _i32]),
     ("o3dr_plane_default_params", None, [C.POINTER(PlaneParamsStruct)]),

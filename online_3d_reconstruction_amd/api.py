@@ -60,6 +60,20 @@ class MlsResult:
     max_neighbors: int
 
 
+@dataclass
+class RigidResult:
+    """o3dr_estimate_rigid_transform's result for one segment: T (float64 4x4, src -> tgt), the rms residual at T over the
+    used pairs, their number and the status (RIGID_OK, RIGID_TOO_FEW, RIGID_DEGENERATE; T is the identity unless OK)."""
+    T: np.ndarray
+    rms: float
+    n_used: int
+    status: int
+
+    @staticmethod
+    def from_record(r):
+        return RigidResult(np.array(r["T"], np.float64).reshape(4, 4), float(r["rms"]), int(r["n_used"]), int(r["status"]))
+
+
 def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
@@ -428,6 +442,148 @@ class Context:
         if return_tile_index:
             ret += (til[:n],)
         return ret
+
+    # -- feature matching (BFMatcher NORM_HAMMING knnMatch k=2 + ratio test, pose.h:180 / pose_functions.cpp:2017, and
+    #    TransformationEstimationSVD, pose.cpp:213-235) --------------------------------------------------------------------
+    @staticmethod
+    def _desc(desc):
+        if _is_torch(desc):
+            assert desc.is_contiguous() and desc.element_size() == 1 and desc.dim() == 2 and desc.shape[1] == 32
+            return desc, int(desc.shape[0])
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        return desc, int(desc.shape[0])
+
+    def matchDescriptors(self, desc, offsets, pairs, ratio=0.5, max_distance=40):
+        """Brute-force Hamming 2-NN of every query row of every (query_set, train_set) pair (contract: include/o3dr.h,
+        DESIGN.md "Feature matching").  desc: uint8 [N, 32] (numpy, or a torch CUDA tensor: results are then CUDA tensors);
+        offsets: the n_sets + 1 row offsets of the sets; pairs: [P, 2] set indices.  -> (records (numpy KNN2 array, or a
+        torch int32 [n, 4] tensor: train_idx[2], distance[2] as bits), good (bool mask)); pair p's records follow those of
+        the pairs before it."""
+        desc, _ = self._desc(desc)
+        pd, mem, _k = _ptr(desc)
+        off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        prs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        n_sets = len(off) - 1
+        n_rec = int(sum(int(off[q + 1] - off[q]) for q, _ in prs)) if n_sets > 0 else 0
+        prm = L.MatchParamsStruct(float(ratio), int(max_distance))
+        n = C.c_int64(0)
+        if mem == L.MEM_DEVICE:
+            import torch
+            rec = torch.empty((max(n_rec, 1), 4), dtype=torch.int32, device=desc.device)
+            good = torch.empty(max(n_rec, 1), dtype=torch.uint8, device=desc.device)
+            self._order_after_torch()
+            pr, pg = rec.data_ptr(), good.data_ptr()
+        else:
+            rec = np.empty(max(n_rec, 1), L.KNN2)
+            good = np.empty(max(n_rec, 1), np.uint8)
+            pr, pg = rec.ctypes.data, good.ctypes.data
+        L.check(self._lib.o3dr_match_knn2_hamming(self._h, pd if len(desc) else None, off.ctypes.data, n_sets,
+                                                  prs.ctypes.data if len(prs) else None, len(prs), C.byref(prm), pr, pg,
+                                                  max(n_rec, 1), C.byref(n), mem))
+        assert n.value == n_rec
+        return rec[:n_rec], good[:n_rec] != 0
+
+    def keypoints3D(self, disp, kp_xy, poses=None, bgr=None):
+        """One point per keypoint, index-aligned (what findFeatures does with Q; contract: include/o3dr.h): the point A1's
+        keypoint pass emits for an accepted keypoint (posed by poses[f] when given, rgba 0 without bgr), NaN x y z and rgba
+        0 for a rejected one.  disp: one frame [H, W] with kp_xy [n, 2], or a stack [F, H, W] with a list of F arrays;
+        poses: None, [4, 4] or [F, 4, 4] float32; bgr: None or [H, W, 3] / [F, H, W, 3] uint8.  numpy, or torch CUDA
+        tensors (the result is then a CUDA [n, 4] tensor)."""
+        dev = _is_torch(disp)
+        single = (disp.dim() if dev else np.ndim(disp)) == 2
+        F = 1 if single else int(disp.shape[0])
+        rows, cols = int(disp.shape[-2]), int(disp.shape[-1])
+        kps = [kp_xy] if single else list(kp_xy)
+        if dev:
+            import torch
+            assert disp.is_cuda
+            disp = disp.contiguous()
+            kp = torch.cat([torch.as_tensor(k, dtype=torch.float32, device=disp.device).reshape(-1, 2) for k in kps]).contiguous()
+            counts = [int(torch.as_tensor(k).reshape(-1, 2).shape[0]) for k in kps]
+            ps = None if poses is None else torch.as_tensor(poses, dtype=torch.float32, device=disp.device).contiguous()
+            bg = None if bgr is None else bgr.contiguous()
+            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+            es, mem = disp.element_size(), L.MEM_DEVICE
+        else:
+            disp = np.ascontiguousarray(disp)
+            kp = np.ascontiguousarray(np.concatenate([np.asarray(k, np.float32).reshape(-1, 2) for k in kps]))
+            counts = [len(np.asarray(k).reshape(-1, 2)) for k in kps]
+            ps = None if poses is None else np.ascontiguousarray(poses, np.float32)
+            bg = None if bgr is None else np.ascontiguousarray(bgr, np.uint8)
+            ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+            es, mem = disp.itemsize, L.MEM_HOST
+        off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        n_kp = int(off[-1])
+        out = self._alloc_out(n_kp, disp)
+        po, _, _k = _ptr(out)
+        n = C.c_int64(0)
+        if dev:
+            self._order_after_torch()
+        L.check(self._lib.o3dr_keypoints_3d(self._h, ptr(disp), rows * cols * es, cols * es, ptr(bg), rows * cols * 3, cols * 3, rows,
+                                            cols, ptr(ps), F, ptr(kp) if n_kp else None, off.ctypes.data, po, max(n_kp, 1), C.byref(n),
+                                            mem))
+        return out[:n_kp]
+
+    def estimateRigidTransform(self, src, tgt, seg_offsets=None, mask=None):
+        """Batched TransformationEstimationSVD (contract: include/o3dr.h, DESIGN.md "Feature matching"): per segment the
+        rigid T mapping src onto tgt over the index-aligned pairs with mask != 0 and finite coordinates.  numpy POINT arrays,
+        or torch [N,4] 4-byte CUDA tensors (mask then a CUDA uint8 / bool tensor).  -> RigidResult, or a list of them with
+        seg_offsets (the n_segs + 1 segment boundaries)."""
+        src, n = self._cloud(src)
+        tgt, n2 = self._cloud(tgt)
+        assert n == n2, "src and tgt must be index-aligned"
+        ps_, mem, _k = _ptr(src)
+        pt, mem2, _k2 = _ptr(tgt)
+        if n:
+            assert mem == mem2, "src and tgt must live in the same memory"
+        pm = None
+        if mask is not None:
+            if _is_torch(mask):
+                import torch
+                mask = mask.to(torch.uint8).contiguous()
+                pm = mask.data_ptr()
+            else:
+                mask = np.ascontiguousarray(mask).astype(np.uint8)
+                pm = mask.ctypes.data
+        segs = None if seg_offsets is None else np.ascontiguousarray(seg_offsets, np.int64).reshape(-1)
+        n_segs = 1 if segs is None else len(segs) - 1
+        res = np.zeros(max(n_segs, 1), L.RIGID_RESULT)
+        if mem == L.MEM_DEVICE:
+            self._order_after_torch()
+        L.check(self._lib.o3dr_estimate_rigid_transform(self._h, ps_ if n else None, pt if n else None, n,
+                                                        None if segs is None else segs.ctypes.data, n_segs, pm, res.ctypes.data, mem))
+        out = [RigidResult.from_record(r) for r in res[:n_segs]]
+        return out[0] if segs is None else out
+
+    def matchFeatures(self, desc_q, desc_t, kp3_q, kp3_t, ratio=0.5, max_distance=40):
+        """One frame pair of the reference's feature-matched mode (generate_tf_of_Matched_Keypoints, pose.cpp:213-235):
+        2-NN match desc_q against desc_t, keep the good matches whose 3-D keypoints (kp3_q, kp3_t: index-aligned with the
+        descriptors, e.g. from keypoints3D) are finite on both sides, and fit T mapping the query's points onto the
+        train's.  All numpy, or all torch CUDA tensors (the gather then stays on the device).
+        -> (records, kept mask (bool, one per query row), RigidResult)."""
+        dq, nq = self._desc(desc_q)
+        dt, nt = self._desc(desc_t)
+        kq, nkq = self._cloud(kp3_q)
+        kt, nkt = self._cloud(kp3_t)
+        assert nkq == nq and nkt == nt, "the 3-D keypoints must be index-aligned with the descriptors"
+        pairs = np.array([[0, 1]], np.int32)
+        offsets = np.array([0, nq, nq + nt], np.int64)
+        if _is_torch(dq):
+            import torch
+            rec, good = self.matchDescriptors(torch.cat([dq, dt]), offsets, pairs, ratio, max_distance)
+            idx = rec[:, 0].to(torch.int64)  # 0xFFFFFFFF reads as -1
+            tgt = kt[idx.clamp(0, max(nt - 1, 0))] if nt else torch.zeros_like(kq)
+            fin = lambda p: torch.isfinite(p.view(torch.float32)[:, :3]).all(1)  # noqa: E731
+            keep = good & (idx >= 0) & fin(kq) & fin(tgt)
+            res = self.estimateRigidTransform(kq, tgt.contiguous(), mask=keep)
+            return rec, keep, res
+        rec, good = self.matchDescriptors(np.concatenate([dq, dt]), offsets, pairs, ratio, max_distance)
+        idx = rec["train_idx"][:, 0].astype(np.int64)
+        tgt = np.ascontiguousarray(kt[np.clip(idx, 0, max(nt - 1, 0))]) if nt else np.zeros_like(kq)
+        fin = lambda p: np.isfinite(p["x"]) & np.isfinite(p["y"]) & np.isfinite(p["z"])  # noqa: E731
+        keep = good & fin(kq) & fin(tgt)
+        res = self.estimateRigidTransform(kq, tgt, mask=keep)
+        return rec, keep, res
 
     def voxelGrid(self, pts, leaf, min_points=0, z_offset=0.0, return_status=False):
         """pcl::VoxelGrid<PointXYZRGB> as the reference configures it (pose_functions.cpp:1689-1700)."""

@@ -520,6 +520,25 @@ __global__ __launch_bounds__(kEmitThreads) void k_reproject_emit(ReprojectArgs a
     }
 }
 
+// one keypoint of the keypoint pass (pose_functions.cpp:1061-1090): truncation to int, the ROI, d > min_disparity, then
+// reproject_one; false: rejected.  bgr == nullptr: colour 0 (o3dr_keypoints_3d without an image)
+__device__ __forceinline__ bool keypoint_one(const ReprojectArgs& a, const uint8_t* disp, const uint8_t* bgr, const float* m, bool xf,
+                                             float kx, float ky, Pix& p)
+{
+    const int x = (int)kx, y = (int)ky;
+    if (!(x >= a.cs && x < a.cols - a.bb && y >= a.bb && y < a.rows - a.bb)) return false;
+    const uint8_t* row = disp + (int64_t)y * a.disp_pitch;
+    const double d = a.disp_f64 ? reinterpret_cast<const double*>(row)[x] : (double)row[x];
+    if (!(d > a.min_disp)) return false;
+    uint32_t b = 0, g = 0, r = 0;
+    if (bgr) {
+        const uint8_t* px = bgr + (int64_t)y * a.bgr_pitch + 3 * (int64_t)x;
+        b = px[0], g = px[1], r = px[2];
+    }
+    p = reproject_one(a.Q, x, y, d, b, g, r, m, xf);
+    return true;
+}
+
 // keypoint pass (pose_functions.cpp:1057-1091): one workgroup walks the keypoints in order
 // one workgroup per frame; kp_off (optional) holds the frames' ranges in kp_xy, else all n_kp belong to frame 0
 __global__ __launch_bounds__(256) void k_keypoint_pass(ReprojectArgs a, const float* __restrict__ kp_xy, int n_kp,
@@ -547,18 +566,7 @@ __global__ __launch_bounds__(256) void k_keypoint_pass(ReprojectArgs a, const fl
         const int i = i0 + threadIdx.x;
         bool ok = false;
         Pix p;
-        if (i < n_kp) {
-            const int x = (int)kp_xy[2 * i], y = (int)kp_xy[2 * i + 1];
-            if (x >= a.cs && x < a.cols - a.bb && y >= a.bb && y < a.rows - a.bb) {
-                const uint8_t* row = disp + (int64_t)y * a.disp_pitch;
-                const double d = a.disp_f64 ? reinterpret_cast<const double*>(row)[x] : (double)row[x];
-                if (d > a.min_disp) {
-                    const uint8_t* px = bgr + (int64_t)y * a.bgr_pitch + 3 * (int64_t)x;
-                    p = reproject_one(a.Q, x, y, d, px[0], px[1], px[2], m, xf);
-                    ok = true;
-                }
-            }
-        }
+        if (i < n_kp) ok = keypoint_one(a, disp, bgr, m, xf, kp_xy[2 * i], kp_xy[2 * i + 1], p);
         uint32_t total;
         const uint32_t pos = block_excl_scan_u32<4>(ok ? 1u : 0u, scan_lds, total);
         if (ok) {

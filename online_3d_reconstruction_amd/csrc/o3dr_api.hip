@@ -138,6 +138,13 @@ struct o3dr_ctx {
     // o3dr_segment_plane: points in tile order + run heads, tile tables, hypotheses + scores, flags, staged host outputs
     DevBuf pl_pts, pl_tiles, pl_hyp, pl_misc, pl_out;
     uint64_t pl_last_hyp = 0;  // hypotheses of the last call in pl_hyp (o3dr_test_plane_hypotheses)
+    // o3dr_match_knn2_hamming: staged pool, pair table, chunk partials, staged records + mask; the host copy of the table
+    DevBuf mt_desc, mt_tab, mt_part, mt_out;
+    std::vector<MatchPair> mt_tab_h;
+    // o3dr_estimate_rigid_transform: staged src / tgt / mask, the segment table and the sums; host copies of the tables
+    DevBuf rg_in, rg_work;
+    std::vector<RigidSeg> rg_seg_h;
+    std::vector<double> rg_T_h;
     int64_t place_ub = -1;   // o3dr_cloud_big_slice_counts_dev ran for a cloud of at most this many points and place_parts slices:
     int place_parts = 0;     // the (slice, tile) table in the workspace is what o3dr_cloud_big_place_slices moves by
     int test_hooks = 0;    // O3DR_TEST_HOOKS=1 at o3dr_ctx_create: the entry points of include/o3dr_testing.h act
@@ -479,7 +486,8 @@ extern "C" int o3dr_ctx_destroy(o3dr_ctx* c)
     }
     for (DevBuf* b : {&c->inc.box, &c->inc.scratch, &c->inc.tg, &c->inc.tmatch, &c->inc.flag, &c->inc.src, &c->inc.keep,
                       &c->inc.partial, &c->inc.words, &c->inc.fb, &c->nn_q, &c->nn_t, &c->nn_cells, &c->nn_src, &c->mls_out, &c->mls_misc,
-                      &c->pl_pts, &c->pl_tiles, &c->pl_hyp, &c->pl_misc, &c->pl_out})
+                      &c->pl_pts, &c->pl_tiles, &c->pl_hyp, &c->pl_misc, &c->pl_out, &c->mt_desc, &c->mt_tab, &c->mt_part,
+                      &c->mt_out, &c->rg_in, &c->rg_work})
         dev_release(*b);
     delete c;
     return O3DR_OK;
@@ -3371,6 +3379,311 @@ extern "C" int o3dr_segment_plane(o3dr_ctx* c, const o3dr_point* cloud, int64_t 
         }
         if (mem == O3DR_MEM_HOST && tiles && tiles_capacity > 0) memset(tiles, 0, (size_t)tiles_capacity * sizeof(o3dr_plane_tile));
     }
+    return rc;
+}
+
+// -------------------------------------------------------------------------------------------------
+// feature matching: Hamming 2-NN, index-aligned 3-D keypoints, batched rigid fit (kernels/match.inc; DESIGN.md
+// "Feature matching")
+// -------------------------------------------------------------------------------------------------
+extern "C" void o3dr_match_default_params(o3dr_match_params* p)
+{
+    if (!p) return;
+    p->ratio = 0.5f;       // the reference's ratio test
+    p->max_distance = 40;  // and its distance gate
+}
+
+// work items (waves) the chunk size aims at: enough to fill 256 CUs several times over
+constexpr uint64_t kMatchTargetItems = 8192;
+
+static int match_knn2(o3dr_ctx* c, const uint8_t* desc, const int64_t* off, int32_t n_sets, const int32_t* pairs, int64_t n_pairs,
+                      const o3dr_match_params* p, o3dr_knn2* out, uint8_t* good, int64_t out_capacity, int64_t* n_out, int32_t mem)
+{
+    if (!n_out) return fail(O3DR_ERR_INVALID_ARG, "n_out is NULL");
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    o3dr_match_params prm;
+    o3dr_match_default_params(&prm);
+    if (p) prm = *p;
+    if (!(std::isfinite(prm.ratio) && prm.ratio > 0.f)) return fail(O3DR_ERR_INVALID_ARG, "ratio must be finite and > 0");
+    if (prm.max_distance < 0 || prm.max_distance > 257) return fail(O3DR_ERR_INVALID_ARG, "max_distance must be in [0, 257]");
+    if (n_sets < 0 || n_pairs < 0 || !off || (n_pairs > 0 && !pairs)) return fail(O3DR_ERR_INVALID_ARG, "bad sets / pairs");
+    if (n_pairs > (int64_t)0xffffffffLL) return fail(O3DR_ERR_INVALID_ARG, "too many pairs");
+    if (off[0] < 0) return fail(O3DR_ERR_INVALID_ARG, "desc_offsets[0] must be >= 0");
+    for (int32_t s = 0; s < n_sets; ++s)
+        if (off[s + 1] < off[s]) return fail(O3DR_ERR_INVALID_ARG, "desc_offsets must not decrease");
+    const int64_t pool = off[n_sets] - off[0];
+    if (pool > (int64_t)0xffffffffLL) return fail(O3DR_ERR_INVALID_ARG, "more than 2^32-1 descriptor rows");
+    if (pool > 0 && !desc) return fail(O3DR_ERR_INVALID_ARG, "desc is NULL");
+    // the pair table, the chunk size and the totals
+    uint64_t n_rec = 0, work = 0;
+    for (int64_t k = 0; k < n_pairs; ++k) {
+        const int32_t qs = pairs[2 * k], ts = pairs[2 * k + 1];
+        if (qs < 0 || qs >= n_sets || ts < 0 || ts >= n_sets) return fail(O3DR_ERR_INVALID_ARG, "a pair names a set outside [0, n_sets)");
+        const uint64_t nq = (uint64_t)(off[qs + 1] - off[qs]), nt = (uint64_t)(off[ts + 1] - off[ts]);
+        n_rec += nq;
+        work += (nq + kWave - 1) / kWave * nt;
+    }
+    *n_out = (int64_t)n_rec;
+    if ((int64_t)n_rec > out_capacity) return fail(O3DR_ERR_CAPACITY, "out_capacity is below the record count");
+    if (n_rec > 0 && !out) return fail(O3DR_ERR_INVALID_ARG, "out is NULL");
+    if (n_rec == 0) return O3DR_OK;
+    uint64_t chunk = (work + kMatchTargetItems - 1) / kMatchTargetItems;
+    chunk = (chunk + kWave - 1) / kWave * kWave;
+    if (chunk < (uint64_t)kWave) chunk = kWave;
+    if (chunk > kMatchMaxChunk) chunk = kMatchMaxChunk;
+    std::vector<MatchPair>& tab = c->mt_tab_h;
+    tab.resize((size_t)n_pairs);
+    uint64_t items = 0, rec = 0, part = 0;
+    for (int64_t k = 0; k < n_pairs; ++k) {
+        const int32_t qs = pairs[2 * k], ts = pairs[2 * k + 1];
+        MatchPair& P = tab[(size_t)k];
+        P.qbase = (uint32_t)(off[qs] - off[0]);
+        P.nq = (uint32_t)(off[qs + 1] - off[qs]);
+        P.tbase = (uint32_t)(off[ts] - off[0]);
+        P.nt = (uint32_t)(off[ts + 1] - off[ts]);
+        P.chunks = (uint32_t)(((uint64_t)P.nt + chunk - 1) / chunk);
+        P.qwaves = (P.nq + kWave - 1) / kWave;
+        P.item0 = items;
+        P.rec0 = rec;
+        P.part0 = part;
+        items += (uint64_t)P.qwaves * P.chunks;
+        rec += P.nq;
+        part += (uint64_t)P.nq * P.chunks;
+    }
+    const void* desc_d = nullptr;
+    if (pool > 0) CHK(stage_in(c, c->mt_desc, desc + 32 * off[0], (size_t)pool * 32, mem, &desc_d));
+    CHK(dev_ensure(c, c->mt_tab, tab.size() * sizeof(MatchPair)));
+    CHK(dev_ensure(c, c->mt_part, (size_t)(part ? part : 1) * sizeof(uint2)));
+    HIPCHK(hipMemcpyAsync(c->mt_tab.p, tab.data(), tab.size() * sizeof(MatchPair), hipMemcpyHostToDevice, c->stream));
+    MatchArgs a;
+    memset(&a, 0, sizeof a);
+    a.desc = (const uint4*)desc_d;
+    a.n_pairs = (uint32_t)n_pairs;
+    a.chunk_rows = (uint32_t)chunk;
+    a.n_items = items;
+    a.n_rec = n_rec;
+    a.rec = (uint4*)out;
+    a.good = good;
+    a.ratio = prm.ratio;
+    a.max_distance = (uint32_t)prm.max_distance;
+    if (mem == O3DR_MEM_HOST) {  // staged: records, then the mask
+        const size_t b_rec = align256((size_t)n_rec * sizeof(o3dr_knn2));
+        CHK(dev_ensure(c, c->mt_out, b_rec + (size_t)n_rec));
+        a.rec = (uint4*)c->mt_out.p;
+        a.good = good ? (uint8_t*)c->mt_out.p + b_rec : nullptr;
+    }
+    launch_match(&c->prof, c->stream, a, (const MatchPair*)c->mt_tab.p, (uint2*)c->mt_part.p);
+    HIPCHK(hipGetLastError());
+    if (mem == O3DR_MEM_HOST) {
+        HIPCHK(hipMemcpyAsync(out, a.rec, (size_t)n_rec * sizeof(o3dr_knn2), hipMemcpyDeviceToHost, c->stream));
+        if (good) HIPCHK(hipMemcpyAsync(good, a.good, (size_t)n_rec, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_match_knn2_hamming(o3dr_ctx* c, const uint8_t* desc, const int64_t* desc_offsets, int32_t n_sets, const int32_t* pairs,
+                                       int64_t n_pairs, const o3dr_match_params* p, o3dr_knn2* out, uint8_t* good, int64_t out_capacity,
+                                       int64_t* n_out, int32_t mem)
+{
+    if (n_out) *n_out = 0;
+    auto entered = [&]() -> int {
+        CTX_ENTER(c);
+        return match_knn2(c, desc, desc_offsets, n_sets, pairs, n_pairs, p, out, good, out_capacity, n_out, mem);
+    };
+    const int rc = entered();
+    if (rc != O3DR_OK && rc != O3DR_ERR_CAPACITY) {  // host outputs zeroed on error
+        if (n_out) *n_out = 0;
+        if (mem == O3DR_MEM_HOST && out_capacity > 0) {
+            if (out) memset(out, 0, (size_t)out_capacity * sizeof(o3dr_knn2));
+            if (good) memset(good, 0, (size_t)out_capacity);
+        }
+    }
+    return rc;
+}
+
+static int keypoints_3d(o3dr_ctx* c, const uint8_t* disp, int64_t disp_frame_stride, int64_t disp_pitch, const uint8_t* bgr,
+                        int64_t bgr_frame_stride, int64_t bgr_pitch, int32_t rows, int32_t cols, const float* poses, int32_t n_frames,
+                        const float* kp_xy, const int64_t* kp_offsets, o3dr_point* out, int64_t out_capacity, int64_t* n_out, int32_t mem)
+{
+    if (!n_out) return fail(O3DR_ERR_INVALID_ARG, "n_out is NULL");
+    if (!c->has_Q) return fail(O3DR_ERR_NOT_CONFIGURED, "o3dr_set_camera has not been called");
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    if (n_frames < 0 || (n_frames > 0 && !kp_offsets)) return fail(O3DR_ERR_INVALID_ARG, "bad frame list");
+    if (n_frames == 0) return O3DR_OK;
+    const uint8_t* bgr_chk = bgr ? bgr : disp;  // (check_images wants both; without bgr only the disparities are read)
+    CHK(check_images(c, disp, disp_pitch, bgr_chk, bgr ? bgr_pitch : 3 * (int64_t)cols, rows, cols, disp_frame_stride));
+    if (disp_frame_stride < (int64_t)rows * disp_pitch || (bgr && bgr_frame_stride < (int64_t)rows * bgr_pitch))
+        return fail(O3DR_ERR_INVALID_ARG, "frame stride smaller than a frame");
+    if (kp_offsets[0] < 0) return fail(O3DR_ERR_INVALID_ARG, "kp_offsets[0] must be >= 0");
+    for (int32_t f = 0; f < n_frames; ++f)
+        if (kp_offsets[f + 1] < kp_offsets[f]) return fail(O3DR_ERR_INVALID_ARG, "kp_offsets must not decrease");
+    const int64_t n_kp = kp_offsets[n_frames] - kp_offsets[0];
+    if (n_kp >= (int64_t)INT32_MAX) return fail(O3DR_ERR_INVALID_ARG, "too many keypoints");
+    *n_out = n_kp;
+    if (n_kp > out_capacity) return fail(O3DR_ERR_CAPACITY, "out_capacity is below the keypoint count");
+    if (n_kp == 0) return O3DR_OK;
+    if (!kp_xy || !out) return fail(O3DR_ERR_INVALID_ARG, "kp_xy / out is NULL");
+    const int64_t last_d = (int64_t)(n_frames - 1) * disp_frame_stride + (int64_t)rows * disp_pitch;
+    const int64_t last_b = bgr ? (int64_t)(n_frames - 1) * bgr_frame_stride + (int64_t)rows * bgr_pitch : 0;
+    const void *disp_d, *bgr_d = nullptr, *poses_d = nullptr, *kp_d;
+    CHK(stage_in(c, c->st_disp, disp, (size_t)last_d, mem, &disp_d));
+    if (bgr) CHK(stage_in(c, c->st_bgr, bgr, (size_t)last_b, mem, &bgr_d));
+    if (poses) CHK(stage_in(c, c->st_poses, poses, (size_t)n_frames * 16 * sizeof(float), mem, &poses_d));
+    CHK(stage_in(c, c->st_kp, kp_xy + 2 * kp_offsets[0], (size_t)n_kp * 2 * sizeof(float), mem, &kp_d));
+    std::vector<int32_t> kp_rel((size_t)n_frames + 1);
+    for (int32_t f = 0; f <= n_frames; ++f) kp_rel[f] = (int32_t)(kp_offsets[f] - kp_offsets[0]);
+    HIPCHK(hipStreamSynchronize(c->stream));  // an earlier call's launches may still read the offsets
+    CHK(dev_ensure(c, c->st_kpoff, kp_rel.size() * sizeof(int32_t)));
+    HIPCHK(hipMemcpy(c->st_kpoff.p, kp_rel.data(), kp_rel.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    const uint8_t* dsp = (const uint8_t*)disp_d;
+    int64_t dsp_pitch = disp_pitch, dsp_fstride = disp_frame_stride;
+    CHK(maybe_blur(c, &dsp, &dsp_pitch, &dsp_fstride, rows, cols, n_frames));
+    const GridShape g = grid_shape(c->params, rows, cols);
+    ReprojectArgs a;
+    fill_args(c, a, dsp, dsp_pitch, dsp_fstride, (const uint8_t*)bgr_d, bgr_pitch, bgr_frame_stride, rows, cols, g, 0);
+    if (poses) {
+        a.xf_mode = 2;
+        a.poses = (const float*)poses_d;
+    }
+    o3dr_point* out_d = out;
+    if (mem == O3DR_MEM_HOST) {
+        CHK(dev_ensure(c, c->st_out, (size_t)n_kp * sizeof(o3dr_point)));
+        out_d = (o3dr_point*)c->st_out.p;
+    }
+    launch_keypoints_3d(&c->prof, c->stream, a, (const float*)kp_d, (const int32_t*)c->st_kpoff.p, n_frames, (int)n_kp, out_d);
+    HIPCHK(hipGetLastError());
+    if (mem == O3DR_MEM_HOST) HIPCHK(hipMemcpyAsync(out, out_d, (size_t)n_kp * sizeof(o3dr_point), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_keypoints_3d(o3dr_ctx* c, const uint8_t* disp, int64_t disp_frame_stride, int64_t disp_pitch, const uint8_t* bgr,
+                                 int64_t bgr_frame_stride, int64_t bgr_pitch, int32_t rows, int32_t cols, const float* poses,
+                                 int32_t n_frames, const float* kp_xy, const int64_t* kp_offsets, o3dr_point* out, int64_t out_capacity,
+                                 int64_t* n_out, int32_t mem)
+{
+    if (n_out) *n_out = 0;
+    auto entered = [&]() -> int {
+        CTX_ENTER(c);
+        return keypoints_3d(c, disp, disp_frame_stride, disp_pitch, bgr, bgr_frame_stride, bgr_pitch, rows, cols, poses, n_frames, kp_xy,
+                            kp_offsets, out, out_capacity, n_out, mem);
+    };
+    const int rc = entered();
+    if (rc != O3DR_OK && rc != O3DR_ERR_CAPACITY) {
+        if (n_out) *n_out = 0;
+        if (mem == O3DR_MEM_HOST && out && out_capacity > 0) memset(out, 0, (size_t)out_capacity * sizeof(o3dr_point));
+    }
+    return rc;
+}
+
+static int rigid_transform(o3dr_ctx* c, const o3dr_point* src, const o3dr_point* tgt, int64_t n, const int64_t* seg_offsets, int32_t n_segs,
+                           const uint8_t* mask, o3dr_rigid_result* res, int32_t mem)
+{
+    if (!res) return fail(O3DR_ERR_INVALID_ARG, "res is NULL");
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    if (n < 0 || (n > 0 && (!src || !tgt))) return fail(O3DR_ERR_INVALID_ARG, "bad src / tgt / n");
+    if (n_segs < 1) return fail(O3DR_ERR_INVALID_ARG, "n_segs must be >= 1");
+    if (!seg_offsets && n_segs != 1) return fail(O3DR_ERR_INVALID_ARG, "seg_offsets is NULL with n_segs != 1");
+    std::vector<RigidSeg>& seg = c->rg_seg_h;
+    seg.resize((size_t)n_segs);
+    uint64_t blocks = 0;
+    for (int32_t s = 0; s < n_segs; ++s) {
+        const int64_t a0 = seg_offsets ? seg_offsets[s] : 0, a1 = seg_offsets ? seg_offsets[s + 1] : n;
+        if (a0 < 0 || a1 < a0 || a1 > n) return fail(O3DR_ERR_INVALID_ARG, "seg_offsets must not decrease and stay within [0, n]");
+        if (a1 - a0 > (int64_t)0xffffffffLL) return fail(O3DR_ERR_INVALID_ARG, "a segment holds more than 2^32-1 points");
+        seg[s].start = (uint64_t)a0;
+        seg[s].n = (uint32_t)(a1 - a0);
+        seg[s].block0 = (uint32_t)blocks;
+        blocks += ((uint64_t)seg[s].n + kRigidPoints - 1) / kRigidPoints;
+        if (blocks > 0x7fffffffull) return fail(O3DR_ERR_INVALID_ARG, "too many points");
+    }
+    for (int32_t s = 0; s < n_segs; ++s) {
+        memset(&res[s], 0, sizeof res[s]);
+        for (int k = 0; k < 16; ++k) res[s].T[k] = k % 5 == 0 ? 1.0 : 0.0;
+        res[s].status = O3DR_RIGID_TOO_FEW;
+    }
+    const void *src_d = nullptr, *tgt_d = nullptr, *mask_d = nullptr;
+    const size_t b_pts = align256((size_t)n * sizeof(o3dr_point));
+    if (mem == O3DR_MEM_HOST) {
+        CHK(dev_ensure(c, c->rg_in, 2 * b_pts + (size_t)n + 1));
+        char* base = (char*)c->rg_in.p;
+        if (n > 0) {
+            HIPCHK(hipMemcpyAsync(base, src, (size_t)n * sizeof(o3dr_point), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(base + b_pts, tgt, (size_t)n * sizeof(o3dr_point), hipMemcpyHostToDevice, c->stream));
+            if (mask) HIPCHK(hipMemcpyAsync(base + 2 * b_pts, mask, (size_t)n, hipMemcpyHostToDevice, c->stream));
+        }
+        src_d = base;
+        tgt_d = base + b_pts;
+        mask_d = mask ? base + 2 * b_pts : nullptr;
+    } else {
+        src_d = src, tgt_d = tgt, mask_d = mask;
+    }
+    const size_t S = (size_t)n_segs;
+    const size_t b_seg = align256(S * sizeof(RigidSeg)), b_first = align256(S * 4);
+    const size_t b_part = align256((size_t)kRigidFields * (size_t)(blocks ? blocks : 1) * 8);
+    const size_t b_rec = align256(S * (kRigidFields + 1) * 8), b_c0 = align256(S * 3 * 8), b_T = align256(S * 12 * 8);
+    CHK(dev_ensure(c, c->rg_work, b_seg + b_first + b_part + b_rec + b_c0 + b_T));
+    char* w = (char*)c->rg_work.p;
+    RigidArgs a;
+    memset(&a, 0, sizeof a);
+    a.src = (const o3dr_point*)src_d;
+    a.tgt = (const o3dr_point*)tgt_d;
+    a.mask = (const uint8_t*)mask_d;
+    a.seg = (const RigidSeg*)w;
+    a.n_segs = (uint32_t)n_segs;
+    a.n_blocks = (uint32_t)blocks;
+    a.first = (uint32_t*)(w + b_seg);
+    a.partial = (double*)(w + b_seg + b_first);
+    a.rec = (double*)(w + b_seg + b_first + b_part);
+    a.c0 = (double*)(w + b_seg + b_first + b_part + b_rec);
+    a.T = (const double*)(w + b_seg + b_first + b_part + b_rec + b_c0);
+    HIPCHK(hipMemcpyAsync(w, seg.data(), S * sizeof(RigidSeg), hipMemcpyHostToDevice, c->stream));
+    launch_rigid(&c->prof, c->stream, a, false);
+    HIPCHK(hipGetLastError());
+    std::vector<double> rec(S * kRigidFields), c0(S * 3);
+    HIPCHK(hipMemcpyAsync(rec.data(), a.rec, rec.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c0.data(), a.c0, c0.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    // the ICP's host Kabsch per segment (icp_solve reads the first 16 fields of an ICP record)
+    std::vector<double>& Th = c->rg_T_h;
+    Th.assign(S * 12, 0.0);
+    for (size_t s = 0; s < S; ++s) {
+        const double* r = &rec[s * kRigidFields];
+        res[s].n_used = (int64_t)r[0];
+        double dT[16];
+        double full[kIcpRecord] = {0.0};
+        for (int k = 0; k < kRigidFields; ++k) full[k] = r[k];
+        if (r[0] < 3.0) {
+            res[s].status = O3DR_RIGID_TOO_FEW;
+        } else if (!icp_solve(full, &c0[3 * s], dT)) {
+            res[s].status = O3DR_RIGID_DEGENERATE;
+        } else {
+            res[s].status = O3DR_RIGID_OK;
+            for (int k = 0; k < 16; ++k) res[s].T[k] = dT[k];
+        }
+        for (int k = 0; k < 12; ++k) Th[12 * s + k] = res[s].T[k];
+    }
+    HIPCHK(hipMemcpyAsync((void*)a.T, Th.data(), S * 12 * 8, hipMemcpyHostToDevice, c->stream));
+    launch_rigid(&c->prof, c->stream, a, true);
+    HIPCHK(hipGetLastError());
+    std::vector<double> d2(S);
+    HIPCHK(hipMemcpyAsync(d2.data(), a.rec + S * kRigidFields, S * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (size_t s = 0; s < S; ++s) res[s].rms = res[s].n_used > 0 ? std::sqrt(d2[s] / (double)res[s].n_used) : 0.0;
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_estimate_rigid_transform(o3dr_ctx* c, const o3dr_point* src, const o3dr_point* tgt, int64_t n,
+                                             const int64_t* seg_offsets, int32_t n_segs, const uint8_t* mask, o3dr_rigid_result* res,
+                                             int32_t mem)
+{
+    auto entered = [&]() -> int {
+        CTX_ENTER(c);
+        return rigid_transform(c, src, tgt, n, seg_offsets, n_segs, mask, res, mem);
+    };
+    const int rc = entered();
+    if (rc != O3DR_OK && res && n_segs > 0) memset(res, 0, (size_t)n_segs * sizeof(o3dr_rigid_result));
     return rc;
 }
 

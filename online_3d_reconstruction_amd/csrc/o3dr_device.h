@@ -302,6 +302,54 @@ void launch_mls_finite(Profiler* pf, hipStream_t s, const o3dr_point* in, int64_
 void launch_mls(Profiler* pf, hipStream_t s, const Workspace& ws, const o3dr_point* cloud, int64_t n, const float* box6,
                 const float4* cell_lo, const float4* cell_hi, double r, int order, double h, o3dr_point* out, float* normals,
                 uint32_t* nn_count, uint8_t* fit, unsigned long long* counters);
+// feature matching (kernels/match.inc)
+struct MatchPair {      // one (query set, train set) pair of a call; rows relative to the pool
+    uint32_t qbase, nq, tbase, nt;
+    uint32_t chunks;    // ceil(nt / chunk_rows)
+    uint32_t qwaves;    // ceil(nq / 64)
+    uint64_t item0;     // first work item (wave); the pair has qwaves * chunks
+    uint64_t rec0;      // first record (exclusive prefix of nq)
+    uint64_t part0;     // first partial slot; chunk c's row i at part0 + c * nq + i
+};
+struct MatchArgs {
+    const uint4* desc;  // the pool, 32 bytes per row
+    uint32_t n_pairs;
+    uint32_t chunk_rows;
+    uint64_t n_items, n_rec;
+    uint4* rec;         // n_rec o3dr_knn2
+    uint8_t* good;      // n_rec or nullptr
+    float ratio;
+    uint32_t max_distance;
+};
+constexpr uint32_t kMatchMaxChunk = 1u << 23;  // train rows per chunk at most (kMatchKeyBits)
+constexpr int64_t kMatchSliceItems = 1 << 24;  // work items per k_match_scan launch at most
+void launch_match(Profiler* pf, hipStream_t s, const MatchArgs& a, const MatchPair* pairs, uint2* partial);
+// index-aligned 3-D keypoints: kp_off (n_frames + 1 int32, device) relative to kp_xy
+void launch_keypoints_3d(Profiler* pf, hipStream_t s, const ReprojectArgs& a, const float* kp_xy, const int32_t* kp_off, int n_frames,
+                         int n_kp, o3dr_point* out);
+// batched rigid fit (segments of at most 2^32-1 points)
+constexpr int kRigidPoints = 256;  // points per workgroup of the sums (ICP's kNnThreads)
+constexpr int kRigidFields = 16;  // count, sum a (3), sum b (3), sum a b^T (9, row-major): the first 16 of kIcpRecord
+struct RigidSeg {
+    uint64_t start;     // first point
+    uint32_t n;         // points
+    uint32_t block0;    // first workgroup of the sums (ceil(n / kRigidPoints) workgroups)
+};
+struct RigidArgs {
+    const o3dr_point* src;
+    const o3dr_point* tgt;
+    const uint8_t* mask;  // or nullptr
+    const RigidSeg* seg;
+    uint32_t n_segs, n_blocks;
+    uint32_t* first;      // n_segs: first used pair inside the segment (0xFFFFFFFF: none)
+    double* partial;      // kRigidFields * n_blocks (field-major)
+    double* rec;          // n_segs * kRigidFields moments, then n_segs residual sums
+    double* c0;           // n_segs * 3
+    const double* T;      // n_segs * 12 (the residual pass)
+};
+// residual == false: first used pairs, moments about c0 and their fold into rec / c0; true: the squared residuals at T
+// folded into rec
+void launch_rigid(Profiler* pf, hipStream_t s, const RigidArgs& a, bool residual);
 // RANSAC plane segmentation (kernels/plane.inc; the fields are filled by o3dr_segment_plane step by step)
 struct PlaneArgs {
     const float4* pts;            // points in tile order: (x, y, z, original index bits) when tiled, else the cloud itself

@@ -29,6 +29,7 @@
 //   nn           exact nearest neighbour into a target's search grid, the fused ICP pass and its fold
 //   mls          moving-least-squares smoothing and normals over the same grid
 //   plane        RANSAC plane segmentation per XY tile
+//   match        Hamming 2-NN descriptor matching, index-aligned 3-D keypoints, the batched rigid fit
 // The launchers follow in this file.
 #include <string.h>
 
@@ -51,6 +52,7 @@ namespace o3dr {
 #include "kernels/nn.inc"
 #include "kernels/mls.inc"
 #include "kernels/plane.inc"
+#include "kernels/match.inc"
 
 // =================================================================================================
 // launchers
@@ -854,6 +856,50 @@ void launch_plane_fit(Profiler* pf, hipStream_t s, const PlaneArgs& a, int64_t m
         k_plane_refine<<<a.n_tiles, kWave, 0, s>>>(a);
     }
     k_plane_label<<<chunk_blocks, kPlaneThreads, 0, s>>>(a);
+}
+
+// feature matching (kernels/match.inc)
+void launch_match(Profiler* pf, hipStream_t s, const MatchArgs& a, const MatchPair* pairs, uint2* partial)
+{
+    ProfScope ps(pf, O3DR_K_OTHER, s);
+    constexpr int wpb = kMatchThreads / kWave;
+    for (int64_t off = 0; off < (int64_t)a.n_items; off += kMatchSliceItems) {
+        const int64_t items = (int64_t)a.n_items - off < kMatchSliceItems ? (int64_t)a.n_items - off : kMatchSliceItems;
+        k_match_scan<<<cdiv64(items, wpb), kMatchThreads, 0, s>>>(a, pairs, a.desc, partial, (uint64_t)off);
+    }
+    int64_t g = cdiv64((int64_t)a.n_rec, 256);
+    if (g > 65536) g = 65536;
+    if (g > 0) k_match_fold<<<(unsigned)g, 256, 0, s>>>(a, pairs, partial);
+}
+
+void launch_keypoints_3d(Profiler* pf, hipStream_t s, const ReprojectArgs& a, const float* kp_xy, const int32_t* kp_off, int n_frames,
+                         int n_kp, o3dr_point* out)
+{
+    ProfScope ps(pf, O3DR_K_OTHER, s);
+    if (n_kp > 0) k_keypoints_3d<<<cdiv64(n_kp, 256), 256, 0, s>>>(a, kp_xy, kp_off, n_frames, n_kp, out);
+}
+
+void launch_rigid(Profiler* pf, hipStream_t s, const RigidArgs& a, bool residual)
+{
+    ProfScope ps(pf, O3DR_K_OTHER, s);
+    const int F = residual ? 1 : kRigidFields;
+    if (a.n_blocks > 0) {
+        if (residual) {
+            k_rigid_sums<true><<<a.n_blocks, kRigidThreads, 0, s>>>(a);
+        } else {
+            (void)hipMemsetAsync(a.first, 0xff, (size_t)a.n_segs * 4, s);
+            k_rigid_first<<<a.n_blocks, kRigidThreads, 0, s>>>(a);
+            k_rigid_sums<false><<<a.n_blocks, kRigidThreads, 0, s>>>(a);
+        }
+    } else if (!residual) {
+        (void)hipMemsetAsync(a.first, 0xff, (size_t)a.n_segs * 4, s);
+    }
+    RigidArgs b = a;
+    if (residual) {
+        b.rec = a.rec + (size_t)a.n_segs * kRigidFields;
+        b.c0 = nullptr;
+    }
+    k_rigid_fold<<<dim3(a.n_segs, F), kIcpFoldThreads, 0, s>>>(b, F);
 }
 
 }  // namespace o3dr
