@@ -586,6 +586,63 @@ int  o3dr_segment_plane(o3dr_ctx* ctx, const o3dr_point* cloud, int64_t n, const
                         int32_t* tile, o3dr_point* projected, o3dr_plane_tile* tiles, int64_t tiles_capacity, int64_t* n_tiles,
                         int32_t mem);
 
+/* ---- height-field surface mesh: the reference's --mesh_surface runs pcl::GreedyProjectionTriangulation (pose.cpp:27-112,
+ * pose_functions.cpp:1711-1813).  GP3 is a sequential advancing front whose output depends on processing order; the map
+ * this library merges is a height field (at most one point per XY cell of voxel_size), so this is a 2.5-D triangulation of
+ * the occupied XY cells instead, exact and parallel.  The contract is this library's own (INTEGRATION.md lists the
+ * differences from GP3).
+ *
+ * Input: n points, n < 2^31, every coordinate finite.  cell_size finite and > 0, with (float)cell_size and
+ * 1.0f / (float)cell_size both finite and > 0; L = max_edge_length > 0 (may be +inf).
+ *   1. Cells: inv = 1.0f / (float)cell_size; a point's cell is cx = (int)floorf(x * inv), cy = (int)floorf(y * inv) (fp32:
+ *      the cell function of the voxel grid, so a map made with voxel_size vs meshes with cell_size = vs).  A cell's vertex
+ *      is its lowest-index point; the cell's other points are shadowed: counted, never referenced.
+ *   2. Quads: the quad with lower-left cell (cx, cy) has corners a = (cx, cy), b = (cx+1, cy), c = (cx+1, cy+1),
+ *      d = (cx, cy+1), counter-clockwise in XY.  Only quads with at least 3 occupied corners emit anything (a may be the
+ *      empty one).
+ *   3. Predicates: orient(p, q, r) = (qx-px)*(ry-py) - (qy-py)*(rx-px) in fp64 from the fp32 coordinates, as written, no
+ *      FMA.  An edge's d2 = ((0 + dx*dx) + dy*dy) + dz*dz in fp32 without FMA (d = q - p; the d2 of o3dr_nearest_neighbors);
+ *      it passes the gate iff d2 <= (float)(L*L), the product in fp64.  A triangle is kept iff orient > 0 and all three
+ *      of its edges pass the gate.
+ *   4. Four corners: diagonal a-c splits into (a,b,c), (a,c,d); diagonal b-d into (a,b,d), (b,c,d).  A split is valid iff
+ *      both of its triangles have orient > 0.  Both valid: the one whose diagonal has the smaller d2, a-c on a tie; one
+ *      valid: that one; neither: a-c.  Then the keep rule of 3 applies to each triangle of the chosen split.
+ *   5. Three corners: the one triangle (b,c,d), (a,c,d), (a,b,d) or (a,b,c) for a missing a, b, c or d; the keep rule
+ *      applies.  A candidate that is not kept counts in n_rejected_orientation (orient <= 0) or else n_rejected_length.
+ *   6. Output: tris holds 3 int32 input indices per kept triangle (so vertices stay index-aligned with the input), in
+ *      ascending (cy, cx) of the quad (y outer, x inner), a quad's triangles in the order of 4 / 5 and their vertices as
+ *      listed there (counter-clockwise in XY).  At most 2 n_vertices triangles.  *n_tris (host) = their count;
+ *      tris_capacity (in triangles) below it: O3DR_ERR_CAPACITY with *n_tris set and nothing else written.  tris NULL
+ *      (capacity 0): only the counts.
+ *   7. vertex_normals (3n floats, optional), index-aligned with the input: for the vertex of cell (cx, cy), the kept
+ *      triangles that use it, from the quads with lower-left cells (cx-1,cy-1), (cx,cy-1), (cx-1,cy), (cx,cy) in that
+ *      order and each quad's triangles in emission order.  Their unnormalised fp64 face normals (q-p) x (r-p), with
+ *      e = q - p, f = r - p in fp64: (ey fz - ez fy, ez fx - ex fz, ex fy - ey fx), are summed in that order from 0; the
+ *      sum s is divided by sqrt((sx sx + sy sy) + sz sz) in fp64, then rounded to fp32.  A vertex without a triangle and a
+ *      shadowed point get NaN.  Kept triangles are counter-clockwise, so normals have nz > 0 (the MLS orientation).
+ * Limits, else O3DR_ERR_INVALID_ARG: cell indices within int32; the cell box (cx_max - cx_min + 1)(cy_max - cy_min + 1)
+ * <= 2^32 cells (the dense cell id is a 32-bit sort key: 65536 x 65536 cells, 3.2 km x 3.2 km at 0.05 m and more).  A
+ * non-finite coordinate anywhere (found before any grid work) or a bad parameter: O3DR_ERR_INVALID_ARG.  On an error other
+ * than CAPACITY the host outputs are zeroed and *n_tris is 0.  n == 0 is OK.  Every count is an integer sum and every
+ * value a fixed-order computation: results are bit-identical across calls and across host and device memory.  The call
+ * synchronises.  It reuses the sort workspace: a pending o3dr_cloud_big_slice_counts_dev table is dropped; cloud_big is
+ * left alone. */
+typedef struct o3dr_mesh_params {
+    double cell_size;        /* > 0, finite; no usable default (0 is rejected): the map's voxel_size */
+    double max_edge_length;  /* > 0, may be +inf; no usable default: GP3's setSearchRadius */
+} o3dr_mesh_params;
+typedef struct o3dr_mesh_result {
+    int64_t n_vertices;              /* occupied cells */
+    int64_t n_shadowed;              /* points not chosen as their cell's vertex (n - n_vertices) */
+    int64_t n_triangles;
+    int64_t n_quads_full;            /* quads with 4 vertices */
+    int64_t n_rejected_orientation;  /* candidate triangles dropped, by rule (checked in that order) */
+    int64_t n_rejected_length;
+} o3dr_mesh_result;
+void o3dr_mesh_default_params(o3dr_mesh_params* p);
+int  o3dr_mesh_surface(o3dr_ctx* ctx, const o3dr_point* cloud, int64_t n, const o3dr_mesh_params* p, int32_t* tris,
+                       int64_t tris_capacity, int64_t* n_tris, float* vertex_normals, o3dr_mesh_result* res, int32_t mem);
+
 /* ---- measurement hooks (bench.py; not part of the reference surface) ------------------------ */
 /* kernel ids for o3dr_profile_* */
 #define O3DR_K_COUNT        0  /* grid-pass valid count per tile */

@@ -9,7 +9,7 @@ There is no CPU fallback: importing works anywhere, but creating a `Context` wit
 library or without a GPU raises.
 """
 from ._lib import KNN2, PLANE_TILE, POINT, RIGID_RESULT, O3drError, lib_path, load_library  # noqa: F401
-from .api import Context, IcpResult, MlsResult, Params, RigidResult  # noqa: F401
+from .api import Context, IcpResult, MeshResult, MlsResult, Params, RigidResult  # noqa: F401
 
-__all__ = ["Context", "IcpResult", "KNN2", "MlsResult", "Params", "PLANE_TILE", "POINT", "RIGID_RESULT", "RigidResult", "O3drError",
+__all__ = ["Context", "IcpResult", "KNN2", "MeshResult", "MlsResult", "Params", "PLANE_TILE", "POINT", "RIGID_RESULT", "RigidResult", "O3drError",
            "lib_path", "load_library"]

@@ -69,6 +69,15 @@ PLANE_OK, PLANE_TOO_FEW, PLANE_DEGENERATE = range(3)
 PLANE_MAX_ITERATIONS = 1 << 20
 
 
+class MeshParamsStruct(C.Structure):
+    _fields_ = [("cell_size", C.c_double), ("max_edge_length", C.c_double)]
+
+
+class MeshResultStruct(C.Structure):
+    _fields_ = [("n_vertices", C.c_int64), ("n_shadowed", C.c_int64), ("n_triangles", C.c_int64), ("n_quads_full", C.c_int64),
+                ("n_rejected_orientation", C.c_int64), ("n_rejected_length", C.c_int64)]
+
+
 class MatchParamsStruct(C.Structure):
     _fields_ = [("ratio", C.c_float), ("max_distance", C.c_int32)]
 
@@ -156,6 +165,9 @@ SYMBOLS = [
     ("o3dr_mls_smooth", C.c_int, [_vp, _vp, _i64, C.POINTER(MlsParamsStruct), _vp, _vp, _vp, _vp, C.POINTER(MlsResultStruct), _i32]),
     ("o3dr_plane_default_params", None, [C.POINTER(PlaneParamsStruct)]),
     ("o3dr_segment_plane", C.c_int, [_vp, _vp, _i64, C.POINTER(PlaneParamsStruct), _vp, _vp, _vp, _vp, _i64, _pi64, _i32]),
+    ("o3dr_mesh_default_params", None, [C.POINTER(MeshParamsStruct)]),
+    ("o3dr_mesh_surface", C.c_int, [_vp, _vp, _i64, C.POINTER(MeshParamsStruct), _vp, _i64, _pi64, _vp,
+                                    C.POINTER(MeshResultStruct), _i32]),
     ("o3dr_profile_enable", C.c_int, [_vp, _i32, _i32]),
     ("o3dr_profile_read", C.c_int, [_vp, _i32, C.POINTER(C.c_double), _pi64]),
     ("o3dr_profile_reset", C.c_int, [_vp]),

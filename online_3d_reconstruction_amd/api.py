@@ -61,6 +61,18 @@ class MlsResult:
 
 
 @dataclass
+class MeshResult:
+    """o3dr_mesh_surface's counts: vertices (occupied cells), shadowed points, kept triangles, quads with four corners and
+    the candidate triangles dropped by the orientation and the edge-length rule."""
+    n_vertices: int
+    n_shadowed: int
+    n_triangles: int
+    n_quads_full: int
+    n_rejected_orientation: int
+    n_rejected_length: int
+
+
+@dataclass
 class RigidResult:
     """o3dr_estimate_rigid_transform's result for one segment: T (float64 4x4, src -> tgt), the rms residual at T over the
     used pairs, their number and the status (RIGID_OK, RIGID_TOO_FEW, RIGID_DEGENERATE; T is the identity unless OK)."""
@@ -584,6 +596,40 @@ class Context:
         keep = good & fin(kq) & fin(tgt)
         res = self.estimateRigidTransform(kq, tgt, mask=keep)
         return rec, keep, res
+
+    # -- surface mesh (pcl::GreedyProjectionTriangulation at --mesh_surface: pose_functions.cpp:1711-1813) -----------------
+    def meshSurface(self, pts, cell_size, max_edge_length, return_normals=False, return_info=False):
+        """Height-field triangulation of the occupied XY cells (contract: include/o3dr.h, DESIGN.md "Surface mesh").
+        numpy POINT arrays, or torch [N,4] 4-byte CUDA tensors such as finalize(device=...) (results are then CUDA
+        tensors).  -> int32 [T, 3] triangles (input indices, counter-clockwise in XY, in quad order); with return_normals
+        also [N, 3] float32 vertex normals (NaN for shadowed points and vertices without a triangle); with return_info
+        also a MeshResult.  One library call: the triangle buffer holds the bound of 2 n triangles."""
+        pts, n = self._cloud(pts)
+        p_in, mem, _k = _ptr(pts)
+        prm = L.MeshParamsStruct(float(cell_size), float(max_edge_length))
+        res = L.MeshResultStruct()
+        n_tris = C.c_int64(0)
+        cap = 2 * n
+        if mem == L.MEM_DEVICE:
+            import torch
+            dev = pts.device
+            tri = torch.empty((max(cap, 1), 3), dtype=torch.int32, device=dev)
+            nrm = torch.empty((max(n, 1), 3), dtype=torch.float32, device=dev) if return_normals else None
+            self._order_after_torch()
+            L.check(self._lib.o3dr_mesh_surface(self._h, p_in, n, C.byref(prm), tri.data_ptr(), cap, C.byref(n_tris),
+                                                None if nrm is None else nrm.data_ptr(), C.byref(res), L.MEM_DEVICE))
+        else:
+            tri = np.empty((max(cap, 1), 3), np.int32)
+            nrm = np.empty((n, 3), np.float32) if return_normals else None
+            L.check(self._lib.o3dr_mesh_surface(self._h, p_in, n, C.byref(prm), tri.ctypes.data, cap, C.byref(n_tris),
+                                                None if nrm is None else nrm.ctypes.data, C.byref(res), mem))
+        ret = (tri[:int(n_tris.value)],)
+        if return_normals:
+            ret += (nrm[:n],)
+        if return_info:
+            ret += (MeshResult(int(res.n_vertices), int(res.n_shadowed), int(res.n_triangles), int(res.n_quads_full),
+                               int(res.n_rejected_orientation), int(res.n_rejected_length)),)
+        return ret[0] if len(ret) == 1 else ret
 
     def voxelGrid(self, pts, leaf, min_points=0, z_offset=0.0, return_status=False):
         """pcl::VoxelGrid<PointXYZRGB> as the reference configures it (pose_functions.cpp:1689-1700)."""

@@ -138,6 +138,8 @@ struct o3dr_ctx {
     // o3dr_segment_plane: points in tile order + run heads, tile tables, hypotheses + scores, flags, staged host outputs
     DevBuf pl_pts, pl_tiles, pl_hyp, pl_misc, pl_out;
     uint64_t pl_last_hyp = 0;  // hypotheses of the last call in pl_hyp (o3dr_test_plane_hypotheses)
+    // o3dr_mesh_surface: run heads + vertex tables, flags / range / counters, staged host outputs
+    DevBuf ms_work, ms_misc, ms_out;
     // o3dr_match_knn2_hamming: staged pool, pair table, chunk partials, staged records + mask; the host copy of the table
     DevBuf mt_desc, mt_tab, mt_part, mt_out;
     std::vector<MatchPair> mt_tab_h;
@@ -487,7 +489,7 @@ extern "C" int o3dr_ctx_destroy(o3dr_ctx* c)
     for (DevBuf* b : {&c->inc.box, &c->inc.scratch, &c->inc.tg, &c->inc.tmatch, &c->inc.flag, &c->inc.src, &c->inc.keep,
                       &c->inc.partial, &c->inc.words, &c->inc.fb, &c->nn_q, &c->nn_t, &c->nn_cells, &c->nn_src, &c->mls_out, &c->mls_misc,
                       &c->pl_pts, &c->pl_tiles, &c->pl_hyp, &c->pl_misc, &c->pl_out, &c->mt_desc, &c->mt_tab, &c->mt_part,
-                      &c->mt_out, &c->rg_in, &c->rg_work})
+                      &c->mt_out, &c->rg_in, &c->rg_work, &c->ms_work, &c->ms_misc, &c->ms_out})
         dev_release(*b);
     delete c;
     return O3DR_OK;
@@ -3378,6 +3380,134 @@ extern "C" int o3dr_segment_plane(o3dr_ctx* c, const o3dr_point* cloud, int64_t 
             if (projected && (const void*)projected != (const void*)cloud) memset(projected, 0, (size_t)n * sizeof(o3dr_point));
         }
         if (mem == O3DR_MEM_HOST && tiles && tiles_capacity > 0) memset(tiles, 0, (size_t)tiles_capacity * sizeof(o3dr_plane_tile));
+    }
+    return rc;
+}
+
+// -------------------------------------------------------------------------------------------------
+// height-field surface mesh (kernels/mesh.inc; DESIGN.md "Surface mesh")
+// -------------------------------------------------------------------------------------------------
+extern "C" void o3dr_mesh_default_params(o3dr_mesh_params* p)
+{
+    if (!p) return;
+    p->cell_size = 0.0;        // no usable default: the map's voxel_size
+    p->max_edge_length = 0.0;  // no usable default: GP3's search radius
+}
+
+static int mesh_surface(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const o3dr_mesh_params* p, int32_t* tris,
+                        int64_t tris_capacity, int64_t* n_tris, float* normals, o3dr_mesh_result* res, int32_t mem)
+{
+    if (n < 0 || (n > 0 && !cloud)) return fail(O3DR_ERR_INVALID_ARG, "bad arguments (cloud pointer / size)");
+    if (n >= (int64_t)1 << 31) return fail(O3DR_ERR_INVALID_ARG, "2^31 or more points in one cloud");
+    if (!p) return fail(O3DR_ERR_INVALID_ARG, "params is NULL");
+    if (!n_tris) return fail(O3DR_ERR_INVALID_ARG, "n_tris is NULL");
+    if (tris_capacity < 0 || (tris_capacity > 0 && !tris)) return fail(O3DR_ERR_INVALID_ARG, "bad tris / tris_capacity");
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    const double cs = p->cell_size, L = p->max_edge_length;
+    const float csf = (float)cs, inv = 1.0f / csf;
+    if (!(std::isfinite(cs) && cs > 0.0 && std::isfinite(csf) && csf > 0.f && std::isfinite(inv) && inv > 0.f))
+        return fail(O3DR_ERR_INVALID_ARG, "cell_size must be finite and > 0 (and usable in fp32)");
+    if (!(L > 0.0)) return fail(O3DR_ERR_INVALID_ARG, "max_edge_length must be > 0 (+inf: no gate)");
+    c->place_ub = -1;
+    if (n == 0) return O3DR_OK;
+    CHK(dev_ensure(c, c->ms_misc, 256));
+    uint32_t* flag = (uint32_t*)c->ms_misc.p;                   // [0] non-finite
+    uint32_t* range = (uint32_t*)((char*)c->ms_misc.p + 64);    // cx_min cx_max cy_min cy_max (order-preserving), [4] out of int32
+    uint32_t* cnt_dev = (uint32_t*)((char*)c->ms_misc.p + 128);  // V, T
+    uint32_t* counters = (uint32_t*)((char*)c->ms_misc.p + 192);
+    const size_t b_u32 = align256((size_t)n * 4), b_f4 = align256((size_t)n * 16);
+    const size_t b_part = align256((size_t)((n + 255) / 256) * kMeshPartWords * 4);  // one record per 256-thread workgroup
+    CHK(dev_ensure(c, c->ms_work, 3 * b_u32 + 2 * b_f4 + b_part));
+    char* wb = (char*)c->ms_work.p;
+    uint32_t* part = (uint32_t*)(wb + 3 * b_u32 + 2 * b_f4);
+    const void* cloud_d;
+    CHK(stage_in(c, c->nn_t, cloud, (size_t)n * sizeof(o3dr_point), mem, &cloud_d));
+    launch_mls_finite(&c->prof, c->stream, (const o3dr_point*)cloud_d, n, flag);
+    HIPCHK(hipGetLastError());
+    uint32_t hbuf[6];
+    HIPCHK(hipMemcpyAsync(hbuf, flag, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (hbuf[0]) return fail(O3DR_ERR_INVALID_ARG, "the cloud has a non-finite coordinate");
+    launch_mesh_range(&c->prof, c->stream, (const o3dr_point*)cloud_d, n, inv, part, range);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hbuf + 1, range, 20, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (hbuf[5]) return fail(O3DR_ERR_INVALID_ARG, "a cell index does not fit in int32 (cell_size too small)");
+
+    MeshArgs a;
+    memset(&a, 0, sizeof a);
+    a.cloud = (const o3dr_point*)cloud_d;
+    a.n = (uint32_t)n;
+    a.inv = inv;
+    a.lf = (float)(L * L);
+    a.cx0 = (int32_t)(hbuf[1] ^ 0x80000000u);
+    a.cy0 = (int32_t)(hbuf[3] ^ 0x80000000u);
+    a.wx = (uint64_t)(hbuf[2] - hbuf[1]) + 1;
+    a.wy = (uint64_t)(hbuf[4] - hbuf[3]) + 1;
+    if (a.wx > (1ull << 32) / a.wy) return fail(O3DR_ERR_INVALID_ARG, "the cells' index box holds more than 2^32 cells");
+    const uint64_t max_key = a.wx * a.wy - 1;
+    int nbits = 0;
+    while (nbits < 32 && (max_key >> nbits) != 0) ++nbits;
+    CHK(ws_ensure(c, 1, n, false));
+    uint32_t* head = (uint32_t*)wb;
+    a.cnt = (uint32_t*)(wb + b_u32);
+    a.vkey = (uint32_t*)(wb + 2 * b_u32);
+    a.vpt = (float4*)(wb + 3 * b_u32);
+    a.nbr = (int4*)(wb + 3 * b_u32 + b_f4);
+    a.n_vert = cnt_dev;
+    a.part = part;
+    a.counters = counters;
+    launch_mesh_cells(&c->prof, c->stream, c->ws, a, nbits, head, cnt_dev);
+    launch_mesh_count(&c->prof, c->stream, c->ws, a, cnt_dev + 1);
+    HIPCHK(hipGetLastError());
+    uint32_t cnt_h[3];
+    HIPCHK(hipMemcpyAsync(hbuf, cnt_dev, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(cnt_h, counters, sizeof cnt_h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const int64_t V = hbuf[0], T = hbuf[1];
+    *n_tris = T;
+    if (tris && T > tris_capacity) return fail(O3DR_ERR_CAPACITY, "tris_capacity is below the triangle count");
+    a.tris = T > 0 ? tris : nullptr;
+    a.normals = normals;
+    if (mem == O3DR_MEM_HOST && (a.tris || normals)) {  // staged: triangles, normals
+        const size_t b_tri = align256((size_t)T * 12);
+        CHK(dev_ensure(c, c->ms_out, b_tri + (size_t)n * 12));
+        if (a.tris) a.tris = (int32_t*)c->ms_out.p;
+        if (normals) a.normals = (float*)((char*)c->ms_out.p + b_tri);
+    }
+    launch_mesh_emit(&c->prof, c->stream, a);
+    HIPCHK(hipGetLastError());
+    if (mem == O3DR_MEM_HOST) {
+        if (a.tris) HIPCHK(hipMemcpyAsync(tris, a.tris, (size_t)T * 12, hipMemcpyDeviceToHost, c->stream));
+        if (normals) HIPCHK(hipMemcpyAsync(normals, a.normals, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (res) {
+        res->n_vertices = V;
+        res->n_shadowed = n - V;
+        res->n_triangles = T;
+        res->n_quads_full = (int64_t)cnt_h[0];
+        res->n_rejected_orientation = (int64_t)cnt_h[1];
+        res->n_rejected_length = (int64_t)cnt_h[2];
+    }
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_mesh_surface(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const o3dr_mesh_params* p, int32_t* tris,
+                                 int64_t tris_capacity, int64_t* n_tris, float* vertex_normals, o3dr_mesh_result* res, int32_t mem)
+{
+    if (n_tris) *n_tris = 0;
+    if (res) memset(res, 0, sizeof *res);
+    auto entered = [&]() -> int {
+        CTX_ENTER(c);
+        return mesh_surface(c, cloud, n, p, tris, tris_capacity, n_tris, vertex_normals, res, mem);
+    };
+    const int rc = entered();
+    if (rc != O3DR_OK && rc != O3DR_ERR_CAPACITY) {  // host outputs zeroed on error
+        if (n_tris) *n_tris = 0;
+        if (mem == O3DR_MEM_HOST && vertex_normals && n > 0 && n < (int64_t)1 << 31) memset(vertex_normals, 0, (size_t)n * 12);
+        if (mem == O3DR_MEM_HOST && tris && tris_capacity > 0 && tris_capacity < (int64_t)1 << 32)
+            memset(tris, 0, (size_t)tris_capacity * 12);
     }
     return rc;
 }

@@ -385,6 +385,37 @@ void launch_plane_order(Profiler* pf, hipStream_t s, Workspace& ws, PlaneArgs& a
                         uint32_t* n_tiles_dev);
 void launch_plane_tiles(Profiler* pf, hipStream_t s, Workspace& ws, const PlaneArgs& a);
 void launch_plane_fit(Profiler* pf, hipStream_t s, const PlaneArgs& a, int64_t max_chunks, int optimize);
+// height-field surface mesh (kernels/mesh.inc; the fields are filled by o3dr_mesh_surface step by step)
+struct MeshArgs {
+    const o3dr_point* cloud;      // the cloud in input order
+    uint32_t n;
+    float inv;                    // 1.0f / (float)cell_size
+    float lf;                     // (float)(L * L): the edge gate on d2
+    int32_t cx0, cy0;             // the cell box's lower corner
+    uint64_t wx, wy;              // its widths in cells (wx * wy <= 2^32)
+    const uint32_t* keys;         // n sorted dense cell ids
+    const uint32_t* perm;         // n input indices in sorted order
+    const uint32_t* ord;          // n: the scanned run heads (the vertex ordinal of every head)
+    const uint32_t* n_vert;       // device: V, the vertex count
+    uint32_t* vkey;               // V cell ids in cell order
+    float4* vpt;                  // V vertices: x y z, input index bits in .w
+    int4* nbr;                    // V: the ordinals of the right, upper-right, upper and upper-left cells (-1: empty)
+    uint32_t* cnt;                // n: kept triangles per vertex, then their exclusive scan (the first triangle's slot)
+    uint32_t* part;               // kMeshPart words per workgroup of the whole-cloud reductions
+    uint32_t* counters;           // full quads, rejected by orientation, rejected by length
+    int32_t* tris;                // 3 T
+    float* normals;               // 3 n
+};
+// launch_mesh_range: the order-preserving cell index range of the n points (range[4]: cx_min cx_max cy_min cy_max, each as
+// int32 ^ 0x80000000; range[4] = 1 if an index leaves int32), through `part` (kMeshPartWords per 256 points).  launch_mesh_cells: the sort of the dense cell ids (nbits
+// wide) in ws, the run heads scanned into vertex ordinals (head, n words; V -> *n_vert_dev) and the vertices gathered
+// (a.keys, a.perm, a.ord set).  launch_mesh_count: neighbours, triangles per vertex scanned into offsets (T -> *n_tris_dev)
+// and the counters.  launch_mesh_emit: the triangles (a.tris) and the vertex normals (a.normals), each if set.
+constexpr int kMeshPartWords = 8;  // kMeshPart
+void launch_mesh_range(Profiler* pf, hipStream_t s, const o3dr_point* in, int64_t n, float inv, uint32_t* part, uint32_t* range);
+void launch_mesh_cells(Profiler* pf, hipStream_t s, Workspace& ws, MeshArgs& a, int nbits, uint32_t* head, uint32_t* n_vert_dev);
+void launch_mesh_count(Profiler* pf, hipStream_t s, Workspace& ws, const MeshArgs& a, uint32_t* n_tris_dev);
+void launch_mesh_emit(Profiler* pf, hipStream_t s, const MeshArgs& a);
 void launch_partition(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelArgs& v, int n_parts, o3dr_point* out,
                       uint64_t* counts_dev, uint32_t* overflow_dev, const void* hdrs_dev = nullptr, int n_hdrs = 0);
 // its two halves: slice sizes without moving anything (the (part, tile) table stays in ws for the second half), then the move

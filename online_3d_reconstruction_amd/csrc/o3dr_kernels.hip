@@ -29,6 +29,7 @@
 //   nn           exact nearest neighbour into a target's search grid, the fused ICP pass and its fold
 //   mls          moving-least-squares smoothing and normals over the same grid
 //   plane        RANSAC plane segmentation per XY tile
+//   mesh         height-field surface mesh over the XY cells
 //   match        Hamming 2-NN descriptor matching, index-aligned 3-D keypoints, the batched rigid fit
 // The launchers follow in this file.
 #include <string.h>
@@ -52,6 +53,7 @@ namespace o3dr {
 #include "kernels/nn.inc"
 #include "kernels/mls.inc"
 #include "kernels/plane.inc"
+#include "kernels/mesh.inc"
 #include "kernels/match.inc"
 
 // =================================================================================================
@@ -808,24 +810,30 @@ void launch_plane_range(Profiler* pf, hipStream_t s, const o3dr_point* in, int64
     k_plane_range<<<g, 256, 0, s>>>(in, n, tile_size, range, flag);
 }
 
+// Stable sort of the n nbits-wide keys in ws.keys[0], the payload being the input position: at least one pass (it also
+// writes the payload).  Returns the buffer the sorted records end in.
+static int launch_sort_keys(Workspace& ws, hipStream_t s, uint32_t n, int nbits)
+{
+    VoxelGeom g;
+    memset(&g, 0, sizeof g);
+    for (int k = 0; k < 3; ++k) g.inv[k] = 1.f, g.div_b[k] = 1;
+    g.mul1 = g.mul2 = 1;
+    g.n = n;
+    if (nbits < 1) nbits = 1;
+    g.passes = (uint32_t)((nbits + kMaxRadixBits - 1) / kMaxRadixBits);
+    g.bpp = (uint32_t)((nbits + (int)g.passes - 1) / (int)g.passes);
+    k_plane_sort_geom<<<1, 1, 0, s>>>(ws.geom, g);
+    launch_radix_passes(ws, s, n, (int)g.passes);
+    return (int)(g.passes & 1u);
+}
+
 void launch_plane_order(Profiler* pf, hipStream_t s, Workspace& ws, PlaneArgs& a, int nbits, uint32_t* head, float4* pts,
                         uint32_t* n_tiles_dev)
 {
     ProfScope ps(pf, O3DR_K_OTHER, s);
     const int64_t n = a.n;
     k_plane_keys<<<cdiv64(n, 256), 256, 0, s>>>(a, ws.keys[0]);
-    // the sort plan: at least one pass (it also writes the payload, the input index)
-    VoxelGeom g;
-    memset(&g, 0, sizeof g);
-    for (int k = 0; k < 3; ++k) g.inv[k] = 1.f, g.div_b[k] = 1;
-    g.mul1 = g.mul2 = 1;
-    g.n = a.n;
-    if (nbits < 1) nbits = 1;
-    g.passes = (uint32_t)((nbits + kMaxRadixBits - 1) / kMaxRadixBits);
-    g.bpp = (uint32_t)((nbits + (int)g.passes - 1) / (int)g.passes);
-    k_plane_sort_geom<<<1, 1, 0, s>>>(ws.geom, g);
-    launch_radix_passes(ws, s, n, (int)g.passes);
-    const int sorted = (int)(g.passes & 1u);
+    const int sorted = launch_sort_keys(ws, s, a.n, nbits);
     a.keys = ws.keys[sorted];
     a.tile_excl = head;
     a.pts = pts;
@@ -900,6 +908,50 @@ void launch_rigid(Profiler* pf, hipStream_t s, const RigidArgs& a, bool residual
         b.c0 = nullptr;
     }
     k_rigid_fold<<<dim3(a.n_segs, F), kIcpFoldThreads, 0, s>>>(b, F);
+}
+
+// height-field surface mesh (kernels/mesh.inc)
+void launch_mesh_range(Profiler* pf, hipStream_t s, const o3dr_point* in, int64_t n, float inv, uint32_t* part, uint32_t* range)
+{
+    ProfScope ps(pf, O3DR_K_OTHER, s);
+    if (n <= 0) return;
+    int g = cdiv64(n, kMeshThreads);
+    if (g > 1024) g = 1024;
+    k_mesh_range<<<g, kMeshThreads, 0, s>>>(in, n, inv, part);
+    k_mesh_fold<<<1, kMeshThreads, 0, s>>>(part, g, 0, 0, 1, 0, 1, range);
+    k_mesh_fold<<<1, kMeshThreads, 0, s>>>(part, g, 4, 1, 1, 1, 1, range + 4);
+}
+
+void launch_mesh_cells(Profiler* pf, hipStream_t s, Workspace& ws, MeshArgs& a, int nbits, uint32_t* head, uint32_t* n_vert_dev)
+{
+    ProfScope ps(pf, O3DR_K_OTHER, s);
+    const int64_t n = a.n;
+    k_mesh_keys<<<cdiv64(n, kMeshThreads), kMeshThreads, 0, s>>>(a, ws.keys[0]);
+    const int sorted = launch_sort_keys(ws, s, a.n, nbits);
+    a.keys = ws.keys[sorted];
+    a.perm = ws.vals[sorted];
+    a.ord = head;
+    k_mesh_heads<<<cdiv64(n, kMeshThreads), kMeshThreads, 0, s>>>(a, head);
+    launch_scan(s, head, n, n, 1, n_vert_dev, nullptr, ws.scan_partial);
+    k_mesh_vertices<<<cdiv64(n, kMeshThreads), kMeshThreads, 0, s>>>(a);
+}
+
+void launch_mesh_count(Profiler* pf, hipStream_t s, Workspace& ws, const MeshArgs& a, uint32_t* n_tris_dev)
+{
+    ProfScope ps(pf, O3DR_K_OTHER, s);
+    const int64_t n = a.n;
+    const int g = cdiv64(n, kMeshThreads);
+    k_mesh_count<<<g, kMeshThreads, 0, s>>>(a);
+    k_mesh_fold<<<1, kMeshThreads, 0, s>>>(a.part, g, 0, 2, 2, 2, 2, a.counters);
+    launch_scan(s, a.cnt, n, n, 1, n_tris_dev, nullptr, ws.scan_partial);
+}
+
+void launch_mesh_emit(Profiler* pf, hipStream_t s, const MeshArgs& a)
+{
+    ProfScope ps(pf, O3DR_K_OTHER, s);
+    const int64_t n = a.n;
+    if (a.tris) k_mesh_emit<<<cdiv64(n, kMeshThreads), kMeshThreads, 0, s>>>(a);
+    if (a.normals) k_mesh_normals<<<cdiv64(n, kMeshThreads), kMeshThreads, 0, s>>>(a);
 }
 
 }  // namespace o3dr

@@ -5,11 +5,11 @@
 // hot path that the CLI needs to run end to end (flag parsing, calibration/pose/time CSV readers,
 // timestamp binding, generateTmat, the variance gate, PNG/PLY I/O) is restated here in plain C++:
 // it is control plane, one call per frame or per run, and stays on the host.  Pose estimation (ORB,
-// matching, the ICP trajectory correction), visualisation, the mesh tool and --segment_cloud in a reconstruction run are not part of
+// matching, the ICP trajectory correction), visualisation and --segment_cloud in a reconstruction run are not part of
 // this build; the CLI runs with the recorded MAVLink poses (the reference's --only_MAVLink mode,
 // pose_functions.cpp:232-236).  The --align_point_cloud tool (ICP on two PLYs) runs on o3dr_icp_align, the
 // --smooth_surface tool (MLS on one PLY) on o3dr_mls_smooth, the --segment_cloud_only tool (RANSAC planes per XY tile on
-// one PLY) on o3dr_segment_plane.
+// one PLY) on o3dr_segment_plane, the --mesh_surface tool (a height-field triangulation of one PLY) on o3dr_mesh_surface.
 #pragma once
 #include <array>
 #include <cmath>
@@ -49,6 +49,10 @@ bool save_ply_binary(const std::string& path, const PointCloud& cloud, const std
 // pcl::PLYReader for binary little-endian files: x y z red green blue by name out of the vertex element (the files
 // save_ply_binary writes, build/cloud.ply); false if one is missing or the vertex layout is not fixed-size
 bool read_ply(const std::string& path, PointCloud& cloud);
+// a triangle mesh as pcl::io::savePLYFileBinary writes a PolygonMesh: the vertices (x y z float + red green blue uchar, with
+// normals (3 floats per point) also nx ny nz float), then `element face` with `property list uchar int vertex_indices`
+bool save_ply_mesh(const std::string& path, const PointCloud& cloud, const std::vector<int32_t>& tris,
+                   const std::vector<float>* normals = nullptr);
 
 class RawImageData {  // pose.h:54-70
 public:
@@ -94,7 +98,7 @@ public:
     int icp_max_iterations = 10;     // --icp_max_iterations (pcl::Registration defaults)
     double icp_max_corr_dist = HUGE_VAL, icp_transformation_epsilon = 0.0;  // --icp_max_corr_dist, --icp_transformation_epsilon
     bool smooth_surface = false;     // --smooth_surface file.ply (pose.cpp:27-112): MLS through o3dr_mls_smooth
-    double search_radius = 0.0;      // --search_radius: required by --smooth_surface, ignored elsewhere
+    double search_radius = 0.0;      // --search_radius: required by --smooth_surface and --mesh_surface, ignored elsewhere
     bool search_radius_set = false;
     int mls_polynomial_order = 2;    // --mls_polynomial_order (PCL's default)
     double mls_sqr_gauss_param = 0.0;  // --mls_sqr_gauss_param (0: search_radius^2)
@@ -106,6 +110,8 @@ public:
     double segment_tile_size = 0.0;  // --segment_tile_size (0: one plane for the cloud)
     unsigned long long sac_seed = 0; // --sac_seed
     int sac_optimize = 1;            // --sac_optimize
+    bool mesh_surface = false;       // --mesh_surface file.ply (pose.cpp:27-112, GP3): o3dr_mesh_surface
+    bool mesh_normals = false;       // --mesh_normals: nx ny nz per vertex
     int device_id = 0;
     int n_gpus = 1;                 // --gpus N: frames sharded over devices device_id .. device_id+N-1, one host thread and
                                     // one context each, merged through o3dr_merge_partitioned (RCCL)
@@ -144,6 +150,7 @@ private:
     void run_align_point_cloud();                   // --align_point_cloud
     void run_smooth_surface();                      // --smooth_surface
     void run_segment_cloud();                       // --segment_cloud_only
+    void run_mesh_surface();                        // --mesh_surface
     int first_img_num = -1, last_img_num = -1;
     bool run3d_reconstruction = true;
     std::vector<std::vector<double>> pose_data, images_times_data;

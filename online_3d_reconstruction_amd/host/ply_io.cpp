@@ -60,6 +60,47 @@ bool save_ply_binary(const std::string& path, const PointCloud& cloud, const std
     return true;
 }
 
+bool save_ply_mesh(const std::string& path, const PointCloud& cloud, const std::vector<int32_t>& tris, const std::vector<float>* normals)
+{
+    if (normals && normals->size() != cloud.points.size() * 3) return false;
+    if (tris.size() % 3 != 0) return false;
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) return false;
+    std::ostringstream h;
+    h << "ply\nformat binary_little_endian 1.0\ncomment PCL generated\n"
+      << "element vertex " << cloud.points.size() << "\n"
+      << "property float x\nproperty float y\nproperty float z\n"
+      << "property uchar red\nproperty uchar green\nproperty uchar blue\n";
+    if (normals) h << "property float nx\nproperty float ny\nproperty float nz\n";
+    h << "element face " << tris.size() / 3 << "\n"
+      << "property list uchar int vertex_indices\nend_header\n";
+    const std::string hs = h.str();
+    bool ok = fwrite(hs.data(), 1, hs.size(), f) == hs.size();
+    const size_t rec_bytes = normals ? 27 : 15;
+    std::vector<uint8_t> buf;
+    buf.reserve(cloud.points.size() * rec_bytes + tris.size() / 3 * 13);
+    for (size_t i = 0; i < cloud.points.size(); ++i) {
+        const PointXYZRGB& p = cloud.points[i];
+        uint8_t rec[27];
+        memcpy(rec, &p.x, 4);
+        memcpy(rec + 4, &p.y, 4);
+        memcpy(rec + 8, &p.z, 4);
+        rec[12] = (uint8_t)(p.rgba >> 16);
+        rec[13] = (uint8_t)(p.rgba >> 8);
+        rec[14] = (uint8_t)p.rgba;
+        if (normals) memcpy(rec + 15, normals->data() + 3 * i, 12);
+        buf.insert(buf.end(), rec, rec + rec_bytes);
+    }
+    for (size_t t = 0; t < tris.size(); t += 3) {
+        uint8_t rec[13];
+        rec[0] = 3;
+        memcpy(rec + 1, &tris[t], 12);
+        buf.insert(buf.end(), rec, rec + 13);
+    }
+    if (!buf.empty()) ok = ok && fwrite(buf.data(), 1, buf.size(), f) == buf.size();
+    return fclose(f) == 0 && ok;
+}
+
 // the byte size of a PLY scalar type (0: unknown)
 static size_t ply_type_size(const std::string& t)
 {

@@ -403,14 +403,18 @@ void Pose::printUsage()
             "       [--mls_normals]   (moving-least-squares smoothing: writes the fitted points, in input order, as\n"
             "                     smoothed_<file> next to it - that file name is this build's own; --search_radius is required\n"
             "                     here; --mls_normals adds normal_x normal_y normal_z curvature per point)\n"
-            "--search_radius is ignored in every other mode.\n"
+            "--search_radius is ignored in every mode but --smooth_surface and --mesh_surface.\n"
             "./pose --segment_cloud_only file.ply --sac_distance_threshold t [--sac_max_iterations n] [--segment_tile_size m]\n"
             "       [--sac_seed s] [--sac_optimize 0|1]   (RANSAC plane per XY tile of m metres, 0 = one plane for the cloud:\n"
             "                     writes the inliers projected onto their tile's plane as ground_<file> and the rest as\n"
             "                     nonground_<file>, both in input order, next to it - those file names are this build's own;\n"
             "                     --sac_distance_threshold is required)\n"
-            "Pose estimation (ORB matching, the ICP trajectory correction), visualisation, the mesh tool and --segment_cloud in a\n"
-            "reconstruction run are not part of this build.\n";
+            "./pose --mesh_surface file.ply --search_radius L [--voxel_size m] [--mesh_normals]   (height-field triangulation of\n"
+            "                     the occupied XY cells of size m, edges up to L: writes every point, in input order, and the\n"
+            "                     triangles as mesh_<file> next to it - that file name is this build's own; --search_radius is\n"
+            "                     required here; --mesh_normals adds nx ny nz per vertex)\n"
+            "Pose estimation (ORB matching, the ICP trajectory correction), visualisation and --segment_cloud in a reconstruction\n"
+            "run are not part of this build.\n";
 }
 
 int Pose::parseCmdArgs(int argc, char** argv)
@@ -450,6 +454,14 @@ int Pose::parseCmdArgs(int argc, char** argv)
             run3d_reconstruction = false;
             read_PLY_filename0 = argv[++i];
         }
+        else if (a == "--mesh_surface") {
+            if (i + 1 >= argc || string(argv[i + 1]).rfind("--", 0) == 0)
+                throw runtime_error("missing argument: --mesh_surface needs file.ply");
+            mesh_surface = true;
+            run3d_reconstruction = false;
+            read_PLY_filename0 = argv[++i];
+        }
+        else if (a == "--mesh_normals") mesh_normals = true;
         else if (a == "--sac_distance_threshold") { sac_distance_threshold = atof(need(i)); sac_distance_threshold_set = true; }
         else if (a == "--sac_max_iterations") sac_max_iterations = atoi(need(i));
         else if (a == "--segment_tile_size") segment_tile_size = atof(need(i));
@@ -481,7 +493,7 @@ int Pose::parseCmdArgs(int argc, char** argv)
         else if (a == "--device") device_id = atoi(need(i));
         else if (a == "--gpus") n_gpus = atoi(need(i));
         else if (a == "--partitioned_merge") partitioned_merge = true;
-        else if (a == "--search_radius") { search_radius = atof(need(i)); search_radius_set = true; }  // --smooth_surface only
+        else if (a == "--search_radius") { search_radius = atof(need(i)); search_radius_set = true; }  // --smooth_surface, --mesh_surface
         else if (a == "--dist_nearby" || a == "--range_width") { need(i); }
         else if (a == "--preview") preview = true;
         else if (a == "--use_segment_labels" || a == "--segment_cloud" || a == "--displayUAVPositions" ||
@@ -649,6 +661,45 @@ void Pose::run_segment_cloud()
     }
 }
 
+// pose.cpp:27-112 --mesh_surface: pcl::GreedyProjectionTriangulation over one PLY, here o3dr_mesh_surface's height-field
+// triangulation of the occupied XY cells of --voxel_size (contract: include/o3dr.h; the differences from GP3 are in
+// INTEGRATION.md).  Every point is written in input order, then the triangles, as mesh_<file> next to the source.
+void Pose::run_mesh_surface()
+{
+    if (!search_radius_set) throw runtime_error("missing argument: --mesh_surface needs --search_radius L");
+    Q = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // the tool needs no camera
+    PointCloud::Ptr cloud = read_PLY_File(read_PLY_filename0);
+    const int64_t n = (int64_t)cloud->points.size();
+    o3dr_mesh_params prm;
+    o3dr_mesh_default_params(&prm);
+    prm.cell_size = voxel_size;
+    prm.max_edge_length = search_radius;
+    vector<int32_t> tris((size_t)(2 * n) * 3);  // at most 2 triangles per vertex
+    vector<float> nrm(mesh_normals ? (size_t)n * 3 : 0);
+    int64_t n_tris = 0;
+    o3dr_mesh_result res;
+    o3dr_ctx* c = ctx_for_this_thread();
+    const auto t0 = chrono::steady_clock::now();
+    chk(o3dr_mesh_surface(c, cloud->points.data(), n, &prm, tris.data(), 2 * n, &n_tris, mesh_normals ? nrm.data() : nullptr, &res,
+                          O3DR_MEM_HOST),
+        "o3dr_mesh_surface");
+    const double ms = chrono::duration<double, milli>(chrono::steady_clock::now() - t0).count();
+    tris.resize((size_t)n_tris * 3);
+    cout << "points in " << n << endl;
+    cout << "vertices " << res.n_vertices << " (shadowed points " << res.n_shadowed << ")" << endl;
+    cout << "triangles " << res.n_triangles << " (full quads " << res.n_quads_full << ")" << endl;
+    cout << "rejected orientation " << res.n_rejected_orientation << ", length " << res.n_rejected_length << endl;
+    char line[64];
+    snprintf(line, sizeof line, "mesh time %.3f ms", ms);
+    cout << line << endl;
+    string outp = read_PLY_filename0;
+    const size_t slash = outp.find_last_of('/');
+    outp = (slash == string::npos ? string() : outp.substr(0, slash + 1)) + "mesh_" +
+           (slash == string::npos ? outp : outp.substr(slash + 1));
+    if (!save_ply_mesh(outp, *cloud, tris, mesh_normals ? &nrm : nullptr)) throw runtime_error("could not write " + outp);
+    cerr << "Saved mesh with " << n << " vertices and " << n_tris << " faces to " << outp << endl;
+}
+
 // pose.cpp:23-565 restricted to the hot path
 Pose::Pose(int argc, char* argv[])
 {
@@ -675,6 +726,10 @@ Pose::Pose(int argc, char* argv[])
     }
     if (segment_cloud_only) {
         run_segment_cloud();
+        return;
+    }
+    if (mesh_surface) {
+        run_mesh_surface();
         return;
     }
     if (!run3d_reconstruction) return;
