@@ -62,9 +62,10 @@ def nn_brute(q, t, max_distance=np.inf, chunk=256):
     return idx, d2
 
 
-def nn_tree(q, t, max_distance=np.inf, k=8):
+def nn_tree(q, t, max_distance=np.inf, k=8, stats=None):
     """the same key with a cKDTree pre-filter (k candidates in fp64) re-checked in fp32; rows whose k-th candidate does not
-    certify the result (possible ties just outside the k) fall back to brute force"""
+    certify the result (possible ties just outside the k) fall back to brute force (stats, a dict: their number is added
+    to stats["fallback"], the number of rows to stats["rows"])"""
     from scipy.spatial import cKDTree
     q, t = np.asarray(q, np.float32), np.asarray(t, np.float32)
     r2 = _r2(max_distance)
@@ -82,6 +83,9 @@ def nn_tree(q, t, max_distance=np.inf, k=8):
     bd = np.where(found, d2.astype(np.float64), np.inf)
     # certified: the k-th candidate is clearly farther than the best (nothing outside the k can tie or beat it)
     unsure = ~(dist[:, -1] ** 2 > np.minimum(bd, np.float64(r2)) * (1 + 1e-5) + 1e-12) if k < len(t) else np.zeros(len(q), bool)
+    if stats is not None:
+        stats["fallback"] = stats.get("fallback", 0) + int(unsure.sum())
+        stats["rows"] = stats.get("rows", 0) + len(q)
     if unsure.any():
         i2, d22 = nn_brute(q[unsure], t, max_distance)
         idx[unsure], d2[unsure] = i2, d22
