@@ -131,20 +131,20 @@ struct o3dr_ctx {
     int test_fail_at = 0;  // o3dr_test_fail_at: the numbered step of the next o3dr_merge_partitioned fails on this rank
     int64_t xchg_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // o3dr_merge_partitioned_stats
     // o3dr_nearest_neighbors / o3dr_icp_align: staged host clouds, the target grid's cell boxes + box, the per-call source
-    // arrays (indices of this and the previous pass, d2, the moment partials and their folded record)
+    // arrays (indices of this and the previous pass, d2, the moment partials and their folded record).  nn_t also holds the
+    // staged cloud of MLS, plane segmentation and meshing, nn_cells the grid boxes of MLS.
     DevBuf nn_q, nn_t, nn_cells, nn_src;
-    // o3dr_mls_smooth: the staged outputs of a host call and the device counters / non-finite flag
-    DevBuf mls_out, mls_misc;
-    // o3dr_segment_plane: points in tile order + run heads, tile tables, hypotheses + scores, flags, staged host outputs
-    DevBuf pl_pts, pl_tiles, pl_hyp, pl_misc, pl_out;
+    // Scratch of the operators after that (MLS, plane, mesh, match, keypoints, rigid fit), shared: nothing in it outlives a
+    // call, and within one call every block is laid out by one carve().  OP_IN: staged host inputs (descriptor pool; src /
+    // tgt / mask).  OP_WORK: the arrays sized from the arguments (plane: points in tile order + run heads; mesh: run heads +
+    // vertex tables; match: pair table + chunk partials; rigid: segment table + sums).  OP_LATE: the arrays sized from a
+    // count read back mid-call (plane: tile tables).  OP_OUT: the staged outputs of a host call.  OP_FLAGS: 256 bytes of
+    // flags / ranges / counters (MlsFlags, PlaneFlags, MeshFlags).
+    enum { OP_IN, OP_WORK, OP_LATE, OP_OUT, OP_FLAGS, OP_BUFS };
+    DevBuf op[OP_BUFS];
+    DevBuf pl_hyp;             // o3dr_segment_plane: hypotheses + scores (plane_hyp_layout), kept for the test hook
     uint64_t pl_last_hyp = 0;  // hypotheses of the last call in pl_hyp (o3dr_test_plane_hypotheses)
-    // o3dr_mesh_surface: run heads + vertex tables, flags / range / counters, staged host outputs
-    DevBuf ms_work, ms_misc, ms_out;
-    // o3dr_match_knn2_hamming: staged pool, pair table, chunk partials, staged records + mask; the host copy of the table
-    DevBuf mt_desc, mt_tab, mt_part, mt_out;
-    std::vector<MatchPair> mt_tab_h;
-    // o3dr_estimate_rigid_transform: staged src / tgt / mask, the segment table and the sums; host copies of the tables
-    DevBuf rg_in, rg_work;
+    std::vector<MatchPair> mt_tab_h;  // host copies of the match pair table, the rigid fit's segment table and transforms
     std::vector<RigidSeg> rg_seg_h;
     std::vector<double> rg_T_h;
     int64_t place_ub = -1;   // o3dr_cloud_big_slice_counts_dev ran for a cloud of at most this many points and place_parts slices:
@@ -203,6 +203,30 @@ static void dev_release(DevBuf& b)
 
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// Walks a block of scratch: take() hands out the next array, each starting on a 256-byte boundary.  A layout is written
+// once, as a function over the walker, and run twice: without a base for the block's size, with it for the pointers.
+struct Carve {
+    char* base = nullptr;
+    size_t off = 0;
+    template <class T>
+    void take(T*& p, size_t count)
+    {
+        p = base ? (T*)(base + off) : nullptr;
+        off += align256(count * sizeof(T));
+    }
+};
+// grows block `b` to hold `layout` and points the layout's arrays into it
+template <class Layout>
+static int carve(o3dr_ctx* c, DevBuf& b, Layout&& layout)
+{
+    Carve size;
+    layout(size);
+    CHK(dev_ensure(c, b, size.off));
+    Carve w{(char*)b.p, 0};
+    layout(w);
+    return O3DR_OK;
+}
+
 // (re)carve the per-batch workspace for `frames` clouds of at most `cap` points
 // need_pts: ws.pts holds frames*cap points (A1 + A2 output); grp_tmp: ws.pts holds the result slots of the grouped
 // whole-cloud voxel grid (one cloud, not in ws.pts itself)
@@ -225,65 +249,38 @@ static int ws_ensure(o3dr_ctx* c, int frames, int64_t cap, bool need_pts, bool g
         const size_t TE = emit_tiles > c->ws_emit_tiles ? emit_tiles : c->ws_emit_tiles;
         const size_t TS = sort_tiles > c->ws_sort_tiles ? sort_tiles : c->ws_sort_tiles;
         const size_t TG = seg_tiles > c->ws_seg_tiles ? seg_tiles : c->ws_seg_tiles;
-        size_t off = 0;
-        size_t o_keys0 = off; off += align256(E * 4);
-        size_t o_keys1 = off; off += align256(E * 4);
-        size_t o_vals0 = off; off += align256(E * 4);
-        size_t o_vals1 = off; off += align256(E * 4);
-        size_t o_seg = off;   off += align256(E * 4);
-        size_t o_keep = off;  off += align256(E * 4);
-        size_t o_rs = off;    off += align256(E * 4);
-        size_t o_gc = off;    off += align256(((E > (size_t)kGroupMinSlots ? E : (size_t)kGroupMinSlots) / kGroupCells + 2) * 4);
-        size_t o_tile = off;  off += align256(TE * 4);
-        size_t o_hist = off;  off += align256(TS * kMaxRadix * 4);
-        size_t o_histp = off; off += align256(TS * kMaxRadix * 4);
-        size_t o_segc = off;  off += align256(TG * 4);
-        size_t o_hb = off;    off += align256(TG * 256);
-        size_t o_part = off;  off += align256(((TS * kMaxRadix + TG + TE + E) / 4096 + 8 * (size_t)F + 16) * 4);
-        size_t o_mm = off;    off += align256(MM * 4);
-        size_t o_nv = off;    off += align256((size_t)F * 4);
-        size_t o_nk = off;    off += align256((size_t)F * 4);
-        size_t o_nx = off;    off += align256((size_t)F * 4);
-        size_t o_no = off;    off += align256((size_t)F * 4);
-        size_t o_oo = off;    off += align256((size_t)F * 8);
-        size_t o_geom = off;  off += align256((size_t)F * sizeof(VoxelGeom));
-        size_t o_geomr = off; off += align256((size_t)F * sizeof(VoxelGeom));
-        size_t o_nr = off;    off += align256((size_t)F * 4);
-        size_t o_ng = off;    off += align256((size_t)F * 4);
-        size_t o_omm = off;   off += align256((E / 64 + 8 * (size_t)F + 64) * 6 * sizeof(float));
-        size_t o_ommp = off;  off += align256((size_t)kBoxFoldBlocks * 6 * sizeof(float));
-        size_t o_wgc = off;   off += align256((E / 64 + 8 * (size_t)F + 64) * 6 * sizeof(int32_t));
-        CHK(dev_ensure(c, c->ws_block, off));
-        char* base = (char*)c->ws_block.p;
         Workspace& w = c->ws;
-        w.keys[0] = (uint32_t*)(base + o_keys0);
-        w.keys[1] = (uint32_t*)(base + o_keys1);
-        w.vals[0] = (uint32_t*)(base + o_vals0);
-        w.vals[1] = (uint32_t*)(base + o_vals1);
-        w.seg_start = (uint32_t*)(base + o_seg);
-        w.keep_idx = (uint32_t*)(base + o_keep);
-        w.run_start = (uint32_t*)(base + o_rs);
-        w.grp_cnt = (uint32_t*)(base + o_gc);
-        w.n_grp_out = (uint32_t*)(base + o_ng);
-        w.geom_runs = (VoxelGeom*)(base + o_geomr);
-        w.n_runs = (uint32_t*)(base + o_nr);
-        w.out_mm = (float*)(base + o_omm);
-        w.out_mm_partial = (float*)(base + o_ommp);
-        w.wave_gc = (int32_t*)(base + o_wgc);
-        w.tile_cnt = (uint32_t*)(base + o_tile);
-        w.hist = (uint32_t*)(base + o_hist);
-        w.hist_part = (uint32_t*)(base + o_histp);
-        w.seg_cnt = (uint32_t*)(base + o_segc);
-        w.head_bits = (uint8_t*)(base + o_hb);
-        w.scan_partial = (uint32_t*)(base + o_part);
-        w.mm = (float*)(base + o_mm);
-        w.n_valid = (uint32_t*)(base + o_nv);
-        w.n_kp = (uint32_t*)(base + o_nk);
-        w.n_vox = (uint32_t*)(base + o_nx);
-        w.n_out = (uint32_t*)(base + o_no);
-        w.out_off = (uint64_t*)(base + o_oo);
-        w.geom = (VoxelGeom*)(base + o_geom);
-        w.bytes = off;
+        const size_t boxes = E / 64 + 8 * (size_t)F + 64;
+        CHK(carve(c, c->ws_block, [&](Carve& k) {
+            k.take(w.keys[0], E);
+            k.take(w.keys[1], E);
+            k.take(w.vals[0], E);
+            k.take(w.vals[1], E);
+            k.take(w.seg_start, E);
+            k.take(w.keep_idx, E);
+            k.take(w.run_start, E);
+            k.take(w.grp_cnt, (E > (size_t)kGroupMinSlots ? E : (size_t)kGroupMinSlots) / kGroupCells + 2);
+            k.take(w.tile_cnt, TE);
+            k.take(w.hist, TS * kMaxRadix);
+            k.take(w.hist_part, TS * kMaxRadix);
+            k.take(w.seg_cnt, TG);
+            k.take(w.head_bits, TG * 256);
+            k.take(w.scan_partial, (TS * kMaxRadix + TG + TE + E) / 4096 + 8 * (size_t)F + 16);
+            k.take(w.mm, MM);
+            k.take(w.n_valid, (size_t)F);
+            k.take(w.n_kp, (size_t)F);
+            k.take(w.n_vox, (size_t)F);
+            k.take(w.n_out, (size_t)F);
+            k.take(w.out_off, (size_t)F);
+            k.take(w.geom, (size_t)F);
+            k.take(w.geom_runs, (size_t)F);
+            k.take(w.n_runs, (size_t)F);
+            k.take(w.n_grp_out, (size_t)F);
+            k.take(w.out_mm, boxes * 6);
+            k.take(w.out_mm_partial, (size_t)kBoxFoldBlocks * 6);
+            k.take(w.wave_gc, boxes * 6);
+            w.bytes = k.off;
+        }));
         c->ws_elems = E;
         c->ws_frames = F;
         c->ws_emit_tiles = TE;
@@ -319,30 +316,19 @@ static int sor_ensure(o3dr_ctx* c, int frames, int64_t cap)
         const size_t F = (size_t)(frames > c->ws_sor_frames ? frames : c->ws_sor_frames);
         uint32_t max_cells = (uint32_t)(C / 2 > 1024 ? C / 2 : 1024);
         if (max_cells > (1u << 22)) max_cells = 1u << 22;
-        size_t off = 0;
-        size_t o_xyz = off;  off += align256(F * (size_t)C * 16);
-        size_t o_pts = off;  off += align256(F * (size_t)C * 16);
-        size_t o_dist = off; off += align256(F * (size_t)C * 4);
-        size_t o_cf = off;   off += align256(F * ((size_t)max_cells + 1) * 4);
-        size_t o_cz = off;   off += align256(F * ((size_t)max_cells + 1) * 8);
-        size_t o_part = off; off += align256(F * 256 * 2 * 8);
-        size_t o_geom = off; off += align256(F * sizeof(SorGeom));
-        size_t o_n = off;    off += align256(F * 4);
-        size_t o_left = off; off += align256(F * (size_t)C * 4);
-        size_t o_lc = off;   off += align256(F * 4);
-        CHK(dev_ensure(c, c->ws_sor_block, off));
-        char* base = (char*)c->ws_sor_block.p;
         Workspace& w = c->ws;
-        w.sor_xyz = (float4*)(base + o_xyz);
-        w.sor_pts = (o3dr_point*)(base + o_pts);
-        w.sor_dist = (float*)(base + o_dist);
-        w.sor_cell_first = (uint32_t*)(base + o_cf);
-        w.sor_cell_z = (float2*)(base + o_cz);
-        w.sor_partial = (double*)(base + o_part);
-        w.sor_geom = (SorGeom*)(base + o_geom);
-        w.sor_n = (uint32_t*)(base + o_n);
-        w.sor_left = (uint32_t*)(base + o_left);
-        w.sor_left_cnt = (uint32_t*)(base + o_lc);
+        CHK(carve(c, c->ws_sor_block, [&](Carve& k) {
+            k.take(w.sor_xyz, F * (size_t)C);
+            k.take(w.sor_pts, F * (size_t)C);
+            k.take(w.sor_dist, F * (size_t)C);
+            k.take(w.sor_cell_first, F * ((size_t)max_cells + 1));
+            k.take(w.sor_cell_z, F * ((size_t)max_cells + 1));
+            k.take(w.sor_partial, F * 256 * 2);
+            k.take(w.sor_geom, F);
+            k.take(w.sor_n, F);
+            k.take(w.sor_left, F * (size_t)C);
+            k.take(w.sor_left_cnt, F);
+        }));
         w.sor_max_cells = max_cells;
         w.sor_cap = C;
         c->ws_sor_cap = C;
@@ -439,24 +425,11 @@ extern "C" int o3dr_ctx_destroy(o3dr_ctx* c)
     if (!c) return O3DR_OK;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    dev_release(c->ws_block);
-    dev_release(c->ws_pts_block);
-    dev_release(c->ws_sor_block);
-    dev_release(c->st_disp);
-    dev_release(c->st_bgr);
-    dev_release(c->st_in);
-    dev_release(c->st_out);
-    dev_release(c->st_kp);
-    dev_release(c->st_kpoff);
-    dev_release(c->st_poses);
-    dev_release(c->st_xchg);
-    dev_release(c->st_merge);
-    dev_release(c->st_gather);
+    for (DevBuf* b : {&c->ws_block, &c->ws_pts_block, &c->ws_sor_block, &c->st_disp, &c->st_bgr, &c->st_in, &c->st_out, &c->st_kp,
+                      &c->st_kpoff, &c->st_poses, &c->st_xchg, &c->st_merge, &c->st_gather, &c->bil_tab, &c->st_blur, &c->st_blur_in,
+                      &c->st_hist})
+        dev_release(*b);
     if (c->xchg_host) (void)hipHostFree(c->xchg_host);
-    dev_release(c->bil_tab);
-    dev_release(c->st_blur);
-    dev_release(c->st_blur_in);
-    dev_release(c->st_hist);
     if (c->cloud_big) (void)hipFree(c->cloud_big);
     if (c->cloud_alt) (void)hipFree(c->cloud_alt);
     if (c->cloud_box) (void)hipFree(c->cloud_box);
@@ -476,21 +449,18 @@ extern "C" int o3dr_ctx_destroy(o3dr_ctx* c)
         dev_release(c->st2_disp[i]);
         dev_release(c->st2_bgr[i]);
         dev_release(c->st2_poses[i]);
+        dev_release(c->inc.grp[i]);
+        dev_release(c->inc.off[i]);
+        dev_release(c->inc.cells[i]);
         if (c->ev_copied[i]) (void)hipEventDestroy(c->ev_copied[i]);
         if (c->ev_done[i]) (void)hipEventDestroy(c->ev_done[i]);
     }
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    for (int i = 0; i < 2; ++i) {
-        dev_release(c->inc.grp[i]);
-        dev_release(c->inc.off[i]);
-        dev_release(c->inc.cells[i]);
-    }
     for (DevBuf* b : {&c->inc.box, &c->inc.scratch, &c->inc.tg, &c->inc.tmatch, &c->inc.flag, &c->inc.src, &c->inc.keep,
-                      &c->inc.partial, &c->inc.words, &c->inc.fb, &c->nn_q, &c->nn_t, &c->nn_cells, &c->nn_src, &c->mls_out, &c->mls_misc,
-                      &c->pl_pts, &c->pl_tiles, &c->pl_hyp, &c->pl_misc, &c->pl_out, &c->mt_desc, &c->mt_tab, &c->mt_part,
-                      &c->mt_out, &c->rg_in, &c->rg_work, &c->ms_work, &c->ms_misc, &c->ms_out})
+                      &c->inc.partial, &c->inc.words, &c->inc.fb, &c->nn_q, &c->nn_t, &c->nn_cells, &c->nn_src, &c->pl_hyp})
         dev_release(*b);
+    for (DevBuf& b : c->op) dev_release(b);
     delete c;
     return O3DR_OK;
 }
@@ -500,6 +470,14 @@ extern "C" int o3dr_ctx_destroy(o3dr_ctx* c)
         if (!(c)) return fail(O3DR_ERR_INVALID_ARG, "ctx is NULL");         \
         HIPCHK(hipSetDevice((c)->device));                                  \
     } while (0)
+
+// CTX_ENTER, then the implementation: for the entry points that clean their outputs up after a failure of either
+template <class Impl>
+static int entered(o3dr_ctx* c, Impl&& impl)
+{
+    CTX_ENTER(c);
+    return impl();
+}
 
 extern "C" int o3dr_ctx_set_stream(o3dr_ctx* c, void* hip_stream)
 {
@@ -678,6 +656,67 @@ static int stage_in(o3dr_ctx* c, DevBuf& b, const void* src, size_t bytes, int m
 }
 
 // read a CloudCounters back (synchronises)
+// The outputs of one call, named once: add() for each (the caller's pointer, nullptr if not asked for, and the elements
+// it holds).  stage() then gives each its device pointer - the caller's own for O3DR_MEM_DEVICE, a slice of the one
+// staging block for O3DR_MEM_HOST -, copy_back() enqueues the device-to-host copies behind the launches, and zero() clears
+// the host outputs where the operator's contract says so.
+struct Outputs {
+    struct Item {
+        void* user;
+        size_t elem, cap, count;  // bytes per element, elements the caller's array holds, elements this call writes
+        void* dev;
+    };
+    int mem, n = 0;
+    Item item[4];
+    template <class T>
+    void add(T* user, int64_t capacity)
+    {
+        const size_t cap = user && capacity > 0 ? (size_t)capacity : 0;
+        item[n++] = Item{(void*)user, sizeof(T), cap, cap, (void*)user};
+    }
+    Item* find(const void* user)
+    {
+        for (int i = 0; i < n; ++i)
+            if (user && item[i].user == user) return &item[i];
+        return nullptr;
+    }
+    // the call writes only the first `count` elements of this output
+    void set_count(const void* user, int64_t count)
+    {
+        if (Item* it = find(user)) it->count = (size_t)count;
+    }
+    int stage(o3dr_ctx* c)
+    {
+        if (mem != O3DR_MEM_HOST) return O3DR_OK;
+        return carve(c, c->op[o3dr_ctx::OP_OUT], [&](Carve& w) {
+            for (Item* it = item; it < item + n; ++it) {
+                char* d;
+                w.take(d, it->count * it->elem);
+                it->dev = it->count ? d : nullptr;
+            }
+        });
+    }
+    // where the kernels write this output (nullptr: not asked for)
+    template <class T>
+    T* dev(T* user)
+    {
+        Item* it = find(user);
+        return it ? (T*)it->dev : nullptr;
+    }
+    int copy_back(o3dr_ctx* c) const
+    {
+        for (const Item* it = item; mem == O3DR_MEM_HOST && it < item + n; ++it)
+            if (it->count) HIPCHK(hipMemcpyAsync(it->user, it->dev, it->count * it->elem, hipMemcpyDeviceToHost, c->stream));
+        return O3DR_OK;
+    }
+    // all of every host output, but for `keep` (an output that is also the call's input)
+    void zero(const void* keep = nullptr) const
+    {
+        for (const Item* it = item; mem == O3DR_MEM_HOST && it < item + n; ++it)
+            if (it->cap && it->user != keep) memset(it->user, 0, it->cap * it->elem);
+    }
+};
+
 static int read_counters(o3dr_ctx* c, const CloudCounters* dev, CloudCounters* host, const CloudCounters* dev2 = nullptr,
                          CloudCounters* host2 = nullptr)
 {
@@ -2878,12 +2917,12 @@ static int nn_target(o3dr_ctx* c, const o3dr_point* target, int64_t n, int mem, 
     CHK(stage_in(c, c->nn_t, target, (size_t)n * sizeof(o3dr_point), mem, &t_d));
     CHK(ws_ensure(c, 1, n, false));
     CHK(sor_ensure(c, 1, n));
-    const size_t cell_bytes = align256(((size_t)c->ws.sor_max_cells + 1) * sizeof(float4));
-    CHK(dev_ensure(c, c->nn_cells, 2 * cell_bytes + 256));
-    char* base = (char*)c->nn_cells.p;
-    *cell_lo = (float4*)base;
-    *cell_hi = (float4*)(base + cell_bytes);
-    *box6 = (float*)(base + 2 * cell_bytes);
+    const size_t cells = (size_t)c->ws.sor_max_cells + 1;
+    CHK(carve(c, c->nn_cells, [&](Carve& w) {
+        w.take(*cell_lo, cells);
+        w.take(*cell_hi, cells);
+        w.take(*box6, 6);
+    }));
     launch_set_counts(&c->prof, c->stream, c->ws.n_valid, (uint32_t)n, 1);
     const int used = launch_points_minmax(&c->prof, c->stream, (const o3dr_point*)t_d, 0, c->ws.n_valid, 1, n, c->ws.mm_stride, c->ws.mm);
     launch_nn_grid(&c->prof, c->stream, c->ws, (const o3dr_point*)t_d, n, used, *box6, *cell_lo, *cell_hi);
@@ -2900,31 +2939,75 @@ struct NnSrc {
 };
 static int nn_source(o3dr_ctx* c, int64_t n, NnSrc* o)
 {
-    const size_t b_idx = align256((size_t)n * 4), b_part = align256((size_t)kIcpRecord * (size_t)nn_partial_blocks(n) * 8);
-    CHK(dev_ensure(c, c->nn_src, 3 * b_idx + b_part + align256(kIcpRecord * 8)));
-    char* base = (char*)c->nn_src.p;
-    o->idx[0] = (uint32_t*)base;
-    o->idx[1] = (uint32_t*)(base + b_idx);
-    o->d2 = (float*)(base + 2 * b_idx);
-    o->partial = (double*)(base + 3 * b_idx);
-    o->rec = (double*)(base + 3 * b_idx + b_part);
-    return O3DR_OK;
+    return carve(c, c->nn_src, [&](Carve& w) {
+        w.take(o->idx[0], (size_t)n);
+        w.take(o->idx[1], (size_t)n);
+        w.take(o->d2, (size_t)n);
+        w.take(o->partial, (size_t)kIcpRecord * (size_t)nn_partial_blocks(n));
+        w.take(o->rec, (size_t)kIcpRecord);
+    });
 }
 
-static int nn_check_cloud(int64_t n, const void* p)
+constexpr int64_t kCloudMax = 0xffffffffLL, kMeshCloudMax = 0x7fffffffLL;  // points in one cloud (the mesh's indices are int32)
+static int nn_check_cloud(int64_t n, const void* p, int64_t max_points = kCloudMax)
 {
     if (n < 0 || (n > 0 && !p)) return fail(O3DR_ERR_INVALID_ARG, "bad arguments (cloud pointer / size)");
-    if (n > (int64_t)0xffffffffLL) return fail(O3DR_ERR_INVALID_ARG, "more than 2^32-1 points in one cloud");
+    if (n > max_points)
+        return fail(O3DR_ERR_INVALID_ARG, max_points == kCloudMax ? "more than 2^32-1 points in one cloud" : "2^31 or more points in one cloud");
     return O3DR_OK;
+}
+// n if it can be a cloud's size, else 0: what an entry point sizes its host outputs by before anything is validated
+static inline int64_t cloud_points(int64_t n, int64_t max_points = kCloudMax) { return n > 0 && n <= max_points ? n : 0; }
+
+// What MLS, plane segmentation and meshing do with a checked cloud of n > 0 points: stage it (c->nn_t), and have every
+// coordinate checked for being finite before a grid sees the cloud.  `flag` is the operator's device flag word, of which
+// the first flag_bytes are read into flag_h; `also` enqueues what else the operator wants done before that one
+// synchronisation.
+template <class Also>
+static int cloud_stage_finite(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, int mem, uint32_t* flag, uint32_t* flag_h, size_t flag_bytes,
+                              const o3dr_point** cloud_d, Also&& also)
+{
+    const void* d;
+    CHK(stage_in(c, c->nn_t, cloud, (size_t)n * sizeof(o3dr_point), mem, &d));
+    *cloud_d = (const o3dr_point*)d;
+    launch_mls_finite(&c->prof, c->stream, *cloud_d, n, flag);
+    CHK(also());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(flag_h, flag, flag_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (flag_h[0]) return fail(O3DR_ERR_INVALID_ARG, "the cloud has a non-finite coordinate");
+    return O3DR_OK;
+}
+static int nothing_else() { return O3DR_OK; }
+// the operators' device flags, ranges and counters (c->op[OP_FLAGS]), 64 bytes apart: each group is read back on its own
+struct MlsFlags {
+    alignas(64) unsigned long long counters[4];  // none, plane, poly, max neighbours
+    alignas(64) uint32_t bad;                    // non-finite
+};
+struct PlaneFlags {
+    alignas(64) uint32_t flag[2];  // [0] non-finite, [1] tile index out of int32
+    alignas(64) int32_t range[4];  // ix_min ix_max iy_min iy_max (order-preserving)
+    alignas(64) uint32_t n_tiles;
+};
+struct MeshFlags {
+    alignas(64) uint32_t bad;          // non-finite
+    alignas(64) uint32_t range[5];     // cx_min cx_max cy_min cy_max (order-preserving), [4] out of int32
+    alignas(64) uint32_t cnt[2];       // V, T
+    alignas(64) uint32_t counters[3];  // full quads, rejected by orientation, rejected by length
+};
+template <class Flags>
+static int op_flags(o3dr_ctx* c, Flags** f)
+{
+    return carve(c, c->op[o3dr_ctx::OP_FLAGS], [&](Carve& w) { w.take(*f, 1); });
 }
 
 extern "C" int o3dr_nearest_neighbors(o3dr_ctx* c, const o3dr_point* query, int64_t n_query, const o3dr_point* target,
                                       int64_t n_target, double max_distance, uint32_t* idx_out, float* d2_out, int32_t mem)
 {
-    if (mem == O3DR_MEM_HOST && n_query > 0 && n_query <= (int64_t)0xffffffffLL) {  // outputs zeroed first
-        if (idx_out) memset(idx_out, 0, (size_t)n_query * sizeof(uint32_t));
-        if (d2_out) memset(d2_out, 0, (size_t)n_query * sizeof(float));
-    }
+    Outputs outs{mem};
+    outs.add(idx_out, cloud_points(n_query));
+    outs.add(d2_out, cloud_points(n_query));
+    outs.zero();  // outputs zeroed first
     CTX_ENTER(c);
     CHK(nn_check_cloud(n_query, query));
     CHK(nn_check_cloud(n_target, target));
@@ -2934,10 +3017,9 @@ extern "C" int o3dr_nearest_neighbors(o3dr_ctx* c, const o3dr_point* query, int6
     c->place_ub = -1;
     if (n_query == 0) return O3DR_OK;
     const float r2 = (float)(max_distance * max_distance);
-    NnSrc o;
-    CHK(nn_source(c, n_query, &o));
-    uint32_t* idx_d = mem == O3DR_MEM_DEVICE ? idx_out : o.idx[0];
-    float* d2_d = mem == O3DR_MEM_DEVICE ? d2_out : o.d2;
+    CHK(outs.stage(c));
+    uint32_t* idx_d = outs.dev(idx_out);
+    float* d2_d = outs.dev(d2_out);
     if (n_target == 0) {  // no target point: none found
         HIPCHK(hipMemsetD32Async((hipDeviceptr_t)idx_d, (int)0xFFFFFFFFu, (size_t)n_query, c->stream));
         HIPCHK(hipMemsetD32Async((hipDeviceptr_t)d2_d, (int)0x7f800000u, (size_t)n_query, c->stream));
@@ -2951,10 +3033,7 @@ extern "C" int o3dr_nearest_neighbors(o3dr_ctx* c, const o3dr_point* query, int6
                         nullptr, nullptr, nullptr);
         HIPCHK(hipGetLastError());
     }
-    if (mem == O3DR_MEM_HOST) {
-        HIPCHK(hipMemcpyAsync(idx_out, idx_d, (size_t)n_query * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(d2_out, d2_d, (size_t)n_query * 4, hipMemcpyDeviceToHost, c->stream));
-    }
+    CHK(outs.copy_back(c));
     HIPCHK(hipStreamSynchronize(c->stream));
     return O3DR_OK;
 }
@@ -3152,12 +3231,12 @@ extern "C" int o3dr_mls_smooth(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, 
                                float* normals, uint32_t* nn_count, uint8_t* fit, o3dr_mls_result* res, int32_t mem)
 {
     if (res) memset(res, 0, sizeof *res);
-    if (mem == O3DR_MEM_HOST && n > 0 && n <= (int64_t)0xffffffffLL) {  // outputs zeroed first (out may be the input)
-        if (out && out != cloud) memset(out, 0, (size_t)n * sizeof(o3dr_point));
-        if (normals) memset(normals, 0, (size_t)n * 4 * sizeof(float));
-        if (nn_count) memset(nn_count, 0, (size_t)n * sizeof(uint32_t));
-        if (fit) memset(fit, 0, (size_t)n);
-    }
+    Outputs outs{mem};
+    outs.add(out, cloud_points(n));
+    outs.add(normals, 4 * cloud_points(n));
+    outs.add(nn_count, cloud_points(n));
+    outs.add(fit, cloud_points(n));
+    outs.zero(cloud);  // outputs zeroed first (out may be the input)
     CTX_ENTER(c);
     CHK(nn_check_cloud(n, cloud));
     if (!p) return fail(O3DR_ERR_INVALID_ARG, "params is NULL");
@@ -3172,48 +3251,23 @@ extern "C" int o3dr_mls_smooth(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, 
     if (!(h > 0.0 && std::isfinite(h))) return fail(O3DR_ERR_INVALID_ARG, "search_radius^2 is not a usable sqr_gauss_param");
     c->place_ub = -1;
     if (n == 0) return O3DR_OK;
-    CHK(dev_ensure(c, c->mls_misc, 256));
-    unsigned long long* counters = (unsigned long long*)c->mls_misc.p;
-    uint32_t* flag = (uint32_t*)((char*)c->mls_misc.p + 64);
-    // every coordinate finite, checked before the grid sees the cloud
-    const void* cloud_d;
-    CHK(stage_in(c, c->nn_t, cloud, (size_t)n * sizeof(o3dr_point), mem, &cloud_d));
-    launch_mls_finite(&c->prof, c->stream, (const o3dr_point*)cloud_d, n, flag);
-    HIPCHK(hipGetLastError());
+    MlsFlags* f;
+    CHK(op_flags(c, &f));
+    const o3dr_point* cloud_d;
     uint32_t bad = 0;
-    HIPCHK(hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (bad) {
-        if (mem == O3DR_MEM_HOST && out == cloud) memset(out, 0, (size_t)n * sizeof(o3dr_point));
-        return fail(O3DR_ERR_INVALID_ARG, "the cloud has a non-finite coordinate");
-    }
+    const int staged = cloud_stage_finite(c, cloud, n, mem, &f->bad, &bad, 4, &cloud_d, nothing_else);
+    if (bad && mem == O3DR_MEM_HOST && out == cloud) memset(out, 0, (size_t)n * sizeof(o3dr_point));
+    CHK(staged);
     float* box6;
     float4 *lo, *hi;
-    CHK(nn_target(c, (const o3dr_point*)cloud_d, n, O3DR_MEM_DEVICE, &box6, &lo, &hi));
-    o3dr_point* out_d = out;
-    float* nrm_d = normals;
-    uint32_t* cnt_d = nn_count;
-    uint8_t* fit_d = fit;
-    if (mem == O3DR_MEM_HOST) {  // staged: points, normals, counts, fit kinds
-        const size_t b_pts = align256((size_t)n * sizeof(o3dr_point)), b_nrm = align256((size_t)n * 16), b_cnt = align256((size_t)n * 4);
-        CHK(dev_ensure(c, c->mls_out, b_pts + b_nrm + b_cnt + align256((size_t)n)));
-        char* base = (char*)c->mls_out.p;
-        out_d = (o3dr_point*)base;
-        nrm_d = normals ? (float*)(base + b_pts) : nullptr;
-        cnt_d = nn_count ? (uint32_t*)(base + b_pts + b_nrm) : nullptr;
-        fit_d = fit ? (uint8_t*)(base + b_pts + b_nrm + b_cnt) : nullptr;
-    }
-    launch_mls(&c->prof, c->stream, c->ws, (const o3dr_point*)cloud_d, n, box6, lo, hi, r, p->polynomial_order, h, out_d, nrm_d, cnt_d,
-               fit_d, counters);
+    CHK(nn_target(c, cloud_d, n, O3DR_MEM_DEVICE, &box6, &lo, &hi));
+    CHK(outs.stage(c));
+    launch_mls(&c->prof, c->stream, c->ws, cloud_d, n, box6, lo, hi, r, p->polynomial_order, h, outs.dev(out), outs.dev(normals),
+               outs.dev(nn_count), outs.dev(fit), f->counters);
     HIPCHK(hipGetLastError());
     unsigned long long cnt_h[4];
-    HIPCHK(hipMemcpyAsync(cnt_h, counters, sizeof cnt_h, hipMemcpyDeviceToHost, c->stream));
-    if (mem == O3DR_MEM_HOST) {
-        HIPCHK(hipMemcpyAsync(out, out_d, (size_t)n * sizeof(o3dr_point), hipMemcpyDeviceToHost, c->stream));
-        if (normals) HIPCHK(hipMemcpyAsync(normals, nrm_d, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
-        if (nn_count) HIPCHK(hipMemcpyAsync(nn_count, cnt_d, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-        if (fit) HIPCHK(hipMemcpyAsync(fit, fit_d, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    }
+    HIPCHK(hipMemcpyAsync(cnt_h, f->counters, sizeof cnt_h, hipMemcpyDeviceToHost, c->stream));
+    CHK(outs.copy_back(c));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (res) {
         res->n_none = (int64_t)cnt_h[0];
@@ -3237,9 +3291,16 @@ extern "C" void o3dr_plane_default_params(o3dr_plane_params* p)
     p->optimize = 1;              // setOptimizeCoefficients(true)
 }
 
+// pl_hyp: nh hypothesis planes, then their scores
+static void plane_hyp_layout(Carve& w, uint64_t nh, float4** hyp, uint32_t** counts)
+{
+    w.take(*hyp, nh);
+    w.take(*counts, nh);
+}
+
 static int segment_plane(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const o3dr_plane_params* p, uint8_t* inlier,
-                         int32_t* tile, o3dr_point* projected, o3dr_plane_tile* tiles, int64_t tiles_capacity, int64_t* n_tiles,
-                         int32_t mem)
+                         int32_t* tile, o3dr_point* projected, Outputs& outs, o3dr_plane_tile* tiles, int64_t tiles_capacity,
+                         int64_t* n_tiles, int32_t mem)
 {
     CHK(nn_check_cloud(n, cloud));
     if (!p) return fail(O3DR_ERR_INVALID_ARG, "params is NULL");
@@ -3255,25 +3316,21 @@ static int segment_plane(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const 
     c->place_ub = -1;
     if (n == 0) return O3DR_OK;
     const bool tiled = ts > 0.0;
-    CHK(dev_ensure(c, c->pl_misc, 256));
-    uint32_t* flag = (uint32_t*)c->pl_misc.p;                     // [0] non-finite, [1] tile index out of int32
-    int32_t* range = (int32_t*)((char*)c->pl_misc.p + 64);        // ix_min ix_max iy_min iy_max (order-preserving)
-    uint32_t* n_tiles_dev = (uint32_t*)((char*)c->pl_misc.p + 128);
-    const void* cloud_d;
-    CHK(stage_in(c, c->nn_t, cloud, (size_t)n * sizeof(o3dr_point), mem, &cloud_d));
-    launch_mls_finite(&c->prof, c->stream, (const o3dr_point*)cloud_d, n, flag);
-    if (tiled) launch_plane_range(&c->prof, c->stream, (const o3dr_point*)cloud_d, n, ts, range, flag);
-    HIPCHK(hipGetLastError());
-    uint32_t hbuf[6];
-    HIPCHK(hipMemcpyAsync(hbuf, flag, 8, hipMemcpyDeviceToHost, c->stream));
-    if (tiled) HIPCHK(hipMemcpyAsync(hbuf + 2, range, 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (hbuf[0]) return fail(O3DR_ERR_INVALID_ARG, "the cloud has a non-finite coordinate");
+    PlaneFlags* f;
+    CHK(op_flags(c, &f));
+    const o3dr_point* cloud_d;
+    uint32_t hbuf[6];  // the two flags, then the range
+    CHK(cloud_stage_finite(c, cloud, n, mem, f->flag, hbuf, 8, &cloud_d, [&]() -> int {
+        if (!tiled) return O3DR_OK;
+        launch_plane_range(&c->prof, c->stream, cloud_d, n, ts, f->range, f->flag);
+        HIPCHK(hipMemcpyAsync(hbuf + 2, f->range, 16, hipMemcpyDeviceToHost, c->stream));
+        return O3DR_OK;
+    }));
     if (tiled && hbuf[1]) return fail(O3DR_ERR_INVALID_ARG, "a tile index does not fit in int32 (tile_size too small)");
 
     PlaneArgs a;
     memset(&a, 0, sizeof a);
-    a.cloud = (const o3dr_point*)cloud_d;
+    a.cloud = cloud_d;
     a.pts = (const float4*)cloud_d;
     a.tiled = tiled ? 1 : 0;
     a.n = (uint32_t)n;
@@ -3281,7 +3338,7 @@ static int segment_plane(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const 
     a.s = ts;
     a.tf = (float)t;
     a.seed = p->seed;
-    a.range = range;
+    a.range = f->range;
     uint64_t T = 1;
     if (tiled) {
         const uint64_t wx = (uint64_t)(hbuf[3] - hbuf[2]) + 1, wy = (uint64_t)(hbuf[5] - hbuf[4]) + 1;
@@ -3291,14 +3348,16 @@ static int segment_plane(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const 
         int nbits = 0;
         while (nbits < 32 && (max_key >> nbits) != 0) ++nbits;
         CHK(ws_ensure(c, 1, n, false));
-        const size_t b_pts = align256((size_t)n * sizeof(float4));
-        CHK(dev_ensure(c, c->pl_pts, b_pts + align256((size_t)n * 4)));
-        float4* pts = (float4*)c->pl_pts.p;
-        uint32_t* head = (uint32_t*)((char*)c->pl_pts.p + b_pts);
-        launch_plane_order(&c->prof, c->stream, c->ws, a, nbits, head, pts, n_tiles_dev);
+        float4* pts;
+        uint32_t* head;
+        CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
+            w.take(pts, (size_t)n);
+            w.take(head, (size_t)n);
+        }));
+        launch_plane_order(&c->prof, c->stream, c->ws, a, nbits, head, pts, &f->n_tiles);
         HIPCHK(hipGetLastError());
         uint32_t th = 0;
-        HIPCHK(hipMemcpyAsync(&th, n_tiles_dev, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(&th, &f->n_tiles, 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         T = th;
     }
@@ -3308,39 +3367,24 @@ static int segment_plane(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const 
     a.n_tiles = (uint32_t)T;
     const int64_t max_chunks = n / kPlaneChunkPoints + (int64_t)T;
     if (!tiled) CHK(ws_ensure(c, 1, 1, false));  // (the scan's chunk partials)
-    const size_t b_ts = align256((T + 1) * 4), b_rec = align256(T * sizeof(o3dr_plane_tile));
-    CHK(dev_ensure(c, c->pl_tiles, 2 * b_ts + b_rec + align256((size_t)max_chunks * kPlaneMomentsHost * 8)));
-    char* tb = (char*)c->pl_tiles.p;
-    a.tstart = (uint32_t*)tb;
-    a.cfirst = (uint32_t*)(tb + b_ts);
-    a.rec = (o3dr_plane_tile*)(tb + 2 * b_ts);
-    a.partial = (double*)(tb + 2 * b_ts + b_rec);
-    const size_t b_hyp = align256(T * a.H * sizeof(float4));
-    CHK(dev_ensure(c, c->pl_hyp, b_hyp + align256(T * a.H * 4)));
-    a.hyp = (float4*)c->pl_hyp.p;
-    a.counts = (uint32_t*)((char*)c->pl_hyp.p + b_hyp);
-    a.inlier = inlier;
-    a.tile = tile;
-    a.projected = projected;
-    if (mem == O3DR_MEM_HOST) {  // staged: labels, tile ordinals, projected points
-        const size_t b_in = align256((size_t)n), b_tl = align256((size_t)n * 4);
-        CHK(dev_ensure(c, c->pl_out, b_in + b_tl + (size_t)n * sizeof(o3dr_point)));
-        char* base = (char*)c->pl_out.p;
-        a.inlier = inlier ? (uint8_t*)base : nullptr;
-        a.tile = tile ? (int32_t*)(base + b_in) : nullptr;
-        a.projected = projected ? (o3dr_point*)(base + b_in + b_tl) : nullptr;
-    }
+    CHK(carve(c, c->op[o3dr_ctx::OP_LATE], [&](Carve& w) {
+        w.take(a.tstart, T + 1);
+        w.take(a.cfirst, T + 1);
+        w.take(a.rec, T);
+        w.take(a.partial, (size_t)max_chunks * kPlaneMomentsHost);
+    }));
+    CHK(carve(c, c->pl_hyp, [&](Carve& w) { plane_hyp_layout(w, T * a.H, &a.hyp, &a.counts); }));
+    CHK(outs.stage(c));  // labels, tile ordinals, projected points
+    a.inlier = outs.dev(inlier);
+    a.tile = outs.dev(tile);
+    a.projected = outs.dev(projected);
     c->pl_last_hyp = 0;
     launch_plane_tiles(&c->prof, c->stream, c->ws, a);
     launch_plane_fit(&c->prof, c->stream, a, max_chunks, p->optimize);
     HIPCHK(hipGetLastError());
     const hipMemcpyKind back = mem == O3DR_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     if (tiles) HIPCHK(hipMemcpyAsync(tiles, a.rec, T * sizeof(o3dr_plane_tile), back, c->stream));
-    if (mem == O3DR_MEM_HOST) {
-        if (inlier) HIPCHK(hipMemcpyAsync(inlier, a.inlier, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-        if (tile) HIPCHK(hipMemcpyAsync(tile, a.tile, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-        if (projected) HIPCHK(hipMemcpyAsync(projected, a.projected, (size_t)n * sizeof(o3dr_point), hipMemcpyDeviceToHost, c->stream));
-    }
+    CHK(outs.copy_back(c));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->pl_last_hyp = T * a.H;
     return O3DR_OK;
@@ -3355,9 +3399,12 @@ extern "C" int o3dr_test_plane_hypotheses(o3dr_ctx* c, float* planes, uint32_t* 
     *n_out = (int64_t)nh;
     if ((uint64_t)capacity < nh) return fail(O3DR_ERR_CAPACITY, "capacity is below the hypothesis count");
     if (nh == 0) return O3DR_OK;
-    const size_t b_hyp = align256(nh * sizeof(float4));
-    HIPCHK(hipMemcpyAsync(planes, c->pl_hyp.p, nh * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(counts, (char*)c->pl_hyp.p + b_hyp, nh * 4, hipMemcpyDeviceToHost, c->stream));
+    Carve w{(char*)c->pl_hyp.p, 0};
+    float4* hyp_d;
+    uint32_t* counts_d;
+    plane_hyp_layout(w, nh, &hyp_d, &counts_d);
+    HIPCHK(hipMemcpyAsync(planes, hyp_d, nh * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(counts, counts_d, nh * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return O3DR_OK;
 }
@@ -3367,18 +3414,14 @@ extern "C" int o3dr_segment_plane(o3dr_ctx* c, const o3dr_point* cloud, int64_t 
                                   int64_t* n_tiles, int32_t mem)
 {
     if (n_tiles) *n_tiles = 0;
-    auto entered = [&]() -> int {
-        CTX_ENTER(c);
-        return segment_plane(c, cloud, n, p, inlier, tile, projected, tiles, tiles_capacity, n_tiles, mem);
-    };
-    const int rc = entered();
-    if (rc != O3DR_OK && rc != O3DR_ERR_CAPACITY) {  // host outputs zeroed on error
+    Outputs outs{mem};
+    outs.add(inlier, cloud_points(n));
+    outs.add(tile, cloud_points(n));
+    outs.add(projected, cloud_points(n));
+    const int rc = entered(c, [&] { return segment_plane(c, cloud, n, p, inlier, tile, projected, outs, tiles, tiles_capacity, n_tiles, mem); });
+    if (rc != O3DR_OK && rc != O3DR_ERR_CAPACITY) {  // host outputs zeroed on error (projected may be the input)
         if (n_tiles) *n_tiles = 0;
-        if (mem == O3DR_MEM_HOST && n > 0 && n <= (int64_t)0xffffffffLL) {
-            if (inlier) memset(inlier, 0, (size_t)n);
-            if (tile) memset(tile, 0, (size_t)n * sizeof(int32_t));
-            if (projected && (const void*)projected != (const void*)cloud) memset(projected, 0, (size_t)n * sizeof(o3dr_point));
-        }
+        outs.zero(cloud);
         if (mem == O3DR_MEM_HOST && tiles && tiles_capacity > 0) memset(tiles, 0, (size_t)tiles_capacity * sizeof(o3dr_plane_tile));
     }
     return rc;
@@ -3395,10 +3438,9 @@ extern "C" void o3dr_mesh_default_params(o3dr_mesh_params* p)
 }
 
 static int mesh_surface(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const o3dr_mesh_params* p, int32_t* tris,
-                        int64_t tris_capacity, int64_t* n_tris, float* normals, o3dr_mesh_result* res, int32_t mem)
+                        int64_t tris_capacity, int64_t* n_tris, float* normals, Outputs& outs, o3dr_mesh_result* res, int32_t mem)
 {
-    if (n < 0 || (n > 0 && !cloud)) return fail(O3DR_ERR_INVALID_ARG, "bad arguments (cloud pointer / size)");
-    if (n >= (int64_t)1 << 31) return fail(O3DR_ERR_INVALID_ARG, "2^31 or more points in one cloud");
+    CHK(nn_check_cloud(n, cloud, kMeshCloudMax));
     if (!p) return fail(O3DR_ERR_INVALID_ARG, "params is NULL");
     if (!n_tris) return fail(O3DR_ERR_INVALID_ARG, "n_tris is NULL");
     if (tris_capacity < 0 || (tris_capacity > 0 && !tris)) return fail(O3DR_ERR_INVALID_ARG, "bad tris / tris_capacity");
@@ -3410,33 +3452,27 @@ static int mesh_surface(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const o
     if (!(L > 0.0)) return fail(O3DR_ERR_INVALID_ARG, "max_edge_length must be > 0 (+inf: no gate)");
     c->place_ub = -1;
     if (n == 0) return O3DR_OK;
-    CHK(dev_ensure(c, c->ms_misc, 256));
-    uint32_t* flag = (uint32_t*)c->ms_misc.p;                   // [0] non-finite
-    uint32_t* range = (uint32_t*)((char*)c->ms_misc.p + 64);    // cx_min cx_max cy_min cy_max (order-preserving), [4] out of int32
-    uint32_t* cnt_dev = (uint32_t*)((char*)c->ms_misc.p + 128);  // V, T
-    uint32_t* counters = (uint32_t*)((char*)c->ms_misc.p + 192);
-    const size_t b_u32 = align256((size_t)n * 4), b_f4 = align256((size_t)n * 16);
-    const size_t b_part = align256((size_t)((n + 255) / 256) * kMeshPartWords * 4);  // one record per 256-thread workgroup
-    CHK(dev_ensure(c, c->ms_work, 3 * b_u32 + 2 * b_f4 + b_part));
-    char* wb = (char*)c->ms_work.p;
-    uint32_t* part = (uint32_t*)(wb + 3 * b_u32 + 2 * b_f4);
-    const void* cloud_d;
-    CHK(stage_in(c, c->nn_t, cloud, (size_t)n * sizeof(o3dr_point), mem, &cloud_d));
-    launch_mls_finite(&c->prof, c->stream, (const o3dr_point*)cloud_d, n, flag);
-    HIPCHK(hipGetLastError());
+    MeshFlags* f;
+    CHK(op_flags(c, &f));
+    MeshArgs a;
+    memset(&a, 0, sizeof a);
+    uint32_t* head;
+    CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
+        w.take(head, (size_t)n);
+        w.take(a.cnt, (size_t)n);
+        w.take(a.vkey, (size_t)n);
+        w.take(a.vpt, (size_t)n);
+        w.take(a.nbr, (size_t)n);
+        w.take(a.part, (size_t)((n + 255) / 256) * kMeshPartWords);  // one record per 256-thread workgroup
+    }));
     uint32_t hbuf[6];
-    HIPCHK(hipMemcpyAsync(hbuf, flag, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (hbuf[0]) return fail(O3DR_ERR_INVALID_ARG, "the cloud has a non-finite coordinate");
-    launch_mesh_range(&c->prof, c->stream, (const o3dr_point*)cloud_d, n, inv, part, range);
+    CHK(cloud_stage_finite(c, cloud, n, mem, &f->bad, hbuf, 4, &a.cloud, nothing_else));
+    launch_mesh_range(&c->prof, c->stream, a.cloud, n, inv, a.part, f->range);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(hbuf + 1, range, 20, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(hbuf + 1, f->range, 20, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (hbuf[5]) return fail(O3DR_ERR_INVALID_ARG, "a cell index does not fit in int32 (cell_size too small)");
 
-    MeshArgs a;
-    memset(&a, 0, sizeof a);
-    a.cloud = (const o3dr_point*)cloud_d;
     a.n = (uint32_t)n;
     a.inv = inv;
     a.lf = (float)(L * L);
@@ -3449,38 +3485,25 @@ static int mesh_surface(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const o
     int nbits = 0;
     while (nbits < 32 && (max_key >> nbits) != 0) ++nbits;
     CHK(ws_ensure(c, 1, n, false));
-    uint32_t* head = (uint32_t*)wb;
-    a.cnt = (uint32_t*)(wb + b_u32);
-    a.vkey = (uint32_t*)(wb + 2 * b_u32);
-    a.vpt = (float4*)(wb + 3 * b_u32);
-    a.nbr = (int4*)(wb + 3 * b_u32 + b_f4);
-    a.n_vert = cnt_dev;
-    a.part = part;
-    a.counters = counters;
-    launch_mesh_cells(&c->prof, c->stream, c->ws, a, nbits, head, cnt_dev);
-    launch_mesh_count(&c->prof, c->stream, c->ws, a, cnt_dev + 1);
+    a.n_vert = &f->cnt[0];
+    a.counters = f->counters;
+    launch_mesh_cells(&c->prof, c->stream, c->ws, a, nbits, head, &f->cnt[0]);
+    launch_mesh_count(&c->prof, c->stream, c->ws, a, &f->cnt[1]);
     HIPCHK(hipGetLastError());
     uint32_t cnt_h[3];
-    HIPCHK(hipMemcpyAsync(hbuf, cnt_dev, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(cnt_h, counters, sizeof cnt_h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(hbuf, f->cnt, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(cnt_h, f->counters, sizeof cnt_h, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     const int64_t V = hbuf[0], T = hbuf[1];
     *n_tris = T;
     if (tris && T > tris_capacity) return fail(O3DR_ERR_CAPACITY, "tris_capacity is below the triangle count");
-    a.tris = T > 0 ? tris : nullptr;
-    a.normals = normals;
-    if (mem == O3DR_MEM_HOST && (a.tris || normals)) {  // staged: triangles, normals
-        const size_t b_tri = align256((size_t)T * 12);
-        CHK(dev_ensure(c, c->ms_out, b_tri + (size_t)n * 12));
-        if (a.tris) a.tris = (int32_t*)c->ms_out.p;
-        if (normals) a.normals = (float*)((char*)c->ms_out.p + b_tri);
-    }
+    outs.set_count(tris, 3 * T);
+    CHK(outs.stage(c));  // triangles, normals
+    a.tris = T > 0 ? outs.dev(tris) : nullptr;
+    a.normals = outs.dev(normals);
     launch_mesh_emit(&c->prof, c->stream, a);
     HIPCHK(hipGetLastError());
-    if (mem == O3DR_MEM_HOST) {
-        if (a.tris) HIPCHK(hipMemcpyAsync(tris, a.tris, (size_t)T * 12, hipMemcpyDeviceToHost, c->stream));
-        if (normals) HIPCHK(hipMemcpyAsync(normals, a.normals, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream));
-    }
+    CHK(outs.copy_back(c));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (res) {
         res->n_vertices = V;
@@ -3498,16 +3521,13 @@ extern "C" int o3dr_mesh_surface(o3dr_ctx* c, const o3dr_point* cloud, int64_t n
 {
     if (n_tris) *n_tris = 0;
     if (res) memset(res, 0, sizeof *res);
-    auto entered = [&]() -> int {
-        CTX_ENTER(c);
-        return mesh_surface(c, cloud, n, p, tris, tris_capacity, n_tris, vertex_normals, res, mem);
-    };
-    const int rc = entered();
+    Outputs outs{mem};
+    outs.add(tris, 3 * cloud_points(tris_capacity));
+    outs.add(vertex_normals, 3 * cloud_points(n, kMeshCloudMax));
+    const int rc = entered(c, [&] { return mesh_surface(c, cloud, n, p, tris, tris_capacity, n_tris, vertex_normals, outs, res, mem); });
     if (rc != O3DR_OK && rc != O3DR_ERR_CAPACITY) {  // host outputs zeroed on error
         if (n_tris) *n_tris = 0;
-        if (mem == O3DR_MEM_HOST && vertex_normals && n > 0 && n < (int64_t)1 << 31) memset(vertex_normals, 0, (size_t)n * 12);
-        if (mem == O3DR_MEM_HOST && tris && tris_capacity > 0 && tris_capacity < (int64_t)1 << 32)
-            memset(tris, 0, (size_t)tris_capacity * 12);
+        outs.zero();
     }
     return rc;
 }
@@ -3527,7 +3547,8 @@ extern "C" void o3dr_match_default_params(o3dr_match_params* p)
 constexpr uint64_t kMatchTargetItems = 8192;
 
 static int match_knn2(o3dr_ctx* c, const uint8_t* desc, const int64_t* off, int32_t n_sets, const int32_t* pairs, int64_t n_pairs,
-                      const o3dr_match_params* p, o3dr_knn2* out, uint8_t* good, int64_t out_capacity, int64_t* n_out, int32_t mem)
+                      const o3dr_match_params* p, o3dr_knn2* out, uint8_t* good, Outputs& outs, int64_t out_capacity, int64_t* n_out,
+                      int32_t mem)
 {
     if (!n_out) return fail(O3DR_ERR_INVALID_ARG, "n_out is NULL");
     if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
@@ -3581,10 +3602,14 @@ static int match_knn2(o3dr_ctx* c, const uint8_t* desc, const int64_t* off, int3
         part += (uint64_t)P.nq * P.chunks;
     }
     const void* desc_d = nullptr;
-    if (pool > 0) CHK(stage_in(c, c->mt_desc, desc + 32 * off[0], (size_t)pool * 32, mem, &desc_d));
-    CHK(dev_ensure(c, c->mt_tab, tab.size() * sizeof(MatchPair)));
-    CHK(dev_ensure(c, c->mt_part, (size_t)(part ? part : 1) * sizeof(uint2)));
-    HIPCHK(hipMemcpyAsync(c->mt_tab.p, tab.data(), tab.size() * sizeof(MatchPair), hipMemcpyHostToDevice, c->stream));
+    if (pool > 0) CHK(stage_in(c, c->op[o3dr_ctx::OP_IN], desc + 32 * off[0], (size_t)pool * 32, mem, &desc_d));
+    MatchPair* tab_d;
+    uint2* part_d;
+    CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
+        w.take(tab_d, tab.size());
+        w.take(part_d, (size_t)(part ? part : 1));
+    }));
+    HIPCHK(hipMemcpyAsync(tab_d, tab.data(), tab.size() * sizeof(MatchPair), hipMemcpyHostToDevice, c->stream));
     MatchArgs a;
     memset(&a, 0, sizeof a);
     a.desc = (const uint4*)desc_d;
@@ -3592,22 +3617,16 @@ static int match_knn2(o3dr_ctx* c, const uint8_t* desc, const int64_t* off, int3
     a.chunk_rows = (uint32_t)chunk;
     a.n_items = items;
     a.n_rec = n_rec;
-    a.rec = (uint4*)out;
-    a.good = good;
     a.ratio = prm.ratio;
     a.max_distance = (uint32_t)prm.max_distance;
-    if (mem == O3DR_MEM_HOST) {  // staged: records, then the mask
-        const size_t b_rec = align256((size_t)n_rec * sizeof(o3dr_knn2));
-        CHK(dev_ensure(c, c->mt_out, b_rec + (size_t)n_rec));
-        a.rec = (uint4*)c->mt_out.p;
-        a.good = good ? (uint8_t*)c->mt_out.p + b_rec : nullptr;
-    }
-    launch_match(&c->prof, c->stream, a, (const MatchPair*)c->mt_tab.p, (uint2*)c->mt_part.p);
+    outs.set_count(out, (int64_t)n_rec);
+    outs.set_count(good, (int64_t)n_rec);
+    CHK(outs.stage(c));  // records, then the mask
+    a.rec = (uint4*)outs.dev(out);
+    a.good = outs.dev(good);
+    launch_match(&c->prof, c->stream, a, tab_d, part_d);
     HIPCHK(hipGetLastError());
-    if (mem == O3DR_MEM_HOST) {
-        HIPCHK(hipMemcpyAsync(out, a.rec, (size_t)n_rec * sizeof(o3dr_knn2), hipMemcpyDeviceToHost, c->stream));
-        if (good) HIPCHK(hipMemcpyAsync(good, a.good, (size_t)n_rec, hipMemcpyDeviceToHost, c->stream));
-    }
+    CHK(outs.copy_back(c));
     HIPCHK(hipStreamSynchronize(c->stream));
     return O3DR_OK;
 }
@@ -3617,24 +3636,21 @@ extern "C" int o3dr_match_knn2_hamming(o3dr_ctx* c, const uint8_t* desc, const i
                                        int64_t* n_out, int32_t mem)
 {
     if (n_out) *n_out = 0;
-    auto entered = [&]() -> int {
-        CTX_ENTER(c);
-        return match_knn2(c, desc, desc_offsets, n_sets, pairs, n_pairs, p, out, good, out_capacity, n_out, mem);
-    };
-    const int rc = entered();
+    Outputs outs{mem};
+    outs.add(out, out_capacity);
+    outs.add(good, out_capacity);
+    const int rc = entered(c, [&] { return match_knn2(c, desc, desc_offsets, n_sets, pairs, n_pairs, p, out, good, outs, out_capacity, n_out, mem); });
     if (rc != O3DR_OK && rc != O3DR_ERR_CAPACITY) {  // host outputs zeroed on error
         if (n_out) *n_out = 0;
-        if (mem == O3DR_MEM_HOST && out_capacity > 0) {
-            if (out) memset(out, 0, (size_t)out_capacity * sizeof(o3dr_knn2));
-            if (good) memset(good, 0, (size_t)out_capacity);
-        }
+        outs.zero();
     }
     return rc;
 }
 
 static int keypoints_3d(o3dr_ctx* c, const uint8_t* disp, int64_t disp_frame_stride, int64_t disp_pitch, const uint8_t* bgr,
                         int64_t bgr_frame_stride, int64_t bgr_pitch, int32_t rows, int32_t cols, const float* poses, int32_t n_frames,
-                        const float* kp_xy, const int64_t* kp_offsets, o3dr_point* out, int64_t out_capacity, int64_t* n_out, int32_t mem)
+                        const float* kp_xy, const int64_t* kp_offsets, o3dr_point* out, Outputs& outs, int64_t out_capacity, int64_t* n_out,
+                        int32_t mem)
 {
     if (!n_out) return fail(O3DR_ERR_INVALID_ARG, "n_out is NULL");
     if (!c->has_Q) return fail(O3DR_ERR_NOT_CONFIGURED, "o3dr_set_camera has not been called");
@@ -3676,14 +3692,11 @@ static int keypoints_3d(o3dr_ctx* c, const uint8_t* disp, int64_t disp_frame_str
         a.xf_mode = 2;
         a.poses = (const float*)poses_d;
     }
-    o3dr_point* out_d = out;
-    if (mem == O3DR_MEM_HOST) {
-        CHK(dev_ensure(c, c->st_out, (size_t)n_kp * sizeof(o3dr_point)));
-        out_d = (o3dr_point*)c->st_out.p;
-    }
-    launch_keypoints_3d(&c->prof, c->stream, a, (const float*)kp_d, (const int32_t*)c->st_kpoff.p, n_frames, (int)n_kp, out_d);
+    outs.set_count(out, n_kp);
+    CHK(outs.stage(c));
+    launch_keypoints_3d(&c->prof, c->stream, a, (const float*)kp_d, (const int32_t*)c->st_kpoff.p, n_frames, (int)n_kp, outs.dev(out));
     HIPCHK(hipGetLastError());
-    if (mem == O3DR_MEM_HOST) HIPCHK(hipMemcpyAsync(out, out_d, (size_t)n_kp * sizeof(o3dr_point), hipMemcpyDeviceToHost, c->stream));
+    CHK(outs.copy_back(c));
     HIPCHK(hipStreamSynchronize(c->stream));
     return O3DR_OK;
 }
@@ -3694,15 +3707,13 @@ extern "C" int o3dr_keypoints_3d(o3dr_ctx* c, const uint8_t* disp, int64_t disp_
                                  int64_t* n_out, int32_t mem)
 {
     if (n_out) *n_out = 0;
-    auto entered = [&]() -> int {
-        CTX_ENTER(c);
-        return keypoints_3d(c, disp, disp_frame_stride, disp_pitch, bgr, bgr_frame_stride, bgr_pitch, rows, cols, poses, n_frames, kp_xy,
-                            kp_offsets, out, out_capacity, n_out, mem);
-    };
-    const int rc = entered();
+    Outputs outs{mem};
+    outs.add(out, out_capacity);
+    const int rc = entered(c, [&] { return keypoints_3d(c, disp, disp_frame_stride, disp_pitch, bgr, bgr_frame_stride, bgr_pitch, rows, cols,
+                                                        poses, n_frames, kp_xy, kp_offsets, out, outs, out_capacity, n_out, mem); });
     if (rc != O3DR_OK && rc != O3DR_ERR_CAPACITY) {
         if (n_out) *n_out = 0;
-        if (mem == O3DR_MEM_HOST && out && out_capacity > 0) memset(out, 0, (size_t)out_capacity * sizeof(o3dr_point));
+        outs.zero();
     }
     return rc;
 }
@@ -3733,42 +3744,34 @@ static int rigid_transform(o3dr_ctx* c, const o3dr_point* src, const o3dr_point*
         for (int k = 0; k < 16; ++k) res[s].T[k] = k % 5 == 0 ? 1.0 : 0.0;
         res[s].status = O3DR_RIGID_TOO_FEW;
     }
-    const void *src_d = nullptr, *tgt_d = nullptr, *mask_d = nullptr;
-    const size_t b_pts = align256((size_t)n * sizeof(o3dr_point));
-    if (mem == O3DR_MEM_HOST) {
-        CHK(dev_ensure(c, c->rg_in, 2 * b_pts + (size_t)n + 1));
-        char* base = (char*)c->rg_in.p;
-        if (n > 0) {
-            HIPCHK(hipMemcpyAsync(base, src, (size_t)n * sizeof(o3dr_point), hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(base + b_pts, tgt, (size_t)n * sizeof(o3dr_point), hipMemcpyHostToDevice, c->stream));
-            if (mask) HIPCHK(hipMemcpyAsync(base + 2 * b_pts, mask, (size_t)n, hipMemcpyHostToDevice, c->stream));
-        }
-        src_d = base;
-        tgt_d = base + b_pts;
-        mask_d = mask ? base + 2 * b_pts : nullptr;
-    } else {
-        src_d = src, tgt_d = tgt, mask_d = mask;
-    }
-    const size_t S = (size_t)n_segs;
-    const size_t b_seg = align256(S * sizeof(RigidSeg)), b_first = align256(S * 4);
-    const size_t b_part = align256((size_t)kRigidFields * (size_t)(blocks ? blocks : 1) * 8);
-    const size_t b_rec = align256(S * (kRigidFields + 1) * 8), b_c0 = align256(S * 3 * 8), b_T = align256(S * 12 * 8);
-    CHK(dev_ensure(c, c->rg_work, b_seg + b_first + b_part + b_rec + b_c0 + b_T));
-    char* w = (char*)c->rg_work.p;
     RigidArgs a;
     memset(&a, 0, sizeof a);
-    a.src = (const o3dr_point*)src_d;
-    a.tgt = (const o3dr_point*)tgt_d;
-    a.mask = (const uint8_t*)mask_d;
-    a.seg = (const RigidSeg*)w;
+    a.src = src, a.tgt = tgt, a.mask = mask;
+    if (mem == O3DR_MEM_HOST) {
+        CHK(carve(c, c->op[o3dr_ctx::OP_IN], [&](Carve& w) {
+            w.take(a.src, (size_t)n);
+            w.take(a.tgt, (size_t)n);
+            w.take(a.mask, (size_t)n + 1);
+        }));
+        if (n > 0) {
+            HIPCHK(hipMemcpyAsync((void*)a.src, src, (size_t)n * sizeof(o3dr_point), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync((void*)a.tgt, tgt, (size_t)n * sizeof(o3dr_point), hipMemcpyHostToDevice, c->stream));
+            if (mask) HIPCHK(hipMemcpyAsync((void*)a.mask, mask, (size_t)n, hipMemcpyHostToDevice, c->stream));
+        }
+        if (!mask) a.mask = nullptr;
+    }
+    const size_t S = (size_t)n_segs;
     a.n_segs = (uint32_t)n_segs;
     a.n_blocks = (uint32_t)blocks;
-    a.first = (uint32_t*)(w + b_seg);
-    a.partial = (double*)(w + b_seg + b_first);
-    a.rec = (double*)(w + b_seg + b_first + b_part);
-    a.c0 = (double*)(w + b_seg + b_first + b_part + b_rec);
-    a.T = (const double*)(w + b_seg + b_first + b_part + b_rec + b_c0);
-    HIPCHK(hipMemcpyAsync(w, seg.data(), S * sizeof(RigidSeg), hipMemcpyHostToDevice, c->stream));
+    CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
+        w.take(a.seg, S);
+        w.take(a.first, S);
+        w.take(a.partial, (size_t)kRigidFields * (size_t)(blocks ? blocks : 1));
+        w.take(a.rec, S * (kRigidFields + 1));
+        w.take(a.c0, S * 3);
+        w.take(a.T, S * 12);
+    }));
+    HIPCHK(hipMemcpyAsync((void*)a.seg, seg.data(), S * sizeof(RigidSeg), hipMemcpyHostToDevice, c->stream));
     launch_rigid(&c->prof, c->stream, a, false);
     HIPCHK(hipGetLastError());
     std::vector<double> rec(S * kRigidFields), c0(S * 3);
@@ -3808,11 +3811,7 @@ extern "C" int o3dr_estimate_rigid_transform(o3dr_ctx* c, const o3dr_point* src,
                                              const int64_t* seg_offsets, int32_t n_segs, const uint8_t* mask, o3dr_rigid_result* res,
                                              int32_t mem)
 {
-    auto entered = [&]() -> int {
-        CTX_ENTER(c);
-        return rigid_transform(c, src, tgt, n, seg_offsets, n_segs, mask, res, mem);
-    };
-    const int rc = entered();
+    const int rc = entered(c, [&] { return rigid_transform(c, src, tgt, n, seg_offsets, n_segs, mask, res, mem); });
     if (rc != O3DR_OK && res && n_segs > 0) memset(res, 0, (size_t)n_segs * sizeof(o3dr_rigid_result));
     return rc;
 }
