@@ -82,9 +82,10 @@ __global__ __launch_bounds__(1024) void k_scan_rows(uint32_t* __restrict__ data,
 // Exclusive scan of the frames' TILE-MAJOR histogram rows ([tile][kMaxRadix], see hist_at in radix_sort.inc) in
 // digit-major order (all tiles of digit 0, then digit 1, ...), in place: one 1024-thread workgroup per frame stages the
 // row in LDS (row stride kMaxRadix + 1 words: conflict-free walks along a digit), so that the global loads and stores
-// are whole lines.  Dynamic LDS: n_tiles * (kMaxRadix + 1) words.
+// are whole lines.  Dynamic LDS: n_tiles * (kMaxRadix + 1) words.  all_live: every one of the n_tiles rows was written
+// (the candidate-aligned tiles k_reproject_emit counts: records may sit in any of them, however few the frame has).
 __global__ __launch_bounds__(1024) void k_scan_hist_tm(uint32_t* __restrict__ hist, const VoxelGeom* __restrict__ geom, int pass,
-                                                       int n_tiles)
+                                                       int n_tiles, int all_live)
 {
     extern __shared__ uint32_t tm_row[];
     __shared__ uint32_t lds[1024 / 64 + 1];
@@ -94,7 +95,7 @@ __global__ __launch_bounds__(1024) void k_scan_hist_tm(uint32_t* __restrict__ hi
     const int bins = geom_bins(g);
     uint32_t* row = hist + (int64_t)f * kMaxRadix * n_tiles;
     const int words = n_tiles * kMaxRadix;
-    const int live = scan_live_tiles(geom, f, n_tiles);
+    const int live = all_live ? n_tiles : scan_live_tiles(geom, f, n_tiles);
     for (int i = threadIdx.x; i < words; i += 1024)
         tm_row[(i >> kMaxRadixBits) * (kMaxRadix + 1) + (i & (kMaxRadix - 1))] = (i >> kMaxRadixBits) < live ? row[i] : 0u;
     __syncthreads();

@@ -162,16 +162,36 @@ struct ScatterLds {
     uint32_t delta[kMaxRadix];
     uint32_t scan_lds[kScatWaves + 1];
 };
-struct ScatterJob {  // per launch and frame
+struct ScatterJob {  // per launch, frame and workgroup
     const uint32_t *kin, *vin;
     uint32_t *kout, *vout;
     const uint32_t* hist;    // the frame's scanned histogram rows
     const uint32_t* hist_part;  // ... and the digit counts of the first part of every tile
-    uint32_t n, dmask;
+    int64_t begin, end;      // the records of this workgroup's part of its tile (at most kScatTile)
+    uint32_t dmask;
     int shift, bins, pass, n_tiles;
-    bool frame_vec;          // the frame's buffers start on a 16-byte boundary
     bool tm;                 // tile-major histogram rows (hist_at)
 };
+
+// Records of part `part` (of kScatParts) of sort tile `tile`.  Every pass but one cuts the frame's n records every
+// kSortTile.  The first pass of a frame whose indices k_reproject_emit wrote AND counted (tile_off != nullptr: the
+// scanned valid candidates per emit tile) cuts at candidate borders instead: sort tile t = the records of emit tiles
+// [kEmitGroup t, kEmitGroup t + kEmitGroup), so that the workgroup that wrote them owned the tile's histogram row.  Such a
+// part holds at most kScatTile records and may hold none; a stable sort does not care where its tiles are cut.
+__device__ __forceinline__ void emit_part_range(const uint32_t* __restrict__ tile_off, int n_emit_tiles, int tile, int part,
+                                                int64_t n, int64_t& begin, int64_t& end)
+{
+    if (tile_off) {
+        constexpr int kPer = kEmitGroup / kScatParts;
+        const int e0 = (tile * kScatParts + part) * kPer;
+        begin = tile_off[e0];
+        end = e0 + kPer < n_emit_tiles ? (int64_t)tile_off[e0 + kPer] : n;
+    } else {
+        begin = (int64_t)tile * kSortTile + (int64_t)part * kScatTile;
+        end = begin + kScatTile < n ? begin + kScatTile : n;
+    }
+}
+typedef uint32_t u32x4_a4_t __attribute__((ext_vector_type(4), aligned(4)));  // 16-byte load from a 4-byte boundary
 
 // the 16 consecutive records of this lane in part `part` of tile `tile` (+ this thread's scanned histogram entry): every
 // global load of the workgroup is issued here, before any LDS work
@@ -179,24 +199,24 @@ __device__ __forceinline__ void scatter_load(const ScatterJob& J, int tile, int 
                                              uint32_t (&val)[kSortRounds], uint32_t& gstart)
 {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t n = J.n;
-    const int64_t lbase = (int64_t)tile * kSortTile + (int64_t)part * kScatTile + (int64_t)w * kSortWaveItems + (int64_t)lane * kSortRounds;
+    const int64_t lbase = J.begin + (int64_t)w * kSortWaveItems + (int64_t)lane * kSortRounds;
     gstart = 0;
     if ((int)threadIdx.x < J.bins) {  // where this part's records of digit threadIdx.x go: after those of the parts before it
         gstart = J.hist[hist_at(J.tm, threadIdx.x, tile, J.n_tiles)];
         if (part != 0) gstart += J.hist_part[hist_at(J.tm, threadIdx.x, tile, J.n_tiles)];
     }
-    const bool vec = J.frame_vec && (lbase + kSortRounds <= n);
-    if (vec) {
+    // four-dword loads from wherever the part starts (a candidate-aligned part of a frame with invalid pixels starts on any
+    // record; global_load_dwordx4 needs dword alignment only)
+    if (lbase + kSortRounds <= J.end) {
 #pragma unroll
         for (int q = 0; q < kSortRounds / 4; ++q) {
-            const uint4 k4 = *reinterpret_cast<const uint4*>(J.kin + lbase + 4 * q);
+            const u32x4_a4_t k4 = *reinterpret_cast<const u32x4_a4_t*>(J.kin + lbase + 4 * q);
             key[4 * q] = k4.x; key[4 * q + 1] = k4.y; key[4 * q + 2] = k4.z; key[4 * q + 3] = k4.w;
         }
         if (J.pass != 0) {
 #pragma unroll
             for (int q = 0; q < kSortRounds / 4; ++q) {
-                const uint4 v4 = *reinterpret_cast<const uint4*>(J.vin + lbase + 4 * q);
+                const u32x4_a4_t v4 = *reinterpret_cast<const u32x4_a4_t*>(J.vin + lbase + 4 * q);
                 val[4 * q] = v4.x; val[4 * q + 1] = v4.y; val[4 * q + 2] = v4.z; val[4 * q + 3] = v4.w;
             }
         }
@@ -204,7 +224,7 @@ __device__ __forceinline__ void scatter_load(const ScatterJob& J, int tile, int 
 #pragma unroll
         for (int r = 0; r < kSortRounds; ++r) {
             const int64_t i = lbase + r;
-            const bool ok = i < n;
+            const bool ok = i < J.end;
             key[r] = ok ? J.kin[i] : 0xffffffffu;
             val[r] = (J.pass != 0 && ok) ? J.vin[i] : 0u;
         }
@@ -215,16 +235,14 @@ __device__ __forceinline__ void scatter_load(const ScatterJob& J, int tile, int 
     }
 }
 
-__device__ __forceinline__ void scatter_tile(const ScatterJob& J, int tile, int part, ScatterLds& L, const uint32_t (&key)[kSortRounds],
+__device__ __forceinline__ void scatter_tile(const ScatterJob& J, ScatterLds& L, const uint32_t (&key)[kSortRounds],
                                              const uint32_t (&val)[kSortRounds], uint32_t gstart)
 {
     uint32_t* smem = L.smem;
     uint32_t* stage = L.smem;  // overlays the counters once every record knows its position
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t n = J.n;
-    const int64_t base = (int64_t)tile * kSortTile + (int64_t)part * kScatTile;
-    const uint32_t cnt = (n - base < (int64_t)kScatTile) ? (uint32_t)(n - base) : (uint32_t)kScatTile;
-    const int64_t lbase = base + (int64_t)w * kSortWaveItems + (int64_t)lane * kSortRounds;
+    const uint32_t cnt = (uint32_t)(J.end - J.begin);
+    const int64_t lbase = J.begin + (int64_t)w * kSortWaveItems + (int64_t)lane * kSortRounds;
     const int shift = J.shift, bins = J.bins;
     const uint32_t dmask = J.dmask;
     for (int i = threadIdx.x; i < kRankWords; i += kScatThreads) smem[i] = 0;
@@ -238,7 +256,7 @@ __device__ __forceinline__ void scatter_tile(const ScatterJob& J, int tile, int 
 #pragma unroll
     for (int r = 0; r < kSortRounds; ++r) {
         own[r] = 0;
-        if (lbase + r < n) {
+        if (lbase + r < J.end) {
             const uint32_t dgt = (key[r] >> shift) & dmask;
             const uint32_t old = atomicAdd(&cw[dgt * kCntStride + quad], 1u << fsh);
             own[r] = (old >> fsh) & 127u;
@@ -290,7 +308,7 @@ __device__ __forceinline__ void scatter_tile(const ScatterJob& J, int tile, int 
     const uint32_t qsh = sub ? 7u * (uint32_t)(sub - 1) : 0u, qmk = sub ? 127u : 0u;  // where the lower lanes' records of the quad stand
 #pragma unroll
     for (int r = 0; r < kSortRounds; ++r) {
-        if (lbase + r < n) {
+        if (lbase + r < J.end) {
             const uint32_t dgt = (key[r] >> shift) & dmask;
             const uint32_t v = cw[dgt * kCntStride + quad];
             pos[r] = L.local_base[dgt] + L.wave_tot[w * kMaxRadix + dgt] + (v >> 21) + ((v >> qsh) & qmk) + own[r];
@@ -301,7 +319,7 @@ __device__ __forceinline__ void scatter_tile(const ScatterJob& J, int tile, int 
     uint32_t* stage_v = L.smem + kScatTile;
 #pragma unroll
     for (int r = 0; r < kSortRounds; ++r) {
-        if (lbase + r < n) {
+        if (lbase + r < J.end) {
             stage[pos[r]] = key[r];
             stage_v[pos[r]] = val[r];
         }
@@ -330,19 +348,27 @@ __global__ __launch_bounds__(kScatThreads) void k_radix_scatter_lane(uint32_t* _
                                                                      uint32_t* __restrict__ keys1, uint32_t* __restrict__ vals1,
                                                                      int64_t cap, const VoxelGeom* __restrict__ geom, int pass,
                                                                      int n_tiles, const uint32_t* __restrict__ hist_scanned,
-                                                                     const uint32_t* __restrict__ hist_part, int tm)
+                                                                     const uint32_t* __restrict__ hist_part, int tm,
+                                                                     const uint32_t* __restrict__ emit_tile_off,
+                                                                     int n_emit_tiles)
 {
     __shared__ ScatterLds L;
     const int f = blockIdx.y;
     const VoxelGeom g = geom[f];
     if (g.overflow || pass >= (int)g.passes) return;
+    // candidate-aligned tiles (emit_part_range): every part of the frame's emit tiles is an item, empty ones included
+    const uint32_t* tile_off = emit_tile_off ? emit_tile_off + (int64_t)f * n_emit_tiles : nullptr;
+    const int n_items = tile_off ? (n_emit_tiles + kEmitGroup / kScatParts - 1) / (kEmitGroup / kScatParts)
+                                 : (int)(((int64_t)g.n + kScatTile - 1) / kScatTile);
     // XCD-contiguous order (gridDim.x is a multiple of 8): a part's 128 output runs (~128 bytes each, unaligned)
     // continue the runs of the part before it, and the lines they share are completed in one L2 instead of being
     // written back in pieces by two: 2.57 -> 2.06 ms per 200-frame step
-    const int item = xcd_chunk_item(blockIdx.x, (int)(((int64_t)g.n + kScatTile - 1) / kScatTile));
+    const int item = xcd_chunk_item(blockIdx.x, n_items);
     if (item < 0) return;
     const int tile = item / kScatParts, part = item % kScatParts;
     ScatterJob J;
+    emit_part_range(tile_off, n_emit_tiles, tile, part, (int64_t)g.n, J.begin, J.end);
+    if (J.begin >= J.end) return;
     const int par = (pass + (int)g.buf0) & 1;  // which of the two buffers this pass reads
     J.kin = (par ? keys1 : keys0) + (int64_t)f * cap;
     J.vin = (par ? vals1 : vals0) + (int64_t)f * cap;
@@ -350,15 +376,13 @@ __global__ __launch_bounds__(kScatThreads) void k_radix_scatter_lane(uint32_t* _
     J.vout = (par ? vals0 : vals1) + (int64_t)f * cap;
     J.hist = hist_scanned + (int64_t)f * kMaxRadix * n_tiles;
     J.hist_part = hist_part + (int64_t)f * kMaxRadix * n_tiles;
-    J.n = g.n;
     J.bins = geom_bins(g);
     J.dmask = (uint32_t)J.bins - 1u;
     J.shift = pass * (int)g.bpp;
     J.pass = pass;
     J.n_tiles = n_tiles;
-    J.frame_vec = (((int64_t)f * cap) & 3) == 0;
     J.tm = tm != 0;
     uint32_t key0[kSortRounds], val0[kSortRounds], g0;
     scatter_load(J, tile, part, key0, val0, g0);
-    scatter_tile(J, tile, part, L, key0, val0, g0);
+    scatter_tile(J, L, key0, val0, g0);
 }

@@ -355,34 +355,64 @@ __global__ __launch_bounds__(kEmitThreads) void k_reproject_count_cbox(Reproject
 // pass 2: recompute, transform, compact in row-major order, write 16-byte points coalesced
 // KEYS (fused batch path: the grid geometry is already known, see k_reproject_bbox_count): the same pass also
 // writes every point's voxel index for the sort, instead of a second kernel reading the 16-byte points back, and
-// orders the tile's points by layout class (slab_class).  mm is not written then.  (Counting the first radix pass's
-// digits here as well - one global atomic per non-empty (sort tile, digit) of every tile, 19 M per 200-frame step -
-// cost this pass 0.2 ms and saved a 0.11 ms histogram pass: k_radix_hist does it.)
+// orders the tile's points by layout class (slab_class).  mm is not written then.
+// A KEYS workgroup walks kEmitGroup consecutive tiles of one frame.  With `hist` it also counts the first radix pass's
+// digits of the indices it writes: the first pass of such a frame sorts over CANDIDATE-ALIGNED tiles (sort tile t = the
+// records of emit tiles [kEmitGroup t, kEmitGroup t + kEmitGroup), its scatter parts = the two halves of those emit
+// tiles; see emit_part_range), so this workgroup is the only writer of sort tile blockIdx.x's histogram row and the
+// counts leave as one 512-byte store - no global atomic, and k_radix_hist's pass over the indices is not needed.
+// (Counted per emit tile into record-aligned sort tiles - one global atomic per non-empty (sort tile, digit), 19 M per
+// 200-frame step - the counting cost this pass 0.2 ms and saved a 0.11 ms histogram pass.)
+__device__ __forceinline__ void emit_digit_count(uint32_t* __restrict__ hw, bool ok, uint32_t dgt)
+{
+    // neighbouring records often share the digit: one add per wave then, else one LDS add per record
+    const unsigned long long act = __ballot(ok);
+    if (act == 0ull) return;
+    const int first = __ffsll((long long)act) - 1;
+    const uint32_t d0 = (uint32_t)__builtin_amdgcn_readlane((int)dgt, first);
+    if (__ballot(ok && dgt == d0) == act) {
+        if ((int)(threadIdx.x & 63) == first) atomicAdd(&hw[d0], (uint32_t)__popcll(act));
+    } else if (ok) {
+        atomicAdd(&hw[dgt], 1u);
+    }
+}
+// KEYS: the tile loop keeps pose, geometry and Q live across tiles; left alone the allocator takes 85 VGPRs = 5 waves per
+// SIMD, one workgroup per CU fewer than the 25.7 KB of LDS allow.  Asked for 6 it fits 79 (SGPR spills into lanes, no
+// scratch).  The other instantiations (42-48 VGPRs, 8 waves) are not constrained by a minimum of 4.
 template <bool F64, bool KEYS>
-__global__ __launch_bounds__(kEmitThreads) void k_reproject_emit(ReprojectArgs a, o3dr_point* __restrict__ out,
+__global__ __launch_bounds__(kEmitThreads) __attribute__((amdgpu_waves_per_eu(KEYS ? 6 : 4)))
+void k_reproject_emit(ReprojectArgs a, o3dr_point* __restrict__ out,
                                                                  const uint32_t* __restrict__ tile_off,
                                                                  const uint32_t* __restrict__ n_kp,
                                                                  float* __restrict__ mm,
                                                                  const VoxelGeom* __restrict__ geom, int64_t cap,
-                                                                 uint32_t* __restrict__ keys)
+                                                                 uint32_t* __restrict__ keys,
+                                                                 uint32_t* __restrict__ hist,
+                                                                 uint32_t* __restrict__ hist_part, int n_sort_tiles)
 {
+    constexpr int kGroup = KEYS ? kEmitGroup : 1;  // tiles per workgroup
+    constexpr int kWaves = kEmitThreads / 64;
     __shared__ uint4 stage[kEmitTile];  // 16 KiB: the tile's points in output order
     __shared__ uint32_t key_stage[KEYS ? kEmitTile : 1];
-    __shared__ uint32_t scan_lds[(kEmitThreads / 64 + 1) * (KEYS ? kSlabClasses / 2 : 1)];
+    __shared__ uint32_t scan_lds[(kWaves + 1) * (KEYS ? kSlabClasses / 2 : 1)];
     __shared__ uint32_t cls_base[kSlabClasses + 1];
-    __shared__ float mm_lds[6 * (kEmitThreads / 64)];
+    __shared__ float mm_lds[6 * kWaves];
     __shared__ double lut_alpha[256];  // rectified-stereo Q: 1/w and Z depend on the disparity byte only
     __shared__ float lut_z[256];
+    __shared__ uint32_t dcnt[KEYS ? kWaves * kMaxRadix : 1];  // digit counts of the workgroup's records, one table per wave
+    if constexpr (KEYS) {
+        // (the first count comes after the barriers of the first tile's scan)
+        for (int i = threadIdx.x; i < kWaves * kMaxRadix; i += kEmitThreads) dcnt[i] = 0;
+    }
     if (a.lut) {
         lut_alpha[threadIdx.x] = a.lut[threadIdx.x].alpha;
         lut_z[threadIdx.x] = a.lut[threadIdx.x].z;
         __syncthreads();
     }
-    const int f = blockIdx.y, tile = blockIdx.x;
+    const int f = blockIdx.y;
     const uint8_t* disp = a.disp + (int64_t)f * a.disp_fstride;
     const uint8_t* bgr = a.bgr + (int64_t)f * a.bgr_fstride;
     const int n_cand = a.Ny * a.Nx;
-    const int c0 = tile * kEmitTile + threadIdx.x * kEmitPerLane;
 
     float m[12];
     const bool xf = a.xf_mode != 0;
@@ -395,127 +425,171 @@ __global__ __launch_bounds__(kEmitThreads) void k_reproject_emit(ReprojectArgs a
         for (int i = 0; i < 12; ++i) m[i] = a.T[i];
     }
     VoxelGeom g;
-    bool want_keys = false, part = false;
+    bool want_keys = false, part = false, count = false;
     int s_axis = 0;
     float s_inv = 0.f;
+    uint32_t dmask = 0;
     if constexpr (KEYS) {
         g = geom[f];
         want_keys = !g.overflow && g.n != 0u && g.passes != 0u;
+        count = want_keys && hist != nullptr;
+        dmask = (uint32_t)geom_bins(g) - 1u;  // the digit k_radix_hist counts in pass 0
         // PCL's overflow guard returns the input as it is: pixel order, one class
         part = a.slab_shift >= 0 && !g.overflow;
         s_axis = slab_axis(m);
         s_inv = a.slab_inv[s_axis];
     }
+    // this workgroup's sort tile (KEYS with hist): row of the frame's tile-major histograms
+    const int64_t hrow = ((int64_t)f * n_sort_tiles + blockIdx.x) * kMaxRadix;
 
-    int x0 = 0, y0 = 0;
-    typename DispT<F64>::type d[4];
-    const uint32_t valid = load_lane_disparities<F64>(a, disp, c0, n_cand, x0, y0, d);
-
-    Pix p[4];
-    float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
-    float hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-    uint32_t cls4 = 0;                        // the lane's classes, 4 bits per pixel
-    uint32_t pc[kSlabClasses / 2];            // its points per class, two 16-bit fields per word
+#pragma unroll 1
+    for (int j = 0; j < kGroup; ++j) {
+        const int tile = blockIdx.x * kGroup + j;
+        if (tile >= a.n_tiles) break;
+        if constexpr (KEYS) {
+            if (j == kGroup / kScatParts && count) {  // the first scatter part's records are counted
+                __syncthreads();
+                if (threadIdx.x < kMaxRadix) {
+                    uint32_t t = 0;
 #pragma unroll
-    for (int j = 0; j < kSlabClasses / 2; ++j) pc[j] = 0;
-    if (valid) {
-        uint32_t cb[4], cg[4], cr[4];
-        if (!F64 && a.vec4) {  // 12 colour bytes of 4 pixels = 3 aligned dwords
-            const uint32_t* q = reinterpret_cast<const uint32_t*>(bgr + (int64_t)y0 * a.bgr_pitch + 3 * (int64_t)x0);
-            const uint32_t w0 = q[0], w1 = q[1], w2 = q[2];
-            cb[0] = w0 & 255u;         cg[0] = (w0 >> 8) & 255u;  cr[0] = (w0 >> 16) & 255u;
-            cb[1] = w0 >> 24;          cg[1] = w1 & 255u;         cr[1] = (w1 >> 8) & 255u;
-            cb[2] = (w1 >> 16) & 255u; cg[2] = w1 >> 24;          cr[2] = w2 & 255u;
-            cb[3] = (w2 >> 8) & 255u;  cg[3] = (w2 >> 16) & 255u; cr[3] = w2 >> 24;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (valid & (1u << k)) {
-                int x, y;
-                if (!F64 && a.vec4) {
-                    x = x0 + k;
-                    y = y0;
-                } else {
-                    const int c = c0 + k;
-                    const int ry = c / a.Nx, rx = c - ry * a.Nx;
-                    y = a.bb + ry * a.jump;
-                    x = a.cs + rx * a.jump;
-                    const uint8_t* px = bgr + (int64_t)y * a.bgr_pitch + 3 * (int64_t)x;
-                    cb[k] = px[0];
-                    cg[k] = px[1];
-                    cr[k] = px[2];
+                    for (int ww = 0; ww < kWaves; ++ww) t += dcnt[ww * kMaxRadix + threadIdx.x];
+                    hist_part[hrow + threadIdx.x] = t;
                 }
-                p[k] = reproject_px<F64>(a, a.lut ? lut_alpha : nullptr, lut_z, m, xf, x, y, d[k], cb[k], cg[k], cr[k]);
-                lo[0] = fminf(lo[0], p[k].x); hi[0] = fmaxf(hi[0], p[k].x);
-                lo[1] = fminf(lo[1], p[k].y); hi[1] = fmaxf(hi[1], p[k].y);
-                lo[2] = fminf(lo[2], p[k].z); hi[2] = fmaxf(hi[2], p[k].z);
-                if constexpr (KEYS) {
-                    const uint32_t cls = part ? slab_class(p[k], s_axis, s_inv, a.slab_shift) : 0u;
-                    cls4 |= cls << (4 * k);
+                // (the counting goes on in the same tables, behind the barriers of this tile's scan)
+            }
+        }
+        const int c0 = tile * kEmitTile + threadIdx.x * kEmitPerLane;
+        int x0 = 0, y0 = 0;
+        typename DispT<F64>::type d[4];
+        const uint32_t valid = load_lane_disparities<F64>(a, disp, c0, n_cand, x0, y0, d);
+
+        Pix p[4];
+        float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
+        float hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+        uint32_t cls4 = 0;                        // the lane's classes, 4 bits per pixel
+        uint32_t pc[kSlabClasses / 2];            // its points per class, two 16-bit fields per word
 #pragma unroll
-                    for (int j = 0; j < kSlabClasses / 2; ++j)
-                        if ((cls >> 1) == (uint32_t)j) pc[j] += 1u << (16u * (cls & 1u));
+        for (int q = 0; q < kSlabClasses / 2; ++q) pc[q] = 0;
+        if (valid) {
+            uint32_t cb[4], cg[4], cr[4];
+            if (!F64 && a.vec4) {  // 12 colour bytes of 4 pixels = 3 aligned dwords
+                const uint32_t* q = reinterpret_cast<const uint32_t*>(bgr + (int64_t)y0 * a.bgr_pitch + 3 * (int64_t)x0);
+                const uint32_t w0 = q[0], w1 = q[1], w2 = q[2];
+                cb[0] = w0 & 255u;         cg[0] = (w0 >> 8) & 255u;  cr[0] = (w0 >> 16) & 255u;
+                cb[1] = w0 >> 24;          cg[1] = w1 & 255u;         cr[1] = (w1 >> 8) & 255u;
+                cb[2] = (w1 >> 16) & 255u; cg[2] = w1 >> 24;          cr[2] = w2 & 255u;
+                cb[3] = (w2 >> 8) & 255u;  cg[3] = (w2 >> 16) & 255u; cr[3] = w2 >> 24;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (valid & (1u << k)) {
+                    int x, y;
+                    if (!F64 && a.vec4) {
+                        x = x0 + k;
+                        y = y0;
+                    } else {
+                        const int c = c0 + k;
+                        const int ry = c / a.Nx, rx = c - ry * a.Nx;
+                        y = a.bb + ry * a.jump;
+                        x = a.cs + rx * a.jump;
+                        const uint8_t* px = bgr + (int64_t)y * a.bgr_pitch + 3 * (int64_t)x;
+                        cb[k] = px[0];
+                        cg[k] = px[1];
+                        cr[k] = px[2];
+                    }
+                    p[k] = reproject_px<F64>(a, a.lut ? lut_alpha : nullptr, lut_z, m, xf, x, y, d[k], cb[k], cg[k], cr[k]);
+                    lo[0] = fminf(lo[0], p[k].x); hi[0] = fmaxf(hi[0], p[k].x);
+                    lo[1] = fminf(lo[1], p[k].y); hi[1] = fmaxf(hi[1], p[k].y);
+                    lo[2] = fminf(lo[2], p[k].z); hi[2] = fmaxf(hi[2], p[k].z);
+                    if constexpr (KEYS) {
+                        const uint32_t cls = part ? slab_class(p[k], s_axis, s_inv, a.slab_shift) : 0u;
+                        cls4 |= cls << (4 * k);
+#pragma unroll
+                        for (int q = 0; q < kSlabClasses / 2; ++q)
+                            if ((cls >> 1) == (uint32_t)q) pc[q] += 1u << (16u * (cls & 1u));
+                    }
+                }
+            }
+        }
+        if constexpr (!KEYS) {
+            uint32_t total;
+            uint32_t pos = block_excl_scan_u32<kWaves>(__popc(valid), scan_lds, total);
+            const uint32_t base = n_kp[f] + tile_off[(int64_t)f * a.n_tiles + tile];  // the tile's first point inside the frame's cloud
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (valid & (1u << k)) {
+                    stage[pos] = make_uint4(__float_as_uint(p[k].x), __float_as_uint(p[k].y), __float_as_uint(p[k].z), p[k].rgba);
+                    ++pos;
+                }
+            }
+            __syncthreads();
+            uint4* dst = reinterpret_cast<uint4*>(out + (int64_t)f * a.out_fstride + base);
+            for (uint32_t i = threadIdx.x; i < total; i += kEmitThreads) dst[i] = stage[i];
+            block_minmax_store<kWaves>(lo, hi, valid != 0, mm_lds, mm + ((int64_t)f * a.mm_stride + tile) * 6);
+        } else {
+            // the tile's points go out class by class (slab_class), pixel order inside a class
+            // (the scan's barriers also end the previous tile's reads of the staging buffers)
+            uint32_t tot[kSlabClasses / 2];
+            block_excl_scan_multi_u32<kWaves, kSlabClasses / 2>(pc, scan_lds, tot);  // pc: places inside the classes
+            if (threadIdx.x == 0) {
+                uint32_t run = 0;
+#pragma unroll
+                for (int q = 0; q < kSlabClasses / 2; ++q) {
+                    cls_base[2 * q] = run;
+                    run += tot[q] & 0xffffu;
+                    cls_base[2 * q + 1] = run;
+                    run += tot[q] >> 16;
+                }
+                cls_base[kSlabClasses] = run;
+            }
+            __syncthreads();
+            const uint32_t total = cls_base[kSlabClasses];
+            const uint32_t base = n_kp[f] + tile_off[(int64_t)f * a.n_tiles + tile];  // the tile's first point inside the frame's cloud
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (valid & (1u << k)) {
+                    const uint32_t cls = (cls4 >> (4 * k)) & 15u;
+                    const uint32_t sh = 16u * (cls & 1u);
+                    uint32_t pos = cls_base[cls];
+#pragma unroll
+                    for (int q = 0; q < kSlabClasses / 2; ++q) {
+                        if ((cls >> 1) == (uint32_t)q) {
+                            pos += (pc[q] >> sh) & 0xffffu;  // among the tile's points of the class
+                            pc[q] += 1u << sh;
+                        }
+                    }
+                    const uint4 v = make_uint4(__float_as_uint(p[k].x), __float_as_uint(p[k].y), __float_as_uint(p[k].z), p[k].rgba);
+                    stage[pos] = v;
+                    if (want_keys) key_stage[pos] = voxel_key_of(v, g, 0.f);
+                }
+            }
+            __syncthreads();
+            uint4* dst = reinterpret_cast<uint4*>(out + (int64_t)f * a.out_fstride + base);
+            for (uint32_t i = threadIdx.x; i < total; i += kEmitThreads) dst[i] = stage[i];
+            if (want_keys) {
+                uint32_t* kd = keys + (int64_t)f * cap + base;
+                uint32_t* hw = dcnt + (threadIdx.x >> 6) * kMaxRadix;
+                for (uint32_t i0 = 0; i0 < total; i0 += kEmitThreads) {  // (uniform trips: the count votes over the wave)
+                    const uint32_t i = i0 + threadIdx.x;
+                    const bool ok = i < total;
+                    const uint32_t key = ok ? key_stage[i] : 0u;
+                    if (ok) kd[i] = key;
+                    if (count) emit_digit_count(hw, ok, key & dmask);
                 }
             }
         }
     }
-    if constexpr (!KEYS) {
-        uint32_t total;
-        uint32_t pos = block_excl_scan_u32<kEmitThreads / 64>(__popc(valid), scan_lds, total);
-        const uint32_t base = n_kp[f] + tile_off[(int64_t)f * a.n_tiles + tile];  // the tile's first point inside the frame's cloud
+    if constexpr (KEYS) {
+        // the tile's row leaves in one piece: all kMaxRadix entries whatever the digit's width, zeros included (this
+        // workgroup is the row's only writer, and k_scan_hist_tm's all_live reads every row of a frame that counts)
+        if (count) {
+            __syncthreads();
+            if (threadIdx.x < kMaxRadix) {
+                uint32_t t = 0;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (valid & (1u << k)) {
-                stage[pos] = make_uint4(__float_as_uint(p[k].x), __float_as_uint(p[k].y), __float_as_uint(p[k].z), p[k].rgba);
-                ++pos;
+                for (int ww = 0; ww < kWaves; ++ww) t += dcnt[ww * kMaxRadix + threadIdx.x];
+                hist[hrow + threadIdx.x] = t;
             }
-        }
-        __syncthreads();
-        uint4* dst = reinterpret_cast<uint4*>(out + (int64_t)f * a.out_fstride + base);
-        for (uint32_t i = threadIdx.x; i < total; i += kEmitThreads) dst[i] = stage[i];
-        block_minmax_store<kEmitThreads / 64>(lo, hi, valid != 0, mm_lds, mm + ((int64_t)f * a.mm_stride + tile) * 6);
-    } else {
-        // the tile's points go out class by class (slab_class), pixel order inside a class
-        uint32_t tot[kSlabClasses / 2];
-        block_excl_scan_multi_u32<kEmitThreads / 64, kSlabClasses / 2>(pc, scan_lds, tot);  // pc: places inside the classes
-        if (threadIdx.x == 0) {
-            uint32_t run = 0;
-#pragma unroll
-            for (int j = 0; j < kSlabClasses / 2; ++j) {
-                cls_base[2 * j] = run;
-                run += tot[j] & 0xffffu;
-                cls_base[2 * j + 1] = run;
-                run += tot[j] >> 16;
-            }
-            cls_base[kSlabClasses] = run;
-        }
-        __syncthreads();
-        const uint32_t total = cls_base[kSlabClasses];
-        const uint32_t base = n_kp[f] + tile_off[(int64_t)f * a.n_tiles + tile];  // the tile's first point inside the frame's cloud
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (valid & (1u << k)) {
-                const uint32_t cls = (cls4 >> (4 * k)) & 15u;
-                const uint32_t sh = 16u * (cls & 1u);
-                uint32_t pos = cls_base[cls];
-#pragma unroll
-                for (int j = 0; j < kSlabClasses / 2; ++j) {
-                    if ((cls >> 1) == (uint32_t)j) {
-                        pos += (pc[j] >> sh) & 0xffffu;  // among the tile's points of the class
-                        pc[j] += 1u << sh;
-                    }
-                }
-                const uint4 v = make_uint4(__float_as_uint(p[k].x), __float_as_uint(p[k].y), __float_as_uint(p[k].z), p[k].rgba);
-                stage[pos] = v;
-                if (want_keys) key_stage[pos] = voxel_key_of(v, g, 0.f);
-            }
-        }
-        __syncthreads();
-        uint4* dst = reinterpret_cast<uint4*>(out + (int64_t)f * a.out_fstride + base);
-        for (uint32_t i = threadIdx.x; i < total; i += kEmitThreads) dst[i] = stage[i];
-        if (want_keys) {
-            uint32_t* kd = keys + (int64_t)f * cap + base;
-            for (uint32_t i = threadIdx.x; i < total; i += kEmitThreads) kd[i] = key_stage[i];
         }
     }
 }

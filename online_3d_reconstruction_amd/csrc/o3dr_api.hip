@@ -1575,13 +1575,15 @@ static int accumulate_impl(o3dr_ctx* c, const uint8_t* disp, int64_t disp_frame_
         const bool fused = !use_kp && !c->params.dont_downsample && a.n_tiles > 0 && !with_sor;
         if (use_kp)
             launch_keypoint_pass(&c->prof, c->stream, a, kp_d, 0, c->ws.pts, c->ws.n_kp, c->ws.mm, kpoff_d + f0, nb);
+        int emit_tiles = 0;
         if (fused)
-            launch_reproject_fused(&c->prof, c->stream, c->ws, a, nb, cap, leaf, !c->exact_box);
+            emit_tiles = launch_reproject_fused(&c->prof, c->stream, c->ws, a, nb, cap, leaf, !c->exact_box);
         else
             launch_reproject(&c->prof, c->stream, a, nb, c->ws.pts, c->ws.tile_cnt, c->ws.n_kp, c->ws.n_valid, c->ws.mm,
                              c->ws.scan_partial);
         VoxelArgs v;
         v.keys_ready = fused ? 1 : 0;
+        v.emit_tiles = emit_tiles;
         v.cloud_box = c->cloud_box_valid ? c->cloud_box : nullptr;
         heads_for_append(c, v);
         v.in = c->ws.pts;

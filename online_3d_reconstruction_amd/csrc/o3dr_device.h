@@ -26,6 +26,10 @@ constexpr int kScatParts = 2;
 constexpr int kScatWaves = kSortWaves / kScatParts;
 constexpr int kScatThreads = kScatWaves * kWave;
 constexpr int kScatTile = kScatWaves * kSortWaveItems;
+// emit tiles per sort tile: a KEYS workgroup of k_reproject_emit walks that many, and the first radix pass of the fused
+// batch path sorts over tiles cut at those candidate borders (emit_part_range in kernels/radix_sort.inc)
+constexpr int kEmitGroup = kSortTile / kEmitTile;
+static_assert(kEmitGroup * kEmitTile == kSortTile && kEmitGroup % kScatParts == 0, "a scatter part is a whole number of emit tiles");
 constexpr int kMaxRadixBits = 7;           // digits are 1..7 bits wide, chosen per frame (k_voxel_geom).  Measured with
                                           // the ballot scatter: 7-bit passes 3.8 TB/s, 10-bit ones 2.5 TB/s (32-byte
                                           // output runs); the lane-counting scatter keeps 128 x 17 counters per wave
@@ -212,8 +216,10 @@ void launch_reproject(Profiler* pf, hipStream_t s, const ReprojectArgs& a, int f
                       uint32_t* scan_partial);
 // A1 + A2 of a batch with the per-frame grid's index produced in the same pass over the pixels as the points
 // (bounding boxes and counts first, then PCL's geometry, then the points): for launch_voxel_grid with
-// v.keys_ready = 1.  No keypoint pass (n_kp must hold zeros).
-void launch_reproject_fused(Profiler* pf, hipStream_t s, Workspace& ws, const ReprojectArgs& a, int frames, int64_t cap,
+// v.keys_ready = 1.  No keypoint pass (n_kp must hold zeros).  Returns what v.emit_tiles must be set to: the emit tiles
+// per frame when the pass also counted the digits of the first radix pass (over candidate-aligned sort tiles, whose record
+// ranges are the scanned counts it leaves in ws.tile_cnt), else 0.
+int launch_reproject_fused(Profiler* pf, hipStream_t s, Workspace& ws, const ReprojectArgs& a, int frames, int64_t cap,
                             const float leaf[3], bool conservative_box = true);
 void launch_transform(Profiler* pf, hipStream_t s, const o3dr_point* in, int64_t n, const float* T16_host,
                       o3dr_point* out);
@@ -242,6 +248,7 @@ struct VoxelArgs {
     CloudHeads cloud_heads = {nullptr, {0.f, 0.f, 0.f}, 0.f, nullptr};  // appending to cloud_big: record the group-run heads of what is appended
     const uint8_t* heads_in = nullptr;  // whole-cloud call on a cloud whose group-run heads are recorded already (for this leaf)
     int keys_ready = 0;  // launch_reproject_fused ran: ws.geom and the indices in ws.keys[0] exist
+    int emit_tiles = 0;  // ... and it returned this: the first radix pass's histograms exist too (ws.hist, ws.hist_part)
     int test_corrupt = 0;  // o3dr_test_corrupt_next_gather: poison one sorted payload before the gather (guard test)
 };
 constexpr int kBoxFoldBlocks = 1024;  // workgroups (and partial boxes) of the running-bounding-box fold

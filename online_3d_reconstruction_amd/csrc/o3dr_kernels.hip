@@ -1,7 +1,8 @@
 // o3dr_kernels.hip — hand-written gfx950 kernels of the reconstruction hot path.
 //
 //   K1  k_reproject_count / k_reproject_emit   A1+A2: (u,v,disparity) -> Q -> SE(3) -> ordered cloud
-//       (batched A6: k_reproject_bbox_count, then k_reproject_emit also writes the voxel index and counts pass-0 digits)
+//       (batched A6: k_reproject_bbox_count, then k_reproject_emit also writes the voxel index and counts the first
+//       radix pass's digits over candidate-aligned sort tiles)
 //   K2  k_voxel_geom / k_voxel_keys_*          A4 steps 1-5: PCL VoxelGrid geometry and linear index
 //       k_radix_hist / k_radix_scatter_lane    A4 step 6: stable LSD radix sort of (index, point id)
 //       k_run_heads / k_run_starts / k_centroid  A4 steps 7-8: runs -> ordered fp32 centroid
@@ -183,17 +184,25 @@ void launch_reproject(Profiler* pf, hipStream_t s, const ReprojectArgs& a, int f
     {
         ProfScope ps(pf, O3DR_K_REPROJECT, s);
         if (a.disp_f64)
-            k_reproject_emit<true, false><<<grid, kEmitThreads, 0, s>>>(a, out, tile_cnt, n_kp, mm, nullptr, 0, nullptr);
+            k_reproject_emit<true, false><<<grid, kEmitThreads, 0, s>>>(a, out, tile_cnt, n_kp, mm, nullptr, 0, nullptr, nullptr, nullptr, 0);
         else
-            k_reproject_emit<false, false><<<grid, kEmitThreads, 0, s>>>(a, out, tile_cnt, n_kp, mm, nullptr, 0, nullptr);
+            k_reproject_emit<false, false><<<grid, kEmitThreads, 0, s>>>(a, out, tile_cnt, n_kp, mm, nullptr, 0, nullptr, nullptr, nullptr, 0);
     }
 }
 
 static inline int xcd_grid(int64_t n) { return (int)((n + kXcds - 1) / kXcds * kXcds); }  // see xcd_chunk_item
-void launch_reproject_fused(Profiler* pf, hipStream_t s, Workspace& ws, const ReprojectArgs& a, int frames, int64_t cap,
+// tile-major histogram rows (hist_at in kernels/radix_sort.inc) where a frame's row fits the one-workgroup scan's LDS
+static inline size_t hist_tm_lds(int n_sort_tiles) { return (size_t)n_sort_tiles * (kMaxRadix + 1) * sizeof(uint32_t); }
+static inline int hist_tm(int n_sort_tiles) { return hist_tm_lds(n_sort_tiles) <= 48 * 1024 ? 1 : 0; }
+int launch_reproject_fused(Profiler* pf, hipStream_t s, Workspace& ws, const ReprojectArgs& a, int frames, int64_t cap,
                             const float leaf[3], bool conservative_box)
 {
-    const dim3 grid(a.n_tiles, frames);
+    // the emit pass counts the first radix pass's digits where its workgroups own whole rows of the histograms: tile-major
+    // rows, and as many sort tiles as groups of kEmitGroup emit tiles (cap = the frame's candidates)
+    const int n_sort_tiles = cdiv64(cap, kSortTile);
+    const bool counts = hist_tm(n_sort_tiles) && cdiv64(a.n_tiles, kEmitGroup) == n_sort_tiles;
+    uint32_t* const hist = counts ? ws.hist : nullptr;
+    const dim3 grid(cdiv64(a.n_tiles, kEmitGroup), frames);
     // rectified-stereo Q and byte disparities: counts + a conservative box from the corners of (x, y, disparity) ranges
     // (k_reproject_count_cbox); the exact box only for frames whose conservative one trips PCL's overflow guard
     const bool cbox = a.lut != nullptr && !a.disp_f64 && conservative_box;
@@ -220,10 +229,13 @@ void launch_reproject_fused(Profiler* pf, hipStream_t s, Workspace& ws, const Re
     {
         ProfScope ps(pf, O3DR_K_REPROJECT, s);
         if (a.disp_f64)
-            k_reproject_emit<true, true><<<grid, kEmitThreads, 0, s>>>(a, ws.pts, ws.tile_cnt, ws.n_kp, ws.mm, ws.geom, cap, ws.keys[0]);
+            k_reproject_emit<true, true><<<grid, kEmitThreads, 0, s>>>(a, ws.pts, ws.tile_cnt, ws.n_kp, ws.mm, ws.geom, cap, ws.keys[0], hist,
+                                                                       ws.hist_part, n_sort_tiles);
         else
-            k_reproject_emit<false, true><<<grid, kEmitThreads, 0, s>>>(a, ws.pts, ws.tile_cnt, ws.n_kp, ws.mm, ws.geom, cap, ws.keys[0]);
+            k_reproject_emit<false, true><<<grid, kEmitThreads, 0, s>>>(a, ws.pts, ws.tile_cnt, ws.n_kp, ws.mm, ws.geom, cap, ws.keys[0], hist,
+                                                                        ws.hist_part, n_sort_tiles);
     }
+    return counts ? a.n_tiles : 0;
 }
 
 void launch_transform(Profiler* pf, hipStream_t s, const o3dr_point* in, int64_t n, const float* T16_host,
@@ -255,9 +267,8 @@ void launch_voxel_grid(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelAr
     const int64_t cap = v.cap;
     const int n_sort_tiles = cdiv64(cap, kSortTile);
     const int n_seg_tiles = cdiv64(cap, kSegTile);
-    // tile-major histogram rows (hist_at in kernels/radix_sort.inc) where a frame's row fits the one-workgroup scan's LDS
-    const size_t tm_lds = (size_t)n_sort_tiles * (kMaxRadix + 1) * sizeof(uint32_t);
-    const int tm = tm_lds <= 48 * 1024 ? 1 : 0;
+    const size_t tm_lds = hist_tm_lds(n_sort_tiles);
+    const int tm = hist_tm(n_sort_tiles);
     if (!v.keys_ready) {
         ProfScope ps(pf, O3DR_K_OTHER, s);
         k_voxel_geom<<<F, 256, 0, s>>>(ws.mm, ws.mm_stride, v.mm_used, v.n_dev, v.leaf[0], v.leaf[1], v.leaf[2],
@@ -311,7 +322,10 @@ void launch_voxel_grid(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelAr
         const int64_t hist_row = (int64_t)kMaxRadix * n_sort_tiles;
 
         for (int pass = 0; pass < kMaxPasses; ++pass) {
-            if (!(pass == 0 && !use_runs && !v.keys_ready)) {  // (k_voxel_keys_hist0 counted the first pass's digits)
+            // the first pass over the candidate-aligned tiles the emit pass counted (emit_part_range)
+            const bool emit_tiles = pass == 0 && v.emit_tiles > 0;
+            // (k_voxel_keys_hist0 or k_reproject_emit counted the first pass's digits)
+            if (!(pass == 0 && ((!use_runs && !v.keys_ready) || emit_tiles))) {
                 ProfScope ps(pf, O3DR_K_SORT_HIST, s);
                 k_radix_hist<<<grid, kSortThreads, 0, s>>>(ws.keys[0], ws.keys[1], cap, sort_geom, pass, n_sort_tiles,
                                                           ws.hist, ws.hist_part, tm);
@@ -319,7 +333,7 @@ void launch_voxel_grid(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelAr
             {
                 ProfScope ps(pf, O3DR_K_OTHER, s);
                 if (tm)
-                    k_scan_hist_tm<<<F, 1024, tm_lds, s>>>(ws.hist, sort_geom, pass, n_sort_tiles);
+                    k_scan_hist_tm<<<F, 1024, tm_lds, s>>>(ws.hist, sort_geom, pass, n_sort_tiles, emit_tiles ? 1 : 0);
                 else
                     launch_scan(s, ws.hist, hist_row, hist_row, F, nullptr, nullptr, ws.scan_partial, sort_geom, pass,
                                 n_sort_tiles);
@@ -327,7 +341,8 @@ void launch_voxel_grid(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelAr
             {
                 ProfScope ps(pf, O3DR_K_SORT_SCATTER, s);
                 k_radix_scatter_lane<<<dim3(xcd_grid((int64_t)n_sort_tiles * kScatParts), F), kScatThreads, 0, s>>>(
-                    ws.keys[0], ws.vals[0], ws.keys[1], ws.vals[1], cap, sort_geom, pass, n_sort_tiles, ws.hist, ws.hist_part, tm);
+                    ws.keys[0], ws.vals[0], ws.keys[1], ws.vals[1], cap, sort_geom, pass, n_sort_tiles, ws.hist, ws.hist_part, tm,
+                    emit_tiles ? ws.tile_cnt : nullptr, v.emit_tiles);
             }
         }
         const dim3 sgrid(n_seg_tiles, F);
@@ -432,8 +447,8 @@ void launch_inc_runs(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_poin
     const int64_t cap = n;
     const int n_sort_tiles = cdiv64(cap, kSortTile);
     const int n_seg_tiles = cdiv64(cap, kSegTile);
-    const size_t tm_lds = (size_t)n_sort_tiles * (kMaxRadix + 1) * sizeof(uint32_t);
-    const int tm = tm_lds <= 48 * 1024 ? 1 : 0;
+    const size_t tm_lds = hist_tm_lds(n_sort_tiles);
+    const int tm = hist_tm(n_sort_tiles);
     const VoxelGeom* sort_geom = ws.geom_runs;
     {
         ProfScope ps(pf, O3DR_K_OTHER, s);
@@ -470,14 +485,14 @@ void launch_inc_runs(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_poin
         {
             ProfScope ps(pf, O3DR_K_OTHER, s);
             if (tm)
-                k_scan_hist_tm<<<1, 1024, tm_lds, s>>>(ws.hist, sort_geom, pass, n_sort_tiles);
+                k_scan_hist_tm<<<1, 1024, tm_lds, s>>>(ws.hist, sort_geom, pass, n_sort_tiles, 0);
             else
                 launch_scan(s, ws.hist, hist_row, hist_row, 1, nullptr, nullptr, ws.scan_partial, sort_geom, pass, n_sort_tiles);
         }
         {
             ProfScope ps(pf, O3DR_K_SORT_SCATTER, s);
             k_radix_scatter_lane<<<dim3(xcd_grid((int64_t)n_sort_tiles * kScatParts), 1), kScatThreads, 0, s>>>(
-                ws.keys[0], ws.vals[0], ws.keys[1], ws.vals[1], cap, sort_geom, pass, n_sort_tiles, ws.hist, ws.hist_part, tm);
+                ws.keys[0], ws.vals[0], ws.keys[1], ws.vals[1], cap, sort_geom, pass, n_sort_tiles, ws.hist, ws.hist_part, tm, nullptr, 0);
         }
     }
     {
@@ -636,17 +651,17 @@ static void launch_radix_passes(Workspace& ws, hipStream_t s, int64_t cap, int p
     const int F = frames;
     const int n_sort_tiles = cdiv64(cap, kSortTile);
     const int64_t hist_row = (int64_t)kMaxRadix * n_sort_tiles;
-    const size_t tm_lds = (size_t)n_sort_tiles * (kMaxRadix + 1) * sizeof(uint32_t);
-    const int tm = tm_lds <= 48 * 1024 ? 1 : 0;
+    const size_t tm_lds = hist_tm_lds(n_sort_tiles);
+    const int tm = hist_tm(n_sort_tiles);
     for (int pass = 0; pass < passes && pass < kMaxPasses; ++pass) {
         k_radix_hist<<<dim3(n_sort_tiles, F), kSortThreads, 0, s>>>(ws.keys[0], ws.keys[1], cap, ws.geom, pass, n_sort_tiles, ws.hist,
                                                                     ws.hist_part, tm);
         if (tm)
-            k_scan_hist_tm<<<F, 1024, tm_lds, s>>>(ws.hist, ws.geom, pass, n_sort_tiles);
+            k_scan_hist_tm<<<F, 1024, tm_lds, s>>>(ws.hist, ws.geom, pass, n_sort_tiles, 0);
         else
             launch_scan(s, ws.hist, hist_row, hist_row, F, nullptr, nullptr, ws.scan_partial, ws.geom, pass, n_sort_tiles);
         k_radix_scatter_lane<<<dim3(xcd_grid((int64_t)n_sort_tiles * kScatParts), F), kScatThreads, 0, s>>>(
-            ws.keys[0], ws.vals[0], ws.keys[1], ws.vals[1], cap, ws.geom, pass, n_sort_tiles, ws.hist, ws.hist_part, tm);
+            ws.keys[0], ws.vals[0], ws.keys[1], ws.vals[1], cap, ws.geom, pass, n_sort_tiles, ws.hist, ws.hist_part, tm, nullptr, 0);
     }
 }
 
