@@ -643,6 +643,83 @@ void o3dr_mesh_default_params(o3dr_mesh_params* p);
 int  o3dr_mesh_surface(o3dr_ctx* ctx, const o3dr_point* cloud, int64_t n, const o3dr_mesh_params* p, int32_t* tris,
                        int64_t tris_capacity, int64_t* n_tris, float* vertex_normals, o3dr_mesh_result* res, int32_t mem);
 
+/* ---- plane-fitted disparity per segment label: the reference's --use_segment_labels front end (SURVEY section 2 row 13:
+ * "per-segment least-squares plane over disparity -> CV_64F disparity").  The reference's source for it is not available
+ * to this build, so the contract below is this library's own (INTEGRATION.md lists the differences); every input is an
+ * integer, so it is exact: results are bit-identical across calls, launch geometries, frame batchings and memory kinds.
+ *
+ * Inputs: n_frames images of rows x cols pixels.  disp: u8, byte pitch and byte frame stride as in
+ * o3dr_disparity_variance.  labels: unsigned integers of label_elem_size bytes (1, 2 or 4) with their own byte pitch and
+ * frame stride (multiples of the element size, like the base address); every value must be < n_labels.  Limits, else
+ * O3DR_ERR_INVALID_ARG: 1 <= rows, cols <= 8192, 1 <= n_labels <= 65536 - with them every sum below is an integer
+ * < 2^53 and converts to fp64 exactly.  p == NULL: the defaults.
+ *   1. A pixel participates in its segment's fit iff (double)d > min_disparity (default 0: d == 0 is the stereo matcher's
+ *      "no value").
+ *   2. Per (frame, label) ten exact integer sums over the participating pixels, x the column and y the row:
+ *      n, Sx, Sy, Sxx, Sxy, Syy, Sd, Sxd, Syd, Sdd (64-bit integer adds: no order dependence, no floating-point atomics),
+ *      and the segment's pixel count (participating or not).
+ *   3. Fit in fp64, every operation one correctly rounded IEEE operation in exactly this order (no FMA), the sums
+ *      converted to fp64 first:  mx = Sx / n, my = Sy / n, c0 = Sd / n;
+ *        cxx = Sxx - Sx * mx, cxy = Sxy - Sx * my, cyy = Syy - Sy * my,
+ *        cxd = Sxd - Sd * mx, cyd = Syd - Sd * my, cdd = Sdd - Sd * c0;
+ *        det = cxx * cyy - cxy * cxy;  degenerate iff det <= (O3DR_PLANE_DISP_TOL * cxx) * cyy;
+ *        a = (cxd * cyy - cyd * cxy) / det, b = (cyd * cxx - cxd * cxy) / det;
+ *        mse = ((cdd - a * cxd) - b * cyd) / n   (mean squared residual, no square root, not clamped).
+ *   4. Status: n == 0: O3DR_PLANE_DISP_NONE, the record's numbers all 0.  Else n < min_pixels or degenerate:
+ *      O3DR_PLANE_DISP_MEAN, a = b = 0 (mse by the same formula: cdd / n).  Else O3DR_PLANE_DISP_PLANE.  Then, if max_mse > 0
+ *      and mse > max_mse: O3DR_PLANE_DISP_NONE (a, b, c0, mse stay in the record as computed).
+ *   5. Output pixel (f64, dense [n_frames][rows][cols]): in a PLANE or MEAN segment
+ *      out(x, y) = (c0 + a * ((double)x - mx)) + b * ((double)y - my), not clamped, for every pixel of the segment when
+ *      fill != 0 (hole filling, the default) and for the participating pixels only when fill == 0; every other pixel keeps
+ *      (double)d.  The image is what o3dr_params.disparity_f64 = 1 reads.
+ *
+ * O3DR_PLANE_DISP_TOL = 2^-20.  Rounding bound of step 3 at the 8192 limit, u = 2^-53: mx carries one rounding, Sx * mx a
+ * second, the subtraction a third, and Sx^2 / n <= Sxx, so |cxx' - cxx| <= (3u + 4u^2) Sxx; likewise for cyy, and for cxy
+ * with sqrt(Sxx Syy).  (1) An exactly collinear set: on a row all y are equal, so my = Sy / n and Sy * my are exact and
+ * cyy' = 0 exactly (a column: cxx' = 0); then det' = -cxy'^2 <= 0 = the right-hand side.  On any other line the n >= 2
+ * pixels have n distinct x and n distinct y, so cxx, cyy >= n (n^2 - 1) / 12 and Sxx / cxx <= 1 + 12 * 8191^2 / (n^2 - 1)
+ * < 2^28: the three moments carry relative errors <= 3u * 2^28 = 3 * 2^-25, and with cxy^2 = cxx cyy exactly,
+ * |det'| <= (4 * 3 * 2^-25 + O(u)) cxx cyy = 0.375 * 2^-20 cxx cyy, below TOL * cxx' * cyy' with a factor 2.6 to spare.
+ * (2) Three pixels in an L: cxx = cyy = 2/3, cxy = -+1/3, det = 1/3 = 0.75 cxx cyy; Sxx <= 3 * 8191^2 bounds the absolute
+ * errors of the moments by 9 * 2^-27, so det' = 1/3 +- 2^-22, far above TOL * 4/9.
+ *
+ * Outputs: out (n_frames * rows * cols doubles, 8-byte aligned) and, optional (NULL: skipped), segments: one record per
+ * (frame, label) in (frame, label) order, n_frames * n_labels of them; both in `mem`.  *status (host, optional) receives
+ * O3DR_STATUS_LABEL_RANGE when a label >= n_labels was found: the call then returns O3DR_ERR_INVALID_ARG (such a pixel is
+ * never used as an index).  Checks, in this order, each O3DR_ERR_INVALID_ARG and all before any device work: ctx, mem
+ * kind, n_frames < 0 / rows / cols / n_labels / label_elem_size, the parameters (min_disparity NaN, max_mse NaN or < 0);
+ * then n_frames == 0 returns O3DR_OK and writes nothing; then NULL disp / labels / out, then pitches, strides and
+ * alignments; the label range is found last, on the device.  On error the host outputs are zeroed.  The call
+ * synchronises once, at its end; it does not use the sort workspace and leaves cloud_big alone. */
+typedef struct o3dr_plane_disp_params {
+    double  min_disparity;  /* default 0 */
+    int32_t min_pixels;     /* default 3 */
+    double  max_mse;        /* default 0: no gate */
+    int32_t fill;           /* default 1 */
+} o3dr_plane_disp_params;
+typedef struct o3dr_plane_disp_segment {  /* 64 bytes */
+    double   a, b;          /* slopes along x and y (0 unless PLANE, or NONE by the mse gate) */
+    double   c0;            /* the intercept: the mean disparity, the plane's value at (mx, my) */
+    double   mx, my;        /* centroid of the participating pixels */
+    double   mse;
+    uint32_t n_pixels;      /* pixels of the segment */
+    uint32_t n;             /* participating pixels */
+    int32_t  status;        /* O3DR_PLANE_DISP_* */
+    int32_t  reserved;      /* 0 */
+} o3dr_plane_disp_segment;
+#define O3DR_PLANE_DISP_NONE  0
+#define O3DR_PLANE_DISP_MEAN  1
+#define O3DR_PLANE_DISP_PLANE 2
+#define O3DR_PLANE_DISP_TOL   9.5367431640625e-07 /* 2^-20 */
+#define O3DR_PLANE_DISP_MAX_SIDE   8192
+#define O3DR_PLANE_DISP_MAX_LABELS 65536
+#define O3DR_STATUS_LABEL_RANGE 2u /* o3dr_plane_fit_disparity: a label >= n_labels in the data */
+void o3dr_plane_disp_default_params(o3dr_plane_disp_params* p);
+int  o3dr_plane_fit_disparity(o3dr_ctx* ctx, const uint8_t* disp, int64_t disp_pitch, int64_t disp_frame_stride, const void* labels,
+                              int32_t label_elem_size, int64_t labels_pitch, int64_t labels_frame_stride, int32_t n_labels,
+                              int32_t rows, int32_t cols, int32_t n_frames, const o3dr_plane_disp_params* p, double* out,
+                              o3dr_plane_disp_segment* segments, uint32_t* status, int32_t mem);
+
 /* ---- measurement hooks (bench.py; not part of the reference surface) ------------------------ */
 /* kernel ids for o3dr_profile_* */
 #define O3DR_K_COUNT        0  /* grid-pass valid count per tile */
@@ -654,7 +731,10 @@ int  o3dr_mesh_surface(o3dr_ctx* ctx, const o3dr_point* cloud, int64_t n, const 
 #define O3DR_K_CENTROID     6  /* ordered per-voxel sums -> centroid */
 #define O3DR_K_OTHER        7  /* scans, grid setup, copies */
 #define O3DR_K_CENTROID_RUNS 8 /* ordered per-voxel sums over group runs of points, one wave per voxel group (whole-cloud calls) */
-#define O3DR_K_NUM          9
+#define O3DR_K_PLANE_DISP_SUMS 9   /* plane-fitted disparity: per-(frame, label) integer sums */
+#define O3DR_K_PLANE_DISP_FIT  10  /* ... the fp64 fit of every (frame, label) */
+#define O3DR_K_PLANE_DISP_EVAL 11  /* ... the f64 image */
+#define O3DR_K_NUM          12
 /* Bracket every launch of kernel `kernel_id` (or all kernels if -1) with HIP events on the
  * context's stream; 0 launches are bracketed when disabled (the default). */
 int o3dr_profile_enable(o3dr_ctx* ctx, int32_t kernel_id, int32_t enable);

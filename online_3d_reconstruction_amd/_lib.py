@@ -13,10 +13,12 @@ OK = 0
 ERR_INVALID_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_CAPACITY, ERR_NOT_CONFIGURED, ERR_ALLOC, ERR_INTERNAL, ERR_PEER = -1, -2, -3, -4, -5, -6, -7, -8
 MEM_HOST, MEM_DEVICE = 0, 1
 STATUS_VOXEL_OVERFLOW = 1
+STATUS_LABEL_RANGE = 2
 STATUS_INTERNAL = 0x80000000
 K_COUNT, K_REPROJECT, K_KEYGEN, K_SORT_HIST, K_SORT_SCATTER, K_SEGMENT, K_CENTROID, K_OTHER, K_CENTROID_RUNS = range(9)
+K_PLANE_DISP_SUMS, K_PLANE_DISP_FIT, K_PLANE_DISP_EVAL = 9, 10, 11
 KERNEL_NAMES = ["reproject_count", "reproject_emit", "voxel_keys", "radix_hist", "radix_scatter", "run_segments",
-                "centroid", "other", "centroid_runs"]
+                "centroid", "other", "centroid_runs", "plane_disp_sums", "plane_disp_fit", "plane_disp_eval"]
 
 
 class O3drError(RuntimeError):
@@ -76,6 +78,19 @@ class MeshParamsStruct(C.Structure):
 class MeshResultStruct(C.Structure):
     _fields_ = [("n_vertices", C.c_int64), ("n_shadowed", C.c_int64), ("n_triangles", C.c_int64), ("n_quads_full", C.c_int64),
                 ("n_rejected_orientation", C.c_int64), ("n_rejected_length", C.c_int64)]
+
+
+class PlaneDispParamsStruct(C.Structure):
+    _fields_ = [("min_disparity", C.c_double), ("min_pixels", C.c_int32), ("max_mse", C.c_double), ("fill", C.c_int32)]
+
+
+# o3dr_plane_disp_segment (64 bytes), as a numpy record: Context.planeFitDisparity returns the segment records in this layout
+PLANE_DISP_SEGMENT = np.dtype([("a", "<f8"), ("b", "<f8"), ("c0", "<f8"), ("mx", "<f8"), ("my", "<f8"), ("mse", "<f8"),
+                               ("n_pixels", "<u4"), ("n", "<u4"), ("status", "<i4"), ("reserved", "<i4")])
+assert PLANE_DISP_SEGMENT.itemsize == 64
+PLANE_DISP_NONE, PLANE_DISP_MEAN, PLANE_DISP_PLANE = range(3)
+PLANE_DISP_TOL = 2.0 ** -20
+PLANE_DISP_MAX_SIDE, PLANE_DISP_MAX_LABELS = 8192, 65536
 
 
 class MatchParamsStruct(C.Structure):
@@ -168,6 +183,9 @@ SYMBOLS = [
     ("o3dr_mesh_default_params", None, [C.POINTER(MeshParamsStruct)]),
     ("o3dr_mesh_surface", C.c_int, [_vp, _vp, _i64, C.POINTER(MeshParamsStruct), _vp, _i64, _pi64, _vp,
                                     C.POINTER(MeshResultStruct), _i32]),
+    ("o3dr_plane_disp_default_params", None, [C.POINTER(PlaneDispParamsStruct)]),
+    ("o3dr_plane_fit_disparity", C.c_int, [_vp, _vp, _i64, _i64, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32,
+                                           C.POINTER(PlaneDispParamsStruct), _vp, _vp, _pu32, _i32]),
     ("o3dr_profile_enable", C.c_int, [_vp, _i32, _i32]),
     ("o3dr_profile_read", C.c_int, [_vp, _i32, C.POINTER(C.c_double), _pi64]),
     ("o3dr_profile_reset", C.c_int, [_vp]),

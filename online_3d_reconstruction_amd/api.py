@@ -290,6 +290,68 @@ class Context:
         L.check(self._lib.o3dr_disparity_variance(self._h, ptr, pitch, fs, rows, cols, F, out.ctypes.data, mem))
         return out
 
+    def planeFitDisparity(self, disp, labels, n_labels=None, min_disparity=0.0, min_pixels=3, max_mse=0.0, fill=True,
+                          return_segments=False):
+        """--use_segment_labels: a least-squares plane over the disparity of every label's pixels (contract: include/o3dr.h,
+        DESIGN.md "Plane-fitted disparity").  disp: [H,W] or [F,H,W] uint8; labels: the same shape, uint8 / uint16 / uint32
+        (numpy), uint8 / int16 / int32 read as unsigned (torch), every value < n_labels (None: the largest label + 1).
+        -> float64 image(s) of the same shape, what Params(disparity_f64=True) reads; with return_segments also the
+        [F, n_labels] (or [n_labels]) PLANE_DISP_SEGMENT records (numpy).  numpy in, numpy out; torch CUDA tensors in, a
+        CUDA float64 tensor out (nothing leaves HBM)."""
+        single = disp.ndim == 2
+        if single:
+            disp, labels = disp[None], labels[None]
+        F, rows, cols = (int(v) for v in disp.shape)
+        assert tuple(int(v) for v in labels.shape) == (F, rows, cols), "disp and labels differ in shape"
+        torch_in = _is_torch(disp)
+        if torch_in:
+            import torch
+            assert _is_torch(labels) and disp.dtype == torch.uint8 and disp.device == labels.device
+            assert labels.dtype in (torch.uint8, torch.int16, torch.int32, getattr(torch, "uint16", None), getattr(torch, "uint32", None))
+            assert F == 0 or (disp.stride(2) == 1 and labels.stride(2) == 1)
+            es = labels.element_size()
+            pd, dfs, dp = disp.data_ptr(), disp.stride(0), disp.stride(1)
+            pl, lfs, lp = labels.data_ptr(), labels.stride(0) * es, labels.stride(1) * es
+            mem = L.MEM_DEVICE if disp.is_cuda else L.MEM_HOST
+            if n_labels is None:
+                n_labels = int(labels.max().item()) + 1 if labels.numel() else 1
+        else:
+            disp = np.asarray(disp)
+            labels = np.asarray(labels)
+            assert disp.dtype == np.uint8 and labels.dtype in (np.uint8, np.uint16, np.uint32)
+            assert F == 0 or (disp.strides[2] == 1 and labels.strides[2] == labels.itemsize)
+            es = labels.itemsize
+            pd, dfs, dp = disp.ctypes.data, disp.strides[0], disp.strides[1]
+            pl, lfs, lp = labels.ctypes.data, labels.strides[0], labels.strides[1]
+            mem = L.MEM_HOST
+            if n_labels is None:
+                n_labels = int(labels.max()) + 1 if labels.size else 1
+        n_labels = int(n_labels)
+        prm = L.PlaneDispParamsStruct(float(min_disparity), int(min_pixels), float(max_mse), 1 if fill else 0)
+        n_rec = F * n_labels if 1 <= n_labels <= L.PLANE_DISP_MAX_LABELS else 0
+        st = C.c_uint32(0)
+        if mem == L.MEM_DEVICE:
+            out = torch.empty((F, rows, cols), dtype=torch.float64, device=disp.device)
+            rec = torch.empty((max(n_rec, 1), 64), dtype=torch.uint8, device=disp.device) if return_segments else None
+            self._order_after_torch()
+            po, pr = out.data_ptr(), (rec.data_ptr() if return_segments else None)
+        else:
+            out = np.empty((F, rows, cols), np.float64)
+            rec = np.empty(max(n_rec, 1), L.PLANE_DISP_SEGMENT) if return_segments else None
+            po, pr = out.ctypes.data, (rec.ctypes.data if return_segments else None)
+        L.check(self._lib.o3dr_plane_fit_disparity(self._h, pd, dp, dfs, pl, es, lp, lfs, n_labels, rows, cols, F, C.byref(prm),
+                                                   po, pr, C.byref(st), mem))
+        if torch_in and mem == L.MEM_HOST:
+            out = torch.from_numpy(out)
+        if single:
+            out = out[0]
+        if not return_segments:
+            return out
+        if mem == L.MEM_DEVICE:
+            rec = rec.cpu().numpy().view(L.PLANE_DISP_SEGMENT).reshape(-1)
+        rec = rec[:n_rec].reshape(F, n_labels)
+        return out, (rec[0] if single else rec)
+
     def statisticalOutlierRemoval(self, pts):
         """pcl::StatisticalOutlierRemoval, mean_k 50, 1 sigma (pose_functions.cpp:1679-1684)."""
         if not _is_torch(pts):

@@ -3818,6 +3818,112 @@ extern "C" int o3dr_estimate_rigid_transform(o3dr_ctx* c, const o3dr_point* src,
     return rc;
 }
 
+// -------------------------------------------------------------------------------------------------
+// plane-fitted disparity per segment label (kernels/plane_disparity.inc; DESIGN.md "Plane-fitted disparity")
+// -------------------------------------------------------------------------------------------------
+extern "C" void o3dr_plane_disp_default_params(o3dr_plane_disp_params* p)
+{
+    if (!p) return;
+    p->min_disparity = 0.0;  // d == 0: the stereo matcher's "no value"
+    p->min_pixels = 3;
+    p->max_mse = 0.0;        // no gate
+    p->fill = 1;
+}
+
+constexpr size_t kPlaneDispTableBytes = (size_t)64 << 20;  // the sums table covers this many bytes of frames at a time
+
+static int plane_fit_disparity(o3dr_ctx* c, const uint8_t* disp, int64_t disp_pitch, int64_t disp_fs, const void* labels, int32_t es,
+                               int64_t lab_pitch, int64_t lab_fs, int32_t n_labels, int32_t rows, int32_t cols, int32_t n_frames,
+                               const o3dr_plane_disp_params* p, double* out, o3dr_plane_disp_segment* segments, Outputs& outs,
+                               uint32_t* status, int32_t mem)
+{
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    if (n_frames < 0) return fail(O3DR_ERR_INVALID_ARG, "bad frame count");
+    if (rows < 1 || rows > O3DR_PLANE_DISP_MAX_SIDE || cols < 1 || cols > O3DR_PLANE_DISP_MAX_SIDE)
+        return fail(O3DR_ERR_INVALID_ARG, "rows and cols must be in 1..8192");
+    if (n_labels < 1 || n_labels > O3DR_PLANE_DISP_MAX_LABELS) return fail(O3DR_ERR_INVALID_ARG, "n_labels must be in 1..65536");
+    if (es != 1 && es != 2 && es != 4) return fail(O3DR_ERR_INVALID_ARG, "label_elem_size must be 1, 2 or 4");
+    o3dr_plane_disp_params prm;
+    o3dr_plane_disp_default_params(&prm);
+    if (p) prm = *p;
+    if (prm.min_disparity != prm.min_disparity) return fail(O3DR_ERR_INVALID_ARG, "min_disparity is NaN");
+    if (!(prm.max_mse >= 0.0)) return fail(O3DR_ERR_INVALID_ARG, "max_mse must be >= 0 (0: no gate)");
+    if (n_frames == 0) return O3DR_OK;
+    if (!disp || !labels || !out) return fail(O3DR_ERR_INVALID_ARG, "disp / labels / out is NULL");
+    if (disp_pitch < cols || lab_pitch < (int64_t)cols * es) return fail(O3DR_ERR_INVALID_ARG, "pitch smaller than a row");
+    if (n_frames > 1 && (disp_fs < (int64_t)rows * disp_pitch || lab_fs < (int64_t)rows * lab_pitch))
+        return fail(O3DR_ERR_INVALID_ARG, "frame stride smaller than a frame");
+    if (((uintptr_t)labels | (uintptr_t)lab_pitch | (uintptr_t)lab_fs) % (uintptr_t)es)
+        return fail(O3DR_ERR_INVALID_ARG, "labels, their pitch and frame stride must be multiples of the element size");
+    if ((uintptr_t)out % 8 || (uintptr_t)segments % 8) return fail(O3DR_ERR_INVALID_ARG, "out / segments must be 8-byte aligned");
+
+    const size_t npix = (size_t)rows * cols, F = (size_t)n_frames;
+    const void *disp_d, *lab_d;
+    CHK(stage_in(c, c->st_blur_in, disp, (size_t)disp_fs * (F - 1) + (size_t)disp_pitch * rows, mem, &disp_d));
+    CHK(stage_in(c, c->op[o3dr_ctx::OP_IN], labels, (size_t)lab_fs * (F - 1) + (size_t)lab_pitch * rows, mem, &lab_d));
+    // frames per pass: the table of sums stays within its budget (and within O3DR_BATCH_FRAMES); results do not depend on it
+    size_t chunk = kPlaneDispTableBytes / ((size_t)n_labels * kPdSums * sizeof(unsigned long long));
+    chunk = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(chunk, (size_t)c->max_batch), F));
+    uint32_t* flag;
+    CHK(op_flags(c, &flag));
+    unsigned long long* table;
+    o3dr_plane_disp_segment* rec_scratch;
+    CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
+        w.take(table, chunk * (size_t)n_labels * kPdSums);
+        w.take(rec_scratch, segments ? 0 : chunk * (size_t)n_labels);
+    }));
+    CHK(outs.stage(c));  // the image, the records
+    HIPCHK(hipMemsetAsync(flag, 0, sizeof(uint32_t), c->stream));
+    PlaneDispArgs a;
+    memset(&a, 0, sizeof a);
+    a.dpitch = disp_pitch, a.dfs = disp_fs, a.lpitch = lab_pitch, a.lfs = lab_fs;
+    a.elem = es, a.rows = rows, a.cols = cols, a.n_labels = (uint32_t)n_labels;
+    {   // (double)d > m  <=>  d > floor(m) for an integer d: the comparison on integers
+        const double m = prm.min_disparity;
+        a.thr = m >= 255.0 ? 255 : (m < 0.0 ? -1 : (int32_t)floor(m));
+    }
+    a.min_pixels = prm.min_pixels, a.fill = prm.fill ? 1 : 0, a.max_mse = prm.max_mse;
+    a.table = table, a.flag = flag;
+    for (size_t f0 = 0; f0 < F; f0 += chunk) {
+        a.frames = (int32_t)std::min(chunk, F - f0);
+        a.disp = (const uint8_t*)disp_d + (int64_t)f0 * disp_fs;
+        a.labels = (const uint8_t*)lab_d + (int64_t)f0 * lab_fs;
+        a.rec = segments ? outs.dev(segments) + f0 * (size_t)n_labels : rec_scratch;
+        a.out = outs.dev(out) + f0 * npix;
+        launch_plane_disp(&c->prof, c->stream, a);
+    }
+    HIPCHK(hipGetLastError());
+    uint32_t flag_h = 0;
+    HIPCHK(hipMemcpyAsync(&flag_h, flag, sizeof flag_h, hipMemcpyDeviceToHost, c->stream));
+    CHK(outs.copy_back(c));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (flag_h) {
+        if (status) *status |= O3DR_STATUS_LABEL_RANGE;
+        return fail(O3DR_ERR_INVALID_ARG, "a label is >= n_labels");
+    }
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_plane_fit_disparity(o3dr_ctx* c, const uint8_t* disp, int64_t disp_pitch, int64_t disp_frame_stride,
+                                        const void* labels, int32_t label_elem_size, int64_t labels_pitch, int64_t labels_frame_stride,
+                                        int32_t n_labels, int32_t rows, int32_t cols, int32_t n_frames, const o3dr_plane_disp_params* p,
+                                        double* out, o3dr_plane_disp_segment* segments, uint32_t* status, int32_t mem)
+{
+    if (status) *status = 0;
+    // what the host outputs hold, for the zeroing after an error: only sizes within the contract's limits count
+    const bool sized = n_frames > 0 && rows >= 1 && rows <= O3DR_PLANE_DISP_MAX_SIDE && cols >= 1 && cols <= O3DR_PLANE_DISP_MAX_SIDE &&
+                       n_labels >= 1 && n_labels <= O3DR_PLANE_DISP_MAX_LABELS;
+    Outputs outs{mem};
+    outs.add(out, sized ? (int64_t)n_frames * rows * cols : 0);
+    outs.add(segments, sized ? (int64_t)n_frames * n_labels : 0);
+    const int rc = entered(c, [&] {
+        return plane_fit_disparity(c, disp, disp_pitch, disp_frame_stride, labels, label_elem_size, labels_pitch, labels_frame_stride,
+                                   n_labels, rows, cols, n_frames, p, out, segments, outs, status, mem);
+    });
+    if (rc != O3DR_OK) outs.zero();
+    return rc;
+}
+
 extern "C" int o3dr_profile_enable(o3dr_ctx* c, int32_t kernel_id, int32_t enable)
 {
     CTX_ENTER(c);

@@ -423,6 +423,27 @@ void launch_mesh_range(Profiler* pf, hipStream_t s, const o3dr_point* in, int64_
 void launch_mesh_cells(Profiler* pf, hipStream_t s, Workspace& ws, MeshArgs& a, int nbits, uint32_t* head, uint32_t* n_vert_dev);
 void launch_mesh_count(Profiler* pf, hipStream_t s, Workspace& ws, const MeshArgs& a, uint32_t* n_tris_dev);
 void launch_mesh_emit(Profiler* pf, hipStream_t s, const MeshArgs& a);
+// plane-fitted disparity per segment label (kernels/plane_disparity.inc).  `table`: kPdSums 64-bit sums per (frame, label) -
+// n Sx Sy Sxx Sxy Syy Sd Sxd Syd Sdd and the pixel count -, zeroed here; thr: d participates iff (int)d > thr; flag: a
+// device word, bit 0 set when a label >= n_labels was seen.  launch_plane_disp runs the three steps for `frames` frames:
+// the sums, the fit of every (frame, label) into rec (frames * n_labels records) and the dense f64 image `out`.
+constexpr int kPdSums = 11;
+struct PlaneDispArgs {
+    const uint8_t* disp;
+    int64_t dpitch, dfs;
+    const uint8_t* labels;
+    int64_t lpitch, lfs;
+    int32_t elem;  // bytes per label: 1, 2, 4
+    int32_t rows, cols, frames;
+    uint32_t n_labels;
+    int32_t thr, min_pixels, fill;
+    double max_mse;
+    unsigned long long* table;
+    o3dr_plane_disp_segment* rec;
+    double* out;
+    uint32_t* flag;
+};
+void launch_plane_disp(Profiler* pf, hipStream_t s, const PlaneDispArgs& a);
 void launch_partition(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelArgs& v, int n_parts, o3dr_point* out,
                       uint64_t* counts_dev, uint32_t* overflow_dev, const void* hdrs_dev = nullptr, int n_hdrs = 0);
 // its two halves: slice sizes without moving anything (the (part, tile) table stays in ws for the second half), then the move

@@ -56,6 +56,7 @@ namespace o3dr {
 #include "kernels/plane.inc"
 #include "kernels/mesh.inc"
 #include "kernels/match.inc"
+#include "kernels/plane_disparity.inc"
 
 // =================================================================================================
 // launchers
@@ -593,6 +594,47 @@ void launch_disp_variance(Profiler* pf, hipStream_t s, const uint8_t* disp, int6
     const int roi_rows = rows - 2 * bb;
     if (roi_rows > 0) k_disp_hist<<<dim3(roi_rows, frames), 256, 0, s>>>(disp, pitch, fstride, rows, cols, bb, cs, min_disp, hist);
     k_disp_variance<<<cdiv64(frames, 64), 64, 0, s>>>(hist, frames, rows, cols, bb, cs, var_out);
+}
+
+template <typename LT>
+static void plane_disp_frames(Profiler* pf, hipStream_t s, const PlaneDispArgs& a, int f0, int nf)
+{
+    const uint8_t* disp = a.disp + (int64_t)f0 * a.dfs;
+    const uint8_t* labels = a.labels + (int64_t)f0 * a.lfs;
+    unsigned long long* table = a.table + (size_t)f0 * a.n_labels * kPdSums;
+    o3dr_plane_disp_segment* rec = a.rec + (size_t)f0 * a.n_labels;
+    const int64_t npix = (int64_t)a.rows * a.cols;
+    const int tiles_x = cdiv64(a.cols, kPdTileX), tiles_y = cdiv64(a.rows, kPdTileY);
+    const int vec = (((uintptr_t)disp | (uintptr_t)labels | (uintptr_t)a.dpitch | (uintptr_t)a.dfs | (uintptr_t)a.lpitch |
+                      (uintptr_t)a.lfs) & 15) == 0;
+    {
+        ProfScope ps(pf, O3DR_K_PLANE_DISP_SUMS, s);
+        k_pd_accumulate<LT><<<dim3(tiles_x * tiles_y, nf), 256, 0, s>>>(disp, a.dpitch, a.dfs, labels, a.lpitch, a.lfs, a.rows, a.cols,
+                                                                         a.n_labels, a.thr, tiles_x, vec, table, a.flag);
+    }
+    {
+        ProfScope ps(pf, O3DR_K_PLANE_DISP_FIT, s);
+        const int64_t n_rec = (int64_t)nf * a.n_labels;
+        k_pd_fit<<<cdiv64(n_rec, 256), 256, 0, s>>>(table, n_rec, a.min_pixels, a.max_mse, rec);
+    }
+    {
+        ProfScope ps(pf, O3DR_K_PLANE_DISP_EVAL, s);
+        const int64_t pairs = npix / 2 + 1;  // (one more than half: a frame may start on the odd half of a 16-byte pair)
+        k_pd_evaluate<LT><<<dim3(cdiv64(pairs, 256 * kPdEvalIter), nf), 256, 0, s>>>(disp, a.dpitch, a.dfs, labels, a.lpitch, a.lfs, a.rows,
+                                                                                   a.cols, a.n_labels, a.thr, a.fill, rec,
+                                                                                   a.out + (int64_t)f0 * npix);
+    }
+}
+void launch_plane_disp(Profiler* pf, hipStream_t s, const PlaneDispArgs& a)
+{
+    if (a.frames <= 0 || a.rows <= 0 || a.cols <= 0) return;
+    (void)hipMemsetAsync(a.table, 0, sizeof(unsigned long long) * kPdSums * (size_t)a.frames * a.n_labels, s);
+    for (int f0 = 0; f0 < a.frames; f0 += 32768) {  // (a grid's y extent is 16 bits)
+        const int nf = a.frames - f0 < 32768 ? a.frames - f0 : 32768;
+        if (a.elem == 1) plane_disp_frames<uint8_t>(pf, s, a, f0, nf);
+        else if (a.elem == 2) plane_disp_frames<uint16_t>(pf, s, a, f0, nf);
+        else plane_disp_frames<uint32_t>(pf, s, a, f0, nf);
+    }
 }
 
 void launch_bbox(Profiler* pf, hipStream_t s, const float* mm, int used, float* out6)

@@ -43,6 +43,13 @@ struct Image8 {                                 // cv::Mat stand-in: 8-bit, 1 or
 // ---- I/O helpers (png_io.cpp, ply_io.cpp) ------------------------------------------------------------
 // cv::imread(path) / cv::imread(path, IMREAD_GRAYSCALE) for 8-bit non-interlaced PNGs; empty on failure
 Image8 read_png(const std::string& path, bool grayscale);
+struct Image16 {                                // one 16-bit channel: a segment label image
+    int rows = 0, cols = 0;
+    std::vector<uint16_t> data;
+    bool empty() const { return data.empty(); }
+};
+// a label image: greyscale (colour type 0), 8 or 16 bits per sample, non-interlaced; empty on failure or any other format
+Image16 read_png_labels(const std::string& path);
 // pcl::io::savePLYFileBinary layout (x,y,z float + r,g,b uchar, then one `camera` element); with normals (4 floats per
 // point: nx ny nz curvature) PointXYZRGBNormal's (the same, then normal_x normal_y normal_z curvature float)
 bool save_ply_binary(const std::string& path, const PointCloud& cloud, const std::vector<float>* normals = nullptr);
@@ -58,6 +65,7 @@ class RawImageData {  // pose.h:54-70
 public:
     int img_num = 0;
     Image8 rgb_image, disparity_image;
+    Image16 label_image;  // --use_segment_labels
     double time = 0, tx = 0, ty = 0, tz = 0, qx = 0, qy = 0, qz = 0, qw = 1;
 };
 
@@ -119,6 +127,13 @@ public:
     bool preview = false;           // --preview: after every cycle, the merged map so far -> <output_dir>/preview.ply
                                     // (pose.cpp:437-448, 638-674), folded incrementally (o3dr_finalize_incremental)
 
+    bool use_segment_labels = false;  // --use_segment_labels: every batch's disparities go through o3dr_plane_fit_disparity
+                                      // and are accumulated as CV_64F (single-GPU batched path, also with --preview)
+    std::string segmentLabelsPrefix = "segmentlabels/";  // --segment_labels_dir: <img_num>.png, 8- or 16-bit greyscale
+    int plane_min_pixels = 3;         // --plane_min_pixels
+    double plane_max_mse = 0.0;       // --plane_max_mse (0: no gate)
+    std::string print_label_png;      // --print_label_png f: rows, cols and the labels of f as text (checks the reader)
+
     std::vector<RawImageData> rawImageDataVec;
     std::vector<ImageData> acceptedImageDataVec;
 
@@ -153,6 +168,7 @@ private:
     void run_mesh_surface();                        // --mesh_surface
     int first_img_num = -1, last_img_num = -1;
     bool run3d_reconstruction = true;
+    bool disparity_f64 = false;  // what push_params sets: on around the accumulate call of a plane-fitted batch
     std::vector<std::vector<double>> pose_data, images_times_data;
     std::vector<double> pose_times_seq, images_times_seq;
     std::ofstream log_file;

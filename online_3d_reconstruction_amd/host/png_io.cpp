@@ -1,6 +1,7 @@
 // png_io.cpp — minimal PNG reader (zlib inflate + PNG unfiltering) standing in for the two cv::imread
 // calls on the hot path's input side (pose_functions.cpp:526 colour, :548 IMREAD_GRAYSCALE).
-// 8-bit, non-interlaced, colour types 0/2/3/4/6 — what the reference's bundled data uses.
+// 8-bit, non-interlaced, colour types 0/2/3/4/6 — what the reference's bundled data uses.  read_png_labels reads the
+// segment label images of --use_segment_labels: greyscale, 8 or 16 bits, non-interlaced.
 #include <zlib.h>
 
 #include <cstdio>
@@ -112,6 +113,75 @@ Image8 read_png(const std::string& path, bool grayscale)
             out.data[p * 3 + 2] = r;
         }
     }
+    return out;
+}
+
+// Segment labels: colour type 0 at 8 or 16 bits per sample (big-endian in the file).  A reader of its own: read_png stays
+// what it is.
+Image16 read_png_labels(const std::string& path)
+{
+    Image16 out;
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) return out;
+    std::vector<uint8_t> file;
+    uint8_t buf[1 << 16];
+    size_t n;
+    while ((n = fread(buf, 1, sizeof buf, f)) > 0) file.insert(file.end(), buf, buf + n);
+    fclose(f);
+    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
+    if (file.size() < 33 || memcmp(file.data(), sig, 8) != 0) return out;
+    uint32_t w = 0, h = 0;
+    int depth = 0, ctype = -1, interlace = 0;
+    std::vector<uint8_t> idat;
+    for (size_t pos = 8; pos + 12 <= file.size();) {
+        const uint32_t len = be32(&file[pos]);
+        const uint8_t* type = &file[pos + 4];
+        const uint8_t* data = &file[pos + 8];
+        if (pos + 12 + (size_t)len > file.size()) return out;
+        if (!memcmp(type, "IHDR", 4)) {
+            if (len < 13) return out;
+            w = be32(data);
+            h = be32(data + 4);
+            depth = data[8];
+            ctype = data[9];
+            interlace = data[12];
+        } else if (!memcmp(type, "IDAT", 4)) {
+            idat.insert(idat.end(), data, data + len);
+        } else if (!memcmp(type, "IEND", 4)) {
+            break;
+        }
+        pos += 12 + (size_t)len;
+    }
+    if (!w || !h || w > 65536 || h > 65536 || ctype != 0 || (depth != 8 && depth != 16) || interlace != 0) return out;
+    const size_t bpp = (size_t)depth / 8, stride = (size_t)w * bpp;
+    std::vector<uint8_t> raw((stride + 1) * h);
+    uLongf raw_len = (uLongf)raw.size();
+    if (uncompress(raw.data(), &raw_len, idat.data(), (uLong)idat.size()) != Z_OK || raw_len != raw.size()) return out;
+    std::vector<uint8_t> img(stride * h);
+    for (uint32_t y = 0; y < h; ++y) {
+        const uint8_t ft = raw[(stride + 1) * y];
+        const uint8_t* src = &raw[(stride + 1) * y + 1];
+        uint8_t* cur = &img[stride * y];
+        const uint8_t* up = y ? &img[stride * (y - 1)] : nullptr;
+        for (size_t i = 0; i < stride; ++i) {
+            const int a = i >= bpp ? cur[i - bpp] : 0, b = up ? up[i] : 0, c = (up && i >= bpp) ? up[i - bpp] : 0;
+            int v = src[i];
+            switch (ft) {
+                case 0: break;
+                case 1: v += a; break;
+                case 2: v += b; break;
+                case 3: v += (a + b) >> 1; break;
+                case 4: v += paeth(a, b, c); break;
+                default: return out;
+            }
+            cur[i] = (uint8_t)v;
+        }
+    }
+    out.rows = (int)h;
+    out.cols = (int)w;
+    out.data.resize((size_t)w * h);
+    for (size_t p = 0; p < (size_t)w * h; ++p)
+        out.data[p] = bpp == 2 ? (uint16_t)((img[2 * p] << 8) | img[2 * p + 1]) : (uint16_t)img[p];
     return out;
 }
 

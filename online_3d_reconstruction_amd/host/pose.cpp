@@ -54,6 +54,7 @@ void Pose::push_params(o3dr_ctx* c)
     p.dont_downsample = dont_downsample ? 1 : 0;
     p.sor_enable = sor ? 1 : 0;
     p.blur_kernel = blur_kernel;  // > 1: bilateral filter on the disparity image first (pose_functions.cpp:1040-1047)
+    p.disparity_f64 = disparity_f64 ? 1 : 0;  // --use_segment_labels: the plane-fitted CV_64F image (pose_functions.cpp:1037,1102)
     chk(o3dr_set_params(c, &p), "o3dr_set_params");
     chk(o3dr_set_camera(c, Q.data()), "o3dr_set_camera");
 }
@@ -337,6 +338,12 @@ void Pose::populateData()
                 RawImageData& r = rawImageDataVec[i];
                 r.rgb_image = read_png(imagePrefix + to_string(r.img_num) + ".png", false);       // :523-536
                 r.disparity_image = read_png(disparityPrefix + to_string(r.img_num) + ".png", true);  // :546-585
+                if (use_segment_labels) {
+                    r.label_image = read_png_labels(segmentLabelsPrefix + to_string(r.img_num) + ".png");
+                    if (!r.disparity_image.empty() &&
+                        (r.label_image.rows != r.disparity_image.rows || r.label_image.cols != r.disparity_image.cols))
+                        r.label_image = Image16();  // (a label image of another size is no label image for this frame)
+                }
                 try {
                     const int it = binarySearchImageTime(0, (int)images_times_seq.size() - 1, r.img_num);
                     const int ip = binarySearchUsingTime(pose_times_seq, 0, (int)pose_times_seq.size() - 1, images_times_seq[it]);
@@ -496,7 +503,12 @@ int Pose::parseCmdArgs(int argc, char** argv)
         else if (a == "--search_radius") { search_radius = atof(need(i)); search_radius_set = true; }  // --smooth_surface, --mesh_surface
         else if (a == "--dist_nearby" || a == "--range_width") { need(i); }
         else if (a == "--preview") preview = true;
-        else if (a == "--use_segment_labels" || a == "--segment_cloud" || a == "--displayUAVPositions" ||
+        else if (a == "--use_segment_labels") use_segment_labels = true;
+        else if (a == "--segment_labels_dir") segmentLabelsPrefix = need(i);
+        else if (a == "--plane_min_pixels") plane_min_pixels = atoi(need(i));
+        else if (a == "--plane_max_mse") plane_max_mse = atof(need(i));
+        else if (a == "--print_label_png") { print_label_png = need(i); run3d_reconstruction = false; }
+        else if (a == "--segment_cloud" || a == "--displayUAVPositions" ||
                  a == "--test_bad_data_rejection")
             cout << a << ": outside the hot path, ignored in this build" << endl;
         else if (a.rfind("--", 0) == 0) throw runtime_error("unknown flag " + a);
@@ -504,6 +516,12 @@ int Pose::parseCmdArgs(int argc, char** argv)
             if (first_img_num == -1) first_img_num = atoi(argv[i]); else last_img_num = atoi(argv[i]);
             ++n_imgs;
         }
+    }
+    if (run3d_reconstruction && use_segment_labels) {
+        // the modes that do not take the fitted images say so instead of dropping the flag
+        if (n_gpus > 1 || partitioned_merge) throw runtime_error("--use_segment_labels is not available with --gpus N > 1 / --partitioned_merge");
+        if (reference_fanout) throw runtime_error("--use_segment_labels is not available with --reference_fanout");
+        if (blur_kernel > 1) throw runtime_error("--use_segment_labels cannot be combined with --blur_kernel > 1 (cv::bilateralFilter rejects CV_64F)");
     }
     if (run3d_reconstruction) {
         if (n_imgs == 0) throw runtime_error("first and last image number are required");
@@ -732,6 +750,16 @@ Pose::Pose(int argc, char* argv[])
         run_mesh_surface();
         return;
     }
+    if (!print_label_png.empty()) {  // what read_png_labels makes of one file: "rows cols", then one row of labels per line
+        const Image16 im = read_png_labels(print_label_png);
+        if (im.empty()) throw runtime_error("could not read " + print_label_png + " as an 8- or 16-bit greyscale PNG");
+        cout << im.rows << " " << im.cols << "\n";
+        for (int y = 0; y < im.rows; ++y) {
+            for (int x = 0; x < im.cols; ++x) cout << (x ? " " : "") << im.data[(size_t)y * im.cols + x];
+            cout << "\n";
+        }
+        return;
+    }
     if (!run3d_reconstruction) return;
     populateData();
     if (rows == 0 || cols == 0 || cols_start_aft_cutout == 0)
@@ -766,6 +794,7 @@ void Pose::run_reconstruction()
             RawImageData& r = rawImageDataVec[current_idx];
             if (r.rgb_image.empty()) { cout << r.img_num << " could not read rgb image. \tRejected!" << endl; current_idx++; continue; }
             if (r.disparity_image.empty()) { cout << r.img_num << " could not read disparity image. \tRejected!" << endl; current_idx++; continue; }
+            if (use_segment_labels && r.label_image.empty()) { cout << r.img_num << " could not read segment label image. \tRejected!" << endl; current_idx++; continue; }
             const double var = getVariance(r.disparity_image);
             cout << r.img_num << " " << flush;
             if (var > 5) { cout << " disp_img_var = " << var << " > 5.\tRejected!" << endl; current_idx++; continue; }
@@ -829,10 +858,45 @@ void Pose::run_reconstruction()
             // page-locked frame stacks cross PCIe by DMA (best effort: pageable memory works too)
             const bool reg_disp = o3dr_host_register(disp.data(), (int64_t)disp.size()) == O3DR_OK;
             const bool reg_bgr = o3dr_host_register(bgr.data(), (int64_t)bgr.size()) == O3DR_OK;
-            const int rc_acc = o3dr_accumulate_frames_kp(c, disp.data(), (int64_t)dsz, cols, bgr.data(), (int64_t)csz, 3 * (int64_t)cols, rows,
-                                                         cols, poses.data(), (int32_t)n_acc, kp_xy.empty() ? nullptr : kp_xy.data(),
-                                                         kp_xy.empty() ? nullptr : kp_off.data(), O3DR_MEM_HOST);
-            const string why_acc = rc_acc != O3DR_OK ? o3dr_last_error() : "";
+            // --use_segment_labels: the batch's 8-bit disparities become plane-fitted CV_64F images first
+            vector<double> fitted;
+            int rc_fit = O3DR_OK;
+            string why_fit;
+            if (use_segment_labels) {
+                vector<uint16_t> lab(dsz * n_acc);
+                uint32_t max_label = 0;
+                for (size_t k = 0; k < n_acc; ++k) {
+                    const Image16& li = acceptedImageDataVec[first_accepted + k].raw_img_data_ptr->label_image;
+                    memcpy(&lab[k * dsz], li.data.data(), dsz * sizeof(uint16_t));
+                    for (uint16_t v : li.data) max_label = max<uint32_t>(max_label, v);
+                }
+                fitted.resize(dsz * n_acc);
+                o3dr_plane_disp_params pp;
+                o3dr_plane_disp_default_params(&pp);
+                pp.min_pixels = plane_min_pixels;
+                pp.max_mse = plane_max_mse;
+                const auto tf = clk::now();
+                rc_fit = o3dr_plane_fit_disparity(c, disp.data(), cols, (int64_t)dsz, lab.data(), 2, 2 * (int64_t)cols, 2 * (int64_t)dsz,
+                                                  (int32_t)max_label + 1, rows, cols, (int32_t)n_acc, &pp, fitted.data(), nullptr, nullptr,
+                                                  O3DR_MEM_HOST);
+                if (rc_fit != O3DR_OK) why_fit = o3dr_last_error();
+                cout << "\nplane-fitted disparity: " << n_acc << " frames, " << max_label + 1 << " labels, "
+                     << chrono::duration<double>(clk::now() - tf).count() << " sec" << flush;
+                disparity_f64 = true;
+                push_params(c);
+            }
+            const uint8_t* disp_in = use_segment_labels ? (const uint8_t*)fitted.data() : disp.data();
+            const int64_t esz = use_segment_labels ? 8 : 1;
+            const int rc_acc = rc_fit != O3DR_OK ? rc_fit
+                                                 : o3dr_accumulate_frames_kp(c, disp_in, esz * (int64_t)dsz, esz * cols, bgr.data(), (int64_t)csz,
+                                                                             3 * (int64_t)cols, rows, cols, poses.data(), (int32_t)n_acc,
+                                                                             kp_xy.empty() ? nullptr : kp_xy.data(),
+                                                                             kp_xy.empty() ? nullptr : kp_off.data(), O3DR_MEM_HOST);
+            const string why_acc = rc_fit != O3DR_OK ? "plane_fit_disparity: " + why_fit : (rc_acc != O3DR_OK ? o3dr_last_error() : "");
+            if (use_segment_labels) {
+                disparity_f64 = false;
+                push_params(c);
+            }
             if (reg_disp) (void)o3dr_host_unregister(disp.data());  // (only what was registered; also on the error path)
             if (reg_bgr) (void)o3dr_host_unregister(bgr.data());
             if (rc_acc != O3DR_OK) throw runtime_error("accumulate_frames: " + why_acc);
