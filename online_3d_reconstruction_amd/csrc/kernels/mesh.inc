@@ -3,9 +3,10 @@
 
 // =================================================================================================
 // Height-field surface mesh (o3dr_mesh_surface; contract: include/o3dr.h, DESIGN.md "Surface mesh")
-//   Cells: the dense cell id (cy - cy_min) * wx + (cx - cx_min) of every point is radix-sorted (stable: the lowest input
-//   index first inside a cell), so cells come in (cy, cx) order.  k_mesh_heads flags the first point of every cell; their
-//   scan numbers the vertices (vertex ordinals, in cell order) and k_mesh_vertices gathers them (key, x y z + input index).
+//   Cells: the cloud's cell order (kernels/cell_order.inc) with MeshCell as the index rule: cells in (cy, cx) order, the
+//   lowest input index first inside a cell.  The first point of every cell is its vertex, the cell ordinals are the
+//   vertex ordinals, and k_mesh_vertices gathers them (key = the dense cell id (cy - cy_min) * wx + (cx - cx_min),
+//   x y z + input index).
 //   Neighbours: the left and right cells are the adjacent ordinals when their keys are; the three cells of the row above
 //   (ul, u, ur) are consecutive keys, found by one binary search; the row below (normals only) likewise.
 //   A quad belongs to its first present corner in a, b, c, d order, so to `a` or, when `a` is empty, to `b`: a vertex owns
@@ -13,9 +14,9 @@
 //   ascending (cy, cx): k_mesh_count counts every vertex's kept triangles, an exclusive scan gives the offsets and
 //   k_mesh_emit writes them, recomputing the same quads (mesh_quad is the one place that decides a quad).
 //   k_mesh_normals gathers the up to four quads around every vertex.  All counts are integer sums: per-workgroup partials
-//   folded by one workgroup (k_mesh_fold), no atomics.
+//   folded by one workgroup (k_fold4_u32), no atomics.
 // =================================================================================================
-constexpr int kMeshThreads = 256;
+constexpr int kMeshThreads = kFoldThreads;  // (block_reduce4_u32)
 
 // orient(p, q, r) of the contract: fp64 from the fp32 coordinates, no FMA (the file is built with -ffp-contract=off)
 __device__ __forceinline__ double mesh_orient(const float4& p, const float4& q, const float4& r)
@@ -79,104 +80,36 @@ __device__ __forceinline__ uint32_t mesh_lower_bound(const uint32_t* __restrict_
 __device__ __forceinline__ void mesh_row3(const MeshArgs& a, uint64_t row, uint64_t dx, uint32_t lo, uint32_t hi, int32_t out[3])
 {
     out[0] = out[1] = out[2] = -1;
-    const uint64_t base = row * a.wx + dx;  // the key of cell dx of that row
-    const uint64_t first = dx > 0 ? base - 1 : base, last = dx + 1 < a.wx ? base + 1 : base;
+    const uint64_t base = row * a.cells.wx + dx;  // the key of cell dx of that row
+    const uint64_t first = dx > 0 ? base - 1 : base, last = dx + 1 < a.cells.wx ? base + 1 : base;
     uint32_t j = mesh_lower_bound(a.vkey, lo, hi, first);
     for (; j < hi && (uint64_t)a.vkey[j] <= last; ++j) out[(int)((uint64_t)a.vkey[j] + 1 - base)] = (int32_t)j;
 }
 
 // ---- cells ---------------------------------------------------------------------------------------
-// Whole-cloud reductions go through per-workgroup partials (kMeshPart words each) and a one-workgroup fold: one atomic
-// per wave on the same few words serialises in L2 and cost ~0.3 ms per kernel at 453k points.
-constexpr int kMeshPart = kMeshPartWords;
-constexpr int kMeshWaves = kMeshThreads / kWave;
-// the four values of every thread reduced over the workgroup (op: 0 min, 1 max, 2 sum per word), written by thread 0
-__device__ __forceinline__ void mesh_block_reduce(uint32_t v[4], const int op[4], uint32_t* __restrict__ out)
-{
-    __shared__ uint32_t lds[kMeshWaves][4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = op[k] == 0 ? wave_min_u32(v[k]) : op[k] == 1 ? wave_max_u32(v[k]) : wave_sum_u32(v[k]);
-    if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < 4; ++k) lds[threadIdx.x >> 6][k] = v[k];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kMeshWaves; ++w)
-            for (int k = 0; k < 4; ++k) {
-                const uint32_t u = lds[w][k];
-                v[k] = op[k] == 0 ? u32_min(v[k], u) : op[k] == 1 ? u32_max(v[k], u) : v[k] + u;
-            }
-        for (int k = 0; k < 4; ++k) out[k] = v[k];
-    }
-    __syncthreads();  // (lds is reused by the next call)
-}
-
-// per workgroup: the cell index range (order-preserving, x ^ 0x80000000) and whether an index leaves int32
-__global__ __launch_bounds__(kMeshThreads) void k_mesh_range(const o3dr_point* __restrict__ in, int64_t n, float inv,
-                                                             uint32_t* __restrict__ part)
-{
-    uint32_t v[4] = {0xffffffffu, 0u, 0xffffffffu, 0u};
-    uint32_t bad = 0u;
-    for (int64_t i = (int64_t)blockIdx.x * kMeshThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kMeshThreads) {
-        const float4 p = reinterpret_cast<const float4*>(in)[i];
+// the contract's cell index floorf(x * inv) with inv = 1.0f / (float)cell_size, in fp32 (the cell functor of
+// kernels/cell_order.inc)
+struct MeshCell {
+    float inv;
+    __device__ __forceinline__ bool operator()(const float4& p, int32_t& ix, int32_t& iy) const
+    {
         const float fx = floorf(p.x * inv), fy = floorf(p.y * inv);
-        if (!(fx >= -2147483648.f && fx < 2147483648.f && fy >= -2147483648.f && fy < 2147483648.f)) {
-            bad = 1u;
-            continue;
-        }
-        const uint32_t ux = (uint32_t)(int32_t)fx ^ 0x80000000u, uy = (uint32_t)(int32_t)fy ^ 0x80000000u;
-        v[0] = u32_min(v[0], ux), v[1] = u32_max(v[1], ux);
-        v[2] = u32_min(v[2], uy), v[3] = u32_max(v[3], uy);
+        if (!(fx >= -2147483648.f && fx < 2147483648.f && fy >= -2147483648.f && fy < 2147483648.f)) return false;
+        ix = (int32_t)fx, iy = (int32_t)fy;
+        return true;
     }
-    const int op[4] = {0, 1, 0, 1};
-    uint32_t* out = part + (int64_t)blockIdx.x * kMeshPart;
-    mesh_block_reduce(v, op, out);
-    uint32_t b[4] = {bad, 0u, 0u, 0u};
-    const int opb[4] = {1, 1, 1, 1};
-    mesh_block_reduce(b, opb, out + 4);
-}
-// one workgroup: the partials of `blocks` workgroups folded (word-wise op) into out[0..3]
-__global__ __launch_bounds__(kMeshThreads) void k_mesh_fold(const uint32_t* __restrict__ part, int blocks, int word0, int op0,
-                                                            int op1, int op2, int op3, uint32_t* __restrict__ out)
-{
-    const int op[4] = {op0, op1, op2, op3};
-    uint32_t v[4];
-    for (int k = 0; k < 4; ++k) v[k] = op[k] == 0 ? 0xffffffffu : 0u;
-    for (int b = threadIdx.x; b < blocks; b += kMeshThreads)
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t u = part[(int64_t)b * kMeshPart + word0 + k];
-            v[k] = op[k] == 0 ? u32_min(v[k], u) : op[k] == 1 ? u32_max(v[k], u) : v[k] + u;
-        }
-    mesh_block_reduce(v, op, out);
-}
+};
+static inline MeshCell cell_of(const MeshArgs& a) { return MeshCell{a.inv}; }
 
-// the dense cell id of every point: the sort key (it fits 32 bits: wx * wy <= 2^32)
-__global__ __launch_bounds__(kMeshThreads) void k_mesh_keys(MeshArgs a, uint32_t* __restrict__ keys)
-{
-    const int64_t i = (int64_t)blockIdx.x * kMeshThreads + threadIdx.x;
-    if (i >= (int64_t)a.n) return;
-    const float4 p = reinterpret_cast<const float4*>(a.cloud)[i];
-    const int32_t cx = (int32_t)floorf(p.x * a.inv), cy = (int32_t)floorf(p.y * a.inv);
-    const uint64_t dx = (uint64_t)((int64_t)cx - a.cx0), dy = (uint64_t)((int64_t)cy - a.cy0);
-    keys[i] = (uint32_t)(dy * a.wx + dx);
-}
-
-// after the sort: 1 for the first point of every cell (the cell's vertex), 0 for the shadowed ones
-__global__ __launch_bounds__(kMeshThreads) void k_mesh_heads(MeshArgs a, uint32_t* __restrict__ head)
-{
-    const int64_t i = (int64_t)blockIdx.x * kMeshThreads + threadIdx.x;
-    if (i >= (int64_t)a.n) return;
-    head[i] = (i == 0 || a.keys[i - 1] != a.keys[i]) ? 1u : 0u;
-}
-
-// the vertices in cell order (a.ord: the scanned heads): key, and x y z with the input index in .w
+// the vertices in cell order (the first point of every cell, at its ordinal): key, and x y z with the input index in .w
 __global__ __launch_bounds__(kMeshThreads) void k_mesh_vertices(MeshArgs a)
 {
     const int64_t i = (int64_t)blockIdx.x * kMeshThreads + threadIdx.x;
     if (i >= (int64_t)a.n) return;
-    if (i != 0 && a.keys[i - 1] == a.keys[i]) return;
-    const uint32_t o = a.ord[i], idx = a.perm[i];
+    if (!cell_head(a.cells, i)) return;
+    const uint32_t o = a.cells.ord[i], idx = a.cells.perm[i];
     const float4 p = reinterpret_cast<const float4*>(a.cloud)[idx];
-    a.vkey[o] = a.keys[i];
+    a.vkey[o] = a.cells.keys[i];
     a.vpt[o] = make_float4(p.x, p.y, p.z, __uint_as_float(idx));
 }
 
@@ -185,11 +118,11 @@ __global__ __launch_bounds__(kMeshThreads) void k_mesh_vertices(MeshArgs a)
 __device__ __forceinline__ void mesh_owned(const MeshArgs& a, uint32_t o, uint32_t V, int32_t left_quad[4], int32_t own_quad[4],
                                            int4& nbr)
 {
-    const uint64_t key = a.vkey[o], dx = key % a.wx, dy = key / a.wx;
+    const uint64_t key = a.vkey[o], dx = key % a.cells.wx, dy = key / a.cells.wx;
     const bool has_left = dx > 0 && o > 0 && (uint64_t)a.vkey[o - 1] + 1 == key;
-    const int32_t right = (dx + 1 < a.wx && o + 1 < V && (uint64_t)a.vkey[o + 1] == key + 1) ? (int32_t)(o + 1) : -1;
+    const int32_t right = (dx + 1 < a.cells.wx && o + 1 < V && (uint64_t)a.vkey[o + 1] == key + 1) ? (int32_t)(o + 1) : -1;
     int32_t up[3] = {-1, -1, -1};
-    if (dy + 1 < a.wy) mesh_row3(a, dy + 1, dx, o + 1, V, up);
+    if (dy + 1 < a.cells.wy) mesh_row3(a, dy + 1, dx, o + 1, V, up);
     nbr = make_int4(right, up[2], up[1], up[0]);
     left_quad[0] = -1, left_quad[1] = has_left ? -1 : (int32_t)o, left_quad[2] = up[1], left_quad[3] = up[0];
     own_quad[0] = (int32_t)o, own_quad[1] = right, own_quad[2] = up[2], own_quad[3] = up[1];
@@ -200,7 +133,7 @@ __device__ __forceinline__ void mesh_owned(const MeshArgs& a, uint32_t o, uint32
 __global__ __launch_bounds__(kMeshThreads) void k_mesh_count(MeshArgs a)
 {
     const int64_t i = (int64_t)blockIdx.x * kMeshThreads + threadIdx.x;
-    const uint32_t V = *a.n_vert;
+    const uint32_t V = *a.cells.n_runs;
     uint32_t kept = 0, full = 0, rej_o = 0, rej_l = 0;
     if (i < (int64_t)V) {
         int32_t q[2][4];
@@ -218,18 +151,18 @@ __global__ __launch_bounds__(kMeshThreads) void k_mesh_count(MeshArgs a)
     if (i < (int64_t)a.n) a.cnt[i] = kept;
     uint32_t v[4] = {full, rej_o, rej_l, 0u};
     const int op[4] = {2, 2, 2, 2};
-    mesh_block_reduce(v, op, a.part + (int64_t)blockIdx.x * kMeshPart);
+    block_reduce4_u32(v, op, a.part + (int64_t)blockIdx.x * kPartWords);
 }
 
 // per vertex: its kept triangles at its scanned offset, as input indices
 __global__ __launch_bounds__(kMeshThreads) void k_mesh_emit(MeshArgs a)
 {
     const int64_t i = (int64_t)blockIdx.x * kMeshThreads + threadIdx.x;
-    const uint32_t V = *a.n_vert;
+    const uint32_t V = *a.cells.n_runs;
     if (i >= (int64_t)V) return;
     const int4 nbr = a.nbr[i];
     const uint64_t key = a.vkey[i];
-    const bool has_left = key % a.wx > 0 && i > 0 && (uint64_t)a.vkey[i - 1] + 1 == key;
+    const bool has_left = key % a.cells.wx > 0 && i > 0 && (uint64_t)a.vkey[i - 1] + 1 == key;
     const int32_t q[2][4] = {{-1, has_left ? -1 : (int32_t)i, nbr.z, nbr.w}, {(int32_t)i, nbr.x, nbr.y, nbr.z}};
     int64_t at = (int64_t)a.cnt[i] * 3;
     for (int k = 0; k < 2; ++k) {
@@ -252,16 +185,16 @@ __global__ __launch_bounds__(kMeshThreads) void k_mesh_normals(MeshArgs a)
 {
     const int64_t i = (int64_t)blockIdx.x * kMeshThreads + threadIdx.x;
     if (i >= (int64_t)a.n) return;
-    const uint32_t idx = a.perm[i];
+    const uint32_t idx = a.cells.perm[i];
     float* dst = a.normals + (int64_t)idx * 3;
     const float nan = __builtin_nanf("");
-    if (i != 0 && a.keys[i - 1] == a.keys[i]) {
+    if (!cell_head(a.cells, i)) {
         dst[0] = nan, dst[1] = nan, dst[2] = nan;
         return;
     }
-    const uint32_t o = a.ord[i];
+    const uint32_t o = a.cells.ord[i];
     const int4 nbr = a.nbr[o];
-    const uint64_t key = a.vkey[o], dx = key % a.wx, dy = key / a.wx;
+    const uint64_t key = a.vkey[o], dx = key % a.cells.wx, dy = key / a.cells.wx;
     const int32_t left = (dx > 0 && o > 0 && (uint64_t)a.vkey[o - 1] + 1 == key) ? (int32_t)(o - 1) : -1;
     int32_t down[3] = {-1, -1, -1};
     if (dy > 0) mesh_row3(a, dy - 1, dx, 0, o, down);

@@ -34,17 +34,6 @@ struct MlsArgs {
     unsigned long long* counters;  // n_none, n_plane, n_poly, max k
 };
 
-__device__ __forceinline__ int mls_col(const SorGeom& g, float x)
-{
-    int cx = (int)((x - g.mnx) * g.inv_h);
-    return cx < 0 ? 0 : (cx >= g.gx ? g.gx - 1 : cx);
-}
-__device__ __forceinline__ int mls_row(const SorGeom& g, float y)
-{
-    int cy = (int)((y - g.mny) * g.inv_h);
-    return cy < 0 ? 0 : (cy >= g.gy ? g.gy - 1 : cy);
-}
-
 // f(p, d2) for every point p of the cloud with the fp32 d2 <= r2, in the fixed order of the contract
 template <class F>
 __device__ __forceinline__ void mls_walk(const MlsArgs& a, const SorGeom& g, int x0, int x1, int y0, int y1, float qx, float qy,
@@ -55,11 +44,7 @@ __device__ __forceinline__ void mls_walk(const MlsArgs& a, const SorGeom& g, int
         for (int xx = x0; xx <= x1; ++xx) {
             const int64_t c = row + xx;
             const float4 lo = a.cell_lo[c], hi = a.cell_hi[c];
-            const float gx = fmaxf(fmaxf(lo.x - qx, qx - hi.x), 0.f);
-            const float gy = fmaxf(fmaxf(lo.y - qy, qy - hi.y), 0.f);
-            const float gz = fmaxf(fmaxf(lo.z - qz, qz - hi.z), 0.f);
-            const float lb = (gx * gx + gy * gy) + gz * gz;  // <= the computed d2 of every point of the cell
-            if (!(lb <= a.r2)) continue;
+            if (!(cell_box_d2_lower_bound(lo, hi, qx, qy, qz) <= a.r2)) continue;
             const uint32_t s = a.cell_first[c], e = a.cell_first[c + 1];
             for (uint32_t j = s; j < e; ++j) {
                 const float4 p = a.sxyz[j];
@@ -85,7 +70,7 @@ __global__ __launch_bounds__(kMlsThreads) void k_mls(MlsArgs a)
         // the window: the cells of the query's box, through the monotone cell assignment of the points
         const float x0f = fmaxf(q.x - a.pad_r, a.box6[0]), x1f = fminf(q.x + a.pad_r, a.box6[3]);
         const float y0f = fmaxf(q.y - a.pad_r, a.box6[1]), y1f = fminf(q.y + a.pad_r, a.box6[4]);
-        const int x0 = mls_col(g, x0f), x1 = mls_col(g, x1f), y0 = mls_row(g, y0f), y1 = mls_row(g, y1f);
+        const int x0 = sor_col(g, x0f), x1 = sor_col(g, x1f), y0 = sor_row(g, y0f), y1 = sor_row(g, y1f);
         // pass 1: k and the moments about the query
         double s1[3] = {0.0, 0.0, 0.0}, s2[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         mls_walk(a, g, x0, x1, y0, y1, q.x, q.y, q.z, [&](const float4& p, float) {
@@ -249,12 +234,3 @@ __global__ __launch_bounds__(kMlsThreads) void k_mls(MlsArgs a)
     }
 }
 static_assert(kMlsThreads % kWave == 0, "the counters are folded per wave");
-
-// 1 in flag[0] if any coordinate of the n points is not finite (every writer stores the same value)
-__global__ __launch_bounds__(256) void k_mls_finite(const o3dr_point* __restrict__ in, int64_t n, uint32_t* __restrict__ flag)
-{
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const float4 p = reinterpret_cast<const float4*>(in)[i];
-        if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) flag[0] = 1u;
-    }
-}

@@ -67,10 +67,7 @@ __device__ __forceinline__ void nn_visit(const NnArgs& a, int64_t c, float qx, f
 {
     const float bd = best != ~0ull ? __uint_as_float((uint32_t)(best >> 32)) : __builtin_huge_valf();
     const float4 lo = a.cell_lo[c], hi = a.cell_hi[c];
-    const float gx = fmaxf(fmaxf(lo.x - qx, qx - hi.x), 0.f);
-    const float gy = fmaxf(fmaxf(lo.y - qy, qy - hi.y), 0.f);
-    const float gz = fmaxf(fmaxf(lo.z - qz, qz - hi.z), 0.f);
-    const float lb = (gx * gx + gy * gy) + gz * gz;  // <= the computed d2 of every point of the cell (monotone roundings)
+    const float lb = cell_box_d2_lower_bound(lo, hi, qx, qy, qz);
     if (!(lb <= bd && lb <= r2)) return;
     const uint32_t s = a.cell_first[c], e = a.cell_first[c + 1];
     for (uint32_t j = s; j < e; ++j) {

@@ -3,9 +3,9 @@
 
 // =================================================================================================
 // RANSAC plane segmentation per XY tile (o3dr_segment_plane; contract: include/o3dr.h, DESIGN.md "Plane segmentation")
-//   Tiles: the dense tile id of every point is radix-sorted (stable: input order inside a tile), the run heads are scanned
-//   into tile ordinals and the points gathered into tile order (x y z, original index in .w).  With tile_size 0 the cloud
-//   is one tile and the cloud itself is read in place.  Every tile is cut into CHUNKS of kPlaneChunk consecutive points
+//   Tiles: the cloud's cell order (kernels/cell_order.inc) with PlaneCell as the index rule: tiles in (iy, ix) order, input
+//   order inside a tile; the points are gathered into it (x y z, original index in .w).  With tile_size 0 the cloud is
+//   one tile and the cloud itself is read in place.  Every tile is cut into CHUNKS of kPlaneChunk consecutive points
 //   (the last one partial); one wave owns one chunk, two points per lane (lane j: points j and 64 + j of the chunk).
 //   k_plane_sample: one lane per (tile, hypothesis): the three draws and the fp64 plane, rounded to fp32 (NaN: degenerate).
 //   k_plane_score: a wave keeps its chunk in registers and walks its tile's H hypotheses, whose coefficients are uniform
@@ -93,62 +93,29 @@ __device__ __forceinline__ f32x2_t plane_dist2(const float4& c, f32x2_t X, f32x2
 }
 
 // ---- tiles ----------------------------------------------------------------------------------------
-// the tile index range (and 1 in flag[1] if an index leaves int32); one integer atomic per wave and bound
-__global__ __launch_bounds__(256) void k_plane_range(const o3dr_point* __restrict__ in, int64_t n, double s, int32_t* __restrict__ range,
-                                                     uint32_t* __restrict__ flag)
-{
-    uint32_t lo_x = 0xffffffffu, hi_x = 0u, lo_y = 0xffffffffu, hi_y = 0u;
-    bool bad = false;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const float4 p = reinterpret_cast<const float4*>(in)[i];
+// the contract's tile index floor((double)x / s), in double (the cell functor of kernels/cell_order.inc)
+struct PlaneCell {
+    double s;
+    __device__ __forceinline__ bool operator()(const float4& p, int32_t& ix, int32_t& iy) const
+    {
         const double fx = floor((double)p.x / s), fy = floor((double)p.y / s);
-        if (!(fx >= -2147483648.0 && fx <= 2147483647.0 && fy >= -2147483648.0 && fy <= 2147483647.0)) {
-            bad = true;
-            continue;
-        }
-        const uint32_t ux = (uint32_t)(int32_t)fx ^ 0x80000000u, uy = (uint32_t)(int32_t)fy ^ 0x80000000u;  // order-preserving
-        lo_x = ux < lo_x ? ux : lo_x, hi_x = ux > hi_x ? ux : hi_x;
-        lo_y = uy < lo_y ? uy : lo_y, hi_y = uy > hi_y ? uy : hi_y;
+        if (!(fx >= -2147483648.0 && fx <= 2147483647.0 && fy >= -2147483648.0 && fy <= 2147483647.0)) return false;
+        ix = (int32_t)fx, iy = (int32_t)fy;
+        return true;
     }
-    lo_x = wave_min_u32(lo_x), hi_x = wave_max_u32(hi_x), lo_y = wave_min_u32(lo_y), hi_y = wave_max_u32(hi_y);
-    const bool any_bad = __ballot(bad) != 0ull;
-    if ((threadIdx.x & 63) == 0) {
-        if (lo_x <= hi_x) {
-            atomicMin(reinterpret_cast<uint32_t*>(range) + 0, lo_x);
-            atomicMax(reinterpret_cast<uint32_t*>(range) + 1, hi_x);
-            atomicMin(reinterpret_cast<uint32_t*>(range) + 2, lo_y);
-            atomicMax(reinterpret_cast<uint32_t*>(range) + 3, hi_y);
-        }
-        if (any_bad) flag[1] = 1u;
-    }
-}
-// (the range is kept order-preserving, x ^ 0x80000000, until the host reads it)
-__device__ __forceinline__ int32_t plane_range_at(const int32_t* range, int k) { return (int32_t)((uint32_t)range[k] ^ 0x80000000u); }
+};
+static inline PlaneCell cell_of(const PlaneArgs& a) { return PlaneCell{a.s}; }
 
-// the dense tile id (iy - iy_min) * wx + (ix - ix_min) of every point: the sort key
-__global__ __launch_bounds__(256) void k_plane_keys(PlaneArgs a, uint32_t* __restrict__ keys)
+// the points gathered into tile order: x y z, the input index in .w
+__global__ __launch_bounds__(256) void k_plane_gather(PlaneArgs a, float4* __restrict__ pts)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (int64_t)a.n) return;
-    const float4 p = reinterpret_cast<const float4*>(a.cloud)[i];
-    const int32_t ix = (int32_t)floor((double)p.x / a.s), iy = (int32_t)floor((double)p.y / a.s);
-    const uint32_t dx = (uint32_t)ix - (uint32_t)plane_range_at(a.range, 0), dy = (uint32_t)iy - (uint32_t)plane_range_at(a.range, 2);
-    keys[i] = dy * a.wx + dx;
-}
-__global__ void k_plane_sort_geom(VoxelGeom* geom, VoxelGeom g) { *geom = g; }
-
-// after the sort: run heads (1 per tile) and the points gathered into tile order
-__global__ __launch_bounds__(256) void k_plane_heads(PlaneArgs a, const uint32_t* __restrict__ perm, uint32_t* __restrict__ head,
-                                                     float4* __restrict__ pts)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)a.n) return;
-    head[i] = (i == 0 || a.keys[i - 1] != a.keys[i]) ? 1u : 0u;
-    const uint32_t idx = perm[i];
+    const uint32_t idx = a.cells.perm[i];
     const float4 p = reinterpret_cast<const float4*>(a.cloud)[idx];
     pts[i] = make_float4(p.x, p.y, p.z, __uint_as_float(idx));
 }
-// tile starts and indices from the scanned heads (tiled), or the one tile of the whole cloud
+// tile starts and indices from the cell order (tiled), or the one tile of the whole cloud
 __global__ __launch_bounds__(256) void k_plane_tiles(PlaneArgs a)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -161,12 +128,12 @@ __global__ __launch_bounds__(256) void k_plane_tiles(PlaneArgs a)
     }
     if (i >= (int64_t)a.n) return;
     if (i == 0) a.tstart[a.n_tiles] = a.n;
-    if (i != 0 && a.keys[i - 1] == a.keys[i]) return;
-    const uint32_t t = a.tile_excl[i];
+    if (!cell_head(a.cells, i)) return;
+    const uint32_t t = a.cells.ord[i];
     a.tstart[t] = (uint32_t)i;
-    const uint32_t key = a.keys[i];
-    a.rec[t].ix = (int32_t)((uint32_t)plane_range_at(a.range, 0) + key % a.wx);
-    a.rec[t].iy = (int32_t)((uint32_t)plane_range_at(a.range, 2) + key / a.wx);
+    const uint32_t key = a.cells.keys[i], wx = (uint32_t)a.cells.wx;  // (at most 2^32-1 tiles: wx fits)
+    a.rec[t].ix = (int32_t)((uint32_t)a.cells.x0 + key % wx);
+    a.rec[t].iy = (int32_t)((uint32_t)a.cells.y0 + key / wx);
 }
 // per tile: its chunk count (-> cfirst by an exclusive scan) and the record's defaults
 __global__ __launch_bounds__(256) void k_plane_chunks(PlaneArgs a)

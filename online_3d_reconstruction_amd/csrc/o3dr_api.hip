@@ -2972,7 +2972,7 @@ static int cloud_stage_finite(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, i
     const void* d;
     CHK(stage_in(c, c->nn_t, cloud, (size_t)n * sizeof(o3dr_point), mem, &d));
     *cloud_d = (const o3dr_point*)d;
-    launch_mls_finite(&c->prof, c->stream, *cloud_d, n, flag);
+    launch_cloud_finite(&c->prof, c->stream, *cloud_d, n, flag);
     CHK(also());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(flag_h, flag, flag_bytes, hipMemcpyDeviceToHost, c->stream));
@@ -2986,17 +2986,36 @@ struct MlsFlags {
     alignas(64) unsigned long long counters[4];  // none, plane, poly, max neighbours
     alignas(64) uint32_t bad;                    // non-finite
 };
+// the non-finite flag and the cell index range (launch_cell_range), read back together
+struct CellFlags {
+    uint32_t bad;           // non-finite
+    uint32_t range[4];      // ix_min ix_max iy_min iy_max (order-preserving)
+    uint32_t off_int32[4];  // [0]: an index leaves int32 (the fold writes four words)
+};
 struct PlaneFlags {
-    alignas(64) uint32_t flag[2];  // [0] non-finite, [1] tile index out of int32
-    alignas(64) int32_t range[4];  // ix_min ix_max iy_min iy_max (order-preserving)
+    alignas(64) CellFlags cell;
     alignas(64) uint32_t n_tiles;
 };
 struct MeshFlags {
-    alignas(64) uint32_t bad;          // non-finite
-    alignas(64) uint32_t range[5];     // cx_min cx_max cy_min cy_max (order-preserving), [4] out of int32
+    alignas(64) CellFlags cell;
     alignas(64) uint32_t cnt[2];       // V, T
     alignas(64) uint32_t counters[3];  // full quads, rejected by orientation, rejected by length
 };
+// The index box of a read-back range: its corner and widths -> o, the width of the largest dense cell id -> *nbits.
+// Fails, with the operator's texts, if an index left int32 or the box holds more than `limit` cells.
+static int cell_box(const CellFlags& h, uint64_t limit, const char* off_int32_text, const char* limit_text, CellOrder* o, int* nbits)
+{
+    if (h.off_int32[0]) return fail(O3DR_ERR_INVALID_ARG, off_int32_text);
+    o->x0 = (int32_t)(h.range[0] ^ 0x80000000u);
+    o->y0 = (int32_t)(h.range[2] ^ 0x80000000u);
+    o->wx = (uint64_t)(h.range[1] - h.range[0]) + 1;
+    o->wy = (uint64_t)(h.range[3] - h.range[2]) + 1;
+    if (o->wx > limit / o->wy) return fail(O3DR_ERR_INVALID_ARG, limit_text);
+    const uint64_t max_key = o->wx * o->wy - 1;
+    *nbits = 0;
+    while (*nbits < 32 && (max_key >> *nbits) != 0) ++*nbits;
+    return O3DR_OK;
+}
 template <class Flags>
 static int op_flags(o3dr_ctx* c, Flags** f)
 {
@@ -3320,43 +3339,35 @@ static int segment_plane(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const 
     const bool tiled = ts > 0.0;
     PlaneFlags* f;
     CHK(op_flags(c, &f));
-    const o3dr_point* cloud_d;
-    uint32_t hbuf[6];  // the two flags, then the range
-    CHK(cloud_stage_finite(c, cloud, n, mem, f->flag, hbuf, 8, &cloud_d, [&]() -> int {
-        if (!tiled) return O3DR_OK;
-        launch_plane_range(&c->prof, c->stream, cloud_d, n, ts, f->range, f->flag);
-        HIPCHK(hipMemcpyAsync(hbuf + 2, f->range, 16, hipMemcpyDeviceToHost, c->stream));
-        return O3DR_OK;
-    }));
-    if (tiled && hbuf[1]) return fail(O3DR_ERR_INVALID_ARG, "a tile index does not fit in int32 (tile_size too small)");
-
     PlaneArgs a;
     memset(&a, 0, sizeof a);
-    a.cloud = cloud_d;
-    a.pts = (const float4*)cloud_d;
     a.tiled = tiled ? 1 : 0;
     a.n = (uint32_t)n;
     a.H = (uint32_t)p->max_iterations;
     a.s = ts;
     a.tf = (float)t;
     a.seed = p->seed;
-    a.range = f->range;
-    uint64_t T = 1;
-    if (tiled) {
-        const uint64_t wx = (uint64_t)(hbuf[3] - hbuf[2]) + 1, wy = (uint64_t)(hbuf[5] - hbuf[4]) + 1;
-        if (wx * wy > 0xffffffffull) return fail(O3DR_ERR_INVALID_ARG, "the tiles' index box holds more than 2^32-1 tiles");
-        a.wx = (uint32_t)wx;
-        const uint64_t max_key = wx * wy - 1;
-        int nbits = 0;
-        while (nbits < 32 && (max_key >> nbits) != 0) ++nbits;
-        CHK(ws_ensure(c, 1, n, false));
-        float4* pts;
-        uint32_t* head;
+    float4* pts = nullptr;
+    uint32_t *head = nullptr, *part = nullptr;
+    if (tiled)
         CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
             w.take(pts, (size_t)n);
             w.take(head, (size_t)n);
+            w.take(part, (size_t)cell_range_parts(n) * kPartWords);
         }));
-        launch_plane_order(&c->prof, c->stream, c->ws, a, nbits, head, pts, &f->n_tiles);
+    CellFlags h;
+    CHK(cloud_stage_finite(c, cloud, n, mem, &f->cell.bad, &h.bad, tiled ? sizeof h : 4, &a.cloud, [&]() -> int {
+        if (tiled) launch_cell_range(&c->prof, c->stream, a, part, f->cell.range);
+        return O3DR_OK;
+    }));
+    a.pts = tiled ? pts : (const float4*)a.cloud;
+    uint64_t T = 1;
+    if (tiled) {
+        int nbits;
+        CHK(cell_box(h, 0xffffffffull, "a tile index does not fit in int32 (tile_size too small)",
+                     "the tiles' index box holds more than 2^32-1 tiles", &a.cells, &nbits));
+        CHK(ws_ensure(c, 1, n, false));
+        launch_cell_order(&c->prof, c->stream, c->ws, a, nbits, head, &f->n_tiles);
         HIPCHK(hipGetLastError());
         uint32_t th = 0;
         HIPCHK(hipMemcpyAsync(&th, &f->n_tiles, 4, hipMemcpyDeviceToHost, c->stream));
@@ -3381,7 +3392,7 @@ static int segment_plane(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const 
     a.tile = outs.dev(tile);
     a.projected = outs.dev(projected);
     c->pl_last_hyp = 0;
-    launch_plane_tiles(&c->prof, c->stream, c->ws, a);
+    launch_plane_tiles(&c->prof, c->stream, c->ws, a, pts);
     launch_plane_fit(&c->prof, c->stream, a, max_chunks, p->optimize);
     HIPCHK(hipGetLastError());
     const hipMemcpyKind back = mem == O3DR_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
@@ -3465,38 +3476,29 @@ static int mesh_surface(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const o
         w.take(a.vkey, (size_t)n);
         w.take(a.vpt, (size_t)n);
         w.take(a.nbr, (size_t)n);
-        w.take(a.part, (size_t)((n + 255) / 256) * kMeshPartWords);  // one record per 256-thread workgroup
+        w.take(a.part, (size_t)((n + 255) / 256) * kPartWords);  // one record per 256-thread workgroup
     }));
-    uint32_t hbuf[6];
-    CHK(cloud_stage_finite(c, cloud, n, mem, &f->bad, hbuf, 4, &a.cloud, nothing_else));
-    launch_mesh_range(&c->prof, c->stream, a.cloud, n, inv, a.part, f->range);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(hbuf + 1, f->range, 20, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (hbuf[5]) return fail(O3DR_ERR_INVALID_ARG, "a cell index does not fit in int32 (cell_size too small)");
-
     a.n = (uint32_t)n;
     a.inv = inv;
     a.lf = (float)(L * L);
-    a.cx0 = (int32_t)(hbuf[1] ^ 0x80000000u);
-    a.cy0 = (int32_t)(hbuf[3] ^ 0x80000000u);
-    a.wx = (uint64_t)(hbuf[2] - hbuf[1]) + 1;
-    a.wy = (uint64_t)(hbuf[4] - hbuf[3]) + 1;
-    if (a.wx > (1ull << 32) / a.wy) return fail(O3DR_ERR_INVALID_ARG, "the cells' index box holds more than 2^32 cells");
-    const uint64_t max_key = a.wx * a.wy - 1;
-    int nbits = 0;
-    while (nbits < 32 && (max_key >> nbits) != 0) ++nbits;
+    CellFlags h;
+    CHK(cloud_stage_finite(c, cloud, n, mem, &f->cell.bad, &h.bad, sizeof h, &a.cloud, [&]() -> int {
+        launch_cell_range(&c->prof, c->stream, a, a.part, f->cell.range);
+        return O3DR_OK;
+    }));
+    int nbits;
+    CHK(cell_box(h, 1ull << 32, "a cell index does not fit in int32 (cell_size too small)",
+                 "the cells' index box holds more than 2^32 cells", &a.cells, &nbits));
     CHK(ws_ensure(c, 1, n, false));
-    a.n_vert = &f->cnt[0];
     a.counters = f->counters;
-    launch_mesh_cells(&c->prof, c->stream, c->ws, a, nbits, head, &f->cnt[0]);
+    launch_cell_order(&c->prof, c->stream, c->ws, a, nbits, head, &f->cnt[0]);
     launch_mesh_count(&c->prof, c->stream, c->ws, a, &f->cnt[1]);
     HIPCHK(hipGetLastError());
-    uint32_t cnt_h[3];
-    HIPCHK(hipMemcpyAsync(hbuf, f->cnt, 8, hipMemcpyDeviceToHost, c->stream));
+    uint32_t vt_h[2], cnt_h[3];
+    HIPCHK(hipMemcpyAsync(vt_h, f->cnt, sizeof vt_h, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(cnt_h, f->counters, sizeof cnt_h, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    const int64_t V = hbuf[0], T = hbuf[1];
+    const int64_t V = vt_h[0], T = vt_h[1];
     *n_tris = T;
     if (tris && T > tris_capacity) return fail(O3DR_ERR_CAPACITY, "tris_capacity is below the triangle count");
     outs.set_count(tris, 3 * T);

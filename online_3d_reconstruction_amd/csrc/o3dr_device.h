@@ -42,6 +42,7 @@ constexpr int kXcds = 8;   // accelerator complex dies of an MI355X, each with i
 constexpr int kPtThreads = 256;
 constexpr int kSegTile = 1024;  // sorted keys per workgroup in the run-head kernels
 constexpr int kMinmaxBlocks = 1024;  // workgroups (= bounding-box slots) of the stand-alone min/max pass
+constexpr int kPartWords = 8;  // words per workgroup partial of the whole-cloud integer reductions (k_fold4_u32 in kernels/util.inc)
 constexpr int kSmallMax = 8192;      // points one workgroup takes through the whole path in one launch (kernels/small.inc)
 // whole-cloud voxel grids (the merge): records of the sort are runs of consecutive points inside one GROUP of
 // 2^kGroupBits consecutive voxel indices; one wave then sums a group, lane = voxel (k_centroid_groups)
@@ -302,10 +303,10 @@ void launch_nn_query(Profiler* pf, hipStream_t s, const Workspace& ws, const o3d
                      const float* box6, const float4* cell_lo, const float4* cell_hi, float r2, uint32_t* idx_out, float* d2_out,
                      const uint32_t* idx_prev, const double c0[3], double* partial, double* rec);
 inline int64_t nn_partial_blocks(int64_t n) { return (n + 255) / 256; }  // workgroups of launch_nn_query (kNnThreads queries each)
-// moving least squares (kernels/mls.inc).  launch_mls_finite: flag[0] = 1 if a coordinate of the n points is not finite.
-// launch_mls: o3dr_mls_smooth over the grid launch_nn_grid built for `cloud` (box6, cell_lo / cell_hi its outputs);
+// launch_cloud_finite: flag[0] = 1 if a coordinate of the n points is not finite.
+// moving least squares (kernels/mls.inc).  launch_mls: o3dr_mls_smooth over the grid launch_nn_grid built for `cloud` (box6, cell_lo / cell_hi its outputs);
 // counters (device, 4 x u64): n_none, n_plane, n_poly, max neighbours
-void launch_mls_finite(Profiler* pf, hipStream_t s, const o3dr_point* in, int64_t n, uint32_t* flag);
+void launch_cloud_finite(Profiler* pf, hipStream_t s, const o3dr_point* in, int64_t n, uint32_t* flag);
 void launch_mls(Profiler* pf, hipStream_t s, const Workspace& ws, const o3dr_point* cloud, int64_t n, const float* box6,
                 const float4* cell_lo, const float4* cell_hi, double r, int order, double h, o3dr_point* out, float* normals,
                 uint32_t* nn_count, uint8_t* fit, unsigned long long* counters);
@@ -357,16 +358,36 @@ struct RigidArgs {
 // residual == false: first used pairs, moments about c0 and their fold into rec / c0; true: the squared residuals at T
 // folded into rec
 void launch_rigid(Profiler* pf, hipStream_t s, const RigidArgs& a, bool residual);
+// The dense XY cell order of a cloud (kernels/cell_order.inc): the points sorted by the dense id
+// (iy - y0) * wx + (ix - x0) of their cell, input order kept inside a cell.  The operator's Args (PlaneArgs, MeshArgs:
+// cloud, n, the parameter of its index rule, `cells`) select the index rule.
+struct CellOrder {
+    int32_t x0, y0;               // the index box's lower corner
+    uint64_t wx, wy;              // its widths (wx * wy within the operator's limit, at most 2^32)
+    uint32_t n;                   // points
+    const uint32_t* keys;         // n sorted dense cell ids
+    const uint32_t* perm;         // n input indices in sorted order
+    const uint32_t* ord;          // n: exclusive scan of the run heads (the cell ordinal at every run head)
+    const uint32_t* n_runs;       // device: the number of occupied cells
+};
+constexpr int kCellRangeBlocks = 1024;  // workgroups (and partials) of the range pass at most
+inline int64_t cell_range_parts(int64_t n) { return n < (int64_t)kCellRangeBlocks * 256 ? (n + 255) / 256 : kCellRangeBlocks; }
+// launch_cell_range: the order-preserving index range of a.n points (range[0..3]: ix_min ix_max iy_min iy_max, each as
+// int32 ^ 0x80000000; range[4] = 1 if an index leaves int32; range[4..7] are written), through `part` (kPartWords words
+// for each of cell_range_parts(n) workgroups).  launch_cell_order (a.cells' box set): the sort of the dense cell ids
+// (nbits wide) in ws and the run heads scanned into cell ordinals (head, n words; the cell count -> *n_runs_dev); fills
+// the rest of a.cells.
+template <class Args>
+void launch_cell_range(Profiler* pf, hipStream_t s, const Args& a, uint32_t* part, uint32_t* range);
+template <class Args>
+void launch_cell_order(Profiler* pf, hipStream_t s, Workspace& ws, Args& a, int nbits, uint32_t* head, uint32_t* n_runs_dev);
 // RANSAC plane segmentation (kernels/plane.inc; the fields are filled by o3dr_segment_plane step by step)
 struct PlaneArgs {
     const float4* pts;            // points in tile order: (x, y, z, original index bits) when tiled, else the cloud itself
     const o3dr_point* cloud;      // the cloud in input order
     int tiled;                    // 1: pts is the gathered tile order
     uint32_t n, n_tiles, H;
-    const uint32_t* keys;         // tiled: the sorted dense tile ids
-    const uint32_t* tile_excl;    // tiled: exclusive scan of the run heads (tile ordinal of every run head)
-    const int32_t* range;         // tiled: ix_min, ix_max, iy_min, iy_max
-    uint32_t wx;                  // tiled: ix_max - ix_min + 1
+    CellOrder cells;              // tiled: the tiles are the cells
     double s;                     // tile size
     float tf;                     // (float)distance_threshold
     uint64_t seed;
@@ -382,15 +403,9 @@ struct PlaneArgs {
 };
 constexpr int kPlaneChunkPoints = 128;  // points per wave chunk (kPlaneChunk)
 constexpr int kPlaneMomentsHost = 10;   // fp64 moments per chunk (kPlaneMoments)
-// launch_plane_range: the order-preserving tile index range of the n points (range[4]: ix_min ix_max iy_min iy_max, each
-// as int32 ^ 0x80000000) and flag[1] = 1 if an index leaves int32.  launch_plane_order: the sort of the dense tile ids
-// (nbits wide) in ws, the run heads scanned into tile ordinals (head, n words; the tile count -> *n_tiles_dev), the points
-// gathered into tile order (pts).  launch_plane_tiles: tile starts, records and chunks (a.n_tiles set).
-// launch_plane_fit: hypotheses, scores, the choice, refinement (optimize) and labels.
-void launch_plane_range(Profiler* pf, hipStream_t s, const o3dr_point* in, int64_t n, double tile_size, int32_t* range, uint32_t* flag);
-void launch_plane_order(Profiler* pf, hipStream_t s, Workspace& ws, PlaneArgs& a, int nbits, uint32_t* head, float4* pts,
-                        uint32_t* n_tiles_dev);
-void launch_plane_tiles(Profiler* pf, hipStream_t s, Workspace& ws, const PlaneArgs& a);
+// launch_plane_tiles: tiled, the points gathered into tile order (pts, which a.pts names); tile starts, records and
+// chunks (a.n_tiles set).  launch_plane_fit: hypotheses, scores, the choice, refinement (optimize) and labels.
+void launch_plane_tiles(Profiler* pf, hipStream_t s, Workspace& ws, const PlaneArgs& a, float4* pts);
 void launch_plane_fit(Profiler* pf, hipStream_t s, const PlaneArgs& a, int64_t max_chunks, int optimize);
 // height-field surface mesh (kernels/mesh.inc; the fields are filled by o3dr_mesh_surface step by step)
 struct MeshArgs {
@@ -398,29 +413,19 @@ struct MeshArgs {
     uint32_t n;
     float inv;                    // 1.0f / (float)cell_size
     float lf;                     // (float)(L * L): the edge gate on d2
-    int32_t cx0, cy0;             // the cell box's lower corner
-    uint64_t wx, wy;              // its widths in cells (wx * wy <= 2^32)
-    const uint32_t* keys;         // n sorted dense cell ids
-    const uint32_t* perm;         // n input indices in sorted order
-    const uint32_t* ord;          // n: the scanned run heads (the vertex ordinal of every head)
-    const uint32_t* n_vert;       // device: V, the vertex count
+    CellOrder cells;              // the cell of a vertex; cells.n_runs: V, the vertex count
     uint32_t* vkey;               // V cell ids in cell order
     float4* vpt;                  // V vertices: x y z, input index bits in .w
     int4* nbr;                    // V: the ordinals of the right, upper-right, upper and upper-left cells (-1: empty)
     uint32_t* cnt;                // n: kept triangles per vertex, then their exclusive scan (the first triangle's slot)
-    uint32_t* part;               // kMeshPart words per workgroup of the whole-cloud reductions
+    uint32_t* part;               // kPartWords words per workgroup of the whole-cloud reductions
     uint32_t* counters;           // full quads, rejected by orientation, rejected by length
     int32_t* tris;                // 3 T
     float* normals;               // 3 n
 };
-// launch_mesh_range: the order-preserving cell index range of the n points (range[4]: cx_min cx_max cy_min cy_max, each as
-// int32 ^ 0x80000000; range[4] = 1 if an index leaves int32), through `part` (kMeshPartWords per 256 points).  launch_mesh_cells: the sort of the dense cell ids (nbits
-// wide) in ws, the run heads scanned into vertex ordinals (head, n words; V -> *n_vert_dev) and the vertices gathered
-// (a.keys, a.perm, a.ord set).  launch_mesh_count: neighbours, triangles per vertex scanned into offsets (T -> *n_tris_dev)
-// and the counters.  launch_mesh_emit: the triangles (a.tris) and the vertex normals (a.normals), each if set.
-constexpr int kMeshPartWords = 8;  // kMeshPart
-void launch_mesh_range(Profiler* pf, hipStream_t s, const o3dr_point* in, int64_t n, float inv, uint32_t* part, uint32_t* range);
-void launch_mesh_cells(Profiler* pf, hipStream_t s, Workspace& ws, MeshArgs& a, int nbits, uint32_t* head, uint32_t* n_vert_dev);
+// launch_mesh_count: the vertices gathered, their neighbours, triangles per vertex scanned into offsets
+// (T -> *n_tris_dev) and the counters.  launch_mesh_emit: the triangles (a.tris) and the vertex normals (a.normals),
+// each if set.
 void launch_mesh_count(Profiler* pf, hipStream_t s, Workspace& ws, const MeshArgs& a, uint32_t* n_tris_dev);
 void launch_mesh_emit(Profiler* pf, hipStream_t s, const MeshArgs& a);
 // plane-fitted disparity per segment label (kernels/plane_disparity.inc).  `table`: kPdSums 64-bit sums per (frame, label) -

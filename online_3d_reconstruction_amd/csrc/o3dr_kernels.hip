@@ -29,6 +29,7 @@
 //   incremental  the combined merge kept as running per-cell sums (o3dr_finalize_incremental)
 //   nn           exact nearest neighbour into a target's search grid, the fused ICP pass and its fold
 //   mls          moving-least-squares smoothing and normals over the same grid
+//   cell_order   the dense XY cell order of a cloud: index box, keys, run heads (plane tiles, mesh cells)
 //   plane        RANSAC plane segmentation per XY tile
 //   mesh         height-field surface mesh over the XY cells
 //   match        Hamming 2-NN descriptor matching, index-aligned 3-D keypoints, the batched rigid fit
@@ -53,6 +54,7 @@ namespace o3dr {
 #include "kernels/small.inc"
 #include "kernels/nn.inc"
 #include "kernels/mls.inc"
+#include "kernels/cell_order.inc"
 #include "kernels/plane.inc"
 #include "kernels/mesh.inc"
 #include "kernels/match.inc"
@@ -805,17 +807,17 @@ void launch_nn_query(Profiler* pf, hipStream_t s, const Workspace& ws, const o3d
     if (partial) k_icp_fold<<<kIcpFields, kIcpFoldThreads, 0, s>>>(partial, a.n_blocks, rec);
 }
 
-// Moving least squares (kernels/mls.inc) over the grid launch_nn_grid left in ws.sor_*
-void launch_mls_finite(Profiler* pf, hipStream_t s, const o3dr_point* in, int64_t n, uint32_t* flag)
+void launch_cloud_finite(Profiler* pf, hipStream_t s, const o3dr_point* in, int64_t n, uint32_t* flag)
 {
     ProfScope ps(pf, O3DR_K_OTHER, s);
     (void)hipMemsetAsync(flag, 0, 4, s);
     if (n <= 0) return;
     int g = cdiv64(n, 256);
     if (g > 4096) g = 4096;
-    k_mls_finite<<<g, 256, 0, s>>>(in, n, flag);
+    k_cloud_finite<<<g, 256, 0, s>>>(in, n, flag);
 }
 
+// Moving least squares (kernels/mls.inc) over the grid launch_nn_grid left in ws.sor_*
 void launch_mls(Profiler* pf, hipStream_t s, const Workspace& ws, const o3dr_point* cloud, int64_t n, const float* box6,
                 const float4* cell_lo, const float4* cell_hi, double r, int order, double h, o3dr_point* out, float* normals,
                 uint32_t* nn_count, uint8_t* fit, unsigned long long* counters)
@@ -852,23 +854,9 @@ void launch_mls(Profiler* pf, hipStream_t s, const Workspace& ws, const o3dr_poi
         k_mls<2><<<blocks, kMlsThreads, 0, s>>>(a);
 }
 
-// RANSAC plane segmentation (kernels/plane.inc)
-void launch_plane_range(Profiler* pf, hipStream_t s, const o3dr_point* in, int64_t n, double tile_size, int32_t* range, uint32_t* flag)
-{
-    ProfScope ps(pf, O3DR_K_OTHER, s);
-    (void)hipMemsetAsync(flag + 1, 0, 4, s);
-    (void)hipMemsetAsync(range, 0xff, 4, s);
-    (void)hipMemsetAsync(range + 1, 0, 4, s);
-    (void)hipMemsetAsync(range + 2, 0xff, 4, s);
-    (void)hipMemsetAsync(range + 3, 0, 4, s);
-    if (n <= 0) return;
-    int g = cdiv64(n, 256);
-    if (g > 4096) g = 4096;
-    k_plane_range<<<g, 256, 0, s>>>(in, n, tile_size, range, flag);
-}
-
 // Stable sort of the n nbits-wide keys in ws.keys[0], the payload being the input position: at least one pass (it also
 // writes the payload).  Returns the buffer the sorted records end in.
+__global__ void k_set_sort_geom(VoxelGeom* geom, VoxelGeom g) { *geom = g; }
 static int launch_sort_keys(Workspace& ws, hipStream_t s, uint32_t n, int nbits)
 {
     VoxelGeom g;
@@ -879,28 +867,47 @@ static int launch_sort_keys(Workspace& ws, hipStream_t s, uint32_t n, int nbits)
     if (nbits < 1) nbits = 1;
     g.passes = (uint32_t)((nbits + kMaxRadixBits - 1) / kMaxRadixBits);
     g.bpp = (uint32_t)((nbits + (int)g.passes - 1) / (int)g.passes);
-    k_plane_sort_geom<<<1, 1, 0, s>>>(ws.geom, g);
+    k_set_sort_geom<<<1, 1, 0, s>>>(ws.geom, g);
     launch_radix_passes(ws, s, n, (int)g.passes);
     return (int)(g.passes & 1u);
 }
 
-void launch_plane_order(Profiler* pf, hipStream_t s, Workspace& ws, PlaneArgs& a, int nbits, uint32_t* head, float4* pts,
-                        uint32_t* n_tiles_dev)
+// The dense XY cell order (kernels/cell_order.inc); cell_of(a) is the operator's index rule
+template <class Args>
+void launch_cell_range(Profiler* pf, hipStream_t s, const Args& a, uint32_t* part, uint32_t* range)
 {
     ProfScope ps(pf, O3DR_K_OTHER, s);
-    const int64_t n = a.n;
-    k_plane_keys<<<cdiv64(n, 256), 256, 0, s>>>(a, ws.keys[0]);
-    const int sorted = launch_sort_keys(ws, s, a.n, nbits);
-    a.keys = ws.keys[sorted];
-    a.tile_excl = head;
-    a.pts = pts;
-    k_plane_heads<<<cdiv64(n, 256), 256, 0, s>>>(a, ws.vals[sorted], head, pts);
-    launch_scan(s, head, n, n, 1, n_tiles_dev, nullptr, ws.scan_partial);
+    const int g = (int)cell_range_parts(a.n);
+    k_cell_range<<<g, kCellThreads, 0, s>>>(a.cloud, (int64_t)a.n, cell_of(a), part);
+    k_fold4_u32<<<1, kFoldThreads, 0, s>>>(part, g, 0, 0, 1, 0, 1, range);
+    k_fold4_u32<<<1, kFoldThreads, 0, s>>>(part, g, 4, 1, 1, 1, 1, range + 4);
 }
-
-void launch_plane_tiles(Profiler* pf, hipStream_t s, Workspace& ws, const PlaneArgs& a)
+template <class Args>
+void launch_cell_order(Profiler* pf, hipStream_t s, Workspace& ws, Args& a, int nbits, uint32_t* head, uint32_t* n_runs_dev)
 {
     ProfScope ps(pf, O3DR_K_OTHER, s);
+    CellOrder& o = a.cells;
+    o.n = a.n;
+    const int g = cdiv64(o.n, kCellThreads);
+    k_cell_keys<<<g, kCellThreads, 0, s>>>(a.cloud, o.n, cell_of(a), o.x0, o.y0, o.wx, ws.keys[0]);
+    const int sorted = launch_sort_keys(ws, s, o.n, nbits);
+    o.keys = ws.keys[sorted];
+    o.perm = ws.vals[sorted];
+    o.ord = head;
+    o.n_runs = n_runs_dev;
+    k_cell_heads<<<g, kCellThreads, 0, s>>>(o, head);
+    launch_scan(s, head, o.n, o.n, 1, n_runs_dev, nullptr, ws.scan_partial);
+}
+template void launch_cell_range<PlaneArgs>(Profiler*, hipStream_t, const PlaneArgs&, uint32_t*, uint32_t*);
+template void launch_cell_range<MeshArgs>(Profiler*, hipStream_t, const MeshArgs&, uint32_t*, uint32_t*);
+template void launch_cell_order<PlaneArgs>(Profiler*, hipStream_t, Workspace&, PlaneArgs&, int, uint32_t*, uint32_t*);
+template void launch_cell_order<MeshArgs>(Profiler*, hipStream_t, Workspace&, MeshArgs&, int, uint32_t*, uint32_t*);
+
+// RANSAC plane segmentation (kernels/plane.inc)
+void launch_plane_tiles(Profiler* pf, hipStream_t s, Workspace& ws, const PlaneArgs& a, float4* pts)
+{
+    ProfScope ps(pf, O3DR_K_OTHER, s);
+    if (a.tiled) k_plane_gather<<<cdiv64(a.n, 256), 256, 0, s>>>(a, pts);
     k_plane_tiles<<<a.tiled ? cdiv64(a.n, 256) : 1, 256, 0, s>>>(a);
     k_plane_chunks<<<cdiv64(a.n_tiles, 256), 256, 0, s>>>(a);
     launch_scan(s, a.cfirst, a.n_tiles, a.n_tiles, 1, a.cfirst + a.n_tiles, nullptr, ws.scan_partial);
@@ -968,38 +975,14 @@ void launch_rigid(Profiler* pf, hipStream_t s, const RigidArgs& a, bool residual
 }
 
 // height-field surface mesh (kernels/mesh.inc)
-void launch_mesh_range(Profiler* pf, hipStream_t s, const o3dr_point* in, int64_t n, float inv, uint32_t* part, uint32_t* range)
-{
-    ProfScope ps(pf, O3DR_K_OTHER, s);
-    if (n <= 0) return;
-    int g = cdiv64(n, kMeshThreads);
-    if (g > 1024) g = 1024;
-    k_mesh_range<<<g, kMeshThreads, 0, s>>>(in, n, inv, part);
-    k_mesh_fold<<<1, kMeshThreads, 0, s>>>(part, g, 0, 0, 1, 0, 1, range);
-    k_mesh_fold<<<1, kMeshThreads, 0, s>>>(part, g, 4, 1, 1, 1, 1, range + 4);
-}
-
-void launch_mesh_cells(Profiler* pf, hipStream_t s, Workspace& ws, MeshArgs& a, int nbits, uint32_t* head, uint32_t* n_vert_dev)
-{
-    ProfScope ps(pf, O3DR_K_OTHER, s);
-    const int64_t n = a.n;
-    k_mesh_keys<<<cdiv64(n, kMeshThreads), kMeshThreads, 0, s>>>(a, ws.keys[0]);
-    const int sorted = launch_sort_keys(ws, s, a.n, nbits);
-    a.keys = ws.keys[sorted];
-    a.perm = ws.vals[sorted];
-    a.ord = head;
-    k_mesh_heads<<<cdiv64(n, kMeshThreads), kMeshThreads, 0, s>>>(a, head);
-    launch_scan(s, head, n, n, 1, n_vert_dev, nullptr, ws.scan_partial);
-    k_mesh_vertices<<<cdiv64(n, kMeshThreads), kMeshThreads, 0, s>>>(a);
-}
-
 void launch_mesh_count(Profiler* pf, hipStream_t s, Workspace& ws, const MeshArgs& a, uint32_t* n_tris_dev)
 {
     ProfScope ps(pf, O3DR_K_OTHER, s);
     const int64_t n = a.n;
     const int g = cdiv64(n, kMeshThreads);
+    k_mesh_vertices<<<g, kMeshThreads, 0, s>>>(a);
     k_mesh_count<<<g, kMeshThreads, 0, s>>>(a);
-    k_mesh_fold<<<1, kMeshThreads, 0, s>>>(a.part, g, 0, 2, 2, 2, 2, a.counters);
+    k_fold4_u32<<<1, kFoldThreads, 0, s>>>(a.part, g, 0, 2, 2, 2, 2, a.counters);
     launch_scan(s, a.cnt, n, n, 1, n_tris_dev, nullptr, ws.scan_partial);
 }
 

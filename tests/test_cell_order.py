@@ -1,0 +1,216 @@
+"""The dense XY cell order that plane segmentation (tiles) and the surface mesh (cells) share (kernels/cell_order.inc;
+DESIGN.md "Cell order"), through the public ABI of both operators.  Expected values come from the operators' own numpy
+restatements (tests/test_plane_segmentation.py, tests/test_mesh_surface.py); what is compared is what the cell order
+decides: the tile records' ix, iy and n_points and every point's tile ordinal, the mesh's vertex and shadowed counts and
+its triangles.  Plane runs without refinement and with a few hypotheses, so that everything else is exact and cheap too.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from test_mesh_surface import ERR_INVALID_ARG, _pts, mesh_numpy
+from test_plane_segmentation import segment_numpy, tiles_numpy
+
+F32 = np.float32
+RANGE_BLOCKS = 1024  # kCellRangeBlocks (o3dr_device.h): workgroups of 256 points of the range pass at most
+NON_FINITE = "the cloud has a non-finite coordinate"
+
+
+# ---- clouds -------------------------------------------------------------------------------------------------------------
+def cloud_in_cells(ix, iy, seed):
+    """one point well inside every given unit cell (size 1.0: both index rules agree there), random z"""
+    rng = np.random.default_rng(seed)
+    ix, iy = np.asarray(ix, np.float64), np.asarray(iy, np.float64)
+    return np.stack([ix + rng.uniform(0.1, 0.9, len(ix)), iy + rng.uniform(0.1, 0.9, len(ix)), rng.normal(0, 0.2, len(ix))], 1).astype(F32)
+
+
+def box_cloud(x0, y0, wx, wy, n, seed):
+    """n shuffled points over the index box [x0, x0 + wx) x [y0, y0 + wy), its four corner cells occupied"""
+    rng = np.random.default_rng(seed)
+    ix = np.concatenate([[x0, x0 + wx - 1, x0, x0 + wx - 1], rng.integers(x0, x0 + wx, n - 4)])
+    iy = np.concatenate([[y0, y0, y0 + wy - 1, y0 + wy - 1], rng.integers(y0, y0 + wy, n - 4)])
+    p = rng.permutation(n)
+    return cloud_in_cells(ix[p], iy[p], seed + 1)
+
+
+def box_cells(xyz, s):
+    """cells of the index box under BOTH rules (the clouds here keep clear of the cell borders, where they differ)"""
+    w = []
+    for k in (0, 1):
+        a = np.floor(xyz[:, k].astype(np.float64) / s).astype(np.int64)
+        b = np.floor(xyz[:, k] * (F32(1) / F32(s))).astype(np.int64)
+        assert np.array_equal(a, b)
+        w.append(int(a.max() - a.min() + 1))
+    return w[0] * w[1]
+
+
+# ---- the two index rules, without a GPU -------------------------------------------------------------------------------------
+RULE_X = [0.7, -0.7, 0.3, 0.65, 0.75, -0.05, 1.0]
+
+
+def test_the_two_index_rules_differ_in_the_restatements():
+    """0.7f at size 0.1: floor((double)x / s) = 6 for the tiles, floorf(x * (1.0f / 0.1f)) = 7 for the cells"""
+    assert [t[0] for t in tiles_numpy(np.array([[0.7, 0, 0]], F32), 0.1)] == [6]
+    assert np.floor(F32(0.7) * (F32(1) / F32(0.1))) == 7
+    # 0.7f shares its TILE with 0.65f and its CELL with 0.75f
+    assert len(tiles_numpy(np.array([[0.7, 0, 0], [0.65, 0, 0]], F32), 0.1)) == 1
+    assert len(tiles_numpy(np.array([[0.7, 0, 0], [0.75, 0, 0]], F32), 0.1)) == 2
+    assert mesh_numpy(np.array([[0.7, 0, 0], [0.65, 0, 0]], F32), 0.1, np.inf)[1]["n_vertices"] == 2
+    assert mesh_numpy(np.array([[0.7, 0, 0], [0.75, 0, 0]], F32), 0.1, np.inf)[1]["n_vertices"] == 1
+
+
+# ---- on the GPU ---------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def cell_ctx():
+    import online_3d_reconstruction_amd as o3dr
+    with o3dr.Context(0) as c:
+        yield c
+
+
+def check_plane(ctx, xyz, s, H=2, seed=7, t=0.05):
+    xyz = np.asarray(xyz, F32)
+    inl, tiles, til = ctx.segmentPlane(_pts(xyz), t, H, s, seed, False, return_tile_index=True)
+    recs, inl_ref, _, til_ref = segment_numpy(xyz, t, H, s, seed, optimize=False)
+    assert len(tiles) == len(recs)
+    assert [(int(r["ix"]), int(r["iy"]), int(r["n_points"])) for r in tiles] == [(r["ix"], r["iy"], r["m"]) for r in recs]
+    assert np.array_equal(til, til_ref)
+    # input order inside a tile: the samples are tile-local positions, reported as input indices
+    for rec, r in zip(tiles, recs):
+        assert rec["status"] == r["status"] and rec["hypothesis"] == r["hypothesis"]
+        if r["status"] == 0:
+            assert list(rec["sample"]) == [int(r["idx"][j]) for j in r["sample"]]
+    assert np.array_equal(inl, inl_ref)
+    return tiles
+
+
+def check_mesh(ctx, xyz, cell, L=np.inf):
+    xyz = np.asarray(xyz, F32)
+    t_ref, cnt_ref, n_ref = mesh_numpy(xyz, cell, L, normals=True)
+    t, nrm, info = ctx.meshSurface(_pts(xyz), cell, L, return_normals=True, return_info=True)
+    assert info.__dict__ == cnt_ref
+    assert t.shape == t_ref.shape and np.array_equal(t, t_ref)
+    assert np.array_equal(nrm.view(np.uint32), n_ref.view(np.uint32))
+    return info
+
+
+@pytest.mark.gpu
+def test_the_two_index_rules_stay_different(cell_ctx):
+    rng = np.random.default_rng(3)
+    xyz = np.stack([RULE_X, rng.uniform(0.01, 0.09, len(RULE_X)), rng.normal(0, 0.1, len(RULE_X))], 1).astype(F32)
+    tiles = check_plane(cell_ctx, xyz, 0.1)
+    check_mesh(cell_ctx, xyz, 0.1)
+    assert 6 in tiles["ix"] and 7 in tiles["ix"]
+    at = lambda x: np.array([[x, 0.05, 0.0]], F32)  # noqa: E731
+    assert list(check_plane(cell_ctx, at(0.7), 0.1)["ix"]) == [6]
+    assert list(check_plane(cell_ctx, np.concatenate([at(0.7), at(0.65)]), 0.1)["n_points"]) == [2]
+    assert list(check_plane(cell_ctx, np.concatenate([at(0.7), at(0.75)]), 0.1)["ix"]) == [6, 7]
+    assert check_mesh(cell_ctx, np.concatenate([at(0.7), at(0.65)]), 0.1).n_vertices == 2   # cells 7 and 6
+    assert check_mesh(cell_ctx, np.concatenate([at(0.7), at(0.75)]), 0.1).n_shadowed == 1   # both in cell 7
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 2, 3])
+def test_a_single_cell(cell_ctx, n):
+    """wx = wy = 1: a 0-bit key, which the sort takes as one pass"""
+    xyz = np.array([[5.3, -2.2, 0.0], [5.6, -2.7, 0.4], [5.1, -2.5, -0.3]], F32)[:n]
+    tiles = check_plane(cell_ctx, xyz, 1.0)
+    assert len(tiles) == 1 and (tiles["ix"][0], tiles["iy"][0], tiles["n_points"][0]) == (5, -3, n)
+    info = check_mesh(cell_ctx, xyz, 1.0)
+    assert (info.n_vertices, info.n_triangles, info.n_shadowed) == (1, 0, n - 1)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("wx,wy", [(16, 8), (43, 3)])
+def test_both_parities_of_the_sorted_buffer(cell_ctx, wx, wy):
+    """128 cells: 7 bits, one radix pass, the records end in buffer 1; 129 cells: 8 bits, two passes, buffer 0"""
+    xyz = box_cloud(-5, 3, wx, wy, 600, seed=wx)
+    assert box_cells(xyz, 1.0) == wx * wy and wx * wy in (128, 129)
+    tiles = check_plane(cell_ctx, xyz, 1.0, H=3)
+    assert tiles["n_points"].max() > 3
+    assert check_mesh(cell_ctx, xyz, 1.0, 1.6).n_shadowed > 300
+
+
+@pytest.mark.gpu
+def test_range_fold_over_several_workgroups(cell_ctx):
+    """n = 257: the minimum index only in point 256 (the second workgroup), the maximum only in point 0"""
+    rng = np.random.default_rng(8)
+    ix, iy = rng.integers(0, 2, 257), rng.integers(0, 2, 257)
+    ix[0] = iy[0] = 2
+    ix[256] = iy[256] = -1
+    xyz = cloud_in_cells(ix, iy, 9)
+    tiles = check_plane(cell_ctx, xyz, 1.0)
+    assert (tiles["ix"][0], tiles["iy"][0]) == (-1, -1) and (tiles["ix"][-1], tiles["iy"][-1]) == (2, 2)
+    assert check_mesh(cell_ctx, xyz, 1.0).n_vertices == 6
+
+
+@pytest.mark.gpu
+def test_range_fold_reaches_the_point_past_the_grid(cell_ctx):
+    """one point more than the capped range grid covers in one sweep: the extreme indices are in that last point only"""
+    n = RANGE_BLOCKS * 256 + 1
+    rng = np.random.default_rng(10)
+    ix, iy = rng.integers(0, 2, n), rng.integers(0, 2, n)
+    ix[-1], iy[-1] = -1, 2
+    xyz = cloud_in_cells(ix, iy, 11)
+    tiles = check_plane(cell_ctx, xyz, 1.0, H=1)
+    assert len(tiles) == 5 and (tiles["ix"][-1], tiles["iy"][-1], tiles["n_points"][-1]) == (-1, 2, 1)
+    info = check_mesh(cell_ctx, xyz, 1.0)
+    assert info.n_vertices == 5 and info.n_shadowed == n - 5
+
+
+@pytest.mark.gpu
+def test_a_box_on_both_sides_of_the_origin(cell_ctx):
+    xyz = box_cloud(-3, -2, 6, 5, 400, seed=21)
+    tiles = check_plane(cell_ctx, xyz, 1.0, H=4)
+    assert len(tiles) == 30 and (tiles["ix"].min(), tiles["ix"].max(), tiles["iy"].min(), tiles["iy"].max()) == (-3, 2, -2, 2)
+    assert check_mesh(cell_ctx, xyz, 1.0, 2.0).n_vertices == 30
+    half = xyz * F32(0.5)  # the same box at size 0.5, negative zero included
+    half[0, :2] = F32(-0.0)
+    check_plane(cell_ctx, half, 0.5, H=4)
+    check_mesh(cell_ctx, half, 0.5, 1.0)
+
+
+@pytest.mark.gpu
+def test_the_two_limits_side_by_side(cell_ctx):
+    """65536 x 65536 indices are exactly 2^32: one more than the tiles' limit of 2^32 - 1, the cells' limit itself"""
+    import online_3d_reconstruction_amd as o3dr
+    xyz = np.array([[0.5, 0.5, 0.0], [65535.5, 0.5, 0.0], [0.5, 65535.5, 0.0]], F32)
+    with pytest.raises(o3dr.O3drError) as e:
+        cell_ctx.segmentPlane(_pts(xyz), 0.05, 2, 1.0)
+    assert e.value.code == ERR_INVALID_ARG and "2^32-1 tiles" in str(e.value)
+    assert check_mesh(cell_ctx, xyz, 1.0).n_vertices == 3
+    check_plane(cell_ctx, xyz[:2], 1.0)  # 65536 x 1 tiles work
+
+
+@pytest.mark.gpu
+def test_non_finite_is_reported_before_an_index_out_of_int32(cell_ctx):
+    """a NaN and a coordinate of 1e30 (its index leaves int32, and so does the NaN's): the non-finite error wins, and the
+    host outputs are zeroed"""
+    from online_3d_reconstruction_amd import PLANE_TILE, _lib
+    L = cell_ctx._lib
+    xyz = cloud_in_cells([0, 1, 2, 3, 4, 5], [0, 0, 1, 1, 2, 2], 4)
+    xyz[1, 1] = np.nan
+    xyz[4, 0] = 1e30
+    pts, n = _pts(xyz), len(xyz)
+    prm = _lib.PlaneParamsStruct(0.05, 2, 1.0, 0, 0)
+    nt = C.c_int64(9)
+    inl, til, prj, rec = np.full(n, 7, np.uint8), np.full(n, 7, np.int32), pts.copy(), np.ones(4, PLANE_TILE)
+    rc = L.o3dr_segment_plane(cell_ctx._h, pts.ctypes.data, n, C.byref(prm), inl.ctypes.data, til.ctypes.data, prj.ctypes.data,
+                              rec.ctypes.data, 4, C.byref(nt), 0)
+    assert rc == ERR_INVALID_ARG and L.o3dr_last_error().decode() == NON_FINITE
+    assert nt.value == 0 and not inl.any() and not til.any() and not prj.view(np.uint8).any() and not rec.view(np.uint8).any()
+    mprm = _lib.MeshParamsStruct(1.0, float("inf"))
+    res = _lib.MeshResultStruct(*([5] * 6))
+    tris, nrm = np.full((2 * n, 3), 7, np.int32), np.full((n, 3), 7, np.float32)
+    rc = L.o3dr_mesh_surface(cell_ctx._h, pts.ctypes.data, n, C.byref(mprm), tris.ctypes.data, 2 * n, C.byref(nt), nrm.ctypes.data,
+                             C.byref(res), 0)
+    assert rc == ERR_INVALID_ARG and L.o3dr_last_error().decode() == NON_FINITE
+    assert nt.value == 0 and not tris.any() and not nrm.any() and res.n_vertices == 0 and res.n_shadowed == 0
+    # without the NaN the index is what is wrong
+    xyz[1, 1] = 0.5
+    for call, text in ((lambda: cell_ctx.segmentPlane(_pts(xyz), 0.05, 2, 1.0), "a tile index does not fit in int32"),
+                       (lambda: cell_ctx.meshSurface(_pts(xyz), 1.0, np.inf), "a cell index does not fit in int32")):
+        import online_3d_reconstruction_amd as o3dr
+        with pytest.raises(o3dr.O3drError) as e:
+            call()
+        assert e.value.code == ERR_INVALID_ARG and text in str(e.value)
