@@ -720,6 +720,89 @@ int  o3dr_plane_fit_disparity(o3dr_ctx* ctx, const uint8_t* disp, int64_t disp_p
                               int32_t rows, int32_t cols, int32_t n_frames, const o3dr_plane_disp_params* p, double* out,
                               o3dr_plane_disp_segment* segments, uint32_t* status, int32_t mem);
 
+/* ---- ORB features: what the reference's findFeatures gets from OpenCV's OrbFeaturesFinder (SURVEY section 2 row 10,
+ * pose.cpp:127,210): oFAST keypoints over a scale pyramid, ranked by a Harris response, oriented by the intensity centroid,
+ * described by 256 steered BRIEF tests on 5 x 5 box sums.  OpenCV's learned test pattern and its float rounding cannot be
+ * pinned here, so the contract below is this library's own; every step is an exact integer computation, so results are
+ * bit-identical across calls, frame batchings and memory kinds.  Not included: OrbFeaturesFinder's 3 x 1 grid.
+ *
+ * Input: n_frames images of rows x cols pixels (1..8192 each), byte `pitch` and byte `frame_stride`, channels = 3
+ * (interleaved B, G, R) or 1 (grey), in `mem`.  W = cols, H = rows.
+ *   1. Grey: g = (1868 B + 9617 G + 4899 R + 8192) >> 14 (channels = 1: the byte itself).
+ *   2. Pyramid: sc_0 = 65536, sc_l = floor(65536 s^l + 0.5) with s^l built by repeated fp64 multiplication of
+ *      (double)scale_factor.  W_l = (W * 65536 + sc_l / 2) / sc_l, H_l likewise (integer division).  A level with W_l = 0 or
+ *      H_l = 0 does not exist (nor do the levels after it).  Level l is resampled from level l - 1: rx = (W_{l-1} << 16) /
+ *      W_l; fx = max(0, ((2x + 1) rx - 65536) >> 1) (arithmetic shift, 64-bit), x0 = min(fx >> 16, W_{l-1} - 1),
+ *      x1 = min(x0 + 1, W_{l-1} - 1), wx = (fx & 0xFFFF) >> 5; y likewise; the pixel is
+ *      (p00 (2048 - wx)(2048 - wy) + p01 wx (2048 - wy) + p10 (2048 - wx) wy + p11 wx wy + (1 << 21)) >> 22, p01 at (x1, y0).
+ *   3. FAST-9/16 on every level: ring offsets (dx, dy), clockwise from the top with y down: (0,-3) (1,-3) (2,-2) (3,-1) (3,0)
+ *      (3,1) (2,2) (1,3) (0,3) (-1,3) (-2,2) (-3,1) (-3,0) (-3,-1) (-2,-2) (-1,-3).  With c the centre and p_i the ring,
+ *      score = max over the 16 arcs of 9 contiguous ring pixels of max(min_i (p_i - c), min_i (c - p_i)); a pixel is a corner
+ *      iff score > fast_threshold; non-corners, and pixels within 3 pixels of the level's border, score 0.  A corner is
+ *      kept iff its score is strictly greater than the scores of all 8 neighbours (equal neighbours suppress each other).
+ *      Candidates: kept corners with edge <= x < W_l - edge and edge <= y < H_l - edge (none when W_l <= 2 edge).
+ *   4. Harris response of a candidate: Ix = 2 (p[y][x+1] - p[y][x-1]) + (p[y-1][x+1] - p[y-1][x-1]) + (p[y+1][x+1] -
+ *      p[y+1][x-1]), Iy its transpose; a = sum Ix^2, b = sum Iy^2, c = sum Ix Iy over the 7 x 7 window centred on the
+ *      candidate; R = 25 (a b - c^2) - (a + b)^2 in int64 (k = 1/25; |R| < 2^57).
+ *   5. Selection: quota_l = floor(n_features W_l / sum_k W_k) over all n_levels levels, the remainder added to level 0.
+ *      Per (frame, level) the quota_l candidates that come first under (R descending, y ascending, x ascending) are kept,
+ *      all of them if there are fewer; nothing is redistributed.  Output order per frame: level, then y, then x ascending.
+ *   6. Orientation: m10 = sum u I, m01 = sum v I over the disc u^2 + v^2 <= 240 of the level image around the keypoint.
+ *      D[k] = (round(16384 cos(2 pi k / 64)), round(16384 sin(2 pi k / 64))), k = 0..63.  angle_bin = the k with the largest
+ *      m10 D[k].x + m01 D[k].y (int64), the lowest k on a tie; m10 = m01 = 0: bin 0.
+ *   7. Descriptor.  Base pattern: test i = (ax, ay, bx, by); the stream is r_n = splitmix64(S + n), n = 0, 1, 2, ... with
+ *      S = splitmix64(O3DR_ORB_PATTERN_SEED) (splitmix64 as in the plane segmentation above); a coordinate is the sum of
+ *      four consecutive draws (r >> 32) % 7, minus 12; a test takes 16 draws (ax, ay, bx, by in that order) and is drawn
+ *      again (the next 16) if a == b or ax^2 + ay^2 > 169 or bx^2 + by^2 > 169.  Steered: rot_k(p) = ((p.x D[k].x - p.y D[k].y
+ *      + 8192) >> 14, (p.x D[k].y + p.y D[k].x + 8192) >> 14), arithmetic shifts; every component stays within [-13, 13].
+ *      o3dr_orb_pattern returns the table [64][256][4] of (rot_k(a).x, rot_k(a).y, rot_k(b).x, rot_k(b).y) as int8.
+ *      S(p) = the sum of the 5 x 5 pixels of the level image centred at keypoint + rot_bin(p).  Bit i = S(a_i) < S(b_i),
+ *      stored in byte i >> 3, bit i & 7.
+ *   8. Reported: x = (float)(((double)xl + 0.5) * W / W_l - 0.5) (the product, then the quotient, then the difference, each
+ *      in fp64), y likewise with H and H_l; size = (float)(31.0 * W / W_l); angle_deg = angle_bin * 5.625.
+ *
+ * Outputs: kp (records), kp_xy ([n, 2] floats: x, y) and desc ([n, 32] bytes) in `mem`, index-aligned, each optional (NULL:
+ * skipped); kp and desc must be 16-byte aligned, kp_xy 8-byte.  offsets: HOST array of n_frames + 1 entries, frame f's rows
+ * are [offsets[f], offsets[f+1]): with kp_xy exactly what o3dr_accumulate_frames_kp, o3dr_keypoints_3d and (with desc)
+ * o3dr_match_knn2_hamming take.  *n_out = offsets[n_frames].  out_capacity (rows of each output) must be at least n_frames *
+ * n_features: below it O3DR_ERR_CAPACITY and none of kp, kp_xy, desc, levels_out is written (offsets and *n_out are zeroed, as
+ * on every error).  With O3DR_MEM_HOST the rows from *n_out up to n_frames *
+ * n_features are zeroed.  levels_out (or NULL), in `mem`: every frame's grey pyramid, frame-major, the existing levels back
+ * to back, rows tight: n_frames * sum_l W_l H_l bytes (o3dr_orb_level_sizes gives the sizes).
+ * o3dr_orb_level_sizes: wh[2l] = W_l, wh[2l+1] = H_l (0 0: no such level), quota[l]; either may be NULL.  Host only.
+ * Limits, else O3DR_ERR_INVALID_ARG (offsets and *n_out zeroed, host outputs zeroed): 1 <= n_features <= 65535,
+ * 1 < scale_factor <= 2, 1 <= n_levels <= 8, 1 <= fast_threshold <= 254, 16 <= edge <= 255, channels 1 or 3, rows and cols in
+ * 1..8192, pitch >= cols * channels, n_frames >= 0 (0: O3DR_OK, offsets[0] = 0).  p == NULL: the defaults.  The call
+ * synchronises the stream once, at its end (with O3DR_MEM_HOST the copies into pageable caller memory - offsets, levels_out -
+ * may block inside the runtime before that, as every host-memory call's do); it carves its own scratch block, does not use the sort workspace and leaves cloud_big
+ * alone. */
+#define O3DR_ORB_PATTERN_SEED 0x4F5242ull /* "ORB" */
+#define O3DR_ORB_MAX_SIDE     8192
+#define O3DR_ORB_MAX_LEVELS   8
+typedef struct o3dr_orb_params {
+    int32_t n_features;     /* default 1500; 1..65535, per frame */
+    float   scale_factor;   /* default 1.3f; (1, 2] */
+    int32_t n_levels;       /* default 5; 1..8 */
+    int32_t fast_threshold; /* default 20; 1..254 */
+    int32_t edge;           /* default 31; 16..255: margin inside every level image */
+    int32_t channels;       /* default 3: B G R interleaved; 1: grey */
+} o3dr_orb_params;
+typedef struct o3dr_orb_keypoint {   /* 32 bytes */
+    float    x, y;            /* level-0 pixel coordinates */
+    float    angle_deg, size; /* angle_bin * 5.625; 31 * W / W_l */
+    int64_t  response;        /* the integer Harris response R */
+    int16_t  xl, yl;          /* position in its level image */
+    uint8_t  level, angle_bin;
+    uint16_t reserved;        /* 0 */
+} o3dr_orb_keypoint;
+void o3dr_orb_default_params(o3dr_orb_params* p);
+/* host only, no context: the steered table, 64 * 256 * 4 int8 */
+int  o3dr_orb_pattern(int8_t* out);
+int  o3dr_orb_level_sizes(int32_t rows, int32_t cols, const o3dr_orb_params* p, int32_t* wh, int32_t* quota);
+int  o3dr_orb_detect(o3dr_ctx* ctx, const uint8_t* img, int64_t frame_stride, int64_t pitch, int32_t rows, int32_t cols,
+                     int32_t n_frames, const o3dr_orb_params* p, o3dr_orb_keypoint* kp, float* kp_xy, uint8_t* desc,
+                     int64_t* offsets, uint8_t* levels_out, int64_t out_capacity, int64_t* n_out, int32_t mem);
+
 /* ---- measurement hooks (bench.py; not part of the reference surface) ------------------------ */
 /* kernel ids for o3dr_profile_* */
 #define O3DR_K_COUNT        0  /* grid-pass valid count per tile */
@@ -734,7 +817,12 @@ int  o3dr_plane_fit_disparity(o3dr_ctx* ctx, const uint8_t* disp, int64_t disp_p
 #define O3DR_K_PLANE_DISP_SUMS 9   /* plane-fitted disparity: per-(frame, label) integer sums */
 #define O3DR_K_PLANE_DISP_FIT  10  /* ... the fp64 fit of every (frame, label) */
 #define O3DR_K_PLANE_DISP_EVAL 11  /* ... the f64 image */
-#define O3DR_K_NUM          12
+#define O3DR_K_ORB_PYRAMID    12  /* ORB: grey + pyramid levels */
+#define O3DR_K_ORB_FAST       13  /* ... FAST score map + 5 x 5 box sums */
+#define O3DR_K_ORB_CANDIDATES 14  /* ... suppression, margin, Harris response, ordered compaction */
+#define O3DR_K_ORB_SELECT     15  /* ... radix select of the cut per (frame, level), output offsets */
+#define O3DR_K_ORB_DESCRIBE   16  /* ... orientation + steered BRIEF, one wave per keypoint */
+#define O3DR_K_NUM          17
 /* Bracket every launch of kernel `kernel_id` (or all kernels if -1) with HIP events on the
  * context's stream; 0 launches are bracketed when disabled (the default). */
 int o3dr_profile_enable(o3dr_ctx* ctx, int32_t kernel_id, int32_t enable);

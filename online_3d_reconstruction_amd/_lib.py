@@ -17,8 +17,10 @@ STATUS_LABEL_RANGE = 2
 STATUS_INTERNAL = 0x80000000
 K_COUNT, K_REPROJECT, K_KEYGEN, K_SORT_HIST, K_SORT_SCATTER, K_SEGMENT, K_CENTROID, K_OTHER, K_CENTROID_RUNS = range(9)
 K_PLANE_DISP_SUMS, K_PLANE_DISP_FIT, K_PLANE_DISP_EVAL = 9, 10, 11
+K_ORB_PYRAMID, K_ORB_FAST, K_ORB_CANDIDATES, K_ORB_SELECT, K_ORB_DESCRIBE = 12, 13, 14, 15, 16
 KERNEL_NAMES = ["reproject_count", "reproject_emit", "voxel_keys", "radix_hist", "radix_scatter", "run_segments",
-                "centroid", "other", "centroid_runs", "plane_disp_sums", "plane_disp_fit", "plane_disp_eval"]
+                "centroid", "other", "centroid_runs", "plane_disp_sums", "plane_disp_fit", "plane_disp_eval",
+                "orb_pyramid", "orb_fast", "orb_candidates", "orb_select", "orb_describe"]
 
 
 class O3drError(RuntimeError):
@@ -91,6 +93,18 @@ assert PLANE_DISP_SEGMENT.itemsize == 64
 PLANE_DISP_NONE, PLANE_DISP_MEAN, PLANE_DISP_PLANE = range(3)
 PLANE_DISP_TOL = 2.0 ** -20
 PLANE_DISP_MAX_SIDE, PLANE_DISP_MAX_LABELS = 8192, 65536
+
+
+class OrbParamsStruct(C.Structure):
+    _fields_ = [("n_features", C.c_int32), ("scale_factor", C.c_float), ("n_levels", C.c_int32), ("fast_threshold", C.c_int32),
+                ("edge", C.c_int32), ("channels", C.c_int32)]
+
+
+# o3dr_orb_keypoint (32 bytes), as a numpy record: Context.findFeatures returns the keypoints in this layout
+ORB_KEYPOINT = np.dtype([("x", "<f4"), ("y", "<f4"), ("angle_deg", "<f4"), ("size", "<f4"), ("response", "<i8"), ("xl", "<i2"),
+                         ("yl", "<i2"), ("level", "u1"), ("angle_bin", "u1"), ("reserved", "<u2")])
+assert ORB_KEYPOINT.itemsize == 32
+ORB_MAX_SIDE, ORB_MAX_LEVELS = 8192, 8
 
 
 class MatchParamsStruct(C.Structure):
@@ -186,6 +200,11 @@ SYMBOLS = [
     ("o3dr_plane_disp_default_params", None, [C.POINTER(PlaneDispParamsStruct)]),
     ("o3dr_plane_fit_disparity", C.c_int, [_vp, _vp, _i64, _i64, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32,
                                            C.POINTER(PlaneDispParamsStruct), _vp, _vp, _pu32, _i32]),
+    ("o3dr_orb_default_params", None, [C.POINTER(OrbParamsStruct)]),
+    ("o3dr_orb_pattern", C.c_int, [_vp]),
+    ("o3dr_orb_level_sizes", C.c_int, [_i32, _i32, C.POINTER(OrbParamsStruct), _vp, _vp]),
+    ("o3dr_orb_detect", C.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, C.POINTER(OrbParamsStruct), _vp, _vp, _vp, _vp, _vp, _i64,
+                                  _pi64, _i32]),
     ("o3dr_profile_enable", C.c_int, [_vp, _i32, _i32]),
     ("o3dr_profile_read", C.c_int, [_vp, _i32, C.POINTER(C.c_double), _pi64]),
     ("o3dr_profile_reset", C.c_int, [_vp]),

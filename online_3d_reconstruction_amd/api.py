@@ -517,6 +517,67 @@ class Context:
             ret += (til[:n],)
         return ret
 
+    # -- ORB features (the reference's findFeatures / OrbFeaturesFinder, pose.cpp:127,210) -------------------------------
+    def findFeatures(self, img, n_features=1500, scale_factor=1.3, n_levels=5, fast_threshold=20, edge=31, return_levels=False):
+        """oFAST keypoints and steered-BRIEF descriptors (contract: include/o3dr.h "ORB features").  img: uint8 [H, W] or
+        [F, H, W] grey, [H, W, 3] or [F, H, W, 3] B G R; numpy, or a torch CUDA tensor (the outputs are then CUDA tensors and
+        nothing leaves HBM).  -> (keypoints, kp_xy [n, 2] float32, desc [n, 32] uint8, offsets): keypoints is an
+        ORB_KEYPOINT array (torch: int32 [n, 8], the same bytes); offsets (numpy int64, F + 1) delimits the frames' rows.
+        kp_xy / desc / offsets go straight into matchDescriptors, keypoints3D and accumulateFrames(keypoints=(kp_xy,
+        offsets)) (accumulateFrames splits the pair into per-frame lists on the host: a CUDA kp_xy is read back there).
+        return_levels: a fifth value, every frame's grey pyramid as a flat uint8 array (frame-major, levels back to back,
+        rows tight)."""
+        dev = _is_torch(img)
+        nd = img.dim() if dev else np.ndim(img)
+        ch = 3 if (nd == 4 or (nd == 3 and int(img.shape[-1]) == 3)) else 1
+        if not dev:
+            img = np.asarray(img)
+            assert img.dtype == np.uint8
+        single = nd == (3 if ch == 3 else 2)
+        assert nd in ((3, 4) if ch == 3 else (2, 3))
+        F = 1 if single else int(img.shape[0])
+        rows, cols = (int(img.shape[-3]), int(img.shape[-2])) if ch == 3 else (int(img.shape[-2]), int(img.shape[-1]))
+        if dev:
+            import torch
+            assert img.is_cuda and img.dtype == torch.uint8
+            if img.stride(-1) != 1 or (ch == 3 and img.stride(-2) != 3) or (not single and img.stride(0) < rows * img.stride(-3 if ch == 3 else -2)):
+                img = img.contiguous()
+            pitch, fs = int(img.stride(-3 if ch == 3 else -2)), (0 if single else int(img.stride(0)))
+            mem, pi = L.MEM_DEVICE, img.data_ptr()
+        else:
+            row_axis = -3 if ch == 3 else -2
+            st = img.strides
+            ok = st[-1] == 1 and (ch == 1 or st[-2] == 3) and st[row_axis] >= cols * ch and (single or st[0] >= rows * st[row_axis])
+            if not ok:  # (a padded pitch or frame stride is passed through as it is)
+                img = np.ascontiguousarray(img)
+            pitch, fs = int(img.strides[row_axis]), (0 if single else int(img.strides[0]))
+            mem, pi = L.MEM_HOST, img.ctypes.data
+        prm = L.OrbParamsStruct(int(n_features), float(scale_factor), int(n_levels), int(fast_threshold), int(edge), ch)
+        wh = np.zeros(2 * max(int(n_levels), 1), np.int32)
+        L.check(self._lib.o3dr_orb_level_sizes(rows, cols, C.byref(prm), wh.ctypes.data, None))
+        cap = max(F * int(n_features), 1)
+        n_lev = F * int(sum(int(wh[2 * l]) * int(wh[2 * l + 1]) for l in range(int(n_levels)))) if return_levels else 0
+        if dev:
+            kp = torch.empty((cap, 8), dtype=torch.int32, device=img.device)
+            xy = torch.empty((cap, 2), dtype=torch.float32, device=img.device)
+            desc = torch.empty((cap, 32), dtype=torch.uint8, device=img.device)
+            lev = torch.empty(max(n_lev, 1), dtype=torch.uint8, device=img.device) if return_levels else None
+            self._order_after_torch()
+            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        else:
+            kp = np.empty(cap, L.ORB_KEYPOINT)
+            xy = np.empty((cap, 2), np.float32)
+            desc = np.empty((cap, 32), np.uint8)
+            lev = np.empty(max(n_lev, 1), np.uint8) if return_levels else None
+            ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        off = np.zeros(F + 1, np.int64)
+        n = C.c_int64(0)
+        L.check(self._lib.o3dr_orb_detect(self._h, pi, fs, pitch, rows, cols, F, C.byref(prm), ptr(kp), ptr(xy), ptr(desc),
+                                          off.ctypes.data, ptr(lev), cap, C.byref(n), mem))
+        k = int(n.value)
+        res = (kp[:k], xy[:k], desc[:k], off)
+        return res + (lev[:n_lev],) if return_levels else res
+
     # -- feature matching (BFMatcher NORM_HAMMING knnMatch k=2 + ratio test, pose.h:180 / pose_functions.cpp:2017, and
     #    TransformationEstimationSVD, pose.cpp:213-235) --------------------------------------------------------------------
     @staticmethod
@@ -716,7 +777,8 @@ class Context:
     # -- fan-out / accumulate / final merge ---------------------------------------------------------
     def accumulateFrames(self, disp, bgr, poses, keypoints=None):
         """pose.cpp:365-434 for a stack of frames: disp [F,H,W] u8, bgr [F,H,W,3] u8, poses [F,4,4] f32;
-        keypoints: optional list of F arrays [n_f,2] of (x,y) floats (KeyPoint::pt), used iff jump_pixels != 1."""
+        keypoints: optional list of F arrays [n_f,2] of (x,y) floats (KeyPoint::pt), or findFeatures' (kp_xy, offsets) pair
+        (split into such lists on the host; a CUDA kp_xy is copied back first, which synchronises), used iff jump_pixels != 1."""
         F, rows, cols = disp.shape
         if _is_torch(disp):
             assert disp.is_contiguous() and bgr.is_contiguous() and poses.is_contiguous()
@@ -732,6 +794,12 @@ class Context:
         pb, mem2, _k2 = _ptr(bgr)
         pp, mem3, _k3 = _ptr(poses)
         assert mem == mem2 == mem3
+        if isinstance(keypoints, tuple):  # (kp_xy, offsets) as findFeatures returns them
+            kxy, koff = keypoints
+            if _is_torch(kxy):
+                kxy = kxy.detach().cpu().numpy()
+            kxy = np.asarray(kxy, np.float32).reshape(-1, 2)
+            keypoints = [kxy[int(koff[f]):int(koff[f + 1])] for f in range(F)]
         if keypoints is not None:
             assert len(keypoints) == F
             kps = [np.ascontiguousarray(k, np.float32).reshape(-1, 2) for k in keypoints]

@@ -142,6 +142,9 @@ struct o3dr_ctx {
     // flags / ranges / counters (MlsFlags, PlaneFlags, MeshFlags).
     enum { OP_IN, OP_WORK, OP_LATE, OP_OUT, OP_FLAGS, OP_BUFS };
     DevBuf op[OP_BUFS];
+    DevBuf orb_work, orb_pat;  // o3dr_orb_detect: its own scratch block (one carve per call) and the steered table
+    bool orb_pat_valid = false;
+    std::vector<int8_t> orb_pat_h;  // (outlives the asynchronous upload)
     DevBuf pl_hyp;             // o3dr_segment_plane: hypotheses + scores (plane_hyp_layout), kept for the test hook
     uint64_t pl_last_hyp = 0;  // hypotheses of the last call in pl_hyp (o3dr_test_plane_hypotheses)
     std::vector<MatchPair> mt_tab_h;  // host copies of the match pair table, the rigid fit's segment table and transforms
@@ -458,7 +461,7 @@ extern "C" int o3dr_ctx_destroy(o3dr_ctx* c)
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     for (DevBuf* b : {&c->inc.box, &c->inc.scratch, &c->inc.tg, &c->inc.tmatch, &c->inc.flag, &c->inc.src, &c->inc.keep,
-                      &c->inc.partial, &c->inc.words, &c->inc.fb, &c->nn_q, &c->nn_t, &c->nn_cells, &c->nn_src, &c->pl_hyp})
+                      &c->inc.partial, &c->inc.words, &c->inc.fb, &c->nn_q, &c->nn_t, &c->nn_cells, &c->nn_src, &c->pl_hyp, &c->orb_work, &c->orb_pat})
         dev_release(*b);
     for (DevBuf& b : c->op) dev_release(b);
     delete c;
@@ -3923,6 +3926,241 @@ extern "C" int o3dr_plane_fit_disparity(o3dr_ctx* c, const uint8_t* disp, int64_
                                    n_labels, rows, cols, n_frames, p, out, segments, outs, status, mem);
     });
     if (rc != O3DR_OK) outs.zero();
+    return rc;
+}
+
+// -------------------------------------------------------------------------------------------------
+// ORB features (kernels/orb.inc; DESIGN.md "ORB features")
+// -------------------------------------------------------------------------------------------------
+extern "C" void o3dr_orb_default_params(o3dr_orb_params* p)
+{
+    if (!p) return;
+    p->n_features = 1500;
+    p->scale_factor = 1.3f;
+    p->n_levels = 5;
+    p->fast_threshold = 20;
+    p->edge = 31;
+    p->channels = 3;
+}
+
+static uint64_t orb_splitmix64(uint64_t x)
+{
+    uint64_t z = x + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+extern "C" int o3dr_orb_pattern(int8_t* out)
+{
+    if (!out) return fail(O3DR_ERR_INVALID_ARG, "out is NULL");
+    static const int16_t dir[64][2] = {O3DR_ORB_DIRECTIONS};
+    const uint64_t S = orb_splitmix64(O3DR_ORB_PATTERN_SEED);
+    uint64_t n = 0;
+    int base[256][4];
+    for (int i = 0; i < 256;) {
+        int v[4];
+        for (int k = 0; k < 4; ++k) {
+            int sum = 0;
+            for (int d = 0; d < 4; ++d) sum += (int)((orb_splitmix64(S + n++) >> 32) % 7);
+            v[k] = sum - 12;
+        }
+        if ((v[0] == v[2] && v[1] == v[3]) || v[0] * v[0] + v[1] * v[1] > 169 || v[2] * v[2] + v[3] * v[3] > 169) continue;
+        memcpy(base[i++], v, sizeof v);
+    }
+    for (int k = 0; k < 64; ++k)
+        for (int i = 0; i < 256; ++i)
+            for (int h = 0; h < 2; ++h) {
+                const int px = base[i][2 * h], py = base[i][2 * h + 1];
+                out[((k * 256 + i) * 4) + 2 * h] = (int8_t)((px * dir[k][0] - py * dir[k][1] + 8192) >> 14);
+                out[((k * 256 + i) * 4) + 2 * h + 1] = (int8_t)((px * dir[k][1] + py * dir[k][0] + 8192) >> 14);
+            }
+    return O3DR_OK;
+}
+
+static int orb_check_params(const o3dr_orb_params& p, int32_t rows, int32_t cols)
+{
+    if (rows < 1 || rows > O3DR_ORB_MAX_SIDE || cols < 1 || cols > O3DR_ORB_MAX_SIDE)
+        return fail(O3DR_ERR_INVALID_ARG, "rows and cols must be in 1..8192");
+    if (p.n_features < 1 || p.n_features > 65535) return fail(O3DR_ERR_INVALID_ARG, "n_features must be in 1..65535");
+    if (!(p.scale_factor > 1.f && p.scale_factor <= 2.f)) return fail(O3DR_ERR_INVALID_ARG, "scale_factor must be in (1, 2]");
+    if (p.n_levels < 1 || p.n_levels > O3DR_ORB_MAX_LEVELS) return fail(O3DR_ERR_INVALID_ARG, "n_levels must be in 1..8");
+    if (p.fast_threshold < 1 || p.fast_threshold > 254) return fail(O3DR_ERR_INVALID_ARG, "fast_threshold must be in 1..254");
+    if (p.edge < 16 || p.edge > 255) return fail(O3DR_ERR_INVALID_ARG, "edge must be in 16..255");
+    if (p.channels != 1 && p.channels != 3) return fail(O3DR_ERR_INVALID_ARG, "channels must be 1 or 3");
+    return O3DR_OK;
+}
+
+// level sizes and quotas (include/o3dr.h steps 2 and 5)
+static void orb_levels(const o3dr_orb_params& p, int32_t rows, int32_t cols, int32_t* wh, int32_t* quota)
+{
+    double s = 1.0;
+    int64_t sum_w = 0;
+    for (int l = 0; l < p.n_levels; ++l) {
+        const int64_t sc = l == 0 ? 65536 : (int64_t)floor(65536.0 * s + 0.5);
+        int64_t w = ((int64_t)cols * 65536 + sc / 2) / sc, h = ((int64_t)rows * 65536 + sc / 2) / sc;
+        if (w == 0 || h == 0) w = h = 0;
+        wh[2 * l] = (int32_t)w;
+        wh[2 * l + 1] = (int32_t)h;
+        sum_w += w;
+        s *= (double)p.scale_factor;
+    }
+    int64_t given = 0;
+    for (int l = 0; l < p.n_levels; ++l) {
+        quota[l] = (int32_t)((int64_t)p.n_features * wh[2 * l] / sum_w);
+        given += quota[l];
+    }
+    quota[0] += (int32_t)(p.n_features - given);
+}
+
+extern "C" int o3dr_orb_level_sizes(int32_t rows, int32_t cols, const o3dr_orb_params* p, int32_t* wh, int32_t* quota)
+{
+    o3dr_orb_params prm;
+    o3dr_orb_default_params(&prm);
+    if (p) prm = *p;
+    CHK(orb_check_params(prm, rows, cols));
+    int32_t wh_[2 * O3DR_ORB_MAX_LEVELS], q_[O3DR_ORB_MAX_LEVELS];
+    orb_levels(prm, rows, cols, wh_, q_);
+    if (wh) memcpy(wh, wh_, sizeof(int32_t) * 2 * prm.n_levels);
+    if (quota) memcpy(quota, q_, sizeof(int32_t) * prm.n_levels);
+    return O3DR_OK;
+}
+
+constexpr size_t kOrbScratchBytes = (size_t)1 << 30;  // a group of frames keeps its scratch within this (one frame always fits)
+
+static int orb_detect(o3dr_ctx* c, const uint8_t* img, int64_t fs, int64_t pitch, int32_t rows, int32_t cols, int32_t n_frames,
+                      const o3dr_orb_params* p, o3dr_orb_keypoint* kp, float* kp_xy, uint8_t* desc, Outputs& outs, int64_t* offsets,
+                      uint8_t* levels_out, int64_t out_capacity, int64_t* n_out, int32_t mem)
+{
+    if (!n_out || !offsets) return fail(O3DR_ERR_INVALID_ARG, "n_out / offsets is NULL");
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    if (n_frames < 0) return fail(O3DR_ERR_INVALID_ARG, "bad frame count");
+    o3dr_orb_params prm;
+    o3dr_orb_default_params(&prm);
+    if (p) prm = *p;
+    CHK(orb_check_params(prm, rows, cols));
+    if (n_frames == 0) return O3DR_OK;
+    if (!img) return fail(O3DR_ERR_INVALID_ARG, "img is NULL");
+    if (pitch < (int64_t)cols * prm.channels) return fail(O3DR_ERR_INVALID_ARG, "pitch smaller than a row");
+    if (n_frames > 1 && fs < (int64_t)rows * pitch) return fail(O3DR_ERR_INVALID_ARG, "frame stride smaller than a frame");
+    if ((uintptr_t)kp % 16 || (uintptr_t)desc % 16 || (uintptr_t)kp_xy % 8)
+        return fail(O3DR_ERR_INVALID_ARG, "kp / desc must be 16-byte aligned, kp_xy 8-byte");
+    const int64_t bound = (int64_t)n_frames * prm.n_features;
+    if (out_capacity < bound) return fail(O3DR_ERR_CAPACITY, "out_capacity is below n_frames * n_features");
+
+    OrbArgs a;
+    memset(&a, 0, sizeof a);
+    int32_t wh[2 * O3DR_ORB_MAX_LEVELS], quota[O3DR_ORB_MAX_LEVELS];
+    orb_levels(prm, rows, cols, wh, quota);
+    int64_t tight = 0;  // pixels of a frame's pyramid, levels back to back
+    for (int l = 0; l < prm.n_levels; ++l) {
+        OrbLevel& L = a.lv[l];
+        L.w = wh[2 * l], L.h = wh[2 * l + 1];
+        const int64_t n = (int64_t)L.w * L.h;
+        L.chunks = (int32_t)((n + kOrbChunk - 1) / kOrbChunk);
+        L.chunk0 = a.chunks_per_frame;
+        L.quota = quota[l];
+        L.qprefix = l ? a.lv[l - 1].qprefix + a.lv[l - 1].quota : 0;
+        L.off = a.P;
+        L.cand0 = a.cands_per_frame;
+        // kept corners are never 8-neighbours of each other: at most one per 2 x 2 block of the margin's interior
+        const int64_t iw = L.w - 2 * prm.edge, ih = L.h - 2 * prm.edge;
+        const int64_t cap = iw > 0 && ih > 0 ? ((iw + 1) / 2) * ((ih + 1) / 2) : 0;
+        a.chunks_per_frame += L.chunks;
+        a.P += (int64_t)align256((size_t)n);
+        a.cands_per_frame += (int64_t)align256((size_t)cap);
+        tight += n;
+    }
+    a.rows = rows, a.cols = cols, a.channels = prm.channels, a.n_levels = prm.n_levels, a.n_features = prm.n_features;
+    a.thr = prm.fast_threshold, a.edge = prm.edge;
+    a.fstride = fs, a.pitch = pitch;
+
+    const void* img_d;
+    CHK(stage_in(c, c->op[o3dr_ctx::OP_IN], img, (size_t)fs * (size_t)(n_frames - 1) + (size_t)pitch * (size_t)(rows - 1) + (size_t)cols * prm.channels, mem, &img_d));
+    if (!c->orb_pat_valid) {
+        std::vector<int8_t>& pat = c->orb_pat_h;
+        pat.resize(64 * 256 * 4);
+        CHK(o3dr_orb_pattern(pat.data()));
+        CHK(dev_ensure(c, c->orb_pat, pat.size()));
+        HIPCHK(hipMemcpyAsync(c->orb_pat.p, pat.data(), pat.size(), hipMemcpyHostToDevice, c->stream));
+        c->orb_pat_valid = true;
+    }
+    a.pattern = (const int8_t*)c->orb_pat.p;
+
+    const size_t per_frame = (size_t)a.P * 4 + (size_t)a.cands_per_frame * 12 + (size_t)a.chunks_per_frame * 4 + (size_t)prm.n_levels * 16;
+    size_t group = std::max<size_t>(1, kOrbScratchBytes / per_frame);
+    group = std::min<size_t>(std::min<size_t>(group, (size_t)n_frames), 32768);
+    CHK(carve(c, c->orb_work, [&](Carve& w) {
+        w.take(a.pyr, group * (size_t)a.P);
+        w.take(a.score, group * (size_t)a.P);
+        w.take(a.box, group * (size_t)a.P);
+        w.take(a.chunk_cnt, group * (size_t)a.chunks_per_frame);
+        w.take(a.cand_r, group * (size_t)a.cands_per_frame);
+        w.take(a.cand_pos, group * (size_t)a.cands_per_frame);
+        w.take(a.seg_cand, group * (size_t)prm.n_levels);
+        w.take(a.seg_sel, group * (size_t)prm.n_levels);
+        w.take(a.seg_out, group * (size_t)prm.n_levels);
+        w.take(a.run_total, 1);
+        w.take(a.offsets, (size_t)n_frames + 1);
+    }));
+    outs.set_count(kp, bound);
+    outs.set_count(kp_xy, bound);
+    outs.set_count(desc, bound);
+    CHK(outs.stage(c));
+    a.kp = outs.dev(kp), a.kp_xy = outs.dev(kp_xy), a.desc = outs.dev(desc);
+    if (mem == O3DR_MEM_HOST)  // the rows past *n_out are copied back as well
+        for (int i = 0; i < outs.n; ++i)
+            if (outs.item[i].dev && outs.item[i].count)
+                HIPCHK(hipMemsetAsync(outs.item[i].dev, 0, outs.item[i].count * outs.item[i].elem, c->stream));
+    HIPCHK(hipMemsetAsync(a.run_total, 0, sizeof(long long), c->stream));
+    HIPCHK(hipMemsetAsync(a.offsets, 0, sizeof(long long), c->stream));
+    for (size_t f0 = 0; f0 < (size_t)n_frames; f0 += group) {
+        a.frames = (int32_t)std::min(group, (size_t)n_frames - f0);
+        a.f0 = (int32_t)f0;
+        a.img = (const uint8_t*)img_d + (int64_t)f0 * fs;
+        launch_orb(&c->prof, c->stream, a);
+        if (levels_out) {
+            int64_t done = 0;
+            for (int l = 0; l < prm.n_levels; ++l) {
+                const size_t n = (size_t)a.lv[l].w * a.lv[l].h;
+                if (!n) continue;
+                HIPCHK(hipMemcpy2DAsync(levels_out + (int64_t)f0 * tight + done, (size_t)tight, a.pyr + a.lv[l].off, (size_t)a.P, n,
+                                        (size_t)a.frames, mem == O3DR_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
+                                        c->stream));
+                done += (int64_t)n;
+            }
+        }
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(offsets, a.offsets, sizeof(int64_t) * ((size_t)n_frames + 1), hipMemcpyDeviceToHost, c->stream));
+    CHK(outs.copy_back(c));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *n_out = offsets[n_frames];
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_orb_detect(o3dr_ctx* c, const uint8_t* img, int64_t frame_stride, int64_t pitch, int32_t rows, int32_t cols,
+                               int32_t n_frames, const o3dr_orb_params* p, o3dr_orb_keypoint* kp, float* kp_xy, uint8_t* desc,
+                               int64_t* offsets, uint8_t* levels_out, int64_t out_capacity, int64_t* n_out, int32_t mem)
+{
+    if (n_out) *n_out = 0;
+    if (offsets && n_frames >= 0) memset(offsets, 0, sizeof(int64_t) * ((size_t)n_frames + 1));
+    Outputs outs{mem};
+    outs.add(kp, out_capacity);
+    outs.add(kp_xy, out_capacity);
+    outs.add(desc, out_capacity);
+    // (kp_xy's element is one float: two per row)
+    if (Outputs::Item* it = outs.find(kp_xy)) it->elem = 2 * sizeof(float);
+    if (Outputs::Item* it = outs.find(desc)) it->elem = 32;
+    const int rc = entered(c, [&] {
+        return orb_detect(c, img, frame_stride, pitch, rows, cols, n_frames, p, kp, kp_xy, desc, outs, offsets, levels_out, out_capacity,
+                          n_out, mem);
+    });
+    if (rc != O3DR_OK && rc != O3DR_ERR_CAPACITY) {
+        if (n_out) *n_out = 0;
+        if (offsets && n_frames >= 0) memset(offsets, 0, sizeof(int64_t) * ((size_t)n_frames + 1));
+        outs.zero();
+    }
     return rc;
 }
 

@@ -449,6 +449,59 @@ struct PlaneDispArgs {
     uint32_t* flag;
 };
 void launch_plane_disp(Profiler* pf, hipStream_t s, const PlaneDispArgs& a);
+// ORB features (kernels/orb.inc; contract: include/o3dr.h "ORB features").  One OrbArgs describes a group of `frames`
+// frames.  Per frame the grey pyramid, the FAST score map (u8) and the 5 x 5 box sums (u16) share one layout: level l at
+// element lv[l].off (a multiple of 256), rows tight, `P` elements per frame.  Candidates are found over chunks of
+// kOrbChunk consecutive pixels of a level in row-major order: chunk_cnt holds chunks_per_frame words per frame (counts,
+// then their exclusive scan per level), cand_r / cand_pos cands_per_frame slots per frame (level l from lv[l].cand0,
+// row-major order; pos = y << 16 | x).  The selection compacts a (frame, level) segment's kept candidates to the front of
+// its slots.  seg_cand / seg_sel / seg_out: frames * n_levels entries (candidates, kept, first output row).
+constexpr int kOrbMaxLevels = 8;
+constexpr int kOrbChunk = 1024;
+// D[k] = (round(16384 cos(2 pi k / 64)), round(16384 sin(2 pi k / 64))), k = 0..63
+#define O3DR_ORB_DIRECTIONS                                                                                                  \
+    {16384, 0}, {16305, 1606}, {16069, 3196}, {15679, 4756}, {15137, 6270}, {14449, 7723}, {13623, 9102}, {12665, 10394},    \
+    {11585, 11585}, {10394, 12665}, {9102, 13623}, {7723, 14449}, {6270, 15137}, {4756, 15679}, {3196, 16069},               \
+    {1606, 16305}, {0, 16384}, {-1606, 16305}, {-3196, 16069}, {-4756, 15679}, {-6270, 15137}, {-7723, 14449},               \
+    {-9102, 13623}, {-10394, 12665}, {-11585, 11585}, {-12665, 10394}, {-13623, 9102}, {-14449, 7723}, {-15137, 6270},       \
+    {-15679, 4756}, {-16069, 3196}, {-16305, 1606}, {-16384, 0}, {-16305, -1606}, {-16069, -3196}, {-15679, -4756},          \
+    {-15137, -6270}, {-14449, -7723}, {-13623, -9102}, {-12665, -10394}, {-11585, -11585}, {-10394, -12665},                 \
+    {-9102, -13623}, {-7723, -14449}, {-6270, -15137}, {-4756, -15679}, {-3196, -16069}, {-1606, -16305}, {0, -16384},       \
+    {1606, -16305}, {3196, -16069}, {4756, -15679}, {6270, -15137}, {7723, -14449}, {9102, -13623}, {10394, -12665},         \
+    {11585, -11585}, {12665, -10394}, {13623, -9102}, {14449, -7723}, {15137, -6270}, {15679, -4756}, {16069, -3196},        \
+    {16305, -1606}
+struct OrbLevel {
+    int32_t w, h;        // 0 x 0: the level does not exist
+    int32_t chunks;      // ceil(w * h / kOrbChunk)
+    int32_t chunk0;      // its first chunk within a frame
+    int32_t quota;       // keypoints kept at most
+    int32_t qprefix;     // sum of the quotas of the levels before it
+    int64_t off;         // first element within a frame's pyramid
+    int64_t cand0;       // first candidate slot within a frame
+};
+struct OrbArgs {
+    const uint8_t* img;
+    int64_t fstride, pitch;
+    int32_t rows, cols, channels, frames, n_levels, n_features, thr, edge;
+    OrbLevel lv[kOrbMaxLevels];
+    int64_t P, cands_per_frame;
+    int32_t chunks_per_frame;
+    int32_t f0;               // index of the group's first frame in the call
+    uint8_t *pyr, *score;
+    uint16_t* box;
+    uint32_t* chunk_cnt;
+    long long* cand_r;
+    uint32_t* cand_pos;
+    uint32_t *seg_cand, *seg_sel;
+    long long* seg_out;
+    long long* run_total;     // device word: keypoints of the groups before this one
+    long long* offsets;       // device copy of the call's offsets (n_frames + 1)
+    const int8_t* pattern;    // the steered table, 64 x 256 x 4
+    o3dr_orb_keypoint* kp;    // each nullptr: not asked for
+    float* kp_xy;
+    uint8_t* desc;
+};
+void launch_orb(Profiler* pf, hipStream_t s, const OrbArgs& a);
 void launch_partition(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelArgs& v, int n_parts, o3dr_point* out,
                       uint64_t* counts_dev, uint32_t* overflow_dev, const void* hdrs_dev = nullptr, int n_hdrs = 0);
 // its two halves: slice sizes without moving anything (the (part, tile) table stays in ws for the second half), then the move

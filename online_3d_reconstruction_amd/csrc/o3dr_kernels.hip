@@ -33,6 +33,7 @@
 //   plane        RANSAC plane segmentation per XY tile
 //   mesh         height-field surface mesh over the XY cells
 //   match        Hamming 2-NN descriptor matching, index-aligned 3-D keypoints, the batched rigid fit
+//   orb          ORB features: grey pyramid, FAST score + box sums, candidates, exact selection, steered BRIEF
 // The launchers follow in this file.
 #include <string.h>
 
@@ -59,6 +60,7 @@ namespace o3dr {
 #include "kernels/mesh.inc"
 #include "kernels/match.inc"
 #include "kernels/plane_disparity.inc"
+#include "kernels/orb.inc"
 
 // =================================================================================================
 // launchers
@@ -636,6 +638,46 @@ void launch_plane_disp(Profiler* pf, hipStream_t s, const PlaneDispArgs& a)
         if (a.elem == 1) plane_disp_frames<uint8_t>(pf, s, a, f0, nf);
         else if (a.elem == 2) plane_disp_frames<uint16_t>(pf, s, a, f0, nf);
         else plane_disp_frames<uint32_t>(pf, s, a, f0, nf);
+    }
+}
+
+// ORB features of one group of frames (a.frames <= 65535: the grid's y extent)
+void launch_orb(Profiler* pf, hipStream_t s, const OrbArgs& a)
+{
+    if (a.frames <= 0) return;
+    const int F = a.frames;
+    {
+        ProfScope ps(pf, O3DR_K_ORB_PYRAMID, s);
+        const int64_t n0 = (int64_t)a.rows * a.cols;
+        if (a.channels == 3)
+            k_orb_level0<3, 4><<<dim3(cdiv64(n0, 256 * 4), F), 256, 0, s>>>(a);
+        else
+            k_orb_level0<1, 16><<<dim3(cdiv64(n0, 256 * 16), F), 256, 0, s>>>(a);
+        for (int l = 1; l < a.n_levels; ++l)
+            if (a.lv[l].chunks > 0) k_orb_down<<<dim3(cdiv64((int64_t)a.lv[l].w * a.lv[l].h, 256 * 4), F), 256, 0, s>>>(a, l);
+    }
+    {
+        ProfScope ps(pf, O3DR_K_ORB_FAST, s);
+        for (int l = 0; l < a.n_levels; ++l) {
+            if (a.lv[l].chunks == 0) continue;
+            const int tiles_x = cdiv64(a.lv[l].w, kOrbTileX), tiles_y = cdiv64(a.lv[l].h, kOrbTileY);
+            k_orb_fast<<<dim3(tiles_x * tiles_y, F), 256, 0, s>>>(a, l, tiles_x);
+        }
+    }
+    {
+        ProfScope ps(pf, O3DR_K_ORB_CANDIDATES, s);
+        k_orb_candidates<false><<<dim3(a.chunks_per_frame, F), 256, 0, s>>>(a);
+        k_orb_scan<<<dim3(a.n_levels, F), 256, 0, s>>>(a);
+        k_orb_candidates<true><<<dim3(a.chunks_per_frame, F), 256, 0, s>>>(a);
+    }
+    {
+        ProfScope ps(pf, O3DR_K_ORB_SELECT, s);
+        k_orb_select<<<dim3(a.n_levels, F), 256, 0, s>>>(a);
+        k_orb_offsets<<<1, 256, 0, s>>>(a);
+    }
+    {
+        ProfScope ps(pf, O3DR_K_ORB_DESCRIBE, s);
+        k_orb_describe<<<cdiv64((int64_t)F * a.n_features, kOrbDescWaves), 64 * kOrbDescWaves, 0, s>>>(a);
     }
 }
 

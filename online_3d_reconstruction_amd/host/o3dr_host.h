@@ -72,7 +72,8 @@ public:
 class ImageData {  // pose.h:73-85 (the hot-path fields)
 public:
     RawImageData* raw_img_data_ptr = nullptr;
-    std::vector<float> keypoints_xy;  // features.keypoints pt.x,pt.y pairs; empty: no ORB in this build
+    std::vector<float> keypoints_xy;  // features.keypoints pt.x,pt.y pairs, from --keypoints_dir; empty: none given
+                                      // (--gpu_keypoints makes a batch's keypoints with o3dr_orb_detect instead)
     Matrix4 t_mat_MAVLink{}, t_mat_FeatureMatched{};
 };
 
@@ -96,7 +97,7 @@ public:
     bool sor = true;                // statistical outlier removal of the per-frame path (pose_functions.cpp:1673-1686:
                                     // always on in the reference when jump_pixels > 0); `--sor 0` switches it off
     std::string keypointsPrefix;    // --keypoints_dir: <img_num>.txt with one "x y" pair per line (KeyPoint::pt of the
-                                    // frame's ORB features, which this build does not compute); empty = no keypoints
+                                    // frame's ORB features, e.g. the files --find_features writes); empty = no keypoints
     std::array<double, 16> Q{};
     std::string calib_file = "cam13calib.yml";
     std::string dataFilesPrefix = "data_files/", imagePrefix = "images/", disparityPrefix = "disparities/";
@@ -132,6 +133,12 @@ public:
     std::string segmentLabelsPrefix = "segmentlabels/";  // --segment_labels_dir: <img_num>.png, 8- or 16-bit greyscale
     int plane_min_pixels = 3;         // --plane_min_pixels
     double plane_max_mse = 0.0;       // --plane_max_mse (0: no gate)
+    std::string find_features_png;    // --find_features image.png: ORB keypoints of one image (o3dr_orb_detect), printed per
+                                      // level and written as <image>.keypoints.txt in the --keypoints_dir format
+    bool gpu_keypoints = false;       // --gpu_keypoints: with jump_pixels != 1 and no --keypoints_dir, every batch's keypoints
+                                      // come from o3dr_orb_detect on its rgb images (single-GPU batched path)
+    int orb_n_features = 1500, orb_levels = 5, orb_fast_threshold = 20;  // --orb_n_features, --orb_levels, --orb_fast_threshold
+    float orb_scale = 1.3f;           // --orb_scale
     std::string print_label_png;      // --print_label_png f: rows, cols and the labels of f as text (checks the reader)
 
     std::vector<RawImageData> rawImageDataVec;
@@ -166,6 +173,8 @@ private:
     void run_smooth_surface();                      // --smooth_surface
     void run_segment_cloud();                       // --segment_cloud_only
     void run_mesh_surface();                        // --mesh_surface
+    void run_find_features();                       // --find_features
+    o3dr_orb_params orb_params() const;             // the --orb_* flags over the defaults
     int first_img_num = -1, last_img_num = -1;
     bool run3d_reconstruction = true;
     bool disparity_f64 = false;  // what push_params sets: on around the accumulate call of a plane-fitted batch

@@ -420,6 +420,11 @@ void Pose::printUsage()
             "                     the occupied XY cells of size m, edges up to L: writes every point, in input order, and the\n"
             "                     triangles as mesh_<file> next to it - that file name is this build's own; --search_radius is\n"
             "                     required here; --mesh_normals adds nx ny nz per vertex)\n"
+            "./pose --find_features image.png [--orb_n_features n] [--orb_levels n] [--orb_scale s] [--orb_fast_threshold t]\n"
+            "                     (ORB keypoints of one image: prints the count per level and writes one \"x y\" per line as\n"
+            "                     <image>.keypoints.txt, the --keypoints_dir format - the flags and the file name are this build's own)\n"
+            "       [--gpu_keypoints]  (reconstruction run with jump_pixels != 1 and no --keypoints_dir: every batch's keypoints come\n"
+            "                     from the same extractor on its rgb images, with the --orb_* flags; single-GPU batched path only)\n"
             "Pose estimation (ORB matching, the ICP trajectory correction), visualisation and --segment_cloud in a reconstruction\n"
             "run are not part of this build.\n";
 }
@@ -507,6 +512,17 @@ int Pose::parseCmdArgs(int argc, char** argv)
         else if (a == "--segment_labels_dir") segmentLabelsPrefix = need(i);
         else if (a == "--plane_min_pixels") plane_min_pixels = atoi(need(i));
         else if (a == "--plane_max_mse") plane_max_mse = atof(need(i));
+        else if (a == "--find_features") {
+            if (i + 1 >= argc || string(argv[i + 1]).rfind("--", 0) == 0)
+                throw runtime_error("missing argument: --find_features needs image.png");
+            find_features_png = argv[++i];
+            run3d_reconstruction = false;
+        }
+        else if (a == "--gpu_keypoints") gpu_keypoints = true;
+        else if (a == "--orb_n_features") orb_n_features = atoi(need(i));
+        else if (a == "--orb_levels") orb_levels = atoi(need(i));
+        else if (a == "--orb_scale") orb_scale = (float)atof(need(i));
+        else if (a == "--orb_fast_threshold") orb_fast_threshold = atoi(need(i));
         else if (a == "--print_label_png") { print_label_png = need(i); run3d_reconstruction = false; }
         else if (a == "--segment_cloud" || a == "--displayUAVPositions" ||
                  a == "--test_bad_data_rejection")
@@ -522,6 +538,10 @@ int Pose::parseCmdArgs(int argc, char** argv)
         if (n_gpus > 1 || partitioned_merge) throw runtime_error("--use_segment_labels is not available with --gpus N > 1 / --partitioned_merge");
         if (reference_fanout) throw runtime_error("--use_segment_labels is not available with --reference_fanout");
         if (blur_kernel > 1) throw runtime_error("--use_segment_labels cannot be combined with --blur_kernel > 1 (cv::bilateralFilter rejects CV_64F)");
+    }
+    if (run3d_reconstruction && gpu_keypoints) {
+        if (n_gpus > 1 || partitioned_merge) throw runtime_error("--gpu_keypoints is not available with --gpus N > 1 / --partitioned_merge");
+        if (reference_fanout) throw runtime_error("--gpu_keypoints is not available with --reference_fanout");
     }
     if (run3d_reconstruction) {
         if (n_imgs == 0) throw runtime_error("first and last image number are required");
@@ -718,6 +738,46 @@ void Pose::run_mesh_surface()
     cerr << "Saved mesh with " << n << " vertices and " << n_tris << " faces to " << outp << endl;
 }
 
+o3dr_orb_params Pose::orb_params() const
+{
+    o3dr_orb_params p;
+    o3dr_orb_default_params(&p);
+    p.n_features = orb_n_features;
+    p.n_levels = orb_levels;
+    p.scale_factor = orb_scale;
+    p.fast_threshold = orb_fast_threshold;
+    return p;
+}
+
+// findFeatures' first half for one image (pose.cpp:127,210: OpenCV's OrbFeaturesFinder), here o3dr_orb_detect (contract:
+// include/o3dr.h "ORB features").  Prints the keypoints per pyramid level and writes KeyPoint::pt, one "x y" per line with
+// %.9g (a float's exact round trip), as <image>.keypoints.txt: what --keypoints_dir reads as <img_num>.txt.
+void Pose::run_find_features()
+{
+    Q = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // the tool needs no camera
+    const Image8 im = read_png(find_features_png, false);
+    if (im.empty()) throw runtime_error("could not read " + find_features_png);
+    const o3dr_orb_params prm = orb_params();
+    const int64_t cap = prm.n_features > 0 ? prm.n_features : 1;
+    vector<o3dr_orb_keypoint> kp((size_t)cap);
+    vector<float> xy((size_t)cap * 2);
+    int64_t off[2] = {0, 0}, n = 0;
+    o3dr_ctx* c = ctx_for_this_thread();
+    chk(o3dr_orb_detect(c, im.data.data(), 0, im.pitch(), im.rows, im.cols, 1, &prm, kp.data(), xy.data(), nullptr, off, nullptr, cap, &n,
+                        O3DR_MEM_HOST),
+        "o3dr_orb_detect");
+    vector<int64_t> per_level((size_t)(prm.n_levels > 0 ? prm.n_levels : 1), 0);
+    for (int64_t i = 0; i < n; ++i) per_level[kp[(size_t)i].level]++;
+    cout << "image " << im.rows << " x " << im.cols << ", keypoints " << n << endl;
+    for (size_t l = 0; l < per_level.size(); ++l) cout << "level " << l << ": " << per_level[l] << endl;
+    const string outp = find_features_png + ".keypoints.txt";
+    FILE* f = fopen(outp.c_str(), "w");
+    if (!f) throw runtime_error("could not write " + outp);
+    for (int64_t i = 0; i < n; ++i) fprintf(f, "%.9g %.9g\n", xy[(size_t)(2 * i)], xy[(size_t)(2 * i + 1)]);
+    fclose(f);
+    cerr << "Saved " << n << " keypoints to " << outp << endl;
+}
+
 // pose.cpp:23-565 restricted to the hot path
 Pose::Pose(int argc, char* argv[])
 {
@@ -748,6 +808,10 @@ Pose::Pose(int argc, char* argv[])
     }
     if (mesh_surface) {
         run_mesh_surface();
+        return;
+    }
+    if (!find_features_png.empty()) {
+        run_find_features();
         return;
     }
     if (!print_label_png.empty()) {  // what read_png_labels makes of one file: "rows cols", then one row of labels per line
@@ -858,6 +922,23 @@ void Pose::run_reconstruction()
             // page-locked frame stacks cross PCIe by DMA (best effort: pageable memory works too)
             const bool reg_disp = o3dr_host_register(disp.data(), (int64_t)disp.size()) == O3DR_OK;
             const bool reg_bgr = o3dr_host_register(bgr.data(), (int64_t)bgr.size()) == O3DR_OK;
+            // --gpu_keypoints: the batch's keypoint lists from the ORB extractor instead of files (the list the reference's
+            // ORB stage leaves in features.keypoints, pose_functions.cpp:1057-1061)
+            int rc_orb = O3DR_OK;
+            string why_orb;
+            if (gpu_keypoints && jump_pixels != 1 && keypointsPrefix.empty()) {
+                const o3dr_orb_params prm = orb_params();
+                const int64_t cap = (int64_t)n_acc * (prm.n_features > 0 ? prm.n_features : 1);
+                kp_xy.assign((size_t)cap * 2, 0.f);
+                int64_t n_kp = 0;
+                const auto tk = clk::now();
+                rc_orb = o3dr_orb_detect(c, bgr.data(), (int64_t)csz, 3 * (int64_t)cols, rows, cols, (int32_t)n_acc, &prm, nullptr, kp_xy.data(),
+                                         nullptr, kp_off.data(), nullptr, cap, &n_kp, O3DR_MEM_HOST);
+                if (rc_orb != O3DR_OK) why_orb = o3dr_last_error();
+                kp_xy.resize((size_t)n_kp * 2);
+                cout << "\nORB keypoints: " << n_kp << " in " << n_acc << " frames, " << chrono::duration<double>(clk::now() - tk).count()
+                     << " sec" << flush;
+            }
             // --use_segment_labels: the batch's 8-bit disparities become plane-fitted CV_64F images first
             vector<double> fitted;
             int rc_fit = O3DR_OK;
@@ -887,12 +968,12 @@ void Pose::run_reconstruction()
             }
             const uint8_t* disp_in = use_segment_labels ? (const uint8_t*)fitted.data() : disp.data();
             const int64_t esz = use_segment_labels ? 8 : 1;
-            const int rc_acc = rc_fit != O3DR_OK ? rc_fit
+            const int rc_acc = rc_orb != O3DR_OK ? rc_orb : rc_fit != O3DR_OK ? rc_fit
                                                  : o3dr_accumulate_frames_kp(c, disp_in, esz * (int64_t)dsz, esz * cols, bgr.data(), (int64_t)csz,
                                                                              3 * (int64_t)cols, rows, cols, poses.data(), (int32_t)n_acc,
                                                                              kp_xy.empty() ? nullptr : kp_xy.data(),
                                                                              kp_xy.empty() ? nullptr : kp_off.data(), O3DR_MEM_HOST);
-            const string why_acc = rc_fit != O3DR_OK ? "plane_fit_disparity: " + why_fit : (rc_acc != O3DR_OK ? o3dr_last_error() : "");
+            const string why_acc = rc_orb != O3DR_OK ? "orb_detect: " + why_orb : rc_fit != O3DR_OK ? "plane_fit_disparity: " + why_fit : (rc_acc != O3DR_OK ? o3dr_last_error() : "");
             if (use_segment_labels) {
                 disparity_f64 = false;
                 push_params(c);
