@@ -803,6 +803,75 @@ int  o3dr_orb_detect(o3dr_ctx* ctx, const uint8_t* img, int64_t frame_stride, in
                      int32_t n_frames, const o3dr_orb_params* p, o3dr_orb_keypoint* kp, float* kp_xy, uint8_t* desc,
                      int64_t* offsets, uint8_t* levels_out, int64_t out_capacity, int64_t* n_out, int32_t mem);
 
+/* ---- pose chain: the reference's default mode (pose.cpp:213-235, generate_tf_of_Matched_Keypoints): every frame gets its
+ * pose from descriptor matches against earlier nearby frames, whose keypoints are moved by THEIR fitted poses - a serial
+ * chain.  The reference's selection rules and PCL's rounding cannot be pinned here, so the contract below is this library's
+ * own; tests/pose_chain_reference.py restates it in numpy.
+ *
+ * Inputs.  desc ([N, 32] bytes) and kp3 (N points, index-aligned with desc: o3dr_keypoints_3d with poses = NULL; a row
+ * with a NaN is a rejected keypoint) in `mem`; frame f's rows are [offsets[f], offsets[f+1]) (HOST, n_frames + 1
+ * non-decreasing entries, offsets[0] >= 0: o3dr_orb_detect's offsets).  prior_poses (HOST, [n_frames, 16] fp32 row-major
+ * 4x4): the recorded pose of every frame.  The first n_fixed frames are history: poses_in ([n_fixed, 16] fp32) and
+ * status_in ([n_fixed] int32, each an O3DR_CHAIN_* value), both HOST, are copied to the outputs unchanged and the chain
+ * starts at frame n_fixed.
+ *   1. Static pair list, a function of prior_poses and the parameters alone, built on the host before any kernel runs:
+ *      frame i is paired with every j < i whose prior translation (T[3], T[7], T[11], taken in fp64) lies within
+ *      dist_nearby of frame i's (squared distance ((dx dx + dy dy) + dz dz) <= dist_nearby^2 in fp64); of those the
+ *      range_width largest j are kept, listed in descending j.  j may be a history frame; the list of a frame does not
+ *      depend on n_fixed.  The call's list holds the pairs of the frames n_fixed .. n_frames - 1, in frame order.
+ *   2. Matching: one batched o3dr_match_knn2_hamming pass over that list (query set i, train set j; ratio, max_distance).
+ *   3. Chain, for i = n_fixed .. n_frames - 1 in order.  No pair: O3DR_CHAIN_ANCHOR, the pose is the prior, the frame is
+ *      accepted.  Else its slots are (pair, query row), pair-major in list order; a slot is used iff frame j is accepted
+ *      (ANCHOR or MATCHED), the row is good, src = kp3[i][row] is finite and tgt is finite, tgt = kp3[j][train_idx[0]] moved
+ *      by frame j's fp32 output pose in A2's arithmetic (fp32, ((m0 x + m1 y) + m2 z) + m3, no contraction).
+ *      n_used < min_matches: O3DR_CHAIN_TOO_FEW.  Else the 16 fp64 moments of o3dr_estimate_rigid_transform step 2 about
+ *      c0 = the first used tgt, summed per run of 256 consecutive slots from the frame's first slot (wave sums, the run =
+ *      the tree of its four waves) and folded over the runs left to right - no float atomics; the Kabsch of step 3 (same
+ *      Jacobi, same rank test, reflection corrected): rank < 2 gives O3DR_CHAIN_DEGENERATE; rms = sqrt(mean |T src -
+ *      tgt|^2) in fp64 over the same partition and fold; !(rms <= max_rms): O3DR_CHAIN_RMS; else O3DR_CHAIN_MATCHED with
+ *      the pose fp32(T), bottom row 0 0 0 1.  Every rejected frame (TOO_FEW, DEGENERATE, RMS) keeps its prior as its pose
+ *      and is never a train frame of a later one.
+ * Outputs.  poses_out ([n_frames, 16] fp32, `mem`).  frames_out (HOST, n_frames records): status; n_pairs;
+ * n_pairs_accepted (pairs whose train frame is accepted); n_good (good rows over the accepted train frames); n_used; rms (the
+ * fit's, also when it failed the gate; else 0); T (3 x 4 row-major fp64: the fit when MATCHED, else the frame's pose
+ * widened).  A history frame's record is its status_in, its pose widened and zeros.  pairs_out (HOST, or NULL): the list as
+ * int32 (query, train) frame pairs; *n_pairs_out (or NULL) = its length; pairs_capacity (in pairs) below it with pairs_out
+ * given: O3DR_ERR_CAPACITY with *n_pairs_out set and nothing else written.
+ * Records and poses are bit-identical across calls, across host and device memory and across any split into history and
+ * new frames (feeding a call's poses and statuses back as poses_in / status_in).
+ * Limits, else O3DR_ERR_INVALID_ARG (host outputs zeroed): 0 <= n_fixed <= n_frames (n_frames == 0: O3DR_OK), dist_nearby
+ * finite and >= 0, 1 <= range_width <= 32, min_matches >= 3, max_rms > 0 (+inf: no gate), ratio and max_distance as in
+ * o3dr_match_params, status_in within the enum, the pool at most 2^31-1 rows, a frame's slots (pairs x rows) at most
+ * 2^31-1.  p == NULL: the defaults.  The call synchronises once, at its end; it does not use the sort workspace and leaves
+ * cloud_big alone. */
+typedef struct o3dr_chain_params {
+    double  dist_nearby;    /* default 2.0 (metres; this build's own) */
+    double  max_rms;        /* default +inf: no gate */
+    int32_t range_width;    /* default 8; 1..32 */
+    int32_t min_matches;    /* default 30; >= 3 */
+    float   ratio;          /* default 0.5 */
+    int32_t max_distance;   /* default 40 */
+} o3dr_chain_params;
+typedef struct o3dr_chain_frame {  /* 128 bytes */
+    int32_t status;            /* O3DR_CHAIN_* */
+    int32_t n_pairs, n_pairs_accepted;
+    int32_t n_good, n_used;
+    int32_t reserved;          /* 0 */
+    double  rms;
+    double  T[12];
+} o3dr_chain_frame;
+#define O3DR_CHAIN_ANCHOR     0
+#define O3DR_CHAIN_MATCHED    1
+#define O3DR_CHAIN_TOO_FEW    2
+#define O3DR_CHAIN_DEGENERATE 3
+#define O3DR_CHAIN_RMS        4
+#define O3DR_CHAIN_MAX_RANGE  32
+void o3dr_chain_default_params(o3dr_chain_params* p);
+int  o3dr_pose_chain(o3dr_ctx* ctx, const uint8_t* desc, const int64_t* offsets, const o3dr_point* kp3, const float* prior_poses,
+                     int32_t n_frames, int32_t n_fixed, const float* poses_in, const int32_t* status_in, const o3dr_chain_params* p,
+                     float* poses_out, o3dr_chain_frame* frames_out, int32_t* pairs_out, int64_t pairs_capacity, int64_t* n_pairs_out,
+                     int32_t mem);
+
 /* ---- measurement hooks (bench.py; not part of the reference surface) ------------------------ */
 /* kernel ids for o3dr_profile_* */
 #define O3DR_K_COUNT        0  /* grid-pass valid count per tile */
@@ -822,7 +891,9 @@ int  o3dr_orb_detect(o3dr_ctx* ctx, const uint8_t* img, int64_t frame_stride, in
 #define O3DR_K_ORB_CANDIDATES 14  /* ... suppression, margin, Harris response, ordered compaction */
 #define O3DR_K_ORB_SELECT     15  /* ... radix select of the cut per (frame, level), output offsets */
 #define O3DR_K_ORB_DESCRIBE   16  /* ... orientation + steered BRIEF, one wave per keypoint */
-#define O3DR_K_NUM          17
+#define O3DR_K_MATCH          17  /* Hamming 2-NN: chunk scans + fold (o3dr_match_knn2_hamming, o3dr_pose_chain) */
+#define O3DR_K_POSE_CHAIN     18  /* pose chain: the one-workgroup walk over the frames */
+#define O3DR_K_NUM          19
 /* Bracket every launch of kernel `kernel_id` (or all kernels if -1) with HIP events on the
  * context's stream; 0 launches are bracketed when disabled (the default). */
 int o3dr_profile_enable(o3dr_ctx* ctx, int32_t kernel_id, int32_t enable);

@@ -18,9 +18,10 @@ STATUS_INTERNAL = 0x80000000
 K_COUNT, K_REPROJECT, K_KEYGEN, K_SORT_HIST, K_SORT_SCATTER, K_SEGMENT, K_CENTROID, K_OTHER, K_CENTROID_RUNS = range(9)
 K_PLANE_DISP_SUMS, K_PLANE_DISP_FIT, K_PLANE_DISP_EVAL = 9, 10, 11
 K_ORB_PYRAMID, K_ORB_FAST, K_ORB_CANDIDATES, K_ORB_SELECT, K_ORB_DESCRIBE = 12, 13, 14, 15, 16
+K_MATCH, K_POSE_CHAIN = 17, 18
 KERNEL_NAMES = ["reproject_count", "reproject_emit", "voxel_keys", "radix_hist", "radix_scatter", "run_segments",
                 "centroid", "other", "centroid_runs", "plane_disp_sums", "plane_disp_fit", "plane_disp_eval",
-                "orb_pyramid", "orb_fast", "orb_candidates", "orb_select", "orb_describe"]
+                "orb_pyramid", "orb_fast", "orb_candidates", "orb_select", "orb_describe", "match", "pose_chain"]
 
 
 class O3drError(RuntimeError):
@@ -124,6 +125,20 @@ MATCH_NONE = 0xFFFFFFFF
 RIGID_OK, RIGID_TOO_FEW, RIGID_DEGENERATE = range(3)
 
 
+class ChainParamsStruct(C.Structure):
+    _fields_ = [("dist_nearby", C.c_double), ("max_rms", C.c_double), ("range_width", C.c_int32), ("min_matches", C.c_int32),
+                ("ratio", C.c_float), ("max_distance", C.c_int32)]
+
+
+# o3dr_chain_frame (128 bytes), as a numpy record: Context.poseChain returns one per frame
+CHAIN_FRAME = np.dtype([("status", "<i4"), ("n_pairs", "<i4"), ("n_pairs_accepted", "<i4"), ("n_good", "<i4"), ("n_used", "<i4"),
+                        ("reserved", "<i4"), ("rms", "<f8"), ("T", "<f8", (12,))])
+assert CHAIN_FRAME.itemsize == 128
+CHAIN_ANCHOR, CHAIN_MATCHED, CHAIN_TOO_FEW, CHAIN_DEGENERATE, CHAIN_RMS = range(5)
+CHAIN_STATUS_NAMES = ["ANCHOR", "MATCHED", "TOO_FEW", "DEGENERATE", "RMS"]
+CHAIN_MAX_RANGE = 32
+
+
 def lib_path():
     return _LIB
 
@@ -204,6 +219,9 @@ SYMBOLS = [
     ("o3dr_orb_pattern", C.c_int, [_vp]),
     ("o3dr_orb_level_sizes", C.c_int, [_i32, _i32, C.POINTER(OrbParamsStruct), _vp, _vp]),
     ("o3dr_orb_detect", C.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, C.POINTER(OrbParamsStruct), _vp, _vp, _vp, _vp, _vp, _i64,
+                                  _pi64, _i32]),
+    ("o3dr_chain_default_params", None, [C.POINTER(ChainParamsStruct)]),
+    ("o3dr_pose_chain", C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, C.POINTER(ChainParamsStruct), _vp, _vp, _vp, _i64,
                                   _pi64, _i32]),
     ("o3dr_profile_enable", C.c_int, [_vp, _i32, _i32]),
     ("o3dr_profile_read", C.c_int, [_vp, _i32, C.POINTER(C.c_double), _pi64]),

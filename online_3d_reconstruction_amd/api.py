@@ -720,6 +720,65 @@ class Context:
         res = self.estimateRigidTransform(kq, tgt, mask=keep)
         return rec, keep, res
 
+    # -- pose chain (the reference's default mode: generate_tf_of_Matched_Keypoints per frame, pose.cpp:213-235) -----------
+    def poseChain(self, desc, offsets, kp3, prior_poses, n_fixed=0, poses_in=None, status_in=None, dist_nearby=2.0, range_width=8,
+                  min_matches=30, max_rms=float("inf"), ratio=0.5, max_distance=40, return_pairs=False):
+        """Every frame's pose from descriptor matches against earlier nearby frames (contract: include/o3dr.h "pose chain",
+        DESIGN.md "Pose chain"): the static pair list from prior_poses, one batched matching pass, one launch that walks the
+        frames n_fixed .. F - 1 in order.  desc uint8 [N, 32], kp3 N points in the camera frame (keypoints3D with poses=None),
+        offsets the F + 1 row offsets (findFeatures'); all numpy, or desc / kp3 torch CUDA tensors.  prior_poses [F, 4, 4];
+        the first n_fixed frames are history with poses_in [n_fixed, 4, 4] and status_in [n_fixed] (an earlier call's
+        outputs).  These three are read on the host (a CUDA tensor is copied back first).
+        -> (poses [F, 4, 4] float32: numpy, or a CUDA tensor for CUDA inputs; records: a numpy CHAIN_FRAME array, one per
+        frame), and with return_pairs the pair list, int32 [P, 2] (query frame, train frame)."""
+        desc, n = self._desc(desc)
+        kp3, n3 = self._cloud(kp3)
+        assert n == n3, "kp3 must be index-aligned with desc"
+        pd, mem, _k = _ptr(desc)
+        pk, mem2, _k2 = _ptr(kp3)
+        if n:
+            assert mem == mem2, "desc and kp3 must live in the same memory"
+        host = lambda a, dt: np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else a, dt)  # noqa: E731
+        off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        F = len(off) - 1
+        prior = host(prior_poses, np.float32).reshape(-1, 16)
+        assert F >= 0 and len(prior) == F, "one prior pose per frame"
+        n_fixed = int(n_fixed)
+        pin = host(poses_in, np.float32).reshape(-1, 16) if poses_in is not None else np.zeros((0, 16), np.float32)
+        sin = host(status_in, np.int32).reshape(-1) if status_in is not None else np.zeros(0, np.int32)
+        if 0 < n_fixed <= F:
+            assert len(pin) >= n_fixed and len(sin) >= n_fixed, "poses_in / status_in must cover the history"
+        prm = L.ChainParamsStruct(float(dist_nearby), float(max_rms), int(range_width), int(min_matches), float(ratio),
+                                  int(max_distance))
+        rec = np.zeros(max(F, 1), L.CHAIN_FRAME)
+        cap = max(F * L.CHAIN_MAX_RANGE, 1) if return_pairs else 0
+        prs = np.zeros((cap, 2), np.int32) if return_pairs else None
+        n_pairs = C.c_int64(0)
+        if mem == L.MEM_DEVICE:
+            import torch
+            poses = torch.zeros((max(F, 1), 16), dtype=torch.float32, device=desc.device)
+            self._order_after_torch()
+            pp = poses.data_ptr()
+        else:
+            poses = np.zeros((max(F, 1), 16), np.float32)
+            pp = poses.ctypes.data
+        L.check(self._lib.o3dr_pose_chain(self._h, pd if n else None, off.ctypes.data, pk if n else None, prior.ctypes.data, F, n_fixed,
+                                          pin.ctypes.data if len(pin) else None, sin.ctypes.data if len(sin) else None, C.byref(prm), pp,
+                                          rec.ctypes.data, None if prs is None else prs.ctypes.data, cap, C.byref(n_pairs), mem))
+        res = (poses[:F].reshape(F, 4, 4), rec[:F])
+        return res + (prs[: n_pairs.value],) if return_pairs else res
+
+    def trackFrames(self, img, disp, prior_poses, n_features=1500, scale_factor=1.3, n_levels=5, fast_threshold=20, edge=31,
+                    **chain_kwargs):
+        """findFeatures(img), keypoints3D(disp, poses=None) and poseChain over a stack of frames (img [F, H, W] or
+        [F, H, W, 3] uint8, disp [F, H, W]; numpy or torch CUDA tensors).  chain_kwargs: poseChain's keywords.
+        -> (poses, records, (kp_xy, offsets)); the pair feeds accumulateFrames(keypoints=...) for the accepted frames."""
+        _kp, xy, desc, off = self.findFeatures(img, n_features=n_features, scale_factor=scale_factor, n_levels=n_levels,
+                                               fast_threshold=fast_threshold, edge=edge)
+        kp3 = self.keypoints3D(disp, [xy[int(off[f]):int(off[f + 1])] for f in range(len(off) - 1)], poses=None)
+        res = self.poseChain(desc, off, kp3, prior_poses, **chain_kwargs)
+        return res[:2] + ((xy, off),) + res[2:]
+
     # -- surface mesh (pcl::GreedyProjectionTriangulation at --mesh_surface: pose_functions.cpp:1711-1813) -----------------
     def meshSurface(self, pts, cell_size, max_edge_length, return_normals=False, return_info=False):
         """Height-field triangulation of the occupied XY cells (contract: include/o3dr.h, DESIGN.md "Surface mesh").

@@ -148,6 +148,8 @@ struct o3dr_ctx {
     DevBuf pl_hyp;             // o3dr_segment_plane: hypotheses + scores (plane_hyp_layout), kept for the test hook
     uint64_t pl_last_hyp = 0;  // hypotheses of the last call in pl_hyp (o3dr_test_plane_hypotheses)
     std::vector<MatchPair> mt_tab_h;  // host copies of the match pair table, the rigid fit's segment table and transforms
+    std::vector<int32_t> ch_pairs_h, ch_train_h, ch_status_h;  // ... and the pose chain's pair list, train frames, statuses, frames
+    std::vector<ChainFrameIn> ch_frames_h;
     std::vector<RigidSeg> rg_seg_h;
     std::vector<double> rg_T_h;
     int64_t place_ub = -1;   // o3dr_cloud_big_slice_counts_dev ran for a cloud of at most this many points and place_parts slices:
@@ -3553,6 +3555,38 @@ extern "C" void o3dr_match_default_params(o3dr_match_params* p)
 // work items (waves) the chunk size aims at: enough to fill 256 CUs several times over
 constexpr uint64_t kMatchTargetItems = 8192;
 
+// the pair table of a call (c->mt_tab_h; the pairs are checked) and its totals; `work` = sum of ceil(nq / 64) nt sizes the chunk
+struct MatchPlan {
+    uint64_t chunk, items, rec, part;  // train rows per chunk; work items, records and partial slots of the call
+};
+static MatchPlan match_plan(o3dr_ctx* c, const int64_t* off, const int32_t* pairs, int64_t n_pairs, uint64_t work)
+{
+    uint64_t chunk = (work + kMatchTargetItems - 1) / kMatchTargetItems;
+    chunk = (chunk + kWave - 1) / kWave * kWave;
+    if (chunk < (uint64_t)kWave) chunk = kWave;
+    if (chunk > kMatchMaxChunk) chunk = kMatchMaxChunk;
+    std::vector<MatchPair>& tab = c->mt_tab_h;
+    tab.resize((size_t)n_pairs);
+    uint64_t items = 0, rec = 0, part = 0;
+    for (int64_t k = 0; k < n_pairs; ++k) {
+        const int32_t qs = pairs[2 * k], ts = pairs[2 * k + 1];
+        MatchPair& P = tab[(size_t)k];
+        P.qbase = (uint32_t)(off[qs] - off[0]);
+        P.nq = (uint32_t)(off[qs + 1] - off[qs]);
+        P.tbase = (uint32_t)(off[ts] - off[0]);
+        P.nt = (uint32_t)(off[ts + 1] - off[ts]);
+        P.chunks = (uint32_t)(((uint64_t)P.nt + chunk - 1) / chunk);
+        P.qwaves = (P.nq + kWave - 1) / kWave;
+        P.item0 = items;
+        P.rec0 = rec;
+        P.part0 = part;
+        items += (uint64_t)P.qwaves * P.chunks;
+        rec += P.nq;
+        part += (uint64_t)P.nq * P.chunks;
+    }
+    return MatchPlan{chunk, items, rec, part};
+}
+
 static int match_knn2(o3dr_ctx* c, const uint8_t* desc, const int64_t* off, int32_t n_sets, const int32_t* pairs, int64_t n_pairs,
                       const o3dr_match_params* p, o3dr_knn2* out, uint8_t* good, Outputs& outs, int64_t out_capacity, int64_t* n_out,
                       int32_t mem)
@@ -3585,29 +3619,9 @@ static int match_knn2(o3dr_ctx* c, const uint8_t* desc, const int64_t* off, int3
     if ((int64_t)n_rec > out_capacity) return fail(O3DR_ERR_CAPACITY, "out_capacity is below the record count");
     if (n_rec > 0 && !out) return fail(O3DR_ERR_INVALID_ARG, "out is NULL");
     if (n_rec == 0) return O3DR_OK;
-    uint64_t chunk = (work + kMatchTargetItems - 1) / kMatchTargetItems;
-    chunk = (chunk + kWave - 1) / kWave * kWave;
-    if (chunk < (uint64_t)kWave) chunk = kWave;
-    if (chunk > kMatchMaxChunk) chunk = kMatchMaxChunk;
-    std::vector<MatchPair>& tab = c->mt_tab_h;
-    tab.resize((size_t)n_pairs);
-    uint64_t items = 0, rec = 0, part = 0;
-    for (int64_t k = 0; k < n_pairs; ++k) {
-        const int32_t qs = pairs[2 * k], ts = pairs[2 * k + 1];
-        MatchPair& P = tab[(size_t)k];
-        P.qbase = (uint32_t)(off[qs] - off[0]);
-        P.nq = (uint32_t)(off[qs + 1] - off[qs]);
-        P.tbase = (uint32_t)(off[ts] - off[0]);
-        P.nt = (uint32_t)(off[ts + 1] - off[ts]);
-        P.chunks = (uint32_t)(((uint64_t)P.nt + chunk - 1) / chunk);
-        P.qwaves = (P.nq + kWave - 1) / kWave;
-        P.item0 = items;
-        P.rec0 = rec;
-        P.part0 = part;
-        items += (uint64_t)P.qwaves * P.chunks;
-        rec += P.nq;
-        part += (uint64_t)P.nq * P.chunks;
-    }
+    const MatchPlan plan = match_plan(c, off, pairs, n_pairs, work);
+    const std::vector<MatchPair>& tab = c->mt_tab_h;
+    const uint64_t chunk = plan.chunk, items = plan.items, part = plan.part;
     const void* desc_d = nullptr;
     if (pool > 0) CHK(stage_in(c, c->op[o3dr_ctx::OP_IN], desc + 32 * off[0], (size_t)pool * 32, mem, &desc_d));
     MatchPair* tab_d;
@@ -3820,6 +3834,200 @@ extern "C" int o3dr_estimate_rigid_transform(o3dr_ctx* c, const o3dr_point* src,
 {
     const int rc = entered(c, [&] { return rigid_transform(c, src, tgt, n, seg_offsets, n_segs, mask, res, mem); });
     if (rc != O3DR_OK && res && n_segs > 0) memset(res, 0, (size_t)n_segs * sizeof(o3dr_rigid_result));
+    return rc;
+}
+
+// -------------------------------------------------------------------------------------------------
+// pose chain (kernels/pose_chain.inc; contract: include/o3dr.h "pose chain", DESIGN.md "Pose chain")
+// -------------------------------------------------------------------------------------------------
+extern "C" void o3dr_chain_default_params(o3dr_chain_params* p)
+{
+    if (!p) return;
+    p->dist_nearby = 2.0;
+    p->max_rms = HUGE_VAL;  // no gate
+    p->range_width = 8;
+    p->min_matches = 30;
+    p->ratio = 0.5f;
+    p->max_distance = 40;
+}
+
+static int pose_chain(o3dr_ctx* c, const uint8_t* desc, const int64_t* off, const o3dr_point* kp3, const float* prior, int32_t n_frames,
+                      int32_t n_fixed, const float* poses_in, const int32_t* status_in, const o3dr_chain_params* p, float* poses_out,
+                      o3dr_chain_frame* frames_out, Outputs& outs, int32_t* pairs_out, int64_t pairs_capacity, int64_t* n_pairs_out,
+                      int32_t mem)
+{
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    o3dr_chain_params prm;
+    o3dr_chain_default_params(&prm);
+    if (p) prm = *p;
+    if (!(std::isfinite(prm.dist_nearby) && prm.dist_nearby >= 0.0)) return fail(O3DR_ERR_INVALID_ARG, "dist_nearby must be finite and >= 0");
+    if (prm.range_width < 1 || prm.range_width > O3DR_CHAIN_MAX_RANGE) return fail(O3DR_ERR_INVALID_ARG, "range_width must be in [1, 32]");
+    if (prm.min_matches < 3) return fail(O3DR_ERR_INVALID_ARG, "min_matches must be >= 3");
+    if (!(prm.max_rms > 0.0)) return fail(O3DR_ERR_INVALID_ARG, "max_rms must be > 0");
+    if (!(std::isfinite(prm.ratio) && prm.ratio > 0.f)) return fail(O3DR_ERR_INVALID_ARG, "ratio must be finite and > 0");
+    if (prm.max_distance < 0 || prm.max_distance > 257) return fail(O3DR_ERR_INVALID_ARG, "max_distance must be in [0, 257]");
+    if (n_frames < 0 || n_fixed < 0 || n_fixed > n_frames) return fail(O3DR_ERR_INVALID_ARG, "0 <= n_fixed <= n_frames must hold");
+    if (n_frames == 0) return O3DR_OK;
+    if (!off || !prior || !poses_out || !frames_out) return fail(O3DR_ERR_INVALID_ARG, "offsets / prior_poses / poses_out / frames_out is NULL");
+    if (n_fixed > 0 && (!poses_in || !status_in)) return fail(O3DR_ERR_INVALID_ARG, "poses_in / status_in is NULL with n_fixed > 0");
+    if (off[0] < 0) return fail(O3DR_ERR_INVALID_ARG, "offsets[0] must be >= 0");
+    for (int32_t f = 0; f < n_frames; ++f)
+        if (off[f + 1] < off[f]) return fail(O3DR_ERR_INVALID_ARG, "offsets must not decrease");
+    const int64_t pool = off[n_frames] - off[0];
+    if (pool > (int64_t)INT32_MAX) return fail(O3DR_ERR_INVALID_ARG, "more than 2^31-1 rows");
+    if (pool > 0 && (!desc || !kp3)) return fail(O3DR_ERR_INVALID_ARG, "desc / kp3 is NULL");
+    for (int32_t f = 0; f < n_fixed; ++f)
+        if (status_in[f] < O3DR_CHAIN_ANCHOR || status_in[f] > O3DR_CHAIN_RMS) return fail(O3DR_ERR_INVALID_ARG, "status_in holds a value outside O3DR_CHAIN_*");
+    c->place_ub = -1;
+    // 1. the static pair list (host, fp64)
+    const size_t F = (size_t)n_frames;
+    std::vector<int32_t>& pl = c->ch_pairs_h;
+    std::vector<int32_t>& train = c->ch_train_h;
+    std::vector<ChainFrameIn>& fr = c->ch_frames_h;
+    pl.clear();
+    train.clear();
+    fr.resize(F);
+    const double r2 = prm.dist_nearby * prm.dist_nearby;
+    uint64_t work = 0;
+    for (int32_t i = 0; i < n_frames; ++i) {
+        ChainFrameIn& f = fr[(size_t)i];
+        f.pair0 = (uint32_t)train.size();
+        f.n_pairs = 0;
+        f.qbase = (uint32_t)(off[i] - off[0]);
+        f.nq = (uint32_t)(off[i + 1] - off[i]);
+        if (i < n_fixed) continue;
+        const double x = prior[16 * (size_t)i + 3], y = prior[16 * (size_t)i + 7], z = prior[16 * (size_t)i + 11];
+        for (int32_t j = i - 1; j >= 0 && (int32_t)f.n_pairs < prm.range_width; --j) {
+            const double dx = (double)prior[16 * (size_t)j + 3] - x, dy = (double)prior[16 * (size_t)j + 7] - y,
+                         dz = (double)prior[16 * (size_t)j + 11] - z;
+            if (!(((dx * dx + dy * dy) + dz * dz) <= r2)) continue;
+            pl.push_back(i);
+            pl.push_back(j);
+            train.push_back(j);
+            ++f.n_pairs;
+            work += ((uint64_t)f.nq + kWave - 1) / kWave * (uint64_t)(off[j + 1] - off[j]);
+        }
+        if ((uint64_t)f.n_pairs * f.nq > (uint64_t)INT32_MAX) return fail(O3DR_ERR_INVALID_ARG, "a frame has more than 2^31-1 slots");
+    }
+    const int64_t n_pairs = (int64_t)train.size();
+    if (n_pairs_out) *n_pairs_out = n_pairs;
+    if (pairs_out && n_pairs > pairs_capacity) return fail(O3DR_ERR_CAPACITY, "pairs_capacity is below the pair count");
+    if (pairs_out && n_pairs > 0) memcpy(pairs_out, pl.data(), (size_t)n_pairs * 2 * sizeof(int32_t));
+    // history: records on the host, poses and statuses to the device
+    std::vector<int32_t>& st_h = c->ch_status_h;
+    st_h.assign(F, 0);
+    for (int32_t f = 0; f < n_fixed; ++f) {
+        o3dr_chain_frame& r = frames_out[f];
+        memset(&r, 0, sizeof r);
+        r.status = st_h[(size_t)f] = status_in[f];
+        for (int k = 0; k < 12; ++k) r.T[k] = (double)poses_in[16 * (size_t)f + k];
+    }
+    // 2. staging and scratch
+    const MatchPlan plan = match_plan(c, off, pl.data(), n_pairs, work);
+    const std::vector<MatchPair>& tab = c->mt_tab_h;
+    const uint8_t* desc_d = desc ? desc + 32 * off[0] : nullptr;
+    const o3dr_point* kp3_d = kp3 ? kp3 + off[0] : nullptr;
+    if (mem == O3DR_MEM_HOST) {
+        CHK(carve(c, c->op[o3dr_ctx::OP_IN], [&](Carve& w) {
+            w.take(desc_d, (size_t)pool * 32 + 1);
+            w.take(kp3_d, (size_t)pool + 1);
+        }));
+        if (pool > 0) {
+            HIPCHK(hipMemcpyAsync((void*)desc_d, desc + 32 * off[0], (size_t)pool * 32, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync((void*)kp3_d, kp3 + off[0], (size_t)pool * sizeof(o3dr_point), hipMemcpyHostToDevice, c->stream));
+        }
+    }
+    MatchPair* tab_d;
+    uint2* part_d;
+    uint4* rec_d;
+    uint8_t* good_d;
+    int32_t *train_d, *status_d;
+    ChainFrameIn* frames_d;
+    float* prior_d;
+    o3dr_chain_frame* out_d;
+    CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
+        w.take(tab_d, tab.size() + 1);
+        w.take(part_d, (size_t)plan.part + 1);
+        w.take(rec_d, (size_t)plan.rec + 1);
+        w.take(good_d, (size_t)plan.rec + 1);
+        w.take(train_d, train.size() + 1);
+        w.take(status_d, F);
+        w.take(frames_d, F);
+        w.take(prior_d, F * 16);
+        w.take(out_d, F);
+    }));
+    CHK(outs.stage(c));
+    float* poses_d = outs.dev(poses_out);
+    if (n_pairs > 0) {
+        HIPCHK(hipMemcpyAsync(tab_d, tab.data(), tab.size() * sizeof(MatchPair), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(train_d, train.data(), train.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(hipMemcpyAsync(frames_d, fr.data(), F * sizeof(ChainFrameIn), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(prior_d, prior, F * 16 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (n_fixed > 0) {
+        HIPCHK(hipMemcpyAsync(status_d, st_h.data(), (size_t)n_fixed * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(poses_d, poses_in, (size_t)n_fixed * 16 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    }
+    // 3. one batched matching pass, then the chain: one launch
+    if (plan.rec > 0) {
+        MatchArgs m;
+        memset(&m, 0, sizeof m);
+        m.desc = (const uint4*)desc_d;
+        m.n_pairs = (uint32_t)n_pairs;
+        m.chunk_rows = (uint32_t)plan.chunk;
+        m.n_items = plan.items;
+        m.n_rec = plan.rec;
+        m.ratio = prm.ratio;
+        m.max_distance = (uint32_t)prm.max_distance;
+        m.rec = rec_d;
+        m.good = good_d;
+        launch_match(&c->prof, c->stream, m, tab_d, part_d);
+        HIPCHK(hipGetLastError());
+    }
+    ChainArgs a;
+    memset(&a, 0, sizeof a);
+    a.kp3 = kp3_d;
+    a.pairs = tab_d;
+    a.pair_train = train_d;
+    a.rec = rec_d;
+    a.good = good_d;
+    a.frames = frames_d;
+    a.prior = prior_d;
+    a.poses = poses_d;
+    a.status = status_d;
+    a.out = out_d;
+    a.n_frames = (uint32_t)n_frames;
+    a.n_fixed = (uint32_t)n_fixed;
+    a.min_matches = (uint32_t)prm.min_matches;
+    a.max_rms = prm.max_rms;
+    launch_pose_chain(&c->prof, c->stream, a);
+    HIPCHK(hipGetLastError());
+    if (n_fixed < n_frames)
+        HIPCHK(hipMemcpyAsync(frames_out + n_fixed, out_d + n_fixed, (size_t)(n_frames - n_fixed) * sizeof(o3dr_chain_frame),
+                              hipMemcpyDeviceToHost, c->stream));
+    CHK(outs.copy_back(c));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_pose_chain(o3dr_ctx* c, const uint8_t* desc, const int64_t* offsets, const o3dr_point* kp3, const float* prior_poses,
+                               int32_t n_frames, int32_t n_fixed, const float* poses_in, const int32_t* status_in,
+                               const o3dr_chain_params* p, float* poses_out, o3dr_chain_frame* frames_out, int32_t* pairs_out,
+                               int64_t pairs_capacity, int64_t* n_pairs_out, int32_t mem)
+{
+    if (n_pairs_out) *n_pairs_out = 0;
+    Outputs outs{mem};
+    outs.add(poses_out, n_frames > 0 ? 16 * (int64_t)n_frames : 0);
+    const int rc = entered(c, [&] {
+        return pose_chain(c, desc, offsets, kp3, prior_poses, n_frames, n_fixed, poses_in, status_in, p, poses_out, frames_out, outs,
+                          pairs_out, pairs_capacity, n_pairs_out, mem);
+    });
+    if (rc != O3DR_OK && rc != O3DR_ERR_CAPACITY) {  // host outputs zeroed on error
+        if (n_pairs_out) *n_pairs_out = 0;
+        outs.zero();
+        if (frames_out && n_frames > 0) memset(frames_out, 0, (size_t)n_frames * sizeof(o3dr_chain_frame));
+        if (pairs_out && pairs_capacity > 0) memset(pairs_out, 0, (size_t)pairs_capacity * 2 * sizeof(int32_t));
+    }
     return rc;
 }
 

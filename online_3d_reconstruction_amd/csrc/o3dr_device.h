@@ -358,6 +358,29 @@ struct RigidArgs {
 // residual == false: first used pairs, moments about c0 and their fold into rec / c0; true: the squared residuals at T
 // folded into rec
 void launch_rigid(Profiler* pf, hipStream_t s, const RigidArgs& a, bool residual);
+// pose chain (kernels/pose_chain.inc): one launch of one workgroup for the whole call
+constexpr int kChainThreads = 1024;
+constexpr int kChainRun = 256;      // slots per run of the moment sums (kRigidPoints)
+constexpr int kChainMaxPairs = 32;  // pairs per frame at most (range_width's limit)
+struct ChainFrameIn {   // one frame of the call; rows relative to the pool
+    uint32_t pair0, n_pairs;  // its pairs in the static list (a history frame: none)
+    uint32_t qbase, nq;
+};
+struct ChainArgs {
+    const o3dr_point* kp3;       // the pool
+    const MatchPair* pairs;      // launch_match's table: qbase / nq / tbase / nt / rec0
+    const int32_t* pair_train;   // the train frame of every pair
+    const uint4* rec;            // launch_match's records and mask
+    const uint8_t* good;
+    const ChainFrameIn* frames;  // n_frames
+    const float* prior;          // n_frames * 16
+    float* poses;                // n_frames * 16: history on entry, every frame on exit
+    int32_t* status;             // n_frames: likewise
+    o3dr_chain_frame* out;       // n_frames records (written from n_fixed on)
+    uint32_t n_frames, n_fixed, min_matches;
+    double max_rms;
+};
+void launch_pose_chain(Profiler* pf, hipStream_t s, const ChainArgs& a);
 // The dense XY cell order of a cloud (kernels/cell_order.inc): the points sorted by the dense id
 // (iy - y0) * wx + (ix - x0) of their cell, input order kept inside a cell.  The operator's Args (PlaneArgs, MeshArgs:
 // cloud, n, the parameter of its index rule, `cells`) select the index rule.

@@ -34,6 +34,7 @@
 //   mesh         height-field surface mesh over the XY cells
 //   match        Hamming 2-NN descriptor matching, index-aligned 3-D keypoints, the batched rigid fit
 //   orb          ORB features: grey pyramid, FAST score + box sums, candidates, exact selection, steered BRIEF
+//   pose_chain   the feature-matched pose chain: one workgroup walks the frames (gather, moments, Kabsch, residual)
 // The launchers follow in this file.
 #include <string.h>
 
@@ -61,6 +62,7 @@ namespace o3dr {
 #include "kernels/match.inc"
 #include "kernels/plane_disparity.inc"
 #include "kernels/orb.inc"
+#include "kernels/pose_chain.inc"
 
 // =================================================================================================
 // launchers
@@ -975,7 +977,7 @@ void launch_plane_fit(Profiler* pf, hipStream_t s, const PlaneArgs& a, int64_t m
 // feature matching (kernels/match.inc)
 void launch_match(Profiler* pf, hipStream_t s, const MatchArgs& a, const MatchPair* pairs, uint2* partial)
 {
-    ProfScope ps(pf, O3DR_K_OTHER, s);
+    ProfScope ps(pf, O3DR_K_MATCH, s);
     constexpr int wpb = kMatchThreads / kWave;
     for (int64_t off = 0; off < (int64_t)a.n_items; off += kMatchSliceItems) {
         const int64_t items = (int64_t)a.n_items - off < kMatchSliceItems ? (int64_t)a.n_items - off : kMatchSliceItems;
@@ -1014,6 +1016,13 @@ void launch_rigid(Profiler* pf, hipStream_t s, const RigidArgs& a, bool residual
         b.c0 = nullptr;
     }
     k_rigid_fold<<<dim3(a.n_segs, F), kIcpFoldThreads, 0, s>>>(b, F);
+}
+
+// pose chain (kernels/pose_chain.inc): one workgroup, the frames in order
+void launch_pose_chain(Profiler* pf, hipStream_t s, const ChainArgs& a)
+{
+    ProfScope ps(pf, O3DR_K_POSE_CHAIN, s);
+    if (a.n_fixed < a.n_frames) k_pose_chain<<<1, kChainThreads, 0, s>>>(a);
 }
 
 // height-field surface mesh (kernels/mesh.inc)

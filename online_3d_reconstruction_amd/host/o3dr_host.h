@@ -4,10 +4,10 @@
 // reference; the bodies call libo3dr (include/o3dr.h) instead of OpenCV/PCL.  Everything outside the
 // hot path that the CLI needs to run end to end (flag parsing, calibration/pose/time CSV readers,
 // timestamp binding, generateTmat, the variance gate, PNG/PLY I/O) is restated here in plain C++:
-// it is control plane, one call per frame or per run, and stays on the host.  Pose estimation (ORB,
-// matching, the ICP trajectory correction), visualisation and --segment_cloud in a reconstruction run are not part of
-// this build; the CLI runs with the recorded MAVLink poses (the reference's --only_MAVLink mode,
-// pose_functions.cpp:232-236).  The --align_point_cloud tool (ICP on two PLYs) runs on o3dr_icp_align, the
+// it is control plane, one call per frame or per run, and stays on the host.  The ICP trajectory correction,
+// visualisation and --segment_cloud in a reconstruction run are not part of this build; by default the CLI runs with the
+// recorded MAVLink poses (the reference's --only_MAVLink mode, pose_functions.cpp:232-236), with --feature_poses every
+// frame's pose comes from o3dr_pose_chain (the reference's default mode, pose.cpp:213-235).  The --align_point_cloud tool (ICP on two PLYs) runs on o3dr_icp_align, the
 // --smooth_surface tool (MLS on one PLY) on o3dr_mls_smooth, the --segment_cloud_only tool (RANSAC planes per XY tile on
 // one PLY) on o3dr_segment_plane, the --mesh_surface tool (a height-field triangulation of one PLY) on o3dr_mesh_surface.
 #pragma once
@@ -139,6 +139,13 @@ public:
                                       // come from o3dr_orb_detect on its rgb images (single-GPU batched path)
     int orb_n_features = 1500, orb_levels = 5, orb_fast_threshold = 20;  // --orb_n_features, --orb_levels, --orb_fast_threshold
     float orb_scale = 1.3f;           // --orb_scale
+    bool feature_poses = false;       // --feature_poses: every cycle's frames go through o3dr_orb_detect, o3dr_keypoints_3d (camera
+                                      // frame) and o3dr_pose_chain; a matched frame's t_mat_FeatureMatched is the chain's pose, a
+                                      // rejected frame is left out of the cycle's accumulate call (single-GPU batched path)
+    double dist_nearby = 2.0;         // --dist_nearby, --range_width: the chain's nearby-frame test (with --feature_poses only)
+    int range_width = 8;
+    int chain_min_matches = 30;       // --chain_min_matches
+    double chain_max_rms = HUGE_VAL;  // --chain_max_rms (default: no gate)
     std::string print_label_png;      // --print_label_png f: rows, cols and the labels of f as text (checks the reader)
 
     std::vector<RawImageData> rawImageDataVec;
@@ -177,6 +184,15 @@ private:
     o3dr_orb_params orb_params() const;             // the --orb_* flags over the defaults
     int first_img_num = -1, last_img_num = -1;
     bool run3d_reconstruction = true;
+    // --feature_poses: the frames already through the chain (descriptors, camera-frame keypoints, row offsets, recorded
+    // poses, the chain's poses and statuses): the history of the next cycle's o3dr_pose_chain call
+    struct ChainHistory {
+        std::vector<uint8_t> desc;
+        std::vector<o3dr_point> kp3;
+        std::vector<int64_t> off{0};
+        std::vector<float> prior, poses;
+        std::vector<int32_t> status;
+    } chain;
     bool disparity_f64 = false;  // what push_params sets: on around the accumulate call of a plane-fitted batch
     std::vector<std::vector<double>> pose_data, images_times_data;
     std::vector<double> pose_times_seq, images_times_seq;

@@ -425,8 +425,15 @@ void Pose::printUsage()
             "                     <image>.keypoints.txt, the --keypoints_dir format - the flags and the file name are this build's own)\n"
             "       [--gpu_keypoints]  (reconstruction run with jump_pixels != 1 and no --keypoints_dir: every batch's keypoints come\n"
             "                     from the same extractor on its rgb images, with the --orb_* flags; single-GPU batched path only)\n"
-            "Pose estimation (ORB matching, the ICP trajectory correction), visualisation and --segment_cloud in a reconstruction\n"
-            "run are not part of this build.\n";
+            "       [--feature_poses] [--dist_nearby m] [--range_width n] [--chain_min_matches n] [--chain_max_rms m]\n"
+            "                     (reconstruction run: every frame's pose from ORB matches against the earlier frames whose recorded\n"
+            "                     position lies within --dist_nearby metres (default 2), at most --range_width of them (default 8,\n"
+            "                     the most recent); a frame with fewer than --chain_min_matches correspondences (default 30), a\n"
+            "                     degenerate fit or an rms above --chain_max_rms is printed as Rejected! and left out of the cloud;\n"
+            "                     --dist_nearby and --range_width act under this flag only; shares the extractor call with\n"
+            "                     --gpu_keypoints; single-GPU batched path only; the flag is this build's own)\n"
+            "Without --feature_poses the run uses the recorded MAVLink poses (--only_MAVLink).  The ICP trajectory correction,\n"
+            "visualisation and --segment_cloud in a reconstruction run are not part of this build.\n";
 }
 
 int Pose::parseCmdArgs(int argc, char** argv)
@@ -506,7 +513,11 @@ int Pose::parseCmdArgs(int argc, char** argv)
         else if (a == "--gpus") n_gpus = atoi(need(i));
         else if (a == "--partitioned_merge") partitioned_merge = true;
         else if (a == "--search_radius") { search_radius = atof(need(i)); search_radius_set = true; }  // --smooth_surface, --mesh_surface
-        else if (a == "--dist_nearby" || a == "--range_width") { need(i); }
+        else if (a == "--dist_nearby") dist_nearby = atof(need(i));  // (both act with --feature_poses only)
+        else if (a == "--range_width") range_width = atoi(need(i));
+        else if (a == "--feature_poses") feature_poses = true;
+        else if (a == "--chain_min_matches") chain_min_matches = atoi(need(i));
+        else if (a == "--chain_max_rms") chain_max_rms = atof(need(i));
         else if (a == "--preview") preview = true;
         else if (a == "--use_segment_labels") use_segment_labels = true;
         else if (a == "--segment_labels_dir") segmentLabelsPrefix = need(i);
@@ -542,6 +553,10 @@ int Pose::parseCmdArgs(int argc, char** argv)
     if (run3d_reconstruction && gpu_keypoints) {
         if (n_gpus > 1 || partitioned_merge) throw runtime_error("--gpu_keypoints is not available with --gpus N > 1 / --partitioned_merge");
         if (reference_fanout) throw runtime_error("--gpu_keypoints is not available with --reference_fanout");
+    }
+    if (run3d_reconstruction && feature_poses) {
+        if (n_gpus > 1 || partitioned_merge) throw runtime_error("--feature_poses is not available with --gpus N > 1 / --partitioned_merge");
+        if (reference_fanout) throw runtime_error("--feature_poses is not available with --reference_fanout");
     }
     if (run3d_reconstruction) {
         if (n_imgs == 0) throw runtime_error("first and last image number are required");
@@ -917,7 +932,7 @@ void Pose::run_reconstruction()
                 memcpy(&poses[16 * k], im.t_mat_FeatureMatched.data(), 64);
                 kp_xy.insert(kp_xy.end(), im.keypoints_xy.begin(), im.keypoints_xy.end());
                 kp_off[k + 1] = (int64_t)(kp_xy.size() / 2);
-                cout << " " << im.raw_img_data_ptr->img_num << flush;
+                if (!feature_poses) cout << " " << im.raw_img_data_ptr->img_num << flush;
             }
             // page-locked frame stacks cross PCIe by DMA (best effort: pageable memory works too)
             const bool reg_disp = o3dr_host_register(disp.data(), (int64_t)disp.size()) == O3DR_OK;
@@ -926,18 +941,28 @@ void Pose::run_reconstruction()
             // ORB stage leaves in features.keypoints, pose_functions.cpp:1057-1061)
             int rc_orb = O3DR_OK;
             string why_orb;
-            if (gpu_keypoints && jump_pixels != 1 && keypointsPrefix.empty()) {
+            const bool orb_for_cloud = gpu_keypoints && jump_pixels != 1 && keypointsPrefix.empty();
+            vector<float> orb_xy;       // --feature_poses: the cycle's features (one extractor call, shared with --gpu_keypoints)
+            vector<uint8_t> orb_desc;
+            vector<int64_t> orb_off(n_acc + 1, 0);
+            if (orb_for_cloud || feature_poses) {
                 const o3dr_orb_params prm = orb_params();
                 const int64_t cap = (int64_t)n_acc * (prm.n_features > 0 ? prm.n_features : 1);
-                kp_xy.assign((size_t)cap * 2, 0.f);
+                orb_xy.assign((size_t)cap * 2, 0.f);
+                if (feature_poses) orb_desc.assign((size_t)cap * 32, 0);
                 int64_t n_kp = 0;
                 const auto tk = clk::now();
-                rc_orb = o3dr_orb_detect(c, bgr.data(), (int64_t)csz, 3 * (int64_t)cols, rows, cols, (int32_t)n_acc, &prm, nullptr, kp_xy.data(),
-                                         nullptr, kp_off.data(), nullptr, cap, &n_kp, O3DR_MEM_HOST);
+                rc_orb = o3dr_orb_detect(c, bgr.data(), (int64_t)csz, 3 * (int64_t)cols, rows, cols, (int32_t)n_acc, &prm, nullptr, orb_xy.data(),
+                                         feature_poses ? orb_desc.data() : nullptr, orb_off.data(), nullptr, cap, &n_kp, O3DR_MEM_HOST);
                 if (rc_orb != O3DR_OK) why_orb = o3dr_last_error();
-                kp_xy.resize((size_t)n_kp * 2);
+                orb_xy.resize((size_t)n_kp * 2);
+                orb_desc.resize(feature_poses ? (size_t)n_kp * 32 : 0);
                 cout << "\nORB keypoints: " << n_kp << " in " << n_acc << " frames, " << chrono::duration<double>(clk::now() - tk).count()
                      << " sec" << flush;
+                if (orb_for_cloud) {
+                    kp_xy = orb_xy;
+                    kp_off = orb_off;
+                }
             }
             // --use_segment_labels: the batch's 8-bit disparities become plane-fitted CV_64F images first
             vector<double> fitted;
@@ -966,14 +991,84 @@ void Pose::run_reconstruction()
                 disparity_f64 = true;
                 push_params(c);
             }
-            const uint8_t* disp_in = use_segment_labels ? (const uint8_t*)fitted.data() : disp.data();
+            uint8_t* disp_in = use_segment_labels ? (uint8_t*)fitted.data() : disp.data();
             const int64_t esz = use_segment_labels ? 8 : 1;
-            const int rc_acc = rc_orb != O3DR_OK ? rc_orb : rc_fit != O3DR_OK ? rc_fit
+            // --feature_poses: the cycle's frames through the chain (history = the frames of the cycles before), then only the
+            // accepted frames stay in the stacks, with the chain's poses
+            size_t n_cloud = n_acc;
+            int rc_chain = O3DR_OK;
+            string why_chain;
+            if (feature_poses && rc_orb == O3DR_OK && rc_fit == O3DR_OK) {
+                const auto tc = clk::now();
+                const size_t n_hist = chain.status.size(), n_all = n_hist + n_acc, n_kp = orb_xy.size() / 2;
+                vector<o3dr_point> kp3(n_kp ? n_kp : 1);
+                int64_t n3 = 0;
+                rc_chain = o3dr_keypoints_3d(c, disp_in, esz * (int64_t)dsz, esz * cols, nullptr, 0, 0, rows, cols, nullptr, (int32_t)n_acc,
+                                             orb_xy.data(), orb_off.data(), kp3.data(), (int64_t)kp3.size(), &n3, O3DR_MEM_HOST);
+                if (rc_chain != O3DR_OK) why_chain = string("keypoints_3d: ") + o3dr_last_error();
+                const int64_t base = chain.off.back();
+                chain.desc.insert(chain.desc.end(), orb_desc.begin(), orb_desc.end());
+                chain.kp3.insert(chain.kp3.end(), kp3.begin(), kp3.begin() + (ptrdiff_t)n_kp);
+                for (size_t k = 0; k < n_acc; ++k) {
+                    chain.off.push_back(base + orb_off[k + 1]);
+                    const Matrix4& m = acceptedImageDataVec[first_accepted + k].t_mat_MAVLink;
+                    chain.prior.insert(chain.prior.end(), m.begin(), m.end());
+                }
+                vector<float> chain_out(16 * n_all);
+                vector<o3dr_chain_frame> recs(n_all);
+                o3dr_chain_params cp;
+                o3dr_chain_default_params(&cp);
+                cp.dist_nearby = dist_nearby;
+                cp.range_width = range_width;
+                cp.min_matches = chain_min_matches;
+                cp.max_rms = chain_max_rms;
+                if (rc_chain == O3DR_OK) {
+                    rc_chain = o3dr_pose_chain(c, chain.desc.data(), chain.off.data(), chain.kp3.data(), chain.prior.data(), (int32_t)n_all,
+                                               (int32_t)n_hist, chain.poses.data(), chain.status.data(), &cp, chain_out.data(), recs.data(),
+                                               nullptr, 0, nullptr, O3DR_MEM_HOST);
+                    if (rc_chain != O3DR_OK) why_chain = string("pose_chain: ") + o3dr_last_error();
+                }
+                if (rc_chain == O3DR_OK) {
+                    static const char* const names[] = {"ANCHOR", "MATCHED", "TOO_FEW", "DEGENERATE", "RMS"};
+                    chain.poses = chain_out;
+                    n_cloud = 0;
+                    kp_off[0] = 0;
+                    size_t kp_rows = 0;
+                    cout << "\npose chain: " << n_acc << " frames after " << n_hist << ", " << chrono::duration<double>(clk::now() - tc).count()
+                         << " sec" << endl;
+                    for (size_t k = 0; k < n_acc; ++k) {
+                        const o3dr_chain_frame& r = recs[n_hist + k];
+                        ImageData& im = acceptedImageDataVec[first_accepted + k];
+                        chain.status.push_back(r.status);
+                        memcpy(im.t_mat_FeatureMatched.data(), &chain_out[16 * (n_hist + k)], 64);
+                        const bool ok = r.status == O3DR_CHAIN_ANCHOR || r.status == O3DR_CHAIN_MATCHED;
+                        cout << im.raw_img_data_ptr->img_num << " pose chain: " << names[r.status] << " pairs " << r.n_pairs_accepted << "/"
+                             << r.n_pairs << " good " << r.n_good << " used " << r.n_used << " rms " << r.rms
+                             << (ok ? "\tAccepted!" : "\tRejected!") << endl;
+                        if (!ok) continue;
+                        // the accepted frames move up in the stacks (m <= k)
+                        const size_t m = n_cloud++;
+                        const size_t r0k = (size_t)(kp_xy.empty() ? 0 : kp_off[k]), r1k = (size_t)(kp_xy.empty() ? 0 : kp_off[k + 1]);
+                        if (m != k) {
+                            memmove(disp_in + m * dsz * (size_t)esz, disp_in + k * dsz * (size_t)esz, dsz * (size_t)esz);
+                            memmove(&bgr[m * csz], &bgr[k * csz], csz);
+                        }
+                        memcpy(&poses[16 * m], im.t_mat_FeatureMatched.data(), 64);
+                        if (!kp_xy.empty()) memmove(&kp_xy[2 * kp_rows], &kp_xy[2 * r0k], (r1k - r0k) * 2 * sizeof(float));
+                        kp_rows += r1k - r0k;
+                        kp_off[m + 1] = (int64_t)kp_rows;
+                    }
+                    if (!kp_xy.empty()) kp_xy.resize(kp_rows * 2);
+                    cout << "Adding Point Cloud number/points: " << n_cloud << " of " << n_acc << " frames" << flush;
+                }
+            }
+            const int rc_acc = rc_orb != O3DR_OK ? rc_orb : rc_fit != O3DR_OK ? rc_fit : rc_chain != O3DR_OK ? rc_chain : n_cloud == 0 ? O3DR_OK
                                                  : o3dr_accumulate_frames_kp(c, disp_in, esz * (int64_t)dsz, esz * cols, bgr.data(), (int64_t)csz,
-                                                                             3 * (int64_t)cols, rows, cols, poses.data(), (int32_t)n_acc,
+                                                                             3 * (int64_t)cols, rows, cols, poses.data(), (int32_t)n_cloud,
                                                                              kp_xy.empty() ? nullptr : kp_xy.data(),
                                                                              kp_xy.empty() ? nullptr : kp_off.data(), O3DR_MEM_HOST);
-            const string why_acc = rc_orb != O3DR_OK ? "orb_detect: " + why_orb : rc_fit != O3DR_OK ? "plane_fit_disparity: " + why_fit : (rc_acc != O3DR_OK ? o3dr_last_error() : "");
+            const string why_acc = rc_orb != O3DR_OK ? "orb_detect: " + why_orb : rc_fit != O3DR_OK ? "plane_fit_disparity: " + why_fit
+                                   : rc_chain != O3DR_OK ? why_chain : (rc_acc != O3DR_OK ? o3dr_last_error() : "");
             if (use_segment_labels) {
                 disparity_f64 = false;
                 push_params(c);

@@ -1,0 +1,208 @@
+"""The pose chain's contract (include/o3dr.h "pose chain") restated in numpy, and the synthetic world its tests use.
+
+pair_list: the static pair list.  chain_ref: brute-force Hamming 2-NN with the library's tie and strictness rules, the
+slot enumeration, the fp32 A2 transform, an fp64 Kabsch (numpy's SVD, mean-centred: another SVD and summation order than the
+library's, so poses agree to rounding, not bit for bit) and the statuses.  make_world: landmarks with random 256-bit
+descriptors seen from true poses."""
+import numpy as np
+
+ANCHOR, MATCHED, TOO_FEW, DEGENERATE, RMS = range(5)
+NONE = 0xFFFFFFFF
+POP8 = np.array([bin(i).count("1") for i in range(256)], np.uint32)
+
+
+# ---- the contract -------------------------------------------------------------------------------------------------------
+def pair_list(prior, dist_nearby=2.0, range_width=8, n_fixed=0):
+    """[(i, j)]: for i = n_fixed .., every j < i within dist_nearby (fp64, squared, <=), the range_width largest, descending"""
+    prior = np.asarray(prior, np.float32).reshape(-1, 16)
+    t = prior[:, [3, 7, 11]].astype(np.float64)
+    r2 = float(dist_nearby) * float(dist_nearby)
+    out = []
+    for i in range(n_fixed, len(prior)):
+        k = 0
+        for j in range(i - 1, -1, -1):
+            if k >= range_width:
+                break
+            d = t[j] - t[i]
+            if (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2] <= r2:
+                out.append((i, j))
+                k += 1
+    return out
+
+
+def knn2_ref(q, t):
+    """(train_idx [n, 2], distance [n, 2]) uint32: the two smallest keys (d, j), 0xFFFFFFFF where missing"""
+    q = np.asarray(q, np.uint8).reshape(-1, 32)
+    t = np.asarray(t, np.uint8).reshape(-1, 32)
+    n, m = len(q), len(t)
+    idx = np.full((n, 2), NONE, np.uint32)
+    dist = np.full((n, 2), NONE, np.uint32)
+    if m == 0 or n == 0:
+        return idx, dist
+    d = POP8[q[:, None, :] ^ t[None, :, :]].sum(-1, dtype=np.uint64)
+    key = (d << np.uint64(32)) | np.arange(m, dtype=np.uint64)[None, :]
+    k = np.sort(key, axis=1)[:, :2]
+    for c in range(k.shape[1]):
+        idx[:, c] = (k[:, c] & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+        dist[:, c] = (k[:, c] >> np.uint64(32)).astype(np.uint32)
+    return idx, dist
+
+
+def good_ref(dist, ratio=0.5, max_distance=40):
+    d1, d2 = dist[:, 0], dist[:, 1]
+    with np.errstate(invalid="ignore"):
+        return (d2 != NONE) & (d1 < max_distance) & (d1.astype(np.float32) < np.float32(ratio) * d2.astype(np.float32))
+
+
+def a2(m, xyz):
+    """A2 in fp32: ((m0 x + m1 y) + m2 z) + m3 per row, every operation rounded on its own"""
+    m = np.asarray(m, np.float32).reshape(16)
+    p = np.asarray(xyz, np.float32).reshape(-1, 3)
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    return np.stack([((m[4 * r] * x + m[4 * r + 1] * y) + m[4 * r + 2] * z) + m[4 * r + 3] for r in range(3)], 1).astype(np.float32)
+
+
+def kabsch_rank_ref(src, tgt):
+    """kabsch_ref of tests/test_feature_matching.py with the contract's rank test -> (T 4x4 fp64, or None: rank < 2)"""
+    a = np.asarray(src, np.float64)
+    b = np.asarray(tgt, np.float64)
+    ma, mb = a.mean(0), b.mean(0)
+    H = (a - ma).T @ (b - mb)
+    U, S, Vt = np.linalg.svd(H)
+    if not (S[0] > 0.0 and np.isfinite(S[0]) and S[1] > 1e-12 * S[0]):
+        return None
+    d = np.sign(np.linalg.det(Vt.T @ U.T))
+    R = Vt.T @ np.diag([1.0, 1.0, d]) @ U.T
+    T = np.eye(4)
+    T[:3, :3] = R
+    T[:3, 3] = mb - R @ ma
+    return T
+
+
+def chain_ref(desc, offsets, kp3, prior, n_fixed=0, poses_in=None, status_in=None, dist_nearby=2.0, range_width=8, min_matches=30,
+              max_rms=np.inf, ratio=0.5, max_distance=40, nudge=0):
+    """-> dict(poses [F, 16] float32, status, n_pairs, n_pairs_accepted, n_good, n_used, rms, T [F, 12] fp64, pairs [(i, j)],
+    gathered {i: (src, tgt) float32 [n_used, 3]}).  nudge = +1 / -1: every fitted fp32 pose entry moved one ulp up / down
+    (the tests measure the chain's sensitivity to the last bit of a pose with it)."""
+    desc = np.asarray(desc, np.uint8).reshape(-1, 32)
+    off = np.asarray(offsets, np.int64)
+    xyz = np.asarray(kp3, np.float32).reshape(-1, 3)
+    prior = np.asarray(prior, np.float32).reshape(-1, 16)
+    F = len(off) - 1
+    pairs = pair_list(prior, dist_nearby, range_width, n_fixed)
+    poses = prior.copy()
+    r = dict(status=np.zeros(F, np.int32), n_pairs=np.zeros(F, np.int32), n_pairs_accepted=np.zeros(F, np.int32),
+             n_good=np.zeros(F, np.int32), n_used=np.zeros(F, np.int32), rms=np.zeros(F), T=np.zeros((F, 12)), pairs=pairs,
+             gathered={})
+    for f in range(n_fixed):
+        poses[f] = np.asarray(poses_in, np.float32).reshape(-1, 16)[f]
+        r["status"][f] = status_in[f]
+    for i in range(n_fixed, F):
+        mine = [j for (q, j) in pairs if q == i]
+        r["n_pairs"][i] = len(mine)
+        if not mine:
+            r["status"][i] = ANCHOR
+            continue
+        q3 = xyz[off[i]:off[i + 1]]
+        src, tgt = [], []
+        for j in mine:
+            if r["status"][j] > MATCHED:
+                continue
+            r["n_pairs_accepted"][i] += 1
+            idx, dist = knn2_ref(desc[off[i]:off[i + 1]], desc[off[j]:off[j + 1]])
+            good = good_ref(dist, ratio, max_distance)
+            r["n_good"][i] += int(good.sum())
+            rows = np.nonzero(good)[0]
+            s = q3[rows]
+            t = a2(poses[j], xyz[off[j]:off[j + 1]][idx[rows, 0].astype(np.int64)])
+            use = np.isfinite(s).all(1) & np.isfinite(t).all(1)
+            src.append(s[use])
+            tgt.append(t[use])
+        src = np.concatenate(src) if src else np.zeros((0, 3), np.float32)
+        tgt = np.concatenate(tgt) if tgt else np.zeros((0, 3), np.float32)
+        r["n_used"][i] = len(src)
+        r["gathered"][i] = (src, tgt)
+        if len(src) < min_matches:
+            r["status"][i] = TOO_FEW
+            continue
+        T = kabsch_rank_ref(src, tgt)
+        if T is None:
+            r["status"][i] = DEGENERATE
+            continue
+        e = src.astype(np.float64) @ T[:3, :3].T + T[:3, 3] - tgt.astype(np.float64)
+        rms = float(np.sqrt((e * e).sum() / len(src)))
+        r["rms"][i] = rms
+        if not rms <= max_rms:
+            r["status"][i] = RMS
+            continue
+        r["status"][i] = MATCHED
+        r["T"][i] = T[:3].reshape(12)
+        p = T.astype(np.float32).reshape(16)
+        if nudge:
+            p[:12] = np.nextafter(p[:12], np.float32(np.inf if nudge > 0 else -np.inf))
+        p[12:] = (0, 0, 0, 1)
+        poses[i] = p
+    for i in range(F):
+        if r["status"][i] != MATCHED or i < n_fixed:
+            r["T"][i] = poses[i, :12].astype(np.float64)
+    r["poses"] = poses
+    return r
+
+
+# ---- the synthetic world --------------------------------------------------------------------------------------------------
+def rot(axis, angle):
+    axis = np.asarray(axis, np.float64) / np.linalg.norm(axis)
+    K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+    return np.eye(3) + np.sin(angle) * K + (1 - np.cos(angle)) * K @ K
+
+
+def true_pose(k, step=0.5):
+    """frame k's true pose (fp64 4x4): a slow turn and `step` metres along x per frame"""
+    T = np.eye(4)
+    T[:3, :3] = rot([0.2, 1.0, 0.1], 0.04 * k)
+    T[:3, 3] = (step * k, 0.05 * np.sin(0.7 * k), 0.03 * k)
+    return T
+
+
+def make_world(seed, views, n_landmarks, step=0.5, prior_err=0.05, max_flips=8, poses=None):
+    """views: per frame, the landmark indices it sees (its rows, in that order).  -> dict(desc [N, 32] uint8, offsets,
+    kp3 [N, 3] float32 = inverse(true pose) landmark, landmark [N] (each row's landmark), true [F, 4, 4] fp64,
+    prior [F, 16] float32 = the true poses plus a translation error of at most prior_err per axis, positions [M, 3])."""
+    rng = np.random.default_rng(seed)
+    M = int(n_landmarks)
+    base = rng.integers(0, 256, (M, 32), dtype=np.uint8)
+    pos = np.stack([rng.uniform(-5, 5, M), rng.uniform(-5, 5, M), rng.uniform(3, 10, M)], 1)
+    F = len(views)
+    true = np.stack([true_pose(k, step) for k in range(F)]) if poses is None else np.asarray(poses, np.float64)
+    desc, kp3, lm = [], [], []
+    for f, v in enumerate(views):
+        v = np.asarray(v, np.int64)
+        d = base[v].copy()
+        for r in range(len(v)):
+            bits = np.unpackbits(d[r], bitorder="little")
+            bits[rng.choice(256, int(rng.integers(0, max_flips + 1)), replace=False)] ^= 1
+            d[r] = np.packbits(bits, bitorder="little")
+        inv = np.linalg.inv(true[f])
+        kp3.append((pos[v] @ inv[:3, :3].T + inv[:3, 3]).astype(np.float32))
+        desc.append(d)
+        lm.append(v)
+    offsets = np.concatenate([[0], np.cumsum([len(v) for v in views])]).astype(np.int64)
+    prior = true.copy()
+    prior[:, :3, 3] += rng.uniform(-prior_err, prior_err, (F, 3))
+    cat = lambda xs, shape, dt: np.concatenate(xs) if xs else np.zeros(shape, dt)  # noqa: E731
+    return dict(desc=cat(desc, (0, 32), np.uint8), offsets=offsets, kp3=cat(kp3, (0, 3), np.float32),
+                landmark=cat(lm, (0,), np.int64), true=true, prior=prior.astype(np.float32).reshape(F, 16), positions=pos)
+
+
+def random_views(seed, n_frames, n_landmarks, per_frame):
+    rng = np.random.default_rng(seed)
+    return [rng.choice(n_landmarks, per_frame, replace=False) for _ in range(n_frames)]
+
+
+def points(xyz):
+    """float32 [n, 3] -> the library's POINT records (rgba 0)"""
+    from online_3d_reconstruction_amd import POINT
+    xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
+    p = np.zeros(len(xyz), POINT)
+    p["x"], p["y"], p["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    return p
