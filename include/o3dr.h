@@ -872,6 +872,81 @@ int  o3dr_pose_chain(o3dr_ctx* ctx, const uint8_t* desc, const int64_t* offsets,
                      float* poses_out, o3dr_chain_frame* frames_out, int32_t* pairs_out, int64_t pairs_capacity, int64_t* n_pairs_out,
                      int32_t mem);
 
+/* ---- robust rigid fit: three-point RANSAC for a rigid transform, the outlier rejection in front of
+ * o3dr_estimate_rigid_transform and inside the pose chain.  The contract is this library's own;
+ * tests/ransac_rigid_reference.py restates it in numpy, operation for operation.
+ *
+ * o3dr_ransac_rigid - batched over segments.  src, tgt, seg_offsets, n_segs and mask as in o3dr_estimate_rigid_transform
+ * (src / tgt / mask in `mem`, seg_offsets HOST; seg_offsets NULL: one segment [0, n) and n_segs must be 1); each segment at
+ * most 2^31-1 points.  seg_keys: HOST, n_segs uint64, or NULL: segment s has the key s.  p: threshold (metres, finite, > 0),
+ * iterations H (1 .. O3DR_RANSAC_MAX_ITERATIONS), seed; p == NULL: the defaults.  Per segment:
+ *   1. Candidates: the pairs with mask != 0 (or no mask) whose six coordinates are finite, in ascending index; m of them.  A
+ *      candidate's local index is its rank in that list.
+ *   2. Sampler (that of o3dr_segment_plane): S = splitmix64(seed ^ key); draw k = 0, 1, 2 of hypothesis h = 0 .. H - 1 is
+ *      r = splitmix64(S + 3 h + k) (64-bit wrap-around), local index ((r >> 32) * m) >> 32.  splitmix64(x): z = x +
+ *      0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31).
+ *   3. Hypothesis, from the drawn pairs (a_k, b_k) = (src, tgt), every coordinate widened to fp64, every operation below a
+ *      single rounded fp64 operation (no contraction), IEEE division and square root.  On each side, with (p0, p1, p2) the
+ *      three points: u = p1 - p0, v = p2 - p0; w = u x v = (uy vz - uz vy, uz vx - ux vz, ux vy - uy vx); uu = (ux ux + uy uy)
+ *      + uz uz, vv and ww likewise; e1 = u / sqrt(uu), e3 = w / sqrt(ww) (each component divided), e2 = e3 x e1 by the same
+ *      cross-product formula; centroid c = ((p0 + p1) + p2) / 3.0 per component.  With e the src side's and e' the tgt
+ *      side's frame: R[i][j] = (e1'[i] e1[j] + e2'[i] e2[j]) + e3'[i] e3[j]; t[i] = c'[i] - ((R[i][0] c[0] + R[i][1] c[1]) +
+ *      R[i][2] c[2]).  The hypothesis is degenerate and scores 0 if two of its local indices coincide, or if on either side
+ *      ww <= (1e-12 * uu) * vv (zero-length edges included).
+ *   4. Score: the number of candidates with (dx dx + dy dy) + dz dz <= threshold * threshold (the product in fp64), d[i] =
+ *      (((R[i][0] x + R[i][1] y) + R[i][2] z) + t[i]) - b[i] for the candidate's src (x, y, z) and tgt b.  An exact integer.
+ *   5. Winner: the greatest score, ties to the lowest h.  No early exit: all H hypotheses are evaluated.
+ * Outputs.  inlier (n bytes, `mem`, index-aligned with src / tgt): 1 for the winner's inliers, 0 everywhere else
+ * (non-candidates included; bytes outside every segment are not written).  res (HOST, n_segs records): T (3 x 4 row-major
+ * fp64, src -> tgt: the winning hypothesis), n_candidates = m, n_inliers = the winning score, best_hypothesis = its h,
+ * sample (the three drawn pairs, as indices relative to the segment's first pair, in draw order), status.
+ * O3DR_RANSAC_TOO_FEW: m < 3.  O3DR_RANSAC_NO_MODEL: the best score is below 3 (every hypothesis degenerate, for one).  Both
+ * leave the segment's bytes 0, T the identity, n_inliers 0, best_hypothesis and sample -1.
+ * A segment's results equal those of a call on that segment alone with the same key; results are bit-identical across
+ * calls, batchings and memory kinds.  Limits, else O3DR_ERR_INVALID_ARG with the host outputs zeroed: the threshold, the
+ * iteration count, the segment list.  The call synchronises once, at its end; it does not use the sort workspace and leaves
+ * cloud_big alone.
+ *
+ * o3dr_pose_chain_robust - o3dr_pose_chain with that filter per pair of the static list.  rp == NULL: no filter, byte for
+ * byte o3dr_pose_chain (which is this call with rp = NULL, ransac_out = NULL).  Else, between the matching (step 2) and the
+ * chain (step 3), every pair (i, j) of the call's list is one segment of the contract above: its positions are the query
+ * rows of frame i, src = kp3[i][row], tgt = kp3[j][train_idx[0]] - both in camera coordinates: whether a correspondence fits
+ * a rigid model does not change when the target set is moved rigidly, so no pose is needed -, candidates = the good rows
+ * with both points finite, key = ((uint64)i << 32) | j with i, j the frame numbers: it does not depend on where the pair
+ * stands in the call's list, so the split into history and new frames stays bit-identical.  Every pair goes through it,
+ * whether or not frame j ends up accepted.  In step 3 a slot is used iff o3dr_pose_chain's conditions hold AND its pair's
+ * inlier byte is 1; n_good keeps its meaning, n_used and everything after it see the filtered set; reserved stays 0.
+ * ransac_out (HOST, or NULL): one o3dr_ransac_result per pair of the list, in list order (at least *n_pairs_out records:
+ * size it like pairs_out); sample holds query rows.  Its length is an output of the call, so an error does not zero it; it
+ * is written by a successful call only, and ignored when rp == NULL. */
+typedef struct o3dr_ransac_params {
+    double   threshold;     /* default 0.05 (metres) */
+    uint64_t seed;          /* default 0 */
+    int32_t  iterations;    /* default 256; 1 .. 65536 */
+    int32_t  reserved;      /* 0 */
+} o3dr_ransac_params;
+typedef struct o3dr_ransac_result {  /* 128 bytes */
+    double  T[12];
+    int32_t n_candidates, n_inliers;
+    int32_t best_hypothesis;
+    int32_t sample[3];
+    int32_t status;         /* O3DR_RANSAC_* */
+    int32_t reserved;       /* 0 */
+} o3dr_ransac_result;
+#define O3DR_RANSAC_OK       0
+#define O3DR_RANSAC_TOO_FEW  1
+#define O3DR_RANSAC_NO_MODEL 2
+#define O3DR_RANSAC_MAX_ITERATIONS 65536
+void o3dr_ransac_default_params(o3dr_ransac_params* p);
+int  o3dr_ransac_rigid(o3dr_ctx* ctx, const o3dr_point* src, const o3dr_point* tgt, int64_t n, const int64_t* seg_offsets,
+                       int32_t n_segs, const uint8_t* mask, const uint64_t* seg_keys, const o3dr_ransac_params* p, uint8_t* inlier,
+                       o3dr_ransac_result* res, int32_t mem);
+int  o3dr_pose_chain_robust(o3dr_ctx* ctx, const uint8_t* desc, const int64_t* offsets, const o3dr_point* kp3, const float* prior_poses,
+                            int32_t n_frames, int32_t n_fixed, const float* poses_in, const int32_t* status_in,
+                            const o3dr_chain_params* p, float* poses_out, o3dr_chain_frame* frames_out, int32_t* pairs_out,
+                            int64_t pairs_capacity, int64_t* n_pairs_out, int32_t mem, const o3dr_ransac_params* rp,
+                            o3dr_ransac_result* ransac_out);
+
 /* ---- measurement hooks (bench.py; not part of the reference surface) ------------------------ */
 /* kernel ids for o3dr_profile_* */
 #define O3DR_K_COUNT        0  /* grid-pass valid count per tile */
@@ -893,7 +968,8 @@ int  o3dr_pose_chain(o3dr_ctx* ctx, const uint8_t* desc, const int64_t* offsets,
 #define O3DR_K_ORB_DESCRIBE   16  /* ... orientation + steered BRIEF, one wave per keypoint */
 #define O3DR_K_MATCH          17  /* Hamming 2-NN: chunk scans + fold (o3dr_match_knn2_hamming, o3dr_pose_chain) */
 #define O3DR_K_POSE_CHAIN     18  /* pose chain: the one-workgroup walk over the frames */
-#define O3DR_K_NUM          19
+#define O3DR_K_RANSAC         19  /* three-point RANSAC for a rigid transform, one workgroup per segment (o3dr_ransac_rigid, o3dr_pose_chain_robust) */
+#define O3DR_K_NUM          20
 /* Bracket every launch of kernel `kernel_id` (or all kernels if -1) with HIP events on the
  * context's stream; 0 launches are bracketed when disabled (the default). */
 int o3dr_profile_enable(o3dr_ctx* ctx, int32_t kernel_id, int32_t enable);

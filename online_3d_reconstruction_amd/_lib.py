@@ -18,10 +18,10 @@ STATUS_INTERNAL = 0x80000000
 K_COUNT, K_REPROJECT, K_KEYGEN, K_SORT_HIST, K_SORT_SCATTER, K_SEGMENT, K_CENTROID, K_OTHER, K_CENTROID_RUNS = range(9)
 K_PLANE_DISP_SUMS, K_PLANE_DISP_FIT, K_PLANE_DISP_EVAL = 9, 10, 11
 K_ORB_PYRAMID, K_ORB_FAST, K_ORB_CANDIDATES, K_ORB_SELECT, K_ORB_DESCRIBE = 12, 13, 14, 15, 16
-K_MATCH, K_POSE_CHAIN = 17, 18
+K_MATCH, K_POSE_CHAIN, K_RANSAC = 17, 18, 19
 KERNEL_NAMES = ["reproject_count", "reproject_emit", "voxel_keys", "radix_hist", "radix_scatter", "run_segments",
                 "centroid", "other", "centroid_runs", "plane_disp_sums", "plane_disp_fit", "plane_disp_eval",
-                "orb_pyramid", "orb_fast", "orb_candidates", "orb_select", "orb_describe", "match", "pose_chain"]
+                "orb_pyramid", "orb_fast", "orb_candidates", "orb_select", "orb_describe", "match", "pose_chain", "ransac"]
 
 
 class O3drError(RuntimeError):
@@ -139,6 +139,19 @@ CHAIN_STATUS_NAMES = ["ANCHOR", "MATCHED", "TOO_FEW", "DEGENERATE", "RMS"]
 CHAIN_MAX_RANGE = 32
 
 
+class RansacParamsStruct(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("seed", C.c_uint64), ("iterations", C.c_int32), ("reserved", C.c_int32)]
+
+
+# o3dr_ransac_result (128 bytes), as a numpy record: one per segment (Context.ransacRigid) or pair (Context.poseChain)
+RANSAC_RESULT = np.dtype([("T", "<f8", (12,)), ("n_candidates", "<i4"), ("n_inliers", "<i4"), ("best_hypothesis", "<i4"),
+                          ("sample", "<i4", (3,)), ("status", "<i4"), ("reserved", "<i4")])
+assert RANSAC_RESULT.itemsize == 128
+RANSAC_OK, RANSAC_TOO_FEW, RANSAC_NO_MODEL = range(3)
+RANSAC_MAX_ITERATIONS = 65536
+RANSAC_STAGE = 1024  # candidates of a segment the kernel stages in LDS (kRansacStage); larger segments read the rest through a list
+
+
 def lib_path():
     return _LIB
 
@@ -223,6 +236,10 @@ SYMBOLS = [
     ("o3dr_chain_default_params", None, [C.POINTER(ChainParamsStruct)]),
     ("o3dr_pose_chain", C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, C.POINTER(ChainParamsStruct), _vp, _vp, _vp, _i64,
                                   _pi64, _i32]),
+    ("o3dr_ransac_default_params", None, [C.POINTER(RansacParamsStruct)]),
+    ("o3dr_ransac_rigid", C.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, C.POINTER(RansacParamsStruct), _vp, _vp, _i32]),
+    ("o3dr_pose_chain_robust", C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, C.POINTER(ChainParamsStruct), _vp, _vp, _vp,
+                                         _i64, _pi64, _i32, C.POINTER(RansacParamsStruct), _vp]),
     ("o3dr_profile_enable", C.c_int, [_vp, _i32, _i32]),
     ("o3dr_profile_read", C.c_int, [_vp, _i32, C.POINTER(C.c_double), _pi64]),
     ("o3dr_profile_reset", C.c_int, [_vp]),

@@ -690,12 +690,55 @@ class Context:
         out = [RigidResult.from_record(r) for r in res[:n_segs]]
         return out[0] if segs is None else out
 
-    def matchFeatures(self, desc_q, desc_t, kp3_q, kp3_t, ratio=0.5, max_distance=40):
+    def ransacRigid(self, src, tgt, threshold, iterations=256, seed=0, seg_offsets=None, mask=None, seg_keys=None):
+        """Batched three-point RANSAC for a rigid transform (contract: include/o3dr.h "robust rigid fit", DESIGN.md "Robust
+        fit"): per segment the hypothesis with the most pairs within `threshold` metres, of `iterations` hypotheses drawn
+        with `seed` and the segment's key (seg_keys, uint64 per segment; default: its ordinal).  Inputs as
+        estimateRigidTransform's.  -> (inlier: bool mask index-aligned with src - numpy, or a CUDA tensor for CUDA inputs -,
+        records: a numpy RANSAC_RESULT array, one per segment)."""
+        src, n = self._cloud(src)
+        tgt, n2 = self._cloud(tgt)
+        assert n == n2, "src and tgt must be index-aligned"
+        ps_, mem, _k = _ptr(src)
+        pt, mem2, _k2 = _ptr(tgt)
+        if n:
+            assert mem == mem2, "src and tgt must live in the same memory"
+        pm = None
+        if mask is not None:
+            if _is_torch(mask):
+                import torch
+                mask = mask.to(torch.uint8).contiguous()
+                pm = mask.data_ptr()
+            else:
+                mask = np.ascontiguousarray(mask).astype(np.uint8)
+                pm = mask.ctypes.data
+        segs = None if seg_offsets is None else np.ascontiguousarray(seg_offsets, np.int64).reshape(-1)
+        n_segs = 1 if segs is None else len(segs) - 1
+        keys = None if seg_keys is None else np.ascontiguousarray(seg_keys, np.uint64).reshape(-1)
+        assert keys is None or len(keys) == n_segs, "one key per segment"
+        prm = L.RansacParamsStruct(float(threshold), int(seed) & 0xFFFFFFFFFFFFFFFF, int(iterations), 0)
+        res = np.zeros(max(n_segs, 1), L.RANSAC_RESULT)
+        if mem == L.MEM_DEVICE and n:
+            import torch
+            inl = torch.zeros(n, dtype=torch.uint8, device=src.device)
+            self._order_after_torch()
+            pi = inl.data_ptr()
+        else:
+            inl = np.zeros(max(n, 1), np.uint8)
+            pi = inl.ctypes.data
+        L.check(self._lib.o3dr_ransac_rigid(self._h, ps_ if n else None, pt if n else None, n, None if segs is None else segs.ctypes.data,
+                                            n_segs, pm, None if keys is None else keys.ctypes.data, C.byref(prm), pi, res.ctypes.data,
+                                            mem))
+        return inl[:n] != 0, res[:n_segs]
+
+    def matchFeatures(self, desc_q, desc_t, kp3_q, kp3_t, ratio=0.5, max_distance=40, ransac_threshold=None, ransac_iterations=256,
+                      ransac_seed=0):
         """One frame pair of the reference's feature-matched mode (generate_tf_of_Matched_Keypoints, pose.cpp:213-235):
         2-NN match desc_q against desc_t, keep the good matches whose 3-D keypoints (kp3_q, kp3_t: index-aligned with the
         descriptors, e.g. from keypoints3D) are finite on both sides, and fit T mapping the query's points onto the
-        train's.  All numpy, or all torch CUDA tensors (the gather then stays on the device).
-        -> (records, kept mask (bool, one per query row), RigidResult)."""
+        train's.  With ransac_threshold (metres) the kept matches first go through ransacRigid (key 0) and the fit runs on
+        its inliers: the kept mask is then the inlier mask.  All numpy, or all torch CUDA tensors (the gather then stays on
+        the device).  -> (records, kept mask (bool, one per query row), RigidResult)."""
         dq, nq = self._desc(desc_q)
         dt, nt = self._desc(desc_t)
         kq, nkq = self._cloud(kp3_q)
@@ -710,27 +753,36 @@ class Context:
             tgt = kt[idx.clamp(0, max(nt - 1, 0))] if nt else torch.zeros_like(kq)
             fin = lambda p: torch.isfinite(p.view(torch.float32)[:, :3]).all(1)  # noqa: E731
             keep = good & (idx >= 0) & fin(kq) & fin(tgt)
-            res = self.estimateRigidTransform(kq, tgt.contiguous(), mask=keep)
+            tgt = tgt.contiguous()
+            if ransac_threshold is not None:
+                keep, _r = self.ransacRigid(kq, tgt, ransac_threshold, ransac_iterations, ransac_seed, mask=keep)
+            res = self.estimateRigidTransform(kq, tgt, mask=keep)
             return rec, keep, res
         rec, good = self.matchDescriptors(np.concatenate([dq, dt]), offsets, pairs, ratio, max_distance)
         idx = rec["train_idx"][:, 0].astype(np.int64)
         tgt = np.ascontiguousarray(kt[np.clip(idx, 0, max(nt - 1, 0))]) if nt else np.zeros_like(kq)
         fin = lambda p: np.isfinite(p["x"]) & np.isfinite(p["y"]) & np.isfinite(p["z"])  # noqa: E731
         keep = good & fin(kq) & fin(tgt)
+        if ransac_threshold is not None:
+            keep, _r = self.ransacRigid(kq, tgt, ransac_threshold, ransac_iterations, ransac_seed, mask=keep)
         res = self.estimateRigidTransform(kq, tgt, mask=keep)
         return rec, keep, res
 
     # -- pose chain (the reference's default mode: generate_tf_of_Matched_Keypoints per frame, pose.cpp:213-235) -----------
     def poseChain(self, desc, offsets, kp3, prior_poses, n_fixed=0, poses_in=None, status_in=None, dist_nearby=2.0, range_width=8,
-                  min_matches=30, max_rms=float("inf"), ratio=0.5, max_distance=40, return_pairs=False):
+                  min_matches=30, max_rms=float("inf"), ratio=0.5, max_distance=40, return_pairs=False, ransac_threshold=None,
+                  ransac_iterations=256, ransac_seed=0, return_ransac=False):
         """Every frame's pose from descriptor matches against earlier nearby frames (contract: include/o3dr.h "pose chain",
         DESIGN.md "Pose chain"): the static pair list from prior_poses, one batched matching pass, one launch that walks the
         frames n_fixed .. F - 1 in order.  desc uint8 [N, 32], kp3 N points in the camera frame (keypoints3D with poses=None),
         offsets the F + 1 row offsets (findFeatures'); all numpy, or desc / kp3 torch CUDA tensors.  prior_poses [F, 4, 4];
         the first n_fixed frames are history with poses_in [n_fixed, 4, 4] and status_in [n_fixed] (an earlier call's
         outputs).  These three are read on the host (a CUDA tensor is copied back first).
+        With ransac_threshold (metres) every pair's correspondences first go through the three-point RANSAC of ransacRigid
+        in camera coordinates (key = query frame << 32 | train frame) and the walk uses the inliers only.
         -> (poses [F, 4, 4] float32: numpy, or a CUDA tensor for CUDA inputs; records: a numpy CHAIN_FRAME array, one per
-        frame), and with return_pairs the pair list, int32 [P, 2] (query frame, train frame)."""
+        frame), with return_pairs the pair list, int32 [P, 2] (query frame, train frame), and with return_ransac a numpy
+        RANSAC_RESULT array, one per pair of the list (empty without ransac_threshold)."""
         desc, n = self._desc(desc)
         kp3, n3 = self._cloud(kp3)
         assert n == n3, "kp3 must be index-aligned with desc"
@@ -751,8 +803,12 @@ class Context:
         prm = L.ChainParamsStruct(float(dist_nearby), float(max_rms), int(range_width), int(min_matches), float(ratio),
                                   int(max_distance))
         rec = np.zeros(max(F, 1), L.CHAIN_FRAME)
-        cap = max(F * L.CHAIN_MAX_RANGE, 1) if return_pairs else 0
-        prs = np.zeros((cap, 2), np.int32) if return_pairs else None
+        robust = ransac_threshold is not None
+        want_pairs = return_pairs or (robust and return_ransac)
+        cap = max(F * L.CHAIN_MAX_RANGE, 1) if want_pairs else 0
+        prs = np.zeros((cap, 2), np.int32) if want_pairs else None
+        rprm = L.RansacParamsStruct(float(ransac_threshold), int(ransac_seed) & 0xFFFFFFFFFFFFFFFF, int(ransac_iterations), 0) if robust else None
+        rres = np.zeros(cap, L.RANSAC_RESULT) if robust and return_ransac else None
         n_pairs = C.c_int64(0)
         if mem == L.MEM_DEVICE:
             import torch
@@ -762,16 +818,25 @@ class Context:
         else:
             poses = np.zeros((max(F, 1), 16), np.float32)
             pp = poses.ctypes.data
-        L.check(self._lib.o3dr_pose_chain(self._h, pd if n else None, off.ctypes.data, pk if n else None, prior.ctypes.data, F, n_fixed,
-                                          pin.ctypes.data if len(pin) else None, sin.ctypes.data if len(sin) else None, C.byref(prm), pp,
-                                          rec.ctypes.data, None if prs is None else prs.ctypes.data, cap, C.byref(n_pairs), mem))
+        args = (self._h, pd if n else None, off.ctypes.data, pk if n else None, prior.ctypes.data, F, n_fixed,
+                pin.ctypes.data if len(pin) else None, sin.ctypes.data if len(sin) else None, C.byref(prm), pp, rec.ctypes.data,
+                None if prs is None else prs.ctypes.data, cap, C.byref(n_pairs), mem)
+        if robust:
+            L.check(self._lib.o3dr_pose_chain_robust(*args, C.byref(rprm), None if rres is None else rres.ctypes.data))
+        else:
+            L.check(self._lib.o3dr_pose_chain(*args))
         res = (poses[:F].reshape(F, 4, 4), rec[:F])
-        return res + (prs[: n_pairs.value],) if return_pairs else res
+        if return_pairs:
+            res += (prs[: n_pairs.value],)
+        if return_ransac:
+            res += (rres[: n_pairs.value] if rres is not None else np.zeros(0, L.RANSAC_RESULT),)
+        return res
 
     def trackFrames(self, img, disp, prior_poses, n_features=1500, scale_factor=1.3, n_levels=5, fast_threshold=20, edge=31,
                     **chain_kwargs):
         """findFeatures(img), keypoints3D(disp, poses=None) and poseChain over a stack of frames (img [F, H, W] or
-        [F, H, W, 3] uint8, disp [F, H, W]; numpy or torch CUDA tensors).  chain_kwargs: poseChain's keywords.
+        [F, H, W, 3] uint8, disp [F, H, W]; numpy or torch CUDA tensors).  chain_kwargs: poseChain's keywords (the
+        ransac_* ones among them).
         -> (poses, records, (kp_xy, offsets)); the pair feeds accumulateFrames(keypoints=...) for the accepted frames."""
         _kp, xy, desc, off = self.findFeatures(img, n_features=n_features, scale_factor=scale_factor, n_levels=n_levels,
                                                fast_threshold=fast_threshold, edge=edge)

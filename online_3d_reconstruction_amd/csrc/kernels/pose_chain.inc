@@ -22,7 +22,7 @@ static_assert(kChainRun == kRigidPoints && kChainRunWaves == 4, "the partition o
 static_assert(kChainThreads >= 12 * kChainMaxPairs, "step 0: one lane per pose entry");
 
 struct ChainSlot {
-    bool good, used;  // good row of an accepted train frame; all of the contract's conditions
+    bool good, used;  // good row of an accepted train frame; all of the contract's conditions (with the RANSAC byte, if any)
     float sx, sy, sz, tx, ty, tz;
 };
 
@@ -48,6 +48,7 @@ __device__ __forceinline__ ChainSlot chain_slot(const ChainArgs& a, const ChainF
     o.sx = sp.x, o.sy = sp.y, o.sz = sp.z;
     o.tx = X, o.ty = Y, o.tz = Z;
     o.used = isfinite(sp.x) && isfinite(sp.y) && isfinite(sp.z) && isfinite(X) && isfinite(Y) && isfinite(Z);
+    if (a.inlier && !a.inlier[r]) o.used = false;  // (o3dr_pose_chain_robust: the pair's RANSAC mask)
     return o;
 }
 

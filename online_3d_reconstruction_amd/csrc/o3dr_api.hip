@@ -151,6 +151,7 @@ struct o3dr_ctx {
     std::vector<int32_t> ch_pairs_h, ch_train_h, ch_status_h;  // ... and the pose chain's pair list, train frames, statuses, frames
     std::vector<ChainFrameIn> ch_frames_h;
     std::vector<RigidSeg> rg_seg_h;
+    std::vector<RansacSeg> rs_seg_h;  // the RANSAC's segment table (o3dr_ransac_rigid; the chain's pairs)
     std::vector<double> rg_T_h;
     int64_t place_ub = -1;   // o3dr_cloud_big_slice_counts_dev ran for a cloud of at most this many points and place_parts slices:
     int place_parts = 0;     // the (slice, tile) table in the workspace is what o3dr_cloud_big_place_slices moves by
@@ -3838,6 +3839,108 @@ extern "C" int o3dr_estimate_rigid_transform(o3dr_ctx* c, const o3dr_point* src,
 }
 
 // -------------------------------------------------------------------------------------------------
+// robust rigid fit (kernels/ransac.inc; contract: include/o3dr.h "robust rigid fit", DESIGN.md "Robust fit")
+// -------------------------------------------------------------------------------------------------
+extern "C" void o3dr_ransac_default_params(o3dr_ransac_params* p)
+{
+    if (!p) return;
+    p->threshold = 0.05;
+    p->seed = 0;
+    p->iterations = 256;
+    p->reserved = 0;
+}
+
+static int ransac_check(const o3dr_ransac_params& p)
+{
+    if (!(std::isfinite(p.threshold) && p.threshold > 0.0)) return fail(O3DR_ERR_INVALID_ARG, "the RANSAC threshold must be finite and > 0");
+    if (p.iterations < 1 || p.iterations > O3DR_RANSAC_MAX_ITERATIONS) return fail(O3DR_ERR_INVALID_ARG, "RANSAC iterations must be in [1, 65536]");
+    return O3DR_OK;
+}
+
+static int ransac_rigid(o3dr_ctx* c, const o3dr_point* src, const o3dr_point* tgt, int64_t n, const int64_t* seg_offsets, int32_t n_segs,
+                        const uint8_t* mask, const uint64_t* seg_keys, const o3dr_ransac_params* p, uint8_t* inlier, Outputs& outs,
+                        o3dr_ransac_result* res, int32_t mem)
+{
+    if (!res) return fail(O3DR_ERR_INVALID_ARG, "res is NULL");
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    if (n < 0 || (n > 0 && (!src || !tgt || !inlier))) return fail(O3DR_ERR_INVALID_ARG, "bad src / tgt / inlier / n");
+    if (n_segs < 1) return fail(O3DR_ERR_INVALID_ARG, "n_segs must be >= 1");
+    if (!seg_offsets && n_segs != 1) return fail(O3DR_ERR_INVALID_ARG, "seg_offsets is NULL with n_segs != 1");
+    o3dr_ransac_params prm;
+    o3dr_ransac_default_params(&prm);
+    if (p) prm = *p;
+    CHK(ransac_check(prm));
+    std::vector<RansacSeg>& seg = c->rs_seg_h;
+    seg.resize((size_t)n_segs);
+    uint64_t over = 0;
+    for (int32_t s = 0; s < n_segs; ++s) {
+        const int64_t a0 = seg_offsets ? seg_offsets[s] : 0, a1 = seg_offsets ? seg_offsets[s + 1] : n;
+        if (a0 < 0 || a1 < a0 || a1 > n) return fail(O3DR_ERR_INVALID_ARG, "seg_offsets must not decrease and stay within [0, n]");
+        if (a1 - a0 > (int64_t)INT32_MAX) return fail(O3DR_ERR_INVALID_ARG, "a segment holds more than 2^31-1 points");
+        seg[s].start = (uint64_t)a0;
+        seg[s].key = seg_keys ? seg_keys[s] : (uint64_t)s;
+        seg[s].over0 = over;
+        seg[s].n = (uint32_t)(a1 - a0);
+        seg[s].reserved = 0;
+        if (seg[s].n > (uint32_t)kRansacStage) over += seg[s].n - (uint32_t)kRansacStage;
+    }
+    c->place_ub = -1;
+    RansacArgs a;
+    memset(&a, 0, sizeof a);
+    a.src = src, a.tgt = tgt, a.mask = mask;
+    if (mem == O3DR_MEM_HOST) {
+        CHK(carve(c, c->op[o3dr_ctx::OP_IN], [&](Carve& w) {
+            w.take(a.src, (size_t)n);
+            w.take(a.tgt, (size_t)n);
+            w.take(a.mask, (size_t)n + 1);
+        }));
+        if (n > 0) {
+            HIPCHK(hipMemcpyAsync((void*)a.src, src, (size_t)n * sizeof(o3dr_point), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync((void*)a.tgt, tgt, (size_t)n * sizeof(o3dr_point), hipMemcpyHostToDevice, c->stream));
+            if (mask) HIPCHK(hipMemcpyAsync((void*)a.mask, mask, (size_t)n, hipMemcpyHostToDevice, c->stream));
+        }
+        if (!mask) a.mask = nullptr;
+    }
+    const size_t S = (size_t)n_segs;
+    RansacSeg* seg_d;
+    CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
+        w.take(seg_d, S);
+        w.take(a.over, (size_t)over + 1);
+        w.take(a.res, S);
+    }));
+    CHK(outs.stage(c));
+    a.seg = seg_d;
+    a.inlier = outs.dev(inlier);
+    a.seed = prm.seed;
+    a.thr2 = prm.threshold * prm.threshold;
+    a.iterations = (uint32_t)prm.iterations;
+    a.n_segs = (uint32_t)n_segs;
+    HIPCHK(hipMemcpyAsync(seg_d, seg.data(), S * sizeof(RansacSeg), hipMemcpyHostToDevice, c->stream));
+    // (bytes outside every segment are not the kernel's: a host output starts from zeros)
+    if (mem == O3DR_MEM_HOST && n > 0) HIPCHK(hipMemsetAsync(a.inlier, 0, (size_t)n, c->stream));
+    launch_ransac(&c->prof, c->stream, a, false);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(res, a.res, S * sizeof(o3dr_ransac_result), hipMemcpyDeviceToHost, c->stream));
+    CHK(outs.copy_back(c));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_ransac_rigid(o3dr_ctx* c, const o3dr_point* src, const o3dr_point* tgt, int64_t n, const int64_t* seg_offsets,
+                                 int32_t n_segs, const uint8_t* mask, const uint64_t* seg_keys, const o3dr_ransac_params* p,
+                                 uint8_t* inlier, o3dr_ransac_result* res, int32_t mem)
+{
+    Outputs outs{mem};
+    outs.add(inlier, n > 0 ? n : 0);
+    const int rc = entered(c, [&] { return ransac_rigid(c, src, tgt, n, seg_offsets, n_segs, mask, seg_keys, p, inlier, outs, res, mem); });
+    if (rc != O3DR_OK) {  // host outputs zeroed on error
+        outs.zero();
+        if (res && n_segs > 0) memset(res, 0, (size_t)n_segs * sizeof(o3dr_ransac_result));
+    }
+    return rc;
+}
+
+// -------------------------------------------------------------------------------------------------
 // pose chain (kernels/pose_chain.inc; contract: include/o3dr.h "pose chain", DESIGN.md "Pose chain")
 // -------------------------------------------------------------------------------------------------
 extern "C" void o3dr_chain_default_params(o3dr_chain_params* p)
@@ -3854,9 +3957,10 @@ extern "C" void o3dr_chain_default_params(o3dr_chain_params* p)
 static int pose_chain(o3dr_ctx* c, const uint8_t* desc, const int64_t* off, const o3dr_point* kp3, const float* prior, int32_t n_frames,
                       int32_t n_fixed, const float* poses_in, const int32_t* status_in, const o3dr_chain_params* p, float* poses_out,
                       o3dr_chain_frame* frames_out, Outputs& outs, int32_t* pairs_out, int64_t pairs_capacity, int64_t* n_pairs_out,
-                      int32_t mem)
+                      int32_t mem, const o3dr_ransac_params* rp, o3dr_ransac_result* ransac_out)
 {
     if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    if (rp) CHK(ransac_check(*rp));
     o3dr_chain_params prm;
     o3dr_chain_default_params(&prm);
     if (p) prm = *p;
@@ -3945,6 +4049,26 @@ static int pose_chain(o3dr_ctx* c, const uint8_t* desc, const int64_t* off, cons
     ChainFrameIn* frames_d;
     float* prior_d;
     o3dr_chain_frame* out_d;
+    // the RANSAC's segments: one per pair, keyed by its two frame numbers
+    std::vector<RansacSeg>& rseg = c->rs_seg_h;
+    rseg.clear();
+    uint64_t over = 0;
+    if (rp) {
+        rseg.resize((size_t)n_pairs);
+        for (int64_t k = 0; k < n_pairs; ++k) {
+            RansacSeg& g = rseg[(size_t)k];
+            g.start = tab[(size_t)k].rec0;
+            g.key = ((uint64_t)(uint32_t)pl[2 * (size_t)k] << 32) | (uint64_t)(uint32_t)pl[2 * (size_t)k + 1];
+            g.over0 = over;
+            g.n = tab[(size_t)k].nq;
+            g.reserved = 0;
+            if (g.n > (uint32_t)kRansacStage) over += g.n - (uint32_t)kRansacStage;
+        }
+    }
+    RansacSeg* rseg_d;
+    uint32_t* over_d;
+    uint8_t* inlier_d;
+    o3dr_ransac_result* rres_d;
     CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
         w.take(tab_d, tab.size() + 1);
         w.take(part_d, (size_t)plan.part + 1);
@@ -3955,6 +4079,10 @@ static int pose_chain(o3dr_ctx* c, const uint8_t* desc, const int64_t* off, cons
         w.take(frames_d, F);
         w.take(prior_d, F * 16);
         w.take(out_d, F);
+        w.take(rseg_d, rseg.size() + 1);
+        w.take(over_d, (size_t)over + 1);
+        w.take(inlier_d, rp ? (size_t)plan.rec + 1 : 1);
+        w.take(rres_d, rseg.size() + 1);
     }));
     CHK(outs.stage(c));
     float* poses_d = outs.dev(poses_out);
@@ -3984,6 +4112,26 @@ static int pose_chain(o3dr_ctx* c, const uint8_t* desc, const int64_t* off, cons
         launch_match(&c->prof, c->stream, m, tab_d, part_d);
         HIPCHK(hipGetLastError());
     }
+    // the pairs' inlier masks, in camera coordinates: static like the matching, one workgroup per pair ahead of the walk
+    if (rp && n_pairs > 0) {
+        RansacArgs g;
+        memset(&g, 0, sizeof g);
+        g.kp3 = kp3_d;
+        g.pairs = tab_d;
+        g.rec = rec_d;
+        g.good = good_d;
+        g.seg = rseg_d;
+        g.over = over_d;
+        g.inlier = inlier_d;
+        g.res = rres_d;
+        g.seed = rp->seed;
+        g.thr2 = rp->threshold * rp->threshold;
+        g.iterations = (uint32_t)rp->iterations;
+        g.n_segs = (uint32_t)n_pairs;
+        HIPCHK(hipMemcpyAsync(rseg_d, rseg.data(), rseg.size() * sizeof(RansacSeg), hipMemcpyHostToDevice, c->stream));
+        launch_ransac(&c->prof, c->stream, g, true);
+        HIPCHK(hipGetLastError());
+    }
     ChainArgs a;
     memset(&a, 0, sizeof a);
     a.kp3 = kp3_d;
@@ -3991,6 +4139,7 @@ static int pose_chain(o3dr_ctx* c, const uint8_t* desc, const int64_t* off, cons
     a.pair_train = train_d;
     a.rec = rec_d;
     a.good = good_d;
+    a.inlier = rp ? inlier_d : nullptr;
     a.frames = frames_d;
     a.prior = prior_d;
     a.poses = poses_d;
@@ -4005,9 +4154,35 @@ static int pose_chain(o3dr_ctx* c, const uint8_t* desc, const int64_t* off, cons
     if (n_fixed < n_frames)
         HIPCHK(hipMemcpyAsync(frames_out + n_fixed, out_d + n_fixed, (size_t)(n_frames - n_fixed) * sizeof(o3dr_chain_frame),
                               hipMemcpyDeviceToHost, c->stream));
+    if (rp && ransac_out && n_pairs > 0)
+        HIPCHK(hipMemcpyAsync(ransac_out, rres_d, (size_t)n_pairs * sizeof(o3dr_ransac_result), hipMemcpyDeviceToHost, c->stream));
     CHK(outs.copy_back(c));
     HIPCHK(hipStreamSynchronize(c->stream));
     return O3DR_OK;
+}
+
+extern "C" int o3dr_pose_chain_robust(o3dr_ctx* c, const uint8_t* desc, const int64_t* offsets, const o3dr_point* kp3,
+                                      const float* prior_poses, int32_t n_frames, int32_t n_fixed, const float* poses_in,
+                                      const int32_t* status_in, const o3dr_chain_params* p, float* poses_out, o3dr_chain_frame* frames_out,
+                                      int32_t* pairs_out, int64_t pairs_capacity, int64_t* n_pairs_out, int32_t mem,
+                                      const o3dr_ransac_params* rp, o3dr_ransac_result* ransac_out)
+{
+    if (n_pairs_out) *n_pairs_out = 0;
+    if (!rp) ransac_out = nullptr;
+    Outputs outs{mem};
+    outs.add(poses_out, n_frames > 0 ? 16 * (int64_t)n_frames : 0);
+    const int rc = entered(c, [&] {
+        return pose_chain(c, desc, offsets, kp3, prior_poses, n_frames, n_fixed, poses_in, status_in, p, poses_out, frames_out, outs,
+                          pairs_out, pairs_capacity, n_pairs_out, mem, rp, ransac_out);
+    });
+    if (rc != O3DR_OK && rc != O3DR_ERR_CAPACITY) {  // host outputs zeroed on error
+        if (n_pairs_out) *n_pairs_out = 0;
+        outs.zero();
+        if (frames_out && n_frames > 0) memset(frames_out, 0, (size_t)n_frames * sizeof(o3dr_chain_frame));
+        if (pairs_out && pairs_capacity > 0) memset(pairs_out, 0, (size_t)pairs_capacity * 2 * sizeof(int32_t));
+        // (ransac_out's length is the pair count, an output of the call: it is not zeroed; its copy is the call's last but one)
+    }
+    return rc;
 }
 
 extern "C" int o3dr_pose_chain(o3dr_ctx* c, const uint8_t* desc, const int64_t* offsets, const o3dr_point* kp3, const float* prior_poses,
@@ -4015,20 +4190,8 @@ extern "C" int o3dr_pose_chain(o3dr_ctx* c, const uint8_t* desc, const int64_t* 
                                const o3dr_chain_params* p, float* poses_out, o3dr_chain_frame* frames_out, int32_t* pairs_out,
                                int64_t pairs_capacity, int64_t* n_pairs_out, int32_t mem)
 {
-    if (n_pairs_out) *n_pairs_out = 0;
-    Outputs outs{mem};
-    outs.add(poses_out, n_frames > 0 ? 16 * (int64_t)n_frames : 0);
-    const int rc = entered(c, [&] {
-        return pose_chain(c, desc, offsets, kp3, prior_poses, n_frames, n_fixed, poses_in, status_in, p, poses_out, frames_out, outs,
-                          pairs_out, pairs_capacity, n_pairs_out, mem);
-    });
-    if (rc != O3DR_OK && rc != O3DR_ERR_CAPACITY) {  // host outputs zeroed on error
-        if (n_pairs_out) *n_pairs_out = 0;
-        outs.zero();
-        if (frames_out && n_frames > 0) memset(frames_out, 0, (size_t)n_frames * sizeof(o3dr_chain_frame));
-        if (pairs_out && pairs_capacity > 0) memset(pairs_out, 0, (size_t)pairs_capacity * 2 * sizeof(int32_t));
-    }
-    return rc;
+    return o3dr_pose_chain_robust(c, desc, offsets, kp3, prior_poses, n_frames, n_fixed, poses_in, status_in, p, poses_out, frames_out,
+                                  pairs_out, pairs_capacity, n_pairs_out, mem, nullptr, nullptr);
 }
 
 // -------------------------------------------------------------------------------------------------

@@ -372,6 +372,7 @@ struct ChainArgs {
     const int32_t* pair_train;   // the train frame of every pair
     const uint4* rec;            // launch_match's records and mask
     const uint8_t* good;
+    const uint8_t* inlier;       // launch_ransac_chain's byte per record, or nullptr: no filter
     const ChainFrameIn* frames;  // n_frames
     const float* prior;          // n_frames * 16
     float* poses;                // n_frames * 16: history on entry, every frame on exit
@@ -381,6 +382,33 @@ struct ChainArgs {
     double max_rms;
 };
 void launch_pose_chain(Profiler* pf, hipStream_t s, const ChainArgs& a);
+// three-point RANSAC for a rigid transform (kernels/ransac.inc): one workgroup per segment
+constexpr int kRansacThreads = 256;
+constexpr int kRansacStage = 1024;  // candidates of a segment staged in LDS (6 floats + the position each: 28 KiB); the rest go through `over`
+struct RansacSeg {
+    uint64_t start;     // first point (o3dr_ransac_rigid) / first record of the pair (the chain): where its inlier bytes start too
+    uint64_t key;       // the sampler's key
+    uint64_t over0;     // its slice of `over`: max(n - kRansacStage, 0) entries
+    uint32_t n;         // points / query rows
+    uint32_t reserved;
+};
+struct RansacArgs {
+    const o3dr_point* src;       // o3dr_ransac_rigid: index-aligned points and the mask (or nullptr)
+    const o3dr_point* tgt;
+    const uint8_t* mask;
+    const o3dr_point* kp3;       // the chain: the pool, launch_match's table, records and mask (ChainArgs)
+    const MatchPair* pairs;
+    const uint4* rec;
+    const uint8_t* good;
+    const RansacSeg* seg;        // n_segs
+    uint32_t* over;              // positions of the candidates past kRansacStage, per segment
+    uint8_t* inlier;             // one byte per point / record
+    o3dr_ransac_result* res;     // n_segs
+    uint64_t seed;
+    double thr2;                 // threshold^2
+    uint32_t iterations, n_segs;
+};
+void launch_ransac(Profiler* pf, hipStream_t s, const RansacArgs& a, bool chain);
 // The dense XY cell order of a cloud (kernels/cell_order.inc): the points sorted by the dense id
 // (iy - y0) * wx + (ix - x0) of their cell, input order kept inside a cell.  The operator's Args (PlaneArgs, MeshArgs:
 // cloud, n, the parameter of its index rule, `cells`) select the index rule.

@@ -35,6 +35,7 @@
 //   match        Hamming 2-NN descriptor matching, index-aligned 3-D keypoints, the batched rigid fit
 //   orb          ORB features: grey pyramid, FAST score + box sums, candidates, exact selection, steered BRIEF
 //   pose_chain   the feature-matched pose chain: one workgroup walks the frames (gather, moments, Kabsch, residual)
+//   ransac       three-point RANSAC for a rigid transform: one workgroup per segment / pair of the chain
 // The launchers follow in this file.
 #include <string.h>
 
@@ -63,6 +64,7 @@ namespace o3dr {
 #include "kernels/plane_disparity.inc"
 #include "kernels/orb.inc"
 #include "kernels/pose_chain.inc"
+#include "kernels/ransac.inc"
 
 // =================================================================================================
 // launchers
@@ -1023,6 +1025,17 @@ void launch_pose_chain(Profiler* pf, hipStream_t s, const ChainArgs& a)
 {
     ProfScope ps(pf, O3DR_K_POSE_CHAIN, s);
     if (a.n_fixed < a.n_frames) k_pose_chain<<<1, kChainThreads, 0, s>>>(a);
+}
+
+// three-point RANSAC (kernels/ransac.inc): one workgroup per segment / pair
+void launch_ransac(Profiler* pf, hipStream_t s, const RansacArgs& a, bool chain)
+{
+    ProfScope ps(pf, O3DR_K_RANSAC, s);
+    if (a.n_segs == 0) return;
+    if (chain)
+        k_ransac_rigid<true><<<a.n_segs, kRansacThreads, 0, s>>>(a);
+    else
+        k_ransac_rigid<false><<<a.n_segs, kRansacThreads, 0, s>>>(a);
 }
 
 // height-field surface mesh (kernels/mesh.inc)

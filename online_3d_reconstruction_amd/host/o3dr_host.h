@@ -146,6 +146,10 @@ public:
     int range_width = 8;
     int chain_min_matches = 30;       // --chain_min_matches
     double chain_max_rms = HUGE_VAL;  // --chain_max_rms (default: no gate)
+    bool chain_ransac = false;        // --chain_ransac_threshold given: o3dr_pose_chain_robust filters every pair's correspondences
+    double chain_ransac_threshold = 0.05;  // (metres), --chain_ransac_iterations, --chain_ransac_seed
+    int chain_ransac_iterations = 256;
+    uint64_t chain_ransac_seed = 0;
     std::string print_label_png;      // --print_label_png f: rows, cols and the labels of f as text (checks the reader)
 
     std::vector<RawImageData> rawImageDataVec;

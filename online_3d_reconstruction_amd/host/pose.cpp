@@ -426,11 +426,16 @@ void Pose::printUsage()
             "       [--gpu_keypoints]  (reconstruction run with jump_pixels != 1 and no --keypoints_dir: every batch's keypoints come\n"
             "                     from the same extractor on its rgb images, with the --orb_* flags; single-GPU batched path only)\n"
             "       [--feature_poses] [--dist_nearby m] [--range_width n] [--chain_min_matches n] [--chain_max_rms m]\n"
+            "       [--chain_ransac_threshold m] [--chain_ransac_iterations n] [--chain_ransac_seed s]\n"
             "                     (reconstruction run: every frame's pose from ORB matches against the earlier frames whose recorded\n"
             "                     position lies within --dist_nearby metres (default 2), at most --range_width of them (default 8,\n"
             "                     the most recent); a frame with fewer than --chain_min_matches correspondences (default 30), a\n"
             "                     degenerate fit or an rms above --chain_max_rms is printed as Rejected! and left out of the cloud;\n"
-            "                     --dist_nearby and --range_width act under this flag only; shares the extractor call with\n"
+            "                     with --chain_ransac_threshold (metres; absent: off) every frame pair's correspondences first go\n"
+            "                     through a three-point RANSAC for a rigid transform (--chain_ransac_iterations hypotheses, default\n"
+            "                     256, drawn with --chain_ransac_seed, default 0), the fit uses the inliers only and the frame's line\n"
+            "                     gains \"dropped n\", the correspondences the filter took out;\n"
+            "                     --dist_nearby, --range_width and the --chain_* flags act under this flag only; shares the extractor call with\n"
             "                     --gpu_keypoints; single-GPU batched path only; the flag is this build's own)\n"
             "Without --feature_poses the run uses the recorded MAVLink poses (--only_MAVLink).  The ICP trajectory correction,\n"
             "visualisation and --segment_cloud in a reconstruction run are not part of this build.\n";
@@ -518,6 +523,9 @@ int Pose::parseCmdArgs(int argc, char** argv)
         else if (a == "--feature_poses") feature_poses = true;
         else if (a == "--chain_min_matches") chain_min_matches = atoi(need(i));
         else if (a == "--chain_max_rms") chain_max_rms = atof(need(i));
+        else if (a == "--chain_ransac_threshold") { chain_ransac_threshold = atof(need(i)); chain_ransac = true; }
+        else if (a == "--chain_ransac_iterations") chain_ransac_iterations = atoi(need(i));
+        else if (a == "--chain_ransac_seed") chain_ransac_seed = strtoull(need(i), nullptr, 0);
         else if (a == "--preview") preview = true;
         else if (a == "--use_segment_labels") use_segment_labels = true;
         else if (a == "--segment_labels_dir") segmentLabelsPrefix = need(i);
@@ -1022,12 +1030,32 @@ void Pose::run_reconstruction()
                 cp.range_width = range_width;
                 cp.min_matches = chain_min_matches;
                 cp.max_rms = chain_max_rms;
+                // --chain_ransac_threshold: the pair list and one RANSAC record per pair come back too, for the dropped counts
+                o3dr_ransac_params rp;
+                o3dr_ransac_default_params(&rp);
+                rp.threshold = chain_ransac_threshold;
+                rp.iterations = chain_ransac_iterations;
+                rp.seed = chain_ransac_seed;
+                const size_t pair_cap = chain_ransac ? n_acc * (size_t)O3DR_CHAIN_MAX_RANGE : 0;
+                vector<int32_t> pair_list(2 * pair_cap + 2);
+                vector<o3dr_ransac_result> rres(pair_cap + 1);
+                int64_t n_list = 0;
                 if (rc_chain == O3DR_OK) {
-                    rc_chain = o3dr_pose_chain(c, chain.desc.data(), chain.off.data(), chain.kp3.data(), chain.prior.data(), (int32_t)n_all,
-                                               (int32_t)n_hist, chain.poses.data(), chain.status.data(), &cp, chain_out.data(), recs.data(),
-                                               nullptr, 0, nullptr, O3DR_MEM_HOST);
+                    rc_chain = o3dr_pose_chain_robust(c, chain.desc.data(), chain.off.data(), chain.kp3.data(), chain.prior.data(),
+                                                      (int32_t)n_all, (int32_t)n_hist, chain.poses.data(), chain.status.data(), &cp,
+                                                      chain_out.data(), recs.data(), chain_ransac ? pair_list.data() : nullptr,
+                                                      (int64_t)pair_cap, &n_list, O3DR_MEM_HOST, chain_ransac ? &rp : nullptr,
+                                                      chain_ransac ? rres.data() : nullptr);
                     if (rc_chain != O3DR_OK) why_chain = string("pose_chain: ") + o3dr_last_error();
                 }
+                // a frame's dropped slots: over its pairs with an accepted train frame, the candidates that are no inliers
+                vector<int64_t> dropped(n_all, 0);
+                if (rc_chain == O3DR_OK && chain_ransac)
+                    for (int64_t k = 0; k < n_list; ++k) {
+                        const int32_t st_j = recs[(size_t)pair_list[2 * (size_t)k + 1]].status;
+                        if (st_j == O3DR_CHAIN_ANCHOR || st_j == O3DR_CHAIN_MATCHED)
+                            dropped[(size_t)pair_list[2 * (size_t)k]] += rres[(size_t)k].n_candidates - rres[(size_t)k].n_inliers;
+                    }
                 if (rc_chain == O3DR_OK) {
                     static const char* const names[] = {"ANCHOR", "MATCHED", "TOO_FEW", "DEGENERATE", "RMS"};
                     chain.poses = chain_out;
@@ -1043,8 +1071,9 @@ void Pose::run_reconstruction()
                         memcpy(im.t_mat_FeatureMatched.data(), &chain_out[16 * (n_hist + k)], 64);
                         const bool ok = r.status == O3DR_CHAIN_ANCHOR || r.status == O3DR_CHAIN_MATCHED;
                         cout << im.raw_img_data_ptr->img_num << " pose chain: " << names[r.status] << " pairs " << r.n_pairs_accepted << "/"
-                             << r.n_pairs << " good " << r.n_good << " used " << r.n_used << " rms " << r.rms
-                             << (ok ? "\tAccepted!" : "\tRejected!") << endl;
+                             << r.n_pairs << " good " << r.n_good << " used " << r.n_used << " rms " << r.rms;
+                        if (chain_ransac) cout << " dropped " << dropped[n_hist + k];
+                        cout << (ok ? "\tAccepted!" : "\tRejected!") << endl;
                         if (!ok) continue;
                         // the accepted frames move up in the stacks (m <= k)
                         const size_t m = n_cloud++;
