@@ -38,6 +38,11 @@ int o3dr_test_fail_at(o3dr_ctx* ctx, int32_t point);
  * capacity (in hypotheses) below it: O3DR_ERR_CAPACITY with *n_out set.  The scores are what the choice of step 4 of the
  * contract reads, so the tests compare every one of them with a restatement. */
 int o3dr_test_plane_hypotheses(o3dr_ctx* ctx, float* planes, uint32_t* counts, int64_t capacity, int64_t* n_out);
+/* Later o3dr_orb_detect calls of this context split their frames into groups whose scratch fits `bytes` instead of the
+ * built-in 1 GiB, so that a handful of small frames runs the group loop (frame base, running total, offsets, pyramid
+ * copies).  bytes = 0 restores the default; a value below one frame's need still gives groups of one frame.  The
+ * results must not depend on it. */
+int o3dr_test_orb_scratch_limit(o3dr_ctx* ctx, int64_t bytes);
 
 #ifdef __cplusplus
 }

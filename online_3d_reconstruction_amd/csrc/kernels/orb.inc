@@ -293,8 +293,8 @@ __global__ __launch_bounds__(256) void k_orb_select(OrbArgs a)
     __shared__ uint32_t s_want;
     const int l = blockIdx.x, f = blockIdx.y, seg = f * a.n_levels + l, tid = threadIdx.x;
     const uint32_t n = a.seg_cand[seg], quota = (uint32_t)a.lv[l].quota;
-    if (n <= quota) {
-        if (tid == 0) a.seg_sel[seg] = n;
+    if (n <= quota || quota == 0) {  // everything is kept, or (a level whose share of n_features rounds to 0) nothing is
+        if (tid == 0) a.seg_sel[seg] = n <= quota ? n : 0u;
         return;
     }
     long long* R = a.cand_r + (int64_t)f * a.cands_per_frame + a.lv[l].cand0;
@@ -322,7 +322,7 @@ __global__ __launch_bounds__(256) void k_orb_select(OrbArgs a)
         __syncthreads();
     }
     const unsigned long long cut = s_prefix;
-    const uint32_t ties_kept = s_want;  // >= 1
+    const uint32_t ties_kept = s_want;  // >= 1: quota >= 1 here, and every pass leaves want >= 1
     uint32_t run_tie = 0, run_out = 0;
     for (uint32_t c0 = 0; c0 < n; c0 += 256) {
         const uint32_t i = c0 + tid;

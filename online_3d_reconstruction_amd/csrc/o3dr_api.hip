@@ -145,6 +145,7 @@ struct o3dr_ctx {
     DevBuf orb_work, orb_pat;  // o3dr_orb_detect: its own scratch block (one carve per call) and the steered table
     bool orb_pat_valid = false;
     std::vector<int8_t> orb_pat_h;  // (outlives the asynchronous upload)
+    int64_t test_orb_scratch = 0;   // o3dr_test_orb_scratch_limit: stands in for kOrbScratchBytes when positive
     DevBuf pl_hyp;             // o3dr_segment_plane: hypotheses + scores (plane_hyp_layout), kept for the test hook
     uint64_t pl_last_hyp = 0;  // hypotheses of the last call in pl_hyp (o3dr_test_plane_hypotheses)
     std::vector<MatchPair> mt_tab_h;  // host copies of the match pair table, the rigid fit's segment table and transforms
@@ -4459,7 +4460,8 @@ static int orb_detect(o3dr_ctx* c, const uint8_t* img, int64_t fs, int64_t pitch
     a.pattern = (const int8_t*)c->orb_pat.p;
 
     const size_t per_frame = (size_t)a.P * 4 + (size_t)a.cands_per_frame * 12 + (size_t)a.chunks_per_frame * 4 + (size_t)prm.n_levels * 16;
-    size_t group = std::max<size_t>(1, kOrbScratchBytes / per_frame);
+    const size_t limit = c->test_orb_scratch > 0 ? (size_t)c->test_orb_scratch : kOrbScratchBytes;
+    size_t group = std::max<size_t>(1, limit / per_frame);
     group = std::min<size_t>(std::min<size_t>(group, (size_t)n_frames), 32768);
     CHK(carve(c, c->orb_work, [&](Carve& w) {
         w.take(a.pyr, group * (size_t)a.P);
@@ -4507,6 +4509,15 @@ static int orb_detect(o3dr_ctx* c, const uint8_t* img, int64_t fs, int64_t pitch
     CHK(outs.copy_back(c));
     HIPCHK(hipStreamSynchronize(c->stream));
     *n_out = offsets[n_frames];
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_test_orb_scratch_limit(o3dr_ctx* c, int64_t bytes)
+{
+    CTX_ENTER(c);
+    if (!c->test_hooks) return fail(O3DR_ERR_INVALID_ARG, "test hooks are off (create the context with O3DR_TEST_HOOKS=1)");
+    if (bytes < 0) return fail(O3DR_ERR_INVALID_ARG, "bytes is negative");
+    c->test_orb_scratch = bytes;
     return O3DR_OK;
 }
 
