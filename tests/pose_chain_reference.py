@@ -80,10 +80,12 @@ def kabsch_rank_ref(src, tgt):
 
 
 def chain_ref(desc, offsets, kp3, prior, n_fixed=0, poses_in=None, status_in=None, dist_nearby=2.0, range_width=8, min_matches=30,
-              max_rms=np.inf, ratio=0.5, max_distance=40, nudge=0):
+              max_rms=np.inf, ratio=0.5, max_distance=40, nudge=0, match=None):
     """-> dict(poses [F, 16] float32, status, n_pairs, n_pairs_accepted, n_good, n_used, rms, T [F, 12] fp64, pairs [(i, j)],
-    gathered {i: (src, tgt) float32 [n_used, 3]}).  nudge = +1 / -1: every fitted fp32 pose entry moved one ulp up / down
-    (the tests measure the chain's sensitivity to the last bit of a pose with it)."""
+    gathered {i: (src, tgt) float32 [n_used, 3]}, match {(i, j): (idx, good)} for the pairs with an accepted train frame).
+    nudge = +1 / -1: every fitted fp32 pose entry moved one ulp up / down (the tests measure the chain's sensitivity to the
+    last bit of a pose with it).  match: an earlier result's `match` for the same desc, offsets, ratio and max_distance (the
+    matching does not depend on the poses), so that a second run need not repeat the brute force."""
     desc = np.asarray(desc, np.uint8).reshape(-1, 32)
     off = np.asarray(offsets, np.int64)
     xyz = np.asarray(kp3, np.float32).reshape(-1, 3)
@@ -93,7 +95,7 @@ def chain_ref(desc, offsets, kp3, prior, n_fixed=0, poses_in=None, status_in=Non
     poses = prior.copy()
     r = dict(status=np.zeros(F, np.int32), n_pairs=np.zeros(F, np.int32), n_pairs_accepted=np.zeros(F, np.int32),
              n_good=np.zeros(F, np.int32), n_used=np.zeros(F, np.int32), rms=np.zeros(F), T=np.zeros((F, 12)), pairs=pairs,
-             gathered={})
+             gathered={}, match={})
     for f in range(n_fixed):
         poses[f] = np.asarray(poses_in, np.float32).reshape(-1, 16)[f]
         r["status"][f] = status_in[f]
@@ -109,8 +111,12 @@ def chain_ref(desc, offsets, kp3, prior, n_fixed=0, poses_in=None, status_in=Non
             if r["status"][j] > MATCHED:
                 continue
             r["n_pairs_accepted"][i] += 1
-            idx, dist = knn2_ref(desc[off[i]:off[i + 1]], desc[off[j]:off[j + 1]])
-            good = good_ref(dist, ratio, max_distance)
+            if match is not None and (i, j) in match:
+                idx, good = match[(i, j)]
+            else:
+                idx, dist = knn2_ref(desc[off[i]:off[i + 1]], desc[off[j]:off[j + 1]])
+                good = good_ref(dist, ratio, max_distance)
+            r["match"][(i, j)] = (idx, good)
             r["n_good"][i] += int(good.sum())
             rows = np.nonzero(good)[0]
             s = q3[rows]
@@ -149,6 +155,33 @@ def chain_ref(desc, offsets, kp3, prior, n_fixed=0, poses_in=None, status_in=Non
     return r
 
 
+def slot_flags(offsets, kp3, ref, i, inlier=None):
+    """Frame i's correspondence slots in the library's order (pair-major: slot s is row s % nq of pair s // nq, the pairs in
+    the list's order), from a chain_ref / robust_chain_ref result alone.  -> dict(good [n_pairs * nq] bool: a good row of an
+    accepted train frame; used [..] bool: good, src and the moved tgt finite (and an inlier, with inlier = the robust
+    reference's {(i, j): mask}); tgt [.., 3] float32: the moved tgt of the good slots, 0 elsewhere)."""
+    off = np.asarray(offsets, np.int64)
+    xyz = np.asarray(kp3, np.float32).reshape(-1, 3)
+    mine = [j for (q, j) in ref["pairs"] if q == i]
+    nq = int(off[i + 1] - off[i])
+    good = np.zeros((len(mine), nq), bool)
+    used = np.zeros((len(mine), nq), bool)
+    tgt = np.zeros((len(mine), nq, 3), np.float32)
+    q3 = xyz[off[i]:off[i + 1]]
+    for lp, j in enumerate(mine):
+        if ref["status"][j] > MATCHED:
+            continue
+        idx, g = ref["match"][(i, j)]
+        rows = np.nonzero(g)[0]
+        t = a2(ref["poses"][j], xyz[off[j]:off[j + 1]][idx[rows, 0].astype(np.int64)])
+        good[lp] = g
+        tgt[lp, rows] = t
+        used[lp, rows] = np.isfinite(q3[rows]).all(1) & np.isfinite(t).all(1)
+        if inlier is not None:
+            used[lp] &= inlier[(i, j)]
+    return dict(good=good.reshape(-1), used=used.reshape(-1), tgt=tgt.reshape(-1, 3))
+
+
 # ---- the synthetic world --------------------------------------------------------------------------------------------------
 def rot(axis, angle):
     axis = np.asarray(axis, np.float64) / np.linalg.norm(axis)
@@ -164,10 +197,12 @@ def true_pose(k, step=0.5):
     return T
 
 
-def make_world(seed, views, n_landmarks, step=0.5, prior_err=0.05, max_flips=8, poses=None):
+def make_world(seed, views, n_landmarks, step=0.5, prior_err=0.05, max_flips=8, poses=None, kp3_noise=0.0):
     """views: per frame, the landmark indices it sees (its rows, in that order).  -> dict(desc [N, 32] uint8, offsets,
     kp3 [N, 3] float32 = inverse(true pose) landmark, landmark [N] (each row's landmark), true [F, 4, 4] fp64,
-    prior [F, 16] float32 = the true poses plus a translation error of at most prior_err per axis, positions [M, 3])."""
+    prior [F, 16] float32 = the true poses plus a translation error of at most prior_err per axis, positions [M, 3]).
+    kp3_noise > 0: Gaussian noise of that many metres (sigma per axis) on the rounded kp3, from a generator of its own, so
+    that everything else equals the world without it: a fit that loses correspondences then moves by far more than rounding."""
     rng = np.random.default_rng(seed)
     M = int(n_landmarks)
     base = rng.integers(0, 256, (M, 32), dtype=np.uint8)
@@ -190,6 +225,9 @@ def make_world(seed, views, n_landmarks, step=0.5, prior_err=0.05, max_flips=8, 
     prior = true.copy()
     prior[:, :3, 3] += rng.uniform(-prior_err, prior_err, (F, 3))
     cat = lambda xs, shape, dt: np.concatenate(xs) if xs else np.zeros(shape, dt)  # noqa: E731
+    if kp3_noise:
+        nrng = np.random.default_rng([int(seed), 0x6B7033])
+        kp3 = [(k.astype(np.float64) + nrng.normal(0.0, float(kp3_noise), k.shape)).astype(np.float32) for k in kp3]
     return dict(desc=cat(desc, (0, 32), np.uint8), offsets=offsets, kp3=cat(kp3, (0, 3), np.float32),
                 landmark=cat(lm, (0,), np.int64), true=true, prior=prior.astype(np.float32).reshape(F, 16), positions=pos)
 

@@ -145,10 +145,12 @@ def pair_key(i, j):
 
 def robust_chain_ref(desc, offsets, kp3, prior, n_fixed=0, poses_in=None, status_in=None, dist_nearby=2.0, range_width=8,
                      min_matches=30, max_rms=np.inf, ratio=0.5, max_distance=40, nudge=0, ransac_threshold=None,
-                     ransac_iterations=256, ransac_seed=0):
+                     ransac_iterations=256, ransac_seed=0, static=None):
     """chain_ref of pose_chain_reference.py with the per-pair RANSAC filter (ransac_threshold None: chain_ref itself, plus
     the empty extras).  Extra keys: ransac (one record dict per pair of the list), inlier {(i, j): bool per query row},
-    n_dropped [F] (slots the filter alone dropped), gap."""
+    n_dropped [F] (slots the filter alone dropped), gap, match {(i, j): (idx, good)} of every pair.  static: an earlier
+    result for the same inputs and parameters but another nudge - the matching and the filter work in camera coordinates
+    and do not depend on the poses, so they are taken from it."""
     desc = np.asarray(desc, np.uint8).reshape(-1, 32)
     off = np.asarray(offsets, np.int64)
     xyz = np.asarray(kp3, np.float32).reshape(-1, 3)
@@ -157,7 +159,10 @@ def robust_chain_ref(desc, offsets, kp3, prior, n_fixed=0, poses_in=None, status
     pairs = R.pair_list(prior, dist_nearby, range_width, n_fixed)
     # static: matching and the filter of every pair, in camera coordinates
     match, inlier, rrec, gap = {}, {}, [], np.inf
-    for (i, j) in pairs:
+    if static is not None:
+        assert static["pairs"] == pairs
+        match, inlier, rrec, gap = static["match"], static["inlier"], static["ransac"], static["gap"]
+    for (i, j) in (pairs if static is None else []):
         idx, dist = R.knn2_ref(desc[off[i]:off[i + 1]], desc[off[j]:off[j + 1]])
         good = R.good_ref(dist, ratio, max_distance)
         match[(i, j)] = (idx, good)
@@ -172,7 +177,7 @@ def robust_chain_ref(desc, offsets, kp3, prior, n_fixed=0, poses_in=None, status
     poses = prior.copy()
     r = dict(status=np.zeros(F, np.int32), n_pairs=np.zeros(F, np.int32), n_pairs_accepted=np.zeros(F, np.int32),
              n_good=np.zeros(F, np.int32), n_used=np.zeros(F, np.int32), rms=np.zeros(F), T=np.zeros((F, 12)), pairs=pairs,
-             gathered={}, ransac=rrec, inlier=inlier, n_dropped=np.zeros(F, np.int32), gap=gap)
+             gathered={}, ransac=rrec, inlier=inlier, n_dropped=np.zeros(F, np.int32), gap=gap, match=match)
     for f in range(n_fixed):
         poses[f] = np.asarray(poses_in, np.float32).reshape(-1, 16)[f]
         r["status"][f] = status_in[f]
@@ -229,6 +234,16 @@ def robust_chain_ref(desc, offsets, kp3, prior, n_fixed=0, poses_in=None, status
             r["T"][i] = poses[i, :12].astype(np.float64)
     r["poses"] = poses
     return r
+
+
+def assert_ransac_equal(rr, ref):
+    """the library's per-pair RANSAC records against robust_chain_ref's: integers exactly, T within 1e-9"""
+    assert len(rr) == len(ref["ransac"])
+    for k, want in enumerate(ref["ransac"]):
+        for f in ("n_candidates", "n_inliers", "best_hypothesis", "status"):
+            assert rr[f][k] == want[f], (k, f)
+        assert rr["sample"][k].tolist() == want["sample"], k
+        assert np.abs(rr["T"][k] - want["T"]).max() <= 1e-9, k
 
 
 # ---- the corrupted world --------------------------------------------------------------------------------------------------

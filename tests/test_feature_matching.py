@@ -466,3 +466,93 @@ def test_scale_against_chunked_torch_reference(ctx):
         d1, d2 = (best[..., 0] >> 32).reshape(-1), (best[..., 1] >> 32).reshape(-1)
         gr = (d1 < 40) & (d1.to(torch.float32) < 0.5 * d2.to(torch.float32))
         assert torch.equal(good[p0 * rows:(p0 + len(q)) * rows], gr), p0
+
+
+# ---- chunk sizes other than 64 ------------------------------------------------------------------------------------------
+BIG_TRAIN = [127, 128, 129, 5000, 1]
+BIG_QUERY = [1, 65, 300]
+BIG_FILLERS = {128: (6400, 8000), 192: (6400, 12000)}  # chunk_rows -> (nq, nt) of a filler pair that raises the call's chunk size
+
+
+def _chunk_rows(pairs_sizes):
+    """match_plan's chunk size (o3dr_api.hip) restated: work = sum over the pairs of ceil(nq / 64) nt, aimed at 8192 work
+    items, rounded up to a multiple of 64, at least 64"""
+    work = sum(-(-nq // 64) * nt for nq, nt in pairs_sizes)
+    return max(64, -(-(-(-work // 8192)) // 64) * 64)
+
+
+def _big_chunk_pool(chunk):
+    """-> (desc, offsets, the checked pairs, the filler pair).  Sets: BIG_TRAIN, BIG_QUERY, the filler's query and train set.
+    Duplicate train rows straddle the chunk boundaries 128 (rows 127 | 128), 192 (191 | 192) and 4992 = 39 x 128 = 26 x 192
+    (4991 | 4992), and queries equal them: d1 == d2 == 0, decided by the lower row, across two chunks."""
+    rng = np.random.default_rng(19 + chunk)
+    fq, ft = BIG_FILLERS[chunk]
+    desc, off = _pool(rng, BIG_TRAIN + BIG_QUERY + [fq, ft])
+    nt = len(BIG_TRAIN)
+    t129, t5000 = int(off[2]), int(off[3])
+    desc[t129 + 128] = desc[t129 + 127]
+    for a in (127, 191, 4991):
+        desc[t5000 + a + 1] = desc[t5000 + a]
+    for qs in (nt + 1, nt + 2):  # the 65- and the 300-row query sets
+        q0 = int(off[qs])
+        desc[q0 + 3] = desc[t5000 + 127]
+        desc[q0 + 20] = desc[t5000 + 191]
+        desc[q0 + 64] = desc[t5000 + 4991]
+        desc[q0 + 40] = desc[t129 + 127]
+    checked = [(nt + k, s) for k in range(len(BIG_QUERY)) for s in range(nt)]
+    filler = (nt + len(BIG_QUERY), nt + len(BIG_QUERY) + 1)
+    return desc, off, checked, filler
+
+
+@pytest.mark.parametrize("chunk", sorted(BIG_FILLERS))
+def test_filler_pair_raises_the_chunk_size(chunk):
+    """CPU twin of test_multi_chunk_pairs_with_a_larger_chunk: with the filler the call's chunk is 128 / 192, so the
+    5000-row train set takes 40 / 27 chunks with a partial last one; without it the checked pairs run at 64."""
+    desc, off, checked, filler = _big_chunk_pool(chunk)
+    size = lambda s: int(off[s + 1] - off[s])  # noqa: E731
+    sizes = [(size(q), size(t)) for q, t in checked]
+    assert sorted(set(sizes)) == sorted((q, t) for q in BIG_QUERY for t in BIG_TRAIN)
+    assert _chunk_rows(sizes) == 64
+    c = _chunk_rows(sizes + [(size(filler[0]), size(filler[1]))])
+    assert c == chunk > 64 and 5000 % c != 0 and c < 5000 and 4992 % c == 0 and size(filler[1]) % c != 0
+    assert _chunk_rows([(1500, 1500)] * 1600) == 7040  # test_scale_against_chunked_torch_reference: one chunk per pair
+    idx, dist, _ = batch_ref(desc, off, [(len(BIG_TRAIN) + 2, 3), (len(BIG_TRAIN) + 2, 2)])
+    assert idx[[3, 20, 64]].tolist() == [[127, 128], [191, 192], [4991, 4992]] and not dist[[3, 20, 64]].any()
+    assert idx[300 + 40].tolist() == [127, 128] and not dist[300 + 40].any()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("chunk", sorted(BIG_FILLERS))
+def test_multi_chunk_pairs_with_a_larger_chunk(ctx, chunk):
+    """Checked pairs next to a filler pair that raises chunk_rows to 128 / 192 (test_filler_pair_raises_the_chunk_size):
+    their records and good mask equal the brute force and, bit for bit, the same pairs run alone at chunk 64.  The filler
+    itself is checked against a torch top-2 on the device, 400 query rows at a time."""
+    import torch
+    desc, off, checked, filler = _big_chunk_pool(chunk)
+    rec, good = ctx.matchDescriptors(desc, off, [filler] + checked)
+    fq = int(off[filler[0] + 1] - off[filler[0]])
+    n = sum(int(off[q + 1] - off[q]) for q, _ in checked)
+    assert len(rec) == fq + n
+    mid, gmid = rec[fq:fq + n], good[fq:fq + n]
+    idx, dist, g = batch_ref(desc, off, checked)
+    gi, gd = _records(mid)
+    assert np.array_equal(gi, idx) and np.array_equal(gd, dist) and np.array_equal(gmid, g)
+    alone, galone = ctx.matchDescriptors(desc, off, checked)
+    assert alone.tobytes() == mid.tobytes() and np.array_equal(galone, gmid)
+    # the filler: (d << 32 | row) keys, the two smallest per query row
+    dd = torch.from_numpy(desc).cuda()
+    pop = torch.tensor(POP8, dtype=torch.int32, device="cuda")
+    q = dd[int(off[filler[0]]):int(off[filler[0] + 1])].to(torch.int32)
+    t = dd[int(off[filler[1]]):int(off[filler[1] + 1])].to(torch.int32)
+    j = torch.arange(len(t), device="cuda", dtype=torch.int64)
+    got = torch.from_numpy(np.ascontiguousarray(rec[:fq]).view(np.uint32).reshape(-1, 4).astype(np.int64)).cuda()
+    for a in range(0, fq, 400):
+        d = torch.zeros((len(q[a:a + 400]), len(t)), dtype=torch.int64, device="cuda")
+        for k in range(32):
+            d += pop[q[a:a + 400, None, k] ^ t[None, :, k]]
+        best = torch.topk((d << 32) | j, 2, dim=1, largest=False, sorted=True).values
+        want = torch.stack([best[:, 0] & 0xFFFFFFFF, best[:, 1] & 0xFFFFFFFF, best[:, 0] >> 32, best[:, 1] >> 32], 1)
+        assert torch.equal(got[a:a + 400], want), a
+        d1, d2 = want[:, 2], want[:, 3]
+        gr = (d1 < 40) & (d1.to(torch.float32) < 0.5 * d2.to(torch.float32))
+        assert np.array_equal(good[a:a + 400], gr.cpu().numpy()), a

@@ -12,6 +12,7 @@ import pytest
 import pose_chain_reference as R
 import ransac_rigid_reference as RR
 from online_3d_reconstruction_amd import _lib as L
+from ransac_rigid_reference import assert_ransac_equal
 
 DIST = 1.2  # (test_pose_chain.py: the two frames before, never the third)
 THR = 0.05
@@ -47,15 +48,6 @@ def assert_integers_equal(rec, ref):
     for k in ("status", "n_pairs", "n_pairs_accepted", "n_good", "n_used"):
         assert np.array_equal(rec[k], ref[k]), (k, rec[k], ref[k])
     assert (rec["reserved"] == 0).all()
-
-
-def assert_ransac_equal(rr, ref):
-    assert len(rr) == len(ref["ransac"])
-    for k, want in enumerate(ref["ransac"]):
-        for f in ("n_candidates", "n_inliers", "best_hypothesis", "status"):
-            assert rr[f][k] == want[f], (k, f)
-        assert rr["sample"][k].tolist() == want["sample"], k
-        assert np.abs(rr["T"][k] - want["T"]).max() <= 1e-9, k
 
 
 # ---- CPU --------------------------------------------------------------------------------------------------------------------
