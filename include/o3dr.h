@@ -947,6 +947,98 @@ int  o3dr_pose_chain_robust(o3dr_ctx* ctx, const uint8_t* desc, const int64_t* o
                             int64_t pairs_capacity, int64_t* n_pairs_out, int32_t mem, const o3dr_ransac_params* rp,
                             o3dr_ransac_result* ransac_out);
 
+/* ---- pose graph: one joint least-squares refinement of the pose chain's accepted frames over all pairs at once.  The chain
+ * (above) fits frame i once, against earlier frames, and never moves it again; here every pair pulls on both of its frames.
+ * The contract is this library's own; tests/pose_graph_reference.py restates it in numpy, DESIGN.md "Pose-graph refinement"
+ * derives the formulas.
+ *
+ * Inputs.  desc, offsets, kp3, n_frames and mem as in o3dr_pose_chain.  poses_in (HOST, [n_frames, 16] fp32) and status_in
+ * (HOST, [n_frames] O3DR_CHAIN_* values): a chain call's outputs.  fixed (HOST, [n_frames] bytes, or NULL: none): a non-zero
+ * byte holds the frame.  prior_poses (HOST, [n_frames, 16] fp32, or NULL): required iff prior_weight > 0; only its
+ * translations are used.  pairs (HOST, n_pairs int32 (i, j) frame pairs, i != j, any order, no pair twice - (i, j) and (j, i)
+ * are different pairs): o3dr_pose_chain's pairs_out goes straight in.  rp: NULL, or the filter of o3dr_pose_chain_robust.
+ *   1. Matching: one batched o3dr_match_knn2_hamming pass over `pairs` (query set i, train set j; ratio, max_distance); with
+ *      rp every pair then goes through the RANSAC of o3dr_pose_chain_robust, key ((uint64)i << 32) | j.
+ *   2. Pair moments.  A query row of pair (i, j) is used iff both frames are accepted (ANCHOR or MATCHED), the row is good,
+ *      a = kp3[i][row] and b = kp3[j][train_idx[0]] are finite and, with rp, the inlier byte is set.  Both points stay in
+ *      camera coordinates.  Per pair 28 fp64 sums, no contraction: n, sum a (3), sum b (3), sum a a^T (xx xy xz yy yz zz),
+ *      sum b b^T (6), sum a b^T (9, row-major), over runs of 256 consecutive rows from the pair's first (wave sums, the run =
+ *      the tree of its four waves), the runs folded left to right - no float atomics.  n_good = the pair's good rows
+ *      (whatever the statuses), n_used = the used rows.  A pair is an edge iff both frames are accepted and n_used >=
+ *      min_pair_matches.  An edge's moments equal those of a call with that pair alone.
+ *   3. Roles (host).  degree = the edges a frame is part of.  A frame is O3DR_REFINE_FREE iff it is MATCHED, not fixed and
+ *      degree > 0; a rejected frame (TOO_FEW, DEGENERATE, RMS) is O3DR_REFINE_REJECTED; every other frame is
+ *      O3DR_REFINE_FIXED, and holds the gauge where degree > 0.  With prior_weight == 0 the free frames of a connected
+ *      component (over the edges) without a gauge frame become O3DR_REFINE_FLOATING: held, and reported.
+ *   4. Solve, one launch of one workgroup.  State (R, t) per frame in fp64: t = (m3, m7, m11) of the fp32 pose, R its rows
+ *      0..2 orthonormalised once: e1 = r1 / |r1|, u = r2 - (r2 . e1) e1, e2 = u / |u|, e3 = e1 x e2.  Energy
+ *        E = sum_edges sum_k |R_i a + t_i - R_j b - t_j|^2 + prior_weight sum_free |t_i - prior_t_i|^2,
+ *      evaluated from the moments.  gn_iterations Gauss-Newton steps, all of them always: the 6 x 6 blocks and gradient
+ *      halves of every edge in the right perturbation R <- R C(w), t <- t + R v; per frame the diagonal block and g summed
+ *      over its (edge, side) list in pair order; each diagonal block inverted by Cholesky; exactly cg_iterations steps of
+ *      block-Jacobi preconditioned CG on H x = -g over the free frames from x = 0 (a dot product: thread t of 256 sums the
+ *      entries t, t + 256, .. in ascending order, wave sums, then (w0 + w1) + (w2 + w3)); p^T H p <= 0 or a non-finite
+ *      scalar stops that solve with what it has and sets O3DR_REFINE_FLAG_CG_STOPPED (a gradient that is exactly zero does
+ *      so too); a diagonal block that is not positive definite holds its frame for that step and sets
+ *      O3DR_REFINE_FLAG_SINGULAR; then every free frame is retracted, C(w) = the rotation of the unit quaternion
+ *      (1, w / 2) / |.|.  Only + - * / sqrt.
+ * Outputs.  poses_out ([n_frames, 16] fp32, `mem`): fp32(R | t) with the bottom row 0 0 0 1 for a free frame, the 64 bytes
+ * of poses_in for every other.  frames_out (HOST, n_frames records): role, degree, T (3 x 4 row-major fp64: the state of a
+ * free frame, else the input pose widened).  edges_out (HOST, n_pairs records, or NULL): n_good, n_used, edge (0 / 1), the
+ * edge's energy at the input and at the output poses (0 for a pair that is no edge).  res (HOST): energy_before /
+ * energy_after; grad_before / grad_after = the 2-norm of g over the free frames at the input / output poses; last_step =
+ * max |x| of the last iteration; n_free, n_gauge (FIXED frames with degree > 0), n_floating, n_rejected, n_edges, n_used
+ * (over the edges), flags.  No free frame or no edge: O3DR_OK, the poses are copied, energy_after == energy_before.
+ * Results are bit-identical across calls and across host and device memory.
+ * Limits, else O3DR_ERR_INVALID_ARG (host outputs and *res zeroed): 1 <= gn_iterations <= 64, 1 <= cg_iterations <= 1024,
+ * min_pair_matches >= 1, prior_weight finite and >= 0, prior_poses given when prior_weight > 0, ratio and max_distance as in
+ * o3dr_match_params, rp as in o3dr_ransac_rigid, status_in within the enum, pair indices within [0, n_frames), i != j, no
+ * pair twice, the pool at most 2^31-1 rows; n_frames == 0: O3DR_OK.  p == NULL: the defaults.  The call synchronises twice:
+ * after the per-pair counts and at its end; it does not use the sort workspace and leaves cloud_big alone. */
+typedef struct o3dr_refine_params {
+    double  prior_weight;      /* default 0: no prior */
+    int32_t gn_iterations;     /* default 5; 1..64 */
+    int32_t cg_iterations;     /* default 32; 1..1024 */
+    int32_t min_pair_matches;  /* default 3; >= 1 */
+    float   ratio;             /* default 0.5 */
+    int32_t max_distance;      /* default 40 */
+    int32_t reserved;          /* 0 */
+} o3dr_refine_params;
+typedef struct o3dr_refine_frame {  /* 104 bytes */
+    int32_t role;              /* O3DR_REFINE_* */
+    int32_t degree;
+    double  T[12];
+} o3dr_refine_frame;
+typedef struct o3dr_refine_edge {  /* 32 bytes */
+    int32_t n_good, n_used;
+    int32_t edge;              /* 1: the pair is an edge */
+    int32_t reserved;          /* 0 */
+    double  energy_before, energy_after;
+} o3dr_refine_edge;
+typedef struct o3dr_refine_result {  /* 72 bytes */
+    double  energy_before, energy_after;
+    double  grad_before, grad_after;
+    double  last_step;
+    int64_t n_used;
+    int32_t n_free, n_gauge, n_floating, n_rejected;
+    int32_t n_edges;
+    int32_t flags;             /* O3DR_REFINE_FLAG_* */
+} o3dr_refine_result;
+#define O3DR_REFINE_FIXED    0
+#define O3DR_REFINE_FREE     1
+#define O3DR_REFINE_FLOATING 2
+#define O3DR_REFINE_REJECTED 3
+#define O3DR_REFINE_FLAG_CG_STOPPED 1
+#define O3DR_REFINE_FLAG_SINGULAR   2
+#define O3DR_REFINE_MAX_GN 64
+#define O3DR_REFINE_MAX_CG 1024
+void o3dr_refine_default_params(o3dr_refine_params* p);
+int  o3dr_pose_graph_refine(o3dr_ctx* ctx, const uint8_t* desc, const int64_t* offsets, const o3dr_point* kp3, int32_t n_frames,
+                            const float* poses_in, const int32_t* status_in, const uint8_t* fixed, const float* prior_poses,
+                            const int32_t* pairs, int64_t n_pairs, const o3dr_refine_params* p, const o3dr_ransac_params* rp,
+                            float* poses_out, o3dr_refine_frame* frames_out, o3dr_refine_edge* edges_out, o3dr_refine_result* res,
+                            int32_t mem);
+
 /* ---- measurement hooks (bench.py; not part of the reference surface) ------------------------ */
 /* kernel ids for o3dr_profile_* */
 #define O3DR_K_COUNT        0  /* grid-pass valid count per tile */
@@ -969,7 +1061,9 @@ int  o3dr_pose_chain_robust(o3dr_ctx* ctx, const uint8_t* desc, const int64_t* o
 #define O3DR_K_MATCH          17  /* Hamming 2-NN: chunk scans + fold (o3dr_match_knn2_hamming, o3dr_pose_chain) */
 #define O3DR_K_POSE_CHAIN     18  /* pose chain: the one-workgroup walk over the frames */
 #define O3DR_K_RANSAC         19  /* three-point RANSAC for a rigid transform, one workgroup per segment (o3dr_ransac_rigid, o3dr_pose_chain_robust) */
-#define O3DR_K_NUM          20
+#define O3DR_K_GRAPH_MOMENTS 20  /* pose graph: the 28 fp64 moments of every pair, one workgroup per pair */
+#define O3DR_K_GRAPH_SOLVE   21  /* ... Gauss-Newton + preconditioned CG, the one-workgroup solve */
+#define O3DR_K_NUM          22
 /* Bracket every launch of kernel `kernel_id` (or all kernels if -1) with HIP events on the
  * context's stream; 0 launches are bracketed when disabled (the default). */
 int o3dr_profile_enable(o3dr_ctx* ctx, int32_t kernel_id, int32_t enable);

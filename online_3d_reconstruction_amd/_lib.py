@@ -19,9 +19,11 @@ K_COUNT, K_REPROJECT, K_KEYGEN, K_SORT_HIST, K_SORT_SCATTER, K_SEGMENT, K_CENTRO
 K_PLANE_DISP_SUMS, K_PLANE_DISP_FIT, K_PLANE_DISP_EVAL = 9, 10, 11
 K_ORB_PYRAMID, K_ORB_FAST, K_ORB_CANDIDATES, K_ORB_SELECT, K_ORB_DESCRIBE = 12, 13, 14, 15, 16
 K_MATCH, K_POSE_CHAIN, K_RANSAC = 17, 18, 19
+K_GRAPH_MOMENTS, K_GRAPH_SOLVE = 20, 21
 KERNEL_NAMES = ["reproject_count", "reproject_emit", "voxel_keys", "radix_hist", "radix_scatter", "run_segments",
                 "centroid", "other", "centroid_runs", "plane_disp_sums", "plane_disp_fit", "plane_disp_eval",
-                "orb_pyramid", "orb_fast", "orb_candidates", "orb_select", "orb_describe", "match", "pose_chain", "ransac"]
+                "orb_pyramid", "orb_fast", "orb_candidates", "orb_select", "orb_describe", "match", "pose_chain", "ransac",
+                "graph_moments", "graph_solve"]
 
 
 class O3drError(RuntimeError):
@@ -152,6 +154,27 @@ RANSAC_MAX_ITERATIONS = 65536
 RANSAC_STAGE = 1024  # candidates of a segment the kernel stages in LDS (kRansacStage); larger segments read the rest through a list
 
 
+class RefineParamsStruct(C.Structure):
+    _fields_ = [("prior_weight", C.c_double), ("gn_iterations", C.c_int32), ("cg_iterations", C.c_int32),
+                ("min_pair_matches", C.c_int32), ("ratio", C.c_float), ("max_distance", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RefineResultStruct(C.Structure):
+    _fields_ = [("energy_before", C.c_double), ("energy_after", C.c_double), ("grad_before", C.c_double), ("grad_after", C.c_double),
+                ("last_step", C.c_double), ("n_used", C.c_int64), ("n_free", C.c_int32), ("n_gauge", C.c_int32),
+                ("n_floating", C.c_int32), ("n_rejected", C.c_int32), ("n_edges", C.c_int32), ("flags", C.c_int32)]
+
+
+# o3dr_refine_frame (104 bytes) and o3dr_refine_edge (32 bytes), as numpy records: Context.refinePoses returns one per frame / pair
+REFINE_FRAME = np.dtype([("role", "<i4"), ("degree", "<i4"), ("T", "<f8", (12,))])
+REFINE_EDGE = np.dtype([("n_good", "<i4"), ("n_used", "<i4"), ("edge", "<i4"), ("reserved", "<i4"), ("energy_before", "<f8"),
+                        ("energy_after", "<f8")])
+assert REFINE_FRAME.itemsize == 104 and REFINE_EDGE.itemsize == 32 and C.sizeof(RefineResultStruct) == 72
+REFINE_FIXED, REFINE_FREE, REFINE_FLOATING, REFINE_REJECTED = range(4)
+REFINE_ROLE_NAMES = ["FIXED", "FREE", "FLOATING", "REJECTED"]
+REFINE_FLAG_CG_STOPPED, REFINE_FLAG_SINGULAR = 1, 2
+
+
 def lib_path():
     return _LIB
 
@@ -240,6 +263,9 @@ SYMBOLS = [
     ("o3dr_ransac_rigid", C.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, C.POINTER(RansacParamsStruct), _vp, _vp, _i32]),
     ("o3dr_pose_chain_robust", C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, C.POINTER(ChainParamsStruct), _vp, _vp, _vp,
                                          _i64, _pi64, _i32, C.POINTER(RansacParamsStruct), _vp]),
+    ("o3dr_refine_default_params", None, [C.POINTER(RefineParamsStruct)]),
+    ("o3dr_pose_graph_refine", C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(RefineParamsStruct),
+                                         C.POINTER(RansacParamsStruct), _vp, _vp, _vp, C.POINTER(RefineResultStruct), _i32]),
     ("o3dr_profile_enable", C.c_int, [_vp, _i32, _i32]),
     ("o3dr_profile_read", C.c_int, [_vp, _i32, C.POINTER(C.c_double), _pi64]),
     ("o3dr_profile_reset", C.c_int, [_vp]),

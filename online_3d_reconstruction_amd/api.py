@@ -86,6 +86,25 @@ class RigidResult:
         return RigidResult(np.array(r["T"], np.float64).reshape(4, 4), float(r["rms"]), int(r["n_used"]), int(r["status"]))
 
 
+@dataclass
+class RefineResult:
+    """o3dr_pose_graph_refine's result: the energy and the 2-norm of the gradient over the free frames at the input and at
+    the output poses, max |step| of the last Gauss-Newton iteration, the frames per role, the edges, the correspondences
+    over the edges and the flags (REFINE_FLAG_CG_STOPPED, REFINE_FLAG_SINGULAR)."""
+    energy_before: float
+    energy_after: float
+    grad_before: float
+    grad_after: float
+    last_step: float
+    n_free: int
+    n_gauge: int
+    n_floating: int
+    n_rejected: int
+    n_edges: int
+    n_used: int
+    flags: int
+
+
 def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
@@ -771,7 +790,7 @@ class Context:
     # -- pose chain (the reference's default mode: generate_tf_of_Matched_Keypoints per frame, pose.cpp:213-235) -----------
     def poseChain(self, desc, offsets, kp3, prior_poses, n_fixed=0, poses_in=None, status_in=None, dist_nearby=2.0, range_width=8,
                   min_matches=30, max_rms=float("inf"), ratio=0.5, max_distance=40, return_pairs=False, ransac_threshold=None,
-                  ransac_iterations=256, ransac_seed=0, return_ransac=False):
+                  ransac_iterations=256, ransac_seed=0, return_ransac=False, refine=False, refine_kw=None):
         """Every frame's pose from descriptor matches against earlier nearby frames (contract: include/o3dr.h "pose chain",
         DESIGN.md "Pose chain"): the static pair list from prior_poses, one batched matching pass, one launch that walks the
         frames n_fixed .. F - 1 in order.  desc uint8 [N, 32], kp3 N points in the camera frame (keypoints3D with poses=None),
@@ -782,7 +801,10 @@ class Context:
         in camera coordinates (key = query frame << 32 | train frame) and the walk uses the inliers only.
         -> (poses [F, 4, 4] float32: numpy, or a CUDA tensor for CUDA inputs; records: a numpy CHAIN_FRAME array, one per
         frame), with return_pairs the pair list, int32 [P, 2] (query frame, train frame), and with return_ransac a numpy
-        RANSAC_RESULT array, one per pair of the list (empty without ransac_threshold)."""
+        RANSAC_RESULT array, one per pair of the list (empty without ransac_threshold).
+        refine=True: refinePoses runs on the outputs and the pair list (the history frames fixed; ratio, max_distance and
+        the ransac_* keywords passed through; refine_kw: its other keywords); the poses returned are the refined ones, the
+        records stay the chain's, and the RefineResult is appended to the tuple."""
         desc, n = self._desc(desc)
         kp3, n3 = self._cloud(kp3)
         assert n == n3, "kp3 must be index-aligned with desc"
@@ -804,7 +826,7 @@ class Context:
                                   int(max_distance))
         rec = np.zeros(max(F, 1), L.CHAIN_FRAME)
         robust = ransac_threshold is not None
-        want_pairs = return_pairs or (robust and return_ransac)
+        want_pairs = return_pairs or (robust and return_ransac) or refine
         cap = max(F * L.CHAIN_MAX_RANGE, 1) if want_pairs else 0
         prs = np.zeros((cap, 2), np.int32) if want_pairs else None
         rprm = L.RansacParamsStruct(float(ransac_threshold), int(ransac_seed) & 0xFFFFFFFFFFFFFFFF, int(ransac_iterations), 0) if robust else None
@@ -826,18 +848,91 @@ class Context:
         else:
             L.check(self._lib.o3dr_pose_chain(*args))
         res = (poses[:F].reshape(F, 4, 4), rec[:F])
+        rr = None
+        if refine:
+            kw = dict(refine_kw or {})
+            fx = np.zeros(F, bool)
+            fx[:max(min(n_fixed, F), 0)] = True
+            kw.setdefault("fixed", fx)
+            if kw.get("prior_weight", 0.0) > 0.0:
+                kw.setdefault("prior_poses", prior)
+            refined, _frames, rr = self.refinePoses(desc, off, kp3, res[0], rec["status"][:F], prs[: n_pairs.value], ratio=ratio,
+                                                    max_distance=max_distance, ransac_threshold=ransac_threshold,
+                                                    ransac_iterations=ransac_iterations, ransac_seed=ransac_seed, **kw)
+            res = (refined, rec[:F])
         if return_pairs:
             res += (prs[: n_pairs.value],)
         if return_ransac:
             res += (rres[: n_pairs.value] if rres is not None else np.zeros(0, L.RANSAC_RESULT),)
+        if refine:
+            res += (rr,)
         return res
+
+    # -- pose-graph refinement (the bundle adjustment the reference leaves commented out: pose_functions.cpp:1876-1921) -----
+    def refinePoses(self, desc, offsets, kp3, poses, status, pairs, fixed=None, prior_poses=None, prior_weight=0.0, gn_iterations=5,
+                    cg_iterations=32, min_pair_matches=3, ratio=0.5, max_distance=40, ransac_threshold=None, ransac_iterations=256,
+                    ransac_seed=0, return_edges=False):
+        """One joint least-squares refinement of a pose chain's accepted frames over all `pairs` at once (contract:
+        include/o3dr.h "pose graph", DESIGN.md "Pose-graph refinement").  desc, offsets, kp3 as in poseChain; poses
+        [F, 4, 4] and status [F] are poseChain's outputs, pairs its pair list (int32 [P, 2]); these, fixed ([F] bool: frames
+        to hold) and prior_poses ([F, 4, 4], needed iff prior_weight > 0) are read on the host.  The ransac_* keywords are
+        poseChain's.  -> (poses [F, 4, 4] float32: numpy, or a CUDA tensor for CUDA desc / kp3; records: a numpy
+        REFINE_FRAME array, one per frame; RefineResult), with return_edges a numpy REFINE_EDGE array, one per pair."""
+        desc, n = self._desc(desc)
+        kp3, n3 = self._cloud(kp3)
+        assert n == n3, "kp3 must be index-aligned with desc"
+        pd, mem, _k = _ptr(desc)
+        pk, mem2, _k2 = _ptr(kp3)
+        if n:
+            assert mem == mem2, "desc and kp3 must live in the same memory"
+        host = lambda a, dt: np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else a, dt)  # noqa: E731
+        off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        F = len(off) - 1
+        pin = host(poses, np.float32).reshape(-1, 16)
+        sin = host(status, np.int32).reshape(-1)
+        assert F >= 0 and len(pin) == F and len(sin) == F, "one pose and one status per frame"
+        prs = host(pairs, np.int32).reshape(-1, 2)
+        P = len(prs)
+        fx = None if fixed is None else np.ascontiguousarray(host(fixed, np.bool_).reshape(-1).astype(np.uint8))
+        assert fx is None or len(fx) == F, "one fixed flag per frame"
+        pri = None if prior_poses is None else host(prior_poses, np.float32).reshape(-1, 16)
+        assert pri is None or len(pri) == F, "one prior pose per frame"
+        prm = L.RefineParamsStruct(float(prior_weight), int(gn_iterations), int(cg_iterations), int(min_pair_matches), float(ratio),
+                                   int(max_distance), 0)
+        rprm = None
+        if ransac_threshold is not None:
+            rprm = L.RansacParamsStruct(float(ransac_threshold), int(ransac_seed) & 0xFFFFFFFFFFFFFFFF, int(ransac_iterations), 0)
+        rec = np.zeros(max(F, 1), L.REFINE_FRAME)
+        edg = np.zeros(max(P, 1), L.REFINE_EDGE) if return_edges else None
+        res = L.RefineResultStruct()
+        if mem == L.MEM_DEVICE:
+            import torch
+            out = torch.zeros((max(F, 1), 16), dtype=torch.float32, device=desc.device)
+            self._order_after_torch()
+            pp = out.data_ptr()
+        else:
+            out = np.zeros((max(F, 1), 16), np.float32)
+            pp = out.ctypes.data
+        L.check(self._lib.o3dr_pose_graph_refine(
+            self._h, pd if n else None, off.ctypes.data, pk if n else None, F, pin.ctypes.data if F else None,
+            sin.ctypes.data if F else None, None if fx is None or not F else fx.ctypes.data,
+            None if pri is None or not F else pri.ctypes.data, prs.ctypes.data if P else None, P, C.byref(prm),
+            None if rprm is None else C.byref(rprm), pp, rec.ctypes.data, None if edg is None else edg.ctypes.data, C.byref(res), mem))
+        rr = RefineResult(float(res.energy_before), float(res.energy_after), float(res.grad_before), float(res.grad_after),
+                          float(res.last_step), int(res.n_free), int(res.n_gauge), int(res.n_floating), int(res.n_rejected),
+                          int(res.n_edges), int(res.n_used), int(res.flags))
+        ret = (out[:F].reshape(F, 4, 4), rec[:F], rr)
+        if return_edges:
+            ret += (edg[:P],)
+        return ret
 
     def trackFrames(self, img, disp, prior_poses, n_features=1500, scale_factor=1.3, n_levels=5, fast_threshold=20, edge=31,
                     **chain_kwargs):
         """findFeatures(img), keypoints3D(disp, poses=None) and poseChain over a stack of frames (img [F, H, W] or
         [F, H, W, 3] uint8, disp [F, H, W]; numpy or torch CUDA tensors).  chain_kwargs: poseChain's keywords (the
-        ransac_* ones among them).
-        -> (poses, records, (kp_xy, offsets)); the pair feeds accumulateFrames(keypoints=...) for the accepted frames."""
+        ransac_* ones and refine / refine_kw among them).
+        -> (poses, records, (kp_xy, offsets)) and poseChain's further outputs; the pair feeds accumulateFrames(keypoints=...)
+        for the accepted frames."""
         _kp, xy, desc, off = self.findFeatures(img, n_features=n_features, scale_factor=scale_factor, n_levels=n_levels,
                                                fast_threshold=fast_threshold, edge=edge)
         kp3 = self.keypoints3D(disp, [xy[int(off[f]):int(off[f + 1])] for f in range(len(off) - 1)], poses=None)

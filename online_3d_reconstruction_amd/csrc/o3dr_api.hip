@@ -154,6 +154,14 @@ struct o3dr_ctx {
     std::vector<RigidSeg> rg_seg_h;
     std::vector<RansacSeg> rs_seg_h;  // the RANSAC's segment table (o3dr_ransac_rigid; the chain's pairs)
     std::vector<double> rg_T_h;
+    // o3dr_pose_graph_refine: pair keys (the duplicate check), accepted-pair bytes, per-pair counts, edges, frames, adjacency,
+    // component ids and gauge bytes, the edges' energies
+    std::vector<uint64_t> gr_keys_h;
+    std::vector<uint8_t> gr_ok_h, gr_gauge_h;
+    std::vector<uint32_t> gr_counts_h, gr_adj_h, gr_comp_h;
+    std::vector<GraphEdgeIn> gr_edges_h;
+    std::vector<GraphFrameIn> gr_frames_h;
+    std::vector<double> gr_energy_h;
     int64_t place_ub = -1;   // o3dr_cloud_big_slice_counts_dev ran for a cloud of at most this many points and place_parts slices:
     int place_parts = 0;     // the (slice, tile) table in the workspace is what o3dr_cloud_big_place_slices moves by
     int test_hooks = 0;    // O3DR_TEST_HOOKS=1 at o3dr_ctx_create: the entry points of include/o3dr_testing.h act
@@ -3942,6 +3950,119 @@ extern "C" int o3dr_ransac_rigid(o3dr_ctx* c, const o3dr_point* src, const o3dr_
 }
 
 // -------------------------------------------------------------------------------------------------
+// The static stage the pose chain and the pose-graph refinement share: the pair table of a list of (query frame, train
+// frame) pairs, the staged pool, one batched matching pass and, with RANSAC parameters, the filter of every pair in camera
+// coordinates (keyed by its two frame numbers).  pair_stage_plan before the caller's OP_WORK layout, pair_stage_take inside
+// it, pair_stage_run after the caller's own uploads.
+// -------------------------------------------------------------------------------------------------
+struct PairStage {
+    MatchPlan plan;
+    uint64_t over;               // candidates past kRansacStage, over all pairs
+    const uint8_t* desc_d;       // the pool (staged for a host call)
+    const o3dr_point* kp3_d;
+    MatchPair* tab_d;
+    uint2* part_d;
+    uint4* rec_d;                // plan.rec records and good bytes
+    uint8_t* good_d;
+    RansacSeg* rseg_d;
+    uint32_t* over_d;
+    uint8_t* inlier_d;           // plan.rec bytes (with the filter)
+    o3dr_ransac_result* rres_d;  // one per pair (with the filter)
+};
+
+static int pair_stage_plan(o3dr_ctx* c, const uint8_t* desc, const int64_t* off, const o3dr_point* kp3, int32_t n_frames,
+                           const int32_t* pl, int64_t n_pairs, uint64_t work, bool robust, int32_t mem, PairStage& S)
+{
+    memset(&S, 0, sizeof S);
+    S.plan = match_plan(c, off, pl, n_pairs, work);
+    const std::vector<MatchPair>& tab = c->mt_tab_h;
+    const int64_t pool = off[n_frames] - off[0];
+    S.desc_d = desc ? desc + 32 * off[0] : nullptr;
+    S.kp3_d = kp3 ? kp3 + off[0] : nullptr;
+    if (mem == O3DR_MEM_HOST) {
+        CHK(carve(c, c->op[o3dr_ctx::OP_IN], [&](Carve& w) {
+            w.take(S.desc_d, (size_t)pool * 32 + 1);
+            w.take(S.kp3_d, (size_t)pool + 1);
+        }));
+        if (pool > 0) {
+            HIPCHK(hipMemcpyAsync((void*)S.desc_d, desc + 32 * off[0], (size_t)pool * 32, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync((void*)S.kp3_d, kp3 + off[0], (size_t)pool * sizeof(o3dr_point), hipMemcpyHostToDevice, c->stream));
+        }
+    }
+    // the RANSAC's segments: one per pair, keyed by its two frame numbers
+    std::vector<RansacSeg>& rseg = c->rs_seg_h;
+    rseg.clear();
+    if (robust) {
+        rseg.resize((size_t)n_pairs);
+        for (int64_t k = 0; k < n_pairs; ++k) {
+            RansacSeg& g = rseg[(size_t)k];
+            g.start = tab[(size_t)k].rec0;
+            g.key = ((uint64_t)(uint32_t)pl[2 * (size_t)k] << 32) | (uint64_t)(uint32_t)pl[2 * (size_t)k + 1];
+            g.over0 = S.over;
+            g.n = tab[(size_t)k].nq;
+            g.reserved = 0;
+            if (g.n > (uint32_t)kRansacStage) S.over += g.n - (uint32_t)kRansacStage;
+        }
+    }
+    return O3DR_OK;
+}
+
+static void pair_stage_take(o3dr_ctx* c, Carve& w, PairStage& S, bool robust)
+{
+    w.take(S.tab_d, c->mt_tab_h.size() + 1);
+    w.take(S.part_d, (size_t)S.plan.part + 1);
+    w.take(S.rec_d, (size_t)S.plan.rec + 1);
+    w.take(S.good_d, (size_t)S.plan.rec + 1);
+    w.take(S.rseg_d, c->rs_seg_h.size() + 1);
+    w.take(S.over_d, (size_t)S.over + 1);
+    w.take(S.inlier_d, robust ? (size_t)S.plan.rec + 1 : 1);
+    w.take(S.rres_d, c->rs_seg_h.size() + 1);
+}
+
+static int pair_stage_run(o3dr_ctx* c, const PairStage& S, int64_t n_pairs, float ratio, int32_t max_distance, const o3dr_ransac_params* rp)
+{
+    const std::vector<MatchPair>& tab = c->mt_tab_h;
+    if (n_pairs > 0) HIPCHK(hipMemcpyAsync(S.tab_d, tab.data(), tab.size() * sizeof(MatchPair), hipMemcpyHostToDevice, c->stream));
+    if (S.plan.rec > 0) {
+        MatchArgs m;
+        memset(&m, 0, sizeof m);
+        m.desc = (const uint4*)S.desc_d;
+        m.n_pairs = (uint32_t)n_pairs;
+        m.chunk_rows = (uint32_t)S.plan.chunk;
+        m.n_items = S.plan.items;
+        m.n_rec = S.plan.rec;
+        m.ratio = ratio;
+        m.max_distance = (uint32_t)max_distance;
+        m.rec = S.rec_d;
+        m.good = S.good_d;
+        launch_match(&c->prof, c->stream, m, S.tab_d, S.part_d);
+        HIPCHK(hipGetLastError());
+    }
+    // the pairs' inlier masks, in camera coordinates: static like the matching, one workgroup per pair
+    if (rp && n_pairs > 0) {
+        const std::vector<RansacSeg>& rseg = c->rs_seg_h;
+        RansacArgs g;
+        memset(&g, 0, sizeof g);
+        g.kp3 = S.kp3_d;
+        g.pairs = S.tab_d;
+        g.rec = S.rec_d;
+        g.good = S.good_d;
+        g.seg = S.rseg_d;
+        g.over = S.over_d;
+        g.inlier = S.inlier_d;
+        g.res = S.rres_d;
+        g.seed = rp->seed;
+        g.thr2 = rp->threshold * rp->threshold;
+        g.iterations = (uint32_t)rp->iterations;
+        g.n_segs = (uint32_t)n_pairs;
+        HIPCHK(hipMemcpyAsync(S.rseg_d, rseg.data(), rseg.size() * sizeof(RansacSeg), hipMemcpyHostToDevice, c->stream));
+        launch_ransac(&c->prof, c->stream, g, true);
+        HIPCHK(hipGetLastError());
+    }
+    return O3DR_OK;
+}
+
+// -------------------------------------------------------------------------------------------------
 // pose chain (kernels/pose_chain.inc; contract: include/o3dr.h "pose chain", DESIGN.md "Pose chain")
 // -------------------------------------------------------------------------------------------------
 extern "C" void o3dr_chain_default_params(o3dr_chain_params* p)
@@ -4028,111 +4149,37 @@ static int pose_chain(o3dr_ctx* c, const uint8_t* desc, const int64_t* off, cons
         for (int k = 0; k < 12; ++k) r.T[k] = (double)poses_in[16 * (size_t)f + k];
     }
     // 2. staging and scratch
-    const MatchPlan plan = match_plan(c, off, pl.data(), n_pairs, work);
-    const std::vector<MatchPair>& tab = c->mt_tab_h;
-    const uint8_t* desc_d = desc ? desc + 32 * off[0] : nullptr;
-    const o3dr_point* kp3_d = kp3 ? kp3 + off[0] : nullptr;
-    if (mem == O3DR_MEM_HOST) {
-        CHK(carve(c, c->op[o3dr_ctx::OP_IN], [&](Carve& w) {
-            w.take(desc_d, (size_t)pool * 32 + 1);
-            w.take(kp3_d, (size_t)pool + 1);
-        }));
-        if (pool > 0) {
-            HIPCHK(hipMemcpyAsync((void*)desc_d, desc + 32 * off[0], (size_t)pool * 32, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync((void*)kp3_d, kp3 + off[0], (size_t)pool * sizeof(o3dr_point), hipMemcpyHostToDevice, c->stream));
-        }
-    }
-    MatchPair* tab_d;
-    uint2* part_d;
-    uint4* rec_d;
-    uint8_t* good_d;
+    PairStage S;
+    CHK(pair_stage_plan(c, desc, off, kp3, n_frames, pl.data(), n_pairs, work, rp != nullptr, mem, S));
     int32_t *train_d, *status_d;
     ChainFrameIn* frames_d;
     float* prior_d;
     o3dr_chain_frame* out_d;
-    // the RANSAC's segments: one per pair, keyed by its two frame numbers
-    std::vector<RansacSeg>& rseg = c->rs_seg_h;
-    rseg.clear();
-    uint64_t over = 0;
-    if (rp) {
-        rseg.resize((size_t)n_pairs);
-        for (int64_t k = 0; k < n_pairs; ++k) {
-            RansacSeg& g = rseg[(size_t)k];
-            g.start = tab[(size_t)k].rec0;
-            g.key = ((uint64_t)(uint32_t)pl[2 * (size_t)k] << 32) | (uint64_t)(uint32_t)pl[2 * (size_t)k + 1];
-            g.over0 = over;
-            g.n = tab[(size_t)k].nq;
-            g.reserved = 0;
-            if (g.n > (uint32_t)kRansacStage) over += g.n - (uint32_t)kRansacStage;
-        }
-    }
-    RansacSeg* rseg_d;
-    uint32_t* over_d;
-    uint8_t* inlier_d;
-    o3dr_ransac_result* rres_d;
     CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
-        w.take(tab_d, tab.size() + 1);
-        w.take(part_d, (size_t)plan.part + 1);
-        w.take(rec_d, (size_t)plan.rec + 1);
-        w.take(good_d, (size_t)plan.rec + 1);
+        pair_stage_take(c, w, S, rp != nullptr);
         w.take(train_d, train.size() + 1);
         w.take(status_d, F);
         w.take(frames_d, F);
         w.take(prior_d, F * 16);
         w.take(out_d, F);
-        w.take(rseg_d, rseg.size() + 1);
-        w.take(over_d, (size_t)over + 1);
-        w.take(inlier_d, rp ? (size_t)plan.rec + 1 : 1);
-        w.take(rres_d, rseg.size() + 1);
     }));
     CHK(outs.stage(c));
     float* poses_d = outs.dev(poses_out);
-    if (n_pairs > 0) {
-        HIPCHK(hipMemcpyAsync(tab_d, tab.data(), tab.size() * sizeof(MatchPair), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(train_d, train.data(), train.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    }
+    if (n_pairs > 0) HIPCHK(hipMemcpyAsync(train_d, train.data(), train.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(frames_d, fr.data(), F * sizeof(ChainFrameIn), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(prior_d, prior, F * 16 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if (n_fixed > 0) {
         HIPCHK(hipMemcpyAsync(status_d, st_h.data(), (size_t)n_fixed * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(poses_d, poses_in, (size_t)n_fixed * 16 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     }
-    // 3. one batched matching pass, then the chain: one launch
-    if (plan.rec > 0) {
-        MatchArgs m;
-        memset(&m, 0, sizeof m);
-        m.desc = (const uint4*)desc_d;
-        m.n_pairs = (uint32_t)n_pairs;
-        m.chunk_rows = (uint32_t)plan.chunk;
-        m.n_items = plan.items;
-        m.n_rec = plan.rec;
-        m.ratio = prm.ratio;
-        m.max_distance = (uint32_t)prm.max_distance;
-        m.rec = rec_d;
-        m.good = good_d;
-        launch_match(&c->prof, c->stream, m, tab_d, part_d);
-        HIPCHK(hipGetLastError());
-    }
-    // the pairs' inlier masks, in camera coordinates: static like the matching, one workgroup per pair ahead of the walk
-    if (rp && n_pairs > 0) {
-        RansacArgs g;
-        memset(&g, 0, sizeof g);
-        g.kp3 = kp3_d;
-        g.pairs = tab_d;
-        g.rec = rec_d;
-        g.good = good_d;
-        g.seg = rseg_d;
-        g.over = over_d;
-        g.inlier = inlier_d;
-        g.res = rres_d;
-        g.seed = rp->seed;
-        g.thr2 = rp->threshold * rp->threshold;
-        g.iterations = (uint32_t)rp->iterations;
-        g.n_segs = (uint32_t)n_pairs;
-        HIPCHK(hipMemcpyAsync(rseg_d, rseg.data(), rseg.size() * sizeof(RansacSeg), hipMemcpyHostToDevice, c->stream));
-        launch_ransac(&c->prof, c->stream, g, true);
-        HIPCHK(hipGetLastError());
-    }
+    // 3. one batched matching pass (and the pairs' inlier masks), then the chain: one launch
+    CHK(pair_stage_run(c, S, n_pairs, prm.ratio, prm.max_distance, rp));
+    const o3dr_point* kp3_d = S.kp3_d;
+    MatchPair* tab_d = S.tab_d;
+    uint4* rec_d = S.rec_d;
+    uint8_t* good_d = S.good_d;
+    uint8_t* inlier_d = S.inlier_d;
+    o3dr_ransac_result* rres_d = S.rres_d;
     ChainArgs a;
     memset(&a, 0, sizeof a);
     a.kp3 = kp3_d;
@@ -4193,6 +4240,247 @@ extern "C" int o3dr_pose_chain(o3dr_ctx* c, const uint8_t* desc, const int64_t* 
 {
     return o3dr_pose_chain_robust(c, desc, offsets, kp3, prior_poses, n_frames, n_fixed, poses_in, status_in, p, poses_out, frames_out,
                                   pairs_out, pairs_capacity, n_pairs_out, mem, nullptr, nullptr);
+}
+
+// -------------------------------------------------------------------------------------------------
+// pose-graph refinement (kernels/pose_graph.inc; contract: include/o3dr.h "pose graph", DESIGN.md "Pose-graph refinement")
+// -------------------------------------------------------------------------------------------------
+extern "C" void o3dr_refine_default_params(o3dr_refine_params* p)
+{
+    if (!p) return;
+    p->prior_weight = 0.0;
+    p->gn_iterations = 5;
+    p->cg_iterations = 32;
+    p->min_pair_matches = 3;
+    p->ratio = 0.5f;
+    p->max_distance = 40;
+    p->reserved = 0;
+}
+
+static int pose_graph_refine(o3dr_ctx* c, const uint8_t* desc, const int64_t* off, const o3dr_point* kp3, int32_t n_frames,
+                             const float* poses_in, const int32_t* status_in, const uint8_t* fixed, const float* prior, const int32_t* pairs,
+                             int64_t n_pairs, const o3dr_refine_params* p, const o3dr_ransac_params* rp, float* poses_out,
+                             o3dr_refine_frame* frames_out, o3dr_refine_edge* edges_out, o3dr_refine_result* res, Outputs& outs,
+                             int32_t mem)
+{
+    if (!res) return fail(O3DR_ERR_INVALID_ARG, "res is NULL");
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    if (rp) CHK(ransac_check(*rp));
+    o3dr_refine_params prm;
+    o3dr_refine_default_params(&prm);
+    if (p) prm = *p;
+    if (prm.gn_iterations < 1 || prm.gn_iterations > O3DR_REFINE_MAX_GN) return fail(O3DR_ERR_INVALID_ARG, "gn_iterations must be in [1, 64]");
+    if (prm.cg_iterations < 1 || prm.cg_iterations > O3DR_REFINE_MAX_CG) return fail(O3DR_ERR_INVALID_ARG, "cg_iterations must be in [1, 1024]");
+    if (prm.min_pair_matches < 1) return fail(O3DR_ERR_INVALID_ARG, "min_pair_matches must be >= 1");
+    if (!(std::isfinite(prm.prior_weight) && prm.prior_weight >= 0.0)) return fail(O3DR_ERR_INVALID_ARG, "prior_weight must be finite and >= 0");
+    if (!(std::isfinite(prm.ratio) && prm.ratio > 0.f)) return fail(O3DR_ERR_INVALID_ARG, "ratio must be finite and > 0");
+    if (prm.max_distance < 0 || prm.max_distance > 257) return fail(O3DR_ERR_INVALID_ARG, "max_distance must be in [0, 257]");
+    if (n_frames < 0 || n_pairs < 0) return fail(O3DR_ERR_INVALID_ARG, "n_frames and n_pairs must be >= 0");
+    memset(res, 0, sizeof *res);
+    if (n_frames == 0) {
+        if (n_pairs > 0) return fail(O3DR_ERR_INVALID_ARG, "a pair names a frame outside [0, n_frames)");
+        return O3DR_OK;
+    }
+    if (!off || !poses_in || !status_in || !poses_out || !frames_out) return fail(O3DR_ERR_INVALID_ARG, "offsets / poses_in / status_in / poses_out / frames_out is NULL");
+    if (n_pairs > 0 && !pairs) return fail(O3DR_ERR_INVALID_ARG, "pairs is NULL");
+    if (n_pairs > (int64_t)INT32_MAX) return fail(O3DR_ERR_INVALID_ARG, "more than 2^31-1 pairs");
+    if (prm.prior_weight > 0.0 && !prior) return fail(O3DR_ERR_INVALID_ARG, "prior_poses is NULL with prior_weight > 0");
+    if (off[0] < 0) return fail(O3DR_ERR_INVALID_ARG, "offsets[0] must be >= 0");
+    for (int32_t f = 0; f < n_frames; ++f)
+        if (off[f + 1] < off[f]) return fail(O3DR_ERR_INVALID_ARG, "offsets must not decrease");
+    const int64_t pool = off[n_frames] - off[0];
+    if (pool > (int64_t)INT32_MAX) return fail(O3DR_ERR_INVALID_ARG, "more than 2^31-1 rows");
+    if (pool > 0 && (!desc || !kp3)) return fail(O3DR_ERR_INVALID_ARG, "desc / kp3 is NULL");
+    for (int32_t f = 0; f < n_frames; ++f)
+        if (status_in[f] < O3DR_CHAIN_ANCHOR || status_in[f] > O3DR_CHAIN_RMS) return fail(O3DR_ERR_INVALID_ARG, "status_in holds a value outside O3DR_CHAIN_*");
+    const size_t F = (size_t)n_frames, P = (size_t)n_pairs;
+    uint64_t work = 0;
+    {
+        std::vector<uint64_t>& keys = c->gr_keys_h;
+        keys.resize(P);
+        for (size_t k = 0; k < P; ++k) {
+            const int32_t i = pairs[2 * k], j = pairs[2 * k + 1];
+            if (i < 0 || i >= n_frames || j < 0 || j >= n_frames) return fail(O3DR_ERR_INVALID_ARG, "a pair names a frame outside [0, n_frames)");
+            if (i == j) return fail(O3DR_ERR_INVALID_ARG, "a pair names one frame twice");
+            keys[k] = ((uint64_t)(uint32_t)i << 32) | (uint64_t)(uint32_t)j;
+            work += ((uint64_t)(off[i + 1] - off[i]) + kWave - 1) / kWave * (uint64_t)(off[j + 1] - off[j]);
+        }
+        std::sort(keys.begin(), keys.end());
+        if (std::adjacent_find(keys.begin(), keys.end()) != keys.end()) return fail(O3DR_ERR_INVALID_ARG, "a pair is listed twice");
+    }
+    c->place_ub = -1;
+    auto accepted = [&](int32_t f) { return status_in[f] <= O3DR_CHAIN_MATCHED; };
+    std::vector<uint8_t>& ok_h = c->gr_ok_h;
+    ok_h.resize(P);
+    for (size_t k = 0; k < P; ++k) ok_h[k] = accepted(pairs[2 * k]) && accepted(pairs[2 * k + 1]) ? 1 : 0;
+    // 1. matching (and the filter): the chain's stage.  2. the moments of every pair
+    PairStage S;
+    CHK(pair_stage_plan(c, desc, off, kp3, n_frames, pairs, n_pairs, work, rp != nullptr, mem, S));
+    GraphMomArgs ma;
+    memset(&ma, 0, sizeof ma);
+    GraphArgs a;
+    memset(&a, 0, sizeof a);
+    uint8_t* ok_d;
+    float *pin_d, *prior_d;
+    GraphEdgeIn* edges_d;
+    GraphFrameIn* frames_d;
+    uint32_t* adj_d;
+    CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
+        pair_stage_take(c, w, S, rp != nullptr);
+        w.take(ok_d, P + 1);
+        w.take(ma.mom, P * kGraphFields + 1);
+        w.take(ma.counts, 2 * P + 1);
+        w.take(pin_d, F * 16);
+        w.take(prior_d, F * 16);
+        w.take(edges_d, P + 1);      // (the edges are a subset of the pairs: sized before the counts are known)
+        w.take(frames_d, F);
+        w.take(adj_d, 2 * P + 1);
+        w.take(a.state, F * 12);
+        w.take(a.Hij, P * 36 + 1);
+        w.take(a.ge, P * 12 + 1);
+        w.take(a.Ee, P * 2 + 1);
+        w.take(a.Hd, F * 72);
+        w.take(a.vec, F * 30);
+        w.take(a.frames_out, F);
+        w.take(a.res, 1);
+    }));
+    CHK(outs.stage(c));
+    if (P > 0) HIPCHK(hipMemcpyAsync(ok_d, ok_h.data(), P, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(pin_d, poses_in, F * 16 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (prior) HIPCHK(hipMemcpyAsync(prior_d, prior, F * 16 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    CHK(pair_stage_run(c, S, n_pairs, prm.ratio, prm.max_distance, rp));
+    ma.kp3 = S.kp3_d;
+    ma.pairs = S.tab_d;
+    ma.rec = S.rec_d;
+    ma.good = S.good_d;
+    ma.inlier = rp ? S.inlier_d : nullptr;
+    ma.pair_ok = ok_d;
+    ma.n_pairs = (uint32_t)n_pairs;
+    launch_graph_moments(&c->prof, c->stream, ma);
+    HIPCHK(hipGetLastError());
+    std::vector<uint32_t>& cnt = c->gr_counts_h;
+    cnt.assign(2 * P + 1, 0u);
+    if (P > 0) HIPCHK(hipMemcpyAsync(cnt.data(), ma.counts, 2 * P * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));  // (the first of the call's two)
+    // 3. edges, roles and the adjacency
+    std::vector<GraphEdgeIn>& ed = c->gr_edges_h;
+    std::vector<GraphFrameIn>& fr = c->gr_frames_h;
+    std::vector<uint32_t>& adj = c->gr_adj_h;
+    ed.clear();
+    fr.assign(F, GraphFrameIn{0, 0, 0, 0});
+    int64_t n_used = 0;
+    for (size_t k = 0; k < P; ++k) {
+        if (!ok_h[k] || cnt[2 * k + 1] < (uint32_t)prm.min_pair_matches) continue;
+        ed.push_back(GraphEdgeIn{(uint32_t)pairs[2 * k], (uint32_t)pairs[2 * k + 1], (uint32_t)k, 0});
+        ++fr[(size_t)pairs[2 * k]].n_adj;
+        ++fr[(size_t)pairs[2 * k + 1]].n_adj;
+        n_used += cnt[2 * k + 1];
+    }
+    const size_t E = ed.size();
+    uint32_t at = 0;
+    for (size_t f = 0; f < F; ++f) {
+        fr[f].adj0 = at;
+        at += fr[f].n_adj;
+        fr[f].n_adj = 0;
+    }
+    adj.assign(2 * E + 1, 0u);
+    for (size_t e = 0; e < E; ++e) {
+        GraphFrameIn& fi = fr[ed[e].i];
+        adj[fi.adj0 + fi.n_adj++] = (uint32_t)(e << 1);
+        GraphFrameIn& fj = fr[ed[e].j];
+        adj[fj.adj0 + fj.n_adj++] = (uint32_t)(e << 1) | 1u;
+    }
+    for (size_t f = 0; f < F; ++f) {
+        if (!accepted((int32_t)f))
+            fr[f].role = O3DR_REFINE_REJECTED;
+        else if (status_in[f] == O3DR_CHAIN_MATCHED && !(fixed && fixed[f]) && fr[f].n_adj > 0)
+            fr[f].role = O3DR_REFINE_FREE;
+        else
+            fr[f].role = O3DR_REFINE_FIXED;
+    }
+    if (prm.prior_weight == 0.0) {  // components without a gauge frame float
+        std::vector<uint32_t>& comp = c->gr_comp_h;
+        comp.resize(F);
+        for (size_t f = 0; f < F; ++f) comp[f] = (uint32_t)f;
+        auto find = [&](uint32_t x) {
+            while (comp[x] != x) x = comp[x] = comp[comp[x]];
+            return x;
+        };
+        for (size_t e = 0; e < E; ++e) comp[find(ed[e].i)] = find(ed[e].j);
+        std::vector<uint8_t>& gauge = c->gr_gauge_h;
+        gauge.assign(F, 0);
+        for (size_t f = 0; f < F; ++f)
+            if (fr[f].role == O3DR_REFINE_FIXED && fr[f].n_adj > 0) gauge[find((uint32_t)f)] = 1;
+        for (size_t f = 0; f < F; ++f)
+            if (fr[f].role == O3DR_REFINE_FREE && !gauge[find((uint32_t)f)]) fr[f].role = O3DR_REFINE_FLOATING;
+    }
+    o3dr_refine_result cn;
+    memset(&cn, 0, sizeof cn);
+    for (size_t f = 0; f < F; ++f) {
+        cn.n_free += fr[f].role == O3DR_REFINE_FREE;
+        cn.n_gauge += fr[f].role == O3DR_REFINE_FIXED && fr[f].n_adj > 0;
+        cn.n_floating += fr[f].role == O3DR_REFINE_FLOATING;
+        cn.n_rejected += fr[f].role == O3DR_REFINE_REJECTED;
+    }
+    cn.n_edges = (int32_t)E;
+    cn.n_used = n_used;
+    // 4. the solve: one launch
+    if (E > 0) HIPCHK(hipMemcpyAsync(edges_d, ed.data(), E * sizeof(GraphEdgeIn), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(frames_d, fr.data(), F * sizeof(GraphFrameIn), hipMemcpyHostToDevice, c->stream));
+    if (E > 0) HIPCHK(hipMemcpyAsync(adj_d, adj.data(), 2 * E * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    a.mom = ma.mom;
+    a.edges = edges_d;
+    a.frames = frames_d;
+    a.adj = adj_d;
+    a.poses_in = pin_d;
+    a.prior = prior && prm.prior_weight > 0.0 ? prior_d : nullptr;
+    a.poses_out = outs.dev(poses_out);
+    a.counts = cn;
+    a.prior_weight = prm.prior_weight;
+    a.n_frames = (uint32_t)n_frames;
+    a.n_edges = (uint32_t)E;
+    a.gn_iterations = cn.n_free > 0 && E > 0 ? (uint32_t)prm.gn_iterations : 0u;  // (nothing to move: one evaluation)
+    a.cg_iterations = (uint32_t)prm.cg_iterations;
+    launch_graph_solve(&c->prof, c->stream, a);
+    HIPCHK(hipGetLastError());
+    std::vector<double>& ee = c->gr_energy_h;
+    ee.assign(2 * E + 1, 0.0);
+    HIPCHK(hipMemcpyAsync(frames_out, a.frames_out, F * sizeof(o3dr_refine_frame), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(res, a.res, sizeof(o3dr_refine_result), hipMemcpyDeviceToHost, c->stream));
+    if (edges_out && E > 0) HIPCHK(hipMemcpyAsync(ee.data(), a.Ee, 2 * E * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    CHK(outs.copy_back(c));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (edges_out) {
+        for (size_t k = 0; k < P; ++k) edges_out[k] = o3dr_refine_edge{(int32_t)cnt[2 * k], (int32_t)cnt[2 * k + 1], 0, 0, 0.0, 0.0};
+        for (size_t e = 0; e < E; ++e) {
+            o3dr_refine_edge& r = edges_out[ed[e].pair];
+            r.edge = 1;
+            r.energy_before = ee[2 * e];
+            r.energy_after = ee[2 * e + 1];
+        }
+    }
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_pose_graph_refine(o3dr_ctx* c, const uint8_t* desc, const int64_t* offsets, const o3dr_point* kp3, int32_t n_frames,
+                                      const float* poses_in, const int32_t* status_in, const uint8_t* fixed, const float* prior_poses,
+                                      const int32_t* pairs, int64_t n_pairs, const o3dr_refine_params* p, const o3dr_ransac_params* rp,
+                                      float* poses_out, o3dr_refine_frame* frames_out, o3dr_refine_edge* edges_out,
+                                      o3dr_refine_result* res, int32_t mem)
+{
+    Outputs outs{mem};
+    outs.add(poses_out, n_frames > 0 ? 16 * (int64_t)n_frames : 0);
+    const int rc = entered(c, [&] {
+        return pose_graph_refine(c, desc, offsets, kp3, n_frames, poses_in, status_in, fixed, prior_poses, pairs, n_pairs, p, rp, poses_out,
+                                 frames_out, edges_out, res, outs, mem);
+    });
+    if (rc != O3DR_OK) {  // host outputs zeroed on error
+        outs.zero();
+        if (frames_out && n_frames > 0) memset(frames_out, 0, (size_t)n_frames * sizeof(o3dr_refine_frame));
+        if (edges_out && n_pairs > 0) memset(edges_out, 0, (size_t)n_pairs * sizeof(o3dr_refine_edge));
+        if (res) memset(res, 0, sizeof *res);
+    }
+    return rc;
 }
 
 // -------------------------------------------------------------------------------------------------

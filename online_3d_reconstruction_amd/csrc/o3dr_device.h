@@ -409,6 +409,53 @@ struct RansacArgs {
     uint32_t iterations, n_segs;
 };
 void launch_ransac(Profiler* pf, hipStream_t s, const RansacArgs& a, bool chain);
+// pose-graph refinement (kernels/pose_graph.inc)
+constexpr int kGraphRun = 256;      // rows per run of the moment sums (kChainRun): one workgroup step
+constexpr int kGraphFields = 29;    // the contract's 28 moments, then the pair's good rows
+constexpr int kGraphThreads = 256;  // the solve's one workgroup
+struct GraphMomArgs {
+    const o3dr_point* kp3;       // the pool, launch_match's table, records and mask, the RANSAC's bytes or nullptr (ChainArgs)
+    const MatchPair* pairs;
+    const uint4* rec;
+    const uint8_t* good;
+    const uint8_t* inlier;
+    const uint8_t* pair_ok;      // n_pairs: both frames accepted
+    double* mom;                 // n_pairs * kGraphFields
+    uint32_t* counts;            // n_pairs * 2: n_good, n_used
+    uint32_t n_pairs;
+};
+void launch_graph_moments(Profiler* pf, hipStream_t s, const GraphMomArgs& a);
+struct GraphFrameIn {
+    uint32_t adj0, n_adj;        // its (edge, side) entries in `adj`
+    uint32_t role;               // O3DR_REFINE_*
+    uint32_t reserved;
+};
+struct GraphEdgeIn {
+    uint32_t i, j;               // the frames
+    uint32_t pair;               // its place in the pair list (moments)
+    uint32_t reserved;
+};
+struct GraphArgs {
+    const double* mom;           // launch_graph_moments' records
+    const GraphEdgeIn* edges;    // n_edges, in pair order
+    const GraphFrameIn* frames;  // n_frames
+    const uint32_t* adj;         // 2 n_edges: edge << 1 | side, per frame in pair order
+    const float* poses_in;       // n_frames * 16
+    const float* prior;          // n_frames * 16, or nullptr
+    float* poses_out;            // n_frames * 16
+    double* state;               // n_frames * 12: R (row-major), t
+    double* Hij;                 // n_edges * 36
+    double* ge;                  // n_edges * 12: g_i, g_j
+    double* Ee;                  // n_edges * 2: the edge's energy at the input, at the output poses
+    double* Hd;                  // n_frames * 36 diagonal blocks, then n_frames * 36 inverses
+    double* vec;                 // 5 vectors of 6 n_frames: r, x, z, p, H p
+    o3dr_refine_frame* frames_out;
+    o3dr_refine_result* res;     // one record; the counts come from the host
+    o3dr_refine_result counts;
+    double prior_weight;
+    uint32_t n_frames, n_edges, gn_iterations, cg_iterations;
+};
+void launch_graph_solve(Profiler* pf, hipStream_t s, const GraphArgs& a);
 // The dense XY cell order of a cloud (kernels/cell_order.inc): the points sorted by the dense id
 // (iy - y0) * wx + (ix - x0) of their cell, input order kept inside a cell.  The operator's Args (PlaneArgs, MeshArgs:
 // cloud, n, the parameter of its index rule, `cells`) select the index rule.

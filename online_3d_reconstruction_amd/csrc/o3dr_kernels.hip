@@ -65,6 +65,7 @@ namespace o3dr {
 #include "kernels/orb.inc"
 #include "kernels/pose_chain.inc"
 #include "kernels/ransac.inc"
+#include "kernels/pose_graph.inc"
 
 // =================================================================================================
 // launchers
@@ -1036,6 +1037,19 @@ void launch_ransac(Profiler* pf, hipStream_t s, const RansacArgs& a, bool chain)
         k_ransac_rigid<true><<<a.n_segs, kRansacThreads, 0, s>>>(a);
     else
         k_ransac_rigid<false><<<a.n_segs, kRansacThreads, 0, s>>>(a);
+}
+
+// pose-graph refinement (kernels/pose_graph.inc): the moments, one workgroup per pair; the solve, one workgroup
+void launch_graph_moments(Profiler* pf, hipStream_t s, const GraphMomArgs& a)
+{
+    ProfScope ps(pf, O3DR_K_GRAPH_MOMENTS, s);
+    if (a.n_pairs > 0) k_graph_moments<<<a.n_pairs, kGraphRun, 0, s>>>(a);
+}
+
+void launch_graph_solve(Profiler* pf, hipStream_t s, const GraphArgs& a)
+{
+    ProfScope ps(pf, O3DR_K_GRAPH_SOLVE, s);
+    if (a.n_frames > 0) k_graph_solve<<<1, kGraphThreads, 0, s>>>(a);
 }
 
 // height-field surface mesh (kernels/mesh.inc)

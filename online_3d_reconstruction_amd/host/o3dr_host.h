@@ -150,6 +150,11 @@ public:
     double chain_ransac_threshold = 0.05;  // (metres), --chain_ransac_iterations, --chain_ransac_seed
     int chain_ransac_iterations = 256;
     uint64_t chain_ransac_seed = 0;
+    bool refine_poses = false;        // --refine_poses (with --feature_poses): after each cycle's chain, o3dr_pose_graph_refine over the
+                                      // cycle's matched frames and pairs, the history held; a free frame's pose becomes the refined one
+    int refine_gn_iterations = 5;     // --refine_gn_iterations, --refine_cg_iterations, --refine_prior_weight
+    int refine_cg_iterations = 32;
+    double refine_prior_weight = 0.0;
     std::string print_label_png;      // --print_label_png f: rows, cols and the labels of f as text (checks the reader)
 
     std::vector<RawImageData> rawImageDataVec;

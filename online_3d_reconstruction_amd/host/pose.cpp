@@ -427,6 +427,7 @@ void Pose::printUsage()
             "                     from the same extractor on its rgb images, with the --orb_* flags; single-GPU batched path only)\n"
             "       [--feature_poses] [--dist_nearby m] [--range_width n] [--chain_min_matches n] [--chain_max_rms m]\n"
             "       [--chain_ransac_threshold m] [--chain_ransac_iterations n] [--chain_ransac_seed s]\n"
+            "       [--refine_poses] [--refine_gn_iterations n] [--refine_cg_iterations n] [--refine_prior_weight w]\n"
             "                     (reconstruction run: every frame's pose from ORB matches against the earlier frames whose recorded\n"
             "                     position lies within --dist_nearby metres (default 2), at most --range_width of them (default 8,\n"
             "                     the most recent); a frame with fewer than --chain_min_matches correspondences (default 30), a\n"
@@ -437,6 +438,10 @@ void Pose::printUsage()
             "                     gains \"dropped n\", the correspondences the filter took out;\n"
             "                     --dist_nearby, --range_width and the --chain_* flags act under this flag only; shares the extractor call with\n"
             "                     --gpu_keypoints; single-GPU batched path only; the flag is this build's own)\n"
+            "                     with --refine_poses every cycle's chain is followed by one joint least-squares refinement of\n"
+            "                     the cycle's matched frames over all of its pairs (earlier cycles held; --refine_gn_iterations,\n"
+            "                     default 5, Gauss-Newton steps of --refine_cg_iterations, default 32, CG steps; --refine_prior_weight,\n"
+            "                     default 0, pulls every free frame's position to its recorded one); one line per cycle reports it\n"
             "Without --feature_poses the run uses the recorded MAVLink poses (--only_MAVLink).  The ICP trajectory correction,\n"
             "visualisation and --segment_cloud in a reconstruction run are not part of this build.\n";
 }
@@ -526,6 +531,10 @@ int Pose::parseCmdArgs(int argc, char** argv)
         else if (a == "--chain_ransac_threshold") { chain_ransac_threshold = atof(need(i)); chain_ransac = true; }
         else if (a == "--chain_ransac_iterations") chain_ransac_iterations = atoi(need(i));
         else if (a == "--chain_ransac_seed") chain_ransac_seed = strtoull(need(i), nullptr, 0);
+        else if (a == "--refine_poses") refine_poses = true;
+        else if (a == "--refine_gn_iterations") refine_gn_iterations = atoi(need(i));
+        else if (a == "--refine_cg_iterations") refine_cg_iterations = atoi(need(i));
+        else if (a == "--refine_prior_weight") refine_prior_weight = atof(need(i));
         else if (a == "--preview") preview = true;
         else if (a == "--use_segment_labels") use_segment_labels = true;
         else if (a == "--segment_labels_dir") segmentLabelsPrefix = need(i);
@@ -562,6 +571,7 @@ int Pose::parseCmdArgs(int argc, char** argv)
         if (n_gpus > 1 || partitioned_merge) throw runtime_error("--gpu_keypoints is not available with --gpus N > 1 / --partitioned_merge");
         if (reference_fanout) throw runtime_error("--gpu_keypoints is not available with --reference_fanout");
     }
+    if (refine_poses && !feature_poses) throw runtime_error("--refine_poses refines the poses of --feature_poses: give both");
     if (run3d_reconstruction && feature_poses) {
         if (n_gpus > 1 || partitioned_merge) throw runtime_error("--feature_poses is not available with --gpus N > 1 / --partitioned_merge");
         if (reference_fanout) throw runtime_error("--feature_poses is not available with --reference_fanout");
@@ -1036,14 +1046,15 @@ void Pose::run_reconstruction()
                 rp.threshold = chain_ransac_threshold;
                 rp.iterations = chain_ransac_iterations;
                 rp.seed = chain_ransac_seed;
-                const size_t pair_cap = chain_ransac ? n_acc * (size_t)O3DR_CHAIN_MAX_RANGE : 0;
+                const bool want_pairs = chain_ransac || refine_poses;
+                const size_t pair_cap = want_pairs ? n_acc * (size_t)O3DR_CHAIN_MAX_RANGE : 0;
                 vector<int32_t> pair_list(2 * pair_cap + 2);
                 vector<o3dr_ransac_result> rres(pair_cap + 1);
                 int64_t n_list = 0;
                 if (rc_chain == O3DR_OK) {
                     rc_chain = o3dr_pose_chain_robust(c, chain.desc.data(), chain.off.data(), chain.kp3.data(), chain.prior.data(),
                                                       (int32_t)n_all, (int32_t)n_hist, chain.poses.data(), chain.status.data(), &cp,
-                                                      chain_out.data(), recs.data(), chain_ransac ? pair_list.data() : nullptr,
+                                                      chain_out.data(), recs.data(), want_pairs ? pair_list.data() : nullptr,
                                                       (int64_t)pair_cap, &n_list, O3DR_MEM_HOST, chain_ransac ? &rp : nullptr,
                                                       chain_ransac ? rres.data() : nullptr);
                     if (rc_chain != O3DR_OK) why_chain = string("pose_chain: ") + o3dr_last_error();
@@ -1056,6 +1067,26 @@ void Pose::run_reconstruction()
                         if (st_j == O3DR_CHAIN_ANCHOR || st_j == O3DR_CHAIN_MATCHED)
                             dropped[(size_t)pair_list[2 * (size_t)k]] += rres[(size_t)k].n_candidates - rres[(size_t)k].n_inliers;
                     }
+                // --refine_poses: one joint refinement of the cycle's matched frames over the cycle's pairs, the history held
+                o3dr_refine_result rr;
+                memset(&rr, 0, sizeof rr);
+                if (rc_chain == O3DR_OK && refine_poses) {
+                    vector<int32_t> st_all(n_all);
+                    vector<uint8_t> held(n_all, 0);
+                    for (size_t f = 0; f < n_all; ++f) st_all[f] = recs[f].status, held[f] = f < n_hist;
+                    vector<float> refined(16 * n_all);
+                    vector<o3dr_refine_frame> rfr(n_all);
+                    o3dr_refine_params fp;
+                    o3dr_refine_default_params(&fp);
+                    fp.gn_iterations = refine_gn_iterations;
+                    fp.cg_iterations = refine_cg_iterations;
+                    fp.prior_weight = refine_prior_weight;
+                    rc_chain = o3dr_pose_graph_refine(c, chain.desc.data(), chain.off.data(), chain.kp3.data(), (int32_t)n_all, chain_out.data(),
+                                                      st_all.data(), held.data(), chain.prior.data(), pair_list.data(), n_list, &fp,
+                                                      chain_ransac ? &rp : nullptr, refined.data(), rfr.data(), nullptr, &rr, O3DR_MEM_HOST);
+                    if (rc_chain != O3DR_OK) why_chain = string("pose_graph_refine: ") + o3dr_last_error();
+                    else chain_out = refined;  // (a frame that is not free keeps its bytes)
+                }
                 if (rc_chain == O3DR_OK) {
                     static const char* const names[] = {"ANCHOR", "MATCHED", "TOO_FEW", "DEGENERATE", "RMS"};
                     chain.poses = chain_out;
@@ -1064,6 +1095,9 @@ void Pose::run_reconstruction()
                     size_t kp_rows = 0;
                     cout << "\npose chain: " << n_acc << " frames after " << n_hist << ", " << chrono::duration<double>(clk::now() - tc).count()
                          << " sec" << endl;
+                    if (refine_poses)
+                        cout << "pose graph: edges " << rr.n_edges << " free " << rr.n_free << " energy " << rr.energy_before << " -> "
+                             << rr.energy_after << " gradient " << rr.grad_after << endl;
                     for (size_t k = 0; k < n_acc; ++k) {
                         const o3dr_chain_frame& r = recs[n_hist + k];
                         ImageData& im = acceptedImageDataVec[first_accepted + k];
