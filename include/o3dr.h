@@ -803,6 +803,69 @@ int  o3dr_orb_detect(o3dr_ctx* ctx, const uint8_t* img, int64_t frame_stride, in
                      int32_t n_frames, const o3dr_orb_params* p, o3dr_orb_keypoint* kp, float* kp_xy, uint8_t* desc,
                      int64_t* offsets, uint8_t* levels_out, int64_t out_capacity, int64_t* n_out, int32_t mem);
 
+/* ---- stereo disparity: the 8-bit disparity image every frame call starts from, made here from a rectified pair by
+ * census-transform semi-global matching.  The reference reads its disparities as files an offline matcher wrote (SURVEY
+ * section 2), so there is nothing of its to pin: the contract below is this library's own; every step is an exact
+ * integer computation, so results are bit-identical across calls, frame batchings and memory kinds;
+ * tests/stereo_reference.py restates it in numpy.  Not included: median and speckle filtering, an adaptive P2, and
+ * rectification itself - the pair must arrive rectified.
+ *
+ * Input: `left` and `right`, n_frames images each of rows x cols pixels (1..8192 each), byte `pitch` and byte
+ * `frame_stride` (the same for both), channels = 3 (interleaved B, G, R) or 1 (grey), both in `mem`.  W = cols, H = rows,
+ * D = n_disparities, d0 = min_disparity; a candidate d in [0, D) stands for the disparity d0 + d.
+ *   1. Grey: g = (1868 B + 9617 G + 4899 R + 8192) >> 14 (the ORB contract's step 1; channels = 1: the byte itself).
+ *   2. Census, 9 x 7: for pixel (x, y) walk dy = -3..3 (outer) and dx = -4..4 (inner), skipping (0, 0); neighbour number
+ *      k = 0..61 in that order; bit k = 1 iff g(clamp(x + dx, 0, W - 1), clamp(y + dy, 0, H - 1)) < g(x, y).  The result is
+ *      a uint64, bits 62 and 63 are 0.
+ *   3. Matching cost: xr = x - d0 - d; C(x, y, d) = popcount(cenL(x, y) ^ cenR(xr, y)) if xr >= 0, else 63.
+ *   4. Paths: the directions (dx, dy) of travel are, in this order, (1,0) (-1,0) (0,1) (0,-1), and for n_paths = 8 also
+ *      (1,1) (-1,-1) (1,-1) (-1,1).  q = p - r is the predecessor of p along r.  q outside the image: L_r(p, d) = C(p, d).
+ *      Otherwise m = min_k L_r(q, k) and L_r(p, d) = C(p, d) + min(L_r(q, d), L_r(q, d-1) + P1, L_r(q, d+1) + P1, m + P2) - m,
+ *      the d-1 term only when d > 0, the d+1 term only when d < D - 1.  All integers; L_r <= 63 + P2 <= 318.
+ *   5. Sum: S(p, d) = sum over r of L_r(p, d) (<= 2544 with 8 paths: a uint16).
+ *   6. Winner: best(p) = the lowest d that minimises S(p, d).  The pixel is rejected if
+ *      (a) x - d0 - best < 0; or
+ *      (b) uniqueness > 0 and some k with |k - best| > 1 has S(p, k) (100 - uniqueness) < 100 S(p, best); or
+ *      (c) lr_max_diff >= 0 and |bestR(xr, y) - best| > lr_max_diff, where xr = x - d0 - best and bestR(xr, y) = the lowest
+ *          d that minimises S((xr + d0 + d, y), d) over the d with xr + d0 + d < W.  lr_max_diff = -1: no such check.
+ *   7. Outputs, all in `mem`, each optional (NULL: skipped), [n_frames][H][W] with rows tight:
+ *      disp (uint8): d0 + best for an accepted pixel, 0 for a rejected one (a winner with d0 + best = 0 also reads 0): the
+ *        image every frame call, o3dr_disparity_variance and o3dr_keypoints_3d take.
+ *      disp_q4 (uint16): 16 (d0 + best) + off for an accepted pixel, 0 for a rejected one.  With a = S(best - 1),
+ *        b = S(best), c = S(best + 1), den = a - 2 b + c: off = floor((16 (a - c) + den) / (2 den)) (floor division), in
+ *        [-8, 8]; best = 0, best = D - 1 or den <= 0: off = 0.
+ *      cost (uint16): S(p, best) of every pixel, the rejected ones included.
+ *      volume_out (uint16, [n_frames][H][W][D]): S itself (what levels_out is to the ORB call: it tells which stage differs).
+ * Limits, else O3DR_ERR_INVALID_ARG before any device work (host outputs zeroed wherever rows, cols, n_frames - and for
+ * volume_out n_disparities - are themselves within their limits, so that the outputs' sizes are known): n_disparities a
+ * multiple of 32 in 32..256; min_disparity >= 0 with min_disparity + n_disparities <= 256; 0 <= p1 <= p2 <= 255; n_paths
+ * 4 or 8; uniqueness in 0..99; lr_max_diff in -1..255; channels 1 or 3; group_frames >= 0; rows and cols in 1..8192;
+ * pitch >= cols * channels; frame_stride >= rows * pitch when n_frames > 1; disp_q4, cost and volume_out 2-byte aligned;
+ * n_frames >= 0 (0: O3DR_OK, nothing is touched).  pitch and frame_stride have no upper limit: with O3DR_MEM_HOST the images are
+ * staged as frame_stride * (n_frames - 1) + pitch * (rows - 1) + cols * channels bytes each, and a stride too large for that
+ * returns O3DR_ERR_ALLOC (host outputs zeroed), not O3DR_ERR_INVALID_ARG.  p == NULL: the defaults.  group_frames: the frames of a call go
+ * through the kernels in groups whose scratch (two census images, S, the winners: rows * cols * (2 D + 21) bytes a frame)
+ * fits 1 GiB - one frame always forms a group -; group_frames = n > 0 caps a group at n frames.  A layout choice inside
+ * the scratch block: results do not depend on it.  The call carves its own scratch block, does not use the sort
+ * workspace, leaves cloud_big alone and synchronises the stream once, at its end (with O3DR_MEM_HOST the copy of
+ * volume_out into pageable caller memory may block inside the runtime before that). */
+#define O3DR_STEREO_MAX_SIDE 8192
+typedef struct o3dr_stereo_params {
+    int32_t n_disparities; /* default 256; a multiple of 32 in 32..256 */
+    int32_t min_disparity; /* default 0; >= 0, min_disparity + n_disparities <= 256 */
+    int32_t p1;            /* default 10; 0..255 */
+    int32_t p2;            /* default 120; p1..255 */
+    int32_t n_paths;       /* default 8; 4 or 8 */
+    int32_t uniqueness;    /* default 10; 0..99 (percent), 0: no check */
+    int32_t lr_max_diff;   /* default 1; -1..255, -1: no left-right check */
+    int32_t channels;      /* default 3: B G R interleaved; 1: grey */
+    int32_t group_frames;  /* default 0: as many frames per launch group as the scratch budget allows; n > 0: at most n */
+} o3dr_stereo_params;
+void o3dr_stereo_default_params(o3dr_stereo_params* p);
+int  o3dr_stereo_disparity(o3dr_ctx* ctx, const uint8_t* left, const uint8_t* right, int64_t frame_stride, int64_t pitch,
+                           int32_t rows, int32_t cols, int32_t n_frames, const o3dr_stereo_params* p, uint8_t* disp,
+                           uint16_t* disp_q4, uint16_t* cost, uint16_t* volume_out, int32_t mem);
+
 /* ---- pose chain: the reference's default mode (pose.cpp:213-235, generate_tf_of_Matched_Keypoints): every frame gets its
  * pose from descriptor matches against earlier nearby frames, whose keypoints are moved by THEIR fitted poses - a serial
  * chain.  The reference's selection rules and PCL's rounding cannot be pinned here, so the contract below is this library's
@@ -1063,7 +1126,10 @@ int  o3dr_pose_graph_refine(o3dr_ctx* ctx, const uint8_t* desc, const int64_t* o
 #define O3DR_K_RANSAC         19  /* three-point RANSAC for a rigid transform, one workgroup per segment (o3dr_ransac_rigid, o3dr_pose_chain_robust) */
 #define O3DR_K_GRAPH_MOMENTS 20  /* pose graph: the 28 fp64 moments of every pair, one workgroup per pair */
 #define O3DR_K_GRAPH_SOLVE   21  /* ... Gauss-Newton + preconditioned CG, the one-workgroup solve */
-#define O3DR_K_NUM          22
+#define O3DR_K_STEREO_CENSUS 22  /* stereo disparity: grey + census of both images */
+#define O3DR_K_STEREO_PATHS  23  /* ... the aggregation, one launch per direction, one wave per scan line */
+#define O3DR_K_STEREO_WINNER 24  /* ... winners of left and right pixels, rejections, outputs */
+#define O3DR_K_NUM          25
 /* Bracket every launch of kernel `kernel_id` (or all kernels if -1) with HIP events on the
  * context's stream; 0 launches are bracketed when disabled (the default). */
 int o3dr_profile_enable(o3dr_ctx* ctx, int32_t kernel_id, int32_t enable);

@@ -20,10 +20,11 @@ K_PLANE_DISP_SUMS, K_PLANE_DISP_FIT, K_PLANE_DISP_EVAL = 9, 10, 11
 K_ORB_PYRAMID, K_ORB_FAST, K_ORB_CANDIDATES, K_ORB_SELECT, K_ORB_DESCRIBE = 12, 13, 14, 15, 16
 K_MATCH, K_POSE_CHAIN, K_RANSAC = 17, 18, 19
 K_GRAPH_MOMENTS, K_GRAPH_SOLVE = 20, 21
+K_STEREO_CENSUS, K_STEREO_PATHS, K_STEREO_WINNER = 22, 23, 24
 KERNEL_NAMES = ["reproject_count", "reproject_emit", "voxel_keys", "radix_hist", "radix_scatter", "run_segments",
                 "centroid", "other", "centroid_runs", "plane_disp_sums", "plane_disp_fit", "plane_disp_eval",
                 "orb_pyramid", "orb_fast", "orb_candidates", "orb_select", "orb_describe", "match", "pose_chain", "ransac",
-                "graph_moments", "graph_solve"]
+                "graph_moments", "graph_solve", "stereo_census", "stereo_paths", "stereo_winner"]
 
 
 class O3drError(RuntimeError):
@@ -108,6 +109,15 @@ ORB_KEYPOINT = np.dtype([("x", "<f4"), ("y", "<f4"), ("angle_deg", "<f4"), ("siz
                          ("yl", "<i2"), ("level", "u1"), ("angle_bin", "u1"), ("reserved", "<u2")])
 assert ORB_KEYPOINT.itemsize == 32
 ORB_MAX_SIDE, ORB_MAX_LEVELS = 8192, 8
+
+
+class StereoParamsStruct(C.Structure):
+    _fields_ = [("n_disparities", C.c_int32), ("min_disparity", C.c_int32), ("p1", C.c_int32), ("p2", C.c_int32),
+                ("n_paths", C.c_int32), ("uniqueness", C.c_int32), ("lr_max_diff", C.c_int32), ("channels", C.c_int32),
+                ("group_frames", C.c_int32)]
+
+
+STEREO_MAX_SIDE = 8192
 
 
 class MatchParamsStruct(C.Structure):
@@ -256,6 +266,9 @@ SYMBOLS = [
     ("o3dr_orb_level_sizes", C.c_int, [_i32, _i32, C.POINTER(OrbParamsStruct), _vp, _vp]),
     ("o3dr_orb_detect", C.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, C.POINTER(OrbParamsStruct), _vp, _vp, _vp, _vp, _vp, _i64,
                                   _pi64, _i32]),
+    ("o3dr_stereo_default_params", None, [C.POINTER(StereoParamsStruct)]),
+    ("o3dr_stereo_disparity", C.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, C.POINTER(StereoParamsStruct), _vp, _vp, _vp, _vp,
+                                        _i32]),
     ("o3dr_chain_default_params", None, [C.POINTER(ChainParamsStruct)]),
     ("o3dr_pose_chain", C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, C.POINTER(ChainParamsStruct), _vp, _vp, _vp, _i64,
                                   _pi64, _i32]),

@@ -597,6 +597,79 @@ class Context:
         res = (kp[:k], xy[:k], desc[:k], off)
         return res + (lev[:n_lev],) if return_levels else res
 
+    # -- stereo disparity (the image every frame call starts from; the reference reads it from files) ----------------------
+    def stereoDisparity(self, left, right, n_disparities=256, min_disparity=0, p1=10, p2=120, n_paths=8, uniqueness=10,
+                        lr_max_diff=1, subpixel=False, return_cost=False, return_volume=False, group_frames=0):
+        """Census-transform semi-global matching of a rectified pair (contract: include/o3dr.h "stereo disparity").  left /
+        right: uint8 [H, W] or [F, H, W] grey, [H, W, 3] or [F, H, W, 3] B G R, same shape; numpy, or torch CUDA tensors (the
+        outputs are then CUDA tensors and nothing leaves HBM).  A 3-D input whose last axis is 3 is taken as one B G R image
+        (as findFeatures does): pass a grey stack of 3-pixel-wide frames one frame at a time.  -> the uint8 disparity image ([H, W] or [F, H, W]; 0: rejected):
+        what accumulateFrames, disparityVariance and keypoints3D take.  subpixel=True: a float64 image instead, disp_q4 / 16.0
+        (exact; rejected pixels 0.0): what the frame calls read under Params(disparity_f64=True).  return_cost: S at the winner
+        (uint16) follows; return_volume: S itself (uint16 [..., H, W, D]) follows that.  group_frames: at most that many frames
+        per launch group (0: as many as the scratch budget allows); results do not depend on it."""
+        dev = _is_torch(left)
+        assert dev == _is_torch(right) and tuple(left.shape) == tuple(right.shape)
+        nd = left.dim() if dev else np.ndim(left)
+        ch = 3 if (nd == 4 or (nd == 3 and int(left.shape[-1]) == 3)) else 1
+        single = nd == (3 if ch == 3 else 2)
+        assert nd in ((3, 4) if ch == 3 else (2, 3))
+        F = 1 if single else int(left.shape[0])
+        rows, cols = (int(left.shape[-3]), int(left.shape[-2])) if ch == 3 else (int(left.shape[-2]), int(left.shape[-1]))
+        row_axis = -3 if ch == 3 else -2
+        if dev:
+            import torch
+            assert left.is_cuda and right.is_cuda and left.dtype == right.dtype == torch.uint8
+
+            def strides_ok(t):
+                return t.stride(-1) == 1 and (ch == 1 or t.stride(-2) == 3) and t.stride(row_axis) >= cols * ch and \
+                    (single or t.stride(0) >= rows * t.stride(row_axis))
+            if not (strides_ok(left) and strides_ok(right) and left.stride() == right.stride()):
+                left, right = left.contiguous(), right.contiguous()
+            pitch, fs = int(left.stride(row_axis)), (0 if single else int(left.stride(0)))
+            mem, pl, pr = L.MEM_DEVICE, left.data_ptr(), right.data_ptr()
+        else:
+            left, right = np.asarray(left), np.asarray(right)
+            assert left.dtype == np.uint8 and right.dtype == np.uint8
+
+            def strides_ok(a):
+                st = a.strides
+                return st[-1] == 1 and (ch == 1 or st[-2] == 3) and st[row_axis] >= cols * ch and (single or st[0] >= rows * st[row_axis])
+            if not (strides_ok(left) and strides_ok(right) and left.strides == right.strides):  # (a shared padded layout passes through)
+                left, right = np.ascontiguousarray(left), np.ascontiguousarray(right)
+            pitch, fs = int(left.strides[row_axis]), (0 if single else int(left.strides[0]))
+            mem, pl, pr = L.MEM_HOST, left.ctypes.data, right.ctypes.data
+        prm = L.StereoParamsStruct(int(n_disparities), int(min_disparity), int(p1), int(p2), int(n_paths), int(uniqueness),
+                                   int(lr_max_diff), ch, int(group_frames))
+        shape = (rows, cols) if single else (F, rows, cols)
+        D = max(int(n_disparities), 1)
+        if dev:
+            def empty(shp, dt):
+                return torch.empty(shp, dtype=dt, device=left.device)
+            u8, u16 = torch.uint8, torch.int16  # (uint16 bits; viewed below)
+            self._order_after_torch()
+            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        else:
+            def empty(shp, dt):
+                return np.empty(shp, dt)
+            u8, u16 = np.uint8, np.uint16
+            ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        disp = None if subpixel else empty(shape, u8)
+        q4 = empty(shape, u16) if subpixel else None
+        cost = empty(shape, u16) if return_cost else None
+        vol = empty(shape + (D,), u16) if return_volume else None
+        L.check(self._lib.o3dr_stereo_disparity(self._h, pl, pr, fs, pitch, rows, cols, F, C.byref(prm), ptr(disp), ptr(q4), ptr(cost),
+                                                ptr(vol), mem))
+        if dev:  # (every value is below 2^15, so the int16 tensors hold the uint16 bits and their values)
+            out = q4.to(torch.float64) / 16.0 if subpixel else disp
+            cost = None if cost is None else cost.view(torch.uint16)
+            vol = None if vol is None else vol.view(torch.uint16)
+        else:
+            out = q4.astype(np.float64) / 16.0 if subpixel else disp
+        if not (return_cost or return_volume):
+            return out
+        return (out,) + ((cost,) if return_cost else ()) + ((vol,) if return_volume else ())
+
     # -- feature matching (BFMatcher NORM_HAMMING knnMatch k=2 + ratio test, pose.h:180 / pose_functions.cpp:2017, and
     #    TransformationEstimationSVD, pose.cpp:213-235) --------------------------------------------------------------------
     @staticmethod

@@ -146,6 +146,7 @@ struct o3dr_ctx {
     bool orb_pat_valid = false;
     std::vector<int8_t> orb_pat_h;  // (outlives the asynchronous upload)
     int64_t test_orb_scratch = 0;   // o3dr_test_orb_scratch_limit: stands in for kOrbScratchBytes when positive
+    DevBuf stereo_work;        // o3dr_stereo_disparity: its own scratch block (one carve per call)
     DevBuf pl_hyp;             // o3dr_segment_plane: hypotheses + scores (plane_hyp_layout), kept for the test hook
     uint64_t pl_last_hyp = 0;  // hypotheses of the last call in pl_hyp (o3dr_test_plane_hypotheses)
     std::vector<MatchPair> mt_tab_h;  // host copies of the match pair table, the rigid fit's segment table and transforms
@@ -473,7 +474,7 @@ extern "C" int o3dr_ctx_destroy(o3dr_ctx* c)
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     for (DevBuf* b : {&c->inc.box, &c->inc.scratch, &c->inc.tg, &c->inc.tmatch, &c->inc.flag, &c->inc.src, &c->inc.keep,
-                      &c->inc.partial, &c->inc.words, &c->inc.fb, &c->nn_q, &c->nn_t, &c->nn_cells, &c->nn_src, &c->pl_hyp, &c->orb_work, &c->orb_pat})
+                      &c->inc.partial, &c->inc.words, &c->inc.fb, &c->nn_q, &c->nn_t, &c->nn_cells, &c->nn_src, &c->pl_hyp, &c->orb_work, &c->orb_pat, &c->stereo_work})
         dev_release(*b);
     for (DevBuf& b : c->op) dev_release(b);
     delete c;
@@ -4830,6 +4831,139 @@ extern "C" int o3dr_orb_detect(o3dr_ctx* c, const uint8_t* img, int64_t frame_st
         if (n_out) *n_out = 0;
         if (offsets && n_frames >= 0) memset(offsets, 0, sizeof(int64_t) * ((size_t)n_frames + 1));
         outs.zero();
+    }
+    return rc;
+}
+
+// =================================================================================================
+// stereo disparity (kernels/stereo.inc; DESIGN.md "Stereo disparity")
+// =================================================================================================
+extern "C" void o3dr_stereo_default_params(o3dr_stereo_params* p)
+{
+    if (!p) return;
+    p->n_disparities = 256;
+    p->min_disparity = 0;
+    p->p1 = 10;
+    p->p2 = 120;
+    p->n_paths = 8;
+    p->uniqueness = 10;
+    p->lr_max_diff = 1;
+    p->channels = 3;
+    p->group_frames = 0;
+}
+
+static bool stereo_shape_ok(int32_t rows, int32_t cols, int32_t n_frames)
+{
+    return rows >= 1 && rows <= O3DR_STEREO_MAX_SIDE && cols >= 1 && cols <= O3DR_STEREO_MAX_SIDE && n_frames >= 0;
+}
+static bool stereo_disparities_ok(int32_t D) { return D >= 32 && D <= 256 && D % 32 == 0; }
+
+static int stereo_check_params(const o3dr_stereo_params& p, int32_t rows, int32_t cols)
+{
+    if (!stereo_shape_ok(rows, cols, 0)) return fail(O3DR_ERR_INVALID_ARG, "rows and cols must be in 1..8192");
+    if (!stereo_disparities_ok(p.n_disparities)) return fail(O3DR_ERR_INVALID_ARG, "n_disparities must be a multiple of 32 in 32..256");
+    if (p.min_disparity < 0 || p.min_disparity + p.n_disparities > 256)
+        return fail(O3DR_ERR_INVALID_ARG, "min_disparity must be >= 0 with min_disparity + n_disparities <= 256");
+    if (p.p1 < 0 || p.p1 > 255) return fail(O3DR_ERR_INVALID_ARG, "p1 must be in 0..255");
+    if (p.p2 < p.p1 || p.p2 > 255) return fail(O3DR_ERR_INVALID_ARG, "p2 must be in p1..255");
+    if (p.n_paths != 4 && p.n_paths != 8) return fail(O3DR_ERR_INVALID_ARG, "n_paths must be 4 or 8");
+    if (p.uniqueness < 0 || p.uniqueness > 99) return fail(O3DR_ERR_INVALID_ARG, "uniqueness must be in 0..99");
+    if (p.lr_max_diff < -1 || p.lr_max_diff > 255) return fail(O3DR_ERR_INVALID_ARG, "lr_max_diff must be in -1..255");
+    if (p.channels != 1 && p.channels != 3) return fail(O3DR_ERR_INVALID_ARG, "channels must be 1 or 3");
+    if (p.group_frames < 0) return fail(O3DR_ERR_INVALID_ARG, "group_frames is negative");
+    return O3DR_OK;
+}
+
+constexpr size_t kStereoScratchBytes = (size_t)1 << 30;  // a group of frames keeps its scratch within this (one frame always forms a group)
+
+static int stereo_disparity(o3dr_ctx* c, const uint8_t* left, const uint8_t* right, int64_t fs, int64_t pitch, int32_t rows,
+                            int32_t cols, int32_t n_frames, const o3dr_stereo_params* p, uint8_t* disp, uint16_t* disp_q4,
+                            uint16_t* cost, Outputs& outs, uint16_t* volume_out, int32_t mem)
+{
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    if (n_frames < 0) return fail(O3DR_ERR_INVALID_ARG, "bad frame count");
+    o3dr_stereo_params prm;
+    o3dr_stereo_default_params(&prm);
+    if (p) prm = *p;
+    CHK(stereo_check_params(prm, rows, cols));
+    if (n_frames == 0) return O3DR_OK;
+    if (!left || !right) return fail(O3DR_ERR_INVALID_ARG, "left / right is NULL");
+    if (pitch < (int64_t)cols * prm.channels) return fail(O3DR_ERR_INVALID_ARG, "pitch smaller than a row");
+    if (n_frames > 1 && fs < (int64_t)rows * pitch) return fail(O3DR_ERR_INVALID_ARG, "frame stride smaller than a frame");
+    if ((uintptr_t)disp_q4 % 2 || (uintptr_t)cost % 2 || (uintptr_t)volume_out % 2)
+        return fail(O3DR_ERR_INVALID_ARG, "disp_q4 / cost / volume_out must be 2-byte aligned");
+
+    StereoArgs a;
+    memset(&a, 0, sizeof a);
+    a.rows = rows, a.cols = cols, a.channels = prm.channels;
+    a.D = prm.n_disparities, a.d0 = prm.min_disparity, a.p1 = prm.p1, a.p2 = prm.p2, a.n_paths = prm.n_paths;
+    a.uniq = prm.uniqueness, a.lr = prm.lr_max_diff;
+    a.fstride = fs, a.pitch = pitch;
+    const size_t n = (size_t)rows * (size_t)cols, D = (size_t)prm.n_disparities;
+    const size_t in_bytes = (size_t)fs * (size_t)(n_frames - 1) + (size_t)pitch * (size_t)(rows - 1) + (size_t)cols * prm.channels;
+    const void *left_d, *right_d;
+    if (mem == O3DR_MEM_HOST) {  // both images in one staging block, the right one behind the left
+        CHK(dev_ensure(c, c->op[o3dr_ctx::OP_IN], 2 * align256(in_bytes)));
+        char* base = (char*)c->op[o3dr_ctx::OP_IN].p;
+        HIPCHK(hipMemcpyAsync(base, left, in_bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(base + align256(in_bytes), right, in_bytes, hipMemcpyHostToDevice, c->stream));
+        left_d = base, right_d = base + align256(in_bytes);
+    } else {
+        left_d = left, right_d = right;
+    }
+
+    const size_t per_frame = n * (2 * D + 21);
+    size_t group = std::max<size_t>(1, kStereoScratchBytes / per_frame);
+    group = std::min<size_t>(std::min<size_t>(group, (size_t)n_frames), 32768);
+    if (prm.group_frames > 0) group = std::min<size_t>(group, (size_t)prm.group_frames);
+    CHK(carve(c, c->stereo_work, [&](Carve& w) {
+        w.take(a.cenL, group * n);
+        w.take(a.cenR, group * n);
+        w.take(a.S, group * n * D);
+        w.take(a.win, group * n);
+        w.take(a.bestR, group * n);
+    }));
+    CHK(outs.stage(c));
+    uint8_t* disp_d = outs.dev(disp);
+    uint16_t *q4_d = outs.dev(disp_q4), *cost_d = outs.dev(cost);
+    for (size_t f0 = 0; f0 < (size_t)n_frames; f0 += group) {
+        a.frames = (int32_t)std::min(group, (size_t)n_frames - f0);
+        a.left = (const uint8_t*)left_d + (int64_t)f0 * fs;
+        a.right = (const uint8_t*)right_d + (int64_t)f0 * fs;
+        a.disp = disp_d ? disp_d + f0 * n : nullptr;
+        a.q4 = q4_d ? q4_d + f0 * n : nullptr;
+        a.cost = cost_d ? cost_d + f0 * n : nullptr;
+        launch_stereo(&c->prof, c->stream, a);
+        if (volume_out)
+            HIPCHK(hipMemcpyAsync(volume_out + f0 * n * D, a.S, (size_t)a.frames * n * D * sizeof(uint16_t),
+                                  mem == O3DR_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+    }
+    HIPCHK(hipGetLastError());
+    CHK(outs.copy_back(c));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_stereo_disparity(o3dr_ctx* c, const uint8_t* left, const uint8_t* right, int64_t frame_stride, int64_t pitch,
+                                     int32_t rows, int32_t cols, int32_t n_frames, const o3dr_stereo_params* p, uint8_t* disp,
+                                     uint16_t* disp_q4, uint16_t* cost, uint16_t* volume_out, int32_t mem)
+{
+    // the outputs' sizes are known only where the shape itself is within its limits
+    const int64_t px = stereo_shape_ok(rows, cols, n_frames) ? (int64_t)n_frames * rows * cols : 0;
+    Outputs outs{mem};
+    outs.add(disp, px);
+    outs.add(disp_q4, px);
+    outs.add(cost, px);
+    const int rc = entered(c, [&] {
+        return stereo_disparity(c, left, right, frame_stride, pitch, rows, cols, n_frames, p, disp, disp_q4, cost, outs, volume_out, mem);
+    });
+    if (rc != O3DR_OK) {
+        outs.zero();
+        o3dr_stereo_params prm;
+        o3dr_stereo_default_params(&prm);
+        if (p) prm = *p;
+        if (mem == O3DR_MEM_HOST && volume_out && px > 0 && stereo_disparities_ok(prm.n_disparities))
+            memset(volume_out, 0, (size_t)px * (size_t)prm.n_disparities * sizeof(uint16_t));
     }
     return rc;
 }

@@ -600,6 +600,22 @@ struct OrbArgs {
     uint8_t* desc;
 };
 void launch_orb(Profiler* pf, hipStream_t s, const OrbArgs& a);
+// Stereo disparity (kernels/stereo.inc; contract: include/o3dr.h "stereo disparity").  One StereoArgs describes a group of
+// `frames` frames.  Per frame: the two census images (rows * cols words each), S (rows * cols * D uint16, candidate
+// fastest), the left winners `win` (cost << 16 | rejected << 15 | (off + 8) << 8 | best) and the right winners bestR.
+struct StereoArgs {
+    const uint8_t *left, *right;
+    int64_t fstride, pitch;
+    int32_t rows, cols, channels, frames;
+    int32_t D, d0, p1, p2, n_paths, uniq, lr;
+    unsigned long long *cenL, *cenR;
+    uint16_t* S;
+    uint32_t* win;
+    uint8_t* bestR;
+    uint8_t* disp;   // the group's first frame in each output, rows tight; each nullptr: not asked for
+    uint16_t *q4, *cost;
+};
+void launch_stereo(Profiler* pf, hipStream_t s, const StereoArgs& a);
 void launch_partition(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelArgs& v, int n_parts, o3dr_point* out,
                       uint64_t* counts_dev, uint32_t* overflow_dev, const void* hdrs_dev = nullptr, int n_hdrs = 0);
 // its two halves: slice sizes without moving anything (the (part, tile) table stays in ws for the second half), then the move

@@ -34,6 +34,7 @@
 //   mesh         height-field surface mesh over the XY cells
 //   match        Hamming 2-NN descriptor matching, index-aligned 3-D keypoints, the batched rigid fit
 //   orb          ORB features: grey pyramid, FAST score + box sums, candidates, exact selection, steered BRIEF
+//   stereo       stereo disparity: grey + census, semi-global aggregation (one wave per scan line), winner + left-right check
 //   pose_chain   the feature-matched pose chain: one workgroup walks the frames (gather, moments, Kabsch, residual)
 //   ransac       three-point RANSAC for a rigid transform: one workgroup per segment / pair of the chain
 // The launchers follow in this file.
@@ -63,6 +64,7 @@ namespace o3dr {
 #include "kernels/match.inc"
 #include "kernels/plane_disparity.inc"
 #include "kernels/orb.inc"
+#include "kernels/stereo.inc"
 #include "kernels/pose_chain.inc"
 #include "kernels/ransac.inc"
 #include "kernels/pose_graph.inc"
@@ -683,6 +685,43 @@ void launch_orb(Profiler* pf, hipStream_t s, const OrbArgs& a)
     {
         ProfScope ps(pf, O3DR_K_ORB_DESCRIBE, s);
         k_orb_describe<<<cdiv64((int64_t)F * a.n_features, kOrbDescWaves), 64 * kOrbDescWaves, 0, s>>>(a);
+    }
+}
+
+// stereo disparity of one group of frames (a.frames <= 65535: the grid's y extent)
+template <int KJ>
+static void stereo_frames(Profiler* pf, hipStream_t s, const StereoArgs& a)
+{
+    static const int kDir[8][2] = {{1, 0}, {-1, 0}, {0, 1}, {0, -1}, {1, 1}, {-1, -1}, {1, -1}, {-1, 1}};
+    const int F = a.frames;
+    {
+        ProfScope ps(pf, O3DR_K_STEREO_PATHS, s);
+        for (int r = 0; r < a.n_paths; ++r) {
+            const int dx = kDir[r][0], dy = kDir[r][1];
+            const int lines = dy == 0 ? a.rows : dx == 0 ? a.cols : a.rows + a.cols - 1;
+            k_stereo_path<KJ><<<dim3(cdiv64(lines, 4), F), 256, 0, s>>>(a, dx, dy, r == 0);
+        }
+    }
+    {
+        ProfScope ps(pf, O3DR_K_STEREO_WINNER, s);
+        const int n_seg = cdiv64(a.cols, kStSeg);
+        k_stereo_winner<KJ><<<dim3(cdiv64((int64_t)a.rows * n_seg, 4), F), 256, 0, s>>>(a, n_seg);
+        k_stereo_finish<<<dim3(cdiv64((int64_t)a.rows * a.cols, 256), F), 256, 0, s>>>(a);
+    }
+}
+void launch_stereo(Profiler* pf, hipStream_t s, const StereoArgs& a)
+{
+    if (a.frames <= 0) return;
+    {
+        ProfScope ps(pf, O3DR_K_STEREO_CENSUS, s);
+        const int tiles_x = cdiv64(a.cols, kStTileX), tiles_y = cdiv64(a.rows, kStTileY);
+        k_stereo_census<<<dim3(tiles_x * tiles_y, a.frames, 2), 256, 0, s>>>(a, tiles_x);
+    }
+    switch ((a.D + 63) / 64) {
+    case 1: stereo_frames<1>(pf, s, a); break;
+    case 2: stereo_frames<2>(pf, s, a); break;
+    case 3: stereo_frames<3>(pf, s, a); break;
+    default: stereo_frames<4>(pf, s, a); break;
     }
 }
 

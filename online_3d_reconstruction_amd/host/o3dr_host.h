@@ -50,6 +50,8 @@ struct Image16 {                                // one 16-bit channel: a segment
 };
 // a label image: greyscale (colour type 0), 8 or 16 bits per sample, non-interlaced; empty on failure or any other format
 Image16 read_png_labels(const std::string& path);
+// an 8-bit greyscale PNG (stored deflate blocks: no compression); false if the file cannot be written
+bool write_png_grey8(const std::string& path, const uint8_t* data, int rows, int cols);
 // pcl::io::savePLYFileBinary layout (x,y,z float + r,g,b uchar, then one `camera` element); with normals (4 floats per
 // point: nx ny nz curvature) PointXYZRGBNormal's (the same, then normal_x normal_y normal_z curvature float)
 bool save_ply_binary(const std::string& path, const PointCloud& cloud, const std::vector<float>* normals = nullptr);
@@ -66,6 +68,7 @@ public:
     int img_num = 0;
     Image8 rgb_image, disparity_image;
     Image16 label_image;  // --use_segment_labels
+    Image8 right_image;   // --gpu_disparity: the pair's right image; disparity_image is then o3dr_stereo_disparity's
     double time = 0, tx = 0, ty = 0, tz = 0, qx = 0, qy = 0, qz = 0, qw = 1;
 };
 
@@ -155,6 +158,13 @@ public:
     int refine_gn_iterations = 5;     // --refine_gn_iterations, --refine_cg_iterations, --refine_prior_weight
     int refine_cg_iterations = 32;
     double refine_prior_weight = 0.0;
+    std::string stereo_left_png, stereo_right_png;  // --stereo_disparity left.png right.png: o3dr_stereo_disparity of one
+                                      // rectified pair, written as <left>.disparity.png (8-bit grey)
+    bool gpu_disparity = false;       // --gpu_disparity: every frame's disparity image comes from o3dr_stereo_disparity on
+    std::string rightImagePrefix;     // image_dir/<n>.png and --right_image_dir d/<n>.png instead of --disparity_dir
+                                      // (single-GPU batched path)
+    int stereo_n_disparities = 256, stereo_min_disparity = 0, stereo_p1 = 10, stereo_p2 = 120;  // --stereo_* flags
+    int stereo_paths = 8, stereo_uniqueness = 10, stereo_lr_max_diff = 1;
     std::string print_label_png;      // --print_label_png f: rows, cols and the labels of f as text (checks the reader)
 
     std::vector<RawImageData> rawImageDataVec;
@@ -190,6 +200,9 @@ private:
     void run_segment_cloud();                       // --segment_cloud_only
     void run_mesh_surface();                        // --mesh_surface
     void run_find_features();                       // --find_features
+    void run_stereo_disparity();                    // --stereo_disparity
+    void compute_gpu_disparities();                 // --gpu_disparity: fills every raw frame's disparity_image
+    o3dr_stereo_params stereo_params(int channels) const;  // the --stereo_* flags over the defaults
     o3dr_orb_params orb_params() const;             // the --orb_* flags over the defaults
     int first_img_num = -1, last_img_num = -1;
     bool run3d_reconstruction = true;

@@ -1,7 +1,8 @@
 // png_io.cpp — minimal PNG reader (zlib inflate + PNG unfiltering) standing in for the two cv::imread
 // calls on the hot path's input side (pose_functions.cpp:526 colour, :548 IMREAD_GRAYSCALE).
 // 8-bit, non-interlaced, colour types 0/2/3/4/6 — what the reference's bundled data uses.  read_png_labels reads the
-// segment label images of --use_segment_labels: greyscale, 8 or 16 bits, non-interlaced.
+// segment label images of --use_segment_labels: greyscale, 8 or 16 bits, non-interlaced.  write_png_grey8 writes the
+// disparity image of --stereo_disparity: 8-bit grey, filter 0, stored (uncompressed) deflate blocks.
 #include <zlib.h>
 
 #include <cstdio>
@@ -183,6 +184,69 @@ Image16 read_png_labels(const std::string& path)
     for (size_t p = 0; p < (size_t)w * h; ++p)
         out.data[p] = bpp == 2 ? (uint16_t)((img[2 * p] << 8) | img[2 * p + 1]) : (uint16_t)img[p];
     return out;
+}
+
+// 8-bit greyscale writer: every row with filter type 0, the zlib stream made of stored blocks (no compression), so the
+// only arithmetic is the two checksums.  Any PNG reader takes it, read_png above included.
+static uint32_t crc32_png(const uint8_t* p, size_t n, uint32_t crc)
+{
+    static uint32_t table[256];
+    if (!table[1])
+        for (uint32_t i = 0; i < 256; ++i) {
+            uint32_t c = i;
+            for (int k = 0; k < 8; ++k) c = (c & 1) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
+            table[i] = c;
+        }
+    crc = ~crc;
+    for (size_t i = 0; i < n; ++i) crc = table[(crc ^ p[i]) & 0xFF] ^ (crc >> 8);
+    return ~crc;
+}
+static void put_be32(std::vector<uint8_t>& v, uint32_t x)
+{
+    for (int s = 24; s >= 0; s -= 8) v.push_back((uint8_t)(x >> s));
+}
+static void put_chunk(std::vector<uint8_t>& file, const char* type, const std::vector<uint8_t>& data)
+{
+    put_be32(file, (uint32_t)data.size());
+    const size_t start = file.size();
+    file.insert(file.end(), type, type + 4);
+    file.insert(file.end(), data.begin(), data.end());
+    put_be32(file, crc32_png(&file[start], file.size() - start, 0));
+}
+bool write_png_grey8(const std::string& path, const uint8_t* data, int rows, int cols)
+{
+    if (!data || rows < 1 || cols < 1) return false;
+    std::vector<uint8_t> raw(((size_t)cols + 1) * rows);  // filter byte 0 + the row
+    for (int y = 0; y < rows; ++y) memcpy(&raw[((size_t)cols + 1) * y + 1], data + (size_t)cols * y, (size_t)cols);
+    std::vector<uint8_t> z = {0x78, 0x01};  // zlib header: deflate, 32 KiB window, no preset dictionary
+    uint32_t a = 1, b = 0;                  // Adler-32 of the raw bytes
+    for (size_t pos = 0; pos < raw.size();) {
+        const size_t n = raw.size() - pos < 65535 ? raw.size() - pos : 65535;
+        z.push_back(pos + n == raw.size() ? 1 : 0);  // BFINAL, BTYPE = 00 (stored)
+        z.push_back((uint8_t)(n & 0xFF));
+        z.push_back((uint8_t)(n >> 8));
+        z.push_back((uint8_t)(~n & 0xFF));
+        z.push_back((uint8_t)((~n >> 8) & 0xFF));
+        z.insert(z.end(), raw.begin() + (long)pos, raw.begin() + (long)(pos + n));
+        for (size_t i = pos; i < pos + n; ++i) {
+            a = (a + raw[i]) % 65521u;
+            b = (b + a) % 65521u;
+        }
+        pos += n;
+    }
+    put_be32(z, (b << 16) | a);
+    std::vector<uint8_t> file = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a}, ihdr;
+    put_be32(ihdr, (uint32_t)cols);
+    put_be32(ihdr, (uint32_t)rows);
+    const uint8_t tail[5] = {8, 0, 0, 0, 0};  // depth 8, colour type 0 (grey), deflate, adaptive filtering, no interlace
+    ihdr.insert(ihdr.end(), tail, tail + 5);
+    put_chunk(file, "IHDR", ihdr);
+    put_chunk(file, "IDAT", z);
+    put_chunk(file, "IEND", {});
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) return false;
+    const bool ok = fwrite(file.data(), 1, file.size(), f) == file.size();
+    return fclose(f) == 0 && ok;
 }
 
 }  // namespace o3dr_host

@@ -337,7 +337,10 @@ void Pose::populateData()
             for (int i = t; i < n; i += n_threads) {
                 RawImageData& r = rawImageDataVec[i];
                 r.rgb_image = read_png(imagePrefix + to_string(r.img_num) + ".png", false);       // :523-536
-                r.disparity_image = read_png(disparityPrefix + to_string(r.img_num) + ".png", true);  // :546-585
+                if (gpu_disparity)  // the disparity image is made after the reads, from the pair (compute_gpu_disparities)
+                    r.right_image = read_png(rightImagePrefix + to_string(r.img_num) + ".png", false);
+                else
+                    r.disparity_image = read_png(disparityPrefix + to_string(r.img_num) + ".png", true);  // :546-585
                 if (use_segment_labels) {
                     r.label_image = read_png_labels(segmentLabelsPrefix + to_string(r.img_num) + ".png");
                     if (!r.disparity_image.empty() &&
@@ -354,14 +357,17 @@ void Pose::populateData()
                     lock_guard<mutex> lk(mu);
                     cout << " no_pose_for_" << r.img_num << " " << flush;
                     r.disparity_image = Image8();
+                    r.right_image = Image8();
                 }
                 lock_guard<mutex> lk(mu);
-                cout << (r.rgb_image.empty() ? " cannot_read_i" : " i") << r.img_num << (r.disparity_image.empty() ? " cannot_read_d" : " d")
+                cout << (r.rgb_image.empty() ? " cannot_read_i" : " i") << r.img_num
+                     << ((gpu_disparity ? r.right_image.empty() : r.disparity_image.empty()) ? " cannot_read_d" : " d")
                      << r.img_num << " " << flush;
             }
         });
     for (thread& t : pool) t.join();
     cout << endl;
+    if (gpu_disparity) compute_gpu_disparities();
     for (const RawImageData& r : rawImageDataVec)
         if (!r.disparity_image.empty()) {  // rows/cols from the first readable image (:635-638)
             rows = r.disparity_image.rows;
@@ -425,6 +431,14 @@ void Pose::printUsage()
             "                     <image>.keypoints.txt, the --keypoints_dir format - the flags and the file name are this build's own)\n"
             "       [--gpu_keypoints]  (reconstruction run with jump_pixels != 1 and no --keypoints_dir: every batch's keypoints come\n"
             "                     from the same extractor on its rgb images, with the --orb_* flags; single-GPU batched path only)\n"
+            "./pose --stereo_disparity left.png right.png [--stereo_n_disparities n] [--stereo_min_disparity n] [--stereo_p1 n]\n"
+            "       [--stereo_p2 n] [--stereo_paths 4|8] [--stereo_uniqueness n] [--stereo_lr_max_diff n]\n"
+            "                     (census semi-global matching of one rectified pair: writes the 8-bit disparity image, 0 = rejected,\n"
+            "                     as <left>.disparity.png and prints the accepted pixels and the call time - the flags and the file\n"
+            "                     name are this build's own)\n"
+            "       [--gpu_disparity --right_image_dir d/]  (reconstruction run: every frame's disparity image comes from the same\n"
+            "                     matcher on image_dir/<n>.png and d/<n>.png, with the --stereo_* flags, instead of --disparity_dir;\n"
+            "                     single-GPU batched path only)\n"
             "       [--feature_poses] [--dist_nearby m] [--range_width n] [--chain_min_matches n] [--chain_max_rms m]\n"
             "       [--chain_ransac_threshold m] [--chain_ransac_iterations n] [--chain_ransac_seed s]\n"
             "       [--refine_poses] [--refine_gn_iterations n] [--refine_cg_iterations n] [--refine_prior_weight w]\n"
@@ -546,6 +560,22 @@ int Pose::parseCmdArgs(int argc, char** argv)
             find_features_png = argv[++i];
             run3d_reconstruction = false;
         }
+        else if (a == "--stereo_disparity") {
+            if (i + 2 >= argc || string(argv[i + 1]).rfind("--", 0) == 0 || string(argv[i + 2]).rfind("--", 0) == 0)
+                throw runtime_error("missing argument: --stereo_disparity needs left.png and right.png");
+            stereo_left_png = argv[++i];
+            stereo_right_png = argv[++i];
+            run3d_reconstruction = false;
+        }
+        else if (a == "--gpu_disparity") gpu_disparity = true;
+        else if (a == "--right_image_dir") rightImagePrefix = need(i);
+        else if (a == "--stereo_n_disparities") stereo_n_disparities = atoi(need(i));
+        else if (a == "--stereo_min_disparity") stereo_min_disparity = atoi(need(i));
+        else if (a == "--stereo_p1") stereo_p1 = atoi(need(i));
+        else if (a == "--stereo_p2") stereo_p2 = atoi(need(i));
+        else if (a == "--stereo_paths") stereo_paths = atoi(need(i));
+        else if (a == "--stereo_uniqueness") stereo_uniqueness = atoi(need(i));
+        else if (a == "--stereo_lr_max_diff") stereo_lr_max_diff = atoi(need(i));
         else if (a == "--gpu_keypoints") gpu_keypoints = true;
         else if (a == "--orb_n_features") orb_n_features = atoi(need(i));
         else if (a == "--orb_levels") orb_levels = atoi(need(i));
@@ -570,6 +600,12 @@ int Pose::parseCmdArgs(int argc, char** argv)
     if (run3d_reconstruction && gpu_keypoints) {
         if (n_gpus > 1 || partitioned_merge) throw runtime_error("--gpu_keypoints is not available with --gpus N > 1 / --partitioned_merge");
         if (reference_fanout) throw runtime_error("--gpu_keypoints is not available with --reference_fanout");
+    }
+    if (run3d_reconstruction && gpu_disparity) {
+        if (n_gpus > 1 || partitioned_merge) throw runtime_error("--gpu_disparity is not available with --gpus N > 1 / --partitioned_merge");
+        if (reference_fanout) throw runtime_error("--gpu_disparity is not available with --reference_fanout");
+        if (use_segment_labels) throw runtime_error("--gpu_disparity is not available with --use_segment_labels");
+        if (rightImagePrefix.empty()) throw runtime_error("--gpu_disparity needs --right_image_dir d/");
     }
     if (refine_poses && !feature_poses) throw runtime_error("--refine_poses refines the poses of --feature_poses: give both");
     if (run3d_reconstruction && feature_poses) {
@@ -811,6 +847,85 @@ void Pose::run_find_features()
     cerr << "Saved " << n << " keypoints to " << outp << endl;
 }
 
+o3dr_stereo_params Pose::stereo_params(int channels) const
+{
+    o3dr_stereo_params prm;
+    o3dr_stereo_default_params(&prm);
+    prm.n_disparities = stereo_n_disparities;
+    prm.min_disparity = stereo_min_disparity;
+    prm.p1 = stereo_p1;
+    prm.p2 = stereo_p2;
+    prm.n_paths = stereo_paths;
+    prm.uniqueness = stereo_uniqueness;
+    prm.lr_max_diff = stereo_lr_max_diff;
+    prm.channels = channels;
+    return prm;
+}
+
+// The disparity image of one rectified pair from o3dr_stereo_disparity (contract: include/o3dr.h "stereo disparity"),
+// written as <left>.disparity.png: what --disparity_dir reads as <img_num>.png.
+void Pose::run_stereo_disparity()
+{
+    Q = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // the tool needs no camera
+    const Image8 left = read_png(stereo_left_png, false), right = read_png(stereo_right_png, false);
+    if (left.empty()) throw runtime_error("could not read " + stereo_left_png);
+    if (right.empty()) throw runtime_error("could not read " + stereo_right_png);
+    if (left.rows != right.rows || left.cols != right.cols) throw runtime_error("--stereo_disparity: the two images differ in size");
+    const o3dr_stereo_params prm = stereo_params(3);
+    vector<uint8_t> disp((size_t)left.rows * left.cols);
+    o3dr_ctx* c = ctx_for_this_thread();
+    const auto t0 = chrono::steady_clock::now();
+    chk(o3dr_stereo_disparity(c, left.data.data(), right.data.data(), 0, left.pitch(), left.rows, left.cols, 1, &prm, disp.data(), nullptr,
+                              nullptr, nullptr, O3DR_MEM_HOST),
+        "o3dr_stereo_disparity");
+    const double ms = chrono::duration<double, milli>(chrono::steady_clock::now() - t0).count();
+    size_t accepted = 0;
+    for (uint8_t d : disp) accepted += d != 0;
+    cout << "pair " << left.rows << " x " << left.cols << ", disparities " << prm.min_disparity << ".." << prm.min_disparity + prm.n_disparities - 1
+         << ", accepted " << accepted << " of " << disp.size() << " pixels, " << ms << " ms" << endl;
+    const string outp = stereo_left_png + ".disparity.png";
+    if (!write_png_grey8(outp, disp.data(), left.rows, left.cols)) throw runtime_error("could not write " + outp);
+    cerr << "Saved the disparity image to " << outp << endl;
+}
+
+// --gpu_disparity: where the disparity PNGs would have been read, every raw frame with a readable pair gets its disparity
+// image from o3dr_stereo_disparity, a cycle's frames (at most 16) per call; the variance gate, the blur and everything
+// after them see that image.  A frame whose pair is unreadable or of another size than the first pair keeps no
+// disparity image and is rejected like one whose PNG is missing.
+void Pose::compute_gpu_disparities()
+{
+    vector<RawImageData*> todo;
+    int prows = 0, pcols = 0;
+    for (RawImageData& r : rawImageDataVec) {
+        if (r.rgb_image.empty() || r.right_image.empty()) continue;
+        if (!prows) prows = r.rgb_image.rows, pcols = r.rgb_image.cols;
+        if (r.rgb_image.rows == prows && r.rgb_image.cols == pcols && r.right_image.rows == prows && r.right_image.cols == pcols)
+            todo.push_back(&r);
+    }
+    if (todo.empty()) return;
+    const o3dr_stereo_params prm = stereo_params(3);
+    const size_t per_call = (size_t)min(seq_len > 0 ? seq_len : 16, 16), n = (size_t)prows * pcols;
+    vector<uint8_t> left(per_call * n * 3), right(per_call * n * 3), disp(per_call * n);
+    o3dr_ctx* c = ctx_for_this_thread();
+    for (size_t k0 = 0; k0 < todo.size(); k0 += per_call) {
+        const size_t k1 = min(todo.size(), k0 + per_call);
+        for (size_t k = k0; k < k1; ++k) {
+            memcpy(&left[(k - k0) * n * 3], todo[k]->rgb_image.data.data(), n * 3);
+            memcpy(&right[(k - k0) * n * 3], todo[k]->right_image.data.data(), n * 3);
+        }
+        chk(o3dr_stereo_disparity(c, left.data(), right.data(), (int64_t)(n * 3), 3 * (int64_t)pcols, prows, pcols, (int32_t)(k1 - k0), &prm,
+                                  disp.data(), nullptr, nullptr, nullptr, O3DR_MEM_HOST),
+            "o3dr_stereo_disparity");
+        for (size_t k = k0; k < k1; ++k) {
+            Image8& d = todo[k]->disparity_image;
+            d.rows = prows, d.cols = pcols, d.channels = 1;
+            d.data.assign(disp.begin() + (long)((k - k0) * n), disp.begin() + (long)((k - k0 + 1) * n));
+            todo[k]->right_image = Image8();
+        }
+    }
+    cout << "--gpu_disparity: " << todo.size() << " disparity images from o3dr_stereo_disparity" << endl;
+}
+
 // pose.cpp:23-565 restricted to the hot path
 Pose::Pose(int argc, char* argv[])
 {
@@ -845,6 +960,10 @@ Pose::Pose(int argc, char* argv[])
     }
     if (!find_features_png.empty()) {
         run_find_features();
+        return;
+    }
+    if (!stereo_left_png.empty()) {
+        run_stereo_disparity();
         return;
     }
     if (!print_label_png.empty()) {  // what read_png_labels makes of one file: "rows cols", then one row of labels per line
