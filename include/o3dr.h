@@ -807,8 +807,8 @@ int  o3dr_orb_detect(o3dr_ctx* ctx, const uint8_t* img, int64_t frame_stride, in
  * census-transform semi-global matching.  The reference reads its disparities as files an offline matcher wrote (SURVEY
  * section 2), so there is nothing of its to pin: the contract below is this library's own; every step is an exact
  * integer computation, so results are bit-identical across calls, frame batchings and memory kinds;
- * tests/stereo_reference.py restates it in numpy.  Not included: median and speckle filtering, an adaptive P2, and
- * rectification itself - the pair must arrive rectified.
+ * tests/stereo_reference.py restates it in numpy.  Median and speckle filtering are a call of their own
+ * (o3dr_disparity_filter, below).  Not included: an adaptive P2, and rectification itself - the pair must arrive rectified.
  *
  * Input: `left` and `right`, n_frames images each of rows x cols pixels (1..8192 each), byte `pitch` and byte
  * `frame_stride` (the same for both), channels = 3 (interleaved B, G, R) or 1 (grey), both in `mem`.  W = cols, H = rows,
@@ -865,6 +865,63 @@ void o3dr_stereo_default_params(o3dr_stereo_params* p);
 int  o3dr_stereo_disparity(o3dr_ctx* ctx, const uint8_t* left, const uint8_t* right, int64_t frame_stride, int64_t pitch,
                            int32_t rows, int32_t cols, int32_t n_frames, const o3dr_stereo_params* p, uint8_t* disp,
                            uint16_t* disp_q4, uint16_t* cost, uint16_t* volume_out, int32_t mem);
+
+/* ---- disparity filter: what every production semi-global matcher ends with (OpenCV's medianBlur, then filterSpeckles):
+ * a k x k median of the disparity image, then the removal of small connected components.  The reference reads finished
+ * disparity files, so there is nothing of its to pin: the contract below is this library's own; every step is an exact
+ * integer computation, so results are bit-identical across calls, frame batchings and memory kinds;
+ * tests/disparity_filter_reference.py restates it in numpy.
+ *
+ * Input: `disp`, n_frames images of rows x cols elements (1..8192 each) of elem_bytes bytes (1: uint8, o3dr_stereo_disparity's
+ * disp; 2: uint16, its disp_q4), byte `pitch` and byte `frame_stride`, in `mem`.  W = cols, H = rows, v(x, y) the input.
+ *   1. Median, median_size = k in {3, 5}: m(x, y) = element k * k / 2 (0-based) of the ascending sort of the k x k values
+ *      v(clamp(x + dx, 0, W - 1), clamp(y + dy, 0, H - 1)), dx and dy in -(k / 2)..k / 2.  Zero (the rejected pixel) is a
+ *      value like any other: an isolated wrong pixel goes, and so does an isolated hole.  k = 0: m = v.
+ *   2. Components: a pixel is valid iff m != 0.  Two 4-neighbours of the same frame are joined iff both are valid and
+ *      |m(p) - m(q)| <= max_diff, the difference taken in a type that holds it (65535 against 1 differs by 65534).
+ *      Components are the transitive closure of the joins.  label(p) = the lowest y * W + x (within the frame) of p's
+ *      component, -1 for an invalid pixel; size(p) = the component's pixel count, 0 for an invalid pixel.
+ *   3. Speckles, max_speckle_size = n > 0: a valid pixel with size(p) <= n becomes 0 (OpenCV's <=); every other pixel
+ *      keeps m.  n = 0: every pixel keeps m.
+ *   4. Outputs, all in `mem`, [n_frames][H][W] with rows tight: out (required, the input's element type, must not overlap
+ *      disp): the image after step 3.  labels_out, sizes_out (int32, each optional, NULL: skipped): label and size of
+ *      step 2, before any removal.  info (HOST, optional, one per frame): n_valid = valid pixels, n_components =
+ *      components among them, n_speckles = components removed, n_removed = pixels removed (both 0 with
+ *      max_speckle_size = 0), largest = the size of the largest component (0: none).
+ *      With max_speckle_size = 0 and none of labels_out, sizes_out and info asked for no labelling kernel is launched;
+ *      with median_size = 0 as well, out = disp.
+ * Limits, else O3DR_ERR_INVALID_ARG before any device work (host outputs zeroed wherever rows, cols, n_frames - and for
+ * out elem_bytes - are themselves within their limits, so that the outputs' sizes are known): elem_bytes 1 or 2;
+ * median_size 0, 3 or 5; max_speckle_size >= 0; max_diff in 0..65535; group_frames >= 0; rows and cols in 1..8192;
+ * pitch >= cols * elem_bytes; frame_stride >= rows * pitch when n_frames > 1; disp and out 2-byte aligned (and pitch and
+ * frame_stride even) when elem_bytes = 2; labels_out and sizes_out 4-byte aligned; the bytes of out apart from the bytes of disp (as staged, below); n_frames >= 0 (0: O3DR_OK,
+ * nothing is touched).  pitch and frame_stride have no upper limit: with O3DR_MEM_HOST the image is staged as
+ * frame_stride * (n_frames - 1) + pitch * (rows - 1) + cols * elem_bytes bytes, and a stride too large for that returns
+ * O3DR_ERR_ALLOC (host outputs zeroed), not O3DR_ERR_INVALID_ARG.  p == NULL: the defaults.  group_frames: the frames of a
+ * call go through the kernels in groups whose scratch (label and count, 8 bytes a pixel) fits 1 GiB - one frame always
+ * forms a group -; group_frames = n > 0 caps a group at n frames.  A layout choice inside the scratch block: results do
+ * not depend on it.  The number of launches of a group depends on the switches and the image's size alone, never on its
+ * content.  The call carves its own scratch block, does not use the sort workspace, leaves cloud_big alone and
+ * synchronises the stream once, at its end. */
+#define O3DR_DISPARITY_FILTER_MAX_SIDE 8192
+typedef struct o3dr_disparity_filter_params {
+    int32_t elem_bytes;       /* default 1: uint8 image (disp); 2: uint16 image (disp_q4) */
+    int32_t median_size;      /* default 0: no median; 3 or 5 */
+    int32_t max_speckle_size; /* default 0: no speckle removal; n > 0: components of <= n pixels are removed */
+    int32_t max_diff;         /* default 1; 0..65535, in the image's own units */
+    int32_t group_frames;     /* default 0: as many frames per launch group as the scratch budget allows; n > 0: at most n */
+} o3dr_disparity_filter_params;
+typedef struct o3dr_disparity_filter_info {   /* one per frame, HOST */
+    int64_t n_valid;        /* non-zero pixels after the median */
+    int64_t n_components;   /* components among them */
+    int64_t n_speckles;     /* components removed */
+    int64_t n_removed;      /* pixels removed */
+    int64_t largest;        /* size of the largest component (0: none) */
+} o3dr_disparity_filter_info;
+void o3dr_disparity_filter_default_params(o3dr_disparity_filter_params* p);
+int  o3dr_disparity_filter(o3dr_ctx* ctx, const void* disp, int64_t frame_stride, int64_t pitch, int32_t rows, int32_t cols,
+                           int32_t n_frames, const o3dr_disparity_filter_params* p, void* out, int32_t* labels_out,
+                           int32_t* sizes_out, o3dr_disparity_filter_info* info, int32_t mem);
 
 /* ---- pose chain: the reference's default mode (pose.cpp:213-235, generate_tf_of_Matched_Keypoints): every frame gets its
  * pose from descriptor matches against earlier nearby frames, whose keypoints are moved by THEIR fitted poses - a serial
@@ -1129,7 +1186,10 @@ int  o3dr_pose_graph_refine(o3dr_ctx* ctx, const uint8_t* desc, const int64_t* o
 #define O3DR_K_STEREO_CENSUS 22  /* stereo disparity: grey + census of both images */
 #define O3DR_K_STEREO_PATHS  23  /* ... the aggregation, one launch per direction, one wave per scan line */
 #define O3DR_K_STEREO_WINNER 24  /* ... winners of left and right pixels, rejections, outputs */
-#define O3DR_K_NUM          25
+#define O3DR_K_DISP_MEDIAN  25  /* disparity filter: the k x k median */
+#define O3DR_K_DISP_LABEL   26  /* ... components: tile labelling in LDS, border merge, flatten + sizes */
+#define O3DR_K_DISP_SPECKLE 27  /* ... removal of the small components and the per-frame counts */
+#define O3DR_K_NUM          28
 /* Bracket every launch of kernel `kernel_id` (or all kernels if -1) with HIP events on the
  * context's stream; 0 launches are bracketed when disabled (the default). */
 int o3dr_profile_enable(o3dr_ctx* ctx, int32_t kernel_id, int32_t enable);

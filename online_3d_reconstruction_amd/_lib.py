@@ -21,10 +21,12 @@ K_ORB_PYRAMID, K_ORB_FAST, K_ORB_CANDIDATES, K_ORB_SELECT, K_ORB_DESCRIBE = 12, 
 K_MATCH, K_POSE_CHAIN, K_RANSAC = 17, 18, 19
 K_GRAPH_MOMENTS, K_GRAPH_SOLVE = 20, 21
 K_STEREO_CENSUS, K_STEREO_PATHS, K_STEREO_WINNER = 22, 23, 24
+K_DISP_MEDIAN, K_DISP_LABEL, K_DISP_SPECKLE = 25, 26, 27
 KERNEL_NAMES = ["reproject_count", "reproject_emit", "voxel_keys", "radix_hist", "radix_scatter", "run_segments",
                 "centroid", "other", "centroid_runs", "plane_disp_sums", "plane_disp_fit", "plane_disp_eval",
                 "orb_pyramid", "orb_fast", "orb_candidates", "orb_select", "orb_describe", "match", "pose_chain", "ransac",
-                "graph_moments", "graph_solve", "stereo_census", "stereo_paths", "stereo_winner"]
+                "graph_moments", "graph_solve", "stereo_census", "stereo_paths", "stereo_winner", "disp_median", "disp_label",
+                "disp_speckle"]
 
 
 class O3drError(RuntimeError):
@@ -118,6 +120,19 @@ class StereoParamsStruct(C.Structure):
 
 
 STEREO_MAX_SIDE = 8192
+
+
+class DisparityFilterParamsStruct(C.Structure):
+    _fields_ = [("elem_bytes", C.c_int32), ("median_size", C.c_int32), ("max_speckle_size", C.c_int32), ("max_diff", C.c_int32),
+                ("group_frames", C.c_int32)]
+
+
+class DisparityFilterInfoStruct(C.Structure):
+    _fields_ = [("n_valid", C.c_int64), ("n_components", C.c_int64), ("n_speckles", C.c_int64), ("n_removed", C.c_int64),
+                ("largest", C.c_int64)]
+
+
+DISPARITY_FILTER_MAX_SIDE = 8192
 
 
 class MatchParamsStruct(C.Structure):
@@ -269,6 +284,9 @@ SYMBOLS = [
     ("o3dr_stereo_default_params", None, [C.POINTER(StereoParamsStruct)]),
     ("o3dr_stereo_disparity", C.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, C.POINTER(StereoParamsStruct), _vp, _vp, _vp, _vp,
                                         _i32]),
+    ("o3dr_disparity_filter_default_params", None, [C.POINTER(DisparityFilterParamsStruct)]),
+    ("o3dr_disparity_filter", C.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, C.POINTER(DisparityFilterParamsStruct), _vp, _vp, _vp,
+                                        _vp, _i32]),
     ("o3dr_chain_default_params", None, [C.POINTER(ChainParamsStruct)]),
     ("o3dr_pose_chain", C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, C.POINTER(ChainParamsStruct), _vp, _vp, _vp, _i64,
                                   _pi64, _i32]),

@@ -105,6 +105,17 @@ class RefineResult:
     flags: int
 
 
+@dataclass
+class DisparityFilterInfo:
+    """o3dr_disparity_filter's counts for one frame: non-zero pixels after the median, components among them, components
+    and pixels removed as speckles, and the size of the largest component (0: none)."""
+    n_valid: int
+    n_components: int
+    n_speckles: int
+    n_removed: int
+    largest: int
+
+
 def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
@@ -599,7 +610,8 @@ class Context:
 
     # -- stereo disparity (the image every frame call starts from; the reference reads it from files) ----------------------
     def stereoDisparity(self, left, right, n_disparities=256, min_disparity=0, p1=10, p2=120, n_paths=8, uniqueness=10,
-                        lr_max_diff=1, subpixel=False, return_cost=False, return_volume=False, group_frames=0):
+                        lr_max_diff=1, subpixel=False, return_cost=False, return_volume=False, group_frames=0, median=0,
+                        speckle_size=0, speckle_diff=1):
         """Census-transform semi-global matching of a rectified pair (contract: include/o3dr.h "stereo disparity").  left /
         right: uint8 [H, W] or [F, H, W] grey, [H, W, 3] or [F, H, W, 3] B G R, same shape; numpy, or torch CUDA tensors (the
         outputs are then CUDA tensors and nothing leaves HBM).  A 3-D input whose last axis is 3 is taken as one B G R image
@@ -607,7 +619,9 @@ class Context:
         what accumulateFrames, disparityVariance and keypoints3D take.  subpixel=True: a float64 image instead, disp_q4 / 16.0
         (exact; rejected pixels 0.0): what the frame calls read under Params(disparity_f64=True).  return_cost: S at the winner
         (uint16) follows; return_volume: S itself (uint16 [..., H, W, D]) follows that.  group_frames: at most that many frames
-        per launch group (0: as many as the scratch budget allows); results do not depend on it."""
+        per launch group (0: as many as the scratch budget allows); results do not depend on it.  median (0, 3, 5) /
+        speckle_size > 0: the image to be returned goes through filterDisparity first - disp with max_diff = speckle_diff,
+        under subpixel=True disp_q4 with max_diff = 16 * speckle_diff before the division; cost and volume stay as they are."""
         dev = _is_torch(left)
         assert dev == _is_torch(right) and tuple(left.shape) == tuple(right.shape)
         nd = left.dim() if dev else np.ndim(left)
@@ -660,6 +674,11 @@ class Context:
         vol = empty(shape + (D,), u16) if return_volume else None
         L.check(self._lib.o3dr_stereo_disparity(self._h, pl, pr, fs, pitch, rows, cols, F, C.byref(prm), ptr(disp), ptr(q4), ptr(cost),
                                                 ptr(vol), mem))
+        if median or speckle_size:
+            if subpixel:
+                q4 = self.filterDisparity(q4, median, speckle_size, 16 * int(speckle_diff), group_frames=group_frames)
+            else:
+                disp = self.filterDisparity(disp, median, speckle_size, speckle_diff, group_frames=group_frames)
         if dev:  # (every value is below 2^15, so the int16 tensors hold the uint16 bits and their values)
             out = q4.to(torch.float64) / 16.0 if subpixel else disp
             cost = None if cost is None else cost.view(torch.uint16)
@@ -669,6 +688,62 @@ class Context:
         if not (return_cost or return_volume):
             return out
         return (out,) + ((cost,) if return_cost else ()) + ((vol,) if return_volume else ())
+
+    # -- disparity filter (what production matchers end with: medianBlur, then filterSpeckles) --------------------------------
+    def filterDisparity(self, disp, median=0, max_speckle_size=0, max_diff=1, return_labels=False, return_sizes=False,
+                        return_info=False, group_frames=0):
+        """k x k median (0: off, 3, 5), then removal of the connected components of at most max_speckle_size pixels (0: off;
+        4-neighbours are joined iff both are non-zero and differ by at most max_diff) - contract: include/o3dr.h "disparity
+        filter".  disp: uint8 or uint16, [H, W] or [F, H, W], a padded pitch or frame stride passes through; numpy, or a
+        torch CUDA tensor (uint8, or uint16 / int16 holding the uint16 bits; the outputs are then CUDA tensors and nothing
+        leaves HBM).  -> the filtered image in the input's type; return_labels / return_sizes: int32 images follow (the
+        lowest pixel index of the pixel's component, -1 for a zero pixel; its pixel count), as they are before the removal;
+        return_info: a list of DisparityFilterInfo, one per frame, follows.  group_frames: at most that many frames per
+        launch group; results do not depend on it."""
+        dev = _is_torch(disp)
+        nd = disp.dim() if dev else np.ndim(disp)
+        assert nd in (2, 3)
+        single = nd == 2
+        F = 1 if single else int(disp.shape[0])
+        rows, cols = int(disp.shape[-2]), int(disp.shape[-1])
+        if dev:
+            import torch
+            assert disp.is_cuda and disp.dtype in (torch.uint8, torch.uint16, torch.int16)
+            E = disp.element_size()
+            if disp.stride(-1) != 1 or disp.stride(-2) < cols or (not single and disp.stride(0) < rows * disp.stride(-2)):
+                disp = disp.contiguous()
+            pitch, fs = int(disp.stride(-2)) * E, (0 if single else int(disp.stride(0)) * E)
+            mem, pi = L.MEM_DEVICE, disp.data_ptr()
+        else:
+            disp = np.asarray(disp)
+            assert disp.dtype in (np.uint8, np.uint16)
+            E = disp.itemsize
+            st = disp.strides
+            if st[-1] != E or st[-2] < cols * E or (not single and st[0] < rows * st[-2]):
+                disp = np.ascontiguousarray(disp)
+            pitch, fs = int(disp.strides[-2]), (0 if single else int(disp.strides[0]))
+            mem, pi = L.MEM_HOST, disp.ctypes.data
+        prm = L.DisparityFilterParamsStruct(E, int(median), int(max_speckle_size), int(max_diff), int(group_frames))
+        shape = (rows, cols) if single else (F, rows, cols)
+        if dev:
+            out = torch.empty(shape, dtype=disp.dtype, device=disp.device)
+            labels = torch.empty(shape, dtype=torch.int32, device=disp.device) if return_labels else None
+            sizes = torch.empty(shape, dtype=torch.int32, device=disp.device) if return_sizes else None
+            self._order_after_torch()
+            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        else:
+            out = np.empty(shape, disp.dtype)
+            labels = np.empty(shape, np.int32) if return_labels else None
+            sizes = np.empty(shape, np.int32) if return_sizes else None
+            ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        info = (L.DisparityFilterInfoStruct * F)() if return_info else None
+        L.check(self._lib.o3dr_disparity_filter(self._h, pi, fs, pitch, rows, cols, F, C.byref(prm), ptr(out), ptr(labels), ptr(sizes),
+                                                C.cast(info, C.c_void_p) if return_info else None, mem))
+        if not (return_labels or return_sizes or return_info):
+            return out
+        infos = [DisparityFilterInfo(int(i.n_valid), int(i.n_components), int(i.n_speckles), int(i.n_removed), int(i.largest))
+                 for i in info] if return_info else None
+        return (out,) + ((labels,) if return_labels else ()) + ((sizes,) if return_sizes else ()) + ((infos,) if return_info else ())
 
     # -- feature matching (BFMatcher NORM_HAMMING knnMatch k=2 + ratio test, pose.h:180 / pose_functions.cpp:2017, and
     #    TransformationEstimationSVD, pose.cpp:213-235) --------------------------------------------------------------------

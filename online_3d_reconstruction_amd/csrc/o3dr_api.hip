@@ -147,6 +147,7 @@ struct o3dr_ctx {
     std::vector<int8_t> orb_pat_h;  // (outlives the asynchronous upload)
     int64_t test_orb_scratch = 0;   // o3dr_test_orb_scratch_limit: stands in for kOrbScratchBytes when positive
     DevBuf stereo_work;        // o3dr_stereo_disparity: its own scratch block (one carve per call)
+    DevBuf dfilter_work;       // o3dr_disparity_filter: its own scratch block (one carve per call)
     DevBuf pl_hyp;             // o3dr_segment_plane: hypotheses + scores (plane_hyp_layout), kept for the test hook
     uint64_t pl_last_hyp = 0;  // hypotheses of the last call in pl_hyp (o3dr_test_plane_hypotheses)
     std::vector<MatchPair> mt_tab_h;  // host copies of the match pair table, the rigid fit's segment table and transforms
@@ -474,7 +475,7 @@ extern "C" int o3dr_ctx_destroy(o3dr_ctx* c)
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     for (DevBuf* b : {&c->inc.box, &c->inc.scratch, &c->inc.tg, &c->inc.tmatch, &c->inc.flag, &c->inc.src, &c->inc.keep,
-                      &c->inc.partial, &c->inc.words, &c->inc.fb, &c->nn_q, &c->nn_t, &c->nn_cells, &c->nn_src, &c->pl_hyp, &c->orb_work, &c->orb_pat, &c->stereo_work})
+                      &c->inc.partial, &c->inc.words, &c->inc.fb, &c->nn_q, &c->nn_t, &c->nn_cells, &c->nn_src, &c->pl_hyp, &c->orb_work, &c->orb_pat, &c->stereo_work, &c->dfilter_work})
         dev_release(*b);
     for (DevBuf& b : c->op) dev_release(b);
     delete c;
@@ -4964,6 +4965,121 @@ extern "C" int o3dr_stereo_disparity(o3dr_ctx* c, const uint8_t* left, const uin
         if (p) prm = *p;
         if (mem == O3DR_MEM_HOST && volume_out && px > 0 && stereo_disparities_ok(prm.n_disparities))
             memset(volume_out, 0, (size_t)px * (size_t)prm.n_disparities * sizeof(uint16_t));
+    }
+    return rc;
+}
+
+// =================================================================================================
+// disparity filter (kernels/disparity_filter.inc; DESIGN.md "Disparity filter")
+// =================================================================================================
+extern "C" void o3dr_disparity_filter_default_params(o3dr_disparity_filter_params* p)
+{
+    if (!p) return;
+    p->elem_bytes = 1;
+    p->median_size = 0;
+    p->max_speckle_size = 0;
+    p->max_diff = 1;
+    p->group_frames = 0;
+}
+
+static bool dfilter_shape_ok(int32_t rows, int32_t cols, int32_t n_frames)
+{
+    return rows >= 1 && rows <= O3DR_DISPARITY_FILTER_MAX_SIDE && cols >= 1 && cols <= O3DR_DISPARITY_FILTER_MAX_SIDE && n_frames >= 0;
+}
+static bool dfilter_elem_ok(int32_t e) { return e == 1 || e == 2; }
+
+constexpr size_t kDfilterScratchBytes = (size_t)1 << 30;  // a group of frames keeps its scratch within this (one frame always forms a group)
+
+static int disparity_filter(o3dr_ctx* c, const void* disp, int64_t fs, int64_t pitch, int32_t rows, int32_t cols, int32_t n_frames,
+                            const o3dr_disparity_filter_params* p, uint8_t* out, int32_t* labels_out, int32_t* sizes_out,
+                            o3dr_disparity_filter_info* info, Outputs& outs, int32_t mem)
+{
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    if (n_frames < 0) return fail(O3DR_ERR_INVALID_ARG, "bad frame count");
+    o3dr_disparity_filter_params prm;
+    o3dr_disparity_filter_default_params(&prm);
+    if (p) prm = *p;
+    if (!dfilter_shape_ok(rows, cols, 0)) return fail(O3DR_ERR_INVALID_ARG, "rows and cols must be in 1..8192");
+    if (!dfilter_elem_ok(prm.elem_bytes)) return fail(O3DR_ERR_INVALID_ARG, "elem_bytes must be 1 or 2");
+    if (prm.median_size != 0 && prm.median_size != 3 && prm.median_size != 5) return fail(O3DR_ERR_INVALID_ARG, "median_size must be 0, 3 or 5");
+    if (prm.max_speckle_size < 0) return fail(O3DR_ERR_INVALID_ARG, "max_speckle_size is negative");
+    if (prm.max_diff < 0 || prm.max_diff > 65535) return fail(O3DR_ERR_INVALID_ARG, "max_diff must be in 0..65535");
+    if (prm.group_frames < 0) return fail(O3DR_ERR_INVALID_ARG, "group_frames is negative");
+    if (n_frames == 0) return O3DR_OK;
+    if (!disp || !out) return fail(O3DR_ERR_INVALID_ARG, "disp / out is NULL");
+    const int64_t E = prm.elem_bytes;
+    if (pitch < (int64_t)cols * E) return fail(O3DR_ERR_INVALID_ARG, "pitch smaller than a row");
+    if (n_frames > 1 && fs < (int64_t)rows * pitch) return fail(O3DR_ERR_INVALID_ARG, "frame stride smaller than a frame");
+    if (E == 2 && ((uintptr_t)disp % 2 || (uintptr_t)out % 2 || pitch % 2 || (n_frames > 1 && fs % 2)))
+        return fail(O3DR_ERR_INVALID_ARG, "uint16 images must be 2-byte aligned");
+    if ((uintptr_t)labels_out % 4 || (uintptr_t)sizes_out % 4) return fail(O3DR_ERR_INVALID_ARG, "labels_out / sizes_out must be 4-byte aligned");
+
+    DfArgs a;
+    memset(&a, 0, sizeof a);
+    a.rows = rows, a.cols = cols, a.elem = prm.elem_bytes, a.median = prm.median_size;
+    a.max_diff = prm.max_diff, a.max_size = prm.max_speckle_size;
+    const size_t n = (size_t)rows * (size_t)cols;
+    const size_t in_bytes = (size_t)fs * (size_t)(n_frames - 1) + (size_t)pitch * (size_t)(rows - 1) + (size_t)cols * (size_t)E;
+    {  // the byte ranges [disp, disp + in_bytes) and [out, out + n_frames * rows * cols * E), in either memory kind
+        const uintptr_t i0 = (uintptr_t)disp, o0 = (uintptr_t)out;
+        if (i0 < o0 + (uintptr_t)n_frames * n * (uintptr_t)E && o0 < i0 + in_bytes) return fail(O3DR_ERR_INVALID_ARG, "out must not overlap disp");
+    }
+    const void* disp_d;
+    CHK(stage_in(c, c->op[o3dr_ctx::OP_IN], disp, in_bytes, mem, &disp_d));
+
+    const bool labelling = prm.max_speckle_size > 0 || labels_out || sizes_out || info;
+    const size_t per_frame = n * 2 * sizeof(int32_t);
+    size_t group = labelling ? std::max<size_t>(1, kDfilterScratchBytes / per_frame) : (size_t)n_frames;
+    group = std::min<size_t>(std::min<size_t>(group, (size_t)n_frames), 32768);
+    if (prm.group_frames > 0) group = std::min<size_t>(group, (size_t)prm.group_frames);
+    unsigned long long* info_d = nullptr;
+    CHK(carve(c, c->dfilter_work, [&](Carve& w) {
+        if (labelling) w.take(a.parent, group * n);
+        if (labelling) w.take(a.cnt, group * n);
+        if (info) w.take(info_d, (size_t)n_frames * 5);
+    }));
+    if (info) HIPCHK(hipMemsetAsync(info_d, 0, (size_t)n_frames * 5 * sizeof(unsigned long long), c->stream));
+    CHK(outs.stage(c));
+    uint8_t* out_d = outs.dev(out);
+    int32_t *labels_d = outs.dev(labels_out), *sizes_d = outs.dev(sizes_out);
+    for (size_t f0 = 0; f0 < (size_t)n_frames; f0 += group) {
+        a.frames = (int32_t)std::min(group, (size_t)n_frames - f0);
+        a.in = DfView{(const char*)disp_d + (int64_t)f0 * fs, fs, pitch};
+        a.out = out_d + f0 * n * (size_t)E;
+        a.labels_out = labels_d ? labels_d + f0 * n : nullptr;
+        a.sizes_out = sizes_d ? sizes_d + f0 * n : nullptr;
+        a.info = info_d ? info_d + f0 * 5 : nullptr;
+        launch_disparity_filter(&c->prof, c->stream, a);
+    }
+    HIPCHK(hipGetLastError());
+    CHK(outs.copy_back(c));
+    std::vector<unsigned long long> counts(info ? (size_t)n_frames * 5 : 0);
+    if (info) HIPCHK(hipMemcpyAsync(counts.data(), info_d, counts.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (size_t f = 0; info && f < (size_t)n_frames; ++f) {
+        const unsigned long long* k = &counts[f * 5];
+        info[f] = o3dr_disparity_filter_info{(int64_t)k[0], (int64_t)k[1], (int64_t)k[2], (int64_t)k[3], (int64_t)k[4]};
+    }
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_disparity_filter(o3dr_ctx* c, const void* disp, int64_t frame_stride, int64_t pitch, int32_t rows, int32_t cols,
+                                     int32_t n_frames, const o3dr_disparity_filter_params* p, void* out, int32_t* labels_out,
+                                     int32_t* sizes_out, o3dr_disparity_filter_info* info, int32_t mem)
+{
+    // the outputs' sizes are known only where the shape itself (and for `out` the element size) is within its limits
+    const int64_t px = dfilter_shape_ok(rows, cols, n_frames) ? (int64_t)n_frames * rows * cols : 0;
+    const int32_t elem = p ? p->elem_bytes : 1;
+    Outputs outs{mem};
+    outs.add((uint8_t*)out, dfilter_elem_ok(elem) ? px * elem : 0);
+    outs.add(labels_out, px);
+    outs.add(sizes_out, px);
+    const int rc = entered(c, [&] {
+        return disparity_filter(c, disp, frame_stride, pitch, rows, cols, n_frames, p, (uint8_t*)out, labels_out, sizes_out, info, outs, mem);
+    });
+    if (rc != O3DR_OK) {
+        outs.zero();
+        if (info && px > 0) memset(info, 0, sizeof(o3dr_disparity_filter_info) * (size_t)n_frames);
     }
     return rc;
 }

@@ -616,6 +616,24 @@ struct StereoArgs {
     uint16_t *q4, *cost;
 };
 void launch_stereo(Profiler* pf, hipStream_t s, const StereoArgs& a);
+// Disparity filter (kernels/disparity_filter.inc; contract: include/o3dr.h "disparity filter").  One DfArgs describes a
+// group of `frames` frames.  in: the caller's image with its strides; median != 0 writes the median of it to `out` (rows
+// tight) and the components are then taken of `out`, else of `in`.  parent / cnt: one int32 per pixel each, the
+// union-find forest (-1: invalid pixel) and the pixel counts at the roots; nullptr: the call needs no labelling.
+struct DfView {
+    const void* p;
+    int64_t fstride, pitch;  // bytes
+};
+struct DfArgs {
+    DfView in, src;      // src: set by the launcher (the image after the median)
+    int32_t rows, cols, frames, elem, median, max_diff, max_size;
+    int32_t* parent;
+    int32_t* cnt;
+    int32_t *labels_out, *sizes_out;  // the group's first frame in each output, rows tight; each nullptr: not asked for
+    unsigned long long* info;         // [frames][5]: n_valid, n_components, n_speckles, n_removed, largest; nullptr: not asked for
+    void* out;
+};
+void launch_disparity_filter(Profiler* pf, hipStream_t s, const DfArgs& a);
 void launch_partition(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelArgs& v, int n_parts, o3dr_point* out,
                       uint64_t* counts_dev, uint32_t* overflow_dev, const void* hdrs_dev = nullptr, int n_hdrs = 0);
 // its two halves: slice sizes without moving anything (the (part, tile) table stays in ws for the second half), then the move

@@ -35,6 +35,7 @@
 //   match        Hamming 2-NN descriptor matching, index-aligned 3-D keypoints, the batched rigid fit
 //   orb          ORB features: grey pyramid, FAST score + box sums, candidates, exact selection, steered BRIEF
 //   stereo       stereo disparity: grey + census, semi-global aggregation (one wave per scan line), winner + left-right check
+//   disparity_filter  median and speckle removal of a disparity image: LDS median network, tiled union-find labelling
 //   pose_chain   the feature-matched pose chain: one workgroup walks the frames (gather, moments, Kabsch, residual)
 //   ransac       three-point RANSAC for a rigid transform: one workgroup per segment / pair of the chain
 // The launchers follow in this file.
@@ -65,6 +66,7 @@ namespace o3dr {
 #include "kernels/plane_disparity.inc"
 #include "kernels/orb.inc"
 #include "kernels/stereo.inc"
+#include "kernels/disparity_filter.inc"
 #include "kernels/pose_chain.inc"
 #include "kernels/ransac.inc"
 #include "kernels/pose_graph.inc"
@@ -723,6 +725,48 @@ void launch_stereo(Profiler* pf, hipStream_t s, const StereoArgs& a)
     case 3: stereo_frames<3>(pf, s, a); break;
     default: stereo_frames<4>(pf, s, a); break;
     }
+}
+
+// disparity filter of one group of frames (a.frames <= 65535: the grid's y extent); the launches depend on the call's
+// switches and the image's size alone
+template <class T>
+static void disparity_filter_frames(Profiler* pf, hipStream_t s, DfArgs a)
+{
+    const int F = a.frames;
+    const int tiles_x = cdiv64(a.cols, kDfTileX), tiles_y = cdiv64(a.rows, kDfTileY);
+    const int px_blocks = cdiv64((int64_t)a.rows * a.cols, 256);
+    a.src = a.in;
+    if (a.median) {
+        ProfScope ps(pf, O3DR_K_DISP_MEDIAN, s);
+        if (a.median == 3)
+            k_df_median<T, 3><<<dim3(tiles_x * tiles_y, F), 256, 0, s>>>(a.in, a.rows, a.cols, tiles_x, (T*)a.out);
+        else
+            k_df_median<T, 5><<<dim3(tiles_x * tiles_y, F), 256, 0, s>>>(a.in, a.rows, a.cols, tiles_x, (T*)a.out);
+        a.src = DfView{a.out, (int64_t)a.rows * a.cols * (int64_t)sizeof(T), (int64_t)a.cols * (int64_t)sizeof(T)};
+    }
+    if (a.parent) {
+        ProfScope ps(pf, O3DR_K_DISP_LABEL, s);
+        k_df_local<T><<<dim3(tiles_x * tiles_y, F), 256, 0, s>>>(a, tiles_x);
+        const int n_vert = (tiles_x - 1) * a.rows, n_all = n_vert + (tiles_y - 1) * a.cols;
+        if (n_all > 0) k_df_merge<T><<<dim3(cdiv64(n_all, 256), F), 256, 0, s>>>(a, n_vert, n_all);
+        k_df_flatten<<<dim3(px_blocks, F), 256, 0, s>>>(a);
+        if (a.labels_out || a.sizes_out) k_df_sizes<<<dim3(px_blocks, F), 256, 0, s>>>(a);
+    }
+    if (a.max_size > 0 || a.info) {
+        ProfScope ps(pf, O3DR_K_DISP_SPECKLE, s);
+        k_df_apply<T><<<dim3(px_blocks, F), 256, 0, s>>>(a);
+    } else if (!a.median) {  // neither filter: out = in
+        ProfScope ps(pf, O3DR_K_OTHER, s);
+        k_df_apply<T><<<dim3(px_blocks, F), 256, 0, s>>>(a);
+    }
+}
+void launch_disparity_filter(Profiler* pf, hipStream_t s, const DfArgs& a)
+{
+    if (a.frames <= 0) return;
+    if (a.elem == 1)
+        disparity_filter_frames<uint8_t>(pf, s, a);
+    else
+        disparity_filter_frames<uint16_t>(pf, s, a);
 }
 
 void launch_bbox(Profiler* pf, hipStream_t s, const float* mm, int used, float* out6)

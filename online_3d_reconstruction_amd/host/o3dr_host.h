@@ -165,6 +165,10 @@ public:
                                       // (single-GPU batched path)
     int stereo_n_disparities = 256, stereo_min_disparity = 0, stereo_p1 = 10, stereo_p2 = 120;  // --stereo_* flags
     int stereo_paths = 8, stereo_uniqueness = 10, stereo_lr_max_diff = 1;
+    // --stereo_median 0|3|5, --stereo_speckle_size n, --stereo_speckle_diff n: o3dr_disparity_filter of the disparity image
+    // in --stereo_disparity, --gpu_disparity and --filter_disparity; parsed and ignored elsewhere
+    int stereo_median = 0, stereo_speckle_size = 0, stereo_speckle_diff = 1;
+    std::string filter_disparity_png;  // --filter_disparity in.png: the filter alone on an 8-bit grey PNG -> <in>.filtered.png
     std::string print_label_png;      // --print_label_png f: rows, cols and the labels of f as text (checks the reader)
 
     std::vector<RawImageData> rawImageDataVec;
@@ -202,6 +206,10 @@ private:
     void run_find_features();                       // --find_features
     void run_stereo_disparity();                    // --stereo_disparity
     void compute_gpu_disparities();                 // --gpu_disparity: fills every raw frame's disparity_image
+    void run_filter_disparity();                    // --filter_disparity
+    bool disparity_filter_on() const { return stereo_median != 0 || stereo_speckle_size > 0; }
+    // o3dr_disparity_filter of n_frames tight uint8 images in place, with the three flags; info: one per frame, or nullptr
+    void filter_disparities(o3dr_ctx* c, std::vector<uint8_t>& disp, int rows, int cols, int n_frames, o3dr_disparity_filter_info* info);
     o3dr_stereo_params stereo_params(int channels) const;  // the --stereo_* flags over the defaults
     o3dr_orb_params orb_params() const;             // the --orb_* flags over the defaults
     int first_img_num = -1, last_img_num = -1;

@@ -436,6 +436,12 @@ void Pose::printUsage()
             "                     (census semi-global matching of one rectified pair: writes the 8-bit disparity image, 0 = rejected,\n"
             "                     as <left>.disparity.png and prints the accepted pixels and the call time - the flags and the file\n"
             "                     name are this build's own)\n"
+            "       [--stereo_median 0|3|5] [--stereo_speckle_size n] [--stereo_speckle_diff n]  (the disparity image then goes\n"
+            "                     through a k x k median and loses its connected components of at most n pixels, neighbours\n"
+            "                     joined when they differ by at most --stereo_speckle_diff (default 1); also under --gpu_disparity)\n"
+            "./pose --filter_disparity in.png [the same three flags]  (the filter alone on an 8-bit grey PNG: writes\n"
+            "                     <in>.filtered.png and prints the components, the speckles, the removed pixels and the call time;\n"
+            "                     at least one of the two filters must be on - the flags and the file name are this build's own)\n"
             "       [--gpu_disparity --right_image_dir d/]  (reconstruction run: every frame's disparity image comes from the same\n"
             "                     matcher on image_dir/<n>.png and d/<n>.png, with the --stereo_* flags, instead of --disparity_dir;\n"
             "                     single-GPU batched path only)\n"
@@ -576,6 +582,15 @@ int Pose::parseCmdArgs(int argc, char** argv)
         else if (a == "--stereo_paths") stereo_paths = atoi(need(i));
         else if (a == "--stereo_uniqueness") stereo_uniqueness = atoi(need(i));
         else if (a == "--stereo_lr_max_diff") stereo_lr_max_diff = atoi(need(i));
+        else if (a == "--stereo_median") stereo_median = atoi(need(i));
+        else if (a == "--stereo_speckle_size") stereo_speckle_size = atoi(need(i));
+        else if (a == "--stereo_speckle_diff") stereo_speckle_diff = atoi(need(i));
+        else if (a == "--filter_disparity") {
+            if (i + 1 >= argc || string(argv[i + 1]).rfind("--", 0) == 0)
+                throw runtime_error("missing argument: --filter_disparity needs in.png");
+            filter_disparity_png = argv[++i];
+            run3d_reconstruction = false;
+        }
         else if (a == "--gpu_keypoints") gpu_keypoints = true;
         else if (a == "--orb_n_features") orb_n_features = atoi(need(i));
         else if (a == "--orb_levels") orb_levels = atoi(need(i));
@@ -606,6 +621,11 @@ int Pose::parseCmdArgs(int argc, char** argv)
         if (reference_fanout) throw runtime_error("--gpu_disparity is not available with --reference_fanout");
         if (use_segment_labels) throw runtime_error("--gpu_disparity is not available with --use_segment_labels");
         if (rightImagePrefix.empty()) throw runtime_error("--gpu_disparity needs --right_image_dir d/");
+    }
+    if (!filter_disparity_png.empty()) {
+        if (!disparity_filter_on())
+            throw runtime_error("--filter_disparity needs a filter: give --stereo_median 3|5 and / or --stereo_speckle_size n");
+        if (!ifstream(filter_disparity_png)) throw runtime_error("could not read " + filter_disparity_png);
     }
     if (refine_poses && !feature_poses) throw runtime_error("--refine_poses refines the poses of --feature_poses: give both");
     if (run3d_reconstruction && feature_poses) {
@@ -878,14 +898,52 @@ void Pose::run_stereo_disparity()
     chk(o3dr_stereo_disparity(c, left.data.data(), right.data.data(), 0, left.pitch(), left.rows, left.cols, 1, &prm, disp.data(), nullptr,
                               nullptr, nullptr, O3DR_MEM_HOST),
         "o3dr_stereo_disparity");
+    o3dr_disparity_filter_info info = {};
+    if (disparity_filter_on()) filter_disparities(c, disp, left.rows, left.cols, 1, &info);
     const double ms = chrono::duration<double, milli>(chrono::steady_clock::now() - t0).count();
     size_t accepted = 0;
     for (uint8_t d : disp) accepted += d != 0;
     cout << "pair " << left.rows << " x " << left.cols << ", disparities " << prm.min_disparity << ".." << prm.min_disparity + prm.n_disparities - 1
-         << ", accepted " << accepted << " of " << disp.size() << " pixels, " << ms << " ms" << endl;
+         << ", accepted " << accepted << " of " << disp.size() << " pixels";
+    if (stereo_speckle_size > 0) cout << ", removed " << info.n_removed << " pixels in " << info.n_speckles << " speckles";
+    cout << ", " << ms << " ms" << endl;
     const string outp = stereo_left_png + ".disparity.png";
     if (!write_png_grey8(outp, disp.data(), left.rows, left.cols)) throw runtime_error("could not write " + outp);
     cerr << "Saved the disparity image to " << outp << endl;
+}
+
+void Pose::filter_disparities(o3dr_ctx* c, vector<uint8_t>& disp, int rows, int cols, int n_frames, o3dr_disparity_filter_info* info)
+{
+    o3dr_disparity_filter_params prm;
+    o3dr_disparity_filter_default_params(&prm);
+    prm.median_size = stereo_median;
+    prm.max_speckle_size = stereo_speckle_size;
+    prm.max_diff = stereo_speckle_diff;
+    const size_t n = (size_t)rows * cols;
+    vector<uint8_t> out(n * (size_t)n_frames);
+    chk(o3dr_disparity_filter(c, disp.data(), (int64_t)n, cols, rows, cols, n_frames, &prm, out.data(), nullptr, nullptr, info, O3DR_MEM_HOST),
+        "o3dr_disparity_filter");
+    copy(out.begin(), out.end(), disp.begin());
+}
+
+// The filter alone on an 8-bit grey PNG (contract: include/o3dr.h "disparity filter"), written as <in>.filtered.png.
+void Pose::run_filter_disparity()
+{
+    Q = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // the tool needs no camera
+    const Image8 in = read_png(filter_disparity_png, true);
+    if (in.empty() || in.channels != 1) throw runtime_error("could not read " + filter_disparity_png + " as an 8-bit grey PNG");
+    vector<uint8_t> disp(in.data.begin(), in.data.begin() + (long)((size_t)in.rows * in.cols));
+    o3dr_ctx* c = ctx_for_this_thread();
+    o3dr_disparity_filter_info info = {};
+    const auto t0 = chrono::steady_clock::now();
+    filter_disparities(c, disp, in.rows, in.cols, 1, &info);
+    const double ms = chrono::duration<double, milli>(chrono::steady_clock::now() - t0).count();
+    cout << "image " << in.rows << " x " << in.cols << ", " << info.n_valid << " valid pixels in " << info.n_components
+         << " components (largest " << info.largest << "), removed " << info.n_removed << " pixels in " << info.n_speckles << " speckles, "
+         << ms << " ms" << endl;
+    const string outp = filter_disparity_png + ".filtered.png";
+    if (!write_png_grey8(outp, disp.data(), in.rows, in.cols)) throw runtime_error("could not write " + outp);
+    cerr << "Saved the filtered image to " << outp << endl;
 }
 
 // --gpu_disparity: where the disparity PNGs would have been read, every raw frame with a readable pair gets its disparity
@@ -916,6 +974,7 @@ void Pose::compute_gpu_disparities()
         chk(o3dr_stereo_disparity(c, left.data(), right.data(), (int64_t)(n * 3), 3 * (int64_t)pcols, prows, pcols, (int32_t)(k1 - k0), &prm,
                                   disp.data(), nullptr, nullptr, nullptr, O3DR_MEM_HOST),
             "o3dr_stereo_disparity");
+        if (disparity_filter_on()) filter_disparities(c, disp, prows, pcols, (int)(k1 - k0), nullptr);  // (disp's first k1 - k0 frames)
         for (size_t k = k0; k < k1; ++k) {
             Image8& d = todo[k]->disparity_image;
             d.rows = prows, d.cols = pcols, d.channels = 1;
@@ -923,7 +982,8 @@ void Pose::compute_gpu_disparities()
             todo[k]->right_image = Image8();
         }
     }
-    cout << "--gpu_disparity: " << todo.size() << " disparity images from o3dr_stereo_disparity" << endl;
+    cout << "--gpu_disparity: " << todo.size() << " disparity images from o3dr_stereo_disparity"
+         << (disparity_filter_on() ? ", filtered by o3dr_disparity_filter" : "") << endl;
 }
 
 // pose.cpp:23-565 restricted to the hot path
@@ -964,6 +1024,10 @@ Pose::Pose(int argc, char* argv[])
     }
     if (!stereo_left_png.empty()) {
         run_stereo_disparity();
+        return;
+    }
+    if (!filter_disparity_png.empty()) {
+        run_filter_disparity();
         return;
     }
     if (!print_label_png.empty()) {  // what read_png_labels makes of one file: "rows cols", then one row of labels per line
