@@ -803,12 +803,75 @@ int  o3dr_orb_detect(o3dr_ctx* ctx, const uint8_t* img, int64_t frame_stride, in
                      int32_t n_frames, const o3dr_orb_params* p, o3dr_orb_keypoint* kp, float* kp_xy, uint8_t* desc,
                      int64_t* offsets, uint8_t* levels_out, int64_t out_capacity, int64_t* n_out, int32_t mem);
 
+/* ---- stereo rectification: what stands between the camera and o3dr_stereo_disparity (OpenCV's initUndistortRectifyMap,
+ * then cv::remap with INTER_LINEAR and a constant border).  The reference reads rectified images, so there is nothing of
+ * its to pin: the contract below is this library's own; the map is a fixed sequence of correctly rounded fp64 operations
+ * (+ - * / and floor, never fused, no reciprocal approximation), the remap is integer arithmetic, so results are
+ * bit-identical across calls, frame batchings and memory kinds; tests/rectify_reference.py restates both in numpy.
+ * Not included: stereoRectify itself (R1 / R2 / P1 / P2 from R and T come from the calibration file), the fisheye and the
+ * thin-prism / tilt models, and masking the disparity image with `valid`.
+ *
+ * o3dr_rectify_maps - the fixed-point map of one camera.  On the host, in fp64 and in this order:
+ *   1. A[i][j] = (P[4i] R[j] + P[4i+1] R[3+j]) + P[4i+2] R[6+j]      (A = the left 3x3 of P, times R)
+ *   2. the cofactors, each a difference of two products:
+ *      c00 = A11 A22 - A12 A21   c01 = A12 A20 - A10 A22   c02 = A10 A21 - A11 A20
+ *      c10 = A02 A21 - A01 A22   c11 = A00 A22 - A02 A20   c12 = A01 A20 - A00 A21
+ *      c20 = A01 A12 - A02 A11   c21 = A02 A10 - A00 A12   c22 = A00 A11 - A01 A10
+ *   3. det = (A00 c00 + A01 c01) + A02 c02
+ *   4. I[i][j] = c[j][i] / det                                       (I = the inverse of A)
+ * In the kernel, per destination pixel (u = column, v = row, both converted to double), with fx = K[0], cx = K[2],
+ * fy = K[4], cy = K[5] and D = k1 k2 p1 p2 k3 k4 k5 k6, in fp64 and in this order:
+ *      X = (I00 u + I01 v) + I02;  Y = (I10 u + I11 v) + I12;  Wc = (I20 u + I21 v) + I22
+ *      iw = 1.0 / Wc;  x = X iw;  y = Y iw
+ *      x2 = x x;  y2 = y y;  r2 = x2 + y2;  xy2 = 2.0 (x y)
+ *      num = 1.0 + ((k3 r2 + k2) r2 + k1) r2;  den = 1.0 + ((k6 r2 + k5) r2 + k4) r2;  kr = num / den
+ *      xd = (x kr + p1 xy2) + p2 (r2 + 2.0 x2);  yd = (y kr + p1 (r2 + 2.0 y2)) + p2 xy2
+ *      mx = fx xd + cx;  my = fy yd + cy
+ *      qx = floor(mx 32.0 + 0.5);  qy = floor(my 32.0 + 0.5)
+ * If both qx and qy satisfy -1048576.0 <= q < 1048576.0 (a NaN does not) the pixel stores (int32 qx, int32 qy), else
+ * (O3DR_RECTIFY_OUTSIDE, O3DR_RECTIFY_OUTSIDE).  The map is Q5 fixed point (five fractional bits, OpenCV's INTER_BITS);
+ * its limits do not depend on the source image's size.  `map`: [rows_out][cols_out][2] int32, in `mem`, 4-byte aligned;
+ * with O3DR_MEM_HOST it is computed on the device and copied out.  Limits, else O3DR_ERR_INVALID_ARG before any device
+ * work (a host map zeroed where rows_out and cols_out are within their limits): rows_out and cols_out in 1..8192; every
+ * entry of `cam` finite; K[1], K[3], K[6], K[7] zero and K[8] one; det finite and not zero.  One launch; the stream is
+ * synchronised once, at the end.
+ *
+ * o3dr_rectify_remap - n_frames images (rows x cols, channels = 1 or 3 interleaved, byte `pitch` and `frame_stride`)
+ * through one map (rows_out x cols_out), all integer.  Per destination pixel with map entry (qx, qy):
+ *   x0 = qx >> 5 (arithmetic shift: floor), ax = qx & 31; y0 and ay likewise.  The taps (x0, y0), (x0 + 1, y0),
+ *   (x0, y0 + 1), (x0 + 1, y0 + 1) weigh (32 - ax)(32 - ay), ax (32 - ay), (32 - ax) ay, ax ay (their sum is 1024).  A tap
+ *   outside [0, cols) x [0, rows) reads `border` in every channel.  Per channel out = (sum of w t + 512) >> 10.
+ *   valid = 1 iff every tap of non-zero weight is inside, else 0: a sentinel entry gives `border` and 0.
+ * src, map, out ([n_frames][rows_out][cols_out][channels], tight) and valid_out (optional, [rows_out][cols_out], one per
+ * map: it does not depend on the frame) are all in `mem`; out must not overlap src; map 4-byte aligned.  Limits, else
+ * O3DR_ERR_INVALID_ARG before any device work (host outputs zeroed wherever the sizes that give their extent are within
+ * their limits): rows, cols, rows_out, cols_out in 1..8192; channels 1 or 3; border in 0..255; group_frames >= 0;
+ * pitch >= cols * channels; frame_stride >= rows * pitch when n_frames > 1; n_frames >= 0 (0: O3DR_OK, nothing is
+ * touched).  pitch and frame_stride have no upper limit: with O3DR_MEM_HOST the images are staged as frame_stride *
+ * (n_frames - 1) + pitch * (rows - 1) + cols * channels bytes, and a stride too large for that returns O3DR_ERR_ALLOC
+ * (host outputs zeroed).  group_frames = n > 0 caps the frames one launch takes (default: all of them); results do not
+ * depend on it.  One launch per group, whatever the content; the map is read once per launch, not once per frame;
+ * valid_out is written by the first launch alone and only when asked for.  The stream is synchronised once, at the end. */
+#define O3DR_RECTIFY_MAX_SIDE 8192
+#define O3DR_RECTIFY_OUTSIDE (-1048576)   /* -32768 * 32 */
+typedef struct o3dr_rectify_camera {
+    double K[9];   /* source camera matrix, row-major: K[0]=fx K[2]=cx K[4]=fy K[5]=cy; K[1],K[3],K[6],K[7] must be 0, K[8] 1 */
+    double D[8];   /* k1 k2 p1 p2 k3 k4 k5 k6 (OpenCV's order); unused ones 0 */
+    double R[9];   /* rectifying rotation (OpenCV R1 / R2), row-major */
+    double P[12];  /* new projection (OpenCV P1 / P2), row-major 3x4; only its left 3x3 is used */
+} o3dr_rectify_camera;
+int  o3dr_rectify_maps(o3dr_ctx* ctx, const o3dr_rectify_camera* cam, int32_t rows_out, int32_t cols_out, int32_t* map, int32_t mem);
+int  o3dr_rectify_remap(o3dr_ctx* ctx, const uint8_t* src, int64_t frame_stride, int64_t pitch, int32_t rows, int32_t cols,
+                        int32_t channels, int32_t n_frames, const int32_t* map, int32_t rows_out, int32_t cols_out, int32_t border,
+                        int32_t group_frames, uint8_t* out, uint8_t* valid_out, int32_t mem);
+
 /* ---- stereo disparity: the 8-bit disparity image every frame call starts from, made here from a rectified pair by
  * census-transform semi-global matching.  The reference reads its disparities as files an offline matcher wrote (SURVEY
  * section 2), so there is nothing of its to pin: the contract below is this library's own; every step is an exact
  * integer computation, so results are bit-identical across calls, frame batchings and memory kinds;
  * tests/stereo_reference.py restates it in numpy.  Median and speckle filtering are a call of their own
- * (o3dr_disparity_filter, below).  Not included: an adaptive P2, and rectification itself - the pair must arrive rectified.
+ * (o3dr_disparity_filter, below).  Not included: an adaptive P2.  The pair must arrive rectified: o3dr_rectify_maps and
+ * o3dr_rectify_remap ("stereo rectification", below) make it so from the raw images and the calibration.
  *
  * Input: `left` and `right`, n_frames images each of rows x cols pixels (1..8192 each), byte `pitch` and byte
  * `frame_stride` (the same for both), channels = 3 (interleaved B, G, R) or 1 (grey), both in `mem`.  W = cols, H = rows,
@@ -1189,7 +1252,9 @@ int  o3dr_pose_graph_refine(o3dr_ctx* ctx, const uint8_t* desc, const int64_t* o
 #define O3DR_K_DISP_MEDIAN  25  /* disparity filter: the k x k median */
 #define O3DR_K_DISP_LABEL   26  /* ... components: tile labelling in LDS, border merge, flatten + sizes */
 #define O3DR_K_DISP_SPECKLE 27  /* ... removal of the small components and the per-frame counts */
-#define O3DR_K_NUM          28
+#define O3DR_K_RECTIFY_MAPS  28  /* stereo rectification: the Q5 map of one camera, one thread per pixel */
+#define O3DR_K_RECTIFY_REMAP 29  /* ... the bilinear remap of a group of frames through one map */
+#define O3DR_K_NUM          30
 /* Bracket every launch of kernel `kernel_id` (or all kernels if -1) with HIP events on the
  * context's stream; 0 launches are bracketed when disabled (the default). */
 int o3dr_profile_enable(o3dr_ctx* ctx, int32_t kernel_id, int32_t enable);

@@ -22,11 +22,12 @@ K_MATCH, K_POSE_CHAIN, K_RANSAC = 17, 18, 19
 K_GRAPH_MOMENTS, K_GRAPH_SOLVE = 20, 21
 K_STEREO_CENSUS, K_STEREO_PATHS, K_STEREO_WINNER = 22, 23, 24
 K_DISP_MEDIAN, K_DISP_LABEL, K_DISP_SPECKLE = 25, 26, 27
+K_RECTIFY_MAPS, K_RECTIFY_REMAP = 28, 29
 KERNEL_NAMES = ["reproject_count", "reproject_emit", "voxel_keys", "radix_hist", "radix_scatter", "run_segments",
                 "centroid", "other", "centroid_runs", "plane_disp_sums", "plane_disp_fit", "plane_disp_eval",
                 "orb_pyramid", "orb_fast", "orb_candidates", "orb_select", "orb_describe", "match", "pose_chain", "ransac",
                 "graph_moments", "graph_solve", "stereo_census", "stereo_paths", "stereo_winner", "disp_median", "disp_label",
-                "disp_speckle"]
+                "disp_speckle", "rectify_maps", "rectify_remap"]
 
 
 class O3drError(RuntimeError):
@@ -133,6 +134,14 @@ class DisparityFilterInfoStruct(C.Structure):
 
 
 DISPARITY_FILTER_MAX_SIDE = 8192
+
+
+class RectifyCameraStruct(C.Structure):
+    _fields_ = [("K", C.c_double * 9), ("D", C.c_double * 8), ("R", C.c_double * 9), ("P", C.c_double * 12)]
+
+
+RECTIFY_MAX_SIDE = 8192
+RECTIFY_OUTSIDE = -1048576
 
 
 class MatchParamsStruct(C.Structure):
@@ -287,6 +296,8 @@ SYMBOLS = [
     ("o3dr_disparity_filter_default_params", None, [C.POINTER(DisparityFilterParamsStruct)]),
     ("o3dr_disparity_filter", C.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, C.POINTER(DisparityFilterParamsStruct), _vp, _vp, _vp,
                                         _vp, _i32]),
+    ("o3dr_rectify_maps", C.c_int, [_vp, C.POINTER(RectifyCameraStruct), _i32, _i32, _vp, _i32]),
+    ("o3dr_rectify_remap", C.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32]),
     ("o3dr_chain_default_params", None, [C.POINTER(ChainParamsStruct)]),
     ("o3dr_pose_chain", C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, C.POINTER(ChainParamsStruct), _vp, _vp, _vp, _i64,
                                   _pi64, _i32]),

@@ -120,6 +120,16 @@ def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
 
+def rectifiedQ(P1, P2):
+    """The 4 x 4 disparity-to-depth matrix Q (what set_camera takes) of a rectified pair from its two projections (3 x 4,
+    OpenCV's P1 / P2), by stereoRectify's formula: Tx = P2[0][3] / P2[0][0]; rows [1, 0, 0, -cx1], [0, 1, 0, -cy1],
+    [0, 0, 0, f], [0, 0, -1 / Tx, (cx1 - cx2) / Tx].  Host only."""
+    P1, P2 = np.asarray(P1, np.float64).reshape(3, 4), np.asarray(P2, np.float64).reshape(3, 4)
+    f, cx1, cy1, cx2 = P1[0, 0], P1[0, 2], P1[1, 2], P2[0, 2]
+    Tx = P2[0, 3] / P2[0, 0]
+    return np.array([[1.0, 0.0, 0.0, -cx1], [0.0, 1.0, 0.0, -cy1], [0.0, 0.0, 0.0, f], [0.0, 0.0, -1.0 / Tx, (cx1 - cx2) / Tx]])
+
+
 def _ptr(x):
     """(address, MEM kind, keepalive) of a numpy array or a torch tensor."""
     if _is_torch(x):
@@ -608,10 +618,94 @@ class Context:
         res = (kp[:k], xy[:k], desc[:k], off)
         return res + (lev[:n_lev],) if return_levels else res
 
+    # -- stereo rectification (initUndistortRectifyMap + remap: what makes the pair the matcher takes) -------------------------
+    def rectifyMaps(self, K, D, R, P, size, device=None):
+        """The Q5 fixed-point undistort-rectify map of one camera (contract: include/o3dr.h "stereo rectification").  K: the
+        3 x 3 camera matrix; D: 4, 5 or 8 distortion coefficients in OpenCV's order (zero-padded); R: the rectifying
+        rotation (R1 / R2); P: the new projection (P1 / P2), 3 x 4 or 3 x 3; size = (rows_out, cols_out).  -> int32
+        [rows_out, cols_out, 2] = (qx, qy), RECTIFY_OUTSIDE in both where the source position is out of the map's range;
+        numpy, or with device= a torch CUDA tensor."""
+        K = np.asarray(K, np.float64).reshape(3, 3)
+        D = np.asarray(D, np.float64).reshape(-1)
+        assert D.size in (4, 5, 8), "D must have 4, 5 or 8 entries"
+        R = np.asarray(R, np.float64).reshape(3, 3)
+        P = np.asarray(P, np.float64)
+        assert P.shape in ((3, 4), (3, 3))
+        P34 = np.zeros((3, 4))
+        P34[:, :P.shape[1]] = P
+        cam = L.RectifyCameraStruct()
+        cam.K[:] = K.reshape(-1).tolist()
+        cam.D[:] = D.tolist() + [0.0] * (8 - D.size)
+        cam.R[:] = R.reshape(-1).tolist()
+        cam.P[:] = P34.reshape(-1).tolist()
+        rows_out, cols_out = int(size[0]), int(size[1])
+        shape = (max(rows_out, 0), max(cols_out, 0), 2)
+        if device is not None:
+            import torch
+            maps = torch.empty(shape, dtype=torch.int32, device=device)
+            self._order_after_torch()
+            L.check(self._lib.o3dr_rectify_maps(self._h, C.byref(cam), rows_out, cols_out, maps.data_ptr(), L.MEM_DEVICE))
+        else:
+            maps = np.empty(shape, np.int32)
+            L.check(self._lib.o3dr_rectify_maps(self._h, C.byref(cam), rows_out, cols_out, maps.ctypes.data, L.MEM_HOST))
+        return maps
+
+    def rectify(self, img, maps, border=0, return_valid=False, group_frames=0):
+        """Bilinear remap of img through one rectifyMaps result (contract: include/o3dr.h "stereo rectification").  img: uint8
+        [H, W] or [F, H, W] grey, [H, W, 3] or [F, H, W, 3] B G R (a 3-D input whose last axis is 3 is one B G R image, as in
+        stereoDisparity); a padded pitch or frame stride passes through.  maps: int32 [H_out, W_out, 2], of img's memory
+        kind: numpy in gives numpy out, torch CUDA tensors in give CUDA tensors out and nothing leaves HBM.  -> the uint8
+        image(s) of the map's size; a tap outside the source reads `border`.  return_valid: a uint8 [H_out, W_out] image
+        follows, 1 where every tap of non-zero weight is inside the source.  group_frames: at most that many frames per
+        launch; results do not depend on it."""
+        dev = _is_torch(img)
+        if dev != _is_torch(maps):
+            raise L.O3drError(L.ERR_INVALID_ARG, "maps must be of the same memory kind as img")
+        nd = img.dim() if dev else np.ndim(img)
+        ch = 3 if (nd == 4 or (nd == 3 and int(img.shape[-1]) == 3)) else 1
+        single = nd == (3 if ch == 3 else 2)
+        assert nd in ((3, 4) if ch == 3 else (2, 3))
+        F = 1 if single else int(img.shape[0])
+        rows, cols = (int(img.shape[-3]), int(img.shape[-2])) if ch == 3 else (int(img.shape[-2]), int(img.shape[-1]))
+        row_axis = -3 if ch == 3 else -2
+        assert len(maps.shape) == 3 and int(maps.shape[2]) == 2
+        rows_out, cols_out = int(maps.shape[0]), int(maps.shape[1])
+        if dev:
+            import torch
+            assert img.is_cuda and maps.is_cuda and img.dtype == torch.uint8 and maps.dtype == torch.int32
+            if not (img.stride(-1) == 1 and (ch == 1 or img.stride(-2) == 3) and img.stride(row_axis) >= cols * ch and
+                    (single or img.stride(0) >= rows * img.stride(row_axis))):
+                img = img.contiguous()
+            maps = maps.contiguous()
+            pitch, fs = int(img.stride(row_axis)), (0 if single else int(img.stride(0)))
+            mem, pi, pm = L.MEM_DEVICE, img.data_ptr(), maps.data_ptr()
+        else:
+            img = np.asarray(img)
+            assert img.dtype == np.uint8
+            st = img.strides
+            if not (st[-1] == 1 and (ch == 1 or st[-2] == 3) and st[row_axis] >= cols * ch and (single or st[0] >= rows * st[row_axis])):
+                img = np.ascontiguousarray(img)  # (a padded pitch or frame stride is passed through as it is)
+            maps = np.ascontiguousarray(maps, np.int32)
+            pitch, fs = int(img.strides[row_axis]), (0 if single else int(img.strides[0]))
+            mem, pi, pm = L.MEM_HOST, img.ctypes.data, maps.ctypes.data
+        shape = (() if single else (F,)) + (rows_out, cols_out) + ((3,) if ch == 3 else ())
+        if dev:
+            out = torch.empty(shape, dtype=torch.uint8, device=img.device)
+            valid = torch.empty((rows_out, cols_out), dtype=torch.uint8, device=img.device) if return_valid else None
+            self._order_after_torch()
+            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        else:
+            out = np.empty(shape, np.uint8)
+            valid = np.empty((rows_out, cols_out), np.uint8) if return_valid else None
+            ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        L.check(self._lib.o3dr_rectify_remap(self._h, pi, fs, pitch, rows, cols, ch, F, pm, rows_out, cols_out, int(border),
+                                             int(group_frames), ptr(out), ptr(valid), mem))
+        return (out, valid) if return_valid else out
+
     # -- stereo disparity (the image every frame call starts from; the reference reads it from files) ----------------------
     def stereoDisparity(self, left, right, n_disparities=256, min_disparity=0, p1=10, p2=120, n_paths=8, uniqueness=10,
                         lr_max_diff=1, subpixel=False, return_cost=False, return_volume=False, group_frames=0, median=0,
-                        speckle_size=0, speckle_diff=1):
+                        speckle_size=0, speckle_diff=1, rectify=None):
         """Census-transform semi-global matching of a rectified pair (contract: include/o3dr.h "stereo disparity").  left /
         right: uint8 [H, W] or [F, H, W] grey, [H, W, 3] or [F, H, W, 3] B G R, same shape; numpy, or torch CUDA tensors (the
         outputs are then CUDA tensors and nothing leaves HBM).  A 3-D input whose last axis is 3 is taken as one B G R image
@@ -621,7 +715,13 @@ class Context:
         (uint16) follows; return_volume: S itself (uint16 [..., H, W, D]) follows that.  group_frames: at most that many frames
         per launch group (0: as many as the scratch budget allows); results do not depend on it.  median (0, 3, 5) /
         speckle_size > 0: the image to be returned goes through filterDisparity first - disp with max_diff = speckle_diff,
-        under subpixel=True disp_q4 with max_diff = 16 * speckle_diff before the division; cost and volume stay as they are."""
+        under subpixel=True disp_q4 with max_diff = 16 * speckle_diff before the division; cost and volume stay as they are.
+        rectify=(maps_left, maps_right), two rectifyMaps results of one size: both inputs go through rectify() first and
+        everything is computed on the rectified pair."""
+        if rectify is not None:
+            ml, mr = rectify
+            assert tuple(ml.shape) == tuple(mr.shape), "the two rectification maps must have one size"
+            left, right = self.rectify(left, ml, group_frames=group_frames), self.rectify(right, mr, group_frames=group_frames)
         dev = _is_torch(left)
         assert dev == _is_torch(right) and tuple(left.shape) == tuple(right.shape)
         nd = left.dim() if dev else np.ndim(left)

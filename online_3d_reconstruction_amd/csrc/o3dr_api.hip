@@ -148,6 +148,7 @@ struct o3dr_ctx {
     int64_t test_orb_scratch = 0;   // o3dr_test_orb_scratch_limit: stands in for kOrbScratchBytes when positive
     DevBuf stereo_work;        // o3dr_stereo_disparity: its own scratch block (one carve per call)
     DevBuf dfilter_work;       // o3dr_disparity_filter: its own scratch block (one carve per call)
+    DevBuf rect_work;          // o3dr_rectify_remap: the staged host map (one carve per call)
     DevBuf pl_hyp;             // o3dr_segment_plane: hypotheses + scores (plane_hyp_layout), kept for the test hook
     uint64_t pl_last_hyp = 0;  // hypotheses of the last call in pl_hyp (o3dr_test_plane_hypotheses)
     std::vector<MatchPair> mt_tab_h;  // host copies of the match pair table, the rigid fit's segment table and transforms
@@ -475,7 +476,7 @@ extern "C" int o3dr_ctx_destroy(o3dr_ctx* c)
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     for (DevBuf* b : {&c->inc.box, &c->inc.scratch, &c->inc.tg, &c->inc.tmatch, &c->inc.flag, &c->inc.src, &c->inc.keep,
-                      &c->inc.partial, &c->inc.words, &c->inc.fb, &c->nn_q, &c->nn_t, &c->nn_cells, &c->nn_src, &c->pl_hyp, &c->orb_work, &c->orb_pat, &c->stereo_work, &c->dfilter_work})
+                      &c->inc.partial, &c->inc.words, &c->inc.fb, &c->nn_q, &c->nn_t, &c->nn_cells, &c->nn_src, &c->pl_hyp, &c->orb_work, &c->orb_pat, &c->stereo_work, &c->dfilter_work, &c->rect_work})
         dev_release(*b);
     for (DevBuf& b : c->op) dev_release(b);
     delete c;
@@ -5081,6 +5082,137 @@ extern "C" int o3dr_disparity_filter(o3dr_ctx* c, const void* disp, int64_t fram
         outs.zero();
         if (info && px > 0) memset(info, 0, sizeof(o3dr_disparity_filter_info) * (size_t)n_frames);
     }
+    return rc;
+}
+
+// =================================================================================================
+// stereo rectification (kernels/rectify.inc; DESIGN.md "Stereo rectification")
+// =================================================================================================
+static bool rect_side_ok(int32_t v) { return v >= 1 && v <= O3DR_RECTIFY_MAX_SIDE; }
+
+static int rectify_maps(o3dr_ctx* c, const o3dr_rectify_camera* cam, int32_t rows_out, int32_t cols_out, int32_t* map, Outputs& outs,
+                        int32_t mem)
+{
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    if (!rect_side_ok(rows_out) || !rect_side_ok(cols_out)) return fail(O3DR_ERR_INVALID_ARG, "rows_out and cols_out must be in 1..8192");
+    if (!cam || !map) return fail(O3DR_ERR_INVALID_ARG, "cam / map is NULL");
+    if ((uintptr_t)map % 4) return fail(O3DR_ERR_INVALID_ARG, "map must be 4-byte aligned");
+    {
+        const double* v = cam->K;  // K, D, R, P lie one after the other: 38 doubles
+        static_assert(sizeof(o3dr_rectify_camera) == 38 * sizeof(double), "o3dr_rectify_camera is 38 doubles");
+        for (int i = 0; i < 38; ++i)
+            if (!std::isfinite(v[i])) return fail(O3DR_ERR_INVALID_ARG, "a non-finite entry in the camera");
+    }
+    const double *K = cam->K, *R = cam->R, *P = cam->P;
+    if (K[1] != 0.0 || K[3] != 0.0 || K[6] != 0.0 || K[7] != 0.0 || K[8] != 1.0)
+        return fail(O3DR_ERR_INVALID_ARG, "K must be [fx 0 cx; 0 fy cy; 0 0 1]");
+    // the contract's host part, operation for operation (this file is built with -ffp-contract=off)
+    double A[3][3], cf[3][3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) A[i][j] = (P[4 * i] * R[j] + P[4 * i + 1] * R[3 + j]) + P[4 * i + 2] * R[6 + j];
+    cf[0][0] = A[1][1] * A[2][2] - A[1][2] * A[2][1];
+    cf[0][1] = A[1][2] * A[2][0] - A[1][0] * A[2][2];
+    cf[0][2] = A[1][0] * A[2][1] - A[1][1] * A[2][0];
+    cf[1][0] = A[0][2] * A[2][1] - A[0][1] * A[2][2];
+    cf[1][1] = A[0][0] * A[2][2] - A[0][2] * A[2][0];
+    cf[1][2] = A[0][1] * A[2][0] - A[0][0] * A[2][1];
+    cf[2][0] = A[0][1] * A[1][2] - A[0][2] * A[1][1];
+    cf[2][1] = A[0][2] * A[1][0] - A[0][0] * A[1][2];
+    cf[2][2] = A[0][0] * A[1][1] - A[0][1] * A[1][0];
+    const double det = (A[0][0] * cf[0][0] + A[0][1] * cf[0][1]) + A[0][2] * cf[0][2];
+    if (det == 0.0 || !std::isfinite(det)) return fail(O3DR_ERR_INVALID_ARG, "P R is singular");
+    RectMapArgs a;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) a.I[3 * i + j] = cf[j][i] / det;
+    for (int i = 0; i < 8; ++i) a.k[i] = cam->D[i];
+    a.fx = K[0], a.cx = K[2], a.fy = K[4], a.cy = K[5];
+    a.rows_out = rows_out, a.cols_out = cols_out;
+    CHK(outs.stage(c));
+    a.map = outs.dev(map);
+    launch_rectify_maps(&c->prof, c->stream, a);
+    HIPCHK(hipGetLastError());
+    CHK(outs.copy_back(c));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_rectify_maps(o3dr_ctx* c, const o3dr_rectify_camera* cam, int32_t rows_out, int32_t cols_out, int32_t* map, int32_t mem)
+{
+    Outputs outs{mem};
+    outs.add(map, rect_side_ok(rows_out) && rect_side_ok(cols_out) ? (int64_t)rows_out * cols_out * 2 : 0);
+    const int rc = entered(c, [&] { return rectify_maps(c, cam, rows_out, cols_out, map, outs, mem); });
+    if (rc != O3DR_OK) outs.zero();
+    return rc;
+}
+
+static int rectify_remap(o3dr_ctx* c, const uint8_t* src, int64_t fs, int64_t pitch, int32_t rows, int32_t cols, int32_t channels,
+                         int32_t n_frames, const int32_t* map, int32_t rows_out, int32_t cols_out, int32_t border, int32_t group_frames,
+                         uint8_t* out, uint8_t* valid_out, Outputs& outs, int32_t mem)
+{
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    if (n_frames < 0) return fail(O3DR_ERR_INVALID_ARG, "bad frame count");
+    if (!rect_side_ok(rows) || !rect_side_ok(cols) || !rect_side_ok(rows_out) || !rect_side_ok(cols_out))
+        return fail(O3DR_ERR_INVALID_ARG, "rows, cols, rows_out and cols_out must be in 1..8192");
+    if (channels != 1 && channels != 3) return fail(O3DR_ERR_INVALID_ARG, "channels must be 1 or 3");
+    if (border < 0 || border > 255) return fail(O3DR_ERR_INVALID_ARG, "border must be in 0..255");
+    if (group_frames < 0) return fail(O3DR_ERR_INVALID_ARG, "group_frames is negative");
+    if (n_frames == 0) return O3DR_OK;
+    if (!src || !map || !out) return fail(O3DR_ERR_INVALID_ARG, "src / map / out is NULL");
+    if ((uintptr_t)map % 4) return fail(O3DR_ERR_INVALID_ARG, "map must be 4-byte aligned");
+    if (pitch < (int64_t)cols * channels) return fail(O3DR_ERR_INVALID_ARG, "pitch smaller than a row");
+    if (n_frames > 1 && fs < (int64_t)rows * pitch) return fail(O3DR_ERR_INVALID_ARG, "frame stride smaller than a frame");
+    const size_t n_out = (size_t)rows_out * (size_t)cols_out;
+    const size_t in_bytes = (size_t)fs * (size_t)(n_frames - 1) + (size_t)pitch * (size_t)(rows - 1) + (size_t)cols * (size_t)channels;
+    {  // the byte ranges [src, src + in_bytes) and [out, out + n_frames * rows_out * cols_out * channels), in either memory kind
+        const uintptr_t i0 = (uintptr_t)src, o0 = (uintptr_t)out;
+        if (i0 < o0 + (uintptr_t)n_frames * n_out * (uintptr_t)channels && o0 < i0 + in_bytes)
+            return fail(O3DR_ERR_INVALID_ARG, "out must not overlap src");
+    }
+    RectArgs a;
+    memset(&a, 0, sizeof a);
+    a.rows = rows, a.cols = cols, a.channels = channels, a.rows_out = rows_out, a.cols_out = cols_out, a.border = border;
+    a.fstride = fs, a.pitch = pitch;
+    const void* src_d;
+    CHK(stage_in(c, c->op[o3dr_ctx::OP_IN], src, in_bytes, mem, &src_d));
+    a.map = map;
+    if (mem == O3DR_MEM_HOST) {
+        int32_t* map_d = nullptr;
+        CHK(carve(c, c->rect_work, [&](Carve& w) { w.take(map_d, n_out * 2); }));
+        HIPCHK(hipMemcpyAsync(map_d, map, n_out * 2 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        a.map = map_d;
+    }
+    CHK(outs.stage(c));
+    uint8_t* out_d = outs.dev(out);
+    a.valid = outs.dev(valid_out);
+    const size_t group = group_frames > 0 ? std::min<size_t>((size_t)group_frames, (size_t)n_frames) : (size_t)n_frames;
+    for (size_t f0 = 0; f0 < (size_t)n_frames; f0 += group) {
+        a.frames = (int32_t)std::min(group, (size_t)n_frames - f0);
+        a.src = (const uint8_t*)src_d + (int64_t)f0 * fs;
+        a.out = out_d + f0 * n_out * (size_t)channels;
+        launch_rectify_remap(&c->prof, c->stream, a);
+        a.valid = nullptr;  // one per map: the first group has written it
+    }
+    HIPCHK(hipGetLastError());
+    CHK(outs.copy_back(c));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_rectify_remap(o3dr_ctx* c, const uint8_t* src, int64_t frame_stride, int64_t pitch, int32_t rows, int32_t cols,
+                                  int32_t channels, int32_t n_frames, const int32_t* map, int32_t rows_out, int32_t cols_out,
+                                  int32_t border, int32_t group_frames, uint8_t* out, uint8_t* valid_out, int32_t mem)
+{
+    // the outputs' sizes are known only where the sizes that give them are within their limits
+    const bool out_ok = rect_side_ok(rows_out) && rect_side_ok(cols_out);
+    const int64_t px = out_ok ? (int64_t)rows_out * cols_out : 0;
+    Outputs outs{mem};
+    outs.add(out, n_frames > 0 && (channels == 1 || channels == 3) ? px * n_frames * channels : 0);
+    outs.add(valid_out, n_frames > 0 ? px : 0);
+    const int rc = entered(c, [&] {
+        return rectify_remap(c, src, frame_stride, pitch, rows, cols, channels, n_frames, map, rows_out, cols_out, border, group_frames, out,
+                             valid_out, outs, mem);
+    });
+    if (rc != O3DR_OK) outs.zero();
     return rc;
 }
 

@@ -634,6 +634,23 @@ struct DfArgs {
     void* out;
 };
 void launch_disparity_filter(Profiler* pf, hipStream_t s, const DfArgs& a);
+// Stereo rectification (kernels/rectify.inc; contract: include/o3dr.h "stereo rectification").  RectMapArgs: the inverse of
+// P R (host fp64), the camera and the distortion, by value.  RectArgs: one launch group of `frames` frames through one map.
+struct RectMapArgs {
+    double I[9], k[8], fx, fy, cx, cy;
+    int32_t rows_out, cols_out;
+    int32_t* map;
+};
+void launch_rectify_maps(Profiler* pf, hipStream_t s, const RectMapArgs& a);
+struct RectArgs {
+    const uint8_t* src;   // the group's first frame
+    int64_t fstride, pitch;
+    int32_t rows, cols, channels, frames, rows_out, cols_out, border;
+    const int32_t* map;
+    uint8_t* out;         // the group's first frame, tight
+    uint8_t* valid;       // nullptr: not asked for (or already written by an earlier group)
+};
+void launch_rectify_remap(Profiler* pf, hipStream_t s, const RectArgs& a);
 void launch_partition(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelArgs& v, int n_parts, o3dr_point* out,
                       uint64_t* counts_dev, uint32_t* overflow_dev, const void* hdrs_dev = nullptr, int n_hdrs = 0);
 // its two halves: slice sizes without moving anything (the (part, tile) table stays in ws for the second half), then the move

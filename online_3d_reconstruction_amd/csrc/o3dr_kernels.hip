@@ -36,6 +36,7 @@
 //   orb          ORB features: grey pyramid, FAST score + box sums, candidates, exact selection, steered BRIEF
 //   stereo       stereo disparity: grey + census, semi-global aggregation (one wave per scan line), winner + left-right check
 //   disparity_filter  median and speckle removal of a disparity image: LDS median network, tiled union-find labelling
+//   rectify      stereo rectification: the fp64 Q5 map of one camera, the integer bilinear remap of a group of frames
 //   pose_chain   the feature-matched pose chain: one workgroup walks the frames (gather, moments, Kabsch, residual)
 //   ransac       three-point RANSAC for a rigid transform: one workgroup per segment / pair of the chain
 // The launchers follow in this file.
@@ -67,6 +68,7 @@ namespace o3dr {
 #include "kernels/orb.inc"
 #include "kernels/stereo.inc"
 #include "kernels/disparity_filter.inc"
+#include "kernels/rectify.inc"
 #include "kernels/pose_chain.inc"
 #include "kernels/ransac.inc"
 #include "kernels/pose_graph.inc"
@@ -767,6 +769,24 @@ void launch_disparity_filter(Profiler* pf, hipStream_t s, const DfArgs& a)
         disparity_filter_frames<uint8_t>(pf, s, a);
     else
         disparity_filter_frames<uint16_t>(pf, s, a);
+}
+
+// stereo rectification: the map of one camera, then one launch per group of frames; both depend on the sizes alone
+void launch_rectify_maps(Profiler* pf, hipStream_t s, const RectMapArgs& a)
+{
+    ProfScope ps(pf, O3DR_K_RECTIFY_MAPS, s);
+    k_rectify_maps<<<cdiv64((int64_t)a.rows_out * a.cols_out, 256), 256, 0, s>>>(a);
+}
+void launch_rectify_remap(Profiler* pf, hipStream_t s, const RectArgs& a)
+{
+    if (a.frames <= 0) return;
+    ProfScope ps(pf, O3DR_K_RECTIFY_REMAP, s);
+    const int quads_x = cdiv64(a.cols_out, 4);
+    const int blocks = cdiv64((int64_t)a.rows_out * quads_x, 256);
+    if (a.channels == 1)
+        k_rectify_remap<1><<<blocks, 256, 0, s>>>(a, quads_x);
+    else
+        k_rectify_remap<3><<<blocks, 256, 0, s>>>(a, quads_x);
 }
 
 void launch_bbox(Profiler* pf, hipStream_t s, const float* mm, int used, float* out6)

@@ -52,6 +52,8 @@ struct Image16 {                                // one 16-bit channel: a segment
 Image16 read_png_labels(const std::string& path);
 // an 8-bit greyscale PNG (stored deflate blocks: no compression); false if the file cannot be written
 bool write_png_grey8(const std::string& path, const uint8_t* data, int rows, int cols);
+// the same for an 8-bit interleaved B G R image (the file holds R G B, colour type 2)
+bool write_png_bgr8(const std::string& path, const uint8_t* data, int rows, int cols);
 // pcl::io::savePLYFileBinary layout (x,y,z float + r,g,b uchar, then one `camera` element); with normals (4 floats per
 // point: nx ny nz curvature) PointXYZRGBNormal's (the same, then normal_x normal_y normal_z curvature float)
 bool save_ply_binary(const std::string& path, const PointCloud& cloud, const std::vector<float>* normals = nullptr);
@@ -168,6 +170,12 @@ public:
     // --stereo_median 0|3|5, --stereo_speckle_size n, --stereo_speckle_diff n: o3dr_disparity_filter of the disparity image
     // in --stereo_disparity, --gpu_disparity and --filter_disparity; parsed and ignored elsewhere
     int stereo_median = 0, stereo_speckle_size = 0, stereo_speckle_diff = 1;
+    std::string rectify_calib;        // --rectify_calib f: an OpenCV YAML file with M1 (or K1) D1 R1 P1 M2 (or K2) D2 R2 P2.  Every
+                                      // rgb_image (under --gpu_disparity every right_image too) is replaced by its rectified
+                                      // version right after it is read; --stereo_disparity rectifies its pair first
+    std::string rectify_left_png, rectify_right_png;  // --rectify_pair left.png right.png: o3dr_rectify_maps + o3dr_rectify_remap of one
+                                      // pair, written as <left>.rectified.png and <right>.rectified.png
+    int rectify_border = 0;           // --rectify_border b: what a tap outside the source reads (0..255)
     std::string filter_disparity_png;  // --filter_disparity in.png: the filter alone on an 8-bit grey PNG -> <in>.filtered.png
     std::string print_label_png;      // --print_label_png f: rows, cols and the labels of f as text (checks the reader)
 
@@ -207,6 +215,12 @@ private:
     void run_stereo_disparity();                    // --stereo_disparity
     void compute_gpu_disparities();                 // --gpu_disparity: fills every raw frame's disparity_image
     void run_filter_disparity();                    // --filter_disparity
+    void readRectifyCalib();                        // --rectify_calib: fills rectify_cam (no device needed)
+    void run_rectify_pair();                        // --rectify_pair
+    void rectify_raw_images();                      // --rectify_calib in a reconstruction run: replaces the images read
+    // o3dr_rectify_remap of images of one size (3 channels) through camera cam's map (0: left, 1: right) of that size, in
+    // place, one call; n_valid: the map's valid-pixel count, or nullptr
+    void rectify_images(o3dr_ctx* c, int cam, const std::vector<Image8*>& imgs, int64_t* n_valid);
     bool disparity_filter_on() const { return stereo_median != 0 || stereo_speckle_size > 0; }
     // o3dr_disparity_filter of n_frames tight uint8 images in place, with the three flags; info: one per frame, or nullptr
     void filter_disparities(o3dr_ctx* c, std::vector<uint8_t>& disp, int rows, int cols, int n_frames, o3dr_disparity_filter_info* info);
@@ -223,6 +237,11 @@ private:
         std::vector<float> prior, poses;
         std::vector<int32_t> status;
     } chain;
+    o3dr_rectify_camera rectify_cam[2] = {};  // --rectify_calib: the left and the right camera
+    struct RectifyMap {          // a camera's map at the size it was last asked for
+        int rows = 0, cols = 0;
+        std::vector<int32_t> map;
+    } rectify_map[2];
     bool disparity_f64 = false;  // what push_params sets: on around the accumulate call of a plane-fitted batch
     std::vector<std::vector<double>> pose_data, images_times_data;
     std::vector<double> pose_times_seq, images_times_seq;

@@ -2,7 +2,8 @@
 // calls on the hot path's input side (pose_functions.cpp:526 colour, :548 IMREAD_GRAYSCALE).
 // 8-bit, non-interlaced, colour types 0/2/3/4/6 — what the reference's bundled data uses.  read_png_labels reads the
 // segment label images of --use_segment_labels: greyscale, 8 or 16 bits, non-interlaced.  write_png_grey8 writes the
-// disparity image of --stereo_disparity: 8-bit grey, filter 0, stored (uncompressed) deflate blocks.
+// disparity image of --stereo_disparity, write_png_bgr8 the colour images of --rectify_pair: 8 bits a sample, filter 0,
+// stored (uncompressed) deflate blocks.
 #include <zlib.h>
 
 #include <cstdio>
@@ -186,7 +187,7 @@ Image16 read_png_labels(const std::string& path)
     return out;
 }
 
-// 8-bit greyscale writer: every row with filter type 0, the zlib stream made of stored blocks (no compression), so the
+// 8-bit writers: every row with filter type 0, the zlib stream made of stored blocks (no compression), so the
 // only arithmetic is the two checksums.  Any PNG reader takes it, read_png above included.
 static uint32_t crc32_png(const uint8_t* p, size_t n, uint32_t crc)
 {
@@ -213,11 +214,9 @@ static void put_chunk(std::vector<uint8_t>& file, const char* type, const std::v
     file.insert(file.end(), data.begin(), data.end());
     put_be32(file, crc32_png(&file[start], file.size() - start, 0));
 }
-bool write_png_grey8(const std::string& path, const uint8_t* data, int rows, int cols)
+// `raw`: every row as its filter byte (0) and its samples; colour_type 0 (grey) or 2 (R G B)
+static bool write_png_rows(const std::string& path, const std::vector<uint8_t>& raw, int rows, int cols, uint8_t colour_type)
 {
-    if (!data || rows < 1 || cols < 1) return false;
-    std::vector<uint8_t> raw(((size_t)cols + 1) * rows);  // filter byte 0 + the row
-    for (int y = 0; y < rows; ++y) memcpy(&raw[((size_t)cols + 1) * y + 1], data + (size_t)cols * y, (size_t)cols);
     std::vector<uint8_t> z = {0x78, 0x01};  // zlib header: deflate, 32 KiB window, no preset dictionary
     uint32_t a = 1, b = 0;                  // Adler-32 of the raw bytes
     for (size_t pos = 0; pos < raw.size();) {
@@ -238,7 +237,7 @@ bool write_png_grey8(const std::string& path, const uint8_t* data, int rows, int
     std::vector<uint8_t> file = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a}, ihdr;
     put_be32(ihdr, (uint32_t)cols);
     put_be32(ihdr, (uint32_t)rows);
-    const uint8_t tail[5] = {8, 0, 0, 0, 0};  // depth 8, colour type 0 (grey), deflate, adaptive filtering, no interlace
+    const uint8_t tail[5] = {8, colour_type, 0, 0, 0};  // depth 8, colour type, deflate, adaptive filtering, no interlace
     ihdr.insert(ihdr.end(), tail, tail + 5);
     put_chunk(file, "IHDR", ihdr);
     put_chunk(file, "IDAT", z);
@@ -247,6 +246,27 @@ bool write_png_grey8(const std::string& path, const uint8_t* data, int rows, int
     if (!f) return false;
     const bool ok = fwrite(file.data(), 1, file.size(), f) == file.size();
     return fclose(f) == 0 && ok;
+}
+bool write_png_grey8(const std::string& path, const uint8_t* data, int rows, int cols)
+{
+    if (!data || rows < 1 || cols < 1) return false;
+    std::vector<uint8_t> raw(((size_t)cols + 1) * rows);  // filter byte 0 + the row
+    for (int y = 0; y < rows; ++y) memcpy(&raw[((size_t)cols + 1) * y + 1], data + (size_t)cols * y, (size_t)cols);
+    return write_png_rows(path, raw, rows, cols, 0);
+}
+// the same for an interleaved B G R image (cv::imwrite's view of a CV_8UC3 Mat): the file holds R G B
+bool write_png_bgr8(const std::string& path, const uint8_t* data, int rows, int cols)
+{
+    if (!data || rows < 1 || cols < 1) return false;
+    const size_t stride = (size_t)cols * 3 + 1;
+    std::vector<uint8_t> raw(stride * rows);
+    for (int y = 0; y < rows; ++y)
+        for (int x = 0; x < cols; ++x) {
+            const uint8_t* s = data + ((size_t)cols * y + x) * 3;
+            uint8_t* d = &raw[stride * y + 1 + (size_t)x * 3];
+            d[0] = s[2], d[1] = s[1], d[2] = s[0];
+        }
+    return write_png_rows(path, raw, rows, cols, 2);
 }
 
 }  // namespace o3dr_host

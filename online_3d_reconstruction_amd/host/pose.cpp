@@ -287,6 +287,33 @@ int Pose::binarySearchUsingTime(const vector<double>& seq, int l, int r, double 
     throw "Exception: binarySearchUsingTime: unsuccessful search!";
 }
 
+// The numbers of `<key>: !!opencv-matrix ... data: [ ... ]` in the text of an OpenCV YAML file, in file order; false if the
+// entry or its data is missing.  The key is looked for at the start of a line (the last "key:" anywhere, if there is none).
+static bool yaml_matrix_data(const string& txt, const string& key, vector<double>& out)
+{
+    size_t p = txt.find("\n" + key + ":");
+    if (p == string::npos) p = txt.rfind(key + ":");
+    if (p == string::npos) return false;
+    p = txt.find("data:", p);
+    if (p == string::npos) return false;
+    const size_t a = txt.find('[', p);
+    const size_t b = a == string::npos ? a : txt.find(']', a);
+    if (a == string::npos || b == string::npos) return false;
+    string body = txt.substr(a + 1, b - a - 1);
+    for (char& ch : body)
+        if (ch == ',' || ch == '\n') ch = ' ';
+    stringstream vs(body);
+    out.clear();
+    string tok;
+    while (vs >> tok) {
+        char* end = nullptr;
+        const double v = strtod(tok.c_str(), &end);
+        if (end == tok.c_str() || *end) return false;
+        out.push_back(v);
+    }
+    return true;
+}
+
 // pose_functions.cpp:467-476 — `Q: !!opencv-matrix ... data: [ 16 doubles ]` of an OpenCV YAML file
 void Pose::readCalibFile()
 {
@@ -294,20 +321,42 @@ void Pose::readCalibFile()
     if (!f.is_open()) throw "Exception: could not read Q matrix";
     stringstream ss;
     ss << f.rdbuf();
-    const string txt = ss.str();
-    size_t p = txt.find("\nQ:");
-    if (p == string::npos) p = txt.rfind("Q:");
-    if (p == string::npos) throw "Exception: could not read Q matrix";
-    p = txt.find("data:", p);
-    const size_t a = txt.find('[', p), b = txt.find(']', a);
-    if (p == string::npos || a == string::npos || b == string::npos) throw "Exception: could not read Q matrix";
-    string body = txt.substr(a + 1, b - a - 1);
-    for (char& ch : body)
-        if (ch == ',' || ch == '\n') ch = ' ';
-    stringstream vs(body);
-    for (int i = 0; i < 16; ++i)
-        if (!(vs >> Q[i])) throw "Exception: could not read Q matrix";
+    vector<double> v;
+    if (!yaml_matrix_data(ss.str(), "Q", v) || v.size() < 16) throw "Exception: could not read Q matrix";
+    for (int i = 0; i < 16; ++i) Q[i] = v[(size_t)i];
     cout << "read calib file." << endl;
+}
+
+// --rectify_calib: the eight matrices stereoCalibrate + stereoRectify leave in one OpenCV YAML file - M1 D1 R1 P1 for the
+// left camera, M2 D2 R2 P2 for the right one (K1 / K2 are taken for M1 / M2); D of 4, 5 or 8 entries.  Host only.
+void Pose::readRectifyCalib()
+{
+    ifstream f(rectify_calib);
+    if (!f.is_open()) throw runtime_error("--rectify_calib: could not read " + rectify_calib);
+    stringstream ss;
+    ss << f.rdbuf();
+    const string txt = ss.str();
+    for (int k = 0; k < 2; ++k) {
+        const string n = to_string(k + 1);
+        o3dr_rectify_camera& cam = rectify_cam[k];
+        auto take = [&](const string& key, const string& alt, double* dst, size_t count) {
+            vector<double> v;
+            if (!yaml_matrix_data(txt, key, v) && (alt.empty() || !yaml_matrix_data(txt, alt, v)))
+                throw runtime_error("--rectify_calib: " + rectify_calib + " has no matrix " + key);
+            if (v.size() != count)
+                throw runtime_error("--rectify_calib: " + key + " must have " + to_string(count) + " entries, has " + to_string(v.size()));
+            copy(v.begin(), v.end(), dst);
+        };
+        take("M" + n, "K" + n, cam.K, 9);
+        take("R" + n, "", cam.R, 9);
+        take("P" + n, "", cam.P, 12);
+        vector<double> d;
+        if (!yaml_matrix_data(txt, "D" + n, d)) throw runtime_error("--rectify_calib: " + rectify_calib + " has no matrix D" + n);
+        if (d.size() != 4 && d.size() != 5 && d.size() != 8)
+            throw runtime_error("--rectify_calib: D" + n + " must have 4, 5 or 8 entries, has " + to_string(d.size()));
+        fill(cam.D, cam.D + 8, 0.0);
+        copy(d.begin(), d.end(), cam.D);
+    }
 }
 
 // pose_functions.cpp:478-506
@@ -367,6 +416,7 @@ void Pose::populateData()
         });
     for (thread& t : pool) t.join();
     cout << endl;
+    if (!rectify_calib.empty()) rectify_raw_images();  // before anything else sees the images
     if (gpu_disparity) compute_gpu_disparities();
     for (const RawImageData& r : rawImageDataVec)
         if (!r.disparity_image.empty()) {  // rows/cols from the first readable image (:635-638)
@@ -439,6 +489,14 @@ void Pose::printUsage()
             "       [--stereo_median 0|3|5] [--stereo_speckle_size n] [--stereo_speckle_diff n]  (the disparity image then goes\n"
             "                     through a k x k median and loses its connected components of at most n pixels, neighbours\n"
             "                     joined when they differ by at most --stereo_speckle_diff (default 1); also under --gpu_disparity)\n"
+            "./pose --rectify_pair left.png right.png --rectify_calib f [--rectify_border b]  (undistorts and rectifies one pair with\n"
+            "                     the matrices M1 D1 R1 P1 M2 D2 R2 P2 of the OpenCV YAML file f (K1 / K2 for M1 / M2; D of 4, 5 or 8\n"
+            "                     entries): writes <left>.rectified.png and <right>.rectified.png at the input's size, a tap outside\n"
+            "                     the source reading b (default 0), and prints each image's valid pixels and the call time; with\n"
+            "                     --stereo_disparity the pair is rectified first - the flags and the file names are this build's own)\n"
+            "       [--rectify_calib f]  (reconstruction run: every image of image_dir, and under --gpu_disparity of right_image_dir,\n"
+            "                     is replaced by its rectified version right after it is read; disparities read from\n"
+            "                     --disparity_dir are taken to be in rectified coordinates already; single-GPU batched path only)\n"
             "./pose --filter_disparity in.png [the same three flags]  (the filter alone on an 8-bit grey PNG: writes\n"
             "                     <in>.filtered.png and prints the components, the speckles, the removed pixels and the call time;\n"
             "                     at least one of the two filters must be on - the flags and the file name are this build's own)\n"
@@ -591,6 +649,15 @@ int Pose::parseCmdArgs(int argc, char** argv)
             filter_disparity_png = argv[++i];
             run3d_reconstruction = false;
         }
+        else if (a == "--rectify_pair") {
+            if (i + 2 >= argc || string(argv[i + 1]).rfind("--", 0) == 0 || string(argv[i + 2]).rfind("--", 0) == 0)
+                throw runtime_error("missing argument: --rectify_pair needs left.png and right.png");
+            rectify_left_png = argv[++i];
+            rectify_right_png = argv[++i];
+            run3d_reconstruction = false;
+        }
+        else if (a == "--rectify_calib") rectify_calib = need(i);
+        else if (a == "--rectify_border") rectify_border = atoi(need(i));
         else if (a == "--gpu_keypoints") gpu_keypoints = true;
         else if (a == "--orb_n_features") orb_n_features = atoi(need(i));
         else if (a == "--orb_levels") orb_levels = atoi(need(i));
@@ -621,6 +688,15 @@ int Pose::parseCmdArgs(int argc, char** argv)
         if (reference_fanout) throw runtime_error("--gpu_disparity is not available with --reference_fanout");
         if (use_segment_labels) throw runtime_error("--gpu_disparity is not available with --use_segment_labels");
         if (rightImagePrefix.empty()) throw runtime_error("--gpu_disparity needs --right_image_dir d/");
+    }
+    if (!rectify_left_png.empty() && rectify_calib.empty()) throw runtime_error("--rectify_pair needs --rectify_calib f");
+    if (!rectify_calib.empty()) {
+        if (run3d_reconstruction) {
+            if (n_gpus > 1 || partitioned_merge) throw runtime_error("--rectify_calib is not available with --gpus N > 1 / --partitioned_merge");
+            if (reference_fanout) throw runtime_error("--rectify_calib is not available with --reference_fanout");
+        }
+        if (rectify_border < 0 || rectify_border > 255) throw runtime_error("--rectify_border must be in 0..255");
+        readRectifyCalib();
     }
     if (!filter_disparity_png.empty()) {
         if (!disparity_filter_on())
@@ -887,7 +963,7 @@ o3dr_stereo_params Pose::stereo_params(int channels) const
 void Pose::run_stereo_disparity()
 {
     Q = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // the tool needs no camera
-    const Image8 left = read_png(stereo_left_png, false), right = read_png(stereo_right_png, false);
+    Image8 left = read_png(stereo_left_png, false), right = read_png(stereo_right_png, false);
     if (left.empty()) throw runtime_error("could not read " + stereo_left_png);
     if (right.empty()) throw runtime_error("could not read " + stereo_right_png);
     if (left.rows != right.rows || left.cols != right.cols) throw runtime_error("--stereo_disparity: the two images differ in size");
@@ -895,6 +971,10 @@ void Pose::run_stereo_disparity()
     vector<uint8_t> disp((size_t)left.rows * left.cols);
     o3dr_ctx* c = ctx_for_this_thread();
     const auto t0 = chrono::steady_clock::now();
+    if (!rectify_calib.empty()) {  // the matcher takes the rectified pair
+        rectify_images(c, 0, {&left}, nullptr);
+        rectify_images(c, 1, {&right}, nullptr);
+    }
     chk(o3dr_stereo_disparity(c, left.data.data(), right.data.data(), 0, left.pitch(), left.rows, left.cols, 1, &prm, disp.data(), nullptr,
                               nullptr, nullptr, O3DR_MEM_HOST),
         "o3dr_stereo_disparity");
@@ -944,6 +1024,86 @@ void Pose::run_filter_disparity()
     const string outp = filter_disparity_png + ".filtered.png";
     if (!write_png_grey8(outp, disp.data(), in.rows, in.cols)) throw runtime_error("could not write " + outp);
     cerr << "Saved the filtered image to " << outp << endl;
+}
+
+// Images of one size through camera `cam`'s map of that size (o3dr_rectify_maps, kept until another size is asked for) in
+// one o3dr_rectify_remap call; the output size equals the input size.
+void Pose::rectify_images(o3dr_ctx* c, int cam, const vector<Image8*>& imgs, int64_t* n_valid)
+{
+    if (imgs.empty()) return;
+    const int rows = imgs[0]->rows, cols = imgs[0]->cols, ch = imgs[0]->channels;
+    const size_t n = (size_t)rows * cols, F = imgs.size();
+    RectifyMap& m = rectify_map[cam];
+    if (m.rows != rows || m.cols != cols) {
+        m.map.assign(n * 2, 0);
+        m.rows = m.cols = 0;
+        chk(o3dr_rectify_maps(c, &rectify_cam[cam], rows, cols, m.map.data(), O3DR_MEM_HOST), "o3dr_rectify_maps");
+        m.rows = rows, m.cols = cols;
+    }
+    vector<uint8_t> src(F * n * ch), out(F * n * ch), valid(n_valid ? n : 0);
+    for (size_t k = 0; k < F; ++k) memcpy(&src[k * n * ch], imgs[k]->data.data(), n * ch);
+    chk(o3dr_rectify_remap(c, src.data(), (int64_t)(n * ch), (int64_t)cols * ch, rows, cols, ch, (int32_t)F, m.map.data(), rows, cols,
+                           rectify_border, 0, out.data(), n_valid ? valid.data() : nullptr, O3DR_MEM_HOST),
+        "o3dr_rectify_remap");
+    for (size_t k = 0; k < F; ++k) memcpy(imgs[k]->data.data(), &out[k * n * ch], n * ch);
+    if (n_valid) {
+        *n_valid = 0;
+        for (uint8_t v : valid) *n_valid += v;
+    }
+}
+
+// One raw pair through o3dr_rectify_maps and o3dr_rectify_remap (contract: include/o3dr.h "stereo rectification"), written
+// as <left>.rectified.png and <right>.rectified.png: what --stereo_disparity, image_dir and right_image_dir take.
+void Pose::run_rectify_pair()
+{
+    Q = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // the tool needs no camera
+    Image8 im[2] = {read_png(rectify_left_png, false), read_png(rectify_right_png, false)};
+    const string* path[2] = {&rectify_left_png, &rectify_right_png};
+    for (int k = 0; k < 2; ++k)
+        if (im[k].empty()) throw runtime_error("could not read " + *path[k]);
+    if (im[0].rows != im[1].rows || im[0].cols != im[1].cols) throw runtime_error("--rectify_pair: the two images differ in size");
+    o3dr_ctx* c = ctx_for_this_thread();
+    int64_t n_valid[2] = {0, 0};
+    const auto t0 = chrono::steady_clock::now();
+    for (int k = 0; k < 2; ++k) rectify_images(c, k, {&im[k]}, &n_valid[k]);
+    const double ms = chrono::duration<double, milli>(chrono::steady_clock::now() - t0).count();
+    cout << "pair " << im[0].rows << " x " << im[0].cols << ", valid " << n_valid[0] << " (left) and " << n_valid[1] << " (right) of "
+         << (size_t)im[0].rows * im[0].cols << " pixels, " << ms << " ms" << endl;
+    for (int k = 0; k < 2; ++k) {
+        const string outp = *path[k] + ".rectified.png";
+        const bool ok = im[k].channels == 3 ? write_png_bgr8(outp, im[k].data.data(), im[k].rows, im[k].cols)
+                                            : write_png_grey8(outp, im[k].data.data(), im[k].rows, im[k].cols);
+        if (!ok) throw runtime_error("could not write " + outp);
+        cerr << "Saved the rectified image to " << outp << endl;
+    }
+}
+
+// --rectify_calib in a reconstruction run: every readable rgb_image - under --gpu_disparity every right_image too - is
+// replaced by its rectified version, a cycle's frames (at most 16) of one size per call and camera.  Colours, keypoints,
+// feature poses and the GPU matcher all see the rectified images; a disparity image read from --disparity_dir is taken to
+// be in rectified coordinates already.
+void Pose::rectify_raw_images()
+{
+    const size_t per_call = (size_t)min(seq_len > 0 ? seq_len : 16, 16);
+    o3dr_ctx* c = ctx_for_this_thread();
+    size_t done[2] = {0, 0};
+    for (int cam = 0; cam < (gpu_disparity ? 2 : 1); ++cam) {
+        vector<Image8*> batch;
+        auto flush = [&]() {
+            rectify_images(c, cam, batch, nullptr);
+            done[cam] += batch.size();
+            batch.clear();
+        };
+        for (RawImageData& r : rawImageDataVec) {
+            Image8& im = cam == 0 ? r.rgb_image : r.right_image;
+            if (im.empty()) continue;
+            if (!batch.empty() && (batch.size() == per_call || batch[0]->rows != im.rows || batch[0]->cols != im.cols)) flush();
+            batch.push_back(&im);
+        }
+        flush();
+    }
+    cout << "--rectify_calib: " << done[0] << " left" << (gpu_disparity ? " and " + to_string(done[1]) + " right" : string())
+         << " images rectified by o3dr_rectify_remap" << endl;
 }
 
 // --gpu_disparity: where the disparity PNGs would have been read, every raw frame with a readable pair gets its disparity
@@ -1024,6 +1184,10 @@ Pose::Pose(int argc, char* argv[])
     }
     if (!stereo_left_png.empty()) {
         run_stereo_disparity();
+        return;
+    }
+    if (!rectify_left_png.empty()) {
+        run_rectify_pair();
         return;
     }
     if (!filter_disparity_png.empty()) {
