@@ -986,6 +986,75 @@ int  o3dr_disparity_filter(o3dr_ctx* ctx, const void* disp, int64_t frame_stride
                            int32_t n_frames, const o3dr_disparity_filter_params* p, void* out, int32_t* labels_out,
                            int32_t* sizes_out, o3dr_disparity_filter_info* info, int32_t mem);
 
+/* ---- image segmentation: the segment label image that o3dr_plane_fit_disparity reads (the reference takes it from offline
+ * files, segmentlabels/<n>.png): grid-seeded k-means superpixels on the colour image (SLIC-like), connected components, a
+ * merge of the small ones, labels numbered compactly.  There is nothing of the reference's to pin: the contract below is
+ * this library's own; every step is an exact integer computation (int64 holds every intermediate value), so results are
+ * bit-identical across calls, frame batchings and memory kinds; tests/segment_reference.py restates it in numpy.
+ *
+ * Input: `img`, n_frames uint8 images of rows x cols pixels (1..8192 each) of `channels` bytes (3: B G R; 1: grey, which
+ * counts as B = G = R), byte `pitch` and byte `frame_stride`, in `mem`.  W = cols, H = rows, S = step, m = compactness,
+ * K = iterations; every division below is the floored integer division of non-negative values.
+ *   1. Seeds: nx = ceil(W / S), ny = ceil(H / S); centre k = gy * nx + gx starts at x_k = min(gx * S + S / 2, W - 1),
+ *      y_k = min(gy * S + S / 2, H - 1) with that pixel's colour (B_k, G_k, R_k).  Centres are integers throughout.
+ *   2. Assignment: pixel (x, y) has the home cell (x / S, y / S); its candidates are the centres of the up to 9 cells
+ *      (hx + dx, hy + dy), dx and dy in -1..1, that exist.  Its label is the candidate k with the lowest
+ *      D = S^2 ((B - B_k)^2 + (G - G_k)^2 + (R - R_k)^2) + m^2 ((x - x_k)^2 + (y - y_k)^2)  (below 2^37); ties go to the
+ *      lowest k.  The colour is raw B G R, not Lab (cube roots cannot be pinned); m = 20 is the default that fits it.
+ *   3. Update: per centre the exact sums n, sum x, sum y, sum B, sum G, sum R over its pixels; each new value is
+ *      (2 sum + n) / (2 n) - the mean rounded half up.  A centre with n = 0 keeps its values and stays a candidate.  A
+ *      centre only ever receives pixels of the 9 cells around its own, so n <= 9 S^2 and sum x < 9 * 2^16 * 2^13 < 2^33:
+ *      the sums are 64-bit, and integer adds carry no order dependence.
+ *   4. Raw labels: K rounds of (assignment, update), then one more assignment: L0, whose values are centre indices.
+ *   5. Components: two 4-neighbours of one frame are joined iff their L0 is equal.  A component is identified by its
+ *      lowest pixel index y * W + x, its first pixel.  It is small iff its pixel count is below min_size.
+ *   6. Merge: a small component c joins the component c' that minimises the 64-bit key (d << 32 | first pixel of c') over
+ *      all not-small components c' 4-adjacent to any pixel of c, d = the squared B G R distance (< 2^18) between the
+ *      centres (after step 4) whose indices are the two components' L0.  If c touches no not-small component - every
+ *      component next to it is small - it goes where the component of the pixel left of its first pixel goes (the
+ *      pixel above it where x = 0); the component that holds pixel 0 then stays as it is.  That neighbour is not in c and
+ *      has a lower index, so its component's first pixel is strictly lower than c's: every chain of such steps ends, at a
+ *      not-small component or at the component of pixel 0.  Not-small components never move.  Every final label is
+ *      4-connected.
+ *   7. Numbering: the final labels are numbered 0 .. n_labels - 1 by ascending first pixel, the first pixel of a label
+ *      being the lowest first pixel of the components that went into it.
+ * Outputs, [n_frames][H][W] with rows tight, in `mem`: labels (int32, required; never negative, so uint32 readers take
+ * it as it is).  raw_out (int32, optional): L0.  sizes_out (int32, optional): the pixel count of the pixel's final label.
+ * info (HOST, optional, one per frame): n_centres = nx ny, n_components (step 5), n_merged = components that joined
+ * another one, n_labels = n_components - n_merged, largest / smallest = pixel counts of the largest and smallest label.
+ * Limits, else O3DR_ERR_INVALID_ARG before any device work (host outputs zeroed wherever rows, cols and n_frames are
+ * themselves within their limits, so that the outputs' sizes are known), checked in this order: mem kind; n_frames >= 0;
+ * rows and cols in 1..8192; channels 1 or 3; step in 4..256; compactness in 0..255; iterations in 0..32; group_frames
+ * >= 0; then n_frames == 0 returns O3DR_OK and touches nothing; img and labels not NULL; pitch >= cols * channels;
+ * frame_stride >= rows * pitch when n_frames > 1; labels, raw_out and sizes_out 4-byte aligned.  min_size: any negative
+ * value means S S / 4; 0: nothing is merged.  p == NULL: the defaults.  pitch and frame_stride have no upper limit (as in
+ * o3dr_disparity_filter: a host image too large to stage returns O3DR_ERR_ALLOC).  group_frames: the frames of a call go
+ * through the kernels in groups whose scratch (28 bytes a pixel, 68 bytes a centre) fits 1 GiB - one frame always forms a
+ * group -; group_frames = n > 0 caps a group at n frames.  Results do not depend on it.  The number of launches of a
+ * group depends on the parameters and the image's size alone, never on its content.  The call carves its own scratch
+ * block, does not use the sort workspace, leaves cloud_big alone and synchronises the stream once, at its end. */
+#define O3DR_SEGMENT_MAX_SIDE 8192
+typedef struct o3dr_segment_params {
+    int32_t channels;      /* default 3: B G R; 1: grey */
+    int32_t step;          /* default 16; 4..256 */
+    int32_t compactness;   /* default 20; 0..255 */
+    int32_t iterations;    /* default 5; 0..32 */
+    int32_t min_size;      /* default -1: step * step / 4; 0: no merging */
+    int32_t group_frames;  /* default 0: as many frames per launch group as the scratch budget allows; n > 0: at most n */
+} o3dr_segment_params;
+typedef struct o3dr_segment_info {   /* one per frame, HOST */
+    int64_t n_centres;      /* nx * ny */
+    int64_t n_components;   /* components of equal raw labels */
+    int64_t n_merged;       /* components that joined another one */
+    int64_t n_labels;       /* final labels */
+    int64_t largest;        /* pixel count of the largest label */
+    int64_t smallest;       /* ... of the smallest */
+} o3dr_segment_info;
+void o3dr_segment_default_params(o3dr_segment_params* p);
+int  o3dr_segment_image(o3dr_ctx* ctx, const uint8_t* img, int64_t frame_stride, int64_t pitch, int32_t rows, int32_t cols,
+                        int32_t n_frames, const o3dr_segment_params* p, int32_t* labels, int32_t* raw_out, int32_t* sizes_out,
+                        o3dr_segment_info* info, int32_t mem);
+
 /* ---- pose chain: the reference's default mode (pose.cpp:213-235, generate_tf_of_Matched_Keypoints): every frame gets its
  * pose from descriptor matches against earlier nearby frames, whose keypoints are moved by THEIR fitted poses - a serial
  * chain.  The reference's selection rules and PCL's rounding cannot be pinned here, so the contract below is this library's
@@ -1254,7 +1323,9 @@ int  o3dr_pose_graph_refine(o3dr_ctx* ctx, const uint8_t* desc, const int64_t* o
 #define O3DR_K_DISP_SPECKLE 27  /* ... removal of the small components and the per-frame counts */
 #define O3DR_K_RECTIFY_MAPS  28  /* stereo rectification: the Q5 map of one camera, one thread per pixel */
 #define O3DR_K_RECTIFY_REMAP 29  /* ... the bilinear remap of a group of frames through one map */
-#define O3DR_K_NUM          30
+#define O3DR_K_SEG_ASSIGN   30  /* image segmentation: seeds, the K + 1 assignments with their tile sums, the updates */
+#define O3DR_K_SEG_LABEL    31  /* ... components, merge of the small ones, ordered numbering, outputs */
+#define O3DR_K_NUM          32
 /* Bracket every launch of kernel `kernel_id` (or all kernels if -1) with HIP events on the
  * context's stream; 0 launches are bracketed when disabled (the default). */
 int o3dr_profile_enable(o3dr_ctx* ctx, int32_t kernel_id, int32_t enable);

@@ -23,11 +23,12 @@ K_GRAPH_MOMENTS, K_GRAPH_SOLVE = 20, 21
 K_STEREO_CENSUS, K_STEREO_PATHS, K_STEREO_WINNER = 22, 23, 24
 K_DISP_MEDIAN, K_DISP_LABEL, K_DISP_SPECKLE = 25, 26, 27
 K_RECTIFY_MAPS, K_RECTIFY_REMAP = 28, 29
+K_SEG_ASSIGN, K_SEG_LABEL = 30, 31
 KERNEL_NAMES = ["reproject_count", "reproject_emit", "voxel_keys", "radix_hist", "radix_scatter", "run_segments",
                 "centroid", "other", "centroid_runs", "plane_disp_sums", "plane_disp_fit", "plane_disp_eval",
                 "orb_pyramid", "orb_fast", "orb_candidates", "orb_select", "orb_describe", "match", "pose_chain", "ransac",
                 "graph_moments", "graph_solve", "stereo_census", "stereo_paths", "stereo_winner", "disp_median", "disp_label",
-                "disp_speckle", "rectify_maps", "rectify_remap"]
+                "disp_speckle", "rectify_maps", "rectify_remap", "seg_assign", "seg_label"]
 
 
 class O3drError(RuntimeError):
@@ -134,6 +135,19 @@ class DisparityFilterInfoStruct(C.Structure):
 
 
 DISPARITY_FILTER_MAX_SIDE = 8192
+
+
+class SegmentParamsStruct(C.Structure):
+    _fields_ = [("channels", C.c_int32), ("step", C.c_int32), ("compactness", C.c_int32), ("iterations", C.c_int32),
+                ("min_size", C.c_int32), ("group_frames", C.c_int32)]
+
+
+class SegmentInfoStruct(C.Structure):
+    _fields_ = [("n_centres", C.c_int64), ("n_components", C.c_int64), ("n_merged", C.c_int64), ("n_labels", C.c_int64),
+                ("largest", C.c_int64), ("smallest", C.c_int64)]
+
+
+SEGMENT_MAX_SIDE = 8192
 
 
 class RectifyCameraStruct(C.Structure):
@@ -296,6 +310,8 @@ SYMBOLS = [
     ("o3dr_disparity_filter_default_params", None, [C.POINTER(DisparityFilterParamsStruct)]),
     ("o3dr_disparity_filter", C.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, C.POINTER(DisparityFilterParamsStruct), _vp, _vp, _vp,
                                         _vp, _i32]),
+    ("o3dr_segment_default_params", None, [C.POINTER(SegmentParamsStruct)]),
+    ("o3dr_segment_image", C.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, C.POINTER(SegmentParamsStruct), _vp, _vp, _vp, _vp, _i32]),
     ("o3dr_rectify_maps", C.c_int, [_vp, C.POINTER(RectifyCameraStruct), _i32, _i32, _vp, _i32]),
     ("o3dr_rectify_remap", C.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32]),
     ("o3dr_chain_default_params", None, [C.POINTER(ChainParamsStruct)]),

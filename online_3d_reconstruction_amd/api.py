@@ -116,6 +116,18 @@ class DisparityFilterInfo:
     largest: int
 
 
+@dataclass
+class SegmentInfo:
+    """o3dr_segment_image's counts for one frame: k-means centres, components of equal raw labels, components merged into
+    another one, final labels, and the pixel counts of the largest and the smallest label."""
+    n_centres: int
+    n_components: int
+    n_merged: int
+    n_labels: int
+    largest: int
+    smallest: int
+
+
 def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
@@ -844,6 +856,68 @@ class Context:
         infos = [DisparityFilterInfo(int(i.n_valid), int(i.n_components), int(i.n_speckles), int(i.n_removed), int(i.largest))
                  for i in info] if return_info else None
         return (out,) + ((labels,) if return_labels else ()) + ((sizes,) if return_sizes else ()) + ((infos,) if return_info else ())
+
+    # -- image segmentation (the label image planeFitDisparity reads; the reference takes it from offline files) ---------------
+    def segmentImage(self, img, step=16, compactness=20, iterations=5, min_size=None, return_raw=False, return_sizes=False,
+                     return_info=False, group_frames=0):
+        """Superpixel labels of a colour image: grid-seeded integer k-means (step, compactness, iterations), connected
+        components, merge of the components below min_size pixels (None: step * step / 4; 0: none) into their nearest
+        neighbour in colour, labels numbered 0 .. n - 1 by first pixel - contract: include/o3dr.h "image segmentation".
+        img: uint8 [H, W] or [F, H, W] grey, [H, W, 3] or [F, H, W, 3] B G R (a 3-D input whose last axis is 3 is one B G R
+        image, as in stereoDisparity); a padded pitch or frame stride passes through.  numpy in gives a numpy uint32 label
+        image, a torch CUDA tensor gives an int32 CUDA tensor and nothing leaves HBM: either goes into
+        planeFitDisparity(disp, labels) as it is.  return_raw / return_sizes: int32 images follow (the k-means centre of
+        every pixel; the pixel count of its label); return_info: a list of SegmentInfo, one per frame, follows.
+        group_frames: at most that many frames per launch group; results do not depend on it."""
+        dev = _is_torch(img)
+        nd = img.dim() if dev else np.ndim(img)
+        ch = 3 if (nd == 4 or (nd == 3 and int(img.shape[-1]) == 3)) else 1
+        single = nd == (3 if ch == 3 else 2)
+        assert nd in ((3, 4) if ch == 3 else (2, 3))
+        F = 1 if single else int(img.shape[0])
+        rows, cols = (int(img.shape[-3]), int(img.shape[-2])) if ch == 3 else (int(img.shape[-2]), int(img.shape[-1]))
+        row_axis = -3 if ch == 3 else -2
+        if dev:
+            import torch
+            assert img.is_cuda and img.dtype == torch.uint8
+            if not (img.stride(-1) == 1 and (ch == 1 or img.stride(-2) == 3) and img.stride(row_axis) >= cols * ch and
+                    (single or img.stride(0) >= rows * img.stride(row_axis))):
+                img = img.contiguous()
+            pitch, fs = int(img.stride(row_axis)), (0 if single else int(img.stride(0)))
+            mem, pi = L.MEM_DEVICE, img.data_ptr()
+        else:
+            img = np.asarray(img)
+            assert img.dtype == np.uint8
+            st = img.strides
+            if not (st[-1] == 1 and (ch == 1 or st[-2] == 3) and st[row_axis] >= cols * ch and (single or st[0] >= rows * st[row_axis])):
+                img = np.ascontiguousarray(img)  # (a padded pitch or frame stride is passed through as it is)
+            pitch, fs = int(img.strides[row_axis]), (0 if single else int(img.strides[0]))
+            mem, pi = L.MEM_HOST, img.ctypes.data
+        prm = L.SegmentParamsStruct(ch, int(step), int(compactness), int(iterations), -1 if min_size is None else int(min_size),
+                                    int(group_frames))
+        shape = (rows, cols) if single else (F, rows, cols)
+        if dev:
+            def empty():
+                return torch.empty(shape, dtype=torch.int32, device=img.device)
+            self._order_after_torch()
+            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        else:
+            def empty():
+                return np.empty(shape, np.int32)
+            ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        labels = empty()
+        raw = empty() if return_raw else None
+        sizes = empty() if return_sizes else None
+        info = (L.SegmentInfoStruct * F)() if return_info else None
+        L.check(self._lib.o3dr_segment_image(self._h, pi, fs, pitch, rows, cols, F, C.byref(prm), ptr(labels), ptr(raw), ptr(sizes),
+                                             C.cast(info, C.c_void_p) if return_info else None, mem))
+        if not dev:
+            labels = labels.view(np.uint32)  # (never negative)
+        if not (return_raw or return_sizes or return_info):
+            return labels
+        infos = [SegmentInfo(int(i.n_centres), int(i.n_components), int(i.n_merged), int(i.n_labels), int(i.largest), int(i.smallest))
+                 for i in info] if return_info else None
+        return (labels,) + ((raw,) if return_raw else ()) + ((sizes,) if return_sizes else ()) + ((infos,) if return_info else ())
 
     # -- feature matching (BFMatcher NORM_HAMMING knnMatch k=2 + ratio test, pose.h:180 / pose_functions.cpp:2017, and
     #    TransformationEstimationSVD, pose.cpp:213-235) --------------------------------------------------------------------

@@ -63,6 +63,12 @@ __device__ __forceinline__ uint32_t df_load(const DfView& v, int f, int y, int x
 {
     return *(const T*)((const char*)v.p + (int64_t)f * v.fstride + (int64_t)y * v.pitch + (int64_t)x * (int64_t)sizeof(T));
 }
+// The equal-label predicate (segment_image.inc): an element type whose value is the int32 label plus one, so that every
+// label >= 0 is a valid pixel and df_joined with max_diff = 0 joins equal labels alone.
+struct DfLabel {
+    int32_t v;
+    __device__ __forceinline__ operator uint32_t() const { return (uint32_t)v + 1u; }
+};
 __device__ __forceinline__ bool df_joined(uint32_t a, uint32_t b, uint32_t max_diff)
 {
     return a != 0 && b != 0 && (a > b ? a - b : b - a) <= max_diff;

@@ -149,6 +149,7 @@ struct o3dr_ctx {
     DevBuf stereo_work;        // o3dr_stereo_disparity: its own scratch block (one carve per call)
     DevBuf dfilter_work;       // o3dr_disparity_filter: its own scratch block (one carve per call)
     DevBuf rect_work;          // o3dr_rectify_remap: the staged host map (one carve per call)
+    DevBuf segment_work;       // o3dr_segment_image: its own scratch block (one carve per call)
     DevBuf pl_hyp;             // o3dr_segment_plane: hypotheses + scores (plane_hyp_layout), kept for the test hook
     uint64_t pl_last_hyp = 0;  // hypotheses of the last call in pl_hyp (o3dr_test_plane_hypotheses)
     std::vector<MatchPair> mt_tab_h;  // host copies of the match pair table, the rigid fit's segment table and transforms
@@ -476,7 +477,7 @@ extern "C" int o3dr_ctx_destroy(o3dr_ctx* c)
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     for (DevBuf* b : {&c->inc.box, &c->inc.scratch, &c->inc.tg, &c->inc.tmatch, &c->inc.flag, &c->inc.src, &c->inc.keep,
-                      &c->inc.partial, &c->inc.words, &c->inc.fb, &c->nn_q, &c->nn_t, &c->nn_cells, &c->nn_src, &c->pl_hyp, &c->orb_work, &c->orb_pat, &c->stereo_work, &c->dfilter_work, &c->rect_work})
+                      &c->inc.partial, &c->inc.words, &c->inc.fb, &c->nn_q, &c->nn_t, &c->nn_cells, &c->nn_src, &c->pl_hyp, &c->orb_work, &c->orb_pat, &c->stereo_work, &c->dfilter_work, &c->rect_work, &c->segment_work})
         dev_release(*b);
     for (DevBuf& b : c->op) dev_release(b);
     delete c;
@@ -5086,6 +5087,124 @@ extern "C" int o3dr_disparity_filter(o3dr_ctx* c, const void* disp, int64_t fram
 }
 
 // =================================================================================================
+// image segmentation (kernels/segment_image.inc; DESIGN.md "Image segmentation")
+// =================================================================================================
+extern "C" void o3dr_segment_default_params(o3dr_segment_params* p)
+{
+    if (!p) return;
+    p->channels = 3;
+    p->step = 16;
+    p->compactness = 20;
+    p->iterations = 5;
+    p->min_size = -1;
+    p->group_frames = 0;
+}
+
+static bool segment_shape_ok(int32_t rows, int32_t cols, int32_t n_frames)
+{
+    return rows >= 1 && rows <= O3DR_SEGMENT_MAX_SIDE && cols >= 1 && cols <= O3DR_SEGMENT_MAX_SIDE && n_frames >= 0;
+}
+
+constexpr size_t kSegmentScratchBytes = (size_t)1 << 30;  // a group of frames keeps its scratch within this (one frame always forms a group)
+
+static int segment_image(o3dr_ctx* c, const uint8_t* img, int64_t fs, int64_t pitch, int32_t rows, int32_t cols, int32_t n_frames,
+                         const o3dr_segment_params* p, int32_t* labels, int32_t* raw_out, int32_t* sizes_out, o3dr_segment_info* info,
+                         Outputs& outs, int32_t mem)
+{
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    if (n_frames < 0) return fail(O3DR_ERR_INVALID_ARG, "bad frame count");
+    o3dr_segment_params prm;
+    o3dr_segment_default_params(&prm);
+    if (p) prm = *p;
+    if (!segment_shape_ok(rows, cols, 0)) return fail(O3DR_ERR_INVALID_ARG, "rows and cols must be in 1..8192");
+    if (prm.channels != 1 && prm.channels != 3) return fail(O3DR_ERR_INVALID_ARG, "channels must be 1 or 3");
+    if (prm.step < 4 || prm.step > 256) return fail(O3DR_ERR_INVALID_ARG, "step must be in 4..256");
+    if (prm.compactness < 0 || prm.compactness > 255) return fail(O3DR_ERR_INVALID_ARG, "compactness must be in 0..255");
+    if (prm.iterations < 0 || prm.iterations > 32) return fail(O3DR_ERR_INVALID_ARG, "iterations must be in 0..32");
+    if (prm.group_frames < 0) return fail(O3DR_ERR_INVALID_ARG, "group_frames is negative");
+    if (n_frames == 0) return O3DR_OK;
+    if (!img || !labels) return fail(O3DR_ERR_INVALID_ARG, "img / labels is NULL");
+    const int64_t ch = prm.channels;
+    if (pitch < (int64_t)cols * ch) return fail(O3DR_ERR_INVALID_ARG, "pitch smaller than a row");
+    if (n_frames > 1 && fs < (int64_t)rows * pitch) return fail(O3DR_ERR_INVALID_ARG, "frame stride smaller than a frame");
+    if ((uintptr_t)labels % 4 || (uintptr_t)raw_out % 4 || (uintptr_t)sizes_out % 4)
+        return fail(O3DR_ERR_INVALID_ARG, "labels / raw_out / sizes_out must be 4-byte aligned");
+
+    SegArgs a;
+    memset(&a, 0, sizeof a);
+    a.rows = rows, a.cols = cols, a.channels = prm.channels, a.S = prm.step, a.m = prm.compactness, a.iterations = prm.iterations;
+    a.min_size = prm.min_size < 0 ? prm.step * prm.step / 4 : prm.min_size;
+    a.nx = (cols + prm.step - 1) / prm.step, a.ny = (rows + prm.step - 1) / prm.step;
+    a.fstride = fs, a.pitch = pitch;
+    const size_t n = (size_t)rows * (size_t)cols, nc = (size_t)a.nx * (size_t)a.ny;
+    const size_t n_chunks = (n + 4095) / 4096;
+    const size_t in_bytes = (size_t)fs * (size_t)(n_frames - 1) + (size_t)pitch * (size_t)(rows - 1) + (size_t)cols * (size_t)ch;
+    const void* img_d;
+    CHK(stage_in(c, c->op[o3dr_ctx::OP_IN], img, in_bytes, mem, &img_d));
+
+    const size_t per_frame = n * 28 + nc * 68 + n_chunks * 4;
+    size_t group = std::max<size_t>(1, kSegmentScratchBytes / per_frame);
+    group = std::min<size_t>(std::min<size_t>(group, (size_t)n_frames), 32768);
+    if (prm.group_frames > 0) group = std::min<size_t>(group, (size_t)prm.group_frames);
+    unsigned long long* info_d = nullptr;
+    int32_t* raw_scratch = nullptr;
+    CHK(carve(c, c->segment_work, [&](Carve& w) {
+        w.take(a.key, group * n);
+        w.take(a.sums, group * nc * 6);
+        if (info) w.take(info_d, (size_t)n_frames * 5);
+        if (!raw_out) w.take(raw_scratch, group * n);
+        w.take(a.parent, group * n);
+        w.take(a.cnt, group * n);
+        w.take(a.link, group * n);
+        w.take(a.flag, group * n);
+        w.take(a.centres, group * nc * 5);
+        w.take(a.partial, group * n_chunks);
+    }));
+    if (info) HIPCHK(hipMemsetAsync(info_d, 0, (size_t)n_frames * 5 * sizeof(unsigned long long), c->stream));
+    CHK(outs.stage(c));
+    int32_t *labels_d = outs.dev(labels), *raw_d = outs.dev(raw_out), *sizes_d = outs.dev(sizes_out);
+    for (size_t f0 = 0; f0 < (size_t)n_frames; f0 += group) {
+        a.frames = (int32_t)std::min(group, (size_t)n_frames - f0);
+        a.img = (const uint8_t*)img_d + (int64_t)f0 * fs;
+        a.labels_out = labels_d + f0 * n;
+        a.raw = raw_d ? raw_d + f0 * n : raw_scratch;
+        a.sizes_out = sizes_d ? sizes_d + f0 * n : nullptr;
+        a.info = info_d ? info_d + f0 * 5 : nullptr;
+        launch_segment_image(&c->prof, c->stream, a);
+    }
+    HIPCHK(hipGetLastError());
+    CHK(outs.copy_back(c));
+    std::vector<unsigned long long> counts(info ? (size_t)n_frames * 5 : 0);
+    if (info) HIPCHK(hipMemcpyAsync(counts.data(), info_d, counts.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (size_t f = 0; info && f < (size_t)n_frames; ++f) {
+        const unsigned long long* k = &counts[f * 5];
+        info[f] = o3dr_segment_info{(int64_t)nc, (int64_t)k[0], (int64_t)k[1], (int64_t)k[2], (int64_t)k[3], (int64_t)(0xffffffffull - k[4])};
+    }
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_segment_image(o3dr_ctx* c, const uint8_t* img, int64_t frame_stride, int64_t pitch, int32_t rows, int32_t cols,
+                                  int32_t n_frames, const o3dr_segment_params* p, int32_t* labels, int32_t* raw_out, int32_t* sizes_out,
+                                  o3dr_segment_info* info, int32_t mem)
+{
+    // the outputs' sizes are known only where the shape itself is within its limits
+    const int64_t px = segment_shape_ok(rows, cols, n_frames) ? (int64_t)n_frames * rows * cols : 0;
+    Outputs outs{mem};
+    outs.add(labels, px);
+    outs.add(raw_out, px);
+    outs.add(sizes_out, px);
+    const int rc = entered(c, [&] {
+        return segment_image(c, img, frame_stride, pitch, rows, cols, n_frames, p, labels, raw_out, sizes_out, info, outs, mem);
+    });
+    if (rc != O3DR_OK) {
+        outs.zero();
+        if (info && px > 0) memset(info, 0, sizeof(o3dr_segment_info) * (size_t)n_frames);
+    }
+    return rc;
+}
+
+// =================================================================================================
 // stereo rectification (kernels/rectify.inc; DESIGN.md "Stereo rectification")
 // =================================================================================================
 static bool rect_side_ok(int32_t v) { return v >= 1 && v <= O3DR_RECTIFY_MAX_SIDE; }
@@ -5220,7 +5339,8 @@ extern "C" int o3dr_profile_enable(o3dr_ctx* c, int32_t kernel_id, int32_t enabl
 {
     CTX_ENTER(c);
     if (kernel_id >= O3DR_K_NUM) return fail(O3DR_ERR_INVALID_ARG, "bad kernel id");
-    const uint32_t bits = kernel_id < 0 ? ((1u << O3DR_K_NUM) - 1u) : (1u << kernel_id);
+    static_assert(O3DR_K_NUM < 64, "the profile mask is 64 bits wide");
+    const uint64_t bits = kernel_id < 0 ? (((uint64_t)1 << O3DR_K_NUM) - 1u) : ((uint64_t)1 << kernel_id);
     if (enable)
         c->prof.mask |= bits;
     else

@@ -634,6 +634,24 @@ struct DfArgs {
     void* out;
 };
 void launch_disparity_filter(Profiler* pf, hipStream_t s, const DfArgs& a);
+// Image segmentation (kernels/segment_image.inc; contract: include/o3dr.h "image segmentation").  One SegArgs describes a
+// group of `frames` frames; every array holds the group's frames one after the other.  centres: [nx * ny][5] int32 x, y,
+// B, G, R; sums: [nx * ny][6] n, sum x, sum y, sum B, sum G, sum R.  Per pixel: raw (the centre index), parent / cnt (the
+// union-find forest of disparity_filter.inc and the pixel counts at the roots), key (the 64-bit bid of a small component,
+// later its final root and its label's first pixel), link, flag (root flags, then their exclusive scan).
+struct SegArgs {
+    const uint8_t* img;  // the group's first frame
+    int64_t fstride, pitch;
+    int32_t rows, cols, channels, frames, S, m, iterations, min_size, nx, ny;
+    int32_t* centres;
+    unsigned long long* sums;
+    int32_t *raw, *parent, *cnt, *link;
+    unsigned long long* key;
+    uint32_t *flag, *partial;         // partial: the scan's chunk sums, frames * ceil(rows * cols / 4096) words
+    int32_t *labels_out, *sizes_out;  // the group's first frame, rows tight; sizes_out nullptr: not asked for
+    unsigned long long* info;         // [frames][5]: n_components, n_merged, n_labels, largest, 2^32 - 1 - smallest; nullptr: not asked for
+};
+void launch_segment_image(Profiler* pf, hipStream_t s, const SegArgs& a);
 // Stereo rectification (kernels/rectify.inc; contract: include/o3dr.h "stereo rectification").  RectMapArgs: the inverse of
 // P R (host fp64), the camera and the distortion, by value.  RectArgs: one launch group of `frames` frames through one map.
 struct RectMapArgs {

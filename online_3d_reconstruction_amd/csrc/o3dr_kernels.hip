@@ -36,6 +36,7 @@
 //   orb          ORB features: grey pyramid, FAST score + box sums, candidates, exact selection, steered BRIEF
 //   stereo       stereo disparity: grey + census, semi-global aggregation (one wave per scan line), winner + left-right check
 //   disparity_filter  median and speckle removal of a disparity image: LDS median network, tiled union-find labelling
+//   segment_image  superpixel labels of a colour image: tiled k-means with LDS sums, the filter's union-find, merge, ordered numbering
 //   rectify      stereo rectification: the fp64 Q5 map of one camera, the integer bilinear remap of a group of frames
 //   pose_chain   the feature-matched pose chain: one workgroup walks the frames (gather, moments, Kabsch, residual)
 //   ransac       three-point RANSAC for a rigid transform: one workgroup per segment / pair of the chain
@@ -68,6 +69,7 @@ namespace o3dr {
 #include "kernels/orb.inc"
 #include "kernels/stereo.inc"
 #include "kernels/disparity_filter.inc"
+#include "kernels/segment_image.inc"
 #include "kernels/rectify.inc"
 #include "kernels/pose_chain.inc"
 #include "kernels/ransac.inc"
@@ -769,6 +771,44 @@ void launch_disparity_filter(Profiler* pf, hipStream_t s, const DfArgs& a)
         disparity_filter_frames<uint8_t>(pf, s, a);
     else
         disparity_filter_frames<uint16_t>(pf, s, a);
+}
+
+// image segmentation of one group of frames (a.frames <= 65535: the grid's y extent); the launches depend on the
+// parameters and the image's size alone
+void launch_segment_image(Profiler* pf, hipStream_t s, const SegArgs& a)
+{
+    if (a.frames <= 0) return;
+    const int F = a.frames;
+    const int tiles_x = cdiv64(a.cols, kDfTileX), tiles_y = cdiv64(a.rows, kDfTileY);
+    const int64_t n = (int64_t)a.rows * a.cols;
+    const int px_blocks = cdiv64(n, 256), c_blocks = cdiv64((int64_t)a.nx * a.ny, 256);
+    {
+        ProfScope ps(pf, O3DR_K_SEG_ASSIGN, s);
+        k_seg_init<<<dim3(c_blocks, F), 256, 0, s>>>(a);
+        for (int k = 0; k < a.iterations; ++k) {
+            k_seg_assign<true><<<dim3(tiles_x * tiles_y, F), 256, 0, s>>>(a, tiles_x);
+            k_seg_update<<<dim3(c_blocks, F), 256, 0, s>>>(a);
+        }
+        k_seg_assign<false><<<dim3(tiles_x * tiles_y, F), 256, 0, s>>>(a, tiles_x);
+    }
+    {
+        ProfScope ps(pf, O3DR_K_SEG_LABEL, s);
+        DfArgs d;
+        memset(&d, 0, sizeof d);
+        d.src = DfView{a.raw, n * (int64_t)sizeof(int32_t), (int64_t)a.cols * (int64_t)sizeof(int32_t)};
+        d.rows = a.rows, d.cols = a.cols, d.frames = F, d.max_diff = 0;
+        d.parent = a.parent, d.cnt = a.cnt;
+        k_df_local<DfLabel><<<dim3(tiles_x * tiles_y, F), 256, 0, s>>>(d, tiles_x);
+        const int n_vert = (tiles_x - 1) * a.rows, n_all = n_vert + (tiles_y - 1) * a.cols;
+        if (n_all > 0) k_df_merge<DfLabel><<<dim3(cdiv64(n_all, 256), F), 256, 0, s>>>(d, n_vert, n_all);
+        k_df_flatten<<<dim3(px_blocks, F), 256, 0, s>>>(d);
+        k_seg_key<<<dim3(px_blocks, F), 256, 0, s>>>(a);
+        k_seg_link<<<dim3(px_blocks, F), 256, 0, s>>>(a);
+        k_seg_chase<<<dim3(px_blocks, F), 256, 0, s>>>(a);
+        k_seg_flag<<<dim3(px_blocks, F), 256, 0, s>>>(a);
+        launch_scan(s, a.flag, n, n, F, nullptr, nullptr, a.partial);
+        k_seg_relabel<<<dim3(px_blocks, F), 256, 0, s>>>(a);
+    }
 }
 
 // stereo rectification: the map of one camera, then one launch per group of frames; both depend on the sizes alone

@@ -11,7 +11,7 @@
 namespace o3dr {
 
 struct Profiler {
-    uint32_t mask = 0;  // bit k: bracket launches of kernel id k
+    uint64_t mask = 0;  // bit k: bracket launches of kernel id k
     struct Pair {
         hipEvent_t a, b;
     };
@@ -71,7 +71,7 @@ struct ProfScope {
     bool on;
     ProfScope(Profiler* pf_, int kid_, hipStream_t s_) : pf(pf_), kid(kid_), s(s_), on(false)
     {
-        if (pf && (pf->mask >> kid) & 1u) {
+        if (pf && ((pf->mask >> kid) & 1u)) {
             p = pf->acquire();
             (void)hipEventRecord(p.a, s);
             on = true;

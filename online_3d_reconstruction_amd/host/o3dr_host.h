@@ -52,6 +52,8 @@ struct Image16 {                                // one 16-bit channel: a segment
 Image16 read_png_labels(const std::string& path);
 // an 8-bit greyscale PNG (stored deflate blocks: no compression); false if the file cannot be written
 bool write_png_grey8(const std::string& path, const uint8_t* data, int rows, int cols);
+// a 16-bit greyscale PNG (a segment label image, as read_png_labels reads it)
+bool write_png_grey16(const std::string& path, const uint16_t* data, int rows, int cols);
 // the same for an 8-bit interleaved B G R image (the file holds R G B, colour type 2)
 bool write_png_bgr8(const std::string& path, const uint8_t* data, int rows, int cols);
 // pcl::io::savePLYFileBinary layout (x,y,z float + r,g,b uchar, then one `camera` element); with normals (4 floats per
@@ -177,6 +179,12 @@ public:
                                       // pair, written as <left>.rectified.png and <right>.rectified.png
     int rectify_border = 0;           // --rectify_border b: what a tap outside the source reads (0..255)
     std::string filter_disparity_png;  // --filter_disparity in.png: the filter alone on an 8-bit grey PNG -> <in>.filtered.png
+    std::string segment_image_png;    // --segment_image image.png: o3dr_segment_image of one image -> <image>.labels.png (16-bit grey)
+    int segment_step = 16, segment_compactness = 20, segment_iterations = 5, segment_min_size = -1;  // --segment_step, --segment_compactness,
+                                      // --segment_iterations, --segment_min_size (negative: step * step / 4)
+    bool gpu_segment_labels = false;  // --gpu_segment_labels (under --use_segment_labels): every frame's label image comes from
+                                      // o3dr_segment_image on its rgb image, with the --segment_* flags, instead of --segment_labels_dir
+    bool segment_labels_dir_set = false;
     std::string print_label_png;      // --print_label_png f: rows, cols and the labels of f as text (checks the reader)
 
     std::vector<RawImageData> rawImageDataVec;
@@ -215,6 +223,9 @@ private:
     void run_stereo_disparity();                    // --stereo_disparity
     void compute_gpu_disparities();                 // --gpu_disparity: fills every raw frame's disparity_image
     void run_filter_disparity();                    // --filter_disparity
+    void run_segment_image();                       // --segment_image
+    void compute_gpu_segment_labels();              // --gpu_segment_labels: fills every raw frame's label_image
+    o3dr_segment_params segment_params(int channels) const;  // the --segment_* flags over the defaults
     void readRectifyCalib();                        // --rectify_calib: fills rectify_cam (no device needed)
     void run_rectify_pair();                        // --rectify_pair
     void rectify_raw_images();                      // --rectify_calib in a reconstruction run: replaces the images read

@@ -2,8 +2,8 @@
 // calls on the hot path's input side (pose_functions.cpp:526 colour, :548 IMREAD_GRAYSCALE).
 // 8-bit, non-interlaced, colour types 0/2/3/4/6 — what the reference's bundled data uses.  read_png_labels reads the
 // segment label images of --use_segment_labels: greyscale, 8 or 16 bits, non-interlaced.  write_png_grey8 writes the
-// disparity image of --stereo_disparity, write_png_bgr8 the colour images of --rectify_pair: 8 bits a sample, filter 0,
-// stored (uncompressed) deflate blocks.
+// disparity image of --stereo_disparity, write_png_bgr8 the colour images of --rectify_pair, write_png_grey16 the label
+// image of --segment_image: 8 (16: big-endian) bits a sample, filter 0, stored (uncompressed) deflate blocks.
 #include <zlib.h>
 
 #include <cstdio>
@@ -215,7 +215,8 @@ static void put_chunk(std::vector<uint8_t>& file, const char* type, const std::v
     put_be32(file, crc32_png(&file[start], file.size() - start, 0));
 }
 // `raw`: every row as its filter byte (0) and its samples; colour_type 0 (grey) or 2 (R G B)
-static bool write_png_rows(const std::string& path, const std::vector<uint8_t>& raw, int rows, int cols, uint8_t colour_type)
+static bool write_png_rows(const std::string& path, const std::vector<uint8_t>& raw, int rows, int cols, uint8_t colour_type,
+                           uint8_t depth = 8)
 {
     std::vector<uint8_t> z = {0x78, 0x01};  // zlib header: deflate, 32 KiB window, no preset dictionary
     uint32_t a = 1, b = 0;                  // Adler-32 of the raw bytes
@@ -237,7 +238,7 @@ static bool write_png_rows(const std::string& path, const std::vector<uint8_t>& 
     std::vector<uint8_t> file = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a}, ihdr;
     put_be32(ihdr, (uint32_t)cols);
     put_be32(ihdr, (uint32_t)rows);
-    const uint8_t tail[5] = {8, colour_type, 0, 0, 0};  // depth 8, colour type, deflate, adaptive filtering, no interlace
+    const uint8_t tail[5] = {depth, colour_type, 0, 0, 0};  // bit depth, colour type, deflate, adaptive filtering, no interlace
     ihdr.insert(ihdr.end(), tail, tail + 5);
     put_chunk(file, "IHDR", ihdr);
     put_chunk(file, "IDAT", z);
@@ -253,6 +254,20 @@ bool write_png_grey8(const std::string& path, const uint8_t* data, int rows, int
     std::vector<uint8_t> raw(((size_t)cols + 1) * rows);  // filter byte 0 + the row
     for (int y = 0; y < rows; ++y) memcpy(&raw[((size_t)cols + 1) * y + 1], data + (size_t)cols * y, (size_t)cols);
     return write_png_rows(path, raw, rows, cols, 0);
+}
+// 16 bits per sample, big-endian in the file: a segment label image, what read_png_labels reads
+bool write_png_grey16(const std::string& path, const uint16_t* data, int rows, int cols)
+{
+    if (!data || rows < 1 || cols < 1) return false;
+    const size_t stride = (size_t)cols * 2 + 1;
+    std::vector<uint8_t> raw(stride * rows);  // filter byte 0 + the row
+    for (int y = 0; y < rows; ++y)
+        for (int x = 0; x < cols; ++x) {
+            const uint16_t v = data[(size_t)cols * y + x];
+            raw[stride * y + 1 + (size_t)x * 2] = (uint8_t)(v >> 8);
+            raw[stride * y + 2 + (size_t)x * 2] = (uint8_t)(v & 0xFF);
+        }
+    return write_png_rows(path, raw, rows, cols, 0, 16);
 }
 // the same for an interleaved B G R image (cv::imwrite's view of a CV_8UC3 Mat): the file holds R G B
 bool write_png_bgr8(const std::string& path, const uint8_t* data, int rows, int cols)

@@ -390,7 +390,7 @@ void Pose::populateData()
                     r.right_image = read_png(rightImagePrefix + to_string(r.img_num) + ".png", false);
                 else
                     r.disparity_image = read_png(disparityPrefix + to_string(r.img_num) + ".png", true);  // :546-585
-                if (use_segment_labels) {
+                if (use_segment_labels && !gpu_segment_labels) {  // (--gpu_segment_labels: made after the reads, compute_gpu_segment_labels)
                     r.label_image = read_png_labels(segmentLabelsPrefix + to_string(r.img_num) + ".png");
                     if (!r.disparity_image.empty() &&
                         (r.label_image.rows != r.disparity_image.rows || r.label_image.cols != r.disparity_image.cols))
@@ -418,6 +418,7 @@ void Pose::populateData()
     cout << endl;
     if (!rectify_calib.empty()) rectify_raw_images();  // before anything else sees the images
     if (gpu_disparity) compute_gpu_disparities();
+    if (use_segment_labels && gpu_segment_labels) compute_gpu_segment_labels();  // where the PNGs would have been read
     for (const RawImageData& r : rawImageDataVec)
         if (!r.disparity_image.empty()) {  // rows/cols from the first readable image (:635-638)
             rows = r.disparity_image.rows;
@@ -500,6 +501,16 @@ void Pose::printUsage()
             "./pose --filter_disparity in.png [the same three flags]  (the filter alone on an 8-bit grey PNG: writes\n"
             "                     <in>.filtered.png and prints the components, the speckles, the removed pixels and the call time;\n"
             "                     at least one of the two filters must be on - the flags and the file name are this build's own)\n"
+            "./pose --segment_image image.png [--segment_step s] [--segment_compactness m] [--segment_iterations k] [--segment_min_size n]\n"
+            "                     (superpixel labels of one image: grid-seeded k-means of step s (default 16), compactness m (default\n"
+            "                     20) and k iterations (default 5), connected components, components below n pixels (default s s / 4)\n"
+            "                     merged into their nearest neighbour in colour; writes the labels as <image>.labels.png, 16-bit grey,\n"
+            "                     what --segment_labels_dir holds, and prints the centres, components, merged components, labels and\n"
+            "                     the call time; an image of more than 65536 labels is refused - the flags and the file name are this\n"
+            "                     build's own)\n"
+            "       [--use_segment_labels --gpu_segment_labels]  (reconstruction run: every frame's label image comes from the same\n"
+            "                     segmentation of its rgb image, after --rectify_calib if given, with the --segment_* flags, instead of\n"
+            "                     --segment_labels_dir, which must not be given then)\n"
             "       [--gpu_disparity --right_image_dir d/]  (reconstruction run: every frame's disparity image comes from the same\n"
             "                     matcher on image_dir/<n>.png and d/<n>.png, with the --stereo_* flags, instead of --disparity_dir;\n"
             "                     single-GPU batched path only)\n"
@@ -615,7 +626,18 @@ int Pose::parseCmdArgs(int argc, char** argv)
         else if (a == "--refine_prior_weight") refine_prior_weight = atof(need(i));
         else if (a == "--preview") preview = true;
         else if (a == "--use_segment_labels") use_segment_labels = true;
-        else if (a == "--segment_labels_dir") segmentLabelsPrefix = need(i);
+        else if (a == "--segment_labels_dir") { segmentLabelsPrefix = need(i); segment_labels_dir_set = true; }
+        else if (a == "--gpu_segment_labels") gpu_segment_labels = true;
+        else if (a == "--segment_image") {
+            if (i + 1 >= argc || string(argv[i + 1]).rfind("--", 0) == 0)
+                throw runtime_error("missing argument: --segment_image needs image.png");
+            segment_image_png = argv[++i];
+            run3d_reconstruction = false;
+        }
+        else if (a == "--segment_step") segment_step = atoi(need(i));
+        else if (a == "--segment_compactness") segment_compactness = atoi(need(i));
+        else if (a == "--segment_iterations") segment_iterations = atoi(need(i));
+        else if (a == "--segment_min_size") segment_min_size = atoi(need(i));
         else if (a == "--plane_min_pixels") plane_min_pixels = atoi(need(i));
         else if (a == "--plane_max_mse") plane_max_mse = atof(need(i));
         else if (a == "--find_features") {
@@ -679,6 +701,11 @@ int Pose::parseCmdArgs(int argc, char** argv)
         if (reference_fanout) throw runtime_error("--use_segment_labels is not available with --reference_fanout");
         if (blur_kernel > 1) throw runtime_error("--use_segment_labels cannot be combined with --blur_kernel > 1 (cv::bilateralFilter rejects CV_64F)");
     }
+    if (run3d_reconstruction && gpu_segment_labels) {
+        if (!use_segment_labels) throw runtime_error("--gpu_segment_labels makes the labels of --use_segment_labels: give both");
+        if (segment_labels_dir_set) throw runtime_error("--gpu_segment_labels cannot be combined with --segment_labels_dir");
+    }
+    if (!segment_image_png.empty() && !ifstream(segment_image_png)) throw runtime_error("could not read " + segment_image_png);
     if (run3d_reconstruction && gpu_keypoints) {
         if (n_gpus > 1 || partitioned_merge) throw runtime_error("--gpu_keypoints is not available with --gpus N > 1 / --partitioned_merge");
         if (reference_fanout) throw runtime_error("--gpu_keypoints is not available with --reference_fanout");
@@ -1026,6 +1053,82 @@ void Pose::run_filter_disparity()
     cerr << "Saved the filtered image to " << outp << endl;
 }
 
+o3dr_segment_params Pose::segment_params(int channels) const
+{
+    o3dr_segment_params prm;
+    o3dr_segment_default_params(&prm);
+    prm.channels = channels;
+    prm.step = segment_step, prm.compactness = segment_compactness, prm.iterations = segment_iterations, prm.min_size = segment_min_size;
+    return prm;
+}
+
+// Superpixel labels of one image (contract: include/o3dr.h "image segmentation"), written as <image>.labels.png, 16-bit grey.
+void Pose::run_segment_image()
+{
+    Q = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // the tool needs no camera
+    const Image8 in = read_png(segment_image_png, false);
+    if (in.empty() || (in.channels != 1 && in.channels != 3)) throw runtime_error("could not read " + segment_image_png + " as an 8-bit PNG");
+    const size_t n = (size_t)in.rows * in.cols;
+    const o3dr_segment_params prm = segment_params(in.channels);
+    vector<int32_t> labels(n);
+    o3dr_segment_info info = {};
+    o3dr_ctx* c = ctx_for_this_thread();
+    const auto t0 = chrono::steady_clock::now();
+    chk(o3dr_segment_image(c, in.data.data(), 0, in.pitch(), in.rows, in.cols, 1, &prm, labels.data(), nullptr, nullptr, &info, O3DR_MEM_HOST),
+        "o3dr_segment_image");
+    const double ms = chrono::duration<double, milli>(chrono::steady_clock::now() - t0).count();
+    cout << "image " << in.rows << " x " << in.cols << ", " << info.n_centres << " centres, " << info.n_components << " components, "
+         << info.n_merged << " merged, " << info.n_labels << " labels (largest " << info.largest << ", smallest " << info.smallest << "), "
+         << ms << " ms" << endl;
+    if (info.n_labels > 65536) throw runtime_error("more than 65536 labels: a 16-bit label image cannot hold them");
+    vector<uint16_t> lab16(n);
+    for (size_t i = 0; i < n; ++i) lab16[i] = (uint16_t)labels[i];
+    const string outp = segment_image_png + ".labels.png";
+    if (!write_png_grey16(outp, lab16.data(), in.rows, in.cols)) throw runtime_error("could not write " + outp);
+    cerr << "Saved the label image to " << outp << endl;
+}
+
+// --gpu_segment_labels: every frame's label image from o3dr_segment_image on its rgb image (as it is after --rectify_calib),
+// the frames of one size in calls of up to 16.  A frame with more than 65536 labels, or whose rgb image is not of its
+// disparity image's size, is left without a label image and is rejected like one whose label PNG could not be read.
+void Pose::compute_gpu_segment_labels()
+{
+    vector<RawImageData*> todo;
+    int prows = 0, pcols = 0;
+    for (RawImageData& r : rawImageDataVec) {
+        r.label_image = Image16();
+        if (r.rgb_image.empty() || r.rgb_image.channels != 3) continue;
+        if (!prows) prows = r.rgb_image.rows, pcols = r.rgb_image.cols;
+        if (r.rgb_image.rows == prows && r.rgb_image.cols == pcols) todo.push_back(&r);
+    }
+    if (todo.empty()) return;
+    const o3dr_segment_params prm = segment_params(3);
+    const size_t per_call = (size_t)min(seq_len > 0 ? seq_len : 16, 16), n = (size_t)prows * pcols;
+    vector<uint8_t> img(per_call * n * 3);
+    vector<int32_t> labels(per_call * n);
+    vector<o3dr_segment_info> info(per_call);
+    o3dr_ctx* c = ctx_for_this_thread();
+    size_t n_made = 0;
+    for (size_t k0 = 0; k0 < todo.size(); k0 += per_call) {
+        const size_t k1 = min(todo.size(), k0 + per_call);
+        for (size_t k = k0; k < k1; ++k) memcpy(&img[(k - k0) * n * 3], todo[k]->rgb_image.data.data(), n * 3);
+        chk(o3dr_segment_image(c, img.data(), (int64_t)(n * 3), 3 * (int64_t)pcols, prows, pcols, (int32_t)(k1 - k0), &prm, labels.data(),
+                               nullptr, nullptr, info.data(), O3DR_MEM_HOST),
+            "o3dr_segment_image");
+        for (size_t k = k0; k < k1; ++k) {
+            RawImageData& r = *todo[k];
+            if (info[k - k0].n_labels > 65536) continue;
+            if (!r.disparity_image.empty() && (r.disparity_image.rows != prows || r.disparity_image.cols != pcols)) continue;
+            Image16& li = r.label_image;
+            li.rows = prows, li.cols = pcols;
+            li.data.resize(n);
+            for (size_t i = 0; i < n; ++i) li.data[i] = (uint16_t)labels[(k - k0) * n + i];
+            ++n_made;
+        }
+    }
+    cout << "--gpu_segment_labels: " << n_made << " label images from o3dr_segment_image" << endl;
+}
+
 // Images of one size through camera `cam`'s map of that size (o3dr_rectify_maps, kept until another size is asked for) in
 // one o3dr_rectify_remap call; the output size equals the input size.
 void Pose::rectify_images(o3dr_ctx* c, int cam, const vector<Image8*>& imgs, int64_t* n_valid)
@@ -1192,6 +1295,10 @@ Pose::Pose(int argc, char* argv[])
     }
     if (!filter_disparity_png.empty()) {
         run_filter_disparity();
+        return;
+    }
+    if (!segment_image_png.empty()) {
+        run_segment_image();
         return;
     }
     if (!print_label_png.empty()) {  // what read_png_labels makes of one file: "rows cols", then one row of labels per line
