@@ -986,6 +986,101 @@ int  o3dr_disparity_filter(o3dr_ctx* ctx, const void* disp, int64_t frame_stride
                            int32_t n_frames, const o3dr_disparity_filter_params* p, void* out, int32_t* labels_out,
                            int32_t* sizes_out, o3dr_disparity_filter_info* info, int32_t mem);
 
+/* ---- multi-view filter: the geometric consistency test multi-view stereo pipelines end on.  Every rejection test before it
+ * (uniqueness, left-right, median, speckles) looks at one stereo pair; this one relates a frame's disparity image to those
+ * of other frames of the same ground through their poses: a depth is kept when other views see the same surface there,
+ * and dropped when nobody confirms it or when it floats in space that other views see through.  The reference has no
+ * such step, so there is nothing of its to pin: the contract below is this library's own; every value is computed in
+ * fp64 in a stated order without fused multiply-add, so results are bit-identical across calls, frame batchings and
+ * memory kinds; tests/multiview_reference.py restates it in numpy.
+ *
+ * Input: `disp`, n_frames images of rows x cols elements (1..8192 each) of elem_bytes bytes (1: uint8, level = v; 2: uint16,
+ * o3dr_stereo_disparity's disp_q4, level = v / 16; 8: float64, level = v), byte `pitch` and byte `frame_stride`, in `mem`.
+ * A pixel is valid iff v != 0; a float64 pixel iff v > 0 and finite.  `poses`: [n_frames][16] float32, row-major
+ * camera-to-world (what o3dr_accumulate_frames takes), always HOST.  `neighbors`: [n_frames][k] int32, always HOST, k in
+ * 0..16: the frames each frame is tested against; -1: none; an entry that equals its own frame or lies outside
+ * 0..n_frames - 1 is O3DR_ERR_INVALID_ARG; a frame listed twice votes twice.  Q is the context's camera (o3dr_set_camera).
+ *   1. Neighbours (o3dr_nearby_frames, host only, no context): a frame's position is the fp64 of its pose's translation
+ *      column; dist2 = (dx * dx + dy * dy) + dz * dz; frame i's list is the frames j != i with dist2 <= max_distance *
+ *      max_distance (an infinite max_distance takes all), ordered by (dist2, j), the first k, padded with -1.  Earlier and
+ *      later frames both count (unlike the pose chain's rule).  NULL poses or neighbors_out with n_frames * k > 0, n_frames
+ *      < 0, k outside 0..16, a negative or NaN max_distance: O3DR_ERR_INVALID_ARG.
+ *   2. Homographies: Q maps (x, y, d, 1) to a homogeneous camera point, a pose maps that to the world, so one matrix per
+ *      ordered pair carries a pixel of frame i and its level to the pixel of frame j it should appear at and the level it
+ *      should have there: H_ij = Q^-1 (T_j^-1 T_i) Q.  All fp64; every product of two 4 x 4 matrices has the elements
+ *      ((a_r0 b_0c + a_r1 b_1c) + a_r2 b_2c) + a_r3 b_3c.  T^-1 of a pose is the rigid inverse of its upper 3 x 4: rows
+ *      (R_0r, R_1r, R_2r, -((R_0r t_0 + R_1r t_1) + R_2r t_2)), r = 0..2, then (0, 0, 0, 1) - a float pose's rotation is
+ *      orthonormal to about 1e-7 only, and that is accepted: H_ii is the identity to that precision, not exactly.
+ *      E = T_j^-1 T_i, G = E Q, H = Q^-1 G.  Q^-1 is the adjugate over the determinant, with a = Q:
+ *        s0 = a00 a11 - a10 a01   s1 = a00 a12 - a10 a02   s2 = a00 a13 - a10 a03
+ *        s3 = a01 a12 - a11 a02   s4 = a01 a13 - a11 a03   s5 = a02 a13 - a12 a03
+ *        c5 = a22 a33 - a32 a23   c4 = a21 a33 - a31 a23   c3 = a21 a32 - a31 a22
+ *        c2 = a20 a33 - a30 a23   c1 = a20 a32 - a30 a22   c0 = a20 a31 - a30 a21
+ *        det = ((((s0 c5 - s1 c4) + s2 c3) + s3 c2) - s4 c1) + s5 c0
+ *        b00 = (a11 c5 - a12 c4) + a13 c3   b01 = (a02 c4 - a01 c5) - a03 c3
+ *        b02 = (a31 s5 - a32 s4) + a33 s3   b03 = (a22 s4 - a21 s5) - a23 s3
+ *        b10 = (a12 c2 - a10 c5) - a13 c1   b11 = (a00 c5 - a02 c2) + a03 c1
+ *        b12 = (a32 s2 - a30 s5) - a33 s1   b13 = (a20 s5 - a22 s2) + a23 s1
+ *        b20 = (a10 c4 - a11 c2) + a13 c0   b21 = (a01 c2 - a00 c4) - a03 c0
+ *        b22 = (a30 s4 - a31 s2) + a33 s0   b23 = (a21 s2 - a20 s4) - a23 s0
+ *        b30 = (a11 c1 - a10 c3) - a12 c0   b31 = (a00 c3 - a01 c1) + a02 c0
+ *        b32 = (a31 s1 - a30 s3) - a32 s0   b33 = (a20 s3 - a21 s1) + a22 s0
+ *      and Q^-1[r][c] = b_rc / det (a true division).  A zero or non-finite determinant is O3DR_ERR_INVALID_ARG.
+ *      o3dr_multiview_homographies returns exactly the matrices the filter uses ([n_frames][k][16], row-major, HOST; zeros
+ *      for a -1 entry), so that a wrong matrix can be told from a wrong kernel; it does no device work.
+ *   3. Tests: per valid pixel (x, y) of frame i with level d, for each listed neighbour j with H = H_ij:
+ *      h_r = ((H[r][0] x + H[r][1] y) + H[r][2] d) + H[r][3]; xp = h0 / h3, yp = h1 / h3, dp = h2 / h3 (true divisions, no
+ *      reciprocal); xr = floor(xp + 0.5), yr = floor(yp + 0.5).  The test is OUTSIDE unless h3 > 0, dp > 0, 0 <= xr < cols
+ *      and 0 <= yr < rows (every comparison is false on NaN).  Otherwise, with e the level of frame j's INPUT pixel
+ *      (xr, yr): HOLE if that pixel is invalid; SUPPORT if |e - dp| <= tolerance; VIOLATION if e < dp (j sees something
+ *      farther through the place this point claims); OCCLUDED otherwise.
+ *   4. Keep rule: support(p) and violations(p) count the tests of those two classes.  A valid pixel is kept iff support >=
+ *      min_support and (max_violations = -1: violations < support; max_violations = n >= 0: violations <= n).  A removed
+ *      pixel becomes 0; an invalid pixel passes through unchanged with both counts 0.  Neighbours are always read from
+ *      the input, never from `out`.
+ *   5. Outputs, all in `mem`, [n_frames][H][W] with rows tight: out (required, the input's element type, must not overlap
+ *      disp).  support_out, violations_out (uint8, each optional, NULL: skipped).  info (HOST, optional, one per frame):
+ *      n_valid; n_kept; n_no_support = removed with support < min_support; n_violated = removed otherwise; n_outside,
+ *      n_hole, n_support, n_violation, n_occluded = the tests of each class over (valid pixel, listed neighbour).
+ * Limits, else O3DR_ERR_INVALID_ARG before any device work (host outputs zeroed wherever rows, cols, n_frames - and for
+ * out elem_bytes - are themselves within their limits, so that the outputs' sizes are known): elem_bytes 1, 2 or 8;
+ * tolerance finite and >= 0; min_support in 0..16; max_violations in -1..16; k in 0..16; rows and cols in 1..8192; pitch >=
+ * cols * elem_bytes; frame_stride >= rows * pitch when n_frames > 1; disp, out, pitch and frame_stride aligned to
+ * elem_bytes; the neighbour entries as above; a singular Q; the bytes of out apart from the bytes of disp; n_frames >= 0
+ * (0: O3DR_OK, nothing is touched).  Without o3dr_set_camera: O3DR_ERR_NOT_CONFIGURED.  p == NULL: the defaults.  Frames
+ * read each other, so a HOST image is staged whole (frame_stride * (n_frames - 1) + pitch * (rows - 1) + cols *
+ * elem_bytes bytes): a call that does not fit returns O3DR_ERR_ALLOC (host outputs zeroed).  The matrices are made on the
+ * host and uploaded (128 bytes a pair).  One launch per 65535 frames: the number of launches depends on the sizes alone,
+ * never on the content.  The call carves its own scratch block, does not use the sort workspace, leaves cloud_big alone
+ * and synchronises the stream once, at its end. */
+#define O3DR_MULTIVIEW_MAX_SIDE 8192
+#define O3DR_MULTIVIEW_MAX_NEIGHBORS 16
+typedef struct o3dr_multiview_params {
+    int32_t elem_bytes;      /* default 1: uint8 levels; 2: uint16 sixteenths of a level (disp_q4); 8: float64 levels */
+    double  tolerance;       /* default 1.0 levels; finite, >= 0 */
+    int32_t min_support;     /* default 1; 0..16 */
+    int32_t max_violations;  /* default -1: fewer violations than supports; n in 0..16: at most n violations */
+} o3dr_multiview_params;
+typedef struct o3dr_multiview_info {   /* one per frame, HOST */
+    int64_t n_valid;        /* valid input pixels */
+    int64_t n_kept;         /* ... that stay */
+    int64_t n_no_support;   /* removed with support < min_support */
+    int64_t n_violated;     /* removed otherwise */
+    int64_t n_outside;      /* tests per class, over (valid pixel, listed neighbour) */
+    int64_t n_hole;
+    int64_t n_support;
+    int64_t n_violation;
+    int64_t n_occluded;
+} o3dr_multiview_info;
+void o3dr_multiview_default_params(o3dr_multiview_params* p);
+int  o3dr_nearby_frames(const float* poses, int32_t n_frames, int32_t k, double max_distance, int32_t* neighbors_out);
+int  o3dr_multiview_homographies(o3dr_ctx* ctx, const float* poses, int32_t n_frames, const int32_t* neighbors, int32_t k,
+                                 double* H_out);
+int  o3dr_multiview_filter(o3dr_ctx* ctx, const void* disp, int64_t frame_stride, int64_t pitch, int32_t rows, int32_t cols,
+                           int32_t n_frames, const float* poses, const int32_t* neighbors, int32_t k,
+                           const o3dr_multiview_params* p, void* out, uint8_t* support_out, uint8_t* violations_out,
+                           o3dr_multiview_info* info, int32_t mem);
+
 /* ---- image segmentation: the segment label image that o3dr_plane_fit_disparity reads (the reference takes it from offline
  * files, segmentlabels/<n>.png): grid-seeded k-means superpixels on the colour image (SLIC-like), connected components, a
  * merge of the small ones, labels numbered compactly.  There is nothing of the reference's to pin: the contract below is
@@ -1325,7 +1420,8 @@ int  o3dr_pose_graph_refine(o3dr_ctx* ctx, const uint8_t* desc, const int64_t* o
 #define O3DR_K_RECTIFY_REMAP 29  /* ... the bilinear remap of a group of frames through one map */
 #define O3DR_K_SEG_ASSIGN   30  /* image segmentation: seeds, the K + 1 assignments with their tile sums, the updates */
 #define O3DR_K_SEG_LABEL    31  /* ... components, merge of the small ones, ordered numbering, outputs */
-#define O3DR_K_NUM          32
+#define O3DR_K_MULTIVIEW    32  /* multi-view filter: the one launch of a call */
+#define O3DR_K_NUM          33
 /* Bracket every launch of kernel `kernel_id` (or all kernels if -1) with HIP events on the
  * context's stream; 0 launches are bracketed when disabled (the default). */
 int o3dr_profile_enable(o3dr_ctx* ctx, int32_t kernel_id, int32_t enable);

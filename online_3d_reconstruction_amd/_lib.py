@@ -24,11 +24,12 @@ K_STEREO_CENSUS, K_STEREO_PATHS, K_STEREO_WINNER = 22, 23, 24
 K_DISP_MEDIAN, K_DISP_LABEL, K_DISP_SPECKLE = 25, 26, 27
 K_RECTIFY_MAPS, K_RECTIFY_REMAP = 28, 29
 K_SEG_ASSIGN, K_SEG_LABEL = 30, 31
+K_MULTIVIEW = 32
 KERNEL_NAMES = ["reproject_count", "reproject_emit", "voxel_keys", "radix_hist", "radix_scatter", "run_segments",
                 "centroid", "other", "centroid_runs", "plane_disp_sums", "plane_disp_fit", "plane_disp_eval",
                 "orb_pyramid", "orb_fast", "orb_candidates", "orb_select", "orb_describe", "match", "pose_chain", "ransac",
                 "graph_moments", "graph_solve", "stereo_census", "stereo_paths", "stereo_winner", "disp_median", "disp_label",
-                "disp_speckle", "rectify_maps", "rectify_remap", "seg_assign", "seg_label"]
+                "disp_speckle", "rectify_maps", "rectify_remap", "seg_assign", "seg_label", "multiview"]
 
 
 class O3drError(RuntimeError):
@@ -135,6 +136,19 @@ class DisparityFilterInfoStruct(C.Structure):
 
 
 DISPARITY_FILTER_MAX_SIDE = 8192
+
+
+class MultiviewParamsStruct(C.Structure):
+    _fields_ = [("elem_bytes", C.c_int32), ("tolerance", C.c_double), ("min_support", C.c_int32), ("max_violations", C.c_int32)]
+
+
+class MultiviewInfoStruct(C.Structure):
+    _fields_ = [("n_valid", C.c_int64), ("n_kept", C.c_int64), ("n_no_support", C.c_int64), ("n_violated", C.c_int64),
+                ("n_outside", C.c_int64), ("n_hole", C.c_int64), ("n_support", C.c_int64), ("n_violation", C.c_int64),
+                ("n_occluded", C.c_int64)]
+
+
+MULTIVIEW_MAX_SIDE, MULTIVIEW_MAX_NEIGHBORS = 8192, 16
 
 
 class SegmentParamsStruct(C.Structure):
@@ -310,6 +324,11 @@ SYMBOLS = [
     ("o3dr_disparity_filter_default_params", None, [C.POINTER(DisparityFilterParamsStruct)]),
     ("o3dr_disparity_filter", C.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, C.POINTER(DisparityFilterParamsStruct), _vp, _vp, _vp,
                                         _vp, _i32]),
+    ("o3dr_multiview_default_params", None, [C.POINTER(MultiviewParamsStruct)]),
+    ("o3dr_nearby_frames", C.c_int, [_vp, _i32, _i32, C.c_double, _vp]),
+    ("o3dr_multiview_homographies", C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp]),
+    ("o3dr_multiview_filter", C.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _i32, C.POINTER(MultiviewParamsStruct), _vp, _vp,
+                                        _vp, _vp, _i32]),
     ("o3dr_segment_default_params", None, [C.POINTER(SegmentParamsStruct)]),
     ("o3dr_segment_image", C.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, C.POINTER(SegmentParamsStruct), _vp, _vp, _vp, _vp, _i32]),
     ("o3dr_rectify_maps", C.c_int, [_vp, C.POINTER(RectifyCameraStruct), _i32, _i32, _vp, _i32]),

@@ -117,6 +117,21 @@ class DisparityFilterInfo:
 
 
 @dataclass
+class MultiviewInfo:
+    """o3dr_multiview_filter's counts for one frame: valid pixels, those kept, those removed for lack of support and for
+    their violations, and the neighbour tests of each class over (valid pixel, listed neighbour)."""
+    n_valid: int
+    n_kept: int
+    n_no_support: int
+    n_violated: int
+    n_outside: int
+    n_hole: int
+    n_support: int
+    n_violation: int
+    n_occluded: int
+
+
+@dataclass
 class SegmentInfo:
     """o3dr_segment_image's counts for one frame: k-means centres, components of equal raw labels, components merged into
     another one, final labels, and the pixel counts of the largest and the smallest label."""
@@ -140,6 +155,16 @@ def rectifiedQ(P1, P2):
     f, cx1, cy1, cx2 = P1[0, 0], P1[0, 2], P1[1, 2], P2[0, 2]
     Tx = P2[0, 3] / P2[0, 0]
     return np.array([[1.0, 0.0, 0.0, -cx1], [0.0, 1.0, 0.0, -cy1], [0.0, 0.0, 0.0, f], [0.0, 0.0, -1.0 / Tx, (cx1 - cx2) / Tx]])
+
+
+def nearbyFrames(poses, k=4, max_distance=float("inf")):
+    """Per frame the k nearest other frames by the distance of the poses' translation columns, none farther than
+    max_distance (contract: include/o3dr.h "multi-view filter", step 1).  poses: [F, 4, 4] or [F, 16] float32 -> int32
+    [F, k], padded with -1.  Host only: needs the built library, not a GPU."""
+    poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 16)
+    out = np.full((len(poses), int(k)), -1, np.int32)
+    L.check(L.load_library().o3dr_nearby_frames(poses.ctypes.data, len(poses), int(k), float(max_distance), out.ctypes.data))
+    return out
 
 
 def _ptr(x):
@@ -856,6 +881,79 @@ class Context:
         infos = [DisparityFilterInfo(int(i.n_valid), int(i.n_components), int(i.n_speckles), int(i.n_removed), int(i.largest))
                  for i in info] if return_info else None
         return (out,) + ((labels,) if return_labels else ()) + ((sizes,) if return_sizes else ()) + ((infos,) if return_info else ())
+
+    # -- multi-view filter (the consistency test across frames that multi-view stereo pipelines end on) -----------------------
+    def multiviewHomographies(self, poses, neighbors):
+        """The matrices multiviewFilter uses: H[i, n] carries (x, y, level, 1) of frame i to frame neighbors[i, n]
+        (contract: include/o3dr.h "multi-view filter", step 2).  -> float64 [F, k, 4, 4], zeros for a -1 entry.  No device work."""
+        poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 16)
+        F = len(poses)
+        neighbors = np.ascontiguousarray(neighbors, np.int32).reshape(F, -1)
+        k = int(neighbors.shape[1])
+        H = np.zeros((F, k, 4, 4), np.float64)
+        L.check(self._lib.o3dr_multiview_homographies(self._h, poses.ctypes.data, F, neighbors.ctypes.data, k, H.ctypes.data))
+        return H
+
+    def multiviewFilter(self, disp, poses, neighbors=None, k=4, max_distance=float("inf"), tolerance=1.0, min_support=1,
+                        max_violations=-1, return_support=False, return_violations=False, return_info=False):
+        """Every valid pixel of every frame is carried into each of the frame's neighbours by their poses and compared with
+        what the neighbour saw there; it stays iff at least min_support neighbours agree within `tolerance` levels and (
+        max_violations = -1) fewer of them see through it than agree, or (n >= 0) at most n see through it - contract:
+        include/o3dr.h "multi-view filter".  disp: [F, H, W] uint8 (levels), uint16 (sixteenths) or float64 (levels), a
+        padded pitch or frame stride passes through; numpy, or a torch CUDA tensor (int16 holding the uint16 bits is taken
+        as uint16; the outputs are then CUDA tensors and nothing leaves HBM).  poses: [F, 4, 4] float32 camera-to-world,
+        host.  neighbors: int32 [F, k'] (-1: none), or None: nearbyFrames(poses, k, max_distance).  -> the filtered images
+        in the input's type; return_support / return_violations: uint8 count images follow; return_info: a list of
+        MultiviewInfo, one per frame, follows."""
+        dev = _is_torch(disp)
+        nd = disp.dim() if dev else np.ndim(disp)
+        assert nd == 3
+        F, rows, cols = (int(v) for v in disp.shape)
+        poses = np.ascontiguousarray(poses.cpu().numpy() if _is_torch(poses) else poses, np.float32).reshape(-1, 16)
+        assert len(poses) == F
+        if neighbors is None:
+            neighbors = nearbyFrames(poses, k, max_distance)
+        neighbors = np.ascontiguousarray(neighbors.cpu().numpy() if _is_torch(neighbors) else neighbors, np.int32).reshape(F, -1)
+        kk = int(neighbors.shape[1])
+        if dev:
+            import torch
+            assert disp.is_cuda and disp.dtype in (torch.uint8, torch.uint16, torch.int16, torch.float64)
+            E = disp.element_size()
+            if disp.stride(-1) != 1 or disp.stride(-2) < cols or disp.stride(0) < rows * disp.stride(-2):
+                disp = disp.contiguous()
+            pitch, fs = int(disp.stride(-2)) * E, int(disp.stride(0)) * E
+            mem, pi = L.MEM_DEVICE, disp.data_ptr()
+        else:
+            disp = np.asarray(disp)
+            assert disp.dtype in (np.uint8, np.uint16, np.float64)
+            E = disp.itemsize
+            st = disp.strides
+            if st[-1] != E or st[-2] < cols * E or st[0] < rows * st[-2]:
+                disp = np.ascontiguousarray(disp)
+            pitch, fs = int(disp.strides[-2]), int(disp.strides[0])
+            mem, pi = L.MEM_HOST, disp.ctypes.data
+        prm = L.MultiviewParamsStruct(E, float(tolerance), int(min_support), int(max_violations))
+        shape = (F, rows, cols)
+        if dev:
+            out = torch.empty(shape, dtype=disp.dtype, device=disp.device)
+            support = torch.empty(shape, dtype=torch.uint8, device=disp.device) if return_support else None
+            violations = torch.empty(shape, dtype=torch.uint8, device=disp.device) if return_violations else None
+            self._order_after_torch()
+            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        else:
+            out = np.empty(shape, disp.dtype)
+            support = np.empty(shape, np.uint8) if return_support else None
+            violations = np.empty(shape, np.uint8) if return_violations else None
+            ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        info = (L.MultiviewInfoStruct * F)() if return_info else None
+        L.check(self._lib.o3dr_multiview_filter(self._h, pi, fs, pitch, rows, cols, F, poses.ctypes.data, neighbors.ctypes.data, kk,
+                                                C.byref(prm), ptr(out), ptr(support), ptr(violations),
+                                                C.cast(info, C.c_void_p) if return_info else None, mem))
+        if not (return_support or return_violations or return_info):
+            return out
+        infos = [MultiviewInfo(*(int(getattr(i, n)) for n, _ in L.MultiviewInfoStruct._fields_)) for i in info] if return_info else None
+        return (out,) + ((support,) if return_support else ()) + ((violations,) if return_violations else ()) + \
+            ((infos,) if return_info else ())
 
     # -- image segmentation (the label image planeFitDisparity reads; the reference takes it from offline files) ---------------
     def segmentImage(self, img, step=16, compactness=20, iterations=5, min_size=None, return_raw=False, return_sizes=False,

@@ -148,6 +148,7 @@ struct o3dr_ctx {
     int64_t test_orb_scratch = 0;   // o3dr_test_orb_scratch_limit: stands in for kOrbScratchBytes when positive
     DevBuf stereo_work;        // o3dr_stereo_disparity: its own scratch block (one carve per call)
     DevBuf dfilter_work;       // o3dr_disparity_filter: its own scratch block (one carve per call)
+    DevBuf multiview_work;     // o3dr_multiview_filter: neighbour lists, matrices and counts (one carve per call)
     DevBuf rect_work;          // o3dr_rectify_remap: the staged host map (one carve per call)
     DevBuf segment_work;       // o3dr_segment_image: its own scratch block (one carve per call)
     DevBuf pl_hyp;             // o3dr_segment_plane: hypotheses + scores (plane_hyp_layout), kept for the test hook
@@ -477,7 +478,7 @@ extern "C" int o3dr_ctx_destroy(o3dr_ctx* c)
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     for (DevBuf* b : {&c->inc.box, &c->inc.scratch, &c->inc.tg, &c->inc.tmatch, &c->inc.flag, &c->inc.src, &c->inc.keep,
-                      &c->inc.partial, &c->inc.words, &c->inc.fb, &c->nn_q, &c->nn_t, &c->nn_cells, &c->nn_src, &c->pl_hyp, &c->orb_work, &c->orb_pat, &c->stereo_work, &c->dfilter_work, &c->rect_work, &c->segment_work})
+                      &c->inc.partial, &c->inc.words, &c->inc.fb, &c->nn_q, &c->nn_t, &c->nn_cells, &c->nn_src, &c->pl_hyp, &c->orb_work, &c->orb_pat, &c->stereo_work, &c->dfilter_work, &c->multiview_work, &c->rect_work, &c->segment_work})
         dev_release(*b);
     for (DevBuf& b : c->op) dev_release(b);
     delete c;
@@ -5082,6 +5083,228 @@ extern "C" int o3dr_disparity_filter(o3dr_ctx* c, const void* disp, int64_t fram
     if (rc != O3DR_OK) {
         outs.zero();
         if (info && px > 0) memset(info, 0, sizeof(o3dr_disparity_filter_info) * (size_t)n_frames);
+    }
+    return rc;
+}
+
+// =================================================================================================
+// multi-view filter (kernels/multiview.inc; DESIGN.md "Multi-view filter")
+// =================================================================================================
+extern "C" void o3dr_multiview_default_params(o3dr_multiview_params* p)
+{
+    if (!p) return;
+    p->elem_bytes = 1;
+    p->tolerance = 1.0;
+    p->min_support = 1;
+    p->max_violations = -1;
+}
+
+extern "C" int o3dr_nearby_frames(const float* poses, int32_t n_frames, int32_t k, double max_distance, int32_t* neighbors_out)
+{
+    if (n_frames < 0) return fail(O3DR_ERR_INVALID_ARG, "bad frame count");
+    if (k < 0 || k > O3DR_MULTIVIEW_MAX_NEIGHBORS) return fail(O3DR_ERR_INVALID_ARG, "k must be in 0..16");
+    if (!(max_distance >= 0.0)) return fail(O3DR_ERR_INVALID_ARG, "max_distance is negative or NaN");
+    if ((int64_t)n_frames * k == 0) return O3DR_OK;
+    if (!poses || !neighbors_out) return fail(O3DR_ERR_INVALID_ARG, "poses / neighbors_out is NULL");
+    const double lim = max_distance * max_distance;
+    std::vector<std::pair<double, int32_t>> cand;
+    for (int32_t i = 0; i < n_frames; ++i) {
+        cand.clear();
+        const float* a = poses + 16 * (size_t)i;
+        for (int32_t j = 0; j < n_frames; ++j) {
+            if (j == i) continue;
+            const float* b = poses + 16 * (size_t)j;
+            const double dx = (double)b[3] - (double)a[3], dy = (double)b[7] - (double)a[7], dz = (double)b[11] - (double)a[11];
+            const double d2 = (dx * dx + dy * dy) + dz * dz;
+            if (d2 <= lim) cand.emplace_back(d2, j);
+        }
+        std::sort(cand.begin(), cand.end());  // (dist2, j)
+        for (int32_t n = 0; n < k; ++n) neighbors_out[(size_t)i * k + n] = n < (int32_t)cand.size() ? cand[(size_t)n].second : -1;
+    }
+    return O3DR_OK;
+}
+
+// 4 x 4 fp64 products and inverses of the contract, every sum in its stated order (this file is built with -ffp-contract=off)
+static void mv_mul4(const double* a, const double* b, double* out)
+{
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c)
+            out[4 * r + c] = ((a[4 * r] * b[c] + a[4 * r + 1] * b[4 + c]) + a[4 * r + 2] * b[8 + c]) + a[4 * r + 3] * b[12 + c];
+}
+static void mv_rigid_inverse(const float* T, double* inv)
+{
+    double t[16];
+    for (int i = 0; i < 16; ++i) t[i] = (double)T[i];
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) inv[4 * r + c] = t[4 * c + r];
+        inv[4 * r + 3] = -((t[r] * t[3] + t[4 + r] * t[7]) + t[8 + r] * t[11]);
+    }
+    inv[12] = inv[13] = inv[14] = 0.0;
+    inv[15] = 1.0;
+}
+static bool mv_adjugate_inverse(const double* a, double* inv)
+{
+    const double a00 = a[0], a01 = a[1], a02 = a[2], a03 = a[3], a10 = a[4], a11 = a[5], a12 = a[6], a13 = a[7];
+    const double a20 = a[8], a21 = a[9], a22 = a[10], a23 = a[11], a30 = a[12], a31 = a[13], a32 = a[14], a33 = a[15];
+    const double s0 = a00 * a11 - a10 * a01, s1 = a00 * a12 - a10 * a02, s2 = a00 * a13 - a10 * a03;
+    const double s3 = a01 * a12 - a11 * a02, s4 = a01 * a13 - a11 * a03, s5 = a02 * a13 - a12 * a03;
+    const double c5 = a22 * a33 - a32 * a23, c4 = a21 * a33 - a31 * a23, c3 = a21 * a32 - a31 * a22;
+    const double c2 = a20 * a33 - a30 * a23, c1 = a20 * a32 - a30 * a22, c0 = a20 * a31 - a30 * a21;
+    const double det = ((((s0 * c5 - s1 * c4) + s2 * c3) + s3 * c2) - s4 * c1) + s5 * c0;
+    if (det == 0.0 || !std::isfinite(det)) return false;
+    const double b[16] = {(a11 * c5 - a12 * c4) + a13 * c3, (a02 * c4 - a01 * c5) - a03 * c3, (a31 * s5 - a32 * s4) + a33 * s3,
+                          (a22 * s4 - a21 * s5) - a23 * s3, (a12 * c2 - a10 * c5) - a13 * c1, (a00 * c5 - a02 * c2) + a03 * c1,
+                          (a32 * s2 - a30 * s5) - a33 * s1, (a20 * s5 - a22 * s2) + a23 * s1, (a10 * c4 - a11 * c2) + a13 * c0,
+                          (a01 * c2 - a00 * c4) - a03 * c0, (a30 * s4 - a31 * s2) + a33 * s0, (a21 * s2 - a20 * s4) - a23 * s0,
+                          (a11 * c1 - a10 * c3) - a12 * c0, (a00 * c3 - a01 * c1) + a02 * c0, (a31 * s1 - a30 * s3) - a32 * s0,
+                          (a20 * s3 - a21 * s1) + a22 * s0};
+    for (int i = 0; i < 16; ++i) inv[i] = b[i] / det;
+    return true;
+}
+
+// the checks the two entry points share, then H [n_frames][k][16] (zeros for a -1 entry)
+static int multiview_matrices(o3dr_ctx* c, const float* poses, int32_t n_frames, const int32_t* neighbors, int32_t k, double* H)
+{
+    if (!c->has_Q) return fail(O3DR_ERR_NOT_CONFIGURED, "o3dr_set_camera has not been called");
+    if (!poses) return fail(O3DR_ERR_INVALID_ARG, "poses is NULL");
+    if (k > 0 && !neighbors) return fail(O3DR_ERR_INVALID_ARG, "neighbors is NULL");
+    for (int64_t e = 0; e < (int64_t)n_frames * k; ++e) {
+        const int32_t j = neighbors[e];
+        if (j == -1) continue;
+        if (j < 0 || j >= n_frames) return fail(O3DR_ERR_INVALID_ARG, "a neighbour lies outside 0..n_frames - 1");
+        if (j == (int32_t)(e / k)) return fail(O3DR_ERR_INVALID_ARG, "a frame is listed as its own neighbour");
+    }
+    double Qinv[16];
+    if (!mv_adjugate_inverse(c->Q, Qinv)) return fail(O3DR_ERR_INVALID_ARG, "Q is singular");
+    std::vector<double> Tinv((size_t)n_frames * 16), Td((size_t)n_frames * 16);
+    for (int32_t f = 0; f < n_frames; ++f) {
+        mv_rigid_inverse(poses + 16 * (size_t)f, &Tinv[16 * (size_t)f]);
+        for (int i = 0; i < 16; ++i) Td[16 * (size_t)f + i] = (double)poses[16 * (size_t)f + i];
+    }
+    for (int64_t e = 0; e < (int64_t)n_frames * k; ++e) {
+        const int32_t j = neighbors[e];
+        double* out = H + 16 * e;
+        if (j < 0) {
+            memset(out, 0, 16 * sizeof(double));
+            continue;
+        }
+        double E[16], G[16];
+        mv_mul4(&Tinv[16 * (size_t)j], &Td[16 * (size_t)(e / k)], E);
+        mv_mul4(E, c->Q, G);
+        mv_mul4(Qinv, G, out);
+    }
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_multiview_homographies(o3dr_ctx* c, const float* poses, int32_t n_frames, const int32_t* neighbors, int32_t k,
+                                           double* H_out)
+{
+    const bool sized = n_frames >= 0 && k >= 0 && k <= O3DR_MULTIVIEW_MAX_NEIGHBORS;
+    const int rc = entered(c, [&] {
+        if (n_frames < 0) return fail(O3DR_ERR_INVALID_ARG, "bad frame count");
+        if (k < 0 || k > O3DR_MULTIVIEW_MAX_NEIGHBORS) return fail(O3DR_ERR_INVALID_ARG, "k must be in 0..16");
+        if ((int64_t)n_frames * k == 0) return (int)O3DR_OK;
+        if (!H_out) return fail(O3DR_ERR_INVALID_ARG, "H_out is NULL");
+        return multiview_matrices(c, poses, n_frames, neighbors, k, H_out);
+    });
+    if (rc != O3DR_OK && sized && H_out) memset(H_out, 0, (size_t)n_frames * (size_t)k * 16 * sizeof(double));
+    return rc;
+}
+
+static bool multiview_shape_ok(int32_t rows, int32_t cols, int32_t n_frames)
+{
+    return rows >= 1 && rows <= O3DR_MULTIVIEW_MAX_SIDE && cols >= 1 && cols <= O3DR_MULTIVIEW_MAX_SIDE && n_frames >= 0;
+}
+static bool multiview_elem_ok(int32_t e) { return e == 1 || e == 2 || e == 8; }
+
+static int multiview_filter(o3dr_ctx* c, const void* disp, int64_t fs, int64_t pitch, int32_t rows, int32_t cols, int32_t n_frames,
+                            const float* poses, const int32_t* neighbors, int32_t k, const o3dr_multiview_params* p, uint8_t* out,
+                            uint8_t* support_out, uint8_t* violations_out, o3dr_multiview_info* info, Outputs& outs, int32_t mem)
+{
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    if (n_frames < 0) return fail(O3DR_ERR_INVALID_ARG, "bad frame count");
+    o3dr_multiview_params prm;
+    o3dr_multiview_default_params(&prm);
+    if (p) prm = *p;
+    if (!multiview_shape_ok(rows, cols, 0)) return fail(O3DR_ERR_INVALID_ARG, "rows and cols must be in 1..8192");
+    if (!multiview_elem_ok(prm.elem_bytes)) return fail(O3DR_ERR_INVALID_ARG, "elem_bytes must be 1, 2 or 8");
+    if (!(prm.tolerance >= 0.0) || !std::isfinite(prm.tolerance)) return fail(O3DR_ERR_INVALID_ARG, "tolerance must be finite and >= 0");
+    if (prm.min_support < 0 || prm.min_support > O3DR_MULTIVIEW_MAX_NEIGHBORS) return fail(O3DR_ERR_INVALID_ARG, "min_support must be in 0..16");
+    if (prm.max_violations < -1 || prm.max_violations > O3DR_MULTIVIEW_MAX_NEIGHBORS)
+        return fail(O3DR_ERR_INVALID_ARG, "max_violations must be in -1..16");
+    if (k < 0 || k > O3DR_MULTIVIEW_MAX_NEIGHBORS) return fail(O3DR_ERR_INVALID_ARG, "k must be in 0..16");
+    if (n_frames == 0) return O3DR_OK;
+    if (!disp || !out) return fail(O3DR_ERR_INVALID_ARG, "disp / out is NULL");
+    const int64_t E = prm.elem_bytes;
+    if (pitch < (int64_t)cols * E) return fail(O3DR_ERR_INVALID_ARG, "pitch smaller than a row");
+    if (n_frames > 1 && fs < (int64_t)rows * pitch) return fail(O3DR_ERR_INVALID_ARG, "frame stride smaller than a frame");
+    if ((uintptr_t)disp % (uintptr_t)E || (uintptr_t)out % (uintptr_t)E || pitch % E || (n_frames > 1 && fs % E))
+        return fail(O3DR_ERR_INVALID_ARG, "images must be aligned to their element size");
+    const size_t n = (size_t)rows * (size_t)cols;
+    const size_t in_bytes = (size_t)fs * (size_t)(n_frames - 1) + (size_t)pitch * (size_t)(rows - 1) + (size_t)cols * (size_t)E;
+    {  // the byte ranges [disp, disp + in_bytes) and [out, out + n_frames * rows * cols * E), in either memory kind
+        const uintptr_t i0 = (uintptr_t)disp, o0 = (uintptr_t)out;
+        if (i0 < o0 + (uintptr_t)n_frames * n * (uintptr_t)E && o0 < i0 + in_bytes) return fail(O3DR_ERR_INVALID_ARG, "out must not overlap disp");
+    }
+    const size_t n_pairs = (size_t)n_frames * (size_t)k;
+    std::vector<double> H(n_pairs * 16);  // (outlives the upload: the call synchronises at its end)
+    CHK(multiview_matrices(c, poses, n_frames, neighbors, k, H.data()));
+
+    const void* disp_d;
+    CHK(stage_in(c, c->op[o3dr_ctx::OP_IN], disp, in_bytes, mem, &disp_d));
+    MvArgs a;
+    memset(&a, 0, sizeof a);
+    a.in = disp_d, a.fstride = fs, a.pitch = pitch;
+    a.rows = rows, a.cols = cols, a.frames = n_frames, a.elem = prm.elem_bytes, a.k = k;
+    a.min_support = prm.min_support, a.max_violations = prm.max_violations, a.tolerance = prm.tolerance;
+    double* H_d = nullptr;
+    int32_t* nb_d = nullptr;
+    CHK(carve(c, c->multiview_work, [&](Carve& w) {
+        w.take(H_d, n_pairs * 16);
+        w.take(nb_d, n_pairs);
+        if (info) w.take(a.info, (size_t)n_frames * 9);
+    }));
+    if (n_pairs) {
+        HIPCHK(hipMemcpyAsync(H_d, H.data(), n_pairs * 16 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(nb_d, neighbors, n_pairs * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    }
+    if (info) HIPCHK(hipMemsetAsync(a.info, 0, (size_t)n_frames * 9 * sizeof(unsigned long long), c->stream));
+    CHK(outs.stage(c));
+    a.H = H_d, a.neighbors = nb_d;
+    a.out = outs.dev(out), a.support_out = outs.dev(support_out), a.violations_out = outs.dev(violations_out);
+    launch_multiview_filter(&c->prof, c->stream, a);
+    HIPCHK(hipGetLastError());
+    CHK(outs.copy_back(c));
+    std::vector<unsigned long long> counts(info ? (size_t)n_frames * 9 : 0);
+    if (info) HIPCHK(hipMemcpyAsync(counts.data(), a.info, counts.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (size_t f = 0; info && f < (size_t)n_frames; ++f) {
+        const unsigned long long* q = &counts[f * 9];
+        info[f] = o3dr_multiview_info{(int64_t)q[0], (int64_t)q[1], (int64_t)q[2], (int64_t)q[3], (int64_t)q[4],
+                                      (int64_t)q[5], (int64_t)q[6], (int64_t)q[7], (int64_t)q[8]};
+    }
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_multiview_filter(o3dr_ctx* c, const void* disp, int64_t frame_stride, int64_t pitch, int32_t rows, int32_t cols,
+                                     int32_t n_frames, const float* poses, const int32_t* neighbors, int32_t k,
+                                     const o3dr_multiview_params* p, void* out, uint8_t* support_out, uint8_t* violations_out,
+                                     o3dr_multiview_info* info, int32_t mem)
+{
+    // the outputs' sizes are known only where the shape itself (and for `out` the element size) is within its limits
+    const int64_t px = multiview_shape_ok(rows, cols, n_frames) ? (int64_t)n_frames * rows * cols : 0;
+    const int32_t elem = p ? p->elem_bytes : 1;
+    Outputs outs{mem};
+    outs.add((uint8_t*)out, multiview_elem_ok(elem) ? px * elem : 0);
+    outs.add(support_out, px);
+    outs.add(violations_out, px);
+    const int rc = entered(c, [&] {
+        return multiview_filter(c, disp, frame_stride, pitch, rows, cols, n_frames, poses, neighbors, k, p, (uint8_t*)out, support_out,
+                                violations_out, info, outs, mem);
+    });
+    if (rc != O3DR_OK) {
+        outs.zero();
+        if (info && px > 0) memset(info, 0, sizeof(o3dr_multiview_info) * (size_t)n_frames);
     }
     return rc;
 }

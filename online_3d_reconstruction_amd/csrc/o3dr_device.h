@@ -634,6 +634,21 @@ struct DfArgs {
     void* out;
 };
 void launch_disparity_filter(Profiler* pf, hipStream_t s, const DfArgs& a);
+// Multi-view filter (kernels/multiview.inc; contract: include/o3dr.h "multi-view filter").  One MvArgs describes the whole
+// call: `in` with its byte strides, the neighbour lists [frames][k] and their matrices [frames][k][16] (row-major, made on
+// the host), the outputs with rows tight.  info: [frames][9] in o3dr_multiview_info's order; nullptr: not asked for.
+struct MvArgs {
+    const void* in;
+    int64_t fstride, pitch;
+    int32_t rows, cols, frames, f0, elem, k, min_support, max_violations;  // f0: set by the launcher (a launch's first frame)
+    double tolerance;
+    const int32_t* neighbors;
+    const double* H;
+    void* out;
+    uint8_t *support_out, *violations_out;  // each nullptr: not asked for
+    unsigned long long* info;
+};
+void launch_multiview_filter(Profiler* pf, hipStream_t s, const MvArgs& a);
 // Image segmentation (kernels/segment_image.inc; contract: include/o3dr.h "image segmentation").  One SegArgs describes a
 // group of `frames` frames; every array holds the group's frames one after the other.  centres: [nx * ny][5] int32 x, y,
 // B, G, R; sums: [nx * ny][6] n, sum x, sum y, sum B, sum G, sum R.  Per pixel: raw (the centre index), parent / cnt (the

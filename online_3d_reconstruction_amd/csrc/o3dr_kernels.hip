@@ -36,6 +36,7 @@
 //   orb          ORB features: grey pyramid, FAST score + box sums, candidates, exact selection, steered BRIEF
 //   stereo       stereo disparity: grey + census, semi-global aggregation (one wave per scan line), winner + left-right check
 //   disparity_filter  median and speckle removal of a disparity image: LDS median network, tiled union-find labelling
+//   multiview    multi-view consistency of a stack of disparity images: one fp64 matrix per (frame, neighbour), one gather per test
 //   segment_image  superpixel labels of a colour image: tiled k-means with LDS sums, the filter's union-find, merge, ordered numbering
 //   rectify      stereo rectification: the fp64 Q5 map of one camera, the integer bilinear remap of a group of frames
 //   pose_chain   the feature-matched pose chain: one workgroup walks the frames (gather, moments, Kabsch, residual)
@@ -69,6 +70,7 @@ namespace o3dr {
 #include "kernels/orb.inc"
 #include "kernels/stereo.inc"
 #include "kernels/disparity_filter.inc"
+#include "kernels/multiview.inc"
 #include "kernels/segment_image.inc"
 #include "kernels/rectify.inc"
 #include "kernels/pose_chain.inc"
@@ -771,6 +773,29 @@ void launch_disparity_filter(Profiler* pf, hipStream_t s, const DfArgs& a)
         disparity_filter_frames<uint8_t>(pf, s, a);
     else
         disparity_filter_frames<uint16_t>(pf, s, a);
+}
+
+// multi-view filter: one launch per 65535 frames (the grid's y extent); the launches depend on the sizes alone
+template <class T>
+static void multiview_frames(Profiler* pf, hipStream_t s, MvArgs a)
+{
+    ProfScope ps(pf, O3DR_K_MULTIVIEW, s);
+    const int tiles_x = cdiv64(a.cols, kMvTileX), tiles_y = cdiv64(a.rows, kMvTileY);
+    for (int f0 = 0; f0 < a.frames; f0 += 65535) {
+        a.f0 = f0;
+        const int nf = a.frames - f0 < 65535 ? a.frames - f0 : 65535;
+        k_multiview_filter<T><<<dim3(tiles_x * tiles_y, nf), kMvTileX * kMvTileY, 0, s>>>(a, tiles_x);
+    }
+}
+void launch_multiview_filter(Profiler* pf, hipStream_t s, const MvArgs& a)
+{
+    if (a.frames <= 0) return;
+    if (a.elem == 1)
+        multiview_frames<uint8_t>(pf, s, a);
+    else if (a.elem == 2)
+        multiview_frames<uint16_t>(pf, s, a);
+    else
+        multiview_frames<double>(pf, s, a);
 }
 
 // image segmentation of one group of frames (a.frames <= 65535: the grid's y extent); the launches depend on the

@@ -185,6 +185,13 @@ public:
     bool gpu_segment_labels = false;  // --gpu_segment_labels (under --use_segment_labels): every frame's label image comes from
                                       // o3dr_segment_image on its rgb image, with the --segment_* flags, instead of --segment_labels_dir
     bool segment_labels_dir_set = false;
+    bool multiview_filter = false;    // --multiview_filter: every cycle's accepted frames go through o3dr_multiview_filter once the
+                                      // cycle's poses are final (recorded, --feature_poses, --refine_poses) and before they are
+                                      // accumulated; neighbours are chosen among that cycle's accepted frames (single-GPU batched path)
+    int mv_neighbors = 4;             // --mv_neighbors k, --mv_max_distance m: o3dr_nearby_frames; parsed and ignored without the flag
+    double mv_max_distance = HUGE_VAL;
+    double mv_tolerance = 1.0;        // --mv_tolerance t (levels), --mv_min_support n, --mv_max_violations n (-1: the majority rule)
+    int mv_min_support = 1, mv_max_violations = -1;
     std::string print_label_png;      // --print_label_png f: rows, cols and the labels of f as text (checks the reader)
 
     std::vector<RawImageData> rawImageDataVec;

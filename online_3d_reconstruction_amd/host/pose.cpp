@@ -531,6 +531,15 @@ void Pose::printUsage()
             "                     the cycle's matched frames over all of its pairs (earlier cycles held; --refine_gn_iterations,\n"
             "                     default 5, Gauss-Newton steps of --refine_cg_iterations, default 32, CG steps; --refine_prior_weight,\n"
             "                     default 0, pulls every free frame's position to its recorded one); one line per cycle reports it\n"
+            "       [--multiview_filter] [--mv_neighbors k] [--mv_max_distance m] [--mv_tolerance t] [--mv_min_support n] [--mv_max_violations n]\n"
+            "                     (reconstruction run: once a cycle's poses are final and before its frames are accumulated, every\n"
+            "                     pixel of every accepted frame is carried into the frame's k nearest accepted frames of the same cycle\n"
+            "                     (default 4, none farther than m metres, default: no limit) and stays iff at least n of them (default 1)\n"
+            "                     saw the same surface within t disparity levels (default 1) and fewer saw through it than agreed\n"
+            "                     (--mv_max_violations n >= 0: at most n saw through it); one line per cycle reports the pixels kept;\n"
+            "                     the variance gate has seen the unfiltered image; not available with --gpus N > 1,\n"
+            "                     --partitioned_merge, --reference_fanout, --use_segment_labels, --blur_kernel > 1; without the flag the\n"
+            "                     --mv_* flags are parsed and ignored; the flags are this build's own)\n"
             "Without --feature_poses the run uses the recorded MAVLink poses (--only_MAVLink).  The ICP trajectory correction,\n"
             "visualisation and --segment_cloud in a reconstruction run are not part of this build.\n";
 }
@@ -685,6 +694,12 @@ int Pose::parseCmdArgs(int argc, char** argv)
         else if (a == "--orb_levels") orb_levels = atoi(need(i));
         else if (a == "--orb_scale") orb_scale = (float)atof(need(i));
         else if (a == "--orb_fast_threshold") orb_fast_threshold = atoi(need(i));
+        else if (a == "--multiview_filter") multiview_filter = true;
+        else if (a == "--mv_neighbors") mv_neighbors = atoi(need(i));
+        else if (a == "--mv_max_distance") mv_max_distance = atof(need(i));
+        else if (a == "--mv_tolerance") mv_tolerance = atof(need(i));
+        else if (a == "--mv_min_support") mv_min_support = atoi(need(i));
+        else if (a == "--mv_max_violations") mv_max_violations = atoi(need(i));
         else if (a == "--print_label_png") { print_label_png = need(i); run3d_reconstruction = false; }
         else if (a == "--segment_cloud" || a == "--displayUAVPositions" ||
                  a == "--test_bad_data_rejection")
@@ -700,6 +715,14 @@ int Pose::parseCmdArgs(int argc, char** argv)
         if (n_gpus > 1 || partitioned_merge) throw runtime_error("--use_segment_labels is not available with --gpus N > 1 / --partitioned_merge");
         if (reference_fanout) throw runtime_error("--use_segment_labels is not available with --reference_fanout");
         if (blur_kernel > 1) throw runtime_error("--use_segment_labels cannot be combined with --blur_kernel > 1 (cv::bilateralFilter rejects CV_64F)");
+    }
+    if (run3d_reconstruction && multiview_filter) {
+        // the filter sits between the cycle's poses and the batched accumulate call: the paths without that call say so
+        if (n_gpus > 1) throw runtime_error("--multiview_filter is not available with --gpus N > 1");
+        if (partitioned_merge) throw runtime_error("--multiview_filter is not available with --partitioned_merge");
+        if (reference_fanout) throw runtime_error("--multiview_filter is not available with --reference_fanout");
+        if (use_segment_labels) throw runtime_error("--multiview_filter is not available with --use_segment_labels (its images are CV_64F fits)");
+        if (blur_kernel > 1) throw runtime_error("--multiview_filter is not available with --blur_kernel > 1 (the blur would run on the filtered image)");
     }
     if (run3d_reconstruction && gpu_segment_labels) {
         if (!use_segment_labels) throw runtime_error("--gpu_segment_labels makes the labels of --use_segment_labels: give both");
@@ -1577,6 +1600,34 @@ void Pose::run_reconstruction()
                     }
                     if (!kp_xy.empty()) kp_xy.resize(kp_rows * 2);
                     cout << "Adding Point Cloud number/points: " << n_cloud << " of " << n_acc << " frames" << flush;
+                }
+            }
+            // --multiview_filter: the frames that go into the cloud, with their final poses, vote on each other's pixels
+            if (multiview_filter && rc_orb == O3DR_OK && rc_fit == O3DR_OK && rc_chain == O3DR_OK && n_cloud > 0) {
+                const auto tm = clk::now();
+                o3dr_multiview_params mp;
+                o3dr_multiview_default_params(&mp);
+                mp.tolerance = mv_tolerance;
+                mp.min_support = mv_min_support;
+                mp.max_violations = mv_max_violations;
+                const int32_t nk = (int32_t)mv_neighbors;
+                vector<int32_t> nb((size_t)n_cloud * (size_t)(nk > 0 && nk <= O3DR_MULTIVIEW_MAX_NEIGHBORS ? nk : 0) + 1);
+                vector<uint8_t> kept(dsz * n_cloud);
+                vector<o3dr_multiview_info> mi(n_cloud);
+                rc_chain = o3dr_nearby_frames(poses.data(), (int32_t)n_cloud, nk, mv_max_distance, nb.data());
+                if (rc_chain == O3DR_OK)
+                    rc_chain = o3dr_multiview_filter(c, disp.data(), (int64_t)dsz, cols, rows, cols, (int32_t)n_cloud, poses.data(), nb.data(), nk,
+                                                     &mp, kept.data(), nullptr, nullptr, mi.data(), O3DR_MEM_HOST);
+                if (rc_chain != O3DR_OK) why_chain = string("multiview_filter: ") + o3dr_last_error();
+                else {
+                    memcpy(disp.data(), kept.data(), kept.size());
+                    int64_t n_pairs = 0, n_valid = 0, n_kept = 0, n_nosup = 0, n_viol = 0;
+                    for (size_t e = 0; e < (size_t)n_cloud * (size_t)nk; ++e) n_pairs += nb[e] >= 0;
+                    for (const o3dr_multiview_info& m : mi)
+                        n_valid += m.n_valid, n_kept += m.n_kept, n_nosup += m.n_no_support, n_viol += m.n_violated;
+                    cout << "\nmultiview filter: " << n_cloud << " frames, " << n_pairs << " pairs, kept " << n_kept << " of " << n_valid
+                         << " pixels (" << n_nosup << " without support, " << n_viol << " violated), "
+                         << chrono::duration<double>(clk::now() - tm).count() << " sec" << flush;
                 }
             }
             const int rc_acc = rc_orb != O3DR_OK ? rc_orb : rc_fit != O3DR_OK ? rc_fit : rc_chain != O3DR_OK ? rc_chain : n_cloud == 0 ? O3DR_OK
