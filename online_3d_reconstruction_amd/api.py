@@ -7,6 +7,7 @@ happens in libo3dr.so; numpy arrays are staged by the library, torch CUDA tensor
 HBM pointers (torch is only device memory + streams here).
 """
 import ctypes as C
+from collections import namedtuple
 from dataclasses import dataclass
 
 import numpy as np
@@ -165,6 +166,48 @@ def nearbyFrames(poses, k=4, max_distance=float("inf")):
     out = np.full((len(poses), int(k)), -1, np.int32)
     L.check(L.load_library().o3dr_nearby_frames(poses.ctypes.data, len(poses), int(k), float(max_distance), out.ctypes.data))
     return out
+
+
+StackLayout = namedtuple("StackLayout", "single F rows cols ch pitch fs copy")
+
+
+def image_stack_layout(shape, strides, itemsize, colour, contiguous=False):
+    """How the image operators read an array as a stack of images (the library's side of the contract:
+    csrc/o3dr_image_stack.h).  shape / strides (in bytes) / itemsize: the array's; colour=True: uint8 images, [H, W] or
+    [F, H, W] grey, [H, W, 3] or [F, H, W, 3] B G R (a 3-D array whose last axis is 3 is one B G R image); colour=False:
+    images of itemsize-byte elements, [H, W] or [F, H, W].  -> StackLayout: single (one image, no frame axis), F, rows, cols,
+    ch, pitch and fs in bytes (fs 0 for a single image) and copy: whether the array must be made contiguous first - pitch and
+    fs are then those of the copy.  Dense pixels with rows at least a row apart and frames at least a frame apart pass through as
+    they are, padding included; contiguous=True asks for the copy regardless.  Pure: no array is touched."""
+    nd, E = len(shape), int(itemsize)
+    ch = 3 if colour and (nd == 4 or (nd == 3 and int(shape[-1]) == 3)) else 1
+    assert nd in ((3, 4) if ch == 3 else (2, 3))
+    single = nd == (3 if ch == 3 else 2)
+    row_axis = -3 if ch == 3 else -2
+    F, rows, cols = (1 if single else int(shape[0])), int(shape[row_axis]), int(shape[row_axis + 1])
+    st = [int(v) for v in strides]
+    passes = st[-1] == E and (ch == 1 or st[-2] == 3 * E) and st[row_axis] >= cols * ch * E and (single or st[0] >= rows * st[row_axis])
+    if passes and not contiguous:
+        return StackLayout(single, F, rows, cols, ch, st[row_axis], 0 if single else st[0], False)
+    pitch = cols * ch * E
+    return StackLayout(single, F, rows, cols, ch, pitch, 0 if single else rows * pitch, True)
+
+
+_TORCH_DTYPE = {np.uint8: "uint8", np.uint16: "int16", np.int32: "int32", np.float32: "float32"}
+
+
+def _dtype_name(x):
+    """"uint8", "int16", ...: of a numpy array or a torch tensor"""
+    return str(x.dtype).replace("torch.", "")
+
+
+def _itemsize(x):
+    return x.element_size() if _is_torch(x) else x.itemsize
+
+
+def _addr(x):
+    """the address of an output array or tensor (None: not asked for)"""
+    return None if x is None else (x.data_ptr() if _is_torch(x) else x.ctypes.data)
 
 
 def _ptr(x):
@@ -594,6 +637,35 @@ class Context:
             ret += (til[:n],)
         return ret
 
+    # -- image stacks: the inputs and outputs of the image operators below ------------------------------------------------
+    @staticmethod
+    def _image_stack(x, colour, contiguous=False):
+        """A numpy array or a torch CUDA tensor as the library reads it (image_stack_layout) -> (x, made contiguous where
+        its layout does not pass through; its StackLayout; its address; its MEM kind)."""
+        if _is_torch(x):
+            assert x.is_cuda
+            E = _itemsize(x)
+            lay = image_stack_layout(tuple(x.shape), [v * E for v in x.stride()], E, colour, contiguous)
+            x = x.contiguous() if lay.copy else x
+            return x, lay, x.data_ptr(), L.MEM_DEVICE
+        x = np.asarray(x)
+        lay = image_stack_layout(x.shape, x.strides, x.itemsize, colour, contiguous)
+        x = np.ascontiguousarray(x) if lay.copy else x
+        return x, lay, x.ctypes.data, L.MEM_HOST
+
+    def _empty_like(self, like, *specs):
+        """Uninitialised outputs of `like`'s memory kind, one per (shape, dtype) and None per None.  dtype: a numpy type - a
+        tensor gets the torch type of _TORCH_DTYPE, for uint16 int16 (which holds the bits) - or a torch type as it is.  The
+        library call may follow at once: it is ordered behind torch's work."""
+        if not _is_torch(like):
+            return [None if sp is None else np.empty(*sp) for sp in specs]
+        import torch
+        outs = [None if sp is None else
+                torch.empty(sp[0], dtype=sp[1] if isinstance(sp[1], torch.dtype) else getattr(torch, _TORCH_DTYPE[sp[1]]), device=like.device)
+                for sp in specs]
+        self._order_after_torch()
+        return outs
+
     # -- ORB features (the reference's findFeatures / OrbFeaturesFinder, pose.cpp:127,210) -------------------------------
     def findFeatures(self, img, n_features=1500, scale_factor=1.3, n_levels=5, fast_threshold=20, edge=31, return_levels=False):
         """oFAST keypoints and steered-BRIEF descriptors (contract: include/o3dr.h "ORB features").  img: uint8 [H, W] or
@@ -604,53 +676,20 @@ class Context:
         offsets)) (accumulateFrames splits the pair into per-frame lists on the host: a CUDA kp_xy is read back there).
         return_levels: a fifth value, every frame's grey pyramid as a flat uint8 array (frame-major, levels back to back,
         rows tight)."""
+        img, (_, F, rows, cols, ch, pitch, fs, _), pi, mem = self._image_stack(img, colour=True)
         dev = _is_torch(img)
-        nd = img.dim() if dev else np.ndim(img)
-        ch = 3 if (nd == 4 or (nd == 3 and int(img.shape[-1]) == 3)) else 1
-        if not dev:
-            img = np.asarray(img)
-            assert img.dtype == np.uint8
-        single = nd == (3 if ch == 3 else 2)
-        assert nd in ((3, 4) if ch == 3 else (2, 3))
-        F = 1 if single else int(img.shape[0])
-        rows, cols = (int(img.shape[-3]), int(img.shape[-2])) if ch == 3 else (int(img.shape[-2]), int(img.shape[-1]))
-        if dev:
-            import torch
-            assert img.is_cuda and img.dtype == torch.uint8
-            if img.stride(-1) != 1 or (ch == 3 and img.stride(-2) != 3) or (not single and img.stride(0) < rows * img.stride(-3 if ch == 3 else -2)):
-                img = img.contiguous()
-            pitch, fs = int(img.stride(-3 if ch == 3 else -2)), (0 if single else int(img.stride(0)))
-            mem, pi = L.MEM_DEVICE, img.data_ptr()
-        else:
-            row_axis = -3 if ch == 3 else -2
-            st = img.strides
-            ok = st[-1] == 1 and (ch == 1 or st[-2] == 3) and st[row_axis] >= cols * ch and (single or st[0] >= rows * st[row_axis])
-            if not ok:  # (a padded pitch or frame stride is passed through as it is)
-                img = np.ascontiguousarray(img)
-            pitch, fs = int(img.strides[row_axis]), (0 if single else int(img.strides[0]))
-            mem, pi = L.MEM_HOST, img.ctypes.data
+        assert _dtype_name(img) == "uint8"
         prm = L.OrbParamsStruct(int(n_features), float(scale_factor), int(n_levels), int(fast_threshold), int(edge), ch)
         wh = np.zeros(2 * max(int(n_levels), 1), np.int32)
         L.check(self._lib.o3dr_orb_level_sizes(rows, cols, C.byref(prm), wh.ctypes.data, None))
         cap = max(F * int(n_features), 1)
         n_lev = F * int(sum(int(wh[2 * l]) * int(wh[2 * l + 1]) for l in range(int(n_levels)))) if return_levels else 0
-        if dev:
-            kp = torch.empty((cap, 8), dtype=torch.int32, device=img.device)
-            xy = torch.empty((cap, 2), dtype=torch.float32, device=img.device)
-            desc = torch.empty((cap, 32), dtype=torch.uint8, device=img.device)
-            lev = torch.empty(max(n_lev, 1), dtype=torch.uint8, device=img.device) if return_levels else None
-            self._order_after_torch()
-            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        else:
-            kp = np.empty(cap, L.ORB_KEYPOINT)
-            xy = np.empty((cap, 2), np.float32)
-            desc = np.empty((cap, 32), np.uint8)
-            lev = np.empty(max(n_lev, 1), np.uint8) if return_levels else None
-            ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        kp, xy, desc, lev = self._empty_like(img, ((cap, 8), np.int32) if dev else (cap, L.ORB_KEYPOINT), ((cap, 2), np.float32),
+                                             ((cap, 32), np.uint8), (max(n_lev, 1), np.uint8) if return_levels else None)
         off = np.zeros(F + 1, np.int64)
         n = C.c_int64(0)
-        L.check(self._lib.o3dr_orb_detect(self._h, pi, fs, pitch, rows, cols, F, C.byref(prm), ptr(kp), ptr(xy), ptr(desc),
-                                          off.ctypes.data, ptr(lev), cap, C.byref(n), mem))
+        L.check(self._lib.o3dr_orb_detect(self._h, pi, fs, pitch, rows, cols, F, C.byref(prm), _addr(kp), _addr(xy), _addr(desc),
+                                          off.ctypes.data, _addr(lev), cap, C.byref(n), mem))
         k = int(n.value)
         res = (kp[:k], xy[:k], desc[:k], off)
         return res + (lev[:n_lev],) if return_levels else res
@@ -698,45 +737,19 @@ class Context:
         dev = _is_torch(img)
         if dev != _is_torch(maps):
             raise L.O3drError(L.ERR_INVALID_ARG, "maps must be of the same memory kind as img")
-        nd = img.dim() if dev else np.ndim(img)
-        ch = 3 if (nd == 4 or (nd == 3 and int(img.shape[-1]) == 3)) else 1
-        single = nd == (3 if ch == 3 else 2)
-        assert nd in ((3, 4) if ch == 3 else (2, 3))
-        F = 1 if single else int(img.shape[0])
-        rows, cols = (int(img.shape[-3]), int(img.shape[-2])) if ch == 3 else (int(img.shape[-2]), int(img.shape[-1]))
-        row_axis = -3 if ch == 3 else -2
+        img, (single, F, rows, cols, ch, pitch, fs, _), pi, mem = self._image_stack(img, colour=True)
+        assert _dtype_name(img) == "uint8"
         assert len(maps.shape) == 3 and int(maps.shape[2]) == 2
         rows_out, cols_out = int(maps.shape[0]), int(maps.shape[1])
         if dev:
-            import torch
-            assert img.is_cuda and maps.is_cuda and img.dtype == torch.uint8 and maps.dtype == torch.int32
-            if not (img.stride(-1) == 1 and (ch == 1 or img.stride(-2) == 3) and img.stride(row_axis) >= cols * ch and
-                    (single or img.stride(0) >= rows * img.stride(row_axis))):
-                img = img.contiguous()
+            assert maps.is_cuda and _dtype_name(maps) == "int32"
             maps = maps.contiguous()
-            pitch, fs = int(img.stride(row_axis)), (0 if single else int(img.stride(0)))
-            mem, pi, pm = L.MEM_DEVICE, img.data_ptr(), maps.data_ptr()
         else:
-            img = np.asarray(img)
-            assert img.dtype == np.uint8
-            st = img.strides
-            if not (st[-1] == 1 and (ch == 1 or st[-2] == 3) and st[row_axis] >= cols * ch and (single or st[0] >= rows * st[row_axis])):
-                img = np.ascontiguousarray(img)  # (a padded pitch or frame stride is passed through as it is)
             maps = np.ascontiguousarray(maps, np.int32)
-            pitch, fs = int(img.strides[row_axis]), (0 if single else int(img.strides[0]))
-            mem, pi, pm = L.MEM_HOST, img.ctypes.data, maps.ctypes.data
         shape = (() if single else (F,)) + (rows_out, cols_out) + ((3,) if ch == 3 else ())
-        if dev:
-            out = torch.empty(shape, dtype=torch.uint8, device=img.device)
-            valid = torch.empty((rows_out, cols_out), dtype=torch.uint8, device=img.device) if return_valid else None
-            self._order_after_torch()
-            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        else:
-            out = np.empty(shape, np.uint8)
-            valid = np.empty((rows_out, cols_out), np.uint8) if return_valid else None
-            ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
-        L.check(self._lib.o3dr_rectify_remap(self._h, pi, fs, pitch, rows, cols, ch, F, pm, rows_out, cols_out, int(border),
-                                             int(group_frames), ptr(out), ptr(valid), mem))
+        out, valid = self._empty_like(img, (shape, np.uint8), ((rows_out, cols_out), np.uint8) if return_valid else None)
+        L.check(self._lib.o3dr_rectify_remap(self._h, pi, fs, pitch, rows, cols, ch, F, _addr(maps), rows_out, cols_out, int(border),
+                                             int(group_frames), _addr(out), _addr(valid), mem))
         return (out, valid) if return_valid else out
 
     # -- stereo disparity (the image every frame call starts from; the reference reads it from files) ----------------------
@@ -761,62 +774,28 @@ class Context:
             left, right = self.rectify(left, ml, group_frames=group_frames), self.rectify(right, mr, group_frames=group_frames)
         dev = _is_torch(left)
         assert dev == _is_torch(right) and tuple(left.shape) == tuple(right.shape)
-        nd = left.dim() if dev else np.ndim(left)
-        ch = 3 if (nd == 4 or (nd == 3 and int(left.shape[-1]) == 3)) else 1
-        single = nd == (3 if ch == 3 else 2)
-        assert nd in ((3, 4) if ch == 3 else (2, 3))
-        F = 1 if single else int(left.shape[0])
-        rows, cols = (int(left.shape[-3]), int(left.shape[-2])) if ch == 3 else (int(left.shape[-2]), int(left.shape[-1]))
-        row_axis = -3 if ch == 3 else -2
-        if dev:
-            import torch
-            assert left.is_cuda and right.is_cuda and left.dtype == right.dtype == torch.uint8
-
-            def strides_ok(t):
-                return t.stride(-1) == 1 and (ch == 1 or t.stride(-2) == 3) and t.stride(row_axis) >= cols * ch and \
-                    (single or t.stride(0) >= rows * t.stride(row_axis))
-            if not (strides_ok(left) and strides_ok(right) and left.stride() == right.stride()):
-                left, right = left.contiguous(), right.contiguous()
-            pitch, fs = int(left.stride(row_axis)), (0 if single else int(left.stride(0)))
-            mem, pl, pr = L.MEM_DEVICE, left.data_ptr(), right.data_ptr()
-        else:
-            left, right = np.asarray(left), np.asarray(right)
-            assert left.dtype == np.uint8 and right.dtype == np.uint8
-
-            def strides_ok(a):
-                st = a.strides
-                return st[-1] == 1 and (ch == 1 or st[-2] == 3) and st[row_axis] >= cols * ch and (single or st[0] >= rows * st[row_axis])
-            if not (strides_ok(left) and strides_ok(right) and left.strides == right.strides):  # (a shared padded layout passes through)
-                left, right = np.ascontiguousarray(left), np.ascontiguousarray(right)
-            pitch, fs = int(left.strides[row_axis]), (0 if single else int(left.strides[0]))
-            mem, pl, pr = L.MEM_HOST, left.ctypes.data, right.ctypes.data
+        (left, lay, pl, mem), (right, lay_r, pr, _) = (self._image_stack(x, colour=True) for x in (left, right))
+        if lay != lay_r:  # (a padded layout passes through where both share it; anything else is made contiguous)
+            (left, lay, pl, mem), (right, _, pr, _) = (self._image_stack(x, colour=True, contiguous=True) for x in (left, right))
+        assert _dtype_name(left) == _dtype_name(right) == "uint8"
+        single, F, rows, cols, ch, pitch, fs, _ = lay
         prm = L.StereoParamsStruct(int(n_disparities), int(min_disparity), int(p1), int(p2), int(n_paths), int(uniqueness),
                                    int(lr_max_diff), ch, int(group_frames))
         shape = (rows, cols) if single else (F, rows, cols)
         D = max(int(n_disparities), 1)
-        if dev:
-            def empty(shp, dt):
-                return torch.empty(shp, dtype=dt, device=left.device)
-            u8, u16 = torch.uint8, torch.int16  # (uint16 bits; viewed below)
-            self._order_after_torch()
-            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        else:
-            def empty(shp, dt):
-                return np.empty(shp, dt)
-            u8, u16 = np.uint8, np.uint16
-            ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
-        disp = None if subpixel else empty(shape, u8)
-        q4 = empty(shape, u16) if subpixel else None
-        cost = empty(shape, u16) if return_cost else None
-        vol = empty(shape + (D,), u16) if return_volume else None
-        L.check(self._lib.o3dr_stereo_disparity(self._h, pl, pr, fs, pitch, rows, cols, F, C.byref(prm), ptr(disp), ptr(q4), ptr(cost),
-                                                ptr(vol), mem))
+        # (a tensor holds uint16 bits as int16; viewed below)
+        disp, q4, cost, vol = self._empty_like(left, None if subpixel else (shape, np.uint8), (shape, np.uint16) if subpixel else None,
+                                               (shape, np.uint16) if return_cost else None,
+                                               (shape + (D,), np.uint16) if return_volume else None)
+        L.check(self._lib.o3dr_stereo_disparity(self._h, pl, pr, fs, pitch, rows, cols, F, C.byref(prm), _addr(disp), _addr(q4),
+                                                _addr(cost), _addr(vol), mem))
         if median or speckle_size:
             if subpixel:
                 q4 = self.filterDisparity(q4, median, speckle_size, 16 * int(speckle_diff), group_frames=group_frames)
             else:
                 disp = self.filterDisparity(disp, median, speckle_size, speckle_diff, group_frames=group_frames)
         if dev:  # (every value is below 2^15, so the int16 tensors hold the uint16 bits and their values)
+            import torch
             out = q4.to(torch.float64) / 16.0 if subpixel else disp
             cost = None if cost is None else cost.view(torch.uint16)
             vol = None if vol is None else vol.view(torch.uint16)
@@ -837,45 +816,15 @@ class Context:
         lowest pixel index of the pixel's component, -1 for a zero pixel; its pixel count), as they are before the removal;
         return_info: a list of DisparityFilterInfo, one per frame, follows.  group_frames: at most that many frames per
         launch group; results do not depend on it."""
-        dev = _is_torch(disp)
-        nd = disp.dim() if dev else np.ndim(disp)
-        assert nd in (2, 3)
-        single = nd == 2
-        F = 1 if single else int(disp.shape[0])
-        rows, cols = int(disp.shape[-2]), int(disp.shape[-1])
-        if dev:
-            import torch
-            assert disp.is_cuda and disp.dtype in (torch.uint8, torch.uint16, torch.int16)
-            E = disp.element_size()
-            if disp.stride(-1) != 1 or disp.stride(-2) < cols or (not single and disp.stride(0) < rows * disp.stride(-2)):
-                disp = disp.contiguous()
-            pitch, fs = int(disp.stride(-2)) * E, (0 if single else int(disp.stride(0)) * E)
-            mem, pi = L.MEM_DEVICE, disp.data_ptr()
-        else:
-            disp = np.asarray(disp)
-            assert disp.dtype in (np.uint8, np.uint16)
-            E = disp.itemsize
-            st = disp.strides
-            if st[-1] != E or st[-2] < cols * E or (not single and st[0] < rows * st[-2]):
-                disp = np.ascontiguousarray(disp)
-            pitch, fs = int(disp.strides[-2]), (0 if single else int(disp.strides[0]))
-            mem, pi = L.MEM_HOST, disp.ctypes.data
-        prm = L.DisparityFilterParamsStruct(E, int(median), int(max_speckle_size), int(max_diff), int(group_frames))
+        disp, (single, F, rows, cols, _, pitch, fs, _), pi, mem = self._image_stack(disp, colour=False)
+        assert _dtype_name(disp) in (("uint8", "uint16", "int16") if _is_torch(disp) else ("uint8", "uint16"))
+        prm = L.DisparityFilterParamsStruct(_itemsize(disp), int(median), int(max_speckle_size), int(max_diff), int(group_frames))
         shape = (rows, cols) if single else (F, rows, cols)
-        if dev:
-            out = torch.empty(shape, dtype=disp.dtype, device=disp.device)
-            labels = torch.empty(shape, dtype=torch.int32, device=disp.device) if return_labels else None
-            sizes = torch.empty(shape, dtype=torch.int32, device=disp.device) if return_sizes else None
-            self._order_after_torch()
-            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        else:
-            out = np.empty(shape, disp.dtype)
-            labels = np.empty(shape, np.int32) if return_labels else None
-            sizes = np.empty(shape, np.int32) if return_sizes else None
-            ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        out, labels, sizes = self._empty_like(disp, (shape, disp.dtype), (shape, np.int32) if return_labels else None,
+                                              (shape, np.int32) if return_sizes else None)
         info = (L.DisparityFilterInfoStruct * F)() if return_info else None
-        L.check(self._lib.o3dr_disparity_filter(self._h, pi, fs, pitch, rows, cols, F, C.byref(prm), ptr(out), ptr(labels), ptr(sizes),
-                                                C.cast(info, C.c_void_p) if return_info else None, mem))
+        L.check(self._lib.o3dr_disparity_filter(self._h, pi, fs, pitch, rows, cols, F, C.byref(prm), _addr(out), _addr(labels),
+                                                _addr(sizes), C.cast(info, C.c_void_p) if return_info else None, mem))
         if not (return_labels or return_sizes or return_info):
             return out
         infos = [DisparityFilterInfo(int(i.n_valid), int(i.n_components), int(i.n_speckles), int(i.n_removed), int(i.largest))
@@ -915,39 +864,15 @@ class Context:
             neighbors = nearbyFrames(poses, k, max_distance)
         neighbors = np.ascontiguousarray(neighbors.cpu().numpy() if _is_torch(neighbors) else neighbors, np.int32).reshape(F, -1)
         kk = int(neighbors.shape[1])
-        if dev:
-            import torch
-            assert disp.is_cuda and disp.dtype in (torch.uint8, torch.uint16, torch.int16, torch.float64)
-            E = disp.element_size()
-            if disp.stride(-1) != 1 or disp.stride(-2) < cols or disp.stride(0) < rows * disp.stride(-2):
-                disp = disp.contiguous()
-            pitch, fs = int(disp.stride(-2)) * E, int(disp.stride(0)) * E
-            mem, pi = L.MEM_DEVICE, disp.data_ptr()
-        else:
-            disp = np.asarray(disp)
-            assert disp.dtype in (np.uint8, np.uint16, np.float64)
-            E = disp.itemsize
-            st = disp.strides
-            if st[-1] != E or st[-2] < cols * E or st[0] < rows * st[-2]:
-                disp = np.ascontiguousarray(disp)
-            pitch, fs = int(disp.strides[-2]), int(disp.strides[0])
-            mem, pi = L.MEM_HOST, disp.ctypes.data
-        prm = L.MultiviewParamsStruct(E, float(tolerance), int(min_support), int(max_violations))
+        disp, (_, _, _, _, _, pitch, fs, _), pi, mem = self._image_stack(disp, colour=False)
+        assert _dtype_name(disp) in (("uint8", "uint16", "int16", "float64") if dev else ("uint8", "uint16", "float64"))
+        prm = L.MultiviewParamsStruct(_itemsize(disp), float(tolerance), int(min_support), int(max_violations))
         shape = (F, rows, cols)
-        if dev:
-            out = torch.empty(shape, dtype=disp.dtype, device=disp.device)
-            support = torch.empty(shape, dtype=torch.uint8, device=disp.device) if return_support else None
-            violations = torch.empty(shape, dtype=torch.uint8, device=disp.device) if return_violations else None
-            self._order_after_torch()
-            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        else:
-            out = np.empty(shape, disp.dtype)
-            support = np.empty(shape, np.uint8) if return_support else None
-            violations = np.empty(shape, np.uint8) if return_violations else None
-            ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        out, support, violations = self._empty_like(disp, (shape, disp.dtype), (shape, np.uint8) if return_support else None,
+                                                    (shape, np.uint8) if return_violations else None)
         info = (L.MultiviewInfoStruct * F)() if return_info else None
         L.check(self._lib.o3dr_multiview_filter(self._h, pi, fs, pitch, rows, cols, F, poses.ctypes.data, neighbors.ctypes.data, kk,
-                                                C.byref(prm), ptr(out), ptr(support), ptr(violations),
+                                                C.byref(prm), _addr(out), _addr(support), _addr(violations),
                                                 C.cast(info, C.c_void_p) if return_info else None, mem))
         if not (return_support or return_violations or return_info):
             return out
@@ -967,49 +892,17 @@ class Context:
         planeFitDisparity(disp, labels) as it is.  return_raw / return_sizes: int32 images follow (the k-means centre of
         every pixel; the pixel count of its label); return_info: a list of SegmentInfo, one per frame, follows.
         group_frames: at most that many frames per launch group; results do not depend on it."""
-        dev = _is_torch(img)
-        nd = img.dim() if dev else np.ndim(img)
-        ch = 3 if (nd == 4 or (nd == 3 and int(img.shape[-1]) == 3)) else 1
-        single = nd == (3 if ch == 3 else 2)
-        assert nd in ((3, 4) if ch == 3 else (2, 3))
-        F = 1 if single else int(img.shape[0])
-        rows, cols = (int(img.shape[-3]), int(img.shape[-2])) if ch == 3 else (int(img.shape[-2]), int(img.shape[-1]))
-        row_axis = -3 if ch == 3 else -2
-        if dev:
-            import torch
-            assert img.is_cuda and img.dtype == torch.uint8
-            if not (img.stride(-1) == 1 and (ch == 1 or img.stride(-2) == 3) and img.stride(row_axis) >= cols * ch and
-                    (single or img.stride(0) >= rows * img.stride(row_axis))):
-                img = img.contiguous()
-            pitch, fs = int(img.stride(row_axis)), (0 if single else int(img.stride(0)))
-            mem, pi = L.MEM_DEVICE, img.data_ptr()
-        else:
-            img = np.asarray(img)
-            assert img.dtype == np.uint8
-            st = img.strides
-            if not (st[-1] == 1 and (ch == 1 or st[-2] == 3) and st[row_axis] >= cols * ch and (single or st[0] >= rows * st[row_axis])):
-                img = np.ascontiguousarray(img)  # (a padded pitch or frame stride is passed through as it is)
-            pitch, fs = int(img.strides[row_axis]), (0 if single else int(img.strides[0]))
-            mem, pi = L.MEM_HOST, img.ctypes.data
+        img, (single, F, rows, cols, ch, pitch, fs, _), pi, mem = self._image_stack(img, colour=True)
+        assert _dtype_name(img) == "uint8"
         prm = L.SegmentParamsStruct(ch, int(step), int(compactness), int(iterations), -1 if min_size is None else int(min_size),
                                     int(group_frames))
         shape = (rows, cols) if single else (F, rows, cols)
-        if dev:
-            def empty():
-                return torch.empty(shape, dtype=torch.int32, device=img.device)
-            self._order_after_torch()
-            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        else:
-            def empty():
-                return np.empty(shape, np.int32)
-            ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
-        labels = empty()
-        raw = empty() if return_raw else None
-        sizes = empty() if return_sizes else None
+        labels, raw, sizes = self._empty_like(img, (shape, np.int32), (shape, np.int32) if return_raw else None,
+                                              (shape, np.int32) if return_sizes else None)
         info = (L.SegmentInfoStruct * F)() if return_info else None
-        L.check(self._lib.o3dr_segment_image(self._h, pi, fs, pitch, rows, cols, F, C.byref(prm), ptr(labels), ptr(raw), ptr(sizes),
+        L.check(self._lib.o3dr_segment_image(self._h, pi, fs, pitch, rows, cols, F, C.byref(prm), _addr(labels), _addr(raw), _addr(sizes),
                                              C.cast(info, C.c_void_p) if return_info else None, mem))
-        if not dev:
+        if not _is_torch(img):
             labels = labels.view(np.uint32)  # (never negative)
         if not (return_raw or return_sizes or return_info):
             return labels

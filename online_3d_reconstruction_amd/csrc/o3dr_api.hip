@@ -21,6 +21,7 @@
 
 #include "../../include/o3dr_testing.h"
 #include "o3dr_device.h"
+#include "o3dr_image_stack.h"
 #include "o3dr_profile.h"
 
 using namespace o3dr;
@@ -134,23 +135,20 @@ struct o3dr_ctx {
     // arrays (indices of this and the previous pass, d2, the moment partials and their folded record).  nn_t also holds the
     // staged cloud of MLS, plane segmentation and meshing, nn_cells the grid boxes of MLS.
     DevBuf nn_q, nn_t, nn_cells, nn_src;
-    // Scratch of the operators after that (MLS, plane, mesh, match, keypoints, rigid fit), shared: nothing in it outlives a
-    // call, and within one call every block is laid out by one carve().  OP_IN: staged host inputs (descriptor pool; src /
-    // tgt / mask).  OP_WORK: the arrays sized from the arguments (plane: points in tile order + run heads; mesh: run heads +
-    // vertex tables; match: pair table + chunk partials; rigid: segment table + sums).  OP_LATE: the arrays sized from a
-    // count read back mid-call (plane: tile tables).  OP_OUT: the staged outputs of a host call.  OP_FLAGS: 256 bytes of
-    // flags / ranges / counters (MlsFlags, PlaneFlags, MeshFlags).
+    // Scratch of the operators after that (MLS, plane, mesh, match, keypoints, rigid fit, the image-stack operators), shared:
+    // nothing in it outlives a call, and within one call every block is laid out by one carve().  OP_IN: staged host inputs
+    // (descriptor pool; src / tgt / mask; image stacks).  OP_WORK: the arrays sized from the arguments (plane: points in tile
+    // order + run heads; mesh: run heads + vertex tables; match: pair table + chunk partials; rigid: segment table + sums;
+    // ORB, stereo, the disparity and multi-view filters, segmentation: a group of frames' arrays and the per-frame counters;
+    // rectification: the staged host map).  OP_LATE: the arrays sized from a count read back mid-call (plane: tile tables).
+    // OP_OUT: the staged outputs of a host call.  OP_FLAGS: 256 bytes of flags / ranges / counters (MlsFlags, PlaneFlags,
+    // MeshFlags).
     enum { OP_IN, OP_WORK, OP_LATE, OP_OUT, OP_FLAGS, OP_BUFS };
     DevBuf op[OP_BUFS];
-    DevBuf orb_work, orb_pat;  // o3dr_orb_detect: its own scratch block (one carve per call) and the steered table
+    DevBuf orb_pat;  // o3dr_orb_detect: the steered table
     bool orb_pat_valid = false;
     std::vector<int8_t> orb_pat_h;  // (outlives the asynchronous upload)
     int64_t test_orb_scratch = 0;   // o3dr_test_orb_scratch_limit: stands in for kOrbScratchBytes when positive
-    DevBuf stereo_work;        // o3dr_stereo_disparity: its own scratch block (one carve per call)
-    DevBuf dfilter_work;       // o3dr_disparity_filter: its own scratch block (one carve per call)
-    DevBuf multiview_work;     // o3dr_multiview_filter: neighbour lists, matrices and counts (one carve per call)
-    DevBuf rect_work;          // o3dr_rectify_remap: the staged host map (one carve per call)
-    DevBuf segment_work;       // o3dr_segment_image: its own scratch block (one carve per call)
     DevBuf pl_hyp;             // o3dr_segment_plane: hypotheses + scores (plane_hyp_layout), kept for the test hook
     uint64_t pl_last_hyp = 0;  // hypotheses of the last call in pl_hyp (o3dr_test_plane_hypotheses)
     std::vector<MatchPair> mt_tab_h;  // host copies of the match pair table, the rigid fit's segment table and transforms
@@ -478,7 +476,7 @@ extern "C" int o3dr_ctx_destroy(o3dr_ctx* c)
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     for (DevBuf* b : {&c->inc.box, &c->inc.scratch, &c->inc.tg, &c->inc.tmatch, &c->inc.flag, &c->inc.src, &c->inc.keep,
-                      &c->inc.partial, &c->inc.words, &c->inc.fb, &c->nn_q, &c->nn_t, &c->nn_cells, &c->nn_src, &c->pl_hyp, &c->orb_work, &c->orb_pat, &c->stereo_work, &c->dfilter_work, &c->multiview_work, &c->rect_work, &c->segment_work})
+                      &c->inc.partial, &c->inc.words, &c->inc.fb, &c->nn_q, &c->nn_t, &c->nn_cells, &c->nn_src, &c->pl_hyp, &c->orb_pat})
         dev_release(*b);
     for (DevBuf& b : c->op) dev_release(b);
     delete c;
@@ -734,6 +732,62 @@ struct Outputs {
     {
         for (const Item* it = item; mem == O3DR_MEM_HOST && it < item + n; ++it)
             if (it->cap && it->user != keep) memset(it->user, 0, it->cap * it->elem);
+    }
+};
+
+// What the front ends of the image-stack operators share (o3dr_image_stack.h holds the layout contract itself).
+// a check of that header: its text, if any, is the call's error
+#define STACKCHK(expr)                                                 \
+    do {                                                               \
+        if (const char* m_ = (expr)) return fail(O3DR_ERR_INVALID_ARG, m_); \
+    } while (0)
+// the two checks every one of them opens with
+static const char* stack_call_error(int32_t mem, int32_t n_frames)
+{
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return "bad mem kind";
+    return n_frames < 0 ? "bad frame count" : nullptr;
+}
+// stages one stack, or two of one layout, of `bytes` each into op[OP_IN] (device pointers pass through): the first at
+// offset 0, the second at align256(bytes)
+static int stage_stacks(o3dr_ctx* c, size_t bytes, int mem, const void* a, const void** a_d, const void* b = nullptr,
+                        const void** b_d = nullptr)
+{
+    DevBuf& in = c->op[o3dr_ctx::OP_IN];
+    if (!b) return stage_in(c, in, a, bytes, mem, a_d);
+    if (mem == O3DR_MEM_DEVICE) {
+        *a_d = a, *b_d = b;
+        return O3DR_OK;
+    }
+    CHK(dev_ensure(c, in, 2 * align256(bytes)));
+    char* base = (char*)in.p;
+    HIPCHK(hipMemcpyAsync(base, a, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(base + align256(bytes), b, bytes, hipMemcpyHostToDevice, c->stream));
+    *a_d = base, *b_d = base + align256(bytes);
+    return O3DR_OK;
+}
+// The per-frame counters behind an operator's *_info: `words` per frame (none where the caller asks for no info), carved
+// with the call's other arrays, zeroed on the stream, copied back behind the launches and valid after the call's one
+// synchronise.
+struct FrameCounters {
+    size_t frames, words;  // frames = 0: not asked for
+    unsigned long long* dev = nullptr;
+    std::vector<unsigned long long> host;
+    FrameCounters(const void* info, int32_t n_frames, size_t words_) : frames(info ? (size_t)n_frames : 0), words(words_) {}
+    void take(Carve& w)
+    {
+        if (frames) w.take(dev, frames * words);
+    }
+    int zero(o3dr_ctx* c)
+    {
+        if (frames) HIPCHK(hipMemsetAsync(dev, 0, frames * words * sizeof(unsigned long long), c->stream));
+        return O3DR_OK;
+    }
+    unsigned long long* of_frame(size_t f) const { return dev ? dev + f * words : nullptr; }
+    int copy_back(o3dr_ctx* c)
+    {
+        host.resize(frames * words);
+        if (frames) HIPCHK(hipMemcpyAsync(host.data(), dev, host.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        return O3DR_OK;
     }
 };
 
@@ -4645,8 +4699,7 @@ extern "C" int o3dr_orb_pattern(int8_t* out)
 
 static int orb_check_params(const o3dr_orb_params& p, int32_t rows, int32_t cols)
 {
-    if (rows < 1 || rows > O3DR_ORB_MAX_SIDE || cols < 1 || cols > O3DR_ORB_MAX_SIDE)
-        return fail(O3DR_ERR_INVALID_ARG, "rows and cols must be in 1..8192");
+    STACKCHK(stack_sides_error(rows, cols, O3DR_ORB_MAX_SIDE));
     if (p.n_features < 1 || p.n_features > 65535) return fail(O3DR_ERR_INVALID_ARG, "n_features must be in 1..65535");
     if (!(p.scale_factor > 1.f && p.scale_factor <= 2.f)) return fail(O3DR_ERR_INVALID_ARG, "scale_factor must be in (1, 2]");
     if (p.n_levels < 1 || p.n_levels > O3DR_ORB_MAX_LEVELS) return fail(O3DR_ERR_INVALID_ARG, "n_levels must be in 1..8");
@@ -4698,18 +4751,19 @@ static int orb_detect(o3dr_ctx* c, const uint8_t* img, int64_t fs, int64_t pitch
                       uint8_t* levels_out, int64_t out_capacity, int64_t* n_out, int32_t mem)
 {
     if (!n_out || !offsets) return fail(O3DR_ERR_INVALID_ARG, "n_out / offsets is NULL");
-    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
-    if (n_frames < 0) return fail(O3DR_ERR_INVALID_ARG, "bad frame count");
+    STACKCHK(stack_call_error(mem, n_frames));
     o3dr_orb_params prm;
     o3dr_orb_default_params(&prm);
     if (p) prm = *p;
     CHK(orb_check_params(prm, rows, cols));
     if (n_frames == 0) return O3DR_OK;
     if (!img) return fail(O3DR_ERR_INVALID_ARG, "img is NULL");
-    if (pitch < (int64_t)cols * prm.channels) return fail(O3DR_ERR_INVALID_ARG, "pitch smaller than a row");
-    if (n_frames > 1 && fs < (int64_t)rows * pitch) return fail(O3DR_ERR_INVALID_ARG, "frame stride smaller than a frame");
+    const ImageStack in{img, fs, pitch, rows, cols, n_frames, prm.channels};
+    STACKCHK(stack_layout_error(in));
     if ((uintptr_t)kp % 16 || (uintptr_t)desc % 16 || (uintptr_t)kp_xy % 8)
         return fail(O3DR_ERR_INVALID_ARG, "kp / desc must be 16-byte aligned, kp_xy 8-byte");
+    int64_t in_bytes;
+    STACKCHK(stack_extent(in, &in_bytes));
     const int64_t bound = (int64_t)n_frames * prm.n_features;
     if (out_capacity < bound) return fail(O3DR_ERR_CAPACITY, "out_capacity is below n_frames * n_features");
 
@@ -4741,7 +4795,7 @@ static int orb_detect(o3dr_ctx* c, const uint8_t* img, int64_t fs, int64_t pitch
     a.fstride = fs, a.pitch = pitch;
 
     const void* img_d;
-    CHK(stage_in(c, c->op[o3dr_ctx::OP_IN], img, (size_t)fs * (size_t)(n_frames - 1) + (size_t)pitch * (size_t)(rows - 1) + (size_t)cols * prm.channels, mem, &img_d));
+    CHK(stage_stacks(c, (size_t)in_bytes, mem, img, &img_d));
     if (!c->orb_pat_valid) {
         std::vector<int8_t>& pat = c->orb_pat_h;
         pat.resize(64 * 256 * 4);
@@ -4754,9 +4808,8 @@ static int orb_detect(o3dr_ctx* c, const uint8_t* img, int64_t fs, int64_t pitch
 
     const size_t per_frame = (size_t)a.P * 4 + (size_t)a.cands_per_frame * 12 + (size_t)a.chunks_per_frame * 4 + (size_t)prm.n_levels * 16;
     const size_t limit = c->test_orb_scratch > 0 ? (size_t)c->test_orb_scratch : kOrbScratchBytes;
-    size_t group = std::max<size_t>(1, limit / per_frame);
-    group = std::min<size_t>(std::min<size_t>(group, (size_t)n_frames), 32768);
-    CHK(carve(c, c->orb_work, [&](Carve& w) {
+    const size_t group = frames_per_group(limit, per_frame, n_frames, 0);
+    CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
         w.take(a.pyr, group * (size_t)a.P);
         w.take(a.score, group * (size_t)a.P);
         w.take(a.box, group * (size_t)a.P);
@@ -4856,15 +4909,11 @@ extern "C" void o3dr_stereo_default_params(o3dr_stereo_params* p)
     p->group_frames = 0;
 }
 
-static bool stereo_shape_ok(int32_t rows, int32_t cols, int32_t n_frames)
-{
-    return rows >= 1 && rows <= O3DR_STEREO_MAX_SIDE && cols >= 1 && cols <= O3DR_STEREO_MAX_SIDE && n_frames >= 0;
-}
 static bool stereo_disparities_ok(int32_t D) { return D >= 32 && D <= 256 && D % 32 == 0; }
 
 static int stereo_check_params(const o3dr_stereo_params& p, int32_t rows, int32_t cols)
 {
-    if (!stereo_shape_ok(rows, cols, 0)) return fail(O3DR_ERR_INVALID_ARG, "rows and cols must be in 1..8192");
+    STACKCHK(stack_sides_error(rows, cols, O3DR_STEREO_MAX_SIDE));
     if (!stereo_disparities_ok(p.n_disparities)) return fail(O3DR_ERR_INVALID_ARG, "n_disparities must be a multiple of 32 in 32..256");
     if (p.min_disparity < 0 || p.min_disparity + p.n_disparities > 256)
         return fail(O3DR_ERR_INVALID_ARG, "min_disparity must be >= 0 with min_disparity + n_disparities <= 256");
@@ -4884,18 +4933,19 @@ static int stereo_disparity(o3dr_ctx* c, const uint8_t* left, const uint8_t* rig
                             int32_t cols, int32_t n_frames, const o3dr_stereo_params* p, uint8_t* disp, uint16_t* disp_q4,
                             uint16_t* cost, Outputs& outs, uint16_t* volume_out, int32_t mem)
 {
-    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
-    if (n_frames < 0) return fail(O3DR_ERR_INVALID_ARG, "bad frame count");
+    STACKCHK(stack_call_error(mem, n_frames));
     o3dr_stereo_params prm;
     o3dr_stereo_default_params(&prm);
     if (p) prm = *p;
     CHK(stereo_check_params(prm, rows, cols));
     if (n_frames == 0) return O3DR_OK;
     if (!left || !right) return fail(O3DR_ERR_INVALID_ARG, "left / right is NULL");
-    if (pitch < (int64_t)cols * prm.channels) return fail(O3DR_ERR_INVALID_ARG, "pitch smaller than a row");
-    if (n_frames > 1 && fs < (int64_t)rows * pitch) return fail(O3DR_ERR_INVALID_ARG, "frame stride smaller than a frame");
+    const ImageStack in{left, fs, pitch, rows, cols, n_frames, prm.channels};  // (the right images have the left ones' layout)
+    STACKCHK(stack_layout_error(in));
     if ((uintptr_t)disp_q4 % 2 || (uintptr_t)cost % 2 || (uintptr_t)volume_out % 2)
         return fail(O3DR_ERR_INVALID_ARG, "disp_q4 / cost / volume_out must be 2-byte aligned");
+    int64_t in_bytes;
+    STACKCHK(stack_extent(in, &in_bytes));
 
     StereoArgs a;
     memset(&a, 0, sizeof a);
@@ -4904,23 +4954,11 @@ static int stereo_disparity(o3dr_ctx* c, const uint8_t* left, const uint8_t* rig
     a.uniq = prm.uniqueness, a.lr = prm.lr_max_diff;
     a.fstride = fs, a.pitch = pitch;
     const size_t n = (size_t)rows * (size_t)cols, D = (size_t)prm.n_disparities;
-    const size_t in_bytes = (size_t)fs * (size_t)(n_frames - 1) + (size_t)pitch * (size_t)(rows - 1) + (size_t)cols * prm.channels;
     const void *left_d, *right_d;
-    if (mem == O3DR_MEM_HOST) {  // both images in one staging block, the right one behind the left
-        CHK(dev_ensure(c, c->op[o3dr_ctx::OP_IN], 2 * align256(in_bytes)));
-        char* base = (char*)c->op[o3dr_ctx::OP_IN].p;
-        HIPCHK(hipMemcpyAsync(base, left, in_bytes, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(base + align256(in_bytes), right, in_bytes, hipMemcpyHostToDevice, c->stream));
-        left_d = base, right_d = base + align256(in_bytes);
-    } else {
-        left_d = left, right_d = right;
-    }
+    CHK(stage_stacks(c, (size_t)in_bytes, mem, left, &left_d, right, &right_d));
 
-    const size_t per_frame = n * (2 * D + 21);
-    size_t group = std::max<size_t>(1, kStereoScratchBytes / per_frame);
-    group = std::min<size_t>(std::min<size_t>(group, (size_t)n_frames), 32768);
-    if (prm.group_frames > 0) group = std::min<size_t>(group, (size_t)prm.group_frames);
-    CHK(carve(c, c->stereo_work, [&](Carve& w) {
+    const size_t group = frames_per_group(kStereoScratchBytes, n * (2 * D + 21), n_frames, prm.group_frames);
+    CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
         w.take(a.cenL, group * n);
         w.take(a.cenR, group * n);
         w.take(a.S, group * n * D);
@@ -4953,7 +4991,7 @@ extern "C" int o3dr_stereo_disparity(o3dr_ctx* c, const uint8_t* left, const uin
                                      uint16_t* disp_q4, uint16_t* cost, uint16_t* volume_out, int32_t mem)
 {
     // the outputs' sizes are known only where the shape itself is within its limits
-    const int64_t px = stereo_shape_ok(rows, cols, n_frames) ? (int64_t)n_frames * rows * cols : 0;
+    const int64_t px = stack_pixels(rows, cols, n_frames, O3DR_STEREO_MAX_SIDE);
     Outputs outs{mem};
     outs.add(disp, px);
     outs.add(disp_q4, px);
@@ -4985,10 +5023,6 @@ extern "C" void o3dr_disparity_filter_default_params(o3dr_disparity_filter_param
     p->group_frames = 0;
 }
 
-static bool dfilter_shape_ok(int32_t rows, int32_t cols, int32_t n_frames)
-{
-    return rows >= 1 && rows <= O3DR_DISPARITY_FILTER_MAX_SIDE && cols >= 1 && cols <= O3DR_DISPARITY_FILTER_MAX_SIDE && n_frames >= 0;
-}
 static bool dfilter_elem_ok(int32_t e) { return e == 1 || e == 2; }
 
 constexpr size_t kDfilterScratchBytes = (size_t)1 << 30;  // a group of frames keeps its scratch within this (one frame always forms a group)
@@ -4997,12 +5031,11 @@ static int disparity_filter(o3dr_ctx* c, const void* disp, int64_t fs, int64_t p
                             const o3dr_disparity_filter_params* p, uint8_t* out, int32_t* labels_out, int32_t* sizes_out,
                             o3dr_disparity_filter_info* info, Outputs& outs, int32_t mem)
 {
-    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
-    if (n_frames < 0) return fail(O3DR_ERR_INVALID_ARG, "bad frame count");
+    STACKCHK(stack_call_error(mem, n_frames));
     o3dr_disparity_filter_params prm;
     o3dr_disparity_filter_default_params(&prm);
     if (p) prm = *p;
-    if (!dfilter_shape_ok(rows, cols, 0)) return fail(O3DR_ERR_INVALID_ARG, "rows and cols must be in 1..8192");
+    STACKCHK(stack_sides_error(rows, cols, O3DR_DISPARITY_FILTER_MAX_SIDE));
     if (!dfilter_elem_ok(prm.elem_bytes)) return fail(O3DR_ERR_INVALID_ARG, "elem_bytes must be 1 or 2");
     if (prm.median_size != 0 && prm.median_size != 3 && prm.median_size != 5) return fail(O3DR_ERR_INVALID_ARG, "median_size must be 0, 3 or 5");
     if (prm.max_speckle_size < 0) return fail(O3DR_ERR_INVALID_ARG, "max_speckle_size is negative");
@@ -5011,37 +5044,32 @@ static int disparity_filter(o3dr_ctx* c, const void* disp, int64_t fs, int64_t p
     if (n_frames == 0) return O3DR_OK;
     if (!disp || !out) return fail(O3DR_ERR_INVALID_ARG, "disp / out is NULL");
     const int64_t E = prm.elem_bytes;
-    if (pitch < (int64_t)cols * E) return fail(O3DR_ERR_INVALID_ARG, "pitch smaller than a row");
-    if (n_frames > 1 && fs < (int64_t)rows * pitch) return fail(O3DR_ERR_INVALID_ARG, "frame stride smaller than a frame");
-    if (E == 2 && ((uintptr_t)disp % 2 || (uintptr_t)out % 2 || pitch % 2 || (n_frames > 1 && fs % 2)))
-        return fail(O3DR_ERR_INVALID_ARG, "uint16 images must be 2-byte aligned");
+    const ImageStack in{disp, fs, pitch, rows, cols, n_frames, prm.elem_bytes};
+    STACKCHK(stack_layout_error(in));
+    if (!stack_aligned(in, E) || (uintptr_t)out % (uintptr_t)E) return fail(O3DR_ERR_INVALID_ARG, "uint16 images must be 2-byte aligned");
     if ((uintptr_t)labels_out % 4 || (uintptr_t)sizes_out % 4) return fail(O3DR_ERR_INVALID_ARG, "labels_out / sizes_out must be 4-byte aligned");
+    int64_t in_bytes;
+    STACKCHK(stack_extent(in, &in_bytes));
 
     DfArgs a;
     memset(&a, 0, sizeof a);
     a.rows = rows, a.cols = cols, a.elem = prm.elem_bytes, a.median = prm.median_size;
     a.max_diff = prm.max_diff, a.max_size = prm.max_speckle_size;
     const size_t n = (size_t)rows * (size_t)cols;
-    const size_t in_bytes = (size_t)fs * (size_t)(n_frames - 1) + (size_t)pitch * (size_t)(rows - 1) + (size_t)cols * (size_t)E;
-    {  // the byte ranges [disp, disp + in_bytes) and [out, out + n_frames * rows * cols * E), in either memory kind
-        const uintptr_t i0 = (uintptr_t)disp, o0 = (uintptr_t)out;
-        if (i0 < o0 + (uintptr_t)n_frames * n * (uintptr_t)E && o0 < i0 + in_bytes) return fail(O3DR_ERR_INVALID_ARG, "out must not overlap disp");
-    }
+    if (ranges_overlap(disp, (size_t)in_bytes, out, (size_t)n_frames * n * (size_t)E)) return fail(O3DR_ERR_INVALID_ARG, "out must not overlap disp");
     const void* disp_d;
-    CHK(stage_in(c, c->op[o3dr_ctx::OP_IN], disp, in_bytes, mem, &disp_d));
+    CHK(stage_stacks(c, (size_t)in_bytes, mem, disp, &disp_d));
 
+    // (without labelling a frame needs no scratch: the budget does not bound the group)
     const bool labelling = prm.max_speckle_size > 0 || labels_out || sizes_out || info;
-    const size_t per_frame = n * 2 * sizeof(int32_t);
-    size_t group = labelling ? std::max<size_t>(1, kDfilterScratchBytes / per_frame) : (size_t)n_frames;
-    group = std::min<size_t>(std::min<size_t>(group, (size_t)n_frames), 32768);
-    if (prm.group_frames > 0) group = std::min<size_t>(group, (size_t)prm.group_frames);
-    unsigned long long* info_d = nullptr;
-    CHK(carve(c, c->dfilter_work, [&](Carve& w) {
+    const size_t group = frames_per_group(labelling ? kDfilterScratchBytes : SIZE_MAX, n * 2 * sizeof(int32_t), n_frames, prm.group_frames);
+    FrameCounters counts(info, n_frames, 5);
+    CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
         if (labelling) w.take(a.parent, group * n);
         if (labelling) w.take(a.cnt, group * n);
-        if (info) w.take(info_d, (size_t)n_frames * 5);
+        counts.take(w);
     }));
-    if (info) HIPCHK(hipMemsetAsync(info_d, 0, (size_t)n_frames * 5 * sizeof(unsigned long long), c->stream));
+    CHK(counts.zero(c));
     CHK(outs.stage(c));
     uint8_t* out_d = outs.dev(out);
     int32_t *labels_d = outs.dev(labels_out), *sizes_d = outs.dev(sizes_out);
@@ -5051,16 +5079,15 @@ static int disparity_filter(o3dr_ctx* c, const void* disp, int64_t fs, int64_t p
         a.out = out_d + f0 * n * (size_t)E;
         a.labels_out = labels_d ? labels_d + f0 * n : nullptr;
         a.sizes_out = sizes_d ? sizes_d + f0 * n : nullptr;
-        a.info = info_d ? info_d + f0 * 5 : nullptr;
+        a.info = counts.of_frame(f0);
         launch_disparity_filter(&c->prof, c->stream, a);
     }
     HIPCHK(hipGetLastError());
     CHK(outs.copy_back(c));
-    std::vector<unsigned long long> counts(info ? (size_t)n_frames * 5 : 0);
-    if (info) HIPCHK(hipMemcpyAsync(counts.data(), info_d, counts.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    CHK(counts.copy_back(c));
     HIPCHK(hipStreamSynchronize(c->stream));
-    for (size_t f = 0; info && f < (size_t)n_frames; ++f) {
-        const unsigned long long* k = &counts[f * 5];
+    for (size_t f = 0; f < counts.frames; ++f) {
+        const unsigned long long* k = &counts.host[f * 5];
         info[f] = o3dr_disparity_filter_info{(int64_t)k[0], (int64_t)k[1], (int64_t)k[2], (int64_t)k[3], (int64_t)k[4]};
     }
     return O3DR_OK;
@@ -5071,7 +5098,7 @@ extern "C" int o3dr_disparity_filter(o3dr_ctx* c, const void* disp, int64_t fram
                                      int32_t* sizes_out, o3dr_disparity_filter_info* info, int32_t mem)
 {
     // the outputs' sizes are known only where the shape itself (and for `out` the element size) is within its limits
-    const int64_t px = dfilter_shape_ok(rows, cols, n_frames) ? (int64_t)n_frames * rows * cols : 0;
+    const int64_t px = stack_pixels(rows, cols, n_frames, O3DR_DISPARITY_FILTER_MAX_SIDE);
     const int32_t elem = p ? p->elem_bytes : 1;
     Outputs outs{mem};
     outs.add((uint8_t*)out, dfilter_elem_ok(elem) ? px * elem : 0);
@@ -5211,22 +5238,17 @@ extern "C" int o3dr_multiview_homographies(o3dr_ctx* c, const float* poses, int3
     return rc;
 }
 
-static bool multiview_shape_ok(int32_t rows, int32_t cols, int32_t n_frames)
-{
-    return rows >= 1 && rows <= O3DR_MULTIVIEW_MAX_SIDE && cols >= 1 && cols <= O3DR_MULTIVIEW_MAX_SIDE && n_frames >= 0;
-}
 static bool multiview_elem_ok(int32_t e) { return e == 1 || e == 2 || e == 8; }
 
 static int multiview_filter(o3dr_ctx* c, const void* disp, int64_t fs, int64_t pitch, int32_t rows, int32_t cols, int32_t n_frames,
                             const float* poses, const int32_t* neighbors, int32_t k, const o3dr_multiview_params* p, uint8_t* out,
                             uint8_t* support_out, uint8_t* violations_out, o3dr_multiview_info* info, Outputs& outs, int32_t mem)
 {
-    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
-    if (n_frames < 0) return fail(O3DR_ERR_INVALID_ARG, "bad frame count");
+    STACKCHK(stack_call_error(mem, n_frames));
     o3dr_multiview_params prm;
     o3dr_multiview_default_params(&prm);
     if (p) prm = *p;
-    if (!multiview_shape_ok(rows, cols, 0)) return fail(O3DR_ERR_INVALID_ARG, "rows and cols must be in 1..8192");
+    STACKCHK(stack_sides_error(rows, cols, O3DR_MULTIVIEW_MAX_SIDE));
     if (!multiview_elem_ok(prm.elem_bytes)) return fail(O3DR_ERR_INVALID_ARG, "elem_bytes must be 1, 2 or 8");
     if (!(prm.tolerance >= 0.0) || !std::isfinite(prm.tolerance)) return fail(O3DR_ERR_INVALID_ARG, "tolerance must be finite and >= 0");
     if (prm.min_support < 0 || prm.min_support > O3DR_MULTIVIEW_MAX_NEIGHBORS) return fail(O3DR_ERR_INVALID_ARG, "min_support must be in 0..16");
@@ -5236,22 +5258,19 @@ static int multiview_filter(o3dr_ctx* c, const void* disp, int64_t fs, int64_t p
     if (n_frames == 0) return O3DR_OK;
     if (!disp || !out) return fail(O3DR_ERR_INVALID_ARG, "disp / out is NULL");
     const int64_t E = prm.elem_bytes;
-    if (pitch < (int64_t)cols * E) return fail(O3DR_ERR_INVALID_ARG, "pitch smaller than a row");
-    if (n_frames > 1 && fs < (int64_t)rows * pitch) return fail(O3DR_ERR_INVALID_ARG, "frame stride smaller than a frame");
-    if ((uintptr_t)disp % (uintptr_t)E || (uintptr_t)out % (uintptr_t)E || pitch % E || (n_frames > 1 && fs % E))
-        return fail(O3DR_ERR_INVALID_ARG, "images must be aligned to their element size");
+    const ImageStack in{disp, fs, pitch, rows, cols, n_frames, prm.elem_bytes};
+    STACKCHK(stack_layout_error(in));
+    if (!stack_aligned(in, E) || (uintptr_t)out % (uintptr_t)E) return fail(O3DR_ERR_INVALID_ARG, "images must be aligned to their element size");
     const size_t n = (size_t)rows * (size_t)cols;
-    const size_t in_bytes = (size_t)fs * (size_t)(n_frames - 1) + (size_t)pitch * (size_t)(rows - 1) + (size_t)cols * (size_t)E;
-    {  // the byte ranges [disp, disp + in_bytes) and [out, out + n_frames * rows * cols * E), in either memory kind
-        const uintptr_t i0 = (uintptr_t)disp, o0 = (uintptr_t)out;
-        if (i0 < o0 + (uintptr_t)n_frames * n * (uintptr_t)E && o0 < i0 + in_bytes) return fail(O3DR_ERR_INVALID_ARG, "out must not overlap disp");
-    }
+    int64_t in_bytes;
+    STACKCHK(stack_extent(in, &in_bytes));
+    if (ranges_overlap(disp, (size_t)in_bytes, out, (size_t)n_frames * n * (size_t)E)) return fail(O3DR_ERR_INVALID_ARG, "out must not overlap disp");
     const size_t n_pairs = (size_t)n_frames * (size_t)k;
     std::vector<double> H(n_pairs * 16);  // (outlives the upload: the call synchronises at its end)
     CHK(multiview_matrices(c, poses, n_frames, neighbors, k, H.data()));
 
     const void* disp_d;
-    CHK(stage_in(c, c->op[o3dr_ctx::OP_IN], disp, in_bytes, mem, &disp_d));
+    CHK(stage_stacks(c, (size_t)in_bytes, mem, disp, &disp_d));
     MvArgs a;
     memset(&a, 0, sizeof a);
     a.in = disp_d, a.fstride = fs, a.pitch = pitch;
@@ -5259,27 +5278,27 @@ static int multiview_filter(o3dr_ctx* c, const void* disp, int64_t fs, int64_t p
     a.min_support = prm.min_support, a.max_violations = prm.max_violations, a.tolerance = prm.tolerance;
     double* H_d = nullptr;
     int32_t* nb_d = nullptr;
-    CHK(carve(c, c->multiview_work, [&](Carve& w) {
+    FrameCounters counts(info, n_frames, 9);
+    CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
         w.take(H_d, n_pairs * 16);
         w.take(nb_d, n_pairs);
-        if (info) w.take(a.info, (size_t)n_frames * 9);
+        counts.take(w);
     }));
     if (n_pairs) {
         HIPCHK(hipMemcpyAsync(H_d, H.data(), n_pairs * 16 * sizeof(double), hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(nb_d, neighbors, n_pairs * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     }
-    if (info) HIPCHK(hipMemsetAsync(a.info, 0, (size_t)n_frames * 9 * sizeof(unsigned long long), c->stream));
+    CHK(counts.zero(c));
     CHK(outs.stage(c));
-    a.H = H_d, a.neighbors = nb_d;
+    a.H = H_d, a.neighbors = nb_d, a.info = counts.dev;
     a.out = outs.dev(out), a.support_out = outs.dev(support_out), a.violations_out = outs.dev(violations_out);
     launch_multiview_filter(&c->prof, c->stream, a);
     HIPCHK(hipGetLastError());
     CHK(outs.copy_back(c));
-    std::vector<unsigned long long> counts(info ? (size_t)n_frames * 9 : 0);
-    if (info) HIPCHK(hipMemcpyAsync(counts.data(), a.info, counts.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    CHK(counts.copy_back(c));
     HIPCHK(hipStreamSynchronize(c->stream));
-    for (size_t f = 0; info && f < (size_t)n_frames; ++f) {
-        const unsigned long long* q = &counts[f * 9];
+    for (size_t f = 0; f < counts.frames; ++f) {
+        const unsigned long long* q = &counts.host[f * 9];
         info[f] = o3dr_multiview_info{(int64_t)q[0], (int64_t)q[1], (int64_t)q[2], (int64_t)q[3], (int64_t)q[4],
                                       (int64_t)q[5], (int64_t)q[6], (int64_t)q[7], (int64_t)q[8]};
     }
@@ -5292,7 +5311,7 @@ extern "C" int o3dr_multiview_filter(o3dr_ctx* c, const void* disp, int64_t fram
                                      o3dr_multiview_info* info, int32_t mem)
 {
     // the outputs' sizes are known only where the shape itself (and for `out` the element size) is within its limits
-    const int64_t px = multiview_shape_ok(rows, cols, n_frames) ? (int64_t)n_frames * rows * cols : 0;
+    const int64_t px = stack_pixels(rows, cols, n_frames, O3DR_MULTIVIEW_MAX_SIDE);
     const int32_t elem = p ? p->elem_bytes : 1;
     Outputs outs{mem};
     outs.add((uint8_t*)out, multiview_elem_ok(elem) ? px * elem : 0);
@@ -5323,23 +5342,17 @@ extern "C" void o3dr_segment_default_params(o3dr_segment_params* p)
     p->group_frames = 0;
 }
 
-static bool segment_shape_ok(int32_t rows, int32_t cols, int32_t n_frames)
-{
-    return rows >= 1 && rows <= O3DR_SEGMENT_MAX_SIDE && cols >= 1 && cols <= O3DR_SEGMENT_MAX_SIDE && n_frames >= 0;
-}
-
 constexpr size_t kSegmentScratchBytes = (size_t)1 << 30;  // a group of frames keeps its scratch within this (one frame always forms a group)
 
 static int segment_image(o3dr_ctx* c, const uint8_t* img, int64_t fs, int64_t pitch, int32_t rows, int32_t cols, int32_t n_frames,
                          const o3dr_segment_params* p, int32_t* labels, int32_t* raw_out, int32_t* sizes_out, o3dr_segment_info* info,
                          Outputs& outs, int32_t mem)
 {
-    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
-    if (n_frames < 0) return fail(O3DR_ERR_INVALID_ARG, "bad frame count");
+    STACKCHK(stack_call_error(mem, n_frames));
     o3dr_segment_params prm;
     o3dr_segment_default_params(&prm);
     if (p) prm = *p;
-    if (!segment_shape_ok(rows, cols, 0)) return fail(O3DR_ERR_INVALID_ARG, "rows and cols must be in 1..8192");
+    STACKCHK(stack_sides_error(rows, cols, O3DR_SEGMENT_MAX_SIDE));
     if (prm.channels != 1 && prm.channels != 3) return fail(O3DR_ERR_INVALID_ARG, "channels must be 1 or 3");
     if (prm.step < 4 || prm.step > 256) return fail(O3DR_ERR_INVALID_ARG, "step must be in 4..256");
     if (prm.compactness < 0 || prm.compactness > 255) return fail(O3DR_ERR_INVALID_ARG, "compactness must be in 0..255");
@@ -5347,11 +5360,12 @@ static int segment_image(o3dr_ctx* c, const uint8_t* img, int64_t fs, int64_t pi
     if (prm.group_frames < 0) return fail(O3DR_ERR_INVALID_ARG, "group_frames is negative");
     if (n_frames == 0) return O3DR_OK;
     if (!img || !labels) return fail(O3DR_ERR_INVALID_ARG, "img / labels is NULL");
-    const int64_t ch = prm.channels;
-    if (pitch < (int64_t)cols * ch) return fail(O3DR_ERR_INVALID_ARG, "pitch smaller than a row");
-    if (n_frames > 1 && fs < (int64_t)rows * pitch) return fail(O3DR_ERR_INVALID_ARG, "frame stride smaller than a frame");
+    const ImageStack in{img, fs, pitch, rows, cols, n_frames, prm.channels};
+    STACKCHK(stack_layout_error(in));
     if ((uintptr_t)labels % 4 || (uintptr_t)raw_out % 4 || (uintptr_t)sizes_out % 4)
         return fail(O3DR_ERR_INVALID_ARG, "labels / raw_out / sizes_out must be 4-byte aligned");
+    int64_t in_bytes;
+    STACKCHK(stack_extent(in, &in_bytes));
 
     SegArgs a;
     memset(&a, 0, sizeof a);
@@ -5361,20 +5375,16 @@ static int segment_image(o3dr_ctx* c, const uint8_t* img, int64_t fs, int64_t pi
     a.fstride = fs, a.pitch = pitch;
     const size_t n = (size_t)rows * (size_t)cols, nc = (size_t)a.nx * (size_t)a.ny;
     const size_t n_chunks = (n + 4095) / 4096;
-    const size_t in_bytes = (size_t)fs * (size_t)(n_frames - 1) + (size_t)pitch * (size_t)(rows - 1) + (size_t)cols * (size_t)ch;
     const void* img_d;
-    CHK(stage_in(c, c->op[o3dr_ctx::OP_IN], img, in_bytes, mem, &img_d));
+    CHK(stage_stacks(c, (size_t)in_bytes, mem, img, &img_d));
 
-    const size_t per_frame = n * 28 + nc * 68 + n_chunks * 4;
-    size_t group = std::max<size_t>(1, kSegmentScratchBytes / per_frame);
-    group = std::min<size_t>(std::min<size_t>(group, (size_t)n_frames), 32768);
-    if (prm.group_frames > 0) group = std::min<size_t>(group, (size_t)prm.group_frames);
-    unsigned long long* info_d = nullptr;
+    const size_t group = frames_per_group(kSegmentScratchBytes, n * 28 + nc * 68 + n_chunks * 4, n_frames, prm.group_frames);
+    FrameCounters counts(info, n_frames, 5);
     int32_t* raw_scratch = nullptr;
-    CHK(carve(c, c->segment_work, [&](Carve& w) {
+    CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
         w.take(a.key, group * n);
         w.take(a.sums, group * nc * 6);
-        if (info) w.take(info_d, (size_t)n_frames * 5);
+        counts.take(w);
         if (!raw_out) w.take(raw_scratch, group * n);
         w.take(a.parent, group * n);
         w.take(a.cnt, group * n);
@@ -5383,7 +5393,7 @@ static int segment_image(o3dr_ctx* c, const uint8_t* img, int64_t fs, int64_t pi
         w.take(a.centres, group * nc * 5);
         w.take(a.partial, group * n_chunks);
     }));
-    if (info) HIPCHK(hipMemsetAsync(info_d, 0, (size_t)n_frames * 5 * sizeof(unsigned long long), c->stream));
+    CHK(counts.zero(c));
     CHK(outs.stage(c));
     int32_t *labels_d = outs.dev(labels), *raw_d = outs.dev(raw_out), *sizes_d = outs.dev(sizes_out);
     for (size_t f0 = 0; f0 < (size_t)n_frames; f0 += group) {
@@ -5392,16 +5402,15 @@ static int segment_image(o3dr_ctx* c, const uint8_t* img, int64_t fs, int64_t pi
         a.labels_out = labels_d + f0 * n;
         a.raw = raw_d ? raw_d + f0 * n : raw_scratch;
         a.sizes_out = sizes_d ? sizes_d + f0 * n : nullptr;
-        a.info = info_d ? info_d + f0 * 5 : nullptr;
+        a.info = counts.of_frame(f0);
         launch_segment_image(&c->prof, c->stream, a);
     }
     HIPCHK(hipGetLastError());
     CHK(outs.copy_back(c));
-    std::vector<unsigned long long> counts(info ? (size_t)n_frames * 5 : 0);
-    if (info) HIPCHK(hipMemcpyAsync(counts.data(), info_d, counts.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    CHK(counts.copy_back(c));
     HIPCHK(hipStreamSynchronize(c->stream));
-    for (size_t f = 0; info && f < (size_t)n_frames; ++f) {
-        const unsigned long long* k = &counts[f * 5];
+    for (size_t f = 0; f < counts.frames; ++f) {
+        const unsigned long long* k = &counts.host[f * 5];
         info[f] = o3dr_segment_info{(int64_t)nc, (int64_t)k[0], (int64_t)k[1], (int64_t)k[2], (int64_t)k[3], (int64_t)(0xffffffffull - k[4])};
     }
     return O3DR_OK;
@@ -5412,7 +5421,7 @@ extern "C" int o3dr_segment_image(o3dr_ctx* c, const uint8_t* img, int64_t frame
                                   o3dr_segment_info* info, int32_t mem)
 {
     // the outputs' sizes are known only where the shape itself is within its limits
-    const int64_t px = segment_shape_ok(rows, cols, n_frames) ? (int64_t)n_frames * rows * cols : 0;
+    const int64_t px = stack_pixels(rows, cols, n_frames, O3DR_SEGMENT_MAX_SIDE);
     Outputs outs{mem};
     outs.add(labels, px);
     outs.add(raw_out, px);
@@ -5430,13 +5439,11 @@ extern "C" int o3dr_segment_image(o3dr_ctx* c, const uint8_t* img, int64_t frame
 // =================================================================================================
 // stereo rectification (kernels/rectify.inc; DESIGN.md "Stereo rectification")
 // =================================================================================================
-static bool rect_side_ok(int32_t v) { return v >= 1 && v <= O3DR_RECTIFY_MAX_SIDE; }
-
 static int rectify_maps(o3dr_ctx* c, const o3dr_rectify_camera* cam, int32_t rows_out, int32_t cols_out, int32_t* map, Outputs& outs,
                         int32_t mem)
 {
     if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
-    if (!rect_side_ok(rows_out) || !rect_side_ok(cols_out)) return fail(O3DR_ERR_INVALID_ARG, "rows_out and cols_out must be in 1..8192");
+    if (!stack_pixels(rows_out, cols_out, 1, O3DR_RECTIFY_MAX_SIDE)) return fail(O3DR_ERR_INVALID_ARG, "rows_out and cols_out must be in 1..8192");
     if (!cam || !map) return fail(O3DR_ERR_INVALID_ARG, "cam / map is NULL");
     if ((uintptr_t)map % 4) return fail(O3DR_ERR_INVALID_ARG, "map must be 4-byte aligned");
     {
@@ -5481,7 +5488,7 @@ static int rectify_maps(o3dr_ctx* c, const o3dr_rectify_camera* cam, int32_t row
 extern "C" int o3dr_rectify_maps(o3dr_ctx* c, const o3dr_rectify_camera* cam, int32_t rows_out, int32_t cols_out, int32_t* map, int32_t mem)
 {
     Outputs outs{mem};
-    outs.add(map, rect_side_ok(rows_out) && rect_side_ok(cols_out) ? (int64_t)rows_out * cols_out * 2 : 0);
+    outs.add(map, stack_pixels(rows_out, cols_out, 1, O3DR_RECTIFY_MAX_SIDE) * 2);
     const int rc = entered(c, [&] { return rectify_maps(c, cam, rows_out, cols_out, map, outs, mem); });
     if (rc != O3DR_OK) outs.zero();
     return rc;
@@ -5491,9 +5498,8 @@ static int rectify_remap(o3dr_ctx* c, const uint8_t* src, int64_t fs, int64_t pi
                          int32_t n_frames, const int32_t* map, int32_t rows_out, int32_t cols_out, int32_t border, int32_t group_frames,
                          uint8_t* out, uint8_t* valid_out, Outputs& outs, int32_t mem)
 {
-    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
-    if (n_frames < 0) return fail(O3DR_ERR_INVALID_ARG, "bad frame count");
-    if (!rect_side_ok(rows) || !rect_side_ok(cols) || !rect_side_ok(rows_out) || !rect_side_ok(cols_out))
+    STACKCHK(stack_call_error(mem, n_frames));
+    if (stack_sides_error(rows, cols, O3DR_RECTIFY_MAX_SIDE) || stack_sides_error(rows_out, cols_out, O3DR_RECTIFY_MAX_SIDE))
         return fail(O3DR_ERR_INVALID_ARG, "rows, cols, rows_out and cols_out must be in 1..8192");
     if (channels != 1 && channels != 3) return fail(O3DR_ERR_INVALID_ARG, "channels must be 1 or 3");
     if (border < 0 || border > 255) return fail(O3DR_ERR_INVALID_ARG, "border must be in 0..255");
@@ -5501,25 +5507,22 @@ static int rectify_remap(o3dr_ctx* c, const uint8_t* src, int64_t fs, int64_t pi
     if (n_frames == 0) return O3DR_OK;
     if (!src || !map || !out) return fail(O3DR_ERR_INVALID_ARG, "src / map / out is NULL");
     if ((uintptr_t)map % 4) return fail(O3DR_ERR_INVALID_ARG, "map must be 4-byte aligned");
-    if (pitch < (int64_t)cols * channels) return fail(O3DR_ERR_INVALID_ARG, "pitch smaller than a row");
-    if (n_frames > 1 && fs < (int64_t)rows * pitch) return fail(O3DR_ERR_INVALID_ARG, "frame stride smaller than a frame");
+    const ImageStack in{src, fs, pitch, rows, cols, n_frames, channels};
+    STACKCHK(stack_layout_error(in));
     const size_t n_out = (size_t)rows_out * (size_t)cols_out;
-    const size_t in_bytes = (size_t)fs * (size_t)(n_frames - 1) + (size_t)pitch * (size_t)(rows - 1) + (size_t)cols * (size_t)channels;
-    {  // the byte ranges [src, src + in_bytes) and [out, out + n_frames * rows_out * cols_out * channels), in either memory kind
-        const uintptr_t i0 = (uintptr_t)src, o0 = (uintptr_t)out;
-        if (i0 < o0 + (uintptr_t)n_frames * n_out * (uintptr_t)channels && o0 < i0 + in_bytes)
-            return fail(O3DR_ERR_INVALID_ARG, "out must not overlap src");
-    }
+    int64_t in_bytes;
+    STACKCHK(stack_extent(in, &in_bytes));
+    if (ranges_overlap(src, (size_t)in_bytes, out, (size_t)n_frames * n_out * (size_t)channels)) return fail(O3DR_ERR_INVALID_ARG, "out must not overlap src");
     RectArgs a;
     memset(&a, 0, sizeof a);
     a.rows = rows, a.cols = cols, a.channels = channels, a.rows_out = rows_out, a.cols_out = cols_out, a.border = border;
     a.fstride = fs, a.pitch = pitch;
     const void* src_d;
-    CHK(stage_in(c, c->op[o3dr_ctx::OP_IN], src, in_bytes, mem, &src_d));
+    CHK(stage_stacks(c, (size_t)in_bytes, mem, src, &src_d));
     a.map = map;
     if (mem == O3DR_MEM_HOST) {
         int32_t* map_d = nullptr;
-        CHK(carve(c, c->rect_work, [&](Carve& w) { w.take(map_d, n_out * 2); }));
+        CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) { w.take(map_d, n_out * 2); }));
         HIPCHK(hipMemcpyAsync(map_d, map, n_out * 2 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         a.map = map_d;
     }
@@ -5545,8 +5548,7 @@ extern "C" int o3dr_rectify_remap(o3dr_ctx* c, const uint8_t* src, int64_t frame
                                   int32_t border, int32_t group_frames, uint8_t* out, uint8_t* valid_out, int32_t mem)
 {
     // the outputs' sizes are known only where the sizes that give them are within their limits
-    const bool out_ok = rect_side_ok(rows_out) && rect_side_ok(cols_out);
-    const int64_t px = out_ok ? (int64_t)rows_out * cols_out : 0;
+    const int64_t px = stack_pixels(rows_out, cols_out, 1, O3DR_RECTIFY_MAX_SIDE);
     Outputs outs{mem};
     outs.add(out, n_frames > 0 && (channels == 1 || channels == 3) ? px * n_frames * channels : 0);
     outs.add(valid_out, n_frames > 0 ? px : 0);
