@@ -113,6 +113,73 @@ def comb(H, W, dtype=np.uint8):
     return img
 
 
+def maze(H, W, seed, dtype=np.uint8, value=6):
+    """a random spanning tree of the cells at even (y, x): every cell and every opened wall pixel carries `value`, the rest
+    is 0.  One component of 2 * cells - 1 pixels whose path turns at random, so its tile-border crossings are spread over
+    every border and its union-find trees have no regular shape.  The tree is an iterative depth-first walk that takes a
+    random unvisited neighbour."""
+    rs = np.random.RandomState(seed)
+    ch, cw = (H + 1) // 2, (W + 1) // 2
+    draws = rs.randint(0, 12, ch * cw).tolist()  # one per step forward; 12 is a multiple of every number of choices
+    img = np.zeros((H, W), dtype)
+    seen = bytearray(ch * cw)
+    seen[0] = 1
+    img[0, 0] = value
+    stack = [0]
+    k = 0
+    while stack:
+        c = stack[-1]
+        y, x = divmod(c, cw)
+        free = [(dy, dx) for dy, dx in ((-1, 0), (0, -1), (0, 1), (1, 0))
+                if 0 <= y + dy < ch and 0 <= x + dx < cw and not seen[c + dy * cw + dx]]
+        if not free:
+            stack.pop()
+            continue
+        dy, dx = free[draws[k] % len(free)]
+        k += 1
+        img[2 * y + dy, 2 * x + dx] = value            # the wall between the two cells
+        img[2 * (y + dy), 2 * (x + dx)] = value
+        seen[c + dy * cw + dx] = 1
+        stack.append(c + dy * cw + dx)
+    return img
+
+
+def spiral(H, W, dtype=np.uint8, value=4):
+    """one arm, one pixel wide, with one pixel of 0 between turns: from (0, 0) clockwise inwards until it can go no further.
+    One component that crosses every tile border once per turn; consecutive pixels of the path lie up to a whole image
+    side apart in index order."""
+    rows = [bytearray(W) for _ in range(H)]
+    rows[0][0] = 1
+    y = x = d = 0
+    steps = ((0, 1), (1, 0), (0, -1), (-1, 0))
+
+    def free(y, x, dy, dx):
+        """the next pixel is inside and touches no pixel of the arm but the one it comes from"""
+        y1, x1 = y + dy, x + dx
+        if not (0 <= y1 < H and 0 <= x1 < W) or rows[y1][x1]:
+            return False
+        return not any(0 <= y2 < H and 0 <= x2 < W and rows[y2][x2] for y2, x2 in ((y1 - 1, x1), (y1 + 1, x1), (y1, x1 - 1), (y1, x1 + 1))
+                       if (y2, x2) != (y, x))
+
+    while True:
+        dy, dx = steps[d]
+        if not free(y, x, dy, dx):
+            d = (d + 1) % 4
+            dy, dx = steps[d]
+            if not free(y, x, dy, dx):
+                break
+        y, x = y + dy, x + dx
+        rows[y][x] = 1
+    return (np.frombuffer(b"".join(rows), np.uint8).reshape(H, W) * value).astype(dtype)
+
+
+def border_pairs(img):
+    """-> (valid-valid pixel pairs across each vertical tile border: x a multiple of 64, across each horizontal one: y a
+    multiple of 16), the tile being the kernels' 64 x 16"""
+    v = np.asarray(img) != 0
+    return (v[:, 63:-1:64] & v[:, 64::64]).sum(axis=0), (v[15:-1:16] & v[16::16]).sum(axis=1)
+
+
 def ramp():
     """3 x 100 uint16, steps of 3 along x"""
     return np.tile((1000 + 3 * np.arange(100)).astype(np.uint16), (3, 1))

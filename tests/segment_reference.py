@@ -2,6 +2,8 @@
 images of the segmentation tests.  Everything is an integer; int64 holds every intermediate value."""
 import numpy as np
 
+import disparity_filter_reference
+
 
 def _bgr(img):
     img = np.asarray(img)
@@ -220,6 +222,16 @@ def comb(H, W):
     img[0, :] = 255
     img[:H - 1, 0::2] = 255
     return img
+
+
+def maze(H, W, seed):
+    """two colours; the bright one is disparity_filter_reference.maze: a random spanning tree, one component"""
+    return ((disparity_filter_reference.maze(H, W, seed) != 0) * 255).astype(np.uint8)
+
+
+def spiral(H, W):
+    """two colours; the bright one is disparity_filter_reference.spiral: one arm that winds inwards, one component"""
+    return ((disparity_filter_reference.spiral(H, W) != 0) * 255).astype(np.uint8)
 
 
 def plane_fit_rms(labels, disp, true):

@@ -1,6 +1,7 @@
 """GPU tests of o3dr_disparity_filter / Context.filterDisparity (include/o3dr.h "disparity filter"): out, labels, sizes and
 every info field bit for bit against tests/disparity_filter_reference.py, at the smallest shapes at which each piece can go
-wrong.  The kernels' tile is 64 x 16 pixels: 67 x 131 has two tile borders in x and four in y, 131 x 67 one and eight."""
+wrong.  The kernels' tile is 64 x 16 pixels: 67 x 131 has two tile borders in x and four in y, 131 x 67 one and eight.
+That is 15 to 18 tiles and three workgroups of border pairs; images of 256 tiles are in tests/test_labelling_scale.py."""
 import ctypes as C
 import functools
 

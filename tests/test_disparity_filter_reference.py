@@ -84,3 +84,73 @@ def test_median_equals_scipy_median_filter(k, dtype):
     rng = np.random.RandomState(k)
     img = rng.randint(0, np.iinfo(dtype).max + 1, (33, 70)).astype(dtype)
     assert np.array_equal(R.median(img, k), ndi.median_filter(img, size=k, mode="nearest"))
+
+
+# ---- the inputs of tests/test_labelling_scale.py -------------------------------------------------------------------------
+@pytest.mark.parametrize("H,W", [(255, 1023), (67, 131)], ids=["255x1023", "67x131"])
+@pytest.mark.parametrize("name", ["maze", "spiral"])
+def test_maze_and_spiral_are_one_component(name, H, W):
+    img = R.maze(H, W, 1) if name == "maze" else R.spiral(H, W)
+    assert img.shape == (H, W) and img.dtype == np.uint8 and len(np.unique(img)) == 2 and img[0, 0] != 0
+    n_valid = int((img != 0).sum())
+    if name == "maze":  # the cells and one opened wall per edge of their spanning tree
+        assert n_valid == 2 * ((H + 1) // 2) * ((W + 1) // 2) - 1
+        assert (img[0::2, 0::2] != 0).all() and not img[1::2, 1::2].any()
+    else:               # one pixel wide: no 2 x 2 block of the arm, and every pixel but the two ends has two neighbours
+        v = np.pad(img != 0, 1)
+        assert not (v[:-1, :-1] & v[1:, :-1] & v[:-1, 1:] & v[1:, 1:]).any()
+        nb = (v[:-2, 1:-1].astype(int) + v[2:, 1:-1] + v[1:-1, :-2] + v[1:-1, 2:])[v[1:-1, 1:-1]]
+        assert sorted(np.unique(nb).tolist()) == [1, 2] and (nb == 1).sum() == 2 and n_valid > H * W // 2 - 2 * (H + W)
+    _, labels, sizes, info = R.filter_disparity(img, max_speckle_size=100)
+    assert info.n_components == 1 and info.largest == n_valid and info.n_valid == n_valid and info.n_removed == 0
+    assert (labels[img != 0] == 0).all() and (labels[img == 0] == -1).all() and (sizes[img != 0] == n_valid).all()
+
+
+@pytest.mark.parametrize("H,W", [(255, 1023), (67, 131)], ids=["255x1023", "67x131"])
+@pytest.mark.parametrize("name", ["maze", "spiral"])
+def test_maze_and_spiral_cross_every_tile_border(name, H, W):
+    """serpentine has one valid pair per horizontal tile border and comb one per vertical one; these two cross every border
+    of either kind, at 255 x 1023 with at least 500 pairs of each kind (67 x 131 has 134 and 524 pairs in all)"""
+    img = R.maze(H, W, 1) if name == "maze" else R.spiral(H, W)
+    vert, horz = R.border_pairs(img)
+    assert len(vert) == (W - 1) // 64 and len(horz) == (H - 1) // 16 and vert.min() >= 1 and horz.min() >= 1
+    print(f"{name} {H}x{W}: {int(vert.sum())} pairs across vertical tile borders, {int(horz.sum())} across horizontal ones")
+    if (H, W) == (255, 1023):
+        assert vert.sum() >= 500 and horz.sum() >= 500
+        assert R.border_pairs(R.serpentine(H, W))[1].sum() == 15 and R.border_pairs(R.comb(H, W))[0].sum() == 15
+
+
+def csgraph_partition(joined_right, joined_down, valid):
+    """labels and sizes as R.components gives them, by scipy's connected components of the graph of the joined 4-neighbour
+    pairs (joined_right [H, W - 1]: pixel (y, x) with (y, x + 1); joined_down [H - 1, W]: with (y + 1, x))"""
+    sparse = pytest.importorskip("scipy.sparse")
+    csgraph = pytest.importorskip("scipy.sparse.csgraph")
+    H, W = valid.shape
+    idx = np.arange(H * W).reshape(H, W)
+    a = np.concatenate([idx[:, :-1][joined_right], idx[:-1][joined_down]])
+    b = np.concatenate([idx[:, 1:][joined_right], idx[1:][joined_down]])
+    graph = sparse.coo_matrix((np.ones(len(a), np.int8), (a, b)), shape=(H * W, H * W))
+    n, comp = csgraph.connected_components(graph, directed=False)
+    lowest = np.full(n, H * W, np.int64)
+    np.minimum.at(lowest, comp, np.arange(H * W))
+    labels = np.where(valid.ravel(), lowest[comp], -1).astype(np.int32)
+    sizes = np.where(valid.ravel(), np.bincount(comp, minlength=n)[comp], 0).astype(np.int32)
+    return labels.reshape(H, W), sizes.reshape(H, W)
+
+
+SCALE_PARTITIONS = [("maze", 1), ("spiral", 1), ("levels uint8", 0), ("levels uint8", 1), ("levels uint16", 0), ("levels uint16", 20000)]
+
+
+@pytest.mark.parametrize("name,max_diff", SCALE_PARTITIONS, ids=[f"{n} max_diff {d}" for n, d in SCALE_PARTITIONS])
+def test_components_equal_csgraph_at_255x1023(name, max_diff):
+    import labelling_scale_cases as X
+    img = X.df_input(name, 255, 1023)
+    v = img.astype(np.int64)
+    ok = v != 0
+    right = ok[:, :-1] & ok[:, 1:] & (np.abs(v[:, :-1] - v[:, 1:]) <= max_diff)
+    down = ok[:-1] & ok[1:] & (np.abs(v[:-1] - v[1:]) <= max_diff)
+    labels, sizes = csgraph_partition(right, down, ok)
+    got = R.components(img, max_diff)
+    assert got[0].dtype == labels.dtype and got[1].dtype == sizes.dtype
+    assert np.array_equal(got[0], labels) and np.array_equal(got[1], sizes)
+    assert sizes.max() > 20 and (labels[ok].max() == 0) == (name in ("maze", "spiral"))

@@ -1,6 +1,7 @@
 """GPU tests of o3dr_segment_image / Context.segmentImage (include/o3dr.h "image segmentation"): labels, raw, sizes and
 every info field bit for bit against tests/segment_reference.py, at the smallest shapes at which each piece can go wrong.
-The kernels' tile is 64 x 16 pixels: 67 x 131 has two tile borders in x and four in y, 70 x 33 none in x and four in y."""
+The kernels' tile is 64 x 16 pixels: 67 x 131 has two tile borders in x and four in y, 70 x 33 none in x and four in y.
+That is 15 tiles and the single-workgroup scan; images of 256 tiles and the chunked scan are in tests/test_labelling_scale.py."""
 import ctypes as C
 import functools
 import itertools

@@ -127,3 +127,22 @@ def test_accuracy_on_known_regions(S, m):
     fit_rms = R.plane_fit_rms(labels, disp, true)
     print(f"S={S} m={m}: plane-fit RMS {fit_rms:.3f} against raw {raw_rms:.3f}")
     assert fit_rms < 0.5 * raw_rms
+
+
+def _scale_cases():
+    import labelling_scale_cases as X
+    return X.SEG_CASES
+
+
+@pytest.mark.parametrize("case", _scale_cases(), ids=lambda c: f"{c[0]} {c[1]}x{c[2]} S {c[3]} K {c[5]}")
+def test_components_equal_csgraph_on_the_scale_cases(case):
+    """the raw labels of every segmentation tests/test_labelling_scale.py asks for: R.components against scipy's connected
+    components of the graph of equal-label 4-neighbour pairs, the root being the lowest index of the component"""
+    import labelling_scale_cases as X
+    from test_disparity_filter_reference import csgraph_partition
+    raw = X.seg_reference(*case)[1].astype(np.int64)
+    labels, sizes = csgraph_partition(raw[:, :-1] == raw[:, 1:], raw[:-1] == raw[1:], np.ones(raw.shape, bool))
+    root = R.components(raw)
+    assert np.array_equal(root, labels)
+    assert np.array_equal(np.bincount(root.ravel(), minlength=raw.size)[root], sizes)
+    assert X.seg_reference(*case)[3][0]["n_components"] == len(np.unique(labels))
