@@ -148,6 +148,10 @@ class MultiviewInfoStruct(C.Structure):
                 ("n_occluded", C.c_int64)]
 
 
+class MultiviewFuseInfoStruct(C.Structure):
+    _fields_ = [("filter", MultiviewInfoStruct), ("n_votes", C.c_int64), ("n_votes_dropped", C.c_int64), ("n_fused", C.c_int64)]
+
+
 MULTIVIEW_MAX_SIDE, MULTIVIEW_MAX_NEIGHBORS = 8192, 16
 
 
@@ -329,6 +333,8 @@ SYMBOLS = [
     ("o3dr_multiview_homographies", C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp]),
     ("o3dr_multiview_filter", C.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _i32, C.POINTER(MultiviewParamsStruct), _vp, _vp,
                                         _vp, _vp, _i32]),
+    ("o3dr_multiview_fuse", C.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _i32, C.POINTER(MultiviewParamsStruct), _vp, _vp,
+                                      _vp, _vp, _vp, _i32]),
     ("o3dr_segment_default_params", None, [C.POINTER(SegmentParamsStruct)]),
     ("o3dr_segment_image", C.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, C.POINTER(SegmentParamsStruct), _vp, _vp, _vp, _vp, _i32]),
     ("o3dr_rectify_maps", C.c_int, [_vp, C.POINTER(RectifyCameraStruct), _i32, _i32, _vp, _i32]),

@@ -133,6 +133,16 @@ class MultiviewInfo:
 
 
 @dataclass
+class MultiviewFuseInfo:
+    """o3dr_multiview_fuse's counts for one frame: the filter's counts for the same call, the supports that voted and
+    those that did not (their sum is filter.n_support), and the kept pixels with at least one vote."""
+    filter: MultiviewInfo
+    n_votes: int
+    n_votes_dropped: int
+    n_fused: int
+
+
+@dataclass
 class SegmentInfo:
     """o3dr_segment_image's counts for one frame: k-means centres, components of equal raw labels, components merged into
     another one, final labels, and the pixel counts of the largest and the smallest label."""
@@ -193,7 +203,7 @@ def image_stack_layout(shape, strides, itemsize, colour, contiguous=False):
     return StackLayout(single, F, rows, cols, ch, pitch, 0 if single else rows * pitch, True)
 
 
-_TORCH_DTYPE = {np.uint8: "uint8", np.uint16: "int16", np.int32: "int32", np.float32: "float32"}
+_TORCH_DTYPE = {np.uint8: "uint8", np.uint16: "int16", np.int32: "int32", np.float32: "float32", np.float64: "float64"}
 
 
 def _dtype_name(x):
@@ -879,6 +889,43 @@ class Context:
         infos = [MultiviewInfo(*(int(getattr(i, n)) for n, _ in L.MultiviewInfoStruct._fields_)) for i in info] if return_info else None
         return (out,) + ((support,) if return_support else ()) + ((violations,) if return_violations else ()) + \
             ((infos,) if return_info else ())
+
+    def multiviewFuse(self, disp, poses, neighbors=None, k=4, max_distance=float("inf"), tolerance=1.0, min_support=1,
+                      max_violations=-1, return_votes=False, return_support=False, return_violations=False, return_info=False):
+        """multiviewFilter's tests and keep rule, and for every kept pixel the mean of its own level and the levels its
+        supporting neighbours vote for (the level on the pixel's own ray at which the neighbour would have seen exactly what
+        it saw), summed in the order of the neighbour list - contract: include/o3dr.h "multi-view fusion".  Inputs as in
+        multiviewFilter.  -> float64 levels [F, H, W], 0.0 at a removed or invalid pixel: what Params(disparity_f64=True)
+        and the frame calls read; numpy in gives numpy out, a torch CUDA tensor gives CUDA tensors and nothing leaves HBM.
+        return_votes / return_support / return_violations: uint8 count images follow in that order; return_info: a list of
+        MultiviewFuseInfo, one per frame, follows."""
+        dev = _is_torch(disp)
+        nd = disp.dim() if dev else np.ndim(disp)
+        assert nd == 3
+        F, rows, cols = (int(v) for v in disp.shape)
+        poses = np.ascontiguousarray(poses.cpu().numpy() if _is_torch(poses) else poses, np.float32).reshape(-1, 16)
+        assert len(poses) == F
+        if neighbors is None:
+            neighbors = nearbyFrames(poses, k, max_distance)
+        neighbors = np.ascontiguousarray(neighbors.cpu().numpy() if _is_torch(neighbors) else neighbors, np.int32).reshape(F, -1)
+        kk = int(neighbors.shape[1])
+        disp, (_, _, _, _, _, pitch, fs, _), pi, mem = self._image_stack(disp, colour=False)
+        assert _dtype_name(disp) in (("uint8", "uint16", "int16", "float64") if dev else ("uint8", "uint16", "float64"))
+        prm = L.MultiviewParamsStruct(_itemsize(disp), float(tolerance), int(min_support), int(max_violations))
+        shape = (F, rows, cols)
+        out, votes, support, violations = self._empty_like(disp, (shape, np.float64), (shape, np.uint8) if return_votes else None,
+                                                           (shape, np.uint8) if return_support else None,
+                                                           (shape, np.uint8) if return_violations else None)
+        info = (L.MultiviewFuseInfoStruct * F)() if return_info else None
+        L.check(self._lib.o3dr_multiview_fuse(self._h, pi, fs, pitch, rows, cols, F, poses.ctypes.data, neighbors.ctypes.data, kk,
+                                              C.byref(prm), _addr(out), _addr(votes), _addr(support), _addr(violations),
+                                              C.cast(info, C.c_void_p) if return_info else None, mem))
+        if not (return_votes or return_support or return_violations or return_info):
+            return out
+        infos = [MultiviewFuseInfo(MultiviewInfo(*(int(getattr(i.filter, n)) for n, _ in L.MultiviewInfoStruct._fields_)),
+                                   int(i.n_votes), int(i.n_votes_dropped), int(i.n_fused)) for i in info] if return_info else None
+        return (out,) + ((votes,) if return_votes else ()) + ((support,) if return_support else ()) + \
+            ((violations,) if return_violations else ()) + ((infos,) if return_info else ())
 
     # -- image segmentation (the label image planeFitDisparity reads; the reference takes it from offline files) ---------------
     def segmentImage(self, img, step=16, compactness=20, iterations=5, min_size=None, return_raw=False, return_sizes=False,

@@ -4,12 +4,13 @@
 // =================================================================================================
 // Multi-view filter: every valid pixel of a frame is carried into each listed neighbour frame by one 4 x 4 fp64 matrix
 // and compared with what that frame saw there (contract: include/o3dr.h "multi-view filter"; DESIGN.md "Multi-view
-// filter").  One launch, one thread per pixel, a 32 x 8 tile per workgroup, the frame in blockIdx.y: the neighbour list
-// and the matrices of a workgroup are the same for every lane, so the compiler fetches them with scalar loads and the
-// loop over the neighbours is wave-uniform.  The neighbour's pixel is a plain gather from the input - H is smooth, so
-// the lanes of a wave land next to each other and the lines come out of L2.  Neighbours are read from the input only:
-// no pixel's result depends on another's, hence on no schedule.  The translation unit is built with -ffp-contract=off:
-// every product below is rounded before it is added, as the contract's numpy restatement does it.
+// filter"); the fusion ("multi-view fusion") runs the same tests and averages what the agreeing frames saw.  One launch,
+// one thread per pixel, a 32 x 8 tile per workgroup, the frame in blockIdx.y: the neighbour list and the matrices of a
+// workgroup are the same for every lane, so the compiler fetches them with scalar loads and the loop over the neighbours
+// is wave-uniform.  The neighbour's pixel is a plain gather from the input - H is smooth, so the lanes of a wave land next
+// to each other and the lines come out of L2.  Neighbours are read from the input only: no pixel's result depends on
+// another's, hence on no schedule.  The translation unit is built with -ffp-contract=off: every product below is rounded
+// before it is added, as the contract's numpy restatement does it.
 //
 // The per-frame counts are integers: ballots and a packed wave sum, LDS atomics per wave, then one 64-bit atomic per
 // counter and workgroup.  All stores are plain vector stores or atomics.
@@ -33,15 +34,21 @@ __device__ __forceinline__ bool mv_level(double v, double& d)
     return v > 0.0 && v <= 1.7976931348623157e308;  // (false on NaN and on +inf)
 }
 
-template <class T>
-__global__ __launch_bounds__(kMvTileX* kMvTileY) void k_multiview_filter(MvArgs a, int tiles_x)
+// One pixel of the filter (kFuse = false) or of the fusion (kFuse = true; contract: include/o3dr.h "multi-view fusion").  The
+// fusion runs the filter's tests unchanged and adds, per supporting neighbour, the level v on this pixel's own ray at which
+// the neighbour would have seen exactly what it saw (two products and sums that the test already has in part, one more
+// division), the sum of those votes in the order of the neighbour list, an 8-byte store per lane in place of the filter's
+// element, and three more counters: a second packed wave sum for the two per-support counts, a ballot for the third.
+template <class T, bool kFuse>
+__device__ __forceinline__ void mv_pixel(const MvArgs& a, int tiles_x)
 {
-    __shared__ unsigned int s_cnt[9];
+    constexpr int kWords = kFuse ? 12 : 9;
+    __shared__ unsigned int s_cnt[kWords];
     const int f = a.f0 + (int)blockIdx.y, W = a.cols, Hh = a.rows;
     const int tid = (int)threadIdx.x;
     const int x = (int)(blockIdx.x % tiles_x) * kMvTileX + (tid & (kMvTileX - 1));
     const int y = (int)(blockIdx.x / tiles_x) * kMvTileY + tid / kMvTileX;
-    if (tid < 9) s_cnt[tid] = 0;
+    if (tid < kWords) s_cnt[tid] = 0;
     __syncthreads();
     const bool in = x < W && y < Hh;
     const char* base = (const char*)a.in;
@@ -53,7 +60,8 @@ __global__ __launch_bounds__(kMvTileX* kMvTileY) void k_multiview_filter(MvArgs 
         valid = mv_level(v, d);
     }
     const double xd = (double)x, yd = (double)y, Wd = (double)W, Hd = (double)Hh;
-    unsigned int sup = 0, vio = 0, n_out = 0, n_hole = 0, n_occ = 0;
+    unsigned int sup = 0, vio = 0, n_out = 0, n_hole = 0, n_occ = 0, votes = 0;
+    double acc = d;  // (fusion: the pixel's own level, then every vote)
     const int32_t* __restrict__ nb = a.neighbors + (int64_t)f * a.k;
     const double* __restrict__ Hf = a.H + (int64_t)f * a.k * 16;
     for (int n = 0; n < a.k; ++n) {  // (wave-uniform: nb and Hf depend on the workgroup alone)
@@ -81,13 +89,29 @@ __global__ __launch_bounds__(kMvTileX* kMvTileY) void k_multiview_filter(MvArgs 
         n_out += valid && !inside;
         n_hole += inside && !ok;
         n_occ += inside && ok && !is_sup && !is_vio;
+        if constexpr (kFuse) {
+            const double a2 = (M[8] * xd + M[9] * yd) + M[11];
+            const double a3 = (M[12] * xd + M[13] * yd) + M[15];
+            const double num = e * a3 - a2;
+            const double den = M[10] - e * M[14];
+            const double vt = num / den;  // dp(vt) = e
+            if (is_sup && vt > 0.0 && vt <= 1.7976931348623157e308) {  // (false on NaN and on +inf)
+                acc = acc + vt;
+                ++votes;
+            }
+        }
     }
     const bool enough = (int)sup >= a.min_support;
     const bool calm = a.max_violations < 0 ? vio < sup : (int)vio <= a.max_violations;
     const bool keep = valid && enough && calm;
     if (in) {
         const int64_t o = ((int64_t)f * Hh + y) * W + x;
-        ((T*)a.out)[o] = valid && !keep ? T(0) : v;
+        if constexpr (kFuse) {
+            a.fused_out[o] = keep ? acc / (double)(1u + votes) : 0.0;
+            if (a.votes_out) a.votes_out[o] = (uint8_t)votes;
+        } else {
+            ((T*)a.out)[o] = valid && !keep ? T(0) : v;
+        }
         if (a.support_out) a.support_out[o] = (uint8_t)sup;
         if (a.violations_out) a.violations_out[o] = (uint8_t)vio;
     }
@@ -99,6 +123,15 @@ __global__ __launch_bounds__(kMvTileX* kMvTileY) void k_multiview_filter(MvArgs 
                                 (unsigned long long)vio << 36 | (unsigned long long)n_occ << 48;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) pk += __shfl_xor(pk, o);
+        // fusion: the votes and the supports that did not vote (at most 16 each, both 0 at an invalid pixel), and the kept
+        // pixels that were fused
+        unsigned int pv = kFuse ? votes | (sup - votes) << 12 : 0u;
+        unsigned long long bf = 0;
+        if constexpr (kFuse) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) pv += __shfl_xor(pv, o);
+            bf = __ballot(keep && votes > 0);
+        }
         if ((tid & 63) == 0) {
             atomicAdd(&s_cnt[0], (unsigned int)__popcll(bv));
             atomicAdd(&s_cnt[1], (unsigned int)__popcll(bk));
@@ -106,8 +139,24 @@ __global__ __launch_bounds__(kMvTileX* kMvTileY) void k_multiview_filter(MvArgs 
             atomicAdd(&s_cnt[3], (unsigned int)__popcll(bc));
 #pragma unroll
             for (int q = 0; q < 5; ++q) atomicAdd(&s_cnt[4 + q], (unsigned int)(pk >> (12 * q)) & 0xFFFu);
+            if constexpr (kFuse) {
+                atomicAdd(&s_cnt[9], pv & 0xFFFu);
+                atomicAdd(&s_cnt[10], pv >> 12);
+                atomicAdd(&s_cnt[11], (unsigned int)__popcll(bf));
+            }
         }
         __syncthreads();
-        if (tid < 9 && s_cnt[tid]) atomicAdd(a.info + (int64_t)f * 9 + tid, (unsigned long long)s_cnt[tid]);
+        if (tid < kWords && s_cnt[tid]) atomicAdd(a.info + (int64_t)f * kWords + tid, (unsigned long long)s_cnt[tid]);
     }
+}
+
+template <class T>
+__global__ __launch_bounds__(kMvTileX* kMvTileY) void k_multiview_filter(MvArgs a, int tiles_x)
+{
+    mv_pixel<T, false>(a, tiles_x);
+}
+template <class T>
+__global__ __launch_bounds__(kMvTileX* kMvTileY) void k_multiview_fuse(MvArgs a, int tiles_x)
+{
+    mv_pixel<T, true>(a, tiles_x);
 }

@@ -5240,9 +5240,13 @@ extern "C" int o3dr_multiview_homographies(o3dr_ctx* c, const float* poses, int3
 
 static bool multiview_elem_ok(int32_t e) { return e == 1 || e == 2 || e == 8; }
 
-static int multiview_filter(o3dr_ctx* c, const void* disp, int64_t fs, int64_t pitch, int32_t rows, int32_t cols, int32_t n_frames,
-                            const float* poses, const int32_t* neighbors, int32_t k, const o3dr_multiview_params* p, uint8_t* out,
-                            uint8_t* support_out, uint8_t* violations_out, o3dr_multiview_info* info, Outputs& outs, int32_t mem)
+// The filter and the fusion: one front end.  The filter writes `out` (the input's element type) and nine counters a frame
+// into `info`; the fusion (fused != nullptr in a valid call; `fuse` says which entry point this is) writes `fused` and
+// `votes_out` instead and twelve counters a frame into `finfo`.
+static int multiview_run(o3dr_ctx* c, const void* disp, int64_t fs, int64_t pitch, int32_t rows, int32_t cols, int32_t n_frames,
+                         const float* poses, const int32_t* neighbors, int32_t k, const o3dr_multiview_params* p, bool fuse, uint8_t* out,
+                         double* fused, uint8_t* votes_out, uint8_t* support_out, uint8_t* violations_out, o3dr_multiview_info* info,
+                         o3dr_multiview_fuse_info* finfo, Outputs& outs, int32_t mem)
 {
     STACKCHK(stack_call_error(mem, n_frames));
     o3dr_multiview_params prm;
@@ -5256,15 +5260,16 @@ static int multiview_filter(o3dr_ctx* c, const void* disp, int64_t fs, int64_t p
         return fail(O3DR_ERR_INVALID_ARG, "max_violations must be in -1..16");
     if (k < 0 || k > O3DR_MULTIVIEW_MAX_NEIGHBORS) return fail(O3DR_ERR_INVALID_ARG, "k must be in 0..16");
     if (n_frames == 0) return O3DR_OK;
-    if (!disp || !out) return fail(O3DR_ERR_INVALID_ARG, "disp / out is NULL");
-    const int64_t E = prm.elem_bytes;
+    const void* dst = fuse ? (const void*)fused : (const void*)out;
+    if (!disp || !dst) return fail(O3DR_ERR_INVALID_ARG, "disp / out is NULL");
+    const int64_t E = prm.elem_bytes, E_out = fuse ? (int64_t)sizeof(double) : E;
     const ImageStack in{disp, fs, pitch, rows, cols, n_frames, prm.elem_bytes};
     STACKCHK(stack_layout_error(in));
-    if (!stack_aligned(in, E) || (uintptr_t)out % (uintptr_t)E) return fail(O3DR_ERR_INVALID_ARG, "images must be aligned to their element size");
+    if (!stack_aligned(in, E) || (uintptr_t)dst % (uintptr_t)E_out) return fail(O3DR_ERR_INVALID_ARG, "images must be aligned to their element size");
     const size_t n = (size_t)rows * (size_t)cols;
     int64_t in_bytes;
     STACKCHK(stack_extent(in, &in_bytes));
-    if (ranges_overlap(disp, (size_t)in_bytes, out, (size_t)n_frames * n * (size_t)E)) return fail(O3DR_ERR_INVALID_ARG, "out must not overlap disp");
+    if (ranges_overlap(disp, (size_t)in_bytes, dst, (size_t)n_frames * n * (size_t)E_out)) return fail(O3DR_ERR_INVALID_ARG, "out must not overlap disp");
     const size_t n_pairs = (size_t)n_frames * (size_t)k;
     std::vector<double> H(n_pairs * 16);  // (outlives the upload: the call synchronises at its end)
     CHK(multiview_matrices(c, poses, n_frames, neighbors, k, H.data()));
@@ -5278,7 +5283,8 @@ static int multiview_filter(o3dr_ctx* c, const void* disp, int64_t fs, int64_t p
     a.min_support = prm.min_support, a.max_violations = prm.max_violations, a.tolerance = prm.tolerance;
     double* H_d = nullptr;
     int32_t* nb_d = nullptr;
-    FrameCounters counts(info, n_frames, 9);
+    const size_t words = fuse ? 12 : 9;
+    FrameCounters counts(fuse ? (const void*)finfo : (const void*)info, n_frames, words);
     CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
         w.take(H_d, n_pairs * 16);
         w.take(nb_d, n_pairs);
@@ -5291,16 +5297,26 @@ static int multiview_filter(o3dr_ctx* c, const void* disp, int64_t fs, int64_t p
     CHK(counts.zero(c));
     CHK(outs.stage(c));
     a.H = H_d, a.neighbors = nb_d, a.info = counts.dev;
-    a.out = outs.dev(out), a.support_out = outs.dev(support_out), a.violations_out = outs.dev(violations_out);
-    launch_multiview_filter(&c->prof, c->stream, a);
+    a.support_out = outs.dev(support_out), a.violations_out = outs.dev(violations_out);
+    if (fuse) {
+        a.fused_out = outs.dev(fused), a.votes_out = outs.dev(votes_out);
+        launch_multiview_fuse(&c->prof, c->stream, a);
+    } else {
+        a.out = outs.dev(out);
+        launch_multiview_filter(&c->prof, c->stream, a);
+    }
     HIPCHK(hipGetLastError());
     CHK(outs.copy_back(c));
     CHK(counts.copy_back(c));
     HIPCHK(hipStreamSynchronize(c->stream));
     for (size_t f = 0; f < counts.frames; ++f) {
-        const unsigned long long* q = &counts.host[f * 9];
-        info[f] = o3dr_multiview_info{(int64_t)q[0], (int64_t)q[1], (int64_t)q[2], (int64_t)q[3], (int64_t)q[4],
-                                      (int64_t)q[5], (int64_t)q[6], (int64_t)q[7], (int64_t)q[8]};
+        const unsigned long long* q = &counts.host[f * words];
+        const o3dr_multiview_info fi{(int64_t)q[0], (int64_t)q[1], (int64_t)q[2], (int64_t)q[3], (int64_t)q[4],
+                                     (int64_t)q[5], (int64_t)q[6], (int64_t)q[7], (int64_t)q[8]};
+        if (fuse)
+            finfo[f] = o3dr_multiview_fuse_info{fi, (int64_t)q[9], (int64_t)q[10], (int64_t)q[11]};
+        else
+            info[f] = fi;
     }
     return O3DR_OK;
 }
@@ -5318,12 +5334,35 @@ extern "C" int o3dr_multiview_filter(o3dr_ctx* c, const void* disp, int64_t fram
     outs.add(support_out, px);
     outs.add(violations_out, px);
     const int rc = entered(c, [&] {
-        return multiview_filter(c, disp, frame_stride, pitch, rows, cols, n_frames, poses, neighbors, k, p, (uint8_t*)out, support_out,
-                                violations_out, info, outs, mem);
+        return multiview_run(c, disp, frame_stride, pitch, rows, cols, n_frames, poses, neighbors, k, p, false, (uint8_t*)out, nullptr,
+                             nullptr, support_out, violations_out, info, nullptr, outs, mem);
     });
     if (rc != O3DR_OK) {
         outs.zero();
         if (info && px > 0) memset(info, 0, sizeof(o3dr_multiview_info) * (size_t)n_frames);
+    }
+    return rc;
+}
+
+// multi-view fusion (contract: include/o3dr.h "multi-view fusion"): the filter's checks and staging, the fusion's kernel
+extern "C" int o3dr_multiview_fuse(o3dr_ctx* c, const void* disp, int64_t frame_stride, int64_t pitch, int32_t rows, int32_t cols,
+                                   int32_t n_frames, const float* poses, const int32_t* neighbors, int32_t k,
+                                   const o3dr_multiview_params* p, double* out, uint8_t* votes_out, uint8_t* support_out,
+                                   uint8_t* violations_out, o3dr_multiview_fuse_info* info, int32_t mem)
+{
+    const int64_t px = stack_pixels(rows, cols, n_frames, O3DR_MULTIVIEW_MAX_SIDE);
+    Outputs outs{mem};
+    outs.add(out, px);  // (float64 whatever the input's element size)
+    outs.add(votes_out, px);
+    outs.add(support_out, px);
+    outs.add(violations_out, px);
+    const int rc = entered(c, [&] {
+        return multiview_run(c, disp, frame_stride, pitch, rows, cols, n_frames, poses, neighbors, k, p, true, nullptr, out, votes_out,
+                             support_out, violations_out, nullptr, info, outs, mem);
+    });
+    if (rc != O3DR_OK) {
+        outs.zero();
+        if (info && px > 0) memset(info, 0, sizeof(o3dr_multiview_fuse_info) * (size_t)n_frames);
     }
     return rc;
 }

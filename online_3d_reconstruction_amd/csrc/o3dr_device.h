@@ -637,6 +637,8 @@ void launch_disparity_filter(Profiler* pf, hipStream_t s, const DfArgs& a);
 // Multi-view filter (kernels/multiview.inc; contract: include/o3dr.h "multi-view filter").  One MvArgs describes the whole
 // call: `in` with its byte strides, the neighbour lists [frames][k] and their matrices [frames][k][16] (row-major, made on
 // the host), the outputs with rows tight.  info: [frames][9] in o3dr_multiview_info's order; nullptr: not asked for.
+// launch_multiview_fuse (contract: "multi-view fusion") takes the same struct: it writes fused_out (float64 levels) and
+// votes_out in place of `out`, and its info is [frames][12]: the filter's nine, then n_votes, n_votes_dropped, n_fused.
 struct MvArgs {
     const void* in;
     int64_t fstride, pitch;
@@ -647,8 +649,11 @@ struct MvArgs {
     void* out;
     uint8_t *support_out, *violations_out;  // each nullptr: not asked for
     unsigned long long* info;
+    double* fused_out;   // the fusion alone
+    uint8_t* votes_out;  // the fusion alone; nullptr: not asked for
 };
 void launch_multiview_filter(Profiler* pf, hipStream_t s, const MvArgs& a);
+void launch_multiview_fuse(Profiler* pf, hipStream_t s, const MvArgs& a);
 // Image segmentation (kernels/segment_image.inc; contract: include/o3dr.h "image segmentation").  One SegArgs describes a
 // group of `frames` frames; every array holds the group's frames one after the other.  centres: [nx * ny][5] int32 x, y,
 // B, G, R; sums: [nx * ny][6] n, sum x, sum y, sum B, sum G, sum R.  Per pixel: raw (the centre index), parent / cnt (the

@@ -36,7 +36,7 @@
 //   orb          ORB features: grey pyramid, FAST score + box sums, candidates, exact selection, steered BRIEF
 //   stereo       stereo disparity: grey + census, semi-global aggregation (one wave per scan line), winner + left-right check
 //   disparity_filter  median and speckle removal of a disparity image: LDS median network, tiled union-find labelling
-//   multiview    multi-view consistency of a stack of disparity images: one fp64 matrix per (frame, neighbour), one gather per test
+//   multiview    multi-view consistency and fusion of a stack of disparity images: one fp64 matrix per (frame, neighbour), one gather per test
 //   segment_image  superpixel labels of a colour image: tiled k-means with LDS sums, the filter's union-find, merge, ordered numbering
 //   rectify      stereo rectification: the fp64 Q5 map of one camera, the integer bilinear remap of a group of frames
 //   pose_chain   the feature-matched pose chain: one workgroup walks the frames (gather, moments, Kabsch, residual)
@@ -775,8 +775,8 @@ void launch_disparity_filter(Profiler* pf, hipStream_t s, const DfArgs& a)
         disparity_filter_frames<uint16_t>(pf, s, a);
 }
 
-// multi-view filter: one launch per 65535 frames (the grid's y extent); the launches depend on the sizes alone
-template <class T>
+// multi-view filter and fusion: one launch per 65535 frames (the grid's y extent); the launches depend on the sizes alone
+template <class T, bool kFuse>
 static void multiview_frames(Profiler* pf, hipStream_t s, MvArgs a)
 {
     ProfScope ps(pf, O3DR_K_MULTIVIEW, s);
@@ -784,19 +784,25 @@ static void multiview_frames(Profiler* pf, hipStream_t s, MvArgs a)
     for (int f0 = 0; f0 < a.frames; f0 += 65535) {
         a.f0 = f0;
         const int nf = a.frames - f0 < 65535 ? a.frames - f0 : 65535;
-        k_multiview_filter<T><<<dim3(tiles_x * tiles_y, nf), kMvTileX * kMvTileY, 0, s>>>(a, tiles_x);
+        if (kFuse)
+            k_multiview_fuse<T><<<dim3(tiles_x * tiles_y, nf), kMvTileX * kMvTileY, 0, s>>>(a, tiles_x);
+        else
+            k_multiview_filter<T><<<dim3(tiles_x * tiles_y, nf), kMvTileX * kMvTileY, 0, s>>>(a, tiles_x);
     }
 }
-void launch_multiview_filter(Profiler* pf, hipStream_t s, const MvArgs& a)
+template <bool kFuse>
+static void multiview_launch(Profiler* pf, hipStream_t s, const MvArgs& a)
 {
     if (a.frames <= 0) return;
     if (a.elem == 1)
-        multiview_frames<uint8_t>(pf, s, a);
+        multiview_frames<uint8_t, kFuse>(pf, s, a);
     else if (a.elem == 2)
-        multiview_frames<uint16_t>(pf, s, a);
+        multiview_frames<uint16_t, kFuse>(pf, s, a);
     else
-        multiview_frames<double>(pf, s, a);
+        multiview_frames<double, kFuse>(pf, s, a);
 }
+void launch_multiview_filter(Profiler* pf, hipStream_t s, const MvArgs& a) { multiview_launch<false>(pf, s, a); }
+void launch_multiview_fuse(Profiler* pf, hipStream_t s, const MvArgs& a) { multiview_launch<true>(pf, s, a); }
 
 // image segmentation of one group of frames (a.frames <= 65535: the grid's y extent); the launches depend on the
 // parameters and the image's size alone

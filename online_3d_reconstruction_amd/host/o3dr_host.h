@@ -188,6 +188,8 @@ public:
     bool multiview_filter = false;    // --multiview_filter: every cycle's accepted frames go through o3dr_multiview_filter once the
                                       // cycle's poses are final (recorded, --feature_poses, --refine_poses) and before they are
                                       // accumulated; neighbours are chosen among that cycle's accepted frames (single-GPU batched path)
+    bool multiview_fuse = false;      // --multiview_fuse: the same step through o3dr_multiview_fuse; the cycle's frames are then accumulated
+                                      // as float64 levels (disparity_f64 for that call); with --multiview_filter it means fuse
     int mv_neighbors = 4;             // --mv_neighbors k, --mv_max_distance m: o3dr_nearby_frames; parsed and ignored without the flag
     double mv_max_distance = HUGE_VAL;
     double mv_tolerance = 1.0;        // --mv_tolerance t (levels), --mv_min_support n, --mv_max_violations n (-1: the majority rule)

@@ -540,6 +540,12 @@ void Pose::printUsage()
             "                     the variance gate has seen the unfiltered image; not available with --gpus N > 1,\n"
             "                     --partitioned_merge, --reference_fanout, --use_segment_labels, --blur_kernel > 1; without the flag the\n"
             "                     --mv_* flags are parsed and ignored; the flags are this build's own)\n"
+            "       [--multiview_fuse]\n"
+            "                     (reconstruction run: the same step with the same --mv_* flags and neighbours, but every pixel that\n"
+            "                     stays is replaced by the mean of its own level and the levels its agreeing neighbours vote for\n"
+            "                     (o3dr_multiview_fuse), and the cycle's frames are accumulated as 64-bit float levels; one line per\n"
+            "                     cycle reports the pixels kept and the votes; given together with --multiview_filter it means fuse;\n"
+            "                     not available where --multiview_filter is not; the flag is this build's own)\n"
             "Without --feature_poses the run uses the recorded MAVLink poses (--only_MAVLink).  The ICP trajectory correction,\n"
             "visualisation and --segment_cloud in a reconstruction run are not part of this build.\n";
 }
@@ -695,6 +701,7 @@ int Pose::parseCmdArgs(int argc, char** argv)
         else if (a == "--orb_scale") orb_scale = (float)atof(need(i));
         else if (a == "--orb_fast_threshold") orb_fast_threshold = atoi(need(i));
         else if (a == "--multiview_filter") multiview_filter = true;
+        else if (a == "--multiview_fuse") multiview_fuse = true;
         else if (a == "--mv_neighbors") mv_neighbors = atoi(need(i));
         else if (a == "--mv_max_distance") mv_max_distance = atof(need(i));
         else if (a == "--mv_tolerance") mv_tolerance = atof(need(i));
@@ -715,6 +722,15 @@ int Pose::parseCmdArgs(int argc, char** argv)
         if (n_gpus > 1 || partitioned_merge) throw runtime_error("--use_segment_labels is not available with --gpus N > 1 / --partitioned_merge");
         if (reference_fanout) throw runtime_error("--use_segment_labels is not available with --reference_fanout");
         if (blur_kernel > 1) throw runtime_error("--use_segment_labels cannot be combined with --blur_kernel > 1 (cv::bilateralFilter rejects CV_64F)");
+    }
+    if (run3d_reconstruction && multiview_fuse) {
+        // the fusion sits where the filter does, and hands the accumulate call float64 images of its own
+        if (n_gpus > 1) throw runtime_error("--multiview_fuse is not available with --gpus N > 1");
+        if (partitioned_merge) throw runtime_error("--multiview_fuse is not available with --partitioned_merge");
+        if (reference_fanout) throw runtime_error("--multiview_fuse is not available with --reference_fanout");
+        if (use_segment_labels) throw runtime_error("--multiview_fuse is not available with --use_segment_labels (its images are CV_64F fits)");
+        if (blur_kernel > 1) throw runtime_error("--multiview_fuse is not available with --blur_kernel > 1 (the blur would run on the fused image)");
+        multiview_filter = false;  // (given together, the two flags mean fuse)
     }
     if (run3d_reconstruction && multiview_filter) {
         // the filter sits between the cycle's poses and the batched accumulate call: the paths without that call say so
@@ -1602,8 +1618,12 @@ void Pose::run_reconstruction()
                     cout << "Adding Point Cloud number/points: " << n_cloud << " of " << n_acc << " frames" << flush;
                 }
             }
-            // --multiview_filter: the frames that go into the cloud, with their final poses, vote on each other's pixels
-            if (multiview_filter && rc_orb == O3DR_OK && rc_fit == O3DR_OK && rc_chain == O3DR_OK && n_cloud > 0) {
+            // --multiview_filter / --multiview_fuse: the frames that go into the cloud, with their final poses, vote on each
+            // other's pixels; the fusion's float64 levels then go into the accumulate call in place of the 8-bit images
+            const uint8_t* acc_in = disp_in;
+            int64_t acc_esz = esz;
+            vector<double> fused;
+            if ((multiview_filter || multiview_fuse) && rc_orb == O3DR_OK && rc_fit == O3DR_OK && rc_chain == O3DR_OK && n_cloud > 0) {
                 const auto tm = clk::now();
                 o3dr_multiview_params mp;
                 o3dr_multiview_default_params(&mp);
@@ -1612,32 +1632,46 @@ void Pose::run_reconstruction()
                 mp.max_violations = mv_max_violations;
                 const int32_t nk = (int32_t)mv_neighbors;
                 vector<int32_t> nb((size_t)n_cloud * (size_t)(nk > 0 && nk <= O3DR_MULTIVIEW_MAX_NEIGHBORS ? nk : 0) + 1);
-                vector<uint8_t> kept(dsz * n_cloud);
+                vector<uint8_t> kept(multiview_fuse ? 0 : dsz * n_cloud);
                 vector<o3dr_multiview_info> mi(n_cloud);
+                vector<o3dr_multiview_fuse_info> fi(multiview_fuse ? n_cloud : 0);
+                if (multiview_fuse) fused.resize(dsz * n_cloud);
                 rc_chain = o3dr_nearby_frames(poses.data(), (int32_t)n_cloud, nk, mv_max_distance, nb.data());
-                if (rc_chain == O3DR_OK)
+                if (rc_chain == O3DR_OK && multiview_fuse)
+                    rc_chain = o3dr_multiview_fuse(c, disp.data(), (int64_t)dsz, cols, rows, cols, (int32_t)n_cloud, poses.data(), nb.data(), nk,
+                                                   &mp, fused.data(), nullptr, nullptr, nullptr, fi.data(), O3DR_MEM_HOST);
+                else if (rc_chain == O3DR_OK)
                     rc_chain = o3dr_multiview_filter(c, disp.data(), (int64_t)dsz, cols, rows, cols, (int32_t)n_cloud, poses.data(), nb.data(), nk,
                                                      &mp, kept.data(), nullptr, nullptr, mi.data(), O3DR_MEM_HOST);
-                if (rc_chain != O3DR_OK) why_chain = string("multiview_filter: ") + o3dr_last_error();
+                if (rc_chain != O3DR_OK) why_chain = string(multiview_fuse ? "multiview_fuse: " : "multiview_filter: ") + o3dr_last_error();
                 else {
-                    memcpy(disp.data(), kept.data(), kept.size());
-                    int64_t n_pairs = 0, n_valid = 0, n_kept = 0, n_nosup = 0, n_viol = 0;
+                    int64_t n_pairs = 0, n_valid = 0, n_kept = 0, n_nosup = 0, n_viol = 0, n_votes = 0, n_fused = 0;
                     for (size_t e = 0; e < (size_t)n_cloud * (size_t)nk; ++e) n_pairs += nb[e] >= 0;
+                    if (multiview_fuse) {
+                        for (size_t f = 0; f < n_cloud; ++f) mi[f] = fi[f].filter, n_votes += fi[f].n_votes, n_fused += fi[f].n_fused;
+                        acc_in = (const uint8_t*)fused.data();
+                        acc_esz = 8;
+                        disparity_f64 = true;  // (for the accumulate call alone: restored after it)
+                        push_params(c);
+                    } else {
+                        memcpy(disp.data(), kept.data(), kept.size());
+                    }
                     for (const o3dr_multiview_info& m : mi)
                         n_valid += m.n_valid, n_kept += m.n_kept, n_nosup += m.n_no_support, n_viol += m.n_violated;
-                    cout << "\nmultiview filter: " << n_cloud << " frames, " << n_pairs << " pairs, kept " << n_kept << " of " << n_valid
-                         << " pixels (" << n_nosup << " without support, " << n_viol << " violated), "
-                         << chrono::duration<double>(clk::now() - tm).count() << " sec" << flush;
+                    cout << "\nmultiview " << (multiview_fuse ? "fuse: " : "filter: ") << n_cloud << " frames, " << n_pairs << " pairs, kept "
+                         << n_kept << " of " << n_valid << " pixels (" << n_nosup << " without support, " << n_viol << " violated), ";
+                    if (multiview_fuse) cout << n_votes << " votes into " << n_fused << " pixels, ";
+                    cout << chrono::duration<double>(clk::now() - tm).count() << " sec" << flush;
                 }
             }
             const int rc_acc = rc_orb != O3DR_OK ? rc_orb : rc_fit != O3DR_OK ? rc_fit : rc_chain != O3DR_OK ? rc_chain : n_cloud == 0 ? O3DR_OK
-                                                 : o3dr_accumulate_frames_kp(c, disp_in, esz * (int64_t)dsz, esz * cols, bgr.data(), (int64_t)csz,
+                                                 : o3dr_accumulate_frames_kp(c, acc_in, acc_esz * (int64_t)dsz, acc_esz * cols, bgr.data(), (int64_t)csz,
                                                                              3 * (int64_t)cols, rows, cols, poses.data(), (int32_t)n_cloud,
                                                                              kp_xy.empty() ? nullptr : kp_xy.data(),
                                                                              kp_xy.empty() ? nullptr : kp_off.data(), O3DR_MEM_HOST);
             const string why_acc = rc_orb != O3DR_OK ? "orb_detect: " + why_orb : rc_fit != O3DR_OK ? "plane_fit_disparity: " + why_fit
                                    : rc_chain != O3DR_OK ? why_chain : (rc_acc != O3DR_OK ? o3dr_last_error() : "");
-            if (use_segment_labels) {
+            if (use_segment_labels || acc_in != disp_in) {
                 disparity_f64 = false;
                 push_params(c);
             }
