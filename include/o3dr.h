@@ -643,6 +643,79 @@ void o3dr_mesh_default_params(o3dr_mesh_params* p);
 int  o3dr_mesh_surface(o3dr_ctx* ctx, const o3dr_point* cloud, int64_t n, const o3dr_mesh_params* p, int32_t* tris,
                        int64_t tris_capacity, int64_t* n_tris, float* vertex_normals, o3dr_mesh_result* res, int32_t mem);
 
+/* ---- map raster: the merged map as images, one pixel per XY cell - the orthophoto (the cells' colours), the elevation
+ * raster (their heights) and a shaded relief.  The reference shows its map in a PCLVisualizer window only (SURVEY section 2
+ * row 15); the contract is this library's own.  Every value is an integer, a comparison, a copy or a correctly rounded
+ * fp64 operation in the stated order, no FMA: results are bit-identical across calls and across host and device memory.
+ *
+ * Input: n points, n < 2^31, every coordinate finite.  cell_size as for the mesh (finite and > 0, with (float)cell_size and
+ * 1.0f / (float)cell_size finite and > 0).
+ *   1. Cells: the mesh's rule, inv = 1.0f / (float)cell_size, cx = (int)floorf(x * inv), cy = (int)floorf(y * inv) in fp32.
+ *      The raster covers width x height cells from (cx0, cy0); element [r, c] of every output is cell (cx0 + c, cy0 + r),
+ *      rows ascending in cy.  o3dr_raster_extent returns the cloud's own cell box; any other box may be given (several maps
+ *      in one raster frame).  Points outside the box are counted in n_outside and ignored.  Limits: width, height >= 1,
+ *      cx0 + width - 1 and cy0 + height - 1 within int32, width * height <= 2^28.
+ *   2. One point per cell, by `select`: O3DR_RASTER_FIRST the lowest input index (the mesh's vertex rule); O3DR_RASTER_TOP
+ *      the greatest z by fp32 >, ties to the lowest index; O3DR_RASTER_BOTTOM the smallest z, ties to the lowest index.
+ *      -0.0f and 0.0f are equal.  The cell's other points are shadowed: counted, never used.  A cell with a point is
+ *      occupied.
+ *   3. Hole fill, fill_radius = R cells, 0 <= R <= 32: an empty cell takes the occupied cell with the smallest
+ *      dx*dx + dy*dy <= R*R, ties to the lowest (cy, cx).  Only the occupied cells of 2 are sources: a fill never feeds a
+ *      fill.  R = 0: no fill.
+ *   4. Outputs, [height, width] each, every pointer optional (NULL: not written): source int32, the input index that
+ *      supplies the cell (its own point or the filled one), -1 if none; distance2 int32, 0 for an occupied cell, the squared
+ *      cell distance for a filled one, -1 if none; height_map float32, the source point's z copied, NaN if none; color uint8
+ *      [.., 3], the source point's colour bytes blue green red (rgba & 255, >> 8, >> 16), 0 if none.
+ *   5. shade uint8 (written iff use_light): l' = l / sqrt((lx*lx + ly*ly) + lz*lz), fp64 on the host, the length finite and
+ *      > 0.  Per cell with a source, on the heights after the fill: hR = the height of the cell to the right if that cell is
+ *      inside the raster and has a source, else the cell's own; hL, hU (row r + 1), hD (row r - 1) likewise; kx = the number
+ *      of present horizontal neighbours, ky of vertical ones; gx = kx == 0 ? 0.0 : ((double)hR - (double)hL) /
+ *      ((double)kx * cell_size), gy likewise from hU - hD; s = (((-gx) * l'x + (-gy) * l'y) + l'z) /
+ *      sqrt((gx*gx + gy*gy) + 1.0); shade = s > 0 ? min(255, 1 + (int)floor(s * 254.0 + 0.5)) : 1 (also for a NaN s);
+ *      0 where there is no source.
+ *   6. o3dr_raster_result: the box, n_inside + n_outside = n, n_occupied + n_shadowed = n_inside, n_occupied + n_filled +
+ *      n_empty = width * height; z_min / z_max over the occupied cells' points (-0.0f taken as 0.0f), NaN when no cell is
+ *      occupied.
+ * Errors, O3DR_ERR_INVALID_ARG, in this order: a bad parameter (cell_size, select, fill_radius, the light, a box with a
+ * side < 1 or a corner outside int32); a non-finite coordinate; a cell index outside int32; a box of more than 2^28 cells
+ * (o3dr_raster_extent: the cloud's own).  All are found before any raster work and before anything of the raster's size is
+ * allocated.  On an error the host outputs and the result are zeroed.  o3dr_raster_extent needs n > 0;
+ * o3dr_rasterize_map takes n == 0 (every cell empty).  Both synchronise, and reuse the operators' scratch: cloud_big and
+ * the sort workspace are left alone. */
+#define O3DR_RASTER_FIRST 0
+#define O3DR_RASTER_TOP 1
+#define O3DR_RASTER_BOTTOM 2
+#define O3DR_RASTER_MAX_FILL_RADIUS 32
+#define O3DR_RASTER_MAX_CELLS (1 << 28)
+typedef struct o3dr_raster_params {
+    double cell_size;     /* > 0, finite; no usable default (0 is rejected): the map's voxel_size */
+    int32_t select;       /* O3DR_RASTER_FIRST */
+    int32_t fill_radius;  /* 0 */
+    int32_t cx0, cy0, width, height; /* the box; no default (0 x 0 is rejected): o3dr_raster_extent's, or the caller's own */
+    int32_t use_light;    /* 0: no shaded relief */
+    int32_t reserved;
+    double light[3];      /* the direction towards the light (-1, 1, 1: from the north-west, 35 degrees up) */
+} o3dr_raster_params;
+typedef struct o3dr_raster_outputs {
+    float* height_map;    /* width * height */
+    uint8_t* color;       /* 3 * width * height */
+    uint8_t* shade;       /* width * height; needs use_light */
+    int32_t* source;      /* width * height */
+    int32_t* distance2;   /* width * height */
+} o3dr_raster_outputs;
+typedef struct o3dr_raster_result {
+    int32_t cx0, cy0, width, height;
+    int64_t n_inside, n_outside;    /* points inside / outside the box */
+    int64_t n_occupied, n_shadowed; /* cells with a point; points inside the box that their cell did not choose */
+    int64_t n_filled, n_empty;      /* empty cells that took a neighbour; cells without a source */
+    float z_min, z_max;             /* over the occupied cells' points; NaN when there is none */
+} o3dr_raster_result;
+void o3dr_raster_default_params(o3dr_raster_params* p);
+int  o3dr_raster_extent(o3dr_ctx* ctx, const o3dr_point* cloud, int64_t n, double cell_size, int32_t* cx0, int32_t* cy0,
+                        int32_t* width, int32_t* height, int32_t mem);
+int  o3dr_rasterize_map(o3dr_ctx* ctx, const o3dr_point* cloud, int64_t n, const o3dr_raster_params* p,
+                        const o3dr_raster_outputs* out, o3dr_raster_result* res, int32_t mem);
+
 /* ---- plane-fitted disparity per segment label: the reference's --use_segment_labels front end (SURVEY section 2 row 13:
  * "per-segment least-squares plane over disparity -> CV_64F disparity").  The reference's source for it is not available
  * to this build, so the contract below is this library's own (INTEGRATION.md lists the differences); every input is an

@@ -91,6 +91,27 @@ class MeshResultStruct(C.Structure):
                 ("n_rejected_orientation", C.c_int64), ("n_rejected_length", C.c_int64)]
 
 
+class RasterParamsStruct(C.Structure):
+    _fields_ = [("cell_size", C.c_double), ("select", C.c_int32), ("fill_radius", C.c_int32), ("cx0", C.c_int32), ("cy0", C.c_int32),
+                ("width", C.c_int32), ("height", C.c_int32), ("use_light", C.c_int32), ("reserved", C.c_int32),
+                ("light", C.c_double * 3)]
+
+
+class RasterOutputsStruct(C.Structure):
+    _fields_ = [("height_map", C.c_void_p), ("color", C.c_void_p), ("shade", C.c_void_p), ("source", C.c_void_p),
+                ("distance2", C.c_void_p)]
+
+
+class RasterResultStruct(C.Structure):
+    _fields_ = [("cx0", C.c_int32), ("cy0", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("n_inside", C.c_int64),
+                ("n_outside", C.c_int64), ("n_occupied", C.c_int64), ("n_shadowed", C.c_int64), ("n_filled", C.c_int64),
+                ("n_empty", C.c_int64), ("z_min", C.c_float), ("z_max", C.c_float)]
+
+
+RASTER_SELECT = {"first": 0, "top": 1, "bottom": 2}
+RASTER_MAX_FILL_RADIUS, RASTER_MAX_CELLS = 32, 1 << 28
+
+
 class PlaneDispParamsStruct(C.Structure):
     _fields_ = [("min_disparity", C.c_double), ("min_pixels", C.c_int32), ("max_mse", C.c_double), ("fill", C.c_int32)]
 
@@ -314,6 +335,10 @@ SYMBOLS = [
     ("o3dr_mesh_default_params", None, [C.POINTER(MeshParamsStruct)]),
     ("o3dr_mesh_surface", C.c_int, [_vp, _vp, _i64, C.POINTER(MeshParamsStruct), _vp, _i64, _pi64, _vp,
                                     C.POINTER(MeshResultStruct), _i32]),
+    ("o3dr_raster_default_params", None, [C.POINTER(RasterParamsStruct)]),
+    ("o3dr_raster_extent", C.c_int, [_vp, _vp, _i64, C.c_double, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _i32]),
+    ("o3dr_rasterize_map", C.c_int, [_vp, _vp, _i64, C.POINTER(RasterParamsStruct), C.POINTER(RasterOutputsStruct),
+                                     C.POINTER(RasterResultStruct), _i32]),
     ("o3dr_plane_disp_default_params", None, [C.POINTER(PlaneDispParamsStruct)]),
     ("o3dr_plane_fit_disparity", C.c_int, [_vp, _vp, _i64, _i64, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32,
                                            C.POINTER(PlaneDispParamsStruct), _vp, _vp, _pu32, _i32]),

@@ -74,6 +74,24 @@ class MeshResult:
 
 
 @dataclass
+class RasterInfo:
+    """o3dr_rasterize_map's record: the raster's box in cells, the points inside and outside it, the occupied cells and the
+    points their cells did not choose, the filled and the empty cells, and the occupied cells' z range (NaN: none)."""
+    cx0: int
+    cy0: int
+    width: int
+    height: int
+    n_inside: int
+    n_outside: int
+    n_occupied: int
+    n_shadowed: int
+    n_filled: int
+    n_empty: int
+    z_min: float
+    z_max: float
+
+
+@dataclass
 class RigidResult:
     """o3dr_estimate_rigid_transform's result for one segment: T (float64 4x4, src -> tgt), the rms residual at T over the
     used pairs, their number and the status (RIGID_OK, RIGID_TOO_FEW, RIGID_DEGENERATE; T is the identity unless OK)."""
@@ -1332,6 +1350,66 @@ class Context:
             ret += (MeshResult(int(res.n_vertices), int(res.n_shadowed), int(res.n_triangles), int(res.n_quads_full),
                                int(res.n_rejected_orientation), int(res.n_rejected_length)),)
         return ret[0] if len(ret) == 1 else ret
+
+    # -- map raster: orthophoto, elevation raster, shaded relief (this build's own) ---------------
+    def rasterExtent(self, pts, cell_size):
+        """The cloud's own cell box (cx0, cy0, width, height) at cell_size: what rasterizeMap(bounds=None) covers."""
+        pts, n = self._cloud(pts)
+        p_in, mem, _k = _ptr(pts)
+        if mem == L.MEM_DEVICE:
+            self._order_after_torch()
+        box = [C.c_int32(0) for _ in range(4)]
+        L.check(self._lib.o3dr_raster_extent(self._h, p_in, n, float(cell_size), *[C.byref(b) for b in box], mem))
+        return tuple(int(b.value) for b in box)
+
+    def rasterizeMap(self, pts, cell_size, bounds=None, select="first", fill_radius=0, light=None, return_source=False,
+                     return_distance=False, return_info=False):
+        """The map as [height, width] images, one pixel per XY cell of cell_size, rows ascending in cy (contract:
+        include/o3dr.h "map raster", DESIGN.md "Map raster").  bounds = (cx0, cy0, width, height) in cells, None: the
+        cloud's own box (rasterExtent).  select "first" | "top" | "bottom" picks a cell's point, fill_radius (0..32 cells)
+        fills empty cells from the nearest occupied one, light = (lx, ly, lz) adds the shaded relief.  numpy POINT arrays
+        give numpy arrays, torch [N,4] 4-byte CUDA tensors such as finalize(device=...) give CUDA tensors.
+        -> (height_map float32, color uint8 [.., 3] B G R[, shade uint8][, source int32][, distance2 int32][, RasterInfo])"""
+        pts, n = self._cloud(pts)
+        p_in, mem, _k = _ptr(pts)
+        if select not in L.RASTER_SELECT:
+            raise L.O3drError(L.ERR_INVALID_ARG, "select must be 'first', 'top' or 'bottom'")
+        cx0, cy0, W, H = (int(v) for v in (self.rasterExtent(pts, cell_size) if bounds is None else bounds))
+        prm = L.RasterParamsStruct()
+        self._lib.o3dr_raster_default_params(C.byref(prm))
+        prm.cell_size, prm.select, prm.fill_radius = float(cell_size), L.RASTER_SELECT[select], int(fill_radius)
+        prm.cx0, prm.cy0, prm.width, prm.height = cx0, cy0, W, H
+        if light is not None:
+            prm.use_light = 1
+            prm.light[:] = [float(v) for v in light]
+        ok = 1 <= W and 1 <= H and W * H <= L.RASTER_MAX_CELLS  # (else the call fails before it writes anything)
+        shape = (H, W) if ok else (1, 1)
+        want = [("height_map", np.float32, ()), ("color", np.uint8, (3,))]
+        want += [("shade", np.uint8, ())] if light is not None else []
+        want += [("source", np.int32, ())] if return_source else []
+        want += [("distance2", np.int32, ())] if return_distance else []
+        outs = L.RasterOutputsStruct()
+        arrays = []
+        if mem == L.MEM_DEVICE:
+            import torch
+            for name, dt, tail in want:
+                t = torch.empty(shape + tail, dtype=getattr(torch, np.dtype(dt).name), device=pts.device)
+                setattr(outs, name, t.data_ptr())
+                arrays.append(t)
+            self._order_after_torch()
+        else:
+            for name, dt, tail in want:
+                t = np.empty(shape + tail, dt)
+                setattr(outs, name, t.ctypes.data)
+                arrays.append(t)
+        res = L.RasterResultStruct()
+        L.check(self._lib.o3dr_rasterize_map(self._h, p_in if n else None, n, C.byref(prm), C.byref(outs), C.byref(res), mem))
+        ret = tuple(arrays)
+        if return_info:
+            ret += (RasterInfo(int(res.cx0), int(res.cy0), int(res.width), int(res.height), int(res.n_inside), int(res.n_outside),
+                               int(res.n_occupied), int(res.n_shadowed), int(res.n_filled), int(res.n_empty), float(res.z_min),
+                               float(res.z_max)),)
+        return ret
 
     def voxelGrid(self, pts, leaf, min_points=0, z_offset=0.0, return_status=False):
         """pcl::VoxelGrid<PointXYZRGB> as the reference configures it (pose_functions.cpp:1689-1700)."""

@@ -138,11 +138,12 @@ struct o3dr_ctx {
     // Scratch of the operators after that (MLS, plane, mesh, match, keypoints, rigid fit, the image-stack operators), shared:
     // nothing in it outlives a call, and within one call every block is laid out by one carve().  OP_IN: staged host inputs
     // (descriptor pool; src / tgt / mask; image stacks).  OP_WORK: the arrays sized from the arguments (plane: points in tile
-    // order + run heads; mesh: run heads + vertex tables; match: pair table + chunk partials; rigid: segment table + sums;
-    // ORB, stereo, the disparity and multi-view filters, segmentation: a group of frames' arrays and the per-frame counters;
-    // rectification: the staged host map).  OP_LATE: the arrays sized from a count read back mid-call (plane: tile tables).
+    // order + run heads; mesh: run heads + vertex tables; raster: the cells' words + column offsets; match: pair table +
+    // chunk partials; rigid: segment table + sums; ORB, stereo, the disparity and multi-view filters, segmentation: a group
+    // of frames' arrays and the per-frame counters; rectification: the staged host map).  OP_LATE: the arrays sized from a
+    // count read back mid-call (plane: tile tables).
     // OP_OUT: the staged outputs of a host call.  OP_FLAGS: 256 bytes of flags / ranges / counters (MlsFlags, PlaneFlags,
-    // MeshFlags).
+    // MeshFlags, RasterFlags).
     enum { OP_IN, OP_WORK, OP_LATE, OP_OUT, OP_FLAGS, OP_BUFS };
     DevBuf op[OP_BUFS];
     DevBuf orb_pat;  // o3dr_orb_detect: the steered table
@@ -685,7 +686,7 @@ struct Outputs {
         void* dev;
     };
     int mem, n = 0;
-    Item item[4];
+    Item item[5];
     template <class T>
     void add(T* user, int64_t capacity)
     {
@@ -3075,6 +3076,10 @@ struct MeshFlags {
     alignas(64) uint32_t cnt[2];       // V, T
     alignas(64) uint32_t counters[3];  // full quads, rejected by orientation, rejected by length
 };
+struct RasterFlags {
+    alignas(64) CellFlags cell;
+    alignas(64) uint32_t counters[12];  // RasterArgs::counters
+};
 // The index box of a read-back range: its corner and widths -> o, the width of the largest dense cell id -> *nbits.
 // Fails, with the operator's texts, if an index left int32 or the box holds more than `limit` cells.
 static int cell_box(const CellFlags& h, uint64_t limit, const char* off_int32_text, const char* limit_text, CellOrder* o, int* nbits)
@@ -3605,6 +3610,179 @@ extern "C" int o3dr_mesh_surface(o3dr_ctx* c, const o3dr_point* cloud, int64_t n
     const int rc = entered(c, [&] { return mesh_surface(c, cloud, n, p, tris, tris_capacity, n_tris, vertex_normals, outs, res, mem); });
     if (rc != O3DR_OK && rc != O3DR_ERR_CAPACITY) {  // host outputs zeroed on error
         if (n_tris) *n_tris = 0;
+        outs.zero();
+    }
+    return rc;
+}
+
+// -------------------------------------------------------------------------------------------------
+// map raster: orthophoto, elevation raster, shaded relief (kernels/raster.inc; DESIGN.md "Map raster")
+// -------------------------------------------------------------------------------------------------
+extern "C" void o3dr_raster_default_params(o3dr_raster_params* p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof *p);  // cell_size and the box: no usable default
+    p->select = O3DR_RASTER_FIRST;
+    p->light[0] = -1.0, p->light[1] = 1.0, p->light[2] = 1.0;
+}
+
+static int raster_cell_size(double cs, float* inv)
+{
+    const float csf = (float)cs;
+    *inv = 1.0f / csf;
+    if (!(std::isfinite(cs) && cs > 0.0 && std::isfinite(csf) && csf > 0.f && std::isfinite(*inv) && *inv > 0.f))
+        return fail(O3DR_ERR_INVALID_ARG, "cell_size must be finite and > 0 (and usable in fp32)");
+    return O3DR_OK;
+}
+// The cloud staged, every coordinate checked for being finite and every cell index for fitting int32: one
+// synchronisation, the cloud's cell range in *h.  The range pass's partials are all of OP_WORK until the box is known.
+static int raster_cloud(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, int mem, RasterArgs& a, RasterFlags* f, CellFlags* h)
+{
+    CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) { w.take(a.part, (size_t)cell_range_parts(n) * kPartWords); }));
+    CHK(cloud_stage_finite(c, cloud, n, mem, &f->cell.bad, &h->bad, sizeof *h, &a.cloud, [&]() -> int {
+        launch_cell_range(&c->prof, c->stream, a, a.part, f->cell.range);
+        return O3DR_OK;
+    }));
+    if (h->off_int32[0]) return fail(O3DR_ERR_INVALID_ARG, "a cell index does not fit in int32 (cell_size too small)");
+    return O3DR_OK;
+}
+constexpr const char* kRasterTooLarge = "the raster's box holds more than 2^28 cells";
+
+static int raster_extent(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, double cell_size, int32_t* box[4], int32_t mem)
+{
+    CHK(nn_check_cloud(n, cloud, kMeshCloudMax));
+    if (!box[0] || !box[1] || !box[2] || !box[3]) return fail(O3DR_ERR_INVALID_ARG, "cx0 / cy0 / width / height is NULL");
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    RasterArgs a;
+    memset(&a, 0, sizeof a);
+    CHK(raster_cell_size(cell_size, &a.inv));
+    if (n == 0) return fail(O3DR_ERR_INVALID_ARG, "an empty cloud has no cell box");
+    c->place_ub = -1;
+    a.n = (uint32_t)n;
+    RasterFlags* f;
+    CHK(op_flags(c, &f));
+    CellFlags h;
+    CHK(raster_cloud(c, cloud, n, mem, a, f, &h));
+    CellOrder o;
+    int nbits;
+    CHK(cell_box(h, (uint64_t)O3DR_RASTER_MAX_CELLS, "", kRasterTooLarge, &o, &nbits));
+    *box[0] = o.x0, *box[1] = o.y0, *box[2] = (int32_t)o.wx, *box[3] = (int32_t)o.wy;
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_raster_extent(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, double cell_size, int32_t* cx0, int32_t* cy0,
+                                  int32_t* width, int32_t* height, int32_t mem)
+{
+    int32_t* box[4] = {cx0, cy0, width, height};
+    for (int32_t* b : box)
+        if (b) *b = 0;
+    const int rc = entered(c, [&] { return raster_extent(c, cloud, n, cell_size, box, mem); });
+    if (rc != O3DR_OK)
+        for (int32_t* b : box)
+            if (b) *b = 0;
+    return rc;
+}
+
+// width * height of a box the outputs can be sized by before anything else is validated: 0 for a box outside the limits
+static int64_t raster_cells(const o3dr_raster_params* p)
+{
+    if (!p || p->width < 1 || p->height < 1) return 0;
+    const int64_t cells = (int64_t)p->width * p->height;
+    return cells <= (int64_t)O3DR_RASTER_MAX_CELLS ? cells : 0;
+}
+
+static int rasterize_map(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const o3dr_raster_params* p, const o3dr_raster_outputs* out,
+                         Outputs& outs, o3dr_raster_result* res, int32_t mem)
+{
+    CHK(nn_check_cloud(n, cloud, kMeshCloudMax));
+    if (!p) return fail(O3DR_ERR_INVALID_ARG, "params is NULL");
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    RasterArgs a;
+    memset(&a, 0, sizeof a);
+    CHK(raster_cell_size(p->cell_size, &a.inv));
+    if (p->select != O3DR_RASTER_FIRST && p->select != O3DR_RASTER_TOP && p->select != O3DR_RASTER_BOTTOM)
+        return fail(O3DR_ERR_INVALID_ARG, "select must be O3DR_RASTER_FIRST, _TOP or _BOTTOM");
+    if (p->fill_radius < 0 || p->fill_radius > O3DR_RASTER_MAX_FILL_RADIUS) return fail(O3DR_ERR_INVALID_ARG, "fill_radius must be in 0..32");
+    if (p->use_light) {
+        const double* l = p->light;
+        const double ln = std::sqrt((l[0] * l[0] + l[1] * l[1]) + l[2] * l[2]);
+        if (!(std::isfinite(ln) && ln > 0.0)) return fail(O3DR_ERR_INVALID_ARG, "the light vector must be finite and not zero");
+        for (int k = 0; k < 3; ++k) a.light[k] = l[k] / ln;
+    } else if (out && out->shade) {
+        return fail(O3DR_ERR_INVALID_ARG, "the shade output needs use_light");
+    }
+    if (p->width < 1 || p->height < 1) return fail(O3DR_ERR_INVALID_ARG, "the raster's box needs width, height >= 1");
+    if ((int64_t)p->cx0 + p->width - 1 > INT32_MAX || (int64_t)p->cy0 + p->height - 1 > INT32_MAX)
+        return fail(O3DR_ERR_INVALID_ARG, "the raster's box leaves int32");
+    c->place_ub = -1;
+    a.n = (uint32_t)n;
+    a.cx0 = p->cx0, a.cy0 = p->cy0, a.width = p->width, a.height = p->height;
+    a.select = p->select, a.R = p->fill_radius;
+    a.cell_size = p->cell_size;
+    RasterFlags* f;
+    CHK(op_flags(c, &f));
+    if (n > 0) {
+        CellFlags h;
+        CHK(raster_cloud(c, cloud, n, mem, a, f, &h));
+    }
+    const int64_t cells = (int64_t)p->width * p->height;
+    if (cells > (int64_t)O3DR_RASTER_MAX_CELLS) return fail(O3DR_ERR_INVALID_ARG, kRasterTooLarge);
+    const int64_t tiles = raster_tiles(p->width, p->height), parts = std::max(tiles, raster_winner_parts(n));
+    float* height_tmp = nullptr;  // the shade reads the filled heights: scratch when the caller does not ask for them
+    const bool want_shade = p->use_light && out && out->shade;
+    CHK(outs.stage(c));
+    CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
+        w.take(a.part, (size_t)parts * kPartWords);
+        w.take(a.win, (size_t)cells);
+        if (a.R > 0) w.take(a.col, (size_t)cells);
+        if (want_shade && !out->height_map) w.take(height_tmp, (size_t)cells);
+    }));
+    a.counters = f->counters;
+    if (out) {
+        a.height_map = outs.dev(out->height_map), a.color = outs.dev(out->color), a.source = outs.dev(out->source);
+        a.distance2 = outs.dev(out->distance2);
+        a.shade = want_shade ? outs.dev(out->shade) : nullptr;
+    }
+    if (!a.height_map) a.height_map = height_tmp;
+    launch_raster(&c->prof, c->stream, a);
+    HIPCHK(hipGetLastError());
+    uint32_t cnt[12];
+    HIPCHK(hipMemcpyAsync(cnt, f->counters, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+    CHK(outs.copy_back(c));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (res) {
+        res->cx0 = p->cx0, res->cy0 = p->cy0, res->width = p->width, res->height = p->height;
+        res->n_inside = cnt[0], res->n_outside = cnt[1];
+        res->n_occupied = cnt[4], res->n_shadowed = (int64_t)cnt[0] - (int64_t)cnt[4];
+        res->n_filled = cnt[5], res->n_empty = cnt[6];
+        const auto ordered = [](uint32_t u) {  // (ordered_f32 of kernels/util.inc)
+            u ^= ((u >> 31) - 1u) | 0x80000000u;
+            float z;
+            memcpy(&z, &u, sizeof z);
+            return z;
+        };
+        res->z_min = cnt[4] ? ordered(cnt[8]) : NAN;
+        res->z_max = cnt[4] ? ordered(cnt[9]) : NAN;
+    }
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_rasterize_map(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const o3dr_raster_params* p,
+                                  const o3dr_raster_outputs* out, o3dr_raster_result* res, int32_t mem)
+{
+    if (res) memset(res, 0, sizeof *res);
+    Outputs outs{mem};
+    const int64_t cells = raster_cells(p);
+    if (out) {
+        outs.add(out->height_map, cells);
+        outs.add(out->color, 3 * cells);
+        outs.add(out->shade, cells);
+        outs.add(out->source, cells);
+        outs.add(out->distance2, cells);
+    }
+    const int rc = entered(c, [&] { return rasterize_map(c, cloud, n, p, out, outs, res, mem); });
+    if (rc != O3DR_OK) {  // host outputs zeroed on error
+        if (res) memset(res, 0, sizeof *res);
         outs.zero();
     }
     return rc;

@@ -526,6 +526,34 @@ struct MeshArgs {
 // each if set.
 void launch_mesh_count(Profiler* pf, hipStream_t s, Workspace& ws, const MeshArgs& a, uint32_t* n_tris_dev);
 void launch_mesh_emit(Profiler* pf, hipStream_t s, const MeshArgs& a);
+// map raster (kernels/raster.inc; the fields are filled by o3dr_rasterize_map step by step; o3dr_raster_extent uses
+// cloud, n, inv alone, for launch_cell_range)
+struct RasterArgs {
+    const o3dr_point* cloud;      // the cloud in input order
+    uint32_t n;
+    float inv;                    // 1.0f / (float)cell_size
+    int32_t cx0, cy0, width, height;
+    int32_t select, R;            // O3DR_RASTER_*, the fill radius in cells
+    double cell_size, light[3];   // light: normalised (read when shade is set)
+    unsigned long long* win;      // width * height: the chosen point's (z key, input index), all ones = empty
+    int8_t* col;                  // width * height (R > 0): the offset in cy of the column's nearest occupied cell, kRasterNone = none
+    uint32_t* part;               // kPartWords words per workgroup: raster_winner_parts(n) of the winner pass, then one per tile
+    uint32_t* counters;           // 12 words: n_inside n_outside - - | n_occupied n_filled n_empty - | z_min z_max (ordered) - -
+    float* height_map;            // the outputs (nullptr: not asked for; height_map is scratch when only the shade needs it)
+    uint8_t* color;
+    uint8_t* shade;
+    int32_t* source;
+    int32_t* distance2;
+};
+constexpr int kRasterTileW = 64, kRasterTileH = 4;  // cells per workgroup of the row pass
+inline int64_t raster_tiles(int64_t width, int64_t height)
+{
+    return ((width + kRasterTileW - 1) / kRasterTileW) * ((height + kRasterTileH - 1) / kRasterTileH);
+}
+inline int64_t raster_winner_parts(int64_t n) { return cell_range_parts(n); }
+// launch_raster: a.win set to empty, the winner pass, the column pass (R > 0), the row pass with the outputs and the shade
+// stencil; the counters folded into a.counters
+void launch_raster(Profiler* pf, hipStream_t s, const RasterArgs& a);
 // plane-fitted disparity per segment label (kernels/plane_disparity.inc).  `table`: kPdSums 64-bit sums per (frame, label) -
 // n Sx Sy Sxx Sxy Syy Sd Sxd Syd Sdd and the pixel count -, zeroed here; thr: d participates iff (int)d > thr; flag: a
 // device word, bit 0 set when a label >= n_labels was seen.  launch_plane_disp runs the three steps for `frames` frames:

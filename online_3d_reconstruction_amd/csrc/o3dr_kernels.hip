@@ -32,6 +32,7 @@
 //   cell_order   the dense XY cell order of a cloud: index box, keys, run heads (plane tiles, mesh cells)
 //   plane        RANSAC plane segmentation per XY tile
 //   mesh         height-field surface mesh over the XY cells
+//   raster       the merged map as images: one point per XY cell, separable hole fill, the output images, shaded relief
 //   match        Hamming 2-NN descriptor matching, index-aligned 3-D keypoints, the batched rigid fit
 //   orb          ORB features: grey pyramid, FAST score + box sums, candidates, exact selection, steered BRIEF
 //   stereo       stereo disparity: grey + census, semi-global aggregation (one wave per scan line), winner + left-right check
@@ -65,6 +66,7 @@ namespace o3dr {
 #include "kernels/cell_order.inc"
 #include "kernels/plane.inc"
 #include "kernels/mesh.inc"
+#include "kernels/raster.inc"
 #include "kernels/match.inc"
 #include "kernels/plane_disparity.inc"
 #include "kernels/orb.inc"
@@ -1121,6 +1123,7 @@ void launch_cell_order(Profiler* pf, hipStream_t s, Workspace& ws, Args& a, int 
 }
 template void launch_cell_range<PlaneArgs>(Profiler*, hipStream_t, const PlaneArgs&, uint32_t*, uint32_t*);
 template void launch_cell_range<MeshArgs>(Profiler*, hipStream_t, const MeshArgs&, uint32_t*, uint32_t*);
+template void launch_cell_range<RasterArgs>(Profiler*, hipStream_t, const RasterArgs&, uint32_t*, uint32_t*);
 template void launch_cell_order<PlaneArgs>(Profiler*, hipStream_t, Workspace&, PlaneArgs&, int, uint32_t*, uint32_t*);
 template void launch_cell_order<MeshArgs>(Profiler*, hipStream_t, Workspace&, MeshArgs&, int, uint32_t*, uint32_t*);
 
@@ -1244,6 +1247,24 @@ void launch_mesh_emit(Profiler* pf, hipStream_t s, const MeshArgs& a)
     const int64_t n = a.n;
     if (a.tris) k_mesh_emit<<<cdiv64(n, kMeshThreads), kMeshThreads, 0, s>>>(a);
     if (a.normals) k_mesh_normals<<<cdiv64(n, kMeshThreads), kMeshThreads, 0, s>>>(a);
+}
+
+// map raster (kernels/raster.inc)
+void launch_raster(Profiler* pf, hipStream_t s, const RasterArgs& a)
+{
+    ProfScope ps(pf, O3DR_K_OTHER, s);
+    const int64_t cells = (int64_t)a.width * a.height;
+    (void)hipMemsetAsync(a.win, 0xff, (size_t)cells * sizeof(unsigned long long), s);
+    const int gw = (int)raster_winner_parts(a.n);
+    if (gw > 0) k_raster_winner<<<gw, kRasterThreads, 0, s>>>(a);
+    k_fold4_u32<<<1, kFoldThreads, 0, s>>>(a.part, gw, 0, 2, 2, 2, 2, a.counters);
+    const int gc = cdiv64(cells, kRasterThreads);
+    if (a.R > 0) k_raster_fill_col<<<gc, kRasterThreads, 0, s>>>(a);
+    const int gt = (int)raster_tiles(a.width, a.height);
+    k_raster_resolve<<<gt, kRasterThreads, 0, s>>>(a);
+    k_fold4_u32<<<1, kFoldThreads, 0, s>>>(a.part, gt, 0, 2, 2, 2, 2, a.counters + 4);
+    k_fold4_u32<<<1, kFoldThreads, 0, s>>>(a.part, gt, 4, 0, 1, 2, 2, a.counters + 8);
+    if (a.shade) k_raster_shade<<<gc, kRasterThreads, 0, s>>>(a);
 }
 
 }  // namespace o3dr

@@ -9,7 +9,8 @@
 // recorded MAVLink poses (the reference's --only_MAVLink mode, pose_functions.cpp:232-236), with --feature_poses every
 // frame's pose comes from o3dr_pose_chain (the reference's default mode, pose.cpp:213-235).  The --align_point_cloud tool (ICP on two PLYs) runs on o3dr_icp_align, the
 // --smooth_surface tool (MLS on one PLY) on o3dr_mls_smooth, the --segment_cloud_only tool (RANSAC planes per XY tile on
-// one PLY) on o3dr_segment_plane, the --mesh_surface tool (a height-field triangulation of one PLY) on o3dr_mesh_surface.
+// one PLY) on o3dr_segment_plane, the --mesh_surface tool (a height-field triangulation of one PLY) on o3dr_mesh_surface,
+// the --orthophoto tool (orthophoto, elevation raster and shaded relief of one PLY) on o3dr_rasterize_map.
 #pragma once
 #include <array>
 #include <cmath>
@@ -128,6 +129,13 @@ public:
     int sac_optimize = 1;            // --sac_optimize
     bool mesh_surface = false;       // --mesh_surface file.ply (pose.cpp:27-112, GP3): o3dr_mesh_surface
     bool mesh_normals = false;       // --mesh_normals: nx ny nz per vertex
+    bool orthophoto = false;         // --orthophoto file.ply: o3dr_rasterize_map of one PLY -> ortho_ / height_ / shade_<file>.png
+    std::string orthophoto_out;      // --orthophoto_out prefix (reconstruction run): the same three images of the final merged
+                                     // cloud, as <prefix>ortho.png, <prefix>height.png and, with --ortho_light, <prefix>shade.png
+    std::string ortho_select = "first";  // --ortho_select first|top|bottom, --ortho_fill_radius r (cells, 0..32), --ortho_light lx ly lz;
+    int ortho_fill_radius = 0;           // parsed and ignored without --orthophoto / --orthophoto_out
+    bool ortho_light_set = false;
+    double ortho_light[3] = {0.0, 0.0, 0.0};
     int device_id = 0;
     int n_gpus = 1;                 // --gpus N: frames sharded over devices device_id .. device_id+N-1, one host thread and
                                     // one context each, merged through o3dr_merge_partitioned (RCCL)
@@ -228,6 +236,11 @@ private:
     void run_smooth_surface();                      // --smooth_surface
     void run_segment_cloud();                       // --segment_cloud_only
     void run_mesh_surface();                        // --mesh_surface
+    void run_orthophoto();                          // --orthophoto
+    // the map's rasters of a host cloud (o3dr_raster_extent, o3dr_rasterize_map with the --ortho_* flags) as PNGs, rows in
+    // descending cy (north up); shade_path is written with --ortho_light only.  Prints the box, the counts and the call time.
+    void write_map_rasters(o3dr_ctx* c, const PointCloud& cloud, const std::string& ortho_path, const std::string& height_path,
+                           const std::string& shade_path);
     void run_find_features();                       // --find_features
     void run_stereo_disparity();                    // --stereo_disparity
     void compute_gpu_disparities();                 // --gpu_disparity: fills every raw frame's disparity_image

@@ -477,6 +477,16 @@ void Pose::printUsage()
             "                     the occupied XY cells of size m, edges up to L: writes every point, in input order, and the\n"
             "                     triangles as mesh_<file> next to it - that file name is this build's own; --search_radius is\n"
             "                     required here; --mesh_normals adds nx ny nz per vertex)\n"
+            "./pose --orthophoto file.ply [--voxel_size m] [--ortho_select first|top|bottom] [--ortho_fill_radius r] [--ortho_light lx ly lz]\n"
+            "                     (the map as images, one pixel per XY cell of size m, north up: the colours as ortho_<file>.png\n"
+            "                     (8-bit B G R), the heights as height_<file>.png (16-bit grey, 0 = no data, else 1 + (z - z_min) / step)\n"
+            "                     and, with --ortho_light, the shaded relief as shade_<file>.png, next to the source; a cell shows\n"
+            "                     its first, highest or lowest point, an empty cell the nearest occupied one within r cells (0..32,\n"
+            "                     default 0); prints the box, the counts, z_min, step and the call time - the flags and the file\n"
+            "                     names are this build's own)\n"
+            "       [--orthophoto_out prefix]  (reconstruction run: the same images of the final merged cloud, after cloud.ply, as\n"
+            "                     <prefix>ortho.png, <prefix>height.png and <prefix>shade.png; not available with --gpus N > 1,\n"
+            "                     --partitioned_merge, --reference_fanout; elsewhere the --ortho_* flags are parsed and ignored)\n"
             "./pose --find_features image.png [--orb_n_features n] [--orb_levels n] [--orb_scale s] [--orb_fast_threshold t]\n"
             "                     (ORB keypoints of one image: prints the count per level and writes one \"x y\" per line as\n"
             "                     <image>.keypoints.txt, the --keypoints_dir format - the flags and the file name are this build's own)\n"
@@ -595,6 +605,21 @@ int Pose::parseCmdArgs(int argc, char** argv)
             read_PLY_filename0 = argv[++i];
         }
         else if (a == "--mesh_normals") mesh_normals = true;
+        else if (a == "--orthophoto") {
+            if (i + 1 >= argc || string(argv[i + 1]).rfind("--", 0) == 0)
+                throw runtime_error("missing argument: --orthophoto needs file.ply");
+            orthophoto = true;
+            run3d_reconstruction = false;
+            read_PLY_filename0 = argv[++i];
+        }
+        else if (a == "--orthophoto_out") orthophoto_out = need(i);
+        else if (a == "--ortho_select") ortho_select = need(i);
+        else if (a == "--ortho_fill_radius") ortho_fill_radius = atoi(need(i));
+        else if (a == "--ortho_light") {
+            if (i + 3 >= argc) throw runtime_error("missing argument: --ortho_light needs lx ly lz");
+            for (int k = 0; k < 3; ++k) ortho_light[k] = atof(argv[++i]);
+            ortho_light_set = true;
+        }
         else if (a == "--sac_distance_threshold") { sac_distance_threshold = atof(need(i)); sac_distance_threshold_set = true; }
         else if (a == "--sac_max_iterations") sac_max_iterations = atoi(need(i));
         else if (a == "--segment_tile_size") segment_tile_size = atof(need(i));
@@ -745,6 +770,20 @@ int Pose::parseCmdArgs(int argc, char** argv)
         if (segment_labels_dir_set) throw runtime_error("--gpu_segment_labels cannot be combined with --segment_labels_dir");
     }
     if (!segment_image_png.empty() && !ifstream(segment_image_png)) throw runtime_error("could not read " + segment_image_png);
+    if (orthophoto || (run3d_reconstruction && !orthophoto_out.empty())) {
+        if (run3d_reconstruction) {
+            if (n_gpus > 1) throw runtime_error("--orthophoto_out is not available with --gpus N > 1");
+            if (partitioned_merge) throw runtime_error("--orthophoto_out is not available with --partitioned_merge");
+            if (reference_fanout) throw runtime_error("--orthophoto_out is not available with --reference_fanout");
+        } else if (!ifstream(read_PLY_filename0)) {
+            throw runtime_error("could not read " + read_PLY_filename0);
+        }
+        if (ortho_select != "first" && ortho_select != "top" && ortho_select != "bottom")
+            throw runtime_error("--ortho_select must be first, top or bottom");
+        if (ortho_fill_radius < 0 || ortho_fill_radius > O3DR_RASTER_MAX_FILL_RADIUS) throw runtime_error("--ortho_fill_radius must be in 0..32");
+        const double ln = sqrt((ortho_light[0] * ortho_light[0] + ortho_light[1] * ortho_light[1]) + ortho_light[2] * ortho_light[2]);
+        if (ortho_light_set && !(isfinite(ln) && ln > 0.0)) throw runtime_error("--ortho_light must be a finite vector that is not zero");
+    }
     if (run3d_reconstruction && gpu_keypoints) {
         if (n_gpus > 1 || partitioned_merge) throw runtime_error("--gpu_keypoints is not available with --gpus N > 1 / --partitioned_merge");
         if (reference_fanout) throw runtime_error("--gpu_keypoints is not available with --reference_fanout");
@@ -967,6 +1006,69 @@ void Pose::run_mesh_surface()
            (slash == string::npos ? outp : outp.substr(slash + 1));
     if (!save_ply_mesh(outp, *cloud, tris, mesh_normals ? &nrm : nullptr)) throw runtime_error("could not write " + outp);
     cerr << "Saved mesh with " << n << " vertices and " << n_tris << " faces to " << outp << endl;
+}
+
+// --orthophoto: the map of one PLY as images (o3dr_rasterize_map; contract: include/o3dr.h "map raster"), written as
+// ortho_<file>.png, height_<file>.png and, with --ortho_light, shade_<file>.png next to the source.
+void Pose::run_orthophoto()
+{
+    Q = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // the tool needs no camera
+    PointCloud::Ptr cloud = read_PLY_File(read_PLY_filename0);
+    const size_t slash = read_PLY_filename0.find_last_of('/');
+    const string dir = slash == string::npos ? string() : read_PLY_filename0.substr(0, slash + 1);
+    const string base = (slash == string::npos ? read_PLY_filename0 : read_PLY_filename0.substr(slash + 1)) + ".png";
+    write_map_rasters(ctx_for_this_thread(), *cloud, dir + "ortho_" + base, dir + "height_" + base, dir + "shade_" + base);
+}
+
+void Pose::write_map_rasters(o3dr_ctx* c, const PointCloud& cloud, const string& ortho_path, const string& height_path,
+                             const string& shade_path)
+{
+    const int64_t n = (int64_t)cloud.points.size();
+    o3dr_raster_params prm;
+    o3dr_raster_default_params(&prm);
+    prm.cell_size = voxel_size;
+    prm.select = ortho_select == "top" ? O3DR_RASTER_TOP : ortho_select == "bottom" ? O3DR_RASTER_BOTTOM : O3DR_RASTER_FIRST;
+    prm.fill_radius = ortho_fill_radius;
+    prm.use_light = ortho_light_set ? 1 : 0;
+    for (int k = 0; k < 3 && ortho_light_set; ++k) prm.light[k] = ortho_light[k];
+    const auto t0 = chrono::steady_clock::now();
+    chk(o3dr_raster_extent(c, cloud.points.data(), n, voxel_size, &prm.cx0, &prm.cy0, &prm.width, &prm.height, O3DR_MEM_HOST),
+        "o3dr_raster_extent");
+    const int W = prm.width, H = prm.height;
+    const size_t cells = (size_t)W * (size_t)H;
+    vector<float> height(cells);
+    vector<uint8_t> color(cells * 3), shade(ortho_light_set ? cells : 0);
+    o3dr_raster_outputs out = {height.data(), color.data(), ortho_light_set ? shade.data() : nullptr, nullptr, nullptr};
+    o3dr_raster_result res;
+    chk(o3dr_rasterize_map(c, cloud.points.data(), n, &prm, &out, &res, O3DR_MEM_HOST), "o3dr_rasterize_map");
+    const double ms = chrono::duration<double, milli>(chrono::steady_clock::now() - t0).count();
+    // the heights as 16-bit grey: 0 = no data, else 1 + min(65534, floor((z - z_min) / step)), fp64
+    const double step = max(((double)res.z_max - (double)res.z_min) / 65534.0, ldexp(1.0, -15));
+    vector<uint16_t> h16(cells);
+    vector<uint8_t> color_up(cells * 3), shade_up(shade.size());
+    for (int r = 0; r < H; ++r) {  // rows in descending cy: north up, not mirrored
+        const size_t src = (size_t)(H - 1 - r) * W, dst = (size_t)r * W;
+        for (int x = 0; x < W; ++x) {
+            const float z = height[src + x];
+            h16[dst + x] = z != z ? 0 : (uint16_t)(1 + (int)min(65534.0, floor(((double)z - (double)res.z_min) / step)));
+        }
+        memcpy(&color_up[dst * 3], &color[src * 3], (size_t)W * 3);
+        if (ortho_light_set) memcpy(&shade_up[dst], &shade[src], (size_t)W);
+    }
+    char line[256];
+    cout << "points in " << n << " (outside the box " << res.n_outside << ")" << endl;
+    cout << "box cx0 " << res.cx0 << " cy0 " << res.cy0 << " width " << res.width << " height " << res.height << endl;
+    cout << "cells occupied " << res.n_occupied << " (shadowed points " << res.n_shadowed << "), filled " << res.n_filled << ", empty "
+         << res.n_empty << endl;
+    snprintf(line, sizeof line, "z_min %.9g z_max %.9g step %.17g", (double)res.z_min, (double)res.z_max, step);
+    cout << line << endl;
+    snprintf(line, sizeof line, "raster time %.3f ms", ms);
+    cout << line << endl;
+    if (!write_png_bgr8(ortho_path, color_up.data(), H, W)) throw runtime_error("could not write " + ortho_path);
+    if (!write_png_grey16(height_path, h16.data(), H, W)) throw runtime_error("could not write " + height_path);
+    if (ortho_light_set && !write_png_grey8(shade_path, shade_up.data(), H, W)) throw runtime_error("could not write " + shade_path);
+    cerr << "Saved " << W << " x " << H << " map rasters to " << ortho_path << ", " << height_path
+         << (ortho_light_set ? ", " + shade_path : string()) << endl;
 }
 
 o3dr_orb_params Pose::orb_params() const
@@ -1318,6 +1420,10 @@ Pose::Pose(int argc, char* argv[])
     }
     if (mesh_surface) {
         run_mesh_surface();
+        return;
+    }
+    if (orthophoto) {
+        run_orthophoto();
         return;
     }
     if (!find_features_png.empty()) {
@@ -1724,6 +1830,8 @@ void Pose::run_reconstruction()
     cout << "Saving point clouds..." << endl;
     string path = outputPrefix + "cloud.ply";
     save_pt_cloud_to_PLY_File(cloud_small, path);
+    if (!orthophoto_out.empty())  // (from the host copy just written: what --orthophoto makes of that cloud.ply)
+        write_map_rasters(c, *cloud_small, orthophoto_out + "ortho.png", orthophoto_out + "height.png", orthophoto_out + "shade.png");
 }
 
 // --gpus N: the fan-out of pose.cpp:392-413 over GPUs instead of threads of one CPU.  Rank g (host thread g, device
