@@ -231,6 +231,21 @@ private:
     o3dr_ctx* ctx_for_this_thread();
     void push_params(o3dr_ctx* c);
     void run_reconstruction();
+    // a reconstruction cycle (pose.cpp): the accept loop, then the accepted frames into cloud_big - by --reference_fanout, or
+    // stacked in one FrameBatch and through the stages in this order, each handing on in the batch or the CycleState
+    struct FrameBatch;
+    struct F64Images;
+    struct CycleState;
+    void accept_cycle(int& current_idx, int cycle_len);
+    void fanout_cycle(size_t first, size_t last, PointCloud& cloud_big_host);
+    void accumulate_cycle(o3dr_ctx* c, size_t first, size_t last);
+    void orb_stage(o3dr_ctx* c, FrameBatch& b, CycleState& s);         // --gpu_keypoints, --feature_poses
+    void plane_fit_stage(o3dr_ctx* c, FrameBatch& b, CycleState& s);   // --use_segment_labels
+    void pose_chain_stage(o3dr_ctx* c, FrameBatch& b, CycleState& s);  // --feature_poses, --chain_ransac_*, --refine_poses
+    void keep_chained_frames(FrameBatch& b, CycleState& s);            // the chain's status lines, its rejected frames leave the batch
+    void multiview_stage(o3dr_ctx* c, FrameBatch& b, CycleState& s);   // --multiview_filter, --multiview_fuse
+    void write_preview(o3dr_ctx* c);                                   // --preview
+    void merge_and_save(o3dr_ctx* c, PointCloud::Ptr cloud_big_host);  // cloud.ply, --orthophoto_out
     void run_sharded(PointCloud::Ptr cloud_small);  // --gpus N
     void run_align_point_cloud();                   // --align_point_cloud
     void run_smooth_surface();                      // --smooth_surface
@@ -275,7 +290,7 @@ private:
         int rows = 0, cols = 0;
         std::vector<int32_t> map;
     } rectify_map[2];
-    bool disparity_f64 = false;  // what push_params sets: on around the accumulate call of a plane-fitted batch
+    bool disparity_f64 = false;  // what push_params sets: on while a cycle's F64Images lives (plane fits, fused levels)
     std::vector<std::vector<double>> pose_data, images_times_data;
     std::vector<double> pose_times_seq, images_times_seq;
     std::ofstream log_file;

@@ -8,6 +8,7 @@
 #include <iomanip>
 #include <iostream>
 #include <mutex>
+#include <optional>
 #include <sstream>
 #include <stdexcept>
 #include <thread>
@@ -21,6 +22,22 @@ namespace o3dr_host {
 static void chk(int rc, const char* what)
 {
     if (rc != O3DR_OK) throw runtime_error(string(what) + ": " + o3dr_last_error());
+}
+
+static const char* const kChainStatusName[] = {"ANCHOR", "MATCHED", "TOO_FEW", "DEGENERATE", "RMS"};             // O3DR_CHAIN_*
+static const char* const kIcpReasonName[] = {"MAX_ITERATIONS", "UNCHANGED", "SMALL_STEP", "TOO_FEW", "DEGENERATE"};  // o3dr_icp_result.reason
+
+// <dir>/<prefix><file><suffix> next to path = <dir>/<file>: where a tool writes what it made of that file
+static string next_to(const string& path, const string& prefix, const string& suffix = string())
+{
+    const size_t cut = path.find_last_of('/') == string::npos ? 0 : path.find_last_of('/') + 1;
+    return path.substr(0, cut) + prefix + path.substr(cut) + suffix;
+}
+
+static void warn_voxel_overflow(uint32_t status)  // PCL_WARN of VoxelGrid::applyFilter
+{
+    if (status & O3DR_STATUS_VOXEL_OVERFLOW)
+        cerr << "[pcl::VoxelGrid::applyFilter] Leaf size is too small for the input dataset. Integer indices would overflow." << endl;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -110,9 +127,7 @@ PointCloud::Ptr Pose::downsamplePtCloud(PointCloud::Ptr& cloudrgb, bool combined
     chk(o3dr_downsample_pt_cloud(ctx_for_this_thread(), cloudrgb->points.data(), n_in, combinedPtCloud ? 1 : 0,
                                  out->points.data(), n_in > 0 ? n_in : 1, &n, &status, O3DR_MEM_HOST),
         "downsamplePtCloud");
-    if (status & O3DR_STATUS_VOXEL_OVERFLOW)  // PCL_WARN of VoxelGrid::applyFilter
-        cerr << "[pcl::VoxelGrid::applyFilter] Leaf size is too small for the input dataset. Integer indices would overflow."
-             << endl;
+    warn_voxel_overflow(status);
     out->points.resize((size_t)n);
     return out;
 }
@@ -571,47 +586,26 @@ int Pose::parseCmdArgs(int argc, char** argv)
         if (i + 1 >= argc) throw runtime_error(string("missing value after ") + argv[i]);
         return argv[++i];
     };
+    // the one or two file operands of a mode flag (none may begin with "--"; `what` names them): the run is then that tool's
+    auto files = [&](int& i, const char* what, string& f0, string* f1 = nullptr) {
+        const int n = f1 ? 2 : 1;
+        bool ok = i + n < argc;
+        for (int k = 1; ok && k <= n; ++k) ok = string(argv[i + k]).rfind("--", 0) != 0;
+        if (!ok) throw runtime_error(string("missing argument: ") + argv[i] + " needs " + what);
+        f0 = argv[++i];
+        if (f1) *f1 = argv[++i];
+        run3d_reconstruction = false;
+    };
     for (int i = 1; i < argc; ++i) {
         const string a = argv[i];
         if (a == "--help" || a == "/?") { printUsage(); return -1; }
         else if (a == "--downsample") { downsample = true; run3d_reconstruction = false; read_PLY_filename0 = need(i); }
-        else if (a == "--align_point_cloud") {
-            if (i + 2 >= argc || string(argv[i + 1]).rfind("--", 0) == 0 || string(argv[i + 2]).rfind("--", 0) == 0)
-                throw runtime_error("missing argument: --align_point_cloud needs source.ply and target.ply");
-            align_point_cloud = true;
-            run3d_reconstruction = false;
-            read_PLY_filename0 = argv[++i];
-            read_PLY_filename1 = argv[++i];
-        }
-        else if (a == "--smooth_surface") {
-            if (i + 1 >= argc || string(argv[i + 1]).rfind("--", 0) == 0)
-                throw runtime_error("missing argument: --smooth_surface needs file.ply");
-            smooth_surface = true;
-            run3d_reconstruction = false;
-            read_PLY_filename0 = argv[++i];
-        }
-        else if (a == "--segment_cloud_only") {
-            if (i + 1 >= argc || string(argv[i + 1]).rfind("--", 0) == 0)
-                throw runtime_error("missing argument: --segment_cloud_only needs file.ply");
-            segment_cloud_only = true;
-            run3d_reconstruction = false;
-            read_PLY_filename0 = argv[++i];
-        }
-        else if (a == "--mesh_surface") {
-            if (i + 1 >= argc || string(argv[i + 1]).rfind("--", 0) == 0)
-                throw runtime_error("missing argument: --mesh_surface needs file.ply");
-            mesh_surface = true;
-            run3d_reconstruction = false;
-            read_PLY_filename0 = argv[++i];
-        }
+        else if (a == "--align_point_cloud") { files(i, "source.ply and target.ply", read_PLY_filename0, &read_PLY_filename1); align_point_cloud = true; }
+        else if (a == "--smooth_surface") { files(i, "file.ply", read_PLY_filename0); smooth_surface = true; }
+        else if (a == "--segment_cloud_only") { files(i, "file.ply", read_PLY_filename0); segment_cloud_only = true; }
+        else if (a == "--mesh_surface") { files(i, "file.ply", read_PLY_filename0); mesh_surface = true; }
         else if (a == "--mesh_normals") mesh_normals = true;
-        else if (a == "--orthophoto") {
-            if (i + 1 >= argc || string(argv[i + 1]).rfind("--", 0) == 0)
-                throw runtime_error("missing argument: --orthophoto needs file.ply");
-            orthophoto = true;
-            run3d_reconstruction = false;
-            read_PLY_filename0 = argv[++i];
-        }
+        else if (a == "--orthophoto") { files(i, "file.ply", read_PLY_filename0); orthophoto = true; }
         else if (a == "--orthophoto_out") orthophoto_out = need(i);
         else if (a == "--ortho_select") ortho_select = need(i);
         else if (a == "--ortho_fill_radius") ortho_fill_radius = atoi(need(i));
@@ -668,31 +662,15 @@ int Pose::parseCmdArgs(int argc, char** argv)
         else if (a == "--use_segment_labels") use_segment_labels = true;
         else if (a == "--segment_labels_dir") { segmentLabelsPrefix = need(i); segment_labels_dir_set = true; }
         else if (a == "--gpu_segment_labels") gpu_segment_labels = true;
-        else if (a == "--segment_image") {
-            if (i + 1 >= argc || string(argv[i + 1]).rfind("--", 0) == 0)
-                throw runtime_error("missing argument: --segment_image needs image.png");
-            segment_image_png = argv[++i];
-            run3d_reconstruction = false;
-        }
+        else if (a == "--segment_image") files(i, "image.png", segment_image_png);
         else if (a == "--segment_step") segment_step = atoi(need(i));
         else if (a == "--segment_compactness") segment_compactness = atoi(need(i));
         else if (a == "--segment_iterations") segment_iterations = atoi(need(i));
         else if (a == "--segment_min_size") segment_min_size = atoi(need(i));
         else if (a == "--plane_min_pixels") plane_min_pixels = atoi(need(i));
         else if (a == "--plane_max_mse") plane_max_mse = atof(need(i));
-        else if (a == "--find_features") {
-            if (i + 1 >= argc || string(argv[i + 1]).rfind("--", 0) == 0)
-                throw runtime_error("missing argument: --find_features needs image.png");
-            find_features_png = argv[++i];
-            run3d_reconstruction = false;
-        }
-        else if (a == "--stereo_disparity") {
-            if (i + 2 >= argc || string(argv[i + 1]).rfind("--", 0) == 0 || string(argv[i + 2]).rfind("--", 0) == 0)
-                throw runtime_error("missing argument: --stereo_disparity needs left.png and right.png");
-            stereo_left_png = argv[++i];
-            stereo_right_png = argv[++i];
-            run3d_reconstruction = false;
-        }
+        else if (a == "--find_features") files(i, "image.png", find_features_png);
+        else if (a == "--stereo_disparity") files(i, "left.png and right.png", stereo_left_png, &stereo_right_png);
         else if (a == "--gpu_disparity") gpu_disparity = true;
         else if (a == "--right_image_dir") rightImagePrefix = need(i);
         else if (a == "--stereo_n_disparities") stereo_n_disparities = atoi(need(i));
@@ -705,19 +683,8 @@ int Pose::parseCmdArgs(int argc, char** argv)
         else if (a == "--stereo_median") stereo_median = atoi(need(i));
         else if (a == "--stereo_speckle_size") stereo_speckle_size = atoi(need(i));
         else if (a == "--stereo_speckle_diff") stereo_speckle_diff = atoi(need(i));
-        else if (a == "--filter_disparity") {
-            if (i + 1 >= argc || string(argv[i + 1]).rfind("--", 0) == 0)
-                throw runtime_error("missing argument: --filter_disparity needs in.png");
-            filter_disparity_png = argv[++i];
-            run3d_reconstruction = false;
-        }
-        else if (a == "--rectify_pair") {
-            if (i + 2 >= argc || string(argv[i + 1]).rfind("--", 0) == 0 || string(argv[i + 2]).rfind("--", 0) == 0)
-                throw runtime_error("missing argument: --rectify_pair needs left.png and right.png");
-            rectify_left_png = argv[++i];
-            rectify_right_png = argv[++i];
-            run3d_reconstruction = false;
-        }
+        else if (a == "--filter_disparity") files(i, "in.png", filter_disparity_png);
+        else if (a == "--rectify_pair") files(i, "left.png and right.png", rectify_left_png, &rectify_right_png);
         else if (a == "--rectify_calib") rectify_calib = need(i);
         else if (a == "--rectify_border") rectify_border = atoi(need(i));
         else if (a == "--gpu_keypoints") gpu_keypoints = true;
@@ -742,28 +709,28 @@ int Pose::parseCmdArgs(int argc, char** argv)
             ++n_imgs;
         }
     }
+    // A feature of the single-GPU batched path says so on the other paths instead of dropping its flag: the first refusal that
+    // applies, --gpus N and --partitioned_merge in one message (combined) or in one each
+    auto batched_path_only = [&](const string& flag, bool combined) {
+        const string head = flag + " is not available with ";
+        if (combined && (n_gpus > 1 || partitioned_merge)) throw runtime_error(head + "--gpus N > 1 / --partitioned_merge");
+        if (n_gpus > 1) throw runtime_error(head + "--gpus N > 1");
+        if (partitioned_merge) throw runtime_error(head + "--partitioned_merge");
+        if (reference_fanout) throw runtime_error(head + "--reference_fanout");
+    };
     if (run3d_reconstruction && use_segment_labels) {
-        // the modes that do not take the fitted images say so instead of dropping the flag
-        if (n_gpus > 1 || partitioned_merge) throw runtime_error("--use_segment_labels is not available with --gpus N > 1 / --partitioned_merge");
-        if (reference_fanout) throw runtime_error("--use_segment_labels is not available with --reference_fanout");
+        batched_path_only("--use_segment_labels", true);
         if (blur_kernel > 1) throw runtime_error("--use_segment_labels cannot be combined with --blur_kernel > 1 (cv::bilateralFilter rejects CV_64F)");
     }
-    if (run3d_reconstruction && multiview_fuse) {
-        // the fusion sits where the filter does, and hands the accumulate call float64 images of its own
-        if (n_gpus > 1) throw runtime_error("--multiview_fuse is not available with --gpus N > 1");
-        if (partitioned_merge) throw runtime_error("--multiview_fuse is not available with --partitioned_merge");
-        if (reference_fanout) throw runtime_error("--multiview_fuse is not available with --reference_fanout");
-        if (use_segment_labels) throw runtime_error("--multiview_fuse is not available with --use_segment_labels (its images are CV_64F fits)");
-        if (blur_kernel > 1) throw runtime_error("--multiview_fuse is not available with --blur_kernel > 1 (the blur would run on the fused image)");
-        multiview_filter = false;  // (given together, the two flags mean fuse)
-    }
-    if (run3d_reconstruction && multiview_filter) {
-        // the filter sits between the cycle's poses and the batched accumulate call: the paths without that call say so
-        if (n_gpus > 1) throw runtime_error("--multiview_filter is not available with --gpus N > 1");
-        if (partitioned_merge) throw runtime_error("--multiview_filter is not available with --partitioned_merge");
-        if (reference_fanout) throw runtime_error("--multiview_filter is not available with --reference_fanout");
-        if (use_segment_labels) throw runtime_error("--multiview_filter is not available with --use_segment_labels (its images are CV_64F fits)");
-        if (blur_kernel > 1) throw runtime_error("--multiview_filter is not available with --blur_kernel > 1 (the blur would run on the filtered image)");
+    if (run3d_reconstruction && (multiview_filter || multiview_fuse)) {
+        // the filter sits between the cycle's poses and the batched accumulate call, the fusion where the filter does (it
+        // hands that call float64 images of its own); given together, the two flags mean fuse
+        const string flag = multiview_fuse ? "--multiview_fuse" : "--multiview_filter";
+        batched_path_only(flag, false);
+        if (use_segment_labels) throw runtime_error(flag + " is not available with --use_segment_labels (its images are CV_64F fits)");
+        if (blur_kernel > 1)
+            throw runtime_error(flag + " is not available with --blur_kernel > 1 (the blur would run on the " + (multiview_fuse ? "fused" : "filtered") + " image)");
+        if (multiview_fuse) multiview_filter = false;
     }
     if (run3d_reconstruction && gpu_segment_labels) {
         if (!use_segment_labels) throw runtime_error("--gpu_segment_labels makes the labels of --use_segment_labels: give both");
@@ -772,9 +739,7 @@ int Pose::parseCmdArgs(int argc, char** argv)
     if (!segment_image_png.empty() && !ifstream(segment_image_png)) throw runtime_error("could not read " + segment_image_png);
     if (orthophoto || (run3d_reconstruction && !orthophoto_out.empty())) {
         if (run3d_reconstruction) {
-            if (n_gpus > 1) throw runtime_error("--orthophoto_out is not available with --gpus N > 1");
-            if (partitioned_merge) throw runtime_error("--orthophoto_out is not available with --partitioned_merge");
-            if (reference_fanout) throw runtime_error("--orthophoto_out is not available with --reference_fanout");
+            batched_path_only("--orthophoto_out", false);
         } else if (!ifstream(read_PLY_filename0)) {
             throw runtime_error("could not read " + read_PLY_filename0);
         }
@@ -784,22 +749,15 @@ int Pose::parseCmdArgs(int argc, char** argv)
         const double ln = sqrt((ortho_light[0] * ortho_light[0] + ortho_light[1] * ortho_light[1]) + ortho_light[2] * ortho_light[2]);
         if (ortho_light_set && !(isfinite(ln) && ln > 0.0)) throw runtime_error("--ortho_light must be a finite vector that is not zero");
     }
-    if (run3d_reconstruction && gpu_keypoints) {
-        if (n_gpus > 1 || partitioned_merge) throw runtime_error("--gpu_keypoints is not available with --gpus N > 1 / --partitioned_merge");
-        if (reference_fanout) throw runtime_error("--gpu_keypoints is not available with --reference_fanout");
-    }
+    if (run3d_reconstruction && gpu_keypoints) batched_path_only("--gpu_keypoints", true);
     if (run3d_reconstruction && gpu_disparity) {
-        if (n_gpus > 1 || partitioned_merge) throw runtime_error("--gpu_disparity is not available with --gpus N > 1 / --partitioned_merge");
-        if (reference_fanout) throw runtime_error("--gpu_disparity is not available with --reference_fanout");
+        batched_path_only("--gpu_disparity", true);
         if (use_segment_labels) throw runtime_error("--gpu_disparity is not available with --use_segment_labels");
         if (rightImagePrefix.empty()) throw runtime_error("--gpu_disparity needs --right_image_dir d/");
     }
     if (!rectify_left_png.empty() && rectify_calib.empty()) throw runtime_error("--rectify_pair needs --rectify_calib f");
     if (!rectify_calib.empty()) {
-        if (run3d_reconstruction) {
-            if (n_gpus > 1 || partitioned_merge) throw runtime_error("--rectify_calib is not available with --gpus N > 1 / --partitioned_merge");
-            if (reference_fanout) throw runtime_error("--rectify_calib is not available with --reference_fanout");
-        }
+        if (run3d_reconstruction) batched_path_only("--rectify_calib", true);
         if (rectify_border < 0 || rectify_border > 255) throw runtime_error("--rectify_border must be in 0..255");
         readRectifyCalib();
     }
@@ -809,10 +767,7 @@ int Pose::parseCmdArgs(int argc, char** argv)
         if (!ifstream(filter_disparity_png)) throw runtime_error("could not read " + filter_disparity_png);
     }
     if (refine_poses && !feature_poses) throw runtime_error("--refine_poses refines the poses of --feature_poses: give both");
-    if (run3d_reconstruction && feature_poses) {
-        if (n_gpus > 1 || partitioned_merge) throw runtime_error("--feature_poses is not available with --gpus N > 1 / --partitioned_merge");
-        if (reference_fanout) throw runtime_error("--feature_poses is not available with --reference_fanout");
-    }
+    if (run3d_reconstruction && feature_poses) batched_path_only("--feature_poses", true);
     if (run3d_reconstruction) {
         if (n_imgs == 0) throw runtime_error("first and last image number are required");
         if (last_img_num < first_img_num) last_img_num = first_img_num;
@@ -828,7 +783,6 @@ int Pose::parseCmdArgs(int argc, char** argv)
 // result is printed and the source, moved by fp32(T) through transformPtCloud, is written as aligned_<source> next to it.
 void Pose::run_align_point_cloud()
 {
-    Q = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // the tool needs no camera
     PointCloud::Ptr src = read_PLY_File(read_PLY_filename0);
     PointCloud::Ptr tgt = read_PLY_File(read_PLY_filename1);
     o3dr_icp_params prm;
@@ -840,7 +794,6 @@ void Pose::run_align_point_cloud()
     chk(o3dr_icp_align(ctx_for_this_thread(), src->points.data(), (int64_t)src->points.size(), tgt->points.data(),
                        (int64_t)tgt->points.size(), nullptr, &prm, &res, O3DR_MEM_HOST),
         "o3dr_icp_align");
-    static const char* kReason[] = {"MAX_ITERATIONS", "UNCHANGED", "SMALL_STEP", "TOO_FEW", "DEGENERATE"};
     char line[256];
     cout << "ICP transformation (source -> target):" << endl;
     for (int r = 0; r < 4; ++r) {
@@ -851,15 +804,12 @@ void Pose::run_align_point_cloud()
     cout << line << endl;
     cout << "correspondences " << res.n_correspondences << endl;
     cout << "iterations " << res.iterations << endl;
-    cout << "reason " << (res.reason >= 0 && res.reason < 5 ? kReason[res.reason] : "?") << endl;
+    cout << "reason " << (res.reason >= 0 && res.reason < 5 ? kIcpReasonName[res.reason] : "?") << endl;
     Matrix4 Tf;
     for (int k = 0; k < 16; ++k) Tf[k] = (float)res.T[k];
     PointCloud::Ptr aligned(new PointCloud());
     if (!src->points.empty()) transformPtCloud(src, aligned, Tf);
-    string out = read_PLY_filename0;
-    const size_t slash = out.find_last_of('/');
-    out = (slash == string::npos ? string() : out.substr(0, slash + 1)) + "aligned_" +
-          (slash == string::npos ? out : out.substr(slash + 1));
+    string out = next_to(read_PLY_filename0, "aligned_");
     save_pt_cloud_to_PLY_File(aligned, out);
 }
 
@@ -869,7 +819,6 @@ void Pose::run_align_point_cloud()
 void Pose::run_smooth_surface()
 {
     if (!search_radius_set) throw runtime_error("missing argument: --smooth_surface needs --search_radius r");
-    Q = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // the tool needs no camera
     PointCloud::Ptr cloud = read_PLY_File(read_PLY_filename0);
     const int64_t n = (int64_t)cloud->points.size();
     o3dr_mls_params prm;
@@ -901,10 +850,7 @@ void Pose::run_smooth_surface()
     char line[64];
     snprintf(line, sizeof line, "mls time %.3f ms", ms);
     cout << line << endl;
-    string outp = read_PLY_filename0;
-    const size_t slash = outp.find_last_of('/');
-    outp = (slash == string::npos ? string() : outp.substr(0, slash + 1)) + "smoothed_" +
-           (slash == string::npos ? outp : outp.substr(slash + 1));
+    const string outp = next_to(read_PLY_filename0, "smoothed_");
     if (!save_ply_binary(outp, *kept, mls_normals ? &kept_nrm : nullptr)) throw runtime_error("could not write " + outp);
     cerr << "Saved Point Cloud with " << kept->points.size() << " data points to " << outp << endl;
 }
@@ -915,7 +861,6 @@ void Pose::run_smooth_surface()
 void Pose::run_segment_cloud()
 {
     if (!sac_distance_threshold_set) throw runtime_error("missing argument: --segment_cloud_only needs --sac_distance_threshold t");
-    Q = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // the tool needs no camera
     PointCloud::Ptr cloud = read_PLY_File(read_PLY_filename0);
     const int64_t n = (int64_t)cloud->points.size();
     o3dr_plane_params prm;
@@ -958,12 +903,8 @@ void Pose::run_segment_cloud()
     if (n_tiles > 10) cout << "... and " << n_tiles - 10 << " more tiles" << endl;
     snprintf(line, sizeof line, "segment time %.3f ms", ms);
     cout << line << endl;
-    string dir = read_PLY_filename0, base = read_PLY_filename0;
-    const size_t slash = base.find_last_of('/');
-    dir = slash == string::npos ? string() : base.substr(0, slash + 1);
-    if (slash != string::npos) base = base.substr(slash + 1);
-    for (const auto& out : {make_pair(string("ground_"), ground), make_pair(string("nonground_"), rest)}) {
-        const string path = dir + out.first + base;
+    for (const auto& out : {make_pair("ground_", ground), make_pair("nonground_", rest)}) {
+        const string path = next_to(read_PLY_filename0, out.first);
         if (!save_ply_binary(path, *out.second)) throw runtime_error("could not write " + path);
         cerr << "Saved Point Cloud with " << out.second->points.size() << " data points to " << path << endl;
     }
@@ -975,7 +916,6 @@ void Pose::run_segment_cloud()
 void Pose::run_mesh_surface()
 {
     if (!search_radius_set) throw runtime_error("missing argument: --mesh_surface needs --search_radius L");
-    Q = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // the tool needs no camera
     PointCloud::Ptr cloud = read_PLY_File(read_PLY_filename0);
     const int64_t n = (int64_t)cloud->points.size();
     o3dr_mesh_params prm;
@@ -1000,10 +940,7 @@ void Pose::run_mesh_surface()
     char line[64];
     snprintf(line, sizeof line, "mesh time %.3f ms", ms);
     cout << line << endl;
-    string outp = read_PLY_filename0;
-    const size_t slash = outp.find_last_of('/');
-    outp = (slash == string::npos ? string() : outp.substr(0, slash + 1)) + "mesh_" +
-           (slash == string::npos ? outp : outp.substr(slash + 1));
+    const string outp = next_to(read_PLY_filename0, "mesh_");
     if (!save_ply_mesh(outp, *cloud, tris, mesh_normals ? &nrm : nullptr)) throw runtime_error("could not write " + outp);
     cerr << "Saved mesh with " << n << " vertices and " << n_tris << " faces to " << outp << endl;
 }
@@ -1012,12 +949,9 @@ void Pose::run_mesh_surface()
 // ortho_<file>.png, height_<file>.png and, with --ortho_light, shade_<file>.png next to the source.
 void Pose::run_orthophoto()
 {
-    Q = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // the tool needs no camera
     PointCloud::Ptr cloud = read_PLY_File(read_PLY_filename0);
-    const size_t slash = read_PLY_filename0.find_last_of('/');
-    const string dir = slash == string::npos ? string() : read_PLY_filename0.substr(0, slash + 1);
-    const string base = (slash == string::npos ? read_PLY_filename0 : read_PLY_filename0.substr(slash + 1)) + ".png";
-    write_map_rasters(ctx_for_this_thread(), *cloud, dir + "ortho_" + base, dir + "height_" + base, dir + "shade_" + base);
+    const string& src = read_PLY_filename0;
+    write_map_rasters(ctx_for_this_thread(), *cloud, next_to(src, "ortho_", ".png"), next_to(src, "height_", ".png"), next_to(src, "shade_", ".png"));
 }
 
 void Pose::write_map_rasters(o3dr_ctx* c, const PointCloud& cloud, const string& ortho_path, const string& height_path,
@@ -1087,7 +1021,6 @@ o3dr_orb_params Pose::orb_params() const
 // %.9g (a float's exact round trip), as <image>.keypoints.txt: what --keypoints_dir reads as <img_num>.txt.
 void Pose::run_find_features()
 {
-    Q = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // the tool needs no camera
     const Image8 im = read_png(find_features_png, false);
     if (im.empty()) throw runtime_error("could not read " + find_features_png);
     const o3dr_orb_params prm = orb_params();
@@ -1130,7 +1063,6 @@ o3dr_stereo_params Pose::stereo_params(int channels) const
 // written as <left>.disparity.png: what --disparity_dir reads as <img_num>.png.
 void Pose::run_stereo_disparity()
 {
-    Q = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // the tool needs no camera
     Image8 left = read_png(stereo_left_png, false), right = read_png(stereo_right_png, false);
     if (left.empty()) throw runtime_error("could not read " + stereo_left_png);
     if (right.empty()) throw runtime_error("could not read " + stereo_right_png);
@@ -1177,7 +1109,6 @@ void Pose::filter_disparities(o3dr_ctx* c, vector<uint8_t>& disp, int rows, int 
 // The filter alone on an 8-bit grey PNG (contract: include/o3dr.h "disparity filter"), written as <in>.filtered.png.
 void Pose::run_filter_disparity()
 {
-    Q = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // the tool needs no camera
     const Image8 in = read_png(filter_disparity_png, true);
     if (in.empty() || in.channels != 1) throw runtime_error("could not read " + filter_disparity_png + " as an 8-bit grey PNG");
     vector<uint8_t> disp(in.data.begin(), in.data.begin() + (long)((size_t)in.rows * in.cols));
@@ -1206,7 +1137,6 @@ o3dr_segment_params Pose::segment_params(int channels) const
 // Superpixel labels of one image (contract: include/o3dr.h "image segmentation"), written as <image>.labels.png, 16-bit grey.
 void Pose::run_segment_image()
 {
-    Q = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // the tool needs no camera
     const Image8 in = read_png(segment_image_png, false);
     if (in.empty() || (in.channels != 1 && in.channels != 3)) throw runtime_error("could not read " + segment_image_png + " as an 8-bit PNG");
     const size_t n = (size_t)in.rows * in.cols;
@@ -1300,7 +1230,6 @@ void Pose::rectify_images(o3dr_ctx* c, int cam, const vector<Image8*>& imgs, int
 // as <left>.rectified.png and <right>.rectified.png: what --stereo_disparity, image_dir and right_image_dir take.
 void Pose::run_rectify_pair()
 {
-    Q = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // the tool needs no camera
     Image8 im[2] = {read_png(rectify_left_png, false), read_png(rectify_right_png, false)};
     const string* path[2] = {&rectify_left_png, &rectify_right_png};
     for (int k = 0; k < 2; ++k)
@@ -1394,15 +1323,11 @@ void Pose::compute_gpu_disparities()
 Pose::Pose(int argc, char* argv[])
 {
     if (parseCmdArgs(argc, argv) != 0) return;
+    if (!run3d_reconstruction) Q = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // a tool needs no camera
     if (downsample) {  // pose.cpp:71-87
-
-        Q = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // the tool needs no camera
         PointCloud::Ptr cloud = read_PLY_File(read_PLY_filename0);
         PointCloud::Ptr small = downsamplePtCloud(cloud, true);
-        string out = read_PLY_filename0;
-        const size_t slash = out.find_last_of('/');
-        out = (slash == string::npos ? string() : out.substr(0, slash + 1)) + "downsampled_" +
-              (slash == string::npos ? out : out.substr(slash + 1));
+        string out = next_to(read_PLY_filename0, "downsampled_");
         save_pt_cloud_to_PLY_File(small, out);
         return;
     }
@@ -1463,353 +1388,388 @@ Pose::Pose(int argc, char* argv[])
     run_reconstruction();
 }
 
-void Pose::run_reconstruction()
-{
-    typedef chrono::steady_clock clk;
-    const auto app_start = clk::now();
-    o3dr_ctx* c = ctx_for_this_thread();
-    chk(o3dr_cloud_big_reset(c), "cloud_big_reset");
-    PointCloud::Ptr cloud_big_host(new PointCloud());  // only used by --reference_fanout
-    const int last_idx = (int)rawImageDataVec.size() - 1;
-    const int cycle_len = seq_len > 0 ? seq_len : (int)rawImageDataVec.size();
-    int current_idx = 0, cycle = 0;
-    acceptedImageDataVec.reserve(rawImageDataVec.size());
-    if (!sor && jump_pixels > 0)
-        cout << "NOTE: --sor 0: the per-frame StatisticalOutlierRemoval of the reference (pose_functions.cpp:1673-1686) is OFF;\n"
-                "      the clouds differ from the reference's for the same command line." << endl;
-    const bool sharded_path = n_gpus > 1 || partitioned_merge;
-    if (preview && (sharded_path || reference_fanout))
-        cout << "--preview: not available on the " << (sharded_path ? "--gpus / --partitioned_merge" : "--reference_fanout")
-             << " path" << endl;
-    cout << "\n\nProgram Start!" << endl;
-    while (current_idx <= last_idx) {
-        cout << "\nCycle " << cycle << endl;
-        const size_t first_accepted = acceptedImageDataVec.size();
-        int images_in_cycle = 0;
-        while (images_in_cycle < cycle_len && current_idx <= last_idx) {  // pose.cpp:162-255
-            RawImageData& r = rawImageDataVec[current_idx];
-            if (r.rgb_image.empty()) { cout << r.img_num << " could not read rgb image. \tRejected!" << endl; current_idx++; continue; }
-            if (r.disparity_image.empty()) { cout << r.img_num << " could not read disparity image. \tRejected!" << endl; current_idx++; continue; }
-            if (use_segment_labels && r.label_image.empty()) { cout << r.img_num << " could not read segment label image. \tRejected!" << endl; current_idx++; continue; }
-            const double var = getVariance(r.disparity_image);
-            cout << r.img_num << " " << flush;
-            if (var > 5) { cout << " disp_img_var = " << var << " > 5.\tRejected!" << endl; current_idx++; continue; }
-            ImageData d;
-            d.raw_img_data_ptr = &r;
-            d.t_mat_MAVLink = generateTmat(current_idx);
-            d.t_mat_FeatureMatched = d.t_mat_MAVLink;  // --only_MAVLink, pose.cpp:238
-            if (!keypointsPrefix.empty()) {
-                // the list the reference's ORB stage would leave in features.keypoints (pose_functions.cpp:1057-1061)
-                ifstream kf(keypointsPrefix + to_string(r.img_num) + ".txt");
-                float kx, ky;
-                while (kf >> kx >> ky) {
-                    d.keypoints_xy.push_back(kx);
-                    d.keypoints_xy.push_back(ky);
-                }
-            }
-            acceptedImageDataVec.push_back(d);
-            cout << "\tAccepted!" << endl;
-            current_idx++;
-            images_in_cycle++;
-        }
-        // ---- point cloud creation for this cycle (pose.cpp:365-434) -------------------------------
-        const auto t3 = clk::now();
-        cout << "Adding Point Cloud number/points ";
-        const size_t n_acc = acceptedImageDataVec.size() - first_accepted;
-        const bool sharded = n_gpus > 1 || partitioned_merge;
-        if (sharded) {
-            // frames are sharded over the GPUs as contiguous blocks of the WHOLE accepted list (global frame order is what
-            // the merge sums in): the clouds are made after the last cycle
-            cout << "(deferred: --gpus)";
-        } else if (reference_fanout) {
-            // the reference's own structure: batches of <= 7 threads, results appended in frame order
-            for (size_t i0 = first_accepted; i0 < first_accepted + n_acc; i0 += 7) {
-                const size_t nb = min<size_t>(7, first_accepted + n_acc - i0);
-                vector<PointCloud::Ptr> clouds(nb);
-                vector<thread> th;
-                for (size_t k = 0; k < nb; ++k) {
-                    clouds[k].reset(new PointCloud());
-                    th.emplace_back([this, i0, k, &clouds]() { createAndTransformPtCloud((int)(i0 + k), clouds[k]); });
-                }
-                for (thread& t : th) t.join();
-                for (size_t k = 0; k < nb; ++k)
-                    cloud_big_host->points.insert(cloud_big_host->points.end(), clouds[k]->points.begin(), clouds[k]->points.end());
-            }
-        } else if (n_acc) {
-            // MI355X-native form of the same loop: the whole cycle in one batched call, cloud_big in HBM
-            const RawImageData& r0 = *acceptedImageDataVec[first_accepted].raw_img_data_ptr;
-            const size_t dsz = r0.disparity_image.data.size(), csz = r0.rgb_image.data.size();
-            vector<uint8_t> disp(dsz * n_acc), bgr(csz * n_acc);
-            vector<float> poses(16 * n_acc), kp_xy;
-            vector<int64_t> kp_off(n_acc + 1, 0);
-            for (size_t k = 0; k < n_acc; ++k) {
-                const ImageData& im = acceptedImageDataVec[first_accepted + k];
-                memcpy(&disp[k * dsz], im.raw_img_data_ptr->disparity_image.data.data(), dsz);
-                memcpy(&bgr[k * csz], im.raw_img_data_ptr->rgb_image.data.data(), csz);
-                memcpy(&poses[16 * k], im.t_mat_FeatureMatched.data(), 64);
-                kp_xy.insert(kp_xy.end(), im.keypoints_xy.begin(), im.keypoints_xy.end());
-                kp_off[k + 1] = (int64_t)(kp_xy.size() / 2);
-                if (!feature_poses) cout << " " << im.raw_img_data_ptr->img_num << flush;
-            }
-            // page-locked frame stacks cross PCIe by DMA (best effort: pageable memory works too)
-            const bool reg_disp = o3dr_host_register(disp.data(), (int64_t)disp.size()) == O3DR_OK;
-            const bool reg_bgr = o3dr_host_register(bgr.data(), (int64_t)bgr.size()) == O3DR_OK;
-            // --gpu_keypoints: the batch's keypoint lists from the ORB extractor instead of files (the list the reference's
-            // ORB stage leaves in features.keypoints, pose_functions.cpp:1057-1061)
-            int rc_orb = O3DR_OK;
-            string why_orb;
-            const bool orb_for_cloud = gpu_keypoints && jump_pixels != 1 && keypointsPrefix.empty();
-            vector<float> orb_xy;       // --feature_poses: the cycle's features (one extractor call, shared with --gpu_keypoints)
-            vector<uint8_t> orb_desc;
-            vector<int64_t> orb_off(n_acc + 1, 0);
-            if (orb_for_cloud || feature_poses) {
-                const o3dr_orb_params prm = orb_params();
-                const int64_t cap = (int64_t)n_acc * (prm.n_features > 0 ? prm.n_features : 1);
-                orb_xy.assign((size_t)cap * 2, 0.f);
-                if (feature_poses) orb_desc.assign((size_t)cap * 32, 0);
-                int64_t n_kp = 0;
-                const auto tk = clk::now();
-                rc_orb = o3dr_orb_detect(c, bgr.data(), (int64_t)csz, 3 * (int64_t)cols, rows, cols, (int32_t)n_acc, &prm, nullptr, orb_xy.data(),
-                                         feature_poses ? orb_desc.data() : nullptr, orb_off.data(), nullptr, cap, &n_kp, O3DR_MEM_HOST);
-                if (rc_orb != O3DR_OK) why_orb = o3dr_last_error();
-                orb_xy.resize((size_t)n_kp * 2);
-                orb_desc.resize(feature_poses ? (size_t)n_kp * 32 : 0);
-                cout << "\nORB keypoints: " << n_kp << " in " << n_acc << " frames, " << chrono::duration<double>(clk::now() - tk).count()
-                     << " sec" << flush;
-                if (orb_for_cloud) {
-                    kp_xy = orb_xy;
-                    kp_off = orb_off;
-                }
-            }
-            // --use_segment_labels: the batch's 8-bit disparities become plane-fitted CV_64F images first
-            vector<double> fitted;
-            int rc_fit = O3DR_OK;
-            string why_fit;
-            if (use_segment_labels) {
-                vector<uint16_t> lab(dsz * n_acc);
-                uint32_t max_label = 0;
-                for (size_t k = 0; k < n_acc; ++k) {
-                    const Image16& li = acceptedImageDataVec[first_accepted + k].raw_img_data_ptr->label_image;
-                    memcpy(&lab[k * dsz], li.data.data(), dsz * sizeof(uint16_t));
-                    for (uint16_t v : li.data) max_label = max<uint32_t>(max_label, v);
-                }
-                fitted.resize(dsz * n_acc);
-                o3dr_plane_disp_params pp;
-                o3dr_plane_disp_default_params(&pp);
-                pp.min_pixels = plane_min_pixels;
-                pp.max_mse = plane_max_mse;
-                const auto tf = clk::now();
-                rc_fit = o3dr_plane_fit_disparity(c, disp.data(), cols, (int64_t)dsz, lab.data(), 2, 2 * (int64_t)cols, 2 * (int64_t)dsz,
-                                                  (int32_t)max_label + 1, rows, cols, (int32_t)n_acc, &pp, fitted.data(), nullptr, nullptr,
-                                                  O3DR_MEM_HOST);
-                if (rc_fit != O3DR_OK) why_fit = o3dr_last_error();
-                cout << "\nplane-fitted disparity: " << n_acc << " frames, " << max_label + 1 << " labels, "
-                     << chrono::duration<double>(clk::now() - tf).count() << " sec" << flush;
-                disparity_f64 = true;
-                push_params(c);
-            }
-            uint8_t* disp_in = use_segment_labels ? (uint8_t*)fitted.data() : disp.data();
-            const int64_t esz = use_segment_labels ? 8 : 1;
-            // --feature_poses: the cycle's frames through the chain (history = the frames of the cycles before), then only the
-            // accepted frames stay in the stacks, with the chain's poses
-            size_t n_cloud = n_acc;
-            int rc_chain = O3DR_OK;
-            string why_chain;
-            if (feature_poses && rc_orb == O3DR_OK && rc_fit == O3DR_OK) {
-                const auto tc = clk::now();
-                const size_t n_hist = chain.status.size(), n_all = n_hist + n_acc, n_kp = orb_xy.size() / 2;
-                vector<o3dr_point> kp3(n_kp ? n_kp : 1);
-                int64_t n3 = 0;
-                rc_chain = o3dr_keypoints_3d(c, disp_in, esz * (int64_t)dsz, esz * cols, nullptr, 0, 0, rows, cols, nullptr, (int32_t)n_acc,
-                                             orb_xy.data(), orb_off.data(), kp3.data(), (int64_t)kp3.size(), &n3, O3DR_MEM_HOST);
-                if (rc_chain != O3DR_OK) why_chain = string("keypoints_3d: ") + o3dr_last_error();
-                const int64_t base = chain.off.back();
-                chain.desc.insert(chain.desc.end(), orb_desc.begin(), orb_desc.end());
-                chain.kp3.insert(chain.kp3.end(), kp3.begin(), kp3.begin() + (ptrdiff_t)n_kp);
-                for (size_t k = 0; k < n_acc; ++k) {
-                    chain.off.push_back(base + orb_off[k + 1]);
-                    const Matrix4& m = acceptedImageDataVec[first_accepted + k].t_mat_MAVLink;
-                    chain.prior.insert(chain.prior.end(), m.begin(), m.end());
-                }
-                vector<float> chain_out(16 * n_all);
-                vector<o3dr_chain_frame> recs(n_all);
-                o3dr_chain_params cp;
-                o3dr_chain_default_params(&cp);
-                cp.dist_nearby = dist_nearby;
-                cp.range_width = range_width;
-                cp.min_matches = chain_min_matches;
-                cp.max_rms = chain_max_rms;
-                // --chain_ransac_threshold: the pair list and one RANSAC record per pair come back too, for the dropped counts
-                o3dr_ransac_params rp;
-                o3dr_ransac_default_params(&rp);
-                rp.threshold = chain_ransac_threshold;
-                rp.iterations = chain_ransac_iterations;
-                rp.seed = chain_ransac_seed;
-                const bool want_pairs = chain_ransac || refine_poses;
-                const size_t pair_cap = want_pairs ? n_acc * (size_t)O3DR_CHAIN_MAX_RANGE : 0;
-                vector<int32_t> pair_list(2 * pair_cap + 2);
-                vector<o3dr_ransac_result> rres(pair_cap + 1);
-                int64_t n_list = 0;
-                if (rc_chain == O3DR_OK) {
-                    rc_chain = o3dr_pose_chain_robust(c, chain.desc.data(), chain.off.data(), chain.kp3.data(), chain.prior.data(),
-                                                      (int32_t)n_all, (int32_t)n_hist, chain.poses.data(), chain.status.data(), &cp,
-                                                      chain_out.data(), recs.data(), want_pairs ? pair_list.data() : nullptr,
-                                                      (int64_t)pair_cap, &n_list, O3DR_MEM_HOST, chain_ransac ? &rp : nullptr,
-                                                      chain_ransac ? rres.data() : nullptr);
-                    if (rc_chain != O3DR_OK) why_chain = string("pose_chain: ") + o3dr_last_error();
-                }
-                // a frame's dropped slots: over its pairs with an accepted train frame, the candidates that are no inliers
-                vector<int64_t> dropped(n_all, 0);
-                if (rc_chain == O3DR_OK && chain_ransac)
-                    for (int64_t k = 0; k < n_list; ++k) {
-                        const int32_t st_j = recs[(size_t)pair_list[2 * (size_t)k + 1]].status;
-                        if (st_j == O3DR_CHAIN_ANCHOR || st_j == O3DR_CHAIN_MATCHED)
-                            dropped[(size_t)pair_list[2 * (size_t)k]] += rres[(size_t)k].n_candidates - rres[(size_t)k].n_inliers;
-                    }
-                // --refine_poses: one joint refinement of the cycle's matched frames over the cycle's pairs, the history held
-                o3dr_refine_result rr;
-                memset(&rr, 0, sizeof rr);
-                if (rc_chain == O3DR_OK && refine_poses) {
-                    vector<int32_t> st_all(n_all);
-                    vector<uint8_t> held(n_all, 0);
-                    for (size_t f = 0; f < n_all; ++f) st_all[f] = recs[f].status, held[f] = f < n_hist;
-                    vector<float> refined(16 * n_all);
-                    vector<o3dr_refine_frame> rfr(n_all);
-                    o3dr_refine_params fp;
-                    o3dr_refine_default_params(&fp);
-                    fp.gn_iterations = refine_gn_iterations;
-                    fp.cg_iterations = refine_cg_iterations;
-                    fp.prior_weight = refine_prior_weight;
-                    rc_chain = o3dr_pose_graph_refine(c, chain.desc.data(), chain.off.data(), chain.kp3.data(), (int32_t)n_all, chain_out.data(),
-                                                      st_all.data(), held.data(), chain.prior.data(), pair_list.data(), n_list, &fp,
-                                                      chain_ransac ? &rp : nullptr, refined.data(), rfr.data(), nullptr, &rr, O3DR_MEM_HOST);
-                    if (rc_chain != O3DR_OK) why_chain = string("pose_graph_refine: ") + o3dr_last_error();
-                    else chain_out = refined;  // (a frame that is not free keeps its bytes)
-                }
-                if (rc_chain == O3DR_OK) {
-                    static const char* const names[] = {"ANCHOR", "MATCHED", "TOO_FEW", "DEGENERATE", "RMS"};
-                    chain.poses = chain_out;
-                    n_cloud = 0;
-                    kp_off[0] = 0;
-                    size_t kp_rows = 0;
-                    cout << "\npose chain: " << n_acc << " frames after " << n_hist << ", " << chrono::duration<double>(clk::now() - tc).count()
-                         << " sec" << endl;
-                    if (refine_poses)
-                        cout << "pose graph: edges " << rr.n_edges << " free " << rr.n_free << " energy " << rr.energy_before << " -> "
-                             << rr.energy_after << " gradient " << rr.grad_after << endl;
-                    for (size_t k = 0; k < n_acc; ++k) {
-                        const o3dr_chain_frame& r = recs[n_hist + k];
-                        ImageData& im = acceptedImageDataVec[first_accepted + k];
-                        chain.status.push_back(r.status);
-                        memcpy(im.t_mat_FeatureMatched.data(), &chain_out[16 * (n_hist + k)], 64);
-                        const bool ok = r.status == O3DR_CHAIN_ANCHOR || r.status == O3DR_CHAIN_MATCHED;
-                        cout << im.raw_img_data_ptr->img_num << " pose chain: " << names[r.status] << " pairs " << r.n_pairs_accepted << "/"
-                             << r.n_pairs << " good " << r.n_good << " used " << r.n_used << " rms " << r.rms;
-                        if (chain_ransac) cout << " dropped " << dropped[n_hist + k];
-                        cout << (ok ? "\tAccepted!" : "\tRejected!") << endl;
-                        if (!ok) continue;
-                        // the accepted frames move up in the stacks (m <= k)
-                        const size_t m = n_cloud++;
-                        const size_t r0k = (size_t)(kp_xy.empty() ? 0 : kp_off[k]), r1k = (size_t)(kp_xy.empty() ? 0 : kp_off[k + 1]);
-                        if (m != k) {
-                            memmove(disp_in + m * dsz * (size_t)esz, disp_in + k * dsz * (size_t)esz, dsz * (size_t)esz);
-                            memmove(&bgr[m * csz], &bgr[k * csz], csz);
-                        }
-                        memcpy(&poses[16 * m], im.t_mat_FeatureMatched.data(), 64);
-                        if (!kp_xy.empty()) memmove(&kp_xy[2 * kp_rows], &kp_xy[2 * r0k], (r1k - r0k) * 2 * sizeof(float));
-                        kp_rows += r1k - r0k;
-                        kp_off[m + 1] = (int64_t)kp_rows;
-                    }
-                    if (!kp_xy.empty()) kp_xy.resize(kp_rows * 2);
-                    cout << "Adding Point Cloud number/points: " << n_cloud << " of " << n_acc << " frames" << flush;
-                }
-            }
-            // --multiview_filter / --multiview_fuse: the frames that go into the cloud, with their final poses, vote on each
-            // other's pixels; the fusion's float64 levels then go into the accumulate call in place of the 8-bit images
-            const uint8_t* acc_in = disp_in;
-            int64_t acc_esz = esz;
-            vector<double> fused;
-            if ((multiview_filter || multiview_fuse) && rc_orb == O3DR_OK && rc_fit == O3DR_OK && rc_chain == O3DR_OK && n_cloud > 0) {
-                const auto tm = clk::now();
-                o3dr_multiview_params mp;
-                o3dr_multiview_default_params(&mp);
-                mp.tolerance = mv_tolerance;
-                mp.min_support = mv_min_support;
-                mp.max_violations = mv_max_violations;
-                const int32_t nk = (int32_t)mv_neighbors;
-                vector<int32_t> nb((size_t)n_cloud * (size_t)(nk > 0 && nk <= O3DR_MULTIVIEW_MAX_NEIGHBORS ? nk : 0) + 1);
-                vector<uint8_t> kept(multiview_fuse ? 0 : dsz * n_cloud);
-                vector<o3dr_multiview_info> mi(n_cloud);
-                vector<o3dr_multiview_fuse_info> fi(multiview_fuse ? n_cloud : 0);
-                if (multiview_fuse) fused.resize(dsz * n_cloud);
-                rc_chain = o3dr_nearby_frames(poses.data(), (int32_t)n_cloud, nk, mv_max_distance, nb.data());
-                if (rc_chain == O3DR_OK && multiview_fuse)
-                    rc_chain = o3dr_multiview_fuse(c, disp.data(), (int64_t)dsz, cols, rows, cols, (int32_t)n_cloud, poses.data(), nb.data(), nk,
-                                                   &mp, fused.data(), nullptr, nullptr, nullptr, fi.data(), O3DR_MEM_HOST);
-                else if (rc_chain == O3DR_OK)
-                    rc_chain = o3dr_multiview_filter(c, disp.data(), (int64_t)dsz, cols, rows, cols, (int32_t)n_cloud, poses.data(), nb.data(), nk,
-                                                     &mp, kept.data(), nullptr, nullptr, mi.data(), O3DR_MEM_HOST);
-                if (rc_chain != O3DR_OK) why_chain = string(multiview_fuse ? "multiview_fuse: " : "multiview_filter: ") + o3dr_last_error();
-                else {
-                    int64_t n_pairs = 0, n_valid = 0, n_kept = 0, n_nosup = 0, n_viol = 0, n_votes = 0, n_fused = 0;
-                    for (size_t e = 0; e < (size_t)n_cloud * (size_t)nk; ++e) n_pairs += nb[e] >= 0;
-                    if (multiview_fuse) {
-                        for (size_t f = 0; f < n_cloud; ++f) mi[f] = fi[f].filter, n_votes += fi[f].n_votes, n_fused += fi[f].n_fused;
-                        acc_in = (const uint8_t*)fused.data();
-                        acc_esz = 8;
-                        disparity_f64 = true;  // (for the accumulate call alone: restored after it)
-                        push_params(c);
-                    } else {
-                        memcpy(disp.data(), kept.data(), kept.size());
-                    }
-                    for (const o3dr_multiview_info& m : mi)
-                        n_valid += m.n_valid, n_kept += m.n_kept, n_nosup += m.n_no_support, n_viol += m.n_violated;
-                    cout << "\nmultiview " << (multiview_fuse ? "fuse: " : "filter: ") << n_cloud << " frames, " << n_pairs << " pairs, kept "
-                         << n_kept << " of " << n_valid << " pixels (" << n_nosup << " without support, " << n_viol << " violated), ";
-                    if (multiview_fuse) cout << n_votes << " votes into " << n_fused << " pixels, ";
-                    cout << chrono::duration<double>(clk::now() - tm).count() << " sec" << flush;
-                }
-            }
-            const int rc_acc = rc_orb != O3DR_OK ? rc_orb : rc_fit != O3DR_OK ? rc_fit : rc_chain != O3DR_OK ? rc_chain : n_cloud == 0 ? O3DR_OK
-                                                 : o3dr_accumulate_frames_kp(c, acc_in, acc_esz * (int64_t)dsz, acc_esz * cols, bgr.data(), (int64_t)csz,
-                                                                             3 * (int64_t)cols, rows, cols, poses.data(), (int32_t)n_cloud,
-                                                                             kp_xy.empty() ? nullptr : kp_xy.data(),
-                                                                             kp_xy.empty() ? nullptr : kp_off.data(), O3DR_MEM_HOST);
-            const string why_acc = rc_orb != O3DR_OK ? "orb_detect: " + why_orb : rc_fit != O3DR_OK ? "plane_fit_disparity: " + why_fit
-                                   : rc_chain != O3DR_OK ? why_chain : (rc_acc != O3DR_OK ? o3dr_last_error() : "");
-            if (use_segment_labels || acc_in != disp_in) {
-                disparity_f64 = false;
-                push_params(c);
-            }
-            if (reg_disp) (void)o3dr_host_unregister(disp.data());  // (only what was registered; also on the error path)
-            if (reg_bgr) (void)o3dr_host_unregister(bgr.data());
-            if (rc_acc != O3DR_OK) throw runtime_error("accumulate_frames: " + why_acc);
-        }
-        chk(o3dr_ctx_synchronize(c), "synchronize");
-        const double dt = chrono::duration<double>(clk::now() - t3).count();
-        cout << "\n\nPoint Cloud Creation time: " << dt << " sec" << endl;  // pose.cpp:429-431
-        if (log_file.is_open()) log_file << "Point Cloud Creation time:\t\t\t" << dt << " sec" << endl;
-        if (preview && !sharded_path && !reference_fanout) {
-            // the reference's preview thread merges a copy of cloud_big after every cycle (pose.cpp:437-448, 638-674); here
-            // only the points this cycle appended are folded into the merge kept on the device
-            int64_t n_prev = 0;
-            uint32_t st = 0;
-            chk(o3dr_finalize_incremental(c, nullptr, 0, &n_prev, &st, O3DR_MEM_HOST), "finalize_incremental");
-            PointCloud::Ptr prev(new PointCloud());
-            prev->points.resize((size_t)(n_prev > 0 ? n_prev : 1));
-            chk(o3dr_finalize_incremental(c, prev->points.data(), n_prev > 0 ? n_prev : 1, &n_prev, &st, O3DR_MEM_HOST),
-                "finalize_incremental");
-            prev->points.resize((size_t)n_prev);
-            string ppath = outputPrefix + "preview.ply";
-            save_pt_cloud_to_PLY_File(prev, ppath);
-            cout << "preview: " << n_prev << " points" << endl;
-        }
-        cycle++;
-    }
-    const double total = chrono::duration<double>(clk::now() - app_start).count();
-    cout << "\nFinished Pose Estimation, total time: " << total << " sec at " << acceptedImageDataVec.size() / total << " fps" << endl;
+// ------------------------------------------------------------------------------------------------
+// the reconstruction run: every cycle accepts frames, stacks the accepted ones in one batch and takes
+// the batch through the stages below into cloud_big (pose.cpp:162-434)
+// ------------------------------------------------------------------------------------------------
+typedef chrono::steady_clock clk;
 
-    // ---- final merge + save (pose.cpp:527-540) ------------------------------------------------------
+// The frames [first, last) of the accepted list, stacked as the batched calls take them.  While the batch lives its two
+// image stacks are page-locked, so that they cross PCIe by DMA (best effort: pageable memory works too, through the
+// runtime's bounce buffers; only what was registered is released).  The stacks never change size.
+struct Pose::FrameBatch {
+    size_t first, n;          // the batch's first frame in the accepted list, the frames stacked
+    size_t n_cloud;           // the frames that go into the cloud, the first n_cloud of the stacks: n until the pose chain drops some
+    size_t dsz = 0, csz = 0;  // bytes of one 8-bit disparity image and of one colour image
+    vector<uint8_t> disp, bgr;
+    vector<float> poses, kp_xy;
+    vector<int64_t> kp_off;
+    bool reg_disp = false, reg_bgr = false;
+
+    FrameBatch(const vector<ImageData>& accepted, size_t first_, size_t last) : first(first_), n(last - first_), n_cloud(n), poses(16 * n), kp_off(n + 1, 0)
+    {
+        const RawImageData& r0 = *accepted[first].raw_img_data_ptr;
+        dsz = r0.disparity_image.data.size(), csz = r0.rgb_image.data.size();
+        disp.resize(dsz * n), bgr.resize(csz * n);
+        for (size_t k = 0; k < n; ++k) {
+            const ImageData& im = accepted[first + k];
+            memcpy(&disp[k * dsz], im.raw_img_data_ptr->disparity_image.data.data(), dsz);
+            memcpy(&bgr[k * csz], im.raw_img_data_ptr->rgb_image.data.data(), csz);
+            memcpy(&poses[16 * k], im.t_mat_FeatureMatched.data(), 64);
+            kp_xy.insert(kp_xy.end(), im.keypoints_xy.begin(), im.keypoints_xy.end());
+            kp_off[k + 1] = (int64_t)(kp_xy.size() / 2);
+        }
+        reg_disp = o3dr_host_register(disp.data(), (int64_t)disp.size()) == O3DR_OK;
+        reg_bgr = o3dr_host_register(bgr.data(), (int64_t)bgr.size()) == O3DR_OK;
+    }
+    FrameBatch(const FrameBatch&) = delete;
+    ~FrameBatch()
+    {
+        if (reg_disp) (void)o3dr_host_unregister(disp.data());
+        if (reg_bgr) (void)o3dr_host_unregister(bgr.data());
+    }
+};
+
+// disparity_f64 on, and pushed, while this lives: the accumulate call then takes float64 images (the plane fits, the fused
+// levels).  Off and pushed again at the end of the scope, on the error path too.
+struct Pose::F64Images {
+    Pose& p;
+    o3dr_ctx* c;
+    F64Images(Pose& p_, o3dr_ctx* c_) : p(p_), c(c_)
+    {
+        p.disparity_f64 = true;
+        p.push_params(c);
+    }
+    ~F64Images()
+    {
+        p.disparity_f64 = false;
+        try {
+            p.push_params(c);  // (the values that went through at the start of the run)
+        } catch (...) {
+        }
+    }
+};
+
+// What a cycle's stages hand on to the later ones
+struct Pose::CycleState {
+    vector<float> orb_xy;           // stage 1: the batch's ORB keypoints, their descriptors (--feature_poses) and row offsets per frame
+    vector<uint8_t> orb_desc;
+    vector<int64_t> orb_off;
+    vector<double> fitted, fused;   // the plane-fitted images (stage 2), the fused levels (stage 5)
+    uint8_t* disp_in = nullptr;     // the disparity stack the pose chain reads and the compaction moves, esz bytes per pixel
+    const uint8_t* acc_in = nullptr;  // the one the accumulate call takes, acc_esz bytes per pixel
+    int64_t esz = 1, acc_esz = 1;
+    vector<o3dr_chain_frame> recs;  // stage 3 for stage 4: the chain's records, poses and dropped counts, history + batch
+    vector<float> chain_poses;
+    vector<int64_t> dropped;
+    optional<F64Images> f64;        // (last: restored before anything above goes)
+};
+
+// A stage's failed library call ends the cycle: "accumulate_frames: <stage><library message>".  Called before any guard makes
+// a library call of its own (o3dr_host_unregister, o3dr_set_params), which may overwrite o3dr_last_error().
+static void stage_chk(int rc, const char* stage)
+{
+    if (rc != O3DR_OK) throw runtime_error(string("accumulate_frames: ") + stage + o3dr_last_error());
+}
+
+// Stage 1, --gpu_keypoints and / or --feature_poses: the batch's ORB features from one extractor call.  With --gpu_keypoints,
+// jump_pixels != 1 and no --keypoints_dir they are the batch's keypoint lists, instead of files (the list the reference's
+// ORB stage leaves in features.keypoints, pose_functions.cpp:1057-1061).
+void Pose::orb_stage(o3dr_ctx* c, FrameBatch& b, CycleState& s)
+{
+    const bool orb_for_cloud = gpu_keypoints && jump_pixels != 1 && keypointsPrefix.empty();
+    if (!orb_for_cloud && !feature_poses) return;
+    const o3dr_orb_params prm = orb_params();
+    const int64_t cap = (int64_t)b.n * (prm.n_features > 0 ? prm.n_features : 1);
+    s.orb_xy.assign((size_t)cap * 2, 0.f);
+    if (feature_poses) s.orb_desc.assign((size_t)cap * 32, 0);
+    s.orb_off.assign(b.n + 1, 0);
+    int64_t n_kp = 0;
+    const auto tk = clk::now();
+    const int rc = o3dr_orb_detect(c, b.bgr.data(), (int64_t)b.csz, 3 * (int64_t)cols, rows, cols, (int32_t)b.n, &prm, nullptr, s.orb_xy.data(),
+                                   feature_poses ? s.orb_desc.data() : nullptr, s.orb_off.data(), nullptr, cap, &n_kp, O3DR_MEM_HOST);
+    cout << "\nORB keypoints: " << n_kp << " in " << b.n << " frames, " << chrono::duration<double>(clk::now() - tk).count() << " sec"
+         << flush;  // (of a failed call too; printing is no library call)
+    stage_chk(rc, "orb_detect: ");
+    s.orb_xy.resize((size_t)n_kp * 2);
+    s.orb_desc.resize(feature_poses ? (size_t)n_kp * 32 : 0);
+    if (orb_for_cloud) {
+        b.kp_xy = s.orb_xy;
+        b.kp_off = s.orb_off;
+    }
+}
+
+// Stage 2, --use_segment_labels: the batch's 8-bit disparities become plane-fitted CV_64F images, which every later stage
+// takes in their place
+void Pose::plane_fit_stage(o3dr_ctx* c, FrameBatch& b, CycleState& s)
+{
+    if (!use_segment_labels) return;
+    vector<uint16_t> lab(b.dsz * b.n);
+    uint32_t max_label = 0;
+    for (size_t k = 0; k < b.n; ++k) {
+        const Image16& li = acceptedImageDataVec[b.first + k].raw_img_data_ptr->label_image;
+        memcpy(&lab[k * b.dsz], li.data.data(), b.dsz * sizeof(uint16_t));
+        for (uint16_t v : li.data) max_label = max<uint32_t>(max_label, v);
+    }
+    s.fitted.resize(b.dsz * b.n);
+    o3dr_plane_disp_params pp;
+    o3dr_plane_disp_default_params(&pp);
+    pp.min_pixels = plane_min_pixels;
+    pp.max_mse = plane_max_mse;
+    const auto tf = clk::now();
+    const int rc = o3dr_plane_fit_disparity(c, b.disp.data(), cols, (int64_t)b.dsz, lab.data(), 2, 2 * (int64_t)cols, 2 * (int64_t)b.dsz,
+                                            (int32_t)max_label + 1, rows, cols, (int32_t)b.n, &pp, s.fitted.data(), nullptr, nullptr,
+                                            O3DR_MEM_HOST);
+    cout << "\nplane-fitted disparity: " << b.n << " frames, " << max_label + 1 << " labels, "
+         << chrono::duration<double>(clk::now() - tf).count() << " sec" << flush;  // (of a failed call too)
+    stage_chk(rc, "plane_fit_disparity: ");
+    s.f64.emplace(*this, c);
+    s.acc_in = s.disp_in = (uint8_t*)s.fitted.data();
+    s.acc_esz = s.esz = 8;
+}
+
+// Stage 3, --feature_poses: the batch's frames through the chain, the frames of the cycles before as its history; with
+// --refine_poses then one joint refinement of the batch's matched frames over the batch's pairs, the history held
+void Pose::pose_chain_stage(o3dr_ctx* c, FrameBatch& b, CycleState& s)
+{
+    if (!feature_poses) return;
+    const auto tc = clk::now();
+    const size_t n_hist = chain.status.size(), n_all = n_hist + b.n, n_kp = s.orb_xy.size() / 2;
+    vector<o3dr_point> kp3(n_kp ? n_kp : 1);
+    int64_t n3 = 0;
+    stage_chk(o3dr_keypoints_3d(c, s.disp_in, s.esz * (int64_t)b.dsz, s.esz * cols, nullptr, 0, 0, rows, cols, nullptr, (int32_t)b.n,
+                                s.orb_xy.data(), s.orb_off.data(), kp3.data(), (int64_t)kp3.size(), &n3, O3DR_MEM_HOST),
+              "keypoints_3d: ");
+    const int64_t base = chain.off.back();
+    chain.desc.insert(chain.desc.end(), s.orb_desc.begin(), s.orb_desc.end());
+    chain.kp3.insert(chain.kp3.end(), kp3.begin(), kp3.begin() + (ptrdiff_t)n_kp);
+    for (size_t k = 0; k < b.n; ++k) {
+        chain.off.push_back(base + s.orb_off[k + 1]);
+        const Matrix4& m = acceptedImageDataVec[b.first + k].t_mat_MAVLink;
+        chain.prior.insert(chain.prior.end(), m.begin(), m.end());
+    }
+    s.chain_poses.resize(16 * n_all);
+    s.recs.resize(n_all);
+    o3dr_chain_params cp;
+    o3dr_chain_default_params(&cp);
+    cp.dist_nearby = dist_nearby;
+    cp.range_width = range_width;
+    cp.min_matches = chain_min_matches;
+    cp.max_rms = chain_max_rms;
+    // --chain_ransac_threshold: the pair list and one RANSAC record per pair come back too, for the dropped counts
+    o3dr_ransac_params rp;
+    o3dr_ransac_default_params(&rp);
+    rp.threshold = chain_ransac_threshold;
+    rp.iterations = chain_ransac_iterations;
+    rp.seed = chain_ransac_seed;
+    const bool want_pairs = chain_ransac || refine_poses;
+    const size_t pair_cap = want_pairs ? b.n * (size_t)O3DR_CHAIN_MAX_RANGE : 0;
+    vector<int32_t> pair_list(2 * pair_cap + 2);
+    vector<o3dr_ransac_result> rres(pair_cap + 1);
+    int64_t n_list = 0;
+    stage_chk(o3dr_pose_chain_robust(c, chain.desc.data(), chain.off.data(), chain.kp3.data(), chain.prior.data(), (int32_t)n_all,
+                                     (int32_t)n_hist, chain.poses.data(), chain.status.data(), &cp, s.chain_poses.data(), s.recs.data(),
+                                     want_pairs ? pair_list.data() : nullptr, (int64_t)pair_cap, &n_list, O3DR_MEM_HOST,
+                                     chain_ransac ? &rp : nullptr, chain_ransac ? rres.data() : nullptr),
+              "pose_chain: ");
+    // a frame's dropped slots: over its pairs with an accepted train frame, the candidates that are no inliers
+    s.dropped.assign(n_all, 0);
+    for (int64_t k = 0; chain_ransac && k < n_list; ++k) {
+        const int32_t st_j = s.recs[(size_t)pair_list[2 * (size_t)k + 1]].status;
+        if (st_j == O3DR_CHAIN_ANCHOR || st_j == O3DR_CHAIN_MATCHED)
+            s.dropped[(size_t)pair_list[2 * (size_t)k]] += rres[(size_t)k].n_candidates - rres[(size_t)k].n_inliers;
+    }
+    o3dr_refine_result rr = {};
+    if (refine_poses) {
+        vector<int32_t> st_all(n_all);
+        vector<uint8_t> held(n_all, 0);
+        for (size_t f = 0; f < n_all; ++f) st_all[f] = s.recs[f].status, held[f] = f < n_hist;
+        vector<float> refined(16 * n_all);
+        vector<o3dr_refine_frame> rfr(n_all);
+        o3dr_refine_params fp;
+        o3dr_refine_default_params(&fp);
+        fp.gn_iterations = refine_gn_iterations;
+        fp.cg_iterations = refine_cg_iterations;
+        fp.prior_weight = refine_prior_weight;
+        stage_chk(o3dr_pose_graph_refine(c, chain.desc.data(), chain.off.data(), chain.kp3.data(), (int32_t)n_all, s.chain_poses.data(),
+                                         st_all.data(), held.data(), chain.prior.data(), pair_list.data(), n_list, &fp,
+                                         chain_ransac ? &rp : nullptr, refined.data(), rfr.data(), nullptr, &rr, O3DR_MEM_HOST),
+                  "pose_graph_refine: ");
+        s.chain_poses = refined;  // (a frame that is not free keeps its bytes)
+    }
+    chain.poses = s.chain_poses;
+    cout << "\npose chain: " << b.n << " frames after " << n_hist << ", " << chrono::duration<double>(clk::now() - tc).count() << " sec" << endl;
+    if (refine_poses)
+        cout << "pose graph: edges " << rr.n_edges << " free " << rr.n_free << " energy " << rr.energy_before << " -> " << rr.energy_after
+             << " gradient " << rr.grad_after << endl;
+}
+
+// Stage 4, --feature_poses: one status line per frame; a matched frame takes the chain's pose, a rejected one leaves the
+// stacks: the accepted frames move up in place (m <= k)
+void Pose::keep_chained_frames(FrameBatch& b, CycleState& s)
+{
+    if (!feature_poses) return;
+    const size_t n_hist = chain.status.size(), fsz = b.dsz * (size_t)s.esz;
+    size_t kp_rows = 0;
+    b.n_cloud = 0;
+    b.kp_off[0] = 0;
+    for (size_t k = 0; k < b.n; ++k) {
+        const o3dr_chain_frame& r = s.recs[n_hist + k];
+        ImageData& im = acceptedImageDataVec[b.first + k];
+        chain.status.push_back(r.status);
+        memcpy(im.t_mat_FeatureMatched.data(), &s.chain_poses[16 * (n_hist + k)], 64);
+        const bool ok = r.status == O3DR_CHAIN_ANCHOR || r.status == O3DR_CHAIN_MATCHED;
+        cout << im.raw_img_data_ptr->img_num << " pose chain: " << kChainStatusName[r.status] << " pairs " << r.n_pairs_accepted << "/"
+             << r.n_pairs << " good " << r.n_good << " used " << r.n_used << " rms " << r.rms;
+        if (chain_ransac) cout << " dropped " << s.dropped[n_hist + k];
+        cout << (ok ? "\tAccepted!" : "\tRejected!") << endl;
+        if (!ok) continue;
+        const size_t m = b.n_cloud++;
+        const size_t r0k = (size_t)(b.kp_xy.empty() ? 0 : b.kp_off[k]), r1k = (size_t)(b.kp_xy.empty() ? 0 : b.kp_off[k + 1]);
+        if (m != k) {
+            memmove(s.disp_in + m * fsz, s.disp_in + k * fsz, fsz);
+            memmove(&b.bgr[m * b.csz], &b.bgr[k * b.csz], b.csz);
+        }
+        memcpy(&b.poses[16 * m], im.t_mat_FeatureMatched.data(), 64);
+        if (!b.kp_xy.empty()) memmove(&b.kp_xy[2 * kp_rows], &b.kp_xy[2 * r0k], (r1k - r0k) * 2 * sizeof(float));
+        kp_rows += r1k - r0k;
+        b.kp_off[m + 1] = (int64_t)kp_rows;
+    }
+    if (!b.kp_xy.empty()) b.kp_xy.resize(kp_rows * 2);
+    cout << "Adding Point Cloud number/points: " << b.n_cloud << " of " << b.n << " frames" << flush;
+}
+
+// Stage 5, --multiview_filter / --multiview_fuse: the frames that go into the cloud, with their final poses, vote on each
+// other's pixels; the fusion's float64 levels then go into the accumulate call in place of the 8-bit images
+void Pose::multiview_stage(o3dr_ctx* c, FrameBatch& b, CycleState& s)
+{
+    if (!(multiview_filter || multiview_fuse) || b.n_cloud == 0) return;
+    const char* const stage = multiview_fuse ? "multiview_fuse: " : "multiview_filter: ";
+    const auto tm = clk::now();
+    const size_t n = b.n_cloud;
+    o3dr_multiview_params mp;
+    o3dr_multiview_default_params(&mp);
+    mp.tolerance = mv_tolerance;
+    mp.min_support = mv_min_support;
+    mp.max_violations = mv_max_violations;
+    const int32_t nk = (int32_t)mv_neighbors;
+    vector<int32_t> nb(n * (size_t)(nk > 0 && nk <= O3DR_MULTIVIEW_MAX_NEIGHBORS ? nk : 0) + 1);
+    vector<o3dr_multiview_info> mi(n);
+    int64_t n_pairs = 0, n_valid = 0, n_kept = 0, n_nosup = 0, n_viol = 0, n_votes = 0, n_fused = 0;
+    stage_chk(o3dr_nearby_frames(b.poses.data(), (int32_t)n, nk, mv_max_distance, nb.data()), stage);
+    if (multiview_fuse) {
+        vector<o3dr_multiview_fuse_info> fi(n);
+        s.fused.resize(b.dsz * n);
+        stage_chk(o3dr_multiview_fuse(c, b.disp.data(), (int64_t)b.dsz, cols, rows, cols, (int32_t)n, b.poses.data(), nb.data(), nk, &mp,
+                                      s.fused.data(), nullptr, nullptr, nullptr, fi.data(), O3DR_MEM_HOST),
+                  stage);
+        for (size_t f = 0; f < n; ++f) mi[f] = fi[f].filter, n_votes += fi[f].n_votes, n_fused += fi[f].n_fused;
+        s.acc_in = (const uint8_t*)s.fused.data();
+        s.acc_esz = 8;
+        s.f64.emplace(*this, c);
+    } else {
+        vector<uint8_t> kept(b.dsz * n);
+        stage_chk(o3dr_multiview_filter(c, b.disp.data(), (int64_t)b.dsz, cols, rows, cols, (int32_t)n, b.poses.data(), nb.data(), nk, &mp,
+                                        kept.data(), nullptr, nullptr, mi.data(), O3DR_MEM_HOST),
+                  stage);
+        memcpy(b.disp.data(), kept.data(), kept.size());
+    }
+    for (size_t e = 0; e < n * (size_t)nk; ++e) n_pairs += nb[e] >= 0;
+    for (const o3dr_multiview_info& m : mi) n_valid += m.n_valid, n_kept += m.n_kept, n_nosup += m.n_no_support, n_viol += m.n_violated;
+    cout << "\nmultiview " << (multiview_fuse ? "fuse: " : "filter: ") << n << " frames, " << n_pairs << " pairs, kept " << n_kept << " of "
+         << n_valid << " pixels (" << n_nosup << " without support, " << n_viol << " violated), ";
+    if (multiview_fuse) cout << n_votes << " votes into " << n_fused << " pixels, ";
+    cout << chrono::duration<double>(clk::now() - tm).count() << " sec" << flush;
+}
+
+// One cycle's accepted frames [first, last) into cloud_big.  MI355X-native form of the reference's loop over the frames
+// (pose.cpp:365-434): the whole cycle in one batched call, cloud_big in HBM.
+void Pose::accumulate_cycle(o3dr_ctx* c, size_t first, size_t last)
+{
+    FrameBatch b(acceptedImageDataVec, first, last);
+    for (size_t k = first; k < last && !feature_poses; ++k) cout << " " << acceptedImageDataVec[k].raw_img_data_ptr->img_num << flush;
+    CycleState s;  // (goes before the batch: disparity_f64 is restored, then the stacks are unpinned)
+    s.acc_in = s.disp_in = b.disp.data();
+    orb_stage(c, b, s);
+    plane_fit_stage(c, b, s);
+    pose_chain_stage(c, b, s);
+    keep_chained_frames(b, s);
+    multiview_stage(c, b, s);
+    if (b.n_cloud == 0) return;
+    stage_chk(o3dr_accumulate_frames_kp(c, s.acc_in, s.acc_esz * (int64_t)b.dsz, s.acc_esz * cols, b.bgr.data(), (int64_t)b.csz,
+                                        3 * (int64_t)cols, rows, cols, b.poses.data(), (int32_t)b.n_cloud,
+                                        b.kp_xy.empty() ? nullptr : b.kp_xy.data(), b.kp_xy.empty() ? nullptr : b.kp_off.data(), O3DR_MEM_HOST),
+              "");
+}
+
+// The accept loop of one cycle (pose.cpp:162-255): up to cycle_len raw frames from current_idx on that can be read and pass
+// the variance gate join the accepted list, with their recorded pose and, under --keypoints_dir, their keypoint file
+void Pose::accept_cycle(int& current_idx, int cycle_len)
+{
+    const int last_idx = (int)rawImageDataVec.size() - 1;
+    for (int images_in_cycle = 0; images_in_cycle < cycle_len && current_idx <= last_idx; current_idx++) {
+        RawImageData& r = rawImageDataVec[current_idx];
+        if (r.rgb_image.empty()) { cout << r.img_num << " could not read rgb image. \tRejected!" << endl; continue; }
+        if (r.disparity_image.empty()) { cout << r.img_num << " could not read disparity image. \tRejected!" << endl; continue; }
+        if (use_segment_labels && r.label_image.empty()) { cout << r.img_num << " could not read segment label image. \tRejected!" << endl; continue; }
+        const double var = getVariance(r.disparity_image);
+        cout << r.img_num << " " << flush;
+        if (var > 5) { cout << " disp_img_var = " << var << " > 5.\tRejected!" << endl; continue; }
+        ImageData d;
+        d.raw_img_data_ptr = &r;
+        d.t_mat_MAVLink = generateTmat(current_idx);
+        d.t_mat_FeatureMatched = d.t_mat_MAVLink;  // --only_MAVLink, pose.cpp:238
+        if (!keypointsPrefix.empty()) {
+            // the list the reference's ORB stage would leave in features.keypoints (pose_functions.cpp:1057-1061)
+            ifstream kf(keypointsPrefix + to_string(r.img_num) + ".txt");
+            float kx, ky;
+            while (kf >> kx >> ky) {
+                d.keypoints_xy.push_back(kx);
+                d.keypoints_xy.push_back(ky);
+            }
+        }
+        acceptedImageDataVec.push_back(d);
+        cout << "\tAccepted!" << endl;
+        images_in_cycle++;
+    }
+}
+
+// --reference_fanout, the reference's own structure: batches of <= 7 threads, results appended in frame order
+void Pose::fanout_cycle(size_t first, size_t last, PointCloud& cloud_big_host)
+{
+    for (size_t i0 = first; i0 < last; i0 += 7) {
+        const size_t nb = min<size_t>(7, last - i0);
+        vector<PointCloud::Ptr> clouds(nb);
+        vector<thread> th;
+        for (size_t k = 0; k < nb; ++k) {
+            clouds[k].reset(new PointCloud());
+            th.emplace_back([this, i0, k, &clouds]() { createAndTransformPtCloud((int)(i0 + k), clouds[k]); });
+        }
+        for (thread& t : th) t.join();
+        for (size_t k = 0; k < nb; ++k)
+            cloud_big_host.points.insert(cloud_big_host.points.end(), clouds[k]->points.begin(), clouds[k]->points.end());
+    }
+}
+
+// --preview: the reference's preview thread merges a copy of cloud_big after every cycle (pose.cpp:437-448, 638-674); here
+// only the points this cycle appended are folded into the merge kept on the device
+void Pose::write_preview(o3dr_ctx* c)
+{
+    int64_t n_prev = 0;
+    uint32_t st = 0;
+    chk(o3dr_finalize_incremental(c, nullptr, 0, &n_prev, &st, O3DR_MEM_HOST), "finalize_incremental");
+    PointCloud::Ptr prev(new PointCloud());
+    prev->points.resize((size_t)(n_prev > 0 ? n_prev : 1));
+    chk(o3dr_finalize_incremental(c, prev->points.data(), n_prev > 0 ? n_prev : 1, &n_prev, &st, O3DR_MEM_HOST), "finalize_incremental");
+    prev->points.resize((size_t)n_prev);
+    string ppath = outputPrefix + "preview.ply";
+    save_pt_cloud_to_PLY_File(prev, ppath);
+    cout << "preview: " << n_prev << " points" << endl;
+}
+
+// The final merge and save (pose.cpp:527-540): cloud.ply and, with --orthophoto_out, the map's rasters
+void Pose::merge_and_save(o3dr_ctx* c, PointCloud::Ptr cloud_big_host)
+{
     PointCloud::Ptr cloud_small(new PointCloud());
     if (n_gpus > 1 || partitioned_merge) {
         run_sharded(cloud_small);
@@ -1823,8 +1783,7 @@ void Pose::run_reconstruction()
         if (!dont_downsample) cout << "downsample before saving..." << endl;
         chk(o3dr_finalize(c, cloud_small->points.data(), n_big > 0 ? n_big : 1, &n_small, &st, O3DR_MEM_HOST), "finalize");
         cloud_small->points.resize((size_t)n_small);
-        if (st & O3DR_STATUS_VOXEL_OVERFLOW)
-            cerr << "[pcl::VoxelGrid::applyFilter] Leaf size is too small for the input dataset. Integer indices would overflow." << endl;
+        warn_voxel_overflow(st);
         cout << "cloud_big " << n_big << " points -> cloud " << n_small << " points" << endl;
     }
     cout << "Saving point clouds..." << endl;
@@ -1834,33 +1793,57 @@ void Pose::run_reconstruction()
         write_map_rasters(c, *cloud_small, orthophoto_out + "ortho.png", orthophoto_out + "height.png", orthophoto_out + "shade.png");
 }
 
+void Pose::run_reconstruction()
+{
+    const auto app_start = clk::now();
+    o3dr_ctx* c = ctx_for_this_thread();
+    chk(o3dr_cloud_big_reset(c), "cloud_big_reset");
+    PointCloud::Ptr cloud_big_host(new PointCloud());  // only used by --reference_fanout
+    const int n_raw = (int)rawImageDataVec.size(), cycle_len = seq_len > 0 ? seq_len : n_raw;
+    acceptedImageDataVec.reserve(rawImageDataVec.size());
+    if (!sor && jump_pixels > 0)
+        cout << "NOTE: --sor 0: the per-frame StatisticalOutlierRemoval of the reference (pose_functions.cpp:1673-1686) is OFF;\n"
+                "      the clouds differ from the reference's for the same command line." << endl;
+    const bool sharded_path = n_gpus > 1 || partitioned_merge;
+    if (preview && (sharded_path || reference_fanout))
+        cout << "--preview: not available on the " << (sharded_path ? "--gpus / --partitioned_merge" : "--reference_fanout")
+             << " path" << endl;
+    cout << "\n\nProgram Start!" << endl;
+    for (int current_idx = 0, cycle = 0; current_idx < n_raw; cycle++) {
+        cout << "\nCycle " << cycle << endl;
+        const size_t first = acceptedImageDataVec.size();
+        accept_cycle(current_idx, cycle_len);
+        const size_t last = acceptedImageDataVec.size();
+        // ---- point cloud creation for this cycle (pose.cpp:365-434) -------------------------------
+        const auto t3 = clk::now();
+        cout << "Adding Point Cloud number/points ";
+        // (sharded: the frames go to the GPUs as contiguous blocks of the WHOLE accepted list - global frame order is what the
+        // merge sums in - so the clouds are made after the last cycle, in run_sharded)
+        if (sharded_path) cout << "(deferred: --gpus)";
+        else if (reference_fanout) fanout_cycle(first, last, *cloud_big_host);
+        else if (last > first) accumulate_cycle(c, first, last);
+        chk(o3dr_ctx_synchronize(c), "synchronize");
+        const double dt = chrono::duration<double>(clk::now() - t3).count();
+        cout << "\n\nPoint Cloud Creation time: " << dt << " sec" << endl;  // pose.cpp:429-431
+        if (log_file.is_open()) log_file << "Point Cloud Creation time:\t\t\t" << dt << " sec" << endl;
+        if (preview && !sharded_path && !reference_fanout) write_preview(c);
+    }
+    const double total = chrono::duration<double>(clk::now() - app_start).count();
+    cout << "\nFinished Pose Estimation, total time: " << total << " sec at " << acceptedImageDataVec.size() / total << " fps" << endl;
+    merge_and_save(c, cloud_big_host);
+}
+
 // --gpus N: the fan-out of pose.cpp:392-413 over GPUs instead of threads of one CPU.  Rank g (host thread g, device
 // device_id + g) takes the g-th contiguous block of the accepted frames through the batched call; o3dr_merge_partitioned
 // then exchanges the per-frame voxels by index slice over RCCL, merges every slice on its GPU and gathers the result.
 void Pose::run_sharded(PointCloud::Ptr cloud_small)
 {
-    typedef chrono::steady_clock clk;
     const auto t0 = clk::now();
     const size_t n_acc = acceptedImageDataVec.size();
     if (n_gpus < 1) throw runtime_error("--gpus must be at least 1");
     if (dont_downsample) throw runtime_error("--gpus / --partitioned_merge need the downsampling path (no --dont_downsample)");
     if (n_acc == 0) return;
-    const RawImageData& r0 = *acceptedImageDataVec[0].raw_img_data_ptr;
-    const size_t dsz = r0.disparity_image.data.size(), csz = r0.rgb_image.data.size();
-    vector<uint8_t> disp(dsz * n_acc), bgr(csz * n_acc);
-    vector<float> poses(16 * n_acc), kp_xy;
-    vector<int64_t> kp_off(n_acc + 1, 0);
-    for (size_t k = 0; k < n_acc; ++k) {
-        const ImageData& im = acceptedImageDataVec[k];
-        memcpy(&disp[k * dsz], im.raw_img_data_ptr->disparity_image.data.data(), dsz);
-        memcpy(&bgr[k * csz], im.raw_img_data_ptr->rgb_image.data.data(), csz);
-        memcpy(&poses[16 * k], im.t_mat_FeatureMatched.data(), 64);
-        kp_xy.insert(kp_xy.end(), im.keypoints_xy.begin(), im.keypoints_xy.end());
-        kp_off[k + 1] = (int64_t)(kp_xy.size() / 2);
-    }
-    // (best effort: pageable memory works too, through the runtime's bounce buffers; only what was registered is released)
-    const bool reg_disp = o3dr_host_register(disp.data(), (int64_t)disp.size()) == O3DR_OK;
-    const bool reg_bgr = o3dr_host_register(bgr.data(), (int64_t)bgr.size()) == O3DR_OK;
+    const FrameBatch b(acceptedImageDataVec, 0, n_acc);  // (unpinned on every way out, after the contexts and communicators go)
     const int W = n_gpus;
     vector<int32_t> devs((size_t)W);
     for (int g = 0; g < W; ++g) devs[(size_t)g] = device_id + g;
@@ -1868,7 +1851,7 @@ void Pose::run_sharded(PointCloud::Ptr cloud_small)
     chk(o3dr_comm_init_all(W, devs.data(), comms.data()), "o3dr_comm_init_all");
     // an upper bound of the merged cloud: no more cells than points, no more points than grid candidates + keypoints
     o3dr_ctx* c0 = ctx_for_this_thread();
-    const int64_t cap = o3dr_max_points(c0, rows, cols) * (int64_t)n_acc + kp_off[n_acc] + 1;
+    const int64_t cap = o3dr_max_points(c0, rows, cols) * (int64_t)n_acc + b.kp_off[n_acc] + 1;
     cloud_small->points.resize((size_t)cap);
     vector<string> errors((size_t)W);
     vector<int64_t> n_out((size_t)W, 0), n_total((size_t)W, 0);
@@ -1882,8 +1865,6 @@ void Pose::run_sharded(PointCloud::Ptr cloud_small)
             const string why = o3dr_last_error();
             for (int k = 0; k < g; ++k) (void)o3dr_ctx_destroy(ctxs[(size_t)k]);
             for (int k = 0; k < W; ++k) (void)o3dr_comm_destroy(comms[(size_t)k]);
-            if (reg_disp) (void)o3dr_host_unregister(disp.data());
-            if (reg_bgr) (void)o3dr_host_unregister(bgr.data());
             throw runtime_error("GPU " + to_string(devs[(size_t)g]) + ": o3dr_ctx_create: " + why);
         }
     }
@@ -1894,11 +1875,11 @@ void Pose::run_sharded(PointCloud::Ptr cloud_small)
             try {
                 push_params(c);
                 const size_t base = n_acc / (size_t)W, rem = n_acc % (size_t)W;  // contiguous blocks (dist.shard_range)
-                const size_t a = (size_t)g * base + min<size_t>((size_t)g, rem), b = a + base + ((size_t)g < rem ? 1 : 0);
-                if (b > a)
-                    chk(o3dr_accumulate_frames_kp(c, disp.data() + a * dsz, (int64_t)dsz, cols, bgr.data() + a * csz, (int64_t)csz,
-                                                  3 * (int64_t)cols, rows, cols, poses.data() + 16 * a, (int32_t)(b - a),
-                                                  kp_xy.empty() ? nullptr : kp_xy.data(), kp_xy.empty() ? nullptr : kp_off.data() + a,
+                const size_t a = (size_t)g * base + min<size_t>((size_t)g, rem), z = a + base + ((size_t)g < rem ? 1 : 0);
+                if (z > a)
+                    chk(o3dr_accumulate_frames_kp(c, b.disp.data() + a * b.dsz, (int64_t)b.dsz, cols, b.bgr.data() + a * b.csz, (int64_t)b.csz,
+                                                  3 * (int64_t)cols, rows, cols, b.poses.data() + 16 * a, (int32_t)(z - a),
+                                                  b.kp_xy.empty() ? nullptr : b.kp_xy.data(), b.kp_xy.empty() ? nullptr : b.kp_off.data() + a,
                                                   O3DR_MEM_HOST),
                         "accumulate_frames");
             } catch (const exception& e) {
@@ -1915,13 +1896,10 @@ void Pose::run_sharded(PointCloud::Ptr cloud_small)
     }
     for (thread& t : th) t.join();
     for (int g = 0; g < W; ++g) (void)o3dr_comm_destroy(comms[(size_t)g]);
-    if (reg_disp) (void)o3dr_host_unregister(disp.data());
-    if (reg_bgr) (void)o3dr_host_unregister(bgr.data());
     for (int g = 0; g < W; ++g)
         if (!errors[(size_t)g].empty()) throw runtime_error("GPU " + to_string(devs[(size_t)g]) + ": " + errors[(size_t)g]);
     cloud_small->points.resize((size_t)n_out[0]);
-    if (st[0] & O3DR_STATUS_VOXEL_OVERFLOW)
-        cerr << "[pcl::VoxelGrid::applyFilter] Leaf size is too small for the input dataset. Integer indices would overflow." << endl;
+    warn_voxel_overflow(st[0]);
     const double dt = chrono::duration<double>(clk::now() - t0).count();
     cout << "\n" << W << " GPU(s): cloud_big " << n_total[0] << " points -> cloud " << n_out[0] << " points, " << dt << " sec" << endl;
 }
