@@ -1552,7 +1552,8 @@ int o3dr_profile_reset(o3dr_ctx* ctx);
 /* Synchronises; counters since the last o3dr_profile_reset, for algorithmic-byte accounting:
  * out[0] = sum over voxel grids of (records x radix passes actually run), out[1] = points that entered
  * voxel grids, out[2] = points that left them, out[3] = 0, out[4] = records that entered the sorts (points or runs
- * of points), out[5..7] = 0. */
+ * of points), out[5] = records whose run-head flag the last scatter pass of their sort wrote (in place of the sorted index
+ * and of the run-head pass over it: the point sorts of the voxel grids), out[6..7] = 0. */
 int o3dr_profile_stats(o3dr_ctx* ctx, int64_t out[8]);
 /* device name / arch / CU count of the context's device, for bench headers */
 int o3dr_device_info(o3dr_ctx* ctx, char* name, int32_t name_len, int32_t* cu_count, int64_t* hbm_bytes);

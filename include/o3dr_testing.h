@@ -12,7 +12,9 @@ extern "C" {
 
 /* Test hook for the gather guards: the next o3dr_voxel_grid / o3dr_downsample_pt_cloud / o3dr_finalize of this
  * context finds one of its sorted payloads pointing outside the cloud, as a bookkeeping error upstream would leave it.
- * That call must return O3DR_ERR_INTERNAL with *n_out = 0 (never a GPU fault), and the context stays usable. */
+ * That call must return O3DR_ERR_INTERNAL with *n_out = 0 (never a GPU fault), and the context stays usable.
+ * o3dr_accumulate_frames takes the hook too (frame 0 of its first batch): the call itself is asynchronous and returns
+ * O3DR_OK; the next read of cloud_big or its size returns O3DR_ERR_INTERNAL, until o3dr_cloud_big_reset. */
 int o3dr_test_corrupt_next_gather(o3dr_ctx* ctx);
 
 /* The mean neighbour distances (pcl::StatisticalOutlierRemoval's `distances`, one per input point, input order) the

@@ -161,10 +161,16 @@ struct ScatterLds {
     uint32_t local_base[kMaxRadix];
     uint32_t delta[kMaxRadix];
     uint32_t scan_lds[kScatWaves + 1];
+    // head flags from the last pass (ScatterJob::heads): digits seen in the look-back [0..3], digits that need it [4..7]
+    uint32_t hmask[8];
+    uint32_t lmin;  // ... and the low bits (below the pass's digit) of the part's first input record
 };
 struct ScatterJob {  // per launch, frame and workgroup
     const uint32_t *kin, *vin;
     uint32_t *kout, *vout;
+    uint8_t* heads;          // last pass of a point sort: "this record starts a run", one byte per record at the record's
+                             // output place, instead of kout (nothing else reads a point sort's sorted indices); else nullptr
+    uint32_t low_mask;       // the index bits below this pass's digit
     const uint32_t* hist;    // the frame's scanned histogram rows
     const uint32_t* hist_part;  // ... and the digit counts of the first part of every tile
     int64_t begin, end;      // the records of this workgroup's part of its tile (at most kScatTile)
@@ -196,11 +202,16 @@ typedef uint32_t u32x4_a4_t __attribute__((ext_vector_type(4), aligned(4)));  //
 // the 16 consecutive records of this lane in part `part` of tile `tile` (+ this thread's scanned histogram entry): every
 // global load of the workgroup is issued here, before any LDS work
 __device__ __forceinline__ void scatter_load(const ScatterJob& J, int tile, int part, uint32_t (&key)[kSortRounds],
-                                             uint32_t (&val)[kSortRounds], uint32_t& gstart)
+                                             uint32_t (&val)[kSortRounds], uint32_t& gstart, uint32_t& back)
 {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int64_t lbase = J.begin + (int64_t)w * kSortWaveItems + (int64_t)lane * kSortRounds;
     gstart = 0;
+    back = 0;
+    if (J.heads && w == kScatWaves - 1) {  // the 64 input records just before the part: first step of the look-back
+        const int64_t j = J.begin - kWave + lane;
+        if (j >= 0) back = J.kin[j];
+    }
     if ((int)threadIdx.x < J.bins) {  // where this part's records of digit threadIdx.x go: after those of the parts before it
         gstart = J.hist[hist_at(J.tm, threadIdx.x, tile, J.n_tiles)];
         if (part != 0) gstart += J.hist_part[hist_at(J.tm, threadIdx.x, tile, J.n_tiles)];
@@ -235,8 +246,18 @@ __device__ __forceinline__ void scatter_load(const ScatterJob& J, int tile, int 
     }
 }
 
+// Head flags from the last pass (J.heads != nullptr).  A record of the part starts a run of equal indices iff its
+// predecessor in the OUTPUT differs.  Inside the part's sorted order that is the record before it, unless it is the part's first record of
+// its digit v: then the predecessor is the last record with digit v among the input records before the part, if any.
+// The input is sorted by the low bits (those below this pass's digit) and the part is a contiguous piece of it, so every
+// record before the part has low bits <= Lmin, the low bits of the part's first record; the ones with low bits == Lmin
+// are one contiguous block that ends just before the part.  So the record continues a run iff its low bits are Lmin and
+// a record with digit v stands in that block.  One wave walks the block backwards, 64 records per step, ORing the digits
+// it sees into a 128-bit mask, until the block ends, the frame starts, or every digit that the part's own records with
+// low bits Lmin have is in the mask (a digit forces a long walk only across a gap in which it did not occur: at most
+// 128 reads per record of a block, usually one 256-byte load per workgroup).  No waiting on other workgroups.
 __device__ __forceinline__ void scatter_tile(const ScatterJob& J, ScatterLds& L, const uint32_t (&key)[kSortRounds],
-                                             const uint32_t (&val)[kSortRounds], uint32_t gstart)
+                                             const uint32_t (&val)[kSortRounds], uint32_t gstart, uint32_t back)
 {
     uint32_t* smem = L.smem;
     uint32_t* stage = L.smem;  // overlays the counters once every record knows its position
@@ -246,7 +267,13 @@ __device__ __forceinline__ void scatter_tile(const ScatterJob& J, ScatterLds& L,
     const int shift = J.shift, bins = J.bins;
     const uint32_t dmask = J.dmask;
     for (int i = threadIdx.x; i < kRankWords; i += kScatThreads) smem[i] = 0;
+    if (J.heads) {
+        if (threadIdx.x < 8) L.hmask[threadIdx.x] = 0;
+        if (threadIdx.x == 0) L.lmin = key[0] & J.low_mask;  // (thread 0 holds the part's first record)
+    }
     __syncthreads();
+    const volatile uint32_t* hmask = L.hmask;
+    const uint32_t lmin = J.heads ? L.lmin : 0u;
 
     // ---- A. own-lane ranks: four lanes share a dword, 7 bits each (a lane has at most 16 records of a digit)
     uint32_t* cw = smem + w * kCntWords;
@@ -260,6 +287,9 @@ __device__ __forceinline__ void scatter_tile(const ScatterJob& J, ScatterLds& L,
             const uint32_t dgt = (key[r] >> shift) & dmask;
             const uint32_t old = atomicAdd(&cw[dgt * kCntStride + quad], 1u << fsh);
             own[r] = (old >> fsh) & 127u;
+            // (the digits whose first record of the part may continue a run from before the part)
+            if (J.heads && (key[r] & J.low_mask) == lmin && !((hmask[4 + (dgt >> 5)] >> (dgt & 31u)) & 1u))
+                atomicOr(&L.hmask[4 + (dgt >> 5)], 1u << (dgt & 31u));
         }
     }
     __builtin_amdgcn_wave_barrier();
@@ -283,6 +313,25 @@ __device__ __forceinline__ void scatter_tile(const ScatterJob& J, ScatterLds& L,
         }
     }
     __syncthreads();
+    if (J.heads && w == kScatWaves - 1) {  // the look-back (see above); `back` = input records [J.begin - 64, J.begin)
+        int64_t j0 = J.begin - kWave;
+        uint32_t kb = back;
+        for (;;) {
+            const bool in = j0 + lane >= 0 && (kb & J.low_mask) == lmin;
+            if (in) {
+                const uint32_t dgt = (kb >> shift) & dmask;
+                atomicOr(&L.hmask[dgt >> 5], 1u << (dgt & 31u));
+            }
+            __builtin_amdgcn_wave_barrier();
+            if (__ballot(in) != ~0ull || j0 <= 0) break;  // the block ends inside these 64, or they start the frame
+            uint32_t miss = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) miss |= hmask[4 + q] & ~hmask[q];
+            if (miss == 0u) break;
+            j0 -= kWave;
+            kb = j0 + lane >= 0 ? J.kin[j0 + lane] : 0u;
+        }
+    }
 
     // ---- 2. one digit per thread: wave prefixes, part total, local start, global delta
     uint32_t tot = 0;
@@ -330,9 +379,20 @@ __device__ __forceinline__ void scatter_tile(const ScatterJob& J, ScatterLds& L,
         const uint32_t p = r * kScatThreads + threadIdx.x;
         if (p < cnt) {
             const uint32_t k = stage[p];
-            const uint32_t d = p + L.delta[(k >> shift) & dmask];
-            J.kout[d] = k;
+            const uint32_t dgt = (k >> shift) & dmask;
+            const uint32_t d = p + L.delta[dgt];
             J.vout[d] = stage_v[p];
+            if (J.heads) {
+                // (consecutive lanes hold consecutive places of a digit run: byte stores to consecutive addresses)
+                bool head;
+                if (p != L.local_base[dgt])
+                    head = k != stage[p - 1];
+                else
+                    head = !((k & J.low_mask) == lmin && ((hmask[dgt >> 5] >> (dgt & 31u)) & 1u));
+                J.heads[d] = head ? 1 : 0;
+            } else {
+                J.kout[d] = k;
+            }
         }
     }
 }
@@ -350,7 +410,8 @@ __global__ __launch_bounds__(kScatThreads) void k_radix_scatter_lane(uint32_t* _
                                                                      int n_tiles, const uint32_t* __restrict__ hist_scanned,
                                                                      const uint32_t* __restrict__ hist_part, int tm,
                                                                      const uint32_t* __restrict__ emit_tile_off,
-                                                                     int n_emit_tiles)
+                                                                     int n_emit_tiles, uint8_t* __restrict__ side,
+                                                                     int64_t side_stride)
 {
     __shared__ ScatterLds L;
     const int f = blockIdx.y;
@@ -382,7 +443,10 @@ __global__ __launch_bounds__(kScatThreads) void k_radix_scatter_lane(uint32_t* _
     J.pass = pass;
     J.n_tiles = n_tiles;
     J.tm = tm != 0;
-    uint32_t key0[kSortRounds], val0[kSortRounds], g0;
-    scatter_load(J, tile, part, key0, val0, g0);
-    scatter_tile(J, L, key0, val0, g0);
+    // side (point sorts in launch_voxel_grid): the last pass leaves the run-head flag of every record, for k_side_heads
+    J.heads = (side && pass + 1 == (int)g.passes) ? side + (int64_t)f * side_stride : nullptr;
+    J.low_mask = (1u << J.shift) - 1u;
+    uint32_t key0[kSortRounds], val0[kSortRounds], g0, back;
+    scatter_load(J, tile, part, key0, val0, g0, back);
+    scatter_tile(J, L, key0, val0, g0, back);
 }

@@ -16,13 +16,14 @@ constexpr int kHeadWaves = 4;  // segment tiles per workgroup of k_run_heads
 __global__ __launch_bounds__(kHeadWaves * kWave) void k_run_heads(const uint32_t* __restrict__ keys0, const uint32_t* __restrict__ keys1,
                                                                   int64_t cap, const VoxelGeom* __restrict__ geom, int n_tiles,
                                                                   uint32_t* __restrict__ seg_cnt, int buf_sel,
-                                                                  uint8_t* __restrict__ head_bits)
+                                                                  uint8_t* __restrict__ head_bits, int side_heads)
 {
     static_assert(kSegTile == 16 * kWave, "16 records per lane");
     const int f = blockIdx.y, lane = threadIdx.x & 63;
     const int tile = blockIdx.x * kHeadWaves + (threadIdx.x >> 6);
     const VoxelGeom g = geom[f];
     if (g.overflow || tile >= n_tiles) return;
+    if (side_heads && g.passes != 0u) return;  // the last scatter pass left this frame's flags as bytes: k_side_heads
     const int64_t n = g.n;
     const uint32_t* k = (buf_sel < 0 ? sorted_buf(g, keys0, keys1) : (buf_sel ? keys1 : keys0)) + (int64_t)f * cap;
     uint32_t c = 0;
@@ -46,6 +47,46 @@ __global__ __launch_bounds__(kHeadWaves * kWave) void k_run_heads(const uint32_t
         for (int q = 0; q < 16; ++q) {
             const int64_t i = i0 + q;
             if (i < n && (i == 0 || kk[q] != (q ? kk[q - 1] : prev))) bits |= 1u << ((q >> 2) * 8 + (q & 3));
+        }
+        reinterpret_cast<uint32_t*>(head_bits + ((int64_t)f * n_tiles + tile) * 256)[lane] = bits;
+        c = (uint32_t)__popc(bits);
+    }
+    c = wave_sum_u32(c);
+    if (lane == 0) seg_cnt[(int64_t)f * n_tiles + tile] = c;
+}
+
+// Run heads of the frames whose last scatter pass decided them itself (scatter_tile, ScatterJob::heads) and left one
+// byte per record, 1 = starts a run, instead of the sorted indices: the bytes packed into k_run_heads' flag layout and
+// counted per segment tile, from one read of the byte array.  One wave per segment tile, 16 records per lane.  Frames
+// that did not sort (PCL's overflow guard, no passes) are k_run_heads' own.
+__global__ __launch_bounds__(kHeadWaves * kWave) void k_side_heads(const uint8_t* __restrict__ side, int64_t side_stride,
+                                                                   const VoxelGeom* __restrict__ geom, int n_tiles,
+                                                                   uint32_t* __restrict__ seg_cnt, uint8_t* __restrict__ head_bits)
+{
+    static_assert(kSegTile == 16 * kWave, "16 records per lane");
+    const int f = blockIdx.y, lane = threadIdx.x & 63;
+    const int tile = blockIdx.x * kHeadWaves + (threadIdx.x >> 6);
+    const VoxelGeom g = geom[f];
+    if (g.overflow || g.passes == 0u || tile >= n_tiles) return;
+    const int64_t n = g.n;
+    const uint8_t* sb = side + (int64_t)f * side_stride;
+    uint32_t c = 0;
+    const int64_t i0 = (int64_t)tile * kSegTile + lane * 16;
+    if ((int64_t)tile * kSegTile < n) {
+        uint32_t w4[4] = {0u, 0u, 0u, 0u};
+        if (i0 + 15 < n) {  // (the frame stride and i0 are multiples of 16)
+            const uint4 v = stream_load_u4(reinterpret_cast<const uint4*>(sb + i0));
+            w4[0] = v.x; w4[1] = v.y; w4[2] = v.z; w4[3] = v.w;
+        } else {
+#pragma unroll
+            for (int q = 0; q < 16; ++q)
+                if (i0 + q < n) w4[q >> 2] |= (uint32_t)(sb[i0 + q] & 1u) << ((q & 3) * 8);
+        }
+        uint32_t bits = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {  // four flag bytes -> the low nibble of flag byte q
+            const uint32_t w = w4[q];
+            bits |= ((w & 1u) | ((w >> 7) & 2u) | ((w >> 14) & 4u) | ((w >> 21) & 8u)) << (8 * q);
         }
         reinterpret_cast<uint32_t*>(head_bits + ((int64_t)f * n_tiles + tile) * 256)[lane] = bits;
         c = (uint32_t)__popc(bits);
@@ -165,10 +206,10 @@ __global__ __launch_bounds__(256) void k_frame_offsets(const VoxelGeom* __restri
                                                        const uint32_t* __restrict__ n_grp, int frames, int passthrough,
                                                        uint32_t* __restrict__ n_out, uint64_t* __restrict__ out_off,
                                                        CloudCounters* __restrict__ cc, SortStats* __restrict__ stats,
-                                                       const VoxelGeom* __restrict__ sort_geom)
+                                                       const VoxelGeom* __restrict__ sort_geom, int side_heads)
 {
     __shared__ uint32_t scan_lds[5];
-    __shared__ unsigned long long acc[6];  // record-passes, points in, points out, status, window frames, records
+    __shared__ unsigned long long acc[6];  // record-passes, points in, points out, status, records flagged by the last pass, records
     if (threadIdx.x < 6) acc[threadIdx.x] = 0;
     __syncthreads();
     const uint64_t base = cc->count;
@@ -187,6 +228,8 @@ __global__ __launch_bounds__(256) void k_frame_offsets(const VoxelGeom* __restri
                 m = (n_grp && sort_geom[f].grouped) ? n_grp[f] : (n_keep ? n_keep[f] : n_vox[f]);
                 atomicAdd(&acc[0], (unsigned long long)sort_geom[f].n * g.passes);  // records actually sorted
                 atomicAdd(&acc[5], (unsigned long long)sort_geom[f].n);
+                // (a point sort's last pass leaves run-head flags instead of the sorted indices: scatter_tile, k_side_heads)
+                if (side_heads && g.passes != 0u) atomicAdd(&acc[4], (unsigned long long)sort_geom[f].n);
                 atomicAdd(&acc[1], (unsigned long long)g.n);
                 atomicAdd(&acc[2], (unsigned long long)m);
             }
@@ -208,6 +251,7 @@ __global__ __launch_bounds__(256) void k_frame_offsets(const VoxelGeom* __restri
             stats->voxel_points_in += acc[1];
             stats->voxel_points_out += acc[2];
             stats->sort_records += acc[5];
+            stats->side_head_records += acc[4];
         }
     }
 }

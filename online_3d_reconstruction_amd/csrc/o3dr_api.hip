@@ -284,6 +284,7 @@ static int ws_ensure(o3dr_ctx* c, int frames, int64_t cap, bool need_pts, bool g
             k.take(w.hist_part, TS * kMaxRadix);
             k.take(w.seg_cnt, TG);
             k.take(w.head_bits, TG * 256);
+            k.take(w.side, E + 16 * (size_t)F);  // (frames * side_frame_stride(cap) <= elems + 14 frames)
             k.take(w.scan_partial, (TS * kMaxRadix + TG + TE + E) / 4096 + 8 * (size_t)F + 16);
             k.take(w.mm, MM);
             k.take(w.n_valid, (size_t)F);
@@ -1677,6 +1678,8 @@ static int accumulate_impl(o3dr_ctx* c, const uint8_t* disp, int64_t disp_frame_
         v.mm_used = a.n_tiles + 1;
         v.stats = c->stats_dev;
         v.use_runs = 0;
+        v.test_corrupt = c->test_corrupt;  // (o3dr_test_corrupt_next_gather: the first batch takes it)
+        c->test_corrupt = 0;
         if (with_sor) {
             v.mm_used = launch_sor(&c->prof, c->stream, c->ws, c->ws.pts, cap, c->ws.n_valid, nb, cap, a.n_tiles + 1, 1.0, c->ws.sor_pts,
                                    cap, c->ws.sor_n);
@@ -5818,7 +5821,8 @@ extern "C" int o3dr_profile_stats(o3dr_ctx* c, int64_t out[8])
     out[2] = (int64_t)c->stats_host->voxel_points_out;
     out[3] = 0;
     out[4] = (int64_t)c->stats_host->sort_records;
-    out[5] = out[6] = out[7] = 0;
+    out[5] = (int64_t)c->stats_host->side_head_records;
+    out[6] = out[7] = 0;
     return O3DR_OK;
 }
 extern "C" int o3dr_device_info(o3dr_ctx* c, char* name, int32_t name_len, int32_t* cu_count, int64_t* hbm_bytes)

@@ -36,6 +36,8 @@ constexpr int kMaxRadixBits = 7;           // digits are 1..7 bits wide, chosen 
 constexpr int kMaxRadix = 1 << kMaxRadixBits;
 constexpr int kMaxPasses = 5;            // 5 x 7 bits covers a full 32-bit index
 static_assert(kMaxRadix <= 2 * kSortThreads, "k_radix_scatter handles two digits per thread");
+// bytes between the frames of Workspace::side (one byte per record): frames start on 16-byte boundaries
+static inline int64_t side_frame_stride(int64_t cap) { return (cap + 15) & ~(int64_t)15; }
 // generic per-point kernels
 constexpr int kSlabClasses = 4;  // layout classes inside an emit tile of the fused batch path (slab_class)
 constexpr int kXcds = 8;   // accelerator complex dies of an MI355X, each with its own L2 (xcd_chunk_item)
@@ -130,6 +132,9 @@ struct Workspace {
     uint32_t* hist_part = nullptr; // frames*kMaxRadix*n_sort_tiles: digit counts of the FIRST scatter part of every tile
     uint32_t* seg_cnt = nullptr;   // frames*n_seg_tiles (run heads per tile, then kept runs per tile)
     uint8_t* head_bits = nullptr;  // frames*n_seg_tiles*256: run-head flags, 4 records per byte (k_run_heads -> k_run_starts)
+    uint8_t* side = nullptr;       // frames*side_frame_stride(cap): one byte per record of a point sort, 1 = starts a run of equal
+                                   // indices, written by the last scatter pass instead of the sorted indices (k_radix_scatter_lane
+                                   // -> k_side_heads); nullptr: the indices are written and k_run_heads reads them
     uint32_t* scan_partial = nullptr;  // chunk sums of the multi-workgroup scan
     // statistical outlier removal (sor_frames clouds of at most sor_cap points)
     SorGeom* sor_geom = nullptr;        // frames
@@ -172,7 +177,8 @@ struct SortStats {
     uint64_t voxel_points_out;    // points leaving them
     uint64_t reserved;
     uint64_t sort_records;        // records entering the sorts (points, or runs of points)
-    uint64_t pad[3];
+    uint64_t side_head_records;   // records whose run-head flag the last scatter pass wrote (no sorted indices, no k_run_heads pass)
+    uint64_t pad[2];
 };
 
 // where cloud_big records the heads of its group runs while it is appended to (k_centroid): the flags (4 records per

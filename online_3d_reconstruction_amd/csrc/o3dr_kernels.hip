@@ -5,7 +5,8 @@
 //       radix pass's digits over candidate-aligned sort tiles)
 //   K2  k_voxel_geom / k_voxel_keys_*          A4 steps 1-5: PCL VoxelGrid geometry and linear index
 //       k_radix_hist / k_radix_scatter_lane    A4 step 6: stable LSD radix sort of (index, point id)
-//       k_run_heads / k_run_starts / k_centroid  A4 steps 7-8: runs -> ordered fp32 centroid
+//       k_run_heads / k_side_heads / k_run_starts / k_centroid  A4 steps 7-8: runs -> ordered fp32 centroid
+//       (the last scatter pass of a point sort leaves run-head flags, not sorted indices: k_side_heads packs them)
 //
 // Everything here is HBM-bound integer/byte/fp32 work: no MFMA.  The whole translation unit is
 // compiled with -ffp-contract=off because the reference arithmetic (unoptimised x86 build,
@@ -342,7 +343,10 @@ void launch_voxel_grid(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelAr
         }
         // always kMaxPasses launch groups; frames whose index needs fewer passes drop out on the device
         const int64_t hist_row = (int64_t)kMaxRadix * n_sort_tiles;
-
+        // the last pass of a point sort leaves, instead of the sorted indices, whether each record starts a run, one byte per
+        // record (nothing but the run heads reads those indices; the group-run sort's are read by k_centroid_groups)
+        uint8_t* const side = use_runs ? nullptr : ws.side;
+        const int64_t side_stride = side_frame_stride(cap);
         for (int pass = 0; pass < kMaxPasses; ++pass) {
             // the first pass over the candidate-aligned tiles the emit pass counted (emit_part_range)
             const bool emit_tiles = pass == 0 && v.emit_tiles > 0;
@@ -364,14 +368,18 @@ void launch_voxel_grid(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelAr
                 ProfScope ps(pf, O3DR_K_SORT_SCATTER, s);
                 k_radix_scatter_lane<<<dim3(xcd_grid((int64_t)n_sort_tiles * kScatParts), F), kScatThreads, 0, s>>>(
                     ws.keys[0], ws.vals[0], ws.keys[1], ws.vals[1], cap, sort_geom, pass, n_sort_tiles, ws.hist, ws.hist_part, tm,
-                    emit_tiles ? ws.tile_cnt : nullptr, v.emit_tiles);
+                    emit_tiles ? ws.tile_cnt : nullptr, v.emit_tiles, side, side_stride);
             }
         }
         const dim3 sgrid(n_seg_tiles, F);
         {
             ProfScope ps(pf, O3DR_K_SEGMENT, s);
+            // (each of the two takes the frames of its kind and returns at once for the others)
             k_run_heads<<<dim3(cdiv64(n_seg_tiles, kHeadWaves), F), kHeadWaves * kWave, 0, s>>>(ws.keys[0], ws.keys[1], cap, sort_geom, n_seg_tiles,
-                                                                                       ws.seg_cnt, -1, ws.head_bits);
+                                                                                       ws.seg_cnt, -1, ws.head_bits, side != nullptr);
+            if (side)
+                k_side_heads<<<dim3(cdiv64(n_seg_tiles, kHeadWaves), F), kHeadWaves * kWave, 0, s>>>(side, side_stride, sort_geom, n_seg_tiles,
+                                                                                            ws.seg_cnt, ws.head_bits);
         }
         {
             ProfScope ps(pf, O3DR_K_OTHER, s);
@@ -424,7 +432,8 @@ void launch_voxel_grid(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelAr
     {
         ProfScope ps(pf, O3DR_K_OTHER, s);
         k_frame_offsets<<<1, 256, 0, s>>>(ws.geom, ws.n_vox, n_keep, use_runs ? ws.n_grp_out : nullptr, F, v.passthrough,
-                                          ws.n_out, ws.out_off, v.cc, v.stats, sort_geom);
+                                          ws.n_out, ws.out_off, v.cc, v.stats, sort_geom,
+                                          (!use_runs && ws.side && !v.passthrough && cap > 0) ? 1 : 0);
     }
     const int nbx = cdiv64(cap, kPtThreads);
     if (cap > 0 && use_runs) {
@@ -514,13 +523,14 @@ void launch_inc_runs(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_poin
         {
             ProfScope ps(pf, O3DR_K_SORT_SCATTER, s);
             k_radix_scatter_lane<<<dim3(xcd_grid((int64_t)n_sort_tiles * kScatParts), 1), kScatThreads, 0, s>>>(
-                ws.keys[0], ws.vals[0], ws.keys[1], ws.vals[1], cap, sort_geom, pass, n_sort_tiles, ws.hist, ws.hist_part, tm, nullptr, 0);
+                ws.keys[0], ws.vals[0], ws.keys[1], ws.vals[1], cap, sort_geom, pass, n_sort_tiles, ws.hist, ws.hist_part, tm, nullptr, 0,
+                nullptr, 0);
         }
     }
     {
         ProfScope ps(pf, O3DR_K_SEGMENT, s);
         k_run_heads<<<dim3(cdiv64(n_seg_tiles, kHeadWaves), 1), kHeadWaves * kWave, 0, s>>>(ws.keys[0], ws.keys[1], cap, sort_geom,
-                                                                                             n_seg_tiles, ws.seg_cnt, -1, ws.head_bits);
+                                                                                             n_seg_tiles, ws.seg_cnt, -1, ws.head_bits, 0);
     }
     {
         ProfScope ps(pf, O3DR_K_OTHER, s);
@@ -928,7 +938,8 @@ static void launch_radix_passes(Workspace& ws, hipStream_t s, int64_t cap, int p
         else
             launch_scan(s, ws.hist, hist_row, hist_row, F, nullptr, nullptr, ws.scan_partial, ws.geom, pass, n_sort_tiles);
         k_radix_scatter_lane<<<dim3(xcd_grid((int64_t)n_sort_tiles * kScatParts), F), kScatThreads, 0, s>>>(
-            ws.keys[0], ws.vals[0], ws.keys[1], ws.vals[1], cap, ws.geom, pass, n_sort_tiles, ws.hist, ws.hist_part, tm, nullptr, 0);
+            ws.keys[0], ws.vals[0], ws.keys[1], ws.vals[1], cap, ws.geom, pass, n_sort_tiles, ws.hist, ws.hist_part, tm, nullptr, 0,
+            nullptr, 0);
     }
 }
 
