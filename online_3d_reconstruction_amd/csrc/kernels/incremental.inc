@@ -7,8 +7,8 @@
 // the cells sorted by ABSOLUTE (layer, row, x), and one IncGroup per occupied absolute voxel group (util.inc:
 // group_coord_of) with its 32-bit occupancy mask; off[g] = cells of the groups before g.  A call folds the points
 // appended since the previous one:
-//   1. the tail's group runs are sorted by group with the merge's own kernels (launch_inc_runs), over a grid laid on the
-//      whole cloud's box: a group key relative to that box orders like the absolute coordinates;
+//   1. the tail's group runs are sorted by group with the merge's own kernels (launch_inc_runs: the merge's
+//      group_run_front, radix_pass and segment_runs), over a grid laid on the whole cloud's box: a group key relative to that box orders like the absolute coordinates;
 //   2. k_inc_fold: one wave per tail group, lane = cell, k_centroid_groups' LDS counting sort and front-to-back adds,
 //      but every lane starts from its cell's stored sums (zero for a new cell) and the sums are kept instead of divided;
 //   3. the tail's groups and the state's are merged by rank (k_inc_place_*), the cells move to their new places

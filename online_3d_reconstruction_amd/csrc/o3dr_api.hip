@@ -358,6 +358,34 @@ static int sor_ensure(o3dr_ctx* c, int frames, int64_t cap)
 }
 static inline bool sor_on(const o3dr_ctx* c) { return c->params.sor_enable && c->params.jump_pixels > 0; }  // :1673
 
+// The voxel grid job over `frames` clouds (cloud f = in + f*in_fstride, n_dev[f] of at most `cap` points) with this leaf,
+// z offset and min_points.  Everything else is off; a caller states what is particular to it.
+static VoxelArgs voxel_args(const o3dr_point* in, int64_t in_fstride, const uint32_t* n_dev, int frames, int64_t cap,
+                            const float leaf[3], float z_offset = 0.f, uint32_t min_points = 0)
+{
+    VoxelArgs v;
+    v.in = in;
+    v.in_fstride = in_fstride;
+    v.n_dev = n_dev;
+    v.frames = frames;
+    v.cap = cap;
+    for (int a = 0; a < 3; ++a) v.leaf[a] = leaf[a];
+    v.z_offset = z_offset;
+    v.min_points = min_points;
+    return v;
+}
+// Outlier removal in front of v's grid (pose_functions.cpp:1673-1686): the grid then reads the inliers and folds the
+// bounding-box slots launch_sor left.  ensure: size the removal's buffers for this job first.
+static int sor_in_front(o3dr_ctx* c, VoxelArgs& v, bool ensure = true)
+{
+    if (ensure) CHK(sor_ensure(c, v.frames, v.cap));
+    v.mm_used = launch_sor(&c->prof, c->stream, c->ws, v.in, v.in_fstride, v.n_dev, v.frames, v.cap, v.mm_used, 1.0, c->ws.sor_pts,
+                           v.in_fstride, c->ws.sor_n);
+    v.in = c->ws.sor_pts;
+    v.n_dev = c->ws.sor_n;
+    return O3DR_OK;
+}
+
 extern "C" int o3dr_version(void) { return O3DR_VERSION; }
 extern "C" const char* o3dr_last_error(void) { return g_err.c_str(); }
 
@@ -1005,28 +1033,14 @@ static int frame_call(o3dr_ctx* c, const uint8_t* disp, int64_t disp_pitch, cons
         CHK(run_reproject_single(c, (const uint8_t*)disp_d, disp_pitch, (const uint8_t*)bgr_d, bgr_pitch, rows, cols, g,
                                  T, (const float*)kp_d, n_kp, c->ws.pts));
         CHK(zero_counters(c, c->cc_tmp));
-        VoxelArgs v;
-        v.in = c->ws.pts;
-        v.in_fstride = 0;
-        v.n_dev = c->ws.n_valid;
-        v.frames = 1;
-        v.cap = cap;
-        v.leaf[0] = v.leaf[1] = v.leaf[2] = (float)(c->params.voxel_size / 5);  // pose_functions.cpp:1698
-        v.min_points = 0;
-        v.z_offset = 0.f;
+        const float lf = (float)(c->params.voxel_size / 5);  // pose_functions.cpp:1698
+        const float leaf[3] = {lf, lf, lf};
+        VoxelArgs v = voxel_args(c->ws.pts, 0, c->ws.n_valid, 1, cap, leaf);
         v.out_base = final_dst;
         v.cc = c->cc_tmp;
-        v.passthrough = 0;
         v.mm_used = (int)((g.n + kEmitTile - 1) / kEmitTile) + 1;
         v.stats = c->stats_dev;
-        v.use_runs = 0;
-        if (sor_on(c)) {  // pose_functions.cpp:1673-1686 in front of the per-frame voxel grid
-            CHK(sor_ensure(c, 1, cap));
-            v.mm_used = launch_sor(&c->prof, c->stream, c->ws, c->ws.pts, 0, c->ws.n_valid, 1, cap, v.mm_used, 1.0, c->ws.sor_pts, 0,
-                                   c->ws.sor_n);
-            v.in = c->ws.sor_pts;
-            v.n_dev = c->ws.sor_n;
-        }
+        if (sor_on(c)) CHK(sor_in_front(c, v));  // in front of the per-frame voxel grid
         launch_voxel_grid(&c->prof, c->stream, c->ws, v);
         HIPCHK(hipGetLastError());
         CloudCounters cc;
@@ -1151,32 +1165,16 @@ static int voxel_single(o3dr_ctx* c, const o3dr_point* in_d, int64_t n_in, const
     else
         mm_used = launch_points_minmax(&c->prof, c->stream, in_d, 0, c->ws.n_valid, 1, n_in, c->ws.mm_stride, c->ws.mm);
     CHK(zero_counters(c, c->cc_tmp));
-    VoxelArgs v;
-    v.in = in_d;
-    v.in_fstride = 0;
-    v.n_dev = c->ws.n_valid;
-    v.frames = 1;
-    v.cap = n_in;
-    v.leaf[0] = leaf[0];
-    v.leaf[1] = leaf[1];
-    v.leaf[2] = leaf[2];
-    v.min_points = min_points;
-    v.z_offset = z_offset;
+    VoxelArgs v = voxel_args(in_d, 0, c->ws.n_valid, 1, n_in, leaf, z_offset, min_points);
     v.out_base = out_d;
     v.cc = c->cc_tmp;
-    v.passthrough = 0;
     v.mm_used = mm_used;
     v.stats = c->stats_dev;
     v.use_runs = c->use_runs;
     v.heads_in = heads_in;
     v.test_corrupt = c->test_corrupt;
     c->test_corrupt = 0;
-    if (do_sor) {
-        CHK(sor_ensure(c, 1, n_in));
-        v.mm_used = launch_sor(&c->prof, c->stream, c->ws, in_d, 0, c->ws.n_valid, 1, n_in, mm_used, 1.0, c->ws.sor_pts, 0, c->ws.sor_n);
-        v.in = c->ws.sor_pts;
-        v.n_dev = c->ws.sor_n;
-    }
+    if (do_sor) CHK(sor_in_front(c, v));
     launch_voxel_grid(&c->prof, c->stream, c->ws, v);
     HIPCHK(hipGetLastError());
     CloudCounters cc;
@@ -1506,18 +1504,11 @@ extern "C" int o3dr_cloud_big_append(o3dr_ctx* c, const o3dr_point* pts, int64_t
     CHK(stage_in(c, c->st_in, pts, (size_t)n * sizeof(o3dr_point), mem, &src));
     CHK(ws_ensure(c, 1, 1, false));
     launch_set_counts(&c->prof, c->stream, c->ws.n_valid, (uint32_t)n, 1);
-    VoxelArgs v;
-    memset(&v, 0, sizeof v);
-    v.in = (const o3dr_point*)src;
-    v.n_dev = c->ws.n_valid;
-    v.frames = 1;
-    v.cap = n;
-    v.leaf[0] = v.leaf[1] = v.leaf[2] = 1.f;
+    const float unit_leaf[3] = {1.f, 1.f, 1.f};
+    VoxelArgs v = voxel_args((const o3dr_point*)src, 0, c->ws.n_valid, 1, n, unit_leaf);
     v.out_base = c->cloud_big;
     v.cc = c->cc_big;
     v.passthrough = 1;
-    v.mm_used = 0;
-    v.stats = nullptr;
     c->cloud_box_valid = false;  // appended points are not tracked
     c->cloud_heads_valid = false;
     launch_voxel_grid(&c->prof, c->stream, c->ws, v);
@@ -1657,35 +1648,19 @@ static int accumulate_impl(o3dr_ctx* c, const uint8_t* disp, int64_t disp_frame_
         else
             launch_reproject(&c->prof, c->stream, a, nb, c->ws.pts, c->ws.tile_cnt, c->ws.n_kp, c->ws.n_valid, c->ws.mm,
                              c->ws.scan_partial);
-        VoxelArgs v;
+        VoxelArgs v = voxel_args(c->ws.pts, cap, c->ws.n_valid, nb, cap, leaf, zo, mp);
         v.keys_ready = fused ? 1 : 0;
         v.emit_tiles = emit_tiles;
         v.cloud_box = c->cloud_box_valid ? c->cloud_box : nullptr;
         heads_for_append(c, v);
-        v.in = c->ws.pts;
-        v.in_fstride = cap;
-        v.n_dev = c->ws.n_valid;
-        v.frames = nb;
-        v.cap = cap;
-        v.leaf[0] = leaf[0];
-        v.leaf[1] = leaf[1];
-        v.leaf[2] = leaf[2];
-        v.min_points = mp;
-        v.z_offset = zo;
         v.out_base = c->cloud_big;
         v.cc = c->cc_big;
         v.passthrough = c->params.dont_downsample ? 1 : 0;
         v.mm_used = a.n_tiles + 1;
         v.stats = c->stats_dev;
-        v.use_runs = 0;
         v.test_corrupt = c->test_corrupt;  // (o3dr_test_corrupt_next_gather: the first batch takes it)
         c->test_corrupt = 0;
-        if (with_sor) {
-            v.mm_used = launch_sor(&c->prof, c->stream, c->ws, c->ws.pts, cap, c->ws.n_valid, nb, cap, a.n_tiles + 1, 1.0, c->ws.sor_pts,
-                                   cap, c->ws.sor_n);
-            v.in = c->ws.sor_pts;
-            v.n_dev = c->ws.sor_n;
-        }
+        if (with_sor) CHK(sor_in_front(c, v, false));  // (the buffers were sized for all batches above)
         launch_voxel_grid(&c->prof, c->stream, c->ws, v);
         HIPCHK(hipGetLastError());
         c->cloud_ub += (int64_t)nb * cap;
@@ -2121,6 +2096,15 @@ extern "C" int o3dr_cloud_big_header_dev(o3dr_ctx* c, void* hdr_dev)
     return O3DR_OK;
 }
 
+// the merge's grid over cloud_big (at most ub points, counted in ws.n_valid): its index slices are what the partitions cut
+static VoxelArgs slice_args(o3dr_ctx* c, int64_t ub)
+{
+    float leaf[3], zo;
+    uint32_t mp;
+    downsample_leaf(c->params, 1, leaf, &mp, &zo);
+    return voxel_args(c->cloud_big, 0, c->ws.n_valid, 1, ub, leaf, zo);
+}
+
 extern "C" int o3dr_cloud_big_partition_dev(o3dr_ctx* c, const void* hdrs_dev, int32_t n_hdrs, int32_t n_parts, int64_t* counts_dev)
 {
     CTX_ENTER(c);
@@ -2134,19 +2118,7 @@ extern "C" int o3dr_cloud_big_partition_dev(o3dr_ctx* c, const void* hdrs_dev, i
     CHK(alt_reserve(c, ub));
     o3dr_point* nb = c->cloud_alt;
     launch_count_from_cc(c->stream, c->cc_big, c->ws.n_valid);
-    float leaf[3], zo;
-    uint32_t mp;
-    downsample_leaf(c->params, 1, leaf, &mp, &zo);
-    VoxelArgs v;
-    memset(&v, 0, sizeof v);
-    v.in = c->cloud_big;
-    v.n_dev = c->ws.n_valid;
-    v.frames = 1;
-    v.cap = ub;
-    v.leaf[0] = leaf[0];
-    v.leaf[1] = leaf[1];
-    v.leaf[2] = leaf[2];
-    v.z_offset = zo;
+    const VoxelArgs v = slice_args(c, ub);
     ++c->cloud_gen;
     launch_partition(&c->prof, c->stream, c->ws, v, n_parts, nb, (uint64_t*)counts_dev, (uint32_t*)(counts_dev + n_parts), hdrs_dev, n_hdrs);
     if (hipGetLastError() != hipSuccess) return fail(O3DR_ERR_HIP, "partition launch failed");
@@ -2159,22 +2131,6 @@ extern "C" int o3dr_cloud_big_partition_dev(o3dr_ctx* c, const void* hdrs_dev, i
 // exchange wants them - [room for what the lower ranks send | this rank's own slice | room for the higher ranks' | the
 // slices that leave, in rank order] - so that the all-to-all receives straight into the gaps and the own slice (95 % of the
 // cloud at the benchmark shapes) is never sent to itself
-static int slice_args(o3dr_ctx* c, VoxelArgs& v, int64_t ub)
-{
-    float leaf[3], zo;
-    uint32_t mp;
-    downsample_leaf(c->params, 1, leaf, &mp, &zo);
-    memset(&v, 0, sizeof v);
-    v.in = c->cloud_big;
-    v.n_dev = c->ws.n_valid;
-    v.frames = 1;
-    v.cap = ub;
-    v.leaf[0] = leaf[0];
-    v.leaf[1] = leaf[1];
-    v.leaf[2] = leaf[2];
-    v.z_offset = zo;
-    return O3DR_OK;
-}
 extern "C" int o3dr_cloud_big_slice_counts_dev(o3dr_ctx* c, const void* hdrs_dev, int32_t n_hdrs, int32_t n_parts, int64_t* counts_dev)
 {
     CTX_ENTER(c);
@@ -2191,8 +2147,7 @@ extern "C" int o3dr_cloud_big_slice_counts_dev(o3dr_ctx* c, const void* hdrs_dev
     if (ub >= (int64_t)0xffffffffLL) return fail(O3DR_ERR_INVALID_ARG, "cloud_big exceeds 2^32-1 points");
     CHK(ws_ensure(c, 1, ub, false));
     launch_count_from_cc(c->stream, c->cc_big, c->ws.n_valid);
-    VoxelArgs v;
-    CHK(slice_args(c, v, ub));
+    const VoxelArgs v = slice_args(c, ub);
     launch_partition_count(&c->prof, c->stream, c->ws, v, n_parts, (uint64_t*)counts_dev, (uint32_t*)(counts_dev + n_parts), hdrs_dev, n_hdrs);
     if (hipGetLastError() != hipSuccess) return fail(O3DR_ERR_HIP, "slice count launch failed");
     c->place_ub = ub;
@@ -2235,8 +2190,7 @@ extern "C" int o3dr_cloud_big_place_slices(o3dr_ctx* c, int32_t n_parts, int32_t
     }
     HIPCHK(hipMemcpyAsync(c->misc_dev + 2560, sh, sizeof(int64_t) * (size_t)n_parts, hipMemcpyHostToDevice, c->stream));
     if (n_local > 0) {
-        VoxelArgs v;
-        CHK(slice_args(c, v, cap_counted));
+        const VoxelArgs v = slice_args(c, cap_counted);
         launch_partition_move(&c->prof, c->stream, c->ws, v, n_parts, c->cloud_alt, (const int64_t*)(c->misc_dev + 2560));
         if (hipGetLastError() != hipSuccess) return fail(O3DR_ERR_HIP, "slice placement launch failed");
         // (the pinned shift table is only written here, and every exchange ends in a stream wait - the merged slice's size -
@@ -2321,19 +2275,7 @@ extern "C" int o3dr_cloud_big_partition(o3dr_ctx* c, const float gmin[3], const 
     o3dr_point* nb = c->cloud_alt;
     launch_set_counts(&c->prof, c->stream, c->ws.n_valid, (uint32_t)n, 1);
     CHK(put_bbox(c, gmin, gmax));
-    float leaf[3], zo;
-    uint32_t mp;
-    downsample_leaf(c->params, 1, leaf, &mp, &zo);
-    VoxelArgs v;
-    memset(&v, 0, sizeof v);
-    v.in = c->cloud_big;
-    v.n_dev = c->ws.n_valid;
-    v.frames = 1;
-    v.cap = n;
-    v.leaf[0] = leaf[0];
-    v.leaf[1] = leaf[1];
-    v.leaf[2] = leaf[2];
-    v.z_offset = zo;
+    const VoxelArgs v = slice_args(c, n);
     uint32_t* ovf_dev = (uint32_t*)(c->misc_dev + 32);
     uint64_t* cnt_dev = (uint64_t*)(c->misc_dev + 64);
     ++c->cloud_gen;

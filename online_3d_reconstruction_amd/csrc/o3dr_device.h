@@ -235,20 +235,20 @@ int launch_points_minmax(Profiler* pf, hipStream_t s, const o3dr_point* in, int6
 // voxel grid over `frames` independent clouds (cloud f = in + f*in_fstride, n_dev[f] points);
 // results are appended at out_base[cc->count + ...] in frame order and cc->count is advanced.
 struct VoxelArgs {
-    const o3dr_point* in;
-    int64_t in_fstride;
-    const uint32_t* n_dev;
-    int frames;
-    int64_t cap;
-    float leaf[3];
-    uint32_t min_points;
-    float z_offset;
-    o3dr_point* out_base;
-    CloudCounters* cc;
-    int passthrough;  // dont_downsample: append the input unchanged
-    int mm_used;      // bounding-box slots to fold per frame
-    SortStats* stats; // optional device statistics
-    int use_runs;     // whole-cloud calls (frames == 1): sort runs of consecutive points of one voxel group instead of points
+    const o3dr_point* in = nullptr;
+    int64_t in_fstride = 0;
+    const uint32_t* n_dev = nullptr;
+    int frames = 0;
+    int64_t cap = 0;
+    float leaf[3] = {0.f, 0.f, 0.f};
+    uint32_t min_points = 0;
+    float z_offset = 0.f;
+    o3dr_point* out_base = nullptr;
+    CloudCounters* cc = nullptr;
+    int passthrough = 0;  // dont_downsample: append the input unchanged
+    int mm_used = 0;      // bounding-box slots to fold per frame
+    SortStats* stats = nullptr;  // optional device statistics
+    int use_runs = 0;     // whole-cloud calls (frames == 1): sort runs of consecutive points of one voxel group instead of points
                       // when they are long enough (decided on the device; 2: whenever the result slots allow it); needs
                       // ws.grp_slots result slots in ws.pts, which must not be the input
     float* cloud_box = nullptr;  // device, 6 floats: running bounding box of out_base's cloud, extended by this call

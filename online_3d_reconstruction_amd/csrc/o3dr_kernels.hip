@@ -217,13 +217,126 @@ static inline int xcd_grid(int64_t n) { return (int)((n + kXcds - 1) / kXcds * k
 // tile-major histogram rows (hist_at in kernels/radix_sort.inc) where a frame's row fits the one-workgroup scan's LDS
 static inline size_t hist_tm_lds(int n_sort_tiles) { return (size_t)n_sort_tiles * (kMaxRadix + 1) * sizeof(uint32_t); }
 static inline int hist_tm(int n_sort_tiles) { return hist_tm_lds(n_sort_tiles) <= 48 * 1024 ? 1 : 0; }
+
+// What the launches of a sort of `frames` frames of at most `cap` records are sized by
+struct SortShape {
+    int64_t cap;
+    int frames;
+    int n_sort_tiles, n_seg_tiles;
+    int64_t hist_row;  // words of one frame's histograms
+    int tm;            // tile-major histogram rows, scanned by one workgroup per frame (hist_tm)
+    size_t tm_lds;
+    SortShape(int64_t cap_, int frames_)
+        : cap(cap_), frames(frames_), n_sort_tiles(cdiv64(cap_, kSortTile)), n_seg_tiles(cdiv64(cap_, kSegTile)),
+          hist_row((int64_t)kMaxRadix * n_sort_tiles), tm(hist_tm(n_sort_tiles)), tm_lds(hist_tm_lds(n_sort_tiles))
+    {
+    }
+};
+
+// One stable radix pass over ws.keys / ws.vals by the plan in `geom`: digit histograms, their scan, the scatter.
+//   have_hist   pass 0 only: ws.hist / ws.hist_part hold the pass's histograms already
+//   emit_tiles  > 0: pass 0 runs over the candidate-aligned tiles the emit pass counted (emit_part_range, ws.tile_cnt)
+//   side        the last pass of a frame's sort leaves run-head flags there, one byte per record, not the sorted indices
+// Always launched; frames whose plan has fewer passes drop out on the device.
+static void radix_pass(Profiler* pf, hipStream_t s, Workspace& ws, const SortShape& sh, const VoxelGeom* geom, int pass,
+                       bool have_hist = false, int emit_tiles = 0, uint8_t* side = nullptr, int64_t side_stride = 0)
+{
+    const bool emit = pass == 0 && emit_tiles > 0;
+    if (!(pass == 0 && have_hist)) {
+        ProfScope ps(pf, O3DR_K_SORT_HIST, s);
+        k_radix_hist<<<dim3(sh.n_sort_tiles, sh.frames), kSortThreads, 0, s>>>(ws.keys[0], ws.keys[1], sh.cap, geom, pass, sh.n_sort_tiles,
+                                                                                ws.hist, ws.hist_part, sh.tm);
+    }
+    {
+        ProfScope ps(pf, O3DR_K_OTHER, s);
+        if (sh.tm)
+            k_scan_hist_tm<<<sh.frames, 1024, sh.tm_lds, s>>>(ws.hist, geom, pass, sh.n_sort_tiles, emit ? 1 : 0);
+        else
+            launch_scan(s, ws.hist, sh.hist_row, sh.hist_row, sh.frames, nullptr, nullptr, ws.scan_partial, geom, pass, sh.n_sort_tiles);
+    }
+    {
+        ProfScope ps(pf, O3DR_K_SORT_SCATTER, s);
+        k_radix_scatter_lane<<<dim3(xcd_grid((int64_t)sh.n_sort_tiles * kScatParts), sh.frames), kScatThreads, 0, s>>>(
+            ws.keys[0], ws.vals[0], ws.keys[1], ws.vals[1], sh.cap, geom, pass, sh.n_sort_tiles, ws.hist, ws.hist_part, sh.tm,
+            emit ? ws.tile_cnt : nullptr, emit_tiles, side, side_stride);
+    }
+}
+
+// The front of a group-run sort of one cloud: the heads of its group runs (runs of consecutive points of one voxel group)
+// per segment tile, their scan -> ws.n_runs, the runs' plan -> ws.geom_runs, the (group, run id) records -> buffer 1 and the
+// runs' starts -> ws.run_start.  The heads: recorded while the cloud was appended to (rec_heads: used in place, or with
+// shift_n > 0 the shift_n flags from flag shift_first on, moved to ws.head_bits first), else from one read of the points.
+static void group_run_front(Profiler* pf, hipStream_t s, Workspace& ws, const SortShape& sh, const o3dr_point* in, float z_offset,
+                            const uint8_t* rec_heads, int64_t shift_first, int64_t shift_n, int force_runs, int64_t grp_slots)
+{
+    const int F = sh.frames, n_seg_tiles = sh.n_seg_tiles;
+    const uint8_t* hb = rec_heads && shift_n <= 0 ? rec_heads : ws.head_bits;
+    {
+        ProfScope ps(pf, O3DR_K_KEYGEN, s);
+        if (rec_heads && shift_n > 0) {
+            const int64_t bytes = (int64_t)n_seg_tiles * 256;
+            k_inc_heads_shift<<<cdiv64(bytes, 256), 256, 0, s>>>(rec_heads, (uint64_t)shift_first, (uint64_t)shift_n, ws.head_bits,
+                                                                 (uint64_t)bytes);
+        }
+        if (rec_heads)
+            k_head_counts<<<cdiv64(n_seg_tiles, 4), 256, 0, s>>>(hb, ws.geom, n_seg_tiles, ws.seg_cnt);
+        else
+            k_group_heads<<<n_seg_tiles, 256, 0, s>>>(in, ws.geom, z_offset, n_seg_tiles, ws.seg_cnt, ws.head_bits);
+    }
+    {
+        ProfScope ps(pf, O3DR_K_OTHER, s);
+        launch_scan(s, ws.seg_cnt, n_seg_tiles, n_seg_tiles, F, ws.n_runs, nullptr, ws.scan_partial);
+    }
+    {
+        ProfScope ps(pf, O3DR_K_SEGMENT, s);
+        // group runs or points?  (decided per cloud on the device; force_runs: group runs whenever they fit grp_slots)
+        k_run_geom<<<cdiv64(F, 64), 64, 0, s>>>(ws.geom, ws.n_runs, F, ws.geom_runs, force_runs, grp_slots);
+        // (group, run id) records in buffer 1
+        k_run_starts<<<dim3(cdiv64(n_seg_tiles, kStartWaves), F), kStartWaves * kWave, 0, s>>>(
+            ws.keys[0], ws.keys[1], sh.cap, ws.geom, n_seg_tiles, ws.seg_cnt, ws.n_runs, ws.run_start, 0, ws.keys[1], ws.geom_runs, in,
+            z_offset, hb);
+    }
+}
+
+// Behind the sort: the runs of equal keys.  Their heads per segment tile (from the sorted keys, or packed from the side bytes
+// the last pass left: each of the two kernels takes the frames of its kind and returns at once for the others), the scan
+// -> ws.n_vox, the runs' starts -> ws.seg_start.
+static void segment_runs(Profiler* pf, hipStream_t s, Workspace& ws, const SortShape& sh, const VoxelGeom* geom, const uint8_t* side,
+                         int64_t side_stride)
+{
+    const int F = sh.frames, n_seg_tiles = sh.n_seg_tiles;
+    {
+        ProfScope ps(pf, O3DR_K_SEGMENT, s);
+        const dim3 hgrid(cdiv64(n_seg_tiles, kHeadWaves), F);
+        k_run_heads<<<hgrid, kHeadWaves * kWave, 0, s>>>(ws.keys[0], ws.keys[1], sh.cap, geom, n_seg_tiles, ws.seg_cnt, -1, ws.head_bits,
+                                                         side != nullptr);
+        if (side) k_side_heads<<<hgrid, kHeadWaves * kWave, 0, s>>>(side, side_stride, geom, n_seg_tiles, ws.seg_cnt, ws.head_bits);
+    }
+    {
+        ProfScope ps(pf, O3DR_K_OTHER, s);
+        launch_scan(s, ws.seg_cnt, n_seg_tiles, n_seg_tiles, F, ws.n_vox, nullptr, ws.scan_partial);
+    }
+    {
+        ProfScope ps(pf, O3DR_K_SEGMENT, s);
+        k_run_starts<<<dim3(cdiv64(n_seg_tiles, kStartWaves), F), kStartWaves * kWave, 0, s>>>(
+            ws.keys[0], ws.keys[1], sh.cap, geom, n_seg_tiles, ws.seg_cnt, ws.n_vox, ws.seg_start, -1, nullptr, nullptr, nullptr, 0.f,
+            ws.head_bits);
+    }
+}
+
+// o3dr_test_corrupt_next_gather: poison one sorted payload in front of the kernels that gather by it
+static void corrupt_payload(hipStream_t s, Workspace& ws, const VoxelGeom* geom)
+{
+    k_test_corrupt_payload<<<1, 1, 0, s>>>(ws.vals[0], ws.vals[1], geom);
+}
+
 int launch_reproject_fused(Profiler* pf, hipStream_t s, Workspace& ws, const ReprojectArgs& a, int frames, int64_t cap,
                             const float leaf[3], bool conservative_box)
 {
     // the emit pass counts the first radix pass's digits where its workgroups own whole rows of the histograms: tile-major
     // rows, and as many sort tiles as groups of kEmitGroup emit tiles (cap = the frame's candidates)
-    const int n_sort_tiles = cdiv64(cap, kSortTile);
-    const bool counts = hist_tm(n_sort_tiles) && cdiv64(a.n_tiles, kEmitGroup) == n_sort_tiles;
+    const SortShape sh(cap, frames);
+    const bool counts = sh.tm && cdiv64(a.n_tiles, kEmitGroup) == sh.n_sort_tiles;
     uint32_t* const hist = counts ? ws.hist : nullptr;
     const dim3 grid(cdiv64(a.n_tiles, kEmitGroup), frames);
     // rectified-stereo Q and byte disparities: counts + a conservative box from the corners of (x, y, disparity) ranges
@@ -253,10 +366,10 @@ int launch_reproject_fused(Profiler* pf, hipStream_t s, Workspace& ws, const Rep
         ProfScope ps(pf, O3DR_K_REPROJECT, s);
         if (a.disp_f64)
             k_reproject_emit<true, true><<<grid, kEmitThreads, 0, s>>>(a, ws.pts, ws.tile_cnt, ws.n_kp, ws.mm, ws.geom, cap, ws.keys[0], hist,
-                                                                       ws.hist_part, n_sort_tiles);
+                                                                       ws.hist_part, sh.n_sort_tiles);
         else
             k_reproject_emit<false, true><<<grid, kEmitThreads, 0, s>>>(a, ws.pts, ws.tile_cnt, ws.n_kp, ws.mm, ws.geom, cap, ws.keys[0], hist,
-                                                                        ws.hist_part, n_sort_tiles);
+                                                                        ws.hist_part, sh.n_sort_tiles);
     }
     return counts ? a.n_tiles : 0;
 }
@@ -283,15 +396,14 @@ int launch_points_minmax(Profiler* pf, hipStream_t s, const o3dr_point* in, int6
 }
 
 // The voxel grid proper.  Expects ws.mm slots [0, v.mm_used) of every frame to hold bounding boxes of
-// the (un-offset) inputs.
+// the (un-offset) inputs.  In order: geometry, group-run front, keys and first histogram, radix passes, run segmentation,
+// min_points filter, (test hook), grouped sums, frame offsets, gather, heads fix, box fold.
 void launch_voxel_grid(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelArgs& v)
 {
     const int F = v.frames;
     const int64_t cap = v.cap;
-    const int n_sort_tiles = cdiv64(cap, kSortTile);
-    const int n_seg_tiles = cdiv64(cap, kSegTile);
-    const size_t tm_lds = hist_tm_lds(n_sort_tiles);
-    const int tm = hist_tm(n_sort_tiles);
+    const SortShape sh(cap, F);
+    const int n_seg_tiles = sh.n_seg_tiles;
     if (!v.keys_ready) {
         ProfScope ps(pf, O3DR_K_OTHER, s);
         k_voxel_geom<<<F, 256, 0, s>>>(ws.mm, ws.mm_stride, v.mm_used, v.n_dev, v.leaf[0], v.leaf[1], v.leaf[2],
@@ -306,90 +418,27 @@ void launch_voxel_grid(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelAr
     // what the sort and the run/cell kernels count (group runs or points)
     const VoxelGeom* sort_geom = use_runs ? ws.geom_runs : ws.geom;
     if (!v.passthrough && cap > 0) {
-        const dim3 grid(n_sort_tiles, F);
-        if (use_runs) {
-            // the heads of the group runs (runs of consecutive points of one voxel group) per segment tile: recorded
-            // while the cloud was appended to, or from one read of the points
-            const uint8_t* hb = v.heads_in ? v.heads_in : ws.head_bits;
-            {
-                ProfScope ps(pf, O3DR_K_KEYGEN, s);
-                if (v.heads_in)
-                    k_head_counts<<<cdiv64(n_seg_tiles, 4), 256, 0, s>>>(v.heads_in, ws.geom, n_seg_tiles, ws.seg_cnt);
-                else
-                    k_group_heads<<<n_seg_tiles, 256, 0, s>>>(v.in, ws.geom, v.z_offset, n_seg_tiles, ws.seg_cnt, ws.head_bits);
-            }
-            {
-                ProfScope ps(pf, O3DR_K_OTHER, s);
-                launch_scan(s, ws.seg_cnt, n_seg_tiles, n_seg_tiles, F, ws.n_runs, nullptr, ws.scan_partial);
-            }
-            {
-                ProfScope ps(pf, O3DR_K_SEGMENT, s);
-                // group runs or points?  (decided per cloud on the device; use_runs == 2: group runs whenever they fit)
-                k_run_geom<<<cdiv64(F, 64), 64, 0, s>>>(ws.geom, ws.n_runs, F, ws.geom_runs, v.use_runs > 1 ? 1 : 0, grp_slots);
-                // (group, run id) records in buffer 1
-                k_run_starts<<<dim3(cdiv64(n_seg_tiles, kStartWaves), F), kStartWaves * kWave, 0, s>>>(
-                    ws.keys[0], ws.keys[1], cap, ws.geom, n_seg_tiles, ws.seg_cnt, ws.n_runs, ws.run_start, 0, ws.keys[1],
-                    ws.geom_runs, v.in, v.z_offset, hb);
-            }
-            {
-                ProfScope ps(pf, O3DR_K_KEYGEN, s);  // a cloud left to the point sort needs PCL's index per point after all
-                k_voxel_keys_hist0<<<grid, kSortThreads, 0, s>>>(v.in, v.in_fstride, ws.geom, v.z_offset, cap, ws.keys[0],
-                                                                 n_sort_tiles, ws.hist, ws.hist_part, ws.geom_runs, tm);
-            }
-        } else if (!v.keys_ready) {  // PCL's index per point and the histogram of the first radix pass
+        // the heads of the group runs: recorded while the cloud was appended to, or from one read of the points
+        // (use_runs == 2: group runs whenever they fit the result slots)
+        if (use_runs) group_run_front(pf, s, ws, sh, v.in, v.z_offset, v.heads_in, 0, 0, v.use_runs > 1 ? 1 : 0, grp_slots);
+        if (use_runs || !v.keys_ready) {
+            // PCL's index per point and, for a point sort, the histogram of the first radix pass (a cloud k_run_geom leaves to
+            // the point sort needs the indices after all)
             ProfScope ps(pf, O3DR_K_KEYGEN, s);
-            k_voxel_keys_hist0<<<grid, kSortThreads, 0, s>>>(v.in, v.in_fstride, ws.geom, v.z_offset, cap, ws.keys[0],
-                                                             n_sort_tiles, ws.hist, ws.hist_part, nullptr, tm);
+            k_voxel_keys_hist0<<<dim3(sh.n_sort_tiles, F), kSortThreads, 0, s>>>(v.in, v.in_fstride, ws.geom, v.z_offset, cap, ws.keys[0],
+                                                                                 sh.n_sort_tiles, ws.hist, ws.hist_part,
+                                                                                 use_runs ? ws.geom_runs : nullptr, sh.tm);
         }
-        // always kMaxPasses launch groups; frames whose index needs fewer passes drop out on the device
-        const int64_t hist_row = (int64_t)kMaxRadix * n_sort_tiles;
+        // the first histogram exists: k_reproject_emit counted it over its candidate-aligned tiles (v.emit_tiles), or
+        // k_voxel_keys_hist0 did just now for a point sort (a group-run sort counts its own records in pass 0)
+        const bool have_hist0 = v.emit_tiles > 0 || (!use_runs && !v.keys_ready);
         // the last pass of a point sort leaves, instead of the sorted indices, whether each record starts a run, one byte per
         // record (nothing but the run heads reads those indices; the group-run sort's are read by k_centroid_groups)
         uint8_t* const side = use_runs ? nullptr : ws.side;
         const int64_t side_stride = side_frame_stride(cap);
-        for (int pass = 0; pass < kMaxPasses; ++pass) {
-            // the first pass over the candidate-aligned tiles the emit pass counted (emit_part_range)
-            const bool emit_tiles = pass == 0 && v.emit_tiles > 0;
-            // (k_voxel_keys_hist0 or k_reproject_emit counted the first pass's digits)
-            if (!(pass == 0 && ((!use_runs && !v.keys_ready) || emit_tiles))) {
-                ProfScope ps(pf, O3DR_K_SORT_HIST, s);
-                k_radix_hist<<<grid, kSortThreads, 0, s>>>(ws.keys[0], ws.keys[1], cap, sort_geom, pass, n_sort_tiles,
-                                                          ws.hist, ws.hist_part, tm);
-            }
-            {
-                ProfScope ps(pf, O3DR_K_OTHER, s);
-                if (tm)
-                    k_scan_hist_tm<<<F, 1024, tm_lds, s>>>(ws.hist, sort_geom, pass, n_sort_tiles, emit_tiles ? 1 : 0);
-                else
-                    launch_scan(s, ws.hist, hist_row, hist_row, F, nullptr, nullptr, ws.scan_partial, sort_geom, pass,
-                                n_sort_tiles);
-            }
-            {
-                ProfScope ps(pf, O3DR_K_SORT_SCATTER, s);
-                k_radix_scatter_lane<<<dim3(xcd_grid((int64_t)n_sort_tiles * kScatParts), F), kScatThreads, 0, s>>>(
-                    ws.keys[0], ws.vals[0], ws.keys[1], ws.vals[1], cap, sort_geom, pass, n_sort_tiles, ws.hist, ws.hist_part, tm,
-                    emit_tiles ? ws.tile_cnt : nullptr, v.emit_tiles, side, side_stride);
-            }
-        }
+        for (int pass = 0; pass < kMaxPasses; ++pass) radix_pass(pf, s, ws, sh, sort_geom, pass, have_hist0, v.emit_tiles, side, side_stride);
+        segment_runs(pf, s, ws, sh, sort_geom, side, side_stride);
         const dim3 sgrid(n_seg_tiles, F);
-        {
-            ProfScope ps(pf, O3DR_K_SEGMENT, s);
-            // (each of the two takes the frames of its kind and returns at once for the others)
-            k_run_heads<<<dim3(cdiv64(n_seg_tiles, kHeadWaves), F), kHeadWaves * kWave, 0, s>>>(ws.keys[0], ws.keys[1], cap, sort_geom, n_seg_tiles,
-                                                                                       ws.seg_cnt, -1, ws.head_bits, side != nullptr);
-            if (side)
-                k_side_heads<<<dim3(cdiv64(n_seg_tiles, kHeadWaves), F), kHeadWaves * kWave, 0, s>>>(side, side_stride, sort_geom, n_seg_tiles,
-                                                                                            ws.seg_cnt, ws.head_bits);
-        }
-        {
-            ProfScope ps(pf, O3DR_K_OTHER, s);
-            launch_scan(s, ws.seg_cnt, n_seg_tiles, n_seg_tiles, F, ws.n_vox, nullptr, ws.scan_partial);
-        }
-        {
-            ProfScope ps(pf, O3DR_K_SEGMENT, s);
-            k_run_starts<<<dim3(cdiv64(n_seg_tiles, kStartWaves), F), kStartWaves * kWave, 0, s>>>(ws.keys[0], ws.keys[1], cap, sort_geom, n_seg_tiles, ws.seg_cnt, ws.n_vox,
-                                              ws.seg_start, -1, nullptr, nullptr, nullptr, 0.f, ws.head_bits);
-        }
         if (v.min_points > 1) {  // (grouped clouds filter inside k_centroid_groups and drop out of these on the device)
             {
                 ProfScope ps(pf, O3DR_K_SEGMENT, s);
@@ -406,9 +455,8 @@ void launch_voxel_grid(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelAr
             }
             n_keep = ws.n_out;
         }
+        if (v.test_corrupt) corrupt_payload(s, ws, sort_geom);
     }
-    if (v.test_corrupt && cap > 0 && !v.passthrough)
-        k_test_corrupt_payload<<<1, 1, 0, s>>>(ws.vals[0], ws.vals[1], sort_geom);
     if (cap > 0 && use_runs) {
         // one wave per voxel group; the groups' output counts are only known afterwards
         {
@@ -470,79 +518,20 @@ void launch_voxel_grid(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelAr
     }
 }
 
-// The grouped steps of launch_voxel_grid up to the group list (heads, run starts, run sort, group starts), on the tail of
+// The grouped steps of launch_voxel_grid up to the group list (group_run_front, the passes, segment_runs), on the tail of
 // an incremental merge; the cloud always takes group runs (its groups are folded by k_inc_fold, which has no point path)
 void launch_inc_runs(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_point* in, int64_t n, const float leaf[3], float z_offset,
                      const uint8_t* rec_heads, int64_t first, int test_corrupt)
 {
-    const int64_t cap = n;
-    const int n_sort_tiles = cdiv64(cap, kSortTile);
-    const int n_seg_tiles = cdiv64(cap, kSegTile);
-    const size_t tm_lds = hist_tm_lds(n_sort_tiles);
-    const int tm = hist_tm(n_sort_tiles);
-    const VoxelGeom* sort_geom = ws.geom_runs;
+    const SortShape sh(n, 1);
     {
         ProfScope ps(pf, O3DR_K_OTHER, s);
         k_voxel_geom<<<1, 256, 0, s>>>(ws.mm, ws.mm_stride, 1, ws.n_valid, leaf[0], leaf[1], leaf[2], z_offset, ws.geom);
     }
-    {
-        ProfScope ps(pf, O3DR_K_KEYGEN, s);
-        if (rec_heads) {
-            const int64_t bytes = (int64_t)n_seg_tiles * 256;
-            k_inc_heads_shift<<<cdiv64(bytes, 256), 256, 0, s>>>(rec_heads, (uint64_t)first, (uint64_t)n, ws.head_bits, (uint64_t)bytes);
-            k_head_counts<<<cdiv64(n_seg_tiles, 4), 256, 0, s>>>(ws.head_bits, ws.geom, n_seg_tiles, ws.seg_cnt);
-        } else {
-            k_group_heads<<<n_seg_tiles, 256, 0, s>>>(in, ws.geom, z_offset, n_seg_tiles, ws.seg_cnt, ws.head_bits);
-        }
-    }
-    {
-        ProfScope ps(pf, O3DR_K_OTHER, s);
-        launch_scan(s, ws.seg_cnt, n_seg_tiles, n_seg_tiles, 1, ws.n_runs, nullptr, ws.scan_partial);
-    }
-    {
-        ProfScope ps(pf, O3DR_K_SEGMENT, s);
-        k_run_geom<<<1, 64, 0, s>>>(ws.geom, ws.n_runs, 1, ws.geom_runs, 1, INT64_MAX);
-        k_run_starts<<<dim3(cdiv64(n_seg_tiles, kStartWaves), 1), kStartWaves * kWave, 0, s>>>(
-            ws.keys[0], ws.keys[1], cap, ws.geom, n_seg_tiles, ws.seg_cnt, ws.n_runs, ws.run_start, 0, ws.keys[1], ws.geom_runs, in,
-            z_offset, ws.head_bits);
-    }
-    const dim3 grid(n_sort_tiles, 1);
-    const int64_t hist_row = (int64_t)kMaxRadix * n_sort_tiles;
-    for (int pass = 0; pass < kMaxPasses; ++pass) {
-        {
-            ProfScope ps(pf, O3DR_K_SORT_HIST, s);
-            k_radix_hist<<<grid, kSortThreads, 0, s>>>(ws.keys[0], ws.keys[1], cap, sort_geom, pass, n_sort_tiles, ws.hist, ws.hist_part, tm);
-        }
-        {
-            ProfScope ps(pf, O3DR_K_OTHER, s);
-            if (tm)
-                k_scan_hist_tm<<<1, 1024, tm_lds, s>>>(ws.hist, sort_geom, pass, n_sort_tiles, 0);
-            else
-                launch_scan(s, ws.hist, hist_row, hist_row, 1, nullptr, nullptr, ws.scan_partial, sort_geom, pass, n_sort_tiles);
-        }
-        {
-            ProfScope ps(pf, O3DR_K_SORT_SCATTER, s);
-            k_radix_scatter_lane<<<dim3(xcd_grid((int64_t)n_sort_tiles * kScatParts), 1), kScatThreads, 0, s>>>(
-                ws.keys[0], ws.vals[0], ws.keys[1], ws.vals[1], cap, sort_geom, pass, n_sort_tiles, ws.hist, ws.hist_part, tm, nullptr, 0,
-                nullptr, 0);
-        }
-    }
-    {
-        ProfScope ps(pf, O3DR_K_SEGMENT, s);
-        k_run_heads<<<dim3(cdiv64(n_seg_tiles, kHeadWaves), 1), kHeadWaves * kWave, 0, s>>>(ws.keys[0], ws.keys[1], cap, sort_geom,
-                                                                                             n_seg_tiles, ws.seg_cnt, -1, ws.head_bits, 0);
-    }
-    {
-        ProfScope ps(pf, O3DR_K_OTHER, s);
-        launch_scan(s, ws.seg_cnt, n_seg_tiles, n_seg_tiles, 1, ws.n_vox, nullptr, ws.scan_partial);
-    }
-    {
-        ProfScope ps(pf, O3DR_K_SEGMENT, s);
-        k_run_starts<<<dim3(cdiv64(n_seg_tiles, kStartWaves), 1), kStartWaves * kWave, 0, s>>>(
-            ws.keys[0], ws.keys[1], cap, sort_geom, n_seg_tiles, ws.seg_cnt, ws.n_vox, ws.seg_start, -1, nullptr, nullptr, nullptr, 0.f,
-            ws.head_bits);
-    }
-    if (test_corrupt) k_test_corrupt_payload<<<1, 1, 0, s>>>(ws.vals[0], ws.vals[1], sort_geom);
+    group_run_front(pf, s, ws, sh, in, z_offset, rec_heads, first, n, 1, INT64_MAX);
+    for (int pass = 0; pass < kMaxPasses; ++pass) radix_pass(pf, s, ws, sh, ws.geom_runs, pass);
+    segment_runs(pf, s, ws, sh, ws.geom_runs, nullptr, 0);
+    if (test_corrupt) corrupt_payload(s, ws, ws.geom_runs);
 }
 
 void launch_inc_fold(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_point* in, float z_offset, const IncFoldArgs& a,
@@ -894,16 +883,15 @@ void launch_set_cloud_count(hipStream_t s, CloudCounters* cc, uint64_t n) { k_se
 void launch_partition_count(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelArgs& v, int n_parts, uint64_t* counts_dev,
                             uint32_t* overflow_dev, const void* hdrs_dev, int n_hdrs)
 {
-    const int64_t cap = v.cap;
-    const int n_sort_tiles = cdiv64(cap, kSortTile);
-    const int64_t hist_row = (int64_t)kMaxRadix * n_sort_tiles;
+    const SortShape sh(v.cap, 1);
+    const int n_sort_tiles = sh.n_sort_tiles;
     ProfScope ps(pf, O3DR_K_OTHER, s);
     if (hdrs_dev) k_fold_headers<<<1, 1, 0, s>>>(reinterpret_cast<const CloudHeader*>(hdrs_dev), n_hdrs, ws.mm);
     k_voxel_geom<<<1, 256, 0, s>>>(ws.mm, ws.mm_stride, 1, v.n_dev, v.leaf[0], v.leaf[1], v.leaf[2], v.z_offset, ws.geom);
     // count per (part, tile), scan; n_parts <= kMaxRadix
     k_part_plan<<<1, 1, 0, s>>>(ws.geom, n_parts);
     k_part_count<<<n_sort_tiles, kSortThreads, 0, s>>>(v.in, ws.geom, v.z_offset, n_parts, n_sort_tiles, ws.hist);
-    launch_scan(s, ws.hist, hist_row, hist_row, 1, nullptr, nullptr, ws.scan_partial, ws.geom, 0, n_sort_tiles);
+    launch_scan(s, ws.hist, sh.hist_row, sh.hist_row, 1, nullptr, nullptr, ws.scan_partial, ws.geom, 0, n_sort_tiles);
     k_part_counts_scanned<<<cdiv64(n_parts, 64), 64, 0, s>>>(ws.hist, ws.geom, n_parts, n_sort_tiles, counts_dev, overflow_dev);
 }
 void launch_partition_move(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelArgs& v, int n_parts, o3dr_point* out,
@@ -922,25 +910,11 @@ void launch_partition(Profiler* pf, hipStream_t s, Workspace& ws, const VoxelArg
 }
 
 // `passes` stable radix passes over ws.keys[0] / ws.vals (the plan in ws.geom, frames of at most cap records); the records
-// end in buffer passes & 1
+// end in buffer passes & 1.  (Runs inside its caller's profiler scope: no scopes of its own.)
 static void launch_radix_passes(Workspace& ws, hipStream_t s, int64_t cap, int passes, int frames = 1)
 {
-    const int F = frames;
-    const int n_sort_tiles = cdiv64(cap, kSortTile);
-    const int64_t hist_row = (int64_t)kMaxRadix * n_sort_tiles;
-    const size_t tm_lds = hist_tm_lds(n_sort_tiles);
-    const int tm = hist_tm(n_sort_tiles);
-    for (int pass = 0; pass < passes && pass < kMaxPasses; ++pass) {
-        k_radix_hist<<<dim3(n_sort_tiles, F), kSortThreads, 0, s>>>(ws.keys[0], ws.keys[1], cap, ws.geom, pass, n_sort_tiles, ws.hist,
-                                                                    ws.hist_part, tm);
-        if (tm)
-            k_scan_hist_tm<<<F, 1024, tm_lds, s>>>(ws.hist, ws.geom, pass, n_sort_tiles, 0);
-        else
-            launch_scan(s, ws.hist, hist_row, hist_row, F, nullptr, nullptr, ws.scan_partial, ws.geom, pass, n_sort_tiles);
-        k_radix_scatter_lane<<<dim3(xcd_grid((int64_t)n_sort_tiles * kScatParts), F), kScatThreads, 0, s>>>(
-            ws.keys[0], ws.vals[0], ws.keys[1], ws.vals[1], cap, ws.geom, pass, n_sort_tiles, ws.hist, ws.hist_part, tm, nullptr, 0,
-            nullptr, 0);
-    }
+    const SortShape sh(cap, frames);
+    for (int pass = 0; pass < passes && pass < kMaxPasses; ++pass) radix_pass(nullptr, s, ws, sh, ws.geom, pass);
 }
 
 // The search grid of a batch of clouds (see o3dr_device.h): plan, cell ids, radix sort of the cell ids, cell populations,

@@ -159,6 +159,19 @@ def test_range_fold_reaches_the_point_past_the_grid(cell_ctx):
 
 
 @pytest.mark.gpu
+def test_one_point_past_the_one_workgroup_histogram_scan(cell_ctx):
+    """95 sort tiles of 8192 records are the most whose digit histograms one workgroup scans in LDS (hist_tm in
+    o3dr_kernels.hip); 95 * 8192 + 1 points are the fewest whose sort takes the chunked scan.  129 cells: two passes"""
+    n = 95 * 8192 + 1
+    xyz = box_cloud(-20, 3, 43, 3, n, seed=31)
+    assert box_cells(xyz, 1.0) == 129
+    tiles = check_plane(cell_ctx, xyz, 1.0, H=1)
+    assert len(tiles) == 129 and int(tiles["n_points"].sum()) == n
+    info = check_mesh(cell_ctx, xyz, 1.0)
+    assert info.n_vertices == 129 and info.n_shadowed == n - 129
+
+
+@pytest.mark.gpu
 def test_a_box_on_both_sides_of_the_origin(cell_ctx):
     xyz = box_cloud(-3, -2, 6, 5, 400, seed=21)
     tiles = check_plane(cell_ctx, xyz, 1.0, H=4)

@@ -375,6 +375,20 @@ def test_nn_map_scale_bit_exact_at_every_translation(sg_ctx, big_map, md):
 
 
 @pytest.mark.gpu
+def test_nn_target_one_point_past_the_one_workgroup_histogram_scan(sg_ctx):
+    """95 sort tiles of 8192 records are the most whose digit histograms one workgroup scans in LDS (hist_tm in
+    o3dr_kernels.hip); a target of 95 * 8192 + 1 points is the smallest whose search-grid sort takes the chunked scan"""
+    n = 95 * 8192 + 1
+    t = map_like(1024, 761, 31)[:n]
+    assert len(t) == n
+    q = big_queries(t, 20000, 32)
+    stats = {}
+    got = _check_nn(sg_ctx, q, t, what=n, oracle=lambda a, b, m: nn_tree(a, b, m, stats=stats))
+    assert stats["fallback"] <= 1e-3 * len(q), stats  # the reference stays cheap (not a property of the kernel)
+    assert (got[0] != NONE).all() and len(np.unique(got[0])) > 15000
+
+
+@pytest.mark.gpu
 def test_nn_skewed_density(sg_ctx):
     """20 000 points in one or two columns of a grid that four far corners stretch: finite and infinite radius"""
     t = skewed(22222, 11)
