@@ -45,6 +45,20 @@ int o3dr_test_plane_hypotheses(o3dr_ctx* ctx, float* planes, uint32_t* counts, i
  * copies).  bytes = 0 restores the default; a value below one frame's need still gives groups of one frame.  The
  * results must not depend on it. */
 int o3dr_test_orb_scratch_limit(o3dr_ctx* ctx, int64_t bytes);
+/* Fills every per-call scratch block this context currently owns with `byte` (0..255), over the block's whole capacity
+ * and not just the last call's layout, in stream order on the context's stream: one hipMemsetAsync per block, no kernel.
+ * *bytes_filled = the sum.  No later call's result may depend on it (DESIGN.md "Scratch contract").
+ * Filled: the shared operator blocks op[0..4]; the sort / voxel workspace, its point block and the outlier removal's
+ * block; the staging buffers (st_*, st2_*, st_blur*, st_hist, st_xchg, st_merge, st_gather); nn_q, nn_t, nn_cells, nn_src;
+ * the incremental merge's per-call buffers (scratch, tg, tmatch, flag, src, keep, partial, words) and its fallback result;
+ * the 4 KiB misc block and the single-shot counters.
+ * Never touched, because they carry state from call to call: cloud_big, its second buffer, its counters, running bounding
+ * box and recorded run heads; the incremental merge's groups, cell offsets, cells and box; the cached tables (bilateral
+ * weights, ORB pattern, Q table); the plane hypotheses kept for o3dr_test_plane_hypotheses; the sort statistics.
+ * Two things that live in scratch are lost: a pending o3dr_cloud_big_slice_counts_dev table (dropped, as the ICP calls
+ * drop it: o3dr_cloud_big_place_slices then asks for the counts again) and the distances o3dr_test_sor_distances reads.
+ * O3DR_ERR_INVALID_ARG: null context, hooks off, byte outside 0..255, bytes_filled NULL. */
+int o3dr_test_fill_scratch(o3dr_ctx* ctx, int32_t byte, int64_t* bytes_filled);
 
 #ifdef __cplusplus
 }

@@ -386,6 +386,7 @@ SYMBOLS = [
     ("o3dr_test_fail_at", C.c_int, [_vp, _i32]),
     ("o3dr_test_plane_hypotheses", C.c_int, [_vp, _vp, _vp, _i64, _pi64]),
     ("o3dr_test_orb_scratch_limit", C.c_int, [_vp, _i64]),
+    ("o3dr_test_fill_scratch", C.c_int, [_vp, _i32, _pi64]),
     ("o3dr_device_info", C.c_int, [_vp, C.c_char_p, _i32, C.POINTER(_i32), _pi64]),
 ]
 

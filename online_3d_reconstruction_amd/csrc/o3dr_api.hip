@@ -252,6 +252,9 @@ static int carve(o3dr_ctx* c, DevBuf& b, Layout&& layout)
 static int ws_ensure(o3dr_ctx* c, int frames, int64_t cap, bool need_pts, bool grp_tmp = false)
 {
     if (cap < 1) cap = 1;
+    // whoever sizes the workspace is about to write it: a pending (slice, tile) table of o3dr_cloud_big_slice_counts_dev
+    // is gone, and o3dr_cloud_big_place_slices must not move points by what the arrays hold afterwards
+    c->place_ub = -1;
     const size_t elems = (size_t)frames * (size_t)(cap + 1);
     const size_t emit_tiles = (size_t)frames * (size_t)((cap + kEmitTile - 1) / kEmitTile);
     const size_t sort_tiles = (size_t)frames * (size_t)((cap + kSortTile - 1) / kSortTile);
@@ -2916,6 +2919,40 @@ extern "C" int o3dr_test_sor_distances(o3dr_ctx* c, float* out, int64_t n)
     if (n == 0) return O3DR_OK;
     HIPCHK(hipMemcpyAsync(out, c->ws.sor_dist, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    return O3DR_OK;
+}
+
+// Every per-call scratch block the context owns, over its whole capacity (DESIGN.md "Scratch contract": the scratch list).
+// Not here, because they carry something from one call to the next: cloud_big, cloud_alt, cc_big, cloud_box, cloud_heads;
+// inc.grp / off / cells / box; bil_tab, orb_pat, q_lut; pl_hyp; stats_dev.
+extern "C" int o3dr_test_fill_scratch(o3dr_ctx* c, int32_t byte, int64_t* bytes_filled)
+{
+    if (bytes_filled) *bytes_filled = 0;
+    CTX_ENTER(c);
+    if (!c->test_hooks) return fail(O3DR_ERR_INVALID_ARG, "test hooks are off (create the context with O3DR_TEST_HOOKS=1)");
+    if (byte < 0 || byte > 255 || !bytes_filled) return fail(O3DR_ERR_INVALID_ARG, "byte must be 0..255, bytes_filled not NULL");
+    c->place_ub = -1;  // a pending (slice, tile) table lives in the workspace
+    int64_t total = 0;
+    std::vector<DevBuf*> blocks = {&c->ws_block, &c->ws_pts_block, &c->ws_sor_block, &c->st_disp, &c->st_bgr, &c->st_in, &c->st_out,
+                                   &c->st_kp, &c->st_kpoff, &c->st_poses, &c->st_blur, &c->st_blur_in, &c->st_hist, &c->st_xchg,
+                                   &c->st_merge, &c->st_gather, &c->nn_q, &c->nn_t, &c->nn_cells, &c->nn_src, &c->inc.scratch,
+                                   &c->inc.tg, &c->inc.tmatch, &c->inc.flag, &c->inc.src, &c->inc.keep, &c->inc.partial,
+                                   &c->inc.words, &c->inc.fb};
+    for (int i = 0; i < 2; ++i) {
+        blocks.push_back(&c->st2_disp[i]);
+        blocks.push_back(&c->st2_bgr[i]);
+        blocks.push_back(&c->st2_poses[i]);
+    }
+    for (DevBuf& b : c->op) blocks.push_back(&b);
+    // (the uploads of a host frame call run on their own stream, but c->stream has waited for each of them)
+    for (DevBuf* b : blocks) {
+        if (!b->p || !b->cap) continue;
+        HIPCHK(hipMemsetAsync(b->p, byte, b->cap, c->stream));
+        total += (int64_t)b->cap;
+    }
+    HIPCHK(hipMemsetAsync(c->misc_dev, byte, 4096, c->stream));
+    HIPCHK(hipMemsetAsync(c->cc_tmp, byte, sizeof(CloudCounters), c->stream));
+    *bytes_filled = total + 4096 + (int64_t)sizeof(CloudCounters);
     return O3DR_OK;
 }
 
