@@ -1542,7 +1542,11 @@ int  o3dr_pose_graph_refine(o3dr_ctx* ctx, const uint8_t* desc, const int64_t* o
 #define O3DR_K_SEG_ASSIGN   30  /* image segmentation: seeds, the K + 1 assignments with their tile sums, the updates */
 #define O3DR_K_SEG_LABEL    31  /* ... components, merge of the small ones, ordered numbering, outputs */
 #define O3DR_K_MULTIVIEW    32  /* multi-view filter and fusion: the one launch of a call */
-#define O3DR_K_NUM          33
+#define O3DR_K_GROUND_WINNER 33  /* ground filter (o3dr_terrain.h): the minimum surface */
+#define O3DR_K_GROUND_ITER   34  /* ... the iterations: four sliding min / max passes each */
+#define O3DR_K_GROUND_FILL   35  /* ... the DTM: ground words, the raster's fill passes */
+#define O3DR_K_GROUND_POINTS 36  /* ... the pass over the points: mask, height above ground */
+#define O3DR_K_NUM          37
 /* Bracket every launch of kernel `kernel_id` (or all kernels if -1) with HIP events on the
  * context's stream; 0 launches are bracketed when disabled (the default). */
 int o3dr_profile_enable(o3dr_ctx* ctx, int32_t kernel_id, int32_t enable);

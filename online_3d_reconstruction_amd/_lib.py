@@ -25,11 +25,13 @@ K_DISP_MEDIAN, K_DISP_LABEL, K_DISP_SPECKLE = 25, 26, 27
 K_RECTIFY_MAPS, K_RECTIFY_REMAP = 28, 29
 K_SEG_ASSIGN, K_SEG_LABEL = 30, 31
 K_MULTIVIEW = 32
+K_GROUND_WINNER, K_GROUND_ITER, K_GROUND_FILL, K_GROUND_POINTS = 33, 34, 35, 36
 KERNEL_NAMES = ["reproject_count", "reproject_emit", "voxel_keys", "radix_hist", "radix_scatter", "run_segments",
                 "centroid", "other", "centroid_runs", "plane_disp_sums", "plane_disp_fit", "plane_disp_eval",
                 "orb_pyramid", "orb_fast", "orb_candidates", "orb_select", "orb_describe", "match", "pose_chain", "ransac",
                 "graph_moments", "graph_solve", "stereo_census", "stereo_paths", "stereo_winner", "disp_median", "disp_label",
-                "disp_speckle", "rectify_maps", "rectify_remap", "seg_assign", "seg_label", "multiview"]
+                "disp_speckle", "rectify_maps", "rectify_remap", "seg_assign", "seg_label", "multiview", "ground_winner", "ground_iter",
+                "ground_fill", "ground_points"]
 
 
 class O3drError(RuntimeError):
@@ -110,6 +112,29 @@ class RasterResultStruct(C.Structure):
 
 RASTER_SELECT = {"first": 0, "top": 1, "bottom": 2}
 RASTER_MAX_FILL_RADIUS, RASTER_MAX_CELLS = 32, 1 << 28
+
+
+# include/o3dr_terrain.h
+class GroundParamsStruct(C.Structure):
+    _fields_ = [("cell_size", C.c_double), ("cx0", C.c_int32), ("cy0", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("max_window_radius", C.c_int32), ("window_base", C.c_int32), ("exponential", C.c_int32), ("reserved0", C.c_int32),
+                ("slope", C.c_double), ("initial_distance", C.c_double), ("max_distance", C.c_double), ("fill_radius", C.c_int32),
+                ("reserved1", C.c_int32)]
+
+
+class GroundOutputsStruct(C.Structure):
+    _fields_ = [("ground", C.c_void_p), ("height_above_ground", C.c_void_p), ("dtm", C.c_void_p), ("cell_state", C.c_void_p)]
+
+
+class GroundResultStruct(C.Structure):
+    _fields_ = [("cx0", C.c_int32), ("cy0", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("n_inside", C.c_int64),
+                ("n_outside", C.c_int64), ("n_occupied", C.c_int64), ("n_ground_cells", C.c_int64), ("n_ground_points", C.c_int64),
+                ("n_dtm_filled", C.c_int64), ("n_dtm_empty", C.c_int64), ("n_iterations", C.c_int32), ("reserved", C.c_int32),
+                ("n_removed", C.c_int64 * 16)]
+
+
+O3DR_GROUND_MAX_WINDOW_RADIUS = 128
+O3DR_GROUND_MAX_ITERATIONS = 16
 
 
 class PlaneDispParamsStruct(C.Structure):
@@ -339,6 +364,10 @@ SYMBOLS = [
     ("o3dr_raster_extent", C.c_int, [_vp, _vp, _i64, C.c_double, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _i32]),
     ("o3dr_rasterize_map", C.c_int, [_vp, _vp, _i64, C.POINTER(RasterParamsStruct), C.POINTER(RasterOutputsStruct),
                                      C.POINTER(RasterResultStruct), _i32]),
+    ("o3dr_ground_default_params", None, [C.POINTER(GroundParamsStruct)]),
+    ("o3dr_ground_schedule", C.c_int, [C.POINTER(GroundParamsStruct), _vp, _vp, C.POINTER(_i32)]),
+    ("o3dr_ground_filter", C.c_int, [_vp, _vp, _i64, C.POINTER(GroundParamsStruct), C.POINTER(GroundOutputsStruct),
+                                     C.POINTER(GroundResultStruct), _i32]),
     ("o3dr_plane_disp_default_params", None, [C.POINTER(PlaneDispParamsStruct)]),
     ("o3dr_plane_fit_disparity", C.c_int, [_vp, _vp, _i64, _i64, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32,
                                            C.POINTER(PlaneDispParamsStruct), _vp, _vp, _pu32, _i32]),

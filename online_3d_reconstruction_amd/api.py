@@ -92,6 +92,45 @@ class RasterInfo:
 
 
 @dataclass
+class GroundInfo:
+    """o3dr_ground_filter's record (include/o3dr_terrain.h): the box in cells, the points inside and outside it, the
+    occupied cells, the ground cells and points, the cells the DTM's fill reached and those without a value, and the
+    cells every iteration removed (n_removed has n_iterations entries)."""
+    cx0: int
+    cy0: int
+    width: int
+    height: int
+    n_inside: int
+    n_outside: int
+    n_occupied: int
+    n_ground_cells: int
+    n_ground_points: int
+    n_dtm_filled: int
+    n_dtm_empty: int
+    n_iterations: int
+    n_removed: tuple
+
+
+def _ground_params(cell_size, max_window_radius, window_base, exponential, slope, initial_distance, max_distance):
+    prm = L.GroundParamsStruct()
+    L.load_library().o3dr_ground_default_params(C.byref(prm))
+    prm.cell_size, prm.max_window_radius, prm.window_base = float(cell_size), int(max_window_radius), int(window_base)
+    prm.exponential = 1 if exponential else 0
+    prm.slope, prm.initial_distance, prm.max_distance = float(slope), float(initial_distance), float(max_distance)
+    return prm
+
+
+def groundSchedule(cell_size, max_window_radius=16, window_base=2, exponential=True, slope=0.7, initial_distance=0.15,
+                   max_distance=10.0):
+    """The ground filter's window schedule (contract: include/o3dr_terrain.h "ground filter", step 3) -> (radii int32,
+    thresholds float32), one entry per iteration.  Host only: needs the built library, not a GPU."""
+    prm = _ground_params(cell_size, max_window_radius, window_base, exponential, slope, initial_distance, max_distance)
+    radii, thr, n = np.zeros(16, np.int32), np.zeros(16, np.float32), C.c_int32(0)
+    L.check(L.load_library().o3dr_ground_schedule(C.byref(prm), radii.ctypes.data, thr.ctypes.data, C.byref(n)))
+    return radii[:n.value].copy(), thr[:n.value].copy()
+
+
+@dataclass
 class RigidResult:
     """o3dr_estimate_rigid_transform's result for one segment: T (float64 4x4, src -> tgt), the rms residual at T over the
     used pairs, their number and the status (RIGID_OK, RIGID_TOO_FEW, RIGID_DEGENERATE; T is the identity unless OK)."""
@@ -1410,6 +1449,52 @@ class Context:
                                int(res.n_occupied), int(res.n_shadowed), int(res.n_filled), int(res.n_empty), float(res.z_min),
                                float(res.z_max)),)
         return ret
+
+    # -- ground filter: ground mask, DTM, height above ground (this build's own) -----------------
+    def groundFilter(self, pts, cell_size, bounds=None, max_window_radius=16, window_base=2, exponential=True, slope=0.7,
+                     initial_distance=0.15, max_distance=10.0, fill_radius=0, return_height=False, return_dtm=False,
+                     return_state=False, return_info=False):
+        """The bare-earth ground mask of a cloud by a progressive morphological filter on the XY cells of cell_size
+        (contract: include/o3dr_terrain.h "ground filter", DESIGN.md "Ground filter").  bounds = (cx0, cy0, width, height)
+        in cells, None: the cloud's own box (rasterExtent).  The windows grow to max_window_radius cells (1..128) by
+        window_base, exponentially or linearly; slope, initial_distance and max_distance give every window's height
+        threshold; fill_radius (0..32 cells) fills the DTM under what was removed.  numpy POINT arrays give numpy arrays,
+        torch [N,4] 4-byte CUDA tensors such as finalize(device=...) give CUDA tensors.
+        -> ground uint8 [n][, height_above_ground float32 [n]][, dtm float32 [height, width]][, cell_state uint8
+        [height, width]][, GroundInfo]"""
+        pts, n = self._cloud(pts)
+        p_in, mem, _k = _ptr(pts)
+        cx0, cy0, W, H = (int(v) for v in (self.rasterExtent(pts, cell_size) if bounds is None else bounds))
+        prm = _ground_params(cell_size, max_window_radius, window_base, exponential, slope, initial_distance, max_distance)
+        prm.cx0, prm.cy0, prm.width, prm.height, prm.fill_radius = cx0, cy0, W, H, int(fill_radius)
+        ok = 1 <= W and 1 <= H and W * H <= L.RASTER_MAX_CELLS  # (else the call fails before it writes anything)
+        shape = (H, W) if ok else (1, 1)
+        want = [("ground", np.uint8, (n,))]
+        want += [("height_above_ground", np.float32, (n,))] if return_height else []
+        want += [("dtm", np.float32, shape)] if return_dtm else []
+        want += [("cell_state", np.uint8, shape)] if return_state else []
+        outs = L.GroundOutputsStruct()
+        arrays = []
+        if mem == L.MEM_DEVICE:
+            import torch
+            for name, dt, shp in want:
+                t = torch.empty(shp, dtype=getattr(torch, np.dtype(dt).name), device=pts.device)
+                setattr(outs, name, t.data_ptr() if t.numel() else None)
+                arrays.append(t)
+            self._order_after_torch()
+        else:
+            for name, dt, shp in want:
+                t = np.empty(shp, dt)
+                setattr(outs, name, t.ctypes.data if t.size else None)
+                arrays.append(t)
+        res = L.GroundResultStruct()
+        L.check(self._lib.o3dr_ground_filter(self._h, p_in if n else None, n, C.byref(prm), C.byref(outs), C.byref(res), mem))
+        ret = tuple(arrays)
+        if return_info:
+            ret += (GroundInfo(int(res.cx0), int(res.cy0), int(res.width), int(res.height), int(res.n_inside), int(res.n_outside),
+                               int(res.n_occupied), int(res.n_ground_cells), int(res.n_ground_points), int(res.n_dtm_filled),
+                               int(res.n_dtm_empty), int(res.n_iterations), tuple(int(v) for v in res.n_removed[:res.n_iterations])),)
+        return ret[0] if len(ret) == 1 else ret
 
     def voxelGrid(self, pts, leaf, min_points=0, z_offset=0.0, return_status=False):
         """pcl::VoxelGrid<PointXYZRGB> as the reference configures it (pose_functions.cpp:1689-1700)."""

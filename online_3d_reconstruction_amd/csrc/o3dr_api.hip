@@ -138,12 +138,12 @@ struct o3dr_ctx {
     // Scratch of the operators after that (MLS, plane, mesh, match, keypoints, rigid fit, the image-stack operators), shared:
     // nothing in it outlives a call, and within one call every block is laid out by one carve().  OP_IN: staged host inputs
     // (descriptor pool; src / tgt / mask; image stacks).  OP_WORK: the arrays sized from the arguments (plane: points in tile
-    // order + run heads; mesh: run heads + vertex tables; raster: the cells' words + column offsets; match: pair table +
-    // chunk partials; rigid: segment table + sums; ORB, stereo, the disparity and multi-view filters, segmentation: a group
+    // order + run heads; mesh: run heads + vertex tables; raster: the cells' words + column offsets; ground: those and
+    // four fp32 rasters; match: pair table + chunk partials; rigid: segment table + sums; ORB, stereo, the disparity and multi-view filters, segmentation: a group
     // of frames' arrays and the per-frame counters; rectification: the staged host map).  OP_LATE: the arrays sized from a
     // count read back mid-call (plane: tile tables).
-    // OP_OUT: the staged outputs of a host call.  OP_FLAGS: 256 bytes of flags / ranges / counters (MlsFlags, PlaneFlags,
-    // MeshFlags, RasterFlags).
+    // OP_OUT: the staged outputs of a host call.  OP_FLAGS: the flags / ranges / counters of one operator (MlsFlags,
+    // PlaneFlags, MeshFlags, RasterFlags: 256 bytes; GroundFlags: 384).
     enum { OP_IN, OP_WORK, OP_LATE, OP_OUT, OP_FLAGS, OP_BUFS };
     DevBuf op[OP_BUFS];
     DevBuf orb_pat;  // o3dr_orb_detect: the steered table
@@ -3062,6 +3062,10 @@ struct RasterFlags {
     alignas(64) CellFlags cell;
     alignas(64) uint32_t counters[12];  // RasterArgs::counters
 };
+struct GroundFlags {
+    alignas(64) CellFlags cell;
+    alignas(64) uint32_t counters[kGroundCounterWords];  // GroundArgs::counters
+};
 // The index box of a read-back range: its corner and widths -> o, the width of the largest dense cell id -> *nbits.
 // Fails, with the operator's texts, if an index left int32 or the box holds more than `limit` cells.
 static int cell_box(const CellFlags& h, uint64_t limit, const char* off_int32_text, const char* limit_text, CellOrder* o, int* nbits)
@@ -3618,7 +3622,8 @@ static int raster_cell_size(double cs, float* inv)
 }
 // The cloud staged, every coordinate checked for being finite and every cell index for fitting int32: one
 // synchronisation, the cloud's cell range in *h.  The range pass's partials are all of OP_WORK until the box is known.
-static int raster_cloud(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, int mem, RasterArgs& a, RasterFlags* f, CellFlags* h)
+template <class Flags>
+static int raster_cloud(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, int mem, RasterArgs& a, Flags* f, CellFlags* h)
 {
     CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) { w.take(a.part, (size_t)cell_range_parts(n) * kPartWords); }));
     CHK(cloud_stage_finite(c, cloud, n, mem, &f->cell.bad, &h->bad, sizeof *h, &a.cloud, [&]() -> int {
@@ -3763,6 +3768,153 @@ extern "C" int o3dr_rasterize_map(o3dr_ctx* c, const o3dr_point* cloud, int64_t 
         outs.add(out->distance2, cells);
     }
     const int rc = entered(c, [&] { return rasterize_map(c, cloud, n, p, out, outs, res, mem); });
+    if (rc != O3DR_OK) {  // host outputs zeroed on error
+        if (res) memset(res, 0, sizeof *res);
+        outs.zero();
+    }
+    return rc;
+}
+
+// -------------------------------------------------------------------------------------------------
+// ground filter: ground mask, DTM, height above ground (kernels/ground.inc; contract: include/o3dr_terrain.h; DESIGN.md
+// "Ground filter")
+// -------------------------------------------------------------------------------------------------
+extern "C" void o3dr_ground_default_params(o3dr_ground_params* p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof *p);  // cell_size and the box: no usable default
+    p->max_window_radius = 16, p->window_base = 2, p->exponential = 1;  // pcl::ProgressiveMorphologicalFilter's defaults
+    p->slope = 0.7, p->initial_distance = 0.15, p->max_distance = 10.0;
+}
+
+// the parameters in the struct's order (whole: with the box and fill_radius), then the schedule of the contract's step 3
+static int ground_schedule(const o3dr_ground_params* p, bool whole, float* inv, int32_t radii[16], float thr[16], int32_t* n_iter)
+{
+    CHK(raster_cell_size(p->cell_size, inv));
+    if (whole) {
+        if (p->width < 1 || p->height < 1) return fail(O3DR_ERR_INVALID_ARG, "the raster's box needs width, height >= 1");
+        if ((int64_t)p->cx0 + p->width - 1 > INT32_MAX || (int64_t)p->cy0 + p->height - 1 > INT32_MAX)
+            return fail(O3DR_ERR_INVALID_ARG, "the raster's box leaves int32");
+    }
+    if (p->max_window_radius < 1 || p->max_window_radius > O3DR_GROUND_MAX_WINDOW_RADIUS)
+        return fail(O3DR_ERR_INVALID_ARG, "max_window_radius must be in 1..128");
+    if (p->window_base < (p->exponential ? 2 : 1))
+        return fail(O3DR_ERR_INVALID_ARG, "window_base must be >= 2 (exponential) or >= 1 (linear)");
+    if (!(std::isfinite(p->slope) && p->slope >= 0.0)) return fail(O3DR_ERR_INVALID_ARG, "slope must be finite and >= 0");
+    if (!(std::isfinite(p->initial_distance) && p->initial_distance >= 0.0))
+        return fail(O3DR_ERR_INVALID_ARG, "initial_distance must be finite and >= 0");
+    if (!(std::isfinite(p->max_distance) && p->max_distance >= 0.0)) return fail(O3DR_ERR_INVALID_ARG, "max_distance must be finite and >= 0");
+    if (whole && (p->fill_radius < 0 || p->fill_radius > O3DR_RASTER_MAX_FILL_RADIUS))
+        return fail(O3DR_ERR_INVALID_ARG, "fill_radius must be in 0..32");
+    int n = 0;
+    int64_t r = p->exponential ? 1 : p->window_base, prev = 0;
+    while (n < O3DR_GROUND_MAX_ITERATIONS && r <= p->max_window_radius) {
+        const double t = n == 0 ? p->initial_distance : p->slope * ((double)(2 * (r - prev)) * p->cell_size) + p->initial_distance;
+        radii[n] = (int32_t)r;
+        thr[n] = (float)std::min(t, p->max_distance);
+        ++n;
+        prev = r;
+        r = p->exponential ? r * p->window_base : r + p->window_base;
+    }
+    if (n == 0) return fail(O3DR_ERR_INVALID_ARG, "the window schedule has no iteration (window_base > max_window_radius)");
+    *n_iter = n;
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_ground_schedule(const o3dr_ground_params* p, int32_t radii[16], float thresholds[16], int32_t* n_iterations)
+{
+    if (radii) memset(radii, 0, 16 * sizeof(int32_t));
+    if (thresholds) memset(thresholds, 0, 16 * sizeof(float));
+    if (n_iterations) *n_iterations = 0;
+    if (!p || !radii || !thresholds || !n_iterations) return fail(O3DR_ERR_INVALID_ARG, "params / radii / thresholds / n_iterations is NULL");
+    int32_t r[16] = {0};
+    float t[16] = {0.f}, inv;
+    int32_t n = 0;
+    CHK(ground_schedule(p, false, &inv, r, t, &n));
+    memcpy(radii, r, sizeof r);
+    memcpy(thresholds, t, sizeof t);
+    *n_iterations = n;
+    return O3DR_OK;
+}
+
+static int ground_filter(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const o3dr_ground_params* p, const o3dr_ground_outputs* out,
+                         Outputs& outs, o3dr_ground_result* res, int32_t mem)
+{
+    if (!p) return fail(O3DR_ERR_INVALID_ARG, "params is NULL");
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    GroundArgs a;
+    memset(&a, 0, sizeof a);
+    RasterArgs& r = a.r;
+    CHK(ground_schedule(p, true, &r.inv, a.radius, a.thr, &a.n_iter));
+    CHK(nn_check_cloud(n, cloud, kMeshCloudMax));
+    c->place_ub = -1;
+    r.n = (uint32_t)n;
+    r.cx0 = p->cx0, r.cy0 = p->cy0, r.width = p->width, r.height = p->height;
+    r.select = O3DR_RASTER_BOTTOM, r.R = p->fill_radius;
+    r.cell_size = p->cell_size;
+    GroundFlags* f;
+    CHK(op_flags(c, &f));
+    if (n > 0) {
+        CellFlags h;
+        CHK(raster_cloud(c, cloud, n, mem, r, f, &h));
+    }
+    const int64_t cells = (int64_t)p->width * p->height;
+    if (cells > (int64_t)O3DR_RASTER_MAX_CELLS) return fail(O3DR_ERR_INVALID_ARG, kRasterTooLarge);
+    const int64_t parts = ground_parts(a);
+    float* dtm_tmp = nullptr;  // the point pass reads the DTM and the states: scratch when the caller does not ask for them
+    uint8_t* state_tmp = nullptr;
+    CHK(outs.stage(c));
+    CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
+        w.take(r.part, (size_t)parts * kPartWords);
+        w.take(r.win, (size_t)cells);
+        w.take(a.zl, (size_t)cells);
+        w.take(a.t1, (size_t)cells);
+        w.take(a.t2, (size_t)cells);
+        w.take(a.run, (size_t)cells);
+        if (r.R > 0) w.take(r.col, (size_t)cells);
+        if (!(out && out->dtm)) w.take(dtm_tmp, (size_t)cells);
+        if (!(out && out->cell_state)) w.take(state_tmp, (size_t)cells);
+    }));
+    a.counters = f->counters;
+    if (out) {
+        a.ground = outs.dev(out->ground), a.hag = outs.dev(out->height_above_ground);
+        r.height_map = outs.dev(out->dtm), a.state = outs.dev(out->cell_state);
+    }
+    if (!r.height_map) r.height_map = dtm_tmp;
+    if (!a.state) a.state = state_tmp;
+    launch_ground(&c->prof, c->stream, a);
+    HIPCHK(hipGetLastError());
+    uint32_t cnt[kGroundCounterWords];
+    HIPCHK(hipMemcpyAsync(cnt, f->counters, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+    CHK(outs.copy_back(c));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (res) {
+        res->cx0 = p->cx0, res->cy0 = p->cy0, res->width = p->width, res->height = p->height;
+        res->n_inside = cnt[0], res->n_outside = cnt[1];
+        res->n_ground_cells = cnt[4], res->n_dtm_filled = cnt[5], res->n_dtm_empty = cnt[6];
+        res->n_ground_points = cnt[12];
+        res->n_iterations = a.n_iter;
+        res->n_occupied = res->n_ground_cells;
+        for (int k = 0; k < a.n_iter; ++k) res->n_occupied += (res->n_removed[k] = cnt[16 + 4 * k]);
+    }
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_ground_filter(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const o3dr_ground_params* p,
+                                  const o3dr_ground_outputs* out, o3dr_ground_result* res, int32_t mem)
+{
+    if (res) memset(res, 0, sizeof *res);
+    Outputs outs{mem};
+    int64_t cells = 0;
+    if (p && p->width >= 1 && p->height >= 1 && (int64_t)p->width * p->height <= (int64_t)O3DR_RASTER_MAX_CELLS)
+        cells = (int64_t)p->width * p->height;
+    if (out) {
+        outs.add(out->ground, cloud_points(n, kMeshCloudMax));
+        outs.add(out->height_above_ground, cloud_points(n, kMeshCloudMax));
+        outs.add(out->dtm, cells);
+        outs.add(out->cell_state, cells);
+    }
+    const int rc = entered(c, [&] { return ground_filter(c, cloud, n, p, out, outs, res, mem); });
     if (rc != O3DR_OK) {  // host outputs zeroed on error
         if (res) memset(res, 0, sizeof *res);
         outs.zero();

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/o3dr.h"
+#include "../../include/o3dr_terrain.h"
 
 namespace o3dr {
 
@@ -560,6 +561,47 @@ inline int64_t raster_winner_parts(int64_t n) { return cell_range_parts(n); }
 // launch_raster: a.win set to empty, the winner pass, the column pass (R > 0), the row pass with the outputs and the shade
 // stencil; the counters folded into a.counters
 void launch_raster(Profiler* pf, hipStream_t s, const RasterArgs& a);
+// ground filter (kernels/ground.inc; contract: include/o3dr_terrain.h "ground filter").  The raster's own passes run on
+// `r`: the winner pass (select = BOTTOM) into r.win, and at the end the fill passes on r.win with every cell that is not
+// ground set empty, r.height_map = the DTM (r.R = fill_radius; r.color, r.shade, r.source, r.distance2 unset).
+struct GroundArgs {
+    RasterArgs r;
+    int32_t n_iter;
+    int32_t radius[O3DR_GROUND_MAX_ITERATIONS];
+    float thr[O3DR_GROUND_MAX_ITERATIONS];
+    float* zl;                    // width * height: Z of a live cell, +inf for an empty or removed one
+    float* t1;                    // width * height: the row passes' results
+    float* t2;                    // width * height: E masked to the live cells (-inf elsewhere)
+    float* run;                   // width * height: the column passes' suffix minima / maxima per block of 2r + 1 rows
+    uint8_t* state;               // width * height: 0 empty, 1 live / ground, 2 + k removed by iteration k
+    uint32_t* counters;           // 80 words: n_inside n_outside - - | n_ground_cells n_dtm_filled n_dtm_empty - | (the resolve's z range) |
+                                  //   n_ground_points - - - | n_removed[k] - - - for k = 0..15
+    uint8_t* ground;              // n or nullptr
+    float* hag;                   // n or nullptr
+};
+constexpr int kGroundTileW = 256;         // cells of one row per workgroup of the row passes
+constexpr int kGroundColRowsMax = 4096;   // row blocks a column pass spreads over workgroups at most (the others by stride)
+constexpr int kGroundCounterWords = 16 + 4 * O3DR_GROUND_MAX_ITERATIONS;
+inline int64_t ground_col_groups(int64_t width) { return (width + 255) / 256; }
+inline int64_t ground_col_rows(int64_t height, int r)
+{
+    const int64_t blocks = (height + 2 * (int64_t)r) / (2 * (int64_t)r + 1) + 1;  // blocks of 2r + 1 rows, and the one before row 0
+    return blocks < kGroundColRowsMax ? blocks : kGroundColRowsMax;
+}
+// workgroup partials of a call: the winner and the point pass, the raster's tiles, the column pass of every iteration
+inline int64_t ground_parts(const GroundArgs& a)
+{
+    int64_t parts = raster_tiles(a.r.width, a.r.height);
+    if (raster_winner_parts(a.r.n) > parts) parts = raster_winner_parts(a.r.n);
+    for (int k = 0; k < a.n_iter; ++k) {
+        const int64_t g = ground_col_groups(a.r.width) * ground_col_rows(a.r.height, a.radius[k]);
+        if (g > parts) parts = g;
+    }
+    return parts;
+}
+// launch_ground: the minimum surface, the iterations (enqueued back to back: nothing is read back), the DTM with its fill,
+// the point pass; every count folded into a.counters
+void launch_ground(Profiler* pf, hipStream_t s, const GroundArgs& a);
 // plane-fitted disparity per segment label (kernels/plane_disparity.inc).  `table`: kPdSums 64-bit sums per (frame, label) -
 // n Sx Sy Sxx Sxy Syy Sd Sxd Syd Sdd and the pixel count -, zeroed here; thr: d participates iff (int)d > thr; flag: a
 // device word, bit 0 set when a label >= n_labels was seen.  launch_plane_disp runs the three steps for `frames` frames:

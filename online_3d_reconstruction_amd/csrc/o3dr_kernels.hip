@@ -34,6 +34,7 @@
 //   plane        RANSAC plane segmentation per XY tile
 //   mesh         height-field surface mesh over the XY cells
 //   raster       the merged map as images: one point per XY cell, separable hole fill, the output images, shaded relief
+//   ground       bare-earth ground filter on the raster's cells: sliding window minima / maxima, DTM, height above ground
 //   match        Hamming 2-NN descriptor matching, index-aligned 3-D keypoints, the batched rigid fit
 //   orb          ORB features: grey pyramid, FAST score + box sums, candidates, exact selection, steered BRIEF
 //   stereo       stereo disparity: grey + census, semi-global aggregation (one wave per scan line), winner + left-right check
@@ -68,6 +69,7 @@ namespace o3dr {
 #include "kernels/plane.inc"
 #include "kernels/mesh.inc"
 #include "kernels/raster.inc"
+#include "kernels/ground.inc"
 #include "kernels/match.inc"
 #include "kernels/plane_disparity.inc"
 #include "kernels/orb.inc"
@@ -1250,6 +1252,51 @@ void launch_raster(Profiler* pf, hipStream_t s, const RasterArgs& a)
     k_fold4_u32<<<1, kFoldThreads, 0, s>>>(a.part, gt, 0, 2, 2, 2, 2, a.counters + 4);
     k_fold4_u32<<<1, kFoldThreads, 0, s>>>(a.part, gt, 4, 0, 1, 2, 2, a.counters + 8);
     if (a.shade) k_raster_shade<<<gc, kRasterThreads, 0, s>>>(a);
+}
+
+// ground filter (kernels/ground.inc)
+void launch_ground(Profiler* pf, hipStream_t s, const GroundArgs& a)
+{
+    const RasterArgs& r = a.r;
+    const int64_t cells = (int64_t)r.width * r.height;
+    const int gc = cdiv64(cells, kGroundThreads);
+    const int gw = (int)raster_winner_parts(r.n);
+    {
+        ProfScope ps(pf, O3DR_K_GROUND_WINNER, s);
+        (void)hipMemsetAsync(r.win, 0xff, (size_t)cells * sizeof(unsigned long long), s);
+        if (gw > 0) k_raster_winner<<<gw, kRasterThreads, 0, s>>>(r);
+        k_fold4_u32<<<1, kFoldThreads, 0, s>>>(r.part, gw, 0, 2, 2, 2, 2, a.counters);
+        k_ground_init<<<gc, kGroundThreads, 0, s>>>(a);
+    }
+    const int64_t tiles_x = ((int64_t)r.width + kGroundTileW - 1) / kGroundTileW, gx = ground_col_groups(r.width);
+    const unsigned g_row = (unsigned)(tiles_x * r.height);
+    for (int k = 0; k < a.n_iter; ++k) {
+        ProfScope ps(pf, O3DR_K_GROUND_ITER, s);
+        const int rad = a.radius[k];
+        int p = 1;
+        while (2 * p <= 2 * rad + 1) p *= 2;  // the largest power of two within the window
+        const unsigned g_col = (unsigned)(gx * ground_col_rows(r.height, rad));
+        k_ground_row<false><<<g_row, kGroundThreads, 0, s>>>(a.zl, a.t1, r.width, tiles_x, rad, p);
+        k_ground_col_suffix<false><<<g_col, kGroundThreads, 0, s>>>(a.t1, a.run, r.width, r.height, gx, rad);
+        k_ground_col_window<false><<<g_col, kGroundThreads, 0, s>>>(a, a.t1, gx, rad, 0.f, 0);
+        k_ground_row<true><<<g_row, kGroundThreads, 0, s>>>(a.t2, a.t1, r.width, tiles_x, rad, p);
+        k_ground_col_suffix<true><<<g_col, kGroundThreads, 0, s>>>(a.t1, a.run, r.width, r.height, gx, rad);
+        k_ground_col_window<true><<<g_col, kGroundThreads, 0, s>>>(a, a.t1, gx, rad, a.thr[k], (uint8_t)(2 + k));
+        k_fold4_u32<<<1, kFoldThreads, 0, s>>>(r.part, (int)g_col, 0, 2, 2, 2, 2, a.counters + 16 + 4 * k);
+    }
+    {
+        ProfScope ps(pf, O3DR_K_GROUND_FILL, s);
+        k_ground_ground_words<<<gc, kGroundThreads, 0, s>>>(a);
+        if (r.R > 0) k_raster_fill_col<<<gc, kRasterThreads, 0, s>>>(r);
+        const int gt = (int)raster_tiles(r.width, r.height);
+        k_raster_resolve<<<gt, kRasterThreads, 0, s>>>(r);
+        k_fold4_u32<<<1, kFoldThreads, 0, s>>>(r.part, gt, 0, 2, 2, 2, 2, a.counters + 4);
+    }
+    {
+        ProfScope ps(pf, O3DR_K_GROUND_POINTS, s);
+        if (gw > 0) k_ground_points<<<gw, kGroundThreads, 0, s>>>(a);
+        k_fold4_u32<<<1, kFoldThreads, 0, s>>>(r.part, gw, 0, 2, 2, 2, 2, a.counters + 12);
+    }
 }
 
 }  // namespace o3dr

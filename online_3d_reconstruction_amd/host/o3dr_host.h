@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/o3dr.h"
+#include "../../include/o3dr_terrain.h"
 
 namespace o3dr_host {
 
@@ -136,6 +137,12 @@ public:
     int ortho_fill_radius = 0;           // parsed and ignored without --orthophoto / --orthophoto_out
     bool ortho_light_set = false;
     double ortho_light[3] = {0.0, 0.0, 0.0};
+    bool ground_filter = false;      // --ground_filter file.ply: o3dr_ground_filter of one PLY -> terrain_ / objects_<file>, dtm_<file>.png
+    int ground_max_window = 16;      // --ground_max_window r (cells, 1..128), --ground_window_base b, --ground_linear,
+    int ground_window_base = 2;      // --ground_slope s, --ground_initial_distance m, --ground_max_distance m,
+    bool ground_linear = false;      // --ground_fill_radius r (cells, 0..32); parsed and ignored without --ground_filter
+    double ground_slope = 0.7, ground_initial_distance = 0.15, ground_max_distance = 10.0;
+    int ground_fill_radius = 0;
     int device_id = 0;
     int n_gpus = 1;                 // --gpus N: frames sharded over devices device_id .. device_id+N-1, one host thread and
                                     // one context each, merged through o3dr_merge_partitioned (RCCL)
@@ -252,6 +259,7 @@ private:
     void run_segment_cloud();                       // --segment_cloud_only
     void run_mesh_surface();                        // --mesh_surface
     void run_orthophoto();                          // --orthophoto
+    void run_ground_filter();                       // --ground_filter
     // the map's rasters of a host cloud (o3dr_raster_extent, o3dr_rasterize_map with the --ortho_* flags) as PNGs, rows in
     // descending cy (north up); shade_path is written with --ortho_light only.  Prints the box, the counts and the call time.
     void write_map_rasters(o3dr_ctx* c, const PointCloud& cloud, const std::string& ortho_path, const std::string& height_path,

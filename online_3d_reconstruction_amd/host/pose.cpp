@@ -502,6 +502,19 @@ void Pose::printUsage()
             "       [--orthophoto_out prefix]  (reconstruction run: the same images of the final merged cloud, after cloud.ply, as\n"
             "                     <prefix>ortho.png, <prefix>height.png and <prefix>shade.png; not available with --gpus N > 1,\n"
             "                     --partitioned_merge, --reference_fanout; elsewhere the --ortho_* flags are parsed and ignored)\n"
+            "./pose --ground_filter file.ply [--voxel_size m] [--ground_max_window r] [--ground_window_base b] [--ground_linear]\n"
+            "       [--ground_slope s] [--ground_initial_distance m] [--ground_max_distance m] [--ground_fill_radius r]\n"
+            "                     (bare-earth ground filter on the XY cells of size m: the minimum surface is opened with windows\n"
+            "                     growing to r cells (1..128, default 16) by powers of b (default 2) or, with --ground_linear, by\n"
+            "                     steps of b, and a cell rising above the opening by more than s (default 0.7) times the window's\n"
+            "                     growth in metres plus --ground_initial_distance (default 0.15), at most --ground_max_distance\n"
+            "                     (default 10), is removed; writes the ground points as terrain_<file> and the others as\n"
+            "                     objects_<file>, both in input order, and the terrain model as dtm_<file>.png (16-bit grey, north\n"
+            "                     up, 0 = no data, else 1 + (z - z_min) / step; cells that are not ground take the nearest ground\n"
+            "                     cell within --ground_fill_radius cells, 0..32, default 0) next to the source; prints the box, the\n"
+            "                     schedule, the removed cells per iteration, the ground cells and points and the call time;\n"
+            "                     elsewhere the --ground_* flags are parsed and ignored - the flags and the file names are this\n"
+            "                     build's own)\n"
             "./pose --find_features image.png [--orb_n_features n] [--orb_levels n] [--orb_scale s] [--orb_fast_threshold t]\n"
             "                     (ORB keypoints of one image: prints the count per level and writes one \"x y\" per line as\n"
             "                     <image>.keypoints.txt, the --keypoints_dir format - the flags and the file name are this build's own)\n"
@@ -607,6 +620,14 @@ int Pose::parseCmdArgs(int argc, char** argv)
         else if (a == "--mesh_normals") mesh_normals = true;
         else if (a == "--orthophoto") { files(i, "file.ply", read_PLY_filename0); orthophoto = true; }
         else if (a == "--orthophoto_out") orthophoto_out = need(i);
+        else if (a == "--ground_filter") { files(i, "file.ply", read_PLY_filename0); ground_filter = true; }
+        else if (a == "--ground_max_window") ground_max_window = atoi(need(i));
+        else if (a == "--ground_window_base") ground_window_base = atoi(need(i));
+        else if (a == "--ground_linear") ground_linear = true;
+        else if (a == "--ground_slope") ground_slope = atof(need(i));
+        else if (a == "--ground_initial_distance") ground_initial_distance = atof(need(i));
+        else if (a == "--ground_max_distance") ground_max_distance = atof(need(i));
+        else if (a == "--ground_fill_radius") ground_fill_radius = atoi(need(i));
         else if (a == "--ortho_select") ortho_select = need(i);
         else if (a == "--ortho_fill_radius") ortho_fill_radius = atoi(need(i));
         else if (a == "--ortho_light") {
@@ -748,6 +769,19 @@ int Pose::parseCmdArgs(int argc, char** argv)
         if (ortho_fill_radius < 0 || ortho_fill_radius > O3DR_RASTER_MAX_FILL_RADIUS) throw runtime_error("--ortho_fill_radius must be in 0..32");
         const double ln = sqrt((ortho_light[0] * ortho_light[0] + ortho_light[1] * ortho_light[1]) + ortho_light[2] * ortho_light[2]);
         if (ortho_light_set && !(isfinite(ln) && ln > 0.0)) throw runtime_error("--ortho_light must be a finite vector that is not zero");
+    }
+    if (ground_filter) {
+        if (!ifstream(read_PLY_filename0)) throw runtime_error("could not read " + read_PLY_filename0);
+        if (ground_max_window < 1 || ground_max_window > O3DR_GROUND_MAX_WINDOW_RADIUS) throw runtime_error("--ground_max_window must be in 1..128");
+        if (ground_window_base < (ground_linear ? 1 : 2))
+            throw runtime_error("--ground_window_base must be >= 2, or >= 1 with --ground_linear");
+        if (ground_linear && ground_window_base > ground_max_window)
+            throw runtime_error("--ground_window_base must not exceed --ground_max_window with --ground_linear (no window fits)");
+        if (!(isfinite(ground_slope) && ground_slope >= 0.0)) throw runtime_error("--ground_slope must be finite and >= 0");
+        if (!(isfinite(ground_initial_distance) && ground_initial_distance >= 0.0))
+            throw runtime_error("--ground_initial_distance must be finite and >= 0");
+        if (!(isfinite(ground_max_distance) && ground_max_distance >= 0.0)) throw runtime_error("--ground_max_distance must be finite and >= 0");
+        if (ground_fill_radius < 0 || ground_fill_radius > O3DR_RASTER_MAX_FILL_RADIUS) throw runtime_error("--ground_fill_radius must be in 0..32");
     }
     if (run3d_reconstruction && gpu_keypoints) batched_path_only("--gpu_keypoints", true);
     if (run3d_reconstruction && gpu_disparity) {
@@ -1003,6 +1037,76 @@ void Pose::write_map_rasters(o3dr_ctx* c, const PointCloud& cloud, const string&
     if (ortho_light_set && !write_png_grey8(shade_path, shade_up.data(), H, W)) throw runtime_error("could not write " + shade_path);
     cerr << "Saved " << W << " x " << H << " map rasters to " << ortho_path << ", " << height_path
          << (ortho_light_set ? ", " + shade_path : string()) << endl;
+}
+
+// --ground_filter: the ground points, the others and the terrain model of one PLY (o3dr_ground_filter; contract:
+// include/o3dr_terrain.h "ground filter"), written as terrain_<file>, objects_<file> and dtm_<file>.png next to the source.
+void Pose::run_ground_filter()
+{
+    PointCloud::Ptr cloud = read_PLY_File(read_PLY_filename0);
+    const int64_t n = (int64_t)cloud->points.size();
+    o3dr_ground_params prm;
+    o3dr_ground_default_params(&prm);
+    prm.cell_size = voxel_size;
+    prm.max_window_radius = ground_max_window, prm.window_base = ground_window_base, prm.exponential = ground_linear ? 0 : 1;
+    prm.slope = ground_slope, prm.initial_distance = ground_initial_distance, prm.max_distance = ground_max_distance;
+    prm.fill_radius = ground_fill_radius;
+    int32_t radii[16], n_iter = 0;
+    float thr[16];
+    chk(o3dr_ground_schedule(&prm, radii, thr, &n_iter), "o3dr_ground_schedule");
+    o3dr_ctx* c = ctx_for_this_thread();
+    const auto t0 = chrono::steady_clock::now();
+    chk(o3dr_raster_extent(c, cloud->points.data(), n, voxel_size, &prm.cx0, &prm.cy0, &prm.width, &prm.height, O3DR_MEM_HOST),
+        "o3dr_raster_extent");
+    const int W = prm.width, H = prm.height;
+    const size_t cells = (size_t)W * (size_t)H;
+    vector<uint8_t> ground((size_t)n);
+    vector<float> dtm(cells);
+    o3dr_ground_outputs out = {ground.data(), nullptr, dtm.data(), nullptr};
+    o3dr_ground_result res;
+    chk(o3dr_ground_filter(c, cloud->points.data(), n, &prm, &out, &res, O3DR_MEM_HOST), "o3dr_ground_filter");
+    const double ms = chrono::duration<double, milli>(chrono::steady_clock::now() - t0).count();
+    PointCloud::Ptr terrain(new PointCloud()), objects(new PointCloud());
+    for (int64_t i = 0; i < n; ++i) (ground[(size_t)i] ? terrain : objects)->points.push_back(cloud->points[(size_t)i]);
+    // the DTM as 16-bit grey, the height PNG's encoding from the DTM's own z range (-0.0f taken as 0.0f)
+    float z_min = NAN, z_max = NAN;
+    for (float z : dtm)
+        if (z == z) {
+            z = z == 0.f ? 0.f : z;
+            z_min = z_min == z_min ? min(z_min, z) : z, z_max = z_max == z_max ? max(z_max, z) : z;
+        }
+    const double step = max(((double)z_max - (double)z_min) / 65534.0, ldexp(1.0, -15));
+    vector<uint16_t> d16(cells);
+    for (int r = 0; r < H; ++r) {  // rows in descending cy: north up, not mirrored
+        const size_t src = (size_t)(H - 1 - r) * W, dst = (size_t)r * W;
+        for (int x = 0; x < W; ++x) {
+            const float z = dtm[src + x];
+            d16[dst + x] = z != z ? 0 : (uint16_t)(1 + (int)min(65534.0, floor(((double)z - (double)z_min) / step)));
+        }
+    }
+    char line[256];
+    cout << "points in " << n << " (outside the box " << res.n_outside << ")" << endl;
+    cout << "box cx0 " << res.cx0 << " cy0 " << res.cy0 << " width " << res.width << " height " << res.height << endl;
+    for (int k = 0; k < n_iter; ++k) {
+        snprintf(line, sizeof line, "iteration %d radius %d threshold %.9g removed cells %lld", k, radii[k], (double)thr[k],
+                 (long long)res.n_removed[k]);
+        cout << line << endl;
+    }
+    cout << "cells occupied " << res.n_occupied << ", ground " << res.n_ground_cells << ", dtm filled " << res.n_dtm_filled << ", dtm empty "
+         << res.n_dtm_empty << endl;
+    cout << "ground points " << res.n_ground_points << ", object points " << n - res.n_ground_points << endl;
+    snprintf(line, sizeof line, "dtm z_min %.9g z_max %.9g step %.17g", (double)z_min, (double)z_max, step);
+    cout << line << endl;
+    snprintf(line, sizeof line, "ground filter time %.3f ms", ms);
+    cout << line << endl;
+    for (const auto& o : {make_pair("terrain_", terrain), make_pair("objects_", objects)}) {
+        const string path = next_to(read_PLY_filename0, o.first);
+        if (!save_ply_binary(path, *o.second)) throw runtime_error("could not write " + path);
+        cerr << "Saved Point Cloud with " << o.second->points.size() << " data points to " << path << endl;
+    }
+    const string dtm_path = next_to(read_PLY_filename0, "dtm_", ".png");
+    if (!write_png_grey16(dtm_path, d16.data(), H, W)) throw runtime_error("could not write " + dtm_path);
+    cerr << "Saved " << W << " x " << H << " terrain model to " << dtm_path << endl;
 }
 
 o3dr_orb_params Pose::orb_params() const
@@ -1349,6 +1453,10 @@ Pose::Pose(int argc, char* argv[])
     }
     if (orthophoto) {
         run_orthophoto();
+        return;
+    }
+    if (ground_filter) {
+        run_ground_filter();
         return;
     }
     if (!find_features_png.empty()) {
