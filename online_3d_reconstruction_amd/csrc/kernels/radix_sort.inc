@@ -197,7 +197,6 @@ __device__ __forceinline__ void emit_part_range(const uint32_t* __restrict__ til
         end = begin + kScatTile < n ? begin + kScatTile : n;
     }
 }
-typedef uint32_t u32x4_a4_t __attribute__((ext_vector_type(4), aligned(4)));  // 16-byte load from a 4-byte boundary
 
 // the 16 consecutive records of this lane in part `part` of tile `tile` (+ this thread's scanned histogram entry): every
 // global load of the workgroup is issued here, before any LDS work
@@ -443,7 +442,7 @@ __global__ __launch_bounds__(kScatThreads) void k_radix_scatter_lane(uint32_t* _
     J.pass = pass;
     J.n_tiles = n_tiles;
     J.tm = tm != 0;
-    // side (point sorts in launch_voxel_grid): the last pass leaves the run-head flag of every record, for k_side_heads
+    // side (point sorts in launch_voxel_grid): the last pass leaves the run-head flag of every record, for k_run_heads (side_heads_tile)
     J.heads = (side && pass + 1 == (int)g.passes) ? side + (int64_t)f * side_stride : nullptr;
     J.low_mask = (1u << J.shift) - 1u;
     uint32_t key0[kSortRounds], val0[kSortRounds], g0, back;

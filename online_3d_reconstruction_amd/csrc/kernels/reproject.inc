@@ -184,7 +184,7 @@ __global__ __launch_bounds__(kEmitThreads) void k_reproject_bbox_count(Reproject
     }
     // a workgroup takes kCountTiles consecutive tiles: one set of wave reductions and barriers for both (the counts
     // stay per tile; the box of both goes to the first tile's slot, the other slots get the neutral box)
-    const int f = blockIdx.y, tile0 = blockIdx.x * kCountTiles;
+    const int f = blockIdx.y;
     const uint8_t* disp = a.disp + (int64_t)f * a.disp_fstride;
     const int n_cand = a.Ny * a.Nx;
     float m[12];
@@ -193,60 +193,68 @@ __global__ __launch_bounds__(kEmitThreads) void k_reproject_bbox_count(Reproject
 #pragma unroll
         for (int i = 0; i < 12; ++i) m[i] = T[i];
     }
-    int x0[kCountTiles], y0[kCountTiles];
-    typename DispT<F64>::type d[kCountTiles][4];
-    uint32_t valid[kCountTiles];
+    // (the grid covers the frame's tile groups once, or - the pass behind the conservative box, where nearly every
+    // workgroup returns above - is a few workgroups per frame that walk them)
+    const int n_groups = (a.n_tiles + kCountTiles - 1) / kCountTiles;
+#pragma unroll 1
+    for (int tg = blockIdx.x; tg < n_groups; tg += gridDim.x) {
+        const int tile0 = tg * kCountTiles;
+        int x0[kCountTiles], y0[kCountTiles];
+        typename DispT<F64>::type d[kCountTiles][4];
+        uint32_t valid[kCountTiles];
 #pragma unroll
-    for (int t = 0; t < kCountTiles; ++t) {
-        x0[t] = y0[t] = 0;
-        valid[t] = load_lane_disparities<F64>(a, disp, (tile0 + t) * kEmitTile + (int)threadIdx.x * kEmitPerLane, n_cand, x0[t], y0[t], d[t]);
-    }
-    float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
-    float hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-    uint32_t packed[kCountTiles / 2];  // the tiles' valid candidates of this lane, 16 bits per tile
+        for (int t = 0; t < kCountTiles; ++t) {
+            x0[t] = y0[t] = 0;
+            valid[t] = load_lane_disparities<F64>(a, disp, (tile0 + t) * kEmitTile + (int)threadIdx.x * kEmitPerLane, n_cand, x0[t], y0[t], d[t]);
+        }
+        float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
+        float hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+        uint32_t packed[kCountTiles / 2];  // the tiles' valid candidates of this lane, 16 bits per tile
 #pragma unroll
-    for (int j = 0; j < kCountTiles / 2; ++j) packed[j] = 0;
-    bool any = false;
+        for (int j = 0; j < kCountTiles / 2; ++j) packed[j] = 0;
+        bool any = false;
 #pragma unroll
-    for (int t = 0; t < kCountTiles; ++t) {
-        const int c0 = (tile0 + t) * kEmitTile + (int)threadIdx.x * kEmitPerLane;
-        packed[t / 2] += (uint32_t)__popc(valid[t]) << (16 * (t & 1));
-        any = any || valid[t] != 0u;
+        for (int t = 0; t < kCountTiles; ++t) {
+            const int c0 = (tile0 + t) * kEmitTile + (int)threadIdx.x * kEmitPerLane;
+            packed[t / 2] += (uint32_t)__popc(valid[t]) << (16 * (t & 1));
+            any = any || valid[t] != 0u;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (valid[t] & (1u << k)) {
-                int x, y;
-                if (!F64 && a.vec4) {
-                    x = x0[t] + k;
-                    y = y0[t];
-                } else {
-                    const int c = c0 + k;
-                    const int ry = c / a.Nx, rx = c - ry * a.Nx;
-                    y = a.bb + ry * a.jump;
-                    x = a.cs + rx * a.jump;
+            for (int k = 0; k < 4; ++k) {
+                if (valid[t] & (1u << k)) {
+                    int x, y;
+                    if (!F64 && a.vec4) {
+                        x = x0[t] + k;
+                        y = y0[t];
+                    } else {
+                        const int c = c0 + k;
+                        const int ry = c / a.Nx, rx = c - ry * a.Nx;
+                        y = a.bb + ry * a.jump;
+                        x = a.cs + rx * a.jump;
+                    }
+                    const Pix p = reproject_px<F64>(a, a.lut ? lut_alpha : nullptr, lut_z, m, true, x, y, d[t][k], 0, 0, 0);
+                    lo[0] = fminf(lo[0], p.x); hi[0] = fmaxf(hi[0], p.x);
+                    lo[1] = fminf(lo[1], p.y); hi[1] = fmaxf(hi[1], p.y);
+                    lo[2] = fminf(lo[2], p.z); hi[2] = fmaxf(hi[2], p.z);
                 }
-                const Pix p = reproject_px<F64>(a, a.lut ? lut_alpha : nullptr, lut_z, m, true, x, y, d[t][k], 0, 0, 0);
-                lo[0] = fminf(lo[0], p.x); hi[0] = fmaxf(hi[0], p.x);
-                lo[1] = fminf(lo[1], p.y); hi[1] = fmaxf(hi[1], p.y);
-                lo[2] = fminf(lo[2], p.z); hi[2] = fmaxf(hi[2], p.z);
             }
         }
-    }
 #pragma unroll
-    for (int j = 0; j < kCountTiles / 2; ++j) {
-        const uint32_t s = wave_sum_u32(packed[j]);
-        if ((threadIdx.x & 63) == 0) lds[j * (kEmitThreads / 64) + (threadIdx.x >> 6)] = s;
-    }
-    block_minmax_store<kEmitThreads / 64>(lo, hi, any, mm_lds, mm + ((int64_t)f * a.mm_stride + tile0) * 6);
-    if (!only_if_overflow && threadIdx.x < kCountTiles && tile0 + (int)threadIdx.x < a.n_tiles) {
-        uint32_t t = 0;
+        for (int j = 0; j < kCountTiles / 2; ++j) {
+            const uint32_t s = wave_sum_u32(packed[j]);
+            if ((threadIdx.x & 63) == 0) lds[j * (kEmitThreads / 64) + (threadIdx.x >> 6)] = s;
+        }
+        block_minmax_store<kEmitThreads / 64>(lo, hi, any, mm_lds, mm + ((int64_t)f * a.mm_stride + tile0) * 6);
+        if (!only_if_overflow && threadIdx.x < kCountTiles && tile0 + (int)threadIdx.x < a.n_tiles) {
+            uint32_t t = 0;
 #pragma unroll
-        for (int i = 0; i < kEmitThreads / 64; ++i) t += lds[(threadIdx.x / 2) * (kEmitThreads / 64) + i];
-        tile_cnt[(int64_t)f * a.n_tiles + tile0 + threadIdx.x] = (t >> (16 * (threadIdx.x & 1))) & 0xffffu;
-    }
-    if (threadIdx.x >= 6 && threadIdx.x < 6 * kCountTiles && tile0 + (int)threadIdx.x / 6 < a.n_tiles) {
-        const int a6 = threadIdx.x % 6;
-        mm[((int64_t)f * a.mm_stride + tile0 + threadIdx.x / 6) * 6 + a6] = a6 < 3 ? __builtin_inff() : -__builtin_inff();
+            for (int i = 0; i < kEmitThreads / 64; ++i) t += lds[(threadIdx.x / 2) * (kEmitThreads / 64) + i];
+            tile_cnt[(int64_t)f * a.n_tiles + tile0 + threadIdx.x] = (t >> (16 * (threadIdx.x & 1))) & 0xffffu;
+        }
+        if (threadIdx.x >= 6 && threadIdx.x < 6 * kCountTiles && tile0 + (int)threadIdx.x / 6 < a.n_tiles) {
+            const int a6 = threadIdx.x % 6;
+            mm[((int64_t)f * a.mm_stride + tile0 + threadIdx.x / 6) * 6 + a6] = a6 < 3 ? __builtin_inff() : -__builtin_inff();
+        }
+        __syncthreads();  // (the next round reuses the count words)
     }
 }
 
@@ -262,55 +270,188 @@ __global__ __launch_bounds__(kEmitThreads) void k_reproject_bbox_count(Reproject
 // evaluate the corners with the arithmetic of the emit pass; the box is widened by 2^-17 of the largest sum of
 // magnitudes entering a coordinate, eight times what the fp32 / fp64 roundings of a pixel and a corner can differ from
 // the exact values by (5 roundings of at most 2^-24 of that sum each).
-template <int kTiles>
-__global__ __launch_bounds__(kEmitThreads) void k_reproject_count_cbox(ReprojectArgs a, uint32_t* __restrict__ tile_cnt,
-                                                                       float* __restrict__ mm)
+// Which lane holds which pixels (kWide: the packed-load layout, ReprojectArgs::vec4).  A wave's share of a tile is 256
+// consecutive candidates.  One dword per lane and tile makes every wave load a 256-byte request, and the pass ran at a
+// quarter of the rate k_radix_hist reaches on a read-only stream.  With kWide, lane l takes piece l >> 3 of a round of 8
+// tiles and 32 consecutive candidates of it, as two 16-byte loads from a 4-byte boundary; a 16-candidate group that
+// crosses the end of a ROI row (or of the frame) falls back to its four dword loads - Nx is a multiple of 4 there, so a
+// quad never crosses (and the launcher asks for Nx >= 32: a lane's run then crosses at most one row end).  The SET of pixels a wave covers is the same in both layouts, hence the same ranges, the same
+// corners and margins, and the same box and counts bit for bit.  A tile's count: the sum over the 8 lanes of its piece.
+// n_kp != nullptr: workgroup (0, f) also writes the neutral box of the keypoint slot (n_tiles) and n_kp[f] = 0 - what
+// k_minmax_init does in front of the other paths (no keypoint pass runs in front of this one).
+__device__ __forceinline__ void cbox_quad(uint32_t w, int x0, int y0, int32_t min_disp_u8, uint32_t& cnt, uint32_t& xmn,
+                                          uint32_t& xmx, uint32_t& ymn, uint32_t& ymx, uint32_t& dmn, uint32_t& dmx)
 {
-    __shared__ uint32_t lds[(kTiles / 2) * (kEmitThreads / 64)];
-    __shared__ float mm_lds[6 * (kEmitThreads / 64)];
+    uint32_t m = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t b = (w >> (8 * k)) & 255u;
+        if ((int32_t)b > min_disp_u8) {
+            m |= 1u << k;
+            dmn = u32_min(dmn, b); dmx = u32_max(dmx, b);
+        }
+    }
+    if (m) {
+        cnt += (uint32_t)__popc(m);
+        xmn = u32_min(xmn, (uint32_t)(x0 + __ffs((int)m) - 1)); xmx = u32_max(xmx, (uint32_t)(x0 + 31 - __clz((int)m)));
+        ymn = u32_min(ymn, (uint32_t)y0); ymx = u32_max(ymx, (uint32_t)y0);
+    }
+}
+template <int kTiles, bool kWide>
+__global__ __launch_bounds__(kEmitThreads) void k_reproject_count_cbox(ReprojectArgs a, uint32_t* __restrict__ tile_cnt,
+                                                                       float* __restrict__ mm, uint32_t* __restrict__ n_kp)
+{
+    constexpr int kWaves = kEmitThreads / 64;
+    static_assert(kTiles % 8 == 0, "a round of the wide layout is 8 tiles, one per 8 lanes");
+    __shared__ uint32_t lds[kWide ? kTiles * kWaves : (kTiles / 2) * kWaves];
+    __shared__ float mm_lds[6 * kWaves];
     const int f = blockIdx.y, tile0 = blockIdx.x * kTiles;
     const uint8_t* disp = a.disp + (int64_t)f * a.disp_fstride;
     const int n_cand = a.Ny * a.Nx;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t packed[kTiles / 2];
-#pragma unroll
-    for (int j = 0; j < kTiles / 2; ++j) packed[j] = 0;
-    uint32_t xmn = 0xffffffffu, xmx = 0u, ymn = 0xffffffffu, ymx = 0u, dmn = 0xffffffffu, dmx = 0u;
-    // (all loads first: kTiles independent requests in flight per lane)
-    int x0[kTiles], y0[kTiles];
-    uint32_t d[kTiles][4], valid[kTiles];
-#pragma unroll
-    for (int t = 0; t < kTiles; ++t) {
-        x0[t] = y0[t] = 0;
-        valid[t] = load_lane_disparities<false>(a, disp, (tile0 + t) * kEmitTile + (int)threadIdx.x * kEmitPerLane, n_cand, x0[t], y0[t], d[t]);
+    if (n_kp && blockIdx.x == 0) {
+        if (threadIdx.x < 6)
+            mm[((int64_t)f * a.mm_stride + a.n_tiles) * 6 + threadIdx.x] = threadIdx.x < 3 ? __builtin_inff() : -__builtin_inff();
+        else if (threadIdx.x == 6)
+            n_kp[f] = 0;
     }
+    // the pose of the corner lanes depends on the frame alone: loaded here, not as a second round trip behind the reductions
+    float m[12];
+    {
+        const float* T = a.poses + 16 * (int64_t)f;
 #pragma unroll
-    for (int t = 0; t < kTiles; ++t) {
-        const int c0 = (tile0 + t) * kEmitTile + (int)threadIdx.x * kEmitPerLane;
-        packed[t / 2] += (uint32_t)__popc(valid[t]) << (16 * (t & 1));
+        for (int i = 0; i < 12; ++i) m[i] = T[i];
+    }
+    uint32_t xmn = 0xffffffffu, xmx = 0u, ymn = 0xffffffffu, ymx = 0u, dmn = 0xffffffffu, dmx = 0u;
+    if constexpr (kWide) {
+        constexpr int kRounds = kTiles / 8;
+        // (all loads first: 2 kRounds independent 16-byte requests in flight per lane; the dword loads of a group at a row
+        // end go to registers of their own, so that no load waits for another one's destination)
+        u32x4_a4_t q[kRounds][2];
+        uint32_t e[kRounds][2][4];
+        int lx[kRounds], ly[kRounds];  // the first of the lane's 32 candidates
+        bool whole[kRounds][2];        // the group came as one 16-byte load
+        const int x_end = a.cs + a.Nx;
+        // pixel `step` candidates behind (x, y), step <= 32 <= Nx: at most one row end between them
+        auto behind = [&](int x, int y, int step, int& qx, int& qy) {
+            const bool wrap = x + step >= x_end;
+            qx = x + step - (wrap ? a.Nx : 0);
+            qy = y + (wrap ? 1 : 0);
+        };
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (valid[t] & (1u << k)) {
-                int x, y;
-                if (a.vec4) {
-                    x = x0[t] + k;
-                    y = y0[t];
-                } else {
-                    const int c = c0 + k;
-                    const int ry = c / a.Nx, rx = c - ry * a.Nx;
-                    y = a.bb + ry * a.jump;
-                    x = a.cs + rx * a.jump;
-                }
-                xmn = u32_min(xmn, (uint32_t)x); xmx = u32_max(xmx, (uint32_t)x);
-                ymn = u32_min(ymn, (uint32_t)y); ymx = u32_max(ymx, (uint32_t)y);
-                dmn = u32_min(dmn, d[t][k]); dmx = u32_max(dmx, d[t][k]);
+        for (int r = 0; r < kRounds; ++r) {
+            const int c = (tile0 + 8 * r + (lane >> 3)) * kEmitTile + w * 256 + (lane & 7) * 32;
+            const int ry = c / a.Nx, rx = c - ry * a.Nx;
+            lx[r] = a.cs + rx;
+            ly[r] = a.bb + ry;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                int gx, gy;
+                behind(lx[r], ly[r], 16 * h, gx, gy);
+                whole[r][h] = c + 16 * h < n_cand && gx + 16 <= x_end;  // (the frame ends with a row)
+                q[r][h] = u32x4_a4_t{0u, 0u, 0u, 0u};
+                if (whole[r][h]) q[r][h] = *reinterpret_cast<const u32x4_a4_t*>(disp + (int64_t)gy * a.disp_pitch + gx);
             }
         }
-    }
 #pragma unroll
-    for (int j = 0; j < kTiles / 2; ++j) {
-        const uint32_t s = wave_sum_u32(packed[j]);
-        if (lane == 0) lds[j * (kEmitThreads / 64) + w] = s;
+        for (int r = 0; r < kRounds; ++r) {
+            const int c = (tile0 + 8 * r + (lane >> 3)) * kEmitTile + w * 256 + (lane & 7) * 32;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) e[r][h][j] = 0u;
+                if (!whole[r][h]) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        if (c + 16 * h + 4 * j < n_cand) {
+                            int qx, qy;
+                            behind(lx[r], ly[r], 16 * h + 4 * j, qx, qy);
+                            e[r][h][j] = *reinterpret_cast<const uint32_t*>(disp + (int64_t)qy * a.disp_pitch + qx);
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < kRounds; ++r) {
+            const int c = (tile0 + 8 * r + (lane >> 3)) * kEmitTile + w * 256 + (lane & 7) * 32;
+            uint32_t wd[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) wd[k] = whole[r][k >> 2] ? q[r][k >> 2][k & 3] : e[r][k >> 2][k & 3];
+            // Dense frames: when all 32 candidates of every lane of the wave exist and are valid, their ranges are those of
+            // all the bytes and of the run of pixels itself, and nothing is decided pixel by pixel.
+            uint32_t bmn = 255u, bmx = 0u;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const uint32_t bt = (wd[k] >> (8 * i)) & 255u;
+                    bmn = u32_min(bmn, bt); bmx = u32_max(bmx, bt);
+                }
+            }
+            uint32_t cnt = 0;
+            if (__all(c + 32 <= n_cand && (int32_t)bmn > a.min_disp_u8)) {
+                cnt = 32;
+                dmn = u32_min(dmn, bmn); dmx = u32_max(dmx, bmx);
+                const bool wrap = lx[r] + 32 > x_end;  // the run goes on in the next row: both rows' ends are covered
+                xmn = u32_min(xmn, (uint32_t)(wrap ? a.cs : lx[r])); xmx = u32_max(xmx, (uint32_t)(wrap ? x_end - 1 : lx[r] + 31));
+                ymn = u32_min(ymn, (uint32_t)ly[r]); ymx = u32_max(ymx, (uint32_t)(ly[r] + (wrap ? 1 : 0)));
+            } else {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    if (c + 4 * k < n_cand) {
+                        int qx, qy;
+                        behind(lx[r], ly[r], 4 * k, qx, qy);
+                        cbox_quad(wd[k], qx, qy, a.min_disp_u8, cnt, xmn, xmx, ymn, ymx, dmn, dmx);
+                    }
+                }
+            }
+            // the piece's count: over its 8 lanes, which share a 16-lane row
+            cnt += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cnt, 0x111, 0xf, 0xf, false);  // row_shr:1
+            cnt += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cnt, 0x112, 0xf, 0xf, false);  // row_shr:2
+            cnt += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cnt, 0x114, 0xf, 0xf, false);  // row_shr:4
+            if ((lane & 7) == 7) lds[(8 * r + (lane >> 3)) * kWaves + w] = cnt;
+        }
+    } else {
+        uint32_t packed[kTiles / 2];
+#pragma unroll
+        for (int j = 0; j < kTiles / 2; ++j) packed[j] = 0;
+        // (all loads first: kTiles independent requests in flight per lane)
+        int x0[kTiles], y0[kTiles];
+        uint32_t d[kTiles][4], valid[kTiles];
+#pragma unroll
+        for (int t = 0; t < kTiles; ++t) {
+            x0[t] = y0[t] = 0;
+            valid[t] = load_lane_disparities<false>(a, disp, (tile0 + t) * kEmitTile + (int)threadIdx.x * kEmitPerLane, n_cand, x0[t], y0[t], d[t]);
+        }
+#pragma unroll
+        for (int t = 0; t < kTiles; ++t) {
+            const int c0 = (tile0 + t) * kEmitTile + (int)threadIdx.x * kEmitPerLane;
+            packed[t / 2] += (uint32_t)__popc(valid[t]) << (16 * (t & 1));
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (valid[t] & (1u << k)) {
+                    int x, y;
+                    if (a.vec4) {
+                        x = x0[t] + k;
+                        y = y0[t];
+                    } else {
+                        const int c = c0 + k;
+                        const int ry = c / a.Nx, rx = c - ry * a.Nx;
+                        y = a.bb + ry * a.jump;
+                        x = a.cs + rx * a.jump;
+                    }
+                    xmn = u32_min(xmn, (uint32_t)x); xmx = u32_max(xmx, (uint32_t)x);
+                    ymn = u32_min(ymn, (uint32_t)y); ymx = u32_max(ymx, (uint32_t)y);
+                    dmn = u32_min(dmn, d[t][k]); dmx = u32_max(dmx, d[t][k]);
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kTiles / 2; ++j) {
+            const uint32_t s = wave_sum_u32(packed[j]);
+            if (lane == 0) lds[j * kWaves + w] = s;
+        }
     }
     xmn = wave_min_u32(xmn); xmx = wave_max_u32(xmx);
     ymn = wave_min_u32(ymn); ymx = wave_max_u32(ymx);
@@ -319,10 +460,6 @@ __global__ __launch_bounds__(kEmitThreads) void k_reproject_count_cbox(Reproject
     float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
     float hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
     if (any && lane < 8) {
-        float m[12];
-        const float* T = a.poses + 16 * (int64_t)f;
-#pragma unroll
-        for (int i = 0; i < 12; ++i) m[i] = T[i];
         const int x = (lane & 1) ? (int)xmx : (int)xmn, y = (lane & 2) ? (int)ymx : (int)ymn;
         const uint32_t d = (lane & 4) ? dmx : dmn;
         // the emit pass's arithmetic (reproject_px with the table), from the table in HBM
@@ -339,12 +476,18 @@ __global__ __launch_bounds__(kEmitThreads) void k_reproject_count_cbox(Reproject
             hi[r] = p + margin;
         }
     }
-    block_minmax_store<kEmitThreads / 64>(lo, hi, any && lane < 8, mm_lds, mm + ((int64_t)f * a.mm_stride + tile0) * 6);
+    block_minmax_store<kWaves>(lo, hi, any && lane < 8, mm_lds, mm + ((int64_t)f * a.mm_stride + tile0) * 6);
     if (threadIdx.x < kTiles && tile0 + (int)threadIdx.x < a.n_tiles) {
         uint32_t t = 0;
+        if constexpr (kWide) {
 #pragma unroll
-        for (int i = 0; i < kEmitThreads / 64; ++i) t += lds[(threadIdx.x / 2) * (kEmitThreads / 64) + i];
-        tile_cnt[(int64_t)f * a.n_tiles + tile0 + threadIdx.x] = (t >> (16 * (threadIdx.x & 1))) & 0xffffu;
+            for (int i = 0; i < kWaves; ++i) t += lds[threadIdx.x * kWaves + i];
+        } else {
+#pragma unroll
+            for (int i = 0; i < kWaves; ++i) t += lds[(threadIdx.x / 2) * kWaves + i];
+            t = (t >> (16 * (threadIdx.x & 1))) & 0xffffu;
+        }
+        tile_cnt[(int64_t)f * a.n_tiles + tile0 + threadIdx.x] = t;
     }
     if (threadIdx.x >= 6 && threadIdx.x < 6 * kTiles && tile0 + (int)threadIdx.x / 6 < a.n_tiles) {
         const int a6 = threadIdx.x % 6;

@@ -19,6 +19,7 @@ __device__ __forceinline__ int xcd_chunk_item(int bx, int n_active)
     return (q < chunk && item < n_active) ? item : -1;
 }
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x4_a4_t __attribute__((ext_vector_type(4), aligned(4)));  // 16-byte load from a 4-byte boundary
 __device__ __forceinline__ uint4 stream_load_u4(const uint4* p)
 {
     const u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p));

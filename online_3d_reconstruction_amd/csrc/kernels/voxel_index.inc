@@ -102,6 +102,67 @@ __global__ __launch_bounds__(256) void k_voxel_geom(const float* __restrict__ mm
     geom[f] = voxel_geom_of(mn, mx, leaf, z_offset, n_dev[f]);
 }
 
+// The front of the fused batch path in one launch, one 1024-thread workgroup per frame: the exclusive scan of the frame's
+// tile counts in place (k_scan_rows' job: cnt[f * L + i], totals[f] = the row's sum + add[f]) and then the frame's
+// geometry from its boxes and that total (k_voxel_geom's job).  Both read what the count pass left and nothing of each
+// other but the total.  For rows the one-workgroup scan takes (launch_scan: L <= 4 * kScanChunk).
+__global__ __launch_bounds__(1024) void k_scan_counts_geom(uint32_t* __restrict__ cnt, int L, uint32_t* __restrict__ totals,
+                                                           const uint32_t* __restrict__ add, const float* __restrict__ mm,
+                                                           int64_t mm_stride, int mm_used, float leaf0, float leaf1, float leaf2,
+                                                           VoxelGeom* __restrict__ geom)
+{
+    __shared__ uint32_t lds[1024 / 64 + 1];
+    __shared__ float red[6 * 16];
+    const int f = blockIdx.x;
+    // the boxes first: their loads are in flight while the counts are scanned
+    float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
+    float hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+    const float* box = mm + (int64_t)f * mm_stride * 6;
+    for (int sidx = threadIdx.x; sidx < mm_used; sidx += 1024) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = fminf(lo[a], box[sidx * 6 + a]);
+            hi[a] = fmaxf(hi[a], box[sidx * 6 + 3 + a]);
+        }
+    }
+    uint32_t* row = cnt + (int64_t)f * L;
+    const int chunk = (L + 1023) / 1024;
+    const int b = (int)threadIdx.x * chunk;
+    const int e = (b + chunk < L) ? b + chunk : L;
+    uint32_t s = 0;
+    for (int i = b; i < e; ++i) s += row[i];
+    uint32_t total;
+    uint32_t run = block_excl_scan_u32<16>(s, lds, total);
+    for (int i = b; i < e; ++i) {
+        const uint32_t v = row[i];
+        row[i] = run;
+        run += v;
+    }
+    total += add ? add[f] : 0u;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float l = wave_min_f32(lo[a]), h = wave_max_f32(hi[a]);
+        if ((threadIdx.x & 63) == 0) {
+            red[(threadIdx.x >> 6) * 6 + a] = l;
+            red[(threadIdx.x >> 6) * 6 + 3 + a] = h;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    totals[f] = total;
+    const float leaf[3] = {leaf0, leaf1, leaf2};
+    float mn[3], mx[3];
+    for (int a = 0; a < 3; ++a) {
+        mn[a] = red[a];
+        mx[a] = red[3 + a];
+        for (int w = 1; w < 16; ++w) {
+            mn[a] = fminf(mn[a], red[w * 6 + a]);
+            mx[a] = fmaxf(mx[a], red[w * 6 + 3 + a]);
+        }
+    }
+    geom[f] = voxel_geom_of(mn, mx, leaf, 0.f, total);
+}
+
 // Whole-cloud calls: the head flags of the GROUP RUNS (a point starts one iff its voxel group differs from its
 // predecessor's; util.inc: group_coord_of) and their number per segment tile, in one read of the points.  One workgroup
 // = one segment tile (kSegTile points, 4 sub-rows of 256 consecutive points).  Flags: see k_run_heads.

@@ -7,87 +7,81 @@
 //   [PCL 1.8 common/impl/accumulators.hpp: fp32 sums, xyz / n, uint32_t(channel / n)]
 // =================================================================================================
 
-// Run heads of a sorted (or, buf_sel 0/1, any) index sequence: one wave per segment tile, a lane takes 16 consecutive
-// records (four 16-byte loads, all issued before anything is compared) and the index just before them; no LDS, no
-// workgroup barrier.  Leaves the head flags (bit q of byte b = record 4 b + q of the tile starts a run; a lane's 16
-// flags are one dword, a tile's 256 bytes are consecutive) and their number per tile.
-// buf_sel < 0: the frame's sorted buffer; 0/1: that buffer as is
+// Run heads per segment tile: one wave per tile, a lane takes 16 consecutive records; no LDS, no workgroup barrier.  Leaves
+// the head flags (bit q of byte b = record 4 b + q of the tile starts a run; a lane's 16 flags are one dword, a tile's 256
+// bytes are consecutive) and their number per tile.  Two sources, picked per frame by the one kernel (k_run_heads):
+
+// ... of a sorted (or, buf_sel 0/1, any) index sequence: four 16-byte loads per lane, all issued before anything is
+// compared, and the index just before them.  buf_sel < 0: the frame's sorted buffer; 0/1: that buffer as is
 constexpr int kHeadWaves = 4;  // segment tiles per workgroup of k_run_heads
+__device__ __forceinline__ uint32_t run_heads_tile(const uint32_t* __restrict__ k, int f, int64_t cap, int64_t n, int tile, int lane)
+{
+    const int64_t i0 = (int64_t)tile * kSegTile + lane * 16;
+    uint32_t kk[16];
+    if (((((int64_t)f * cap) & 3) == 0) && i0 + 15 < n) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint4 v = *reinterpret_cast<const uint4*>(k + i0 + 4 * q);
+            kk[4 * q] = v.x; kk[4 * q + 1] = v.y; kk[4 * q + 2] = v.z; kk[4 * q + 3] = v.w;
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) kk[q] = (i0 + q < n) ? k[i0 + q] : 0u;
+    }
+    uint32_t prev = (uint32_t)wave_shr1_i32((int32_t)kk[15]);
+    if (lane == 0) prev = (i0 > 0 && i0 < n) ? k[i0 - 1] : 0u;  // the tile before this one ends with it
+    uint32_t bits = 0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        const int64_t i = i0 + q;
+        if (i < n && (i == 0 || kk[q] != (q ? kk[q - 1] : prev))) bits |= 1u << ((q >> 2) * 8 + (q & 3));
+    }
+    return bits;
+}
+// ... of a frame whose last scatter pass decided them itself (scatter_tile, ScatterJob::heads) and left one byte per
+// record, 1 = starts a run, instead of the sorted indices: the bytes packed into the flag layout, from one read of the
+// byte array.  Frames that did not sort (PCL's overflow guard, no passes) have no such bytes and take the indices.
+__device__ __forceinline__ uint32_t side_heads_tile(const uint8_t* __restrict__ sb, int64_t n, int tile, int lane)
+{
+    const int64_t i0 = (int64_t)tile * kSegTile + lane * 16;
+    uint32_t w4[4] = {0u, 0u, 0u, 0u};
+    if (i0 + 15 < n) {  // (the frame stride and i0 are multiples of 16)
+        const uint4 v = stream_load_u4(reinterpret_cast<const uint4*>(sb + i0));
+        w4[0] = v.x; w4[1] = v.y; w4[2] = v.z; w4[3] = v.w;
+    } else {
+#pragma unroll
+        for (int q = 0; q < 16; ++q)
+            if (i0 + q < n) w4[q >> 2] |= (uint32_t)(sb[i0 + q] & 1u) << ((q & 3) * 8);
+    }
+    uint32_t bits = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {  // four flag bytes -> the low nibble of flag byte q
+        const uint32_t w = w4[q];
+        bits |= ((w & 1u) | ((w >> 7) & 2u) | ((w >> 14) & 4u) | ((w >> 21) & 8u)) << (8 * q);
+    }
+    return bits;
+}
+// side != nullptr: the frames that sorted (passes != 0) left side bytes and are packed from them; the others compare indices
 __global__ __launch_bounds__(kHeadWaves * kWave) void k_run_heads(const uint32_t* __restrict__ keys0, const uint32_t* __restrict__ keys1,
                                                                   int64_t cap, const VoxelGeom* __restrict__ geom, int n_tiles,
                                                                   uint32_t* __restrict__ seg_cnt, int buf_sel,
-                                                                  uint8_t* __restrict__ head_bits, int side_heads)
+                                                                  uint8_t* __restrict__ head_bits, const uint8_t* __restrict__ side,
+                                                                  int64_t side_stride)
 {
     static_assert(kSegTile == 16 * kWave, "16 records per lane");
     const int f = blockIdx.y, lane = threadIdx.x & 63;
     const int tile = blockIdx.x * kHeadWaves + (threadIdx.x >> 6);
     const VoxelGeom g = geom[f];
     if (g.overflow || tile >= n_tiles) return;
-    if (side_heads && g.passes != 0u) return;  // the last scatter pass left this frame's flags as bytes: k_side_heads
     const int64_t n = g.n;
-    const uint32_t* k = (buf_sel < 0 ? sorted_buf(g, keys0, keys1) : (buf_sel ? keys1 : keys0)) + (int64_t)f * cap;
     uint32_t c = 0;
-    const int64_t i0 = (int64_t)tile * kSegTile + lane * 16;
     if ((int64_t)tile * kSegTile < n) {
-        uint32_t kk[16];
-        if (((((int64_t)f * cap) & 3) == 0) && i0 + 15 < n) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const uint4 v = *reinterpret_cast<const uint4*>(k + i0 + 4 * q);
-                kk[4 * q] = v.x; kk[4 * q + 1] = v.y; kk[4 * q + 2] = v.z; kk[4 * q + 3] = v.w;
-            }
-        } else {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) kk[q] = (i0 + q < n) ? k[i0 + q] : 0u;
-        }
-        uint32_t prev = (uint32_t)wave_shr1_i32((int32_t)kk[15]);
-        if (lane == 0) prev = (i0 > 0 && i0 < n) ? k[i0 - 1] : 0u;  // the tile before this one ends with it
-        uint32_t bits = 0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int64_t i = i0 + q;
-            if (i < n && (i == 0 || kk[q] != (q ? kk[q - 1] : prev))) bits |= 1u << ((q >> 2) * 8 + (q & 3));
-        }
-        reinterpret_cast<uint32_t*>(head_bits + ((int64_t)f * n_tiles + tile) * 256)[lane] = bits;
-        c = (uint32_t)__popc(bits);
-    }
-    c = wave_sum_u32(c);
-    if (lane == 0) seg_cnt[(int64_t)f * n_tiles + tile] = c;
-}
-
-// Run heads of the frames whose last scatter pass decided them itself (scatter_tile, ScatterJob::heads) and left one
-// byte per record, 1 = starts a run, instead of the sorted indices: the bytes packed into k_run_heads' flag layout and
-// counted per segment tile, from one read of the byte array.  One wave per segment tile, 16 records per lane.  Frames
-// that did not sort (PCL's overflow guard, no passes) are k_run_heads' own.
-__global__ __launch_bounds__(kHeadWaves * kWave) void k_side_heads(const uint8_t* __restrict__ side, int64_t side_stride,
-                                                                   const VoxelGeom* __restrict__ geom, int n_tiles,
-                                                                   uint32_t* __restrict__ seg_cnt, uint8_t* __restrict__ head_bits)
-{
-    static_assert(kSegTile == 16 * kWave, "16 records per lane");
-    const int f = blockIdx.y, lane = threadIdx.x & 63;
-    const int tile = blockIdx.x * kHeadWaves + (threadIdx.x >> 6);
-    const VoxelGeom g = geom[f];
-    if (g.overflow || g.passes == 0u || tile >= n_tiles) return;
-    const int64_t n = g.n;
-    const uint8_t* sb = side + (int64_t)f * side_stride;
-    uint32_t c = 0;
-    const int64_t i0 = (int64_t)tile * kSegTile + lane * 16;
-    if ((int64_t)tile * kSegTile < n) {
-        uint32_t w4[4] = {0u, 0u, 0u, 0u};
-        if (i0 + 15 < n) {  // (the frame stride and i0 are multiples of 16)
-            const uint4 v = stream_load_u4(reinterpret_cast<const uint4*>(sb + i0));
-            w4[0] = v.x; w4[1] = v.y; w4[2] = v.z; w4[3] = v.w;
-        } else {
-#pragma unroll
-            for (int q = 0; q < 16; ++q)
-                if (i0 + q < n) w4[q >> 2] |= (uint32_t)(sb[i0 + q] & 1u) << ((q & 3) * 8);
-        }
-        uint32_t bits = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {  // four flag bytes -> the low nibble of flag byte q
-            const uint32_t w = w4[q];
-            bits |= ((w & 1u) | ((w >> 7) & 2u) | ((w >> 14) & 4u) | ((w >> 21) & 8u)) << (8 * q);
-        }
+        uint32_t bits;
+        if (side && g.passes != 0u)
+            bits = side_heads_tile(side + (int64_t)f * side_stride, n, tile, lane);
+        else
+            bits = run_heads_tile((buf_sel < 0 ? sorted_buf(g, keys0, keys1) : (buf_sel ? keys1 : keys0)) + (int64_t)f * cap, f, cap, n,
+                                  tile, lane);
         reinterpret_cast<uint32_t*>(head_bits + ((int64_t)f * n_tiles + tile) * 256)[lane] = bits;
         c = (uint32_t)__popc(bits);
     }
@@ -228,7 +222,7 @@ __global__ __launch_bounds__(256) void k_frame_offsets(const VoxelGeom* __restri
                 m = (n_grp && sort_geom[f].grouped) ? n_grp[f] : (n_keep ? n_keep[f] : n_vox[f]);
                 atomicAdd(&acc[0], (unsigned long long)sort_geom[f].n * g.passes);  // records actually sorted
                 atomicAdd(&acc[5], (unsigned long long)sort_geom[f].n);
-                // (a point sort's last pass leaves run-head flags instead of the sorted indices: scatter_tile, k_side_heads)
+                // (a point sort's last pass leaves run-head flags instead of the sorted indices: scatter_tile, side_heads_tile)
                 if (side_heads && g.passes != 0u) atomicAdd(&acc[4], (unsigned long long)sort_geom[f].n);
                 atomicAdd(&acc[1], (unsigned long long)g.n);
                 atomicAdd(&acc[2], (unsigned long long)m);

@@ -1639,10 +1639,13 @@ static int accumulate_impl(o3dr_ctx* c, const uint8_t* disp, int64_t disp_frame_
         a.poses = (const float*)poses_d;
         for (int i = 0; i < 3; ++i) a.slab_inv[i] = 1.0f / leaf[i];
         a.slab_shift = slab_shift_for(c, rows, cols, leaf);
-        launch_minmax_init(&c->prof, c->stream, c->ws.mm, c->ws.mm_stride, a.n_tiles, c->ws.n_kp, nb);
         // no keypoint pass in front of the grid pass and a voxel grid behind it: index and first digit histogram are
         // produced by the pass that writes the points (the keypoint pass would need them too: it keeps the two-step form)
         const bool fused = !use_kp && !c->params.dont_downsample && a.n_tiles > 0 && !with_sor;
+        // the neutral keypoint slot and n_kp = 0 (nothing in front of the passes below writes either; the keypoint pass
+        // overwrites both): a launch of its own, or the work of the fused path's first pass
+        if (!(fused && reproject_fused_inits(a, !c->exact_box)))
+            launch_minmax_init(&c->prof, c->stream, c->ws.mm, c->ws.mm_stride, a.n_tiles, c->ws.n_kp, nb);
         if (use_kp)
             launch_keypoint_pass(&c->prof, c->stream, a, kp_d, 0, c->ws.pts, c->ws.n_kp, c->ws.mm, kpoff_d + f0, nb);
         int emit_tiles = 0;

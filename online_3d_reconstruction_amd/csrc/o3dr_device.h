@@ -135,7 +135,7 @@ struct Workspace {
     uint8_t* head_bits = nullptr;  // frames*n_seg_tiles*256: run-head flags, 4 records per byte (k_run_heads -> k_run_starts)
     uint8_t* side = nullptr;       // frames*side_frame_stride(cap): one byte per record of a point sort, 1 = starts a run of equal
                                    // indices, written by the last scatter pass instead of the sorted indices (k_radix_scatter_lane
-                                   // -> k_side_heads); nullptr: the indices are written and k_run_heads reads them
+                                   // -> k_run_heads packs them); nullptr: the indices are written and k_run_heads compares them
     uint32_t* scan_partial = nullptr;  // chunk sums of the multi-workgroup scan
     // statistical outlier removal (sor_frames clouds of at most sor_cap points)
     SorGeom* sor_geom = nullptr;        // frames
@@ -229,6 +229,9 @@ void launch_reproject(Profiler* pf, hipStream_t s, const ReprojectArgs& a, int f
 // ranges are the scanned counts it leaves in ws.tile_cnt), else 0.
 int launch_reproject_fused(Profiler* pf, hipStream_t s, Workspace& ws, const ReprojectArgs& a, int frames, int64_t cap,
                             const float leaf[3], bool conservative_box = true);
+// ... whose first pass also does launch_minmax_init's job (neutral keypoint slot, ws.n_kp = 0) for these arguments: the
+// caller then leaves that launch out
+bool reproject_fused_inits(const ReprojectArgs& a, bool conservative_box);
 void launch_transform(Profiler* pf, hipStream_t s, const o3dr_point* in, int64_t n, const float* T16_host,
                       o3dr_point* out);
 int launch_points_minmax(Profiler* pf, hipStream_t s, const o3dr_point* in, int64_t in_fstride,

@@ -5,8 +5,8 @@
 //       radix pass's digits over candidate-aligned sort tiles)
 //   K2  k_voxel_geom / k_voxel_keys_*          A4 steps 1-5: PCL VoxelGrid geometry and linear index
 //       k_radix_hist / k_radix_scatter_lane    A4 step 6: stable LSD radix sort of (index, point id)
-//       k_run_heads / k_side_heads / k_run_starts / k_centroid  A4 steps 7-8: runs -> ordered fp32 centroid
-//       (the last scatter pass of a point sort leaves run-head flags, not sorted indices: k_side_heads packs them)
+//       k_run_heads / k_run_starts / k_centroid  A4 steps 7-8: runs -> ordered fp32 centroid
+//       (the last scatter pass of a point sort leaves run-head flags, not sorted indices: k_run_heads packs them)
 //
 // Everything here is HBM-bound integer/byte/fp32 work: no MFMA.  The whole translation unit is
 // compiled with -ffp-contract=off because the reference arithmetic (unoptimised x86 build,
@@ -301,7 +301,7 @@ static void group_run_front(Profiler* pf, hipStream_t s, Workspace& ws, const So
 }
 
 // Behind the sort: the runs of equal keys.  Their heads per segment tile (from the sorted keys, or packed from the side bytes
-// the last pass left: each of the two kernels takes the frames of its kind and returns at once for the others), the scan
+// the last pass left: one launch, every frame by the source of its kind), the scan
 // -> ws.n_vox, the runs' starts -> ws.seg_start.
 static void segment_runs(Profiler* pf, hipStream_t s, Workspace& ws, const SortShape& sh, const VoxelGeom* geom, const uint8_t* side,
                          int64_t side_stride)
@@ -311,8 +311,7 @@ static void segment_runs(Profiler* pf, hipStream_t s, Workspace& ws, const SortS
         ProfScope ps(pf, O3DR_K_SEGMENT, s);
         const dim3 hgrid(cdiv64(n_seg_tiles, kHeadWaves), F);
         k_run_heads<<<hgrid, kHeadWaves * kWave, 0, s>>>(ws.keys[0], ws.keys[1], sh.cap, geom, n_seg_tiles, ws.seg_cnt, -1, ws.head_bits,
-                                                         side != nullptr);
-        if (side) k_side_heads<<<hgrid, kHeadWaves * kWave, 0, s>>>(side, side_stride, geom, n_seg_tiles, ws.seg_cnt, ws.head_bits);
+                                                         side, side_stride);
     }
     {
         ProfScope ps(pf, O3DR_K_OTHER, s);
@@ -332,6 +331,17 @@ static void corrupt_payload(hipStream_t s, Workspace& ws, const VoxelGeom* geom)
     k_test_corrupt_payload<<<1, 1, 0, s>>>(ws.vals[0], ws.vals[1], geom);
 }
 
+// rectified-stereo Q and byte disparities: counts + a conservative box from the corners of (x, y, disparity) ranges
+// (k_reproject_count_cbox); the exact box only for frames whose conservative one trips PCL's overflow guard
+static inline bool fused_cbox(const ReprojectArgs& a, bool conservative_box) { return a.lut != nullptr && !a.disp_f64 && conservative_box; }
+bool reproject_fused_inits(const ReprojectArgs& a, bool conservative_box) { return fused_cbox(a, conservative_box); }
+
+// Workgroups of the exact-box pass behind the conservative one.  Nearly always no frame needs it and every workgroup
+// returns at once; when frames do (a leaf near PCL's overflow guard, where the conservative box of every frame trips it) the
+// grid must still fill the chip: about kExactGrid workgroups over the batch, each walking its share of a frame's tile groups.
+// (Four per frame cost such batches 0.2 ms per step: 1080p at voxel_size 0.02 7.68 -> 7.92 ms, 4096x2160 at jump_pixels 4
+// 3.12 -> 3.32.)
+constexpr int kExactGrid = 8192;
 int launch_reproject_fused(Profiler* pf, hipStream_t s, Workspace& ws, const ReprojectArgs& a, int frames, int64_t cap,
                             const float leaf[3], bool conservative_box)
 {
@@ -341,14 +351,16 @@ int launch_reproject_fused(Profiler* pf, hipStream_t s, Workspace& ws, const Rep
     const bool counts = sh.tm && cdiv64(a.n_tiles, kEmitGroup) == sh.n_sort_tiles;
     uint32_t* const hist = counts ? ws.hist : nullptr;
     const dim3 grid(cdiv64(a.n_tiles, kEmitGroup), frames);
-    // rectified-stereo Q and byte disparities: counts + a conservative box from the corners of (x, y, disparity) ranges
-    // (k_reproject_count_cbox); the exact box only for frames whose conservative one trips PCL's overflow guard
-    const bool cbox = a.lut != nullptr && !a.disp_f64 && conservative_box;
-    const dim3 cgrid(cdiv64(a.n_tiles, kCountTiles), frames);
+    const bool cbox = fused_cbox(a, conservative_box);
+    const int n_cgroups = cdiv64(a.n_tiles, kCountTiles);
+    const dim3 cgrid(n_cgroups, frames);
     {
         ProfScope ps(pf, O3DR_K_COUNT, s);
-        if (cbox)
-            k_reproject_count_cbox<kCboxTiles><<<dim3(cdiv64(a.n_tiles, kCboxTiles), frames), kEmitThreads, 0, s>>>(a, ws.tile_cnt, ws.mm);
+        const dim3 bgrid(cdiv64(a.n_tiles, kCboxTiles), frames);
+        if (cbox && a.vec4 && a.Nx >= 32)  // (with reproject_fused_inits: ws.n_kp and the keypoint slot are this launch's to set)
+            k_reproject_count_cbox<kCboxTiles, true><<<bgrid, kEmitThreads, 0, s>>>(a, ws.tile_cnt, ws.mm, ws.n_kp);
+        else if (cbox)
+            k_reproject_count_cbox<kCboxTiles, false><<<bgrid, kEmitThreads, 0, s>>>(a, ws.tile_cnt, ws.mm, ws.n_kp);
         else if (a.disp_f64)
             k_reproject_bbox_count<true><<<cgrid, kEmitThreads, 0, s>>>(a, ws.tile_cnt, ws.mm, nullptr);
         else
@@ -356,12 +368,20 @@ int launch_reproject_fused(Profiler* pf, hipStream_t s, Workspace& ws, const Rep
     }
     {
         ProfScope ps(pf, O3DR_K_OTHER, s);
-        launch_scan(s, ws.tile_cnt, a.n_tiles, a.n_tiles, frames, ws.n_valid, ws.n_kp, ws.scan_partial);
-        k_voxel_geom<<<frames, 256, 0, s>>>(ws.mm, ws.mm_stride, a.n_tiles + 1, ws.n_valid, leaf[0], leaf[1], leaf[2], 0.f, ws.geom);
+        if (a.n_tiles <= 4 * kScanChunk) {  // (launch_scan's one-workgroup form) scan and geometry in one launch
+            k_scan_counts_geom<<<frames, 1024, 0, s>>>(ws.tile_cnt, a.n_tiles, ws.n_valid, ws.n_kp, ws.mm, ws.mm_stride, a.n_tiles + 1,
+                                                       leaf[0], leaf[1], leaf[2], ws.geom);
+        } else {
+            launch_scan(s, ws.tile_cnt, a.n_tiles, a.n_tiles, frames, ws.n_valid, ws.n_kp, ws.scan_partial);
+            k_voxel_geom<<<frames, 256, 0, s>>>(ws.mm, ws.mm_stride, a.n_tiles + 1, ws.n_valid, leaf[0], leaf[1], leaf[2], 0.f, ws.geom);
+        }
     }
     if (cbox) {
         ProfScope ps(pf, O3DR_K_COUNT, s);
-        k_reproject_bbox_count<false><<<cgrid, kEmitThreads, 0, s>>>(a, ws.tile_cnt, ws.mm, ws.geom);
+        int walkers = cdiv64(kExactGrid, frames);
+        if (walkers < 4) walkers = 4;
+        const dim3 wgrid(n_cgroups < walkers ? n_cgroups : walkers, frames);
+        k_reproject_bbox_count<false><<<wgrid, kEmitThreads, 0, s>>>(a, ws.tile_cnt, ws.mm, ws.geom);
         k_voxel_geom<<<frames, 256, 0, s>>>(ws.mm, ws.mm_stride, a.n_tiles + 1, ws.n_valid, leaf[0], leaf[1], leaf[2], 0.f, ws.geom, 1);
     }
     {
