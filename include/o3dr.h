@@ -1546,7 +1546,10 @@ int  o3dr_pose_graph_refine(o3dr_ctx* ctx, const uint8_t* desc, const int64_t* o
 #define O3DR_K_GROUND_ITER   34  /* ... the iterations: four sliding min / max passes each */
 #define O3DR_K_GROUND_FILL   35  /* ... the DTM: ground words, the raster's fill passes */
 #define O3DR_K_GROUND_POINTS 36  /* ... the pass over the points: mask, height above ground */
-#define O3DR_K_NUM          37
+#define O3DR_K_CLUSTER_LINK    37  /* Euclidean clustering (o3dr_objects.h): the radius walk with its union-find */
+#define O3DR_K_CLUSTER_NUMBER  38  /* ... flatten, sizes, flags, the two scans */
+#define O3DR_K_CLUSTER_RECORDS 39  /* ... point outputs, boxes, centroid sums, records, indices */
+#define O3DR_K_NUM          40
 /* Bracket every launch of kernel `kernel_id` (or all kernels if -1) with HIP events on the
  * context's stream; 0 launches are bracketed when disabled (the default). */
 int o3dr_profile_enable(o3dr_ctx* ctx, int32_t kernel_id, int32_t enable);

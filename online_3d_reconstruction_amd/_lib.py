@@ -26,12 +26,13 @@ K_RECTIFY_MAPS, K_RECTIFY_REMAP = 28, 29
 K_SEG_ASSIGN, K_SEG_LABEL = 30, 31
 K_MULTIVIEW = 32
 K_GROUND_WINNER, K_GROUND_ITER, K_GROUND_FILL, K_GROUND_POINTS = 33, 34, 35, 36
+K_CLUSTER_LINK, K_CLUSTER_NUMBER, K_CLUSTER_RECORDS = 37, 38, 39
 KERNEL_NAMES = ["reproject_count", "reproject_emit", "voxel_keys", "radix_hist", "radix_scatter", "run_segments",
                 "centroid", "other", "centroid_runs", "plane_disp_sums", "plane_disp_fit", "plane_disp_eval",
                 "orb_pyramid", "orb_fast", "orb_candidates", "orb_select", "orb_describe", "match", "pose_chain", "ransac",
                 "graph_moments", "graph_solve", "stereo_census", "stereo_paths", "stereo_winner", "disp_median", "disp_label",
                 "disp_speckle", "rectify_maps", "rectify_remap", "seg_assign", "seg_label", "multiview", "ground_winner", "ground_iter",
-                "ground_fill", "ground_points"]
+                "ground_fill", "ground_points", "cluster_link", "cluster_number", "cluster_records"]
 
 
 class O3drError(RuntimeError):
@@ -135,6 +136,26 @@ class GroundResultStruct(C.Structure):
 
 O3DR_GROUND_MAX_WINDOW_RADIUS = 128
 O3DR_GROUND_MAX_ITERATIONS = 16
+
+
+# include/o3dr_objects.h
+class ClusterParamsStruct(C.Structure):
+    _fields_ = [("tolerance", C.c_double), ("min_size", C.c_int32), ("max_size", C.c_int32)]
+
+
+class ClusterOutputsStruct(C.Structure):
+    _fields_ = [("label", C.c_void_p), ("raw", C.c_void_p), ("size", C.c_void_p), ("indices", C.c_void_p)]
+
+
+class ClusterResultStruct(C.Structure):
+    _fields_ = [("n_components", C.c_int64), ("n_clusters", C.c_int64), ("n_too_small", C.c_int64), ("n_too_large", C.c_int64),
+                ("n_clustered_points", C.c_int64), ("n_rejected_points", C.c_int64), ("largest", C.c_int64), ("n_pairs", C.c_int64)]
+
+
+# o3dr_cluster: one record per cluster, 64 bytes
+CLUSTER = np.dtype([("first", np.int32), ("size", np.int32), ("begin", np.int32), ("reserved", np.int32),
+                    ("lo", np.float32, (3,)), ("hi", np.float32, (3,)), ("centroid", np.float64, (3,))])
+assert CLUSTER.itemsize == 64
 
 
 class PlaneDispParamsStruct(C.Structure):
@@ -368,6 +389,9 @@ SYMBOLS = [
     ("o3dr_ground_schedule", C.c_int, [C.POINTER(GroundParamsStruct), _vp, _vp, C.POINTER(_i32)]),
     ("o3dr_ground_filter", C.c_int, [_vp, _vp, _i64, C.POINTER(GroundParamsStruct), C.POINTER(GroundOutputsStruct),
                                      C.POINTER(GroundResultStruct), _i32]),
+    ("o3dr_cluster_default_params", None, [C.POINTER(ClusterParamsStruct)]),
+    ("o3dr_cluster_euclidean", C.c_int, [_vp, _vp, _i64, C.POINTER(ClusterParamsStruct), C.POINTER(ClusterOutputsStruct), _vp, _i64,
+                                         C.POINTER(_i64), C.POINTER(ClusterResultStruct), _i32]),
     ("o3dr_plane_disp_default_params", None, [C.POINTER(PlaneDispParamsStruct)]),
     ("o3dr_plane_fit_disparity", C.c_int, [_vp, _vp, _i64, _i64, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32,
                                            C.POINTER(PlaneDispParamsStruct), _vp, _vp, _pu32, _i32]),

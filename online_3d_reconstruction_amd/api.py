@@ -111,6 +111,21 @@ class GroundInfo:
     n_removed: tuple
 
 
+@dataclass
+class ClusterInfo:
+    """o3dr_cluster_euclidean's counters (include/o3dr_objects.h): the components of the links' closure, those kept as
+    clusters and those rejected as too small / too large, the points in clusters and in rejected components, the size of
+    the largest component, and the linked pairs i < j."""
+    n_components: int
+    n_clusters: int
+    n_too_small: int
+    n_too_large: int
+    n_clustered_points: int
+    n_rejected_points: int
+    largest: int
+    n_pairs: int
+
+
 def _ground_params(cell_size, max_window_radius, window_base, exponential, slope, initial_distance, max_distance):
     prm = L.GroundParamsStruct()
     L.load_library().o3dr_ground_default_params(C.byref(prm))
@@ -1494,6 +1509,56 @@ class Context:
             ret += (GroundInfo(int(res.cx0), int(res.cy0), int(res.width), int(res.height), int(res.n_inside), int(res.n_outside),
                                int(res.n_occupied), int(res.n_ground_cells), int(res.n_ground_points), int(res.n_dtm_filled),
                                int(res.n_dtm_empty), int(res.n_iterations), tuple(int(v) for v in res.n_removed[:res.n_iterations])),)
+        return ret[0] if len(ret) == 1 else ret
+
+    # -- Euclidean clustering: object labels and per-object records (this build's own) ----------
+    def clusterCloud(self, pts, tolerance, min_size=1, max_size=None, return_clusters=False, return_raw=False, return_sizes=False,
+                     return_indices=False, return_info=False):
+        """Which points belong to the same object: points closer than `tolerance` are linked, a component of the links'
+        closure with min_size <= points <= max_size (None: no limit) is a cluster, numbered by its lowest point index
+        (contract: include/o3dr_objects.h, DESIGN.md "Euclidean clustering").  numpy POINT arrays give numpy arrays, torch
+        [N,4] 4-byte CUDA tensors such as finalize(device=...) give CUDA tensors (the records then as a CUDA uint8
+        [K, 64] tensor: `.cpu().numpy().view(CLUSTER)`).
+        -> label int32 [n] (-1: rejected)[, clusters CLUSTER [K]][, raw int32 [n]][, sizes int32 [n]][, indices int32
+        [n_clustered_points]][, ClusterInfo]"""
+        pts, n = self._cloud(pts)
+        p_in, mem, _k = _ptr(pts)
+        prm = L.ClusterParamsStruct()
+        self._lib.o3dr_cluster_default_params(C.byref(prm))
+        prm.tolerance, prm.min_size = float(tolerance), int(min_size)
+        if max_size is not None:
+            prm.max_size = int(max_size)
+        cap = n // int(min_size) if return_clusters and int(min_size) >= 1 else 0  # no more clusters fit in n points
+        want = ["label"] + [name for name, on in (("raw", return_raw), ("size", return_sizes), ("indices", return_indices)) if on]
+        outs = L.ClusterOutputsStruct()
+        arrays = {}
+        if mem == L.MEM_DEVICE:
+            import torch
+            for name in want:
+                arrays[name] = torch.empty(n, dtype=torch.int32, device=pts.device)
+            rec = torch.empty((cap, 64), dtype=torch.uint8, device=pts.device)
+            self._order_after_torch()
+        else:
+            for name in want:
+                arrays[name] = np.empty(n, np.int32)
+            rec = np.empty(cap, L.CLUSTER)
+        for name in want:
+            setattr(outs, name, _addr(arrays[name]) if n else None)
+        res, k = L.ClusterResultStruct(), C.c_int64(0)
+        L.check(self._lib.o3dr_cluster_euclidean(self._h, p_in if n else None, n, C.byref(prm), C.byref(outs), _addr(rec) if cap else None,
+                                                 cap, C.byref(k), C.byref(res), mem))
+        ret = (arrays["label"],)
+        if return_clusters:
+            ret += (rec[:int(k.value)],)
+        if return_raw:
+            ret += (arrays["raw"],)
+        if return_sizes:
+            ret += (arrays["size"],)
+        if return_indices:
+            ret += (arrays["indices"][:int(res.n_clustered_points)],)
+        if return_info:
+            ret += (ClusterInfo(int(res.n_components), int(res.n_clusters), int(res.n_too_small), int(res.n_too_large),
+                                int(res.n_clustered_points), int(res.n_rejected_points), int(res.largest), int(res.n_pairs)),)
         return ret[0] if len(ret) == 1 else ret
 
     def voxelGrid(self, pts, leaf, min_points=0, z_offset=0.0, return_status=False):

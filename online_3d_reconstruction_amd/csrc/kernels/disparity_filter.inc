@@ -103,44 +103,7 @@ __global__ __launch_bounds__(256) void k_df_median(DfView in, int rows, int cols
     }
 }
 
-// ---- union-find.  `Mem` reads and lowers parent words: in LDS (workgroup scope) or in global memory (agent scope).
-struct DfLds {
-    static __device__ __forceinline__ int load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-    static __device__ __forceinline__ int lower(int* p, int v) { return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-};
-struct DfGlobal {
-    static __device__ __forceinline__ int load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    static __device__ __forceinline__ int lower(int* p, int v) { return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-};
-template <class Mem>
-__device__ __forceinline__ int df_find(const int* parent, int x)
-{
-    // Ends: parent[i] <= i for every i at every moment (words start at i and are only ever lowered), so each step goes
-    // to a strictly smaller index, and indices are >= 0.  A stale value is a former ancestor: still of the same tree.
-    for (int p = Mem::load(parent + x); p < x; p = Mem::load(parent + x)) x = p;
-    return x;
-}
-template <class Mem>
-__device__ __forceinline__ void df_union(int* parent, int a, int b)
-{
-    // Ends: a retry happens only when the atomic min returned old < a, and the next round starts from old: the larger
-    // index of the pair strictly decreases from round to round (find only lowers it further), and indices are >= 0.
-    // Nothing waits for another thread.  The link a -> old that the min may have replaced is carried on by this
-    // thread, which goes on to join old and b.
-    for (;;) {
-        a = df_find<Mem>(parent, a);
-        b = df_find<Mem>(parent, b);
-        if (a == b) return;
-        if (a < b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = Mem::lower(parent + a, b);  // the larger root goes under the smaller
-        if (old == a) return;                       // a was a root: linked
-        a = old;                                    // old < a: a had been linked meanwhile
-    }
-}
+// (the union-find the labelling runs on - DfLds / DfGlobal, df_find, df_union - is in util.inc: the clustering shares it)
 
 template <class T>
 __global__ __launch_bounds__(256) void k_df_local(DfArgs a, int tiles_x)

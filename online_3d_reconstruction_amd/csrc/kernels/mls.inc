@@ -34,27 +34,7 @@ struct MlsArgs {
     unsigned long long* counters;  // n_none, n_plane, n_poly, max k
 };
 
-// f(p, d2) for every point p of the cloud with the fp32 d2 <= r2, in the fixed order of the contract
-template <class F>
-__device__ __forceinline__ void mls_walk(const MlsArgs& a, const SorGeom& g, int x0, int x1, int y0, int y1, float qx, float qy,
-                                         float qz, F&& f)
-{
-    for (int yy = y0; yy <= y1; ++yy) {
-        const int64_t row = (int64_t)yy * g.gx;
-        for (int xx = x0; xx <= x1; ++xx) {
-            const int64_t c = row + xx;
-            const float4 lo = a.cell_lo[c], hi = a.cell_hi[c];
-            if (!(cell_box_d2_lower_bound(lo, hi, qx, qy, qz) <= a.r2)) continue;
-            const uint32_t s = a.cell_first[c], e = a.cell_first[c + 1];
-            for (uint32_t j = s; j < e; ++j) {
-                const float4 p = a.sxyz[j];
-                const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
-                const float d = (dx * dx + dy * dy) + dz * dz;
-                if (d <= a.r2) f(p, d);
-            }
-        }
-    }
-}
+// (mls_walk, the exact radius walk over the window's cells, is in util.inc: the clustering shares it)
 
 template <int O>
 __global__ __launch_bounds__(kMlsThreads) void k_mls(MlsArgs a)

@@ -330,3 +330,83 @@ __device__ __forceinline__ void mls_jacobi3(double A[3][3], double V[3][3])
         }
     }
 }
+
+// The exact radius walk over a search grid (launch_nn_grid), shared by MLS (kernels/mls.inc) and the clustering
+// (kernels/cluster.inc): f(p, d2) for every point p of the cloud with the fp32 d2 <= r2, in the fixed order of the MLS
+// contract.  `a` holds the grid (sxyz, cell_first, cell_lo, cell_hi) and r2.
+template <class Args, class F>
+__device__ __forceinline__ void mls_walk(const Args& a, const SorGeom& g, int x0, int x1, int y0, int y1, float qx, float qy,
+                                         float qz, F&& f)
+{
+    for (int yy = y0; yy <= y1; ++yy) {
+        const int64_t row = (int64_t)yy * g.gx;
+        for (int xx = x0; xx <= x1; ++xx) {
+            const int64_t c = row + xx;
+            const float4 lo = a.cell_lo[c], hi = a.cell_hi[c];
+            if (!(cell_box_d2_lower_bound(lo, hi, qx, qy, qz) <= a.r2)) continue;
+            const uint32_t s = a.cell_first[c], e = a.cell_first[c + 1];
+            for (uint32_t j = s; j < e; ++j) {
+                const float4 p = a.sxyz[j];
+                const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
+                const float d = (dx * dx + dy * dy) + dz * dz;
+                if (d <= a.r2) f(p, d);
+            }
+        }
+    }
+}
+
+// ---- union-find, shared by the disparity filter (kernels/disparity_filter.inc) and the clustering (kernels/cluster.inc).
+// `Mem` reads and lowers parent words: in LDS (workgroup scope) or in global memory (agent scope).
+struct DfLds {
+    static __device__ __forceinline__ int load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+    static __device__ __forceinline__ int lower(int* p, int v) { return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+};
+struct DfGlobal {
+    static __device__ __forceinline__ int load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    static __device__ __forceinline__ int lower(int* p, int v) { return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+};
+template <class Mem>
+__device__ __forceinline__ int df_find(const int* parent, int x)
+{
+    // Ends: parent[i] <= i for every i at every moment (words start at i and are only ever lowered), so each step goes
+    // to a strictly smaller index, and indices are >= 0.  A stale value is a former ancestor: still of the same tree.
+    for (int p = Mem::load(parent + x); p < x; p = Mem::load(parent + x)) x = p;
+    return x;
+}
+// df_find that halves the path it walks: every other node on it is lowered to its grandparent.  The grandparent is an
+// ancestor, so the word is only lowered and the node stays in its tree; a min that meets a word another thread lowered
+// meanwhile keeps the smaller of two ancestors.  Ends as df_find does: x strictly decreases.  (The clustering's trees are
+// linked by point index in whatever order the lanes meet: without this their depth is not bounded by a tile.)
+template <class Mem>
+__device__ __forceinline__ int df_find_halve(int* parent, int x)
+{
+    for (;;) {
+        const int p = Mem::load(parent + x);
+        if (p >= x) return x;
+        const int g = Mem::load(parent + p);
+        if (g >= p) return p;
+        Mem::lower(parent + x, g);
+        x = g;
+    }
+}
+template <class Mem>
+__device__ __forceinline__ void df_union(int* parent, int a, int b)
+{
+    // Ends: a retry happens only when the atomic min returned old < a, and the next round starts from old: the larger
+    // index of the pair strictly decreases from round to round (find only lowers it further), and indices are >= 0.
+    // Nothing waits for another thread.  The link a -> old that the min may have replaced is carried on by this
+    // thread, which goes on to join old and b.
+    for (;;) {
+        a = df_find<Mem>(parent, a);
+        b = df_find<Mem>(parent, b);
+        if (a == b) return;
+        if (a < b) {
+            const int t = a;
+            a = b;
+            b = t;
+        }
+        const int old = Mem::lower(parent + a, b);  // the larger root goes under the smaller
+        if (old == a) return;                       // a was a root: linked
+        a = old;                                    // old < a: a had been linked meanwhile
+    }
+}

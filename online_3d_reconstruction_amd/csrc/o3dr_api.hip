@@ -139,11 +139,12 @@ struct o3dr_ctx {
     // nothing in it outlives a call, and within one call every block is laid out by one carve().  OP_IN: staged host inputs
     // (descriptor pool; src / tgt / mask; image stacks).  OP_WORK: the arrays sized from the arguments (plane: points in tile
     // order + run heads; mesh: run heads + vertex tables; raster: the cells' words + column offsets; ground: those and
-    // four fp32 rasters; match: pair table + chunk partials; rigid: segment table + sums; ORB, stereo, the disparity and multi-view filters, segmentation: a group
+    // four fp32 rasters; clustering: the union-find, sizes, numbers, begins; match: pair table + chunk partials; rigid:
+    // segment table + sums; ORB, stereo, the disparity and multi-view filters, segmentation: a group
     // of frames' arrays and the per-frame counters; rectification: the staged host map).  OP_LATE: the arrays sized from a
-    // count read back mid-call (plane: tile tables).
+    // count read back mid-call (plane: tile tables; clustering: the clusters' boxes and sums).
     // OP_OUT: the staged outputs of a host call.  OP_FLAGS: the flags / ranges / counters of one operator (MlsFlags,
-    // PlaneFlags, MeshFlags, RasterFlags: 256 bytes; GroundFlags: 384).
+    // PlaneFlags, MeshFlags, RasterFlags, ClusterFlags: 256 bytes; GroundFlags: 384).
     enum { OP_IN, OP_WORK, OP_LATE, OP_OUT, OP_FLAGS, OP_BUFS };
     DevBuf op[OP_BUFS];
     DevBuf orb_pat;  // o3dr_orb_detect: the steered table
@@ -3922,6 +3923,141 @@ extern "C" int o3dr_ground_filter(o3dr_ctx* c, const o3dr_point* cloud, int64_t 
         if (res) memset(res, 0, sizeof *res);
         outs.zero();
     }
+    return rc;
+}
+
+// -------------------------------------------------------------------------------------------------
+// Euclidean clustering: object labels and per-object records (kernels/cluster.inc; contract: include/o3dr_objects.h;
+// DESIGN.md "Euclidean clustering")
+// -------------------------------------------------------------------------------------------------
+extern "C" void o3dr_cluster_default_params(o3dr_cluster_params* p)
+{
+    if (!p) return;
+    p->tolerance = 0.0;  // no usable default: the caller sets it
+    p->min_size = 1, p->max_size = INT32_MAX;  // pcl::EuclideanClusterExtraction's defaults
+}
+
+struct ClusterFlags {
+    alignas(64) uint32_t bad;  // non-finite; read back with the box
+    float box6[6];
+    alignas(64) uint32_t counters[kClusterCounterWords];  // ClusterArgs::counters
+    alignas(64) unsigned long long n_pairs;
+};
+struct ClusterHead {  // the first words of ClusterFlags on the host
+    uint32_t bad;
+    float box6[6];
+};
+static_assert(offsetof(ClusterFlags, box6) == offsetof(ClusterHead, box6), "bad and the box are read back together");
+
+static int cluster_euclidean(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const o3dr_cluster_params* p, const o3dr_cluster_outputs* out,
+                             o3dr_cluster* clusters, int64_t clusters_capacity, int64_t* n_clusters, Outputs& outs,
+                             o3dr_cluster_result* res, int32_t mem)
+{
+    CHK(nn_check_cloud(n, cloud, kMeshCloudMax));
+    if (!p) return fail(O3DR_ERR_INVALID_ARG, "params is NULL");
+    if (!n_clusters) return fail(O3DR_ERR_INVALID_ARG, "n_clusters is NULL");
+    if (clusters_capacity < 0 || (clusters_capacity > 0 && !clusters))
+        return fail(O3DR_ERR_INVALID_ARG, "bad clusters / clusters_capacity");
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    const double tol = p->tolerance;
+    const float r2 = (float)(tol * tol);
+    if (!(std::isfinite(tol) && tol > 0.0 && std::isfinite(r2) && r2 > 0.f))
+        return fail(O3DR_ERR_INVALID_ARG, "tolerance must be finite and > 0 (and its square usable in fp32)");
+    if (p->min_size < 1) return fail(O3DR_ERR_INVALID_ARG, "min_size must be >= 1");
+    if (p->max_size < p->min_size) return fail(O3DR_ERR_INVALID_ARG, "max_size must be >= min_size");
+    c->place_ub = -1;
+    if (n == 0) return O3DR_OK;
+    ClusterFlags* f;
+    CHK(op_flags(c, &f));
+    const o3dr_point* cloud_d = nullptr;
+    ClusterHead h;
+    memset(&h, 0, sizeof h);
+    CHK(cloud_stage_finite(c, cloud, n, mem, &f->bad, &h.bad, sizeof h, &cloud_d, [&]() -> int {
+        CHK(ws_ensure(c, 1, n, false));  // the cloud's box, before any grid work
+        launch_set_counts(&c->prof, c->stream, c->ws.n_valid, (uint32_t)n, 1);
+        const int used = launch_points_minmax(&c->prof, c->stream, cloud_d, 0, c->ws.n_valid, 1, n, c->ws.mm_stride, c->ws.mm);
+        launch_bbox(&c->prof, c->stream, c->ws.mm, used, f->box6);
+        return O3DR_OK;
+    }));
+    for (int k = 0; k < 3; ++k)
+        if (!((double)h.box6[3 + k] - (double)h.box6[k] < 32768.0))
+            return fail(O3DR_ERR_INVALID_ARG, "a side of the cloud's bounding box is 32768 m or more");
+    float* box6;
+    float4 *lo, *hi;
+    CHK(nn_target(c, cloud_d, n, O3DR_MEM_DEVICE, &box6, &lo, &hi));
+    ClusterArgs a;
+    memset(&a, 0, sizeof a);
+    CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
+        w.take(a.parent, (size_t)n);
+        w.take(a.cnt, (size_t)n);
+        w.take(a.num, (size_t)n);
+        w.take(a.beg, (size_t)n);
+        w.take(a.part, (size_t)cluster_blocks(n) * kPartWords);
+    }));
+    a.n = (uint32_t)n;
+    a.sxyz = c->ws.sor_xyz, a.cell_first = c->ws.sor_cell_first, a.cell_lo = lo, a.cell_hi = hi, a.sg = c->ws.sor_geom, a.box6 = box6;
+    a.r2 = r2;
+    const double pad = tol * (1.0 + 1e-5);
+    a.pad_r = (float)(pad > 1e-18 ? pad : 1e-18);
+    a.min_size = p->min_size, a.max_size = p->max_size;
+    a.counters = f->counters, a.n_pairs = &f->n_pairs;
+    launch_cluster_link(&c->prof, c->stream, c->ws, a);
+    HIPCHK(hipGetLastError());
+    uint32_t cnt[kClusterCounterWords];
+    unsigned long long pairs = 0;
+    HIPCHK(hipMemcpyAsync(cnt, f->counters, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&pairs, &f->n_pairs, sizeof pairs, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const int64_t K = cnt[8], n_clustered = cnt[9];
+    *n_clusters = K;
+    if (clusters && K > clusters_capacity) return fail(O3DR_ERR_CAPACITY, "clusters_capacity is below the cluster count");
+    outs.set_count(clusters, K);
+    if (out) outs.set_count(out->indices, n_clustered);
+    CHK(outs.stage(c));
+    if (out) a.label = outs.dev(out->label), a.raw = outs.dev(out->raw), a.size = outs.dev(out->size), a.indices = outs.dev(out->indices);
+    a.rec = K > 0 ? outs.dev(clusters) : nullptr;
+    if (a.rec)
+        CHK(carve(c, c->op[o3dr_ctx::OP_LATE], [&](Carve& w) {
+            w.take(a.box_lo, (size_t)K * 3);
+            w.take(a.box_hi, (size_t)K * 3);
+            w.take(a.sums, (size_t)K * 3);
+        }));
+    launch_cluster_outputs(&c->prof, c->stream, c->ws, a, (uint32_t)K, (uint32_t)n_clustered);
+    HIPCHK(hipGetLastError());
+    CHK(outs.copy_back(c));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (res) {
+        res->n_components = cnt[0], res->n_clusters = K, res->n_too_small = cnt[1], res->n_too_large = cnt[2];
+        res->n_clustered_points = n_clustered, res->n_rejected_points = n - n_clustered;
+        res->largest = cnt[3];
+        res->n_pairs = (int64_t)pairs;
+    }
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_cluster_euclidean(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const o3dr_cluster_params* p,
+                                      const o3dr_cluster_outputs* out, o3dr_cluster* clusters, int64_t clusters_capacity,
+                                      int64_t* n_clusters, o3dr_cluster_result* res, int32_t mem)
+{
+    if (n_clusters) *n_clusters = 0;
+    if (res) memset(res, 0, sizeof *res);
+    Outputs outs{mem};
+    const int64_t pts = cloud_points(n, kMeshCloudMax);
+    if (out) {
+        outs.add(out->label, pts);
+        outs.add(out->raw, pts);
+        outs.add(out->size, pts);
+        outs.add(out->indices, pts);
+    }
+    outs.add(clusters, cloud_points(clusters_capacity, kMeshCloudMax));
+    const int rc = entered(c, [&] {
+        return cluster_euclidean(c, cloud, n, p, out, clusters, clusters_capacity, n_clusters, outs, res, mem);
+    });
+    if (rc != O3DR_OK && rc != O3DR_ERR_CAPACITY) {  // host outputs zeroed on error
+        if (n_clusters) *n_clusters = 0;
+        outs.zero();
+    }
+    if (rc != O3DR_OK && res) memset(res, 0, sizeof *res);
     return rc;
 }
 

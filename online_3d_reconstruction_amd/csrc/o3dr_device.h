@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/o3dr.h"
+#include "../../include/o3dr_objects.h"
 #include "../../include/o3dr_terrain.h"
 
 namespace o3dr {
@@ -605,6 +606,44 @@ inline int64_t ground_parts(const GroundArgs& a)
 // launch_ground: the minimum surface, the iterations (enqueued back to back: nothing is read back), the DTM with its fill,
 // the point pass; every count folded into a.counters
 void launch_ground(Profiler* pf, hipStream_t s, const GroundArgs& a);
+// Euclidean clustering (kernels/cluster.inc; contract: include/o3dr_objects.h).  The grid is launch_nn_grid's (ws.sor_*, the
+// cells' boxes, the cloud's box); every array below is the call's own scratch but the outputs.
+struct ClusterArgs {
+    uint32_t n;
+    const float4* sxyz;           // the cloud in cell order, .w = original index bits
+    const uint32_t* cell_first;
+    const float4* cell_lo;
+    const float4* cell_hi;
+    const SorGeom* sg;
+    const float* box6;            // the cloud's bounding box (min xyz, max xyz)
+    float r2;                     // (float)(tolerance * tolerance)
+    float pad_r;                  // max(tolerance (1 + 1e-5), 1e-18): half the side of a point's box
+    int32_t min_size, max_size;
+    int* parent;                  // n, by original index: the union-find, then every point's final root (raw)
+    uint32_t* cnt;                // n: the size of the component at its root
+    uint32_t* num;                // n: 1 at a root that is a cluster -> its number (exclusive scan)
+    uint32_t* beg;                // n: the size at such a root -> its begin in indices (exclusive scan)
+    uint32_t* part;               // cluster_blocks(n) * kPartWords
+    uint32_t* counters;           // 12 words: n_components n_too_small n_too_large largest | n_clustered_points - - - |
+                                  //   n_clusters (the first scan's total), n_clustered_points (the second's), - -
+    unsigned long long* n_pairs;
+    int32_t* label;               // n or nullptr
+    int32_t* raw;                 // n or nullptr
+    int32_t* size;                // n or nullptr
+    int32_t* indices;             // n_clustered_points or nullptr
+    o3dr_cluster* rec;            // n_clusters or nullptr
+    uint32_t* box_lo;             // 3 * n_clusters: order-preserving words of the boxes' minima (with rec)
+    uint32_t* box_hi;             // 3 * n_clusters: ... maxima
+    unsigned long long* sums;     // 3 * n_clusters: the quantised offsets' sums
+};
+constexpr int kClusterCounterWords = 12;
+inline int64_t cluster_blocks(int64_t n) { return (n + 255) / 256; }
+// launch_cluster_link: parent initialised, the links joined and counted, every point flattened to its root, the sizes, the
+// cluster flags with the result's counters, the two scans.  Nothing of the caller's is written.
+void launch_cluster_link(Profiler* pf, hipStream_t s, Workspace& ws, const ClusterArgs& a);
+// launch_cluster_outputs: after the counts were read back: the point outputs, the records (a.rec), indices (a stable sort
+// of the points by cluster number through ws.keys / ws.vals: only the passes n_clusters needs)
+void launch_cluster_outputs(Profiler* pf, hipStream_t s, Workspace& ws, const ClusterArgs& a, uint32_t n_clusters, uint32_t n_clustered);
 // plane-fitted disparity per segment label (kernels/plane_disparity.inc).  `table`: kPdSums 64-bit sums per (frame, label) -
 // n Sx Sy Sxx Sxy Syy Sd Sxd Syd Sdd and the pixel count -, zeroed here; thr: d participates iff (int)d > thr; flag: a
 // device word, bit 0 set when a label >= n_labels was seen.  launch_plane_disp runs the three steps for `frames` frames:

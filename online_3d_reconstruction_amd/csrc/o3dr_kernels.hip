@@ -35,6 +35,7 @@
 //   mesh         height-field surface mesh over the XY cells
 //   raster       the merged map as images: one point per XY cell, separable hole fill, the output images, shaded relief
 //   ground       bare-earth ground filter on the raster's cells: sliding window minima / maxima, DTM, height above ground
+//   cluster      Euclidean clustering: radius walk + union-find, sizes, numbering, per-cluster records, indices
 //   match        Hamming 2-NN descriptor matching, index-aligned 3-D keypoints, the batched rigid fit
 //   orb          ORB features: grey pyramid, FAST score + box sums, candidates, exact selection, steered BRIEF
 //   stereo       stereo disparity: grey + census, semi-global aggregation (one wave per scan line), winner + left-right check
@@ -65,6 +66,7 @@ namespace o3dr {
 #include "kernels/small.inc"
 #include "kernels/nn.inc"
 #include "kernels/mls.inc"
+#include "kernels/cluster.inc"
 #include "kernels/cell_order.inc"
 #include "kernels/plane.inc"
 #include "kernels/mesh.inc"
@@ -1316,6 +1318,50 @@ void launch_ground(Profiler* pf, hipStream_t s, const GroundArgs& a)
         ProfScope ps(pf, O3DR_K_GROUND_POINTS, s);
         if (gw > 0) k_ground_points<<<gw, kGroundThreads, 0, s>>>(a);
         k_fold4_u32<<<1, kFoldThreads, 0, s>>>(r.part, gw, 0, 2, 2, 2, 2, a.counters + 12);
+    }
+}
+
+// Euclidean clustering (kernels/cluster.inc) over the grid launch_nn_grid left in ws.sor_*
+void launch_cluster_link(Profiler* pf, hipStream_t s, Workspace& ws, const ClusterArgs& a)
+{
+    const int g = (int)cluster_blocks(a.n);
+    {
+        ProfScope ps(pf, O3DR_K_CLUSTER_LINK, s);
+        (void)hipMemsetAsync(a.n_pairs, 0, sizeof(unsigned long long), s);
+        k_cluster_init<<<g, kClusterThreads, 0, s>>>(a.parent, a.n);
+        k_cluster_link<<<g, kClusterThreads, 0, s>>>(a);
+    }
+    {
+        ProfScope ps(pf, O3DR_K_CLUSTER_NUMBER, s);
+        (void)hipMemsetAsync(a.cnt, 0, (size_t)a.n * sizeof(uint32_t), s);
+        k_cluster_flatten<<<g, kClusterThreads, 0, s>>>(a);
+        k_cluster_flags<<<g, kClusterThreads, 0, s>>>(a);
+        k_fold4_u32<<<1, kFoldThreads, 0, s>>>(a.part, g, 0, 2, 2, 2, 1, a.counters);
+        k_fold4_u32<<<1, kFoldThreads, 0, s>>>(a.part, g, 4, 2, 2, 2, 2, a.counters + 4);
+        launch_scan(s, a.num, a.n, a.n, 1, a.counters + 8, nullptr, ws.scan_partial);
+        launch_scan(s, a.beg, a.n, a.n, 1, a.counters + 9, nullptr, ws.scan_partial);
+    }
+}
+
+void launch_cluster_outputs(Profiler* pf, hipStream_t s, Workspace& ws, const ClusterArgs& a, uint32_t n_clusters, uint32_t n_clustered)
+{
+    ProfScope ps(pf, O3DR_K_CLUSTER_RECORDS, s);
+    const int g = (int)cluster_blocks(a.n);
+    k_cluster_points<<<g, kClusterThreads, 0, s>>>(a);
+    if (a.rec && n_clusters > 0) {
+        (void)hipMemsetAsync(a.box_lo, 0xff, (size_t)n_clusters * 3 * sizeof(uint32_t), s);
+        (void)hipMemsetAsync(a.box_hi, 0, (size_t)n_clusters * 3 * sizeof(uint32_t), s);
+        (void)hipMemsetAsync(a.sums, 0, (size_t)n_clusters * 3 * sizeof(unsigned long long), s);
+        k_cluster_boxes<<<g, kClusterThreads, 0, s>>>(a);
+        k_cluster_sums<<<g, kClusterThreads, 0, s>>>(a);
+        k_cluster_records<<<(int)cluster_blocks(n_clusters), kClusterThreads, 0, s>>>(a, n_clusters);
+    }
+    if (a.indices && n_clustered > 0) {
+        int nbits = 0;
+        while (nbits < 32 && (n_clusters >> nbits) != 0) ++nbits;  // the keys are 0 .. n_clusters
+        k_cluster_keys<<<g, kClusterThreads, 0, s>>>(a, n_clusters, ws.keys[0]);
+        const int sorted = launch_sort_keys(ws, s, a.n, nbits);
+        k_cluster_indices<<<(int)cluster_blocks(n_clustered), kClusterThreads, 0, s>>>(ws.vals[sorted], n_clustered, a.indices);
     }
 }
 

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/o3dr.h"
+#include "../../include/o3dr_objects.h"
 #include "../../include/o3dr_terrain.h"
 
 namespace o3dr_host {
@@ -143,6 +144,10 @@ public:
     bool ground_linear = false;      // --ground_fill_radius r (cells, 0..32); parsed and ignored without --ground_filter
     double ground_slope = 0.7, ground_initial_distance = 0.15, ground_max_distance = 10.0;
     int ground_fill_radius = 0;
+    bool cluster_cloud = false;      // --cluster_cloud file.ply: o3dr_cluster_euclidean of one PLY -> clusters_ / unclustered_<file>,
+    bool cluster_tolerance_set = false;  // clusters_<file>.txt; --cluster_tolerance t (metres, required there),
+    double cluster_tolerance = 0.0;  // --cluster_min_size n, --cluster_max_size n; parsed and ignored without --cluster_cloud
+    int cluster_min_size = 1, cluster_max_size = INT32_MAX;
     int device_id = 0;
     int n_gpus = 1;                 // --gpus N: frames sharded over devices device_id .. device_id+N-1, one host thread and
                                     // one context each, merged through o3dr_merge_partitioned (RCCL)
@@ -260,6 +265,7 @@ private:
     void run_mesh_surface();                        // --mesh_surface
     void run_orthophoto();                          // --orthophoto
     void run_ground_filter();                       // --ground_filter
+    void run_cluster_cloud();                       // --cluster_cloud
     // the map's rasters of a host cloud (o3dr_raster_extent, o3dr_rasterize_map with the --ortho_* flags) as PNGs, rows in
     // descending cy (north up); shade_path is written with --ortho_light only.  Prints the box, the counts and the call time.
     void write_map_rasters(o3dr_ctx* c, const PointCloud& cloud, const std::string& ortho_path, const std::string& height_path,

@@ -515,6 +515,14 @@ void Pose::printUsage()
             "                     schedule, the removed cells per iteration, the ground cells and points and the call time;\n"
             "                     elsewhere the --ground_* flags are parsed and ignored - the flags and the file names are this\n"
             "                     build's own)\n"
+            "./pose --cluster_cloud file.ply --cluster_tolerance t [--cluster_min_size n] [--cluster_max_size n]\n"
+            "                     (Euclidean clustering: points closer than t metres are linked, a component of the links' closure\n"
+            "                     with n_min <= points <= n_max (defaults 1 and 2^31 - 1) is a cluster, numbered by its lowest point\n"
+            "                     index; writes the clustered points as clusters_<file>, cluster by cluster with a colour per\n"
+            "                     cluster, the other points as unclustered_<file> in input order, and clusters_<file>.txt, one line\n"
+            "                     per cluster: number first size lo[3] hi[3] centroid[3]; prints the counters, the first ten\n"
+            "                     records and the call time; objects_<file> of --ground_filter is the intended input; elsewhere\n"
+            "                     the --cluster_* flags are parsed and ignored - the flags and the file names are this build's own)\n"
             "./pose --find_features image.png [--orb_n_features n] [--orb_levels n] [--orb_scale s] [--orb_fast_threshold t]\n"
             "                     (ORB keypoints of one image: prints the count per level and writes one \"x y\" per line as\n"
             "                     <image>.keypoints.txt, the --keypoints_dir format - the flags and the file name are this build's own)\n"
@@ -628,6 +636,10 @@ int Pose::parseCmdArgs(int argc, char** argv)
         else if (a == "--ground_initial_distance") ground_initial_distance = atof(need(i));
         else if (a == "--ground_max_distance") ground_max_distance = atof(need(i));
         else if (a == "--ground_fill_radius") ground_fill_radius = atoi(need(i));
+        else if (a == "--cluster_cloud") { files(i, "file.ply", read_PLY_filename0); cluster_cloud = true; }
+        else if (a == "--cluster_tolerance") { cluster_tolerance = atof(need(i)); cluster_tolerance_set = true; }
+        else if (a == "--cluster_min_size") cluster_min_size = atoi(need(i));
+        else if (a == "--cluster_max_size") cluster_max_size = atoi(need(i));
         else if (a == "--ortho_select") ortho_select = need(i);
         else if (a == "--ortho_fill_radius") ortho_fill_radius = atoi(need(i));
         else if (a == "--ortho_light") {
@@ -782,6 +794,13 @@ int Pose::parseCmdArgs(int argc, char** argv)
             throw runtime_error("--ground_initial_distance must be finite and >= 0");
         if (!(isfinite(ground_max_distance) && ground_max_distance >= 0.0)) throw runtime_error("--ground_max_distance must be finite and >= 0");
         if (ground_fill_radius < 0 || ground_fill_radius > O3DR_RASTER_MAX_FILL_RADIUS) throw runtime_error("--ground_fill_radius must be in 0..32");
+    }
+    if (cluster_cloud) {
+        if (!ifstream(read_PLY_filename0)) throw runtime_error("could not read " + read_PLY_filename0);
+        if (!cluster_tolerance_set) throw runtime_error("--cluster_cloud needs --cluster_tolerance t (metres)");
+        if (!(isfinite(cluster_tolerance) && cluster_tolerance > 0.0)) throw runtime_error("--cluster_tolerance must be finite and > 0");
+        if (cluster_min_size < 1) throw runtime_error("--cluster_min_size must be >= 1");
+        if (cluster_max_size < cluster_min_size) throw runtime_error("--cluster_max_size must be >= --cluster_min_size");
     }
     if (run3d_reconstruction && gpu_keypoints) batched_path_only("--gpu_keypoints", true);
     if (run3d_reconstruction && gpu_disparity) {
@@ -1107,6 +1126,65 @@ void Pose::run_ground_filter()
     const string dtm_path = next_to(read_PLY_filename0, "dtm_", ".png");
     if (!write_png_grey16(dtm_path, d16.data(), H, W)) throw runtime_error("could not write " + dtm_path);
     cerr << "Saved " << W << " x " << H << " terrain model to " << dtm_path << endl;
+}
+
+// --cluster_cloud: the objects of one PLY (o3dr_cluster_euclidean; contract: include/o3dr_objects.h), written as
+// clusters_<file>, unclustered_<file> and clusters_<file>.txt next to the source.
+void Pose::run_cluster_cloud()
+{
+    PointCloud::Ptr cloud = read_PLY_File(read_PLY_filename0);
+    const int64_t n = (int64_t)cloud->points.size();
+    o3dr_cluster_params prm;
+    o3dr_cluster_default_params(&prm);
+    prm.tolerance = cluster_tolerance, prm.min_size = cluster_min_size, prm.max_size = cluster_max_size;
+    vector<int32_t> label((size_t)n), indices((size_t)n);
+    vector<o3dr_cluster> rec((size_t)(n / cluster_min_size));  // no more clusters fit in n points
+    o3dr_cluster_outputs out = {label.data(), nullptr, nullptr, indices.data()};
+    o3dr_cluster_result res;
+    int64_t K = 0;
+    o3dr_ctx* c = ctx_for_this_thread();
+    const auto t0 = chrono::steady_clock::now();
+    chk(o3dr_cluster_euclidean(c, cloud->points.data(), n, &prm, &out, rec.empty() ? nullptr : rec.data(), (int64_t)rec.size(), &K, &res,
+                               O3DR_MEM_HOST),
+        "o3dr_cluster_euclidean");
+    const double ms = chrono::duration<double, milli>(chrono::steady_clock::now() - t0).count();
+    // the clustered points in indices order, a colour per cluster number (a hash: neighbours in number differ); the others
+    PointCloud::Ptr clustered(new PointCloud()), rest(new PointCloud());
+    for (int64_t k = 0; k < K; ++k) {
+        const uint32_t h = (uint32_t)(k + 1) * 2654435761u;
+        const uint32_t rgba = 0xff000000u | (h >> 8) | 0x00404040u;
+        for (int32_t j = rec[(size_t)k].begin; j < rec[(size_t)k].begin + rec[(size_t)k].size; ++j) {
+            auto p = cloud->points[(size_t)indices[(size_t)j]];
+            p.rgba = rgba;
+            clustered->points.push_back(p);
+        }
+    }
+    for (int64_t i = 0; i < n; ++i)
+        if (label[(size_t)i] < 0) rest->points.push_back(cloud->points[(size_t)i]);
+    char line[512];
+    const string txt_path = next_to(read_PLY_filename0, "clusters_", ".txt");
+    ofstream txt(txt_path);
+    cout << "points in " << n << ", linked pairs " << res.n_pairs << endl;
+    cout << "components " << res.n_components << " (largest " << res.largest << "), clusters " << res.n_clusters << ", too small " << res.n_too_small
+         << ", too large " << res.n_too_large << endl;
+    cout << "clustered points " << res.n_clustered_points << ", other points " << res.n_rejected_points << endl;
+    for (int64_t k = 0; k < K; ++k) {
+        const o3dr_cluster& r = rec[(size_t)k];
+        snprintf(line, sizeof line, "%lld %d %d %.9g %.9g %.9g %.9g %.9g %.9g %.17g %.17g %.17g", (long long)k, r.first, r.size, (double)r.lo[0],
+                 (double)r.lo[1], (double)r.lo[2], (double)r.hi[0], (double)r.hi[1], (double)r.hi[2], r.centroid[0], r.centroid[1], r.centroid[2]);
+        txt << line << "\n";
+        if (k < 10) cout << "cluster " << line << endl;
+    }
+    txt.close();
+    if (!txt) throw runtime_error("could not write " + txt_path);
+    snprintf(line, sizeof line, "cluster time %.3f ms", ms);
+    cout << line << endl;
+    for (const auto& o : {make_pair("clusters_", clustered), make_pair("unclustered_", rest)}) {
+        const string path = next_to(read_PLY_filename0, o.first);
+        if (!save_ply_binary(path, *o.second)) throw runtime_error("could not write " + path);
+        cerr << "Saved Point Cloud with " << o.second->points.size() << " data points to " << path << endl;
+    }
+    cerr << "Saved " << K << " cluster records to " << txt_path << endl;
 }
 
 o3dr_orb_params Pose::orb_params() const
@@ -1457,6 +1535,10 @@ Pose::Pose(int argc, char* argv[])
     }
     if (ground_filter) {
         run_ground_filter();
+        return;
+    }
+    if (cluster_cloud) {
+        run_cluster_cloud();
         return;
     }
     if (!find_features_png.empty()) {
