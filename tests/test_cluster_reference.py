@@ -105,3 +105,89 @@ def test_components_agree_with_scipy_where_it_is_installed():
         first = np.full(k, len(xyz))
         np.minimum.at(first, lab, np.arange(len(xyz)))
         assert np.array_equal(first[lab], r.raw)
+
+
+# ---- the pair search and the components that scale (cluster(..., pairs="tree")) against the brute force --------------------
+BELOW_QUARTER = float(np.nextafter(F32(0.25), F32(0)))
+
+
+def duplicated_scene():
+    """300 points, 100 of them twice more and 50 a fourth time, in random order: pairs at d2 == 0"""
+    rng = np.random.default_rng(7)
+    base = (rng.random((300, 3)) * 4.0).astype(F32)
+    xyz = np.concatenate([base, base[:100], base[:100], base[:50]])
+    return xyz[rng.permutation(len(xyz))]
+
+
+def far_scene():
+    """the random scene moved by 8192 m in x and y (fp32 sums: the coordinates keep 2^-10 m)"""
+    xyz = random_scene()
+    xyz[:, :2] += F32(8192.0)
+    return xyz
+
+
+SCENES = {"random 0.3": (random_scene, 0.3), "random 0.4": (random_scene, 0.4), "random 0.5": (random_scene, 0.5),
+          "line at the tolerance": (line, 0.25), "line just below": (line, BELOW_QUARTER), "column": (column, 0.5),
+          "column below": (column, 0.49), "duplicates": (duplicated_scene, 1e-3), "duplicates 0.3": (duplicated_scene, 0.3),
+          "far 0.4": (far_scene, 0.4)}
+
+
+def records_by_loop(xyz, r):
+    """step 5 of the contract cluster by cluster, as the reference computed it before records() was vectorised"""
+    rec = r.clusters.copy()
+    for name in ("lo", "hi", "centroid"):
+        rec[name] = 0
+    for k in range(len(rec)):
+        m = xyz[r.indices[rec["begin"][k]:rec["begin"][k] + rec["size"][k]]]
+        c = m + F32(0)
+        lo, hi = c.min(0), c.max(0)
+        q = np.floor((m.astype(np.float64) - lo.astype(np.float64)) * 65536.0 + 0.5).astype(np.int64)
+        S = q.sum(0, dtype=np.int64)
+        rec["lo"][k], rec["hi"][k] = lo, hi
+        rec["centroid"][k] = lo.astype(np.float64) + (S.astype(np.float64) / 65536.0) / np.float64(rec["size"][k])
+    return rec
+
+
+def assert_identical(a, b, what):
+    assert sorted(vars(a)) == sorted(vars(b)) == ["clusters", "indices", "info", "label", "raw", "size"]
+    for name in ("label", "raw", "size", "indices"):
+        x, y = getattr(a, name), getattr(b, name)
+        assert x.dtype == y.dtype == np.int32 and x.shape == y.shape and np.array_equal(x, y), (what, name)
+    assert a.info == b.info, (what, a.info, b.info)
+    assert a.clusters.dtype == b.clusters.dtype == cr.CLUSTER and a.clusters.tobytes() == b.clusters.tobytes(), (what, "records")
+
+
+@pytest.mark.parametrize("scene", list(SCENES))
+def test_the_tree_search_finds_the_pairs_of_the_brute_force(scene):
+    make, tolerance = SCENES[scene]
+    xyz = make()
+    I, J = cr.linked_pairs(xyz, tolerance)
+    It, Jt = cr.linked_pairs_tree(xyz, tolerance)
+    assert It.dtype == Jt.dtype == np.int64 and (It > Jt).all() and len(np.unique(It * len(xyz) + Jt)) == len(It)
+    assert np.array_equal(np.sort(It * len(xyz) + Jt), np.sort(I * len(xyz) + J))
+    assert np.array_equal(cr.components_graph(len(xyz), It, Jt), cr.components(len(xyz), I, J))
+    if scene.startswith("line"):  # d2 == r2 decides every pair here
+        assert len(I) == (599 if tolerance == 0.25 else 0)
+    if scene == "duplicates":
+        assert len(I) == 50 * 3 + 50 * 6  # a point three / four times: 3 / 6 pairs at distance 0
+
+
+@pytest.mark.parametrize("limits", [(1, cr.MAX_SIZE), (2, 50)])
+@pytest.mark.parametrize("scene", list(SCENES))
+def test_the_tree_cluster_is_the_brute_force_cluster_and_the_records_are_the_loops(scene, limits):
+    make, tolerance = SCENES[scene]
+    xyz = make()
+    brute = random_result(tolerance, *limits) if make is random_scene else cr.cluster(xyz, tolerance, *limits)
+    assert_identical(cr.cluster(xyz, tolerance, *limits, pairs="tree"), brute, scene)
+    assert brute.clusters.tobytes() == records_by_loop(xyz, brute).tobytes(), scene
+    if limits == (2, 50) and scene in ("random 0.5", "duplicates 0.3", "far 0.4"):
+        assert brute.info["n_too_small"] > 0 and brute.info["n_clusters"] > 0 and brute.info["n_rejected_points"] > 0
+
+
+def test_the_tree_search_on_an_empty_cloud_and_a_single_point():
+    for n in (0, 1):
+        xyz = np.full((n, 3), 2.5, F32)
+        assert_identical(cr.cluster(xyz, 0.5, pairs="tree"), cr.cluster(xyz, 0.5), n)
+    # the slack of the candidate radius is above the gate's rounding (cluster_reference.tree_radius) at every magnitude
+    for tol in (1e-22, 1e-3, 0.1, 1.0, 1e4):
+        assert cr.tree_radius(tol) > tol * (1 + 2.0 ** -24) ** 3 + np.sqrt(3.0) * 2.0 ** -75
