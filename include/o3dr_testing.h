@@ -48,8 +48,8 @@ int o3dr_test_orb_scratch_limit(o3dr_ctx* ctx, int64_t bytes);
 /* Fills every per-call scratch block this context currently owns with `byte` (0..255), over the block's whole capacity
  * and not just the last call's layout, in stream order on the context's stream: one hipMemsetAsync per block, no kernel.
  * *bytes_filled = the sum.  No later call's result may depend on it (DESIGN.md "Scratch contract").
- * Filled: the shared operator blocks op[0..4]; the sort / voxel workspace, its point block and the outlier removal's
- * block; the staging buffers (st_*, st2_*, st_blur*, st_hist, st_xchg, st_merge, st_gather); nn_q, nn_t, nn_cells, nn_src;
+ * Filled: the shared operator blocks op[0..4]; the sort / voxel workspace, its point block, the search grids' block and
+ * the outlier removal's block; the staging buffers (st_*, st2_*, st_blur*, st_hist, st_xchg, st_merge, st_gather); nn_q, nn_t, nn_cells, nn_src;
  * the incremental merge's per-call buffers (scratch, tg, tmatch, flag, src, keep, partial, words) and its fallback result;
  * the 4 KiB misc block and the single-shot counters.
  * Never touched, because they carry state from call to call: cloud_big, its second buffer, its counters, running bounding

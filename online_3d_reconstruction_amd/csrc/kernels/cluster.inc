@@ -3,7 +3,7 @@
 
 // =================================================================================================
 // Euclidean clustering (contract: include/o3dr_objects.h; DESIGN.md "Euclidean clustering").  The cloud's search grid is
-// the nearest-neighbour grid (launch_nn_grid), the links come from MLS's exact radius walk (mls_walk, util.inc) and the
+// the nearest-neighbour grid (launch_nn_grid), the links come from MLS's exact radius walk (grid_radius_walk, util.inc) and the
 // components from the disparity filter's lock-free union-find (df_find_halve / df_union<DfGlobal>, util.inc) over `parent`, one
 // int32 per point indexed by ORIGINAL index: parent[i] <= i always, a larger root only ever goes under a smaller one, so
 // a component's final root is its lowest index whatever the order of the links.  No thread waits for another, no
@@ -33,17 +33,13 @@ __global__ __launch_bounds__(kClusterThreads) void k_cluster_link(ClusterArgs a)
     const int64_t t = (int64_t)blockIdx.x * kClusterThreads + threadIdx.x;
     uint32_t pairs = 0;
     if (t < (int64_t)a.n) {
-        const SorGeom g = *a.sg;
-        const float4 q = a.sxyz[t];
+        const SorGeom g = *a.grid.geom;
+        const float4 q = a.grid.xyz[t];
         const int idx = (int)__float_as_uint(q.w);
-        // the window of k_mls: the cells of the point's box, through the monotone cell assignment of the points
-        const float x0f = fmaxf(q.x - a.pad_r, a.box6[0]), x1f = fminf(q.x + a.pad_r, a.box6[3]);
-        const float y0f = fmaxf(q.y - a.pad_r, a.box6[1]), y1f = fminf(q.y + a.pad_r, a.box6[4]);
-        const int x0 = sor_col(g, x0f), x1 = sor_col(g, x1f), y0 = sor_row(g, y0f), y1 = sor_row(g, y1f);
         // The lane's current root stays in a register: in a dense cloud most neighbours are in the lane's tree already,
         // and one find of the neighbour tells.  A stale root only costs a union that finds nothing to do.
         int root = df_find_halve<DfGlobal>(a.parent, idx);
-        mls_walk(a, g, x0, x1, y0, y1, q.x, q.y, q.z, [&](const float4& p, float) {
+        grid_radius_walk(a.grid, g, q, a.pad_r, a.r2, [&](const float4& p, float) {
             const int j = (int)__float_as_uint(p.w);
             if (j >= idx) return;  // every pair once, from its higher index (the point itself and later duplicates: not here)
             ++pairs;
@@ -87,7 +83,7 @@ __global__ __launch_bounds__(kClusterThreads) void k_cluster_flatten(ClusterArgs
     const bool valid = t < (int64_t)a.n;
     int root = 0;
     if (valid) {
-        const int idx = (int)__float_as_uint(a.sxyz[t].w);
+        const int idx = (int)__float_as_uint(a.grid.xyz[t].w);
         root = df_find_halve<DfGlobal>(a.parent, idx);
         if (root != idx) DfGlobal::lower(a.parent + idx, root);  // an ancestor: the word is only lowered
     }
@@ -155,7 +151,7 @@ __global__ __launch_bounds__(kClusterThreads) void k_cluster_boxes(ClusterArgs a
     uint32_t number = 0;
     bool kept = false;
     if (t < (int64_t)a.n) {
-        p = a.sxyz[t];
+        p = a.grid.xyz[t];
         kept = cluster_number_of(a, p, number);
     }
     const uint32_t c[3] = {f32_ordered(p.x + 0.0f), f32_ordered(p.y + 0.0f), f32_ordered(p.z + 0.0f)};
@@ -186,7 +182,7 @@ __global__ __launch_bounds__(kClusterThreads) void k_cluster_sums(ClusterArgs a)
     uint32_t number = 0;
     bool kept = false;
     if (t < (int64_t)a.n) {
-        p = a.sxyz[t];
+        p = a.grid.xyz[t];
         kept = cluster_number_of(a, p, number);
     }
     unsigned long long q[3] = {0ull, 0ull, 0ull};

@@ -5,11 +5,9 @@
 // Moving-least-squares smoothing and normals (o3dr_mls_smooth; DESIGN.md "MLS")
 //   The cloud's search grid is the nearest-neighbour grid (launch_nn_grid: points in cell order with their original index
 //   in .w, exact per-cell boxes, the cloud's box).  ONE LANE PER QUERY, queries taken in the grid's cell order (lane t:
-//   sor_xyz[t], results to index .w), so the lanes of a wave share cells.  The window is every cell between the cells of
-//   the query's box (q -/+ r(1 + 1e-5), clamped to the cloud's box) in x and y: the cell assignment (sor_cell) is monotone
-//   in the coordinate, so no neighbour lies outside it.  A cell whose exact box is farther than r2 is skipped (the lower
-//   bound of nn_visit, never above a computed distance).  Pass 1: k and the fp64 moments about the query; a fixed-sweep
-//   3x3 Jacobi; pass 2 (polynomial fit): the weighted moments sum w u^a v^b (a + b <= 2 order) and sum w f u^a v^b; a
+//   grid.xyz[t], results to index .w), so the lanes of a wave share cells.  The neighbours come from the exact radius walk
+//   over the window of the query's box (grid_radius_walk, util.inc: the clustering shares it).  Pass 1: k and the fp64
+//   moments about the query; a fixed-sweep 3x3 Jacobi; pass 2 (polynomial fit): the weighted moments sum w u^a v^b (a + b <= 2 order) and sum w f u^a v^b; a
 //   Cholesky solve and the epilogue.  Sums run over the window's cells row by row, points in cell order: no atomics
 //   but the integer counters of the result.
 // =================================================================================================
@@ -18,23 +16,16 @@ constexpr int kMlsThreads = 256;
 struct MlsArgs {
     const o3dr_point* cloud;  // n points in the caller's order (colours are read here)
     uint32_t n;
-    const float4* sxyz;       // the cloud in cell order, .w = original index bits
-    const uint32_t* cell_first;
-    const float4* cell_lo;
-    const float4* cell_hi;
-    const SorGeom* sg;
-    const float* box6;        // the cloud's bounding box (min xyz, max xyz)
+    SearchGrid grid;          // the cloud's
     float r2;                 // (float)(r * r)
     double r, inv_h;          // search radius; 1 / sqr_gauss_param
-    float pad_r;              // max(r (1 + 1e-5), 1e-18): half the side of the query's box
+    float pad_r;              // grid_pad_radius(r): half the side of the query's box
     o3dr_point* out;          // n (may be cloud)
     float* normals;           // 4 n (nx ny nz curvature) or nullptr
     uint32_t* nn_count;       // n or nullptr
     uint8_t* fit;             // n or nullptr
     unsigned long long* counters;  // n_none, n_plane, n_poly, max k
 };
-
-// (mls_walk, the exact radius walk over the window's cells, is in util.inc: the clustering shares it)
 
 template <int O>
 __global__ __launch_bounds__(kMlsThreads) void k_mls(MlsArgs a)
@@ -44,16 +35,12 @@ __global__ __launch_bounds__(kMlsThreads) void k_mls(MlsArgs a)
     int kind = -1;
     uint32_t k = 0;
     if (valid) {
-        const SorGeom g = *a.sg;
-        const float4 q = a.sxyz[t];
+        const SorGeom g = *a.grid.geom;
+        const float4 q = a.grid.xyz[t];
         const uint32_t idx = __float_as_uint(q.w);
-        // the window: the cells of the query's box, through the monotone cell assignment of the points
-        const float x0f = fmaxf(q.x - a.pad_r, a.box6[0]), x1f = fminf(q.x + a.pad_r, a.box6[3]);
-        const float y0f = fmaxf(q.y - a.pad_r, a.box6[1]), y1f = fminf(q.y + a.pad_r, a.box6[4]);
-        const int x0 = sor_col(g, x0f), x1 = sor_col(g, x1f), y0 = sor_row(g, y0f), y1 = sor_row(g, y1f);
         // pass 1: k and the moments about the query
         double s1[3] = {0.0, 0.0, 0.0}, s2[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        mls_walk(a, g, x0, x1, y0, y1, q.x, q.y, q.z, [&](const float4& p, float) {
+        grid_radius_walk(a.grid, g, q, a.pad_r, a.r2, [&](const float4& p, float) {
             const double ex = (double)p.x - (double)q.x, ey = (double)p.y - (double)q.y, ez = (double)p.z - (double)q.z;
             ++k;
             s1[0] += ex, s1[1] += ey, s1[2] += ez;
@@ -111,7 +98,7 @@ __global__ __launch_bounds__(kMlsThreads) void k_mls(MlsArgs a)
 #pragma unroll
                     for (int m = 0; m < nc; ++m) Fv[m] = 0.0;
                     const double inv_r = 1.0 / a.r, inv_h = a.inv_h;
-                    mls_walk(a, g, x0, x1, y0, y1, q.x, q.y, q.z, [&](const float4& p, float d) {
+                    grid_radius_walk(a.grid, g, q, a.pad_r, a.r2, [&](const float4& p, float d) {
                         const double ex = (double)p.x - px, ey = (double)p.y - py, ez = (double)p.z - pz;
                         const double u = (ex * ux + ey * uy + ez * uz) * inv_r, v = (ex * vx + ey * vy + ez * vz) * inv_r;
                         const double f = ex * nx + ey * ny + ez * nz;

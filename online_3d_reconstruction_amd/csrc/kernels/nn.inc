@@ -47,12 +47,7 @@ struct NnArgs {
     uint32_t n;
     int32_t xf;               // 1: the query is a2_apply(T, point) (the ICP pass); 0: the point as it is
     Mat34 T;
-    const float4* txyz;       // target in cell order, .w = original index bits
-    const uint32_t* cell_first;
-    const float4* cell_lo;
-    const float4* cell_hi;
-    const SorGeom* sg;        // the target's grid (n == 0 or inactive: no target points)
-    const float* box6;        // the target's bounding box (min xyz, max xyz)
+    SearchGrid grid;          // the target's
     float r2;
     uint32_t* idx_out;        // n
     float* d2_out;            // n or nullptr
@@ -66,12 +61,12 @@ __device__ __forceinline__ void nn_visit(const NnArgs& a, int64_t c, float qx, f
                                          unsigned long long& best, float4& bp)
 {
     const float bd = best != ~0ull ? __uint_as_float((uint32_t)(best >> 32)) : __builtin_huge_valf();
-    const float4 lo = a.cell_lo[c], hi = a.cell_hi[c];
+    const float4 lo = a.grid.cell_lo[c], hi = a.grid.cell_hi[c];
     const float lb = cell_box_d2_lower_bound(lo, hi, qx, qy, qz);
     if (!(lb <= bd && lb <= r2)) return;
-    const uint32_t s = a.cell_first[c], e = a.cell_first[c + 1];
+    const uint32_t s = a.grid.cell_first[c], e = a.grid.cell_first[c + 1];
     for (uint32_t j = s; j < e; ++j) {
-        const float4 p = a.txyz[j];
+        const float4 p = a.grid.xyz[j];
         const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
         const float d = (dx * dx + dy * dy) + dz * dz;
         const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned long long)__float_as_uint(p.w);
@@ -132,7 +127,7 @@ __global__ __launch_bounds__(kNnThreads) void k_nn_query(NnArgs a)
     }
     unsigned long long best = ~0ull;
     float4 bp = make_float4(0.f, 0.f, 0.f, 0.f);
-    const SorGeom g = *a.sg;
+    const SorGeom g = *a.grid.geom;
     const float r2 = a.r2;
     // (a query with a non-finite coordinate has no neighbour)
     if (valid && g.active && g.n > 0 && isfinite(qx) && isfinite(qy) && isfinite(qz)) {
@@ -150,7 +145,7 @@ __global__ __launch_bounds__(kNnThreads) void k_nn_query(NnArgs a)
                     if (cx + r < g.gx) nn_visit(a, row + cx + r, qx, qy, qz, r2, best, bp);
                 }
             }
-            const double lb = nn_unvisited_bound(g, a.box6, cx, cy, r, (double)qx, (double)qy);
+            const double lb = nn_unvisited_bound(g, a.grid.box6, cx, cy, r, (double)qx, (double)qy);
             if (lb == __builtin_huge_val()) break;  // every cell visited
             const double thr = lb * (1.0 - 4e-6) - 1e-30;  // below the computed d2 of every unvisited point
             const double bd = best != ~0ull ? (double)__uint_as_float((uint32_t)(best >> 32)) : __builtin_huge_val();

@@ -88,24 +88,7 @@ __global__ __launch_bounds__(256) void k_sor_plan(const float* __restrict__ mm_a
     sor_plan_of(mn2, mx2, n_dev[f], max_cells, sg[f], geom[f], cell_points, active_above);
 }
 
-// the search grid's cell of a point: its column and row (clamped: the outermost ones are open-ended), and the cell id
-__device__ __forceinline__ int sor_col(const SorGeom& g, float x)
-{
-    const int cx = (int)((x - g.mnx) * g.inv_h);
-    return cx < 0 ? 0 : (cx >= g.gx ? g.gx - 1 : cx);
-}
-__device__ __forceinline__ int sor_row(const SorGeom& g, float y)
-{
-    const int cy = (int)((y - g.mny) * g.inv_h);
-    return cy < 0 ? 0 : (cy >= g.gy ? g.gy - 1 : cy);
-}
-__device__ __forceinline__ int sor_cell(const SorGeom& g, float x, float y, int& cx, int& cy)
-{
-    cx = sor_col(g, x), cy = sor_row(g, y);
-    return cy * g.gx + cx;
-}
-
-// cell id per point (the sort key)
+// cell id per point (the sort key; sor_cell and its column / row are in util.inc, next to the radius walk that shares them)
 __global__ __launch_bounds__(256) void k_sor_cells(const o3dr_point* __restrict__ in, int64_t in_fstride, const SorGeom* __restrict__ sg,
                                                    int64_t cap, uint32_t* __restrict__ keys)
 {

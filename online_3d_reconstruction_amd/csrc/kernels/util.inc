@@ -331,25 +331,46 @@ __device__ __forceinline__ void mls_jacobi3(double A[3][3], double V[3][3])
     }
 }
 
+// the search grid's cell of a point: its column and row (clamped: the outermost ones are open-ended), and the cell id
+__device__ __forceinline__ int sor_col(const SorGeom& g, float x)
+{
+    const int cx = (int)((x - g.mnx) * g.inv_h);
+    return cx < 0 ? 0 : (cx >= g.gx ? g.gx - 1 : cx);
+}
+__device__ __forceinline__ int sor_row(const SorGeom& g, float y)
+{
+    const int cy = (int)((y - g.mny) * g.inv_h);
+    return cy < 0 ? 0 : (cy >= g.gy ? g.gy - 1 : cy);
+}
+__device__ __forceinline__ int sor_cell(const SorGeom& g, float x, float y, int& cx, int& cy)
+{
+    cx = sor_col(g, x), cy = sor_row(g, y);
+    return cy * g.gx + cx;
+}
+
 // The exact radius walk over a search grid (launch_nn_grid), shared by MLS (kernels/mls.inc) and the clustering
 // (kernels/cluster.inc): f(p, d2) for every point p of the cloud with the fp32 d2 <= r2, in the fixed order of the MLS
-// contract.  `a` holds the grid (sxyz, cell_first, cell_lo, cell_hi) and r2.
-template <class Args, class F>
-__device__ __forceinline__ void mls_walk(const Args& a, const SorGeom& g, int x0, int x1, int y0, int y1, float qx, float qy,
-                                         float qz, F&& f)
+// contract.  g is *grid.geom, loaded by the caller.  The window is every cell between the cells of the query's box
+// (q -/+ pad_r = grid_pad_radius(r), clamped to the cloud's box) in x and y: the cell assignment is monotone in the
+// coordinate, so no neighbour lies outside it.  A cell whose exact box is farther than r2 is skipped.
+template <class F>
+__device__ __forceinline__ void grid_radius_walk(const SearchGrid& grid, const SorGeom& g, const float4& q, float pad_r, float r2, F&& f)
 {
+    const float x0f = fmaxf(q.x - pad_r, grid.box6[0]), x1f = fminf(q.x + pad_r, grid.box6[3]);
+    const float y0f = fmaxf(q.y - pad_r, grid.box6[1]), y1f = fminf(q.y + pad_r, grid.box6[4]);
+    const int x0 = sor_col(g, x0f), x1 = sor_col(g, x1f), y0 = sor_row(g, y0f), y1 = sor_row(g, y1f);
     for (int yy = y0; yy <= y1; ++yy) {
         const int64_t row = (int64_t)yy * g.gx;
         for (int xx = x0; xx <= x1; ++xx) {
             const int64_t c = row + xx;
-            const float4 lo = a.cell_lo[c], hi = a.cell_hi[c];
-            if (!(cell_box_d2_lower_bound(lo, hi, qx, qy, qz) <= a.r2)) continue;
-            const uint32_t s = a.cell_first[c], e = a.cell_first[c + 1];
+            const float4 lo = grid.cell_lo[c], hi = grid.cell_hi[c];
+            if (!(cell_box_d2_lower_bound(lo, hi, q.x, q.y, q.z) <= r2)) continue;
+            const uint32_t s = grid.cell_first[c], e = grid.cell_first[c + 1];
             for (uint32_t j = s; j < e; ++j) {
-                const float4 p = a.sxyz[j];
-                const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
+                const float4 p = grid.xyz[j];
+                const float dx = q.x - p.x, dy = q.y - p.y, dz = q.z - p.z;
                 const float d = (dx * dx + dy * dy) + dz * dz;
-                if (d <= a.r2) f(p, d);
+                if (d <= r2) f(p, d);
             }
         }
     }

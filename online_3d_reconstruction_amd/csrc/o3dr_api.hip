@@ -84,9 +84,9 @@ struct o3dr_ctx {
     size_t ws_pts_elems = 0;
     int ws_frames = 0;
     size_t ws_emit_tiles = 0, ws_sort_tiles = 0, ws_seg_tiles = 0, ws_mm_floats = 0;
-    DevBuf ws_block, ws_pts_block, ws_sor_block;
-    int64_t ws_sor_cap = 0;
-    int ws_sor_frames = 0;
+    DevBuf ws_block, ws_pts_block, ws_grid_block, ws_sor_block;
+    int64_t ws_grid_cap = 0, ws_sor_cap = 0;  // points per cloud and clouds the search grids / SOR's arrays are carved for
+    int ws_grid_frames = 0, ws_sor_frames = 0;
 
     // accumulating cloud (pose.cpp:434 cloud_big)
     o3dr_point* cloud_big = nullptr;
@@ -131,9 +131,10 @@ struct o3dr_ctx {
     int test_corrupt = 0;  // o3dr_test_corrupt_next_gather: consumed by the next voxel grid
     int test_fail_at = 0;  // o3dr_test_fail_at: the numbered step of the next o3dr_merge_partitioned fails on this rank
     int64_t xchg_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // o3dr_merge_partitioned_stats
-    // o3dr_nearest_neighbors / o3dr_icp_align: staged host clouds, the target grid's cell boxes + box, the per-call source
-    // arrays (indices of this and the previous pass, d2, the moment partials and their folded record).  nn_t also holds the
-    // staged cloud of MLS, plane segmentation and meshing, nn_cells the grid boxes of MLS.
+    // o3dr_nearest_neighbors / o3dr_icp_align: staged host clouds, the per-call source arrays (indices of this and the previous
+    // pass, d2, the moment partials and their folded record).  nn_t also holds the staged cloud of MLS, clustering, plane
+    // segmentation and meshing.  nn_cells: the part of a SearchGrid that is not in ws_grid_block, the cells' exact boxes and
+    // the cloud's box (search_grid_build, for every operator that searches one cloud's grid).
     DevBuf nn_q, nn_t, nn_cells, nn_src;
     // Scratch of the operators after that (MLS, plane, mesh, match, keypoints, rigid fit, the image-stack operators), shared:
     // nothing in it outlives a call, and within one call every block is laid out by one carve().  OP_IN: staged host inputs
@@ -329,32 +330,49 @@ static int ws_ensure(o3dr_ctx* c, int frames, int64_t cap, bool need_pts, bool g
     return O3DR_OK;
 }
 
-// buffers of the statistical outlier removal for `frames` clouds of at most `cap` points (allocated on first use: the
-// measured configs run without it)
+// the search grids of `frames` clouds of at most `cap` points (ws.grid_*), for SOR and for the operators that search one
+// cloud's grid (search_grid_build).  sor_cell_z is SOR's but lives here: it is strided by grid_max_cells + 1 like
+// grid_cell_first, and in SOR's block it would have to be carved again whenever the grid grows.
+static int grid_ensure(o3dr_ctx* c, int frames, int64_t cap)
+{
+    if (cap < 1) cap = 1;
+    if (frames < 1) frames = 1;
+    if (cap > c->ws_grid_cap || frames > c->ws_grid_frames) {
+        const int64_t C = cap > c->ws_grid_cap ? cap : c->ws_grid_cap;
+        const size_t F = (size_t)(frames > c->ws_grid_frames ? frames : c->ws_grid_frames);
+        const uint32_t max_cells = search_grid_max_cells(C);
+        Workspace& w = c->ws;
+        CHK(carve(c, c->ws_grid_block, [&](Carve& k) {
+            k.take(w.grid_xyz, F * (size_t)C);
+            k.take(w.grid_cell_first, F * ((size_t)max_cells + 1));
+            k.take(w.sor_cell_z, F * ((size_t)max_cells + 1));
+            k.take(w.grid_geom, F);
+        }));
+        w.grid_max_cells = max_cells;
+        c->ws_grid_cap = C;
+        c->ws_grid_frames = (int)F;
+    }
+    return O3DR_OK;
+}
+// ... and the arrays of the statistical outlier removal itself (allocated on first use: the measured configs run without
+// it, and the map operators that only search a grid never pay for them)
 static int sor_ensure(o3dr_ctx* c, int frames, int64_t cap)
 {
+    CHK(grid_ensure(c, frames, cap));
     if (cap < 1) cap = 1;
     if (frames < 1) frames = 1;
     if (cap > c->ws_sor_cap || frames > c->ws_sor_frames) {
         const int64_t C = cap > c->ws_sor_cap ? cap : c->ws_sor_cap;
         const size_t F = (size_t)(frames > c->ws_sor_frames ? frames : c->ws_sor_frames);
-        uint32_t max_cells = (uint32_t)(C / 2 > 1024 ? C / 2 : 1024);
-        if (max_cells > (1u << 22)) max_cells = 1u << 22;
         Workspace& w = c->ws;
         CHK(carve(c, c->ws_sor_block, [&](Carve& k) {
-            k.take(w.sor_xyz, F * (size_t)C);
             k.take(w.sor_pts, F * (size_t)C);
             k.take(w.sor_dist, F * (size_t)C);
-            k.take(w.sor_cell_first, F * ((size_t)max_cells + 1));
-            k.take(w.sor_cell_z, F * ((size_t)max_cells + 1));
             k.take(w.sor_partial, F * 256 * 2);
-            k.take(w.sor_geom, F);
             k.take(w.sor_n, F);
             k.take(w.sor_left, F * (size_t)C);
             k.take(w.sor_left_cnt, F);
         }));
-        w.sor_max_cells = max_cells;
-        w.sor_cap = C;
         c->ws_sor_cap = C;
         c->ws_sor_frames = (int)F;
     }
@@ -477,9 +495,9 @@ extern "C" int o3dr_ctx_destroy(o3dr_ctx* c)
     if (!c) return O3DR_OK;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    for (DevBuf* b : {&c->ws_block, &c->ws_pts_block, &c->ws_sor_block, &c->st_disp, &c->st_bgr, &c->st_in, &c->st_out, &c->st_kp,
-                      &c->st_kpoff, &c->st_poses, &c->st_xchg, &c->st_merge, &c->st_gather, &c->bil_tab, &c->st_blur, &c->st_blur_in,
-                      &c->st_hist})
+    for (DevBuf* b : {&c->ws_block, &c->ws_pts_block, &c->ws_grid_block, &c->ws_sor_block, &c->st_disp, &c->st_bgr, &c->st_in, &c->st_out,
+                      &c->st_kp, &c->st_kpoff, &c->st_poses, &c->st_xchg, &c->st_merge, &c->st_gather, &c->bil_tab, &c->st_blur,
+                      &c->st_blur_in, &c->st_hist})
         dev_release(*b);
     if (c->xchg_host) (void)hipHostFree(c->xchg_host);
     if (c->cloud_big) (void)hipFree(c->cloud_big);
@@ -2937,11 +2955,11 @@ extern "C" int o3dr_test_fill_scratch(o3dr_ctx* c, int32_t byte, int64_t* bytes_
     if (byte < 0 || byte > 255 || !bytes_filled) return fail(O3DR_ERR_INVALID_ARG, "byte must be 0..255, bytes_filled not NULL");
     c->place_ub = -1;  // a pending (slice, tile) table lives in the workspace
     int64_t total = 0;
-    std::vector<DevBuf*> blocks = {&c->ws_block, &c->ws_pts_block, &c->ws_sor_block, &c->st_disp, &c->st_bgr, &c->st_in, &c->st_out,
-                                   &c->st_kp, &c->st_kpoff, &c->st_poses, &c->st_blur, &c->st_blur_in, &c->st_hist, &c->st_xchg,
-                                   &c->st_merge, &c->st_gather, &c->nn_q, &c->nn_t, &c->nn_cells, &c->nn_src, &c->inc.scratch,
-                                   &c->inc.tg, &c->inc.tmatch, &c->inc.flag, &c->inc.src, &c->inc.keep, &c->inc.partial,
-                                   &c->inc.words, &c->inc.fb};
+    std::vector<DevBuf*> blocks = {&c->ws_block, &c->ws_pts_block, &c->ws_grid_block, &c->ws_sor_block, &c->st_disp, &c->st_bgr,
+                                   &c->st_in, &c->st_out, &c->st_kp, &c->st_kpoff, &c->st_poses, &c->st_blur, &c->st_blur_in,
+                                   &c->st_hist, &c->st_xchg, &c->st_merge, &c->st_gather, &c->nn_q, &c->nn_t, &c->nn_cells,
+                                   &c->nn_src, &c->inc.scratch, &c->inc.tg, &c->inc.tmatch, &c->inc.flag, &c->inc.src,
+                                   &c->inc.keep, &c->inc.partial, &c->inc.words, &c->inc.fb};
     for (int i = 0; i < 2; ++i) {
         blocks.push_back(&c->st2_disp[i]);
         blocks.push_back(&c->st2_bgr[i]);
@@ -2971,24 +2989,30 @@ extern "C" void o3dr_icp_default_params(o3dr_icp_params* p)
     p->transformation_epsilon = 0.0;
 }
 
-// the target's search grid, built once per call: grid in ws.sor_* (which the SOR path rebuilds whenever it runs), the
-// cells' boxes and the target's box in c->nn_cells.  The sort workspace is reused: the exchange's pending slice table is gone.
-static int nn_target(o3dr_ctx* c, const o3dr_point* target, int64_t n, int mem, float** box6, float4** cell_lo, float4** cell_hi)
+// One cloud's search grid, built once per call: the grid in ws.grid_* (which the SOR path rebuilds whenever it runs: *grid
+// is good for this call only), the cells' boxes and the cloud's box in c->nn_cells.  The sort workspace is reused: the
+// exchange's pending slice table is gone.  mm_used >= 0: the cloud's min/max slots are in ws.mm [0, mm_used) and
+// ws.n_valid[0] is set already (by a caller whose ws_ensure had the arguments of the one here); < 0: taken here.
+static int search_grid_build(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, int mem, int mm_used, SearchGrid* grid)
 {
     c->place_ub = -1;
     const void* t_d;
-    CHK(stage_in(c, c->nn_t, target, (size_t)n * sizeof(o3dr_point), mem, &t_d));
+    CHK(stage_in(c, c->nn_t, cloud, (size_t)n * sizeof(o3dr_point), mem, &t_d));
     CHK(ws_ensure(c, 1, n, false));
-    CHK(sor_ensure(c, 1, n));
-    const size_t cells = (size_t)c->ws.sor_max_cells + 1;
+    CHK(grid_ensure(c, 1, n));
+    const size_t cells = (size_t)c->ws.grid_max_cells + 1;
+    float* box6;
+    float4 *cell_lo, *cell_hi;
     CHK(carve(c, c->nn_cells, [&](Carve& w) {
-        w.take(*cell_lo, cells);
-        w.take(*cell_hi, cells);
-        w.take(*box6, 6);
+        w.take(cell_lo, cells);
+        w.take(cell_hi, cells);
+        w.take(box6, 6);
     }));
-    launch_set_counts(&c->prof, c->stream, c->ws.n_valid, (uint32_t)n, 1);
-    const int used = launch_points_minmax(&c->prof, c->stream, (const o3dr_point*)t_d, 0, c->ws.n_valid, 1, n, c->ws.mm_stride, c->ws.mm);
-    launch_nn_grid(&c->prof, c->stream, c->ws, (const o3dr_point*)t_d, n, used, *box6, *cell_lo, *cell_hi);
+    if (mm_used < 0) {
+        launch_set_counts(&c->prof, c->stream, c->ws.n_valid, (uint32_t)n, 1);
+        mm_used = launch_points_minmax(&c->prof, c->stream, (const o3dr_point*)t_d, 0, c->ws.n_valid, 1, n, c->ws.mm_stride, c->ws.mm);
+    }
+    *grid = launch_nn_grid(&c->prof, c->stream, c->ws, (const o3dr_point*)t_d, n, mm_used, box6, cell_lo, cell_hi);
     HIPCHK(hipGetLastError());
     return O3DR_OK;
 }
@@ -3114,13 +3138,12 @@ extern "C" int o3dr_nearest_neighbors(o3dr_ctx* c, const o3dr_point* query, int6
         HIPCHK(hipMemsetD32Async((hipDeviceptr_t)idx_d, (int)0xFFFFFFFFu, (size_t)n_query, c->stream));
         HIPCHK(hipMemsetD32Async((hipDeviceptr_t)d2_d, (int)0x7f800000u, (size_t)n_query, c->stream));
     } else {
-        float *box6;
-        float4 *lo, *hi;
-        CHK(nn_target(c, target, n_target, mem, &box6, &lo, &hi));
+        SearchGrid grid;
+        CHK(search_grid_build(c, target, n_target, mem, -1, &grid));
         const void* q_d;
         CHK(stage_in(c, c->nn_q, query, (size_t)n_query * sizeof(o3dr_point), mem, &q_d));
-        launch_nn_query(&c->prof, c->stream, c->ws, (const o3dr_point*)q_d, n_query, nullptr, box6, lo, hi, r2, idx_d, d2_d, nullptr,
-                        nullptr, nullptr, nullptr);
+        launch_nn_query(&c->prof, c->stream, grid, (const o3dr_point*)q_d, n_query, nullptr, r2, idx_d, d2_d, nullptr, nullptr, nullptr,
+                        nullptr);
         HIPCHK(hipGetLastError());
     }
     CHK(outs.copy_back(c));
@@ -3233,15 +3256,14 @@ extern "C" int o3dr_icp_align(o3dr_ctx* c, const o3dr_point* source, int64_t n_s
     res->reason = O3DR_ICP_TOO_FEW;
     if (n_source == 0 || n_target == 0) return O3DR_OK;
 
-    float *box6;
-    float4 *lo, *hi;
-    CHK(nn_target(c, target, n_target, mem, &box6, &lo, &hi));
+    SearchGrid grid;
+    CHK(search_grid_build(c, target, n_target, mem, -1, &grid));
     const void* s_d;
     CHK(stage_in(c, c->nn_q, source, (size_t)n_source * sizeof(o3dr_point), mem, &s_d));
     NnSrc o;
     CHK(nn_source(c, n_source, &o));
     float box_h[6];
-    HIPCHK(hipMemcpyAsync(box_h, box6, sizeof box_h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(box_h, grid.box6, sizeof box_h, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     const double c0[3] = {((double)box_h[0] + (double)box_h[3]) * 0.5, ((double)box_h[1] + (double)box_h[4]) * 0.5,
                           ((double)box_h[2] + (double)box_h[5]) * 0.5};
@@ -3252,7 +3274,7 @@ extern "C" int o3dr_icp_align(o3dr_ctx* c, const o3dr_point* source, int64_t n_s
     auto pass = [&](bool compare) -> int {
         float Tf[12];
         for (int k = 0; k < 12; ++k) Tf[k] = (float)T[k];
-        launch_nn_query(&c->prof, c->stream, c->ws, (const o3dr_point*)s_d, n_source, Tf, box6, lo, hi, r2, o.idx[cur], nullptr,
+        launch_nn_query(&c->prof, c->stream, grid, (const o3dr_point*)s_d, n_source, Tf, r2, o.idx[cur], nullptr,
                         compare ? o.idx[cur ^ 1] : nullptr, c0, o.partial, o.rec);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(rec, o.rec, sizeof rec, hipMemcpyDeviceToHost, c->stream));
@@ -3348,11 +3370,10 @@ extern "C" int o3dr_mls_smooth(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, 
     const int staged = cloud_stage_finite(c, cloud, n, mem, &f->bad, &bad, 4, &cloud_d, nothing_else);
     if (bad && mem == O3DR_MEM_HOST && out == cloud) memset(out, 0, (size_t)n * sizeof(o3dr_point));
     CHK(staged);
-    float* box6;
-    float4 *lo, *hi;
-    CHK(nn_target(c, cloud_d, n, O3DR_MEM_DEVICE, &box6, &lo, &hi));
+    SearchGrid grid;
+    CHK(search_grid_build(c, cloud_d, n, O3DR_MEM_DEVICE, -1, &grid));
     CHK(outs.stage(c));
-    launch_mls(&c->prof, c->stream, c->ws, cloud_d, n, box6, lo, hi, r, p->polynomial_order, h, outs.dev(out), outs.dev(normals),
+    launch_mls(&c->prof, c->stream, grid, cloud_d, n, r, p->polynomial_order, h, outs.dev(out), outs.dev(normals),
                outs.dev(nn_count), outs.dev(fit), f->counters);
     HIPCHK(hipGetLastError());
     unsigned long long cnt_h[4];
@@ -3972,19 +3993,21 @@ static int cluster_euclidean(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, co
     const o3dr_point* cloud_d = nullptr;
     ClusterHead h;
     memset(&h, 0, sizeof h);
+    int used = 0;
     CHK(cloud_stage_finite(c, cloud, n, mem, &f->bad, &h.bad, sizeof h, &cloud_d, [&]() -> int {
         CHK(ws_ensure(c, 1, n, false));  // the cloud's box, before any grid work
         launch_set_counts(&c->prof, c->stream, c->ws.n_valid, (uint32_t)n, 1);
-        const int used = launch_points_minmax(&c->prof, c->stream, cloud_d, 0, c->ws.n_valid, 1, n, c->ws.mm_stride, c->ws.mm);
+        used = launch_points_minmax(&c->prof, c->stream, cloud_d, 0, c->ws.n_valid, 1, n, c->ws.mm_stride, c->ws.mm);
         launch_bbox(&c->prof, c->stream, c->ws.mm, used, f->box6);
         return O3DR_OK;
     }));
     for (int k = 0; k < 3; ++k)
         if (!((double)h.box6[3 + k] - (double)h.box6[k] < 32768.0))
             return fail(O3DR_ERR_INVALID_ARG, "a side of the cloud's bounding box is 32768 m or more");
-    float* box6;
-    float4 *lo, *hi;
-    CHK(nn_target(c, cloud_d, n, O3DR_MEM_DEVICE, &box6, &lo, &hi));
+    // The grid is built from the min/max slots and the count taken above: ws_ensure(c, 1, n, false) in front of them has the
+    // arguments of the one inside the build, so ws_block is not carved again in between, and nothing else has run in it.
+    SearchGrid grid;
+    CHK(search_grid_build(c, cloud_d, n, O3DR_MEM_DEVICE, used, &grid));
     ClusterArgs a;
     memset(&a, 0, sizeof a);
     CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
@@ -3995,10 +4018,9 @@ static int cluster_euclidean(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, co
         w.take(a.part, (size_t)cluster_blocks(n) * kPartWords);
     }));
     a.n = (uint32_t)n;
-    a.sxyz = c->ws.sor_xyz, a.cell_first = c->ws.sor_cell_first, a.cell_lo = lo, a.cell_hi = hi, a.sg = c->ws.sor_geom, a.box6 = box6;
+    a.grid = grid;
     a.r2 = r2;
-    const double pad = tol * (1.0 + 1e-5);
-    a.pad_r = (float)(pad > 1e-18 ? pad : 1e-18);
+    a.pad_r = grid_pad_radius(tol);
     a.min_size = p->min_size, a.max_size = p->max_size;
     a.counters = f->counters, a.n_pairs = &f->n_pairs;
     launch_cluster_link(&c->prof, c->stream, c->ws, a);

@@ -89,6 +89,29 @@ struct SorGeom {
     uint32_t n, active;
     double threshold;
 };
+// ---- the XY search grid of one cloud, as a kernel sees it (by value).  launch_nn_grid builds and returns it; SOR's own
+// search kernels read the same arrays of a batch of clouds through Workspace::grid_*. ----
+struct SearchGrid {
+    const SorGeom* geom;         // the plan (n == 0 or inactive: no points)
+    const float4* xyz;           // points in cell order, .w = original index bits
+    const uint32_t* cell_first;  // cells + 1: exclusive scan of the populations
+    const float4* cell_lo;       // exact box of every cell's points (k_nn_cell_box)
+    const float4* cell_hi;
+    const float* box6;           // the cloud's box, min xyz then max xyz
+};
+// the grid never has more cells than points / 2 (at least 1024, at most 2^22): it is only a search structure, and the cell
+// ids of clouds of at most `cap` points then need few sort passes
+inline uint32_t search_grid_max_cells(int64_t cap)
+{
+    const int64_t cells = cap / 2 > 1024 ? cap / 2 : 1024;
+    return (uint32_t)(cells < (1 << 22) ? cells : (1 << 22));
+}
+// half the side of the box whose cells a radius walk visits (grid_radius_walk, kernels/util.inc): max(r (1 + 1e-5), 1e-18)
+inline float grid_pad_radius(double r)
+{
+    const double pad = r * (1.0 + 1e-5);
+    return (float)(pad > 1e-18 ? pad : 1e-18);
+}
 
 // disparity-byte table of the rectified-stereo fast path: alpha = 1./(Q[14]*d + Q[15]), z = float(t2*alpha + 0)
 struct QLutEntry {
@@ -138,19 +161,20 @@ struct Workspace {
                                    // indices, written by the last scatter pass instead of the sorted indices (k_radix_scatter_lane
                                    // -> k_run_heads packs them); nullptr: the indices are written and k_run_heads compares them
     uint32_t* scan_partial = nullptr;  // chunk sums of the multi-workgroup scan
-    // statistical outlier removal (sor_frames clouds of at most sor_cap points)
-    SorGeom* sor_geom = nullptr;        // frames
-    float4* sor_xyz = nullptr;          // frames*cap      coordinates in cell order
+    // the search grids of `frames` clouds (grid_ensure; SearchGrid above is one cloud's, with its cells' boxes)
+    SorGeom* grid_geom = nullptr;        // frames
+    float4* grid_xyz = nullptr;          // frames*cap      coordinates in cell order
+    uint32_t* grid_cell_first = nullptr; // frames*(grid_max_cells+1): points in cells below c (exclusive scan of the populations)
+    float2* sor_cell_z = nullptr;        // frames*(grid_max_cells+1): z range of every cell's points (SOR's handed-over queries;
+                                         // carved with the grid, whose cell stride it shares)
+    uint32_t grid_max_cells = 0;
+    // statistical outlier removal (sor_ensure)
     float* sor_dist = nullptr;          // frames*cap      mean neighbour distance per point
-    uint32_t* sor_cell_first = nullptr; // frames*(sor_max_cells+1): points in cells below c (exclusive scan of the populations)
-    float2* sor_cell_z = nullptr;       // frames*(sor_max_cells+1): z range of every cell's points (for the handed-over queries)
-    uint32_t sor_max_cells = 0;
     double* sor_partial = nullptr;      // frames*256*2
     o3dr_point* sor_pts = nullptr;      // frames*cap      inliers
     uint32_t* sor_n = nullptr;          // frames          inlier count
     uint32_t* sor_left = nullptr;       // frames*cap      queries (cell-sorted index) left to k_sor_knn_left
     uint32_t* sor_left_cnt = nullptr;   // frames
-    int64_t sor_cap = 0;                // points per frame the arrays above are laid out for
     uint32_t* keep_idx = nullptr;  // frames*cap  (only when min_points > 1)
     uint32_t* run_start = nullptr; // frames*(cap+1)  first point of every group run (grouped path), + sentinel
     uint32_t* grp_cnt = nullptr;   // grp_slots/64 + 2: output voxels per group -> exclusive prefix (grouped path, frames == 1)
@@ -299,28 +323,28 @@ int launch_sor(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_point* in,
                int frames, int64_t cap, int mm_used, double stddev_mul, o3dr_point* out, int64_t out_fstride,
                uint32_t* n_out_dev);
 // the search grid of `frames` clouds (plan with ~cell_points points per column, active above active_above points, cell ids,
-// radix sort, populations -> ws.sor_cell_first, points in cell order with their original index in .w -> ws.sor_xyz);
+// radix sort, populations -> ws.grid_cell_first, points in cell order with their original index in .w -> ws.grid_xyz);
 // bounding boxes in ws.mm slots [0, mm_used) of every frame.  Part of launch_sor; the nearest-neighbour target grid too.
 void launch_search_grid(Workspace& ws, hipStream_t s, const o3dr_point* in, int64_t in_fstride, const uint32_t* n_dev, int frames,
                         int64_t cap, int mm_used, double cell_points, uint32_t active_above);
 // exact nearest neighbour (kernels/nn.inc).  launch_nn_grid: the target's grid (n points, also in ws.n_valid[0]; bounding-box
-// slots ws.mm [0, mm_used)) in ws.sor_*, its box -> box6 (device, 6 floats), the cells' boxes -> cell_lo / cell_hi
-// (ws.sor_max_cells + 1 each).  launch_nn_query: idx (+ d2) of n queries (T12 != nullptr: each query is A2(T12, point) first);
+// slots ws.mm [0, mm_used)) in ws.grid_*, its box -> box6 (device, 6 floats), the cells' boxes -> cell_lo / cell_hi
+// (ws.grid_max_cells + 1 each); returns the view of it that the kernels below search, good until the next grid is built in
+// ws.  launch_nn_query: idx (+ d2) of n queries (T12 != nullptr: each query is A2(T12, point) first);
 // partial != nullptr: the ICP epilogue (changed against idx_prev, moments about c0) and its fold into rec[kIcpRecord]
 constexpr int kIcpRecord = 18;  // count, sum a (3), sum b (3), sum a b^T (9, row-major), sum d2, changed queries
-void launch_nn_grid(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_point* target, int64_t n, int mm_used, float* box6,
-                    float4* cell_lo, float4* cell_hi);
-void launch_nn_query(Profiler* pf, hipStream_t s, const Workspace& ws, const o3dr_point* query, int64_t n, const float* T12,
-                     const float* box6, const float4* cell_lo, const float4* cell_hi, float r2, uint32_t* idx_out, float* d2_out,
-                     const uint32_t* idx_prev, const double c0[3], double* partial, double* rec);
+SearchGrid launch_nn_grid(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_point* target, int64_t n, int mm_used, float* box6,
+                          float4* cell_lo, float4* cell_hi);
+void launch_nn_query(Profiler* pf, hipStream_t s, const SearchGrid& grid, const o3dr_point* query, int64_t n, const float* T12,
+                     float r2, uint32_t* idx_out, float* d2_out, const uint32_t* idx_prev, const double c0[3], double* partial,
+                     double* rec);
 inline int64_t nn_partial_blocks(int64_t n) { return (n + 255) / 256; }  // workgroups of launch_nn_query (kNnThreads queries each)
 // launch_cloud_finite: flag[0] = 1 if a coordinate of the n points is not finite.
-// moving least squares (kernels/mls.inc).  launch_mls: o3dr_mls_smooth over the grid launch_nn_grid built for `cloud` (box6, cell_lo / cell_hi its outputs);
+// moving least squares (kernels/mls.inc).  launch_mls: o3dr_mls_smooth over the grid launch_nn_grid built for `cloud`;
 // counters (device, 4 x u64): n_none, n_plane, n_poly, max neighbours
 void launch_cloud_finite(Profiler* pf, hipStream_t s, const o3dr_point* in, int64_t n, uint32_t* flag);
-void launch_mls(Profiler* pf, hipStream_t s, const Workspace& ws, const o3dr_point* cloud, int64_t n, const float* box6,
-                const float4* cell_lo, const float4* cell_hi, double r, int order, double h, o3dr_point* out, float* normals,
-                uint32_t* nn_count, uint8_t* fit, unsigned long long* counters);
+void launch_mls(Profiler* pf, hipStream_t s, const SearchGrid& grid, const o3dr_point* cloud, int64_t n, double r, int order,
+                double h, o3dr_point* out, float* normals, uint32_t* nn_count, uint8_t* fit, unsigned long long* counters);
 // feature matching (kernels/match.inc)
 struct MatchPair {      // one (query set, train set) pair of a call; rows relative to the pool
     uint32_t qbase, nq, tbase, nt;
@@ -606,18 +630,13 @@ inline int64_t ground_parts(const GroundArgs& a)
 // launch_ground: the minimum surface, the iterations (enqueued back to back: nothing is read back), the DTM with its fill,
 // the point pass; every count folded into a.counters
 void launch_ground(Profiler* pf, hipStream_t s, const GroundArgs& a);
-// Euclidean clustering (kernels/cluster.inc; contract: include/o3dr_objects.h).  The grid is launch_nn_grid's (ws.sor_*, the
-// cells' boxes, the cloud's box); every array below is the call's own scratch but the outputs.
+// Euclidean clustering (kernels/cluster.inc; contract: include/o3dr_objects.h).  The grid is launch_nn_grid's; every array
+// below it is the call's own scratch but the outputs.
 struct ClusterArgs {
     uint32_t n;
-    const float4* sxyz;           // the cloud in cell order, .w = original index bits
-    const uint32_t* cell_first;
-    const float4* cell_lo;
-    const float4* cell_hi;
-    const SorGeom* sg;
-    const float* box6;            // the cloud's bounding box (min xyz, max xyz)
+    SearchGrid grid;              // the cloud's
     float r2;                     // (float)(tolerance * tolerance)
-    float pad_r;                  // max(tolerance (1 + 1e-5), 1e-18): half the side of a point's box
+    float pad_r;                  // grid_pad_radius(tolerance): half the side of a point's box
     int32_t min_size, max_size;
     int* parent;                  // n, by original index: the union-find, then every point's final root (raw)
     uint32_t* cnt;                // n: the size of the component at its root

@@ -141,21 +141,21 @@ void launch_sor_small(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_poi
                       double stddev_mul, o3dr_point* out, uint32_t* n_out_dev)
 {
     ProfScope ps(pf, O3DR_K_OTHER, s);
-    const int64_t cell_stride = (int64_t)ws.sor_max_cells + 1;
-    uint32_t max_cells = (uint32_t)(cap / 2 > 1024 ? cap / 2 : 1024);  // (as launch_sor: the grid is only a search structure)
-    if (max_cells > ws.sor_max_cells) max_cells = ws.sor_max_cells;
-    k_sor_small_prep<<<1, kSmallThreads, 0, s>>>(in, n_dev, max_cells, ws.sor_geom, ws.geom, ws.vals[0], ws.sor_cell_first, ws.sor_xyz,
+    const int64_t cell_stride = (int64_t)ws.grid_max_cells + 1;
+    uint32_t max_cells = search_grid_max_cells(cap);
+    if (max_cells > ws.grid_max_cells) max_cells = ws.grid_max_cells;
+    k_sor_small_prep<<<1, kSmallThreads, 0, s>>>(in, n_dev, max_cells, ws.grid_geom, ws.geom, ws.vals[0], ws.grid_cell_first, ws.grid_xyz,
                                                  ws.sor_left_cnt);
-    k_sor_knn<<<dim3(cdiv64(cap, kWave), 1), kWave, 0, s>>>(ws.sor_xyz, ws.vals[0], ws.vals[1], ws.geom, ws.sor_cell_first, cell_stride,
-                                                           ws.sor_geom, cap, ws.sor_dist, ws.sor_left, ws.sor_left_cnt);
+    k_sor_knn<<<dim3(cdiv64(cap, kWave), 1), kWave, 0, s>>>(ws.grid_xyz, ws.vals[0], ws.vals[1], ws.geom, ws.grid_cell_first, cell_stride,
+                                                           ws.grid_geom, cap, ws.sor_dist, ws.sor_left, ws.sor_left_cnt);
     int lg = cdiv64(cap, kWave * kSorLeftWaves);
     if (lg > 1024) lg = 1024;
     int zg = cdiv64((int64_t)max_cells, 256);
     if (zg > 256) zg = 256;
-    k_sor_cell_z<<<dim3(zg, 1), 256, 0, s>>>(ws.sor_xyz, ws.sor_cell_first, cell_stride, ws.sor_geom, cap, ws.sor_left_cnt, ws.sor_cell_z);
-    k_sor_knn_left<<<dim3(lg, 1), kSorLeftWaves * kWave, 0, s>>>(ws.sor_xyz, ws.vals[0], ws.vals[1], ws.geom, ws.sor_cell_first, cell_stride,
-                                                                ws.sor_geom, cap, ws.sor_dist, ws.sor_left, ws.sor_left_cnt, ws.sor_cell_z);
-    k_sor_small_tail<<<1, kSmallThreads, 0, s>>>(in, ws.sor_dist, ws.sor_geom, stddev_mul, out, n_out_dev);
+    k_sor_cell_z<<<dim3(zg, 1), 256, 0, s>>>(ws.grid_xyz, ws.grid_cell_first, cell_stride, ws.grid_geom, cap, ws.sor_left_cnt, ws.sor_cell_z);
+    k_sor_knn_left<<<dim3(lg, 1), kSorLeftWaves * kWave, 0, s>>>(ws.grid_xyz, ws.vals[0], ws.vals[1], ws.geom, ws.grid_cell_first, cell_stride,
+                                                                ws.grid_geom, cap, ws.sor_dist, ws.sor_left, ws.sor_left_cnt, ws.sor_cell_z);
+    k_sor_small_tail<<<1, kSmallThreads, 0, s>>>(in, ws.sor_dist, ws.grid_geom, stddev_mul, out, n_out_dev);
 }
 
 void launch_small_voxel(Profiler* pf, hipStream_t s, const o3dr_point* in, const uint32_t* n_in_dev, uint32_t n_in,
@@ -947,26 +947,26 @@ void launch_search_grid(Workspace& ws, hipStream_t s, const o3dr_point* in, int6
                         int64_t cap, int mm_used, double cell_points, uint32_t active_above)
 {
     const int F = frames;
-    const int64_t cell_stride = (int64_t)ws.sor_max_cells + 1;
-    // The search grid never has more cells than points / 2 (and at least 1024): the cell ids of clouds of at most `cap`
-    // points need ceil(log2(max_cells) / 7) sort passes, and only those are launched (a --jump_pixels 15 frame: 2 instead of
-    // 5 launch groups that find nothing to do).  The grid is a search structure: the neighbours found do not depend on it.
-    uint32_t max_cells = (uint32_t)(cap / 2 > 1024 ? cap / 2 : 1024);
-    if (max_cells > ws.sor_max_cells) max_cells = ws.sor_max_cells;
+    const int64_t cell_stride = (int64_t)ws.grid_max_cells + 1;
+    // The cell ids of clouds of at most `cap` points need ceil(log2(max_cells) / 7) sort passes, and only those are launched
+    // (a --jump_pixels 15 frame: 2 instead of 5 launch groups that find nothing to do).  The grid is a search structure: the
+    // neighbours found do not depend on it.
+    uint32_t max_cells = search_grid_max_cells(cap);
+    if (max_cells > ws.grid_max_cells) max_cells = ws.grid_max_cells;
     int cell_bits = 1;
     while ((1u << cell_bits) < max_cells) ++cell_bits;
     const int sort_passes = (cell_bits + kMaxRadixBits - 1) / kMaxRadixBits;
-    k_sor_plan<<<F, 256, 0, s>>>(ws.mm, ws.mm_stride, mm_used, n_dev, max_cells, ws.sor_geom, ws.geom, cell_points, active_above);
-    (void)hipMemsetAsync(ws.sor_cell_first, 0, (size_t)F * (size_t)cell_stride * 4, s);
-    k_sor_cells<<<dim3(cdiv64(cap, 256), F), 256, 0, s>>>(in, in_fstride, ws.sor_geom, cap, ws.keys[0]);
+    k_sor_plan<<<F, 256, 0, s>>>(ws.mm, ws.mm_stride, mm_used, n_dev, max_cells, ws.grid_geom, ws.geom, cell_points, active_above);
+    (void)hipMemsetAsync(ws.grid_cell_first, 0, (size_t)F * (size_t)cell_stride * 4, s);
+    k_sor_cells<<<dim3(cdiv64(cap, 256), F), 256, 0, s>>>(in, in_fstride, ws.grid_geom, cap, ws.keys[0]);
     launch_radix_passes(ws, s, cap, sort_passes, F);
-    k_sor_cell_counts<<<dim3(cdiv64(cap, 256), F), 256, 0, s>>>(ws.keys[0], ws.keys[1], ws.geom, ws.sor_geom, cap, cell_stride, ws.sor_cell_first);
-    launch_scan(s, ws.sor_cell_first, cell_stride, cell_stride, F, nullptr, nullptr, ws.scan_partial);
-    k_sor_gather<<<dim3(cdiv64(cap, 256), F), 256, 0, s>>>(in, in_fstride, ws.vals[0], ws.vals[1], ws.sor_geom, ws.geom, cap, ws.sor_xyz);
+    k_sor_cell_counts<<<dim3(cdiv64(cap, 256), F), 256, 0, s>>>(ws.keys[0], ws.keys[1], ws.geom, ws.grid_geom, cap, cell_stride, ws.grid_cell_first);
+    launch_scan(s, ws.grid_cell_first, cell_stride, cell_stride, F, nullptr, nullptr, ws.scan_partial);
+    k_sor_gather<<<dim3(cdiv64(cap, 256), F), 256, 0, s>>>(in, in_fstride, ws.vals[0], ws.vals[1], ws.grid_geom, ws.geom, cap, ws.grid_xyz);
 }
 
-// Statistical outlier removal of a batch of clouds (see o3dr_device.h).  ws.sor_* are laid out for ws.sor_cap points
-// per frame; cap (<= ws.sor_cap) sizes the grids.
+// Statistical outlier removal of a batch of clouds (see o3dr_device.h).  cap, at most what ws.grid_* and ws.sor_* were
+// carved for, sizes the grids and is the arrays' frame stride.
 int launch_sor(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_point* in, int64_t in_fstride, const uint32_t* n_dev,
                int frames, int64_t cap, int mm_used, double stddev_mul, o3dr_point* out, int64_t out_fstride,
                uint32_t* n_out_dev)
@@ -974,45 +974,47 @@ int launch_sor(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_point* in,
     ProfScope ps(pf, O3DR_K_OTHER, s);
     const int F = frames;
     const int n_tiles = cdiv64(cap, 1024);
-    const int64_t cell_stride = (int64_t)ws.sor_max_cells + 1;
+    const int64_t cell_stride = (int64_t)ws.grid_max_cells + 1;
     launch_search_grid(ws, s, in, in_fstride, n_dev, F, cap, mm_used, kSorCellPoints, (uint32_t)kSorMeanK);
     (void)hipMemsetAsync(ws.sor_left_cnt, 0, (size_t)F * 4, s);
-    k_sor_knn<<<dim3(cdiv64(cap, kWave), F), kWave, 0, s>>>(ws.sor_xyz, ws.vals[0], ws.vals[1], ws.geom, ws.sor_cell_first, cell_stride,
-                                                           ws.sor_geom, cap, ws.sor_dist, ws.sor_left, ws.sor_left_cnt);
+    k_sor_knn<<<dim3(cdiv64(cap, kWave), F), kWave, 0, s>>>(ws.grid_xyz, ws.vals[0], ws.vals[1], ws.geom, ws.grid_cell_first, cell_stride,
+                                                           ws.grid_geom, cap, ws.sor_dist, ws.sor_left, ws.sor_left_cnt);
     {   // the queries the wave-shared search handed over (a looping grid: their number is only known on the device)
         int lg = cdiv64(cap, kWave * kSorLeftWaves);
         if (lg > 1024) lg = 1024;
-        int zg = cdiv64((int64_t)ws.sor_max_cells, 256);
+        int zg = cdiv64((int64_t)ws.grid_max_cells, 256);
         if (zg > 256) zg = 256;
-        k_sor_cell_z<<<dim3(zg, F), 256, 0, s>>>(ws.sor_xyz, ws.sor_cell_first, cell_stride, ws.sor_geom, cap, ws.sor_left_cnt, ws.sor_cell_z);
-        k_sor_knn_left<<<dim3(lg, F), kSorLeftWaves * kWave, 0, s>>>(ws.sor_xyz, ws.vals[0], ws.vals[1], ws.geom, ws.sor_cell_first, cell_stride,
-                                                                    ws.sor_geom, cap, ws.sor_dist, ws.sor_left, ws.sor_left_cnt, ws.sor_cell_z);
+        k_sor_cell_z<<<dim3(zg, F), 256, 0, s>>>(ws.grid_xyz, ws.grid_cell_first, cell_stride, ws.grid_geom, cap, ws.sor_left_cnt, ws.sor_cell_z);
+        k_sor_knn_left<<<dim3(lg, F), kSorLeftWaves * kWave, 0, s>>>(ws.grid_xyz, ws.vals[0], ws.vals[1], ws.geom, ws.grid_cell_first, cell_stride,
+                                                                    ws.grid_geom, cap, ws.sor_dist, ws.sor_left, ws.sor_left_cnt, ws.sor_cell_z);
     }
-    k_sor_partial<<<dim3(kSorStatBlocks, F), 256, 0, s>>>(ws.sor_dist, cap, ws.sor_geom, ws.sor_partial);
-    k_sor_threshold<<<cdiv64(F, 64), 64, 0, s>>>(ws.sor_partial, stddev_mul, ws.sor_geom, F);
-    k_sor_count<<<dim3(n_tiles, F), 256, 0, s>>>(ws.sor_dist, cap, ws.sor_geom, n_tiles, ws.tile_cnt);
+    k_sor_partial<<<dim3(kSorStatBlocks, F), 256, 0, s>>>(ws.sor_dist, cap, ws.grid_geom, ws.sor_partial);
+    k_sor_threshold<<<cdiv64(F, 64), 64, 0, s>>>(ws.sor_partial, stddev_mul, ws.grid_geom, F);
+    k_sor_count<<<dim3(n_tiles, F), 256, 0, s>>>(ws.sor_dist, cap, ws.grid_geom, n_tiles, ws.tile_cnt);
     launch_scan(s, ws.tile_cnt, n_tiles, n_tiles, F, n_out_dev, nullptr, ws.scan_partial);
-    k_sor_emit<<<dim3(n_tiles, F), 256, 0, s>>>(in, in_fstride, ws.sor_dist, cap, ws.sor_geom, n_tiles, ws.tile_cnt, out, out_fstride,
+    k_sor_emit<<<dim3(n_tiles, F), 256, 0, s>>>(in, in_fstride, ws.sor_dist, cap, ws.grid_geom, n_tiles, ws.tile_cnt, out, out_fstride,
                                                 ws.mm_stride, ws.mm);
     return n_tiles;
 }
 
-// Nearest neighbour (kernels/nn.inc).  launch_nn_grid: the target's search grid in ws.sor_* (its n points counted in
-// ws.n_valid[0], its bounding-box slots in ws.mm [0, mm_used)), the folded box -> box6 and the cells' exact boxes.
-void launch_nn_grid(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_point* target, int64_t n, int mm_used, float* box6,
-                    float4* cell_lo, float4* cell_hi)
+// Nearest neighbour (kernels/nn.inc).  launch_nn_grid: the target's search grid in ws.grid_* (its n points counted in
+// ws.n_valid[0], its bounding-box slots in ws.mm [0, mm_used)), the folded box -> box6 and the cells' exact boxes.  The
+// one place that knows where the members of a SearchGrid live.
+SearchGrid launch_nn_grid(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_point* target, int64_t n, int mm_used, float* box6,
+                          float4* cell_lo, float4* cell_hi)
 {
     ProfScope ps(pf, O3DR_K_OTHER, s);
     k_bbox_fold<<<1, 256, 0, s>>>(ws.mm, mm_used, box6);
     launch_search_grid(ws, s, target, 0, ws.n_valid, 1, n, mm_used, kNnCellPoints, 0u);
-    int cg = cdiv64((int64_t)ws.sor_max_cells, 256);
+    int cg = cdiv64((int64_t)ws.grid_max_cells, 256);
     if (cg > 4096) cg = 4096;
-    k_nn_cell_box<<<cg, 256, 0, s>>>(ws.sor_xyz, ws.sor_cell_first, ws.sor_geom, cell_lo, cell_hi);
+    k_nn_cell_box<<<cg, 256, 0, s>>>(ws.grid_xyz, ws.grid_cell_first, ws.grid_geom, cell_lo, cell_hi);
+    return SearchGrid{ws.grid_geom, ws.grid_xyz, ws.grid_cell_first, cell_lo, cell_hi, box6};
 }
 
-void launch_nn_query(Profiler* pf, hipStream_t s, const Workspace& ws, const o3dr_point* query, int64_t n, const float* T12,
-                     const float* box6, const float4* cell_lo, const float4* cell_hi, float r2, uint32_t* idx_out, float* d2_out,
-                     const uint32_t* idx_prev, const double c0[3], double* partial, double* rec)
+void launch_nn_query(Profiler* pf, hipStream_t s, const SearchGrid& grid, const o3dr_point* query, int64_t n, const float* T12,
+                     float r2, uint32_t* idx_out, float* d2_out, const uint32_t* idx_prev, const double c0[3], double* partial,
+                     double* rec)
 {
     if (n <= 0) return;
     ProfScope ps(pf, O3DR_K_OTHER, s);
@@ -1022,12 +1024,7 @@ void launch_nn_query(Profiler* pf, hipStream_t s, const Workspace& ws, const o3d
     a.n = (uint32_t)n;
     a.xf = T12 ? 1 : 0;
     for (int k = 0; k < 12; ++k) a.T.m[k] = T12 ? T12[k] : 0.f;
-    a.txyz = ws.sor_xyz;
-    a.cell_first = ws.sor_cell_first;
-    a.cell_lo = cell_lo;
-    a.cell_hi = cell_hi;
-    a.sg = ws.sor_geom;
-    a.box6 = box6;
+    a.grid = grid;
     a.r2 = r2;
     a.idx_out = idx_out;
     a.d2_out = d2_out;
@@ -1049,10 +1046,9 @@ void launch_cloud_finite(Profiler* pf, hipStream_t s, const o3dr_point* in, int6
     k_cloud_finite<<<g, 256, 0, s>>>(in, n, flag);
 }
 
-// Moving least squares (kernels/mls.inc) over the grid launch_nn_grid left in ws.sor_*
-void launch_mls(Profiler* pf, hipStream_t s, const Workspace& ws, const o3dr_point* cloud, int64_t n, const float* box6,
-                const float4* cell_lo, const float4* cell_hi, double r, int order, double h, o3dr_point* out, float* normals,
-                uint32_t* nn_count, uint8_t* fit, unsigned long long* counters)
+// Moving least squares (kernels/mls.inc) over the grid launch_nn_grid built for `cloud`
+void launch_mls(Profiler* pf, hipStream_t s, const SearchGrid& grid, const o3dr_point* cloud, int64_t n, double r, int order,
+                double h, o3dr_point* out, float* normals, uint32_t* nn_count, uint8_t* fit, unsigned long long* counters)
 {
     ProfScope ps(pf, O3DR_K_OTHER, s);
     (void)hipMemsetAsync(counters, 0, 4 * sizeof(unsigned long long), s);
@@ -1061,17 +1057,11 @@ void launch_mls(Profiler* pf, hipStream_t s, const Workspace& ws, const o3dr_poi
     memset(&a, 0, sizeof a);
     a.cloud = cloud;
     a.n = (uint32_t)n;
-    a.sxyz = ws.sor_xyz;
-    a.cell_first = ws.sor_cell_first;
-    a.cell_lo = cell_lo;
-    a.cell_hi = cell_hi;
-    a.sg = ws.sor_geom;
-    a.box6 = box6;
+    a.grid = grid;
     a.r2 = (float)(r * r);
     a.r = r;
     a.inv_h = 1.0 / h;
-    const double pad = r * (1.0 + 1e-5);
-    a.pad_r = (float)(pad > 1e-18 ? pad : 1e-18);
+    a.pad_r = grid_pad_radius(r);
     a.out = out;
     a.normals = normals;
     a.nn_count = nn_count;
