@@ -1549,7 +1549,10 @@ int  o3dr_pose_graph_refine(o3dr_ctx* ctx, const uint8_t* desc, const int64_t* o
 #define O3DR_K_CLUSTER_LINK    37  /* Euclidean clustering (o3dr_objects.h): the radius walk with its union-find */
 #define O3DR_K_CLUSTER_NUMBER  38  /* ... flatten, sizes, flags, the two scans */
 #define O3DR_K_CLUSTER_RECORDS 39  /* ... point outputs, boxes, centroid sums, records, indices */
-#define O3DR_K_NUM          40
+#define O3DR_K_INTERP_PULL   40  /* raster interpolation (o3dr_dem.h): the tiled pull launches and the one-workgroup top of the pyramid */
+#define O3DR_K_INTERP_PUSH   41  /* ... the tiled push launches with their sweeps, the outputs, the counters' fold */
+#define O3DR_K_RASTER_SAMPLE 42  /* raster sample (o3dr_dem.h): the pass over the points */
+#define O3DR_K_NUM          43
 /* Bracket every launch of kernel `kernel_id` (or all kernels if -1) with HIP events on the
  * context's stream; 0 launches are bracketed when disabled (the default). */
 int o3dr_profile_enable(o3dr_ctx* ctx, int32_t kernel_id, int32_t enable);

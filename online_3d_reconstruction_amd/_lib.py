@@ -27,12 +27,16 @@ K_SEG_ASSIGN, K_SEG_LABEL = 30, 31
 K_MULTIVIEW = 32
 K_GROUND_WINNER, K_GROUND_ITER, K_GROUND_FILL, K_GROUND_POINTS = 33, 34, 35, 36
 K_CLUSTER_LINK, K_CLUSTER_NUMBER, K_CLUSTER_RECORDS = 37, 38, 39
+K_INTERP_PULL, K_INTERP_PUSH, K_RASTER_SAMPLE = 40, 41, 42
 KERNEL_NAMES = ["reproject_count", "reproject_emit", "voxel_keys", "radix_hist", "radix_scatter", "run_segments",
                 "centroid", "other", "centroid_runs", "plane_disp_sums", "plane_disp_fit", "plane_disp_eval",
                 "orb_pyramid", "orb_fast", "orb_candidates", "orb_select", "orb_describe", "match", "pose_chain", "ransac",
                 "graph_moments", "graph_solve", "stereo_census", "stereo_paths", "stereo_winner", "disp_median", "disp_label",
                 "disp_speckle", "rectify_maps", "rectify_remap", "seg_assign", "seg_label", "multiview", "ground_winner", "ground_iter",
                 "ground_fill", "ground_points", "cluster_link", "cluster_number", "cluster_records"]
+# the ids of include/o3dr_dem.h's operators, from K_INTERP_PULL on: a list of their own, KERNEL_NAMES stays the 40 ids that
+# the benchmark and the clustering test enumerate
+DEM_KERNEL_NAMES = ["interp_pull", "interp_push", "raster_sample"]
 
 
 class O3drError(RuntimeError):
@@ -136,6 +140,23 @@ class GroundResultStruct(C.Structure):
 
 O3DR_GROUND_MAX_WINDOW_RADIUS = 128
 O3DR_GROUND_MAX_ITERATIONS = 16
+
+
+# include/o3dr_dem.h
+class InterpolateParamsStruct(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("smooth", C.c_int32), ("max_level", C.c_int32)]
+
+
+class InterpolateOutputsStruct(C.Structure):
+    _fields_ = [("filled", C.c_void_p), ("level", C.c_void_p)]
+
+
+class InterpolateResultStruct(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("n_levels", C.c_int32), ("reserved", C.c_int32),
+                ("n_data", C.c_int64), ("n_filled", C.c_int64), ("n_empty", C.c_int64), ("n_by_level", C.c_int64 * 32)]
+
+
+INTERPOLATE_MAX_SMOOTH, INTERPOLATE_MAX_LEVELS = 8, 32
 
 
 # include/o3dr_objects.h
@@ -389,6 +410,10 @@ SYMBOLS = [
     ("o3dr_ground_schedule", C.c_int, [C.POINTER(GroundParamsStruct), _vp, _vp, C.POINTER(_i32)]),
     ("o3dr_ground_filter", C.c_int, [_vp, _vp, _i64, C.POINTER(GroundParamsStruct), C.POINTER(GroundOutputsStruct),
                                      C.POINTER(GroundResultStruct), _i32]),
+    ("o3dr_interpolate_default_params", None, [C.POINTER(InterpolateParamsStruct)]),
+    ("o3dr_raster_interpolate", C.c_int, [_vp, _vp, C.POINTER(InterpolateParamsStruct), C.POINTER(InterpolateOutputsStruct),
+                                          C.POINTER(InterpolateResultStruct), _i32]),
+    ("o3dr_raster_sample", C.c_int, [_vp, _vp, _i64, C.c_double, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _pi64, _i32]),
     ("o3dr_cluster_default_params", None, [C.POINTER(ClusterParamsStruct)]),
     ("o3dr_cluster_euclidean", C.c_int, [_vp, _vp, _i64, C.POINTER(ClusterParamsStruct), C.POINTER(ClusterOutputsStruct), _vp, _i64,
                                          C.POINTER(_i64), C.POINTER(ClusterResultStruct), _i32]),

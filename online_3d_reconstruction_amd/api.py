@@ -112,6 +112,19 @@ class GroundInfo:
 
 
 @dataclass
+class InterpolateInfo:
+    """o3dr_raster_interpolate's record (include/o3dr_dem.h): the raster's shape, the pyramid's levels, the data cells, the
+    holes that got a value and those left NaN (max_level), and the cells per level (n_by_level has n_levels entries)."""
+    width: int
+    height: int
+    n_levels: int
+    n_data: int
+    n_filled: int
+    n_empty: int
+    n_by_level: tuple
+
+
+@dataclass
 class ClusterInfo:
     """o3dr_cluster_euclidean's counters (include/o3dr_objects.h): the components of the links' closure, those kept as
     clusters and those rejected as too small / too large, the points in clusters and in rejected components, the size of
@@ -1468,15 +1481,20 @@ class Context:
     # -- ground filter: ground mask, DTM, height above ground (this build's own) -----------------
     def groundFilter(self, pts, cell_size, bounds=None, max_window_radius=16, window_base=2, exponential=True, slope=0.7,
                      initial_distance=0.15, max_distance=10.0, fill_radius=0, return_height=False, return_dtm=False,
-                     return_state=False, return_info=False):
+                     return_state=False, return_info=False, interpolate=False, smooth=2):
         """The bare-earth ground mask of a cloud by a progressive morphological filter on the XY cells of cell_size
         (contract: include/o3dr_terrain.h "ground filter", DESIGN.md "Ground filter").  bounds = (cx0, cy0, width, height)
         in cells, None: the cloud's own box (rasterExtent).  The windows grow to max_window_radius cells (1..128) by
         window_base, exponentially or linearly; slope, initial_distance and max_distance give every window's height
-        threshold; fill_radius (0..32 cells) fills the DTM under what was removed.  numpy POINT arrays give numpy arrays,
-        torch [N,4] 4-byte CUDA tensors such as finalize(device=...) give CUDA tensors.
+        threshold; fill_radius (0..32 cells) fills the DTM under what was removed.  interpolate=True (fill_radius must be
+        0) interpolates the DTM from the ground cells instead, at any distance (interpolateRaster with `smooth`), and takes
+        the heights above that DTM (sampleRaster): finite for every point inside the box; the mask and the states do not
+        change.  numpy POINT arrays give numpy arrays, torch [N,4] 4-byte CUDA tensors such as finalize(device=...) give
+        CUDA tensors.
         -> ground uint8 [n][, height_above_ground float32 [n]][, dtm float32 [height, width]][, cell_state uint8
-        [height, width]][, GroundInfo]"""
+        [height, width]][, GroundInfo[, InterpolateInfo with interpolate]]"""
+        if interpolate and int(fill_radius) != 0:
+            raise ValueError("groundFilter(interpolate=True) needs fill_radius = 0: the interpolation is the fill")
         pts, n = self._cloud(pts)
         p_in, mem, _k = _ptr(pts)
         cx0, cy0, W, H = (int(v) for v in (self.rasterExtent(pts, cell_size) if bounds is None else bounds))
@@ -1486,8 +1504,10 @@ class Context:
         shape = (H, W) if ok else (1, 1)
         want = [("ground", np.uint8, (n,))]
         want += [("height_above_ground", np.float32, (n,))] if return_height else []
-        want += [("dtm", np.float32, shape)] if return_dtm else []
+        want += [("dtm", np.float32, shape)] if return_dtm or interpolate else []
         want += [("cell_state", np.uint8, shape)] if return_state else []
+        if interpolate:  # (the heights come from sampleRaster)
+            want = [w for w in want if w[0] != "height_above_ground"]
         outs = L.GroundOutputsStruct()
         arrays = []
         if mem == L.MEM_DEVICE:
@@ -1504,11 +1524,91 @@ class Context:
                 arrays.append(t)
         res = L.GroundResultStruct()
         L.check(self._lib.o3dr_ground_filter(self._h, p_in if n else None, n, C.byref(prm), C.byref(outs), C.byref(res), mem))
+        info = (GroundInfo(int(res.cx0), int(res.cy0), int(res.width), int(res.height), int(res.n_inside), int(res.n_outside),
+                           int(res.n_occupied), int(res.n_ground_cells), int(res.n_ground_points), int(res.n_dtm_filled),
+                           int(res.n_dtm_empty), int(res.n_iterations), tuple(int(v) for v in res.n_removed[:res.n_iterations])),)
+        if interpolate:  # the DTM from the ground cells alone, at any distance; the heights above it
+            got = dict(zip((name for name, _, _ in want), arrays))
+            dtm, dem_info = self.interpolateRaster(got["dtm"], smooth=smooth, return_info=True)
+            above = self.sampleRaster(pts, dtm, cell_size, (cx0, cy0, W, H)) if return_height else None
+            arrays = [got["ground"]] + ([above] if return_height else []) + ([dtm] if return_dtm else [])
+            arrays += [got["cell_state"]] if return_state else []
+            info += (dem_info,)
         ret = tuple(arrays)
         if return_info:
-            ret += (GroundInfo(int(res.cx0), int(res.cy0), int(res.width), int(res.height), int(res.n_inside), int(res.n_outside),
-                               int(res.n_occupied), int(res.n_ground_cells), int(res.n_ground_points), int(res.n_dtm_filled),
-                               int(res.n_dtm_empty), int(res.n_iterations), tuple(int(v) for v in res.n_removed[:res.n_iterations])),)
+            ret += info
+        return ret[0] if len(ret) == 1 else ret
+
+    # -- raster interpolation and raster sample (this build's own) -------------------------------
+    def interpolateRaster(self, raster, smooth=2, max_level=0, return_level=False, return_info=False):
+        """Every hole (NaN) of a float32 [height, width] raster filled from the data around it, at any distance: pull-push
+        over an image pyramid with `smooth` (0..8) Jacobi sweeps per level on the way down (contract: include/o3dr_dem.h
+        "raster interpolation", DESIGN.md "Raster interpolation").  max_level (1..31) leaves the holes whose nearest data
+        lies under a higher pyramid level NaN; 0: no limit.  A numpy array gives numpy arrays, a torch CUDA tensor gives
+        CUDA tensors without leaving HBM.  -> filled float32[, level uint8][, InterpolateInfo]"""
+        if _is_torch(raster):
+            import torch
+            assert raster.dtype == torch.float32 and raster.dim() == 2
+            raster = raster.contiguous()
+        else:
+            raster = np.ascontiguousarray(raster, np.float32)
+            assert raster.ndim == 2
+        H, W = (int(v) for v in raster.shape)
+        p_in, mem, _k = _ptr(raster)
+        prm = L.InterpolateParamsStruct()
+        self._lib.o3dr_interpolate_default_params(C.byref(prm))
+        prm.width, prm.height, prm.smooth, prm.max_level = W, H, int(smooth), int(max_level)
+        if mem == L.MEM_DEVICE:
+            import torch
+            filled = torch.empty((H, W), dtype=torch.float32, device=raster.device)
+            level = torch.empty((H, W), dtype=torch.uint8, device=raster.device) if return_level else None
+            self._order_after_torch()
+        else:
+            filled = np.empty((H, W), np.float32)
+            level = np.empty((H, W), np.uint8) if return_level else None
+        outs = L.InterpolateOutputsStruct(_addr(filled) if W * H else None, _addr(level) if W * H else None)
+        res = L.InterpolateResultStruct()
+        L.check(self._lib.o3dr_raster_interpolate(self._h, p_in if W * H else None, C.byref(prm), C.byref(outs), C.byref(res), mem))
+        ret = (filled,)
+        if return_level:
+            ret += (level,)
+        if return_info:
+            ret += (InterpolateInfo(int(res.width), int(res.height), int(res.n_levels), int(res.n_data), int(res.n_filled),
+                                    int(res.n_empty), tuple(int(v) for v in res.n_by_level[:res.n_levels])),)
+        return ret[0] if len(ret) == 1 else ret
+
+    def sampleRaster(self, pts, raster, cell_size, bounds, return_value=False, return_info=False):
+        """A float32 [height, width] raster read back at every point: bounds = (cx0, cy0, width, height) is the raster's box
+        in cells of cell_size (contract: include/o3dr_dem.h "raster sample").  The points and the raster live in the same
+        memory: numpy POINT array and numpy raster, or torch CUDA tensors.
+        -> height_above float32 [n] (z minus the raster at the point's cell; NaN outside the box or on a NaN cell)[, value
+        float32 [n]][, (points inside the box, outside it, inside it on a NaN cell)]"""
+        pts, n = self._cloud(pts)
+        p_in, mem, _k = _ptr(pts)
+        cx0, cy0, W, H = (int(v) for v in bounds)
+        if _is_torch(pts):
+            import torch
+            assert _is_torch(raster) and raster.dtype == torch.float32 and raster.is_cuda == pts.is_cuda
+            raster = raster.contiguous()
+        else:
+            raster = np.ascontiguousarray(raster, np.float32)
+        assert tuple(raster.shape) == (H, W), "the raster's shape is (height, width) of bounds"
+        if mem == L.MEM_DEVICE:
+            import torch
+            above = torch.empty(n, dtype=torch.float32, device=pts.device)
+            value = torch.empty(n, dtype=torch.float32, device=pts.device) if return_value else None
+            self._order_after_torch()
+        else:
+            above = np.empty(n, np.float32)
+            value = np.empty(n, np.float32) if return_value else None
+        counts = (C.c_int64 * 3)()
+        L.check(self._lib.o3dr_raster_sample(self._h, p_in if n else None, n, float(cell_size), cx0, cy0, W, H, _addr(raster),
+                                             _addr(value) if n else None, _addr(above) if n else None, counts, mem))
+        ret = (above,)
+        if return_value:
+            ret += (value,)
+        if return_info:
+            ret += (tuple(int(v) for v in counts),)
         return ret[0] if len(ret) == 1 else ret
 
     # -- Euclidean clustering: object labels and per-object records (this build's own; SURVEY section 2 row 16) ----------

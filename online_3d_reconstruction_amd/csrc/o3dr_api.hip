@@ -145,7 +145,8 @@ struct o3dr_ctx {
     // of frames' arrays and the per-frame counters; rectification: the staged host map).  OP_LATE: the arrays sized from a
     // count read back mid-call (plane: tile tables; clustering: the clusters' boxes and sums).
     // OP_OUT: the staged outputs of a host call.  OP_FLAGS: the flags / ranges / counters of one operator (MlsFlags,
-    // PlaneFlags, MeshFlags, RasterFlags, ClusterFlags: 256 bytes; GroundFlags: 384).
+    // PlaneFlags, MeshFlags, RasterFlags, ClusterFlags, InterpFlags: 256 bytes; GroundFlags: 384; SampleFlags: 128).
+    // Raster interpolation: OP_IN the staged raster, OP_WORK the partials and the pyramid's levels above 0.
     enum { OP_IN, OP_WORK, OP_LATE, OP_OUT, OP_FLAGS, OP_BUFS };
     DevBuf op[OP_BUFS];
     DevBuf orb_pat;  // o3dr_orb_detect: the steered table
@@ -3942,6 +3943,162 @@ extern "C" int o3dr_ground_filter(o3dr_ctx* c, const o3dr_point* cloud, int64_t 
     const int rc = entered(c, [&] { return ground_filter(c, cloud, n, p, out, outs, res, mem); });
     if (rc != O3DR_OK) {  // host outputs zeroed on error
         if (res) memset(res, 0, sizeof *res);
+        outs.zero();
+    }
+    return rc;
+}
+
+// -------------------------------------------------------------------------------------------------
+// raster interpolation and raster sample (kernels/interpolate.inc; contract: include/o3dr_dem.h; DESIGN.md "Raster
+// interpolation")
+// -------------------------------------------------------------------------------------------------
+extern "C" void o3dr_interpolate_default_params(o3dr_interpolate_params* p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof *p);  // the raster's shape: no usable default
+    p->smooth = 2;
+}
+
+struct InterpFlags {
+    alignas(64) uint32_t counters[kInterpPartWords];  // InterpArgs::counters
+    alignas(64) uint32_t bad;                         // an infinite input value
+};
+struct SampleFlags {
+    alignas(64) CellFlags cell;
+    alignas(64) uint32_t counters[4];  // SampleArgs::counters
+};
+
+// width * height of a raster the outputs can be sized by before anything else is validated: 0 outside the limits
+static int64_t interp_cells(const o3dr_interpolate_params* p)
+{
+    if (!p || p->width < 1 || p->height < 1) return 0;
+    const int64_t cells = (int64_t)p->width * p->height;
+    return cells <= (int64_t)O3DR_RASTER_MAX_CELLS ? cells : 0;
+}
+
+static int raster_interpolate(o3dr_ctx* c, const float* raster, const o3dr_interpolate_params* p, const o3dr_interpolate_outputs* out,
+                              Outputs& outs, o3dr_interpolate_result* res, int32_t mem)
+{
+    if (!p || !raster || !out || !out->filled) return fail(O3DR_ERR_INVALID_ARG, "params / raster / outputs / outputs->filled is NULL");
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    if (p->width < 1 || p->height < 1) return fail(O3DR_ERR_INVALID_ARG, "the raster needs width, height >= 1");
+    if (p->smooth < 0 || p->smooth > O3DR_INTERPOLATE_MAX_SMOOTH) return fail(O3DR_ERR_INVALID_ARG, "smooth must be in 0..8");
+    if (p->max_level < 0 || p->max_level > O3DR_INTERPOLATE_MAX_LEVELS - 1) return fail(O3DR_ERR_INVALID_ARG, "max_level must be in 0..31");
+    const int64_t cells = (int64_t)p->width * p->height;
+    if (cells > (int64_t)O3DR_RASTER_MAX_CELLS) return fail(O3DR_ERR_INVALID_ARG, "the raster holds more than 2^28 cells");
+    c->place_ub = -1;
+    InterpArgs a;
+    memset(&a, 0, sizeof a);
+    a.smooth = p->smooth, a.max_level = p->max_level;
+    a.lv[0].W = p->width, a.lv[0].H = p->height;
+    int64_t upper = 0;  // cells of the levels 1 .. L
+    while (a.lv[a.L].W > 1 || a.lv[a.L].H > 1) {
+        InterpLevel& v = a.lv[a.L + 1];
+        v.W = (a.lv[a.L].W + 1) >> 1, v.H = (a.lv[a.L].H + 1) >> 1;
+        v.off = upper;
+        upper += (int64_t)v.W * v.H;
+        ++a.L;
+    }
+    InterpFlags* f;
+    CHK(op_flags(c, &f));
+    const void* raster_d;
+    CHK(stage_in(c, c->op[o3dr_ctx::OP_IN], raster, (size_t)cells * sizeof(float), mem, &raster_d));
+    a.raster = (const float*)raster_d;
+    CHK(outs.stage(c));
+    CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
+        w.take(a.part, (size_t)interp_blocks(interp_push_tiles(a.lv[0], a.smooth)) * kInterpPartWords);
+        w.take(a.cnt, (size_t)upper);
+        w.take(a.val, (size_t)upper);
+    }));
+    a.counters = f->counters, a.bad = &f->bad;
+    a.filled = outs.dev(out->filled), a.level = outs.dev(out->level);
+    launch_interpolate(&c->prof, c->stream, a);
+    HIPCHK(hipGetLastError());
+    InterpFlags h;
+    HIPCHK(hipMemcpyAsync(&h, f, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    CHK(outs.copy_back(c));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (h.bad) return fail(O3DR_ERR_INVALID_ARG, "the raster has an infinite value (a hole is a NaN)");
+    if (res) {
+        res->width = p->width, res->height = p->height, res->n_levels = a.L + 1;
+        for (int l = 0; l < O3DR_INTERPOLATE_MAX_LEVELS; ++l) res->n_by_level[l] = h.counters[l];
+        res->n_data = h.counters[0];
+        res->n_filled = h.counters[O3DR_INTERPOLATE_MAX_LEVELS], res->n_empty = h.counters[O3DR_INTERPOLATE_MAX_LEVELS + 1];
+    }
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_raster_interpolate(o3dr_ctx* c, const float* raster, const o3dr_interpolate_params* p,
+                                       const o3dr_interpolate_outputs* out, o3dr_interpolate_result* res, int32_t mem)
+{
+    if (res) memset(res, 0, sizeof *res);
+    Outputs outs{mem};
+    if (out) {
+        outs.add(out->filled, interp_cells(p));
+        outs.add(out->level, interp_cells(p));
+    }
+    const int rc = entered(c, [&] { return raster_interpolate(c, raster, p, out, outs, res, mem); });
+    if (rc != O3DR_OK) {  // host outputs zeroed on error
+        if (res) memset(res, 0, sizeof *res);
+        outs.zero();
+    }
+    return rc;
+}
+
+static int raster_sample(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, double cell_size, const int32_t box[4], const float* raster,
+                         float* value, float* height_above, Outputs& outs, int64_t counts[3], int32_t mem)
+{
+    if (!raster) return fail(O3DR_ERR_INVALID_ARG, "raster is NULL");
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    SampleArgs a;
+    memset(&a, 0, sizeof a);
+    RasterArgs& r = a.r;
+    CHK(raster_cell_size(cell_size, &r.inv));
+    if (box[2] < 1 || box[3] < 1) return fail(O3DR_ERR_INVALID_ARG, "the raster's box needs width, height >= 1");
+    if ((int64_t)box[0] + box[2] - 1 > INT32_MAX || (int64_t)box[1] + box[3] - 1 > INT32_MAX)
+        return fail(O3DR_ERR_INVALID_ARG, "the raster's box leaves int32");
+    CHK(nn_check_cloud(n, cloud, kMeshCloudMax));
+    c->place_ub = -1;
+    r.n = (uint32_t)n;
+    r.cx0 = box[0], r.cy0 = box[1], r.width = box[2], r.height = box[3];
+    r.cell_size = cell_size;
+    SampleFlags* f;
+    CHK(op_flags(c, &f));
+    if (n > 0) {
+        CellFlags h;
+        CHK(raster_cloud(c, cloud, n, mem, r, f, &h));
+    }
+    const int64_t cells = (int64_t)box[2] * box[3];
+    if (cells > (int64_t)O3DR_RASTER_MAX_CELLS) return fail(O3DR_ERR_INVALID_ARG, kRasterTooLarge);
+    const void* raster_d;
+    CHK(stage_in(c, c->op[o3dr_ctx::OP_IN], raster, (size_t)cells * sizeof(float), mem, &raster_d));
+    r.height_map = const_cast<float*>((const float*)raster_d);  // (read only)
+    CHK(outs.stage(c));
+    CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) { w.take(r.part, (size_t)std::max<int64_t>(raster_winner_parts(n), 1) * kPartWords); }));
+    a.counters = f->counters;
+    a.value = outs.dev(value), a.hag = outs.dev(height_above);
+    launch_raster_sample(&c->prof, c->stream, a);
+    HIPCHK(hipGetLastError());
+    uint32_t cnt[4];
+    HIPCHK(hipMemcpyAsync(cnt, f->counters, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+    CHK(outs.copy_back(c));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (counts) counts[0] = cnt[0], counts[1] = cnt[1], counts[2] = cnt[2];
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_raster_sample(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, double cell_size, int32_t cx0, int32_t cy0,
+                                  int32_t width, int32_t height, const float* raster, float* value, float* height_above,
+                                  int64_t counts[3], int32_t mem)
+{
+    if (counts) memset(counts, 0, 3 * sizeof(int64_t));
+    Outputs outs{mem};
+    outs.add(value, cloud_points(n, kMeshCloudMax));
+    outs.add(height_above, cloud_points(n, kMeshCloudMax));
+    const int32_t box[4] = {cx0, cy0, width, height};
+    const int rc = entered(c, [&] { return raster_sample(c, cloud, n, cell_size, box, raster, value, height_above, outs, counts, mem); });
+    if (rc != O3DR_OK) {  // host outputs zeroed on error
+        if (counts) memset(counts, 0, 3 * sizeof(int64_t));
         outs.zero();
     }
     return rc;

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/o3dr.h"
+#include "../../include/o3dr_dem.h"
 #include "../../include/o3dr_objects.h"
 #include "../../include/o3dr_terrain.h"
 
@@ -630,6 +631,62 @@ inline int64_t ground_parts(const GroundArgs& a)
 // launch_ground: the minimum surface, the iterations (enqueued back to back: nothing is read back), the DTM with its fill,
 // the point pass; every count folded into a.counters
 void launch_ground(Profiler* pf, hipStream_t s, const GroundArgs& a);
+// raster interpolation (kernels/interpolate.inc; contract: include/o3dr_dem.h "raster interpolation").  Level 0 is the
+// input itself (the NaN test is its count); the levels 1 .. L live one after the other in cnt / val, level l from lv[l].off.
+// val holds m_l after the pull and F_l after the push: the push writes the cells with c_l = 0 only, and nobody reads m_l there.
+struct InterpLevel {
+    int32_t W, H;
+    int64_t off;                  // the level's first cell in cnt / val (level 0: unused)
+};
+struct InterpArgs {
+    const float* raster;          // level 0
+    int32_t L;                    // the top level
+    int32_t smooth, max_level;
+    InterpLevel lv[O3DR_INTERPOLATE_MAX_LEVELS];
+    int32_t* cnt;                 // c_l, l >= 1
+    float* val;                   // m_l, then F_l, l >= 1
+    float* filled;                // width * height
+    uint8_t* level;               // width * height or nullptr
+    uint32_t* part;               // kInterpPartWords words per workgroup of the level-0 push
+    uint32_t* counters;           // kInterpPartWords words: n_by_level[0..31], n_filled, n_empty, - ...
+    uint32_t* bad;                // 1: an infinite input value
+};
+constexpr int kInterpPullTile = 32;       // cells a side of a pull tile: five levels per launch (32 -> 16 -> 8 -> 4 -> 2 -> 1)
+constexpr int kInterpPullLevels = 5;
+constexpr int kInterpRegion = 64;         // cells a side of a push tile with its apron of `smooth` cells; a level that fits
+                                          // in one region is finished by the one-workgroup kernel
+constexpr int kInterpMaxBlocks = 1024;    // workgroups of a tiled launch at most (the other tiles by stride)
+constexpr int kInterpPartWords = 40;
+inline int64_t interp_blocks(int64_t tiles) { return tiles < kInterpMaxBlocks ? tiles : kInterpMaxBlocks; }
+inline int64_t interp_pull_tiles(const InterpLevel& v)
+{
+    return (((int64_t)v.W + kInterpPullTile - 1) / kInterpPullTile) * (((int64_t)v.H + kInterpPullTile - 1) / kInterpPullTile);
+}
+inline int interp_push_tile(int smooth) { return kInterpRegion - 2 * smooth; }
+inline int64_t interp_push_tiles(const InterpLevel& v, int smooth)
+{
+    const int64_t t = interp_push_tile(smooth);
+    return (((int64_t)v.W + t - 1) / t) * (((int64_t)v.H + t - 1) / t);
+}
+// the first level that fits in one region (0 for a raster of at most 64 x 64 cells)
+inline int interp_top_level(const InterpArgs& a)
+{
+    int l = 0;
+    while (a.lv[l].W > kInterpRegion || a.lv[l].H > kInterpRegion) ++l;
+    return l;
+}
+// launch_interpolate: the pulls, the one-workgroup top, the pushes down to level 0 with the outputs; the counters folded
+// into a.counters, a.bad set (it is cleared first)
+void launch_interpolate(Profiler* pf, hipStream_t s, const InterpArgs& a);
+// raster sample (kernels/interpolate.inc; contract: include/o3dr_dem.h "raster sample"): r.cloud, r.n, r.inv, the box,
+// r.part and r.height_map = the raster are read
+struct SampleArgs {
+    RasterArgs r;
+    float* value;                 // n or nullptr
+    float* hag;                   // n or nullptr
+    uint32_t* counters;           // 4 words: inside, outside, on a NaN cell, -
+};
+void launch_raster_sample(Profiler* pf, hipStream_t s, const SampleArgs& a);
 // Euclidean clustering (kernels/cluster.inc; contract: include/o3dr_objects.h).  The grid is launch_nn_grid's; every array
 // below it is the call's own scratch but the outputs.
 struct ClusterArgs {

@@ -35,6 +35,7 @@
 //   mesh         height-field surface mesh over the XY cells
 //   raster       the merged map as images: one point per XY cell, separable hole fill, the output images, shaded relief
 //   ground       bare-earth ground filter on the raster's cells: sliding window minima / maxima, DTM, height above ground
+//   interpolate  hole-free rasters: pull-push over an image pyramid with Jacobi sweeps in LDS on the way down; a raster read at points
 //   cluster      Euclidean clustering: radius walk + union-find, sizes, numbering, per-cluster records, indices
 //   match        Hamming 2-NN descriptor matching, index-aligned 3-D keypoints, the batched rigid fit
 //   orb          ORB features: grey pyramid, FAST score + box sums, candidates, exact selection, steered BRIEF
@@ -72,6 +73,7 @@ namespace o3dr {
 #include "kernels/mesh.inc"
 #include "kernels/raster.inc"
 #include "kernels/ground.inc"
+#include "kernels/interpolate.inc"
 #include "kernels/match.inc"
 #include "kernels/plane_disparity.inc"
 #include "kernels/orb.inc"
@@ -1309,6 +1311,47 @@ void launch_ground(Profiler* pf, hipStream_t s, const GroundArgs& a)
         if (gw > 0) k_ground_points<<<gw, kGroundThreads, 0, s>>>(a);
         k_fold4_u32<<<1, kFoldThreads, 0, s>>>(r.part, gw, 0, 2, 2, 2, 2, a.counters + 12);
     }
+}
+
+// raster interpolation (kernels/interpolate.inc)
+void launch_interpolate(Profiler* pf, hipStream_t s, const InterpArgs& a)
+{
+    const int lt = interp_top_level(a);
+    {
+        ProfScope ps(pf, O3DR_K_INTERP_PULL, s);
+        (void)hipMemsetAsync(a.bad, 0, sizeof(uint32_t), s);
+        int pulled = 0;
+        while (pulled < lt) {  // (level pulled + 1 then has at most 32 x 32 cells)
+            const int nl = a.L - pulled < kInterpPullLevels ? a.L - pulled : kInterpPullLevels;
+            const int64_t tiles = interp_pull_tiles(a.lv[pulled]), tiles_x = ((int64_t)a.lv[pulled].W + kInterpPullTile - 1) / kInterpPullTile;
+            k_interp_pull<<<(unsigned)interp_blocks(tiles), kInterpThreads, 0, s>>>(a, pulled, nl, tiles_x, tiles);
+            pulled += nl;
+        }
+        if (a.L > 0) k_interp_top<<<1, kInterpThreads, 0, s>>>(a, pulled, lt);
+    }
+    {
+        ProfScope ps(pf, O3DR_K_INTERP_PUSH, s);
+        const int64_t t = interp_push_tile(a.smooth);
+        for (int l = (lt > 1 ? lt : 1) - 1; l >= 0; --l) {
+            const int64_t tiles = interp_push_tiles(a.lv[l], a.smooth), tiles_x = ((int64_t)a.lv[l].W + t - 1) / t;
+            const unsigned g = (unsigned)interp_blocks(tiles);
+            if (l > 0) {
+                k_interp_push<false><<<g, kInterpThreads, 0, s>>>(a, l, tiles_x, tiles);
+            } else {
+                k_interp_push<true><<<g, kInterpThreads, 0, s>>>(a, l, tiles_x, tiles);
+                k_interp_fold<<<1, kFoldThreads, 0, s>>>(a.part, (int)g, a.counters);
+            }
+        }
+    }
+}
+
+// raster sample (kernels/interpolate.inc)
+void launch_raster_sample(Profiler* pf, hipStream_t s, const SampleArgs& a)
+{
+    ProfScope ps(pf, O3DR_K_RASTER_SAMPLE, s);
+    const int g = (int)raster_winner_parts(a.r.n);
+    if (g > 0) k_raster_sample<<<g, kInterpThreads, 0, s>>>(a);
+    k_fold4_u32<<<1, kFoldThreads, 0, s>>>(a.r.part, g, 0, 2, 2, 2, 2, a.counters);
 }
 
 // Euclidean clustering (kernels/cluster.inc) over the grid launch_nn_grid left in ws.sor_*

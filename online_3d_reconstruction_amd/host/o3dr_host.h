@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/o3dr.h"
+#include "../../include/o3dr_dem.h"
 #include "../../include/o3dr_objects.h"
 #include "../../include/o3dr_terrain.h"
 
@@ -144,6 +145,8 @@ public:
     bool ground_linear = false;      // --ground_fill_radius r (cells, 0..32); parsed and ignored without --ground_filter
     double ground_slope = 0.7, ground_initial_distance = 0.15, ground_max_distance = 10.0;
     int ground_fill_radius = 0;
+    bool ground_interpolate = false; // --ground_interpolate: the DTM interpolated from the ground cells (o3dr_raster_interpolate),
+    int ground_smooth = 2;           // --ground_smooth n (sweeps per level, 0..8); parsed and ignored without --ground_filter
     bool cluster_cloud = false;      // --cluster_cloud file.ply: o3dr_cluster_euclidean of one PLY -> clusters_ / unclustered_<file>,
     bool cluster_tolerance_set = false;  // clusters_<file>.txt; --cluster_tolerance t (metres, required there),
     double cluster_tolerance = 0.0;  // --cluster_min_size n, --cluster_max_size n; parsed and ignored without --cluster_cloud

@@ -504,6 +504,7 @@ void Pose::printUsage()
             "                     --partitioned_merge, --reference_fanout; elsewhere the --ortho_* flags are parsed and ignored)\n"
             "./pose --ground_filter file.ply [--voxel_size m] [--ground_max_window r] [--ground_window_base b] [--ground_linear]\n"
             "       [--ground_slope s] [--ground_initial_distance m] [--ground_max_distance m] [--ground_fill_radius r]\n"
+            "       [--ground_interpolate] [--ground_smooth n]\n"
             "                     (bare-earth ground filter on the XY cells of size m: the minimum surface is opened with windows\n"
             "                     growing to r cells (1..128, default 16) by powers of b (default 2) or, with --ground_linear, by\n"
             "                     steps of b, and a cell rising above the opening by more than s (default 0.7) times the window's\n"
@@ -513,6 +514,10 @@ void Pose::printUsage()
             "                     up, 0 = no data, else 1 + (z - z_min) / step; cells that are not ground take the nearest ground\n"
             "                     cell within --ground_fill_radius cells, 0..32, default 0) next to the source; prints the box, the\n"
             "                     schedule, the removed cells per iteration, the ground cells and points and the call time;\n"
+            "                     with --ground_interpolate (and --ground_fill_radius 0) the terrain model is interpolated from the\n"
+            "                     ground cells at any distance instead, pull-push over an image pyramid with n (0..8, default 2)\n"
+            "                     smoothing sweeps per level: the picture has no 0 pixel, and the data cells, the filled cells and\n"
+            "                     the pyramid's levels are printed;\n"
             "                     elsewhere the --ground_* flags are parsed and ignored - the flags and the file names are this\n"
             "                     build's own)\n"
             "./pose --cluster_cloud file.ply --cluster_tolerance t [--cluster_min_size n] [--cluster_max_size n]\n"
@@ -636,6 +641,8 @@ int Pose::parseCmdArgs(int argc, char** argv)
         else if (a == "--ground_initial_distance") ground_initial_distance = atof(need(i));
         else if (a == "--ground_max_distance") ground_max_distance = atof(need(i));
         else if (a == "--ground_fill_radius") ground_fill_radius = atoi(need(i));
+        else if (a == "--ground_interpolate") ground_interpolate = true;
+        else if (a == "--ground_smooth") ground_smooth = atoi(need(i));
         else if (a == "--cluster_cloud") { files(i, "file.ply", read_PLY_filename0); cluster_cloud = true; }
         else if (a == "--cluster_tolerance") { cluster_tolerance = atof(need(i)); cluster_tolerance_set = true; }
         else if (a == "--cluster_min_size") cluster_min_size = atoi(need(i));
@@ -794,6 +801,8 @@ int Pose::parseCmdArgs(int argc, char** argv)
             throw runtime_error("--ground_initial_distance must be finite and >= 0");
         if (!(isfinite(ground_max_distance) && ground_max_distance >= 0.0)) throw runtime_error("--ground_max_distance must be finite and >= 0");
         if (ground_fill_radius < 0 || ground_fill_radius > O3DR_RASTER_MAX_FILL_RADIUS) throw runtime_error("--ground_fill_radius must be in 0..32");
+        if (ground_interpolate && ground_fill_radius != 0) throw runtime_error("--ground_interpolate needs --ground_fill_radius 0 (the interpolation is the fill)");
+        if (ground_interpolate && (ground_smooth < 0 || ground_smooth > O3DR_INTERPOLATE_MAX_SMOOTH)) throw runtime_error("--ground_smooth must be in 0..8");
     }
     if (cluster_cloud) {
         if (!ifstream(read_PLY_filename0)) throw runtime_error("could not read " + read_PLY_filename0);
@@ -1084,6 +1093,16 @@ void Pose::run_ground_filter()
     o3dr_ground_outputs out = {ground.data(), nullptr, dtm.data(), nullptr};
     o3dr_ground_result res;
     chk(o3dr_ground_filter(c, cloud->points.data(), n, &prm, &out, &res, O3DR_MEM_HOST), "o3dr_ground_filter");
+    o3dr_interpolate_result dem;
+    if (ground_interpolate) {  // the DTM from the ground cells alone, at any distance
+        o3dr_interpolate_params ip;
+        o3dr_interpolate_default_params(&ip);
+        ip.width = W, ip.height = H, ip.smooth = ground_smooth;
+        vector<float> filled(cells);
+        o3dr_interpolate_outputs io = {filled.data(), nullptr};
+        chk(o3dr_raster_interpolate(c, dtm.data(), &ip, &io, &dem, O3DR_MEM_HOST), "o3dr_raster_interpolate");
+        dtm.swap(filled);
+    }
     const double ms = chrono::duration<double, milli>(chrono::steady_clock::now() - t0).count();
     PointCloud::Ptr terrain(new PointCloud()), objects(new PointCloud());
     for (int64_t i = 0; i < n; ++i) (ground[(size_t)i] ? terrain : objects)->points.push_back(cloud->points[(size_t)i]);
@@ -1114,6 +1133,8 @@ void Pose::run_ground_filter()
     cout << "cells occupied " << res.n_occupied << ", ground " << res.n_ground_cells << ", dtm filled " << res.n_dtm_filled << ", dtm empty "
          << res.n_dtm_empty << endl;
     cout << "ground points " << res.n_ground_points << ", object points " << n - res.n_ground_points << endl;
+    if (ground_interpolate)
+        cout << "dtm interpolated: " << dem.n_data << " data cells, " << dem.n_filled << " filled, " << dem.n_levels << " levels" << endl;
     snprintf(line, sizeof line, "dtm z_min %.9g z_max %.9g step %.17g", (double)z_min, (double)z_max, step);
     cout << line << endl;
     snprintf(line, sizeof line, "ground filter time %.3f ms", ms);
