@@ -752,7 +752,7 @@ class Context:
         """Uninitialised outputs of `like`'s memory kind, one per (shape, dtype) and None per None.  dtype: a numpy type - a
         tensor gets the torch type of _TORCH_DTYPE, for uint16 int16 (which holds the bits) - or a torch type as it is.  The
         library call may follow at once: it is ordered behind torch's work."""
-        if not _is_torch(like):
+        if not (_is_torch(like) and like.is_cuda):  # (a torch host tensor is read as host memory: numpy outputs)
             return [None if sp is None else np.empty(*sp) for sp in specs]
         import torch
         outs = [None if sp is None else
@@ -1397,19 +1397,9 @@ class Context:
         res = L.MeshResultStruct()
         n_tris = C.c_int64(0)
         cap = 2 * n
-        if mem == L.MEM_DEVICE:
-            import torch
-            dev = pts.device
-            tri = torch.empty((max(cap, 1), 3), dtype=torch.int32, device=dev)
-            nrm = torch.empty((max(n, 1), 3), dtype=torch.float32, device=dev) if return_normals else None
-            self._order_after_torch()
-            L.check(self._lib.o3dr_mesh_surface(self._h, p_in, n, C.byref(prm), tri.data_ptr(), cap, C.byref(n_tris),
-                                                None if nrm is None else nrm.data_ptr(), C.byref(res), L.MEM_DEVICE))
-        else:
-            tri = np.empty((max(cap, 1), 3), np.int32)
-            nrm = np.empty((n, 3), np.float32) if return_normals else None
-            L.check(self._lib.o3dr_mesh_surface(self._h, p_in, n, C.byref(prm), tri.ctypes.data, cap, C.byref(n_tris),
-                                                None if nrm is None else nrm.ctypes.data, C.byref(res), mem))
+        rows = max(n, 1) if mem == L.MEM_DEVICE else n  # (a tensor is never empty)
+        tri, nrm = self._empty_like(pts, ((max(cap, 1), 3), np.int32), ((rows, 3), np.float32) if return_normals else None)
+        L.check(self._lib.o3dr_mesh_surface(self._h, p_in, n, C.byref(prm), _addr(tri), cap, C.byref(n_tris), _addr(nrm), C.byref(res), mem))
         ret = (tri[:int(n_tris.value)],)
         if return_normals:
             ret += (nrm[:n],)
@@ -1456,19 +1446,9 @@ class Context:
         want += [("source", np.int32, ())] if return_source else []
         want += [("distance2", np.int32, ())] if return_distance else []
         outs = L.RasterOutputsStruct()
-        arrays = []
-        if mem == L.MEM_DEVICE:
-            import torch
-            for name, dt, tail in want:
-                t = torch.empty(shape + tail, dtype=getattr(torch, np.dtype(dt).name), device=pts.device)
-                setattr(outs, name, t.data_ptr())
-                arrays.append(t)
-            self._order_after_torch()
-        else:
-            for name, dt, tail in want:
-                t = np.empty(shape + tail, dt)
-                setattr(outs, name, t.ctypes.data)
-                arrays.append(t)
+        arrays = self._empty_like(pts, *[(shape + tail, dt) for _, dt, tail in want])
+        for (name, _, _), t in zip(want, arrays):
+            setattr(outs, name, _addr(t))
         res = L.RasterResultStruct()
         L.check(self._lib.o3dr_rasterize_map(self._h, p_in if n else None, n, C.byref(prm), C.byref(outs), C.byref(res), mem))
         ret = tuple(arrays)
@@ -1509,19 +1489,9 @@ class Context:
         if interpolate:  # (the heights come from sampleRaster)
             want = [w for w in want if w[0] != "height_above_ground"]
         outs = L.GroundOutputsStruct()
-        arrays = []
-        if mem == L.MEM_DEVICE:
-            import torch
-            for name, dt, shp in want:
-                t = torch.empty(shp, dtype=getattr(torch, np.dtype(dt).name), device=pts.device)
-                setattr(outs, name, t.data_ptr() if t.numel() else None)
-                arrays.append(t)
-            self._order_after_torch()
-        else:
-            for name, dt, shp in want:
-                t = np.empty(shp, dt)
-                setattr(outs, name, t.ctypes.data if t.size else None)
-                arrays.append(t)
+        arrays = self._empty_like(pts, *[(shp, dt) for _, dt, shp in want])
+        for (name, _, shp), t in zip(want, arrays):
+            setattr(outs, name, _addr(t) if 0 not in shp else None)
         res = L.GroundResultStruct()
         L.check(self._lib.o3dr_ground_filter(self._h, p_in if n else None, n, C.byref(prm), C.byref(outs), C.byref(res), mem))
         info = (GroundInfo(int(res.cx0), int(res.cy0), int(res.width), int(res.height), int(res.n_inside), int(res.n_outside),
@@ -1547,8 +1517,7 @@ class Context:
         lies under a higher pyramid level NaN; 0: no limit.  A numpy array gives numpy arrays, a torch CUDA tensor gives
         CUDA tensors without leaving HBM.  -> filled float32[, level uint8][, InterpolateInfo]"""
         if _is_torch(raster):
-            import torch
-            assert raster.dtype == torch.float32 and raster.dim() == 2
+            assert _dtype_name(raster) == "float32" and raster.dim() == 2
             raster = raster.contiguous()
         else:
             raster = np.ascontiguousarray(raster, np.float32)
@@ -1558,14 +1527,7 @@ class Context:
         prm = L.InterpolateParamsStruct()
         self._lib.o3dr_interpolate_default_params(C.byref(prm))
         prm.width, prm.height, prm.smooth, prm.max_level = W, H, int(smooth), int(max_level)
-        if mem == L.MEM_DEVICE:
-            import torch
-            filled = torch.empty((H, W), dtype=torch.float32, device=raster.device)
-            level = torch.empty((H, W), dtype=torch.uint8, device=raster.device) if return_level else None
-            self._order_after_torch()
-        else:
-            filled = np.empty((H, W), np.float32)
-            level = np.empty((H, W), np.uint8) if return_level else None
+        filled, level = self._empty_like(raster, ((H, W), np.float32), ((H, W), np.uint8) if return_level else None)
         outs = L.InterpolateOutputsStruct(_addr(filled) if W * H else None, _addr(level) if W * H else None)
         res = L.InterpolateResultStruct()
         L.check(self._lib.o3dr_raster_interpolate(self._h, p_in if W * H else None, C.byref(prm), C.byref(outs), C.byref(res), mem))
@@ -1587,20 +1549,12 @@ class Context:
         p_in, mem, _k = _ptr(pts)
         cx0, cy0, W, H = (int(v) for v in bounds)
         if _is_torch(pts):
-            import torch
-            assert _is_torch(raster) and raster.dtype == torch.float32 and raster.is_cuda == pts.is_cuda
+            assert _is_torch(raster) and _dtype_name(raster) == "float32" and raster.is_cuda == pts.is_cuda
             raster = raster.contiguous()
         else:
             raster = np.ascontiguousarray(raster, np.float32)
         assert tuple(raster.shape) == (H, W), "the raster's shape is (height, width) of bounds"
-        if mem == L.MEM_DEVICE:
-            import torch
-            above = torch.empty(n, dtype=torch.float32, device=pts.device)
-            value = torch.empty(n, dtype=torch.float32, device=pts.device) if return_value else None
-            self._order_after_torch()
-        else:
-            above = np.empty(n, np.float32)
-            value = np.empty(n, np.float32) if return_value else None
+        above, value = self._empty_like(pts, (n, np.float32), (n, np.float32) if return_value else None)
         counts = (C.c_int64 * 3)()
         L.check(self._lib.o3dr_raster_sample(self._h, p_in if n else None, n, float(cell_size), cx0, cy0, W, H, _addr(raster),
                                              _addr(value) if n else None, _addr(above) if n else None, counts, mem))
@@ -1631,17 +1585,8 @@ class Context:
         cap = n // int(min_size) if return_clusters and int(min_size) >= 1 else 0  # no more clusters fit in n points
         want = ["label"] + [name for name, on in (("raw", return_raw), ("size", return_sizes), ("indices", return_indices)) if on]
         outs = L.ClusterOutputsStruct()
-        arrays = {}
-        if mem == L.MEM_DEVICE:
-            import torch
-            for name in want:
-                arrays[name] = torch.empty(n, dtype=torch.int32, device=pts.device)
-            rec = torch.empty((cap, 64), dtype=torch.uint8, device=pts.device)
-            self._order_after_torch()
-        else:
-            for name in want:
-                arrays[name] = np.empty(n, np.int32)
-            rec = np.empty(cap, L.CLUSTER)
+        rec, *made = self._empty_like(pts, ((cap, 64), np.uint8) if mem == L.MEM_DEVICE else (cap, L.CLUSTER), *[(n, np.int32)] * len(want))
+        arrays = dict(zip(want, made))
         for name in want:
             setattr(outs, name, _addr(arrays[name]) if n else None)
         res, k = L.ClusterResultStruct(), C.c_int64(0)

@@ -5,7 +5,7 @@
 // The dense XY cell order of a cloud (CellOrder in o3dr_device.h; DESIGN.md "Cell order"): what plane segmentation
 // (tiles) and the surface mesh (cells) start with.
 //   A CELL FUNCTOR is the operator's index rule: bool operator()(const float4& p, int32_t& ix, int32_t& iy), false when
-//   an index leaves int32 (PlaneCell in plane.inc, MeshCell in mesh.inc; the arithmetic is part of the ABI contract).
+//   an index leaves int32 (PlaneCell in plane.inc, FloorCell below; the arithmetic is part of the ABI contract).
 //   k_cell_range: the index box, kept order-preserving as int32 ^ 0x80000000, and "an index leaves int32", as
 //   per-workgroup partials folded by one workgroup (k_fold4_u32): no atomics.  The host reads the box back (cell_box in
 //   o3dr_api.hip) and checks that the dense id (iy - y0) * wx + (ix - x0) fits a 32-bit sort key.
@@ -13,8 +13,34 @@
 //   cell (launch_sort_keys, payload = input position); k_cell_heads flags the first point of every cell and the scan of
 //   the flags numbers the cells (ordinals, in cell order; their count is the run count).
 //   What is gathered into that order is the operator's business (k_plane_gather, k_mesh_vertices).
+//   The raster family does not sort: its box is the caller's (RasterFrame in o3dr_device.h; DESIGN.md "Raster frame"), the
+//   range pass only proves that every index fits int32, and frame_cell is the dense id of a point's cell in that box.
 // =================================================================================================
 constexpr int kCellThreads = kFoldThreads;
+
+// the contract's cell index floorf(x * inv) with inv = 1.0f / (float)cell_size, in fp32: the cell functor of the surface
+// mesh, the map raster, the ground filter and the raster sample
+struct FloorCell {
+    float inv;
+    __device__ __forceinline__ bool operator()(const float4& p, int32_t& ix, int32_t& iy) const
+    {
+        const float fx = floorf(p.x * inv), fy = floorf(p.y * inv);
+        if (!(fx >= -2147483648.f && fx < 2147483648.f && fy >= -2147483648.f && fy < 2147483648.f)) return false;
+        ix = (int32_t)fx, iy = (int32_t)fy;
+        return true;
+    }
+};
+static inline FloorCell cell_of(const RasterFrame& f) { return FloorCell{f.inv}; }
+
+// the dense id dy * width + dx of p's cell in the frame's box (64-bit differences: a box may span all of int32), -1 outside
+// the box or off int32
+__device__ __forceinline__ int64_t frame_cell(const RasterFrame& f, const float4& p)
+{
+    int32_t ix, iy;
+    if (!FloorCell{f.inv}(p, ix, iy)) return -1;
+    const int64_t dx = (int64_t)ix - f.cx0, dy = (int64_t)iy - f.cy0;
+    return (dx < 0 || dx >= f.width || dy < 0 || dy >= f.height) ? -1 : dy * f.width + dx;
+}
 
 // per workgroup: words 0..3 the index range (min ix, max ix, min iy, max iy, order-preserving), word 4 "out of int32"
 template <class Cell>

@@ -39,12 +39,12 @@ __device__ __forceinline__ float ground_op(float a, float b)
 // per cell: zl = the z of its word's point (+inf: empty), state = 1 / 0
 __global__ __launch_bounds__(kGroundThreads) void k_ground_init(GroundArgs a)
 {
-    const int64_t cells = (int64_t)a.r.width * a.r.height;
+    const int64_t cells = (int64_t)a.r.f.width * a.r.f.height;
     const int64_t id = (int64_t)blockIdx.x * kGroundThreads + threadIdx.x;
     if (id >= cells) return;
     const unsigned long long w = a.r.win[id];
     const bool occupied = w != kRasterEmpty;
-    a.zl[id] = occupied ? reinterpret_cast<const float4*>(a.r.cloud)[raster_index(w)].z : __builtin_inff();
+    a.zl[id] = occupied ? reinterpret_cast<const float4*>(a.r.f.cloud)[raster_index(w)].z : __builtin_inff();
     a.state[id] = occupied ? 1 : 0;
 }
 
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(kGroundThreads) void k_ground_col_window(GroundArgs
     constexpr bool MAX = FINAL;
     int64_t x, b0, stride;
     ground_col_place(groups_x, x, b0, stride);
-    const int64_t width = a.r.width, height = a.r.height, w = 2 * (int64_t)r + 1;
+    const int64_t width = a.r.f.width, height = a.r.f.height, w = 2 * (int64_t)r + 1;
     uint32_t removed = 0;
     if (x < width) {
         for (int64_t B = b0 - 1; B * w + r < height; B += stride) {
@@ -149,14 +149,14 @@ __global__ __launch_bounds__(kGroundThreads) void k_ground_col_window(GroundArgs
     if (FINAL) {
         uint32_t cnt[4] = {removed, 0u, 0u, 0u};
         const int op[4] = {2, 2, 2, 2};
-        block_reduce4_u32(cnt, op, a.r.part + (int64_t)blockIdx.x * kPartWords);
+        block_reduce4_u32(cnt, op, a.r.f.part + (int64_t)blockIdx.x * kPartWords);
     }
 }
 
 // per cell that is not ground: its word set to empty (the DTM's sources are the ground cells)
 __global__ __launch_bounds__(kGroundThreads) void k_ground_ground_words(GroundArgs a)
 {
-    const int64_t cells = (int64_t)a.r.width * a.r.height;
+    const int64_t cells = (int64_t)a.r.f.width * a.r.f.height;
     const int64_t id = (int64_t)blockIdx.x * kGroundThreads + threadIdx.x;
     if (id < cells && a.state[id] != 1) a.r.win[id] = kRasterEmpty;
 }
@@ -164,18 +164,15 @@ __global__ __launch_bounds__(kGroundThreads) void k_ground_ground_words(GroundAr
 // per point: the mask and the height above the DTM.  Per workgroup: ground points.
 __global__ __launch_bounds__(kGroundThreads) void k_ground_points(GroundArgs a)
 {
-    const MeshCell cell{a.r.inv};
+    const RasterFrame& f = a.r.f;
     const float thr0 = a.thr[0];
     uint32_t n_ground = 0;
-    for (int64_t i = (int64_t)blockIdx.x * kGroundThreads + threadIdx.x; i < (int64_t)a.r.n; i += (int64_t)gridDim.x * kGroundThreads) {
-        const float4 p = reinterpret_cast<const float4*>(a.r.cloud)[i];
-        int32_t ix, iy;
-        int64_t dx = -1, dy = -1;
-        if (cell(p, ix, iy)) dx = (int64_t)ix - a.r.cx0, dy = (int64_t)iy - a.r.cy0;
+    for (int64_t i = (int64_t)blockIdx.x * kGroundThreads + threadIdx.x; i < (int64_t)f.n; i += (int64_t)gridDim.x * kGroundThreads) {
+        const float4 p = reinterpret_cast<const float4*>(f.cloud)[i];
+        const int64_t id = frame_cell(f, p);
         uint8_t g = 0;
         float h = __builtin_nanf("");
-        if (dx >= 0 && dx < a.r.width && dy >= 0 && dy < a.r.height) {
-            const int64_t id = dy * a.r.width + dx;
+        if (id >= 0) {
             const float d = a.r.height_map[id];
             if (d == d) h = p.z - d;  // (a cell without a value: the one NaN of every output, not the subtraction's)
             g = (a.state[id] == 1 && h <= thr0) ? 1 : 0;  // a ground cell's DTM is its Z
@@ -186,5 +183,5 @@ __global__ __launch_bounds__(kGroundThreads) void k_ground_points(GroundArgs a)
     }
     uint32_t v[4] = {n_ground, 0u, 0u, 0u};
     const int op[4] = {2, 2, 2, 2};
-    block_reduce4_u32(v, op, a.r.part + (int64_t)blockIdx.x * kPartWords);
+    block_reduce4_u32(v, op, a.r.f.part + (int64_t)blockIdx.x * kPartWords);
 }

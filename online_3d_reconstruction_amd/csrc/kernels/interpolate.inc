@@ -254,17 +254,14 @@ __global__ __launch_bounds__(kFoldThreads) void k_interp_fold(const uint32_t* __
 // per point: the raster at its cell and the height above it.  Per workgroup: points inside the box, outside, on a NaN cell.
 __global__ __launch_bounds__(kInterpThreads) void k_raster_sample(SampleArgs a)
 {
-    const MeshCell cell{a.r.inv};
     uint32_t inside = 0, outside = 0, on_nan = 0;
-    for (int64_t i = (int64_t)blockIdx.x * kInterpThreads + threadIdx.x; i < (int64_t)a.r.n; i += (int64_t)gridDim.x * kInterpThreads) {
-        const float4 p = reinterpret_cast<const float4*>(a.r.cloud)[i];
-        int32_t ix, iy;
-        int64_t dx = -1, dy = -1;
-        if (cell(p, ix, iy)) dx = (int64_t)ix - a.r.cx0, dy = (int64_t)iy - a.r.cy0;
+    for (int64_t i = (int64_t)blockIdx.x * kInterpThreads + threadIdx.x; i < (int64_t)a.f.n; i += (int64_t)gridDim.x * kInterpThreads) {
+        const float4 p = reinterpret_cast<const float4*>(a.f.cloud)[i];
+        const int64_t id = frame_cell(a.f, p);
         float v = __builtin_nanf(""), h = __builtin_nanf("");
-        if (dx >= 0 && dx < a.r.width && dy >= 0 && dy < a.r.height) {
+        if (id >= 0) {
             ++inside;
-            const float d = a.r.height_map[dy * a.r.width + dx];
+            const float d = a.raster[id];
             if (d == d)
                 v = d, h = p.z - d;  // (a NaN cell: the one NaN of every output, not the cell's own or the subtraction's)
             else
@@ -277,5 +274,5 @@ __global__ __launch_bounds__(kInterpThreads) void k_raster_sample(SampleArgs a)
     }
     uint32_t cnt[4] = {inside, outside, on_nan, 0u};
     const int op[4] = {2, 2, 2, 2};
-    block_reduce4_u32(cnt, op, a.r.part + (int64_t)blockIdx.x * kPartWords);
+    block_reduce4_u32(cnt, op, a.f.part + (int64_t)blockIdx.x * kPartWords);
 }

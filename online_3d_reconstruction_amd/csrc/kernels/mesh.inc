@@ -3,7 +3,7 @@
 
 // =================================================================================================
 // Height-field surface mesh (o3dr_mesh_surface; contract: include/o3dr.h, DESIGN.md "Surface mesh")
-//   Cells: the cloud's cell order (kernels/cell_order.inc) with MeshCell as the index rule: cells in (cy, cx) order, the
+//   Cells: the cloud's cell order (kernels/cell_order.inc) with FloorCell as the index rule: cells in (cy, cx) order, the
 //   lowest input index first inside a cell.  The first point of every cell is its vertex, the cell ordinals are the
 //   vertex ordinals, and k_mesh_vertices gathers them (key = the dense cell id (cy - cy_min) * wx + (cx - cx_min),
 //   x y z + input index).
@@ -87,19 +87,7 @@ __device__ __forceinline__ void mesh_row3(const MeshArgs& a, uint64_t row, uint6
 }
 
 // ---- cells ---------------------------------------------------------------------------------------
-// the contract's cell index floorf(x * inv) with inv = 1.0f / (float)cell_size, in fp32 (the cell functor of
-// kernels/cell_order.inc)
-struct MeshCell {
-    float inv;
-    __device__ __forceinline__ bool operator()(const float4& p, int32_t& ix, int32_t& iy) const
-    {
-        const float fx = floorf(p.x * inv), fy = floorf(p.y * inv);
-        if (!(fx >= -2147483648.f && fx < 2147483648.f && fy >= -2147483648.f && fy < 2147483648.f)) return false;
-        ix = (int32_t)fx, iy = (int32_t)fy;
-        return true;
-    }
-};
-static inline MeshCell cell_of(const MeshArgs& a) { return MeshCell{a.inv}; }
+static inline FloorCell cell_of(const MeshArgs& a) { return FloorCell{a.inv}; }
 
 // the vertices in cell order (the first point of every cell, at its ordinal): key, and x y z with the input index in .w
 __global__ __launch_bounds__(kMeshThreads) void k_mesh_vertices(MeshArgs a)

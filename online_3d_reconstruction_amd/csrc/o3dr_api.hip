@@ -3087,14 +3087,15 @@ struct MeshFlags {
     alignas(64) uint32_t cnt[2];       // V, T
     alignas(64) uint32_t counters[3];  // full quads, rejected by orientation, rejected by length
 };
-struct RasterFlags {
+// the raster family (a RasterFrame's range pass, then the operator's own counters)
+template <int N>
+struct FrameFlags {
     alignas(64) CellFlags cell;
-    alignas(64) uint32_t counters[12];  // RasterArgs::counters
+    alignas(64) uint32_t counters[N];
 };
-struct GroundFlags {
-    alignas(64) CellFlags cell;
-    alignas(64) uint32_t counters[kGroundCounterWords];  // GroundArgs::counters
-};
+using RasterFlags = FrameFlags<12>;                   // RasterArgs::counters
+using GroundFlags = FrameFlags<kGroundCounterWords>;  // GroundArgs::counters
+using SampleFlags = FrameFlags<4>;                    // SampleArgs::counters
 // The index box of a read-back range: its corner and widths -> o, the width of the largest dense cell id -> *nbits.
 // Fails, with the operator's texts, if an index left int32 or the box holds more than `limit` cells.
 static int cell_box(const CellFlags& h, uint64_t limit, const char* off_int32_text, const char* limit_text, CellOrder* o, int* nbits)
@@ -3532,6 +3533,71 @@ extern "C" int o3dr_segment_plane(o3dr_ctx* c, const o3dr_point* cloud, int64_t 
 }
 
 // -------------------------------------------------------------------------------------------------
+// The raster frame's host side (RasterFrame in o3dr_device.h; DESIGN.md "Raster frame"): what the map raster, the ground
+// filter and the raster sample check and stage alike.  Each operator calls these where its contract's error order has them.
+// -------------------------------------------------------------------------------------------------
+// inv = 1.0f / (float)cell_size of the floor rule (the surface mesh's too)
+static int frame_cell_size(double cs, float* inv)
+{
+    const float csf = (float)cs;
+    *inv = 1.0f / csf;
+    if (!(std::isfinite(cs) && cs > 0.0 && std::isfinite(csf) && csf > 0.f && std::isfinite(*inv) && *inv > 0.f))
+        return fail(O3DR_ERR_INVALID_ARG, "cell_size must be finite and > 0 (and usable in fp32)");
+    return O3DR_OK;
+}
+static int box_check(int32_t cx0, int32_t cy0, int32_t width, int32_t height)
+{
+    if (width < 1 || height < 1) return fail(O3DR_ERR_INVALID_ARG, "the raster's box needs width, height >= 1");
+    if ((int64_t)cx0 + width - 1 > INT32_MAX || (int64_t)cy0 + height - 1 > INT32_MAX)
+        return fail(O3DR_ERR_INVALID_ARG, "the raster's box leaves int32");
+    return O3DR_OK;
+}
+// width * height of a box or raster the outputs can be sized by before anything else is validated: 0 outside the limits
+static int64_t box_cells(int32_t width, int32_t height)
+{
+    if (width < 1 || height < 1) return 0;
+    const int64_t cells = (int64_t)width * height;
+    return cells <= (int64_t)O3DR_RASTER_MAX_CELLS ? cells : 0;
+}
+constexpr const char* kRasterTooLarge = "the raster's box holds more than 2^28 cells";
+// the cells of a box that has passed box_check
+static int box_limit(const RasterFrame& f, int64_t* cells)
+{
+    *cells = box_cells(f.width, f.height);
+    return *cells ? O3DR_OK : fail(O3DR_ERR_INVALID_ARG, kRasterTooLarge);
+}
+// The frame of a call filled: the box, and for n > 0 the cloud staged, every coordinate checked for being finite and every
+// cell index for fitting int32 in one synchronisation (dev: the operator's device flags; the cloud's cell range in *h).
+// f->part is the range pass's partials, all of OP_WORK until the operator carves its own.
+static int raster_frame(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, int mem, float inv, const int32_t box[4], CellFlags* dev,
+                        CellFlags* h, RasterFrame* f)
+{
+    f->n = (uint32_t)n, f->inv = inv;
+    f->cx0 = box[0], f->cy0 = box[1], f->width = box[2], f->height = box[3];
+    if (n == 0) return O3DR_OK;
+    CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) { w.take(f->part, (size_t)cell_range_parts(n) * kPartWords); }));
+    CHK(cloud_stage_finite(c, cloud, n, mem, &dev->bad, &h->bad, sizeof *h, &f->cloud, [&]() -> int {
+        launch_cell_range(&c->prof, c->stream, *f, f->part, dev->range);
+        return O3DR_OK;
+    }));
+    if (h->off_int32[0]) return fail(O3DR_ERR_INVALID_ARG, "a cell index does not fit in int32 (cell_size too small)");
+    return O3DR_OK;
+}
+// An entry point of the family: the result (res, res_bytes; may be NULL) cleared, the call under `entered`, and on any
+// error the result cleared again and the host outputs zeroed.
+template <class Impl>
+static int raster_entry(o3dr_ctx* c, const Outputs& outs, void* res, size_t res_bytes, Impl&& impl)
+{
+    if (res) memset(res, 0, res_bytes);
+    const int rc = entered(c, impl);
+    if (rc != O3DR_OK) {
+        if (res) memset(res, 0, res_bytes);
+        outs.zero();
+    }
+    return rc;
+}
+
+// -------------------------------------------------------------------------------------------------
 // height-field surface mesh (kernels/mesh.inc; DESIGN.md "Surface mesh")
 // -------------------------------------------------------------------------------------------------
 extern "C" void o3dr_mesh_default_params(o3dr_mesh_params* p)
@@ -3549,10 +3615,9 @@ static int mesh_surface(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const o
     if (!n_tris) return fail(O3DR_ERR_INVALID_ARG, "n_tris is NULL");
     if (tris_capacity < 0 || (tris_capacity > 0 && !tris)) return fail(O3DR_ERR_INVALID_ARG, "bad tris / tris_capacity");
     if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
-    const double cs = p->cell_size, L = p->max_edge_length;
-    const float csf = (float)cs, inv = 1.0f / csf;
-    if (!(std::isfinite(cs) && cs > 0.0 && std::isfinite(csf) && csf > 0.f && std::isfinite(inv) && inv > 0.f))
-        return fail(O3DR_ERR_INVALID_ARG, "cell_size must be finite and > 0 (and usable in fp32)");
+    const double L = p->max_edge_length;
+    float inv;
+    CHK(frame_cell_size(p->cell_size, &inv));
     if (!(L > 0.0)) return fail(O3DR_ERR_INVALID_ARG, "max_edge_length must be > 0 (+inf: no gate)");
     c->place_ub = -1;
     if (n == 0) return O3DR_OK;
@@ -3638,44 +3703,21 @@ extern "C" void o3dr_raster_default_params(o3dr_raster_params* p)
     p->light[0] = -1.0, p->light[1] = 1.0, p->light[2] = 1.0;
 }
 
-static int raster_cell_size(double cs, float* inv)
-{
-    const float csf = (float)cs;
-    *inv = 1.0f / csf;
-    if (!(std::isfinite(cs) && cs > 0.0 && std::isfinite(csf) && csf > 0.f && std::isfinite(*inv) && *inv > 0.f))
-        return fail(O3DR_ERR_INVALID_ARG, "cell_size must be finite and > 0 (and usable in fp32)");
-    return O3DR_OK;
-}
-// The cloud staged, every coordinate checked for being finite and every cell index for fitting int32: one
-// synchronisation, the cloud's cell range in *h.  The range pass's partials are all of OP_WORK until the box is known.
-template <class Flags>
-static int raster_cloud(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, int mem, RasterArgs& a, Flags* f, CellFlags* h)
-{
-    CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) { w.take(a.part, (size_t)cell_range_parts(n) * kPartWords); }));
-    CHK(cloud_stage_finite(c, cloud, n, mem, &f->cell.bad, &h->bad, sizeof *h, &a.cloud, [&]() -> int {
-        launch_cell_range(&c->prof, c->stream, a, a.part, f->cell.range);
-        return O3DR_OK;
-    }));
-    if (h->off_int32[0]) return fail(O3DR_ERR_INVALID_ARG, "a cell index does not fit in int32 (cell_size too small)");
-    return O3DR_OK;
-}
-constexpr const char* kRasterTooLarge = "the raster's box holds more than 2^28 cells";
-
 static int raster_extent(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, double cell_size, int32_t* box[4], int32_t mem)
 {
     CHK(nn_check_cloud(n, cloud, kMeshCloudMax));
     if (!box[0] || !box[1] || !box[2] || !box[3]) return fail(O3DR_ERR_INVALID_ARG, "cx0 / cy0 / width / height is NULL");
     if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
-    RasterArgs a;
-    memset(&a, 0, sizeof a);
-    CHK(raster_cell_size(cell_size, &a.inv));
+    float inv;
+    CHK(frame_cell_size(cell_size, &inv));
     if (n == 0) return fail(O3DR_ERR_INVALID_ARG, "an empty cloud has no cell box");
     c->place_ub = -1;
-    a.n = (uint32_t)n;
     RasterFlags* f;
     CHK(op_flags(c, &f));
+    const int32_t no_box[4] = {0, 0, 0, 0};  // (the cloud's own box is what is asked for)
+    RasterFrame frame{};
     CellFlags h;
-    CHK(raster_cloud(c, cloud, n, mem, a, f, &h));
+    CHK(raster_frame(c, cloud, n, mem, inv, no_box, &f->cell, &h, &frame));
     CellOrder o;
     int nbits;
     CHK(cell_box(h, (uint64_t)O3DR_RASTER_MAX_CELLS, "", kRasterTooLarge, &o, &nbits));
@@ -3696,14 +3738,6 @@ extern "C" int o3dr_raster_extent(o3dr_ctx* c, const o3dr_point* cloud, int64_t 
     return rc;
 }
 
-// width * height of a box the outputs can be sized by before anything else is validated: 0 for a box outside the limits
-static int64_t raster_cells(const o3dr_raster_params* p)
-{
-    if (!p || p->width < 1 || p->height < 1) return 0;
-    const int64_t cells = (int64_t)p->width * p->height;
-    return cells <= (int64_t)O3DR_RASTER_MAX_CELLS ? cells : 0;
-}
-
 static int rasterize_map(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const o3dr_raster_params* p, const o3dr_raster_outputs* out,
                          Outputs& outs, o3dr_raster_result* res, int32_t mem)
 {
@@ -3712,7 +3746,8 @@ static int rasterize_map(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const 
     if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
     RasterArgs a;
     memset(&a, 0, sizeof a);
-    CHK(raster_cell_size(p->cell_size, &a.inv));
+    float inv;
+    CHK(frame_cell_size(p->cell_size, &inv));
     if (p->select != O3DR_RASTER_FIRST && p->select != O3DR_RASTER_TOP && p->select != O3DR_RASTER_BOTTOM)
         return fail(O3DR_ERR_INVALID_ARG, "select must be O3DR_RASTER_FIRST, _TOP or _BOTTOM");
     if (p->fill_radius < 0 || p->fill_radius > O3DR_RASTER_MAX_FILL_RADIUS) return fail(O3DR_ERR_INVALID_ARG, "fill_radius must be in 0..32");
@@ -3724,28 +3759,23 @@ static int rasterize_map(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const 
     } else if (out && out->shade) {
         return fail(O3DR_ERR_INVALID_ARG, "the shade output needs use_light");
     }
-    if (p->width < 1 || p->height < 1) return fail(O3DR_ERR_INVALID_ARG, "the raster's box needs width, height >= 1");
-    if ((int64_t)p->cx0 + p->width - 1 > INT32_MAX || (int64_t)p->cy0 + p->height - 1 > INT32_MAX)
-        return fail(O3DR_ERR_INVALID_ARG, "the raster's box leaves int32");
+    CHK(box_check(p->cx0, p->cy0, p->width, p->height));
     c->place_ub = -1;
-    a.n = (uint32_t)n;
-    a.cx0 = p->cx0, a.cy0 = p->cy0, a.width = p->width, a.height = p->height;
     a.select = p->select, a.R = p->fill_radius;
     a.cell_size = p->cell_size;
     RasterFlags* f;
     CHK(op_flags(c, &f));
-    if (n > 0) {
-        CellFlags h;
-        CHK(raster_cloud(c, cloud, n, mem, a, f, &h));
-    }
-    const int64_t cells = (int64_t)p->width * p->height;
-    if (cells > (int64_t)O3DR_RASTER_MAX_CELLS) return fail(O3DR_ERR_INVALID_ARG, kRasterTooLarge);
+    const int32_t box[4] = {p->cx0, p->cy0, p->width, p->height};
+    CellFlags h;
+    CHK(raster_frame(c, cloud, n, mem, inv, box, &f->cell, &h, &a.f));
+    int64_t cells;
+    CHK(box_limit(a.f, &cells));
     const int64_t tiles = raster_tiles(p->width, p->height), parts = std::max(tiles, raster_winner_parts(n));
     float* height_tmp = nullptr;  // the shade reads the filled heights: scratch when the caller does not ask for them
     const bool want_shade = p->use_light && out && out->shade;
     CHK(outs.stage(c));
     CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
-        w.take(a.part, (size_t)parts * kPartWords);
+        w.take(a.f.part, (size_t)parts * kPartWords);
         w.take(a.win, (size_t)cells);
         if (a.R > 0) w.take(a.col, (size_t)cells);
         if (want_shade && !out->height_map) w.take(height_tmp, (size_t)cells);
@@ -3783,9 +3813,8 @@ static int rasterize_map(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const 
 extern "C" int o3dr_rasterize_map(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const o3dr_raster_params* p,
                                   const o3dr_raster_outputs* out, o3dr_raster_result* res, int32_t mem)
 {
-    if (res) memset(res, 0, sizeof *res);
     Outputs outs{mem};
-    const int64_t cells = raster_cells(p);
+    const int64_t cells = p ? box_cells(p->width, p->height) : 0;
     if (out) {
         outs.add(out->height_map, cells);
         outs.add(out->color, 3 * cells);
@@ -3793,12 +3822,7 @@ extern "C" int o3dr_rasterize_map(o3dr_ctx* c, const o3dr_point* cloud, int64_t 
         outs.add(out->source, cells);
         outs.add(out->distance2, cells);
     }
-    const int rc = entered(c, [&] { return rasterize_map(c, cloud, n, p, out, outs, res, mem); });
-    if (rc != O3DR_OK) {  // host outputs zeroed on error
-        if (res) memset(res, 0, sizeof *res);
-        outs.zero();
-    }
-    return rc;
+    return raster_entry(c, outs, res, sizeof *res, [&] { return rasterize_map(c, cloud, n, p, out, outs, res, mem); });
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -3816,12 +3840,8 @@ extern "C" void o3dr_ground_default_params(o3dr_ground_params* p)
 // the parameters in the struct's order (whole: with the box and fill_radius), then the schedule of the contract's step 3
 static int ground_schedule(const o3dr_ground_params* p, bool whole, float* inv, int32_t radii[16], float thr[16], int32_t* n_iter)
 {
-    CHK(raster_cell_size(p->cell_size, inv));
-    if (whole) {
-        if (p->width < 1 || p->height < 1) return fail(O3DR_ERR_INVALID_ARG, "the raster's box needs width, height >= 1");
-        if ((int64_t)p->cx0 + p->width - 1 > INT32_MAX || (int64_t)p->cy0 + p->height - 1 > INT32_MAX)
-            return fail(O3DR_ERR_INVALID_ARG, "the raster's box leaves int32");
-    }
+    CHK(frame_cell_size(p->cell_size, inv));
+    if (whole) CHK(box_check(p->cx0, p->cy0, p->width, p->height));
     if (p->max_window_radius < 1 || p->max_window_radius > O3DR_GROUND_MAX_WINDOW_RADIUS)
         return fail(O3DR_ERR_INVALID_ARG, "max_window_radius must be in 1..128");
     if (p->window_base < (p->exponential ? 2 : 1))
@@ -3871,27 +3891,25 @@ static int ground_filter(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const 
     GroundArgs a;
     memset(&a, 0, sizeof a);
     RasterArgs& r = a.r;
-    CHK(ground_schedule(p, true, &r.inv, a.radius, a.thr, &a.n_iter));
+    float inv;
+    CHK(ground_schedule(p, true, &inv, a.radius, a.thr, &a.n_iter));
     CHK(nn_check_cloud(n, cloud, kMeshCloudMax));
     c->place_ub = -1;
-    r.n = (uint32_t)n;
-    r.cx0 = p->cx0, r.cy0 = p->cy0, r.width = p->width, r.height = p->height;
     r.select = O3DR_RASTER_BOTTOM, r.R = p->fill_radius;
     r.cell_size = p->cell_size;
     GroundFlags* f;
     CHK(op_flags(c, &f));
-    if (n > 0) {
-        CellFlags h;
-        CHK(raster_cloud(c, cloud, n, mem, r, f, &h));
-    }
-    const int64_t cells = (int64_t)p->width * p->height;
-    if (cells > (int64_t)O3DR_RASTER_MAX_CELLS) return fail(O3DR_ERR_INVALID_ARG, kRasterTooLarge);
+    const int32_t box[4] = {p->cx0, p->cy0, p->width, p->height};
+    CellFlags h;
+    CHK(raster_frame(c, cloud, n, mem, inv, box, &f->cell, &h, &r.f));
+    int64_t cells;
+    CHK(box_limit(r.f, &cells));
     const int64_t parts = ground_parts(a);
     float* dtm_tmp = nullptr;  // the point pass reads the DTM and the states: scratch when the caller does not ask for them
     uint8_t* state_tmp = nullptr;
     CHK(outs.stage(c));
     CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
-        w.take(r.part, (size_t)parts * kPartWords);
+        w.take(r.f.part, (size_t)parts * kPartWords);
         w.take(r.win, (size_t)cells);
         w.take(a.zl, (size_t)cells);
         w.take(a.t1, (size_t)cells);
@@ -3929,23 +3947,15 @@ static int ground_filter(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const 
 extern "C" int o3dr_ground_filter(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, const o3dr_ground_params* p,
                                   const o3dr_ground_outputs* out, o3dr_ground_result* res, int32_t mem)
 {
-    if (res) memset(res, 0, sizeof *res);
     Outputs outs{mem};
-    int64_t cells = 0;
-    if (p && p->width >= 1 && p->height >= 1 && (int64_t)p->width * p->height <= (int64_t)O3DR_RASTER_MAX_CELLS)
-        cells = (int64_t)p->width * p->height;
+    const int64_t cells = p ? box_cells(p->width, p->height) : 0;
     if (out) {
         outs.add(out->ground, cloud_points(n, kMeshCloudMax));
         outs.add(out->height_above_ground, cloud_points(n, kMeshCloudMax));
         outs.add(out->dtm, cells);
         outs.add(out->cell_state, cells);
     }
-    const int rc = entered(c, [&] { return ground_filter(c, cloud, n, p, out, outs, res, mem); });
-    if (rc != O3DR_OK) {  // host outputs zeroed on error
-        if (res) memset(res, 0, sizeof *res);
-        outs.zero();
-    }
-    return rc;
+    return raster_entry(c, outs, res, sizeof *res, [&] { return ground_filter(c, cloud, n, p, out, outs, res, mem); });
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -3963,18 +3973,6 @@ struct InterpFlags {
     alignas(64) uint32_t counters[kInterpPartWords];  // InterpArgs::counters
     alignas(64) uint32_t bad;                         // an infinite input value
 };
-struct SampleFlags {
-    alignas(64) CellFlags cell;
-    alignas(64) uint32_t counters[4];  // SampleArgs::counters
-};
-
-// width * height of a raster the outputs can be sized by before anything else is validated: 0 outside the limits
-static int64_t interp_cells(const o3dr_interpolate_params* p)
-{
-    if (!p || p->width < 1 || p->height < 1) return 0;
-    const int64_t cells = (int64_t)p->width * p->height;
-    return cells <= (int64_t)O3DR_RASTER_MAX_CELLS ? cells : 0;
-}
 
 static int raster_interpolate(o3dr_ctx* c, const float* raster, const o3dr_interpolate_params* p, const o3dr_interpolate_outputs* out,
                               Outputs& outs, o3dr_interpolate_result* res, int32_t mem)
@@ -4031,18 +4029,13 @@ static int raster_interpolate(o3dr_ctx* c, const float* raster, const o3dr_inter
 extern "C" int o3dr_raster_interpolate(o3dr_ctx* c, const float* raster, const o3dr_interpolate_params* p,
                                        const o3dr_interpolate_outputs* out, o3dr_interpolate_result* res, int32_t mem)
 {
-    if (res) memset(res, 0, sizeof *res);
     Outputs outs{mem};
+    const int64_t cells = p ? box_cells(p->width, p->height) : 0;
     if (out) {
-        outs.add(out->filled, interp_cells(p));
-        outs.add(out->level, interp_cells(p));
+        outs.add(out->filled, cells);
+        outs.add(out->level, cells);
     }
-    const int rc = entered(c, [&] { return raster_interpolate(c, raster, p, out, outs, res, mem); });
-    if (rc != O3DR_OK) {  // host outputs zeroed on error
-        if (res) memset(res, 0, sizeof *res);
-        outs.zero();
-    }
-    return rc;
+    return raster_entry(c, outs, res, sizeof *res, [&] { return raster_interpolate(c, raster, p, out, outs, res, mem); });
 }
 
 static int raster_sample(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, double cell_size, const int32_t box[4], const float* raster,
@@ -4052,29 +4045,22 @@ static int raster_sample(o3dr_ctx* c, const o3dr_point* cloud, int64_t n, double
     if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
     SampleArgs a;
     memset(&a, 0, sizeof a);
-    RasterArgs& r = a.r;
-    CHK(raster_cell_size(cell_size, &r.inv));
-    if (box[2] < 1 || box[3] < 1) return fail(O3DR_ERR_INVALID_ARG, "the raster's box needs width, height >= 1");
-    if ((int64_t)box[0] + box[2] - 1 > INT32_MAX || (int64_t)box[1] + box[3] - 1 > INT32_MAX)
-        return fail(O3DR_ERR_INVALID_ARG, "the raster's box leaves int32");
+    float inv;
+    CHK(frame_cell_size(cell_size, &inv));
+    CHK(box_check(box[0], box[1], box[2], box[3]));
     CHK(nn_check_cloud(n, cloud, kMeshCloudMax));
     c->place_ub = -1;
-    r.n = (uint32_t)n;
-    r.cx0 = box[0], r.cy0 = box[1], r.width = box[2], r.height = box[3];
-    r.cell_size = cell_size;
     SampleFlags* f;
     CHK(op_flags(c, &f));
-    if (n > 0) {
-        CellFlags h;
-        CHK(raster_cloud(c, cloud, n, mem, r, f, &h));
-    }
-    const int64_t cells = (int64_t)box[2] * box[3];
-    if (cells > (int64_t)O3DR_RASTER_MAX_CELLS) return fail(O3DR_ERR_INVALID_ARG, kRasterTooLarge);
+    CellFlags h;
+    CHK(raster_frame(c, cloud, n, mem, inv, box, &f->cell, &h, &a.f));
+    int64_t cells;
+    CHK(box_limit(a.f, &cells));
     const void* raster_d;
     CHK(stage_in(c, c->op[o3dr_ctx::OP_IN], raster, (size_t)cells * sizeof(float), mem, &raster_d));
-    r.height_map = const_cast<float*>((const float*)raster_d);  // (read only)
+    a.raster = (const float*)raster_d;
     CHK(outs.stage(c));
-    CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) { w.take(r.part, (size_t)std::max<int64_t>(raster_winner_parts(n), 1) * kPartWords); }));
+    CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) { w.take(a.f.part, (size_t)std::max<int64_t>(raster_winner_parts(n), 1) * kPartWords); }));
     a.counters = f->counters;
     a.value = outs.dev(value), a.hag = outs.dev(height_above);
     launch_raster_sample(&c->prof, c->stream, a);
@@ -4091,17 +4077,12 @@ extern "C" int o3dr_raster_sample(o3dr_ctx* c, const o3dr_point* cloud, int64_t 
                                   int32_t width, int32_t height, const float* raster, float* value, float* height_above,
                                   int64_t counts[3], int32_t mem)
 {
-    if (counts) memset(counts, 0, 3 * sizeof(int64_t));
     Outputs outs{mem};
     outs.add(value, cloud_points(n, kMeshCloudMax));
     outs.add(height_above, cloud_points(n, kMeshCloudMax));
     const int32_t box[4] = {cx0, cy0, width, height};
-    const int rc = entered(c, [&] { return raster_sample(c, cloud, n, cell_size, box, raster, value, height_above, outs, counts, mem); });
-    if (rc != O3DR_OK) {  // host outputs zeroed on error
-        if (counts) memset(counts, 0, 3 * sizeof(int64_t));
-        outs.zero();
-    }
-    return rc;
+    return raster_entry(c, outs, counts, 3 * sizeof(int64_t),
+                        [&] { return raster_sample(c, cloud, n, cell_size, box, raster, value, height_above, outs, counts, mem); });
 }
 
 // -------------------------------------------------------------------------------------------------

@@ -494,7 +494,7 @@ struct GraphArgs {
 void launch_graph_solve(Profiler* pf, hipStream_t s, const GraphArgs& a);
 // The dense XY cell order of a cloud (kernels/cell_order.inc): the points sorted by the dense id
 // (iy - y0) * wx + (ix - x0) of their cell, input order kept inside a cell.  The operator's Args (PlaneArgs, MeshArgs:
-// cloud, n, the parameter of its index rule, `cells`) select the index rule.
+// cloud, n, the parameter of its index rule, `cells`) select the index rule; a RasterFrame takes the range pass alone.
 struct CellOrder {
     int32_t x0, y0;               // the index box's lower corner
     uint64_t wx, wy;              // its widths (wx * wy within the operator's limit, at most 2^32)
@@ -562,18 +562,22 @@ struct MeshArgs {
 // each if set.
 void launch_mesh_count(Profiler* pf, hipStream_t s, Workspace& ws, const MeshArgs& a, uint32_t* n_tris_dev);
 void launch_mesh_emit(Profiler* pf, hipStream_t s, const MeshArgs& a);
-// map raster (kernels/raster.inc; the fields are filled by o3dr_rasterize_map step by step; o3dr_raster_extent uses
-// cloud, n, inv alone, for launch_cell_range)
-struct RasterArgs {
+// The raster frame (DESIGN.md "Raster frame"): what a pass over the points of a box of XY cells needs and nothing else.
+// Held by value by every operator of the raster family; o3dr_raster_extent builds a frame alone, for launch_cell_range.
+struct RasterFrame {
     const o3dr_point* cloud;      // the cloud in input order
     uint32_t n;
     float inv;                    // 1.0f / (float)cell_size
-    int32_t cx0, cy0, width, height;
+    int32_t cx0, cy0, width, height;  // the box: cells cx0 .. cx0 + width - 1, cy0 .. cy0 + height - 1
+    uint32_t* part;               // kPartWords words per workgroup of the operator's passes (cell_range_parts(n) for a point pass)
+};
+// map raster (kernels/raster.inc; the fields are filled by o3dr_rasterize_map step by step)
+struct RasterArgs {
+    RasterFrame f;                // f.part: raster_winner_parts(n) records of the winner pass, then one per tile
     int32_t select, R;            // O3DR_RASTER_*, the fill radius in cells
     double cell_size, light[3];   // light: normalised (read when shade is set)
     unsigned long long* win;      // width * height: the chosen point's (z key, input index), all ones = empty
     int8_t* col;                  // width * height (R > 0): the offset in cy of the column's nearest occupied cell, kRasterNone = none
-    uint32_t* part;               // kPartWords words per workgroup: raster_winner_parts(n) of the winner pass, then one per tile
     uint32_t* counters;           // 12 words: n_inside n_outside - - | n_occupied n_filled n_empty - | z_min z_max (ordered) - -
     float* height_map;            // the outputs (nullptr: not asked for; height_map is scratch when only the shade needs it)
     uint8_t* color;
@@ -620,10 +624,11 @@ inline int64_t ground_col_rows(int64_t height, int r)
 // workgroup partials of a call: the winner and the point pass, the raster's tiles, the column pass of every iteration
 inline int64_t ground_parts(const GroundArgs& a)
 {
-    int64_t parts = raster_tiles(a.r.width, a.r.height);
-    if (raster_winner_parts(a.r.n) > parts) parts = raster_winner_parts(a.r.n);
+    const RasterFrame& f = a.r.f;
+    int64_t parts = raster_tiles(f.width, f.height);
+    if (raster_winner_parts(f.n) > parts) parts = raster_winner_parts(f.n);
     for (int k = 0; k < a.n_iter; ++k) {
-        const int64_t g = ground_col_groups(a.r.width) * ground_col_rows(a.r.height, a.radius[k]);
+        const int64_t g = ground_col_groups(f.width) * ground_col_rows(f.height, a.radius[k]);
         if (g > parts) parts = g;
     }
     return parts;
@@ -678,10 +683,10 @@ inline int interp_top_level(const InterpArgs& a)
 // launch_interpolate: the pulls, the one-workgroup top, the pushes down to level 0 with the outputs; the counters folded
 // into a.counters, a.bad set (it is cleared first)
 void launch_interpolate(Profiler* pf, hipStream_t s, const InterpArgs& a);
-// raster sample (kernels/interpolate.inc; contract: include/o3dr_dem.h "raster sample"): r.cloud, r.n, r.inv, the box,
-// r.part and r.height_map = the raster are read
+// raster sample (kernels/interpolate.inc; contract: include/o3dr_dem.h "raster sample")
 struct SampleArgs {
-    RasterArgs r;
+    RasterFrame f;
+    const float* raster;          // width * height: the raster of the frame's box
     float* value;                 // n or nullptr
     float* hag;                   // n or nullptr
     uint32_t* counters;           // 4 words: inside, outside, on a NaN cell, -

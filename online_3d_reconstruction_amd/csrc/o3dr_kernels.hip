@@ -1124,7 +1124,7 @@ void launch_cell_order(Profiler* pf, hipStream_t s, Workspace& ws, Args& a, int 
 }
 template void launch_cell_range<PlaneArgs>(Profiler*, hipStream_t, const PlaneArgs&, uint32_t*, uint32_t*);
 template void launch_cell_range<MeshArgs>(Profiler*, hipStream_t, const MeshArgs&, uint32_t*, uint32_t*);
-template void launch_cell_range<RasterArgs>(Profiler*, hipStream_t, const RasterArgs&, uint32_t*, uint32_t*);
+template void launch_cell_range<RasterFrame>(Profiler*, hipStream_t, const RasterFrame&, uint32_t*, uint32_t*);
 template void launch_cell_order<PlaneArgs>(Profiler*, hipStream_t, Workspace&, PlaneArgs&, int, uint32_t*, uint32_t*);
 template void launch_cell_order<MeshArgs>(Profiler*, hipStream_t, Workspace&, MeshArgs&, int, uint32_t*, uint32_t*);
 
@@ -1254,17 +1254,18 @@ void launch_mesh_emit(Profiler* pf, hipStream_t s, const MeshArgs& a)
 void launch_raster(Profiler* pf, hipStream_t s, const RasterArgs& a)
 {
     ProfScope ps(pf, O3DR_K_OTHER, s);
-    const int64_t cells = (int64_t)a.width * a.height;
+    const RasterFrame& f = a.f;
+    const int64_t cells = (int64_t)f.width * f.height;
     (void)hipMemsetAsync(a.win, 0xff, (size_t)cells * sizeof(unsigned long long), s);
-    const int gw = (int)raster_winner_parts(a.n);
+    const int gw = (int)raster_winner_parts(f.n);
     if (gw > 0) k_raster_winner<<<gw, kRasterThreads, 0, s>>>(a);
-    k_fold4_u32<<<1, kFoldThreads, 0, s>>>(a.part, gw, 0, 2, 2, 2, 2, a.counters);
+    k_fold4_u32<<<1, kFoldThreads, 0, s>>>(f.part, gw, 0, 2, 2, 2, 2, a.counters);
     const int gc = cdiv64(cells, kRasterThreads);
     if (a.R > 0) k_raster_fill_col<<<gc, kRasterThreads, 0, s>>>(a);
-    const int gt = (int)raster_tiles(a.width, a.height);
+    const int gt = (int)raster_tiles(f.width, f.height);
     k_raster_resolve<<<gt, kRasterThreads, 0, s>>>(a);
-    k_fold4_u32<<<1, kFoldThreads, 0, s>>>(a.part, gt, 0, 2, 2, 2, 2, a.counters + 4);
-    k_fold4_u32<<<1, kFoldThreads, 0, s>>>(a.part, gt, 4, 0, 1, 2, 2, a.counters + 8);
+    k_fold4_u32<<<1, kFoldThreads, 0, s>>>(f.part, gt, 0, 2, 2, 2, 2, a.counters + 4);
+    k_fold4_u32<<<1, kFoldThreads, 0, s>>>(f.part, gt, 4, 0, 1, 2, 2, a.counters + 8);
     if (a.shade) k_raster_shade<<<gc, kRasterThreads, 0, s>>>(a);
 }
 
@@ -1272,44 +1273,45 @@ void launch_raster(Profiler* pf, hipStream_t s, const RasterArgs& a)
 void launch_ground(Profiler* pf, hipStream_t s, const GroundArgs& a)
 {
     const RasterArgs& r = a.r;
-    const int64_t cells = (int64_t)r.width * r.height;
+    const RasterFrame& f = r.f;
+    const int64_t cells = (int64_t)f.width * f.height;
     const int gc = cdiv64(cells, kGroundThreads);
-    const int gw = (int)raster_winner_parts(r.n);
+    const int gw = (int)raster_winner_parts(f.n);
     {
         ProfScope ps(pf, O3DR_K_GROUND_WINNER, s);
         (void)hipMemsetAsync(r.win, 0xff, (size_t)cells * sizeof(unsigned long long), s);
         if (gw > 0) k_raster_winner<<<gw, kRasterThreads, 0, s>>>(r);
-        k_fold4_u32<<<1, kFoldThreads, 0, s>>>(r.part, gw, 0, 2, 2, 2, 2, a.counters);
+        k_fold4_u32<<<1, kFoldThreads, 0, s>>>(f.part, gw, 0, 2, 2, 2, 2, a.counters);
         k_ground_init<<<gc, kGroundThreads, 0, s>>>(a);
     }
-    const int64_t tiles_x = ((int64_t)r.width + kGroundTileW - 1) / kGroundTileW, gx = ground_col_groups(r.width);
-    const unsigned g_row = (unsigned)(tiles_x * r.height);
+    const int64_t tiles_x = ((int64_t)f.width + kGroundTileW - 1) / kGroundTileW, gx = ground_col_groups(f.width);
+    const unsigned g_row = (unsigned)(tiles_x * f.height);
     for (int k = 0; k < a.n_iter; ++k) {
         ProfScope ps(pf, O3DR_K_GROUND_ITER, s);
         const int rad = a.radius[k];
         int p = 1;
         while (2 * p <= 2 * rad + 1) p *= 2;  // the largest power of two within the window
-        const unsigned g_col = (unsigned)(gx * ground_col_rows(r.height, rad));
-        k_ground_row<false><<<g_row, kGroundThreads, 0, s>>>(a.zl, a.t1, r.width, tiles_x, rad, p);
-        k_ground_col_suffix<false><<<g_col, kGroundThreads, 0, s>>>(a.t1, a.run, r.width, r.height, gx, rad);
+        const unsigned g_col = (unsigned)(gx * ground_col_rows(f.height, rad));
+        k_ground_row<false><<<g_row, kGroundThreads, 0, s>>>(a.zl, a.t1, f.width, tiles_x, rad, p);
+        k_ground_col_suffix<false><<<g_col, kGroundThreads, 0, s>>>(a.t1, a.run, f.width, f.height, gx, rad);
         k_ground_col_window<false><<<g_col, kGroundThreads, 0, s>>>(a, a.t1, gx, rad, 0.f, 0);
-        k_ground_row<true><<<g_row, kGroundThreads, 0, s>>>(a.t2, a.t1, r.width, tiles_x, rad, p);
-        k_ground_col_suffix<true><<<g_col, kGroundThreads, 0, s>>>(a.t1, a.run, r.width, r.height, gx, rad);
+        k_ground_row<true><<<g_row, kGroundThreads, 0, s>>>(a.t2, a.t1, f.width, tiles_x, rad, p);
+        k_ground_col_suffix<true><<<g_col, kGroundThreads, 0, s>>>(a.t1, a.run, f.width, f.height, gx, rad);
         k_ground_col_window<true><<<g_col, kGroundThreads, 0, s>>>(a, a.t1, gx, rad, a.thr[k], (uint8_t)(2 + k));
-        k_fold4_u32<<<1, kFoldThreads, 0, s>>>(r.part, (int)g_col, 0, 2, 2, 2, 2, a.counters + 16 + 4 * k);
+        k_fold4_u32<<<1, kFoldThreads, 0, s>>>(f.part, (int)g_col, 0, 2, 2, 2, 2, a.counters + 16 + 4 * k);
     }
     {
         ProfScope ps(pf, O3DR_K_GROUND_FILL, s);
         k_ground_ground_words<<<gc, kGroundThreads, 0, s>>>(a);
         if (r.R > 0) k_raster_fill_col<<<gc, kRasterThreads, 0, s>>>(r);
-        const int gt = (int)raster_tiles(r.width, r.height);
+        const int gt = (int)raster_tiles(f.width, f.height);
         k_raster_resolve<<<gt, kRasterThreads, 0, s>>>(r);
-        k_fold4_u32<<<1, kFoldThreads, 0, s>>>(r.part, gt, 0, 2, 2, 2, 2, a.counters + 4);
+        k_fold4_u32<<<1, kFoldThreads, 0, s>>>(f.part, gt, 0, 2, 2, 2, 2, a.counters + 4);
     }
     {
         ProfScope ps(pf, O3DR_K_GROUND_POINTS, s);
         if (gw > 0) k_ground_points<<<gw, kGroundThreads, 0, s>>>(a);
-        k_fold4_u32<<<1, kFoldThreads, 0, s>>>(r.part, gw, 0, 2, 2, 2, 2, a.counters + 12);
+        k_fold4_u32<<<1, kFoldThreads, 0, s>>>(f.part, gw, 0, 2, 2, 2, 2, a.counters + 12);
     }
 }
 
@@ -1349,9 +1351,9 @@ void launch_interpolate(Profiler* pf, hipStream_t s, const InterpArgs& a)
 void launch_raster_sample(Profiler* pf, hipStream_t s, const SampleArgs& a)
 {
     ProfScope ps(pf, O3DR_K_RASTER_SAMPLE, s);
-    const int g = (int)raster_winner_parts(a.r.n);
+    const int g = (int)raster_winner_parts(a.f.n);
     if (g > 0) k_raster_sample<<<g, kInterpThreads, 0, s>>>(a);
-    k_fold4_u32<<<1, kFoldThreads, 0, s>>>(a.r.part, g, 0, 2, 2, 2, 2, a.counters);
+    k_fold4_u32<<<1, kFoldThreads, 0, s>>>(a.f.part, g, 0, 2, 2, 2, 2, a.counters);
 }
 
 // Euclidean clustering (kernels/cluster.inc) over the grid launch_nn_grid left in ws.sor_*
