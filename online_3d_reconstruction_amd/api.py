@@ -1052,6 +1052,56 @@ class Context:
         desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
         return desc, int(desc.shape[0])
 
+    def _point_pairs(self, src, tgt, mask, seg_offsets):
+        """The index-aligned point pairs of estimateRigidTransform / ransacRigid as the library reads them -> ((src, tgt,
+        mask) kept alive, their addresses (None where absent), n, MEM kind, segs (int64 array or None), n_segs)."""
+        src, n = self._cloud(src)
+        tgt, n2 = self._cloud(tgt)
+        assert n == n2, "src and tgt must be index-aligned"
+        ps_, mem, _k = _ptr(src)
+        pt, mem2, _k2 = _ptr(tgt)
+        if n:
+            assert mem == mem2, "src and tgt must live in the same memory"
+        pm = None
+        if mask is not None:
+            if _is_torch(mask):
+                import torch
+                mask = mask.to(torch.uint8).contiguous()
+                pm = mask.data_ptr()
+            else:
+                mask = np.ascontiguousarray(mask).astype(np.uint8)
+                pm = mask.ctypes.data
+        segs = None if seg_offsets is None else np.ascontiguousarray(seg_offsets, np.int64).reshape(-1)
+        n_segs = 1 if segs is None else len(segs) - 1
+        return (src, tgt, mask), (ps_ if n else None, pt if n else None, pm), n, mem, segs, n_segs
+
+    def _feature_pool(self, desc, kp3, offsets):
+        """The pool of poseChain / refinePoses as the library reads it -> (desc, kp3, their addresses (None for an empty
+        pool), MEM kind, off (int64 array), F)."""
+        desc, n = self._desc(desc)
+        kp3, n3 = self._cloud(kp3)
+        assert n == n3, "kp3 must be index-aligned with desc"
+        pd, mem, _k = _ptr(desc)
+        pk, mem2, _k2 = _ptr(kp3)
+        if n:
+            assert mem == mem2, "desc and kp3 must live in the same memory"
+        off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        return desc, kp3, pd if n else None, pk if n else None, mem, off, len(off) - 1
+
+    @staticmethod
+    def _ransac_params(threshold, seed, iterations):
+        return L.RansacParamsStruct(float(threshold), int(seed) & 0xFFFFFFFFFFFFFFFF, int(iterations), 0)
+
+    def _pose_out(self, like, mem, F):
+        """The pose output of poseChain / refinePoses: [max(F, 1), 16] float32 zeros in `like`'s memory -> (it, its address)."""
+        if mem == L.MEM_DEVICE:
+            import torch
+            poses = torch.zeros((max(F, 1), 16), dtype=torch.float32, device=like.device)
+            self._order_after_torch()
+            return poses, poses.data_ptr()
+        poses = np.zeros((max(F, 1), 16), np.float32)
+        return poses, poses.ctypes.data
+
     def matchDescriptors(self, desc, offsets, pairs, ratio=0.5, max_distance=40):
         """Brute-force Hamming 2-NN of every query row of every (query_set, train_set) pair (contract: include/o3dr.h,
         DESIGN.md "Feature matching").  desc: uint8 [N, 32] (numpy, or a torch CUDA tensor: results are then CUDA tensors);
@@ -1128,29 +1178,12 @@ class Context:
         rigid T mapping src onto tgt over the index-aligned pairs with mask != 0 and finite coordinates.  numpy POINT arrays,
         or torch [N,4] 4-byte CUDA tensors (mask then a CUDA uint8 / bool tensor).  -> RigidResult, or a list of them with
         seg_offsets (the n_segs + 1 segment boundaries)."""
-        src, n = self._cloud(src)
-        tgt, n2 = self._cloud(tgt)
-        assert n == n2, "src and tgt must be index-aligned"
-        ps_, mem, _k = _ptr(src)
-        pt, mem2, _k2 = _ptr(tgt)
-        if n:
-            assert mem == mem2, "src and tgt must live in the same memory"
-        pm = None
-        if mask is not None:
-            if _is_torch(mask):
-                import torch
-                mask = mask.to(torch.uint8).contiguous()
-                pm = mask.data_ptr()
-            else:
-                mask = np.ascontiguousarray(mask).astype(np.uint8)
-                pm = mask.ctypes.data
-        segs = None if seg_offsets is None else np.ascontiguousarray(seg_offsets, np.int64).reshape(-1)
-        n_segs = 1 if segs is None else len(segs) - 1
+        _keep, (ps_, pt, pm), n, mem, segs, n_segs = self._point_pairs(src, tgt, mask, seg_offsets)
         res = np.zeros(max(n_segs, 1), L.RIGID_RESULT)
         if mem == L.MEM_DEVICE:
             self._order_after_torch()
-        L.check(self._lib.o3dr_estimate_rigid_transform(self._h, ps_ if n else None, pt if n else None, n,
-                                                        None if segs is None else segs.ctypes.data, n_segs, pm, res.ctypes.data, mem))
+        L.check(self._lib.o3dr_estimate_rigid_transform(self._h, ps_, pt, n, None if segs is None else segs.ctypes.data, n_segs, pm,
+                                                        res.ctypes.data, mem))
         out = [RigidResult.from_record(r) for r in res[:n_segs]]
         return out[0] if segs is None else out
 
@@ -1160,27 +1193,10 @@ class Context:
         with `seed` and the segment's key (seg_keys, uint64 per segment; default: its ordinal).  Inputs as
         estimateRigidTransform's.  -> (inlier: bool mask index-aligned with src - numpy, or a CUDA tensor for CUDA inputs -,
         records: a numpy RANSAC_RESULT array, one per segment)."""
-        src, n = self._cloud(src)
-        tgt, n2 = self._cloud(tgt)
-        assert n == n2, "src and tgt must be index-aligned"
-        ps_, mem, _k = _ptr(src)
-        pt, mem2, _k2 = _ptr(tgt)
-        if n:
-            assert mem == mem2, "src and tgt must live in the same memory"
-        pm = None
-        if mask is not None:
-            if _is_torch(mask):
-                import torch
-                mask = mask.to(torch.uint8).contiguous()
-                pm = mask.data_ptr()
-            else:
-                mask = np.ascontiguousarray(mask).astype(np.uint8)
-                pm = mask.ctypes.data
-        segs = None if seg_offsets is None else np.ascontiguousarray(seg_offsets, np.int64).reshape(-1)
-        n_segs = 1 if segs is None else len(segs) - 1
+        (src, _t, _m), (ps_, pt, pm), n, mem, segs, n_segs = self._point_pairs(src, tgt, mask, seg_offsets)
         keys = None if seg_keys is None else np.ascontiguousarray(seg_keys, np.uint64).reshape(-1)
         assert keys is None or len(keys) == n_segs, "one key per segment"
-        prm = L.RansacParamsStruct(float(threshold), int(seed) & 0xFFFFFFFFFFFFFFFF, int(iterations), 0)
+        prm = self._ransac_params(threshold, seed, iterations)
         res = np.zeros(max(n_segs, 1), L.RANSAC_RESULT)
         if mem == L.MEM_DEVICE and n:
             import torch
@@ -1190,9 +1206,8 @@ class Context:
         else:
             inl = np.zeros(max(n, 1), np.uint8)
             pi = inl.ctypes.data
-        L.check(self._lib.o3dr_ransac_rigid(self._h, ps_ if n else None, pt if n else None, n, None if segs is None else segs.ctypes.data,
-                                            n_segs, pm, None if keys is None else keys.ctypes.data, C.byref(prm), pi, res.ctypes.data,
-                                            mem))
+        L.check(self._lib.o3dr_ransac_rigid(self._h, ps_, pt, n, None if segs is None else segs.ctypes.data, n_segs, pm,
+                                            None if keys is None else keys.ctypes.data, C.byref(prm), pi, res.ctypes.data, mem))
         return inl[:n] != 0, res[:n_segs]
 
     def matchFeatures(self, desc_q, desc_t, kp3_q, kp3_t, ratio=0.5, max_distance=40, ransac_threshold=None, ransac_iterations=256,
@@ -1250,16 +1265,8 @@ class Context:
         refine=True: refinePoses runs on the outputs and the pair list (the history frames fixed; ratio, max_distance and
         the ransac_* keywords passed through; refine_kw: its other keywords); the poses returned are the refined ones, the
         records stay the chain's, and the RefineResult is appended to the tuple."""
-        desc, n = self._desc(desc)
-        kp3, n3 = self._cloud(kp3)
-        assert n == n3, "kp3 must be index-aligned with desc"
-        pd, mem, _k = _ptr(desc)
-        pk, mem2, _k2 = _ptr(kp3)
-        if n:
-            assert mem == mem2, "desc and kp3 must live in the same memory"
+        desc, kp3, pd, pk, mem, off, F = self._feature_pool(desc, kp3, offsets)
         host = lambda a, dt: np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else a, dt)  # noqa: E731
-        off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
-        F = len(off) - 1
         prior = host(prior_poses, np.float32).reshape(-1, 16)
         assert F >= 0 and len(prior) == F, "one prior pose per frame"
         n_fixed = int(n_fixed)
@@ -1274,18 +1281,11 @@ class Context:
         want_pairs = return_pairs or (robust and return_ransac) or refine
         cap = max(F * L.CHAIN_MAX_RANGE, 1) if want_pairs else 0
         prs = np.zeros((cap, 2), np.int32) if want_pairs else None
-        rprm = L.RansacParamsStruct(float(ransac_threshold), int(ransac_seed) & 0xFFFFFFFFFFFFFFFF, int(ransac_iterations), 0) if robust else None
+        rprm = self._ransac_params(ransac_threshold, ransac_seed, ransac_iterations) if robust else None
         rres = np.zeros(cap, L.RANSAC_RESULT) if robust and return_ransac else None
         n_pairs = C.c_int64(0)
-        if mem == L.MEM_DEVICE:
-            import torch
-            poses = torch.zeros((max(F, 1), 16), dtype=torch.float32, device=desc.device)
-            self._order_after_torch()
-            pp = poses.data_ptr()
-        else:
-            poses = np.zeros((max(F, 1), 16), np.float32)
-            pp = poses.ctypes.data
-        args = (self._h, pd if n else None, off.ctypes.data, pk if n else None, prior.ctypes.data, F, n_fixed,
+        poses, pp = self._pose_out(desc, mem, F)
+        args = (self._h, pd, off.ctypes.data, pk, prior.ctypes.data, F, n_fixed,
                 pin.ctypes.data if len(pin) else None, sin.ctypes.data if len(sin) else None, C.byref(prm), pp, rec.ctypes.data,
                 None if prs is None else prs.ctypes.data, cap, C.byref(n_pairs), mem)
         if robust:
@@ -1323,16 +1323,8 @@ class Context:
         to hold) and prior_poses ([F, 4, 4], needed iff prior_weight > 0) are read on the host.  The ransac_* keywords are
         poseChain's.  -> (poses [F, 4, 4] float32: numpy, or a CUDA tensor for CUDA desc / kp3; records: a numpy
         REFINE_FRAME array, one per frame; RefineResult), with return_edges a numpy REFINE_EDGE array, one per pair."""
-        desc, n = self._desc(desc)
-        kp3, n3 = self._cloud(kp3)
-        assert n == n3, "kp3 must be index-aligned with desc"
-        pd, mem, _k = _ptr(desc)
-        pk, mem2, _k2 = _ptr(kp3)
-        if n:
-            assert mem == mem2, "desc and kp3 must live in the same memory"
+        desc, kp3, pd, pk, mem, off, F = self._feature_pool(desc, kp3, offsets)
         host = lambda a, dt: np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else a, dt)  # noqa: E731
-        off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
-        F = len(off) - 1
         pin = host(poses, np.float32).reshape(-1, 16)
         sin = host(status, np.int32).reshape(-1)
         assert F >= 0 and len(pin) == F and len(sin) == F, "one pose and one status per frame"
@@ -1344,22 +1336,13 @@ class Context:
         assert pri is None or len(pri) == F, "one prior pose per frame"
         prm = L.RefineParamsStruct(float(prior_weight), int(gn_iterations), int(cg_iterations), int(min_pair_matches), float(ratio),
                                    int(max_distance), 0)
-        rprm = None
-        if ransac_threshold is not None:
-            rprm = L.RansacParamsStruct(float(ransac_threshold), int(ransac_seed) & 0xFFFFFFFFFFFFFFFF, int(ransac_iterations), 0)
+        rprm = None if ransac_threshold is None else self._ransac_params(ransac_threshold, ransac_seed, ransac_iterations)
         rec = np.zeros(max(F, 1), L.REFINE_FRAME)
         edg = np.zeros(max(P, 1), L.REFINE_EDGE) if return_edges else None
         res = L.RefineResultStruct()
-        if mem == L.MEM_DEVICE:
-            import torch
-            out = torch.zeros((max(F, 1), 16), dtype=torch.float32, device=desc.device)
-            self._order_after_torch()
-            pp = out.data_ptr()
-        else:
-            out = np.zeros((max(F, 1), 16), np.float32)
-            pp = out.ctypes.data
+        out, pp = self._pose_out(desc, mem, F)
         L.check(self._lib.o3dr_pose_graph_refine(
-            self._h, pd if n else None, off.ctypes.data, pk if n else None, F, pin.ctypes.data if F else None,
+            self._h, pd, off.ctypes.data, pk, F, pin.ctypes.data if F else None,
             sin.ctypes.data if F else None, None if fx is None or not F else fx.ctypes.data,
             None if pri is None or not F else pri.ctypes.data, prs.ctypes.data if P else None, P, C.byref(prm),
             None if rprm is None else C.byref(rprm), pp, rec.ctypes.data, None if edg is None else edg.ctypes.data, C.byref(res), mem))

@@ -122,6 +122,40 @@ __global__ __launch_bounds__(256) void k_match_fold(MatchArgs a, const MatchPair
     }
 }
 
+// ---- the one lookup of a matched row ----------------------------------------------------------------
+// Query row `row` of pair P through what the matching pass left (MatchedPairs): the record r = P.rec0 + row, the good
+// gate, the best train row ti and its gate ti < P.nt (a good row has both neighbours), the two keypoints as float4 and the
+// RANSAC's byte.  chain_slot, ransac_load<true> and k_graph_moments read a row through it and add what is their own.
+// qbase is the query set's first row: P.qbase, which the chain passes as its frame's ChainFrameIn::qbase (pose_chain fills
+// both from the same offsets, so they are equal; with the pair's value k_pose_chain measured 2.5 % slower, DESIGN.md
+// "Matched pairs").  The RANSAC's RansacSeg::start likewise repeats P.rec0.  points == false: only `good` is wanted.
+struct MatchedRow {
+    bool good;    // the matcher's byte
+    bool hit;     // good and ti < nt: s and t are loaded
+    bool in;      // the RANSAC kept the record (true without a filter)
+    uint32_t ti;  // the train row inside its set
+    float4 s, t;  // the query row's keypoint, the train row's
+};
+__device__ __forceinline__ MatchedRow matched_row(const MatchedPairs& M, const MatchPair& P, uint32_t qbase, uint32_t row, bool points = true)
+{
+    MatchedRow o;
+    o.good = o.hit = false;
+    o.in = true;
+    o.ti = kMatchNone;
+    o.s = o.t = make_float4(0.f, 0.f, 0.f, 0.f);
+    const uint64_t r = P.rec0 + row;
+    if (!M.good[r]) return o;
+    o.good = true;
+    if (!points) return o;
+    o.ti = M.rec[r].x;
+    if (o.ti >= P.nt) return o;
+    o.hit = true;
+    o.s = reinterpret_cast<const float4*>(M.kp3)[(uint64_t)qbase + row];
+    o.t = reinterpret_cast<const float4*>(M.kp3)[(uint64_t)P.tbase + o.ti];
+    if (M.inlier && !M.inlier[r]) o.in = false;
+    return o;
+}
+
 // ---- index-aligned 3-D keypoints --------------------------------------------------------------------
 // one lane per keypoint; kp_off: n_frames + 1 int32 entries (relative to the first keypoint)
 __global__ __launch_bounds__(256) void k_keypoints_3d(ReprojectArgs a, const float* __restrict__ kp_xy, const int32_t* __restrict__ kp_off,

@@ -35,20 +35,16 @@ __device__ __forceinline__ ChainSlot chain_slot(const ChainArgs& a, const ChainF
     o.sx = o.sy = o.sz = o.tx = o.ty = o.tz = 0.f;
     const uint32_t lp = s / F.nq, row = s - lp * F.nq;
     if (!accepted[lp]) return o;
-    const MatchPair P = a.pairs[F.pair0 + lp];
-    const uint64_t r = P.rec0 + row;
-    if (!a.good[r]) return o;
-    o.good = true;
-    const uint32_t ti = a.rec[r].x;
-    if (ti >= P.nt) return o;  // (a good row has both neighbours)
-    const float4 sp = reinterpret_cast<const float4*>(a.kp3)[(uint64_t)F.qbase + row];
-    const float4 tp = reinterpret_cast<const float4*>(a.kp3)[(uint64_t)P.tbase + ti];
+    const MatchedRow m = matched_row(a.m, a.m.pairs[F.pair0 + lp], F.qbase, row);
+    o.good = m.good;
+    if (!m.hit) return o;
+    const float4 sp = m.s, tp = m.t;
     float X, Y, Z;
     a2_apply(pose[lp], tp.x, tp.y, tp.z, X, Y, Z);
     o.sx = sp.x, o.sy = sp.y, o.sz = sp.z;
     o.tx = X, o.ty = Y, o.tz = Z;
     o.used = isfinite(sp.x) && isfinite(sp.y) && isfinite(sp.z) && isfinite(X) && isfinite(Y) && isfinite(Z);
-    if (a.inlier && !a.inlier[r]) o.used = false;  // (o3dr_pose_chain_robust: the pair's RANSAC mask)
+    if (!m.in) o.used = false;  // (o3dr_pose_chain_robust: the pair's RANSAC mask)
     return o;
 }
 

@@ -23,7 +23,7 @@ __global__ __launch_bounds__(kGraphRun) void k_graph_moments(GraphMomArgs a)
     if (p >= a.n_pairs) return;  // (uniform)
     const uint32_t tid = threadIdx.x;
     const int lane = tid & 63, wv = tid >> 6;
-    const MatchPair P = a.pairs[p];
+    const MatchPair P = a.m.pairs[p];
     const bool ok = a.pair_ok[p] != 0;
     const uint32_t n_steps = (P.nq + kGraphRun - 1) / kGraphRun;
     double tot = 0.0;
@@ -32,14 +32,12 @@ __global__ __launch_bounds__(kGraphRun) void k_graph_moments(GraphMomArgs a)
         bool good = false, used = false;
         float4 sp = make_float4(0.f, 0.f, 0.f, 0.f), tp = sp;
         if (row < P.nq) {
-            const uint64_t r = P.rec0 + row;
-            good = a.good[r] != 0;
-            const uint32_t ti = a.rec[r].x;
-            if (good && ok && ti < P.nt) {  // (a good row has both neighbours)
-                sp = reinterpret_cast<const float4*>(a.kp3)[(uint64_t)P.qbase + row];
-                tp = reinterpret_cast<const float4*>(a.kp3)[(uint64_t)P.tbase + ti];
+            const MatchedRow m = matched_row(a.m, P, P.qbase, row, ok);  // (a rejected frame's pair: its good rows are still counted)
+            good = m.good;
+            if (m.hit) {
+                sp = m.s, tp = m.t;
                 used = isfinite(sp.x) && isfinite(sp.y) && isfinite(sp.z) && isfinite(tp.x) && isfinite(tp.y) && isfinite(tp.z);
-                if (a.inlier && !a.inlier[r]) used = false;
+                if (!m.in) used = false;
             }
         }
         const double ax = used ? (double)sp.x : 0.0, ay = used ? (double)sp.y : 0.0, az = used ? (double)sp.z : 0.0;

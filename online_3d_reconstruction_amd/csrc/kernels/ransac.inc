@@ -36,12 +36,9 @@ __device__ __forceinline__ bool ransac_load(const RansacArgs& a, const RansacSeg
 {
     float4 s, t;
     if constexpr (kChain) {
-        const uint64_t r = S.start + i;
-        if (!a.good[r]) return false;
-        const uint32_t ti = a.rec[r].x;
-        if (ti >= P.nt) return false;  // (a good row has both neighbours)
-        s = reinterpret_cast<const float4*>(a.kp3)[(uint64_t)P.qbase + i];
-        t = reinterpret_cast<const float4*>(a.kp3)[(uint64_t)P.tbase + ti];
+        const MatchedRow m = matched_row(a.m, P, P.qbase, i);  // (S.start is P.rec0)
+        if (!m.hit) return false;
+        s = m.s, t = m.t;
     } else {
         if (a.mask && !a.mask[S.start + i]) return false;
         s = reinterpret_cast<const float4*>(a.src)[S.start + i];
@@ -141,7 +138,7 @@ __global__ __launch_bounds__(kRansacThreads) void k_ransac_rigid(RansacArgs a)
     const RansacSeg S = a.seg[sg];
     MatchPair P;
     P.qbase = P.nq = P.tbase = P.nt = 0;
-    if constexpr (kChain) P = a.pairs[sg];
+    if constexpr (kChain) P = a.m.pairs[sg];
     const uint32_t n_steps = (S.n + kRansacThreads - 1) / kRansacThreads;
 
     // 1. the candidates, in ascending position

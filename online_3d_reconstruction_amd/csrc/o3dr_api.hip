@@ -4235,12 +4235,54 @@ extern "C" void o3dr_match_default_params(o3dr_match_params* p)
 // work items (waves) the chunk size aims at: enough to fill 256 CUs several times over
 constexpr uint64_t kMatchTargetItems = 8192;
 
-// the pair table of a call (c->mt_tab_h; the pairs are checked) and its totals; `work` = sum of ceil(nq / 64) nt sizes the chunk
+// ---- the checks the feature-pose entry points share; every caller keeps its own texts and limits ----
+// row offsets of n sets / frames: `name` is the array's name in the text
+static int offsets_check(const int64_t* off, int32_t n, const char* name)
+{
+    if (off[0] < 0) return fail(O3DR_ERR_INVALID_ARG, (std::string(name) + "[0] must be >= 0").c_str());
+    for (int32_t s = 0; s < n; ++s)
+        if (off[s + 1] < off[s]) return fail(O3DR_ERR_INVALID_ARG, (std::string(name) + " must not decrease").c_str());
+    return O3DR_OK;
+}
+
+static int match_params_check(float ratio, int32_t max_distance)
+{
+    if (!(std::isfinite(ratio) && ratio > 0.f)) return fail(O3DR_ERR_INVALID_ARG, "ratio must be finite and > 0");
+    if (max_distance < 0 || max_distance > 257) return fail(O3DR_ERR_INVALID_ARG, "max_distance must be in [0, 257]");
+    return O3DR_OK;
+}
+
+// the pool of the chain and the graph: descriptors and 3-D keypoints, row for row
+static int feature_pool_check(const uint8_t* desc, const o3dr_point* kp3, const int64_t* off, int32_t n_frames)
+{
+    CHK(offsets_check(off, n_frames, "offsets"));
+    const int64_t pool = off[n_frames] - off[0];
+    if (pool > (int64_t)INT32_MAX) return fail(O3DR_ERR_INVALID_ARG, "more than 2^31-1 rows");
+    if (pool > 0 && (!desc || !kp3)) return fail(O3DR_ERR_INVALID_ARG, "desc / kp3 is NULL");
+    return O3DR_OK;
+}
+
+static int chain_status_check(const int32_t* status, int32_t n)
+{
+    for (int32_t f = 0; f < n; ++f)
+        if (status[f] < O3DR_CHAIN_ANCHOR || status[f] > O3DR_CHAIN_RMS) return fail(O3DR_ERR_INVALID_ARG, "status_in holds a value outside O3DR_CHAIN_*");
+    return O3DR_OK;
+}
+
+// the RANSAC sampler's key of the pair (query frame i, train frame j)
+static inline uint64_t pair_key(int32_t i, int32_t j) { return ((uint64_t)(uint32_t)i << 32) | (uint64_t)(uint32_t)j; }
+
+// the pair table of a call (c->mt_tab_h; the pairs are checked) and its totals
 struct MatchPlan {
     uint64_t chunk, items, rec, part;  // train rows per chunk; work items, records and partial slots of the call
 };
-static MatchPlan match_plan(o3dr_ctx* c, const int64_t* off, const int32_t* pairs, int64_t n_pairs, uint64_t work)
+static MatchPlan match_plan(o3dr_ctx* c, const int64_t* off, const int32_t* pairs, int64_t n_pairs)
 {
+    uint64_t work = 0;  // sum of ceil(nq / 64) nt: it sizes the chunk
+    for (int64_t k = 0; k < n_pairs; ++k) {
+        const int32_t qs = pairs[2 * k], ts = pairs[2 * k + 1];
+        work += ((uint64_t)(off[qs + 1] - off[qs]) + kWave - 1) / kWave * (uint64_t)(off[ts + 1] - off[ts]);
+    }
     uint64_t chunk = (work + kMatchTargetItems - 1) / kMatchTargetItems;
     chunk = (chunk + kWave - 1) / kWave * kWave;
     if (chunk < (uint64_t)kWave) chunk = kWave;
@@ -4267,6 +4309,14 @@ static MatchPlan match_plan(o3dr_ctx* c, const int64_t* off, const int32_t* pair
     return MatchPlan{chunk, items, rec, part};
 }
 
+// launch_match's arguments for a planned call: the staged pool, the parameters, where the records and the mask go
+static MatchArgs match_args(const MatchPlan& plan, const void* desc_d, int64_t n_pairs, float ratio, int32_t max_distance, uint4* rec,
+                            uint8_t* good)
+{
+    return MatchArgs{(const uint4*)desc_d, (uint32_t)n_pairs, (uint32_t)plan.chunk, plan.items, plan.rec, rec, good, ratio,
+                     (uint32_t)max_distance};
+}
+
 static int match_knn2(o3dr_ctx* c, const uint8_t* desc, const int64_t* off, int32_t n_sets, const int32_t* pairs, int64_t n_pairs,
                       const o3dr_match_params* p, o3dr_knn2* out, uint8_t* good, Outputs& outs, int64_t out_capacity, int64_t* n_out,
                       int32_t mem)
@@ -4276,55 +4326,39 @@ static int match_knn2(o3dr_ctx* c, const uint8_t* desc, const int64_t* off, int3
     o3dr_match_params prm;
     o3dr_match_default_params(&prm);
     if (p) prm = *p;
-    if (!(std::isfinite(prm.ratio) && prm.ratio > 0.f)) return fail(O3DR_ERR_INVALID_ARG, "ratio must be finite and > 0");
-    if (prm.max_distance < 0 || prm.max_distance > 257) return fail(O3DR_ERR_INVALID_ARG, "max_distance must be in [0, 257]");
+    CHK(match_params_check(prm.ratio, prm.max_distance));
     if (n_sets < 0 || n_pairs < 0 || !off || (n_pairs > 0 && !pairs)) return fail(O3DR_ERR_INVALID_ARG, "bad sets / pairs");
     if (n_pairs > (int64_t)0xffffffffLL) return fail(O3DR_ERR_INVALID_ARG, "too many pairs");
-    if (off[0] < 0) return fail(O3DR_ERR_INVALID_ARG, "desc_offsets[0] must be >= 0");
-    for (int32_t s = 0; s < n_sets; ++s)
-        if (off[s + 1] < off[s]) return fail(O3DR_ERR_INVALID_ARG, "desc_offsets must not decrease");
+    CHK(offsets_check(off, n_sets, "desc_offsets"));
     const int64_t pool = off[n_sets] - off[0];
     if (pool > (int64_t)0xffffffffLL) return fail(O3DR_ERR_INVALID_ARG, "more than 2^32-1 descriptor rows");
     if (pool > 0 && !desc) return fail(O3DR_ERR_INVALID_ARG, "desc is NULL");
-    // the pair table, the chunk size and the totals
-    uint64_t n_rec = 0, work = 0;
+    uint64_t n_rec = 0;
     for (int64_t k = 0; k < n_pairs; ++k) {
         const int32_t qs = pairs[2 * k], ts = pairs[2 * k + 1];
         if (qs < 0 || qs >= n_sets || ts < 0 || ts >= n_sets) return fail(O3DR_ERR_INVALID_ARG, "a pair names a set outside [0, n_sets)");
-        const uint64_t nq = (uint64_t)(off[qs + 1] - off[qs]), nt = (uint64_t)(off[ts + 1] - off[ts]);
-        n_rec += nq;
-        work += (nq + kWave - 1) / kWave * nt;
+        n_rec += (uint64_t)(off[qs + 1] - off[qs]);
     }
     *n_out = (int64_t)n_rec;
     if ((int64_t)n_rec > out_capacity) return fail(O3DR_ERR_CAPACITY, "out_capacity is below the record count");
     if (n_rec > 0 && !out) return fail(O3DR_ERR_INVALID_ARG, "out is NULL");
     if (n_rec == 0) return O3DR_OK;
-    const MatchPlan plan = match_plan(c, off, pairs, n_pairs, work);
+    // the pair table, the chunk size and the totals
+    const MatchPlan plan = match_plan(c, off, pairs, n_pairs);
     const std::vector<MatchPair>& tab = c->mt_tab_h;
-    const uint64_t chunk = plan.chunk, items = plan.items, part = plan.part;
     const void* desc_d = nullptr;
     if (pool > 0) CHK(stage_in(c, c->op[o3dr_ctx::OP_IN], desc + 32 * off[0], (size_t)pool * 32, mem, &desc_d));
     MatchPair* tab_d;
     uint2* part_d;
     CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
         w.take(tab_d, tab.size());
-        w.take(part_d, (size_t)(part ? part : 1));
+        w.take(part_d, (size_t)(plan.part ? plan.part : 1));
     }));
     HIPCHK(hipMemcpyAsync(tab_d, tab.data(), tab.size() * sizeof(MatchPair), hipMemcpyHostToDevice, c->stream));
-    MatchArgs a;
-    memset(&a, 0, sizeof a);
-    a.desc = (const uint4*)desc_d;
-    a.n_pairs = (uint32_t)n_pairs;
-    a.chunk_rows = (uint32_t)chunk;
-    a.n_items = items;
-    a.n_rec = n_rec;
-    a.ratio = prm.ratio;
-    a.max_distance = (uint32_t)prm.max_distance;
     outs.set_count(out, (int64_t)n_rec);
     outs.set_count(good, (int64_t)n_rec);
     CHK(outs.stage(c));  // records, then the mask
-    a.rec = (uint4*)outs.dev(out);
-    a.good = outs.dev(good);
+    const MatchArgs a = match_args(plan, desc_d, n_pairs, prm.ratio, prm.max_distance, (uint4*)outs.dev(out), outs.dev(good));
     launch_match(&c->prof, c->stream, a, tab_d, part_d);
     HIPCHK(hipGetLastError());
     CHK(outs.copy_back(c));
@@ -4362,9 +4396,7 @@ static int keypoints_3d(o3dr_ctx* c, const uint8_t* disp, int64_t disp_frame_str
     CHK(check_images(c, disp, disp_pitch, bgr_chk, bgr ? bgr_pitch : 3 * (int64_t)cols, rows, cols, disp_frame_stride));
     if (disp_frame_stride < (int64_t)rows * disp_pitch || (bgr && bgr_frame_stride < (int64_t)rows * bgr_pitch))
         return fail(O3DR_ERR_INVALID_ARG, "frame stride smaller than a frame");
-    if (kp_offsets[0] < 0) return fail(O3DR_ERR_INVALID_ARG, "kp_offsets[0] must be >= 0");
-    for (int32_t f = 0; f < n_frames; ++f)
-        if (kp_offsets[f + 1] < kp_offsets[f]) return fail(O3DR_ERR_INVALID_ARG, "kp_offsets must not decrease");
+    CHK(offsets_check(kp_offsets, n_frames, "kp_offsets"));
     const int64_t n_kp = kp_offsets[n_frames] - kp_offsets[0];
     if (n_kp >= (int64_t)INT32_MAX) return fail(O3DR_ERR_INVALID_ARG, "too many keypoints");
     *n_out = n_kp;
@@ -4419,6 +4451,41 @@ extern "C" int o3dr_keypoints_3d(o3dr_ctx* c, const uint8_t* disp, int64_t disp_
     return rc;
 }
 
+// the index-aligned point pairs of the two rigid operators, as the kernels read them: a host call's src / tgt / mask go to
+// OP_IN (a NULL mask stays NULL: its slot only keeps the layout the same)
+static int stage_point_pairs(o3dr_ctx* c, const o3dr_point* src, const o3dr_point* tgt, const uint8_t* mask, int64_t n, int32_t mem,
+                             const o3dr_point*& src_d, const o3dr_point*& tgt_d, const uint8_t*& mask_d)
+{
+    src_d = src, tgt_d = tgt, mask_d = mask;
+    if (mem != O3DR_MEM_HOST) return O3DR_OK;
+    CHK(carve(c, c->op[o3dr_ctx::OP_IN], [&](Carve& w) {
+        w.take(src_d, (size_t)n);
+        w.take(tgt_d, (size_t)n);
+        w.take(mask_d, (size_t)n + 1);
+    }));
+    if (n > 0) {
+        HIPCHK(hipMemcpyAsync((void*)src_d, src, (size_t)n * sizeof(o3dr_point), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync((void*)tgt_d, tgt, (size_t)n * sizeof(o3dr_point), hipMemcpyHostToDevice, c->stream));
+        if (mask) HIPCHK(hipMemcpyAsync((void*)mask_d, mask, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    }
+    if (!mask) mask_d = nullptr;
+    return O3DR_OK;
+}
+
+// the segment table of the two rigid operators: every segment is checked against [0, n] and the operator's own limit, then
+// fill(s, first point, points) writes the operator's record
+template <class Fill>
+static int segments_walk(const int64_t* seg_offsets, int32_t n_segs, int64_t n, int64_t limit, const char* limit_text, Fill&& fill)
+{
+    for (int32_t s = 0; s < n_segs; ++s) {
+        const int64_t a0 = seg_offsets ? seg_offsets[s] : 0, a1 = seg_offsets ? seg_offsets[s + 1] : n;
+        if (a0 < 0 || a1 < a0 || a1 > n) return fail(O3DR_ERR_INVALID_ARG, "seg_offsets must not decrease and stay within [0, n]");
+        if (a1 - a0 > limit) return fail(O3DR_ERR_INVALID_ARG, limit_text);
+        CHK(fill(s, (uint64_t)a0, (uint32_t)(a1 - a0)));
+    }
+    return O3DR_OK;
+}
+
 static int rigid_transform(o3dr_ctx* c, const o3dr_point* src, const o3dr_point* tgt, int64_t n, const int64_t* seg_offsets, int32_t n_segs,
                            const uint8_t* mask, o3dr_rigid_result* res, int32_t mem)
 {
@@ -4430,16 +4497,12 @@ static int rigid_transform(o3dr_ctx* c, const o3dr_point* src, const o3dr_point*
     std::vector<RigidSeg>& seg = c->rg_seg_h;
     seg.resize((size_t)n_segs);
     uint64_t blocks = 0;
-    for (int32_t s = 0; s < n_segs; ++s) {
-        const int64_t a0 = seg_offsets ? seg_offsets[s] : 0, a1 = seg_offsets ? seg_offsets[s + 1] : n;
-        if (a0 < 0 || a1 < a0 || a1 > n) return fail(O3DR_ERR_INVALID_ARG, "seg_offsets must not decrease and stay within [0, n]");
-        if (a1 - a0 > (int64_t)0xffffffffLL) return fail(O3DR_ERR_INVALID_ARG, "a segment holds more than 2^32-1 points");
-        seg[s].start = (uint64_t)a0;
-        seg[s].n = (uint32_t)(a1 - a0);
-        seg[s].block0 = (uint32_t)blocks;
-        blocks += ((uint64_t)seg[s].n + kRigidPoints - 1) / kRigidPoints;
-        if (blocks > 0x7fffffffull) return fail(O3DR_ERR_INVALID_ARG, "too many points");
-    }
+    CHK(segments_walk(seg_offsets, n_segs, n, (int64_t)0xffffffffLL, "a segment holds more than 2^32-1 points",
+                      [&](int32_t s, uint64_t start, uint32_t len) {
+                          seg[s] = RigidSeg{start, len, (uint32_t)blocks};
+                          blocks += ((uint64_t)len + kRigidPoints - 1) / kRigidPoints;
+                          return blocks > 0x7fffffffull ? fail(O3DR_ERR_INVALID_ARG, "too many points") : O3DR_OK;
+                      }));
     for (int32_t s = 0; s < n_segs; ++s) {
         memset(&res[s], 0, sizeof res[s]);
         for (int k = 0; k < 16; ++k) res[s].T[k] = k % 5 == 0 ? 1.0 : 0.0;
@@ -4447,20 +4510,7 @@ static int rigid_transform(o3dr_ctx* c, const o3dr_point* src, const o3dr_point*
     }
     RigidArgs a;
     memset(&a, 0, sizeof a);
-    a.src = src, a.tgt = tgt, a.mask = mask;
-    if (mem == O3DR_MEM_HOST) {
-        CHK(carve(c, c->op[o3dr_ctx::OP_IN], [&](Carve& w) {
-            w.take(a.src, (size_t)n);
-            w.take(a.tgt, (size_t)n);
-            w.take(a.mask, (size_t)n + 1);
-        }));
-        if (n > 0) {
-            HIPCHK(hipMemcpyAsync((void*)a.src, src, (size_t)n * sizeof(o3dr_point), hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync((void*)a.tgt, tgt, (size_t)n * sizeof(o3dr_point), hipMemcpyHostToDevice, c->stream));
-            if (mask) HIPCHK(hipMemcpyAsync((void*)a.mask, mask, (size_t)n, hipMemcpyHostToDevice, c->stream));
-        }
-        if (!mask) a.mask = nullptr;
-    }
+    CHK(stage_point_pairs(c, src, tgt, mask, n, mem, a.src, a.tgt, a.mask));
     const size_t S = (size_t)n_segs;
     a.n_segs = (uint32_t)n_segs;
     a.n_blocks = (uint32_t)blocks;
@@ -4536,6 +4586,14 @@ static int ransac_check(const o3dr_ransac_params& p)
     return O3DR_OK;
 }
 
+// one segment's record; `over` runs on by the candidates it may have past kRansacStage
+static RansacSeg ransac_seg(uint64_t start, uint64_t key, uint32_t n, uint64_t& over)
+{
+    const RansacSeg g{start, key, over, n, 0};
+    if (n > (uint32_t)kRansacStage) over += n - (uint32_t)kRansacStage;
+    return g;
+}
+
 static int ransac_rigid(o3dr_ctx* c, const o3dr_point* src, const o3dr_point* tgt, int64_t n, const int64_t* seg_offsets, int32_t n_segs,
                         const uint8_t* mask, const uint64_t* seg_keys, const o3dr_ransac_params* p, uint8_t* inlier, Outputs& outs,
                         o3dr_ransac_result* res, int32_t mem)
@@ -4552,34 +4610,15 @@ static int ransac_rigid(o3dr_ctx* c, const o3dr_point* src, const o3dr_point* tg
     std::vector<RansacSeg>& seg = c->rs_seg_h;
     seg.resize((size_t)n_segs);
     uint64_t over = 0;
-    for (int32_t s = 0; s < n_segs; ++s) {
-        const int64_t a0 = seg_offsets ? seg_offsets[s] : 0, a1 = seg_offsets ? seg_offsets[s + 1] : n;
-        if (a0 < 0 || a1 < a0 || a1 > n) return fail(O3DR_ERR_INVALID_ARG, "seg_offsets must not decrease and stay within [0, n]");
-        if (a1 - a0 > (int64_t)INT32_MAX) return fail(O3DR_ERR_INVALID_ARG, "a segment holds more than 2^31-1 points");
-        seg[s].start = (uint64_t)a0;
-        seg[s].key = seg_keys ? seg_keys[s] : (uint64_t)s;
-        seg[s].over0 = over;
-        seg[s].n = (uint32_t)(a1 - a0);
-        seg[s].reserved = 0;
-        if (seg[s].n > (uint32_t)kRansacStage) over += seg[s].n - (uint32_t)kRansacStage;
-    }
+    CHK(segments_walk(seg_offsets, n_segs, n, (int64_t)INT32_MAX, "a segment holds more than 2^31-1 points",
+                      [&](int32_t s, uint64_t start, uint32_t len) {
+                          seg[s] = ransac_seg(start, seg_keys ? seg_keys[s] : (uint64_t)s, len, over);
+                          return O3DR_OK;
+                      }));
     c->place_ub = -1;
     RansacArgs a;
     memset(&a, 0, sizeof a);
-    a.src = src, a.tgt = tgt, a.mask = mask;
-    if (mem == O3DR_MEM_HOST) {
-        CHK(carve(c, c->op[o3dr_ctx::OP_IN], [&](Carve& w) {
-            w.take(a.src, (size_t)n);
-            w.take(a.tgt, (size_t)n);
-            w.take(a.mask, (size_t)n + 1);
-        }));
-        if (n > 0) {
-            HIPCHK(hipMemcpyAsync((void*)a.src, src, (size_t)n * sizeof(o3dr_point), hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync((void*)a.tgt, tgt, (size_t)n * sizeof(o3dr_point), hipMemcpyHostToDevice, c->stream));
-            if (mask) HIPCHK(hipMemcpyAsync((void*)a.mask, mask, (size_t)n, hipMemcpyHostToDevice, c->stream));
-        }
-        if (!mask) a.mask = nullptr;
-    }
+    CHK(stage_point_pairs(c, src, tgt, mask, n, mem, a.src, a.tgt, a.mask));
     const size_t S = (size_t)n_segs;
     RansacSeg* seg_d;
     CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
@@ -4628,35 +4667,33 @@ extern "C" int o3dr_ransac_rigid(o3dr_ctx* c, const o3dr_point* src, const o3dr_
 struct PairStage {
     MatchPlan plan;
     uint64_t over;               // candidates past kRansacStage, over all pairs
-    const uint8_t* desc_d;       // the pool (staged for a host call)
-    const o3dr_point* kp3_d;
-    MatchPair* tab_d;
+    const uint8_t* desc_d;       // the descriptors of the pool (staged for a host call)
+    MatchedPairs m;              // what the stage leaves: the pool's keypoints, the table, plan.rec records and good bytes,
+                                 // and the filter's bytes (nullptr without it)
     uint2* part_d;
-    uint4* rec_d;                // plan.rec records and good bytes
-    uint8_t* good_d;
     RansacSeg* rseg_d;
     uint32_t* over_d;
-    uint8_t* inlier_d;           // plan.rec bytes (with the filter)
+    uint8_t* inlier_d;           // plan.rec bytes, as the filter writes them
     o3dr_ransac_result* rres_d;  // one per pair (with the filter)
 };
 
 static int pair_stage_plan(o3dr_ctx* c, const uint8_t* desc, const int64_t* off, const o3dr_point* kp3, int32_t n_frames,
-                           const int32_t* pl, int64_t n_pairs, uint64_t work, bool robust, int32_t mem, PairStage& S)
+                           const int32_t* pl, int64_t n_pairs, bool robust, int32_t mem, PairStage& S)
 {
     memset(&S, 0, sizeof S);
-    S.plan = match_plan(c, off, pl, n_pairs, work);
+    S.plan = match_plan(c, off, pl, n_pairs);
     const std::vector<MatchPair>& tab = c->mt_tab_h;
     const int64_t pool = off[n_frames] - off[0];
     S.desc_d = desc ? desc + 32 * off[0] : nullptr;
-    S.kp3_d = kp3 ? kp3 + off[0] : nullptr;
+    S.m.kp3 = kp3 ? kp3 + off[0] : nullptr;
     if (mem == O3DR_MEM_HOST) {
         CHK(carve(c, c->op[o3dr_ctx::OP_IN], [&](Carve& w) {
             w.take(S.desc_d, (size_t)pool * 32 + 1);
-            w.take(S.kp3_d, (size_t)pool + 1);
+            w.take(S.m.kp3, (size_t)pool + 1);
         }));
         if (pool > 0) {
             HIPCHK(hipMemcpyAsync((void*)S.desc_d, desc + 32 * off[0], (size_t)pool * 32, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync((void*)S.kp3_d, kp3 + off[0], (size_t)pool * sizeof(o3dr_point), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync((void*)S.m.kp3, kp3 + off[0], (size_t)pool * sizeof(o3dr_point), hipMemcpyHostToDevice, c->stream));
         }
     }
     // the RANSAC's segments: one per pair, keyed by its two frame numbers
@@ -4664,48 +4701,32 @@ static int pair_stage_plan(o3dr_ctx* c, const uint8_t* desc, const int64_t* off,
     rseg.clear();
     if (robust) {
         rseg.resize((size_t)n_pairs);
-        for (int64_t k = 0; k < n_pairs; ++k) {
-            RansacSeg& g = rseg[(size_t)k];
-            g.start = tab[(size_t)k].rec0;
-            g.key = ((uint64_t)(uint32_t)pl[2 * (size_t)k] << 32) | (uint64_t)(uint32_t)pl[2 * (size_t)k + 1];
-            g.over0 = S.over;
-            g.n = tab[(size_t)k].nq;
-            g.reserved = 0;
-            if (g.n > (uint32_t)kRansacStage) S.over += g.n - (uint32_t)kRansacStage;
-        }
+        for (size_t k = 0; k < (size_t)n_pairs; ++k) rseg[k] = ransac_seg(tab[k].rec0, pair_key(pl[2 * k], pl[2 * k + 1]), tab[k].nq, S.over);
     }
     return O3DR_OK;
 }
 
 static void pair_stage_take(o3dr_ctx* c, Carve& w, PairStage& S, bool robust)
 {
-    w.take(S.tab_d, c->mt_tab_h.size() + 1);
+    w.take(S.m.pairs, c->mt_tab_h.size() + 1);
     w.take(S.part_d, (size_t)S.plan.part + 1);
-    w.take(S.rec_d, (size_t)S.plan.rec + 1);
-    w.take(S.good_d, (size_t)S.plan.rec + 1);
+    w.take(S.m.rec, (size_t)S.plan.rec + 1);
+    w.take(S.m.good, (size_t)S.plan.rec + 1);
     w.take(S.rseg_d, c->rs_seg_h.size() + 1);
     w.take(S.over_d, (size_t)S.over + 1);
     w.take(S.inlier_d, robust ? (size_t)S.plan.rec + 1 : 1);
     w.take(S.rres_d, c->rs_seg_h.size() + 1);
+    S.m.inlier = robust ? S.inlier_d : nullptr;
 }
 
+// (the stage writes what S.m shows its readers as const: the table, the records and the mask)
 static int pair_stage_run(o3dr_ctx* c, const PairStage& S, int64_t n_pairs, float ratio, int32_t max_distance, const o3dr_ransac_params* rp)
 {
     const std::vector<MatchPair>& tab = c->mt_tab_h;
-    if (n_pairs > 0) HIPCHK(hipMemcpyAsync(S.tab_d, tab.data(), tab.size() * sizeof(MatchPair), hipMemcpyHostToDevice, c->stream));
+    if (n_pairs > 0) HIPCHK(hipMemcpyAsync((void*)S.m.pairs, tab.data(), tab.size() * sizeof(MatchPair), hipMemcpyHostToDevice, c->stream));
     if (S.plan.rec > 0) {
-        MatchArgs m;
-        memset(&m, 0, sizeof m);
-        m.desc = (const uint4*)S.desc_d;
-        m.n_pairs = (uint32_t)n_pairs;
-        m.chunk_rows = (uint32_t)S.plan.chunk;
-        m.n_items = S.plan.items;
-        m.n_rec = S.plan.rec;
-        m.ratio = ratio;
-        m.max_distance = (uint32_t)max_distance;
-        m.rec = S.rec_d;
-        m.good = S.good_d;
-        launch_match(&c->prof, c->stream, m, S.tab_d, S.part_d);
+        const MatchArgs m = match_args(S.plan, S.desc_d, n_pairs, ratio, max_distance, const_cast<uint4*>(S.m.rec), const_cast<uint8_t*>(S.m.good));
+        launch_match(&c->prof, c->stream, m, S.m.pairs, S.part_d);
         HIPCHK(hipGetLastError());
     }
     // the pairs' inlier masks, in camera coordinates: static like the matching, one workgroup per pair
@@ -4713,10 +4734,8 @@ static int pair_stage_run(o3dr_ctx* c, const PairStage& S, int64_t n_pairs, floa
         const std::vector<RansacSeg>& rseg = c->rs_seg_h;
         RansacArgs g;
         memset(&g, 0, sizeof g);
-        g.kp3 = S.kp3_d;
-        g.pairs = S.tab_d;
-        g.rec = S.rec_d;
-        g.good = S.good_d;
+        g.m = S.m;
+        g.m.inlier = nullptr;  // (the kernel writes the mask: g.inlier)
         g.seg = S.rseg_d;
         g.over = S.over_d;
         g.inlier = S.inlier_d;
@@ -4760,20 +4779,13 @@ static int pose_chain(o3dr_ctx* c, const uint8_t* desc, const int64_t* off, cons
     if (prm.range_width < 1 || prm.range_width > O3DR_CHAIN_MAX_RANGE) return fail(O3DR_ERR_INVALID_ARG, "range_width must be in [1, 32]");
     if (prm.min_matches < 3) return fail(O3DR_ERR_INVALID_ARG, "min_matches must be >= 3");
     if (!(prm.max_rms > 0.0)) return fail(O3DR_ERR_INVALID_ARG, "max_rms must be > 0");
-    if (!(std::isfinite(prm.ratio) && prm.ratio > 0.f)) return fail(O3DR_ERR_INVALID_ARG, "ratio must be finite and > 0");
-    if (prm.max_distance < 0 || prm.max_distance > 257) return fail(O3DR_ERR_INVALID_ARG, "max_distance must be in [0, 257]");
+    CHK(match_params_check(prm.ratio, prm.max_distance));
     if (n_frames < 0 || n_fixed < 0 || n_fixed > n_frames) return fail(O3DR_ERR_INVALID_ARG, "0 <= n_fixed <= n_frames must hold");
     if (n_frames == 0) return O3DR_OK;
     if (!off || !prior || !poses_out || !frames_out) return fail(O3DR_ERR_INVALID_ARG, "offsets / prior_poses / poses_out / frames_out is NULL");
     if (n_fixed > 0 && (!poses_in || !status_in)) return fail(O3DR_ERR_INVALID_ARG, "poses_in / status_in is NULL with n_fixed > 0");
-    if (off[0] < 0) return fail(O3DR_ERR_INVALID_ARG, "offsets[0] must be >= 0");
-    for (int32_t f = 0; f < n_frames; ++f)
-        if (off[f + 1] < off[f]) return fail(O3DR_ERR_INVALID_ARG, "offsets must not decrease");
-    const int64_t pool = off[n_frames] - off[0];
-    if (pool > (int64_t)INT32_MAX) return fail(O3DR_ERR_INVALID_ARG, "more than 2^31-1 rows");
-    if (pool > 0 && (!desc || !kp3)) return fail(O3DR_ERR_INVALID_ARG, "desc / kp3 is NULL");
-    for (int32_t f = 0; f < n_fixed; ++f)
-        if (status_in[f] < O3DR_CHAIN_ANCHOR || status_in[f] > O3DR_CHAIN_RMS) return fail(O3DR_ERR_INVALID_ARG, "status_in holds a value outside O3DR_CHAIN_*");
+    CHK(feature_pool_check(desc, kp3, off, n_frames));
+    CHK(chain_status_check(status_in, n_fixed));
     c->place_ub = -1;
     // 1. the static pair list (host, fp64)
     const size_t F = (size_t)n_frames;
@@ -4784,7 +4796,6 @@ static int pose_chain(o3dr_ctx* c, const uint8_t* desc, const int64_t* off, cons
     train.clear();
     fr.resize(F);
     const double r2 = prm.dist_nearby * prm.dist_nearby;
-    uint64_t work = 0;
     for (int32_t i = 0; i < n_frames; ++i) {
         ChainFrameIn& f = fr[(size_t)i];
         f.pair0 = (uint32_t)train.size();
@@ -4801,7 +4812,6 @@ static int pose_chain(o3dr_ctx* c, const uint8_t* desc, const int64_t* off, cons
             pl.push_back(j);
             train.push_back(j);
             ++f.n_pairs;
-            work += ((uint64_t)f.nq + kWave - 1) / kWave * (uint64_t)(off[j + 1] - off[j]);
         }
         if ((uint64_t)f.n_pairs * f.nq > (uint64_t)INT32_MAX) return fail(O3DR_ERR_INVALID_ARG, "a frame has more than 2^31-1 slots");
     }
@@ -4820,7 +4830,7 @@ static int pose_chain(o3dr_ctx* c, const uint8_t* desc, const int64_t* off, cons
     }
     // 2. staging and scratch
     PairStage S;
-    CHK(pair_stage_plan(c, desc, off, kp3, n_frames, pl.data(), n_pairs, work, rp != nullptr, mem, S));
+    CHK(pair_stage_plan(c, desc, off, kp3, n_frames, pl.data(), n_pairs, rp != nullptr, mem, S));
     int32_t *train_d, *status_d;
     ChainFrameIn* frames_d;
     float* prior_d;
@@ -4844,20 +4854,10 @@ static int pose_chain(o3dr_ctx* c, const uint8_t* desc, const int64_t* off, cons
     }
     // 3. one batched matching pass (and the pairs' inlier masks), then the chain: one launch
     CHK(pair_stage_run(c, S, n_pairs, prm.ratio, prm.max_distance, rp));
-    const o3dr_point* kp3_d = S.kp3_d;
-    MatchPair* tab_d = S.tab_d;
-    uint4* rec_d = S.rec_d;
-    uint8_t* good_d = S.good_d;
-    uint8_t* inlier_d = S.inlier_d;
-    o3dr_ransac_result* rres_d = S.rres_d;
     ChainArgs a;
     memset(&a, 0, sizeof a);
-    a.kp3 = kp3_d;
-    a.pairs = tab_d;
+    a.m = S.m;
     a.pair_train = train_d;
-    a.rec = rec_d;
-    a.good = good_d;
-    a.inlier = rp ? inlier_d : nullptr;
     a.frames = frames_d;
     a.prior = prior_d;
     a.poses = poses_d;
@@ -4873,7 +4873,7 @@ static int pose_chain(o3dr_ctx* c, const uint8_t* desc, const int64_t* off, cons
         HIPCHK(hipMemcpyAsync(frames_out + n_fixed, out_d + n_fixed, (size_t)(n_frames - n_fixed) * sizeof(o3dr_chain_frame),
                               hipMemcpyDeviceToHost, c->stream));
     if (rp && ransac_out && n_pairs > 0)
-        HIPCHK(hipMemcpyAsync(ransac_out, rres_d, (size_t)n_pairs * sizeof(o3dr_ransac_result), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(ransac_out, S.rres_d, (size_t)n_pairs * sizeof(o3dr_ransac_result), hipMemcpyDeviceToHost, c->stream));
     CHK(outs.copy_back(c));
     HIPCHK(hipStreamSynchronize(c->stream));
     return O3DR_OK;
@@ -4943,8 +4943,7 @@ static int pose_graph_refine(o3dr_ctx* c, const uint8_t* desc, const int64_t* of
     if (prm.cg_iterations < 1 || prm.cg_iterations > O3DR_REFINE_MAX_CG) return fail(O3DR_ERR_INVALID_ARG, "cg_iterations must be in [1, 1024]");
     if (prm.min_pair_matches < 1) return fail(O3DR_ERR_INVALID_ARG, "min_pair_matches must be >= 1");
     if (!(std::isfinite(prm.prior_weight) && prm.prior_weight >= 0.0)) return fail(O3DR_ERR_INVALID_ARG, "prior_weight must be finite and >= 0");
-    if (!(std::isfinite(prm.ratio) && prm.ratio > 0.f)) return fail(O3DR_ERR_INVALID_ARG, "ratio must be finite and > 0");
-    if (prm.max_distance < 0 || prm.max_distance > 257) return fail(O3DR_ERR_INVALID_ARG, "max_distance must be in [0, 257]");
+    CHK(match_params_check(prm.ratio, prm.max_distance));
     if (n_frames < 0 || n_pairs < 0) return fail(O3DR_ERR_INVALID_ARG, "n_frames and n_pairs must be >= 0");
     memset(res, 0, sizeof *res);
     if (n_frames == 0) {
@@ -4955,16 +4954,9 @@ static int pose_graph_refine(o3dr_ctx* c, const uint8_t* desc, const int64_t* of
     if (n_pairs > 0 && !pairs) return fail(O3DR_ERR_INVALID_ARG, "pairs is NULL");
     if (n_pairs > (int64_t)INT32_MAX) return fail(O3DR_ERR_INVALID_ARG, "more than 2^31-1 pairs");
     if (prm.prior_weight > 0.0 && !prior) return fail(O3DR_ERR_INVALID_ARG, "prior_poses is NULL with prior_weight > 0");
-    if (off[0] < 0) return fail(O3DR_ERR_INVALID_ARG, "offsets[0] must be >= 0");
-    for (int32_t f = 0; f < n_frames; ++f)
-        if (off[f + 1] < off[f]) return fail(O3DR_ERR_INVALID_ARG, "offsets must not decrease");
-    const int64_t pool = off[n_frames] - off[0];
-    if (pool > (int64_t)INT32_MAX) return fail(O3DR_ERR_INVALID_ARG, "more than 2^31-1 rows");
-    if (pool > 0 && (!desc || !kp3)) return fail(O3DR_ERR_INVALID_ARG, "desc / kp3 is NULL");
-    for (int32_t f = 0; f < n_frames; ++f)
-        if (status_in[f] < O3DR_CHAIN_ANCHOR || status_in[f] > O3DR_CHAIN_RMS) return fail(O3DR_ERR_INVALID_ARG, "status_in holds a value outside O3DR_CHAIN_*");
+    CHK(feature_pool_check(desc, kp3, off, n_frames));
+    CHK(chain_status_check(status_in, n_frames));
     const size_t F = (size_t)n_frames, P = (size_t)n_pairs;
-    uint64_t work = 0;
     {
         std::vector<uint64_t>& keys = c->gr_keys_h;
         keys.resize(P);
@@ -4972,8 +4964,7 @@ static int pose_graph_refine(o3dr_ctx* c, const uint8_t* desc, const int64_t* of
             const int32_t i = pairs[2 * k], j = pairs[2 * k + 1];
             if (i < 0 || i >= n_frames || j < 0 || j >= n_frames) return fail(O3DR_ERR_INVALID_ARG, "a pair names a frame outside [0, n_frames)");
             if (i == j) return fail(O3DR_ERR_INVALID_ARG, "a pair names one frame twice");
-            keys[k] = ((uint64_t)(uint32_t)i << 32) | (uint64_t)(uint32_t)j;
-            work += ((uint64_t)(off[i + 1] - off[i]) + kWave - 1) / kWave * (uint64_t)(off[j + 1] - off[j]);
+            keys[k] = pair_key(i, j);
         }
         std::sort(keys.begin(), keys.end());
         if (std::adjacent_find(keys.begin(), keys.end()) != keys.end()) return fail(O3DR_ERR_INVALID_ARG, "a pair is listed twice");
@@ -4985,7 +4976,7 @@ static int pose_graph_refine(o3dr_ctx* c, const uint8_t* desc, const int64_t* of
     for (size_t k = 0; k < P; ++k) ok_h[k] = accepted(pairs[2 * k]) && accepted(pairs[2 * k + 1]) ? 1 : 0;
     // 1. matching (and the filter): the chain's stage.  2. the moments of every pair
     PairStage S;
-    CHK(pair_stage_plan(c, desc, off, kp3, n_frames, pairs, n_pairs, work, rp != nullptr, mem, S));
+    CHK(pair_stage_plan(c, desc, off, kp3, n_frames, pairs, n_pairs, rp != nullptr, mem, S));
     GraphMomArgs ma;
     memset(&ma, 0, sizeof ma);
     GraphArgs a;
@@ -5019,11 +5010,7 @@ static int pose_graph_refine(o3dr_ctx* c, const uint8_t* desc, const int64_t* of
     HIPCHK(hipMemcpyAsync(pin_d, poses_in, F * 16 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if (prior) HIPCHK(hipMemcpyAsync(prior_d, prior, F * 16 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     CHK(pair_stage_run(c, S, n_pairs, prm.ratio, prm.max_distance, rp));
-    ma.kp3 = S.kp3_d;
-    ma.pairs = S.tab_d;
-    ma.rec = S.rec_d;
-    ma.good = S.good_d;
-    ma.inlier = rp ? S.inlier_d : nullptr;
+    ma.m = S.m;
     ma.pair_ok = ok_d;
     ma.n_pairs = (uint32_t)n_pairs;
     launch_graph_moments(&c->prof, c->stream, ma);

@@ -368,6 +368,16 @@ struct MatchArgs {
 constexpr uint32_t kMatchMaxChunk = 1u << 23;  // train rows per chunk at most (kMatchKeyBits)
 constexpr int64_t kMatchSliceItems = 1 << 24;  // work items per k_match_scan launch at most
 void launch_match(Profiler* pf, hipStream_t s, const MatchArgs& a, const MatchPair* pairs, uint2* partial);
+// What a matching pass leaves for the kernel that reads next (the chain, the chain form of the RANSAC, the graph's moments):
+// the pool's 3-D keypoints, launch_match's table, its records and mask, and the RANSAC's byte per record.  One device
+// function reads a row through it: matched_row (kernels/match.inc).
+struct MatchedPairs {
+    const o3dr_point* kp3;   // the pool
+    const MatchPair* pairs;  // qbase / nq / tbase / nt / rec0
+    const uint4* rec;        // o3dr_knn2 per record
+    const uint8_t* good;
+    const uint8_t* inlier;   // launch_ransac's byte per record, or nullptr: no filter
+};
 // index-aligned 3-D keypoints: kp_off (n_frames + 1 int32, device) relative to kp_xy
 void launch_keypoints_3d(Profiler* pf, hipStream_t s, const ReprojectArgs& a, const float* kp_xy, const int32_t* kp_off, int n_frames,
                          int n_kp, o3dr_point* out);
@@ -403,12 +413,8 @@ struct ChainFrameIn {   // one frame of the call; rows relative to the pool
     uint32_t qbase, nq;
 };
 struct ChainArgs {
-    const o3dr_point* kp3;       // the pool
-    const MatchPair* pairs;      // launch_match's table: qbase / nq / tbase / nt / rec0
+    MatchedPairs m;
     const int32_t* pair_train;   // the train frame of every pair
-    const uint4* rec;            // launch_match's records and mask
-    const uint8_t* good;
-    const uint8_t* inlier;       // launch_ransac_chain's byte per record, or nullptr: no filter
     const ChainFrameIn* frames;  // n_frames
     const float* prior;          // n_frames * 16
     float* poses;                // n_frames * 16: history on entry, every frame on exit
@@ -432,10 +438,8 @@ struct RansacArgs {
     const o3dr_point* src;       // o3dr_ransac_rigid: index-aligned points and the mask (or nullptr)
     const o3dr_point* tgt;
     const uint8_t* mask;
-    const o3dr_point* kp3;       // the chain: the pool, launch_match's table, records and mask (ChainArgs)
-    const MatchPair* pairs;
-    const uint4* rec;
-    const uint8_t* good;
+    MatchedPairs m;              // the chain: one segment per pair.  m.inlier stays nullptr: the kernel reads no filter, it
+                                 // writes one, so its mask is the writable member below, not the read-only one in `m`
     const RansacSeg* seg;        // n_segs
     uint32_t* over;              // positions of the candidates past kRansacStage, per segment
     uint8_t* inlier;             // one byte per point / record
@@ -450,11 +454,7 @@ constexpr int kGraphRun = 256;      // rows per run of the moment sums (kChainRu
 constexpr int kGraphFields = 29;    // the contract's 28 moments, then the pair's good rows
 constexpr int kGraphThreads = 256;  // the solve's one workgroup
 struct GraphMomArgs {
-    const o3dr_point* kp3;       // the pool, launch_match's table, records and mask, the RANSAC's bytes or nullptr (ChainArgs)
-    const MatchPair* pairs;
-    const uint4* rec;
-    const uint8_t* good;
-    const uint8_t* inlier;
+    MatchedPairs m;
     const uint8_t* pair_ok;      // n_pairs: both frames accepted
     double* mom;                 // n_pairs * kGraphFields
     uint32_t* counts;            // n_pairs * 2: n_good, n_used
