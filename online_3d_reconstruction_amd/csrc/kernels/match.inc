@@ -12,8 +12,9 @@
 //   k_match_fold: one lane per record folds the pair's chunk partials in chunk order into (d, global row) keys.  The keys
 //   are a total order, so the records do not depend on the chunk size.
 //   k_keypoints_3d: one lane per keypoint, the keypoint pass's own per-keypoint body (keypoint_one, kernels/reproject.inc).
-//   k_rigid_first / k_rigid_sums / k_rigid_fold: per-segment moments over runs of 256 points from the segment's first
-//   point, the workgroup tree of k_nn_query, folded per segment like k_icp_fold.
+//   k_rigid_first / k_rigid_sums / k_rigid_fold: per-segment rigid_moments (or rigid_residual2) over runs of 256 points
+//   from the segment's first point, wave_fields and tree4 per run, fold_partials per segment (kernels/rigid_core.inc);
+//   the host solves each record with rigid_solve (o3dr_rigid_solve.h).
 // =================================================================================================
 constexpr int kMatchThreads = 256;          // four work items per workgroup
 constexpr int kMatchKeyBits = 23;           // row-inside-chunk bits of a key (d <= 256 takes the upper 9)
@@ -193,7 +194,7 @@ __device__ __forceinline__ bool rigid_used(const RigidArgs& a, uint64_t i, float
     s = reinterpret_cast<const float4*>(a.src)[i];
     t = reinterpret_cast<const float4*>(a.tgt)[i];
     if (a.mask && !a.mask[i]) return false;
-    return isfinite(s.x) && isfinite(s.y) && isfinite(s.z) && isfinite(t.x) && isfinite(t.y) && isfinite(t.z);
+    return pair_finite(s, t);
 }
 
 // the segment of a workgroup: the last segment whose first workgroup is <= b
@@ -239,12 +240,8 @@ __global__ __launch_bounds__(kRigidThreads) void k_rigid_sums(RigidArgs a)
     const bool used = k < S.n && rigid_used(a, S.start + k, s, t);
     double v[F];
     if constexpr (kResidual) {
-        const double* T = a.T + 12 * (uint64_t)sid;
-        const double sx = s.x, sy = s.y, sz = s.z;
-        const double ex = ((T[0] * sx + T[1] * sy) + T[2] * sz) + T[3] - (double)t.x;
-        const double ey = ((T[4] * sx + T[5] * sy) + T[6] * sz) + T[7] - (double)t.y;
-        const double ez = ((T[8] * sx + T[9] * sy) + T[10] * sz) + T[11] - (double)t.z;
-        v[0] = used ? (ex * ex + ey * ey) + ez * ez : 0.0;
+        const double r2 = rigid_residual2(a.T + 12 * (uint64_t)sid, s, t);
+        v[0] = used ? r2 : 0.0;
     } else {
         const uint32_t f = a.first[sid];
         double c0[3] = {0.0, 0.0, 0.0};
@@ -252,45 +249,27 @@ __global__ __launch_bounds__(kRigidThreads) void k_rigid_sums(RigidArgs a)
             const float4 c = reinterpret_cast<const float4*>(a.tgt)[S.start + f];
             c0[0] = c.x, c0[1] = c.y, c0[2] = c.z;
         }
-        const double ax = used ? (double)s.x - c0[0] : 0.0, ay = used ? (double)s.y - c0[1] : 0.0, az = used ? (double)s.z - c0[2] : 0.0;
-        const double bx = used ? (double)t.x - c0[0] : 0.0, by = used ? (double)t.y - c0[1] : 0.0, bz = used ? (double)t.z - c0[2] : 0.0;
-        v[0] = used ? 1.0 : 0.0;
-        v[1] = ax, v[2] = ay, v[3] = az;
-        v[4] = bx, v[5] = by, v[6] = bz;
-        v[7] = ax * bx, v[8] = ax * by, v[9] = ax * bz;
-        v[10] = ay * bx, v[11] = ay * by, v[12] = ay * bz;
-        v[13] = az * bx, v[14] = az * by, v[15] = az * bz;
+        rigid_moments(used, s, t, c0, v);
     }
-    const int wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int f = 0; f < F; ++f) {
-        const double x = wave_sum_f64(v[f]);
-        if ((threadIdx.x & 63) == 0) red[f][wv] = x;
-    }
+    wave_fields<F>(v, red, threadIdx.x & 63, threadIdx.x >> 6);
     __syncthreads();
     if (threadIdx.x < F) {
         const int f = threadIdx.x;
-        a.partial[(uint64_t)f * a.n_blocks + b] = (red[f][0] + red[f][1]) + (red[f][2] + red[f][3]);
+        a.partial[(uint64_t)f * a.n_blocks + b] = tree4(red[f]);
     }
 }
 
-// one workgroup per (segment, field): the segment's partials in k_icp_fold's order -> rec[segment * n_fields + field];
+// one workgroup per (segment, field): the segment's partials through fold_partials -> rec[segment * n_fields + field];
 // field 0's workgroup also writes the segment's c0 (3 doubles)
-__global__ __launch_bounds__(kIcpFoldThreads) void k_rigid_fold(RigidArgs a, int n_fields)
+__global__ __launch_bounds__(kRigidFoldThreads) void k_rigid_fold(RigidArgs a, int n_fields)
 {
-    __shared__ double red[kIcpFoldThreads / kWave];
+    __shared__ double red[kRigidFoldThreads / kWave];
     const int k = blockIdx.y;
     const uint32_t sid = blockIdx.x;
     const RigidSeg S = a.seg[sid];
     const uint32_t nb = (S.n + kRigidThreads - 1) / kRigidThreads;
-    double s = 0.0;
-    for (uint32_t b = threadIdx.x; b < nb; b += kIcpFoldThreads) s += a.partial[(uint64_t)k * a.n_blocks + S.block0 + b];
-    s = wave_sum_f64(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
+    const double t = fold_partials(a.partial + (uint64_t)k * a.n_blocks + S.block0, nb, red);
     if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int j = 0; j < kIcpFoldThreads / kWave; ++j) t += red[j];
         a.rec[(uint64_t)sid * n_fields + k] = t;
         if (k == 0 && a.c0) {
             const uint32_t f = a.first[sid];

@@ -13,11 +13,13 @@
 //   lie in four strips of the target's box whose distance from the query is bounded from below (cell assignment
 //   (x - mn) * inv_h in fp32: within 4 ulps of the real quotient, taken as 1e-6 relative).
 //   The ICP pass fuses the query transform (A2, a2_apply), the search and the epilogue: index (+ d2), "index changed since
-//   the previous pass" per workgroup and the fp64 moments per workgroup, folded in workgroup order by k_icp_fold.
+//   the previous pass" per workgroup and the fp64 moments per workgroup (rigid_moments, wave_fields, tree4 of
+//   kernels/rigid_core.inc), folded in workgroup order by k_icp_fold (fold_partials); the host solves the record with
+//   rigid_solve (o3dr_rigid_solve.h).
 // =================================================================================================
 constexpr double kNnCellPoints = 8.0;  // target points per column of the grid (SOR's grid: kSorCellPoints)
 constexpr int kNnThreads = 256;        // queries per workgroup = the fixed partition of the moment sums
-constexpr int kIcpFields = kIcpRecord;  // count, sum a (3), sum b (3), sum a b^T (9, row-major), sum d2, changed queries
+constexpr int kIcpFields = kIcpRecord;  // the rigid record, ICP_D2, ICP_CHANGED
 
 // exact bounding box of every cell's points (empty cell: +inf .. -inf, a lower bound of +inf)
 __global__ __launch_bounds__(256) void k_nn_cell_box(const float4* __restrict__ sxyz, const uint32_t* __restrict__ cell_first,
@@ -105,13 +107,6 @@ __device__ __forceinline__ double nn_unvisited_bound(const SorGeom& g, const flo
     return lb;
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(kNnThreads) void k_nn_query(NnArgs a)
 {
     __shared__ double red[kIcpFields][kNnThreads / kWave];
@@ -163,45 +158,23 @@ __global__ __launch_bounds__(kNnThreads) void k_nn_query(NnArgs a)
     // the epilogue of the ICP pass: fixed partition (kNnThreads queries per workgroup), fixed reduction tree
     const bool corr = valid && found;
     double v[kIcpFields];
-    const double ax = corr ? (double)qx - a.c0[0] : 0.0, ay = corr ? (double)qy - a.c0[1] : 0.0, az = corr ? (double)qz - a.c0[2] : 0.0;
-    const double bx = corr ? (double)bp.x - a.c0[0] : 0.0, by = corr ? (double)bp.y - a.c0[1] : 0.0, bz = corr ? (double)bp.z - a.c0[2] : 0.0;
-    v[0] = corr ? 1.0 : 0.0;
-    v[1] = ax, v[2] = ay, v[3] = az;
-    v[4] = bx, v[5] = by, v[6] = bz;
-    v[7] = ax * bx, v[8] = ax * by, v[9] = ax * bz;
-    v[10] = ay * bx, v[11] = ay * by, v[12] = ay * bz;
-    v[13] = az * bx, v[14] = az * by, v[15] = az * bz;
-    v[16] = corr ? (double)d2 : 0.0;
-    v[17] = (valid && a.idx_prev && a.idx_prev[i] != idx) ? 1.0 : 0.0;
-    const int w = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < kIcpFields; ++k) {
-        const double s = wave_sum_f64(v[k]);
-        if ((threadIdx.x & 63) == 0) red[k][w] = s;
-    }
+    rigid_moments(corr, make_float4(qx, qy, qz, 0.f), bp, a.c0, v);
+    v[ICP_D2] = corr ? (double)d2 : 0.0;
+    v[ICP_CHANGED] = (valid && a.idx_prev && a.idx_prev[i] != idx) ? 1.0 : 0.0;
+    wave_fields<kIcpFields>(v, red, threadIdx.x & 63, threadIdx.x >> 6);
     __syncthreads();
     if (threadIdx.x < kIcpFields) {
         const int k = threadIdx.x;
-        a.partial[(int64_t)k * a.n_blocks + blockIdx.x] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
+        a.partial[(int64_t)k * a.n_blocks + blockIdx.x] = tree4(red[k]);
     }
 }
-static_assert(kNnThreads == 4 * kWave && kNnThreads == 256, "the workgroup fold above adds four waves; nn_partial_blocks");
+static_assert(kNnThreads == 4 * kWave && kNnThreads == 256, "tree4 adds four waves; nn_partial_blocks");
 
-// one workgroup per field: the per-workgroup partials summed in a fixed order (thread t: partials t, t + 1024, ... in
-// order; then a fixed tree) -> rec[field]
-constexpr int kIcpFoldThreads = 1024;
-__global__ __launch_bounds__(kIcpFoldThreads) void k_icp_fold(const double* __restrict__ partial, uint32_t n_blocks, double* __restrict__ rec)
+// one workgroup per field: the per-workgroup partials summed in a fixed order (fold_partials) -> rec[field]
+__global__ __launch_bounds__(kRigidFoldThreads) void k_icp_fold(const double* __restrict__ partial, uint32_t n_blocks, double* __restrict__ rec)
 {
-    __shared__ double red[kIcpFoldThreads / kWave];
+    __shared__ double red[kRigidFoldThreads / kWave];
     const int k = blockIdx.x;
-    double s = 0.0;
-    for (uint32_t b = threadIdx.x; b < n_blocks; b += kIcpFoldThreads) s += partial[(int64_t)k * n_blocks + b];
-    s = wave_sum_f64(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int j = 0; j < kIcpFoldThreads / kWave; ++j) t += red[j];
-        rec[k] = t;
-    }
+    const double t = fold_partials(partial + (int64_t)k * n_blocks, n_blocks, red);
+    if (threadIdx.x == 0) rec[k] = t;
 }

@@ -7,7 +7,7 @@
 //   order inside a tile; the points are gathered into it (x y z, original index in .w).  With tile_size 0 the cloud is
 //   one tile and the cloud itself is read in place.  Every tile is cut into CHUNKS of kPlaneChunk consecutive points
 //   (the last one partial); one wave owns one chunk, two points per lane (lane j: points j and 64 + j of the chunk).
-//   k_plane_sample: one lane per (tile, hypothesis): the three draws and the fp64 plane, rounded to fp32 (NaN: degenerate).
+//   k_plane_sample: one lane per (tile, hypothesis): the three draws (draw3, kernels/rigid_core.inc) and the fp64 plane, rounded to fp32 (NaN: degenerate).
 //   k_plane_score: a wave keeps its chunk in registers and walks its tile's H hypotheses, whose coefficients are uniform
 //   (scalar loads); each test's lane masks are popcounted, lane j of a 64-hypothesis block keeps hypothesis j's count and
 //   adds it with one integer atomic per (wave, hypothesis): exact counts, no order dependence.
@@ -21,25 +21,9 @@ constexpr int kPlaneMoments = kPlaneMomentsHost;  // k, sum e, sum e e^T (upper 
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 static_assert(kPlaneChunk == 2 * kWave, "two points per lane");
 
-__device__ __forceinline__ uint64_t plane_splitmix64(uint64_t x)
-{
-    uint64_t z = x + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 __device__ __forceinline__ uint64_t plane_tile_key(const o3dr_plane_tile& r)
 {
     return ((uint64_t)(uint32_t)r.iy << 32) | (uint64_t)(uint32_t)r.ix;
-}
-// the three local indices (0 .. m-1) of hypothesis h
-__device__ __forceinline__ void plane_draw(uint64_t S, uint32_t h, uint32_t m, uint32_t loc[3])
-{
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const uint64_t r = plane_splitmix64(S + 3ull * (uint64_t)h + (uint64_t)k);
-        loc[k] = (uint32_t)(((r >> 32) * (uint64_t)m) >> 32);
-    }
 }
 // orientation rule of the contract: nz > 0, then ny > 0, then nx > 0
 __device__ __forceinline__ bool plane_flip(double nx, double ny, double nz)
@@ -169,7 +153,7 @@ __global__ __launch_bounds__(256) void k_plane_sample(PlaneArgs a)
     float4 out = make_float4(nan, nan, nan, nan);
     if (m >= 3u) {
         uint32_t loc[3];
-        plane_draw(plane_splitmix64(a.seed ^ plane_tile_key(a.rec[t])), h, m, loc);
+        draw3(splitmix64(a.seed ^ plane_tile_key(a.rec[t])), h, m, loc);
         const float4 p0 = plane_point(a, t0, loc[0]), p1 = plane_point(a, t0, loc[1]), p2 = plane_point(a, t0, loc[2]);
         const double x0 = p0.x, y0 = p0.y, z0 = p0.z;
         const double e1x = (double)p1.x - x0, e1y = (double)p1.y - y0, e1z = (double)p1.z - z0;
@@ -252,7 +236,7 @@ __global__ __launch_bounds__(kWave) void k_plane_best(PlaneArgs a)
     const uint32_t h = 0xffffffffu - (uint32_t)best;
     o3dr_plane_tile& r = a.rec[t];
     uint32_t loc[3];
-    plane_draw(plane_splitmix64(a.seed ^ plane_tile_key(r)), h, m, loc);
+    draw3(splitmix64(a.seed ^ plane_tile_key(r)), h, m, loc);
     const float4 c = hp[h];
     r.coeff[0] = c.x, r.coeff[1] = c.y, r.coeff[2] = c.z, r.coeff[3] = c.w;
     r.ransac_inliers = (uint32_t)(best >> 32);

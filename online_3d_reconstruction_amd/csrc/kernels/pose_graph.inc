@@ -4,8 +4,9 @@
 // =================================================================================================
 // Pose-graph refinement (o3dr_pose_graph_refine; contract: include/o3dr.h "pose graph", DESIGN.md "Pose-graph refinement")
 //   k_graph_moments: ONE workgroup of kGraphRun threads per pair.  A step covers one run of 256 query rows: every thread
-//   loads its row's correspondence in camera coordinates, the 29 fields go through wave sums, the run is the tree of its
-//   four waves and one lane per field folds the runs left to right (the chain's partition).  The pair's whole contribution
+//   loads its row's correspondence in camera coordinates (used: pair_finite and the pair's gates), the 29 fields go through
+//   wave_fields, the run is tree4 of its four waves (kernels/rigid_core.inc) and one lane per field folds the runs left to
+//   right (the chain's partition).  The record keeps its own products: it is not the rigid record.  The pair's whole contribution
 //   to the solve is that record: the iterations never touch a keypoint again.
 //   k_graph_solve: ONE workgroup of kGraphThreads threads, vectors in global memory.  Per Gauss-Newton iteration one thread
 //   per edge builds the edge's blocks, one thread per (frame, row) sums the gradient over the frame's adjacency, then
@@ -36,8 +37,7 @@ __global__ __launch_bounds__(kGraphRun) void k_graph_moments(GraphMomArgs a)
             good = m.good;
             if (m.hit) {
                 sp = m.s, tp = m.t;
-                used = isfinite(sp.x) && isfinite(sp.y) && isfinite(sp.z) && isfinite(tp.x) && isfinite(tp.y) && isfinite(tp.z);
-                if (!m.in) used = false;
+                used = pair_finite(sp, tp) && m.in;
             }
         }
         const double ax = used ? (double)sp.x : 0.0, ay = used ? (double)sp.y : 0.0, az = used ? (double)sp.z : 0.0;
@@ -53,13 +53,9 @@ __global__ __launch_bounds__(kGraphRun) void k_graph_moments(GraphMomArgs a)
         v[25] = az * bx, v[26] = az * by, v[27] = az * bz;
         v[28] = good ? 1.0 : 0.0;
         double(*rd)[kGraphRun / kWave] = red[st & 1];
-#pragma unroll
-        for (int f = 0; f < kGraphFields; ++f) {
-            const double x = wave_sum_f64(v[f]);
-            if (lane == 0) rd[f][wv] = x;
-        }
+        wave_fields<kGraphFields>(v, rd, lane, wv);
         __syncthreads();  // (the other buffer is written next: its readers passed this barrier's predecessor)
-        if (tid < (uint32_t)kGraphFields) tot += (rd[tid][0] + rd[tid][1]) + (rd[tid][2] + rd[tid][3]);
+        if (tid < (uint32_t)kGraphFields) tot += tree4(rd[tid]);
     }
     if (tid < (uint32_t)kGraphFields) a.mom[(uint64_t)p * kGraphFields + tid] = tot;
     if (tid == 0) a.counts[2 * (uint64_t)p + 1] = (uint32_t)tot;   // (counts are exact in fp64)
@@ -73,10 +69,9 @@ __device__ double graph_sum(const double* x, const double* y, uint32_t n, double
 {
     double s = 0.0;
     for (uint32_t k = threadIdx.x; k < n; k += kGraphThreads) s += y ? x[k] * y[k] : x[k];
-    s = wave_sum_f64(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    wave_fields<1>(&s, reinterpret_cast<double(*)[kGraphThreads / kWave]>(red), threadIdx.x & 63, threadIdx.x >> 6);
     __syncthreads();
-    const double r = (red[0] + red[1]) + (red[2] + red[3]);
+    const double r = tree4(red);
     __syncthreads();
     return r;
 }

@@ -16,19 +16,13 @@
 //     3. one LDS reduction over the waves' keys picks the winner;
 //     4. every thread rebuilds the winner's model with the same operation sequence and the workgroup writes one byte per
 //        position of the segment (each byte once: no ordering between stores is needed); lane 0 writes the record.
+//   The finite test, the sampler (splitmix64, draw3) and the residual (rigid_residual2) are the rigid core's
+//   (kernels/rigid_core.inc, o3dr_rigid_solve.h).
 //   24 + 4 KiB of LDS per workgroup: five workgroups per CU fit in the 160 KiB, so a chain's ~1500 pairs cover the machine
 //   in one to two rounds.  No float atomics, and every loop is bounded by a count from the arguments.
 // =================================================================================================
 constexpr int kRansacWaves = kRansacThreads / kWave;
 static_assert(kRansacStage % kWave == 0, "a wave's 64 candidates are all staged or all read through the list");
-
-__device__ __forceinline__ uint64_t ransac_splitmix64(uint64_t x)  // (plane_splitmix64: the same generator)
-{
-    uint64_t z = x + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 // position i of the segment: its six coordinates; true: a candidate
 template <bool kChain>
@@ -45,7 +39,7 @@ __device__ __forceinline__ bool ransac_load(const RansacArgs& a, const RansacSeg
         t = reinterpret_cast<const float4*>(a.tgt)[S.start + i];
     }
     p[0] = s.x, p[1] = s.y, p[2] = s.z, p[3] = t.x, p[4] = t.y, p[5] = t.z;
-    return isfinite(s.x) && isfinite(s.y) && isfinite(s.z) && isfinite(t.x) && isfinite(t.y) && isfinite(t.z);
+    return pair_finite(s, t);
 }
 
 // the candidate of rank r (< m): its coordinates and its position in the segment
@@ -101,11 +95,7 @@ __device__ __forceinline__ bool ransac_model(const float q[3][6], double T[12])
 
 __device__ __forceinline__ bool ransac_inlier(const double T[12], const float p[6], double thr2)
 {
-    const double x = p[0], y = p[1], z = p[2];
-    const double dx = (((T[0] * x + T[1] * y) + T[2] * z) + T[3]) - (double)p[3];
-    const double dy = (((T[4] * x + T[5] * y) + T[6] * z) + T[7]) - (double)p[4];
-    const double dz = (((T[8] * x + T[9] * y) + T[10] * z) + T[11]) - (double)p[5];
-    return (dx * dx + dy * dy) + dz * dz <= thr2;
+    return rigid_residual2(T, make_float4(p[0], p[1], p[2], 0.f), make_float4(p[3], p[4], p[5], 0.f)) <= thr2;
 }
 
 // hypothesis h of a segment with m candidates: the three ranks, the model; false: degenerate
@@ -116,12 +106,9 @@ __device__ __forceinline__ bool ransac_hypothesis(const RansacArgs& a, const Ran
 {
     uint32_t loc[3];
     float q[3][6];
+    draw3(seed_s, h, m, loc);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const uint64_t r = ransac_splitmix64(seed_s + 3ull * (uint64_t)h + (uint64_t)k);
-        loc[k] = (uint32_t)(((r >> 32) * (uint64_t)m) >> 32);
-        pos[k] = ransac_candidate<kChain>(a, S, P, loc[k], pt_s, pos_s, q[k]);
-    }
+    for (int k = 0; k < 3; ++k) pos[k] = ransac_candidate<kChain>(a, S, P, loc[k], pt_s, pos_s, q[k]);
     if (loc[0] == loc[1] || loc[0] == loc[2] || loc[1] == loc[2]) return false;
     return ransac_model(q, T);
 }
@@ -172,7 +159,7 @@ __global__ __launch_bounds__(kRansacThreads) void k_ransac_rigid(RansacArgs a)
     }
 
     // 2. the hypotheses, round-robin over the waves
-    const uint64_t seed_s = ransac_splitmix64(a.seed ^ S.key);
+    const uint64_t seed_s = splitmix64(a.seed ^ S.key);
     unsigned long long best = 0ull;  // score << 32 | ~h; a score below 3 is no model
     if (m >= 3u) {
         for (uint32_t h = wv; h < a.iterations; h += kRansacWaves) {

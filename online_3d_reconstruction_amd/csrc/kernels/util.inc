@@ -65,6 +65,14 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
 {
     return (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan_u32(v), 63);
 }
+// the fp64 sum over the wave as a fixed butterfly (lane ^ 32, 16, .. 1), the same value in every lane: the order is part
+// of the contract of every fp64 sum built on it (kernels/rigid_core.inc)
+__device__ __forceinline__ double wave_sum_f64(double v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
 // fp32 min / max over the wave, in every lane.  Reduced as order-preserving integers: fminf / fmaxf cost a
 // canonicalising v_max_f32 per operand in front of every step (IEEE NaN rules), v_min_u32 / v_max_u32 take the DPP
 // operand directly - a third of the instructions.  (No NaNs reach these; -0 orders below +0, which no consumer

@@ -3153,89 +3153,6 @@ extern "C" int o3dr_nearest_neighbors(o3dr_ctx* c, const o3dr_point* query, int6
     return O3DR_OK;
 }
 
-// ---- the rigid solve (fp64, host): Kabsch / Umeyama without scale ----------------------------------
-// one-sided Jacobi SVD of a 3x3 matrix: A = U diag(S) V^T, S descending; U's first two columns (the third is not needed)
-static void svd3(const double A_in[3][3], double U[3][3], double S[3], double V[3][3])
-{
-    double A[3][3];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) A[i][j] = A_in[i][j], V[i][j] = i == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 64; ++sweep) {
-        bool rotated = false;
-        for (int p = 0; p < 2; ++p)
-            for (int q = p + 1; q < 3; ++q) {
-                double alpha = 0.0, beta = 0.0, gamma = 0.0;
-                for (int i = 0; i < 3; ++i) {
-                    alpha += A[i][p] * A[i][p];
-                    beta += A[i][q] * A[i][q];
-                    gamma += A[i][p] * A[i][q];
-                }
-                if (!(std::fabs(gamma) > 1e-15 * std::sqrt(alpha * beta))) continue;
-                rotated = true;
-                const double zeta = (beta - alpha) / (2.0 * gamma);
-                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (std::fabs(zeta) + std::sqrt(1.0 + zeta * zeta));
-                const double cs = 1.0 / std::sqrt(1.0 + t * t), sn = cs * t;
-                for (int i = 0; i < 3; ++i) {
-                    const double ap = A[i][p], aq = A[i][q];
-                    A[i][p] = cs * ap - sn * aq;
-                    A[i][q] = sn * ap + cs * aq;
-                    const double vp = V[i][p], vq = V[i][q];
-                    V[i][p] = cs * vp - sn * vq;
-                    V[i][q] = sn * vp + cs * vq;
-                }
-            }
-        if (!rotated) break;
-    }
-    int order[3] = {0, 1, 2};
-    double nrm[3];
-    for (int j = 0; j < 3; ++j) nrm[j] = std::sqrt(A[0][j] * A[0][j] + A[1][j] * A[1][j] + A[2][j] * A[2][j]);
-    std::sort(order, order + 3, [&](int a, int b) { return nrm[a] > nrm[b]; });
-    double Vs[3][3];
-    for (int k = 0; k < 3; ++k) {
-        const int j = order[k];
-        S[k] = nrm[j];
-        for (int i = 0; i < 3; ++i) {
-            Vs[i][k] = V[i][j];
-            U[i][k] = nrm[j] > 0.0 ? A[i][j] / nrm[j] : 0.0;
-        }
-    }
-    for (int i = 0; i < 3; ++i)
-        for (int k = 0; k < 3; ++k) V[i][k] = Vs[i][k];
-}
-
-// dT (row-major 4x4) from the folded record of one pass (moments about c0): R = V diag(1, 1, d) U^T, t = mu_b - R mu_a
-// (pcl::registration::TransformationEstimationSVD with the reflection corrected); false: cross-covariance of rank < 2
-static bool icp_solve(const double* rec, const double c0[3], double dT[16])
-{
-    const double n = rec[0];
-    double ma[3], mb[3], H[3][3];
-    for (int k = 0; k < 3; ++k) ma[k] = rec[1 + k] / n, mb[k] = rec[4 + k] / n;
-    for (int j = 0; j < 3; ++j)
-        for (int k = 0; k < 3; ++k) H[j][k] = rec[7 + 3 * j + k] - n * ma[j] * mb[k];
-    double U[3][3], S[3], V[3][3];
-    svd3(H, U, S, V);
-    if (!(S[0] > 0.0) || !std::isfinite(S[0]) || !(S[1] > 1e-12 * S[0])) return false;
-    // U's third column as u1 x u2 (det U = +1): then d = det(V) gives the proper rotation
-    U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1];
-    U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];
-    U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
-    const double detV = V[0][0] * (V[1][1] * V[2][2] - V[1][2] * V[2][1]) - V[0][1] * (V[1][0] * V[2][2] - V[1][2] * V[2][0]) +
-                        V[0][2] * (V[1][0] * V[2][1] - V[1][1] * V[2][0]);
-    const double d[3] = {1.0, 1.0, detV < 0.0 ? -1.0 : 1.0};
-    double R[3][3];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) R[i][j] = V[i][0] * d[0] * U[j][0] + V[i][1] * d[1] * U[j][1] + V[i][2] * d[2] * U[j][2];
-    for (int i = 0; i < 3; ++i) {
-        double t = c0[i] + mb[i];
-        for (int j = 0; j < 3; ++j) t -= R[i][j] * (c0[j] + ma[j]);
-        for (int j = 0; j < 3; ++j) dT[4 * i + j] = R[i][j];
-        dT[4 * i + 3] = t;
-    }
-    dT[12] = dT[13] = dT[14] = 0.0;
-    dT[15] = 1.0;
-    return std::isfinite(dT[3]) && std::isfinite(dT[7]) && std::isfinite(dT[11]);
-}
-
 extern "C" int o3dr_icp_align(o3dr_ctx* c, const o3dr_point* source, int64_t n_source, const o3dr_point* target, int64_t n_target,
                               const float T_init[16], const o3dr_icp_params* p, o3dr_icp_result* res, int32_t mem)
 {
@@ -3294,16 +3211,16 @@ extern "C" int o3dr_icp_align(o3dr_ctx* c, const o3dr_point* source, int64_t n_s
         }
         CHK(pass(passes > 0));
         rec_at_T = true;
-        if (passes > 1 && rec[17] == 0.0) {
+        if (passes > 1 && rec[ICP_CHANGED] == 0.0) {
             reason = O3DR_ICP_UNCHANGED;
             break;
         }
-        if (rec[0] < 3.0) {
+        if (rec[RIGID_N] < 3.0) {
             reason = O3DR_ICP_TOO_FEW;
             break;
         }
-        double dT[16];
-        if (!icp_solve(rec, c0, dT)) {
+        double dT[16] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0};
+        if (!rigid_solve(rec, c0, dT)) {  // (the Kabsch of the rigid core: o3dr_rigid_solve.h)
             reason = O3DR_ICP_DEGENERATE;
             break;
         }
@@ -3323,8 +3240,8 @@ extern "C" int o3dr_icp_align(o3dr_ctx* c, const o3dr_point* source, int64_t n_s
     }
     if (!rec_at_T) CHK(pass(false));  // fitness at T_out
     for (int k = 0; k < 16; ++k) res->T[k] = T[k];
-    res->n_correspondences = (int64_t)rec[0];
-    res->fitness = rec[0] > 0.0 ? rec[16] / rec[0] : DBL_MAX;
+    res->n_correspondences = (int64_t)rec[RIGID_N];
+    res->fitness = rec[RIGID_N] > 0.0 ? rec[ICP_D2] / rec[RIGID_N] : DBL_MAX;
     res->iterations = iterations;
     res->reason = reason;
     return O3DR_OK;
@@ -4529,22 +4446,20 @@ static int rigid_transform(o3dr_ctx* c, const o3dr_point* src, const o3dr_point*
     HIPCHK(hipMemcpyAsync(rec.data(), a.rec, rec.size() * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(c0.data(), a.c0, c0.size() * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    // the ICP's host Kabsch per segment (icp_solve reads the first 16 fields of an ICP record)
+    // the ICP's host Kabsch per segment (rigid_solve; res[s].T is the identity, so its bottom row stands)
     std::vector<double>& Th = c->rg_T_h;
     Th.assign(S * 12, 0.0);
     for (size_t s = 0; s < S; ++s) {
         const double* r = &rec[s * kRigidFields];
-        res[s].n_used = (int64_t)r[0];
-        double dT[16];
-        double full[kIcpRecord] = {0.0};
-        for (int k = 0; k < kRigidFields; ++k) full[k] = r[k];
-        if (r[0] < 3.0) {
+        res[s].n_used = (int64_t)r[RIGID_N];
+        double T[12];
+        if (r[RIGID_N] < 3.0) {
             res[s].status = O3DR_RIGID_TOO_FEW;
-        } else if (!icp_solve(full, &c0[3 * s], dT)) {
+        } else if (!rigid_solve(r, &c0[3 * s], T)) {
             res[s].status = O3DR_RIGID_DEGENERATE;
         } else {
             res[s].status = O3DR_RIGID_OK;
-            for (int k = 0; k < 16; ++k) res[s].T[k] = dT[k];
+            for (int k = 0; k < 12; ++k) res[s].T[k] = T[k];
         }
         for (int k = 0; k < 12; ++k) Th[12 * s + k] = res[s].T[k];
     }
@@ -5260,26 +5175,18 @@ extern "C" void o3dr_orb_default_params(o3dr_orb_params* p)
     p->channels = 3;
 }
 
-static uint64_t orb_splitmix64(uint64_t x)
-{
-    uint64_t z = x + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 extern "C" int o3dr_orb_pattern(int8_t* out)
 {
     if (!out) return fail(O3DR_ERR_INVALID_ARG, "out is NULL");
     static const int16_t dir[64][2] = {O3DR_ORB_DIRECTIONS};
-    const uint64_t S = orb_splitmix64(O3DR_ORB_PATTERN_SEED);
+    const uint64_t S = splitmix64(O3DR_ORB_PATTERN_SEED);
     uint64_t n = 0;
     int base[256][4];
     for (int i = 0; i < 256;) {
         int v[4];
         for (int k = 0; k < 4; ++k) {
             int sum = 0;
-            for (int d = 0; d < 4; ++d) sum += (int)((orb_splitmix64(S + n++) >> 32) % 7);
+            for (int d = 0; d < 4; ++d) sum += (int)((splitmix64(S + n++) >> 32) % 7);
             v[k] = sum - 12;
         }
         if ((v[0] == v[2] && v[1] == v[3]) || v[0] * v[0] + v[1] * v[1] > 169 || v[2] * v[2] + v[3] * v[3] > 169) continue;

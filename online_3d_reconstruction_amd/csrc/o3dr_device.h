@@ -8,6 +8,7 @@
 #include "../../include/o3dr_dem.h"
 #include "../../include/o3dr_objects.h"
 #include "../../include/o3dr_terrain.h"
+#include "o3dr_rigid_solve.h"
 
 namespace o3dr {
 
@@ -333,7 +334,10 @@ void launch_search_grid(Workspace& ws, hipStream_t s, const o3dr_point* in, int6
 // (ws.grid_max_cells + 1 each); returns the view of it that the kernels below search, good until the next grid is built in
 // ws.  launch_nn_query: idx (+ d2) of n queries (T12 != nullptr: each query is A2(T12, point) first);
 // partial != nullptr: the ICP epilogue (changed against idx_prev, moments about c0) and its fold into rec[kIcpRecord]
-constexpr int kIcpRecord = 18;  // count, sum a (3), sum b (3), sum a b^T (9, row-major), sum d2, changed queries
+constexpr int kIcpRecord = 18;  // the rigid record (o3dr_rigid_solve.h), then sum d2, changed queries
+enum : int { ICP_D2 = kRigidFields, ICP_CHANGED = kRigidFields + 1 };
+static_assert(RIGID_N == 0 && RIGID_SA == 1 && RIGID_SB == 4 && RIGID_SAB == 7 && kRigidFields == 16 && kIcpRecord == kRigidFields + 2,
+              "an ICP record's first 16 fields are the rigid record: rigid_solve reads either");
 SearchGrid launch_nn_grid(Profiler* pf, hipStream_t s, Workspace& ws, const o3dr_point* target, int64_t n, int mm_used, float* box6,
                           float4* cell_lo, float4* cell_hi);
 void launch_nn_query(Profiler* pf, hipStream_t s, const SearchGrid& grid, const o3dr_point* query, int64_t n, const float* T12,
@@ -383,7 +387,6 @@ void launch_keypoints_3d(Profiler* pf, hipStream_t s, const ReprojectArgs& a, co
                          int n_kp, o3dr_point* out);
 // batched rigid fit (segments of at most 2^32-1 points)
 constexpr int kRigidPoints = 256;  // points per workgroup of the sums (ICP's kNnThreads)
-constexpr int kRigidFields = 16;  // count, sum a (3), sum b (3), sum a b^T (9, row-major): the first 16 of kIcpRecord
 struct RigidSeg {
     uint64_t start;     // first point
     uint32_t n;         // points

@@ -65,6 +65,7 @@ namespace o3dr {
 #include "kernels/multigpu.inc"
 #include "kernels/sor.inc"
 #include "kernels/small.inc"
+#include "kernels/rigid_core.inc"
 #include "kernels/nn.inc"
 #include "kernels/mls.inc"
 #include "kernels/cluster.inc"
@@ -1035,7 +1036,7 @@ void launch_nn_query(Profiler* pf, hipStream_t s, const SearchGrid& grid, const 
     a.partial = partial;
     a.n_blocks = (uint32_t)cdiv64(n, kNnThreads);
     k_nn_query<<<a.n_blocks, kNnThreads, 0, s>>>(a);
-    if (partial) k_icp_fold<<<kIcpFields, kIcpFoldThreads, 0, s>>>(partial, a.n_blocks, rec);
+    if (partial) k_icp_fold<<<kIcpFields, kRigidFoldThreads, 0, s>>>(partial, a.n_blocks, rec);
 }
 
 void launch_cloud_finite(Profiler* pf, hipStream_t s, const o3dr_point* in, int64_t n, uint32_t* flag)
@@ -1196,7 +1197,7 @@ void launch_rigid(Profiler* pf, hipStream_t s, const RigidArgs& a, bool residual
         b.rec = a.rec + (size_t)a.n_segs * kRigidFields;
         b.c0 = nullptr;
     }
-    k_rigid_fold<<<dim3(a.n_segs, F), kIcpFoldThreads, 0, s>>>(b, F);
+    k_rigid_fold<<<dim3(a.n_segs, F), kRigidFoldThreads, 0, s>>>(b, F);
 }
 
 // pose chain (kernels/pose_chain.inc): one workgroup, the frames in order
