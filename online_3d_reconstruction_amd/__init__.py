@@ -8,8 +8,8 @@ generates the benchmark inputs of SURVEY.md section 8d, `dist` shards frames ove
 There is no CPU fallback: importing works anywhere, but creating a `Context` without the built
 library or without a GPU raises.
 """
-from ._lib import CHAIN_FRAME, CLUSTER, KNN2, ORB_KEYPOINT, PLANE_DISP_SEGMENT, PLANE_TILE, POINT, RANSAC_RESULT, REFINE_EDGE, REFINE_FRAME, RIGID_RESULT, O3drError, lib_path, load_library  # noqa: F401
-from .api import ClusterInfo, Context, DisparityFilterInfo, GroundInfo, IcpResult, InterpolateInfo, MeshResult, MlsResult, MultiviewFuseInfo, MultiviewInfo, Params, RasterInfo, RefineResult, RigidResult, SegmentInfo, groundSchedule, nearbyFrames, rectifiedQ  # noqa: F401
+from ._lib import CHAIN_FRAME, CLUSTER, CONTOUR_LINE, CONTOUR_SEGMENT, KNN2, ORB_KEYPOINT, PLANE_DISP_SEGMENT, PLANE_TILE, POINT, RANSAC_RESULT, REFINE_EDGE, REFINE_FRAME, RIGID_RESULT, O3drError, lib_path, load_library  # noqa: F401
+from .api import ClusterInfo, ContourInfo, Context, DisparityFilterInfo, GroundInfo, IcpResult, InterpolateInfo, MeshResult, MlsResult, MultiviewFuseInfo, MultiviewInfo, Params, RasterInfo, RefineResult, RigidResult, SegmentInfo, contourPolylines, groundSchedule, nearbyFrames, rectifiedQ  # noqa: F401
 
-__all__ = ["CHAIN_FRAME", "CLUSTER", "ClusterInfo", "Context", "DisparityFilterInfo", "GroundInfo", "IcpResult", "InterpolateInfo", "KNN2", "MeshResult", "MlsResult", "MultiviewFuseInfo", "MultiviewInfo", "ORB_KEYPOINT", "Params", "PLANE_DISP_SEGMENT", "PLANE_TILE", "POINT", "RANSAC_RESULT", "RasterInfo", "REFINE_EDGE", "REFINE_FRAME", "RIGID_RESULT", "RefineResult", "RigidResult", "SegmentInfo", "O3drError",
-           "groundSchedule", "lib_path", "load_library", "nearbyFrames", "rectifiedQ"]
+__all__ = ["CHAIN_FRAME", "CLUSTER", "CONTOUR_LINE", "CONTOUR_SEGMENT", "ClusterInfo", "ContourInfo", "Context", "DisparityFilterInfo", "GroundInfo", "IcpResult", "InterpolateInfo", "KNN2", "MeshResult", "MlsResult", "MultiviewFuseInfo", "MultiviewInfo", "ORB_KEYPOINT", "Params", "PLANE_DISP_SEGMENT", "PLANE_TILE", "POINT", "RANSAC_RESULT", "RasterInfo", "REFINE_EDGE", "REFINE_FRAME", "RIGID_RESULT", "RefineResult", "RigidResult", "SegmentInfo", "O3drError",
+           "contourPolylines", "groundSchedule", "lib_path", "load_library", "nearbyFrames", "rectifiedQ"]

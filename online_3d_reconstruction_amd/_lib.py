@@ -159,6 +159,32 @@ class InterpolateResultStruct(C.Structure):
 INTERPOLATE_MAX_SMOOTH, INTERPOLATE_MAX_LEVELS = 8, 32
 
 
+# include/o3dr_contour.h
+class ContourParamsStruct(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("interval", C.c_double), ("base", C.c_double),
+                ("cell_size", C.c_double), ("cx0", C.c_int32), ("cy0", C.c_int32)]
+
+
+class ContourOutputsStruct(C.Structure):
+    _fields_ = [("segments", C.c_void_p), ("seg_capacity", C.c_int64), ("lines", C.c_void_p), ("line_capacity", C.c_int64),
+                ("vertices", C.c_void_p), ("vertex_capacity", C.c_int64)]
+
+
+class ContourResultStruct(C.Structure):
+    _fields_ = [("n_quads", C.c_int64), ("n_quads_crossed", C.c_int64), ("n_segments", C.c_int64), ("n_lines", C.c_int64),
+                ("n_closed", C.c_int64), ("n_vertices", C.c_int64), ("n_longest", C.c_int64), ("k_lo", C.c_int32),
+                ("k_hi", C.c_int32)]
+
+
+# o3dr_contour_segment (48 bytes) and o3dr_contour_line (32 bytes), as numpy records
+CONTOUR_SEGMENT = np.dtype([("x0", "<f8"), ("y0", "<f8"), ("x1", "<f8"), ("y1", "<f8"), ("k", "<i4"), ("line", "<i4"),
+                            ("rank", "<i4"), ("next", "<i4")])
+CONTOUR_LINE = np.dtype([("head", "<i4"), ("n_segments", "<i4"), ("k", "<i4"), ("closed", "<i4"), ("begin", "<i8"),
+                         ("level", "<f8")])
+assert CONTOUR_SEGMENT.itemsize == 48 and CONTOUR_LINE.itemsize == 32 and C.sizeof(ContourResultStruct) == 64
+CONTOUR_MAX_SEGMENTS = 1 << 28
+
+
 # include/o3dr_objects.h
 class ClusterParamsStruct(C.Structure):
     _fields_ = [("tolerance", C.c_double), ("min_size", C.c_int32), ("max_size", C.c_int32)]
@@ -414,6 +440,10 @@ SYMBOLS = [
     ("o3dr_raster_interpolate", C.c_int, [_vp, _vp, C.POINTER(InterpolateParamsStruct), C.POINTER(InterpolateOutputsStruct),
                                           C.POINTER(InterpolateResultStruct), _i32]),
     ("o3dr_raster_sample", C.c_int, [_vp, _vp, _i64, C.c_double, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _pi64, _i32]),
+    ("o3dr_contour_default_params", None, [C.POINTER(ContourParamsStruct)]),
+    ("o3dr_raster_contours_count", C.c_int, [_vp, _vp, C.POINTER(ContourParamsStruct), _pi64, _i32]),
+    ("o3dr_raster_contours", C.c_int, [_vp, _vp, C.POINTER(ContourParamsStruct), C.POINTER(ContourOutputsStruct),
+                                       C.POINTER(ContourResultStruct), _i32]),
     ("o3dr_cluster_default_params", None, [C.POINTER(ClusterParamsStruct)]),
     ("o3dr_cluster_euclidean", C.c_int, [_vp, _vp, _i64, C.POINTER(ClusterParamsStruct), C.POINTER(ClusterOutputsStruct), _vp, _i64,
                                          C.POINTER(_i64), C.POINTER(ClusterResultStruct), _i32]),

@@ -125,6 +125,36 @@ class InterpolateInfo:
 
 
 @dataclass
+class ContourInfo:
+    """o3dr_raster_contours' record (include/o3dr_contour.h): the quads without a NaN corner and those a level
+    crosses, the segments, the lines and how many of them are closed, the polyline vertices (n_segments + n_lines), the
+    segments of the longest line, the least and the greatest level index emitted (both 0 when nothing is)."""
+    n_quads: int
+    n_quads_crossed: int
+    n_segments: int
+    n_lines: int
+    n_closed: int
+    n_vertices: int
+    n_longest: int
+    k_lo: int
+    k_hi: int
+
+
+def contourPolylines(lines, vertices):
+    """contourRaster's lines and vertices as a list of float64 [n_segments + 1, 2] arrays, one per line in line order (a
+    closed line's last vertex is its first).  Host only: CUDA tensors are copied back first."""
+    if _is_torch(lines):
+        lines = lines.cpu().numpy()
+    if _is_torch(vertices):
+        vertices = vertices.cpu().numpy()
+    lines = np.ascontiguousarray(lines)
+    if lines.dtype != L.CONTOUR_LINE:
+        lines = lines.view(L.CONTOUR_LINE).reshape(-1)
+    vertices = np.asarray(vertices, np.float64).reshape(-1, 2)
+    return [vertices[int(b):int(b) + int(n) + 1].copy() for b, n in zip(lines["begin"], lines["n_segments"])]
+
+
+@dataclass
 class ClusterInfo:
     """o3dr_cluster_euclidean's counters (include/o3dr_objects.h): the components of the links' closure, those kept as
     clusters and those rejected as too small / too large, the points in clusters and in rejected components, the size of
@@ -1546,6 +1576,54 @@ class Context:
             ret += (value,)
         if return_info:
             ret += (tuple(int(v) for v in counts),)
+        return ret[0] if len(ret) == 1 else ret
+
+    # -- contour lines of a raster (this build's own) ---------------------------------------------
+    def contourRaster(self, raster, interval, base=0.0, cell_size=1.0, origin=(0, 0), return_lines=False, return_vertices=False,
+                      return_info=False):
+        """The contour lines of a float32 [height, width] raster at the levels base + k * interval: marching squares over
+        the quads of four cell centres, the segments linked into lines and ranked along them (contract: include/o3dr_dem.h
+        "contour lines", DESIGN.md "Contour lines").  A NaN is a hole: lines end beside it.  Element [r, c] is the value at
+        the centre of cell (origin[0] + c, origin[1] + r) of cell_size, as rasterizeMap and groundFilter lay their rasters
+        out with origin = bounds[:2].  A numpy array gives numpy records, a torch CUDA tensor gives CUDA tensors without
+        leaving HBM (the same bytes: `.cpu().numpy().view(CONTOUR_SEGMENT)`).
+        -> segments CONTOUR_SEGMENT [S] (torch: uint8 [S, 48])[, lines CONTOUR_LINE [n] (uint8 [n, 32])][, vertices float64
+        [S + n, 2]: contourPolylines(lines, vertices) splits them][, ContourInfo]"""
+        if _is_torch(raster):
+            assert _dtype_name(raster) == "float32" and raster.dim() == 2
+            raster = raster.contiguous()
+        else:
+            raster = np.ascontiguousarray(raster, np.float32)
+            assert raster.ndim == 2
+        H, W = (int(v) for v in raster.shape)
+        p_in, mem, _k = _ptr(raster)
+        prm = L.ContourParamsStruct()
+        self._lib.o3dr_contour_default_params(C.byref(prm))
+        prm.width, prm.height, prm.interval, prm.base, prm.cell_size = W, H, float(interval), float(base), float(cell_size)
+        prm.cx0, prm.cy0 = int(origin[0]), int(origin[1])
+        count = C.c_int64(0)
+        if mem == L.MEM_DEVICE:  # (the count call reads the raster before any output is made)
+            self._order_after_torch()
+        L.check(self._lib.o3dr_raster_contours_count(self._h, p_in if W * H else None, C.byref(prm), C.byref(count), mem))
+        S = int(count.value)  # n_lines <= S and n_vertices <= 2 S
+        if S > L.CONTOUR_MAX_SEGMENTS:
+            raise L.O3drError(L.ERR_CAPACITY, "the raster has more than 2^28 contour segments at this interval")
+        dev = mem == L.MEM_DEVICE
+        seg, lin, ver = self._empty_like(raster, ((S, 48), np.uint8) if dev else (S, L.CONTOUR_SEGMENT),
+                                         (((S, 32), np.uint8) if dev else (S, L.CONTOUR_LINE)) if return_lines else None,
+                                         ((2 * S, 2), np.float64) if return_vertices else None)
+        addr = lambda t: _addr(t) if t is not None and S else None  # noqa: E731
+        outs = L.ContourOutputsStruct(addr(seg), S, addr(lin), S, addr(ver), 2 * S)
+        res = L.ContourResultStruct()
+        L.check(self._lib.o3dr_raster_contours(self._h, p_in if W * H else None, C.byref(prm), C.byref(outs), C.byref(res), mem))
+        ret = (seg[:int(res.n_segments)],)
+        if return_lines:
+            ret += (lin[:int(res.n_lines)],)
+        if return_vertices:
+            ret += (ver[:int(res.n_vertices)],)
+        if return_info:
+            ret += (ContourInfo(int(res.n_quads), int(res.n_quads_crossed), int(res.n_segments), int(res.n_lines), int(res.n_closed),
+                                int(res.n_vertices), int(res.n_longest), int(res.k_lo), int(res.k_hi)),)
         return ret[0] if len(ret) == 1 else ret
 
     # -- Euclidean clustering: object labels and per-object records (this build's own; SURVEY section 2 row 16) ----------

@@ -4003,6 +4003,142 @@ extern "C" int o3dr_raster_sample(o3dr_ctx* c, const o3dr_point* cloud, int64_t 
 }
 
 // -------------------------------------------------------------------------------------------------
+// contour lines (kernels/contour.inc; contract: include/o3dr_contour.h; DESIGN.md "Contour lines")
+// -------------------------------------------------------------------------------------------------
+extern "C" void o3dr_contour_default_params(o3dr_contour_params* p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof *p);  // the raster's shape and the interval: no usable default
+    p->cell_size = 1.0;
+}
+
+struct ContourFlags {
+    alignas(64) uint32_t counters[kContourCounterWords];  // ContourArgs::counters
+    alignas(64) uint32_t flags[2];                        // ContourArgs::flags
+};
+
+// The checks of both entry points, the staged raster, the count pass and its read-back: a.n_seg is not set, *n_seg is the
+// 64-bit sum, h the counters.
+static int contour_count(o3dr_ctx* c, const float* raster, const o3dr_contour_params* p, int32_t mem, ContourArgs& a, ContourFlags** f,
+                         ContourFlags& h, int64_t* n_seg)
+{
+    if (mem != O3DR_MEM_HOST && mem != O3DR_MEM_DEVICE) return fail(O3DR_ERR_INVALID_ARG, "bad mem kind");
+    if (p->width < 1 || p->height < 1) return fail(O3DR_ERR_INVALID_ARG, "the raster needs width, height >= 1");
+    if (!(std::isfinite(p->interval) && std::isfinite(p->base) && p->interval > 0.0))
+        return fail(O3DR_ERR_INVALID_ARG, "interval must be finite and > 0, base finite");
+    if (!(std::isfinite(p->cell_size) && p->cell_size > 0.0)) return fail(O3DR_ERR_INVALID_ARG, "cell_size must be finite and > 0");
+    const int64_t cells = (int64_t)p->width * p->height;
+    if (cells > (int64_t)O3DR_RASTER_MAX_CELLS) return fail(O3DR_ERR_INVALID_ARG, "the raster holds more than 2^28 cells");
+    c->place_ub = -1;
+    memset(&a, 0, sizeof a);
+    a.W = p->width, a.H = p->height, a.cx0 = p->cx0, a.cy0 = p->cy0;
+    a.interval = p->interval, a.base = p->base, a.cell_size = p->cell_size;
+    const int64_t quads = (int64_t)(p->width - 1) * (p->height - 1);
+    a.n_quads = (uint32_t)quads;
+    CHK(op_flags(c, f));
+    const void* raster_d;
+    CHK(stage_in(c, c->op[o3dr_ctx::OP_IN], raster, (size_t)cells * sizeof(float), mem, &raster_d));
+    a.raster = (const float*)raster_d;
+    CHK(carve(c, c->op[o3dr_ctx::OP_WORK], [&](Carve& w) {
+        w.take(a.kc, (size_t)cells);
+        w.take(a.off, (size_t)std::max<int64_t>(quads, 1));
+        w.take(a.part, (size_t)kContourMaxBlocks * kPartWords);
+        w.take(a.scan_partial, (size_t)contour_scan_words(quads));
+    }));
+    a.counters = (*f)->counters, a.flags = (*f)->flags;
+    launch_contour_count(&c->prof, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&h, *f, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (h.flags[0]) return fail(O3DR_ERR_INVALID_ARG, "the raster has an infinite value (a hole is a NaN)");
+    if (h.flags[1]) return fail(O3DR_ERR_INVALID_ARG, "a level index of the raster lies outside +-2^30 (the levels are too fine for its values)");
+    *n_seg = (int64_t)(((uint64_t)h.counters[13] << 32) | h.counters[12]);
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_raster_contours_count(o3dr_ctx* c, const float* raster, const o3dr_contour_params* p, int64_t* n_segments, int32_t mem)
+{
+    if (n_segments) *n_segments = 0;
+    const int rc = entered(c, [&] {
+        if (!raster || !p || !n_segments) return fail(O3DR_ERR_INVALID_ARG, "raster / params / n_segments is NULL");
+        ContourArgs a;
+        ContourFlags *f, h;
+        return contour_count(c, raster, p, mem, a, &f, h, n_segments);
+    });
+    if (rc != O3DR_OK && n_segments) *n_segments = 0;
+    return rc;
+}
+
+static int raster_contours(o3dr_ctx* c, const float* raster, const o3dr_contour_params* p, const o3dr_contour_outputs* out, Outputs& outs,
+                           o3dr_contour_result* res, int32_t mem)
+{
+    if (!raster || !p || !out || !res) return fail(O3DR_ERR_INVALID_ARG, "raster / params / outputs / result is NULL");
+    ContourArgs a;
+    ContourFlags *f, h;
+    int64_t S = 0;
+    CHK(contour_count(c, raster, p, mem, a, &f, h, &S));
+    res->n_quads = h.counters[0], res->n_quads_crossed = h.counters[1], res->n_segments = S;
+    if (S > 0) res->k_lo = (int32_t)(h.counters[2] ^ 0x80000000u), res->k_hi = (int32_t)(h.counters[3] ^ 0x80000000u);
+    if (S > (int64_t)O3DR_CONTOUR_MAX_SEGMENTS) return fail(O3DR_ERR_CAPACITY, "the raster has more than 2^28 contour segments at this interval");
+    ContourVertex* vertices = (ContourVertex*)out->vertices;
+    if (S == 0) {
+        outs.set_count(out->segments, 0), outs.set_count(out->lines, 0), outs.set_count(vertices, 0);
+        return O3DR_OK;
+    }
+    a.n_seg = (uint32_t)S;
+    CHK(carve(c, c->op[o3dr_ctx::OP_LATE], [&](Carve& w) {
+        w.take(a.xy, (size_t)S);
+        w.take(a.kn, (size_t)S);
+        w.take(a.parent, (size_t)S);
+        w.take(a.prev, (size_t)S);
+        w.take(a.head, (size_t)S);
+        w.take(a.cnt, (size_t)S);
+        w.take(a.num, (size_t)S);
+        w.take(a.beg, (size_t)S);
+        w.take(a.jump[0], (size_t)S);
+        w.take(a.jump[1], (size_t)S);
+        w.take(a.part, (size_t)contour_blocks(S) * kPartWords);
+        w.take(a.scan_partial, (size_t)contour_scan_words(S));
+    }));
+    launch_contour_lines(&c->prof, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&h, f, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const int64_t n_lines = h.counters[8], n_vertices = h.counters[9];
+    res->n_lines = n_lines, res->n_closed = h.counters[4], res->n_longest = h.counters[5], res->n_vertices = n_vertices;
+    if ((out->segments && out->seg_capacity < S) || (out->lines && out->line_capacity < n_lines) ||
+        (vertices && out->vertex_capacity < n_vertices))
+        return fail(O3DR_ERR_CAPACITY, "seg_capacity / line_capacity / vertex_capacity is below what the raster's contours need");
+    outs.set_count(out->segments, S), outs.set_count(out->lines, n_lines), outs.set_count(vertices, n_vertices);
+    CHK(outs.stage(c));
+    a.seg_out = outs.dev(out->segments), a.lines_out = outs.dev(out->lines), a.vertices = outs.dev(vertices);
+    if (a.seg_out || a.lines_out || a.vertices) launch_contour_outputs(&c->prof, c->stream, a);
+    HIPCHK(hipGetLastError());
+    CHK(outs.copy_back(c));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return O3DR_OK;
+}
+
+extern "C" int o3dr_raster_contours(o3dr_ctx* c, const float* raster, const o3dr_contour_params* p, const o3dr_contour_outputs* out,
+                                    o3dr_contour_result* res, int32_t mem)
+{
+    if (res) memset(res, 0, sizeof *res);
+    Outputs outs{mem};
+    const int64_t bound = O3DR_CONTOUR_MAX_SEGMENTS;  // (a capacity above what any call writes is as good as that)
+    if (out) {
+        outs.add(out->segments, std::min(out->seg_capacity, bound));
+        outs.add(out->lines, std::min(out->line_capacity, bound));
+        outs.add((ContourVertex*)out->vertices, std::min(out->vertex_capacity, 2 * bound));
+    }
+    const int rc = entered(c, [&] { return raster_contours(c, raster, p, out, outs, res, mem); });
+    if (rc != O3DR_OK && rc != O3DR_ERR_CAPACITY) {  // host outputs and the result zeroed on an error
+        if (res) memset(res, 0, sizeof *res);
+        outs.zero();
+    }
+    return rc;
+}
+
+// -------------------------------------------------------------------------------------------------
 // Euclidean clustering: object labels and per-object records (kernels/cluster.inc; contract: include/o3dr_objects.h;
 // DESIGN.md "Euclidean clustering")
 // -------------------------------------------------------------------------------------------------

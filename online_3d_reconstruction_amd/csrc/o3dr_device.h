@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/o3dr.h"
+#include "../../include/o3dr_contour.h"
 #include "../../include/o3dr_dem.h"
 #include "../../include/o3dr_objects.h"
 #include "../../include/o3dr_terrain.h"
@@ -695,6 +696,57 @@ struct SampleArgs {
     uint32_t* counters;           // 4 words: inside, outside, on a NaN cell, -
 };
 void launch_raster_sample(Profiler* pf, hipStream_t s, const SampleArgs& a);
+// contour lines (kernels/contour.inc; contract: include/o3dr_contour.h).  Every array is the call's own scratch
+// but lines_out / seg_out / vertices.  The first block is what the count pass needs; the second is sized by the segments
+// counted (n_seg).
+struct ContourVertex {
+    double x, y;
+};
+struct ContourArgs {
+    const float* raster;          // W * H
+    int32_t W, H, cx0, cy0;
+    double interval, base, cell_size;
+    uint32_t n_quads;             // (W - 1) * (H - 1)
+    int32_t* kc;                  // W * H: K(z) of every cell, kContourHole on a NaN
+    uint32_t* off;                // n_quads: a quad's segments -> its first segment (exclusive scan)
+    uint32_t* part;               // contour_blocks(max(cells, n_quads, n_seg)) * kPartWords
+    uint32_t* scan_partial;       // contour_scan_words(max(n_quads, n_seg))
+    uint32_t* counters;           // kContourCounterWords: n_quads n_crossed k_lo k_hi (order-preserving words) | n_closed
+                                  //   n_longest - - | n_lines n_vertices (the scans' totals) - - | the segments (low, high word) - -
+    uint32_t* flags;              // 2 words: an infinite value, a level index outside +-2^30
+    uint32_t n_seg;
+    double4* xy;                  // n_seg: x0 y0 x1 y1
+    int2* kn;                     // n_seg: k, next
+    int* parent;                  // n_seg: the union-find, then every segment's root = its line's lowest index
+    int* prev;                    // n_seg: the inverse of next, -1
+    int* head;                    // n_seg, at a root: the line's head
+    uint32_t* cnt;                // n_seg, at a root: the line's segments
+    uint32_t* num;                // n_seg: 1 at a root -> the line's number (exclusive scan)
+    uint32_t* beg;                // n_seg: n_segments + 1 at a root -> the line's begin (exclusive scan)
+    int2* jump[2];                // n_seg each: (the predecessor 2^round steps back or -1, the steps taken): the rank
+    o3dr_contour_segment* seg_out;  // n_seg or nullptr
+    o3dr_contour_line* lines_out;   // n_lines or nullptr
+    ContourVertex* vertices;        // n_seg + n_lines or nullptr
+};
+constexpr int kContourThreads = 256;      // quads (cells, segments) per workgroup turn
+constexpr int kContourMaxBlocks = 1024;   // workgroups of a launch over cells or quads at most (the others by stride)
+constexpr int kContourCounterWords = 16;
+constexpr int32_t kContourHole = INT32_MIN;
+constexpr int32_t kContourMaxLevel = 1 << 30;
+inline int64_t contour_blocks(int64_t n) { return (n + kContourThreads - 1) / kContourThreads; }
+inline int64_t contour_scan_words(int64_t n) { return n / 4096 + 16; }
+inline int contour_rank_rounds(uint32_t n_seg)  // the bit length of n_seg: 2^rounds > every rank
+{
+    int r = 0;
+    while ((n_seg >> r) != 0) ++r;
+    return r;
+}
+// launch_contour_count: flags cleared, K per cell, the quads' counts with the result's first counters and the 64-bit
+// sum, the exclusive scan of the counts.  launch_contour_lines (n_seg > 0, after the sum was read back): the segments,
+// links, components, heads, sizes, numbers, begins and ranks.  launch_contour_outputs: the caller's arrays.
+void launch_contour_count(Profiler* pf, hipStream_t s, const ContourArgs& a);
+void launch_contour_lines(Profiler* pf, hipStream_t s, const ContourArgs& a);
+void launch_contour_outputs(Profiler* pf, hipStream_t s, const ContourArgs& a);
 // Euclidean clustering (kernels/cluster.inc; contract: include/o3dr_objects.h).  The grid is launch_nn_grid's; every array
 // below it is the call's own scratch but the outputs.
 struct ClusterArgs {

@@ -36,6 +36,7 @@
 //   raster       the merged map as images: one point per XY cell, separable hole fill, the output images, shaded relief
 //   ground       bare-earth ground filter on the raster's cells: sliding window minima / maxima, DTM, height above ground
 //   interpolate  hole-free rasters: pull-push over an image pyramid with Jacobi sweeps in LDS on the way down; a raster read at points
+//   contour      contour lines of a raster: K per cell, counted and emitted marching-squares segments, union-find lines, pointer-jumped ranks
 //   cluster      Euclidean clustering: radius walk + union-find, sizes, numbering, per-cluster records, indices
 //   match        Hamming 2-NN descriptor matching, index-aligned 3-D keypoints, the batched rigid fit
 //   orb          ORB features: grey pyramid, FAST score + box sums, candidates, exact selection, steered BRIEF
@@ -75,6 +76,7 @@ namespace o3dr {
 #include "kernels/raster.inc"
 #include "kernels/ground.inc"
 #include "kernels/interpolate.inc"
+#include "kernels/contour.inc"
 #include "kernels/match.inc"
 #include "kernels/plane_disparity.inc"
 #include "kernels/orb.inc"
@@ -1355,6 +1357,50 @@ void launch_raster_sample(Profiler* pf, hipStream_t s, const SampleArgs& a)
     const int g = (int)raster_winner_parts(a.f.n);
     if (g > 0) k_raster_sample<<<g, kInterpThreads, 0, s>>>(a);
     k_fold4_u32<<<1, kFoldThreads, 0, s>>>(a.f.part, g, 0, 2, 2, 2, 2, a.counters);
+}
+
+// contour lines (kernels/contour.inc)
+static inline unsigned contour_grid(int64_t n)
+{
+    const int64_t b = contour_blocks(n);
+    return (unsigned)(b < kContourMaxBlocks ? b : kContourMaxBlocks);
+}
+void launch_contour_count(Profiler* pf, hipStream_t s, const ContourArgs& a)
+{
+    ProfScope ps(pf, O3DR_K_OTHER, s);
+    (void)hipMemsetAsync(a.flags, 0, 2 * sizeof(uint32_t), s);
+    (void)hipMemsetAsync(a.counters, 0, kContourCounterWords * sizeof(uint32_t), s);
+    k_contour_levels<<<contour_grid((int64_t)a.W * a.H), kContourThreads, 0, s>>>(a);
+    if (a.n_quads == 0) return;
+    const unsigned g = contour_grid(a.n_quads);
+    k_contour_count<<<g, kContourThreads, 0, s>>>(a);
+    k_fold4_u32<<<1, kFoldThreads, 0, s>>>(a.part, (int)g, 0, 2, 2, 0, 1, a.counters);
+    launch_scan(s, a.off, a.n_quads, a.n_quads, 1, nullptr, nullptr, a.scan_partial);
+}
+
+void launch_contour_lines(Profiler* pf, hipStream_t s, const ContourArgs& a)
+{
+    ProfScope ps(pf, O3DR_K_OTHER, s);
+    const int g = (int)contour_blocks(a.n_seg);
+    k_contour_emit<<<contour_grid(a.n_quads), kContourThreads, 0, s>>>(a);
+    (void)hipMemsetAsync(a.prev, 0xff, (size_t)a.n_seg * sizeof(int), s);
+    (void)hipMemsetAsync(a.head, 0xff, (size_t)a.n_seg * sizeof(int), s);
+    (void)hipMemsetAsync(a.cnt, 0, (size_t)a.n_seg * sizeof(uint32_t), s);
+    k_cluster_init<<<g, kClusterThreads, 0, s>>>(a.parent, a.n_seg);
+    k_contour_link<<<g, kContourThreads, 0, s>>>(a);
+    k_contour_flatten<<<g, kContourThreads, 0, s>>>(a);
+    k_contour_flags<<<g, kContourThreads, 0, s>>>(a);
+    k_fold4_u32<<<1, kFoldThreads, 0, s>>>(a.part, g, 0, 2, 1, 2, 2, a.counters + 4);
+    launch_scan(s, a.num, a.n_seg, a.n_seg, 1, a.counters + 8, nullptr, a.scan_partial);
+    launch_scan(s, a.beg, a.n_seg, a.n_seg, 1, a.counters + 9, nullptr, a.scan_partial);
+    const int rounds = contour_rank_rounds(a.n_seg);
+    for (int r = 0; r < rounds; ++r) k_contour_jump<<<g, kContourThreads, 0, s>>>(a.jump[r & 1], a.jump[(r + 1) & 1], a.n_seg);
+}
+
+void launch_contour_outputs(Profiler* pf, hipStream_t s, const ContourArgs& a)
+{
+    ProfScope ps(pf, O3DR_K_OTHER, s);
+    k_contour_outputs<<<(int)contour_blocks(a.n_seg), kContourThreads, 0, s>>>(a, a.jump[contour_rank_rounds(a.n_seg) & 1]);
 }
 
 // Euclidean clustering (kernels/cluster.inc) over the grid launch_nn_grid left in ws.sor_*

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/o3dr.h"
+#include "../../include/o3dr_contour.h"
 #include "../../include/o3dr_dem.h"
 #include "../../include/o3dr_objects.h"
 #include "../../include/o3dr_terrain.h"
@@ -151,6 +152,11 @@ public:
     bool cluster_tolerance_set = false;  // clusters_<file>.txt; --cluster_tolerance t (metres, required there),
     double cluster_tolerance = 0.0;  // --cluster_min_size n, --cluster_max_size n; parsed and ignored without --cluster_cloud
     int cluster_min_size = 1, cluster_max_size = INT32_MAX;
+    bool contours = false;           // --contours file.ply: o3dr_raster_contours of one PLY's terrain model -> contours_<file>.geojson;
+    bool contour_interval_set = false;  // --contour_interval m (required there), --contour_base b, --contour_surface dtm|dsm,
+    double contour_interval = 0.0, contour_base = 0.0;  // --contour_min_segments n; parsed and ignored without --contours
+    std::string contour_surface = "dtm";
+    int contour_min_segments = 1;
     int device_id = 0;
     int n_gpus = 1;                 // --gpus N: frames sharded over devices device_id .. device_id+N-1, one host thread and
                                     // one context each, merged through o3dr_merge_partitioned (RCCL)
@@ -269,6 +275,7 @@ private:
     void run_orthophoto();                          // --orthophoto
     void run_ground_filter();                       // --ground_filter
     void run_cluster_cloud();                       // --cluster_cloud
+    void run_contours();                            // --contours
     // the map's rasters of a host cloud (o3dr_raster_extent, o3dr_rasterize_map with the --ortho_* flags) as PNGs, rows in
     // descending cy (north up); shade_path is written with --ortho_light only.  Prints the box, the counts and the call time.
     void write_map_rasters(o3dr_ctx* c, const PointCloud& cloud, const std::string& ortho_path, const std::string& height_path,

@@ -528,6 +528,16 @@ void Pose::printUsage()
             "                     per cluster: number first size lo[3] hi[3] centroid[3]; prints the counters, the first ten\n"
             "                     records and the call time; objects_<file> of --ground_filter is the intended input; elsewhere\n"
             "                     the --cluster_* flags are parsed and ignored - the flags and the file names are this build's own)\n"
+            "./pose --contours file.ply --contour_interval m [--contour_base b] [--voxel_size m] [--contour_surface dtm|dsm]\n"
+            "       [--contour_min_segments n]\n"
+            "                     (contour lines at the elevations b + k m (b default 0) of the terrain model on the XY cells of\n"
+            "                     --voxel_size: dtm (the default) is the ground filter's interpolated terrain model, --ground_filter\n"
+            "                     --ground_interpolate at their defaults; dsm is the raster of every cell's highest point as it is,\n"
+            "                     where lines end at holes; writes contours_<file>.geojson next to the source, a FeatureCollection\n"
+            "                     with one LineString per line of at least n segments (default 1), in line order, with the\n"
+            "                     properties line, level (k), elevation, closed and segments; prints the box, the level range, the\n"
+            "                     counts and the call time; elsewhere the --contour_* flags are parsed and ignored - the flags and\n"
+            "                     the file name are this build's own)\n"
             "./pose --find_features image.png [--orb_n_features n] [--orb_levels n] [--orb_scale s] [--orb_fast_threshold t]\n"
             "                     (ORB keypoints of one image: prints the count per level and writes one \"x y\" per line as\n"
             "                     <image>.keypoints.txt, the --keypoints_dir format - the flags and the file name are this build's own)\n"
@@ -647,6 +657,11 @@ int Pose::parseCmdArgs(int argc, char** argv)
         else if (a == "--cluster_tolerance") { cluster_tolerance = atof(need(i)); cluster_tolerance_set = true; }
         else if (a == "--cluster_min_size") cluster_min_size = atoi(need(i));
         else if (a == "--cluster_max_size") cluster_max_size = atoi(need(i));
+        else if (a == "--contours") { files(i, "file.ply", read_PLY_filename0); contours = true; }
+        else if (a == "--contour_interval") { contour_interval = atof(need(i)); contour_interval_set = true; }
+        else if (a == "--contour_base") contour_base = atof(need(i));
+        else if (a == "--contour_surface") contour_surface = need(i);
+        else if (a == "--contour_min_segments") contour_min_segments = atoi(need(i));
         else if (a == "--ortho_select") ortho_select = need(i);
         else if (a == "--ortho_fill_radius") ortho_fill_radius = atoi(need(i));
         else if (a == "--ortho_light") {
@@ -810,6 +825,14 @@ int Pose::parseCmdArgs(int argc, char** argv)
         if (!(isfinite(cluster_tolerance) && cluster_tolerance > 0.0)) throw runtime_error("--cluster_tolerance must be finite and > 0");
         if (cluster_min_size < 1) throw runtime_error("--cluster_min_size must be >= 1");
         if (cluster_max_size < cluster_min_size) throw runtime_error("--cluster_max_size must be >= --cluster_min_size");
+    }
+    if (contours) {
+        if (!ifstream(read_PLY_filename0)) throw runtime_error("could not read " + read_PLY_filename0);
+        if (!contour_interval_set) throw runtime_error("--contours needs --contour_interval m (metres)");
+        if (!(isfinite(contour_interval) && contour_interval > 0.0)) throw runtime_error("--contour_interval must be finite and > 0");
+        if (!isfinite(contour_base)) throw runtime_error("--contour_base must be finite");
+        if (contour_surface != "dtm" && contour_surface != "dsm") throw runtime_error("--contour_surface must be dtm or dsm");
+        if (contour_min_segments < 1) throw runtime_error("--contour_min_segments must be >= 1");
     }
     if (run3d_reconstruction && gpu_keypoints) batched_path_only("--gpu_keypoints", true);
     if (run3d_reconstruction && gpu_disparity) {
@@ -1208,6 +1231,89 @@ void Pose::run_cluster_cloud()
     cerr << "Saved " << K << " cluster records to " << txt_path << endl;
 }
 
+// --contours: the contour lines of one PLY's terrain model (o3dr_raster_contours; contract: include/o3dr_contour.h), written
+// as contours_<file>.geojson next to the source.  dtm: the ground filter's DTM at its defaults, interpolated
+// (o3dr_ground_filter, o3dr_raster_interpolate); dsm: the raster of every cell's highest point (o3dr_rasterize_map).
+void Pose::run_contours()
+{
+    PointCloud::Ptr cloud = read_PLY_File(read_PLY_filename0);
+    const int64_t n = (int64_t)cloud->points.size();
+    o3dr_ctx* c = ctx_for_this_thread();
+    o3dr_contour_params prm;
+    o3dr_contour_default_params(&prm);
+    prm.interval = contour_interval, prm.base = contour_base, prm.cell_size = voxel_size;
+    chk(o3dr_raster_extent(c, cloud->points.data(), n, voxel_size, &prm.cx0, &prm.cy0, &prm.width, &prm.height, O3DR_MEM_HOST),
+        "o3dr_raster_extent");
+    const size_t cells = (size_t)prm.width * (size_t)prm.height;
+    vector<float> surface(cells);
+    if (contour_surface == "dsm") {
+        o3dr_raster_params rp;
+        o3dr_raster_default_params(&rp);
+        rp.cell_size = voxel_size, rp.select = O3DR_RASTER_TOP;
+        rp.cx0 = prm.cx0, rp.cy0 = prm.cy0, rp.width = prm.width, rp.height = prm.height;
+        vector<uint8_t> color(cells * 3);
+        o3dr_raster_outputs out = {surface.data(), color.data(), nullptr, nullptr, nullptr};
+        o3dr_raster_result res;
+        chk(o3dr_rasterize_map(c, cloud->points.data(), n, &rp, &out, &res, O3DR_MEM_HOST), "o3dr_rasterize_map");
+    } else {
+        o3dr_ground_params gp;
+        o3dr_ground_default_params(&gp);
+        gp.cell_size = voxel_size;
+        gp.cx0 = prm.cx0, gp.cy0 = prm.cy0, gp.width = prm.width, gp.height = prm.height;
+        vector<uint8_t> ground((size_t)n);
+        vector<float> dtm(cells);
+        o3dr_ground_outputs out = {ground.data(), nullptr, dtm.data(), nullptr};
+        o3dr_ground_result res;
+        chk(o3dr_ground_filter(c, cloud->points.data(), n, &gp, &out, &res, O3DR_MEM_HOST), "o3dr_ground_filter");
+        o3dr_interpolate_params ip;
+        o3dr_interpolate_default_params(&ip);
+        ip.width = prm.width, ip.height = prm.height;
+        o3dr_interpolate_outputs io = {surface.data(), nullptr};
+        o3dr_interpolate_result dem;
+        chk(o3dr_raster_interpolate(c, dtm.data(), &ip, &io, &dem, O3DR_MEM_HOST), "o3dr_raster_interpolate");
+    }
+    const auto t0 = chrono::steady_clock::now();
+    int64_t S = 0;
+    chk(o3dr_raster_contours_count(c, surface.data(), &prm, &S, O3DR_MEM_HOST), "o3dr_raster_contours_count");
+    if (S > (int64_t)O3DR_CONTOUR_MAX_SEGMENTS) throw runtime_error("more than 2^28 contour segments: --contour_interval is too small for this surface");
+    vector<o3dr_contour_line> lines((size_t)S);  // n_lines <= n_segments, n_vertices <= 2 n_segments
+    vector<double> vertices((size_t)S * 4);
+    o3dr_contour_outputs out = {nullptr, 0, S ? lines.data() : nullptr, S, S ? vertices.data() : nullptr, 2 * S};
+    o3dr_contour_result res;
+    chk(o3dr_raster_contours(c, surface.data(), &prm, &out, &res, O3DR_MEM_HOST), "o3dr_raster_contours");
+    const double ms = chrono::duration<double, milli>(chrono::steady_clock::now() - t0).count();
+    const string path = next_to(read_PLY_filename0, "contours_", ".geojson");
+    ofstream js(path);
+    char num[96];
+    int64_t written = 0;
+    js << "{\"type\": \"FeatureCollection\", \"features\": [";
+    for (int64_t l = 0; l < res.n_lines; ++l) {
+        const o3dr_contour_line& ln = lines[(size_t)l];
+        if (ln.n_segments < contour_min_segments) continue;
+        snprintf(num, sizeof num, "%.17g", ln.level);
+        js << (written++ ? ",\n" : "\n") << "{\"type\": \"Feature\", \"properties\": {\"line\": " << l << ", \"level\": " << ln.k << ", \"elevation\": " << num
+           << ", \"closed\": " << ln.closed << ", \"segments\": " << ln.n_segments << "}, \"geometry\": {\"type\": \"LineString\", \"coordinates\": [";
+        for (int64_t v = ln.begin; v <= ln.begin + ln.n_segments; ++v) {
+            snprintf(num, sizeof num, "[%.17g, %.17g]", vertices[(size_t)v * 2], vertices[(size_t)v * 2 + 1]);
+            js << (v > ln.begin ? ", " : "") << num;
+        }
+        js << "]}}";
+    }
+    js << "\n]}\n";
+    js.close();
+    if (!js) throw runtime_error("could not write " + path);
+    char line[128];
+    cout << "points in " << n << ", surface " << contour_surface << endl;
+    cout << "box cx0 " << prm.cx0 << " cy0 " << prm.cy0 << " width " << prm.width << " height " << prm.height << endl;
+    snprintf(line, sizeof line, "levels k %d .. %d (interval %.17g base %.17g)", res.k_lo, res.k_hi, contour_interval, contour_base);
+    cout << line << endl;
+    cout << "quads " << res.n_quads << " (crossed " << res.n_quads_crossed << "), segments " << res.n_segments << ", lines " << res.n_lines
+         << " (closed " << res.n_closed << ", longest " << res.n_longest << " segments), vertices " << res.n_vertices << endl;
+    snprintf(line, sizeof line, "contour time %.3f ms", ms);
+    cout << line << endl;
+    cerr << "Saved " << written << " contour lines to " << path << endl;
+}
+
 o3dr_orb_params Pose::orb_params() const
 {
     o3dr_orb_params p;
@@ -1560,6 +1666,10 @@ Pose::Pose(int argc, char* argv[])
     }
     if (cluster_cloud) {
         run_cluster_cloud();
+        return;
+    }
+    if (contours) {
+        run_contours();
         return;
     }
     if (!find_features_png.empty()) {
