@@ -641,7 +641,11 @@ void launch_disp_variance(Profiler* pf, hipStream_t s, const uint8_t* disp, int6
     ProfScope ps(pf, O3DR_K_OTHER, s);
     (void)hipMemsetAsync(hist, 0, sizeof(unsigned long long) * 256 * (size_t)frames, s);
     const int roi_rows = rows - 2 * bb;
-    if (roi_rows > 0) k_disp_hist<<<dim3(roi_rows, frames), 256, 0, s>>>(disp, pitch, fstride, rows, cols, bb, cs, min_disp, hist);
+    for (int f0 = 0; roi_rows > 0 && f0 < frames; f0 += 65535) {  // (a grid's y extent is 16 bits)
+        const int nf = frames - f0 < 65535 ? frames - f0 : 65535;
+        k_disp_hist<<<dim3(roi_rows, nf), 256, 0, s>>>(disp + (int64_t)f0 * fstride, pitch, fstride, rows, cols, bb, cs, min_disp,
+                                                       hist + (int64_t)f0 * 256);
+    }
     k_disp_variance<<<cdiv64(frames, 64), 64, 0, s>>>(hist, frames, rows, cols, bb, cs, var_out);
 }
 
@@ -678,12 +682,10 @@ void launch_plane_disp(Profiler* pf, hipStream_t s, const PlaneDispArgs& a)
 {
     if (a.frames <= 0 || a.rows <= 0 || a.cols <= 0) return;
     (void)hipMemsetAsync(a.table, 0, sizeof(unsigned long long) * kPdSums * (size_t)a.frames * a.n_labels, s);
-    for (int f0 = 0; f0 < a.frames; f0 += 32768) {  // (a grid's y extent is 16 bits)
-        const int nf = a.frames - f0 < 32768 ? a.frames - f0 : 32768;
-        if (a.elem == 1) plane_disp_frames<uint8_t>(pf, s, a, f0, nf);
-        else if (a.elem == 2) plane_disp_frames<uint16_t>(pf, s, a, f0, nf);
-        else plane_disp_frames<uint32_t>(pf, s, a, f0, nf);
-    }
+    // one launch group: plane_fit_disparity passes at most O3DR_BATCH_FRAMES <= 512 frames, far below a grid's y extent
+    if (a.elem == 1) plane_disp_frames<uint8_t>(pf, s, a, 0, a.frames);
+    else if (a.elem == 2) plane_disp_frames<uint16_t>(pf, s, a, 0, a.frames);
+    else plane_disp_frames<uint32_t>(pf, s, a, 0, a.frames);
 }
 
 // ORB features of one group of frames (a.frames <= 65535: the grid's y extent)
