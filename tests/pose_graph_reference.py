@@ -1,8 +1,9 @@
 """The pose-graph refinement's contract (include/o3dr.h "pose graph") restated in numpy, on top of pose_chain_reference.
 
 refine_ref: per-pair moments from the matching (chain_ref's `match`, or a brute force of its own), the edge formulas of
-DESIGN.md "Pose-graph refinement", block-Jacobi preconditioned CG with the contract's iteration counts and the Cayley
-retraction.  The summation orders are numpy's, not the library's: poses agree to rounding, not bit for bit.  reverse=True
+DESIGN.md "Pose-graph refinement", block-Jacobi preconditioned CG with the contract's iteration counts (the diagonal blocks
+inverted by the library's own Cholesky, invert6, so that a block that is not positive definite is held and flagged as the
+contract says) and the Cayley retraction.  The summation orders are numpy's, not the library's: poses agree to rounding, not bit for bit.  reverse=True
 sums every pair's rows in the opposite order; the tests take the distance between the two runs as the floor of what rounding
 alone moves.  direct_energy / direct_gradient evaluate the energy and its gradient per correspondence, without moments."""
 import numpy as np
@@ -11,6 +12,7 @@ import pose_chain_reference as R
 
 FIXED, FREE, FLOATING, REJECTED = range(4)  # O3DR_REFINE_*
 FLAG_CG_STOPPED = 1
+FLAG_SINGULAR = 2
 
 
 # ---- small algebra --------------------------------------------------------------------------------------------------------
@@ -78,6 +80,40 @@ def diag_block(n, S, SS):
     H[3:, :3] = hat(S)
     H[3:, 3:] = np.trace(SS) * np.eye(3) - SS
     return H
+
+
+def invert6(A):
+    """graph_invert6 operation for operation: A = L L^T with the pivots in order (row i over j <= i, s -= L[i][k] L[j][k]
+    with k ascending), L^-1 column by column by forward substitution, the inverse L^-T L^-1.  None: a pivot that is not
+    > 0 or not finite - the block is not positive definite."""
+    A = np.asarray(A, np.float64)
+    L = np.zeros((6, 6))
+    for i in range(6):
+        for j in range(i + 1):
+            s = A[i, j]
+            for k in range(j):
+                s = s - L[i, k] * L[j, k]
+            if i == j:
+                if not (s > 0.0) or not np.isfinite(s):
+                    return None
+                L[i, i] = np.sqrt(s)
+            else:
+                L[i, j] = s / L[j, j]
+    Li = np.zeros((6, 6))
+    for c in range(6):
+        for i in range(c, 6):
+            s = 1.0 if i == c else 0.0
+            for k in range(c, i):
+                s = s - L[i, k] * Li[k, c]
+            Li[i, c] = s / L[i, i]
+    inv = np.zeros((6, 6))
+    for i in range(6):
+        for j in range(6):
+            s = 0.0
+            for k in range(max(i, j), 6):
+                s = s + Li[k, i] * Li[k, j]
+            inv[i, j] = s
+    return inv
 
 
 def edge_terms(m, Ri, ti, Rj, tj):
@@ -260,7 +296,11 @@ def refine_ref(desc, offsets, kp3, poses, status, pairs, fixed=None, prior_poses
         if it == int(gn_iterations) or not free or not edges:
             out["e_after"], out["energy_after"], out["grad_after"] = E.copy(), float(E.sum() + Ep), gnorm(g)
             break
-        Minv = {f: np.linalg.inv(Hd[f]) for f in free}
+        Minv = {f: invert6(Hd[f]) for f in free}
+        for f in free:  # a block that is not positive definite: the frame stands still for this step
+            if Minv[f] is None:
+                out["flags"] |= FLAG_SINGULAR
+                Minv[f] = np.zeros((6, 6))
         n = len(free)
         x = np.zeros((n, 6))
         r = -np.stack([g[f] for f in free])

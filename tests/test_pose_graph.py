@@ -66,10 +66,20 @@ def assert_integers_equal(frames, edges, res, ref):
     assert (edges["reserved"] == 0).all()
     assert (res.n_free, res.n_gauge, res.n_floating, res.n_rejected, res.n_edges, res.n_used) == \
         (ref["n_free"], ref["n_gauge"], ref["n_floating"], ref["n_rejected"], ref["n_edges"], ref["n_used_total"])
+    assert res.flags == ref["flags"], (res.flags, ref["flags"])
 
 
-def assert_parity(ctx, w, ch, label, rule="floor", **kw):
-    """integers, energies within 1e-9 relative, poses against the reference -> the GPU's outputs.
+def pose_distance(ref, Ta, Tb):
+    """the largest entry difference of two [F, 12] fp64 pose sets over the reference's free frames; a held frame's T is its
+    input pose widened, which has no rounding in it and may be NaN (a rejected frame's pose): those are equal, NaN to NaN"""
+    free = ref["role"] == G.FREE
+    assert np.array_equal(Ta[~free], Tb[~free], equal_nan=True)
+    return float(np.abs(Ta[free] - Tb[free]).max()) if free.any() else 0.0
+
+
+def assert_parity(ctx, w, ch, label, rule="floor", refs=None, **kw):
+    """integers, flags, energies within 1e-9 relative, poses against the reference -> the GPU's outputs.  refs: the reference
+    of this very call and its reverse=True run, where the caller has them already.
     rule "floor" (the loop world): within four times the reversed-summation floor.  rule "nm" (the boundary worlds, where
     the floor is a few ulps and some solves stop before their fixed point): within 1e-9 m.  What those tests look for - a
     row lost at a run boundary, an entry lost past a stride, a neighbour lost past a wave - moves a pose by the order of
@@ -77,12 +87,11 @@ def assert_parity(ctx, w, ch, label, rule="floor", **kw):
     that, two below the 1e-7 m resolution of the fp32 poses, and six above one ulp of fp64.  rule None
     (test_role_rules_on_the_cpu's weakly held case, whose truncated CG is far from its fixed point): the integers, the
     input energy and the held poses are compared, and the energy must fall."""
-    ref = ref_of(w, ch, **kw)
-    rev = ref_of(w, ch, reverse=True, **kw)
-    floor = float(np.abs(ref["T"] - rev["T"]).max())
+    ref, rev = refs if refs is not None else (ref_of(w, ch, **kw), ref_of(w, ch, reverse=True, **kw))
+    floor = pose_distance(ref, ref["T"], rev["T"])
     poses, frames, res, edges = run(ctx, w, ch, return_edges=True, **kw)
     assert_integers_equal(frames, edges, res, ref)
-    diff = float(np.abs(frames["T"] - ref["T"]).max())
+    diff = pose_distance(ref, frames["T"], ref["T"])
     print(f"pose graph, {label}: floor {floor:.3e}, gpu vs reference {diff:.3e}, energy {res.energy_before:.6g} -> "
           f"{res.energy_after:.6g}, gradient {res.grad_before:.3e} -> {res.grad_after:.3e}")
     assert abs(res.energy_before - ref["energy_before"]) <= 1e-9 * ref["energy_before"]
@@ -113,6 +122,24 @@ def test_energy_from_moments_equals_the_direct_sum():
     i, j, a, b = ref["rows"][k]
     Rs, ts = G.state_of(input_T(ch))
     assert abs(G.direct_energy([ref["rows"][k]], Rs, ts) - ref["e_before"][k]) <= 1e-9 * ref["e_before"][k]
+
+
+def test_invert6_restates_the_cholesky_inverse_on_the_cpu():
+    """the reference's inverse is the library's Cholesky, pivot by pivot: on the loop world's positive definite blocks it is
+    the inverse (1e-9 relative: cond ~ 1e4 x 2e-16), and on the block of one point a - whose rotation about a costs nothing,
+    a (0; a) = 0 in exact arithmetic for this a - it reports "not positive definite" where np.linalg.inv returns numbers"""
+    ref = loop_ref()
+    blocks = {f: np.zeros((6, 6)) for f in ref["free"]}
+    for (i, j, a, b) in ref["rows"]:
+        for f, x in ((i, a), (j, b)):
+            if f in blocks:
+                blocks[f] += G.diag_block(float(len(x)), x.sum(0), x.T @ x)
+    assert len(blocks) == 15
+    for H in blocks.values():
+        inv, want = G.invert6(H), np.linalg.inv(H)
+        assert inv is not None and np.abs(inv - want).max() <= 1e-9 * np.abs(want).max()
+    a = np.array([0.5, -0.25, 2.0])
+    assert G.invert6(G.diag_block(1, a, np.outer(a, a))) is None
 
 
 def test_noisy_loop_converges_on_the_cpu():
