@@ -8,7 +8,7 @@ HBM pointers (torch is only device memory + streams here).
 """
 import ctypes as C
 from collections import namedtuple
-from dataclasses import dataclass
+from dataclasses import dataclass, fields
 
 import numpy as np
 
@@ -199,7 +199,7 @@ class RigidResult:
 
     @staticmethod
     def from_record(r):
-        return RigidResult(np.array(r["T"], np.float64).reshape(4, 4), float(r["rms"]), int(r["n_used"]), int(r["status"]))
+        return _result(RigidResult, r, T=np.array(r["T"], np.float64).reshape(4, 4))
 
 
 @dataclass
@@ -318,7 +318,8 @@ def image_stack_layout(shape, strides, itemsize, colour, contiguous=False):
     return StackLayout(single, F, rows, cols, ch, pitch, 0 if single else rows * pitch, True)
 
 
-_TORCH_DTYPE = {np.uint8: "uint8", np.uint16: "int16", np.int32: "int32", np.float32: "float32", np.float64: "float64"}
+_TORCH_DTYPE = {np.uint8: "uint8", np.uint16: "int16", np.int32: "int32", np.uint32: "int32", np.float32: "float32",
+                np.float64: "float64"}
 
 
 def _dtype_name(x):
@@ -330,9 +331,80 @@ def _itemsize(x):
     return x.element_size() if _is_torch(x) else x.itemsize
 
 
-def _addr(x):
-    """the address of an output array or tensor (None: not asked for)"""
-    return None if x is None else (x.data_ptr() if _is_torch(x) else x.ctypes.data)
+def _addr(x, n=1):
+    """the address of an array or tensor; None (NULL) for one not asked for and for one of n = 0 elements the library
+    neither reads nor writes"""
+    return None if x is None or not n else (x.data_ptr() if _is_torch(x) else x.ctypes.data)
+
+
+def _head(x, n):
+    """the first n rows of an output (None: not asked for)"""
+    return None if x is None else x[:n]
+
+
+def _unsigned(x):
+    """A returned int16 / int32 tensor that holds unsigned bits, viewed as uint16 / uint32 where torch has the type (a
+    numpy output is unsigned as it is made)."""
+    if not _is_torch(x):
+        return x
+    import torch
+    u = getattr(torch, "u" + _dtype_name(x), None)
+    return x if u is None else x.view(u)
+
+
+def _mem(x):
+    """the MEM kind of an array or tensor (a torch host tensor is host memory)"""
+    return L.MEM_DEVICE if _is_torch(x) and x.is_cuda else L.MEM_HOST
+
+
+# An array the library reads, as an intake hands it on: the array or tensor to keep alive, its rows, its address (None:
+# no rows - the entry points return on n = 0 before they look at the pointer) and its MEM kind.
+Input = namedtuple("Input", "x n addr mem")
+Raster = namedtuple("Raster", "raster H W addr mem")
+
+# Output specs of Context._empty_like besides (shape, dtype): n rows, never fewer than one allocated (a tensor is never
+# empty, a capacity never 0), which the caller slices on return.  A numpy record dtype gives records on the host and on the
+# device the tensor the operators return for it: int32 [n, itemsize / 4] for the records of 4-byte fields listed in
+# _WORD_RECORDS (words: another 4-byte type for them, such as the one of the cloud the points come from), uint8
+# [n, itemsize] for the others.
+_Rows = namedtuple("_Rows", "n dtype tail words")
+_WORD_RECORDS = (POINT, L.ORB_KEYPOINT, L.KNN2)
+
+
+def _rows(n, dtype, *tail, words=np.int32):
+    return _Rows(int(n), dtype, tail, words)
+
+
+def _out_spec(sp, host):
+    """(shape, dtype) of one _empty_like spec in host or device memory"""
+    if not isinstance(sp, _Rows):
+        return sp
+    n, dtype = max(sp.n, 1), sp.dtype
+    if host or getattr(dtype, "names", None) is None:
+        return (n,) + sp.tail, dtype
+    words = dtype in _WORD_RECORDS
+    return (n, dtype.itemsize // (4 if words else 1)), sp.words if words else np.uint8
+
+
+def _result(cls, res, **override):
+    """A ctypes result struct (or a numpy record) as its dataclass, by field name - the dataclass's order may differ from
+    the struct's: integers through int, floats through float, ctypes arrays as tuples, a nested struct as the field's
+    own dataclass; override: the fields that are not a plain copy."""
+    def value(f):
+        v = res[f.name] if isinstance(res, np.void) else getattr(res, f.name)
+        if isinstance(v, C.Structure):
+            return _result(f.type, v)
+        if isinstance(v, C.Array):
+            return tuple(v)
+        return int(v) if isinstance(v, (int, np.integer)) else float(v)
+    return cls(**{f.name: override[f.name] if f.name in override else value(f) for f in fields(cls)})
+
+
+def _returned(always, *optional):
+    """A method's return value: the values it always returns, then the value of every (flag, value) pair whose flag is
+    set; the bare value when that is exactly one."""
+    ret = tuple(always) + tuple(v for on, v in optional if on)
+    return ret[0] if len(ret) == 1 else ret
 
 
 def _ptr(x):
@@ -418,11 +490,51 @@ class Context:
         assert disp.strides[1] == disp.itemsize and bgr.strides[2] == 1 and bgr.strides[1] == 3
         return rows, cols, disp.strides[0], bgr.strides[0]
 
-    def _alloc_out(self, n, like):
-        if _is_torch(like) and like.is_cuda:
-            import torch
-            return torch.empty((max(n, 1), 4), dtype=torch.int32, device=like.device)
-        return np.empty(max(n, 1), POINT)
+    def _mem_after_torch(self, x):
+        """_mem(x), after ordering the library behind the work torch's stream holds now when x is a CUDA tensor: an
+        intake's last step, behind every torch operation that prepares what the call reads."""
+        if _mem(x) == L.MEM_DEVICE:
+            self._order_after_torch()
+        return _mem(x)
+
+    def _cloud(self, pts):
+        """A cloud as the library reads it -> Input: a numpy array made contiguous POINT records, or a contiguous torch
+        [N, 4] tensor of 4-byte elements as it is."""
+        if _is_torch(pts):
+            assert pts.is_contiguous() and tuple(pts.shape[1:]) == (4,) and pts.element_size() == 4
+        else:
+            pts = np.ascontiguousarray(pts, POINT)
+        n = int(pts.shape[0])
+        return Input(pts, n, _addr(pts, n), self._mem_after_torch(pts))
+
+    def _raster(self, raster):
+        """A float32 [height, width] raster as the library reads it, made contiguous -> Raster."""
+        if _is_torch(raster):
+            assert _dtype_name(raster) == "float32" and raster.dim() == 2
+            raster = raster.contiguous()
+        else:
+            raster = np.ascontiguousarray(raster, np.float32)
+            assert raster.ndim == 2
+        H, W = (int(v) for v in raster.shape)
+        return Raster(raster, H, W, _addr(raster, W * H), self._mem_after_torch(raster))
+
+    def _empty_like(self, like, *specs, device=None, zeros=False):
+        """Outputs in `like`'s memory (or on `device`), one per spec and None per None: (shape, dtype), or _rows(n, dtype,
+        ...) for n rows or records that the caller slices on return.  dtype: a numpy type - a tensor gets the torch type
+        of _TORCH_DTYPE, for uint16 / uint32 the int16 / int32 that holds the bits - or a torch type as it is.
+        Uninitialised, or zeros.  The library call may follow at once: it is ordered behind torch's work."""
+        if device is None and _mem(like) == L.MEM_HOST:  # (a torch host tensor is read as host memory: numpy outputs)
+            make = np.zeros if zeros else np.empty
+            return [None if sp is None else make(*_out_spec(sp, True)) for sp in specs]
+        import torch
+        make = torch.zeros if zeros else torch.empty
+
+        def tensor(shape, dt):
+            dt = dt if isinstance(dt, torch.dtype) else getattr(torch, _TORCH_DTYPE[dt])
+            return make(shape, dtype=dt, device=like.device if device is None else device)
+        outs = [None if sp is None else tensor(*_out_spec(sp, False)) for sp in specs]
+        self._order_after_torch()
+        return outs
 
     @staticmethod
     def _kp(kp_xy, like):
@@ -448,8 +560,7 @@ class Context:
         assert mem == mem2
         kp_ptr, n_kp, _k3 = self._kp(kp_xy, disp)
         cap = self.max_points(rows, cols) + n_kp
-        out = self._alloc_out(cap, disp)
-        po, _, _k4 = _ptr(out)
+        out, = self._empty_like(disp, _rows(cap, POINT))
         n = C.c_int64(0)
         st = C.c_uint32(0)
         fn = getattr(self._lib, fn_name)
@@ -457,7 +568,7 @@ class Context:
         if T is not None:
             Tn = self._T(T)
             args.append(Tn.ctypes.data)
-        args += [kp_ptr, n_kp, po, cap, C.byref(n)]
+        args += [kp_ptr, n_kp, _addr(out), cap, C.byref(n)]
         if with_status:
             args.append(C.byref(st))
         args.append(mem)
@@ -472,13 +583,9 @@ class Context:
     def transformPtCloud(self, pts, T):
         """pose.h:199 / pose_functions.cpp:1358-1362."""
         Tn = self._T(T)
-        if not _is_torch(pts):
-            pts = np.ascontiguousarray(pts, POINT)
-        pi, mem, _k = _ptr(pts)
-        n = int(pts.shape[0])
-        out = self._alloc_out(n, pts)
-        po, _, _k2 = _ptr(out)
-        L.check(self._lib.o3dr_transform_pt_cloud(self._h, pi, n, Tn.ctypes.data, po, mem))
+        pts, n, p_in, mem = self._cloud(pts)
+        out, = self._empty_like(pts, _rows(n, POINT))
+        L.check(self._lib.o3dr_transform_pt_cloud(self._h, p_in, n, Tn.ctypes.data, _addr(out), mem))
         return out[:n]
 
     def reprojectTransform(self, disp, bgr, T, kp_xy=None):
@@ -487,17 +594,13 @@ class Context:
 
     def downsamplePtCloud(self, pts, combinedPtCloud, return_status=False):
         """pose.h:216 / pose_functions.cpp:1654-1709."""
-        if not _is_torch(pts):
-            pts = np.ascontiguousarray(pts, POINT)
-        pi, mem, _k = _ptr(pts)
-        n_in = int(pts.shape[0])
-        out = self._alloc_out(n_in, pts)
-        po, _, _k2 = _ptr(out)
+        pts, n_in, p_in, mem = self._cloud(pts)
+        out, = self._empty_like(pts, _rows(n_in, POINT))
         n = C.c_int64(0)
         st = C.c_uint32(0)
-        L.check(self._lib.o3dr_downsample_pt_cloud(self._h, pi, n_in, int(bool(combinedPtCloud)), po, max(n_in, 1),
+        L.check(self._lib.o3dr_downsample_pt_cloud(self._h, p_in, n_in, int(bool(combinedPtCloud)), _addr(out), len(out),
                                                   C.byref(n), C.byref(st), mem))
-        return (out[: n.value], st.value) if return_status else out[: n.value]
+        return _returned((out[: n.value],), (return_status, st.value))
 
     def bilateralFilter(self, img, d, sigma_color, sigma_space):
         """cv::bilateralFilter on a u8 image (pose_functions.cpp:1044); numpy in/out or torch CUDA in/out."""
@@ -599,68 +702,36 @@ class Context:
 
     def statisticalOutlierRemoval(self, pts):
         """pcl::StatisticalOutlierRemoval, mean_k 50, 1 sigma (pose_functions.cpp:1679-1684)."""
-        if not _is_torch(pts):
-            pts = np.ascontiguousarray(pts, POINT)
-        pi, mem, _k = _ptr(pts)
-        n_in = int(pts.shape[0])
-        out = self._alloc_out(n_in, pts)
-        po, _, _k2 = _ptr(out)
+        pts, n_in, p_in, mem = self._cloud(pts)
+        out, = self._empty_like(pts, _rows(n_in, POINT))
         n = C.c_int64(0)
-        L.check(self._lib.o3dr_statistical_outlier_removal(self._h, pi, n_in, po, max(n_in, 1), C.byref(n), mem))
+        L.check(self._lib.o3dr_statistical_outlier_removal(self._h, p_in, n_in, _addr(out), len(out), C.byref(n), mem))
         return out[: n.value]
 
     # -- alignment (pcl::IterativeClosestPoint, pose.cpp:46-112 / pose_functions.cpp:1634-1652) -----------------------
-    @staticmethod
-    def _cloud(pts):
-        if _is_torch(pts):
-            assert pts.is_contiguous() and tuple(pts.shape[1:]) == (4,) and pts.element_size() == 4
-            return pts, int(pts.shape[0])
-        pts = np.ascontiguousarray(pts, POINT)
-        return pts, int(pts.shape[0])
-
     def nearestNeighbors(self, query, target, max_distance=float("inf")):
         """Exact nearest neighbour of every query point in `target`: -> (idx uint32, d2 float32), the point minimising
         (fp32 d2, original index); idx 0xFFFFFFFF / d2 inf where no target point lies within max_distance.  numpy POINT
         arrays, or torch [N,4] 4-byte CUDA tensors (results are then CUDA tensors too)."""
-        query, nq = self._cloud(query)
-        target, nt = self._cloud(target)
-        pq, mem, _k = _ptr(query)
-        pt, mem2, _k2 = _ptr(target)
-        if nq and nt:
-            assert mem == mem2, "query and target must live in the same memory"
-        if _is_torch(query) and query.is_cuda:
-            import torch
-            idx = torch.empty(max(nq, 1), dtype=torch.int32, device=query.device)
-            d2 = torch.empty(max(nq, 1), dtype=torch.float32, device=query.device)
-            self._order_after_torch()
-            L.check(self._lib.o3dr_nearest_neighbors(self._h, pq, nq, pt, nt, float(max_distance), idx.data_ptr(), d2.data_ptr(),
-                                                     L.MEM_DEVICE))
-            return idx[:nq].view(torch.uint32) if hasattr(torch, "uint32") else idx[:nq], d2[:nq]
-        idx = np.empty(max(nq, 1), np.uint32)
-        d2 = np.empty(max(nq, 1), np.float32)
-        L.check(self._lib.o3dr_nearest_neighbors(self._h, pq, nq, pt, nt, float(max_distance), idx.ctypes.data, d2.ctypes.data, mem))
-        return idx[:nq], d2[:nq]
+        q, t = self._cloud(query), self._cloud(target)
+        if q.n and t.n:
+            assert q.mem == t.mem, "query and target must live in the same memory"
+        idx, d2 = self._empty_like(q.x, _rows(q.n, np.uint32), _rows(q.n, np.float32))
+        L.check(self._lib.o3dr_nearest_neighbors(self._h, q.addr, q.n, t.addr, t.n, float(max_distance), _addr(idx), _addr(d2), q.mem))
+        return _unsigned(idx[:q.n]), d2[:q.n]
 
     def icpAlign(self, source, target, T_init=None, max_iterations=10, max_correspondence_distance=float("inf"),
                  transformation_epsilon=0.0):
         """Point-to-point ICP of `source` onto `target` (contract: include/o3dr.h, DESIGN.md "ICP") -> IcpResult."""
-        source, ns = self._cloud(source)
-        target, nt = self._cloud(target)
-        ps_, mem, _k = _ptr(source)
-        pt, mem2, _k2 = _ptr(target)
-        if ns and nt:
-            assert mem == mem2, "source and target must live in the same memory"
-        elif ns == 0:
-            mem = mem2
+        s, t = self._cloud(source), self._cloud(target)
+        if s.n and t.n:
+            assert s.mem == t.mem, "source and target must live in the same memory"
         Tn = None if T_init is None else self._T(T_init)
         prm = L.IcpParamsStruct(int(max_iterations), float(max_correspondence_distance), float(transformation_epsilon))
         res = L.IcpResultStruct()
-        if mem == L.MEM_DEVICE:
-            self._order_after_torch()
-        L.check(self._lib.o3dr_icp_align(self._h, ps_, ns, pt, nt, None if Tn is None else Tn.ctypes.data, C.byref(prm), C.byref(res),
-                                         mem))
-        return IcpResult(np.array(res.T[:], np.float64).reshape(4, 4), float(res.fitness), int(res.n_correspondences),
-                         int(res.iterations), int(res.reason))
+        L.check(self._lib.o3dr_icp_align(self._h, s.addr, s.n, t.addr, t.n, _addr(Tn), C.byref(prm), C.byref(res),
+                                         s.mem if s.n else t.mem))
+        return _result(IcpResult, res, T=np.array(res.T[:], np.float64).reshape(4, 4))
 
     # -- surface smoothing (pcl::MovingLeastSquares, pose.cpp:27-112 / pose_functions.cpp:1711-1813) ---------------------
     def mlsSmooth(self, pts, search_radius, polynomial_order=2, sqr_gauss_param=0.0, return_normals=False, return_info=False,
@@ -671,45 +742,27 @@ class Context:
         NaN where no fit); with return_info also nn_count (uint32 / int32), fit (uint8, MLS_*) and an MlsResult.
         fitted_only: keep only the fitted points (fit != MLS_NONE), in input order.  out: where the points go (may be
         `pts` itself: in place)."""
-        pts, n = self._cloud(pts)
-        p_in, mem, _k = _ptr(pts)
+        pts, n, p_in, mem = self._cloud(pts)
         prm = L.MlsParamsStruct(float(search_radius), int(polynomial_order), float(sqr_gauss_param))
         res = L.MlsResultStruct()
-        if mem == L.MEM_DEVICE:
-            import torch
-            dev = pts.device
-            o = torch.empty_like(pts) if out is None else out
-            assert o.is_cuda and o.is_contiguous() and o.shape == pts.shape and o.element_size() == 4
-            nrm = torch.empty((max(n, 1), 4), dtype=torch.float32, device=dev) if return_normals else None
-            cnt = torch.empty(max(n, 1), dtype=torch.int32, device=dev) if return_info or fitted_only else None
-            fit = torch.empty(max(n, 1), dtype=torch.uint8, device=dev) if return_info or fitted_only else None
-            self._order_after_torch()
-            L.check(self._lib.o3dr_mls_smooth(self._h, p_in, n, C.byref(prm), o.data_ptr() if n else None,
-                                              None if nrm is None else nrm.data_ptr(), None if cnt is None else cnt.data_ptr(),
-                                              None if fit is None else fit.data_ptr(), C.byref(res), L.MEM_DEVICE))
-        else:
-            o = np.empty(n, POINT) if out is None else out
-            assert isinstance(o, np.ndarray) and o.dtype == POINT and o.shape == (n,) and o.flags.c_contiguous
-            nrm = np.empty((n, 4), np.float32) if return_normals else None
-            cnt = np.empty(n, np.uint32) if return_info or fitted_only else None
-            fit = np.empty(n, np.uint8) if return_info or fitted_only else None
-            L.check(self._lib.o3dr_mls_smooth(self._h, p_in, n, C.byref(prm), o.ctypes.data if n else None,
-                                              None if nrm is None else nrm.ctypes.data, None if cnt is None else cnt.ctypes.data,
-                                              None if fit is None else fit.ctypes.data, C.byref(res), mem))
-        o, nrm, cnt, fit = o[:n], (None if nrm is None else nrm[:n]), (None if cnt is None else cnt[:n]), (None if fit is None else fit[:n])
+        per_point = return_info or fitted_only
+        o, nrm, cnt, fit = self._empty_like(pts, _rows(n, POINT, words=pts.dtype) if out is None else None,
+                                            _rows(n, np.float32, 4) if return_normals else None,
+                                            _rows(n, np.uint32) if per_point else None, _rows(n, np.uint8) if per_point else None)
+        if out is not None:
+            o = out
+            if mem == L.MEM_DEVICE:
+                assert o.is_cuda and o.is_contiguous() and o.shape == pts.shape and o.element_size() == 4
+            else:
+                assert isinstance(o, np.ndarray) and o.dtype == POINT and o.shape == (n,) and o.flags.c_contiguous
+        L.check(self._lib.o3dr_mls_smooth(self._h, p_in, n, C.byref(prm), _addr(o, n), _addr(nrm), _addr(cnt), _addr(fit), C.byref(res),
+                                          mem))
+        o, nrm, cnt, fit = o[:n], _head(nrm, n), _head(cnt, n), _head(fit, n)
         if fitted_only:
             keep = fit != L.MLS_NONE
             o, nrm, cnt, fit = o[keep], (None if nrm is None else nrm[keep]), cnt[keep], fit[keep]
-        if mem == L.MEM_DEVICE and cnt is not None:
-            import torch
-            if hasattr(torch, "uint32"):
-                cnt = cnt.view(torch.uint32)
-        ret = (o,)
-        if return_normals:
-            ret += (nrm,)
-        if return_info:
-            ret += (cnt, fit, MlsResult(int(res.n_poly), int(res.n_plane), int(res.n_none), int(res.max_neighbors)))
-        return ret[0] if len(ret) == 1 else ret
+        return _returned((o,), (return_normals, nrm), (return_info, _unsigned(cnt)), (return_info, fit),
+                         (return_info, _result(MlsResult, res)))
 
     # -- plane segmentation (pcl::SACSegmentation + ProjectInliers, segmentCloud: pose_functions.cpp:2094-2249) -----------
     def segmentPlane(self, pts, distance_threshold, max_iterations=1000, tile_size=0.0, seed=0, optimize=True, project=False,
@@ -719,48 +772,27 @@ class Context:
         finalize(device=...) (per-point results are then CUDA tensors).  -> (inlier mask (bool, index-aligned with `pts`),
         tile records (numpy PLANE_TILE array, tile order)); with project also the points with the inliers projected onto
         their tile's plane; with return_tile_index also every point's tile ordinal (int32)."""
-        pts, n = self._cloud(pts)
-        p_in, mem, _k = _ptr(pts)
+        pts, n, p_in, mem = self._cloud(pts)
         prm = L.PlaneParamsStruct(float(distance_threshold), int(max_iterations), float(tile_size), int(seed) & (2**64 - 1),
                                   1 if optimize else 0)
         n_tiles = C.c_int64(0)
         cap = 1 if tile_size == 0 else 64
         for attempt in range(2):  # one retry with the tile count the first call reported
-            if mem == L.MEM_DEVICE:
-                import torch
-                dev = pts.device
-                inl = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
-                til = torch.empty(max(n, 1), dtype=torch.int32, device=dev) if return_tile_index else None
-                prj = torch.empty_like(pts) if project else None
-                rec = torch.empty((cap, 64), dtype=torch.uint8, device=dev)
-                self._order_after_torch()
-                ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-                rc = self._lib.o3dr_segment_plane(self._h, p_in, n, C.byref(prm), ptr(inl) if n else None, ptr(til) if n else None,
-                                                  ptr(prj) if n else None, rec.data_ptr(), cap, C.byref(n_tiles), L.MEM_DEVICE)
-            else:
-                inl = np.empty(n, np.uint8)
-                til = np.empty(n, np.int32) if return_tile_index else None
-                prj = np.empty(n, POINT) if project else None
-                rec = np.empty(cap, L.PLANE_TILE)
-                ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
-                rc = self._lib.o3dr_segment_plane(self._h, p_in, n, C.byref(prm), ptr(inl) if n else None, ptr(til) if n else None,
-                                                  ptr(prj) if n else None, rec.ctypes.data, cap, C.byref(n_tiles), mem)
+            inl, til, prj, rec = self._empty_like(pts, _rows(n, np.uint8), _rows(n, np.int32) if return_tile_index else None,
+                                                  _rows(n, POINT, words=pts.dtype) if project else None, _rows(cap, L.PLANE_TILE))
+            rc = self._lib.o3dr_segment_plane(self._h, p_in, n, C.byref(prm), _addr(inl, n), _addr(til, n), _addr(prj, n), _addr(rec),
+                                              cap, C.byref(n_tiles), mem)
             if rc == L.ERR_CAPACITY and attempt == 0:
                 cap = int(n_tiles.value)
                 continue
             L.check(rc)
             break
         nt = int(n_tiles.value)
-        if mem == L.MEM_DEVICE:
+        if _is_torch(rec):  # (the tile records come back on the host)
             tiles = rec[:nt].cpu().numpy().view(L.PLANE_TILE).reshape(nt)
         else:
             tiles = rec[:nt].copy()
-        ret = (inl[:n] != 0, tiles)
-        if project:
-            ret += (prj[:n],)
-        if return_tile_index:
-            ret += (til[:n],)
-        return ret
+        return _returned((inl[:n] != 0, tiles), (project, _head(prj, n)), (return_tile_index, _head(til, n)))
 
     # -- image stacks: the inputs and outputs of the image operators below ------------------------------------------------
     @staticmethod
@@ -778,19 +810,6 @@ class Context:
         x = np.ascontiguousarray(x) if lay.copy else x
         return x, lay, x.ctypes.data, L.MEM_HOST
 
-    def _empty_like(self, like, *specs):
-        """Uninitialised outputs of `like`'s memory kind, one per (shape, dtype) and None per None.  dtype: a numpy type - a
-        tensor gets the torch type of _TORCH_DTYPE, for uint16 int16 (which holds the bits) - or a torch type as it is.  The
-        library call may follow at once: it is ordered behind torch's work."""
-        if not (_is_torch(like) and like.is_cuda):  # (a torch host tensor is read as host memory: numpy outputs)
-            return [None if sp is None else np.empty(*sp) for sp in specs]
-        import torch
-        outs = [None if sp is None else
-                torch.empty(sp[0], dtype=sp[1] if isinstance(sp[1], torch.dtype) else getattr(torch, _TORCH_DTYPE[sp[1]]), device=like.device)
-                for sp in specs]
-        self._order_after_torch()
-        return outs
-
     # -- ORB features (the reference's findFeatures / OrbFeaturesFinder, pose.cpp:127,210) -------------------------------
     def findFeatures(self, img, n_features=1500, scale_factor=1.3, n_levels=5, fast_threshold=20, edge=31, return_levels=False):
         """oFAST keypoints and steered-BRIEF descriptors (contract: include/o3dr.h "ORB features").  img: uint8 [H, W] or
@@ -802,22 +821,20 @@ class Context:
         return_levels: a fifth value, every frame's grey pyramid as a flat uint8 array (frame-major, levels back to back,
         rows tight)."""
         img, (_, F, rows, cols, ch, pitch, fs, _), pi, mem = self._image_stack(img, colour=True)
-        dev = _is_torch(img)
         assert _dtype_name(img) == "uint8"
         prm = L.OrbParamsStruct(int(n_features), float(scale_factor), int(n_levels), int(fast_threshold), int(edge), ch)
         wh = np.zeros(2 * max(int(n_levels), 1), np.int32)
         L.check(self._lib.o3dr_orb_level_sizes(rows, cols, C.byref(prm), wh.ctypes.data, None))
         cap = max(F * int(n_features), 1)
         n_lev = F * int(sum(int(wh[2 * l]) * int(wh[2 * l + 1]) for l in range(int(n_levels)))) if return_levels else 0
-        kp, xy, desc, lev = self._empty_like(img, ((cap, 8), np.int32) if dev else (cap, L.ORB_KEYPOINT), ((cap, 2), np.float32),
-                                             ((cap, 32), np.uint8), (max(n_lev, 1), np.uint8) if return_levels else None)
+        kp, xy, desc, lev = self._empty_like(img, _rows(cap, L.ORB_KEYPOINT), ((cap, 2), np.float32), ((cap, 32), np.uint8),
+                                             _rows(n_lev, np.uint8) if return_levels else None)
         off = np.zeros(F + 1, np.int64)
         n = C.c_int64(0)
         L.check(self._lib.o3dr_orb_detect(self._h, pi, fs, pitch, rows, cols, F, C.byref(prm), _addr(kp), _addr(xy), _addr(desc),
                                           off.ctypes.data, _addr(lev), cap, C.byref(n), mem))
         k = int(n.value)
-        res = (kp[:k], xy[:k], desc[:k], off)
-        return res + (lev[:n_lev],) if return_levels else res
+        return _returned((kp[:k], xy[:k], desc[:k], off), (return_levels, _head(lev, n_lev)))
 
     # -- stereo rectification (initUndistortRectifyMap + remap: what makes the pair the matcher takes) -------------------------
     def rectifyMaps(self, K, D, R, P, size, device=None):
@@ -841,14 +858,8 @@ class Context:
         cam.P[:] = P34.reshape(-1).tolist()
         rows_out, cols_out = int(size[0]), int(size[1])
         shape = (max(rows_out, 0), max(cols_out, 0), 2)
-        if device is not None:
-            import torch
-            maps = torch.empty(shape, dtype=torch.int32, device=device)
-            self._order_after_torch()
-            L.check(self._lib.o3dr_rectify_maps(self._h, C.byref(cam), rows_out, cols_out, maps.data_ptr(), L.MEM_DEVICE))
-        else:
-            maps = np.empty(shape, np.int32)
-            L.check(self._lib.o3dr_rectify_maps(self._h, C.byref(cam), rows_out, cols_out, maps.ctypes.data, L.MEM_HOST))
+        maps, = self._empty_like(None, (shape, np.int32), device=device)
+        L.check(self._lib.o3dr_rectify_maps(self._h, C.byref(cam), rows_out, cols_out, _addr(maps), _mem(maps)))
         return maps
 
     def rectify(self, img, maps, border=0, return_valid=False, group_frames=0):
@@ -875,7 +886,7 @@ class Context:
         out, valid = self._empty_like(img, (shape, np.uint8), ((rows_out, cols_out), np.uint8) if return_valid else None)
         L.check(self._lib.o3dr_rectify_remap(self._h, pi, fs, pitch, rows, cols, ch, F, _addr(maps), rows_out, cols_out, int(border),
                                              int(group_frames), _addr(out), _addr(valid), mem))
-        return (out, valid) if return_valid else out
+        return _returned((out,), (return_valid, valid))
 
     # -- stereo disparity (the image every frame call starts from; the reference reads it from files) ----------------------
     def stereoDisparity(self, left, right, n_disparities=256, min_disparity=0, p1=10, p2=120, n_paths=8, uniqueness=10,
@@ -926,9 +937,7 @@ class Context:
             vol = None if vol is None else vol.view(torch.uint16)
         else:
             out = q4.astype(np.float64) / 16.0 if subpixel else disp
-        if not (return_cost or return_volume):
-            return out
-        return (out,) + ((cost,) if return_cost else ()) + ((vol,) if return_volume else ())
+        return _returned((out,), (return_cost, cost), (return_volume, vol))
 
     # -- disparity filter (what production matchers end with: medianBlur, then filterSpeckles) --------------------------------
     def filterDisparity(self, disp, median=0, max_speckle_size=0, max_diff=1, return_labels=False, return_sizes=False,
@@ -950,11 +959,8 @@ class Context:
         info = (L.DisparityFilterInfoStruct * F)() if return_info else None
         L.check(self._lib.o3dr_disparity_filter(self._h, pi, fs, pitch, rows, cols, F, C.byref(prm), _addr(out), _addr(labels),
                                                 _addr(sizes), C.cast(info, C.c_void_p) if return_info else None, mem))
-        if not (return_labels or return_sizes or return_info):
-            return out
-        infos = [DisparityFilterInfo(int(i.n_valid), int(i.n_components), int(i.n_speckles), int(i.n_removed), int(i.largest))
-                 for i in info] if return_info else None
-        return (out,) + ((labels,) if return_labels else ()) + ((sizes,) if return_sizes else ()) + ((infos,) if return_info else ())
+        infos = [_result(DisparityFilterInfo, i) for i in info or ()]
+        return _returned((out,), (return_labels, labels), (return_sizes, sizes), (return_info, infos))
 
     # -- multi-view filter (the consistency test across frames that multi-view stereo pipelines end on) -----------------------
     def multiviewHomographies(self, poses, neighbors):
@@ -999,11 +1005,8 @@ class Context:
         L.check(self._lib.o3dr_multiview_filter(self._h, pi, fs, pitch, rows, cols, F, poses.ctypes.data, neighbors.ctypes.data, kk,
                                                 C.byref(prm), _addr(out), _addr(support), _addr(violations),
                                                 C.cast(info, C.c_void_p) if return_info else None, mem))
-        if not (return_support or return_violations or return_info):
-            return out
-        infos = [MultiviewInfo(*(int(getattr(i, n)) for n, _ in L.MultiviewInfoStruct._fields_)) for i in info] if return_info else None
-        return (out,) + ((support,) if return_support else ()) + ((violations,) if return_violations else ()) + \
-            ((infos,) if return_info else ())
+        infos = [_result(MultiviewInfo, i) for i in info or ()]
+        return _returned((out,), (return_support, support), (return_violations, violations), (return_info, infos))
 
     def multiviewFuse(self, disp, poses, neighbors=None, k=4, max_distance=float("inf"), tolerance=1.0, min_support=1,
                       max_violations=-1, return_votes=False, return_support=False, return_violations=False, return_info=False):
@@ -1035,12 +1038,8 @@ class Context:
         L.check(self._lib.o3dr_multiview_fuse(self._h, pi, fs, pitch, rows, cols, F, poses.ctypes.data, neighbors.ctypes.data, kk,
                                               C.byref(prm), _addr(out), _addr(votes), _addr(support), _addr(violations),
                                               C.cast(info, C.c_void_p) if return_info else None, mem))
-        if not (return_votes or return_support or return_violations or return_info):
-            return out
-        infos = [MultiviewFuseInfo(MultiviewInfo(*(int(getattr(i.filter, n)) for n, _ in L.MultiviewInfoStruct._fields_)),
-                                   int(i.n_votes), int(i.n_votes_dropped), int(i.n_fused)) for i in info] if return_info else None
-        return (out,) + ((votes,) if return_votes else ()) + ((support,) if return_support else ()) + \
-            ((violations,) if return_violations else ()) + ((infos,) if return_info else ())
+        infos = [_result(MultiviewFuseInfo, i) for i in info or ()]
+        return _returned((out,), (return_votes, votes), (return_support, support), (return_violations, violations), (return_info, infos))
 
     # -- image segmentation (the label image planeFitDisparity reads; the reference takes it from offline files) ---------------
     def segmentImage(self, img, step=16, compactness=20, iterations=5, min_size=None, return_raw=False, return_sizes=False,
@@ -1066,71 +1065,45 @@ class Context:
                                              C.cast(info, C.c_void_p) if return_info else None, mem))
         if not _is_torch(img):
             labels = labels.view(np.uint32)  # (never negative)
-        if not (return_raw or return_sizes or return_info):
-            return labels
-        infos = [SegmentInfo(int(i.n_centres), int(i.n_components), int(i.n_merged), int(i.n_labels), int(i.largest), int(i.smallest))
-                 for i in info] if return_info else None
-        return (labels,) + ((raw,) if return_raw else ()) + ((sizes,) if return_sizes else ()) + ((infos,) if return_info else ())
+        infos = [_result(SegmentInfo, i) for i in info or ()]
+        return _returned((labels,), (return_raw, raw), (return_sizes, sizes), (return_info, infos))
 
     # -- feature matching (BFMatcher NORM_HAMMING knnMatch k=2 + ratio test, pose.h:180 / pose_functions.cpp:2017, and
     #    TransformationEstimationSVD, pose.cpp:213-235) --------------------------------------------------------------------
-    @staticmethod
-    def _desc(desc):
+    def _desc(self, desc):
+        """Descriptor rows as the library reads them -> Input: a numpy array made contiguous uint8 [N, 32], or a
+        contiguous torch [N, 32] tensor of 1-byte elements as it is."""
         if _is_torch(desc):
             assert desc.is_contiguous() and desc.element_size() == 1 and desc.dim() == 2 and desc.shape[1] == 32
-            return desc, int(desc.shape[0])
-        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
-        return desc, int(desc.shape[0])
+        else:
+            desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        n = int(desc.shape[0])
+        return Input(desc, n, _addr(desc, n), self._mem_after_torch(desc))
 
     def _point_pairs(self, src, tgt, mask, seg_offsets):
-        """The index-aligned point pairs of estimateRigidTransform / ransacRigid as the library reads them -> ((src, tgt,
-        mask) kept alive, their addresses (None where absent), n, MEM kind, segs (int64 array or None), n_segs)."""
-        src, n = self._cloud(src)
-        tgt, n2 = self._cloud(tgt)
-        assert n == n2, "src and tgt must be index-aligned"
-        ps_, mem, _k = _ptr(src)
-        pt, mem2, _k2 = _ptr(tgt)
-        if n:
-            assert mem == mem2, "src and tgt must live in the same memory"
-        pm = None
-        if mask is not None:
-            if _is_torch(mask):
-                import torch
-                mask = mask.to(torch.uint8).contiguous()
-                pm = mask.data_ptr()
-            else:
-                mask = np.ascontiguousarray(mask).astype(np.uint8)
-                pm = mask.ctypes.data
+        """The index-aligned point pairs of estimateRigidTransform / ransacRigid as the library reads them -> (src, tgt
+        (Input), mask (uint8, kept alive; None: absent), segs (int64 array or None), n_segs)."""
+        if mask is not None:  # (before the intakes: they order the call behind this conversion too)
+            mask = mask.byte().contiguous() if _is_torch(mask) else np.ascontiguousarray(mask).astype(np.uint8)
+        s, t = self._cloud(src), self._cloud(tgt)
+        assert s.n == t.n, "src and tgt must be index-aligned"
+        if s.n:
+            assert s.mem == t.mem, "src and tgt must live in the same memory"
         segs = None if seg_offsets is None else np.ascontiguousarray(seg_offsets, np.int64).reshape(-1)
-        n_segs = 1 if segs is None else len(segs) - 1
-        return (src, tgt, mask), (ps_ if n else None, pt if n else None, pm), n, mem, segs, n_segs
+        return s, t, mask, segs, 1 if segs is None else len(segs) - 1
 
     def _feature_pool(self, desc, kp3, offsets):
-        """The pool of poseChain / refinePoses as the library reads it -> (desc, kp3, their addresses (None for an empty
-        pool), MEM kind, off (int64 array), F)."""
-        desc, n = self._desc(desc)
-        kp3, n3 = self._cloud(kp3)
-        assert n == n3, "kp3 must be index-aligned with desc"
-        pd, mem, _k = _ptr(desc)
-        pk, mem2, _k2 = _ptr(kp3)
-        if n:
-            assert mem == mem2, "desc and kp3 must live in the same memory"
+        """The pool of poseChain / refinePoses as the library reads it -> (desc, kp3 (Input), off (int64 array), F)."""
+        d, k = self._desc(desc), self._cloud(kp3)
+        assert d.n == k.n, "kp3 must be index-aligned with desc"
+        if d.n:
+            assert d.mem == k.mem, "desc and kp3 must live in the same memory"
         off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
-        return desc, kp3, pd if n else None, pk if n else None, mem, off, len(off) - 1
+        return d, k, off, len(off) - 1
 
     @staticmethod
     def _ransac_params(threshold, seed, iterations):
         return L.RansacParamsStruct(float(threshold), int(seed) & 0xFFFFFFFFFFFFFFFF, int(iterations), 0)
-
-    def _pose_out(self, like, mem, F):
-        """The pose output of poseChain / refinePoses: [max(F, 1), 16] float32 zeros in `like`'s memory -> (it, its address)."""
-        if mem == L.MEM_DEVICE:
-            import torch
-            poses = torch.zeros((max(F, 1), 16), dtype=torch.float32, device=like.device)
-            self._order_after_torch()
-            return poses, poses.data_ptr()
-        poses = np.zeros((max(F, 1), 16), np.float32)
-        return poses, poses.ctypes.data
 
     def matchDescriptors(self, desc, offsets, pairs, ratio=0.5, max_distance=40):
         """Brute-force Hamming 2-NN of every query row of every (query_set, train_set) pair (contract: include/o3dr.h,
@@ -1138,27 +1111,16 @@ class Context:
         offsets: the n_sets + 1 row offsets of the sets; pairs: [P, 2] set indices.  -> (records (numpy KNN2 array, or a
         torch int32 [n, 4] tensor: train_idx[2], distance[2] as bits), good (bool mask)); pair p's records follow those of
         the pairs before it."""
-        desc, _ = self._desc(desc)
-        pd, mem, _k = _ptr(desc)
+        d = self._desc(desc)
         off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
         prs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
         n_sets = len(off) - 1
         n_rec = int(sum(int(off[q + 1] - off[q]) for q, _ in prs)) if n_sets > 0 else 0
         prm = L.MatchParamsStruct(float(ratio), int(max_distance))
         n = C.c_int64(0)
-        if mem == L.MEM_DEVICE:
-            import torch
-            rec = torch.empty((max(n_rec, 1), 4), dtype=torch.int32, device=desc.device)
-            good = torch.empty(max(n_rec, 1), dtype=torch.uint8, device=desc.device)
-            self._order_after_torch()
-            pr, pg = rec.data_ptr(), good.data_ptr()
-        else:
-            rec = np.empty(max(n_rec, 1), L.KNN2)
-            good = np.empty(max(n_rec, 1), np.uint8)
-            pr, pg = rec.ctypes.data, good.ctypes.data
-        L.check(self._lib.o3dr_match_knn2_hamming(self._h, pd if len(desc) else None, off.ctypes.data, n_sets,
-                                                  prs.ctypes.data if len(prs) else None, len(prs), C.byref(prm), pr, pg,
-                                                  max(n_rec, 1), C.byref(n), mem))
+        rec, good = self._empty_like(d.x, _rows(n_rec, L.KNN2), _rows(n_rec, np.uint8))
+        L.check(self._lib.o3dr_match_knn2_hamming(self._h, d.addr, off.ctypes.data, n_sets, _addr(prs, len(prs)), len(prs),
+                                                  C.byref(prm), _addr(rec), _addr(good), len(rec), C.byref(n), d.mem))
         assert n.value == n_rec
         return rec[:n_rec], good[:n_rec] != 0
 
@@ -1181,26 +1143,19 @@ class Context:
             counts = [int(torch.as_tensor(k).reshape(-1, 2).shape[0]) for k in kps]
             ps = None if poses is None else torch.as_tensor(poses, dtype=torch.float32, device=disp.device).contiguous()
             bg = None if bgr is None else bgr.contiguous()
-            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-            es, mem = disp.element_size(), L.MEM_DEVICE
         else:
             disp = np.ascontiguousarray(disp)
             kp = np.ascontiguousarray(np.concatenate([np.asarray(k, np.float32).reshape(-1, 2) for k in kps]))
             counts = [len(np.asarray(k).reshape(-1, 2)) for k in kps]
             ps = None if poses is None else np.ascontiguousarray(poses, np.float32)
             bg = None if bgr is None else np.ascontiguousarray(bgr, np.uint8)
-            ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
-            es, mem = disp.itemsize, L.MEM_HOST
         off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        n_kp = int(off[-1])
-        out = self._alloc_out(n_kp, disp)
-        po, _, _k = _ptr(out)
+        n_kp, es = int(off[-1]), _itemsize(disp)
+        out, = self._empty_like(disp, _rows(n_kp, POINT))
         n = C.c_int64(0)
-        if dev:
-            self._order_after_torch()
-        L.check(self._lib.o3dr_keypoints_3d(self._h, ptr(disp), rows * cols * es, cols * es, ptr(bg), rows * cols * 3, cols * 3, rows,
-                                            cols, ptr(ps), F, ptr(kp) if n_kp else None, off.ctypes.data, po, max(n_kp, 1), C.byref(n),
-                                            mem))
+        L.check(self._lib.o3dr_keypoints_3d(self._h, _addr(disp), rows * cols * es, cols * es, _addr(bg), rows * cols * 3, cols * 3, rows,
+                                            cols, _addr(ps), F, _addr(kp, n_kp), off.ctypes.data, _addr(out), len(out), C.byref(n),
+                                            _mem(disp)))
         return out[:n_kp]
 
     def estimateRigidTransform(self, src, tgt, seg_offsets=None, mask=None):
@@ -1208,12 +1163,10 @@ class Context:
         rigid T mapping src onto tgt over the index-aligned pairs with mask != 0 and finite coordinates.  numpy POINT arrays,
         or torch [N,4] 4-byte CUDA tensors (mask then a CUDA uint8 / bool tensor).  -> RigidResult, or a list of them with
         seg_offsets (the n_segs + 1 segment boundaries)."""
-        _keep, (ps_, pt, pm), n, mem, segs, n_segs = self._point_pairs(src, tgt, mask, seg_offsets)
+        s, t, mask, segs, n_segs = self._point_pairs(src, tgt, mask, seg_offsets)
         res = np.zeros(max(n_segs, 1), L.RIGID_RESULT)
-        if mem == L.MEM_DEVICE:
-            self._order_after_torch()
-        L.check(self._lib.o3dr_estimate_rigid_transform(self._h, ps_, pt, n, None if segs is None else segs.ctypes.data, n_segs, pm,
-                                                        res.ctypes.data, mem))
+        L.check(self._lib.o3dr_estimate_rigid_transform(self._h, s.addr, t.addr, s.n, _addr(segs), n_segs, _addr(mask), res.ctypes.data,
+                                                        s.mem))
         out = [RigidResult.from_record(r) for r in res[:n_segs]]
         return out[0] if segs is None else out
 
@@ -1223,22 +1176,15 @@ class Context:
         with `seed` and the segment's key (seg_keys, uint64 per segment; default: its ordinal).  Inputs as
         estimateRigidTransform's.  -> (inlier: bool mask index-aligned with src - numpy, or a CUDA tensor for CUDA inputs -,
         records: a numpy RANSAC_RESULT array, one per segment)."""
-        (src, _t, _m), (ps_, pt, pm), n, mem, segs, n_segs = self._point_pairs(src, tgt, mask, seg_offsets)
+        s, t, mask, segs, n_segs = self._point_pairs(src, tgt, mask, seg_offsets)
         keys = None if seg_keys is None else np.ascontiguousarray(seg_keys, np.uint64).reshape(-1)
         assert keys is None or len(keys) == n_segs, "one key per segment"
         prm = self._ransac_params(threshold, seed, iterations)
         res = np.zeros(max(n_segs, 1), L.RANSAC_RESULT)
-        if mem == L.MEM_DEVICE and n:
-            import torch
-            inl = torch.zeros(n, dtype=torch.uint8, device=src.device)
-            self._order_after_torch()
-            pi = inl.data_ptr()
-        else:
-            inl = np.zeros(max(n, 1), np.uint8)
-            pi = inl.ctypes.data
-        L.check(self._lib.o3dr_ransac_rigid(self._h, ps_, pt, n, None if segs is None else segs.ctypes.data, n_segs, pm,
-                                            None if keys is None else keys.ctypes.data, C.byref(prm), pi, res.ctypes.data, mem))
-        return inl[:n] != 0, res[:n_segs]
+        inl, = self._empty_like(s.x, _rows(s.n, np.uint8), zeros=True)
+        L.check(self._lib.o3dr_ransac_rigid(self._h, s.addr, t.addr, s.n, _addr(segs), n_segs, _addr(mask), _addr(keys), C.byref(prm),
+                                            _addr(inl), res.ctypes.data, s.mem))
+        return inl[:s.n] != 0, res[:n_segs]
 
     def matchFeatures(self, desc_q, desc_t, kp3_q, kp3_t, ratio=0.5, max_distance=40, ransac_threshold=None, ransac_iterations=256,
                       ransac_seed=0):
@@ -1248,10 +1194,8 @@ class Context:
         train's.  With ransac_threshold (metres) the kept matches first go through ransacRigid (key 0) and the fit runs on
         its inliers: the kept mask is then the inlier mask.  All numpy, or all torch CUDA tensors (the gather then stays on
         the device).  -> (records, kept mask (bool, one per query row), RigidResult)."""
-        dq, nq = self._desc(desc_q)
-        dt, nt = self._desc(desc_t)
-        kq, nkq = self._cloud(kp3_q)
-        kt, nkt = self._cloud(kp3_t)
+        (dq, nq, _, _), (dt, nt, _, _) = self._desc(desc_q), self._desc(desc_t)
+        (kq, nkq, _, _), (kt, nkt, _, _) = self._cloud(kp3_q), self._cloud(kp3_t)
         assert nkq == nq and nkt == nt, "the 3-D keypoints must be index-aligned with the descriptors"
         pairs = np.array([[0, 1]], np.int32)
         offsets = np.array([0, nq, nq + nt], np.int64)
@@ -1295,7 +1239,7 @@ class Context:
         refine=True: refinePoses runs on the outputs and the pair list (the history frames fixed; ratio, max_distance and
         the ransac_* keywords passed through; refine_kw: its other keywords); the poses returned are the refined ones, the
         records stay the chain's, and the RefineResult is appended to the tuple."""
-        desc, kp3, pd, pk, mem, off, F = self._feature_pool(desc, kp3, offsets)
+        d, k3, off, F = self._feature_pool(desc, kp3, offsets)
         host = lambda a, dt: np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else a, dt)  # noqa: E731
         prior = host(prior_poses, np.float32).reshape(-1, 16)
         assert F >= 0 and len(prior) == F, "one prior pose per frame"
@@ -1314,12 +1258,11 @@ class Context:
         rprm = self._ransac_params(ransac_threshold, ransac_seed, ransac_iterations) if robust else None
         rres = np.zeros(cap, L.RANSAC_RESULT) if robust and return_ransac else None
         n_pairs = C.c_int64(0)
-        poses, pp = self._pose_out(desc, mem, F)
-        args = (self._h, pd, off.ctypes.data, pk, prior.ctypes.data, F, n_fixed,
-                pin.ctypes.data if len(pin) else None, sin.ctypes.data if len(sin) else None, C.byref(prm), pp, rec.ctypes.data,
-                None if prs is None else prs.ctypes.data, cap, C.byref(n_pairs), mem)
+        poses, = self._empty_like(d.x, _rows(F, np.float32, 16), zeros=True)
+        args = (self._h, d.addr, off.ctypes.data, k3.addr, prior.ctypes.data, F, n_fixed, _addr(pin, len(pin)), _addr(sin, len(sin)),
+                C.byref(prm), _addr(poses), rec.ctypes.data, _addr(prs), cap, C.byref(n_pairs), d.mem)
         if robust:
-            L.check(self._lib.o3dr_pose_chain_robust(*args, C.byref(rprm), None if rres is None else rres.ctypes.data))
+            L.check(self._lib.o3dr_pose_chain_robust(*args, C.byref(rprm), _addr(rres)))
         else:
             L.check(self._lib.o3dr_pose_chain(*args))
         res = (poses[:F].reshape(F, 4, 4), rec[:F])
@@ -1331,17 +1274,12 @@ class Context:
             kw.setdefault("fixed", fx)
             if kw.get("prior_weight", 0.0) > 0.0:
                 kw.setdefault("prior_poses", prior)
-            refined, _frames, rr = self.refinePoses(desc, off, kp3, res[0], rec["status"][:F], prs[: n_pairs.value], ratio=ratio,
+            refined, _frames, rr = self.refinePoses(d.x, off, k3.x, res[0], rec["status"][:F], prs[: n_pairs.value], ratio=ratio,
                                                     max_distance=max_distance, ransac_threshold=ransac_threshold,
                                                     ransac_iterations=ransac_iterations, ransac_seed=ransac_seed, **kw)
             res = (refined, rec[:F])
-        if return_pairs:
-            res += (prs[: n_pairs.value],)
-        if return_ransac:
-            res += (rres[: n_pairs.value] if rres is not None else np.zeros(0, L.RANSAC_RESULT),)
-        if refine:
-            res += (rr,)
-        return res
+        return _returned(res, (return_pairs, _head(prs, n_pairs.value)),
+                         (return_ransac, rres[: n_pairs.value] if rres is not None else np.zeros(0, L.RANSAC_RESULT)), (refine, rr))
 
     # -- pose-graph refinement (the bundle adjustment the reference leaves commented out: pose_functions.cpp:1876-1921) -----
     def refinePoses(self, desc, offsets, kp3, poses, status, pairs, fixed=None, prior_poses=None, prior_weight=0.0, gn_iterations=5,
@@ -1353,7 +1291,7 @@ class Context:
         to hold) and prior_poses ([F, 4, 4], needed iff prior_weight > 0) are read on the host.  The ransac_* keywords are
         poseChain's.  -> (poses [F, 4, 4] float32: numpy, or a CUDA tensor for CUDA desc / kp3; records: a numpy
         REFINE_FRAME array, one per frame; RefineResult), with return_edges a numpy REFINE_EDGE array, one per pair."""
-        desc, kp3, pd, pk, mem, off, F = self._feature_pool(desc, kp3, offsets)
+        d, k3, off, F = self._feature_pool(desc, kp3, offsets)
         host = lambda a, dt: np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else a, dt)  # noqa: E731
         pin = host(poses, np.float32).reshape(-1, 16)
         sin = host(status, np.int32).reshape(-1)
@@ -1370,19 +1308,11 @@ class Context:
         rec = np.zeros(max(F, 1), L.REFINE_FRAME)
         edg = np.zeros(max(P, 1), L.REFINE_EDGE) if return_edges else None
         res = L.RefineResultStruct()
-        out, pp = self._pose_out(desc, mem, F)
+        out, = self._empty_like(d.x, _rows(F, np.float32, 16), zeros=True)
         L.check(self._lib.o3dr_pose_graph_refine(
-            self._h, pd, off.ctypes.data, pk, F, pin.ctypes.data if F else None,
-            sin.ctypes.data if F else None, None if fx is None or not F else fx.ctypes.data,
-            None if pri is None or not F else pri.ctypes.data, prs.ctypes.data if P else None, P, C.byref(prm),
-            None if rprm is None else C.byref(rprm), pp, rec.ctypes.data, None if edg is None else edg.ctypes.data, C.byref(res), mem))
-        rr = RefineResult(float(res.energy_before), float(res.energy_after), float(res.grad_before), float(res.grad_after),
-                          float(res.last_step), int(res.n_free), int(res.n_gauge), int(res.n_floating), int(res.n_rejected),
-                          int(res.n_edges), int(res.n_used), int(res.flags))
-        ret = (out[:F].reshape(F, 4, 4), rec[:F], rr)
-        if return_edges:
-            ret += (edg[:P],)
-        return ret
+            self._h, d.addr, off.ctypes.data, k3.addr, F, _addr(pin, F), _addr(sin, F), _addr(fx, F), _addr(pri, F), _addr(prs, P), P,
+            C.byref(prm), None if rprm is None else C.byref(rprm), _addr(out), rec.ctypes.data, _addr(edg), C.byref(res), d.mem))
+        return _returned((out[:F].reshape(F, 4, 4), rec[:F], _result(RefineResult, res)), (return_edges, _head(edg, P)))
 
     def trackFrames(self, img, disp, prior_poses, n_features=1500, scale_factor=1.3, n_levels=5, fast_threshold=20, edge=31,
                     **chain_kwargs):
@@ -1404,30 +1334,20 @@ class Context:
         tensors).  -> int32 [T, 3] triangles (input indices, counter-clockwise in XY, in quad order); with return_normals
         also [N, 3] float32 vertex normals (NaN for shadowed points and vertices without a triangle); with return_info
         also a MeshResult.  One library call: the triangle buffer holds the bound of 2 n triangles."""
-        pts, n = self._cloud(pts)
-        p_in, mem, _k = _ptr(pts)
+        pts, n, p_in, mem = self._cloud(pts)
         prm = L.MeshParamsStruct(float(cell_size), float(max_edge_length))
         res = L.MeshResultStruct()
         n_tris = C.c_int64(0)
         cap = 2 * n
-        rows = max(n, 1) if mem == L.MEM_DEVICE else n  # (a tensor is never empty)
-        tri, nrm = self._empty_like(pts, ((max(cap, 1), 3), np.int32), ((rows, 3), np.float32) if return_normals else None)
-        L.check(self._lib.o3dr_mesh_surface(self._h, p_in, n, C.byref(prm), _addr(tri), cap, C.byref(n_tris), _addr(nrm), C.byref(res), mem))
-        ret = (tri[:int(n_tris.value)],)
-        if return_normals:
-            ret += (nrm[:n],)
-        if return_info:
-            ret += (MeshResult(int(res.n_vertices), int(res.n_shadowed), int(res.n_triangles), int(res.n_quads_full),
-                               int(res.n_rejected_orientation), int(res.n_rejected_length)),)
-        return ret[0] if len(ret) == 1 else ret
+        tri, nrm = self._empty_like(pts, _rows(cap, np.int32, 3), _rows(n, np.float32, 3) if return_normals else None)
+        L.check(self._lib.o3dr_mesh_surface(self._h, p_in, n, C.byref(prm), _addr(tri), cap, C.byref(n_tris), _addr(nrm), C.byref(res),
+                                            mem))
+        return _returned((tri[:int(n_tris.value)],), (return_normals, _head(nrm, n)), (return_info, _result(MeshResult, res)))
 
     # -- map raster: orthophoto, elevation raster, shaded relief (this build's own; SURVEY section 2 row 15) ---------------
     def rasterExtent(self, pts, cell_size):
         """The cloud's own cell box (cx0, cy0, width, height) at cell_size: what rasterizeMap(bounds=None) covers."""
-        pts, n = self._cloud(pts)
-        p_in, mem, _k = _ptr(pts)
-        if mem == L.MEM_DEVICE:
-            self._order_after_torch()
+        pts, n, p_in, mem = self._cloud(pts)
         box = [C.c_int32(0) for _ in range(4)]
         L.check(self._lib.o3dr_raster_extent(self._h, p_in, n, float(cell_size), *[C.byref(b) for b in box], mem))
         return tuple(int(b.value) for b in box)
@@ -1440,8 +1360,7 @@ class Context:
         fills empty cells from the nearest occupied one, light = (lx, ly, lz) adds the shaded relief.  numpy POINT arrays
         give numpy arrays, torch [N,4] 4-byte CUDA tensors such as finalize(device=...) give CUDA tensors.
         -> (height_map float32, color uint8 [.., 3] B G R[, shade uint8][, source int32][, distance2 int32][, RasterInfo])"""
-        pts, n = self._cloud(pts)
-        p_in, mem, _k = _ptr(pts)
+        pts, n, p_in, mem = self._cloud(pts)
         if select not in L.RASTER_SELECT:
             raise L.O3drError(L.ERR_INVALID_ARG, "select must be 'first', 'top' or 'bottom'")
         cx0, cy0, W, H = (int(v) for v in (self.rasterExtent(pts, cell_size) if bounds is None else bounds))
@@ -1463,13 +1382,8 @@ class Context:
         for (name, _, _), t in zip(want, arrays):
             setattr(outs, name, _addr(t))
         res = L.RasterResultStruct()
-        L.check(self._lib.o3dr_rasterize_map(self._h, p_in if n else None, n, C.byref(prm), C.byref(outs), C.byref(res), mem))
-        ret = tuple(arrays)
-        if return_info:
-            ret += (RasterInfo(int(res.cx0), int(res.cy0), int(res.width), int(res.height), int(res.n_inside), int(res.n_outside),
-                               int(res.n_occupied), int(res.n_shadowed), int(res.n_filled), int(res.n_empty), float(res.z_min),
-                               float(res.z_max)),)
-        return ret
+        L.check(self._lib.o3dr_rasterize_map(self._h, p_in, n, C.byref(prm), C.byref(outs), C.byref(res), mem))
+        return _returned(arrays, (return_info, _result(RasterInfo, res)))
 
     # -- ground filter: ground mask, DTM, height above ground (this build's own) -----------------
     def groundFilter(self, pts, cell_size, bounds=None, max_window_radius=16, window_base=2, exponential=True, slope=0.7,
@@ -1488,8 +1402,7 @@ class Context:
         [height, width]][, GroundInfo[, InterpolateInfo with interpolate]]"""
         if interpolate and int(fill_radius) != 0:
             raise ValueError("groundFilter(interpolate=True) needs fill_radius = 0: the interpolation is the fill")
-        pts, n = self._cloud(pts)
-        p_in, mem, _k = _ptr(pts)
+        pts, n, p_in, mem = self._cloud(pts)
         cx0, cy0, W, H = (int(v) for v in (self.rasterExtent(pts, cell_size) if bounds is None else bounds))
         prm = _ground_params(cell_size, max_window_radius, window_base, exponential, slope, initial_distance, max_distance)
         prm.cx0, prm.cy0, prm.width, prm.height, prm.fill_radius = cx0, cy0, W, H, int(fill_radius)
@@ -1504,23 +1417,17 @@ class Context:
         outs = L.GroundOutputsStruct()
         arrays = self._empty_like(pts, *[(shp, dt) for _, dt, shp in want])
         for (name, _, shp), t in zip(want, arrays):
-            setattr(outs, name, _addr(t) if 0 not in shp else None)
+            setattr(outs, name, _addr(t, int(np.prod(shp))))
         res = L.GroundResultStruct()
-        L.check(self._lib.o3dr_ground_filter(self._h, p_in if n else None, n, C.byref(prm), C.byref(outs), C.byref(res), mem))
-        info = (GroundInfo(int(res.cx0), int(res.cy0), int(res.width), int(res.height), int(res.n_inside), int(res.n_outside),
-                           int(res.n_occupied), int(res.n_ground_cells), int(res.n_ground_points), int(res.n_dtm_filled),
-                           int(res.n_dtm_empty), int(res.n_iterations), tuple(int(v) for v in res.n_removed[:res.n_iterations])),)
+        L.check(self._lib.o3dr_ground_filter(self._h, p_in, n, C.byref(prm), C.byref(outs), C.byref(res), mem))
+        info, dem_info = _result(GroundInfo, res, n_removed=tuple(res.n_removed[:res.n_iterations])), None
         if interpolate:  # the DTM from the ground cells alone, at any distance; the heights above it
             got = dict(zip((name for name, _, _ in want), arrays))
             dtm, dem_info = self.interpolateRaster(got["dtm"], smooth=smooth, return_info=True)
             above = self.sampleRaster(pts, dtm, cell_size, (cx0, cy0, W, H)) if return_height else None
             arrays = [got["ground"]] + ([above] if return_height else []) + ([dtm] if return_dtm else [])
             arrays += [got["cell_state"]] if return_state else []
-            info += (dem_info,)
-        ret = tuple(arrays)
-        if return_info:
-            ret += info
-        return ret[0] if len(ret) == 1 else ret
+        return _returned(arrays, (return_info, info), (return_info and interpolate, dem_info))
 
     # -- raster interpolation and raster sample (this build's own) -------------------------------
     def interpolateRaster(self, raster, smooth=2, max_level=0, return_level=False, return_info=False):
@@ -1529,28 +1436,16 @@ class Context:
         "raster interpolation", DESIGN.md "Raster interpolation").  max_level (1..31) leaves the holes whose nearest data
         lies under a higher pyramid level NaN; 0: no limit.  A numpy array gives numpy arrays, a torch CUDA tensor gives
         CUDA tensors without leaving HBM.  -> filled float32[, level uint8][, InterpolateInfo]"""
-        if _is_torch(raster):
-            assert _dtype_name(raster) == "float32" and raster.dim() == 2
-            raster = raster.contiguous()
-        else:
-            raster = np.ascontiguousarray(raster, np.float32)
-            assert raster.ndim == 2
-        H, W = (int(v) for v in raster.shape)
-        p_in, mem, _k = _ptr(raster)
+        raster, H, W, p_in, mem = self._raster(raster)
         prm = L.InterpolateParamsStruct()
         self._lib.o3dr_interpolate_default_params(C.byref(prm))
         prm.width, prm.height, prm.smooth, prm.max_level = W, H, int(smooth), int(max_level)
         filled, level = self._empty_like(raster, ((H, W), np.float32), ((H, W), np.uint8) if return_level else None)
-        outs = L.InterpolateOutputsStruct(_addr(filled) if W * H else None, _addr(level) if W * H else None)
+        outs = L.InterpolateOutputsStruct(_addr(filled, W * H), _addr(level, W * H))
         res = L.InterpolateResultStruct()
-        L.check(self._lib.o3dr_raster_interpolate(self._h, p_in if W * H else None, C.byref(prm), C.byref(outs), C.byref(res), mem))
-        ret = (filled,)
-        if return_level:
-            ret += (level,)
-        if return_info:
-            ret += (InterpolateInfo(int(res.width), int(res.height), int(res.n_levels), int(res.n_data), int(res.n_filled),
-                                    int(res.n_empty), tuple(int(v) for v in res.n_by_level[:res.n_levels])),)
-        return ret[0] if len(ret) == 1 else ret
+        L.check(self._lib.o3dr_raster_interpolate(self._h, p_in, C.byref(prm), C.byref(outs), C.byref(res), mem))
+        info = _result(InterpolateInfo, res, n_by_level=tuple(res.n_by_level[:res.n_levels]))
+        return _returned((filled,), (return_level, level), (return_info, info))
 
     def sampleRaster(self, pts, raster, cell_size, bounds, return_value=False, return_info=False):
         """A float32 [height, width] raster read back at every point: bounds = (cx0, cy0, width, height) is the raster's box
@@ -1558,25 +1453,17 @@ class Context:
         memory: numpy POINT array and numpy raster, or torch CUDA tensors.
         -> height_above float32 [n] (z minus the raster at the point's cell; NaN outside the box or on a NaN cell)[, value
         float32 [n]][, (points inside the box, outside it, inside it on a NaN cell)]"""
-        pts, n = self._cloud(pts)
-        p_in, mem, _k = _ptr(pts)
+        pts, n, p_in, mem = self._cloud(pts)
         cx0, cy0, W, H = (int(v) for v in bounds)
-        if _is_torch(pts):
-            assert _is_torch(raster) and _dtype_name(raster) == "float32" and raster.is_cuda == pts.is_cuda
-            raster = raster.contiguous()
-        else:
-            raster = np.ascontiguousarray(raster, np.float32)
-        assert tuple(raster.shape) == (H, W), "the raster's shape is (height, width) of bounds"
+        raster, rH, rW, _, rmem = self._raster(raster)
+        assert (rH, rW) == (H, W), "the raster's shape is (height, width) of bounds"
+        assert rmem == mem, "the points and the raster live in the same memory"
         above, value = self._empty_like(pts, (n, np.float32), (n, np.float32) if return_value else None)
         counts = (C.c_int64 * 3)()
-        L.check(self._lib.o3dr_raster_sample(self._h, p_in if n else None, n, float(cell_size), cx0, cy0, W, H, _addr(raster),
-                                             _addr(value) if n else None, _addr(above) if n else None, counts, mem))
-        ret = (above,)
-        if return_value:
-            ret += (value,)
-        if return_info:
-            ret += (tuple(int(v) for v in counts),)
-        return ret[0] if len(ret) == 1 else ret
+        # (the raster's address goes as it is: the library wants one even for a raster of no cells)
+        L.check(self._lib.o3dr_raster_sample(self._h, p_in, n, float(cell_size), cx0, cy0, W, H, _addr(raster), _addr(value, n),
+                                             _addr(above, n), counts, mem))
+        return _returned((above,), (return_value, value), (return_info, tuple(int(v) for v in counts)))
 
     # -- contour lines of a raster (this build's own; SURVEY section 2 row 16) ---------------------------------------------
     def contourRaster(self, raster, interval, base=0.0, cell_size=1.0, origin=(0, 0), return_lines=False, return_vertices=False,
@@ -1589,42 +1476,23 @@ class Context:
         leaving HBM (the same bytes: `.cpu().numpy().view(CONTOUR_SEGMENT)`).
         -> segments CONTOUR_SEGMENT [S] (torch: uint8 [S, 48])[, lines CONTOUR_LINE [n] (uint8 [n, 32])][, vertices float64
         [S + n, 2]: contourPolylines(lines, vertices) splits them][, ContourInfo]"""
-        if _is_torch(raster):
-            assert _dtype_name(raster) == "float32" and raster.dim() == 2
-            raster = raster.contiguous()
-        else:
-            raster = np.ascontiguousarray(raster, np.float32)
-            assert raster.ndim == 2
-        H, W = (int(v) for v in raster.shape)
-        p_in, mem, _k = _ptr(raster)
+        raster, H, W, p_in, mem = self._raster(raster)  # (the count call reads the raster before any output is made)
         prm = L.ContourParamsStruct()
         self._lib.o3dr_contour_default_params(C.byref(prm))
         prm.width, prm.height, prm.interval, prm.base, prm.cell_size = W, H, float(interval), float(base), float(cell_size)
         prm.cx0, prm.cy0 = int(origin[0]), int(origin[1])
         count = C.c_int64(0)
-        if mem == L.MEM_DEVICE:  # (the count call reads the raster before any output is made)
-            self._order_after_torch()
-        L.check(self._lib.o3dr_raster_contours_count(self._h, p_in if W * H else None, C.byref(prm), C.byref(count), mem))
+        L.check(self._lib.o3dr_raster_contours_count(self._h, p_in, C.byref(prm), C.byref(count), mem))
         S = int(count.value)  # n_lines <= S and n_vertices <= 2 S
         if S > L.CONTOUR_MAX_SEGMENTS:
             raise L.O3drError(L.ERR_CAPACITY, "the raster has more than 2^28 contour segments at this interval")
-        dev = mem == L.MEM_DEVICE
-        seg, lin, ver = self._empty_like(raster, ((S, 48), np.uint8) if dev else (S, L.CONTOUR_SEGMENT),
-                                         (((S, 32), np.uint8) if dev else (S, L.CONTOUR_LINE)) if return_lines else None,
-                                         ((2 * S, 2), np.float64) if return_vertices else None)
-        addr = lambda t: _addr(t) if t is not None and S else None  # noqa: E731
-        outs = L.ContourOutputsStruct(addr(seg), S, addr(lin), S, addr(ver), 2 * S)
+        seg, lin, ver = self._empty_like(raster, _rows(S, L.CONTOUR_SEGMENT), _rows(S, L.CONTOUR_LINE) if return_lines else None,
+                                         _rows(2 * S, np.float64, 2) if return_vertices else None)
+        outs = L.ContourOutputsStruct(_addr(seg, S), S, _addr(lin, S), S, _addr(ver, S), 2 * S)
         res = L.ContourResultStruct()
-        L.check(self._lib.o3dr_raster_contours(self._h, p_in if W * H else None, C.byref(prm), C.byref(outs), C.byref(res), mem))
-        ret = (seg[:int(res.n_segments)],)
-        if return_lines:
-            ret += (lin[:int(res.n_lines)],)
-        if return_vertices:
-            ret += (ver[:int(res.n_vertices)],)
-        if return_info:
-            ret += (ContourInfo(int(res.n_quads), int(res.n_quads_crossed), int(res.n_segments), int(res.n_lines), int(res.n_closed),
-                                int(res.n_vertices), int(res.n_longest), int(res.k_lo), int(res.k_hi)),)
-        return ret[0] if len(ret) == 1 else ret
+        L.check(self._lib.o3dr_raster_contours(self._h, p_in, C.byref(prm), C.byref(outs), C.byref(res), mem))
+        return _returned((seg[:int(res.n_segments)],), (return_lines, _head(lin, int(res.n_lines))),
+                         (return_vertices, _head(ver, int(res.n_vertices))), (return_info, _result(ContourInfo, res)))
 
     # -- Euclidean clustering: object labels and per-object records (this build's own; SURVEY section 2 row 16) ----------
     def clusterCloud(self, pts, tolerance, min_size=1, max_size=None, return_clusters=False, return_raw=False, return_sizes=False,
@@ -1636,8 +1504,7 @@ class Context:
         [K, 64] tensor: `.cpu().numpy().view(CLUSTER)`).
         -> label int32 [n] (-1: rejected)[, clusters CLUSTER [K]][, raw int32 [n]][, sizes int32 [n]][, indices int32
         [n_clustered_points]][, ClusterInfo]"""
-        pts, n = self._cloud(pts)
-        p_in, mem, _k = _ptr(pts)
+        pts, n, p_in, mem = self._cloud(pts)
         prm = L.ClusterParamsStruct()
         self._lib.o3dr_cluster_default_params(C.byref(prm))
         prm.tolerance, prm.min_size = float(tolerance), int(min_size)
@@ -1646,41 +1513,27 @@ class Context:
         cap = n // int(min_size) if return_clusters and int(min_size) >= 1 else 0  # no more clusters fit in n points
         want = ["label"] + [name for name, on in (("raw", return_raw), ("size", return_sizes), ("indices", return_indices)) if on]
         outs = L.ClusterOutputsStruct()
-        rec, *made = self._empty_like(pts, ((cap, 64), np.uint8) if mem == L.MEM_DEVICE else (cap, L.CLUSTER), *[(n, np.int32)] * len(want))
+        rec, *made = self._empty_like(pts, _rows(cap, L.CLUSTER), *[(n, np.int32)] * len(want))
         arrays = dict(zip(want, made))
         for name in want:
-            setattr(outs, name, _addr(arrays[name]) if n else None)
+            setattr(outs, name, _addr(arrays[name], n))
         res, k = L.ClusterResultStruct(), C.c_int64(0)
-        L.check(self._lib.o3dr_cluster_euclidean(self._h, p_in if n else None, n, C.byref(prm), C.byref(outs), _addr(rec) if cap else None,
-                                                 cap, C.byref(k), C.byref(res), mem))
-        ret = (arrays["label"],)
-        if return_clusters:
-            ret += (rec[:int(k.value)],)
-        if return_raw:
-            ret += (arrays["raw"],)
-        if return_sizes:
-            ret += (arrays["size"],)
-        if return_indices:
-            ret += (arrays["indices"][:int(res.n_clustered_points)],)
-        if return_info:
-            ret += (ClusterInfo(int(res.n_components), int(res.n_clusters), int(res.n_too_small), int(res.n_too_large),
-                                int(res.n_clustered_points), int(res.n_rejected_points), int(res.largest), int(res.n_pairs)),)
-        return ret[0] if len(ret) == 1 else ret
+        L.check(self._lib.o3dr_cluster_euclidean(self._h, p_in, n, C.byref(prm), C.byref(outs), _addr(rec, cap), cap, C.byref(k),
+                                                 C.byref(res), mem))
+        return _returned((arrays["label"],), (return_clusters, rec[:min(int(k.value), cap)]), (return_raw, arrays.get("raw")),
+                         (return_sizes, arrays.get("size")), (return_indices, _head(arrays.get("indices"), int(res.n_clustered_points))),
+                         (return_info, _result(ClusterInfo, res)))
 
     def voxelGrid(self, pts, leaf, min_points=0, z_offset=0.0, return_status=False):
         """pcl::VoxelGrid<PointXYZRGB> as the reference configures it (pose_functions.cpp:1689-1700)."""
-        if not _is_torch(pts):
-            pts = np.ascontiguousarray(pts, POINT)
+        pts, n_in, p_in, mem = self._cloud(pts)
         leaf = np.ascontiguousarray(leaf, np.float32).reshape(3)
-        pi, mem, _k = _ptr(pts)
-        n_in = int(pts.shape[0])
-        out = self._alloc_out(n_in, pts)
-        po, _, _k2 = _ptr(out)
+        out, = self._empty_like(pts, _rows(n_in, POINT))
         n = C.c_int64(0)
         st = C.c_uint32(0)
-        L.check(self._lib.o3dr_voxel_grid(self._h, pi, n_in, leaf.ctypes.data, int(min_points), float(z_offset), po,
-                                         max(n_in, 1), C.byref(n), C.byref(st), mem))
-        return (out[: n.value], st.value) if return_status else out[: n.value]
+        L.check(self._lib.o3dr_voxel_grid(self._h, p_in, n_in, leaf.ctypes.data, int(min_points), float(z_offset), _addr(out),
+                                         len(out), C.byref(n), C.byref(st), mem))
+        return _returned((out[: n.value],), (return_status, st.value))
 
     def createAndTransformPtCloud(self, disp, bgr, T, kp_xy=None, return_status=False):
         """pose.h:231 / pose.cpp:596-636."""
